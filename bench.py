@@ -68,7 +68,31 @@ def parse():
                          'BASELINE config 4 as stated: contact map -> top-k -> RecCut -> per-domain fingerprints at D = 2560)')
     ap.add_argument('--extra-steps', type=int, default=10, help='timed steps of each of those workloads (warm-up 2)')
     ap.add_argument('--pipeline-proteins', type=int, default=2048, help='proteins per flush of the c4_pipeline workload')
-    return ap.parse_args()
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the headline workload\'s last step returned to DIR/*.npy (float32; '
+                         'a fixed, seeded sample of its rows when the whole exceeds 64 MB) to compare two builds output for output')
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
+    return args
+
+
+DUMP_LIMIT_BYTES = 64_000_000
+
+
+def dump_outputs(directory, np, fingerprints, rank: int = 0, world: int = 1):
+    """`fingerprints` (the int8 rows a caller of the timed path receives) -> DIR/fingerprints.npy as float32 (exact), every rank
+    its own file at N > 1.  Over the size limit (shared by the ranks), a sample of rows drawn with a fixed seed, sorted,
+    and their indices in DIR/fingerprint_rows.npy (float64, exact)."""
+    os.makedirs(directory, exist_ok=True)
+    suffix = f'.rank{rank}' if world > 1 else ''
+    n_rows, width = fingerprints.shape
+    budget = DUMP_LIMIT_BYTES // world - 4096           # (two .npy headers)
+    if n_rows * width * 4 > budget:
+        rows = np.sort(np.random.default_rng(0).choice(n_rows, size=budget // (width * 4 + 8), replace=False))
+        fingerprints = fingerprints[rows]
+        np.save(os.path.join(directory, f'fingerprint_rows{suffix}.npy'), rows.astype(np.float64))
+    np.save(os.path.join(directory, f'fingerprints{suffix}.npy'), fingerprints.astype(np.float32))
 
 
 def make_layer(torch, gen, n_rows, D, device):
@@ -318,6 +342,8 @@ def measure(args, wl, steps, warmup, env):
     fastest_kernel_ms = -ddist.max_over_ranks(-own_kernel_ms, device if nccl else None)
     fp_all_ranks = ddist.sum_over_ranks(n_fp, device if nccl else None)   # ragged workloads differ per rank
     last_path = ctx.get_option('last_path')
+    if args.dump_outputs and wl == args.workload:   # the last timed step's result, before anything below runs `step` again
+        dump_outputs(args.dump_outputs, np, out.cpu().numpy(), rank, world)
 
     # ---- N > 1: what makes a bad curve readable from the line alone.  Per rank: where it ran, what it streamed, its own step
     # and kernel time -- and clock / package power sampled while the same step loops for two more seconds (the timed region

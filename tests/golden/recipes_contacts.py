@@ -30,3 +30,29 @@ def make_contacts(recipe: str, L: int, seed: int, nb: int = 3) -> np.ndarray:
         raise KeyError(recipe)
     p = 0.5 * (p + p.T)
     return np.ascontiguousarray(p, dtype=np.float32)
+
+
+def fuzz_graphs(seed: int = 20240, n: int = 120):
+    """Random block / interleaved contact graphs (blocks merged at random: discontinuous domains), as the selection of
+    writece would pass them on: yields (L, i, j, v) with at most int(2.6 L) contacts, strongest first."""
+    rng = np.random.default_rng(seed)
+    for _ in range(n):
+        L = int(rng.integers(22, 360))
+        nb = int(rng.integers(1, 8))
+        bounds = np.sort(rng.choice(np.arange(1, L), size=min(nb - 1, L - 1), replace=False)) if nb > 1 else []
+        lab = np.zeros(L, int)
+        for b in bounds:
+            lab[b:] += 1
+        for _m in range(int(rng.integers(0, 3))):
+            if nb >= 3:
+                a, b = sorted(rng.choice(nb, 2, replace=False))
+                lab[lab == b] = a
+        same = lab[:, None] == lab[None, :]
+        p = rng.random((L, L)) * (same * rng.uniform(0.5, 1.0) + (~same) * rng.uniform(0.0, 0.3))
+        mask = np.triu(rng.random((L, L)) < rng.uniform(0.02, 0.3), 5)
+        ii, jj = np.nonzero(mask)
+        t = int(2.6 * L)
+        if len(ii) > t:
+            order = np.argsort(-p[ii, jj], kind='stable')[:t]
+            ii, jj = ii[order], jj[order]
+        yield L, ii, jj, p[ii, jj].astype(np.float32)

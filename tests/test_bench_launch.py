@@ -109,3 +109,44 @@ def test_pipeline_workload_in_the_line():
     assert w['value'] > 0 and w['us_per_protein'] > 0 and w['gpu_ms']['domain_cutter'] > 0
     assert w['parity']['checked'] >= 6 and w['parity']['mismatching_fingerprints'] == 0 and w['parity']['mismatching_domain_lists'] == 0
     assert line['parity']['mismatching_fingerprints'] == 0
+
+
+def test_dump_outputs_is_exact_and_capped(tmp_path):
+    """--dump-outputs: int8 rows -> float32 unchanged while they fit; over the 64 MB limit a sorted, seeded sample of rows
+    (the same from run to run) and its indices, everything written within the limit."""
+    import numpy as np
+    import bench
+    rng = np.random.default_rng(5)
+    small = rng.integers(-128, 128, size=(100, 480)).astype(np.int8)
+    bench.dump_outputs(str(tmp_path / 'small'), np, small)
+    got = np.load(tmp_path / 'small' / 'fingerprints.npy')
+    assert got.dtype == np.float32 and np.array_equal(got, small) and sorted(os.listdir(tmp_path / 'small')) == ['fingerprints.npy']
+    big = rng.integers(-128, 128, size=(bench.DUMP_LIMIT_BYTES // (480 * 4) + 1000, 480)).astype(np.int8)
+    for name in ('a', 'b'):
+        bench.dump_outputs(str(tmp_path / name), np, big)
+    assert sum(os.path.getsize(tmp_path / 'a' / f) for f in os.listdir(tmp_path / 'a')) <= bench.DUMP_LIMIT_BYTES
+    rows = np.load(tmp_path / 'a' / 'fingerprint_rows.npy')
+    assert rows.dtype == np.float64 and np.all(np.diff(rows) > 0) and len(rows) > 0.9 * len(big)
+    got = np.load(tmp_path / 'a' / 'fingerprints.npy')
+    assert np.array_equal(got, big[rows.astype(np.int64)])
+    for f in ('fingerprints.npy', 'fingerprint_rows.npy'):
+        assert np.array_equal(np.load(tmp_path / 'a' / f), np.load(tmp_path / 'b' / f))
+
+
+@pytest.mark.gpu
+def test_dump_outputs_of_the_timed_steps(tmp_path):
+    """Two runs with the same arguments: --steps timed steps in the line, and the fingerprints of the last one dumped, the same
+    in both runs and equal to the oracle's on the parity sample."""
+    import numpy as np
+    lines = []
+    for name in ('a', 'b'):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--n-seq', '600', '--steps', '4', '--warmup', '1',
+                            '--cpu-seconds', '0', '--parity-sample', '8', '--workloads', 'none', '--dump-outputs', str(tmp_path / name)],
+                           env=_env(), capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines.append(json.loads(r.stdout.strip().splitlines()[-1]))
+    for line in lines:
+        assert line['steps'] == 4 and line['ms_per_step'] > 0 and line['parity']['mismatching_fingerprints'] == 0
+    a, b = (np.load(tmp_path / n / 'fingerprints.npy') for n in ('a', 'b'))
+    assert a.dtype == np.float32 and a.shape == (600, 480) and np.array_equal(a, b)
+    assert np.array_equal(a, np.round(a)) and a.min() >= -128 and a.max() <= 127 and np.any(a != 0)

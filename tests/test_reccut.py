@@ -13,7 +13,7 @@ import pytest
 import golden_util as gu
 from oracle import contacts_oracle as co
 from recipes import make_input, sha256_of
-from recipes_contacts import make_contacts
+from recipes_contacts import fuzz_graphs, make_contacts
 
 with open(os.path.join(gu.GOLD, 'reccut_golden.json')) as fh:
     CASES = json.load(fh)['cases']
@@ -56,36 +56,20 @@ def test_libreccut_matches_reference_binary_golden(case):
     assert co.parse_reccut(case['reccut_stdout'], case['L']) == case['domains']
 
 
-@pytest.mark.skipif(not os.path.exists(co.REF_BIN), reason='oracle/_ref/RecCut not built')
 def test_libreccut_fuzz_against_reference_binary():
-    """Random block / interleaved graphs straight into both implementations."""
+    """Random block / interleaved graphs straight into libreccut, against what the reference binary printed for the same
+    .ce text (tests/golden/make_golden_reccut_fuzz.py)."""
     from dctdomain_amd import reccut
-    rng = np.random.default_rng(20240)
+    with open(os.path.join(gu.GOLD, 'reccut_fuzz_golden.json')) as fh:
+        golden = json.load(fh)['cases']
+    graphs = list(fuzz_graphs())
+    assert len(graphs) == len(golden)
     n_multi = n_disc = 0
-    for _ in range(120):
-        L = int(rng.integers(22, 360))
-        nb = int(rng.integers(1, 8))
-        bounds = np.sort(rng.choice(np.arange(1, L), size=min(nb - 1, L - 1), replace=False)) if nb > 1 else []
-        lab = np.zeros(L, int)
-        for b in bounds:
-            lab[b:] += 1
-        for _m in range(int(rng.integers(0, 3))):
-            if nb >= 3:
-                a, b = sorted(rng.choice(nb, 2, replace=False))
-                lab[lab == b] = a
-        same = lab[:, None] == lab[None, :]
-        p = rng.random((L, L)) * (same * rng.uniform(0.5, 1.0) + (~same) * rng.uniform(0.0, 0.3))
-        mask = np.triu(rng.random((L, L)) < rng.uniform(0.02, 0.3), 5)
-        ii, jj = np.nonzero(mask)
-        t = int(2.6 * L)
-        if len(ii) > t:
-            order = np.argsort(-p[ii, jj], kind='stable')[:t]
-            ii, jj = ii[order], jj[order]
-        pv = p[ii, jj].astype(np.float32)
+    for (L, ii, jj, pv), case in zip(graphs, golden):
         text = co.ce_text('x', 'A' * L, ii, jj, pv)
-        rc, out = co.run_ref_binary(text)
-        assert rc == 0
-        exp = out.strip().split()[2].split(';')[:-1]
+        assert L == case['L'] and hashlib.sha256(text.encode()).hexdigest() == case['ce_sha256']
+        assert case['reccut_rc'] == 0
+        exp = case['domains']
         got = reccut.domains_from_contacts([L], [0, len(ii)], ii, jj, pv)[0]
         assert got == exp, (L, exp, got)
         n_multi += len(exp) > 1

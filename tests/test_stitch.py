@@ -138,6 +138,11 @@ def test_gpu_batch_one_launch_and_sequential_form():
             assert torch.equal(o, e), (width, [w.shape[0] for w in ws])
 
 
+# what the reference's RecCut binary (oracle/_ref/RecCut) prints for the .ce text of the CPU chain below
+LONG_CE_SHA256 = '8bafb0b8da7c31eeeba952b1bdda44472a9dbe2be5995786fdbab60f6f0f573e'
+LONG_RECCUT_STDOUT = 'long 8 1-172;173-311;312-455;456-563;564-642;643-759;760-912;913-1035;\n'
+
+
 @pytest.mark.gpu
 def test_gpu_chunked_pipeline_end_to_end():
     """BASELINE config 3 flavour: long sequence -> windows -> stitch -> reccut -> quantize, all on the
@@ -164,15 +169,12 @@ def test_gpu_chunked_pipeline_end_to_end():
         cts.append(res['contacts'][0])
     ed, ct = so.stitch(embs, cts, maxlen)
     ci, cj, cv = co.top_contacts(ct.numpy(), 2.6)
+    text = co.ce_text('long', seq, ci, cj, cv)
+    assert hashlib.sha256(text.encode()).hexdigest() == LONG_CE_SHA256
     if os.path.exists(co.REF_BIN):
-        rc, out = co.run_ref_binary(co.ce_text('long', seq, ci, cj, cv), 'long')
-        assert rc == 0
-        doms = co.parse_reccut(out, L)
-        q = orc.quantize([ed[15].numpy(), ed[21].numpy()], doms, [3, 80, 3, 80])
-        assert fp.domains == list(q.keys())
-        for k in q:
-            np.testing.assert_array_equal(fp.quants[k], q[k])
-    else:
-        q = orc.quantize([ed[15].numpy(), ed[21].numpy()], fp.domains, [3, 80, 3, 80])
-        for k in q:
-            np.testing.assert_array_equal(fp.quants[k], q[k])
+        assert co.run_ref_binary(text, 'long') == (0, LONG_RECCUT_STDOUT)
+    doms = co.parse_reccut(LONG_RECCUT_STDOUT, L)
+    q = orc.quantize([ed[15].numpy(), ed[21].numpy()], doms, [3, 80, 3, 80])
+    assert fp.domains == list(q.keys())
+    for k in q:
+        np.testing.assert_array_equal(fp.quants[k], q[k])
