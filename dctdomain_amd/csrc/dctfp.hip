@@ -2647,6 +2647,52 @@ int dctfp_row_order(dctfp_ctx* ctx, int32_t* val, int32_t* idx, int64_t n_rows, 
     return DCTFP_OK;
 } DCTFP_GUARD("dctfp_row_order")
 
+int dctfp_pair_min(dctfp_ctx* ctx, const int32_t* pairs, int64_t n_pairs, const int8_t* a, int64_t lda, const int64_t* idx_a, int64_t npa,
+                   const int8_t* b, int64_t ldb, const int64_t* idx_b, int64_t npb, int32_t d, int32_t* out_min, int32_t* out_last,
+                   void* stream_v) try {
+    if (!ctx || !pairs || !a || !idx_a || !b || !idx_b || !out_min || !out_last) return fail(DCTFP_ERR_INVALID, "dctfp_pair_min: NULL argument");
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    if (n_pairs < 0 || npa < 0 || npb < 0 || d < 1 || lda < d || ldb < d) return fail(DCTFP_ERR_INVALID, "dctfp_pair_min: bad shape");
+    if (npa > 0x7fffffff || npb > 0x7fffffff) return fail(DCTFP_ERR_LIMIT, "dctfp_pair_min: more than 2^31 - 1 proteins on a side");
+    if ((n_pairs + 3) / 4 > 0x7fffffff) return fail(DCTFP_ERR_LIMIT, "dctfp_pair_min: too many pairs per call");
+    if (n_pairs == 0) return DCTFP_OK;
+    HIP_TRY(hipSetDevice(ctx->device));
+    launch_pair_min(pairs, n_pairs, a, lda, idx_a, npa, b, ldb, idx_b, npb, d, out_min, out_last, (hipStream_t)stream_v);
+    HIP_TRY(hipGetLastError());
+    return DCTFP_OK;
+} DCTFP_GUARD("dctfp_pair_min")
+
+int dctfp_select_count(dctfp_ctx* ctx, const int32_t* dist, int64_t n_rows, int64_t n_cols, int64_t ld, const uint8_t* row_empty,
+                       const uint8_t* col_empty, int32_t cap, int32_t bound, int32_t top, int32_t* out_count, int32_t* out_cut,
+                       void* stream_v) try {
+    if (!ctx || !dist || !out_count || !out_cut) return fail(DCTFP_ERR_INVALID, "dctfp_select_count: NULL argument");
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    if (n_rows < 0 || n_cols < 1 || ld < n_cols || top < 1 || cap < 0 || bound < -1 || bound > cap)
+        return fail(DCTFP_ERR_INVALID, "dctfp_select_count: bad shape or bound");
+    if (cap > select_max_cap()) return fail(DCTFP_ERR_LIMIT, "dctfp_select_count: cap above %d", select_max_cap());
+    if (n_rows > 0x7fffffff || n_cols > 0x7fffffff) return fail(DCTFP_ERR_LIMIT, "dctfp_select_count: more than 2^31 - 1 rows or columns");
+    if (n_rows == 0) return DCTFP_OK;
+    HIP_TRY(hipSetDevice(ctx->device));
+    launch_select_count(dist, n_rows, n_cols, ld, row_empty, col_empty, cap, bound, top, out_count, out_cut, (hipStream_t)stream_v);
+    HIP_TRY(hipGetLastError());
+    return DCTFP_OK;
+} DCTFP_GUARD("dctfp_select_count")
+
+int dctfp_select_fill(dctfp_ctx* ctx, const int32_t* dist, int64_t n_rows, int64_t n_cols, int64_t ld, const uint8_t* row_empty,
+                      const uint8_t* col_empty, int32_t cap, const int32_t* cut, const int64_t* offsets, int32_t max_count, int32_t* out_key,
+                      int32_t* out_col, void* stream_v) try {
+    if (!ctx || !dist || !cut || !offsets || !out_key || !out_col) return fail(DCTFP_ERR_INVALID, "dctfp_select_fill: NULL argument");
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    if (n_rows < 0 || n_cols < 1 || ld < n_cols || cap < 0 || max_count < 0) return fail(DCTFP_ERR_INVALID, "dctfp_select_fill: bad shape");
+    if (cap > select_max_cap()) return fail(DCTFP_ERR_LIMIT, "dctfp_select_fill: cap above %d", select_max_cap());
+    if (n_rows > 0x7fffffff || n_cols > 0x7fffffff) return fail(DCTFP_ERR_LIMIT, "dctfp_select_fill: more than 2^31 - 1 rows or columns");
+    if (n_rows == 0) return DCTFP_OK;
+    HIP_TRY(hipSetDevice(ctx->device));
+    launch_select_fill(dist, n_rows, n_cols, ld, row_empty, col_empty, cap, cut, offsets, max_count, out_key, out_col, (hipStream_t)stream_v);
+    HIP_TRY(hipGetLastError());
+    return DCTFP_OK;
+} DCTFP_GUARD("dctfp_select_fill")
+
 int dctfp_host_device_pointer(void* host, void** dev) try {
     if (!host || !dev) return fail(DCTFP_ERR_INVALID, "dctfp_host_device_pointer: NULL argument");
     *dev = nullptr;

@@ -141,5 +141,14 @@ int launch_gen(const GParams& p, int dtype, int vec, int n, LaunchError* err);
 constexpr int kCutClasses = 4;
 int reccut_class_of(int n_res, int64_t n_contacts);
 int launch_reccut(int cls, const dctfp::CutJob* jobs, unsigned n, double cut1, double cut2, hipStream_t stream, LaunchError* err);
+// protein-level search (k_search.hip): pair minima from the fingerprints, threshold-aware selection on a last-row distance tile
+void launch_pair_min(const int32_t* pairs, int64_t n_pairs, const int8_t* a, int64_t lda, const int64_t* idx_a, int64_t npa, const int8_t* b,
+                     int64_t ldb, const int64_t* idx_b, int64_t npb, int d, int32_t* out_min, int32_t* out_last, hipStream_t stream);
+int select_max_cap();   // the largest key the selection's LDS histogram holds
+void launch_select_count(const int32_t* dist, int64_t n_rows, int64_t n_cols, int64_t ld, const uint8_t* row_empty, const uint8_t* col_empty,
+                         int32_t cap, int32_t bound, int32_t top, int32_t* out_count, int32_t* out_cut, hipStream_t stream);
+void launch_select_fill(const int32_t* dist, int64_t n_rows, int64_t n_cols, int64_t ld, const uint8_t* row_empty, const uint8_t* col_empty,
+                        int32_t cap, const int32_t* cut, const int64_t* offsets, int32_t max_count, int32_t* out_key, int32_t* out_col,
+                        hipStream_t stream);
 
 }  // namespace dctfp_host

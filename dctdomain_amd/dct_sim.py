@@ -8,11 +8,16 @@ Same flags, same output text (src/dct-sim.py:179-211).  DCTdomain = max over all
 ``1 - min(L1/17000, 1)``, DCTglobal = the same for the two last (whole-protein) fingerprints
 (:12-50).
 
-Where the reference loops over protein pairs and, inside, over domain pairs in Python, this module
-makes ONE pass on the GPU per run: the int8 L1 matrix of all fingerprints against all fingerprints
-(``dctfp_l1_matrix``) reduced per protein x protein block to (minimum, last-last) (``dctfp_block_min``).
-The three modes only differ in which blocks they print.  Scores are formed from the integer L1
-values with the reference's arithmetic (int64 / 17000 in float64), so the printed floats are identical."""
+Where the reference loops over protein pairs and, inside, over domain pairs in Python:
+- ``all_sim`` makes ONE pass on the GPU: the int8 L1 matrix of all fingerprints against all fingerprints
+  (``dctfp_l1_matrix``) reduced per protein x protein block to (minimum, last-last) (``dctfp_block_min``) -- it prints
+  every pair anyway (``Blocks``);
+- ``db_search`` ranks on the whole-protein fingerprints only (one L1 per protein pair), selects the printed hits of
+  every query on the GPU (``dctfp_select_count`` / ``dctfp_select_fill``) and computes DCTdomain for those pairs only
+  (``dctfp_pair_min``): ``ProteinSearch``.  Host memory is what is printed plus one tile, not n_query x n_db;
+- ``pair_sim`` uploads the fingerprints of the proteins its pairs name and runs ``dctfp_pair_min`` on the pairs.
+Scores are formed from the integer L1 values with the reference's arithmetic (int64 / 17000 in float64), so the printed
+floats are identical."""
 
 from __future__ import annotations
 
@@ -22,7 +27,7 @@ import time
 
 import numpy as np
 
-from .similarity import block_min, l1_matrix, to_device_int8
+from .similarity import block_min, l1_matrix, pair_min, threshold_select, to_device_int8
 
 L1_FULL_SCALE = 17000      # src/dct-sim.py:24
 HEADER = '#prot1 prot2 sim-domain sim-global'
@@ -116,6 +121,180 @@ class Blocks:
         return _scores(self.mn[i, j], self.last[i, j])
 
 
+def _load_npz(filename: str) -> tuple:
+    """(sid, idx, dct) of a ``-dct.npz``, with load_dct's progress line (src/dct-sim.py:52-84) -- without the per-protein
+    list, which at a million proteins costs as much as the load."""
+    t0 = time.time()
+    with np.load(filename) as data:
+        seqid, bounds, rows = data['sid'], np.asarray(data['idx'], dtype=np.int64), data['dct']
+    print(f"dct loaded for {len(seqid)} sequences, time used: {time.time() - t0:.1f}s")
+    return seqid, bounds, rows
+
+
+def sim_bound(threshold: float) -> int:
+    """The largest L1 in 0 .. 17000 whose similarity, with ``_sim``'s arithmetic, is not below ``threshold`` -- the
+    reference keeps a hit past the first ``top`` unless ``sim < threshold`` (src/dct-sim.py:151) -- found by evaluating
+    that expression on every L1, not by algebra.  -1 = none (threshold > 1); 17000 = every L1 (threshold <= 0, NaN).
+    Similarity does not increase with L1, so the L1 values that pass are exactly 0 .. sim_bound."""
+    ok = ~(_sim(np.arange(L1_FULL_SCALE + 1)) < threshold)
+    return int(np.count_nonzero(ok)) - 1
+
+
+def _last_rows(fps, idx):
+    """(last fingerprint of every protein, a zero row where it has none; uint8 flag of the proteins without one)."""
+    idx = np.asarray(idx, dtype=np.int64)
+    empty = idx[1:] == idx[:-1]
+    last = np.zeros((len(idx) - 1, fps.shape[1]), dtype=np.int8)
+    last[~empty] = fps[idx[1:][~empty] - 1]
+    return last, empty.astype(np.uint8)
+
+
+def merge_candidates(parts, top: int, bound: int):
+    """One query's hits from the hits of each database group: ``parts`` = [(keys, global columns)] of the groups, each the
+    group's first max(top, #(key <= bound)) entries in (key, column) order.  Exact: the global entries with key <= bound are
+    the union of the groups' ones, and the global first ``top`` lie within the union of the groups' first ``top``.
+    Returns (keys, columns) of the first max(top, #(key <= bound)) entries of the union in (key, column) order."""
+    if len(parts) == 1:
+        return parts[0]
+    keys = np.concatenate([k for k, _ in parts])
+    cols = np.concatenate([c for _, c in parts])
+    order = np.lexsort((cols, keys))
+    m = min(len(order), max(top, int(np.count_nonzero(keys <= bound))))
+    return keys[order[:m]], cols[order[:m]]
+
+
+def _pair_chunks(idx, pairs, max_rows: int):
+    """[start, end) ranges of ``pairs`` whose proteins (deduplicated) have at most ``max_rows`` fingerprints between them --
+    at least one pair per range."""
+    sizes = np.diff(np.asarray(idx, dtype=np.int64))
+    start, seen, rows = 0, set(), 0
+    for k, (i, j) in enumerate(pairs):
+        new = [p for p in {int(i), int(j)} if p not in seen]
+        more = int(sum(sizes[p] for p in new))
+        if k > start and rows + more > max_rows:
+            yield start, k
+            start, seen, rows = k, set(), 0
+            new = list({int(i), int(j)})
+            more = int(sum(sizes[p] for p in new))
+        seen.update(new)
+        rows += more
+    if start < len(pairs):
+        yield start, len(pairs)
+
+
+def _compact(fps, idx, proteins):
+    """(fingerprint rows of ``proteins``, their prefix array): the part of an npz a pair list needs on the device."""
+    idx = np.asarray(idx, dtype=np.int64)
+    lens = idx[proteins + 1] - idx[proteins]
+    sub_idx = np.zeros(len(proteins) + 1, dtype=np.int64)
+    np.cumsum(lens, out=sub_idx[1:])
+    rows = np.repeat(idx[proteins] - sub_idx[:-1], lens) + np.arange(sub_idx[-1])
+    return fps[rows], sub_idx
+
+
+def pair_scores(fps, idx, pairs, max_rows: int = None):
+    """(min, last) L1 of every (protein i, protein j) of ``pairs`` within one npz (``dctfp_pair_min``): only the fingerprints of
+    the proteins the pairs name go to the device, at most ``max_rows`` (``ProteinSearch.COL_ROWS``) of them at a time."""
+    pairs = np.asarray(pairs, dtype=np.int64).reshape(-1, 2)
+    mn = np.full(len(pairs), 0x7fffffff, dtype=np.int64)
+    last = mn.copy()
+    for k0, k1 in _pair_chunks(idx, pairs, max_rows or ProteinSearch.COL_ROWS):
+        proteins, local = np.unique(pairs[k0:k1], return_inverse=True)
+        rows, sub_idx = _compact(fps, idx, proteins)
+        if len(rows):
+            dev = to_device_int8(rows)
+            mn[k0:k1], last[k0:k1] = pair_min(dev, sub_idx, dev, sub_idx, local.reshape(-1, 2))
+    return mn, last
+
+
+class ProteinSearch:
+    """A fingerprint database (the ``dct`` / ``idx`` arrays of a ``-dct.npz``) searched protein by protein the way db_search
+    does (src/dct-sim.py:126-156), without the n_query x n_db block matrix:
+
+    1. rank on the whole-protein fingerprints only: an int32 tile of L1 distances, query last rows x database last rows;
+    2. select each query's printed hits on the GPU (``threshold_select``): key min(L1, 17000) ascending, ties to the lower
+       database index, the first max(top, #(DCTglobal >= threshold));
+    3. DCTdomain (``pair_min``) for the printed pairs only.
+
+    The database goes to the device in protein groups of at most COL_ROWS fingerprints (a single group stays there between
+    searches); the query side is tiled so that a distance tile holds at most TILE_INTS entries.  The groups' hit lists are
+    merged per query (``merge_candidates``).  ``search`` returns, per query, (database protein indices, min L1, last L1)."""
+
+    COL_ROWS = 1 << 22      # fingerprints of the database on the device at a time (2 GB of int8 at 480 columns)
+    TILE_INTS = 1 << 28     # int32 entries of one distance tile (1 GiB)
+    MAX_TILE_ROWS = 1 << 20  # (dctfp_l1_matrix takes at most 8M rows per call)
+
+    def __init__(self, db_fps, db_idx):
+        self.fps = db_fps
+        self.idx = np.asarray(db_idx, dtype=np.int64)
+        self.groups = list(_protein_groups(self.idx, self.COL_ROWS))
+        self._resident = {}
+
+    def _group(self, g: int, need_rows: bool):
+        """(device fingerprints or None, prefix array, device last rows, empty flags) of database group g."""
+        hit = self._resident.get(g)
+        if hit is not None and (hit[0] is not None or not need_rows):
+            return hit
+        p0, p1 = self.groups[g]
+        r0, r1 = self.idx[p0], self.idx[p1]
+        sub_idx = self.idx[p0:p1 + 1] - r0
+        last, empty = _last_rows(self.fps[r0:r1], sub_idx)
+        rows = to_device_int8(self.fps[r0:r1]) if need_rows and r1 > r0 else None
+        entry = (rows, sub_idx, to_device_int8(last), empty)
+        if len(self.groups) == 1:
+            self._resident[g] = entry
+        return entry
+
+    def search(self, query_fps, query_idx, top: int, threshold: float):
+        top = int(top)
+        qidx = np.asarray(query_idx, dtype=np.int64)
+        nq, n_db = len(qidx) - 1, len(self.idx) - 1
+        if nq == 0 or n_db == 0:
+            return [(np.zeros(0, dtype=np.int64),) * 3 for _ in range(nq)]
+        bound = sim_bound(threshold)
+        top1 = max(top, 1)      # (top <= 0: the reference prints the threshold hits only -- trimmed after the merge)
+        q_last, q_empty = _last_rows(query_fps, qidx)
+        parts = [[] for _ in range(nq)]
+        for g, (p0, p1) in enumerate(self.groups):
+            _, _, last, empty = self._group(g, need_rows=False)
+            rows = int(min(self.MAX_TILE_ROWS, max(1, self.TILE_INTS // (p1 - p0))))
+            for t0 in range(0, nq, rows):
+                t1 = min(nq, t0 + rows)
+                off, key, col = threshold_select(l1_matrix(q_last[t0:t1], last), top1, bound, q_empty[t0:t1], empty)
+                for r in range(t1 - t0):
+                    s = slice(off[r], off[r + 1])
+                    parts[t0 + r].append((key[s], col[s] + p0))
+        merged = (merge_candidates(pq, top1, bound) for pq in parts)
+        hits = [c if top >= 1 else c[k <= bound] for k, c in merged]
+        del parts
+        counts = np.array([len(h) for h in hits], dtype=np.int64)
+        q_of = np.repeat(np.arange(nq, dtype=np.int64), counts)
+        db_of = np.concatenate(hits).astype(np.int64) if nq else np.zeros(0, dtype=np.int64)
+        mn, last_l1 = self._pair_scores(query_fps, qidx, q_of, db_of)
+        bounds = np.concatenate([[0], np.cumsum(counts)])
+        return [(db_of[a:b], mn[a:b], last_l1[a:b]) for a, b in zip(bounds[:-1], bounds[1:])]
+
+    def _pair_scores(self, query_fps, qidx, q_of, db_of):
+        """(min, last) L1 of the pairs (query q_of[k], database protein db_of[k]): per database group, per chunk of queries."""
+        mn = np.full(len(q_of), 0x7fffffff, dtype=np.int64)
+        last = mn.copy()
+        for g, (p0, p1) in enumerate(self.groups):
+            in_g = np.flatnonzero((db_of >= p0) & (db_of < p1))
+            if len(in_g) == 0:
+                continue
+            rows, sub_idx, _, _ = self._group(g, need_rows=True)
+            if rows is None:
+                continue
+            for c0, c1 in _protein_groups(qidx, self.COL_ROWS):
+                sel = in_g[(q_of[in_g] >= c0) & (q_of[in_g] < c1)]
+                if len(sel) == 0 or qidx[c1] == qidx[c0]:
+                    continue
+                qrows = to_device_int8(query_fps[qidx[c0]:qidx[c1]])
+                pairs = np.stack([q_of[sel] - c0, db_of[sel] - p0], axis=1)
+                mn[sel], last[sel] = pair_min(qrows, qidx[c0:c1 + 1] - qidx[c0], rows, sub_idx, pairs)
+        return mn, last
+
+
 class Report:
     """Result lines to a file (header first) or to stdout."""
 
@@ -155,10 +334,10 @@ def _reporting(fn):
 def pair_sim(npzfile: str, pairfile: str, pairfound: str, report: Report):
     """Similarity of every listed protein pair (src/dct-sim.py:86-124).  Lines starting with ``#``
     are comments (copied to ``pairfound``); pairs with an unknown protein are counted, not printed."""
-    blk = Blocks(npzfile)
-    where = {name: i for i, name in enumerate(blk.rows)}      # a repeated id: the later one, like a dict of arrays
-    listed = found = 0
-    kept = []
+    sid, idx, fps = _load_npz(npzfile)
+    where = {name: i for i, name in enumerate(sid)}           # a repeated id: the later one, like a dict of arrays
+    listed = 0
+    kept, found = [], []
     with open(pairfile, encoding='utf8') as pairs:
         for text in pairs:
             if text.startswith('#'):
@@ -168,11 +347,13 @@ def pair_sim(npzfile: str, pairfile: str, pairfound: str, report: Report):
             listed += 1
             if first not in where or second not in where:
                 continue
-            maxs, s = blk.scores(where[first], where[second])
-            report.line(f'{first} {second} {maxs} {s}')
+            found.append((first, second, where[first], where[second]))
             kept.append(text)
-            found += 1
-    print(f'total pair {pairfile} found {found} (not found: {listed - found})')
+    mn, last = pair_scores(fps, idx, [(i, j) for _, _, i, j in found])
+    for (first, second, _, _), m, l in zip(found, mn, last):
+        maxs, s = _scores(m, l)
+        report.line(f'{first} {second} {maxs} {s}')
+    print(f'total pair {pairfile} found {len(found)} (not found: {listed - len(found)})')
     if pairfound:
         with open(pairfound, 'w', encoding='utf8') as out:
             out.writelines(kept)
@@ -183,15 +364,13 @@ def pair_sim(npzfile: str, pairfile: str, pairfound: str, report: Report):
 def db_search(npzfile: str, dbfile: str, top: int, threshold: float, report: Report):
     """Hits of every query protein in a fingerprint database, best DCTglobal first (stable); the first
     ``top`` always, further ones while they reach ``threshold`` (src/dct-sim.py:126-156)."""
-    blk = Blocks(npzfile, dbfile)
-    glob = _sim(blk.last)                                     # (n_query, n_db) float64
-    for i, query in enumerate(blk.rows):
-        order = np.argsort(-glob[i], kind='stable')
-        for rank, q in enumerate(order):
-            if rank >= top and glob[i, q] < threshold:
-                break
-            maxs, s = blk.scores(i, q)
-            report.line(f'{query} {blk.cols[q]} {maxs} {s}')
+    sid, idx, fps = _load_npz(npzfile)
+    db_sid, db_idx, db_fps = _load_npz(dbfile)
+    hits = ProteinSearch(db_fps, db_idx).search(fps, idx, top, threshold)
+    for query, (cols, mn, last) in zip(sid, hits):
+        for q, m, l in zip(cols, mn, last):
+            maxs, s = _scores(m, l)
+            report.line(f'{query} {db_sid[q]} {maxs} {s}')
 
 
 @_reporting

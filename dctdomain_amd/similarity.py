@@ -108,3 +108,80 @@ def _pair_to_host(val: torch.Tensor, idx: torch.Tensor, dtype=np.int64):
     torch.cuda.current_stream(val.device).synchronize()
     host = pin[:2 * n].numpy().astype(dtype)                    # (the copy out of the staging buffer, and the widening, in one)
     return host[:n].reshape(val.shape), host[n:].reshape(idx.shape)
+
+
+def _device_int64(a, device) -> torch.Tensor:
+    return torch.as_tensor(np.ascontiguousarray(np.asarray(a, dtype=np.int64)), device=device)
+
+
+def pair_min(a, idx_a, b, idx_b, pairs):
+    """(min, last) int64 numpy arrays, one entry per row (protein of ``a``, protein of ``b``) of ``pairs``: the smallest L1 over
+    all fingerprint pairs of the two proteins and the L1 of their last rows (``dctfp_pair_min``; no distance matrix).
+    ``idx_a`` / ``idx_b``: the npz prefix arrays of the two fingerprint matrices.  A protein without fingerprints gives
+    0x7fffffff in both, as ``block_min``."""
+    pairs = np.ascontiguousarray(np.asarray(pairs, dtype=np.int64).reshape(-1, 2))
+    ia, ib = np.asarray(idx_a, dtype=np.int64), np.asarray(idx_b, dtype=np.int64)
+    npa, npb = len(ia) - 1, len(ib) - 1
+    ta, tb = to_device_int8(a), to_device_int8(b)
+    if ta.dim() != 2 or tb.dim() != 2 or ta.shape[1] != tb.shape[1]:
+        raise ValueError('fingerprint sets must be 2-D with equal width')
+    for idx, rows in ((ia, ta.shape[0]), (ib, tb.shape[0])):    # (the kernel trusts the prefix arrays: check them here)
+        if len(idx) < 1 or idx[0] < 0 or idx[-1] > rows or (np.diff(idx) < 0).any():
+            raise ValueError('idx must be a non-decreasing prefix array within its fingerprint matrix')
+    if len(pairs) and (pairs[:, 0].min() < 0 or pairs[:, 0].max() >= npa or pairs[:, 1].min() < 0 or pairs[:, 1].max() >= npb):
+        raise IndexError('protein index out of range')
+    n = len(pairs)
+    if n == 0 or ta.shape[0] == 0 or tb.shape[0] == 0:          # (no fingerprint on a side: every pair is empty)
+        full = np.full(n, 0x7fffffff, dtype=np.int64)
+        return full, full.copy()
+    dev = ta.device
+    mn = torch.empty(n, dtype=torch.int32, device=dev)
+    last = torch.empty(n, dtype=torch.int32, device=dev)
+    tp = torch.as_tensor(pairs.astype(np.int32), device=dev)
+    da, db = _device_int64(ia, dev), _device_int64(ib, dev)
+    ctx = _lib.get_context(dev.index)
+    stream = torch.cuda.current_stream(dev)
+    _lib.check(ctx._lib.dctfp_pair_min(ctx.handle, tp.data_ptr(), n, ta.data_ptr(), ta.stride(0) if ta.shape[0] > 1 else ta.shape[1],
+                                       da.data_ptr(), npa, tb.data_ptr(), tb.stride(0) if tb.shape[0] > 1 else tb.shape[1], db.data_ptr(),
+                                       npb, ta.shape[1], mn.data_ptr(), last.data_ptr(), C.c_void_p(stream.cuda_stream)))
+    return _pair_to_host(mn, last)
+
+
+def threshold_select(dist: torch.Tensor, top: int, bound: int, row_empty=None, col_empty=None, cap: int = 17000):
+    """The hits of every row of a last-row distance tile in db_search's order (src/dct-sim.py:146-156): key = min(L1, cap)
+    (``cap`` for a row / column flagged empty), ascending, ties to the lower column; the first max(top, #(key <= bound))
+    of them.  Counted and selected on the GPU (``dctfp_select_count`` / ``dctfp_select_fill``), rows of up to 1024 hits
+    ordered there too.  Returns numpy (offsets int64 (n_rows + 1), keys, columns): row r's hits are [offsets[r], offsets[r+1])."""
+    n_rows, n_cols = dist.shape
+    if n_rows == 0:
+        return np.zeros(1, dtype=np.int64), np.zeros(0, dtype=np.int64), np.zeros(0, dtype=np.int64)
+    dev = dist.device
+    ld = dist.stride(0) if n_rows > 1 else n_cols
+    flags = []
+    for f, n in ((row_empty, n_rows), (col_empty, n_cols)):
+        if f is not None:
+            f = torch.as_tensor(np.asarray(f, dtype=np.uint8) if not isinstance(f, torch.Tensor) else f, device=dev).to(torch.uint8).contiguous()
+            if f.numel() != n:
+                raise ValueError('empty flags must have one entry per row / column')
+        flags.append(f)
+    ptr = [f.data_ptr() if f is not None else None for f in flags]
+    bound = int(max(-1, min(int(bound), cap)))
+    ctx = _lib.get_context(dev.index)
+    stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    count = torch.empty(n_rows, dtype=torch.int32, device=dev)
+    cut = torch.empty((n_rows, 2), dtype=torch.int32, device=dev)
+    _lib.check(ctx._lib.dctfp_select_count(ctx.handle, dist.data_ptr(), n_rows, n_cols, ld, ptr[0], ptr[1], cap, bound, max(1, int(top)),
+                                           count.data_ptr(), cut.data_ptr(), stream))
+    m = count.cpu().numpy().astype(np.int64)
+    offsets = np.zeros(n_rows + 1, dtype=np.int64)
+    np.cumsum(m, out=offsets[1:])
+    key = torch.empty(int(offsets[-1]), dtype=torch.int32, device=dev)
+    col = torch.empty(int(offsets[-1]), dtype=torch.int32, device=dev)
+    _lib.check(ctx._lib.dctfp_select_fill(ctx.handle, dist.data_ptr(), n_rows, n_cols, ld, ptr[0], ptr[1], cap, cut.data_ptr(),
+                                          _device_int64(offsets, dev).data_ptr(), int(m.max()), key.data_ptr(), col.data_ptr(), stream))
+    k, c = _pair_to_host(key, col)
+    for r in np.flatnonzero(m > 1024):                             # (rows the device left in column order)
+        s = slice(offsets[r], offsets[r + 1])
+        o = np.argsort(k[s], kind='stable')
+        k[s], c[s] = k[s][o], c[s][o]
+    return offsets, k, c

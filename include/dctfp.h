@@ -299,6 +299,36 @@ int dctfp_row_select(dctfp_ctx* ctx, const int32_t* dist, int64_t n_rows, int64_
  * order those on the host). */
 int dctfp_row_order(dctfp_ctx* ctx, int32_t* val, int32_t* idx, int64_t n_rows, int32_t k, void* stream);
 
+/* domain_sim (src/dct-sim.py:28-50) for a list of protein pairs, straight from the fingerprints -- no distance matrix: pair p
+ * = (pairs[2p], pairs[2p+1]) = (protein of a, protein of b), the proteins' rows given by the npz "idx" prefix arrays idx_a
+ * (npa + 1 entries) and idx_b (npb + 1) as in dctfp_block_min.  out_min[p] = the smallest L1 over all fingerprint pairs of the
+ * two proteins (-> DCTdomain), out_last[p] = the L1 of their last (whole-protein) rows (-> DCTglobal).  Replaces the pair loop
+ * of pair_sim (:104-111) and the per-hit domain_sim of db_search (:143-145).  All device pointers; the prefix arrays must be
+ * non-decreasing and within their matrices (the caller's guarantee, as for dctfp_block_min).  A protein without fingerprints
+ * gives 0x7fffffff in both outputs (dctfp_block_min's fill); a pair index outside [0, npa) x [0, npb) gives -1 in both.
+ * DCTFP_ERR_LIMIT above 2^31 - 1 proteins on a side. */
+int dctfp_pair_min(dctfp_ctx* ctx, const int32_t* pairs, int64_t n_pairs, const int8_t* a, int64_t lda, const int64_t* idx_a, int64_t npa,
+                   const int8_t* b, int64_t ldb, const int64_t* idx_b, int64_t npb, int32_t d, int32_t* out_min, int32_t* out_last,
+                   void* stream);
+
+/* The hits db_search prints (src/dct-sim.py:146-156), selected on the device from an int32 tile of L1 distances between the
+ * queries' and the database proteins' last fingerprints (dctfp_l1_matrix).  Key of an entry: min(L1, cap) (cap = 17000: the
+ * reference's sorted(..., reverse=True) on 1 - min(L1 / 17000, 1) is "key ascending, ties by column"); row_empty[r] /
+ * col_empty[c] (device uint8, either may be NULL) != 0 marks a protein without fingerprints, key cap against everything.
+ * `bound` = the largest key whose similarity still reaches the threshold (-1: none, cap: all).  A row's hits are its first
+ * m = min(n_cols, max(top, #(key <= bound))) entries in that order.
+ * dctfp_select_count: out_count[r] = m (device int32 n_rows), out_cut[2r, 2r+1] (device int32 2 n_rows) = what the fill needs.
+ * dctfp_select_fill: offsets (device int64, n_rows + 1) = the exclusive prefix sum of out_count, computed by the caller; the
+ * hits of row r go to out_key / out_col [offsets[r], offsets[r+1]) (device int32), ordered by (key, column) when
+ * m <= min(max_count, 1024) -- max_count = the largest m of the call -- and in column order when m > 1024 (the caller orders
+ * those).  cap <= 17407 (the LDS histogram of the count; DCTFP_ERR_LIMIT beyond), top >= 1, n_rows and n_cols < 2^31. */
+int dctfp_select_count(dctfp_ctx* ctx, const int32_t* dist, int64_t n_rows, int64_t n_cols, int64_t ld, const uint8_t* row_empty,
+                       const uint8_t* col_empty, int32_t cap, int32_t bound, int32_t top, int32_t* out_count, int32_t* out_cut,
+                       void* stream);
+int dctfp_select_fill(dctfp_ctx* ctx, const int32_t* dist, int64_t n_rows, int64_t n_cols, int64_t ld, const uint8_t* row_empty,
+                      const uint8_t* col_empty, int32_t cap, const int32_t* cut, const int64_t* offsets, int32_t max_count, int32_t* out_key,
+                      int32_t* out_col, void* stream);
+
 /* The address under which the GPU sees a pinned (page-locked, mapped) host buffer, e.g. a torch tensor created with
  * pin_memory=True.  A caller that passes this address as `out` of dctfp_quantize gets the int8 result written straight
  * into host memory: no device buffer, no copy -- what a one-protein-per-call user wants (480 bytes per domain). */
