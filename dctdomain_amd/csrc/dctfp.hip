@@ -2693,6 +2693,21 @@ int dctfp_select_fill(dctfp_ctx* ctx, const int32_t* dist, int64_t n_rows, int64
     return DCTFP_OK;
 } DCTFP_GUARD("dctfp_select_fill")
 
+int dctfp_sim_lines(dctfp_ctx* ctx, const int32_t* mn, const int32_t* last, int64_t ld, int64_t n_rows, int64_t row0, int64_t col0,
+                    int64_t n_cols, const uint8_t* ids, const int64_t* id_off, const char* table, const int64_t* row_base, uint8_t* out,
+                    void* stream_v) try {
+    if (!ctx || !mn || !last || !ids || !id_off || !table || !row_base || !out) return fail(DCTFP_ERR_INVALID, "dctfp_sim_lines: NULL argument");
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    if (n_rows < 0 || n_cols < 0 || ld < n_cols || row0 < 0 || col0 < 0) return fail(DCTFP_ERR_INVALID, "dctfp_sim_lines: bad shape");
+    // (one 256-thread workgroup per 256 columns; gridDim.x * blockDim.x must stay below 2^32)
+    if ((n_cols + 255) / 256 > (int64_t)(0xffffffffu / 256)) return fail(DCTFP_ERR_LIMIT, "dctfp_sim_lines: more than 2^32 - 256 columns per call");
+    if (n_rows == 0 || n_cols == 0) return DCTFP_OK;
+    HIP_TRY(hipSetDevice(ctx->device));
+    launch_sim_lines(mn, last, ld, n_rows, row0, col0, n_cols, ids, id_off, table, row_base, out, (hipStream_t)stream_v);
+    HIP_TRY(hipGetLastError());
+    return DCTFP_OK;
+} DCTFP_GUARD("dctfp_sim_lines")
+
 int dctfp_host_device_pointer(void* host, void** dev) try {
     if (!host || !dev) return fail(DCTFP_ERR_INVALID, "dctfp_host_device_pointer: NULL argument");
     *dev = nullptr;

@@ -2,7 +2,8 @@
 //   pair_min_kernel      -- DCTdomain / DCTglobal L1 of a list of protein pairs, read straight from the fingerprints;
 //   select_count_kernel  -- per row of a last-row distance tile: how many hits the reference prints, and where the cut is;
 //   select_fill_kernel   -- the hits themselves, compacted into a ragged array at host-computed offsets;
-//   select_order_kernel  -- each row's hits in the reference's order (key ascending, ties by column), rows of <= 1024 hits.
+//   select_order_kernel  -- each row's hits in the reference's order (key ascending, ties by column), rows of <= 1024 hits;
+//   sim_lines_kernel     -- all_sim's result lines (src/dct-sim.py:158-176) as text, from a (min, last) tile.
 #define DCTFP_TEMPLATES_ONLY
 #include "launch.h"
 
@@ -253,6 +254,110 @@ __global__ __launch_bounds__(N / 2) void select_order_kernel(int32_t* __restrict
     }
 }
 
+// ---- all_sim's result lines.  Line (i, j) is "{id_i} {id_j} {a} {b}\n", len_i + len_j + 14 bytes, a / b the five characters
+// of the score table for min / last (rows 0 .. 17000 = that L1, row 17001 = every larger value).  Row i prints j = i + 1 .. n - 1
+// contiguously from row_base[r]; the line of column j starts (j - (i + 1)) (len_i + 14) + (P[j] - P[i + 1]) bytes later
+// (P = id_off), so every workgroup knows where its bytes go without a scan over lines.
+constexpr int kLineThreads = 256;    // one workgroup per (row, run of 256 columns)
+constexpr int kIdStage = 4096;       // id bytes staged in LDS (longer: read from global memory)
+constexpr int kScoreRows = 17002;
+
+// The byte at offset o of a line: id_i, ' ', id_j, then the 13-byte tail " a.aaa b.bbb\n".
+__device__ inline uint32_t line_byte(int64_t o, int64_t len_i, int64_t len_j, const uint8_t* si, const uint8_t* sj, const uint8_t* tail) {
+    if (o < len_i) return si[o];
+    if (o == len_i) return ' ';
+    o -= len_i + 1;
+    return o < len_j ? sj[o] : tail[o - len_j];
+}
+
+// One workgroup per (row r, run of up to 256 columns of the tile): the run's lines are one contiguous byte range.  Its line
+// starts and score tails go to LDS (and the ids, when short), then the threads fill the range 16 aligned bytes at a time --
+// whole words with one 16-byte store, only the first and last word of the range byte by byte (the neighbouring runs own the
+// rest of those words).  Rows loop over gridDim.y.  Writes exactly [row_base[r] + start of the run's first line, ... + run bytes).
+__global__ __launch_bounds__(kLineThreads) void sim_lines_kernel(const int32_t* __restrict__ mn, const int32_t* __restrict__ last, int64_t ld,
+                                                                 int64_t n_rows, int64_t row0, int64_t col0, int64_t n_cols,
+                                                                 const uint8_t* __restrict__ ids, const int64_t* __restrict__ id_off,
+                                                                 const char* __restrict__ table, const int64_t* __restrict__ row_base,
+                                                                 uint8_t* __restrict__ out) {
+    __shared__ int64_t start[kLineThreads + 1];          // line starts, relative to the run's first byte
+    __shared__ uint8_t tail[kLineThreads][16];
+    __shared__ uint8_t stage_i[kIdStage], stage_j[kIdStage];
+    const int tid = threadIdx.x;
+    const int64_t c_lo = (int64_t)blockIdx.x * kLineThreads;
+    for (int64_t r = blockIdx.y; r < n_rows; r += gridDim.y) {
+        const int64_t i = row0 + r, js = i + 1;
+        const int64_t j_lo = max(col0 + c_lo, js), j_hi = col0 + min(c_lo + kLineThreads, n_cols);
+        if (j_lo >= j_hi) continue;                       // (uniform: the run lies left of the diagonal)
+        const int64_t cnt = j_hi - j_lo;
+        const int64_t off_i = id_off[i], len_i = id_off[i + 1] - off_i, pj0 = id_off[j_lo], len_js = id_off[j_hi] - pj0;
+        const int64_t run0 = row_base[r] + (j_lo - js) * (len_i + 14) + (pj0 - id_off[js]);
+        if (tid < cnt) {
+            start[tid] = tid * (len_i + 14) + (id_off[j_lo + tid] - pj0);
+            const int64_t c = j_lo + tid - col0;
+            const uint32_t a = min((uint32_t)mn[r * ld + c], (uint32_t)(kScoreRows - 1));
+            const uint32_t b = min((uint32_t)last[r * ld + c], (uint32_t)(kScoreRows - 1));
+            uint8_t* t = tail[tid];
+            t[0] = ' ';
+            t[6] = ' ';
+            t[12] = '\n';
+#pragma unroll
+            for (int k = 0; k < 5; ++k) {
+                t[1 + k] = (uint8_t)table[5 * a + k];
+                t[7 + k] = (uint8_t)table[5 * (kScoreRows + b) + k];
+            }
+        }
+        if (tid == 0) start[cnt] = cnt * (len_i + 14) + len_js;
+        const bool stage_ok_i = len_i <= kIdStage, stage_ok_j = len_js <= kIdStage;
+        if (stage_ok_i)
+            for (int64_t k = tid; k < len_i; k += kLineThreads) stage_i[k] = ids[off_i + k];
+        if (stage_ok_j)
+            for (int64_t k = tid; k < len_js; k += kLineThreads) stage_j[k] = ids[pj0 + k];
+        __syncthreads();
+        const uint8_t* si = stage_ok_i ? stage_i : ids + off_i;
+        const uint8_t* sj = stage_ok_j ? stage_j : ids + pj0;
+        const int64_t total = start[cnt];
+        uint8_t* g = out + run0;
+        const int64_t head = (int64_t)(reinterpret_cast<uintptr_t>(g) & 15u);   // bytes of the first word before the range
+        const int64_t n_words = (head + total + 15) / 16;
+        for (int64_t w = tid; w < n_words; w += kLineThreads) {
+            const int64_t p0 = 16 * w - head;                   // range offset of the word's first byte (may be < 0)
+            // the line holding max(p0, 0): the last l with start[l] <= it
+            const int64_t q = max(p0, (int64_t)0);
+            int lo = 0, hi = (int)cnt - 1;
+            while (lo < hi) {
+                const int mid = (lo + hi + 1) >> 1;
+                if (start[mid] <= q) lo = mid;
+                else hi = mid - 1;
+            }
+            int l = lo;
+            int64_t ls = start[l], le = start[l + 1];
+            uint32_t word[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+            for (int k = 0; k < 16; ++k) {
+                const int64_t p = p0 + k;
+                if (p >= 0 && p < total) {
+                    while (p >= le) {
+                        ++l;
+                        ls = le;
+                        le = start[l + 1];
+                    }
+                    const int64_t len_j = le - ls - len_i - 14;
+                    const uint32_t ch = line_byte(p - ls, len_i, len_j, si, sj + (ls - l * (len_i + 14)), tail[l]);
+                    word[k >> 2] |= ch << (8 * (k & 3));
+                }
+            }
+            if (p0 >= 0 && p0 + 16 <= total) {
+                *reinterpret_cast<uint4*>(g + p0) = make_uint4(word[0], word[1], word[2], word[3]);
+            } else {
+#pragma unroll
+                for (int k = 0; k < 16; ++k)
+                    if (p0 + k >= 0 && p0 + k < total) g[p0 + k] = (uint8_t)(word[k >> 2] >> (8 * (k & 3)));
+            }
+        }
+        __syncthreads();                                    // (LDS is refilled for the next row)
+    }
+}
+
 }  // namespace
 
 namespace dctfp_host {
@@ -286,6 +391,13 @@ void launch_select_fill(const int32_t* dist, int64_t n_rows, int64_t n_cols, int
     if (max_count <= 128) hipLaunchKernelGGL((select_order_kernel<128>), dim3((unsigned)n_rows), dim3(64), 0, stream, out_key, out_col, offsets);
     else if (max_count <= 256) hipLaunchKernelGGL((select_order_kernel<256>), dim3((unsigned)n_rows), dim3(128), 0, stream, out_key, out_col, offsets);
     else hipLaunchKernelGGL((select_order_kernel<1024>), dim3((unsigned)n_rows), dim3(512), 0, stream, out_key, out_col, offsets);
+}
+
+void launch_sim_lines(const int32_t* mn, const int32_t* last, int64_t ld, int64_t n_rows, int64_t row0, int64_t col0, int64_t n_cols,
+                      const uint8_t* ids, const int64_t* id_off, const char* table, const int64_t* row_base, uint8_t* out, hipStream_t stream) {
+    const dim3 grid((unsigned)((n_cols + kLineThreads - 1) / kLineThreads), (unsigned)min(n_rows, (int64_t)65535));
+    hipLaunchKernelGGL(sim_lines_kernel, grid, dim3(kLineThreads), 0, stream, mn, last, ld, n_rows, row0, col0, n_cols, ids, id_off, table,
+                       row_base, out);
 }
 
 }  // namespace dctfp_host

@@ -150,5 +150,8 @@ void launch_select_count(const int32_t* dist, int64_t n_rows, int64_t n_cols, in
 void launch_select_fill(const int32_t* dist, int64_t n_rows, int64_t n_cols, int64_t ld, const uint8_t* row_empty, const uint8_t* col_empty,
                         int32_t cap, const int32_t* cut, const int64_t* offsets, int32_t max_count, int32_t* out_key, int32_t* out_col,
                         hipStream_t stream);
+// all_sim's result lines (k_search.hip): text from a (min, last) tile at offsets computed from the id lengths
+void launch_sim_lines(const int32_t* mn, const int32_t* last, int64_t ld, int64_t n_rows, int64_t row0, int64_t col0, int64_t n_cols,
+                      const uint8_t* ids, const int64_t* id_off, const char* table, const int64_t* row_base, uint8_t* out, hipStream_t stream);
 
 }  // namespace dctfp_host

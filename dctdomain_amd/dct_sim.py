@@ -9,9 +9,10 @@ Same flags, same output text (src/dct-sim.py:179-211).  DCTdomain = max over all
 (:12-50).
 
 Where the reference loops over protein pairs and, inside, over domain pairs in Python:
-- ``all_sim`` makes ONE pass on the GPU: the int8 L1 matrix of all fingerprints against all fingerprints
-  (``dctfp_l1_matrix``) reduced per protein x protein block to (minimum, last-last) (``dctfp_block_min``) -- it prints
-  every pair anyway (``Blocks``);
+- ``all_sim`` walks the upper triangle in stripes of proteins (``AllPairs``): the int8 L1 matrix of a stripe's fingerprints
+  against those of the later proteins (``dctfp_l1_matrix``), reduced per protein x protein block to (minimum, last-last)
+  (``dctfp_block_min``) and turned into the result text on the device (``dctfp_sim_lines``), which streams out through two
+  pinned buffers.  Host memory is the two buffers plus O(n), not the n x n block matrix (``Blocks``, kept for its callers);
 - ``db_search`` ranks on the whole-protein fingerprints only (one L1 per protein pair), selects the printed hits of
   every query on the GPU (``dctfp_select_count`` / ``dctfp_select_fill``) and computes DCTdomain for those pairs only
   (``dctfp_pair_min``): ``ProteinSearch``.  Host memory is what is printed plus one tile, not n_query x n_db;
@@ -27,7 +28,7 @@ import time
 
 import numpy as np
 
-from .similarity import block_min, l1_matrix, pair_min, threshold_select, to_device_int8
+from .similarity import LineIds, block_min, block_min_device, l1_matrix, pair_min, sim_lines, threshold_select, to_device_int8
 
 L1_FULL_SCALE = 17000      # src/dct-sim.py:24
 HEADER = '#prot1 prot2 sim-domain sim-global'
@@ -76,11 +77,10 @@ def load_dct(filename: str, asmap=True) -> tuple:
 def _protein_groups(idx, max_rows: int):
     """[p0, p1) ranges of consecutive proteins whose fingerprints (idx = prefix offsets) number at most ``max_rows``
     -- at least one protein per range, however many fingerprints it has."""
+    idx = np.asarray(idx, dtype=np.int64)
     p0, n = 0, len(idx) - 1
-    while p0 < n:
-        p1 = p0 + 1
-        while p1 < n and idx[p1 + 1] - idx[p0] <= max_rows:
-            p1 += 1
+    while p0 < n:       # (one search per range, not a step per protein: all_sim groups the later proteins once per stripe)
+        p1 = min(n, max(p0 + 1, int(np.searchsorted(idx, idx[p0] + max_rows, 'right')) - 1))
         yield p0, p1
         p0 = p1
 
@@ -119,6 +119,116 @@ class Blocks:
 
     def scores(self, i: int, j: int) -> tuple:
         return _scores(self.mn[i, j], self.last[i, j])
+
+
+SCORE_ROWS = L1_FULL_SCALE + 2    # score table rows: L1 0 .. 17000, then one row for every larger value (0x7fffffff included)
+
+
+def score_table() -> np.ndarray:
+    """uint8 (2, SCORE_ROWS, 5): the text all_sim prints for each L1 value -- ``f'{v:.3f}'`` of ``_scores``' DCTdomain (by the
+    block minimum) and DCTglobal (by the last-last value), evaluated for every L1 rather than derived: Python's correctly
+    rounded ``.3f`` of the float64 is the definition.  Every one is five characters."""
+    pairs = [_scores(v, v) for v in range(SCORE_ROWS)]
+    text = ''.join(f'{a:.3f}' for a, _ in pairs) + ''.join(f'{b:.3f}' for _, b in pairs)
+    if len(text) != 2 * SCORE_ROWS * 5:
+        raise AssertionError('a score does not print as five characters')
+    return np.frombuffer(bytearray(text.encode('ascii')), dtype=np.uint8).reshape(2, SCORE_ROWS, 5)
+
+
+def row_text_bytes(id_lens) -> np.ndarray:
+    """Bytes all_sim prints for row i (lines j = i + 1 .. n - 1, each len_i + len_j + 14), rows 0 .. n - 2."""
+    lens = np.asarray(id_lens, dtype=np.int64)
+    n = len(lens)
+    if n < 2:
+        return np.zeros(0, dtype=np.int64)
+    after = np.cumsum(lens[::-1])[::-1]                      # after[k] = sum of lens[k:]
+    i = np.arange(n - 1, dtype=np.int64)
+    return (n - 1 - i) * (lens[:-1] + 14) + after[1:]
+
+
+def plan_stripes(id_lens, idx, text_bytes: int, fp_rows: int):
+    """Stripes [i0, i1) of rows 0 .. n - 2 in order, each as (i0, i1, row bases (int64, relative to the stripe's first byte),
+    stripe bytes): as many rows as keep the text within ``text_bytes`` and the rows' fingerprints within ``fp_rows`` -- at
+    least one row, however large."""
+    size = row_text_bytes(id_lens)
+    fps = np.diff(np.asarray(idx, dtype=np.int64))[:len(size)]
+    cb = np.concatenate([[0], np.cumsum(size)])
+    cf = np.concatenate([[0], np.cumsum(fps)])
+    out, i0, m = [], 0, len(size)
+    while i0 < m:
+        i1 = min(int(np.searchsorted(cb, cb[i0] + text_bytes, 'right')), int(np.searchsorted(cf, cf[i0] + fp_rows, 'right'))) - 1
+        i1 = min(m, max(i0 + 1, i1))
+        out.append((i0, i1, cb[i0:i1] - cb[i0], int(cb[i1] - cb[i0])))
+        i0 = i1
+    return out
+
+
+class AllPairs:
+    """all_sim's text (src/dct-sim.py:158-176) for one file, upper triangle only, streamed: rows in stripes (``plan_stripes``)
+    whose text fits in TEXT_BYTES and whose fingerprints times a column group fit in TILE_INTS; per stripe and group of at most
+    COL_ROWS later fingerprints, ``l1_matrix`` -> ``block_min_device`` -> ``sim_lines`` into one device text buffer, copied
+    to one of two pinned buffers while the host writes out the other.  No per-line Python; host memory beyond the data is the
+    two buffers plus O(n)."""
+
+    TEXT_BYTES = 1 << 28    # text of one stripe (a single row may exceed it: the buffers grow)
+    COL_ROWS = 1 << 22      # fingerprints of the column side on the device at a time (the whole file stays there if it fits)
+    TILE_INTS = 1 << 28     # int32 entries of one distance matrix (1 GiB)
+
+    def __init__(self, sid, idx, fps):
+        self.sid, self.idx, self.fps = sid, np.asarray(idx, dtype=np.int64), fps
+
+    def stripes(self, id_lens):
+        total = int(self.idx[-1]) if len(self.idx) else 0
+        fp_rows = max(1, self.TILE_INTS // max(1, min(self.COL_ROWS, total)))
+        return plan_stripes(id_lens, self.idx, self.TEXT_BYTES, fp_rows)
+
+    def write(self, sink):
+        """Calls ``sink(memoryview)`` with the text of each stripe, in order."""
+        import torch
+        n = len(self.idx) - 1
+        if n < 2:
+            return
+        ids = LineIds([f'{s}' for s in self.sid])
+        dev = ids.bytes_dev.device
+        stream = torch.cuda.current_stream(dev)
+        table = torch.as_tensor(score_table(), device=dev)
+        total = int(self.idx[-1])
+        resident = to_device_int8(self.fps[:total]) if 0 < total <= self.COL_ROWS else None
+
+        def rows(p0, p1):
+            if resident is not None:
+                return resident[self.idx[p0]:self.idx[p1]]
+            return to_device_int8(self.fps[self.idx[p0]:self.idx[p1]])
+
+        text, pinned, pending = None, [None, None], None
+        for k, (i0, i1, base, nbytes) in enumerate(self.stripes(ids.lens)):
+            if text is None or text.numel() < nbytes:
+                text = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+            a = rows(i0, i1) if self.idx[i1] > self.idx[i0] else None
+            ia = self.idx[i0:i1 + 1] - self.idx[i0]
+            col0 = i0 + 1
+            for q0, q1 in _protein_groups(self.idx[col0:] - self.idx[col0], self.COL_ROWS):
+                q0, q1 = q0 + col0, q1 + col0
+                b = rows(q0, q1) if a is not None and self.idx[q1] > self.idx[q0] else None
+                dist = l1_matrix(a, b) if b is not None else torch.empty((0, 0), dtype=torch.int32, device=dev)
+                mn, last = block_min_device(dist, ia, self.idx[q0:q1 + 1] - self.idx[q0])
+                sim_lines(mn, last, i0, q0, ids, table, base, text)
+                del dist, mn, last, b
+            pin = pinned[k % 2]                                 # (written out by the host two stripes ago)
+            if pin is None or pin.numel() < nbytes:
+                pin = pinned[k % 2] = torch.empty(max(nbytes, min(self.TEXT_BYTES, 2 * nbytes)), dtype=torch.uint8, pin_memory=True)
+            pin[:nbytes].copy_(text[:nbytes], non_blocking=True)
+            done = torch.cuda.Event()
+            done.record(stream)
+            if pending is not None:                             # the previous stripe goes out while the device fills this one
+                self._flush(sink, *pending)
+            pending = (pin, nbytes, done)
+        self._flush(sink, *pending)
+
+    @staticmethod
+    def _flush(sink, pin, nbytes, done):
+        done.synchronize()
+        sink(memoryview(pin.numpy())[:nbytes])
 
 
 def _load_npz(filename: str) -> tuple:
@@ -306,6 +416,16 @@ class Report:
     def line(self, text: str):
         self.out.write(text + '\n')
 
+    def raw(self, data):
+        """UTF-8 bytes straight to the binary layer under the text one (flushed first, so that the order of everything written
+        stays as it is); text for a stream without one (a ``StringIO``) or with another encoding."""
+        buf = getattr(self.out, 'buffer', None)
+        if buf is None or (getattr(self.out, 'encoding', None) or '').lower().replace('-', '').replace('_', '') != 'utf8':
+            self.out.write(bytes(data).decode('utf8'))
+            return
+        self.out.flush()
+        buf.write(data)
+
     def close(self):
         if self.path:
             self.out.close()
@@ -375,12 +495,9 @@ def db_search(npzfile: str, dbfile: str, top: int, threshold: float, report: Rep
 
 @_reporting
 def all_sim(npzfile: str, report: Report):
-    """All-against-all, upper triangle (src/dct-sim.py:158-176)."""
-    blk = Blocks(npzfile)
-    n = len(blk.rows)
-    for i, j in zip(*np.triu_indices(n, k=1)):
-        maxs, s = blk.scores(i, j)
-        report.line(f'{blk.rows[i]} {blk.rows[j]} {maxs:.3f} {s:.3f}')
+    """All-against-all, upper triangle (src/dct-sim.py:158-176), streamed from the device (``AllPairs``)."""
+    sid, idx, fps = _load_npz(npzfile)
+    AllPairs(sid, idx, fps).write(report.raw)
 
 
 def build_parser() -> argparse.ArgumentParser:

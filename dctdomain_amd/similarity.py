@@ -53,6 +53,11 @@ def block_min(dist: torch.Tensor, idx_a, idx_b):
     if dist.numel() == 0:       # proteins without a single fingerprint on either side: every block is empty
         empty = np.full((npa, npb), 0x7fffffff, dtype=np.int32)     # what block_min_kernel writes for an empty block
         return empty, empty.copy()
+    return _pair_to_host(*_block_min_launch(dist, ia, ib), np.int32)
+
+
+def _block_min_launch(dist: torch.Tensor, ia: torch.Tensor, ib: torch.Tensor):
+    npa, npb = len(ia) - 1, len(ib) - 1
     mn = torch.empty((npa, npb), dtype=torch.int32, device=dist.device)
     last = torch.empty((npa, npb), dtype=torch.int32, device=dist.device)
     if mn.numel():
@@ -62,7 +67,18 @@ def block_min(dist: torch.Tensor, idx_a, idx_b):
                                             dist.stride(0) if dist.shape[0] > 1 else dist.shape[1], ia.data_ptr(), npa,
                                             ib.data_ptr(), npb, mn.data_ptr(), last.data_ptr(),
                                             C.c_void_p(stream.cuda_stream)))
-    return _pair_to_host(mn, last, np.int32)
+    return mn, last
+
+
+def block_min_device(dist: torch.Tensor, idx_a, idx_b):
+    """``block_min`` with its two (npa, npb) int32 outputs left on the device (contiguous, row stride npb)."""
+    ia = torch.as_tensor(np.asarray(idx_a, dtype=np.int64), device=dist.device)
+    ib = torch.as_tensor(np.asarray(idx_b, dtype=np.int64), device=dist.device)
+    if dist.numel() == 0:       # (block_min_kernel's fill for empty blocks)
+        shape = (len(ia) - 1, len(ib) - 1)
+        return (torch.full(shape, 0x7fffffff, dtype=torch.int32, device=dist.device),
+                torch.full(shape, 0x7fffffff, dtype=torch.int32, device=dist.device))
+    return _block_min_launch(dist, ia, ib)
 
 
 def order_pairs(v: np.ndarray, i: np.ndarray):
@@ -185,3 +201,50 @@ def threshold_select(dist: torch.Tensor, top: int, bound: int, row_empty=None, c
         o = np.argsort(k[s], kind='stable')
         k[s], c[s] = k[s][o], c[s][o]
     return offsets, k, c
+
+
+class LineIds:
+    """The protein ids of a file as ``dctfp_sim_lines`` reads them: ``off`` = int64 prefix offsets of their UTF-8 bytes (host),
+    ``bytes_dev`` / ``off_dev`` = the concatenated bytes and the offsets on the device."""
+
+    def __init__(self, names, device=None):
+        device = device if device is not None else _dev()
+        enc = [str(s).encode('utf8') for s in names]
+        self.lens = np.fromiter((len(e) for e in enc), dtype=np.int64, count=len(enc))
+        self.off = np.zeros(len(enc) + 1, dtype=np.int64)
+        np.cumsum(self.lens, out=self.off[1:])
+        raw = np.frombuffer(bytearray(b''.join(enc)), dtype=np.uint8)
+        self.bytes_dev = torch.as_tensor(raw if len(raw) else np.zeros(1, dtype=np.uint8), device=device)
+        self.off_dev = _device_int64(self.off, device)
+
+
+def sim_lines(mn: torch.Tensor, last: torch.Tensor, row0: int, col0: int, ids: LineIds, table: torch.Tensor, row_base, out: torch.Tensor):
+    """all_sim's text for a (min, last) device tile (``block_min_device``): the lines (row0 + r, col0 + c) with column > row, row
+    r's lines from byte ``row_base[r]`` of the device uint8 buffer ``out`` (``dctfp_sim_lines``; include/dctfp.h has the
+    layout).  ``table``: device uint8 (2, 17002, 5), ``dct_sim.score_table``.  Every line must fit in ``out``: checked here."""
+    n_rows, n_cols = mn.shape
+    row_base = np.asarray(row_base, dtype=np.int64)
+    n = len(ids.off) - 1
+    if last.shape != mn.shape or len(row_base) != n_rows or mn.dtype != torch.int32 or last.dtype != torch.int32:
+        raise ValueError('mn / last must be int32 tiles of one shape, one row base per row')
+    if not (mn.is_contiguous() and last.is_contiguous()):
+        raise ValueError('mn / last must be contiguous')
+    if table.dtype != torch.uint8 or table.numel() != 2 * 17002 * 5 or out.dtype != torch.uint8 or not out.is_contiguous():
+        raise ValueError('table must be uint8 (2, 17002, 5) and out a contiguous uint8 buffer')
+    if n_rows == 0 or n_cols == 0:
+        return
+    if row0 < 0 or col0 < 0 or row0 + n_rows > n or col0 + n_cols > n:
+        raise IndexError('tile outside the proteins of the id list')
+    i = row0 + np.arange(n_rows, dtype=np.int64)              # (the kernel trusts its offsets: bound every row's last line here)
+    j_hi = col0 + n_cols
+    live = j_hi > i + 1
+    ends = row_base[live] + (j_hi - i[live] - 1) * (ids.lens[i[live]] + 14) + (ids.off[j_hi] - ids.off[i[live] + 1])
+    if (row_base < 0).any() or (len(ends) and ends.max() > out.numel()):
+        raise ValueError('the lines do not fit in the output buffer')
+    dev = mn.device
+    ctx = _lib.get_context(dev.index)
+    stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    base = _device_int64(row_base, dev)
+    _lib.check(ctx._lib.dctfp_sim_lines(ctx.handle, mn.data_ptr(), last.data_ptr(), n_cols, n_rows, int(row0), int(col0), n_cols,
+                                        ids.bytes_dev.data_ptr(), ids.off_dev.data_ptr(), table.data_ptr(), base.data_ptr(), out.data_ptr(),
+                                        stream))

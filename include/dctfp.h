@@ -329,6 +329,19 @@ int dctfp_select_fill(dctfp_ctx* ctx, const int32_t* dist, int64_t n_rows, int64
                       const uint8_t* col_empty, int32_t cap, const int32_t* cut, const int64_t* offsets, int32_t max_count, int32_t* out_key,
                       int32_t* out_col, void* stream);
 
+/* all_sim's result lines (src/dct-sim.py:158-176) as UTF-8 text, from a tile of (min, last) L1 values (dctfp_block_min's two
+ * outputs, device int32, row stride ld): entry (r, c) belongs to proteins i = row0 + r and j = col0 + c, and only j > i is
+ * printed.  Line (i, j) = "{id_i} {id_j} {a} {b}\n": ids[id_off[p] .. id_off[p+1]) is protein p's id (device bytes and int64
+ * prefix offsets, every protein of the file); a / b = the five bytes of row min(L1, 17001) of the score table (device,
+ * 2 x 17002 rows of 5 bytes: DCTdomain text by min, then DCTglobal text by last; row 17001 stands for every L1 above 17000,
+ * 0x7fffffff included).  Row i's lines, j = i + 1 .. in order, start at out + row_base[r] (device int64, n_rows); the line of
+ * j starts (j - i - 1) (len_i + 14) + (id_off[j] - id_off[i + 1]) bytes after that.  The call writes the lines of columns
+ * [col0, col0 + n_cols) only, so a row may be filled by several calls; nothing outside those lines' bytes is written (the
+ * caller sizes `out`).  Any id length, any alignment of `out`. */
+int dctfp_sim_lines(dctfp_ctx* ctx, const int32_t* mn, const int32_t* last, int64_t ld, int64_t n_rows, int64_t row0, int64_t col0,
+                    int64_t n_cols, const uint8_t* ids, const int64_t* id_off, const char* table, const int64_t* row_base, uint8_t* out,
+                    void* stream);
+
 /* The address under which the GPU sees a pinned (page-locked, mapped) host buffer, e.g. a torch tensor created with
  * pin_memory=True.  A caller that passes this address as `out` of dctfp_quantize gets the int8 result written straight
  * into host memory: no device buffer, no copy -- what a one-protein-per-call user wants (480 bytes per domain). */

@@ -1,0 +1,174 @@
+"""dct-sim all-against-all (all_sim) streamed from the device: identity with the block-matrix path, and rates at scale.
+
+    python tools/all_sim_bench.py --part compare [--n 2000]            # old (Blocks) and new path: sha256 of the text, times
+    python tools/all_sim_bench.py --part scale --n 20000 [--dir D]     # new path to /dev/null and to a file under D
+
+`scale` writes a synthetic -dct.npz (about 4.5 fingerprints per protein, 17-character ids) and runs the new path in a child
+process per sink (and one that only initialises the GPU: the RSS floor), so that the child's peak RSS (ru_maxrss of RUSAGE_CHILDREN, as tools/run_with_rss.py) is that of the run
+alone.  The child also measures the pinned device-to-host copy rate of one TEXT_BYTES buffer.  The file run is skipped when
+the disk under D has less room than the text.  Prints one JSON line per part; --out appends it to a file."""
+
+from __future__ import annotations
+
+import argparse
+import hashlib
+import json
+import os
+import resource
+import shutil
+import subprocess
+import sys
+import tempfile
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def synth(path: str, n: int, seed: int):
+    rng = np.random.default_rng(seed)
+    counts = rng.integers(1, 9, size=n)                       # 1 .. 8 fingerprints, 4.5 on average
+    idx = np.zeros(n + 1, dtype=np.int64)
+    np.cumsum(counts, out=idx[1:])
+    dct = rng.integers(-48, 49, size=(int(idx[-1]), 480), dtype=np.int8)
+    sid = np.array([f'UniRef50_{k:08d}' for k in range(n)])
+    np.savez(path, sid=sid, idx=idx, dom=np.array(['1-9'] * len(dct)), dct=dct)
+    return int(idx[-1])
+
+
+def _old_text(path: str) -> bytes:
+    """all_sim as it printed through dct_sim.Blocks (header and result lines)."""
+    from dctdomain_amd import dct_sim
+    blk = dct_sim.Blocks(path)
+    lines = [dct_sim.HEADER]
+    for i, j in zip(*np.triu_indices(len(blk.rows), k=1)):
+        maxs, s = blk.scores(i, j)
+        lines.append(f'{blk.rows[i]} {blk.rows[j]} {maxs:.3f} {s:.3f}')
+    return ('\n'.join(lines) + '\n').encode('utf8')
+
+
+def part_compare(args):
+    import torch
+    from dctdomain_amd import dct_sim
+    with tempfile.TemporaryDirectory(dir=args.dir) as tmp:
+        path = os.path.join(tmp, 'c-dct.npz')
+        synth(path, args.n, 5)
+        dct_sim.main(['--dct', path, '--output', os.path.join(tmp, 'warm.txt')])     # (context, kernels loaded)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        old = _old_text(path)
+        t_old = time.perf_counter() - t0
+        out = os.path.join(tmp, 'new.txt')
+        t0 = time.perf_counter()
+        dct_sim.main(['--dct', path, '--output', out])
+        t_new = time.perf_counter() - t0
+        new = open(out, 'rb').read()
+    return {'part': 'compare', 'n': args.n, 'lines': new.count(b'\n') - 1, 'sha256_old': hashlib.sha256(old).hexdigest(),
+            'sha256_new': hashlib.sha256(new).hexdigest(), 'identical': old == new, 'old_s': round(t_old, 3), 'new_s': round(t_new, 3)}
+
+
+def part_run(args):
+    """(child) one streamed run of the new path from --npz to --sink, after the load."""
+    import torch
+    from dctdomain_amd import dct_sim
+    sid, idx, fps = dct_sim._load_npz(args.npz)
+    n = len(sid)
+    ap = dct_sim.AllPairs(sid, idx, fps)
+    written = [0]
+    with open(args.sink, 'wb', buffering=0) as fh:
+        def sink(mv):
+            fh.write(mv)
+            written[0] += len(mv)
+        t0 = time.perf_counter()
+        ap.write(sink)
+        torch.cuda.synchronize()
+        os.fsync(fh.fileno()) if args.sink != os.devnull else None
+        dt = time.perf_counter() - t0
+    dev = torch.device('cuda', 0)
+    # pinned device-to-host rate of one text buffer, in this process (after the run: its buffers come from the same cache)
+    size = int(min(ap.TEXT_BYTES, 1 << 28))
+    src = torch.empty(size, dtype=torch.uint8, device=dev)
+    pin = torch.empty(size, dtype=torch.uint8, pin_memory=True)
+    pin.copy_(src, non_blocking=True)
+    torch.cuda.synchronize()
+    reps = 10
+    t0 = time.perf_counter()
+    for _ in range(reps):
+        pin.copy_(src, non_blocking=True)
+    torch.cuda.synchronize()
+    d2h = reps * size / (time.perf_counter() - t0)
+    del src, pin
+    lines = n * (n - 1) // 2
+    return {'n': n, 'fingerprints': int(idx[-1]), 'lines': lines, 'text_bytes': written[0], 'seconds': round(dt, 3),
+            'lines_per_s': round(lines / dt), 'text_GBps': round(written[0] / dt / 1e9, 2), 'd2h_pinned_GBps': round(d2h / 1e9, 2),
+            'text_over_d2h': round(written[0] / dt / d2h, 3)}
+
+
+def part_base(args):
+    """(child) a process that has only initialised the GPU and run one small distance tile: the RSS floor of the run."""
+    import torch
+    from dctdomain_amd.similarity import l1_matrix
+    l1_matrix(np.zeros((4, 480), dtype=np.int8), np.zeros((4, 480), dtype=np.int8))
+    torch.cuda.synchronize()
+    return {'part': 'base'}
+
+
+def _child_rss(cmd, timeout):
+    """(completed process, its peak RSS in MiB): one fresh process per measurement.  ru_maxrss of RUSAGE_CHILDREN is the
+    largest over every child so far, so None means "not above an earlier child's"."""
+    before = resource.getrusage(resource.RUSAGE_CHILDREN).ru_maxrss
+    p = subprocess.run(cmd, capture_output=True, text=True, timeout=timeout)
+    peak = resource.getrusage(resource.RUSAGE_CHILDREN).ru_maxrss
+    return p, (round(peak / 1024) if peak > before else None)
+
+
+def part_scale(args):
+    from dctdomain_amd import dct_sim
+    res = {'part': 'scale', 'n': args.n}
+    with tempfile.TemporaryDirectory(dir=args.dir) as tmp:
+        path = os.path.join(tmp, 's-dct.npz')
+        rows = synth(path, args.n, 7)
+        res['npz_MB'] = round(os.path.getsize(path) / 2 ** 20)
+        res['data_MB'] = round(rows * 480 / 2 ** 20)
+        res['two_buffers_MB'] = round(2 * dct_sim.AllPairs.TEXT_BYTES / 2 ** 20)
+        text = int(dct_sim.row_text_bytes(np.full(args.n, 17)).sum())
+        p, res['base_rss_MB'] = _child_rss([sys.executable, os.path.abspath(__file__), '--part', 'base'], args.timeout)
+        for name, sink in (('devnull', os.devnull), ('file', os.path.join(tmp, 'all.txt'))):
+            if name == 'file' and shutil.disk_usage(tmp).free < text + (1 << 30):
+                res[name] = {'skipped': f'{shutil.disk_usage(tmp).free / 1e9:.0f} GB free, {text / 1e9:.0f} GB of text'}
+                continue
+            cmd = [sys.executable, os.path.abspath(__file__), '--part', 'run', '--npz', path, '--sink', sink]
+            p, peak = _child_rss(cmd, args.timeout)
+            if p.returncode != 0:
+                res[name] = {'rc': p.returncode, 'stderr': p.stderr[-2000:]}
+                break
+            r = json.loads(p.stdout.strip().splitlines()[-1])
+            r['peak_rss_MB'] = peak
+            res[name] = r
+            if name == 'file':
+                os.unlink(sink)
+    return res
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--part', required=True, choices=['compare', 'scale', 'run', 'base'])
+    ap.add_argument('--n', type=int, default=2000)
+    ap.add_argument('--dir', default=None, help='where the npz and the text file go (local disk)')
+    ap.add_argument('--npz')
+    ap.add_argument('--sink')
+    ap.add_argument('--timeout', type=float, default=1200)
+    ap.add_argument('--out')
+    args = ap.parse_args()
+    res = {'compare': part_compare, 'scale': part_scale, 'run': part_run, 'base': part_base}[args.part](args)
+    line = json.dumps(res)
+    print(line)
+    if args.out:
+        with open(args.out, 'a') as fh:
+            fh.write(line + '\n')
+
+
+if __name__ == '__main__':
+    main()
