@@ -136,6 +136,154 @@ struct Staging {  // pinned host buffer + the event after its last H2D copy (or 
     }
 };
 
+// A device buffer of the context that calls on different streams take in turn (the job tables, the Y' scratch, the cutter's
+// adjacency lists, the generic scratch).  The rule -- wait for the last reader before you overwrite, record after your last
+// reader -- is applied by Hold and TableLease only.
+struct SharedBuf {
+    DevBuf buf;
+    hipEvent_t ev_free = nullptr;  // after the last reader of the call that used the buffer last (any stream)
+    bool busy = false;
+    void release() {
+        buf.release();
+        if (ev_free) (void)hipEventDestroy(ev_free);
+    }
+};
+
+// A call's hold on a SharedBuf: take() on the stream that first touches it, give_back() on the caller's stream after the last
+// reader.  Taken and not given back, it gives the buffer back when it goes out of scope, on every path out of the call;
+// keep() instead: the caller waits for its stream before anything else can touch the context.
+struct Hold {
+    SharedBuf& b;
+    hipStream_t caller;
+    bool armed = false;
+    int take(size_t bytes, hipStream_t s) {
+        armed = true;
+        const int rc = b.buf.ensure(bytes);
+        if (rc == DCTFP_OK && b.busy) HIP_TRY(hipStreamWaitEvent(s, b.ev_free, 0));
+        return rc;
+    }
+    void* p() const { return b.buf.p; }
+    int give_back() {
+        armed = false;
+        if (!b.ev_free) HIP_TRY(hipEventCreateWithFlags(&b.ev_free, hipEventDisableTiming));
+        HIP_TRY(hipEventRecord(b.ev_free, caller));
+        b.busy = true;
+        return DCTFP_OK;
+    }
+    void keep() { armed = false; }
+    ~Hold() {
+        if (armed) (void)give_back();
+    }
+};
+
+// The job tables of the calls: two buffers (pinned staging + device copy) taken in turn, so that the tables of one call go up
+// while the kernels of the one before still read theirs.  Only a TableLease reaches them.
+class TableRing {
+    struct Slot {
+        SharedBuf tab;
+        Staging stg;
+    } slot_[2];
+    int next_ = 0;
+    friend class TableLease;
+
+  public:
+    void release() { for (Slot& s : slot_) s.tab.release(), s.stg.release(); }
+};
+
+// A call's lease on the next buffer of the ring.  The host writes the tables into stage(); upload() sends them up on the
+// caller's or the copy stream, behind the last reader of the call that had the buffer two calls ago; or the kernels read them
+// through zero_copy().  release() marks the point after the last reader on the caller's stream.  A lease that has uploaded
+// or handed out its pinned buffer gives the buffer back there when it goes out of scope unreleased (declare the call's Fork
+// after the lease: whatever the context's own streams read is joined into the caller's stream by then).
+class TableLease {
+    TableRing::Slot& s_;
+    Hold tab_;
+    hipStream_t up_ = nullptr;
+    bool uploaded_ = false, zero_copy_ = false;
+
+  public:
+    TableLease(TableRing& r, hipStream_t caller) : s_(r.slot_[r.next_]), tab_{s_.tab, caller} { r.next_ ^= 1; }
+    int stage(size_t bytes) { return s_.stg.ensure(bytes); }
+    char* host() const { return (char*)s_.stg.p; }
+    char* dev() const { return (char*)s_.tab.buf.p; }
+    bool mapped() const { return s_.stg.dev != nullptr; }
+    char* zero_copy() { return zero_copy_ = true, (char*)s_.stg.dev; }
+    int upload(size_t bytes, hipStream_t s, size_t dev_bytes = 0) {  // (into a device buffer of at least dev_bytes)
+        const int rc = tab_.take(std::max(bytes, dev_bytes), s);
+        if (rc) return rc;
+        uploaded_ = true;
+        up_ = s;
+        HIP_TRY(hipMemcpyAsync(dev(), host(), bytes, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipEventRecord(s_.stg.ev, s));
+        s_.stg.pending = true;
+        return DCTFP_OK;
+    }
+    int release() {
+        const bool zc = zero_copy_;
+        uploaded_ = zero_copy_ = false;
+        const int rc = tab_.give_back();
+        if (rc || !zc) return rc;
+        HIP_TRY(hipEventRecord(s_.stg.ev, tab_.caller));  // the kernels read the staging buffer itself: free again after them
+        s_.stg.pending = true;
+        return DCTFP_OK;
+    }
+    void keep() { tab_.keep(), uploaded_ = zero_copy_ = false; }
+    ~TableLease() {
+        if (uploaded_ && up_ != tab_.caller) (void)hipStreamWaitEvent(tab_.caller, s_.stg.ev, 0);
+        if (uploaded_ || zero_copy_) (void)release();
+    }
+};
+
+// One of the context's own streams and the event that joins it back into a caller's.
+struct Branch {
+    hipStream_t s = nullptr;
+    hipEvent_t ev = nullptr;
+    int create(int priority = 0) {
+        if (!s) HIP_TRY(hipStreamCreateWithPriority(&s, hipStreamNonBlocking, priority));
+        if (!ev) HIP_TRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+        return DCTFP_OK;
+    }
+    void destroy() {
+        if (s) (void)hipStreamDestroy(s);
+        if (ev) (void)hipEventDestroy(ev);
+    }
+};
+
+// Work a call sends off the caller's stream onto the context's own streams.  branch() hands out a stream, which waits for the
+// fork point the first time the call uses it, if the call has set one (fork(); the copy stream, ahead of the caller's, has
+// none).  join() -- or the destructor, on every path out of the call -- makes the caller's stream wait for every branch used.
+// Declared after the call's TableLease and Holds, it is destroyed first: what they give back on the caller's stream then comes
+// after every reader.
+class Fork {
+    hipStream_t caller_;
+    hipEvent_t fork_ = nullptr;
+    const Branch* used_[kCutClasses] = {};
+    int n_used_ = 0;
+
+  public:
+    explicit Fork(hipStream_t caller) : caller_(caller) {}
+    int fork(hipEvent_t ev) {
+        fork_ = ev;
+        HIP_TRY(hipEventRecord(ev, caller_));
+        return DCTFP_OK;
+    }
+    int branch(const Branch& b, hipStream_t* s) {
+        *s = b.s;
+        if (std::find(used_, used_ + n_used_, &b) != used_ + n_used_) return DCTFP_OK;
+        used_[n_used_++] = &b;
+        if (fork_) HIP_TRY(hipStreamWaitEvent(b.s, fork_, 0));
+        return DCTFP_OK;
+    }
+    int join() {
+        for (; n_used_ > 0; --n_used_) {
+            HIP_TRY(hipEventRecord(used_[n_used_ - 1]->ev, used_[n_used_ - 1]->s));
+            HIP_TRY(hipStreamWaitEvent(caller_, used_[n_used_ - 1]->ev, 0));
+        }
+        return DCTFP_OK;
+    }
+    ~Fork() { (void)join(); }
+};
+
 struct StEntry {  // stage-B basis  St[d][c] (ldy x cp), zero padded
     double* dev = nullptr;
     double* frag = nullptr;  // even/odd halves of the basis in MFMA-fragment order (walk_ab_kernel), `frag_groups` 16-pair groups
@@ -163,31 +311,24 @@ constexpr size_t kCounterBytes = 24 * sizeof(unsigned long long);  // [0] degene
 struct dctfp_ctx {
     int device = 0;
     int64_t opt_overlap = 4;
-    hipStream_t side = nullptr;
-    hipStream_t copy = nullptr;                 // table upload + cosine tables, ahead of the caller's stream
-    hipEvent_t ev_tab_free[2] = {}, ev_tab_ready = nullptr;
-    hipEvent_t ev_ws_free = nullptr;            // after the last reader of the Y' scratch (any stream, any call)
+    Branch side;                                // stage B of the two-kernel path
+    Branch copy;                                // table upload + cosine tables, ahead of the caller's stream
     hipEvent_t ev_basis = nullptr;              // after the last basis_kernel (cosine tables are shared by all later calls)
     hipStream_t basis_stream = nullptr;
     bool basis_valid = false;
-    bool tab_busy[2] = {false, false};
-    bool ws_busy = false;
     std::mutex mu;                              // one host thread at a time inside a context
     int ensure_copy() {
-        if (copy) return DCTFP_OK;
-        if (hipStreamCreateWithFlags(&copy, hipStreamNonBlocking) != hipSuccess) { copy = nullptr; set_err("hipStreamCreate(copy) failed"); return DCTFP_ERR_HIP; }
-        if (hipEventCreateWithFlags(&ev_tab_ready, hipEventDisableTiming) != hipSuccess ||
-            hipEventCreateWithFlags(&ev_ws_free, hipEventDisableTiming) != hipSuccess ||
-            hipEventCreateWithFlags(&ev_basis, hipEventDisableTiming) != hipSuccess ||
-            hipEventCreateWithFlags(&ev_tab_free[0], hipEventDisableTiming) != hipSuccess ||
-            hipEventCreateWithFlags(&ev_tab_free[1], hipEventDisableTiming) != hipSuccess) { set_err("hipEventCreate failed"); return DCTFP_ERR_HIP; }
+        if (copy.s) return DCTFP_OK;
+        int rc = copy.create();
+        if (rc) return rc;
+        HIP_TRY(hipEventCreateWithFlags(&ev_basis, hipEventDisableTiming));
         return DCTFP_OK;
     }
     hipEvent_t ev_a[kMaxSlots] = {}, ev_b[kMaxSlots] = {};
     int ensure_side() {
-        if (side) return DCTFP_OK;
-        hipError_t e = hipStreamCreateWithFlags(&side, hipStreamNonBlocking);
-        if (e != hipSuccess) { side = nullptr; snprintf(g_err, sizeof g_err, "hipStreamCreate: %s", hipGetErrorString(e)); return DCTFP_ERR_HIP; }
+        if (side.s) return DCTFP_OK;
+        int rc = side.create();
+        if (rc) return rc;
         for (int i = 0; i < kMaxSlots; ++i) {
             if (hipEventCreateWithFlags(&ev_a[i], hipEventDisableTiming) != hipSuccess ||
                 hipEventCreateWithFlags(&ev_b[i], hipEventDisableTiming) != hipSuccess) {
@@ -198,12 +339,10 @@ struct dctfp_ctx {
         return DCTFP_OK;
     }
     int64_t opt_stage_b = 1, opt_a_waves = 0, opt_a_unroll = 4, opt_profile = 0, opt_ws_mb = 4096;
-    DevBuf tables[2];
-    Staging staging[2];
-    int flip = 0;
-    DevBuf ws;       // yprime
+    TableRing ring;
+    SharedBuf ws;       // yprime
     int64_t opt_fuse = 1, opt_pack_y = 1;
-    DevBuf scratch;  // generic idct_quant fs
+    SharedBuf scratch;  // dctfp_idct_quant's coefficients, dctfp_row_select's candidates
     DevBuf split_ws; // partial sums of the row-split stage A (small calls)
     uint32_t* small_tickets = nullptr;  // small_call_kernel: arrival counters, zeroed once (their last taker resets them)
     // "small_one": 1 = a small call of the production shape in ONE launch (small_call_kernel, round 5).  Off by default: measured
@@ -221,13 +360,11 @@ struct dctfp_ctx {
     int n_cu = 256;  // compute units of the device (workgroup slots of the walk kernel = n_cu x workgroups per CU)
     void *trace_dev = nullptr, *trace_host = nullptr;  // instrumented build only (walk_trace)
     int64_t trace_waves = 0;
-    DevBuf cut_ws;   // dctfp_reccut: adjacency lists and node stacks of a batch
-    hipStream_t cut_stream[kCutClasses - 1] = {};   // ... its larger size classes run beside the small one
-    hipEvent_t cut_ev[kCutClasses] = {};
-    hipEvent_t ev_cut_ws_free = nullptr;            // after the last dctfp_reccut that used cut_ws (calls on different streams share it)
-    bool cut_ws_busy = false;
+    SharedBuf cut_ws;   // dctfp_reccut: adjacency lists and node stacks of a batch
+    Branch cut[kCutClasses - 1];    // ... its larger size classes run beside the small one (and dctfp_contact_topk's long chain)
+    hipEvent_t cut_fork = nullptr;
     int ensure_cut_streams() {
-        if (cut_stream[0]) return DCTFP_OK;
+        if (cut[kCutClasses - 2].s) return DCTFP_OK;
         // (the highest priority the device offers: what runs on them -- the long proteins' workgroups, the striped selection -- is
         //  what a flush waits for, and its workgroups should take the CUs the short proteins' ones leave)
         int prio_low = 0, prio_high = 0;
@@ -235,10 +372,11 @@ struct dctfp_ctx {
             (void)hipGetLastError();
             prio_high = 0;
         }
-        for (int i = 0; i < kCutClasses - 1; ++i)
-            if (hipStreamCreateWithPriority(&cut_stream[i], hipStreamNonBlocking, prio_high) != hipSuccess) { cut_stream[i] = nullptr; set_err("hipStreamCreate(cut) failed"); return DCTFP_ERR_HIP; }
-        for (int i = 0; i < kCutClasses; ++i)
-            if (hipEventCreateWithFlags(&cut_ev[i], hipEventDisableTiming) != hipSuccess) { set_err("hipEventCreate failed"); return DCTFP_ERR_HIP; }
+        if (!cut_fork) HIP_TRY(hipEventCreateWithFlags(&cut_fork, hipEventDisableTiming));
+        for (Branch& b : cut) {
+            const int rc = b.create(prio_high);
+            if (rc) return rc;
+        }
         return DCTFP_OK;
     }
     int64_t opt_path = 0, opt_ab_group = 0, opt_ab_unroll = 0, opt_ab_run_jobs = 0, opt_small_b_jobs = 512, opt_ab_longest_first = 0, opt_ab_mfma_a = 0, opt_ab_taper = 4, opt_ab_align = 2, opt_l1_kernel = 0, opt_row_select = 0, opt_stitch_once = 0, opt_topk_kernel = 0;
@@ -259,16 +397,6 @@ struct dctfp_ctx {
 };
 
 namespace {
-
-// Records that `stream` has (enqueued) the last reader of table buffer `buf`: a later dctfp_quantize uploads into it
-// from the copy stream only after this point.
-int mark_table_used(dctfp_ctx* ctx, int buf, hipStream_t stream) {
-    int rc = ctx->ensure_copy();
-    if (rc) return rc;
-    HIP_TRY(hipEventRecord(ctx->ev_tab_free[buf], stream));
-    ctx->tab_busy[buf] = true;
-    return DCTFP_OK;
-}
 
 inline size_t dtype_size(int dtype) { return dtype == DCTFP_F64 ? 8 : (dtype == DCTFP_F32 ? 4 : 2); }
 
@@ -617,8 +745,7 @@ int dctfp_destroy(dctfp_ctx* ctx) try {
     if (!ctx) return DCTFP_OK;
     (void)hipSetDevice(ctx->device);
     (void)hipDeviceSynchronize();
-    for (auto& t : ctx->tables) t.release();
-    for (auto& s : ctx->staging) s.release();
+    ctx->ring.release();
     ctx->ws.release();
     ctx->scratch.release();
     ctx->split_ws.release();
@@ -637,26 +764,15 @@ int dctfp_destroy(dctfp_ctx* ctx) try {
         (void)hipEventDestroy(e.a);
         (void)hipEventDestroy(e.b);
     }
-    if (ctx->copy) {
-        (void)hipStreamDestroy(ctx->copy);
-        (void)hipEventDestroy(ctx->ev_tab_ready);
-        (void)hipEventDestroy(ctx->ev_ws_free);
-        (void)hipEventDestroy(ctx->ev_basis);
-        (void)hipEventDestroy(ctx->ev_tab_free[0]);
-        (void)hipEventDestroy(ctx->ev_tab_free[1]);
+    ctx->copy.destroy();
+    if (ctx->ev_basis) (void)hipEventDestroy(ctx->ev_basis);
+    ctx->side.destroy();
+    for (int i = 0; i < kMaxSlots; ++i) {
+        if (ctx->ev_a[i]) (void)hipEventDestroy(ctx->ev_a[i]);
+        if (ctx->ev_b[i]) (void)hipEventDestroy(ctx->ev_b[i]);
     }
-    if (ctx->side) {
-        (void)hipStreamDestroy(ctx->side);
-        for (int i = 0; i < kMaxSlots; ++i) {
-            if (ctx->ev_a[i]) (void)hipEventDestroy(ctx->ev_a[i]);
-            if (ctx->ev_b[i]) (void)hipEventDestroy(ctx->ev_b[i]);
-        }
-    }
-    for (int i = 0; i < kCutClasses; ++i)
-        if (ctx->cut_ev[i]) (void)hipEventDestroy(ctx->cut_ev[i]);
-    if (ctx->ev_cut_ws_free) (void)hipEventDestroy(ctx->ev_cut_ws_free);
-    for (int i = 0; i < kCutClasses - 1; ++i)
-        if (ctx->cut_stream[i]) (void)hipStreamDestroy(ctx->cut_stream[i]);
+    for (Branch& b : ctx->cut) b.destroy();
+    if (ctx->cut_fork) (void)hipEventDestroy(ctx->cut_fork);
     delete ctx;
     return DCTFP_OK;
 } DCTFP_GUARD("dctfp_destroy")
@@ -1095,13 +1211,12 @@ int quantize_impl(dctfp_ctx* ctx, const dctfp_layer* layers, int32_t n_layers, i
         const size_t off_run = align_up(off_walk + (size_t)n_jobs * sizeof(Walk), 16);
         const size_t off_btab = align_up(off_run + (size_t)n_jobs * sizeof(Run), 16);
         const size_t max_bytes = align_up(off_btab + (size_t)n_domains * sizeof(BasisJob), 16);
-        const int buf = ctx->flip;
-        Staging& stg = ctx->staging[buf];
-        DevBuf& tab = ctx->tables[buf];
-        ctx->flip ^= 1;
-        int rc = stg.ensure(max_bytes);
+        TableLease tables(ctx->ring, stream);
+        Hold ws{ctx->ws, stream};
+        Fork fork(stream);
+        int rc = tables.stage(max_bytes);
         if (rc) return rc;
-        char* h = (char*)stg.p;
+        char* h = tables.host();
         JobB* hjb = (JobB*)(h + off_jobb);
         JobA* hja = (JobA*)(h + off_joba);
         PieceA* hpc = (PieceA*)(h + off_piece);
@@ -1420,8 +1535,6 @@ int quantize_impl(dctfp_ctx* ctx, const dctfp_layer* layers, int32_t n_layers, i
         }
 
         const size_t tab_bytes = align_up(off_btab + fresh.size() * sizeof(BasisJob), 16);
-        rc = tab.ensure(tab_bytes);
-        if (rc) return rc;
         // The tables go up on the context's copy stream, so the upload of this call overlaps the kernels of
         // the previous one; the copy waits until the last user of this table buffer (two calls ago) is done.
         rc = ctx->ensure_copy();
@@ -1431,15 +1544,12 @@ int quantize_impl(dctfp_ctx* ctx, const dctfp_layer* layers, int32_t n_layers, i
         const bool inline_tables = tab_bytes <= (64u << 10) && n_jobs < 512;
         // ... and read the few hundred bytes of tables straight from the pinned staging buffer: an upload through the copy
         // engine costs more latency than the kernels of such a call take
-        const bool zero_copy = inline_tables && stg.dev != nullptr;
-        hipStream_t ts = inline_tables ? stream : ctx->copy;
-        if (!zero_copy) {
-            if (ctx->tab_busy[buf]) HIP_TRY(hipStreamWaitEvent(ts, ctx->ev_tab_free[buf], 0));
-            HIP_TRY(hipMemcpyAsync(tab.p, stg.p, tab_bytes, hipMemcpyHostToDevice, ts));
-            HIP_TRY(hipEventRecord(stg.ev, ts));
-            stg.pending = true;
-        }
-        char* dt = zero_copy ? (char*)stg.dev : (char*)tab.p;
+        const bool zero_copy = inline_tables && tables.mapped();
+        hipStream_t ts = stream;
+        if (!inline_tables) rc = fork.branch(ctx->copy, &ts);
+        if (rc == DCTFP_OK && !zero_copy) rc = tables.upload(tab_bytes, ts);
+        if (rc) return rc;
+        char* dt = zero_copy ? tables.zero_copy() : tables.dev();
         const JobB* djb = (const JobB*)(dt + off_jobb);
         const JobA* dja = (const JobA*)(dt + off_joba);
         const PieceA* dpc = (const PieceA*)(dt + off_piece);
@@ -1448,20 +1558,14 @@ int quantize_impl(dctfp_ctx* ctx, const dctfp_layer* layers, int32_t n_layers, i
         const BasisJob* dbt = (const BasisJob*)(dt + off_btab);
 
         if (trivial) {
-            if (!inline_tables) {
-                HIP_TRY(hipEventRecord(ctx->ev_tab_ready, ctx->copy));
-                HIP_TRY(hipStreamWaitEvent(stream, ctx->ev_tab_ready, 0));
-            }
+            rc = fork.join();
+            if (rc) return rc;
             const int64_t total = n_jobs * n * m;
             const unsigned grid = (unsigned)std::min<int64_t>((total + 255) / 256, 4096);
             hipLaunchKernelGGL(fill_zero_kernel, dim3(grid), dim3(256), 0, stream, djb, n_jobs, n * m, out);
             HIP_TRY(hipGetLastError());
-            HIP_TRY(hipEventRecord(ctx->ev_tab_free[buf], stream));
-            ctx->tab_busy[buf] = true;
-            if (zero_copy) {  // the kernels read the staging buffer itself: it is free again after them
-                HIP_TRY(hipEventRecord(stg.ev, stream));
-                stg.pending = true;
-            }
+            rc = tables.release();
+            if (rc) return rc;
             l0 = l1;
             continue;
         }
@@ -1497,10 +1601,8 @@ int quantize_impl(dctfp_ctx* ctx, const dctfp_layer* layers, int32_t n_layers, i
             basis_publish(ctx, fresh, nk);
         }
         basis_guard.armed = false;
-        if (!inline_tables) {
-            HIP_TRY(hipEventRecord(ctx->ev_tab_ready, ctx->copy));
-            HIP_TRY(hipStreamWaitEvent(stream, ctx->ev_tab_ready, 0));
-        }
+        rc = fork.join();
+        if (rc) return rc;
         // tables cached by an earlier call may have been filled on another stream
         if (ctx->basis_valid && ctx->basis_stream != stream) HIP_TRY(hipStreamWaitEvent(stream, ctx->ev_basis, 0));
 
@@ -1541,12 +1643,8 @@ int quantize_impl(dctfp_ctx* ctx, const dctfp_layer* layers, int32_t n_layers, i
             HIP_TRY(hipGetLastError());
             rc = prof_end(ep, stream);
             if (rc) return rc;
-            HIP_TRY(hipEventRecord(ctx->ev_tab_free[buf], stream));
-            ctx->tab_busy[buf] = true;
-            if (zero_copy) {  // the kernels read the staging buffer itself: it is free again after them
-                HIP_TRY(hipEventRecord(stg.ev, stream));
-                stg.pending = true;
-            }
+            rc = tables.release();
+            if (rc) return rc;
             l0 = l1;
             continue;
         }
@@ -1579,12 +1677,8 @@ int quantize_impl(dctfp_ctx* ctx, const dctfp_layer* layers, int32_t n_layers, i
             HIP_TRY(hipGetLastError());
             rc = prof_end(ep, stream);
             if (rc) return rc;
-            HIP_TRY(hipEventRecord(ctx->ev_tab_free[buf], stream));
-            ctx->tab_busy[buf] = true;
-            if (zero_copy) {  // the kernels read the staging buffer itself: it is free again after them
-                HIP_TRY(hipEventRecord(stg.ev, stream));
-                stg.pending = true;
-            }
+            rc = tables.release();
+            if (rc) return rc;
             l0 = l1;
             continue;
         }
@@ -1592,22 +1686,21 @@ int quantize_impl(dctfp_ctx* ctx, const dctfp_layer* layers, int32_t n_layers, i
         // Stage A of chunk c runs on the caller's stream, stage B of it on the context's side
         // stream, so the MFMA-bound stage B of one chunk overlaps the HBM-bound stage A of the next.
         if (ldy != ldy_pre) return fail(DCTFP_ERR_INVALID, "internal: basis width mismatch");
-        rc = ctx->ws.ensure((size_t)sub * slots * job_bytes);
+        rc = ws.take((size_t)sub * slots * job_bytes, stream);  // (the scratch is the context's: behind whatever call used it last)
         if (rc) return rc;
         const bool side = slots > 1;
+        hipStream_t sb = stream;
         if (side) {
             rc = ctx->ensure_side();
+            if (rc == DCTFP_OK) rc = fork.branch(ctx->side, &sb);
             if (rc) return rc;
         }
-        hipStream_t sb = side ? ctx->side : stream;
-        // the scratch is the context's: wait for whatever call used it last, on whatever stream
-        if (ctx->ws_busy) HIP_TRY(hipStreamWaitEvent(stream, ctx->ev_ws_free, 0));
 
         int64_t c = 0;
         for (const Chunk& ck : plan) {
             const int64_t j0 = ck.j0, jn = ck.j1 - ck.j0;
             const int slot = (int)(c % slots);
-            char* yprime = (char*)ctx->ws.p + (size_t)slot * sub * job_bytes;
+            char* yprime = (char*)ws.p() + (size_t)slot * sub * job_bytes;
             if (side && c >= slots) HIP_TRY(hipStreamWaitEvent(stream, ctx->ev_b[slot], 0));  // slot free again?
             EventPair* ep = nullptr;
             rc = prof_begin(ctx, 0, stream, &ep);
@@ -1734,23 +1827,19 @@ int quantize_impl(dctfp_ctx* ctx, const dctfp_layer* layers, int32_t n_layers, i
             if (side) HIP_TRY(hipEventRecord(ctx->ev_b[slot], sb));
             ++c;
         }
-        if (side) {  // the caller's stream continues only after every stage B of this group
-            const int64_t used = std::min<int64_t>(c, slots);
-            for (int64_t k = 0; k < used; ++k) HIP_TRY(hipStreamWaitEvent(stream, ctx->ev_b[k], 0));
-        }
+        rc = fork.join();  // the caller's stream continues only after every stage B of this group
+        if (rc) return rc;
         // (dctfp_quantize_one waits for the stream before it returns: scratch, tables and staging buffer ARE free for whoever
         //  comes next, on whatever stream -- three event records, 4-5 us of a 56-us call, say nothing it does not already know)
         // -- for the LAST layer group of the call only: an earlier group's buffers are taken again by a later group of the same call
         // (five layers of five geometries: the staging buffer of group 1 is group 3's), long before the call's wait.
-        if (!(tl_sync_call && l1 == n_layers)) {
-            HIP_TRY(hipEventRecord(ctx->ev_ws_free, stream));  // ... and the scratch is free for the next call after this point
-            ctx->ws_busy = true;
-            HIP_TRY(hipEventRecord(ctx->ev_tab_free[buf], stream));  // this table buffer may be overwritten after this point
-            ctx->tab_busy[buf] = true;
-            if (zero_copy) {
-                HIP_TRY(hipEventRecord(stg.ev, stream));
-                stg.pending = true;
-            }
+        if (tl_sync_call && l1 == n_layers) {
+            ws.keep();
+            tables.keep();
+        } else {  // ... and the scratch and this table buffer may be overwritten after this point
+            rc = ws.give_back();
+            if (rc == DCTFP_OK) rc = tables.release();
+            if (rc) return rc;
         }
         l0 = l1;
     }
@@ -1972,9 +2061,10 @@ int dctfp_idct_quant(dctfp_ctx* ctx, const void* vec, int32_t dtype, int64_t n_r
     if (num > 65535) return fail(DCTFP_ERR_LIMIT, "dctfp_idct_quant: num %d", num);
     hipStream_t stream = (hipStream_t)stream_v;
     HIP_TRY(hipSetDevice(ctx->device));
-    int rc = ctx->scratch.ensure((size_t)num * n_cols * sizeof(double));
+    Hold scratch{ctx->scratch, stream};
+    int rc = scratch.take((size_t)num * n_cols * sizeof(double), stream);
     if (rc) return rc;
-    double* fs = (double*)ctx->scratch.p;
+    double* fs = (double*)scratch.p();
     dim3 grid((unsigned)((n_cols + 63) / 64), (unsigned)num);
     if (dtype == DCTFP_F32)
         hipLaunchKernelGGL((generic_forward_kernel<float>), grid, dim3(64), 0, stream, (const float*)vec, n_rows, n_cols, ld, num, fs, coef_out);
@@ -1985,7 +2075,7 @@ int dctfp_idct_quant(dctfp_ctx* ctx, const void* vec, int32_t dtype, int64_t n_r
         hipLaunchKernelGGL(generic_inverse_kernel, dim3((unsigned)((n_cols + 63) / 64)), dim3(64), 0, stream, fs, n_cols, num, scaled_out);
         HIP_TRY(hipGetLastError());
     }
-    return DCTFP_OK;
+    return scratch.give_back();
 } DCTFP_GUARD("dctfp_idct_quant")
 
 int dctfp_scale(dctfp_ctx* ctx, const double* vec, int64_t n, double* out, void* stream_v) try {
@@ -2007,13 +2097,10 @@ int dctfp_gather_rows(dctfp_ctx* ctx, const void* embed, int32_t dtype, int64_t 
     hipStream_t stream = (hipStream_t)stream_v;
     HIP_TRY(hipSetDevice(ctx->device));
     const size_t esz = dtype == DCTFP_F32 ? 4 : 8;
-    const int buf = ctx->flip;
-    Staging& stg = ctx->staging[buf];
-    DevBuf& tab = ctx->tables[buf];
-    ctx->flip ^= 1;
-    int rc = stg.ensure((size_t)n_pieces * sizeof(PieceA));
+    TableLease tables(ctx->ring, stream);
+    int rc = tables.stage((size_t)n_pieces * sizeof(PieceA));
     if (rc) return rc;
-    PieceA* h = (PieceA*)stg.p;
+    PieceA* h = (PieceA*)tables.host();
     uint64_t t0 = 0;
     uint32_t max_rows = 0;
     for (int64_t i = 0; i < n_pieces; ++i) {
@@ -2027,21 +2114,15 @@ int dctfp_gather_rows(dctfp_ctx* ctx, const void* embed, int32_t dtype, int64_t 
         max_rows = std::max(max_rows, (uint32_t)pc.n_rows);
         if (t0 > 0x7fffffffu) return fail(DCTFP_ERR_LIMIT, "dctfp_gather_rows: more than 2^31 rows");
     }
-    rc = tab.ensure((size_t)n_pieces * sizeof(PieceA));
+    rc = tables.upload((size_t)n_pieces * sizeof(PieceA), stream);
     if (rc) return rc;
-    // (the table buffer may still be read by kernels another stream runs -- a flush's cutter on its side stream while the caller's
-    //  stream stitches the next proteins: overwrite it only behind them)
-    if (ctx->tab_busy[buf]) HIP_TRY(hipStreamWaitEvent(stream, ctx->ev_tab_free[buf], 0));
-    HIP_TRY(hipMemcpyAsync(tab.p, stg.p, (size_t)n_pieces * sizeof(PieceA), hipMemcpyHostToDevice, stream));
-    HIP_TRY(hipEventRecord(stg.ev, stream));
-    stg.pending = true;
     const unsigned gx = (unsigned)std::min<int64_t>(((int64_t)max_rows * n_cols + 255) / 256, 2048);
     if (dtype == DCTFP_F32)
-        hipLaunchKernelGGL((gather_rows_kernel<float>), dim3(gx, (unsigned)n_pieces), dim3(256), 0, stream, (const PieceA*)tab.p, (int)n_pieces, n_cols, ld, out);
+        hipLaunchKernelGGL((gather_rows_kernel<float>), dim3(gx, (unsigned)n_pieces), dim3(256), 0, stream, (const PieceA*)tables.dev(), (int)n_pieces, n_cols, ld, out);
     else
-        hipLaunchKernelGGL((gather_rows_kernel<double>), dim3(gx, (unsigned)n_pieces), dim3(256), 0, stream, (const PieceA*)tab.p, (int)n_pieces, n_cols, ld, out);
+        hipLaunchKernelGGL((gather_rows_kernel<double>), dim3(gx, (unsigned)n_pieces), dim3(256), 0, stream, (const PieceA*)tables.dev(), (int)n_pieces, n_cols, ld, out);
     HIP_TRY(hipGetLastError());
-    return mark_table_used(ctx, buf, stream);
+    return tables.release();
 } DCTFP_GUARD("dctfp_gather_rows")
 
 
@@ -2101,16 +2182,14 @@ int dctfp_contact_topk(dctfp_ctx* ctx, const void* const* maps, const int64_t* l
     const size_t up_bytes = align_up(off_state + (size_t)n_long * sizeof(TopkState), 16);
     const size_t off_ties = up_bytes;
     const size_t all_bytes = off_ties + (size_t)n_stripes * sizeof(int32_t);
-    const int buf = ctx->flip;
-    Staging& stg = ctx->staging[buf];
-    DevBuf& tab = ctx->tables[buf];
-    ctx->flip ^= 1;
-    int rc = stg.ensure(up_bytes);
+    TableLease tables(ctx->ring, stream);
+    Fork fork(stream);
+    int rc = tables.stage(up_bytes);
     if (rc) return rc;
-    TopkJob* h = (TopkJob*)stg.p;
-    TopkStripe* hs = (TopkStripe*)((char*)stg.p + off_stripe);
-    int32_t* hfirst = (int32_t*)((char*)stg.p + off_first);
-    TopkState* hstate = (TopkState*)((char*)stg.p + off_state);
+    TopkJob* h = (TopkJob*)tables.host();
+    TopkStripe* hs = (TopkStripe*)(tables.host() + off_stripe);
+    int32_t* hfirst = (int32_t*)(tables.host() + off_first);
+    TopkState* hstate = (TopkState*)(tables.host() + off_state);
     int64_t s_fill = 0;
     for (int32_t q = 0; q < n_prot; ++q) {
         const int32_t p = order[q];
@@ -2153,27 +2232,21 @@ int dctfp_contact_topk(dctfp_ctx* ctx, const void* const* maps, const int64_t* l
         }
     }
     const int64_t used_stripes = s_fill;  // (a stripe can come out empty when rows are long: it is simply not emitted)
-    rc = tab.ensure(all_bytes);
+    rc = tables.upload(up_bytes, stream, all_bytes);
     if (rc) return rc;
-    // (the table buffer may still be read by kernels another stream runs -- a flush's cutter on its side stream while the caller's
-    //  stream stitches the next proteins: overwrite it only behind them)
-    if (ctx->tab_busy[buf]) HIP_TRY(hipStreamWaitEvent(stream, ctx->ev_tab_free[buf], 0));
-    HIP_TRY(hipMemcpyAsync(tab.p, stg.p, up_bytes, hipMemcpyHostToDevice, stream));
-    HIP_TRY(hipEventRecord(stg.ev, stream));
-    stg.pending = true;
-    const TopkJob* djobs = (const TopkJob*)tab.p;
+    const TopkJob* djobs = (const TopkJob*)tables.dev();
     // The selection of the long proteins (stripes: four histogram passes, the collection, the ties) and that of the short ones
     // (one workgroup each: one read, what it hands back, ...) touch different proteins: they run side by side -- the long chain on
     // a stream of its own, forked here (the tables are up) and joined before the caller's stream goes on.  A flush of 2 048
     // proteins spent 2.8 ms in the two chains one after the other, 0.9 ms of kernels each and a dozen launch gaps
     // (profiles/r05/flush_kernel_stats_tiefree.txt).
     const bool long_beside = n_long > 0 && used_stripes > 0 && n_short > 0;
-    const hipStream_t short_stream = stream;
+    hipStream_t long_stream = stream;
     if (long_beside) {
         rc = ctx->ensure_cut_streams();
+        if (rc == DCTFP_OK) rc = fork.fork(ctx->cut_fork);
+        if (rc == DCTFP_OK) rc = fork.branch(ctx->cut[0], &long_stream);
         if (rc) return rc;
-        HIP_TRY(hipEventRecord(ctx->cut_ev[0], stream));
-        HIP_TRY(hipStreamWaitEvent(ctx->cut_stream[0], ctx->cut_ev[0], 0));
     }
     if (n_short > 0) {
         if (ctx->opt_topk_kernel != 1) {   // one read of the map (0; 2 = straight to the two-read kernel of round 4); what a kernel hands
@@ -2196,13 +2269,13 @@ int dctfp_contact_topk(dctfp_ctx* ctx, const void* const* maps, const int64_t* l
         }
         HIP_TRY(hipGetLastError());
     }
-    if (long_beside) stream = ctx->cut_stream[0];
     if (n_long > 0 && used_stripes > 0) {
+        stream = long_stream;
         const TopkJob* dlong = djobs + n_short;
-        const TopkStripe* dstripes = (const TopkStripe*)((char*)tab.p + off_stripe);
-        const int32_t* dfirst = (const int32_t*)((char*)tab.p + off_first);
-        TopkState* dstate = (TopkState*)((char*)tab.p + off_state);
-        int32_t* dties = (int32_t*)((char*)tab.p + off_ties);
+        const TopkStripe* dstripes = (const TopkStripe*)(tables.dev() + off_stripe);
+        const int32_t* dfirst = (const int32_t*)(tables.dev() + off_first);
+        TopkState* dstate = (TopkState*)(tables.dev() + off_state);
+        int32_t* dties = (int32_t*)(tables.dev() + off_ties);
         for (int shift = 24; shift >= 0; shift -= 8) {
             hipLaunchKernelGGL(topk_hist_kernel, dim3((unsigned)used_stripes), dim3(1024), 0, stream, dlong, dstripes, dstate, shift);
             hipLaunchKernelGGL(topk_pick_kernel, dim3((unsigned)n_long), dim3(64), 0, stream, dlong, dstate, shift, out_n);
@@ -2213,12 +2286,8 @@ int dctfp_contact_topk(dctfp_ctx* ctx, const void* const* maps, const int64_t* l
                            out_i, out_j, out_v);
         HIP_TRY(hipGetLastError());
     }
-    if (long_beside) {
-        HIP_TRY(hipEventRecord(ctx->cut_ev[1], stream));
-        stream = short_stream;
-        HIP_TRY(hipStreamWaitEvent(stream, ctx->cut_ev[1], 0));
-    }
-    return mark_table_used(ctx, buf, stream);
+    rc = fork.join();
+    return rc ? rc : tables.release();
 } DCTFP_GUARD("dctfp_contact_topk")
 
 // The order of the CON line (src/fingerprint.py:58-61) on the device: see include/dctfp.h.
@@ -2250,15 +2319,10 @@ int dctfp_contact_sort(dctfp_ctx* ctx, const void* const* maps, const int64_t* l
     }
     const size_t n_jobs = group[0].size() + group[1].size() + group[2].size() + group[3].size();
     if (n_jobs == 0) return DCTFP_OK;
-    const int buf = ctx->flip;
-    Staging& stg = ctx->staging[buf];
-    DevBuf& tab = ctx->tables[buf];
-    ctx->flip ^= 1;
-    int rc = stg.ensure(n_jobs * sizeof(TopkJob));
+    TableLease tables(ctx->ring, stream);
+    int rc = tables.stage(n_jobs * sizeof(TopkJob));
     if (rc) return rc;
-    rc = tab.ensure(n_jobs * sizeof(TopkJob));
-    if (rc) return rc;
-    TopkJob* h = (TopkJob*)stg.p;
+    TopkJob* h = (TopkJob*)tables.host();
     size_t q = 0;
     for (int g = 0; g < 4; ++g)
         for (int32_t p : group[g]) {
@@ -2271,11 +2335,9 @@ int dctfp_contact_sort(dctfp_ctx* ctx, const void* const* maps, const int64_t* l
             h[q].reserved = 0;
             ++q;
         }
-    if (ctx->tab_busy[buf]) HIP_TRY(hipStreamWaitEvent(stream, ctx->ev_tab_free[buf], 0));
-    HIP_TRY(hipMemcpyAsync(tab.p, stg.p, n_jobs * sizeof(TopkJob), hipMemcpyHostToDevice, stream));
-    HIP_TRY(hipEventRecord(stg.ev, stream));
-    stg.pending = true;
-    const TopkJob* d = (const TopkJob*)tab.p;
+    rc = tables.upload(n_jobs * sizeof(TopkJob), stream);
+    if (rc) return rc;
+    const TopkJob* d = (const TopkJob*)tables.dev();
     size_t first = 0;
     for (int g = 0; g < 4; ++g) {
         const unsigned n = (unsigned)group[g].size();
@@ -2287,7 +2349,7 @@ int dctfp_contact_sort(dctfp_ctx* ctx, const void* const* maps, const int64_t* l
         HIP_TRY(hipGetLastError());
         first += n;
     }
-    return mark_table_used(ctx, buf, stream);
+    return tables.release();
 } DCTFP_GUARD("dctfp_contact_sort")
 
 int64_t dctfp_reccut_room(int32_t n_res) {
@@ -2330,22 +2392,17 @@ int dctfp_reccut(dctfp_ctx* ctx, const int32_t* n_res, int32_t n_prot, const int
     }
     const size_t stack_ints = (size_t)kCutStack * kCutNodeInts;
     const size_t ws_bytes = align_up(adj_total * sizeof(uint32_t), 16) + (size_t)n_prot * stack_ints * sizeof(int32_t);
-    int rc = ctx->cut_ws.ensure(ws_bytes);
-    if (rc) return rc;
     // (adjacency lists and node stacks are the context's: a call on another stream waits for the kernels of the last one)
-    if (!ctx->ev_cut_ws_free) HIP_TRY(hipEventCreateWithFlags(&ctx->ev_cut_ws_free, hipEventDisableTiming));
-    if (ctx->cut_ws_busy) HIP_TRY(hipStreamWaitEvent((hipStream_t)stream_v, ctx->ev_cut_ws_free, 0));
-    const int buf = ctx->flip;
-    Staging& stg = ctx->staging[buf];
-    DevBuf& tab = ctx->tables[buf];
-    ctx->flip ^= 1;
-    rc = stg.ensure((size_t)n_prot * sizeof(CutJob));
+    Hold cut_ws{ctx->cut_ws, stream};
+    int rc = cut_ws.take(ws_bytes, stream);
     if (rc) return rc;
-    rc = tab.ensure((size_t)n_prot * sizeof(CutJob));
+    TableLease tables(ctx->ring, stream);
+    Fork fork(stream);
+    rc = tables.stage((size_t)n_prot * sizeof(CutJob));
     if (rc) return rc;
-    CutJob* h = (CutJob*)stg.p;
-    uint32_t* adj = (uint32_t*)ctx->cut_ws.p;
-    int32_t* stacks = (int32_t*)((char*)ctx->cut_ws.p + align_up(adj_total * sizeof(uint32_t), 16));
+    CutJob* h = (CutJob*)tables.host();
+    uint32_t* adj = (uint32_t*)cut_ws.p();
+    int32_t* stacks = (int32_t*)((char*)cut_ws.p() + align_up(adj_total * sizeof(uint32_t), 16));
     size_t adj_at = 0;
     for (int32_t q = 0; q < n_prot; ++q) {
         const int32_t p = order[(size_t)q];
@@ -2367,13 +2424,9 @@ int dctfp_reccut(dctfp_ctx* ctx, const int32_t* n_res, int32_t n_prot, const int
         j.out_cap = (int32_t)std::min<int64_t>(out_offs[p + 1] - out_offs[p], 0x7fffffff);
         j.reserved = 0;
     }
-    // (the table buffer may still be read by kernels another stream runs -- a flush's cutter on its side stream while the caller's
-    //  stream stitches the next proteins: overwrite it only behind them)
-    if (ctx->tab_busy[buf]) HIP_TRY(hipStreamWaitEvent(stream, ctx->ev_tab_free[buf], 0));
-    HIP_TRY(hipMemcpyAsync(tab.p, stg.p, (size_t)n_prot * sizeof(CutJob), hipMemcpyHostToDevice, stream));
-    HIP_TRY(hipEventRecord(stg.ev, stream));
-    stg.pending = true;
-    const CutJob* d = (const CutJob*)tab.p;
+    rc = tables.upload((size_t)n_prot * sizeof(CutJob), stream);
+    if (rc) return rc;
+    const CutJob* d = (const CutJob*)tables.dev();
     // A class's launch lasts as long as its slowest protein (one workgroup each): the larger classes run on streams of their
     // own beside the small one, and the caller's stream continues after all of them.
     int n_used = 0;
@@ -2381,16 +2434,17 @@ int dctfp_reccut(dctfp_ctx* ctx, const int32_t* n_res, int32_t n_prot, const int
     const bool beside = n_used > 1;
     if (beside) {
         rc = ctx->ensure_cut_streams();
+        if (rc == DCTFP_OK) rc = fork.fork(ctx->cut_fork);
         if (rc) return rc;
-        HIP_TRY(hipEventRecord(ctx->cut_ev[0], stream));
     }
     // (the small class first: its many short workgroups fill the chip three per CU and drain within a few hundred microseconds; the
     //  long classes, on high-priority streams, take the CUs as they come free.  The other way round the 80-155 KB workgroups of the
     //  long classes held the LDS of most CUs and the small class ran in what was left: 3.3 ms for kernels of 1.8 / 1.7 / 0.8 ms)
     for (int c = 0; c < kCutClasses; ++c) {
         if (count[c] == 0) continue;
-        hipStream_t s = beside && c > 0 ? ctx->cut_stream[c - 1] : stream;
-        if (s != stream) HIP_TRY(hipStreamWaitEvent(s, ctx->cut_ev[0], 0));
+        hipStream_t s = stream;
+        if (beside && c > 0) rc = fork.branch(ctx->cut[c - 1], &s);
+        if (rc) return rc;
         for (int32_t done = 0; done < count[c]; done += 65535 * 16) {
             const unsigned n = (unsigned)std::min<int32_t>(count[c] - done, 65535 * 16);
             LaunchError le;
@@ -2398,14 +2452,11 @@ int dctfp_reccut(dctfp_ctx* ctx, const int32_t* n_res, int32_t n_prot, const int
             if (rc) return rc;
             HIP_TRY(hipGetLastError());
         }
-        if (s != stream) {
-            HIP_TRY(hipEventRecord(ctx->cut_ev[c], s));
-            HIP_TRY(hipStreamWaitEvent(stream, ctx->cut_ev[c], 0));
-        }
+        rc = fork.join();
+        if (rc) return rc;
     }
-    HIP_TRY(hipEventRecord(ctx->ev_cut_ws_free, stream));
-    ctx->cut_ws_busy = true;
-    return mark_table_used(ctx, buf, stream);
+    rc = cut_ws.give_back();
+    return rc ? rc : tables.release();
 } DCTFP_GUARD("dctfp_reccut")
 
 }  // extern "C"
@@ -2439,16 +2490,11 @@ int stitch_impl(dctfp_ctx* ctx, const dctfp_stitch_job* jobs, int64_t n_jobs, in
         max_level = std::max(max_level, j.level);
     }
     if (once) max_level = 0;   // every window in the one launch
-    const int buf = ctx->flip;
-    Staging& stg = ctx->staging[buf];
-    DevBuf& tab = ctx->tables[buf];
-    ctx->flip ^= 1;
-    int rc = stg.ensure((size_t)n_jobs * sizeof(StitchJob));
-    if (rc) return rc;
-    rc = tab.ensure((size_t)n_jobs * sizeof(StitchJob));
+    TableLease tables(ctx->ring, stream);
+    int rc = tables.stage((size_t)n_jobs * sizeof(StitchJob));
     if (rc) return rc;
     // bucket the windows by level (stable), one launch per level in ascending order
-    StitchJob* h = (StitchJob*)stg.p;
+    StitchJob* h = (StitchJob*)tables.host();
     std::vector<int64_t> start((size_t)max_level + 2, 0);
     for (int64_t i = 0; i < n_jobs; ++i) start[(size_t)(once ? 0 : jobs[i].level) + 1] += 1;
     for (int32_t l = 0; l <= max_level; ++l) start[(size_t)l + 1] += start[(size_t)l];
@@ -2470,13 +2516,9 @@ int stitch_impl(dctfp_ctx* ctx, const dctfp_stitch_job* jobs, int64_t n_jobs, in
         o.reserved = 0;
         max_rows[(size_t)level] = std::max(max_rows[(size_t)level], j.n_rows);
     }
-    // (the table buffer may still be read by kernels another stream runs -- a flush's cutter on its side stream while the caller's
-    //  stream stitches the next proteins: overwrite it only behind them)
-    if (ctx->tab_busy[buf]) HIP_TRY(hipStreamWaitEvent(stream, ctx->ev_tab_free[buf], 0));
-    HIP_TRY(hipMemcpyAsync(tab.p, stg.p, (size_t)n_jobs * sizeof(StitchJob), hipMemcpyHostToDevice, stream));
-    HIP_TRY(hipEventRecord(stg.ev, stream));
-    stg.pending = true;
-    const StitchJob* d = (const StitchJob*)tab.p;
+    rc = tables.upload((size_t)n_jobs * sizeof(StitchJob), stream);
+    if (rc) return rc;
+    const StitchJob* d = (const StitchJob*)tables.dev();
     for (int32_t l = 0; l <= max_level; ++l) {
         int64_t cnt = start[(size_t)l + 1] - start[(size_t)l];
         int64_t done = 0;
@@ -2490,7 +2532,7 @@ int stitch_impl(dctfp_ctx* ctx, const dctfp_stitch_job* jobs, int64_t n_jobs, in
             done += ny;
         }
     }
-    return mark_table_used(ctx, buf, stream);
+    return tables.release();
 }
 
 }  // namespace
@@ -2604,6 +2646,7 @@ int dctfp_row_select(dctfp_ctx* ctx, const int32_t* dist, int64_t n_rows, int64_
     if (n_rows > 0x7fffffff) return fail(DCTFP_ERR_LIMIT, "dctfp_row_select: too many rows");
     HIP_TRY(hipSetDevice(ctx->device));
     hipStream_t stream = (hipStream_t)stream_v;
+    Hold scratch{ctx->scratch, stream};   // (given back when the candidates were used: the destructor)
     // The row (or a segment of it) in the registers of one workgroup, read once (row_select_reg_kernel); longer rows in segments
     // whose k candidates each a second launch selects from.  Large k, or more candidates than one workgroup holds: the radix
     // select, which reads its row six times but has no limit.
@@ -2616,9 +2659,9 @@ int dctfp_row_select(dctfp_ctx* ctx, const int32_t* dist, int64_t n_rows, int64_
                            ld, n_cols, kSeg, (int64_t)1, (int)k, out_val, out_idx);
     } else if (reg_ok) {
         const int64_t n_in = n_seg * k;                       // candidates per row
-        int rc = ctx->scratch.ensure((size_t)n_rows * n_in * 2 * sizeof(int32_t));
+        int rc = scratch.take((size_t)n_rows * n_in * 2 * sizeof(int32_t), stream);
         if (rc) return rc;
-        int32_t* cand_val = (int32_t*)ctx->scratch.p;
+        int32_t* cand_val = (int32_t*)scratch.p();
         int32_t* cand_idx = cand_val + (size_t)n_rows * n_in;
         hipLaunchKernelGGL((row_select_reg_kernel<2 * kPer, false, 512>), dim3((unsigned)(n_rows * n_seg)), dim3(512), 0, stream, dist,
                            (const int32_t*)nullptr, ld, n_cols, kSeg, n_seg, (int)k, cand_val, cand_idx);
@@ -2628,7 +2671,7 @@ int dctfp_row_select(dctfp_ctx* ctx, const int32_t* dist, int64_t n_rows, int64_
         hipLaunchKernelGGL(row_select_kernel, dim3((unsigned)n_rows), dim3(1024), 0, stream, dist, ld, n_cols, k, out_val, out_idx);
     }
     HIP_TRY(hipGetLastError());
-    return DCTFP_OK;
+    return scratch.armed ? scratch.give_back() : DCTFP_OK;
 } DCTFP_GUARD("dctfp_row_select")
 
 int dctfp_row_order(dctfp_ctx* ctx, int32_t* val, int32_t* idx, int64_t n_rows, int32_t k, void* stream_v) try {

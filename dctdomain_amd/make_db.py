@@ -100,9 +100,6 @@ LAST_PATH = [None]
 
 _SEQ, _CONTACTS, _EMBED, _DOMAINS, _QUANTS, _PID = (_attrgetter(a) for a in ('seq', 'contacts', 'embed', 'domains', 'quants', 'pid'))
 _SIDE_STREAMS = {}
-#: which of the two sets of page-locked result buffers the next flush takes (two flushes are alive at a time in process_sequences: the one
-#: whose cutter runs and the one being finished; the buffers themselves are per thread, reccut._pinned)
-_FLUSH_SLOT = [0]
 
 
 def _side_stream(device):
@@ -124,7 +121,9 @@ class _Flush:
                   ``Fingerprint`` as ``queue_cpu`` does (int64 rows, the reference's dtype) and returns the list;
                   ``objects=False`` returns what the writer stores -- (pid, domains, int8 rows) -- and leaves the objects alone.
 
-    Both return None / False where the flush is not of the plain kind; the caller then runs ``_fingerprint_batch_generic``."""
+    Both return None / False where the flush is not of the plain kind; the caller then runs ``_fingerprint_batch_generic``.
+    A flush owns its page-locked result buffers from ``start()`` to the end of ``finish()``: any number of flushes may be
+    started before the first is finished, and finished in any order."""
 
     def __init__(self, fps, threads=1, qdim=QDIM, threshold=THRESHOLD):
         self.fps, self.threads, self.qdim, self.threshold = fps, max(1, threads), list(qdim), threshold
@@ -160,11 +159,10 @@ class _Flush:
         _mark('maps')
         ctx = _lib_mod().get_context(device.index)
         self.ctx, self.device = ctx, device
-        slot = _FLUSH_SLOT[0] = _FLUSH_SLOT[0] ^ 1
         main = torch.cuda.current_stream(device)
         stream = _side_stream(device)
         stream.wait_stream(main)               # (the maps were written on the caller's stream)
-        self.cut = reccut.CutInFlight(ptrs, lds, lens.astype(np.int32), device, self.threshold, stream=stream, slot=slot,
+        self.cut = reccut.CutInFlight(ptrs, lds, lens.astype(np.int32), device, self.threshold, stream=stream,
                                       timing=MARKS is not None)
         self._maps = cts
         _mark('enqueued top-k + cutter')
@@ -189,7 +187,7 @@ class _Flush:
 
     def _abandon(self):
         if self.cut is not None:
-            self.cut.done.synchronize()        # (its buffers are this thread's: nothing may still be writing them)
+            self.cut.release()
             self.cut = None
         return False
 
@@ -197,8 +195,6 @@ class _Flush:
         from .batch import PieceTable, quantize_batch
         fps, n, lens = self.fps, len(self.fps), self.lens
         lib = _lib_mod().load()
-        enc = self.cut.wait()
-        _mark('cutter waited for')
         enc_off = self.cut.enc_off
         n_enc = int(enc_off[-1])
         # (segments + proteins bound the pieces; 24 bytes per segment + 32 per protein the text: an encoded record spends two
@@ -209,10 +205,14 @@ class _Flush:
         text = np.empty(text_cap, dtype=np.uint8)
         counts = np.empty(n, dtype=np.int32)
         text_len, n_pieces, n_dom, n_undone = C.c_int64(), C.c_int64(), C.c_int64(), C.c_int64()
-        enc = np.ascontiguousarray(enc)
-        _lib_mod().check(lib.dctfp_reccut_pieces(n, enc.ctypes.data, enc_off.ctypes.data, lens.ctypes.data, text.ctypes.data, text_cap,
-                                                C.byref(text_len), counts.ctypes.data, pieces.ctypes.data, piece_cap, C.byref(n_pieces),
-                                                C.byref(n_dom), C.byref(n_undone)), lib)
+        try:
+            enc = np.ascontiguousarray(self.cut.wait())
+            _mark('cutter waited for')
+            _lib_mod().check(lib.dctfp_reccut_pieces(n, enc.ctypes.data, enc_off.ctypes.data, lens.ctypes.data, text.ctypes.data, text_cap,
+                                                    C.byref(text_len), counts.ctypes.data, pieces.ctypes.data, piece_cap, C.byref(n_pieces),
+                                                    C.byref(n_dom), C.byref(n_undone)), lib)
+        finally:
+            self.cut.release()                 # (the results are decoded: the page-locked buffers go back to the free list)
         if n_undone.value:
             return None                        # (a protein whose strings Python's own parser must judge: never seen; the general path)
         flat = text[:text_len.value].tobytes().decode('ascii').split(';')

@@ -59,6 +59,20 @@ def _pinned(name: str, dtype, n: int) -> torch.Tensor:
     return buf[:n]
 
 
+def _pinned_take(name: str, dtype, n: int) -> torch.Tensor:
+    """A page-locked buffer of at least ``n`` elements from this thread's free list ``name`` (grown as ``_pinned`` grows its
+    own), owned by the caller until ``_pinned_give`` puts it back."""
+    free = _PINNED.__dict__.setdefault('free_' + name, [])
+    buf = free.pop() if free else None
+    if buf is None or buf.numel() < n:
+        buf = torch.empty(max(n + n // 2, 1 << 16), dtype=dtype, pin_memory=True)
+    return buf
+
+
+def _pinned_give(name: str, buf: torch.Tensor):
+    _PINNED.__dict__.setdefault('free_' + name, []).append(buf)
+
+
 def top_contacts_batch(maps: Sequence[torch.Tensor], t: float, sort: bool = True, own: bool = True):
     """Top ``int(t*L)`` contacts of each map.  Returns (offs, i, j, v) as numpy arrays: protein
     p's contacts are ``[offs[p], offs[p+1])``; with ``sort`` they are ordered by (-v, i, j) -- the
@@ -209,9 +223,11 @@ def reccut_room(n_res: np.ndarray) -> np.ndarray:
 class CutInFlight:
     """Contact selection + domain cutter of a batch, enqueued on ``stream`` (``dctfp_contact_topk`` + ``dctfp_reccut``), the
     encoded results on their way into a page-locked buffer: what a database flush starts early and picks up when it needs
-    the domains (``make_db._Flush``).  ``ptrs`` / ``lds`` / ``n_res``: the contact maps' geometry (``_geom.tensor_table``)."""
+    the domains (``make_db._Flush``).  ``ptrs`` / ``lds`` / ``n_res``: the contact maps' geometry (``_geom.tensor_table``).
+    Its page-locked result buffers are its own, from this thread's free list, until ``release()``: any number of batches may be
+    in flight at once."""
 
-    def __init__(self, ptrs, lds, n_res, device, t: float, cut1=CUT1_DEFAULT, cut2=CUT2_DEFAULT, stream=None, slot: int = 0,
+    def __init__(self, ptrs, lds, n_res, device, t: float, cut1=CUT1_DEFAULT, cut2=CUT2_DEFAULT, stream=None,
                  timing: bool = False):
         lib = _lib.load()
         self.events = [torch.cuda.Event(enable_timing=True) for _ in range(4)] if timing else None    # (tools/flush_timeline.py)
@@ -251,9 +267,9 @@ class CutInFlight:
                                         self.offs.ctypes.data, self.cut1, self.cut2, enc.data_ptr(), self.enc_off.ctypes.data, sp), lib)
             if timing:
                 self.events[2].record(self.stream)
-            self.penc = _pinned(f'enc{slot}', torch.int32, n_enc)
+            self._pins = (_pinned_take('enc', torch.int32, n_enc), _pinned_take('n', torch.int32, n))
+            self.penc, self.pn = self._pins[0][:n_enc], self._pins[1][:n]
             self.penc.copy_(enc, non_blocking=True)
-            self.pn = _pinned(f'n{slot}', torch.int32, n)
             self.pn.copy_(on, non_blocking=True)
             if timing:
                 self.events[3].record(self.stream)
@@ -262,8 +278,8 @@ class CutInFlight:
         self._keep = (enc, on)
 
     def wait(self) -> np.ndarray:
-        """The encoded results (host view, valid until this thread's next batch in the same slot); proteins the GPU cutter
-        handed back (status -1) are redone by the host library here and written into the same encoding."""
+        """The encoded results (host view, valid until ``release()``); proteins the GPU cutter handed back (status -1) are
+        redone by the host library here and written into the same encoding."""
         self.done.synchronize()
         if self.events is not None:
             e = self.events
@@ -287,6 +303,14 @@ class CutInFlight:
                 if rec is not None and len(rec) <= b - a:
                     enc[a:a + len(rec)] = rec           # (else: status stays -1 and the caller parses the strings itself)
         return enc
+
+    def release(self):
+        """Waits for the copies into the page-locked result buffers and puts those back on this thread's free list."""
+        if self._pins is not None:
+            self.done.synchronize()
+            _pinned_give('enc', self._pins[0])
+            _pinned_give('n', self._pins[1])
+            self._pins = self.penc = self.pn = None
 
 
 def _encode_domains(doms: List[str]):

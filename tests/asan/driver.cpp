@@ -15,6 +15,10 @@
 #include "dctfp.h"
 
 extern "C" unsigned long dctfp_stub_counter(int which);
+extern "C" void* stub_new_stream();
+extern "C" void stub_call_begin();
+extern "C" long stub_call_end(void* stream);
+extern "C" unsigned long stub_fail_launch(long n);
 
 // ---- allocation-failure hook: the N-th operator new from now on throws std::bad_alloc (once).  Nothing may throw across
 // the C ABI -- an exception that left dctfp_quantize would end this process in std::terminate (SIGABRT on the calling
@@ -61,6 +65,38 @@ void operator delete[](void* p, std::align_val_t, const std::nothrow_t&) noexcep
         }                                                                                   \
     } while (0)
 
+// ---- stream order and launch failures (hip_stub.cpp).  Every call runs on the caller's stream of the moment -- the null stream
+// or one of two others, in turn -- and must leave nothing running on another stream that this one is not ordered after: the
+// context's own streams are joined back before a call returns, on its error paths too.  Where `inject` is set, one kernel launch
+// of the call fails now and then, and the call must come back as DCTFP_ERR_HIP.  (Decisions from a generator of their own: the
+// seeded shapes of the batches stay what they were.)
+static void* g_streams[3];
+static void* g_stream = nullptr;
+static unsigned long g_rotation = 0;
+static std::mt19937_64 g_aux;
+static bool g_launch_failed = false;   // the last call's injected launch failure fired
+static int g_stream_errors = 0;
+static long g_launch_failures = 0;
+template <typename F>
+static int call(const char* name, F f, bool inject = false) {
+    g_stream = g_streams[g_rotation++ % 3];
+    const unsigned long fired = stub_fail_launch(inject && g_aux() % 4 == 0 ? (long)(g_aux() % 8) : -1);
+    stub_call_begin();
+    const int rc = f();
+    const long unjoined = stub_call_end(g_stream);
+    g_launch_failed = stub_fail_launch(-1) != fired;
+    g_launch_failures += g_launch_failed ? 1 : 0;
+    if (unjoined) {
+        fprintf(stderr, "%s (rc %d): %ld operations left on other streams the caller's stream is not ordered after\n", name, rc, unjoined);
+        ++g_stream_errors;
+    }
+    if (g_launch_failed && rc != DCTFP_ERR_HIP) {
+        fprintf(stderr, "%s: an injected launch failure came back as %d\n", name, rc);
+        ++g_stream_errors;
+    }
+    return rc;
+}
+
 // ---- the entry points either side of dctfp_quantize: argument checks, table builds (top-k jobs and stripes, sorting-network
 // groups, window jobs by level and in the one-launch form, candidate scratch of the row select), the host-only parsers.  The
 // kernels themselves are no-ops under the stub; what runs is every line of host code, with allocation failures injected.
@@ -69,7 +105,8 @@ static int other_entry_points(dctfp_ctx* ctx, std::mt19937_64& rng, int rounds, 
     auto ok_or_expected = [&](int rc, const char* what) {
         ++*n_calls;
         if (rc == DCTFP_OK) return true;
-        if (rc == DCTFP_ERR_NOMEM || rc == DCTFP_ERR_SHAPE || rc == DCTFP_ERR_INVALID || rc == DCTFP_ERR_LIMIT || rc == DCTFP_ERR_UNSUPPORTED) { ++*n_expected; return true; }
+        if (rc == DCTFP_ERR_NOMEM || rc == DCTFP_ERR_SHAPE || rc == DCTFP_ERR_INVALID || rc == DCTFP_ERR_LIMIT || rc == DCTFP_ERR_UNSUPPORTED ||
+            (rc == DCTFP_ERR_HIP && g_launch_failed)) { ++*n_expected; return true; }
         fprintf(stderr, "%s -> %d: %s\n", what, rc, dctfp_last_error());
         return false;
     };
@@ -191,11 +228,13 @@ static int other_entry_points(dctfp_ctx* ctx, std::mt19937_64& rng, int rounds, 
             std::vector<float> ov(total);
             std::vector<uint8_t> sorted(n_prot);
             if (starve) g_fail_after = uni(0, 10);
-            int rc = dctfp_contact_topk(ctx, ptrs.data(), ld.data(), n_res.data(), n_prot, t, oi.data(), oj.data(), ov.data(), offs.data(), on.data(), nullptr);
+            int rc = call("dctfp_contact_topk", [&] { return dctfp_contact_topk(ctx, ptrs.data(), ld.data(), n_res.data(), n_prot, t, oi.data(), oj.data(), ov.data(),
+                                                                                offs.data(), on.data(), g_stream); }, true);
             g_fail_after = -1;
             if (!ok_or_expected(rc, "dctfp_contact_topk")) return 1;
             if (starve) g_fail_after = uni(0, 10);
-            rc = dctfp_contact_sort(ctx, ptrs.data(), ld.data(), n_res.data(), n_prot, t, oi.data(), oj.data(), ov.data(), offs.data(), sorted.data(), nullptr);
+            rc = call("dctfp_contact_sort", [&] { return dctfp_contact_sort(ctx, ptrs.data(), ld.data(), n_res.data(), n_prot, t, oi.data(), oj.data(), ov.data(),
+                                                                            offs.data(), sorted.data(), g_stream); });
             g_fail_after = -1;
             if (!ok_or_expected(rc, "dctfp_contact_sort")) return 1;
             // ---- the domain cutter on the selected contacts: job table, scratch sizes, the three size classes on their streams
@@ -203,9 +242,21 @@ static int other_entry_points(dctfp_ctx* ctx, std::mt19937_64& rng, int rounds, 
             for (int p = 0; p < n_prot; ++p) enc_off[p + 1] = enc_off[p] + dctfp_reccut_room(n_res[p]) - (uni(0, 30) == 0 ? 100 : 0);   // (sometimes no room: an error)
             std::vector<int32_t> enc((size_t)std::max<int64_t>(enc_off[n_prot], 1));
             if (starve) g_fail_after = uni(0, 8);
-            rc = enc_off[n_prot] >= 0 ? dctfp_reccut(ctx, n_res.data(), n_prot, oi.data(), oj.data(), ov.data(), offs.data(), 0.08, 0.07, enc.data(), enc_off.data(), nullptr)
+            rc = enc_off[n_prot] >= 0 ? call("dctfp_reccut", [&] { return dctfp_reccut(ctx, n_res.data(), n_prot, oi.data(), oj.data(), ov.data(), offs.data(), 0.08,
+                                                                                   0.07, enc.data(), enc_off.data(), g_stream); }, true)
                                       : DCTFP_OK;
             g_fail_after = -1;
+            if (!ok_or_expected(rc, "dctfp_reccut")) return 1;
+            // ... and proteins of every size class without contacts (the generator of `call`): three classes on the context's streams
+            std::vector<int32_t> cls_res;
+            for (int c = 0; c < 4; ++c)
+                for (int i = (int)(g_aux() % 3); i > 0; --i) cls_res.push_back(512 * c + 1 + (int32_t)(g_aux() % 512));
+            const int n_cls = (int)cls_res.size();
+            std::vector<int64_t> no_contacts(n_cls + 1, 0), cls_off(n_cls + 1, 0);
+            for (int p = 0; p < n_cls; ++p) cls_off[p + 1] = cls_off[p] + dctfp_reccut_room(cls_res[p]);
+            std::vector<int32_t> cls_enc((size_t)std::max<int64_t>(cls_off[n_cls], 1));
+            rc = call("dctfp_reccut", [&] { return dctfp_reccut(ctx, cls_res.data(), n_cls, nullptr, nullptr, nullptr, no_contacts.data(), 0.08, 0.07,
+                                                                cls_enc.data(), cls_off.data(), g_stream); }, true);
             if (!ok_or_expected(rc, "dctfp_reccut")) return 1;
         }
         // ---- Fingerprint.quantize over windows: the geometry of every piece (one window's rows / the rows two windows share), the
@@ -281,8 +332,8 @@ static int other_entry_points(dctfp_ctx* ctx, std::mt19937_64& rng, int rounds, 
             const int path = uni(0, 2);
             if (dctfp_set_option(ctx, "path", path) != DCTFP_OK) return 1;
             if (starve) g_fail_after = uni(0, 30);
-            rc = dctfp_quantize_windows(ctx, layers.data(), n_layers, n_seq, seq_win.data(), win_rows.data(), overlap, pieces.data(), (int64_t)pieces.size(),
-                                        n_domains, out.data(), off, nullptr);
+            rc = call("dctfp_quantize_windows", [&] { return dctfp_quantize_windows(ctx, layers.data(), n_layers, n_seq, seq_win.data(), win_rows.data(), overlap,
+                                                                                    pieces.data(), (int64_t)pieces.size(), n_domains, out.data(), off, g_stream); }, true);
             g_fail_after = -1;
             if (dctfp_set_option(ctx, "path", 0) != DCTFP_OK) return 1;
             for (int l = 0; l < n_layers; ++l)
@@ -326,7 +377,8 @@ static int other_entry_points(dctfp_ctx* ctx, std::mt19937_64& rng, int rounds, 
                     dp[s] = outs[s].data();
                 }
                 if (starve) g_fail_after = uni(0, 8);
-                rc = dctfp_stitch_sequences(ctx, wp.data(), win_rows.data(), win_ld.data(), seq_win.data(), n_seq, dp.data(), dld.data(), n_cols, step, square, nullptr);
+                rc = call("dctfp_stitch_sequences", [&] { return dctfp_stitch_sequences(ctx, wp.data(), win_rows.data(), win_ld.data(), seq_win.data(), n_seq, dp.data(),
+                                                                                        dld.data(), n_cols, step, square, g_stream); }, true);
                 g_fail_after = -1;
                 if (!ok_or_expected(rc, "dctfp_stitch_sequences")) return 1;
                 // the same windows as explicit jobs (what dctfp_stitch takes), one of them malformed now and then
@@ -338,7 +390,7 @@ static int other_entry_points(dctfp_ctx* ctx, std::mt19937_64& rng, int rounds, 
                         jobs.push_back(j);
                     }
                 if (starve) g_fail_after = uni(0, 8);
-                rc = dctfp_stitch(ctx, jobs.data(), (int64_t)jobs.size(), n_cols, square, nullptr);
+                rc = call("dctfp_stitch", [&] { return dctfp_stitch(ctx, jobs.data(), (int64_t)jobs.size(), n_cols, square, g_stream); }, true);
                 g_fail_after = -1;
                 if (!ok_or_expected(rc, "dctfp_stitch")) return 1;
             }
@@ -350,21 +402,23 @@ static int other_entry_points(dctfp_ctx* ctx, std::mt19937_64& rng, int rounds, 
             const int64_t lda = d + (int[]){0, 0, 10, 16}[uni(0, 3)], ldb = d + (int[]){0, 0, 6, 16}[uni(0, 3)];
             std::vector<int8_t> a((size_t)na * lda + 16), b((size_t)nb * ldb + 16);
             std::vector<int32_t> dist((size_t)na * nb);
-            if (!ok_or_expected(dctfp_l1_matrix(ctx, a.data() + uni(0, 1), na, lda, b.data(), nb, ldb, d, dist.data(), nb, nullptr), "dctfp_l1_matrix")) return 1;
+            const int a_off = uni(0, 1);
+            if (!ok_or_expected(call("dctfp_l1_matrix", [&] { return dctfp_l1_matrix(ctx, a.data() + a_off, na, lda, b.data(), nb, ldb, d, dist.data(), nb, g_stream); }),
+                                "dctfp_l1_matrix")) return 1;
             std::vector<int64_t> ia{0}, ib{0};
             while (ia.back() < na) ia.push_back(std::min<int64_t>(na, ia.back() + uni(0, 7)));
             while (ib.back() < nb) ib.push_back(std::min<int64_t>(nb, ib.back() + uni(0, 7)));
             std::vector<int32_t> mn((ia.size() - 1) * (ib.size() - 1) + 1), last(mn.size());
-            if (!ok_or_expected(dctfp_block_min(ctx, dist.data(), nb, ia.data(), (int64_t)ia.size() - 1, ib.data(), (int64_t)ib.size() - 1, mn.data(), last.data(),
-                                                nullptr), "dctfp_block_min")) return 1;
+            if (!ok_or_expected(call("dctfp_block_min", [&] { return dctfp_block_min(ctx, dist.data(), nb, ia.data(), (int64_t)ia.size() - 1, ib.data(),
+                                                                                     (int64_t)ib.size() - 1, mn.data(), last.data(), g_stream); }), "dctfp_block_min")) return 1;
             const int64_t n_rows = uni(1, 20), n_cols = (int64_t[]){1, 50, 40960, 40961, 130000}[uni(0, 4)];
             const int32_t k = (int32_t)std::min<int64_t>(n_cols, (int64_t[]){1, 100, 1024, 1025, 5000}[uni(0, 4)]);
             std::vector<int32_t> wide((size_t)n_rows * n_cols), val((size_t)n_rows * k), idx((size_t)n_rows * k);
             if (starve) g_fail_after = uni(0, 4);
-            const int rc = dctfp_row_select(ctx, wide.data(), n_rows, n_cols, n_cols, k, val.data(), idx.data(), nullptr);
+            const int rc = call("dctfp_row_select", [&] { return dctfp_row_select(ctx, wide.data(), n_rows, n_cols, n_cols, k, val.data(), idx.data(), g_stream); });
             g_fail_after = -1;
             if (!ok_or_expected(rc, "dctfp_row_select")) return 1;
-            if (!ok_or_expected(dctfp_row_order(ctx, val.data(), idx.data(), n_rows, k, nullptr), "dctfp_row_order")) return 1;   // (k > 1024: the limit error)
+            if (!ok_or_expected(call("dctfp_row_order", [&] { return dctfp_row_order(ctx, val.data(), idx.data(), n_rows, k, g_stream); }), "dctfp_row_order")) return 1;   // (k > 1024: the limit error)
         }
     }
     return 0;
@@ -374,6 +428,10 @@ int main(int argc, char** argv) {
     const int rounds = argc > 1 ? atoi(argv[1]) : 300;
     std::mt19937_64 rng(argc > 2 ? strtoull(argv[2], nullptr, 10) : 12345);
     auto uni = [&](int lo, int hi) { return (int)(lo + rng() % (uint64_t)(hi - lo + 1)); };
+    g_aux.seed((argc > 2 ? strtoull(argv[2], nullptr, 10) : 12345) ^ 0x5eedu);
+    auto aux = [&](int lo, int hi) { return (int)(lo + g_aux() % (uint64_t)(hi - lo + 1)); };
+    g_streams[1] = stub_new_stream();
+    g_streams[2] = stub_new_stream();
     dctfp_ctx* ctx = nullptr;
     CHECK(dctfp_create(0, &ctx));
     int n_calls = 0, n_errors_expected = 0;
@@ -484,13 +542,55 @@ int main(int argc, char** argv) {
         const bool starve = uni(0, 5) == 0;
         for (int rep = 0; rep < 2; ++rep) {
             if (starve) g_fail_after = uni(0, rep == 0 ? 40 : 12);
-            const int rc = dctfp_quantize(ctx, layers.data(), n_layers, n_seq, seq_rows.data(), pieces.data(), (int64_t)pieces.size(),
-                                          n_domains, out.data(), out_stride, nullptr);
+            const int rc = call("dctfp_quantize", [&] { return dctfp_quantize(ctx, layers.data(), n_layers, n_seq, seq_rows.data(), pieces.data(),
+                                                                              (int64_t)pieces.size(), n_domains, out.data(), out_stride, g_stream); }, true);
             g_fail_after = -1;
             ++n_calls;
-            if (rc == DCTFP_ERR_SHAPE || rc == DCTFP_ERR_NOMEM) { ++n_errors_expected; continue; }   // D < m / L < n / the injected failure
+            // D < m / L < n / the injected failures
+            if (rc == DCTFP_ERR_SHAPE || rc == DCTFP_ERR_NOMEM || (rc == DCTFP_ERR_HIP && g_launch_failed)) { ++n_errors_expected; continue; }
             if (rc != DCTFP_OK) {
                 fprintf(stderr, "round %d: dctfp_quantize -> %d: %s\n", round, rc, dctfp_last_error());
+                return 1;
+            }
+        }
+        // ---- one protein through dctfp_quantize_one (its last layer group leaves the context's buffers to the stream wait it does)
+        // and dctfp_gather_rows, on the first sequence
+        if (aux(0, 2) == 0) {
+            const int64_t L = seq_rows[0];
+            std::string text;
+            const int n_str = aux(1, 4);
+            for (int i = 0; i < n_str; ++i) {
+                const int64_t a = aux(1, (int)L), b = std::min<int64_t>(L, a + aux(0, 300));
+                text += (i ? "\n" : "") + std::to_string(a) + "-" + std::to_string(b) + (aux(0, 3) == 0 ? ",1-" + std::to_string(std::min<int64_t>(L, 5)) : "");
+            }
+            const int64_t rows = 2 * n_str + 1;
+            std::vector<int8_t> out1((size_t)rows * out_stride);
+            std::vector<int32_t> str_row(n_str);
+            std::vector<uint8_t> changed(n_str);
+            std::vector<char> keys(text.size() + n_str + 1);
+            int64_t key_len = 0, n_dom = 0, n_other = 0;
+            int32_t degenerate = 0;
+            const int rc = call("dctfp_quantize_one", [&] { return dctfp_quantize_one(ctx, layers.data(), n_layers, L, text.data(), (int64_t)text.size(), n_str,
+                                                                                      out1.data(), rows, out_stride, str_row.data(), changed.data(), keys.data(),
+                                                                                      (int64_t)keys.size(), &key_len, &n_dom, &n_other, &degenerate, g_stream); }, true);
+            ++n_calls;
+            if (rc != DCTFP_OK && rc != DCTFP_ERR_SHAPE && rc != DCTFP_ERR_NOMEM && !(rc == DCTFP_ERR_HIP && g_launch_failed)) {
+                fprintf(stderr, "round %d: dctfp_quantize_one -> %d: %s\n", round, rc, dctfp_last_error());
+                return 1;
+            }
+            std::vector<dctfp_piece> gp(aux(1, 6));
+            int64_t total_rows = 0;
+            for (auto& pc : gp) {
+                const int64_t a = aux(0, (int)L - 1);
+                pc = {a, (int32_t)aux(1, (int)(L - a)), 0, 0, 0};
+                total_rows += pc.n_rows;
+            }
+            std::vector<double> gathered((size_t)total_rows * D);
+            const int rg = call("dctfp_gather_rows", [&] { return dctfp_gather_rows(ctx, ptrs[0][0], dtype, L, D, ld, gp.data(), (int64_t)gp.size(), gathered.data(),
+                                                                                    g_stream); }, true);
+            ++n_calls;
+            if (rg != DCTFP_OK && !(rg == DCTFP_ERR_INVALID && dtype != DCTFP_F32 && dtype != DCTFP_F64) && !(rg == DCTFP_ERR_HIP && g_launch_failed)) {
+                fprintf(stderr, "round %d: dctfp_gather_rows -> %d: %s\n", round, rg, dctfp_last_error());
                 return 1;
             }
         }
@@ -506,6 +606,11 @@ int main(int argc, char** argv) {
     if (other_entry_points(ctx, rng, std::max(20, rounds / 3), &n_other_calls, &n_other_expected)) return 1;
     printf("the other entry points: %d calls (%d ended in an expected error)\n", n_other_calls, n_other_expected);
     CHECK(dctfp_destroy(ctx));
+    printf("kernel launch failures injected and reported as DCTFP_ERR_HIP: %ld\n", g_launch_failures);
+    if (g_stream_errors) {
+        printf("stream order: %d calls left work running that the caller's stream is not ordered after\n", g_stream_errors);
+        return 1;
+    }
     printf("allocation failures injected and reported as DCTFP_ERR_NOMEM: %ld\n", g_failed);
     printf("asan driver: %d calls over %d rounds (%d ended in an expected error), %lu walk-kernel launches, %lu stage-A launches, "
            "%lu jobs walked by the table emulation: no memory error\n", n_calls, rounds, n_errors_expected, dctfp_stub_counter(0),

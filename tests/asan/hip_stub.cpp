@@ -265,6 +265,49 @@ void emulate_basis(dim3 grid, void** a) {
     for (unsigned y = 0; y < grid.y; ++y) touch_w(tabs[y].tab, ((size_t)tabs[y].len * nk + ((size_t)tabs[y].len + 1) * nk) * sizeof(double));
 }
 
+// ---- stream order: a vector clock over streams per stream (the null stream included) and per event.  An enqueue ticks its
+// stream, hipEventRecord copies the stream's clock into the event, hipStreamWaitEvent merges the event's into the stream, and
+// what the host has waited for (stream / event / device synchronisation) every later enqueue inherits.  stub_call_end(s) counts
+// the operations a library call enqueued on other streams that stream s is not ordered after: work the call left running
+// unowned.  Fixed-size arrays: the driver injects std::bad_alloc through operator new, and nothing here may allocate that way.
+constexpr int kMaxStreams = 64;
+struct Clock {
+    uint32_t t[kMaxStreams];
+    void merge(const Clock& o) {
+        for (int i = 0; i < kMaxStreams; ++i) t[i] = t[i] > o.t[i] ? t[i] : o.t[i];
+    }
+};
+struct StubStream {
+    int id;
+    Clock c;
+};
+struct StubEvent {
+    Clock c;
+};
+StubStream g_null_stream{0, {}};
+StubStream* g_streams[kMaxStreams] = {&g_null_stream};
+int g_n_streams = 1;
+Clock g_host{}, g_call_begin{};
+StubStream* of(hipStream_t s) { return s ? (StubStream*)s : &g_null_stream; }
+void enqueue(hipStream_t s) {
+    StubStream* st = of(s);
+    st->c.merge(g_host);
+    st->c.t[st->id] += 1;
+}
+hipStream_t new_stream() {
+    if (g_n_streams == kMaxStreams) { fprintf(stderr, "stub: more than %d streams\n", kMaxStreams); abort(); }
+    StubStream* st = (StubStream*)calloc(1, sizeof(StubStream));
+    st->id = g_n_streams;
+    g_streams[g_n_streams++] = st;
+    return (hipStream_t)st;
+}
+
+// ---- launch-failure injection: the n-th hipLaunchKernel from now on fails (hipErrorLaunchFailure -- the device's error, which
+// a later launch on the stream reports -- returned and reported by the next hipGetLastError)
+long g_launch_fail_after = -1;
+unsigned long g_launch_failures = 0;
+hipError_t g_last_error = hipSuccess;
+
 void emulate_stage_b(void** a) {
     const int64_t rows = *(int64_t*)a[2];
     const JobB* jobs = *(const JobB**)a[5];
@@ -281,6 +324,28 @@ void emulate_stage_b(void** a) {
 
 extern "C" {
 unsigned long dctfp_stub_counter(int which) { return which == 0 ? g_walk_launches : (which == 1 ? g_stage_a_launches : g_jobs_walked); }
+void* stub_new_stream() { return new_stream(); }
+void stub_call_begin() {
+    for (int i = 0; i < g_n_streams; ++i)
+        if (g_streams[i]) g_call_begin.t[i] = g_streams[i]->c.t[i];
+}
+long stub_call_end(void* stream) {
+    const StubStream* caller = of((hipStream_t)stream);
+    long unjoined = 0;
+    for (int i = 0; i < g_n_streams; ++i) {
+        if (!g_streams[i] || i == caller->id) continue;
+        uint32_t done = g_call_begin.t[i];
+        if (caller->c.t[i] > done) done = caller->c.t[i];
+        if (g_host.t[i] > done) done = g_host.t[i];
+        if (g_streams[i]->c.t[i] > done) unjoined += g_streams[i]->c.t[i] - done;
+    }
+    return unjoined;
+}
+// the n-th kernel launch from now on fails (n < 0: none); returns how many injected failures have fired so far
+unsigned long stub_fail_launch(long n) {
+    g_launch_fail_after = n;
+    return g_launch_failures;
+}
 
 hipError_t hipGetDeviceCount(int* n) { *n = 1; return hipSuccess; }
 hipError_t hipSetDevice(int) { return hipSuccess; }
@@ -296,22 +361,39 @@ hipError_t hipHostMalloc(void** p, size_t n, unsigned) { *p = malloc(n ? n : 1);
 hipError_t hipHostFree(void* p) { free(p); return hipSuccess; }
 hipError_t hipHostGetDevicePointer(void** d, void* h, unsigned) { *d = h; return hipSuccess; }
 hipError_t hipMemcpy(void* d, const void* s, size_t n, hipMemcpyKind) { memcpy(d, s, n); return hipSuccess; }
-hipError_t hipMemcpyAsync(void* d, const void* s, size_t n, hipMemcpyKind, hipStream_t) { memcpy(d, s, n); return hipSuccess; }
+hipError_t hipMemcpyAsync(void* d, const void* s, size_t n, hipMemcpyKind, hipStream_t st) { memcpy(d, s, n); enqueue(st); return hipSuccess; }
+hipError_t hipMemsetAsync(void* d, int v, size_t n, hipStream_t st) { memset(d, v, n); enqueue(st); return hipSuccess; }
 hipError_t hipMemset(void* d, int v, size_t n) { memset(d, v, n); return hipSuccess; }
-hipError_t hipDeviceSynchronize() { return hipSuccess; }
-hipError_t hipStreamCreateWithFlags(hipStream_t* s, unsigned) { *s = (hipStream_t)malloc(8); return hipSuccess; }
-hipError_t hipStreamCreateWithPriority(hipStream_t* s, unsigned, int) { *s = (hipStream_t)malloc(8); return hipSuccess; }
+hipError_t hipDeviceSynchronize() {
+    for (int i = 0; i < g_n_streams; ++i)
+        if (g_streams[i]) g_host.merge(g_streams[i]->c);
+    return hipSuccess;
+}
+hipError_t hipStreamCreateWithFlags(hipStream_t* s, unsigned) { *s = new_stream(); return hipSuccess; }
+hipError_t hipStreamCreateWithPriority(hipStream_t* s, unsigned, int) { *s = new_stream(); return hipSuccess; }
 hipError_t hipDeviceGetStreamPriorityRange(int* lo, int* hi) { *lo = 1; *hi = -1; return hipSuccess; }
-hipError_t hipStreamDestroy(hipStream_t s) { free(s); return hipSuccess; }
-hipError_t hipStreamSynchronize(hipStream_t) { return hipSuccess; }
-hipError_t hipStreamWaitEvent(hipStream_t, hipEvent_t, unsigned) { return hipSuccess; }
-hipError_t hipEventCreate(hipEvent_t* e) { *e = (hipEvent_t)malloc(8); return hipSuccess; }
-hipError_t hipEventCreateWithFlags(hipEvent_t* e, unsigned) { *e = (hipEvent_t)malloc(8); return hipSuccess; }
+hipError_t hipStreamDestroy(hipStream_t s) {
+    g_streams[of(s)->id] = nullptr;
+    free(s);
+    return hipSuccess;
+}
+hipError_t hipStreamSynchronize(hipStream_t s) { g_host.merge(of(s)->c); return hipSuccess; }
+hipError_t hipStreamWaitEvent(hipStream_t s, hipEvent_t e, unsigned) { of(s)->c.merge(((StubEvent*)e)->c); return hipSuccess; }
+hipError_t hipEventCreate(hipEvent_t* e) { *e = (hipEvent_t)calloc(1, sizeof(StubEvent)); return hipSuccess; }
+hipError_t hipEventCreateWithFlags(hipEvent_t* e, unsigned) { *e = (hipEvent_t)calloc(1, sizeof(StubEvent)); return hipSuccess; }
 hipError_t hipEventDestroy(hipEvent_t e) { free(e); return hipSuccess; }
-hipError_t hipEventRecord(hipEvent_t, hipStream_t) { return hipSuccess; }
-hipError_t hipEventSynchronize(hipEvent_t) { return hipSuccess; }
+hipError_t hipEventRecord(hipEvent_t e, hipStream_t s) {
+    of(s)->c.merge(g_host);
+    ((StubEvent*)e)->c = of(s)->c;
+    return hipSuccess;
+}
+hipError_t hipEventSynchronize(hipEvent_t e) { g_host.merge(((StubEvent*)e)->c); return hipSuccess; }
 hipError_t hipEventElapsedTime(float* ms, hipEvent_t, hipEvent_t) { *ms = 1.0f; return hipSuccess; }
-hipError_t hipGetLastError() { return hipSuccess; }
+hipError_t hipGetLastError() {
+    const hipError_t e = g_last_error;
+    g_last_error = hipSuccess;
+    return e;
+}
 const char* hipGetErrorString(hipError_t) { return "stub"; }
 const char* hipGetErrorName(hipError_t) { return "stub"; }
 hipError_t hipRuntimeGetVersion(int* v) { *v = 0; return hipSuccess; }
@@ -333,7 +415,12 @@ hipError_t __hipPopCallConfiguration(dim3* grid, dim3* block, size_t* shmem, hip
     return hipSuccess;
 }
 hipError_t hipFuncSetAttribute(const void*, hipFuncAttribute, int) { return hipSuccess; }
-hipError_t hipLaunchKernel(const void* fn, dim3 grid, dim3 block, void** args, size_t shmem, hipStream_t) {
+hipError_t hipLaunchKernel(const void* fn, dim3 grid, dim3 block, void** args, size_t shmem, hipStream_t stream) {
+    enqueue(stream);   // (a failed launch too: what the caller cannot know is whether its stream still runs something)
+    if (g_launch_fail_after >= 0 && g_launch_fail_after-- == 0) {
+        ++g_launch_failures;
+        return g_last_error = hipErrorLaunchFailure;
+    }
     const auto it = names().find(fn);
     if (it == names().end()) { fprintf(stderr, "stub: launch of an unregistered kernel\n"); abort(); }
     const std::string& n = it->second;

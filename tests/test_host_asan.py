@@ -9,7 +9,10 @@ fused-group layout, the split at giant domains, failure injection (also std::bad
 build: the C ABI must answer DCTFP_ERR_NOMEM, not std::terminate) and arena restarts of the cosine-table cache.  Round 4: the
 entry points either side of dctfp_quantize too -- the domain-string parser, the top-k job / stripe tables and sorting-network
 groups, the window jobs of the stitcher in both forms, the L1 matrix / block minima / row select with its candidate scratch
--- over random and malformed arguments, again with allocation failures injected."""
+-- over random and malformed arguments, again with allocation failures injected.  Every call runs on one of three caller's
+streams in turn, the stub keeps the stream order (a vector clock per stream and event), and no call may return with work on
+another stream that its caller's stream is not ordered after -- on its error paths either, where kernel launches are made to
+fail now and then."""
 
 import os
 import re
@@ -79,6 +82,9 @@ def test_host_code_under_address_sanitizer(tmp_path):
         assert 'no memory error' in r.stdout
         # std::bad_alloc inside the table build comes back as DCTFP_ERR_NOMEM through the exception barrier of the C ABI
         assert int(re.search(r'reported as DCTFP_ERR_NOMEM: (\d+)', r.stdout).group(1)) >= 10, r.stdout
+        # a kernel launch that fails (hip_stub.cpp) comes back as DCTFP_ERR_HIP -- with the context's own streams joined back into the
+        # caller's, as on every path (the driver fails on any call that leaves work on another stream its caller's is not ordered after)
+        assert int(re.search(r'reported as DCTFP_ERR_HIP: (\d+)', r.stdout).group(1)) >= 40, r.stdout
         walked = int(re.search(r'(\d+) walk-kernel launches', r.stdout).group(1))
         assert walked >= 12, r.stdout          # the production path is among what was exercised (a seed's share: 15-40 of 500 calls)
         # the entry points either side of dctfp_quantize (round 4): domain-string parser, top-k tables, stitch jobs, row select

@@ -344,3 +344,24 @@ def test_cutter_in_flight_while_the_callers_stream_uses_the_context():
         for a, b in zip(alone[:8], few):
             assert a[1] == b[1]
             np.testing.assert_array_equal(a[2], b[2])
+
+
+def test_three_flushes_in_flight_finished_out_of_order():
+    """A flush owns its page-locked result buffers from start() to the end of finish(): three flushes started before the first is
+    finished, finished out of order, each give what flush_records gives for their proteins alone (with two sets of buffers shared
+    by turns, the third start() wrote over the first flush's results, and its finish() decoded them without an error)."""
+    from dctdomain_amd import make_db
+    rng = np.random.default_rng(21)
+    lens = np.clip(rng.gamma(2.2, 160.0, size=360).astype(int), 40, 1300).tolist()
+    fresh = _embedded(lens, seed=11)
+    groups = [slice(0, 90), slice(90, 220), slice(220, 360)]
+    alone = [make_db.flush_records(fresh()[g], threads=4) for g in groups]
+    flushes = [make_db._Flush(fresh()[g], threads=4) for g in groups]
+    for fl in flushes:
+        assert fl.start()
+    for i in (1, 2, 0):
+        recs = flushes[i].finish(objects=False)
+        assert recs is not None and len(recs) == len(alone[i])
+        for a, b in zip(alone[i], recs):
+            assert a[0] == b[0] and a[1] == b[1]
+            np.testing.assert_array_equal(a[2], b[2])
