@@ -3099,7 +3099,8 @@ __device__ inline uint32_t kth_smallest(const uint32_t (&key)[E], uint32_t lo, u
         const int b = ok != 0 ? (int)__builtin_ctzll(ok) : 63;
         if (b > 0) n_less += (uint32_t)__builtin_amdgcn_readlane((int)cum, b - 1);
         lo += (uint32_t)b << sft;
-        hi = min(hi, lo + ((1u << sft) - 1u));
+        hi = lo + min((1u << sft) - 1u, hi - lo);   // (the top bin of a range near 2^32: lo + 2^sft - 1 wrapped round to a
+                                                    //  hi below lo, and an entry keyed -inf was lost)
         ++step;   // (the next pass takes the other set of histograms: a wave still adding up this one is not disturbed)
     }
     return lo;
@@ -3131,7 +3132,7 @@ __device__ inline uint32_t wave_kth_upper(const uint32_t (&key)[E], uint32_t lo,
         const int b = ok != 0 ? (int)__builtin_ctzll(ok) : 63;
         if (b > 0) n_less += (uint32_t)__builtin_amdgcn_readlane((int)cum, b - 1);
         lo += (uint32_t)b << sft;
-        hi = min(hi, lo + ((1u << sft) - 1u));
+        hi = lo + min((1u << sft) - 1u, hi - lo);
         __builtin_amdgcn_wave_barrier();
     }
     return hi;

@@ -56,3 +56,33 @@ def fuzz_graphs(seed: int = 20240, n: int = 120):
             order = np.argsort(-p[ii, jj], kind='stable')[:t]
             ii, jj = ii[order], jj[order]
         yield L, ii, jj, p[ii, jj].astype(np.float32)
+
+
+def weight_class_graphs(seed: int = 4711, n: int = 60):
+    """Block contact graphs whose weights leave 0 .. 255, the range of a probability: some contacts negative (weight below 0,
+    or rounded to 0 from just under 0) and some at 2.555 and above (weight 256 and up), all finite.  Yields (L, i, j, v) as
+    fuzz_graphs does, up to 4 L contacts, strongest first; what the reference's cutter makes of such a .ce file is
+    tests/golden/reccut_weights_golden.json."""
+    rng = np.random.default_rng(seed)
+    for g in range(n):
+        L = int(rng.integers(22, 300))
+        nb = int(rng.integers(1, 6))
+        bounds = np.sort(rng.choice(np.arange(1, L), size=min(nb - 1, L - 1), replace=False)) if nb > 1 else []
+        lab = np.zeros(L, int)
+        for b in bounds:
+            lab[b:] += 1
+        same = lab[:, None] == lab[None, :]
+        p = rng.random((L, L)) * (same * rng.uniform(0.5, 1.0) + (~same) * rng.uniform(0.0, 0.3))
+        mask = np.triu(rng.random((L, L)) < rng.uniform(0.05, 0.3), 1)
+        ii, jj = np.nonzero(mask)
+        t = int(rng.uniform(1.0, 4.0) * L)
+        if len(ii) > t:
+            order = np.argsort(-p[ii, jj], kind='stable')[:t]
+            ii, jj = ii[order], jj[order]
+        v = p[ii, jj]
+        u = rng.random(len(v))
+        neg, big = (0.05, 0.3) if g % 3 else (0.3, 0.05)
+        v = np.where(u < neg, -rng.uniform(0.0, 1.5, len(v)), v)                               # below 0 (and -0.0149 .. 0: weight 0)
+        v = np.where((u >= neg) & (u < neg + big), 2.555 + rng.uniform(0.0, 40.0, len(v)), v)  # weight 256 and up
+        v = np.where((u >= neg + big) & (u < neg + big + 0.02), -rng.uniform(0.0, 0.0149, len(v)), v)
+        yield L, ii.astype(np.int32), jj.astype(np.int32), v.astype(np.float32)

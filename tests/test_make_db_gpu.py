@@ -365,3 +365,57 @@ def test_three_flushes_in_flight_finished_out_of_order():
         for a, b in zip(alone[i], recs):
             assert a[0] == b[0] and a[1] == b[1]
             np.testing.assert_array_equal(a[2], b[2])
+
+
+def test_flush_on_padded_batches_every_protein_against_the_oracles():
+    """Batches of several sequences through Batch.embed_parallel: every protein's contact map is a view of the batch's padded
+    (B, W, W) tensor, row stride W, W of every residue mod 4, member lengths of every residue mod 4 (16-byte loads whose last
+    one crosses the end of a row, maps 4 bytes off a 16-byte boundary), plus one protein longer than 2 048 alone in its batch
+    (handed back to the host library).  The flush must take them all, and EVERY protein must get the host library's cut of the
+    oracle's top contacts on its contiguous map (and the reference binary's strings, where it is built) and the oracle's quants."""
+    import dctdomain_amd as dd
+    from dctdomain_amd import make_db, reccut
+    from dctdomain_amd.embedding import Batch, SyntheticModel
+    from oracle import contacts_oracle as co
+    from oracle import dct_oracle as orc
+    rng = np.random.default_rng(404)
+    aa = np.frombuffer(b'ACDEFGHIKLMNPQRSTVWY', dtype=np.uint8)
+    dev = torch.device('cuda', 0)
+    model = SyntheticModel(dim=640)
+    model.to_device(dev)
+    embeds, widths = [], []
+    for W in (440, 361, 282, 203, 2101):
+        lens = [W] if W > 2048 else [W] + [int(rng.integers(30, W - 3)) // 4 * 4 + r for r in (0, 1, 2, 3, 3, 2, 1, 0)]
+        b = Batch([(f'w{W}_{q}', aa[rng.integers(0, 20, size=L)].tobytes().decode()) for q, L in enumerate(lens)], model, dev)
+        b.embed_parallel([15, 21])
+        for e in b.embeds:
+            assert e.contacts.shape == (len(e.seq), len(e.seq))
+            assert len(e.seq) < 2 or e.contacts.stride(0) == W
+        embeds += b.embeds
+        widths += [W] * len(b.embeds)
+    lens = [len(e.seq) for e in embeds]
+    assert {W % 4 for W in widths} == {0, 1, 2, 3}
+    for W in set(widths) - {2101}:
+        assert {L % 4 for L, w in zip(lens, widths) if w == W and L < W} == {0, 1, 2, 3}
+    assert any(e.contacts.data_ptr() % 16 for e in embeds)
+    fps = [dd.Fingerprint(pid=e.pid, seq=e.seq, embed=e.embed, contacts=e.contacts) for e in embeds]
+    make_db.fingerprint_batch(fps, threads=4)
+    assert make_db.LAST_PATH[0] == 'flush'
+    assert reccut.LAST.host_redo == [lens.index(2101)]
+    have_ref = os.path.exists(co.REF_BIN)
+    n_multi = 0
+    for e, fp, L in zip(embeds, fps, lens):
+        cmap = e.contacts.contiguous().cpu().numpy()
+        ci, cj, cv = co.top_contacts(cmap, 2.6)
+        d = reccut.domains_from_contacts([L], [0, len(ci)], ci, cj, cv)[0]
+        exp = d + [f'1-{L}'] if len(d) > 1 else d
+        assert fp.domains == exp, (fp.pid, L, fp.domains, exp)
+        if have_ref:
+            rc, out = co.run_ref_binary(co.ce_text(fp.pid, fp.seq, ci, cj, cv))
+            assert rc == 0 and co.parse_reccut(out, L) == exp, (fp.pid, L)
+        q = orc.quantize([e.embed[15].cpu().numpy(), e.embed[21].cpu().numpy()], exp, [3, 80, 3, 80])
+        assert list(fp.quants) == list(q) == exp
+        for k in q:
+            np.testing.assert_array_equal(fp.quants[k], q[k], err_msg=f'{fp.pid} {k}')
+        n_multi += len(exp) > 1
+    assert n_multi >= 5

@@ -13,7 +13,7 @@ import pytest
 import golden_util as gu
 from oracle import contacts_oracle as co
 from recipes import make_input, sha256_of
-from recipes_contacts import fuzz_graphs, make_contacts
+from recipes_contacts import fuzz_graphs, make_contacts, weight_class_graphs
 
 with open(os.path.join(gu.GOLD, 'reccut_golden.json')) as fh:
     CASES = json.load(fh)['cases']
@@ -75,6 +75,28 @@ def test_libreccut_fuzz_against_reference_binary():
         n_multi += len(exp) > 1
         n_disc += any(',' in d for d in exp)
     assert n_multi > 30 and n_disc > 3
+
+
+def test_libreccut_weights_outside_a_probability_against_reference_binary():
+    """Finite weights a probability never gives -- below 0, rounded to 0 from just under 0, 256 and up -- straight into
+    libreccut, against what the reference binary printed for the same .ce text (tests/golden/make_golden_reccut_weights.py).
+    The GPU cutter hands such proteins back to this library."""
+    from dctdomain_amd import reccut
+    with open(os.path.join(gu.GOLD, 'reccut_weights_golden.json')) as fh:
+        golden = json.load(fh)['cases']
+    graphs = list(weight_class_graphs())
+    assert len(graphs) == len(golden)
+    n_multi = n_neg = n_big = 0
+    for (L, ii, jj, pv), case in zip(graphs, golden):
+        text = co.ce_text('x', 'A' * L, ii, jj, pv)
+        assert L == case['L'] and hashlib.sha256(text.encode()).hexdigest() == case['ce_sha256']
+        assert case['reccut_rc'] == 0
+        got = reccut.domains_from_contacts([L], [0, len(ii)], ii, jj, pv)[0]
+        assert got == case['domains'], (L, case['domains'], got)
+        n_multi += len(got) > 1
+        n_neg += bool((pv <= -0.015).any())
+        n_big += bool((pv >= 2.555).any())
+    assert n_multi > 20 and n_neg == n_big == len(golden)
 
 
 def test_libreccut_batch_threads():
@@ -291,3 +313,112 @@ def test_contact_weight_exact_is_the_text_round_trip():
                            [1 / 128, 3 / 128, 5 / 256, 0.0, 1.0, 0.999999, 0.9999995, 0.5, 0.005, 0.015, 0.025, 1e-7]]).astype(np.float32)
     for p in vals.tolist():
         assert lib.reccut_contact_weight_exact(p) == int(float('%.6f' % p) * 100 + 0.5) == lib.reccut_contact_weight(p), p
+
+
+# ------------------------------------------------------------------ what the GPU cutter hands back to the host library
+def _graph_n(rng, L, n):
+    """Block contact graph of exactly n distinct pairs (i < j, band contacts included), strongest first."""
+    nb = int(rng.integers(1, 6))
+    bounds = np.sort(rng.choice(np.arange(1, L), size=min(nb - 1, L - 1), replace=False)) if nb > 1 else []
+    lab = np.zeros(L, int)
+    for b in bounds:
+        lab[b:] += 1
+    ii, jj = np.triu_indices(L, 1)
+    same = lab[ii] == lab[jj]
+    p = rng.random(len(ii)) * np.where(same, rng.uniform(0.5, 1.0), rng.uniform(0.0, 0.3))
+    order = np.argsort(-(p + 0.3 * rng.random(len(ii))), kind='stable')[:n]
+    assert len(order) == n
+    return ii[order].astype(np.int32), jj[order].astype(np.int32), p[order].astype(np.float32)
+
+
+def _weight_exact(v):
+    """reccut_contact_weight_exact, vectorised: rint(p 10^6) / 10^6, times 100 and plus 0.5 rounded one by one, truncated."""
+    x = np.rint(np.asarray(v, np.float64) * 1e6) / 1e6
+    with np.errstate(invalid='ignore'):
+        return np.trunc(x * 100.0 + 0.5)
+
+
+def _hands_back(L, ii, jj, pv):
+    """The input rules of dctfp_reccut: status -1 for L > 2 048, more contacts + 3 L than the largest LDS class holds (12 288),
+    a contact outside the protein, |p| >= 10^6 or not finite, a weight outside 0 .. 255 off the band -- a protein under 22
+    residues is one domain whatever its contacts."""
+    if L < 22:
+        return False
+    if L > 2048 or len(ii) + 3 * L > 12288:
+        return True
+    ii, jj, pv = np.asarray(ii, np.int64), np.asarray(jj, np.int64), np.asarray(pv, np.float32)
+    if ((ii < 0) | (jj < 0) | (ii >= L) | (jj >= L)).any() or not (np.abs(pv) < np.float32(1e6)).all():
+        return True
+    w = _weight_exact(pv[np.abs(ii - jj) > 3])
+    return bool(((w != 0) & ((w < 0) | (w > 255))).any())
+
+
+@pytest.mark.gpu
+def test_gpu_reccut_hand_backs_are_exactly_the_rules():
+    """domains_from_contacts_gpu against the host library on what the GPU cutter's input rules send back (reccut.LAST.host_redo
+    must be exactly the proteins the rules name) and on what they let through: contact counts up to 6 L (a larger LDS class
+    than the residues ask for), contacts + 3 L at 6 cap and 6 cap + 1 of every class, L <= 2 048 beyond the largest class,
+    negative weights and weights of 256 and up, |p| >= 10^6, +-inf, NaN, L = 21 / 22 / 23 (kCutMinSize = 22)."""
+    from dctdomain_amd import reccut
+    rng = np.random.default_rng(2048)
+    cases = []                                            # (L, i, j, v, what)
+    for L, n in ((300, 1800), (450, 2700), (480, 2880), (900, 5400), (1200, 7000)):      # up to 6 L contacts
+        cases.append((L, *_graph_n(rng, L, n), f'{n} contacts'))
+    for cap, L in ((512, 500), (1024, 900), (1536, 1400), (2048, 2000)):              # n + 3 L == 6 cap, 6 cap + 1
+        for extra in (0, 1):
+            n = 6 * cap - 3 * L + extra
+            cases.append((L, *_graph_n(rng, L, n), f'cap {cap}: 6 cap + {extra}'))
+    cases.append((1000, *_graph_n(rng, 1000, 9289), 'L <= 2048, contacts + 3 L = 12 289'))
+    cases.append((2049, *_graph_n(rng, 2049, 3000), 'L = 2049'))
+    for L in (21, 22, 23, 60):
+        cases.append((L, *_graph_n(rng, L, 2 * L), f'L = {L}'))
+    for what, fn in (('negative', lambda v, m: np.where(m, -0.2 - v, v)),
+                     ('just under 0 (weight 0)', lambda v, m: np.where(m, -0.0149 * v, v)),
+                     ('2.555', lambda v, m: np.where(m, np.float32(2.555), v)),
+                     ('2.5549 (weight 255)', lambda v, m: np.where(m, np.float32(2.5549), v)),
+                     ('above 2.555', lambda v, m: np.where(m, 3.0 + 50 * v, v)),
+                     ('1e6', lambda v, m: np.where(m, np.float32(1e6), v)),
+                     ('-1e6', lambda v, m: np.where(m, np.float32(-1e6), v)),
+                     ('999999', lambda v, m: np.where(m, np.float32(999999.0), v)),
+                     ('inf', lambda v, m: np.where(m, np.float32(np.inf), v)),
+                     ('-inf', lambda v, m: np.where(m, np.float32(-np.inf), v)),
+                     ('nan', lambda v, m: np.where(m, np.float32(np.nan), v))):
+        for L in (21, 23, 150):
+            ii, jj, pv = _graph_n(rng, L, 3 * L)
+            m = rng.random(len(pv)) < 0.02
+            m[np.flatnonzero(np.abs(ii - jj) > 3)[:1]] = True           # at least one contact off the band
+            cases.append((L, ii, jj, fn(pv, m).astype(np.float32), f'{what}, L = {L}'))
+        ii, jj, pv = _graph_n(rng, 150, 400)                             # ... on the band only (the band overwrites it)
+        m = np.abs(ii - jj) <= 3
+        cases.append((150, ii, jj, fn(pv, m).astype(np.float32), f'{what} on the band only'))
+    n_res = [c[0] for c in cases]
+    offs = np.concatenate([[0], np.cumsum([len(c[1]) for c in cases])])
+    args = (n_res, offs, np.concatenate([c[1] for c in cases]), np.concatenate([c[2] for c in cases]),
+            np.concatenate([c[3] for c in cases]))
+    predicted = [p for p, c in enumerate(cases) if _hands_back(*c[:4])]
+    exp = reccut.domains_from_contacts(*args, threads=8)
+    got = reccut.domains_from_contacts_gpu(*args)
+    assert sorted(reccut.LAST.host_redo) == predicted, ([cases[p][4] for p in reccut.LAST.host_redo], [cases[p][4] for p in predicted])
+    for p, (e, g) in enumerate(zip(exp, got)):
+        assert e == g, (cases[p][4], e, g)
+    whats = {cases[p][4] for p in predicted}
+    assert {'cap 2048: 6 cap + 1', 'L <= 2048, contacts + 3 L = 12 289', 'L = 2049', 'negative, L = 150', '2.555, L = 150',
+            'above 2.555, L = 150', '1e6, L = 150', '-1e6, L = 150', 'inf, L = 150', '-inf, L = 150', 'nan, L = 150',
+            'nan on the band only'} <= whats
+    assert not whats & {'cap 512: 6 cap + 1', 'cap 2048: 6 cap + 0', 'just under 0 (weight 0), L = 150', '2.5549 (weight 255), L = 150',
+                        '999999 on the band only', 'negative on the band only', 'L = 23'}
+    assert sum(len(e) > 1 for e in exp) >= 10
+    # a contact outside the protein: the same outcome as the host library -- its exception, or (L < 22) one domain
+    for L, bad in ((21, (3, 21)), (23, (3, 23)), (23, (-1, 9)), (150, (149, 150)), (150, (150, 151)), (150, (-2, 40))):
+        ii, jj, pv = _graph_n(rng, L, 2 * L)
+        ii[len(ii) // 2], jj[len(ii) // 2] = bad
+        a = ([L], [0, len(ii)], ii, jj, pv)
+        outcome = []
+        for fn in (reccut.domains_from_contacts, reccut.domains_from_contacts_gpu):
+            try:
+                outcome.append(fn(*a))
+            except RuntimeError as e:
+                outcome.append(type(e))
+        assert outcome[0] == outcome[1], (L, bad, outcome)
+        assert (outcome[0] == RuntimeError) == (L >= 22), (L, bad, outcome)
+        assert reccut.LAST.host_redo == ([0] if L >= 22 else [])
