@@ -2751,6 +2751,61 @@ int dctfp_sim_lines(dctfp_ctx* ctx, const int32_t* mn, const int32_t* last, int6
     return DCTFP_OK;
 } DCTFP_GUARD("dctfp_sim_lines")
 
+int dctfp_l1_knn(dctfp_ctx* ctx, const int8_t* q, int64_t nq, int64_t ldq, const int8_t* b, int64_t nb, int64_t ldb, int32_t d, int32_t k,
+                 int64_t col0, int32_t* out_val, int32_t* out_idx, void* stream_v) try {
+    if (!ctx || !q || !b || !out_val || !out_idx) return fail(DCTFP_ERR_INVALID, "dctfp_l1_knn: NULL argument");
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    if (nq < 0 || nb < 0 || d < 1 || ldq < d || ldb < d || k < 1 || col0 < 0) return fail(DCTFP_ERR_INVALID, "dctfp_l1_knn: bad shape");
+    if (((reinterpret_cast<uintptr_t>(q) | reinterpret_cast<uintptr_t>(b) | (uintptr_t)ldq | (uintptr_t)ldb) & 15u) != 0)
+        return fail(DCTFP_ERR_INVALID, "dctfp_l1_knn: fingerprint rows must start on 16-byte boundaries");
+    if (nq == 0 || nb == 0) return DCTFP_OK;
+    if (k > 1024 || d > 512) return fail(DCTFP_ERR_LIMIT, "dctfp_l1_knn: k above 1024 or rows above 512 bytes (use l1_matrix + row_select)");
+    if ((nq + 127) / 128 > 65535 || nb + col0 > 0x7fffffff || ldq >= (1 << 24) || ldb >= (1 << 24))
+        return fail(DCTFP_ERR_LIMIT, "dctfp_l1_knn: more than 8M query rows, 2^31 - 1 columns or 2^24-byte rows per call");
+    HIP_TRY(hipSetDevice(ctx->device));
+    hipStream_t stream = (hipStream_t)stream_v;
+    const int slices = knn_slices(nq, nb, k);
+    Hold scratch{ctx->scratch, stream};   // the rows' k-lists (and the slices' candidates): given back after the last kernel
+    int rc = scratch.take(knn_scratch_bytes(nq, k, slices), stream);
+    if (rc) return rc;
+    launch_l1_knn(q, nq, ldq, b, nb, ldb, d, k, slices, scratch.p(), out_val, out_idx, col0, stream);
+    HIP_TRY(hipGetLastError());
+    return scratch.give_back();
+} DCTFP_GUARD("dctfp_l1_knn")
+
+int dctfp_query_rank(dctfp_ctx* ctx, const int32_t* val, const int32_t* idx, int64_t n_rows, int32_t k, const int64_t* qoff,
+                     const int32_t* prot_of_row, const int64_t* line_base, int32_t khits, int32_t* out_qrow, int32_t* out_drow,
+                     int32_t* out_dist, void* stream_v) try {
+    if (!ctx || !val || !idx || !qoff || !prot_of_row || !line_base || !out_qrow || !out_drow || !out_dist)
+        return fail(DCTFP_ERR_INVALID, "dctfp_query_rank: NULL argument");
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    if (n_rows < 0 || k < 1 || khits < 1) return fail(DCTFP_ERR_INVALID, "dctfp_query_rank: bad shape");
+    if (n_rows * (int64_t)k > (int64_t)0xffffffffu * 256 / 2) return fail(DCTFP_ERR_LIMIT, "dctfp_query_rank: too many hits per call");
+    if (n_rows == 0) return DCTFP_OK;
+    HIP_TRY(hipSetDevice(ctx->device));
+    launch_query_rank(val, idx, n_rows, k, qoff, prot_of_row, line_base, khits, out_qrow, out_drow, out_dist, (hipStream_t)stream_v);
+    HIP_TRY(hipGetLastError());
+    return DCTFP_OK;
+} DCTFP_GUARD("dctfp_query_rank")
+
+int dctfp_query_lines(dctfp_ctx* ctx, int64_t n_lines, const int32_t* qrow, const int32_t* drow, const int32_t* dist, const int32_t* rank,
+                      const uint8_t* q_txt, const int64_t* q_pid_off, const int64_t* q_dom_off, const uint8_t* d_txt, const int64_t* d_pid_off,
+                      const int64_t* d_dom_off, const uint8_t* score_txt, const int64_t* score_off, const int64_t* line_off, uint8_t* out,
+                      void* stream_v) try {
+    if (!ctx || !qrow || !drow || !dist || !rank || !q_txt || !q_pid_off || !q_dom_off || !d_txt || !d_pid_off || !d_dom_off || !score_txt ||
+        !score_off || !line_off || !out)
+        return fail(DCTFP_ERR_INVALID, "dctfp_query_lines: NULL argument");
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    if (n_lines < 0) return fail(DCTFP_ERR_INVALID, "dctfp_query_lines: bad shape");
+    if ((n_lines + 255) / 256 > (int64_t)0xffffffffu / 256) return fail(DCTFP_ERR_LIMIT, "dctfp_query_lines: too many lines per call");
+    if (n_lines == 0) return DCTFP_OK;
+    HIP_TRY(hipSetDevice(ctx->device));
+    launch_query_lines(n_lines, qrow, drow, dist, rank, q_txt, q_pid_off, q_dom_off, d_txt, d_pid_off, d_dom_off, score_txt, score_off, line_off,
+                       out, (hipStream_t)stream_v);
+    HIP_TRY(hipGetLastError());
+    return DCTFP_OK;
+} DCTFP_GUARD("dctfp_query_lines")
+
 int dctfp_host_device_pointer(void* host, void** dev) try {
     if (!host || !dev) return fail(DCTFP_ERR_INVALID, "dctfp_host_device_pointer: NULL argument");
     *dev = nullptr;

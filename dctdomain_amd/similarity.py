@@ -248,3 +248,62 @@ def sim_lines(mn: torch.Tensor, last: torch.Tensor, row0: int, col0: int, ids: L
     _lib.check(ctx._lib.dctfp_sim_lines(ctx.handle, mn.data_ptr(), last.data_ptr(), n_cols, n_rows, int(row0), int(col0), n_cols,
                                         ids.bytes_dev.data_ptr(), ids.off_dev.data_ptr(), table.data_ptr(), base.data_ptr(), out.data_ptr(),
                                         stream))
+
+
+KNN_MAX_K = 1024     # dctfp_l1_knn's limits: larger k or wider rows take l1_matrix + row_select
+KNN_MAX_D = 512
+KNN_SCRATCH_BYTES = 1 << 31
+
+
+def _aligned16(t: torch.Tensor) -> bool:
+    ld = t.stride(0) if t.shape[0] > 1 else t.shape[1]
+    return (t.data_ptr() | ld) & 15 == 0 and t.stride(1) == 1
+
+
+def _rows16(t: torch.Tensor, w: int) -> torch.Tensor:
+    """``t`` copied into zero-padded rows of ``w`` bytes (what dctfp_l1_knn reads: rows on 16-byte boundaries; zeros on both
+    sides add nothing to an L1 distance)."""
+    out = torch.zeros((t.shape[0], w), dtype=torch.int8, device=t.device)
+    out[:, :t.shape[1]] = t
+    return out
+
+
+def l1_knn_device(q, db, k: int, col0: int = 0):
+    """(values, indices): device int32 (nq, min(k, nb)) -- each query row's k nearest database rows by L1, ascending, ties to the
+    lower row, ``col0`` added to the indices (``dctfp_l1_knn``: distances and selection in one kernel, no distance matrix).
+    What ``row_select(l1_matrix(q, db), k)`` returns; k > 1024 or rows wider than 512 bytes go that way."""
+    tq, tb = to_device_int8(q), to_device_int8(db)
+    if tq.dim() != 2 or tb.dim() != 2 or tq.shape[1] != tb.shape[1]:
+        raise ValueError('fingerprint sets must be 2-D with equal width')
+    nq, nb, d = tq.shape[0], tb.shape[0], tq.shape[1]
+    k = min(int(k), nb)
+    dev = tq.device
+    if nq == 0 or k <= 0:
+        return (torch.empty((nq, max(k, 0)), dtype=torch.int32, device=dev), torch.empty((nq, max(k, 0)), dtype=torch.int32, device=dev))
+    if k > KNN_MAX_K or d > KNN_MAX_D:
+        v, i = row_select(l1_matrix(tq, tb), k)
+        return (torch.as_tensor(v.astype(np.int32), device=dev), torch.as_tensor((i + col0).astype(np.int32), device=dev))
+    if not (_aligned16(tq) and _aligned16(tb)):
+        w = (d + 15) // 16 * 16
+        tq, tb = _rows16(tq, w), _rows16(tb, w)
+    val = torch.empty((nq, k), dtype=torch.int32, device=dev)
+    idx = torch.empty((nq, k), dtype=torch.int32, device=dev)
+    ctx = _lib.get_context(dev.index)
+    stream = torch.cuda.current_stream(dev)
+    # query rows per call sized by the scratch they take: 2 k-lists of k 8-byte keys per (row, database slice), and with several
+    # slices (only when there are few row tiles) the slices' lists once more and a half -- about 2 GiB at most per call
+    step = max(128, KNN_SCRATCH_BYTES // (32 * k) // 128 * 128)
+    for q0 in range(0, nq, step):
+        qs = tq[q0:q0 + step]
+        _lib.check(ctx._lib.dctfp_l1_knn(ctx.handle, qs.data_ptr(), qs.shape[0], qs.stride(0) if qs.shape[0] > 1 else tq.shape[1],
+                                         tb.data_ptr(), nb, tb.stride(0) if nb > 1 else tb.shape[1], tq.shape[1], k, int(col0),
+                                         val[q0:].data_ptr(), idx[q0:].data_ptr(), C.c_void_p(stream.cuda_stream)))
+    return val, idx
+
+
+def l1_knn(q, db, k: int, col0: int = 0):
+    """``l1_knn_device`` as int64 numpy arrays: the same pair as ``row_select(l1_matrix(q, db), k)`` (indices + ``col0``)."""
+    val, idx = l1_knn_device(q, db, k, col0)
+    if val.numel() == 0:
+        return np.zeros(tuple(val.shape), np.int64), np.zeros(tuple(idx.shape), np.int64)
+    return _pair_to_host(val, idx)

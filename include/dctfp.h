@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define DCTFP_VERSION 100 /* 0.1.0 */
+#define DCTFP_VERSION 101 /* 0.1.1: dctfp_l1_knn, dctfp_query_rank, dctfp_query_lines */
 
 #define DCTFP_OK 0
 #define DCTFP_ERR_INVALID (-1) /* bad argument (null pointer, piece outside its sequence, ...) */
@@ -341,6 +341,38 @@ int dctfp_select_fill(dctfp_ctx* ctx, const int32_t* dist, int64_t n_rows, int64
 int dctfp_sim_lines(dctfp_ctx* ctx, const int32_t* mn, const int32_t* last, int64_t ld, int64_t n_rows, int64_t row0, int64_t col0,
                     int64_t n_cols, const uint8_t* ids, const int64_t* id_off, const char* table, const int64_t* row_base, uint8_t* out,
                     void* stream);
+
+/* query_db's search (src/query_db.py:75-87: a flat FAISS index forced to METRIC_L1 at :76, index.search at :87) without a
+ * distance matrix: for query rows q (nq x d, row stride ldq) and database rows b (nb x d, stride ldb), int8 on the device, each
+ * query row's k_eff = min(k, nb) nearest database rows by L1, ascending, ties to the lower row -- what dctfp_row_select +
+ * dctfp_row_order return on the dctfp_l1_matrix of the two.  out_val / out_idx: device int32 (nq, k_eff), contiguous; col0 is
+ * added to every index (a caller streaming database blocks).  The distances of a 128-row query tile against a slice of the
+ * database and the selection run in one kernel; the slices' lists are merged on the device.  Rows must start on 16-byte
+ * boundaries (q, b, ldq, ldb); an empty side returns at once.  DCTFP_ERR_LIMIT for k > 1024 or d > 512 (the caller takes
+ * dctfp_l1_matrix + dctfp_row_select then), more than 8M query rows, or col0 + nb >= 2^31.  Uses the context's scratch. */
+int dctfp_l1_knn(dctfp_ctx* ctx, const int8_t* q, int64_t nq, int64_t ldq, const int8_t* b, int64_t nb, int64_t ldb, int32_t d, int32_t k,
+                 int64_t col0, int32_t* out_val, int32_t* out_idx, void* stream);
+
+/* ranked_hits (src/query_db.py:33-40: the reference's stable sort of a query protein's hits by distance) for many proteins:
+ * val / idx = the (n_rows, k) sorted hit lists of dctfp_l1_knn, protein p owning rows [qoff[p], qoff[p + 1]) (prot_of_row[r] =
+ * its protein; < 0: a protein the caller ranks itself, skipped).  The protein's hits ordered by (distance, fingerprint within
+ * the protein, hit rank); the first min(khits, f k) of them are written from line line_base[p] on: out_qrow = the fingerprint
+ * row, out_drow = the database row (idx), out_dist.  All device pointers.  Work per hit grows with the protein's f (one binary
+ * search per other fingerprint): callers send proteins of many fingerprints to the host. */
+int dctfp_query_rank(dctfp_ctx* ctx, const int32_t* val, const int32_t* idx, int64_t n_rows, int32_t k, const int64_t* qoff,
+                     const int32_t* prot_of_row, const int64_t* line_base, int32_t khits, int32_t* out_qrow, int32_t* out_drow,
+                     int32_t* out_dist, void* stream);
+
+/* query_db's result lines (src/query_db.py:57): line n = "Query: {qpid} {qdom}, Result {rank}: {dpid} {ddom}, Similarity: {score}\n"
+ * in UTF-8, from byte line_off[n] of out.  qrow / drow index the query / database string tables: the pid of row r is bytes
+ * [q_pid_off[r], q_pid_off[r + 1]) of q_txt, its domain [q_dom_off[r], q_dom_off[r + 1]) (likewise d_*); rank = the printed
+ * number; the score of distance x is bytes [score_off[x], score_off[x + 1]) of score_txt (a host-built table of the strings the
+ * reference prints).  line_off = the prefix sum of the line lengths (the caller's: every line must fit in out).  All device
+ * pointers. */
+int dctfp_query_lines(dctfp_ctx* ctx, int64_t n_lines, const int32_t* qrow, const int32_t* drow, const int32_t* dist, const int32_t* rank,
+                      const uint8_t* q_txt, const int64_t* q_pid_off, const int64_t* q_dom_off, const uint8_t* d_txt, const int64_t* d_pid_off,
+                      const int64_t* d_dom_off, const uint8_t* score_txt, const int64_t* score_off, const int64_t* line_off, uint8_t* out,
+                      void* stream);
 
 /* The address under which the GPU sees a pinned (page-locked, mapped) host buffer, e.g. a torch tensor created with
  * pin_memory=True.  A caller that passes this address as `out` of dctfp_quantize gets the int8 result written straight
