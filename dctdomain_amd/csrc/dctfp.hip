@@ -385,6 +385,8 @@ struct dctfp_ctx {
     int64_t last_walk_groups = 0;  // ... or walk_ab_kernel: its build's 16-column groups (5: m <= 80, 6: 80 < m <= 96), 0 = another kernel
     int64_t opt_gen_fuse = 1;    // "gen_fuse": fused walks through the general walk kernel (n <= 5); 0 = the two kernels, as through round 4
     int64_t walk_launches = 0;  // walk-kernel launches so far (a call split at a giant domain ends on the two-kernel path)
+    int64_t last_knn_slices = 0;  // database slices that owned a column in the last dctfp_l1_knn launch
+    int64_t knn_calls = 0;        // dctfp_l1_knn launches so far
     int64_t test_fail_once = 0;                    // test hook: the next dctfp_quantize fails after its table lookups
     int64_t basis_cap_doubles = (int64_t)1 << 27;  // 1 GiB of cosine tables, then the arena starts over (test hook: basis_cap_kb)
     int64_t basis_restarts = 0;                    // how often it did
@@ -901,6 +903,8 @@ int dctfp_get_option(dctfp_ctx* ctx, const char* name, int64_t* value) try {
     else if (n == "small_one") *value = ctx->opt_small_one;
     else if (n == "last_small_one") *value = ctx->last_small_one;
     else if (n == "walk_launches") *value = ctx->walk_launches;
+    else if (n == "last_knn_slices") *value = ctx->last_knn_slices;
+    else if (n == "knn_calls") *value = ctx->knn_calls;
     else if (n == "fuse") *value = ctx->opt_fuse;
     else if (n == "workspace_mb") *value = ctx->opt_ws_mb;
     else if (n == "profile") *value = ctx->opt_profile;
@@ -2768,7 +2772,8 @@ int dctfp_l1_knn(dctfp_ctx* ctx, const int8_t* q, int64_t nq, int64_t ldq, const
     Hold scratch{ctx->scratch, stream};   // the rows' k-lists (and the slices' candidates): given back after the last kernel
     int rc = scratch.take(knn_scratch_bytes(nq, k, slices), stream);
     if (rc) return rc;
-    launch_l1_knn(q, nq, ldq, b, nb, ldb, d, k, slices, scratch.p(), out_val, out_idx, col0, stream);
+    ctx->last_knn_slices = launch_l1_knn(q, nq, ldq, b, nb, ldb, d, k, slices, scratch.p(), out_val, out_idx, col0, stream);
+    ++ctx->knn_calls;
     HIP_TRY(hipGetLastError());
     return scratch.give_back();
 } DCTFP_GUARD("dctfp_l1_knn")

@@ -404,8 +404,8 @@ size_t knn_scratch_bytes(int64_t na, int k, int n_slices) {
     return keys * sizeof(unsigned long long);
 }
 
-void launch_l1_knn(const int8_t* a, int64_t na, int64_t lda, const int8_t* b, int64_t nb, int64_t ldb, int d, int k, int n_slices,
-                   void* scratch, int32_t* out_val, int32_t* out_idx, int64_t col0, hipStream_t stream) {
+int launch_l1_knn(const int8_t* a, int64_t na, int64_t lda, const int8_t* b, int64_t nb, int64_t ldb, int d, int k, int n_slices,
+                  void* scratch, int32_t* out_val, int32_t* out_idx, int64_t col0, hipStream_t stream) {
     const int k_eff = (int)min((int64_t)k, nb);
     const int64_t blocks = (nb + kTile - 1) / kTile;
     const int64_t slice_cols = (blocks + n_slices - 1) / n_slices * kTile;
@@ -426,6 +426,7 @@ void launch_l1_knn(const int8_t* a, int64_t na, int64_t lda, const int8_t* b, in
         n_in = n_out;
         std::swap(src, dst);
     }
+    return S;
 }
 
 void launch_query_rank(const int32_t* val, const int32_t* idx, int64_t n_rows, int k, const int64_t* qoff, const int32_t* prot_of_row,

@@ -157,8 +157,9 @@ void launch_sim_lines(const int32_t* mn, const int32_t* last, int64_t ld, int64_
 // query_db at database scale (k_query.hip): fused L1 + k nearest, the protein-level ranking, the hit lines as text
 int knn_slices(int64_t na, int64_t nb, int k);
 size_t knn_scratch_bytes(int64_t na, int k, int n_slices);
-void launch_l1_knn(const int8_t* a, int64_t na, int64_t lda, const int8_t* b, int64_t nb, int64_t ldb, int d, int k, int n_slices,
-                   void* scratch, int32_t* out_val, int32_t* out_idx, int64_t col0, hipStream_t stream);
+// returns the number of slices that own a column (at most n_slices)
+int launch_l1_knn(const int8_t* a, int64_t na, int64_t lda, const int8_t* b, int64_t nb, int64_t ldb, int d, int k, int n_slices,
+                  void* scratch, int32_t* out_val, int32_t* out_idx, int64_t col0, hipStream_t stream);
 void launch_query_rank(const int32_t* val, const int32_t* idx, int64_t n_rows, int k, const int64_t* qoff, const int32_t* prot_of_row,
                        const int64_t* line_base, int khits, int32_t* out_qrow, int32_t* out_drow, int32_t* out_dist, hipStream_t stream);
 void launch_query_lines(int64_t n_lines, const int32_t* qrow, const int32_t* drow, const int32_t* dist, const int32_t* rank,

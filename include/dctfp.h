@@ -406,6 +406,8 @@ int dctfp_crash_handler(int enable);
  *                  1 = always the two-kernel path; 2 = the walk kernel wherever its shapes allow (any number of jobs)
  *   "last_path"    read only: which kernels the last dctfp_quantize launched last (1 = two kernels, 2 = walk kernel)
  *   "walk_launches" read only: walk-kernel launches of this context so far
+ *   "last_knn_slices" read only: database slices that owned a column in the last dctfp_l1_knn launch (1: no merge kernels)
+ *   "knn_calls"    read only: dctfp_l1_knn launches of this context so far
  *   "fuse"         1 (default) = proteins given as parts + whole protein are streamed once
  *   "small_one"    1 = a call below 128 job-slabs of the production shape (float32 rows, n = 3, m <= 80) in ONE launch
  *                  (small_call_kernel); 0 (default) = three kernels -- the faster form on this chip (dctfp.hip).
