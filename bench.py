@@ -7,6 +7,11 @@
 
 A step = one pass of the hot path (dctfp_quantize: job tables + stage A + stage B) over the
 rank's whole batch, inputs resident in HBM.  Rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times the steps, writes --dump-outputs and prints the line.
+--full adds what the headline figure does not need: the CPU baseline leg, the parity sample
+against the oracle, the other workloads behind the headline (N = 1) and the per-rank
+clock / power block (N > 1).
 """
 
 from __future__ import annotations
@@ -39,11 +44,17 @@ def parse():
     ap.add_argument('--seq-len', type=int, default=500)
     ap.add_argument('--dim', type=int, default=None, help='embedding width (default: 1280 for c2/c3, 2560 for c4, 640 for c5)')
     ap.add_argument('--layers', type=int, default=2)
-    ap.add_argument('--cpu-seconds', type=float, default=12.0, help='0 disables the CPU baseline leg')
+    ap.add_argument('--full', action='store_true',
+                    help='besides the headline: the CPU baseline leg, the parity sample, the other workloads (--workloads auto, '
+                         'N = 1) and the per-rank block (N > 1); a plain run only sets up, warms up, times --steps, dumps and '
+                         'prints the line')
+    ap.add_argument('--cpu-seconds', type=float, default=None,
+                    help='seconds of the CPU baseline leg, 0 = no leg (default: 12 with --full, 0 without)')
     ap.add_argument('--cpu-procs', type=int, default=0,
                     help='CPU baseline worker processes (0 = every usable core: os.cpu_count() clipped by the affinity mask and the '
                          'cgroup quota, at most 256)')
-    ap.add_argument('--parity-sample', type=int, default=64)   # 64 sequences
+    ap.add_argument('--parity-sample', type=int, default=None,    # 64 sequences
+                    help='sequences compared with the oracle after the timed steps (default: 64 with --full, 0 without)')
     ap.add_argument('--opt', action='append', default=[], help='name=value passed to dctfp_set_option')
     ap.add_argument('--storage', choices=['float32', 'float16', 'bfloat16'], default='float32',
                     help='storage type of the synthetic embeddings (the headline metric is float32, as the reference)')
@@ -51,7 +62,7 @@ def parse():
                     help='torch.distributed backend for the barrier / max-over-ranks (gloo: rehearsal of N > 1 on one GPU)')
     ap.add_argument('--qdim', default='3,80', help='kept points n,m of every layer (default: the reference\'s 3,80; 5,44 and 3,85 are '
                     'PROST\'s -- these run through walk_gen_kernel)')
-    ap.add_argument('--diag', action='store_true', help='per-rank placement / clock / power block in the line also at N = 1')
+    ap.add_argument('--diag', action='store_true', help='per-rank placement / clock / power block in the line, at any N (--full adds it at N > 1)')
     ap.add_argument('--diag-seconds', type=float, default=2.0, help='length of the untimed loop behind that block (N > 1)')
     ap.add_argument('--workload', choices=['c2', 'c3', 'c4', 'c5'], default='c2',
                     help='c2 = headline (fixed L, whole-sequence domains); c3 = ragged L in [50,2000] given as the language '
@@ -64,8 +75,8 @@ def parse():
                          'region starts from already stitched matrices (rounds 1-4; not BASELINE config 3 as stated)')
     ap.add_argument('--workloads', default='auto',
                     help='N = 1 only: further workloads measured after the headline and reported in the line\'s "workloads" object '
-                         '(auto = c3,c4,c5,c4_pipeline behind the default c2 run, none otherwise; "none"; or a comma list; c4_pipeline = '
-                         'BASELINE config 4 as stated: contact map -> top-k -> RecCut -> per-domain fingerprints at D = 2560)')
+                         '(auto = c3,c4,c5,c4_pipeline behind the default c2 run with --full, none otherwise; "none"; or a comma list; '
+                         'c4_pipeline = BASELINE config 4 as stated: contact map -> top-k -> RecCut -> per-domain fingerprints at D = 2560)')
     ap.add_argument('--extra-steps', type=int, default=10, help='timed steps of each of those workloads (warm-up 2)')
     ap.add_argument('--pipeline-proteins', type=int, default=2048, help='proteins per flush of the c4_pipeline workload')
     ap.add_argument('--dump-outputs', metavar='DIR', default=None,
@@ -74,6 +85,14 @@ def parse():
     args = ap.parse_args()
     if args.steps < 1:
         ap.error('--steps must be at least 1')
+    if args.cpu_seconds is None:
+        args.cpu_seconds = 12.0 if args.full else 0.0
+    if args.parity_sample is None:
+        args.parity_sample = 64 if args.full else 0
+    if args.workloads == 'auto':
+        headline = args.workload == 'c2' and args.n_seq == 10000 and args.seq_len == 500 and args.dim in (None, 1280) and not args.opt \
+            and args.storage == 'float32' and args.qdim == '3,80' and args.layers == 2
+        args.workloads = 'c3,c4,c5,c4_pipeline' if args.full and headline else 'none'
     return args
 
 
@@ -314,7 +333,7 @@ def measure(args, wl, steps, warmup, env):
     for _ in range(warmup):
         step()
     # host side of one call with the GPU idle (C-side job tables + enqueue; inside the timed loop it runs under the previous
-    # step's kernel)
+    # step's kernel).  Also in a plain run: three steps, and the timed ones start from the state they always started from.
     call_host_ms = []
     for _ in range(3):
         torch.cuda.synchronize(device)
@@ -347,9 +366,10 @@ def measure(args, wl, steps, warmup, env):
 
     # ---- N > 1: what makes a bad curve readable from the line alone.  Per rank: where it ran, what it streamed, its own step
     # and kernel time -- and clock / package power sampled while the same step loops for two more seconds (the timed region
-    # is too short for rocm-smi; the walks run a package into its power limit, eight of them share a chassis).
+    # is too short for rocm-smi; the walks run a package into its power limit, eight of them share a chassis).  With --full
+    # (or --diag, also at N = 1).
     per_rank = None
-    if (world > 1 or args.diag) and wl == args.workload:
+    if (world > 1 and args.full or args.diag) and wl == args.workload:
         diag = dict(rank=rank, cuda_index=dev_index, gb_per_step=round(args.layers * data_rows * D * layers[0].element_size() / 1e9, 3),
                     step_ms=round(1e3 * own_elapsed / steps, 4), kernel_launch_ms=round(own_kernel_ms, 4))
         try:        # (diagnostics must never cost the line: whatever fails here is reported in the block, and every rank
@@ -562,7 +582,7 @@ def main():
     if world != args.gpus:
         raise SystemExit(f'--gpus {args.gpus} but WORLD_SIZE={world}')
 
-    # ---- CPU baseline leg first (rank 0, N = 1 only), before this process touches the GPU ----
+    # ---- with --full: the CPU baseline leg first (rank 0, N = 1 only), before this process touches the GPU ----
     # The faithful oracle form in one process per usable core, as the reference's Pool(cpu) runs it (src/make_db.py:48-49;
     # P = os.cpu_count(), clipped here by the affinity mask and the cgroup quota -- what the box really grants).
     cpu_baseline = None
@@ -605,25 +625,21 @@ def main():
                ctx=ctx, nccl=args.backend == 'nccl')
     head = measure(args, args.workload, args.steps, args.warmup, env)
 
-    # ---- N = 1: the other BASELINE configurations behind the headline, in the same line (what the driver's
-    # run attests is then every config, not C2 alone).  Each at its default size, inputs resident, parity-sampled; the
+    # ---- N = 1 with --full: the other BASELINE configurations behind the headline, in the same line (what the
+    # full run attests is then every config, not C2 alone).  Each at its default size, inputs resident, parity-sampled; the
     # headline fields are not touched.  Never at N > 1: that line is the scaling contract's.
     others = None
-    want = args.workloads
-    if want == 'auto':
-        plain = args.workload == 'c2' and args.n_seq == 10000 and args.seq_len == 500 and args.dim in (None, 1280) and not args.opt \
-            and args.storage == 'float32' and args.qdim == '3,80' and args.layers == 2
-        want = 'c3,c4,c5' if plain else 'none'
-    if world == 1 and want != 'none':
+    if world == 1 and args.workloads != 'none':
+        want = args.workloads.split(',')
         others = {}
-        for wl in want.split(','):
+        for wl in want:
             if wl == 'c4_pipeline':
                 continue
             r = measure(args, wl, args.extra_steps, 2, env)
             if r is not None:
                 others[wl] = {'value': r['value'], 'unit': 'fingerprints/s', 'ms_per_step': r['ms_per_step'], 'steps': r['steps'],
                               'config': r['config'], 'roofline': r['roofline'], 'host_table_ms': r['host_table_ms'], 'parity': r['parity']}
-        if args.workloads == 'auto' or 'c4_pipeline' in args.workloads.split(','):
+        if 'c4_pipeline' in want:
             others['c4_pipeline'] = measure_pipeline(args, args.extra_steps, env, n_prot=args.pipeline_proteins)
 
     if rank == 0:

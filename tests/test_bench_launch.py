@@ -32,11 +32,49 @@ def test_bare_gpus2_starts_its_own_ranks_cpu():
     assert r.stderr.count('bench.py needs an MI355X') >= 1, r.stderr[-2000:]
 
 
+def _parse(*argv):
+    import bench
+    saved, sys.argv = sys.argv, ['bench.py', *argv]
+    try:
+        return bench.parse()
+    finally:
+        sys.argv = saved
+
+
+def test_plain_run_is_lean_and_full_adds_the_legs():
+    """A plain run (`--gpus 1 --steps N --warmup W`) has no CPU leg, no parity sample and no further workloads; --full turns
+    each of them on at its old default, and an explicit option still sets its own leg either way."""
+    plain = _parse('--gpus', '1', '--steps', '20', '--warmup', '5')
+    assert not plain.full and plain.cpu_seconds == 0 and plain.parity_sample == 0 and plain.workloads == 'none'
+    full = _parse('--gpus', '1', '--steps', '20', '--warmup', '5', '--full')
+    assert full.cpu_seconds == 12.0 and full.parity_sample == 64 and full.workloads == 'c3,c4,c5,c4_pipeline'
+    # behind a non-headline configuration --full adds no further workloads, as the default run did before
+    assert _parse('--full', '--workload', 'c5').workloads == 'none' and _parse('--full', '--qdim', '5,44').workloads == 'none'
+    some = _parse('--full', '--cpu-seconds', '0', '--parity-sample', '8', '--workloads', 'c4_pipeline')
+    assert some.cpu_seconds == 0 and some.parity_sample == 8 and some.workloads == 'c4_pipeline'
+    assert _parse('--parity-sample', '6').parity_sample == 6
+
+
+@pytest.mark.gpu
+def test_plain_run_prints_the_headline_only():
+    """Without --full the line carries the headline and the figures of its own timed steps, nothing measured beside them."""
+    r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--n-seq', '600', '--steps', '3', '--warmup', '1'],
+                       env=_env(), capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith('{')]
+    assert len(lines) == 1, r.stdout[-2000:]
+    line = json.loads(lines[0])
+    assert line['metric'] == 'DCT fingerprints/sec on L=500 D=1280' and line['unit'] == 'fingerprints/s'
+    assert line['higher_is_better'] is True and line['dtype'] == 'f64' and line['steps'] == 3 and line['warmup'] == 1
+    assert line['value'] > 0 and line['ms_per_step'] > 0 and line['config']['sequences_per_gpu'] == 600
+    assert line['cpu_baseline'] is None and line['parity'] is None and line['per_rank'] is None and 'workloads' not in line
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize('launcher', ['bare', 'torchrun'])
 def test_gpus2_on_one_gpu_over_gloo(launcher):
     """Two ranks sharing the one GPU (gloo control plane): one JSON line, n_gpus 2, parity sample clean."""
-    args = ['--gpus', '2', '--backend', 'gloo', '--n-seq', '2000', '--steps', '3', '--warmup', '1', '--cpu-seconds', '0',
+    args = ['--gpus', '2', '--backend', 'gloo', '--n-seq', '2000', '--steps', '3', '--warmup', '1', '--full', '--cpu-seconds', '0',
             '--parity-sample', '8']
     if launcher == 'bare':
         cmd = [sys.executable, os.path.join(ROOT, 'bench.py')] + args
@@ -66,7 +104,7 @@ def test_ragged_workload_is_dealt_to_the_ranks():
     """`--workload c5 --gpus 2`: ONE job of 2 x n_seq sequences, length-balanced over the ranks (dist.balanced_shards) -- the
     two ranks stream the same bytes to a sequence; parity sample (multi-domain proteins, fused walks) clean."""
     args = ['--gpus', '2', '--backend', 'gloo', '--workload', 'c5', '--n-seq', '1500', '--steps', '3', '--warmup', '1',
-            '--cpu-seconds', '0', '--parity-sample', '6', '--diag-seconds', '0.5']
+            '--full', '--cpu-seconds', '0', '--parity-sample', '6', '--diag-seconds', '0.5']
     r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py')] + args, env=_env(), capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith('{')][0])
