@@ -338,19 +338,12 @@ struct dctfp_ctx {
         }
         return DCTFP_OK;
     }
-    int64_t opt_stage_b = 1, opt_a_waves = 0, opt_a_unroll = 4, opt_profile = 0, opt_ws_mb = 4096;
+    int64_t opt_a_waves = 0, opt_profile = 0, opt_ws_mb = 4096;
     TableRing ring;
     SharedBuf ws;       // yprime
     int64_t opt_fuse = 1, opt_pack_y = 1;
     SharedBuf scratch;  // dctfp_idct_quant's coefficients, dctfp_row_select's candidates
     DevBuf split_ws; // partial sums of the row-split stage A (small calls)
-    uint32_t* small_tickets = nullptr;  // small_call_kernel: arrival counters, zeroed once (their last taker resets them)
-    // "small_one": 1 = a small call of the production shape in ONE launch (small_call_kernel, round 5).  Off by default: measured
-    // 86 us per one-protein call against 57 through the three kernels (profiles/r05/pcie_rate_one_launch.txt, _three_launches.txt) --
-    // what the launches cost is what the hand-over inside a grid costs too on this chip: a workgroup on another XCD sees the
-    // partial sums only through agent-scope release / acquire (L2 write-back and invalidate per workgroup) and memory-side atomics.
-    int64_t opt_small_one = 0;
-    int64_t last_small_one = 0;         // read only ("last_small_one"): the last dctfp_quantize went through small_call_kernel
     // stage-A cosine tables, one per (domain length, n - 1): filled once, kept for the life of the context
     std::vector<BasisSlab> basis_slabs;
     std::unordered_map<uint64_t, double*> basis_tabs;
@@ -379,7 +372,7 @@ struct dctfp_ctx {
         }
         return DCTFP_OK;
     }
-    int64_t opt_path = 0, opt_ab_group = 0, opt_ab_unroll = 0, opt_ab_run_jobs = 0, opt_small_b_jobs = 512, opt_ab_longest_first = 0, opt_ab_mfma_a = 0, opt_ab_taper = 4, opt_ab_align = 2, opt_l1_kernel = 0, opt_row_select = 0, opt_stitch_once = 0, opt_topk_kernel = 0;
+    int64_t opt_path = 0, opt_ab_run_jobs = 0, opt_small_b_jobs = 512, opt_ab_longest_first = 0, opt_ab_taper = 4, opt_ab_align = 2, opt_l1_kernel = 0, opt_row_select = 0, opt_stitch_once = 0, opt_topk_kernel = 0;
     int64_t last_path = 0;  // which kernels the last dctfp_quantize launched: 1 = stage A + stage B, 2 = walk kernel
     int64_t last_gen_fused = 0;  // ... and whether that was the general walk kernel streaming fused walks (parts + whole protein)
     int64_t last_walk_groups = 0;  // ... or walk_ab_kernel: its build's 16-column groups (5: m <= 80, 6: 80 < m <= 96), 0 = another kernel
@@ -647,11 +640,11 @@ int launch_fail(LaunchError* err, int code, const char* fmt, ...) {
 namespace {
 
 // stage A of the two-kernel path, by storage type (each in its own translation unit)
-void launch_a(const AParams& p, int dtype, int vec, int n, int waves, int unroll) {
-    if (dtype == DCTFP_F32) launch_a_f32(p, vec, n, waves, unroll);
-    else if (dtype == DCTFP_F64) launch_a_f64(p, vec, n, waves, unroll);
-    else if (dtype == DCTFP_F16) launch_a_f16(p, vec, n, waves, unroll);
-    else launch_a_bf16(p, vec, n, waves, unroll);
+void launch_a(const AParams& p, int dtype, int vec, int n, int waves) {
+    if (dtype == DCTFP_F32) launch_a_f32(p, vec, n, waves);
+    else if (dtype == DCTFP_F64) launch_a_f64(p, vec, n, waves);
+    else if (dtype == DCTFP_F16) launch_a_f16(p, vec, n, waves);
+    else launch_a_bf16(p, vec, n, waves);
 }
 
 // a launcher's failure -> this thread's error message
@@ -751,8 +744,6 @@ int dctfp_destroy(dctfp_ctx* ctx) try {
     ctx->ws.release();
     ctx->scratch.release();
     ctx->split_ws.release();
-    if (ctx->small_tickets) (void)hipFree(ctx->small_tickets);
-    ctx->small_tickets = nullptr;
     ctx->cut_ws.release();
     for (auto& kv : ctx->st_cache) {
         (void)hipFree(kv.second.dev);
@@ -791,8 +782,6 @@ int dctfp_set_option(dctfp_ctx* ctx, const char* name, int64_t value) try {
         ctx->opt_fuse = value ? 1 : 0;
     } else if (n == "gen_fuse") {
         ctx->opt_gen_fuse = value ? 1 : 0;
-    } else if (n == "small_one") {
-        ctx->opt_small_one = value ? 1 : 0;
     } else if (n == "workspace_mb") {
         if (value < 16) return fail(DCTFP_ERR_INVALID, "workspace_mb must be >= 16");
         ctx->opt_ws_mb = value;
@@ -826,25 +815,12 @@ int dctfp_set_option(dctfp_ctx* ctx, const char* name, int64_t value) try {
 #endif
 #ifdef DCTFP_EXPERIMENTS
     // ---- engineering knobs and test hooks: libdctfp_experiments.so only (A/B tools, kernel-variant parity tests, cache tests)
-    else if (n == "stage_b") {
-        if (value != 0 && value != 1) return fail(DCTFP_ERR_INVALID, "stage_b must be 0 or 1");
-        ctx->opt_stage_b = value;
-    } else if (n == "a_waves") {
-        if (value != 0 && value != 1 && value != 2 && value != 4 && value != 8 && value != 16)
-            return fail(DCTFP_ERR_INVALID, "a_waves must be 0 (auto), 1, 2, 4, 8 or 16");
+    else if (n == "a_waves") {
+        if (value != 0 && value != 2 && value != 4 && value != 8 && value != 16)
+            return fail(DCTFP_ERR_INVALID, "a_waves must be 0 (auto), 2, 4, 8 or 16");
         ctx->opt_a_waves = value;
-    } else if (n == "a_unroll") {
-        if (value != 4 && value != 8) return fail(DCTFP_ERR_INVALID, "a_unroll must be 4 or 8");
-        ctx->opt_a_unroll = value;
     } else if (n == "pack_y") {
         ctx->opt_pack_y = value ? 1 : 0;
-    } else if (n == "ab_group") {
-        if (value != 0 && value != 3 && value != 4) return fail(DCTFP_ERR_INVALID, "ab_group must be 0 (auto), 3 or 4 jobs per flush");
-        ctx->opt_ab_group = value;
-    } else if (n == "ab_unroll") {
-        if (value != 0 && value != 4 && value != 6 && value != 8 && value != 12 && value != 16)
-            return fail(DCTFP_ERR_INVALID, "ab_unroll must be 0 (auto), 4, 6, 8, 12 or 16");
-        ctx->opt_ab_unroll = value;
     } else if (n == "small_b_jobs") {
         if (value < 0 || value > 1 << 20) return fail(DCTFP_ERR_INVALID, "small_b_jobs must be 0 .. 2^20");
         ctx->opt_small_b_jobs = value;
@@ -870,8 +846,6 @@ int dctfp_set_option(dctfp_ctx* ctx, const char* name, int64_t value) try {
     } else if (n == "row_select") {
         if (value != 0 && value != 1) return fail(DCTFP_ERR_INVALID, "row_select must be 0 (by shape) or 1 (the radix select whatever the shape)");
         ctx->opt_row_select = value;
-    } else if (n == "ab_mfma_a") {
-        ctx->opt_ab_mfma_a = value ? 1 : 0;
     } else if (n == "ab_run_jobs") {
         if (value < 0 || value > 4096) return fail(DCTFP_ERR_INVALID, "ab_run_jobs must be 0 (auto) .. 4096");
         ctx->opt_ab_run_jobs = value;
@@ -900,8 +874,6 @@ int dctfp_get_option(dctfp_ctx* ctx, const char* name, int64_t* value) try {
     else if (n == "last_gen_fused") *value = ctx->last_gen_fused;
     else if (n == "last_walk_groups") *value = ctx->last_walk_groups;
     else if (n == "gen_fuse") *value = ctx->opt_gen_fuse;
-    else if (n == "small_one") *value = ctx->opt_small_one;
-    else if (n == "last_small_one") *value = ctx->last_small_one;
     else if (n == "walk_launches") *value = ctx->walk_launches;
     else if (n == "last_knn_slices") *value = ctx->last_knn_slices;
     else if (n == "knn_calls") *value = ctx->knn_calls;
@@ -919,16 +891,11 @@ int dctfp_get_option(dctfp_ctx* ctx, const char* name, int64_t* value) try {
         *value = __atomic_exchange_n(ctx->flag_host, 0u, __ATOMIC_ACQ_REL) ? 1 : 0;
     }
 #ifdef DCTFP_EXPERIMENTS
-    else if (n == "stage_b") *value = ctx->opt_stage_b;
     else if (n == "a_waves") *value = ctx->opt_a_waves;
-    else if (n == "a_unroll") *value = ctx->opt_a_unroll;
     else if (n == "overlap") *value = ctx->opt_overlap;
-    else if (n == "ab_group") *value = ctx->opt_ab_group;
-    else if (n == "ab_unroll") *value = ctx->opt_ab_unroll;
     else if (n == "ab_run_jobs") *value = ctx->opt_ab_run_jobs;
     else if (n == "ab_longest_first") *value = ctx->opt_ab_longest_first;
     else if (n == "small_b_jobs") *value = ctx->opt_small_b_jobs;
-    else if (n == "ab_mfma_a") *value = ctx->opt_ab_mfma_a;
     else if (n == "ab_taper") *value = ctx->opt_ab_taper;
     else if (n == "ab_align") *value = ctx->opt_ab_align;
     else if (n == "l1_kernel") *value = ctx->opt_l1_kernel;
@@ -1037,8 +1004,8 @@ int64_t stitch_geometry(const int32_t* rows, int64_t n_win, int32_t step, bool s
     return size;
 }
 // The walk kernels address the rows of a piece through a 32-bit buffer offset and stream a whole domain per wave.
-bool walk_rows_ok(const dctfp_ctx* ctx, const dctfp_layer& g, uint32_t max_len_all) {
-    return max_len_all <= kWalkMaxRows && (size_t)g.ld * dtype_size(g.dtype) <= ((size_t)1 << 31) / kWalkMaxRows && ctx->opt_stage_b == 1;
+bool walk_rows_ok(const dctfp_layer& g, uint32_t max_len_all) {
+    return max_len_all <= kWalkMaxRows && (size_t)g.ld * dtype_size(g.dtype) <= ((size_t)1 << 31) / kWalkMaxRows;
 }
 // ... and take a call by the "path" option: always (2), or from 256 jobs (a smaller call is latency-bound: two kernels)
 bool walk_by_path(const dctfp_ctx* ctx, int64_t n_jobs) { return ctx->opt_path == 2 || (ctx->opt_path == 0 && n_jobs >= 256); }
@@ -1255,7 +1222,7 @@ int quantize_impl(dctfp_ctx* ctx, const dctfp_layer* layers, int32_t n_layers, i
         // (a wave streams all rows of its channels).  Every other shape of float32 / float64 rows that fits the LDS goes to the
         // general walk kernel (round 4); the rest -- and calls too small to fill the chip -- run stage A -> Y' -> stage B.
         // (rows are addressed through a 32-bit buffer offset: a piece of at most kWalkMaxRows rows stays below 2^31 bytes)
-        const bool rows_ok = walk_rows_ok(ctx, g, max_len_all);
+        const bool rows_ok = walk_rows_ok(g, max_len_all);
         const bool walk_ok = !trivial && walk_shape(g) && vec_ok && rows_ok;
         const bool use_walk = walk_ok && walk_by_path(ctx, n_jobs);
         if (two_source && !(use_walk && g.dtype == DCTFP_F32 && m <= 80))  // (dctfp_quantize_windows has asked takes_two_sources() before anything was launched)
@@ -1344,15 +1311,14 @@ int quantize_impl(dctfp_ctx* ctx, const dctfp_layer* layers, int32_t n_layers, i
         // which spreads one job over slabs x 8 waves, finishes first.
         // walks of ALL jobs (walk kernel) -- the two-kernel path builds its walks per chunk below
         int64_t n_walks = 0, n_runs = 0;
-        int walk_s = 0, walk_g = 0;
+        int walk_s = 0;
+        constexpr int walk_g = 4;  // jobs per flush: the rows of an MFMA tile (a flush costs the same MFMAs for 1..4 jobs)
         // workgroups of the kernel the chip holds at once, per CU (LDS: 5 / 3 / 1 at 3 / 5 / 10 waves of the walk kernel)
         int64_t wg_per_cu = 1;
         if (use_walk || use_gen) {
             walk_s = use_gen ? gen_waves : (g.n_cols <= 768 ? 3 : (g.n_cols <= 1280 ? 5 : 10));
             wg_per_cu = use_gen ? std::max<int64_t>(1, std::min<int64_t>(20 / gen_waves, (int64_t)(kGenLdsBudget / (gen_slots * gen_slot_bytes(n, m, gen_waves, gen_vec) + 64))))
                                 : (walk_s == 3 ? 5 : (walk_s == 5 ? 3 : 1));
-            // jobs per flush: 4 = the rows of an MFMA tile (a flush costs the same MFMAs for 1..4 jobs)
-            walk_g = ctx->opt_ab_group && !two_source && m <= 80 ? (int)ctx->opt_ab_group : 4;
             for (int64_t j = 0; j < n_jobs;) {
                 const int64_t d = j % n_domains;
                 Walk& wk = hwalk[n_walks++];
@@ -1474,8 +1440,8 @@ int quantize_impl(dctfp_ctx* ctx, const dctfp_layer* layers, int32_t n_layers, i
         // Below 512 jobs the MFMA stage B (a few workgroups walking the D channels in 80 dependent steps: ~80 us of
         // latency) loses to stage B over 64-channel slabs (stage_b_slab_kernel): 57 against 147 us at 8 jobs, 195 against
         // 245 us at 256, even at 512 (profiles/r02/midsize_probe.txt); the walk kernel takes over from 256 jobs.
-        const bool small_b = n_jobs < ctx->opt_small_b_jobs && ctx->opt_stage_b == 1;
-        const bool packed = ctx->opt_pack_y && n == 3 && ctx->opt_stage_b == 1 && !small_b;
+        const bool small_b = n_jobs < ctx->opt_small_b_jobs;
+        const bool packed = ctx->opt_pack_y && n == 3 && !small_b;
         const size_t job_bytes = packed ? (size_t)ldy_pre * 9 : (size_t)n * ldy_pre * sizeof(double);
         const int n_slabs = (ldy_pre + 64 * vec - 1) / (64 * vec);
         int slots = 1;
@@ -1674,8 +1640,7 @@ int quantize_impl(dctfp_ctx* ctx, const dctfp_layer* layers, int32_t n_layers, i
             wp.two_source = two_source;
             {
                 LaunchError le;
-                rc = launcher_rc(launch_walk(wp, g.dtype, walk_s, walk_g, ctx->opt_ab_unroll && !two_source ? (int)ctx->opt_ab_unroll : 8, fuse,
-                                             ctx->opt_ab_mfma_a != 0 && !two_source, &le), le);
+                rc = launcher_rc(launch_walk(wp, g.dtype, walk_s, fuse, &le), le);
             }
             if (rc) return rc;
             HIP_TRY(hipGetLastError());
@@ -1713,7 +1678,6 @@ int quantize_impl(dctfp_ctx* ctx, const dctfp_layer* layers, int32_t n_layers, i
             const int n_kslabs = (g.n_cols + kSlabChannels - 1) / kSlabChannels;
             auto zpart_bytes = [&](int64_t jobs_here) { return (size_t)jobs_here * n_kslabs * n * m * sizeof(double); };
             double* zpart = nullptr;
-            bool one_launch = false;   // small_call_kernel has done stage A, stage B and the int8 rows of this chunk
             {
                 AParams ap;
                 ap.jobs = dja + j0;
@@ -1739,35 +1703,13 @@ int quantize_impl(dctfp_ctx* ctx, const dctfp_layer* layers, int32_t n_layers, i
                     chunk_rows = std::max<uint32_t>(32, (chunk_rows + 31) / 32 * 32);  // 8 waves x 4 rows in flight
                     const int n_chunks = (int)((max_len_all + chunk_rows - 1) / chunk_rows);
                     const size_t partial_bytes = (size_t)jn * n_chunks * nk * ldy * sizeof(double);
-                    // (small_call_kernel keeps a 3 x 80 block per job and 256-channel slab behind the partial sums)
-                    rc = ctx->split_ws.ensure(partial_bytes + (small_b ? std::max(zpart_bytes(jn), (size_t)jn * n_slabs * 3 * 80 * sizeof(double)) : 0));
+                    rc = ctx->split_ws.ensure(partial_bytes + (small_b ? zpart_bytes(jn) : 0));
                     if (rc) return rc;
                     static const InvTab<3> inv3 = make_inv<3>();
-                    // Round 5: the three steps of a small call in ONE launch (small_call_kernel: they hand over by tickets).
-                    // n = 3, m <= 80 (five column groups of fragments per k-step in registers): the production shape.
-                    if (small_b && m <= 80 && ctx->opt_small_one) {
-                        rc = get_st_plain(ctx, st, g.n_cols);
-                        if (rc) return rc;
-                        constexpr size_t kTickets = 1024;   // jn * n_slabs < 128 here: (n_slabs + 1) counters per job
-                        if (!ctx->small_tickets) {
-                            HIP_TRY(hipMalloc((void**)&ctx->small_tickets, kTickets * sizeof(uint32_t)));
-                            HIP_TRY(hipMemset(ctx->small_tickets, 0, kTickets * sizeof(uint32_t)));
-                        }
-                        if ((size_t)jn * (n_slabs + 1) <= kTickets) {
-                            zpart = (double*)((char*)ctx->split_ws.p + partial_bytes);   // (jn x n_slabs blocks of 3 x 80: below zpart_bytes(jn))
-                            hipLaunchKernelGGL((small_call_kernel<8, 4>), dim3((unsigned)(jn * n_chunks * n_slabs)), dim3(512), 0, stream,
-                                               dja + j0, djb + j0, dpc, (double*)ctx->split_ws.p, zpart, ctx->small_tickets, (int)jn, n_chunks,
-                                               chunk_rows, g.n_cols, g.ld, ldy, n_slabs, (const double*)st->fragp, m, inv3, ctx->degenerate, out);
-                            HIP_TRY(hipGetLastError());
-                            one_launch = true;
-                        }
-                    }
-                    if (!one_launch)
                     hipLaunchKernelGGL((stage_a_split_kernel<float, 3, 4, 8, 4>), dim3((unsigned)(jn * n_chunks * n_slabs)), dim3(512), 0, stream,
                                        dja + j0, dpc, (double*)ctx->split_ws.p, n_chunks, chunk_rows, g.n_cols, g.ld, ldy, n_slabs);
                     HIP_TRY(hipGetLastError());
-                    if (one_launch) {
-                    } else if (small_b) {  // the slabs of stage B add the chunks and scale their channels themselves
+                    if (small_b) {  // the slabs of stage B add the chunks and scale their channels themselves
                         zpart = (double*)((char*)ctx->split_ws.p + partial_bytes);
                         hipLaunchKernelGGL((stage_b_slab_kernel<true>), dim3((unsigned)n_kslabs, (unsigned)jn), dim3(256), 0, stream,
                                            (const double*)nullptr, ldy, (const double*)ctx->split_ws.p, n_chunks, inv3, ctx->degenerate,
@@ -1779,19 +1721,16 @@ int quantize_impl(dctfp_ctx* ctx, const dctfp_layer* layers, int32_t n_layers, i
                     }
                     HIP_TRY(hipGetLastError());
                 }
-                int waves = (int)ctx->opt_a_waves;
-                int unroll = (int)ctx->opt_a_unroll;
+                int waves = (int)ctx->opt_a_waves;  // (a forced count -- test hook -- goes through the same rules)
                 if (waves == 0) {  // auto: short walks want more, smaller workgroups per CU
                     waves = avg_rows >= 320 ? 8 : (avg_rows >= 160 ? 4 : 2);
                     // a call that cannot fill the chip (a protein at a time) is bound by the latency of one workgroup:
-                    // as many waves and rows in flight as a workgroup can have
-                    if (ck.wn * n_slabs < 256 && avg_rows >= 128 && vec == 4) {
-                        waves = 16;
-                        if (!fuse) unroll = 8;
-                    }
-                    if (vec == 8 && waves > 4) waves = 4;  // 8 channels per lane: keep the LDS reduction buffer small
+                    // as many waves and rows in flight as a workgroup can have (16 waves: k_stage_a.inc)
+                    if (ck.wn * n_slabs < 256 && avg_rows >= 128 && vec == 4) waves = 16;
                 }
-                if (!split) launch_a(ap, g.dtype, vec, n, waves, unroll);
+                if (waves == 16 && vec != 4) waves = 8;  // 16 waves at 4 channels per lane only
+                if (vec == 8 && waves > 4) waves = 4;    // 8 channels per lane: keep the LDS reduction buffer small
+                if (!split) launch_a(ap, g.dtype, vec, n, waves);
                 HIP_TRY(hipGetLastError());
             }
             rc = prof_end(ep, stream);
@@ -1803,13 +1742,11 @@ int quantize_impl(dctfp_ctx* ctx, const dctfp_layer* layers, int32_t n_layers, i
 
             rc = prof_begin(ctx, 1, sb, &ep);
             if (rc) return rc;
-            ctx->last_small_one = one_launch ? 1 : 0;
-            if (one_launch) {
-            } else if (ctx->opt_stage_b == 1 && !small_b) {
+            if (!small_b) {
                 const int64_t rows = jn * n;
                 launch_b_mfma(st->cp / 16, packed, (unsigned)((rows + kBWaves * 16 - 1) / (kBWaves * 16)), sb, yprime, (int64_t)job_bytes, rows, ldy,
                               st->dev, djb + j0, n, m, out);
-            } else if (small_b) {
+            } else {
                 if (!zpart) {  // stage A wrote Y' (no row split): the slabs read it
                     rc = ctx->split_ws.ensure(zpart_bytes(jn));
                     if (rc) return rc;
@@ -1821,9 +1758,6 @@ int quantize_impl(dctfp_ctx* ctx, const dctfp_layer* layers, int32_t n_layers, i
                     HIP_TRY(hipGetLastError());
                 }
                 hipLaunchKernelGGL(stage_b_finish_kernel, dim3((unsigned)jn), dim3(256), 0, sb, (const double*)zpart, n_kslabs, djb + j0, n, m, out);
-            } else {
-                hipLaunchKernelGGL(stage_b_valu_kernel, dim3((unsigned)jn), dim3(1024), 0, sb, (const double*)yprime, ldy, g.n_cols,
-                                   st->dev, st->cp, djb + j0, n, m, out);
             }
             HIP_TRY(hipGetLastError());
             rc = prof_end(ep, sb);
@@ -2005,7 +1939,7 @@ int dctfp_quantize_windows(dctfp_ctx* ctx, const dctfp_layer* layers, int32_t n_
             if (!g.seq_data || g.dtype != DCTFP_F32) why = "windows are averaged in float32 (as dctfp_stitch)";
             else if (!walk_shape(g) || g.m_keep > 80) why = "kept sizes / width outside the one-launch kernel's (n = 3, 64 < m <= 80, 512 <= D <= 2560, D % 4 == 0)";
             else if (!rows_aligned16(layers + l0, l1 - l0, n_win, nullptr)) why = "rows are not 16-byte aligned";
-            else if (!walk_rows_ok(ctx, g, max_len)) why = "a domain above 8 192 rows";
+            else if (!walk_rows_ok(g, max_len)) why = "a domain above 8 192 rows";
             else if (!walk_by_path(ctx, (int64_t)(l1 - l0) * n_domains)) why = "fewer than 256 jobs (layers x domains) in the call";
             if (why)
                 return fail(DCTFP_ERR_UNSUPPORTED, "dctfp_quantize_windows: layer %d: %s -- stitch with dctfp_stitch_sequences, then dctfp_quantize", l0, why);

@@ -6,9 +6,9 @@ namespace dctfp_host {
 
 #include "k_stage_a.inc"
 
-void launch_a_f32(const AParams& p, int vec, int n, int waves, int unroll) {
-    if (vec == 4) launch_a_n<float, 4>(p, n, waves, unroll);
-    else launch_a_n<float, 1>(p, n, waves, unroll);
+void launch_a_f32(const AParams& p, int vec, int n, int waves) {
+    if (vec == 4) launch_a_n<float, 4>(p, n, waves);
+    else launch_a_n<float, 1>(p, n, waves);
 }
 
 }  // namespace dctfp_host

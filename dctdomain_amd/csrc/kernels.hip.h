@@ -768,83 +768,6 @@ __global__ __launch_bounds__(kBWaves * 64, MINW) void stage_b_mfma_kernel(const 
 }
 
 // ---------------------------------------------------------------------------
-// K2 (VALU): same result as the MFMA kernel, one workgroup per job, plain FMAs.
-// Kept as the cross-check of the MFMA fragment layout and for A/B timing.
-// ---------------------------------------------------------------------------
-#ifndef DCTFP_TEMPLATES_ONLY   // (a plain kernel: defined in dctfp.hip only, the kernel-family units see the templates)
-__global__ __launch_bounds__(1024) void stage_b_valu_kernel(const double* __restrict__ yp, int ldy, int n_cols,
-                                                             const double* __restrict__ st, int cp,
-                                                             const JobB* __restrict__ jobs, int n, int m,
-                                                             int8_t* __restrict__ out) {
-    // 1024 threads = 4 groups x 256: group kg takes every fourth 64-channel stretch of a staged chunk, so the D-long sums
-    // of a job -- the whole latency of a small call -- run four abreast; the partial sums meet in LDS in group order.
-    constexpr int DCH = 256;  // channels staged per pass
-    constexpr int KG = 4;
-    __shared__ double ys[DCTFP_MAX_N_K][DCH];
-    __shared__ double part[KG][DCTFP_MAX_N_K * DCTFP_MAX_M_K];
-    __shared__ double bl[DCTFP_MAX_N_K * DCTFP_MAX_M_K];
-    const int job = blockIdx.x;
-    const double* __restrict__ yj = yp + (size_t)job * n * ldy;
-    const int n_out = n * m;
-    const int kg = threadIdx.x >> 8, tx = threadIdx.x & 255;
-    double acc[4] = {0.0, 0.0, 0.0, 0.0};
-    for (int d0 = 0; d0 < n_cols; d0 += DCH) {
-        const int dn = min(DCH, n_cols - d0);
-        __syncthreads();
-        for (int i = threadIdx.x; i < n * DCH; i += 1024) {
-            const int j = i / DCH, d = i % DCH;
-            ys[j][d] = (d < dn) ? yj[(size_t)j * ldy + d0 + d] : 0.0;
-        }
-        __syncthreads();
-        const int da = kg * (DCH / KG), db = min(dn, da + DCH / KG);
-#pragma unroll
-        for (int s = 0; s < 4; ++s) {
-            const int o = tx + s * 256;
-            if (o < n_out) {
-                const int j = o / m, c = o % m;
-                double a0 = 0.0, a1 = 0.0;
-                int d = da;
-                for (; d + 1 < db; d += 2) {
-                    a0 = fma(ys[j][d], st[(size_t)(d0 + d) * cp + c], a0);
-                    a1 = fma(ys[j][d + 1], st[(size_t)(d0 + d + 1) * cp + c], a1);
-                }
-                if (d < db) a0 = fma(ys[j][d], st[(size_t)(d0 + d) * cp + c], a0);
-                acc[s] += a0 + a1;
-            }
-        }
-    }
-#pragma unroll
-    for (int s = 0; s < 4; ++s) {
-        const int o = tx + s * 256;
-        if (o < n_out) part[kg][o] = acc[s];
-    }
-    __syncthreads();
-    for (int o = threadIdx.x; o < n_out; o += 1024) bl[o] = ((part[0][o] + part[1][o]) + part[2][o]) + part[3][o];
-    __syncthreads();
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    for (int j = wave; j < n; j += 16) {
-        double mn = INFINITY, mx = -INFINITY;
-        int bad = 0;
-        for (int c = lane; c < m; c += 64) {
-            const double v = bl[j * m + c];
-            bad |= (v != v) ? 1 : 0;
-            mn = fmin(mn, v);
-            mx = fmax(mx, v);
-        }
-#pragma unroll
-        for (int s = 1; s < 64; s <<= 1) {
-            mn = fmin(mn, __shfl_xor(mn, s));
-            mx = fmax(mx, __shfl_xor(mx, s));
-            bad |= __shfl_xor(bad, s);
-        }
-        int8_t* __restrict__ o = out + jobs[job].out_off + (int64_t)j * m;
-        const double den = mx - mn;
-        for (int c = lane; c < m; c += 64) o[c] = quant127(bl[j * m + c] - mn, den, bad != 0);
-    }
-}
-#endif
-
-// ---------------------------------------------------------------------------
 // K2s: stage B of a small call (a protein per call: one or two jobs).  One workgroup per job spent 46 us on the D-long
 // sums -- three quarters of the call's GPU time -- so the channels are spread over workgroups of 64: each adds its slab's
 // share of the job's n x m block (FROM_SPLIT: after adding the row chunks of stage_a_split_kernel and scaling its 64
@@ -996,39 +919,6 @@ __device__ inline void wave_min_max48(double& mn, double& mx) {
     mx = fmax(fmax(lane_value(mx, 0), lane_value(mx, 16)), lane_value(mx, 32));
 }
 
-// Transposition of a 4 x 4 arrangement across the four 16-lane rows of a wave: in, lane row g holds r[h]; out, lane row g
-// holds o[i] = (what lane row i held in r[g]), same lane inside the row.  v_permlane32_swap exchanges the upper half of its
-// first operand with the lower half of the second, v_permlane16_swap the odd rows of the first with the even rows of the
-// second (tools/microbench/permlane_swap_probe.hip): two of each per 32-bit register quartet.
-__device__ inline void lane_rows_swap32(uint32_t& a, uint32_t& b) {
-    const v2u32 r = __builtin_amdgcn_permlane32_swap(a, b, false, false);
-    a = r[0];
-    b = r[1];
-}
-__device__ inline void lane_rows_swap16(uint32_t& a, uint32_t& b) {
-    const v2u32 r = __builtin_amdgcn_permlane16_swap(a, b, false, false);
-    a = r[0];
-    b = r[1];
-}
-template <int NOUT>  // the first NOUT (2 or 4) of the transposed values are wanted
-__device__ inline void lane_rows_transpose(const double (&r)[4], double (&o)[NOUT]) {
-    uint32_t w[4][2];
-#pragma unroll
-    for (int h = 0; h < 4; ++h) {
-        w[h][0] = (uint32_t)__double2loint(r[h]);
-        w[h][1] = (uint32_t)__double2hiint(r[h]);
-    }
-#pragma unroll
-    for (int c = 0; c < 2; ++c) {
-        lane_rows_swap32(w[0][c], w[2][c]);  // w0 = [r0.0 r0.1 r2.0 r2.1]   w2 = [r0.2 r0.3 r2.2 r2.3]   (rX.g = lane row g of r[X])
-        lane_rows_swap32(w[1][c], w[3][c]);  // w1 = [r1.0 r1.1 r3.0 r3.1]   w3 = [r1.2 r1.3 r3.2 r3.3]
-        lane_rows_swap16(w[0][c], w[1][c]);  // w0 = [r0.0 r1.0 r2.0 r3.0]   w1 = [r0.1 r1.1 r2.1 r3.1]
-        if constexpr (NOUT > 2) lane_rows_swap16(w[2][c], w[3][c]);  // w2 = [r0.2 r1.2 r2.2 r3.2]   w3 = [r0.3 r1.3 r2.3 r3.3]
-    }
-#pragma unroll
-    for (int i = 0; i < NOUT; ++i) o[i] = __hiloint2double((int)w[i][1], (int)w[i][0]);
-}
-
 // The row two overlapping windows share, as Embedding.embed_seq leaves it (src/embedding.py:185-187): float32 (old + new) / 2 --
 // the sum rounded to float32, the halving exact -- the very expression of stitch_rows_kernel.
 template <typename R>
@@ -1081,7 +971,7 @@ struct Run {
 
 // WIN: builds that also take two-source pieces (PieceA::ptr2; float32 rows) -- builds of their own, because the fused variants sit
 // exactly at their register budget and the second row stream costs the ordinary calls nothing this way.
-template <typename T, int S, int G, int NT, int UNROLL, bool FUSED, bool MA = false, bool WIN = false>
+template <typename T, int S, int G, int NT, int UNROLL, bool FUSED, bool WIN = false>
 __global__ __launch_bounds__(S * 64, S >= 10 ? 3 : DCTFP_WALK_MIN_WAVES) void walk_ab_kernel(const JobA* __restrict__ jobs, const JobB* __restrict__ jobb,
                                                           const Walk* __restrict__ walks, const Run* __restrict__ runs,
                                                           const PieceA* __restrict__ pieces, const double* __restrict__ stf,
@@ -1135,24 +1025,6 @@ __global__ __launch_bounds__(S * 64, S >= 10 ? 3 : DCTFP_WALK_MIN_WAVES) void wa
     uint32_t group_job = run.job_begin;  // job of slot 0
     DCTFP_TL_DECL
 
-    // MA, rare path: bit e = my channel e differs somewhere in the job from the job's first row (an exactly constant
-    // channel has no bit: its F must be exactly 0).  One more pass over the job's rows, by the whole wave.
-    auto differs_from_first_row = [&](const JobA& jb) {
-        const PieceA* __restrict__ pcs = pieces + jb.piece_begin;
-        const Rw r0 = load_raw<T, VEC>(reinterpret_cast<const T*>(pcs[0].ptr) + colc);
-        uint32_t dif = 0;
-        for (uint32_t p = 0; p < jb.n_pieces; ++p) {
-            const PieceA piece = pcs[p];
-            const __amdgpu_buffer_rsrc_t rows = wave_buffer(piece.ptr);
-            for (uint32_t r = 0; r < piece.n_rows; ++r) {
-                const Rw x = buffer_load_raw<Rw, false>(rows, col_bytes, (int)r * ld_bytes);
-#pragma unroll
-                for (int e = 0; e < VEC; ++e) dif |= (raw_elem<T, VEC>(x, e) != raw_elem<T, VEC>(r0, e) ? 1u : 0u) << e;
-            }
-        }
-        return dif;
-    };
-
     for (uint32_t wi = 0; wi < run.n_walks; ++wi) {
         const Walk wk = walks[run.walk_begin + wi];
         const bool has_w = FUSED && wk.whole_job >= 0;
@@ -1164,7 +1036,6 @@ __global__ __launch_bounds__(S * 64, S >= 10 ? 3 : DCTFP_WALK_MIN_WAVES) void wa
             for (int k = 0; k < (FUSED ? NK : 1); ++k) wacc[k][v] = 0.0;
         // rows of the whole protein = offset of the prefix sums behind its cosine table
         const uint32_t w_rows = has_w ? jobs[wk.whole_job].n_rows : 0u;
-        uint32_t w_suspect = 0xfu;  // MA: bit e = my channel e was within the round-off bound of a constant channel in every part so far
 
         for (uint32_t part = 0; part < n_walk_jobs; ++part) {
             double f[NK][VEC];
@@ -1181,120 +1052,6 @@ __global__ __launch_bounds__(S * 64, S >= 10 ? 3 : DCTFP_WALK_MIN_WAVES) void wa
                 // ---- stage A of one job: every row of this wave's 256 channels
                 const JobA job = jobs[wk.job_begin + part];
                 const PieceA* __restrict__ pc = pieces + job.piece_begin;
-                if constexpr (MA) {
-                // ---- the multiply-adds of stage A on the matrix pipe (fused walks of float32 rows).  The fused walks run the
-                // package into its power limit; a float64 multiply-add costs 2.6 x less energy in an MFMA
-                // than in v_fma_f64 (tools/microbench/power_pipes.hip, stage_a_pipes.hip).  One load instruction fetches 4
-                // consecutive rows x 64 channels: lane (q, g) = (lane & 15, lane >> 4) reads row r + g, the 16 bytes lane
-                // 16 h + q of the vector layout owns (chunk h = 0..3: the same two 512-byte segments per row and wave as
-                // before, in 256-byte halves) -- which IS the B operand layout B[k = lane >> 4][j = lane & 3] of the four
-                // 4 x 4 x 4 blocks, no shuffle.  The A operand A[i = lane & 3][k = lane >> 4] is one double per lane and 4-row
-                // step: cos of {part k=1, part k=2, whole k=1, whole k=2} at row r + k, straight from the cosine tables.
-                // D[i = lane >> 4][j]: 16 MFMAs per step leave 4 outputs x 256 channels in macc.  Per element that is one
-                // v_cvt_f64_f32 and a sixteenth of an MFMA -- no subtraction: the cosines of a job sum to zero, so the first-row
-                // shift of the vector path only matters for an exactly constant channel (which must give exactly 0, not the
-                // round-off of sum c(t) x).  That case is caught afterwards: |F| below the round-off bound of a constant channel
-                // -> the wave re-reads the job and compares (differs_from_first_row, above); no healthy channel comes near the bound.
-                // Outcome: same bytes, a quarter of the vector instructions, 6-11 % more shader clock -- and the
-                // same kernel time to 0.1 %: the fused walks do not hang on the clock.  Kept as an experiment (libdctfp_experiments.so,
-                // option ab_mfma_a); at four waves per SIMD it spills, so A/B it in a build with -DDCTFP_WALK_MIN_WAVES=3.
-                static_assert(!MA || (FUSED && sizeof(T) == 4 && VEC == 4 && UNROLL % 4 == 0), "matrix-pipe stage A: fused walks of float32 rows");
-                const int mq = lane & 15, mg = lane >> 4;
-                int mcol[4];  // my 16 bytes inside a row, per chunk
-#pragma unroll
-                for (int h = 0; h < 4; ++h) {
-                    const int p0 = wave * (WCH / 2) + 64 * (h & 1) + VEC * mq;
-                    mcol[h] = (p0 >= half ? 0 : (h >= 2 ? n_cols - VEC - p0 : p0)) * (int)sizeof(T);
-                }
-                const int n_act = (half - wave * (WCH / 2) + 63) / 64;  // chunk pairs (h, h + 2) that hold channels: <= 0, 1, >= 2
-                // macc[h][e]: lane (q, i = lane >> 4) holds output i (0, 1: the part's F1, F2; 2, 3: the whole protein's share of this
-                // part) of channel colc(lane 16 h + q) + e
-                double macc[4][4];
-#pragma unroll
-                for (int h = 0; h < 4; ++h)
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) macc[h][e] = 0.0;
-                // (my channels' first row, for the round-off bound at the end: asked for now, its latency under the stream's)
-                const Rw rp = load_raw<T, VEC>(reinterpret_cast<const T*>(pc[0].ptr) + colc);
-                typedef const double __attribute__((address_space(1))) * GD;
-                auto stream_piece = [&](auto nch_tag, const PieceA& piece) {
-                    constexpr int NCH = decltype(nch_tag)::value;
-                    const __amdgpu_buffer_rsrc_t rows = wave_buffer(piece.ptr);
-                    const bool whole_lane = has_w && (lane & 2);  // (a walk without whole protein: outputs 2, 3 repeat 0, 1, unused)
-                    const GD ap = (GD)(uintptr_t)((whole_lane ? job.w_basis + (size_t)piece.w0 * NK : job.basis + (size_t)piece.t0 * NK) +
-                                                  mg * NK + (lane & 1));
-                    auto load_step = [&](Rw (&x)[4], int lane_rows, uint32_t r) {
-#pragma unroll
-                        for (int h = 0; h < 4; ++h)
-                            if ((h & 1) < NCH) x[h] = buffer_load_raw<Rw, true>(rows, mcol[h] + lane_rows, (int)r * ld_bytes);
-                    };
-                    auto step = [&](const Rw (&x)[4], double a) {
-#pragma unroll
-                        for (int h = 0; h < 4; ++h)
-                            if ((h & 1) < NCH) {
-#pragma unroll
-                                for (int e = 0; e < 4; ++e)
-                                    macc[h][e] = __builtin_amdgcn_mfma_f64_4x4x4f64(a, (double)x[h][e], macc[h][e], 0, 0, 0);
-                            }
-                    };
-                    constexpr int STEPS = UNROLL / 4;
-                    const int my_rows = mg * ld_bytes;
-                    uint32_t r = 0;
-                    for (; r + 4 * STEPS <= piece.n_rows; r += 4 * STEPS) {
-                        Rw x[STEPS][4];
-                        double a[STEPS];
-#pragma unroll
-                        for (int st = 0; st < STEPS; ++st) {
-                            load_step(x[st], my_rows, r + 4 * st);
-                            a[st] = ap[(size_t)(r + 4 * st) * NK];
-                        }
-#pragma unroll
-                        for (int st = 0; st < STEPS; ++st) step(x[st], a[st]);
-                    }
-                    if (r < piece.n_rows) {  // the last 1-7 rows in one round of loads: the lanes past the end repeat the piece's
-                        const int rem = (int)(piece.n_rows - r);  // last row with cosine 0
-                        const int rr0 = min(mg, rem - 1), rr1 = min(4 + mg, rem - 1);
-                        Rw x[2][4];
-                        load_step(x[0], rr0 * ld_bytes, r);
-                        const double a0 = ap[((int64_t)r + rr0 - mg) * NK];
-                        double a1 = 0.0;
-                        if (rem > 4) {
-                            load_step(x[1], rr1 * ld_bytes, r);
-                            a1 = ap[((int64_t)r + rr1 - mg) * NK];
-                        }
-                        step(x[0], mg < rem ? a0 : 0.0);
-                        if (rem > 4) step(x[1], 4 + mg < rem ? a1 : 0.0);
-                    }
-                };
-                for (uint32_t p = 0; p < job.n_pieces; ++p) {
-                    const PieceA piece = pc[p];
-                    if (n_act >= 2) stream_piece(std::integral_constant<int, 2>{}, piece);
-                    else if (n_act == 1) stream_piece(std::integral_constant<int, 1>{}, piece);
-                }
-                // back to the vector layout: lane l = 16 g + q owns colc(l) + e = the channels of chunk g -> after the lane-row
-                // transposition of macc[0..3][e] every lane holds the four outputs of its own channel e.
-                uint32_t suspect = 0;
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const double r4[4] = {macc[0][e], macc[1][e], macc[2][e], macc[3][e]};
-                    double o[4];
-                    lane_rows_transpose<4>(r4, o);
-                    f[0][e] = o[0];
-                    f[1][e] = o[1];
-                    wacc[0][e] += o[2];
-                    wacc[1][e] += o[3];
-                    // round-off of an exactly constant channel: |sum c(t) x| <= |x| (L 2^-51 + L^2 2^-54); 16 x that
-                    const double bound = fabs((double)rp[e]) * ((double)job.n_rows * (double)job.n_rows) * 0x1p-50;
-                    suspect |= (fabs(o[0]) <= bound && fabs(o[1]) <= bound ? 1u : 0u) << e;
-                }
-                w_suspect &= suspect;  // a channel constant over the whole protein is constant in every part
-                if (__builtin_amdgcn_ballot_w64(suspect != 0 && !pad) != 0) {
-                    const uint32_t dif = differs_from_first_row(job);
-#pragma unroll
-                    for (int e = 0; e < 4; ++e)
-                        if (!((dif >> e) & 1)) f[0][e] = f[1][e] = 0.0;
-                }
-                } else {
                 double ref[VEC];
 #pragma unroll
                 for (int k = 0; k < NK; ++k)
@@ -1433,19 +1190,6 @@ __global__ __launch_bounds__(S * 64, S >= 10 ? 3 : DCTFP_WALK_MIN_WAVES) void wa
                     }
                 }
                 }  // !pad
-                }  // !MA
-            } else if constexpr (MA) {
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    f[0][e] = wacc[0][e];
-                    f[1][e] = wacc[1][e];
-                }
-                if (__builtin_amdgcn_ballot_w64(w_suspect != 0 && !pad) != 0) {
-                    const uint32_t dif = differs_from_first_row(jobs[wk.whole_job]);
-#pragma unroll
-                    for (int e = 0; e < 4; ++e)
-                        if (!((dif >> e) & 1)) f[0][e] = f[1][e] = 0.0;
-                }
             } else {
 #pragma unroll
                 for (int k = 0; k < NK; ++k)
@@ -1468,8 +1212,6 @@ __global__ __launch_bounds__(S * 64, S >= 10 ? 3 : DCTFP_WALK_MIN_WAVES) void wa
                     c4 |= code << (8 * v);
                     __builtin_amdgcn_sched_barrier(0);  // one channel at a time (register pressure)
                 }
-                int sl = lane;
-                if constexpr (MA) asm volatile("" : "+v"(sl));
                 if (pending == 0 && done_expected != 0) {  // first write of a flush group: the rows of the last one must be out
                     DCTFP_TL_MARK(1);
                     while (__hip_atomic_load(&lds_done, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) != done_expected)
@@ -1477,8 +1219,8 @@ __global__ __launch_bounds__(S * 64, S >= 10 ? 3 : DCTFP_WALK_MIN_WAVES) void wa
                     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
                     DCTFP_TL_MARK(5);
                 }
-                *reinterpret_cast<v4d*>(&lds_t[wave][pending][VEC * sl]) = (v4d){tv[0], tv[1], tv[2], tv[3]};
-                lds_c[wave][pending][sl] = c4;
+                *reinterpret_cast<v4d*>(&lds_t[wave][pending][VEC * lane]) = (v4d){tv[0], tv[1], tv[2], tv[3]};
+                lds_c[wave][pending][lane] = c4;
             }
             ++pending;
             DCTFP_TL_MARK(1);
@@ -1530,7 +1272,7 @@ __global__ __launch_bounds__(S * 64, S >= 10 ? 3 : DCTFP_WALK_MIN_WAVES) void wa
                 // k-step took 2 600 cycles against 255 of its 15 MFMAs (tools/walk_timeline.py, profiles/r03).
                 // As deep as the registers allow without spilling (the loads go through a buffer descriptor: no address
                 // registers): 4 steps where the budget is 168 registers (10 waves), 2 where the kernel carries no second accumulator set.
-                constexpr int DEPTH = DCTFP_WALK_B_DEPTH ? DCTFP_WALK_B_DEPTH : (S >= 10 ? (MA ? 2 : 4) : (FUSED ? 1 : 2));
+                constexpr int DEPTH = DCTFP_WALK_B_DEPTH ? DCTFP_WALK_B_DEPTH : (S >= 10 ? 4 : (FUSED ? 1 : 2));
                 static_assert(DEPTH == 1 || DEPTH == 2 || DEPTH == 4, "slot of a k-step must be static under the 4-step unroll");
                 double bq[DEPTH][NT];
                 if (n_q > 0) {
@@ -1585,10 +1327,7 @@ __global__ __launch_bounds__(S * 64, S >= 10 ? 3 : DCTFP_WALK_MIN_WAVES) void wa
             // float32 variants at the 128-register budget take them one by one (together they spill 4 registers per lane).
             constexpr int ROWS = (FUSED && S < 10 && sizeof(T) == 4) ? 1 : 3;
             auto finish_job = [&](uint32_t g) {
-                // (MA: the lane index through an opaque copy, like the flush above -- the store offsets and masks derived from it
-                //  would otherwise be computed at the top of the kernel and held in ~20 registers through the row stream)
-                int lane = threadIdx.x & 63;
-                if constexpr (MA) asm volatile("" : "+v"(lane));
+                const int lane = threadIdx.x & 63;
                 const int hm = (m + 1) >> 1;
                 const bool valid0 = lane < hm;
                 const bool valid1 = lane < hm && (m - 1 - lane) != lane;  // odd m: the middle column is its own mirror (O = 0 there)
@@ -1990,246 +1729,6 @@ __global__ __launch_bounds__(FUSED ? 640 : 1024) void walk_gen_kernel(const JobA
             if (lane == 0) __hip_atomic_fetch_add(&counters[2 + slot], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
         }
     }
-    }
-}
-
-// ---------------------------------------------------------------------------
-// K1s: a SMALL call -- a protein at a time, the reference's own calling pattern (src/make_db.py:29-30) -- in ONE launch (round 5).
-// Such a call is the latency of a dependent chain, not bandwidth: stage_a_split_kernel -> stage_b_slab_kernel ->
-// stage_b_finish_kernel were three launches, ~ 22 us on the GPU of a 56-us call (profiles/r05/pcie_inclusive_rate.txt).  Here the
-// same three steps hand over inside one grid, by tickets: nobody waits for anybody (a workgroup that is not the last of its group
-// to arrive is done), so no assumption about which workgroups are resident together.
-//
-//   grid   : jobs x row chunks x 256-channel slabs (as stage_a_split_kernel), 8 waves each.
-//   step 1 : every workgroup: the partial sums of its rows for its 256 channels -> `partial` (global), fence, ticket of
-//            (job, slab).
-//   step 2 : the LAST workgroup of a (job, slab) to arrive: adds the chunks in chunk order, scales its 256 channels
-//            (scale_channel<3>) into LDS, contracts them against the stage-B basis -- a wave per 32 channels, all eight k-steps of
-//            fragments in flight at once (one L2 round trip), v_mfma_f64_4x4x4, rows = the 3 resampled rows -- adds the eight
-//            waves' blocks in wave order -> `zpart` (global), fence, ticket of the job.
-//   step 3 : the LAST slab of a job to arrive: adds the slabs in slab order, scales the three rows over their m values, writes
-//            the int8 block (into pinned host memory for a one-protein call).
-// Every sum runs in a fixed order, whoever does it: the bytes do not depend on the order of arrival.  The tickets are reset by
-// their last taker; the host zeroes them once, when it allocates them.
-// OUTCOME (profiles/r05/pcie_rate_one_launch.txt against pcie_rate_three_launches.txt): bit-exact, and SLOWER -- 86 us per
-// one-protein call against 57 with the three kernels.  The eight XCDs of the chip do not share an L2: what one workgroup wrote
-// reaches a workgroup on another XCD through an agent-scope release (L2 write-back) and acquire (L2 invalidate) per workgroup
-// and step, and the tickets are memory-side atomics -- dearer than the two launch boundaries they replace, which do the same
-// once for the whole grid.  Kept behind the option "small_one" (default 0) with its parity test; the dispatch does not pick it.
-//   stp    : the plain basis in fragment order (host: get_st_plain), NT = cp / 16 column groups (m <= 80: NT <= 5).
-// ---------------------------------------------------------------------------
-template <int WAVES, int UNROLL>
-__global__ __launch_bounds__(WAVES * 64) void small_call_kernel(const JobA* __restrict__ jobs, const JobB* __restrict__ jobb,
-                                                                 const PieceA* __restrict__ pieces, double* __restrict__ partial,
-                                                                 double* __restrict__ zpart, uint32_t* __restrict__ tickets, int n_jobs,
-                                                                 int n_chunks, uint32_t chunk_rows, int n_cols, int64_t ld, int ldy,
-                                                                 int n_slabs, const double* __restrict__ stp, int m, InvTab<3> inv,
-                                                                 unsigned long long* __restrict__ degenerate, int8_t* __restrict__ out) {
-    typedef float T;
-    constexpr int N = 3, NK = 2, VEC = 4, NTC = 5, SLAB = 64 * VEC;
-    static_assert(WAVES == 8, "a wave per 32 channels of the slab in step 2");
-    __shared__ double red[WAVES][NK * VEC][64];      // step 1: per-wave sums; step 2: Y'[3][256] + the waves' partial blocks [8][3][80]
-    __shared__ uint32_t last_flag;
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const uint32_t slab = blockIdx.x % (uint32_t)n_slabs;
-    const uint32_t jc = blockIdx.x / (uint32_t)n_slabs;
-    const uint32_t chunk = jc % (uint32_t)n_chunks, job_id = jc / (uint32_t)n_chunks;
-    const int col0 = ((int)slab * 64 + lane) * VEC;
-    const int colc = (col0 < n_cols) ? col0 : 0;
-    const JobA job = jobs[job_id];
-    // ---- step 1 (stage_a_split_kernel's body)
-    {
-        const PieceA* __restrict__ pc = pieces + job.piece_begin;
-        const uint32_t lo = chunk * chunk_rows;
-        const uint32_t hi = min(job.n_rows, lo + chunk_rows);  // this workgroup's rows of the job: [lo, hi)
-        double acc[NK][VEC];
-        double ref[VEC];
-#pragma unroll
-        for (int k = 0; k < NK; ++k)
-#pragma unroll
-            for (int v = 0; v < VEC; ++v) acc[k][v] = 0.0;
-        if (lo < hi) {
-            {
-                auto r0 = load_raw<T, VEC>(reinterpret_cast<const T*>(pc[0].ptr) + colc);
-#pragma unroll
-                for (int v = 0; v < VEC; ++v) ref[v] = raw_elem<T, VEC>(r0, v);
-            }
-            const CosTab bt = cos_tab(job.basis);
-            for (uint32_t p = 0; p < job.n_pieces; ++p) {
-                const PieceA piece = pc[p];
-                const uint32_t a = max(lo, piece.t0), b = min(hi, piece.t0 + piece.n_rows);  // job rows of this piece in the chunk
-                if (a >= b) continue;
-                const T* __restrict__ base = reinterpret_cast<const T*>(piece.ptr) + colc;
-                auto row_update = [&](const typename Raw<T, VEC>::type& x, uint32_t t) {  // t = row of the job
-                    const CosTab c = bt + (size_t)t * NK;
-#pragma unroll
-                    for (int v = 0; v < VEC; ++v) {
-                        const double d = raw_elem<T, VEC>(x, v) - ref[v];
-#pragma unroll
-                        for (int k = 0; k < NK; ++k) acc[k][v] = fma(c[k], d, acc[k][v]);
-                    }
-                };
-                uint32_t t = a + (uint32_t)wave;
-                for (; t + (UNROLL - 1) * WAVES < b; t += UNROLL * WAVES) {
-                    typename Raw<T, VEC>::type xv[UNROLL];
-#pragma unroll
-                    for (int u = 0; u < UNROLL; ++u) xv[u] = load_raw<T, VEC>(base + (size_t)(t + u * WAVES - piece.t0) * ld);
-#pragma unroll
-                    for (int u = 0; u < UNROLL; ++u) row_update(xv[u], t + u * WAVES);
-                }
-                for (; t < b; t += WAVES) {
-                    auto x1 = load_raw<T, VEC>(base + (size_t)(t - piece.t0) * ld);
-                    row_update(x1, t);
-                }
-            }
-        }
-#pragma unroll
-        for (int k = 0; k < NK; ++k)
-#pragma unroll
-            for (int v = 0; v < VEC; ++v) red[wave][k * VEC + v][lane] = acc[k][v];
-        __syncthreads();
-        for (int cl = threadIdx.x; cl < SLAB; cl += WAVES * 64) {
-            const int ln = cl / VEC, v = cl % VEC;
-            const int col = (int)slab * SLAB + cl;
-            if (col >= ldy) continue;
-#pragma unroll
-            for (int k = 0; k < NK; ++k) {
-                double sum = red[0][k * VEC + v][ln];
-#pragma unroll
-                for (int w = 1; w < WAVES; ++w) sum += red[w][k * VEC + v][ln];
-                store_through(&partial[((size_t)jc * NK + k) * ldy + col], sum);
-            }
-        }
-    }
-    // ---- ticket of (job, slab): the last of its n_chunks workgroups goes on
-    __threadfence();
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        uint32_t* __restrict__ tk = tickets + (size_t)job_id * n_slabs + slab;
-        const uint32_t t = __hip_atomic_fetch_add(tk, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
-        const bool last = t == (uint32_t)n_chunks - 1u;
-        if (last) __hip_atomic_store(tk, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // (for the next call)
-        last_flag = last ? 1u : 0u;
-    }
-    __syncthreads();
-    if (last_flag == 0) return;
-    __threadfence();
-    // ---- step 2: my 256 channels of the job, scaled, against the basis
-    double* const ys = &red[0][0][0];                 // [3][SLAB]
-    double* const pzb = ys + N * SLAB;                // [WAVES][3][16 NTC]
-    static_assert((size_t)N * SLAB + (size_t)WAVES * N * 16 * NTC <= (size_t)WAVES * NK * VEC * 64, "step 2 fits the reduction buffer");
-    const int NT = (m + 15) >> 4, cp = 16 * NT;
-    const int d0 = (int)slab * SLAB;
-    if ((int)threadIdx.x < SLAB) {
-        const int d = d0 + (int)threadIdx.x;
-        double f[2] = {0.0, 0.0};
-        if (d < ldy) {
-            const double* __restrict__ pj = partial + ((size_t)job_id * n_chunks) * NK * ldy + d;
-            // chunk order; sixteen chunks' loads in flight at a time (a loop of unknown length issued them one by one, each a round
-            // trip to where the other workgroups' write-through stores went: 16 x 2 dependent latencies in the chain of a call)
-            for (int c0 = 0; c0 < n_chunks; c0 += 16) {
-                double pv[16][NK];
-#pragma unroll
-                for (int i = 0; i < 16; ++i)
-#pragma unroll
-                    for (int k = 0; k < NK; ++k)
-                        pv[i][k] = (c0 + i < n_chunks) ? __builtin_nontemporal_load(pj + ((size_t)(c0 + i) * NK + k) * ldy) : 0.0;
-#pragma unroll
-                for (int i = 0; i < 16; ++i)
-                    if (c0 + i < n_chunks) {
-#pragma unroll
-                        for (int k = 0; k < NK; ++k) f[k] += pv[i][k];
-                    }
-            }
-        }
-        double z[3];
-        scale_channel<3>(f, inv, d >= n_cols, z, degenerate);
-#pragma unroll
-        for (int j = 0; j < N; ++j) ys[j * SLAB + threadIdx.x] = z[j];
-    }
-    __syncthreads();
-    {
-        const int i4 = lane & 3, k4 = lane >> 4;
-        const int wch = d0 + 32 * wave;                                       // my 32 channels: k-steps wch / 4 + 0 .. 7
-        const int steps = min(8, max(0, (n_cols - wch + 3) >> 2));
-        const __amdgpu_buffer_rsrc_t frag = wave_buffer(stp + ((size_t)(wch >> 2) * NT) * 64);
-        double b[8][NTC];
-#pragma unroll
-        for (int q = 0; q < 8; ++q)
-#pragma unroll
-            for (int c = 0; c < NTC; ++c)
-                b[q][c] = (q < steps && c < NT) ? buffer_load_raw<double, false>(frag, lane * 8, (q * NT + c) * 512) : 0.0;
-        double acc[NTC];
-#pragma unroll
-        for (int c = 0; c < NTC; ++c) acc[c] = 0.0;
-#pragma unroll
-        for (int q = 0; q < 8; ++q) {
-            const double a = ys[min(i4, N - 1) * SLAB + 32 * wave + 4 * q + k4];   // (a channel past D holds 0, a step past `steps` meets b = 0)
-#pragma unroll
-            for (int c = 0; c < NTC; ++c) acc[c] = __builtin_amdgcn_mfma_f64_4x4x4f64(a, b[q][c], acc[c], 0, 0, 0);
-        }
-        // D[i = lane >> 4][j = lane & 3] of block (lane >> 2) & 3: row lane >> 4, column 16 c + (lane & 15)
-        const int row = lane >> 4;
-        if (row < N) {
-#pragma unroll
-            for (int c = 0; c < NTC; ++c)
-                if (c < NT) pzb[((size_t)wave * N + row) * (16 * NTC) + 16 * c + (lane & 15)] = acc[c];
-        }
-    }
-    __syncthreads();
-    const int n_out = N * m;
-    double* __restrict__ zp = zpart + ((size_t)job_id * n_slabs + slab) * (N * 16 * NTC);
-    for (int o = threadIdx.x; o < N * cp; o += WAVES * 64) {
-        const int j = o / cp, c = o % cp;
-        double sum = 0.0;
-#pragma unroll
-        for (int w = 0; w < WAVES; ++w) sum += pzb[((size_t)w * N + j) * (16 * NTC) + c];   // wave order
-        store_through(&zp[j * (16 * NTC) + c], sum);
-    }
-    // ---- ticket of the job: the last of its n_slabs slabs goes on
-    __threadfence();
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        uint32_t* __restrict__ tk = tickets + (size_t)n_jobs * n_slabs + job_id;
-        const uint32_t t = __hip_atomic_fetch_add(tk, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
-        const bool last = t == (uint32_t)n_slabs - 1u;
-        if (last) __hip_atomic_store(tk, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        last_flag = last ? 1u : 0u;
-    }
-    __syncthreads();
-    if (last_flag == 0) return;
-    __threadfence();
-    // ---- step 3: the slabs in slab order, per-row min-max scale, int8 (src/fingerprint.py:193-195)
-    double* const bl = ys;                            // [3][m]  (everybody is past the partial blocks: the barrier above)
-    for (int o = threadIdx.x; o < n_out; o += WAVES * 64) {
-        const int j = o / m, c = o % m;
-        const double* __restrict__ zj = zpart + (size_t)job_id * n_slabs * (N * 16 * NTC) + j * (16 * NTC) + c;
-        double sum = 0.0;
-        for (int s0 = 0; s0 < n_slabs; s0 += 8) {   // slab order, eight loads in flight
-            double zv[8];
-#pragma unroll
-            for (int i = 0; i < 8; ++i) zv[i] = (s0 + i < n_slabs) ? __builtin_nontemporal_load(zj + (size_t)(s0 + i) * (N * 16 * NTC)) : 0.0;
-#pragma unroll
-            for (int i = 0; i < 8; ++i)
-                if (s0 + i < n_slabs) sum += zv[i];
-        }
-        bl[o] = sum;
-    }
-    __syncthreads();
-    if (wave < N) {
-        const int j = wave;
-        const bool ok0 = lane < m, ok1 = lane + 64 < m;
-        const double v0 = ok0 ? bl[j * m + lane] : 0.0, v1 = ok1 ? bl[j * m + lane + 64] : 0.0;
-        double mn = fmin(ok0 ? v0 : INFINITY, ok1 ? v1 : INFINITY);
-        double mx = fmax(ok0 ? v0 : -INFINITY, ok1 ? v1 : -INFINITY);
-        const bool nan_here = (ok0 && v0 != v0) || (ok1 && v1 != v1);
-        wave_min_max64(mn, mx);
-        const bool bad = __builtin_amdgcn_ballot_w64(nan_here) != 0;   // a NaN anywhere in the row: the whole row is 0
-        const double den = mx - mn;
-        int8_t* __restrict__ o = out + jobb[job_id].out_off + (int64_t)j * m;
-        if (ok0) o[lane] = quant127(v0 - mn, den, bad);
-        if (ok1) o[lane + 64] = quant127(v1 - mn, den, bad);
     }
 }
 

@@ -1,5 +1,5 @@
 // Launchers of the gfx950 kernels, one translation unit per kernel family so that they compile side by side
-// (build_ext.py): the stage-A instantiations alone are two thirds of the device code.  dctfp.hip -- the host side of the C
+// (build_ext.py): the stage-A instantiations alone are a third of the device code.  dctfp.hip -- the host side of the C
 // ABI -- sees the parameter blocks and the launcher declarations below and no kernel template of these families.
 #pragma once
 
@@ -91,7 +91,7 @@ struct WParams {
     unsigned long long* degenerate;
     unsigned grid;
     hipStream_t stream;
-    bool two_source = false;  // some piece has PieceA::ptr2 (float32 rows, 8 rows in flight, 4 jobs per flush only)
+    bool two_source = false;  // some piece has PieceA::ptr2 (float32 rows, m <= 80 only)
 };
 
 // walk_gen_kernel: the shapes walk_ab_kernel does not take.
@@ -127,15 +127,15 @@ inline size_t gen_slot_bytes(int n, int m, int waves, int vec) {
 
 
 // stage A (k_stage_a_*.hip: one unit per storage type)
-void launch_a_f32(const AParams& p, int vec, int n, int waves, int unroll);
-void launch_a_f64(const AParams& p, int vec, int n, int waves, int unroll);
-void launch_a_f16(const AParams& p, int vec, int n, int waves, int unroll);
-void launch_a_bf16(const AParams& p, int vec, int n, int waves, int unroll);
+void launch_a_f32(const AParams& p, int vec, int n, int waves);
+void launch_a_f64(const AParams& p, int vec, int n, int waves);
+void launch_a_f16(const AParams& p, int vec, int n, int waves);
+void launch_a_bf16(const AParams& p, int vec, int n, int waves);
 // stage B on the matrix pipe (k_stage_b.hip)
 void launch_b_mfma(int nt, bool packed, unsigned grid, hipStream_t s, const char* yp, int64_t job_bytes, int64_t rows,
                    int ldy, const double* st, const JobB* jobs, int n, int m, int8_t* out);
 // the walk kernels (k_walk.hip, k_gen.hip)
-int launch_walk(const WParams& p, int dtype, int s, int g, int unroll, bool fused, bool mfma_a, LaunchError* err);
+int launch_walk(const WParams& p, int dtype, int s, bool fused, LaunchError* err);
 int launch_gen(const GParams& p, int dtype, int vec, int n, LaunchError* err);
 // the domain cutter's recursion (k_reccut.hip): LDS class of a protein (0 .. 3: 512 / 1024 / 1536 / 2048 residues), launch of one class
 constexpr int kCutClasses = 4;

@@ -409,9 +409,6 @@ int dctfp_crash_handler(int enable);
  *   "last_knn_slices" read only: database slices that owned a column in the last dctfp_l1_knn launch (1: no merge kernels)
  *   "knn_calls"    read only: dctfp_l1_knn launches of this context so far
  *   "fuse"         1 (default) = proteins given as parts + whole protein are streamed once
- *   "small_one"    1 = a call below 128 job-slabs of the production shape (float32 rows, n = 3, m <= 80) in ONE launch
- *                  (small_call_kernel); 0 (default) = three kernels -- the faster form on this chip (dctfp.hip).
- *                  "last_small_one" (read only): whether the last dctfp_quantize went that way
  *   "gen_fuse"     1 (default) = ... also by the general walk kernel ("path" = 2, n <= 5, at most ten waves per workgroup);
  *                  0 = it streams every job on its own, as through round 4.  "last_gen_fused" (read only): whether the last
  *                  dctfp_quantize launched the general walk kernel with fused walks
@@ -432,22 +429,18 @@ int dctfp_crash_handler(int enable);
  * Engineering knobs -- ONLY in libdctfp_experiments.so, the same sources built with -DDCTFP_EXPERIMENTS (A/B measurements
  * under tools/, kernel-variant parity tests); libdctfp.so answers DCTFP_ERR_INVALID "unknown option" to them.  Their
  * defaults are what is measured and shipped:
- *   "ab_group"     walk kernel: jobs per stage-B flush (0 = auto = 4, 3, 4)
- *   "ab_unroll"    walk kernel: rows in flight per wave (0 = 8; 4, 6, 8, 12, 16; float32 rows only)
  *   "ab_run_jobs"  walk kernel: jobs per workgroup (0 = by the bytes per job and the size of the call)
  *   "ab_align"     walk kernel: walks to look ahead for a workgroup whose job count is a multiple of the flush group, so that
  *                  its last flush is a full one (default 2; 0 = off)
  *   "ab_taper"     walk kernel: the jobs of the last N quarter-rounds of workgroups go out in workgroups of one flush
  *                  group, so that the launch ends evenly (default 4 = one round; 0 = off)
- *   "ab_mfma_a"    walk kernel, fused walks of float32 rows: 1 = the multiply-adds of stage A as v_mfma_f64_4x4x4 on
- *                  4-row x 64-channel loads, no first-row shift (an experiment of round 3: same bytes, same rate; default 0)
  *   "ab_longest_first" walk kernel: workgroups ordered by the rows they stream, longest first (0 = auto: batches of
  *                  domains at D > 1280, 1 = always, 2 = never)
  *   "small_b_jobs" two-kernel path: calls with fewer jobs (layers x domains) than this run stage B over 64-channel slabs
  *                  instead of the MFMA kernel (default 512)
- *   "stage_b"      two-kernel path: 0 = plain VALU stage B, 1 = MFMA f64 kernel (default)
- *   "a_waves"      two-kernel path: waves per stage-A workgroup: 0 = by average rows per job (default), 2, 4, 8, 16
- *   "a_unroll"     two-kernel path: rows in flight per wave (4 or 8)
+ *   "a_waves"      two-kernel path: waves per stage-A workgroup: 0 = by average rows per job (default), 2, 4, 8, 16 --
+ *                  a forced count goes through the same rules as the automatic one (16 at 4 channels per lane only, at most
+ *                  4 at 8 channels per lane, n >= 4 always 4), so it selects one of the builds the automatic choice uses
  *   "overlap"      two-kernel path: sub-chunks of a large batch whose stage B runs on a side stream under the
  *                  next sub-chunk's stage A (1 = off, default 4)
  *   "pack_y"       two-kernel path, 1 (default) = n = 3: the scratch between the kernels holds {0, t, 1} as one

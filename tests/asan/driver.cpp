@@ -517,10 +517,10 @@ int main(int argc, char** argv) {
         const int64_t out_stride = off + (uni(0, 2) == 0 ? 16 : 0);
         std::vector<int8_t> out((size_t)n_domains * out_stride);
         // ---- options
-        static const char* names[] = {"path", "fuse", "ab_run_jobs", "ab_longest_first", "workspace_mb", "overlap", "ab_group", "pack_y", "small_b_jobs", "a_waves", "gen_fuse"};
+        static const char* names[] = {"path", "fuse", "ab_run_jobs", "ab_longest_first", "workspace_mb", "overlap", "pack_y", "small_b_jobs", "a_waves", "gen_fuse"};
         std::vector<std::pair<const char*, int64_t>> saved;
         for (int i = 0; i < uni(0, 3); ++i) {
-            const char* nm = names[uni(0, 10)];
+            const char* nm = names[uni(0, 9)];
             int64_t v = 0, old = 0;
             if (!strcmp(nm, "path")) v = uni(0, 2);
             else if (!strcmp(nm, "fuse") || !strcmp(nm, "pack_y") || !strcmp(nm, "gen_fuse")) v = uni(0, 1);
@@ -528,7 +528,6 @@ int main(int argc, char** argv) {
             else if (!strcmp(nm, "ab_longest_first")) v = uni(0, 2);
             else if (!strcmp(nm, "workspace_mb")) v = (int64_t[]){16, 64, 4096}[uni(0, 2)];
             else if (!strcmp(nm, "overlap")) v = uni(1, 8);
-            else if (!strcmp(nm, "ab_group")) v = (int64_t[]){0, 3, 4}[uni(0, 2)];
             else if (!strcmp(nm, "small_b_jobs")) v = (int64_t[]){0, 512, 1 << 20}[uni(0, 2)];
             else v = (int64_t[]){0, 2, 4, 8, 16}[uni(0, 4)];
             CHECK(dctfp_get_option(ctx, nm, &old));

@@ -64,14 +64,12 @@ def walk_eligible(case, layers):
         and x.shape[0] <= 8192 and len(case['keys']) > 0
 
 
-@pytest.mark.parametrize('opts', [dict(stage_b=0), dict(stage_b=1), dict(a_waves=8, a_unroll=4),
-                                  dict(a_waves=16, a_unroll=8), dict(a_waves=4, a_unroll=4),
-                                  dict(workspace_mb=16), dict(a_waves=2, a_unroll=8), dict(a_waves=1), dict(overlap=1), dict(fuse=0), dict(pack_y=0),
-                                  dict(path=1), dict(path=1, fuse=0), dict(path=2, ab_unroll=4), dict(path=2, ab_unroll=6), dict(path=2, ab_unroll=8),
-                                  dict(path=2, ab_group=3), dict(path=2, ab_group=4), dict(path=2), dict(path=2, ab_run_jobs=4), dict(path=2, ab_run_jobs=64),
-                                  dict(path=2, ab_run_jobs=1), dict(small_b_jobs=0), dict(path=1, small_b_jobs=1 << 20), dict(small_one=1)],
-                         ids=['valuB', 'mfmaB', 'w8u4', 'w16u8', 'w4u4', 'smallws', 'w2u8', 'w1', 'nooverlap', 'nofuse', 'nopack',
-                              'twokernels', 'twokernels_nofuse', 'walk_u4', 'walk_u6', 'walk_u8', 'walk_g3', 'walk_g4', 'walk_forced', 'walk_run4', 'walk_run64', 'walk_run1', 'mfmaB_small_calls', 'slabB_always', 'small_calls_one_launch'])
+@pytest.mark.parametrize('opts', [dict(), dict(a_waves=8), dict(a_waves=16), dict(a_waves=4),
+                                  dict(workspace_mb=16), dict(a_waves=2), dict(overlap=1), dict(fuse=0), dict(pack_y=0),
+                                  dict(path=1), dict(path=1, fuse=0), dict(path=2), dict(path=2, ab_run_jobs=4), dict(path=2, ab_run_jobs=64),
+                                  dict(path=2, ab_run_jobs=1), dict(small_b_jobs=0), dict(path=1, small_b_jobs=1 << 20)],
+                         ids=['default', 'w8', 'w16', 'w4', 'smallws', 'w2', 'nooverlap', 'nofuse', 'nopack',
+                              'twokernels', 'twokernels_nofuse', 'walk_forced', 'walk_run4', 'walk_run64', 'walk_run1', 'mfmaB_small_calls', 'slabB_always'])
 def test_kernel_variants_agree_with_golden(dd, opts):
     """Every kernel configuration the dispatch can pick (and the engineering knobs can force) against the golden subset.
     The knobs live in libdctfp_experiments.so only (same kernels and dispatch as the product, -DDCTFP_EXPERIMENTS), so this
@@ -800,24 +798,13 @@ def test_walk_kernel_on_half_precision_rows(dd, tdtype):
         ctx.set_option('path', 0)
 
 
-def test_small_calls_in_one_launch(dd):
-    """A protein at a time -- the reference's calling pattern -- through small_call_kernel (stage A over row chunks, stage B over
-    256-channel slabs and the int8 rows handed over by tickets inside ONE launch): asserted to be the kernel that ran, bit-exact
-    against the oracle and against the three kernels it replaces, over widths that end inside a slab, kept columns below and above
-    64, domain lists with discontinuous parts, NaN / inf, and call after call on one context (the tickets must come back to zero)."""
+def test_one_protein_per_call_bit_exact(dd):
+    """A protein at a time -- the reference's calling pattern -- through the small-call path (stage A over row chunks, stage B
+    over 64-channel slabs): bit-exact against the oracle over widths that end inside a slab, kept columns below and above 64,
+    domain lists with discontinuous parts, NaN / inf, GPU and host embeddings, and call after call on one context."""
     import torch
     ctx = dd.get_context(torch.cuda.current_device())
-    ctx.set_option('small_one', 1)             # (not the default: slower than the three launches on this chip, kernels.hip.h)
-    try:
-        _small_calls_in_one_launch(dd, ctx)
-    finally:
-        ctx.set_option('small_one', 0)
-
-
-def _small_calls_in_one_launch(dd, ctx):
-    import torch
     rng = np.random.default_rng(2024)
-    n_one = 0
     shapes = [(500, 1280, [3, 80, 3, 80]), (500, 1280, [3, 80, 3, 80]), (129, 640, [3, 80, 3, 65]), (1999, 2560, [3, 80, 3, 80]),
               (300, 1000, [3, 70, 3, 33]), (128, 520, [3, 16, 3, 80]), (777, 1284, [3, 80]), (256, 2048, [3, 72, 3, 72, 3, 72])]
     for rep, (L, D, qdim) in enumerate(shapes):
@@ -834,29 +821,15 @@ def _small_calls_in_one_launch(dd, ctx):
         for embed in ({i: torch.from_numpy(x).cuda() for i, x in enumerate(layers)}, {i: x for i, x in enumerate(layers)}):
             fp = dd.Fingerprint(pid=f'small{rep}', seq='A' * L, embed=embed, domains=list(doms))
             fp.quantize(list(qdim))
-            one = ctx.get_option('last_small_one')
-            n_one += one
-            assert one == 1, (L, D, qdim)
             assert list(fp.quants) == list(want)
             for key in want:
                 np.testing.assert_array_equal(fp.quants[key], want[key], err_msg=f'L={L} D={D} {qdim} {key}')
-        ctx.set_option('small_one', 0)
-        try:
-            fp3 = dd.Fingerprint(pid='three', seq='A' * L, embed={i: torch.from_numpy(x).cuda() for i, x in enumerate(layers)}, domains=list(doms))
-            fp3.quantize(list(qdim))
-            assert ctx.get_option('last_small_one') == 0
-        finally:
-            ctx.set_option('small_one', 1)
-        for key in want:
-            np.testing.assert_array_equal(fp3.quants[key], fp.quants[key])
-    assert n_one == 2 * len(shapes)
-    # a handful of proteins per call through the batch API: still one launch per layer group
+    # a handful of proteins per call through the batch API
     lens = [150, 400, 260]
     layers = [[make_input('esm', L, 1280, 50 + 3 * s + i) for s, L in enumerate(lens)] for i in range(2)]
     table = dd.PieceTable(lens, [[f'1-{L}'] for L in lens])
     lbs = [dd.LayerBatch([torch.from_numpy(x).cuda() for x in layers[i]], 3, 80) for i in range(2)]
     out = dd.quantize_batch(lbs, table, ctx=ctx).cpu().numpy()
-    assert ctx.get_option('last_small_one') == 1
     for s, L in enumerate(lens):
         q = orc.quantize([layers[0][s], layers[1][s]], [f'1-{L}'], [3, 80, 3, 80])
         np.testing.assert_array_equal(out[s].astype(np.int64), q[f'1-{L}'])

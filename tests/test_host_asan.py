@@ -53,7 +53,7 @@ def test_stub_records_match_the_kernel_header():
 
 
 @pytest.mark.skipif(not (os.path.exists(HIPCC) and os.path.exists(CLANG)), reason='needs the ROCm compilers')
-def test_host_code_under_address_sanitizer(tmp_path):
+def test_host_calls_under_address_sanitizer(tmp_path):
     flags = ['-O1', '-g', '-std=c++17', '-fsanitize=address', '-fno-omit-frame-pointer']
     inc = ['-I', os.path.join(ROOT, 'include'), '-I', os.path.join(ROOT, 'dctdomain_amd', 'csrc')]
     import build_ext

@@ -265,12 +265,11 @@ def test_one_giant_domain_does_not_take_the_call_off_the_walk_kernel(dd):
 
 
 @pytest.mark.parametrize('D', [640, 1280, 2560])
-def test_matrix_pipe_stage_a_matches_the_vector_path(dd, D):
-    """Round-3 experiment kept as an engineering knob of libdctfp_experiments.so (`ab_mfma_a`): the multiply-adds of stage A of
-    the fused walks as v_mfma_f64_4x4x4 on 4-row x 64-channel loads, without the first-row shift.  Same bytes as the
-    vector path on RecCut-shaped proteins (parts of 3 .. 130 rows that are no multiples of 4, discontinuous domains) --
-    including the inputs the shift exists for: channels that are exactly constant over a part, over a whole protein, as
-    +0.0 / -0.0, next to a channel that differs from a constant in one bit of one row, and a channel holding a NaN."""
+def test_first_row_shift_walk_matches_two_kernels(dd, D):
+    """The inputs the first-row shift of stage A exists for, through the fused walks of the walk kernel and through the two-kernel
+    path: the same bytes on RecCut-shaped proteins (parts of 3 .. 130 rows that are no multiples of 4, discontinuous domains) with
+    channels that are exactly constant over a part, over a whole protein, as +0.0 / -0.0, next to a channel that differs from a
+    constant in one bit of one row, and a channel holding a NaN -- and the same constant channels counted."""
     import torch
     from dctdomain_amd import _lib
     rng = np.random.default_rng(1000 + D)
@@ -310,13 +309,13 @@ def test_matrix_pipe_stage_a_matches_the_vector_path(dd, D):
     lbs = [dd.LayerBatch(x, 3, 80, row_offsets=offs) for x in layers]
     xctx = _lib.experiments_context(torch.cuda.current_device())
     got = {}
-    for flag in (0, 1):
-        with _Options(xctx, ab_mfma_a=flag, path=2):
+    for path in (2, 1):
+        with _Options(xctx, path=path):
             xctx.set_option('degenerate_channels', 0)
             out = dd.quantize_batch(lbs, table, ctx=xctx).cpu().numpy()
-            assert xctx.get_option('last_path') == 2
-            got[flag] = (out, xctx.get_option('degenerate_channels'))
-    assert got[0][1] > 0 and got[1][1] == got[0][1], (got[0][1], got[1][1])      # the same channels were found constant
-    np.testing.assert_array_equal(got[1][0], got[0][0])
+            assert xctx.get_option('last_path') == path
+            got[path] = (out, xctx.get_option('degenerate_channels'))
+    assert got[2][1] > 0 and got[1][1] == got[2][1], (got[2][1], got[1][1])      # the same channels were found constant
+    np.testing.assert_array_equal(got[1][0], got[2][0])
     # ... and both are the product library's bytes
-    np.testing.assert_array_equal(dd.quantize_batch(lbs, table).cpu().numpy(), got[0][0])
+    np.testing.assert_array_equal(dd.quantize_batch(lbs, table).cpu().numpy(), got[2][0])

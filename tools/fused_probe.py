@@ -11,7 +11,7 @@ layers = [torch.randn((n_seq * L, D), device=dev) for _ in range(2)]
 offs = np.arange(n_seq, dtype=np.int64) * L
 lbs = [dd.LayerBatch(x, 3, 80, row_offsets=offs) for x in layers]
 ctx = dd.get_context(0)
-for arg in sys.argv[2:]:   # an overlap count, or name=value options of the experiments library (ab_mfma_a=1 ...)
+for arg in sys.argv[2:]:   # an overlap count, or name=value options of the experiments library (ab_run_jobs=4 ...)
     if '=' in arg:
         ctx.set_option(arg.split('=')[0], int(arg.split('=')[1]))
     else:

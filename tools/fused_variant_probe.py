@@ -15,13 +15,8 @@ one_fused = [[f'1-250', f'251-{L}', f'1-{L}']] + [[f'1-{L}']] * (n_seq - 1)
 parts5 = [[f'{100*i+1}-{100*i+100}' for i in range(5)]] * n_seq
 parts5_onefused = [[f'1-250', f'251-{L}', f'1-{L}']] + [[f'{100*i+1}-{100*i+100}' for i in range(5)]] * (n_seq - 1)
 nbytes = 2 * n_seq * L * D * 4
-for name, doms, opts in (('whole only, plain kernel (U8 G4)', whole, {}), ('whole only, plain kernel U4 G3', whole, {'ab_unroll': 4, 'ab_group': 3}),
-                         ('whole only but FUSED kernel variant (one fused protein)', one_fused, {}),
-                         ('5 x 100-row parts, plain kernel', parts5, {}), ('5 x 100-row parts, FUSED kernel variant', parts5_onefused, {})):
-    for k in ('ab_unroll', 'ab_group'):
-        ctx.set_option(k, 0)
-    for k, v in opts.items():
-        ctx.set_option(k, v)
+for name, doms in (('whole only, plain kernel', whole), ('whole only but FUSED kernel variant (one fused protein)', one_fused),
+                   ('5 x 100-row parts, plain kernel', parts5), ('5 x 100-row parts, FUSED kernel variant', parts5_onefused)):
     table = dd.PieceTable([L] * n_seq, doms)
     out = torch.empty((table.n_domains, 480), dtype=torch.int8, device=dev)
     for _ in range(3):

@@ -13,14 +13,14 @@ offs = np.arange(n_seq, dtype=np.int64) * L
 lbs = [dd.LayerBatch(x, 3, 80, row_offsets=offs) for x in layers]
 ctx = dd.get_context(0)
 nbytes = 2 * n_seq * L * D * 4
-print('rows/job ' + ' '.join(f'waves={w:<5}' for w in ('auto', 1, 2, 4, 8)) + '  (stage A GB/s | stage B ms)')
+print('rows/job ' + ' '.join(f'waves={w:<5}' for w in ('auto', 2, 4, 8)) + '  (stage A GB/s | stage B ms)')
 for k in (1, 2, 5, 10, 20):
     e = [round(i * L / k) for i in range(k + 1)]
     doms = [f'{a + 1}-{b}' for a, b in zip(e[:-1], e[1:])]
     table = dd.PieceTable([L] * n_seq, [doms] * n_seq)
     out = torch.empty((table.n_domains, 480), dtype=torch.int8, device=dev)
     cells = []
-    for w in (0, 1, 2, 4, 8):
+    for w in (0, 2, 4, 8):
         ctx.set_option('a_waves', w)
         for _ in range(2):
             dd.quantize_batch(lbs, table, out=out, ctx=ctx)

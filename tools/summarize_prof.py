@@ -18,7 +18,7 @@ def find(sub, pat):
 
 def short(name):
     name = name.split('(')[0]
-    for key in ('walk_ab_kernel', 'walk_gen_kernel', 'stage_a_kernel', 'stage_b_mfma_kernel', 'stage_b_valu_kernel', 'basis_kernel'):
+    for key in ('walk_ab_kernel', 'walk_gen_kernel', 'stage_a_kernel', 'stage_b_mfma_kernel', 'basis_kernel'):
         if key in name:
             return key
     return name[-60:]
