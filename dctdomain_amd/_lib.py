@@ -58,7 +58,7 @@ EXPORTS = ('dctfp_version', 'dctfp_last_error', 'dctfp_create', 'dctfp_destroy',
            'dctfp_stream_synchronize', 'dctfp_runtime_info', 'dctfp_crash_handler', 'dctfp_build_pieces', 'dctfp_contact_sort', 'dctfp_stitch_sizes',
            'dctfp_stitch_sequences', 'dctfp_quantize_windows', 'dctfp_reccut', 'dctfp_reccut_room', 'dctfp_quantize_one', 'dctfp_reccut_pieces',
            'dctfp_pair_min', 'dctfp_select_count', 'dctfp_select_fill', 'dctfp_sim_lines',
-           'dctfp_l1_knn', 'dctfp_query_rank', 'dctfp_query_lines')
+           'dctfp_l1_knn', 'dctfp_query_rank', 'dctfp_query_lines', 'dctfp_protein_min')
 
 
 def load(path: str = None):
@@ -169,6 +169,8 @@ def _configure(lib):
         lib.dctfp_row_order.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p]
         lib.dctfp_pair_min.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p,
                                        C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.dctfp_protein_min.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p,
+                                          C.c_int64, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]
         lib.dctfp_select_count.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32,
                                            C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
         lib.dctfp_select_fill.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32,

@@ -154,6 +154,12 @@ void launch_select_fill(const int32_t* dist, int64_t n_rows, int64_t n_cols, int
 void launch_sim_lines(const int32_t* mn, const int32_t* last, int64_t ld, int64_t n_rows, int64_t row0, int64_t col0, int64_t n_cols,
                       const uint8_t* ids, const int64_t* id_off, const char* table, const int64_t* row_base, uint8_t* out, hipStream_t stream);
 
+// DCTdomain of every protein pair from the fingerprints (k_protein.hip): scratch bytes of one side's block plan, and the launches
+// (the two plans, then the protein-minimum kernel on a grid of n_workgroups that walks the block pairs)
+size_t protein_plan_bytes(int64_t np);
+int launch_protein_min(const int8_t* a, int64_t lda, const int64_t* idx_a, int64_t npa, const int8_t* b, int64_t ldb, const int64_t* idx_b,
+                       int64_t npb, int d, int32_t* out, int64_t ldo, void* scratch, int n_workgroups, hipStream_t stream);
+
 // query_db at database scale (k_query.hip): fused L1 + k nearest, the protein-level ranking, the hit lines as text
 int knn_slices(int64_t na, int64_t nb, int k);
 size_t knn_scratch_bytes(int64_t na, int k, int n_slices);

@@ -1,10 +1,11 @@
 """Drop-in for mgtools/DCTdomain ``src/dct-sim.py``: similarity between proteins from their DCT
 fingerprints (``-dct.npz``), with the L1 distances computed on the GPU.
 
-    python -m dctdomain_amd.dct_sim --dct X-dct.npz [--pair P | --db Y-dct.npz] [--output F]
+    python -m dctdomain_amd.dct_sim --dct X-dct.npz [--pair P | --db Y-dct.npz [--rank {global,domain}]] [--output F]
                                     [--pairfound F] [--top 5] [--threshold 0.25]
 
-Same flags, same output text (src/dct-sim.py:179-211).  DCTdomain = max over all domain pairs of
+Same flags, same output text (src/dct-sim.py:179-211); ``--rank domain`` (not in the reference) orders database hits by
+DCTdomain instead of DCTglobal.  DCTdomain = max over all domain pairs of
 ``1 - min(L1/17000, 1)``, DCTglobal = the same for the two last (whole-protein) fingerprints
 (:12-50).
 
@@ -15,7 +16,9 @@ Where the reference loops over protein pairs and, inside, over domain pairs in P
   pinned buffers.  Host memory is the two buffers plus O(n), not the n x n block matrix (``Blocks``, kept for its callers);
 - ``db_search`` ranks on the whole-protein fingerprints only (one L1 per protein pair), selects the printed hits of
   every query on the GPU (``dctfp_select_count`` / ``dctfp_select_fill``) and computes DCTdomain for those pairs only
-  (``dctfp_pair_min``): ``ProteinSearch``.  Host memory is what is printed plus one tile, not n_query x n_db;
+  (``dctfp_pair_min``): ``ProteinSearch``.  Host memory is what is printed plus one tile, not n_query x n_db.  With
+  ``--rank domain`` it ranks on DCTdomain instead: the tiles hold every protein pair's minimum over all fingerprint pairs
+  (``dctfp_protein_min``), selected the same way;
 - ``pair_sim`` uploads the fingerprints of the proteins its pairs name and runs ``dctfp_pair_min`` on the pairs.
 Scores are formed from the integer L1 values with the reference's arithmetic (int64 / 17000 in float64), so the printed
 floats are identical."""
@@ -28,7 +31,8 @@ import time
 
 import numpy as np
 
-from .similarity import LineIds, block_min, block_min_device, l1_matrix, pair_min, sim_lines, threshold_select, to_device_int8
+from .similarity import (LineIds, block_min, block_min_device, l1_matrix, pair_min, protein_min, sim_lines, threshold_select,
+                         to_device_int8)
 
 L1_FULL_SCALE = 17000      # src/dct-sim.py:24
 HEADER = '#prot1 prot2 sim-domain sim-global'
@@ -326,6 +330,10 @@ class ProteinSearch:
        database index, the first max(top, #(DCTglobal >= threshold));
     3. DCTdomain (``pair_min``) for the printed pairs only.
 
+    ``rank='domain'`` ranks on DCTdomain instead: the tile of step 1 holds each (query, database protein) pair's minimum L1
+    over all their fingerprints (``protein_min``, the group's fingerprints resident on the device), and steps 2 and 3 are
+    the same -- the first max(top, #(DCTdomain >= threshold)), best DCTdomain first.
+
     The database goes to the device in protein groups of at most COL_ROWS fingerprints (a single group stays there between
     searches); the query side is tiled so that a distance tile holds at most TILE_INTS entries.  The groups' hit lists are
     merged per query (``merge_candidates``).  ``search`` returns, per query, (database protein indices, min L1, last L1)."""
@@ -355,7 +363,9 @@ class ProteinSearch:
             self._resident[g] = entry
         return entry
 
-    def search(self, query_fps, query_idx, top: int, threshold: float):
+    def search(self, query_fps, query_idx, top: int, threshold: float, rank: str = 'global'):
+        if rank not in RANKS:
+            raise ValueError(f'rank must be one of {RANKS}')
         top = int(top)
         qidx = np.asarray(query_idx, dtype=np.int64)
         nq, n_db = len(qidx) - 1, len(self.idx) - 1
@@ -365,15 +375,18 @@ class ProteinSearch:
         top1 = max(top, 1)      # (top <= 0: the reference prints the threshold hits only -- trimmed after the merge)
         q_last, q_empty = _last_rows(query_fps, qidx)
         parts = [[] for _ in range(nq)]
-        for g, (p0, p1) in enumerate(self.groups):
-            _, _, last, empty = self._group(g, need_rows=False)
-            rows = int(min(self.MAX_TILE_ROWS, max(1, self.TILE_INTS // (p1 - p0))))
-            for t0 in range(0, nq, rows):
-                t1 = min(nq, t0 + rows)
-                off, key, col = threshold_select(l1_matrix(q_last[t0:t1], last), top1, bound, q_empty[t0:t1], empty)
-                for r in range(t1 - t0):
-                    s = slice(off[r], off[r + 1])
-                    parts[t0 + r].append((key[s], col[s] + p0))
+        if rank == 'domain':
+            self._domain_parts(query_fps, qidx, q_empty, top1, bound, parts)
+        else:
+            for g, (p0, p1) in enumerate(self.groups):
+                _, _, last, empty = self._group(g, need_rows=False)
+                rows = int(min(self.MAX_TILE_ROWS, max(1, self.TILE_INTS // (p1 - p0))))
+                for t0 in range(0, nq, rows):
+                    t1 = min(nq, t0 + rows)
+                    off, key, col = threshold_select(l1_matrix(q_last[t0:t1], last), top1, bound, q_empty[t0:t1], empty)
+                    for r in range(t1 - t0):
+                        s = slice(off[r], off[r + 1])
+                        parts[t0 + r].append((key[s], col[s] + p0))
         merged = (merge_candidates(pq, top1, bound) for pq in parts)
         hits = [c if top >= 1 else c[k <= bound] for k, c in merged]
         del parts
@@ -383,6 +396,34 @@ class ProteinSearch:
         mn, last_l1 = self._pair_scores(query_fps, qidx, q_of, db_of)
         bounds = np.concatenate([[0], np.cumsum(counts)])
         return [(db_of[a:b], mn[a:b], last_l1[a:b]) for a, b in zip(bounds[:-1], bounds[1:])]
+
+    def _domain_parts(self, query_fps, qidx, q_empty, top1: int, bound: int, parts):
+        """Step 1-2 of rank='domain': per database group (its fingerprints on the device) and query tile (at most TILE_INTS
+        protein pairs; the query fingerprints go up in chunks of at most COL_ROWS), the protein-minimum tile and its
+        selection, appended to ``parts``."""
+        import torch
+        chunks = list(_protein_groups(qidx, self.COL_ROWS))
+        resident = None
+        for g, (p0, p1) in enumerate(self.groups):
+            rows, sub_idx, _, empty = self._group(g, need_rows=True)
+            if rows is None:                                    # (a group without fingerprints: every pair is empty)
+                rows = torch.empty((0, self.fps.shape[1]), dtype=torch.int8, device=torch.cuda.current_device())
+            per = int(max(1, self.TILE_INTS // (p1 - p0)))
+            for c0, c1 in chunks:
+                if resident is not None and resident[0] == c0:
+                    q = resident[1]
+                else:
+                    q = to_device_int8(query_fps[qidx[c0]:qidx[c1]])
+                    if len(chunks) == 1:
+                        resident = (c0, q)
+                for t0 in range(c0, c1, per):
+                    t1 = min(c1, t0 + per)
+                    tile = protein_min(q, qidx[t0:t1 + 1] - qidx[c0], rows, sub_idx)
+                    off, key, col = threshold_select(tile, top1, bound, q_empty[t0:t1], empty)
+                    for r in range(t1 - t0):
+                        s = slice(off[r], off[r + 1])
+                        parts[t0 + r].append((key[s], col[s] + p0))
+                    del tile
 
     def _pair_scores(self, query_fps, qidx, q_of, db_of):
         """(min, last) L1 of the pairs (query q_of[k], database protein db_of[k]): per database group, per chunk of queries."""
@@ -436,14 +477,14 @@ class Report:
 
 def _reporting(fn):
     """The mode functions keep the reference's signature -- the last argument may be an output path or
-    ``None`` (stdout) -- and also take an open ``Report``."""
-    def run(*args):
+    ``None`` (stdout) -- and also take an open ``Report``.  Keyword arguments (options beyond the reference's) pass through."""
+    def run(*args, **kw):
         *head, output = args
         if isinstance(output, Report):
-            return fn(*head, output)
+            return fn(*head, output, **kw)
         report = Report(output)
         try:
-            return fn(*head, report)
+            return fn(*head, report, **kw)
         finally:
             report.close()
     run.__doc__, run.__name__ = fn.__doc__, fn.__name__
@@ -481,12 +522,13 @@ def pair_sim(npzfile: str, pairfile: str, pairfound: str, report: Report):
 
 
 @_reporting
-def db_search(npzfile: str, dbfile: str, top: int, threshold: float, report: Report):
+def db_search(npzfile: str, dbfile: str, top: int, threshold: float, report: Report, rank: str = 'global'):
     """Hits of every query protein in a fingerprint database, best DCTglobal first (stable); the first
-    ``top`` always, further ones while they reach ``threshold`` (src/dct-sim.py:126-156)."""
+    ``top`` always, further ones while they reach ``threshold`` (src/dct-sim.py:126-156).  ``rank='domain'``: best
+    DCTdomain first, and the threshold applies to DCTdomain (the same loop with the domain score as the key)."""
     sid, idx, fps = _load_npz(npzfile)
     db_sid, db_idx, db_fps = _load_npz(dbfile)
-    hits = ProteinSearch(db_fps, db_idx).search(fps, idx, top, threshold)
+    hits = ProteinSearch(db_fps, db_idx).search(fps, idx, top, threshold, rank=rank)
     for query, (cols, mn, last) in zip(sid, hits):
         for q, m, l in zip(cols, mn, last):
             maxs, s = _scores(m, l)
@@ -500,15 +542,32 @@ def all_sim(npzfile: str, report: Report):
     AllPairs(sid, idx, fps).write(report.raw)
 
 
+RANKS = ('global', 'domain')
+
+
+class _Parser(argparse.ArgumentParser):
+    """``--rank`` orders database hits: it is an error without ``--db`` or beside ``--pair`` (which takes precedence)."""
+
+    def parse_known_args(self, args=None, namespace=None):
+        ns, rest = super().parse_known_args(args, namespace)
+        if getattr(ns, 'rank', None) is not None and (ns.pair or not ns.db):
+            self.error('--rank applies to database search (--db) only, not to --pair or all-against-all')
+        return ns, rest
+
+
 def build_parser() -> argparse.ArgumentParser:
-    ap = argparse.ArgumentParser(description='protein similarity from DCT fingerprints (GPU L1)')
+    ap = _Parser(description='protein similarity from DCT fingerprints (GPU L1)')
     ap.add_argument('--dct', required=True, help='fingerprints of the proteins to compare (-dct.npz)')
     ap.add_argument('--output', help='write the result lines here instead of stdout')
     ap.add_argument('--pair', help='file of protein pairs to score (two ids per line)')
     ap.add_argument('--pairfound', help='copy of --pair restricted to the pairs that were scored')
     ap.add_argument('--db', help='search every protein of --dct in this -dct.npz')
     ap.add_argument('--top', type=int, default=5, help='database search: hits always reported per query')
-    ap.add_argument('--threshold', type=float, default=0.25, help='database search: further hits down to this DCTglobal')
+    ap.add_argument('--threshold', type=float, default=0.25,
+                    help='database search: further hits down to this score (DCTglobal, or DCTdomain with --rank domain)')
+    ap.add_argument('--rank', choices=RANKS, default=None,
+                    help='database search: order hits by the whole-protein score (global, the default) or by the best '
+                         'domain pair (domain)')
     return ap
 
 
@@ -520,7 +579,7 @@ def main(argv=None):
     if args.pair:
         pair_sim(args.dct, args.pair, args.pairfound, report)
     elif args.db:
-        db_search(args.dct, args.db, args.top, args.threshold, report)
+        db_search(args.dct, args.db, args.top, args.threshold, report, rank=args.rank or 'global')
     else:
         all_sim(args.dct, report)
     report.close()

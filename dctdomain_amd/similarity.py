@@ -163,6 +163,56 @@ def pair_min(a, idx_a, b, idx_b, pairs):
     return _pair_to_host(mn, last)
 
 
+def protein_min(a, idx_a, b, idx_b, out: torch.Tensor = None) -> torch.Tensor:
+    """int32 (npa, npb) on the device: the smallest L1 over all fingerprint pairs of every (protein of ``a``, protein of ``b``)
+    -- DCTdomain's distance, ``block_min(l1_matrix(a, b), idx_a, idx_b)[0]`` without the distance matrix
+    (``dctfp_protein_min``).  ``idx_a`` / ``idx_b``: the npz prefix arrays; a protein without fingerprints gives 0x7fffffff.
+    ``out``: an int32 (npa, npb) device tensor with unit column stride to write into (any row stride).  Rows not on 16-byte
+    boundaries are copied into padded ones; rows wider than 512 bytes (the kernel's limit) take l1_matrix + block_min."""
+    ia, ib = np.asarray(idx_a, dtype=np.int64), np.asarray(idx_b, dtype=np.int64)
+    npa, npb = len(ia) - 1, len(ib) - 1
+    ta, tb = _row_major_int8(a), _row_major_int8(b)
+    if ta.dim() != 2 or tb.dim() != 2 or ta.shape[1] != tb.shape[1]:
+        raise ValueError('fingerprint sets must be 2-D with equal width')
+    for idx, rows in ((ia, ta.shape[0]), (ib, tb.shape[0])):    # (the kernel trusts the prefix arrays: check them here)
+        if len(idx) < 1 or idx[0] < 0 or idx[-1] > rows or (np.diff(idx) < 0).any():
+            raise ValueError('idx must be a non-decreasing prefix array within its fingerprint matrix')
+    dev = ta.device
+    if out is None:
+        out = torch.empty((npa, npb), dtype=torch.int32, device=dev)
+    elif out.dtype != torch.int32 or tuple(out.shape) != (npa, npb) or out.device != dev or (npb > 1 and out.stride(1) != 1):
+        raise ValueError('out must be an int32 (npa, npb) tensor on the fingerprints\' device with unit column stride')
+    if out.numel() == 0:
+        return out
+    if ia[-1] == ia[0] or ib[-1] == ib[0]:                      # (no fingerprint on a side: every pair is empty)
+        return out.fill_(0x7fffffff)
+    d = ta.shape[1]
+    if d <= PROTEIN_MIN_MAX_D and not (_aligned16(ta) and _aligned16(tb)):
+        w = (d + 15) // 16 * 16
+        ta, tb = _rows16(ta, w), _rows16(tb, w)
+    da, db = _device_int64(ia, dev), _device_int64(ib, dev)
+    ctx = _lib.get_context(dev.index)
+    stream = torch.cuda.current_stream(dev)
+    ldo = out.stride(0) if npa > 1 else npb
+    try:
+        _lib.check(ctx._lib.dctfp_protein_min(ctx.handle, ta.data_ptr(), ta.stride(0) if ta.shape[0] > 1 else ta.shape[1], da.data_ptr(),
+                                              npa, tb.data_ptr(), tb.stride(0) if tb.shape[0] > 1 else tb.shape[1], db.data_ptr(), npb, d,
+                                              out.data_ptr(), ldo, C.c_void_p(stream.cuda_stream)))
+    except _lib.DctfpError as e:
+        if e.code != _lib.DCTFP_ERR_LIMIT:
+            raise
+        out.copy_(block_min_device(l1_matrix(ta[:, :d], tb[:, :d]), ia, ib)[0])
+    return out
+
+
+def _row_major_int8(x) -> torch.Tensor:
+    """A device int8 matrix with unit column stride as it is (a row stride of its own is kept); anything else through
+    ``to_device_int8``."""
+    if isinstance(x, torch.Tensor) and x.dtype == torch.int8 and x.device.type == 'cuda' and x.dim() == 2 and (x.shape[1] <= 1 or x.stride(1) == 1):
+        return x
+    return to_device_int8(x)
+
+
 def threshold_select(dist: torch.Tensor, top: int, bound: int, row_empty=None, col_empty=None, cap: int = 17000):
     """The hits of every row of a last-row distance tile in db_search's order (src/dct-sim.py:146-156): key = min(L1, cap)
     (``cap`` for a row / column flagged empty), ascending, ties to the lower column; the first max(top, #(key <= bound))
@@ -253,6 +303,7 @@ def sim_lines(mn: torch.Tensor, last: torch.Tensor, row0: int, col0: int, ids: L
 KNN_MAX_K = 1024     # dctfp_l1_knn's limits: larger k or wider rows take l1_matrix + row_select
 KNN_MAX_D = 512
 KNN_SCRATCH_BYTES = 1 << 31
+PROTEIN_MIN_MAX_D = 512   # dctfp_protein_min's limit: wider rows take l1_matrix + block_min
 
 
 def _aligned16(t: torch.Tensor) -> bool:

@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define DCTFP_VERSION 101 /* 0.1.1: dctfp_l1_knn, dctfp_query_rank, dctfp_query_lines */
+#define DCTFP_VERSION 102 /* 0.1.2: dctfp_protein_min */
 
 #define DCTFP_OK 0
 #define DCTFP_ERR_INVALID (-1) /* bad argument (null pointer, piece outside its sequence, ...) */
@@ -310,6 +310,19 @@ int dctfp_row_order(dctfp_ctx* ctx, int32_t* val, int32_t* idx, int64_t n_rows, 
 int dctfp_pair_min(dctfp_ctx* ctx, const int32_t* pairs, int64_t n_pairs, const int8_t* a, int64_t lda, const int64_t* idx_a, int64_t npa,
                    const int8_t* b, int64_t ldb, const int64_t* idx_b, int64_t npb, int32_t d, int32_t* out_min, int32_t* out_last,
                    void* stream);
+
+/* DCTdomain's L1 for every protein pair of two fingerprint sets, straight from the fingerprints (dct-sim --db --rank domain):
+ *     out[pa * ldo + pb] = min over rows r of protein pa (idx_a) and rows s of protein pb (idx_b) of
+ *                          sum_k |a[r * lda + k] - b[s * ldb + k]|,  k < d
+ * -- dctfp_block_min's out_min on the dctfp_l1_matrix of the two sets, without the distance matrix.  idx_a (npa + 1 entries)
+ * and idx_b (npb + 1) are the npz "idx" prefix arrays, as in dctfp_pair_min (non-decreasing and within their matrices: the
+ * caller's guarantee).  A protein without fingerprints gives 0x7fffffff (dctfp_block_min's fill).  All device pointers; out is
+ * int32 (npa, npb) with row stride ldo >= npb, every entry written, nothing else.  Consecutive proteins are packed into blocks
+ * of at most 128 rows on the device; a protein of more rows is a block of its own.  DCTFP_ERR_LIMIT (nothing written) for rows
+ * above 512 bytes, rows not on 16-byte boundaries (a, b, lda, ldb) or 2^24 bytes apart, or more than 2^31 - 1 proteins on a
+ * side: dctfp_l1_matrix + dctfp_block_min give the same values there.  Uses the context's scratch. */
+int dctfp_protein_min(dctfp_ctx* ctx, const int8_t* a, int64_t lda, const int64_t* idx_a, int64_t npa, const int8_t* b, int64_t ldb,
+                      const int64_t* idx_b, int64_t npb, int32_t d, int32_t* out, int64_t ldo, void* stream);
 
 /* The hits db_search prints (src/dct-sim.py:146-156), selected on the device from an int32 tile of L1 distances between the
  * queries' and the database proteins' last fingerprints (dctfp_l1_matrix).  Key of an entry: min(L1, cap) (cap = 17000: the
