@@ -78,23 +78,16 @@ def queue_cpu(fp: Fingerprint) -> Fingerprint:
 
 def fingerprint_batch(fps: List[Fingerprint], threads: int = 1, qdim=QDIM, threshold: float = THRESHOLD):
     """``queue_cpu`` for many proteins at once: same ``domains`` / ``quants`` per object as calling it one by one
-    (src/make_db.py:19-33 inside the pool of :36-51).  The flush as ``_Flush`` runs it -- geometry of all tensors in one pass,
-    contact selection + domain cutter on the GPU, strings and piece table straight from the cutter's integers, one
-    ``dctfp_quantize``, the objects filled while the kernels run; anything out of the ordinary (domains or fingerprints already
-    in an object, embeddings that are not GPU tensors of one layout, a protein whose domain strings need Python's own parser)
-    goes through ``_fingerprint_batch_generic``, which takes every input the reference takes."""
+    (src/make_db.py:19-33 inside the pool of :36-51), by one ``_Flush``."""
     if not fps:
         return fps
     fl = _Flush(fps, threads, qdim, threshold)
-    if fl.start():
-        if fl.finish(objects=True) is not None:
-            LAST_PATH[0] = 'flush'
-            return fps
-    LAST_PATH[0] = 'generic'
-    return _fingerprint_batch_generic(fps, threads, qdim, threshold)
+    fl.start()
+    return fl.finish(objects=True)
 
 
-#: which way the last ``fingerprint_batch`` / ``flush_records`` of this process went ('flush' or 'generic'): tests assert it
+#: how the last flush of this process went: 'flush' when every input was taken as it is, 'converted' when some had to be
+#: converted first or the piece table was built from strings -- tests assert it
 LAST_PATH = [None]
 
 
@@ -109,6 +102,20 @@ def _side_stream(device):
     return s
 
 
+def _converted_layer(vals, n_keep, m_keep):
+    """A layer ``LayerBatch.from_table`` refused: every input the reference takes (numpy or CPU matrices, other dtypes
+    promoted as it promotes them, views of other strides) as device matrices ``LayerBatch`` takes."""
+    from .batch import LayerBatch
+    from .fingerprint import _to_device_matrix
+    if not (all(map(torch.is_tensor, vals)) and all(map(_IS_CUDA, vals)) and set(map(_DTYPE, vals)) <= _KEPT_DTYPES):
+        vals = [_to_device_matrix(v, keep_half=True) for v in vals]
+    try:
+        return vals, LayerBatch(vals, n_keep, m_keep)
+    except ValueError:       # (row-strided or transposed views, mixed strides: made contiguous one by one, then judged again)
+        vals = [_to_device_matrix(v, keep_half=True).contiguous() for v in vals]
+        return vals, LayerBatch(vals, n_keep, m_keep)
+
+
 class _Flush:
     """One flush of a database build in two halves, so that the build can do something else in between
     (``process_sequences`` embeds the next proteins; the domain cutter is a latency, not a load: a few long proteins, one
@@ -119,9 +126,14 @@ class _Flush:
     ``finish()``  the cutter's integers -> strings + piece table (``dctfp_reccut_pieces``), one ``dctfp_quantize``, the
                   per-protein results assembled while the kernels run.  ``objects=True`` fills ``domains`` / ``quants`` of every
                   ``Fingerprint`` as ``queue_cpu`` does (int64 rows, the reference's dtype) and returns the list;
-                  ``objects=False`` returns what the writer stores -- (pid, domains, int8 rows) -- and leaves the objects alone.
+                  ``objects=False`` returns what the writer stores -- (pid, domains, int8 rows).
 
-    Both return None / False where the flush is not of the plain kind; the caller then runs ``_fingerprint_batch_generic``.
+    Inputs straight off the language model (GPU tensors of one layout) are taken as they are.  Every other input the
+    reference takes is converted first, only where needed: contact maps by ``reccut._contact_tensor``, embedding layers by
+    ``_converted_layer``.  Where the domain strings must be judged by the reference's own rules -- domains or fingerprints
+    already in an object, embeddings of other lengths than their sequences, a cutter result ``dctfp_reccut_pieces`` leaves
+    undone -- the piece table is built from the strings (``PieceTable``) and the objects are filled as the reference fills
+    them (``_extend_quants``).
     A flush owns its page-locked result buffers from ``start()`` to the end of ``finish()``: any number of flushes may be
     started before the first is finished, and finished in any order."""
 
@@ -130,35 +142,38 @@ class _Flush:
         self.cut = None
 
     def start(self) -> bool:
+        """Enqueues the first half; True (errors in the inputs raise what the reference raises)."""
         from . import _geom, reccut
         from .batch import LayerBatch
         fps = self.fps
         n = len(fps)
         _mark('start')
-        if any(map(_DOMAINS, fps)) or any(map(_QUANTS, fps)):
-            return False                       # (domains given by the caller, or a second quantize: the general bookkeeping)
-        seqs = list(map(_SEQ, fps))
-        lens = np.fromiter(map(len, seqs), dtype=np.int64, count=n)
+        # (domains given by the caller, or a second quantize: the reference's bookkeeping, on strings)
+        self.strings = any(map(_DOMAINS, fps)) or any(map(_QUANTS, fps))
+        self.converted = self.strings
+        lens = np.fromiter(map(len, map(_SEQ, fps)), dtype=np.int64, count=n)
         cts = list(map(_CONTACTS, fps))
         ptrs, meta = _geom.tensor_table(cts)
         first = cts[0]
-        if not (torch.is_tensor(first) and first.is_cuda and first.dtype == torch.float32):
-            return False
-        side = lens > 1
-        if not ((meta[:, _geom.DIM] == 2).all() and (meta[:, _geom.CODE] == meta[0, _geom.CODE]).all()
-                and (meta[:, _geom.SIZE0] == lens).all() and (meta[:, _geom.SIZE1] == lens).all()
-                and (meta[side, _geom.STRIDE1] == 1).all() and (lens >= 1).all() and lens.max() < (1 << 31)):
-            return False                       # (maps given as numpy / flat / transposed: _contact_tensor judges them one by one)
-        device = first.device
-        lds = np.where(side, meta[:, _geom.STRIDE0], np.maximum(lens, 1))
+        device = first.device if torch.is_tensor(first) and first.is_cuda else torch.device('cuda', torch.cuda.current_device())
+        code = meta[0, _geom.CODE] if torch.is_tensor(first) and first.is_cuda and first.dtype == torch.float32 \
+            else _geom.code_of(torch.empty(0, dtype=torch.float32, device=device))
+        ok = ((meta[:, _geom.DIM] == 2) & (meta[:, _geom.CODE] == code)
+              & (meta[:, _geom.SIZE0] == lens) & (meta[:, _geom.SIZE1] == lens) & ((meta[:, _geom.STRIDE1] == 1) | (lens <= 1))
+              & (lens >= 1))
+        if not ok.all():        # (maps given as numpy / CPU / flat / of another dtype / row-strided: converted one by one)
+            for s in np.flatnonzero(~ok).tolist():
+                cts[s] = reccut._contact_tensor(cts[s], int(lens[s]), device)
+            ptrs, meta = _geom.tensor_table(cts)
+            self.converted = True
+        lds = np.where(lens > 1, meta[:, _geom.STRIDE0], np.maximum(lens, 1))
         self.lens = lens
         keys0 = list(fps[0].embed.keys())
         if not keys0:
-            return False
+            raise IndexError('the proteins have no embedding layers')
         embeds = list(map(_EMBED, fps))
         _mark('maps')
-        ctx = _lib_mod().get_context(device.index)
-        self.ctx, self.device = ctx, device
+        self.ctx, self.device = _lib_mod().get_context(device.index), device
         main = torch.cuda.current_stream(device)
         stream = _side_stream(device)
         stream.wait_stream(main)               # (the maps were written on the caller's stream)
@@ -167,59 +182,92 @@ class _Flush:
         self._maps = cts
         _mark('enqueued top-k + cutter')
         # ---- the embedding tables, while the GPU selects and cuts
-        layers, mats = [], []
+        layers, mats, converted = [], [], False
         try:
             for i, k in enumerate(keys0):
                 vals = [e[k] for e in embeds]
                 p, m = _geom.tensor_table(vals)
-                if not (m[:, _geom.SIZE0] == lens).all():
-                    return self._abandon()     # (rows of an embedding differ from the sequence's length: the general path names it)
                 t0 = vals[0]
-                if not (t0.is_cuda and t0.dtype in _KEPT_DTYPES and t0.device == device):
-                    return self._abandon()
-                layers.append(LayerBatch.from_table(vals, p, m, self.qdim[2 * i], self.qdim[2 * i + 1]))
+                layer = None
+                if (m[:, _geom.SIZE0] == lens).all() and torch.is_tensor(t0) and t0.is_cuda and t0.dtype in _KEPT_DTYPES \
+                        and t0.device == device:
+                    try:
+                        layer = LayerBatch.from_table(vals, p, m, self.qdim[2 * i], self.qdim[2 * i + 1])
+                    except ValueError:
+                        pass
+                if i == 0:
+                    self.rows = lens
+                if layer is None:
+                    vals, layer = _converted_layer(vals, self.qdim[2 * i], self.qdim[2 * i + 1])
+                    converted = True
+                    if i == 0:
+                        self.rows = np.fromiter(map(len, vals), dtype=np.int64, count=n)
+                layers.append(layer)
                 mats.append(vals)
-        except (ValueError, KeyError, AttributeError, TypeError, IndexError):
-            return self._abandon()
+        except BaseException:
+            self.cut.release()
+            self.cut = None
+            raise
+        if converted:
+            stream.wait_stream(main)           # (the converted matrices were written on the caller's stream)
+        # (embeddings of other lengths than their sequences: the piece table speaks of the first layer's rows, as the reference's
+        #  get_doms slices them)
+        self.strings = self.strings or not (self.rows == lens).all()
+        self.converted = self.converted or converted or self.strings
         self.layers, self.mats, self.keys0 = layers, mats, keys0
         _mark('embedding tables')
         return True
 
-    def _abandon(self):
-        if self.cut is not None:
-            self.cut.release()
-            self.cut = None
-        return False
+    def _domain_strings(self):
+        """Per protein the strings the piece table is built from: those already in the object, then the cutter's (+ ``1-L``
+        where it cut several) -- ``Fingerprint.reccut`` appending to ``domains``."""
+        doms = self.cut.wait(self.threads, strings=True)
+        for d, fp, n in zip(doms, self.fps, self.lens.tolist()):
+            if len(d) > 1:
+                d.append(f'1-{n}')                                 # src/fingerprint.py:106-107
+            d[:0] = fp.domains
+        return doms
 
     def finish(self, objects: bool):
+        from . import reccut
         from .batch import PieceTable, quantize_batch
         fps, n, lens = self.fps, len(self.fps), self.lens
         lib = _lib_mod().load()
-        enc_off = self.cut.enc_off
-        n_enc = int(enc_off[-1])
-        # (segments + proteins bound the pieces; 24 bytes per segment + 32 per protein the text: an encoded record spends two
-        #  ints per segment)
-        piece_cap = n_enc // 2 + n + 1
-        text_cap = 12 * n_enc + 32 * n + 64
-        pieces = np.empty(piece_cap, dtype=_lib_mod().PIECE_DTYPE)
-        text = np.empty(text_cap, dtype=np.uint8)
-        counts = np.empty(n, dtype=np.int32)
-        text_len, n_pieces, n_dom, n_undone = C.c_int64(), C.c_int64(), C.c_int64(), C.c_int64()
         try:
-            enc = np.ascontiguousarray(self.cut.wait())
-            _mark('cutter waited for')
-            _lib_mod().check(lib.dctfp_reccut_pieces(n, enc.ctypes.data, enc_off.ctypes.data, lens.ctypes.data, text.ctypes.data, text_cap,
-                                                    C.byref(text_len), counts.ctypes.data, pieces.ctypes.data, piece_cap, C.byref(n_pieces),
-                                                    C.byref(n_dom), C.byref(n_undone)), lib)
+            if self.strings:
+                table = PieceTable(self.rows, self._domain_strings())
+                _mark('cutter waited for')
+            else:
+                enc_off = self.cut.enc_off
+                n_enc = int(enc_off[-1])
+                # (segments + proteins bound the pieces; 24 bytes per segment + 32 per protein the text: an encoded record spends
+                #  two ints per segment)
+                piece_cap = n_enc // 2 + n + 1
+                text_cap = 12 * n_enc + 32 * n + 64
+                pieces = np.empty(piece_cap, dtype=_lib_mod().PIECE_DTYPE)
+                text = np.empty(text_cap, dtype=np.uint8)
+                counts = np.empty(n, dtype=np.int32)
+                text_len, n_pieces, n_dom, n_undone = C.c_int64(), C.c_int64(), C.c_int64(), C.c_int64()
+                enc = np.ascontiguousarray(self.cut.wait(self.threads))
+                _mark('cutter waited for')
+                _lib_mod().check(lib.dctfp_reccut_pieces(n, enc.ctypes.data, enc_off.ctypes.data, lens.ctypes.data, text.ctypes.data,
+                                                        text_cap, C.byref(text_len), counts.ctypes.data, pieces.ctypes.data, piece_cap,
+                                                        C.byref(n_pieces), C.byref(n_dom), C.byref(n_undone)), lib)
+                if n_undone.value:             # (a protein whose strings Python's own parser must judge: never seen)
+                    redone = set(reccut.LAST.host_redo)
+                    self.strings = self.converted = True
+                    table = PieceTable(self.rows, self._domain_strings())
+                    reccut.LAST.host_redo = sorted(redone.union(reccut.LAST.host_redo))
+                else:
+                    flat = text[:text_len.value].tobytes().decode('ascii').split(';')
+                    flat.pop()
+                    table = PieceTable.from_pieces(lens, pieces[:n_pieces.value], n_dom.value, flat, counts)
         finally:
             self.cut.release()                 # (the results are decoded: the page-locked buffers go back to the free list)
-        if n_undone.value:
-            return None                        # (a protein whose strings Python's own parser must judge: never seen; the general path)
-        flat = text[:text_len.value].tobytes().decode('ascii').split(';')
-        flat.pop()
-        nd = n_dom.value
-        table = PieceTable.from_pieces(lens, pieces[:n_pieces.value], nd, flat, counts)
+        LAST_PATH[0] = 'converted' if self.converted else 'flush'
         _mark('strings + piece table')
+        nd = table.n_domains
+        keys = table.keys
         total = sum(l.n_keep * l.m_keep for l in self.layers)
         self.ctx.get_option('degenerate_seen')  # (the flag is the context's: drop what earlier callers left unread)
         # On the flush's own stream, not the caller's: inside a build the caller's stream still holds the language model's kernels for
@@ -235,37 +283,39 @@ class _Flush:
             view.copy_(out, non_blocking=True)
         _mark('quantize enqueued')
         # ---- everything that needs only the SHAPE of the result, while the kernels run
-        bounds = np.zeros(n + 1, dtype=np.int64)
-        np.cumsum(counts, out=bounds[1:])
+        if self.strings:
+            bounds = np.searchsorted(table.owner, np.arange(n + 1))
+        else:
+            bounds = np.zeros(n + 1, dtype=np.int64)
+            np.cumsum(counts, out=bounds[1:])
         bl = bounds.tolist()
         host8 = np.empty((nd, total), dtype=np.int8)
-        result = None
-        if objects:
+        fill = objects or self.strings         # (the reference's bookkeeping on the objects; the writer's records from those)
+        if fill:
             host64 = np.empty((nd, total), dtype=np.int64)      # np.array(list of ints) in the reference: int64
             rows64 = list(host64)                               # (row views, made in one C-level pass)
-            dup = []
+            merge = []
             for s, fp in enumerate(fps):
                 a, b = bl[s], bl[s + 1]
-                ks = flat[a:b]
+                ks = keys[a:b]
                 q = dict(zip(ks, rows64[a:b]))                  # a row already is layer 0's block, layer 1's block, ... (:184-196)
-                if len(q) != b - a:                             # (a key twice: never from the cutter -- its domains are disjoint)
-                    dup.append(s)
+                if fp.quants or len(q) != b - a:                # (fingerprints already there, or a key twice: never from the cutter)
+                    merge.append(s)
                     continue
                 fp.quants = q
                 fp.domains = ks
                 fp._rows8 = host8[a:b]                          # what the writer stores (see _records)
-            result = fps
         else:
-            result = [(pid, flat[a:b], host8[a:b]) for pid, a, b in zip(map(_PID, fps), bl[:-1], bl[1:])]
+            result = [(pid, keys[a:b], host8[a:b]) for pid, a, b in zip(map(_PID, fps), bl[:-1], bl[1:])]
         _mark('results laid out')
         stream.synchronize()
         np.copyto(host8, view.numpy())
-        if objects:
+        if fill:
             _widen(host64, host8)
-            for s in dup:
+            for s in merge:
                 a, b = bl[s], bl[s + 1]
-                fps[s].domains.extend(flat[a:b])
-                _extend_quants(fps[s], flat[a:b], host64[a:b], self.qdim, len(self.keys0))
+                _extend_quants(fps[s], keys[a:b], host64[a:b], self.qdim, len(self.keys0))
+            result = fps if objects else _records(fps)
         _mark('results on the host')
         if nd and self.ctx.get_option('degenerate_seen'):
             # rare: the flush saw an exactly constant channel (0/0 -> all-zero block, the documented deviation).  Name the proteins.
@@ -306,104 +356,13 @@ def _widen(dst64: np.ndarray, src8: np.ndarray):
 
 def flush_records(fps: List[Fingerprint], threads: int = 1, qdim=QDIM, threshold: float = THRESHOLD):
     """What the writer stores for a flush -- (pid, domains, int8 rows) per protein, the files' content -- without filling the
-    ``Fingerprint`` objects (``make_db`` never looks at them again).  Same values as ``_records(fingerprint_batch(fps))``."""
+    ``Fingerprint`` objects where the reference's bookkeeping is not needed (``make_db`` never looks at them again).  Same
+    values as ``_records(fingerprint_batch(fps))``."""
     if not fps:
         return []
     fl = _Flush(fps, threads, qdim, threshold)
-    if fl.start():
-        recs = fl.finish(objects=False)
-        if recs is not None:
-            LAST_PATH[0] = 'flush'
-            return recs
-    LAST_PATH[0] = 'generic'
-    return _records(_fingerprint_batch_generic(fps, threads, qdim, threshold))
-
-
-def _fingerprint_batch_generic(fps: List[Fingerprint], threads: int = 1, qdim=QDIM, threshold: float = THRESHOLD):
-    """The flush for every input the reference takes (numpy or CPU tensors, domains already present, a second ``quantize``
-    on the same objects, strings only Python's parser can judge): what ``fingerprint_batch`` was through round 5's first half.
-
-    Nothing in here loops over domains in Python (the flush used to cost 117 us per protein against < 1 us
-    of kernels): the contact selection is one GPU call, RecCut one threaded C call that runs while this thread prepares
-    the embedding tables, the piece table is built by ``dctfp_build_pieces``, and every ``fp.quants[key]`` is a row VIEW of
-    one int64 copy of the flush's result (the reference's dtype; keep ``fp`` alive and the flush's array stays alive)."""
-    from . import reccut
-    from .batch import LayerBatch, PieceTable, quantize_batch
-    from . import _lib
-    from .fingerprint import _to_device_matrix, warn_constant_channel
-    if not fps:
-        return fps
-    _mark('start')
-    lens = [len(fp.seq) for fp in fps]
-    maps = [reccut._contact_tensor(fp.contacts, n) for fp, n in zip(fps, lens)]
-    ctx = _lib.get_context(maps[0].device.index)
-    ctx.get_option('degenerate_seen')                          # (the flag is the context's: drop what earlier callers left unread)
-    # Contact selection and the domain cutter's recursion both run on the GPU (round 5: dctfp_contact_topk + dctfp_reccut; the
-    # host library cost 9 us per protein on 16 threads, and the selected contacts had to come over for it); while the kernels
-    # run, this thread builds the embedding tables.  What comes back is a few ints per domain.
-    built = {}
-    _mark('maps')
-
-    def build_tables():
-        _mark('enqueued top-k + cutter')
-        keys0 = list(fps[0].embed.keys())
-        mats = []
-        for k in keys0:
-            vals = [fp.embed[k] for fp in fps]
-            # straight off the language model (float tensors on the GPU, rows contiguous): nothing to convert -- judged in a few
-            # C-level passes over the list instead of a Python call per tensor; LayerBatch checks shapes and strides itself
-            if not (all(map(torch.is_tensor, vals)) and all(map(_IS_CUDA, vals)) and set(map(_DTYPE, vals)) <= _KEPT_DTYPES):
-                vals = [_to_device_matrix(v, keep_half=True) for v in vals]
-            mats.append(vals)
-        layers = []
-        for i in range(len(keys0)):
-            try:
-                layers.append(LayerBatch(mats[i], qdim[2 * i], qdim[2 * i + 1]))
-            except ValueError:       # (row-strided or transposed views, mixed strides: made contiguous one by one, then judged again)
-                mats[i] = [_to_device_matrix(v, keep_half=True).contiguous() for v in mats[i]]
-                layers.append(LayerBatch(mats[i], qdim[2 * i], qdim[2 * i + 1]))
-        built['keys0'], built['mats'], built['layers'] = keys0, mats, layers
-        _mark('embedding tables')
-
-    cut = {'doms': reccut.domains_from_maps(maps, threshold, threads=max(1, threads), before_wait=build_tables)}
-    _mark('cutter waited for + strings')
-    if 'layers' not in built:
-        build_tables()
-    keys0, mats, layers = built['keys0'], built['mats'], built['layers']
-    for fp, d, n in zip(fps, cut['doms'], lens):
-        if len(d) > 1:
-            d.append(f'1-{n}')                                 # src/fingerprint.py:106-107
-        fp.domains.extend(d)
-    rows = [m.shape[0] for m in mats[0]]
-    _mark('domains extended')
-    table = PieceTable(rows, [fp.domains for fp in fps])
-    _mark('piece table')
-    out = quantize_batch(layers, table)
-    _mark('quantize enqueued')
-    host8 = _to_host(out) if table.n_domains else np.zeros((0, 0), np.int8)
-    _mark('results on the host')
-    if table.n_domains and ctx.get_option('degenerate_seen'):
-        # rare: the flush saw an exactly constant channel (0/0 -> all-zero block, the documented deviation).  Name the proteins.
-        warn_constant_channel(_constant_channel_pids(fps, mats, table) or [fp.pid for fp in fps])
-    host64 = host8.astype(np.int64)                            # np.array(list of ints) in the reference: int64
-    keys = table.keys
-    bounds = np.searchsorted(table.owner, np.arange(len(fps) + 1)).tolist()   # output rows of protein s: [bounds[s], bounds[s+1])
-    for s, fp in enumerate(fps):
-        a, b = bounds[s], bounds[s + 1]
-        ks = keys[a:b]
-        if not fp.quants:
-            q = dict(zip(ks, host64[a:b]))                     # a row already is layer 0's block, layer 1's block, ... (:184-196)
-            if len(q) == b - a:                                # (no key twice: RecCut's domains are disjoint)
-                fp.quants = q
-                fp.domains = ks
-                fp._rows8 = host8[a:b]                         # what the writer stores (see _records)
-                continue
-        _extend_quants(fp, ks, host64[a:b], qdim, len(keys0))
-    _mark('unpacked into the objects')
-    if logging.getLogger().isEnabledFor(logging.INFO):         # one line per protein, as the reference writes them
-        now = datetime.datetime.now()
-        logging.info('\n'.join(f'{now} Fingerprinted {fp.pid}' for fp in fps))
-    return fps
+    fl.start()
+    return fl.finish(objects=False)
 
 
 def _extend_quants(fp, ks, rows, qdim, n_layers):
@@ -423,20 +382,6 @@ def _extend_quants(fp, ks, rows, qdim, n_layers):
 
 
 _PINNED = threading.local()
-
-
-def _to_host(t: torch.Tensor) -> np.ndarray:
-    """Device tensor -> numpy through a page-locked staging buffer (a pageable ``.cpu()`` of a flush's results runs at a
-    fraction of the PCIe rate).  Returns a copy: the staging buffer is reused by the next call of this thread."""
-    n = t.numel()
-    pin = getattr(_PINNED, 'buf', None)
-    if pin is None or pin.dtype != t.dtype or pin.numel() < n:
-        pin = torch.empty(max(n + n // 4, 1 << 20), dtype=t.dtype, pin_memory=True)
-        _PINNED.buf = pin
-    view = pin[:n].view(t.shape)
-    view.copy_(t, non_blocking=True)
-    torch.cuda.current_stream(t.device).synchronize()
-    return view.numpy().copy()
 
 
 def _constant_channel_pids(fps, mats, table):
@@ -510,11 +455,9 @@ def process_sequences(seqs, model, device, maxlen: int, cpu: int, flush: int, si
 
     def finish_pending():
         while pending:
-            fl, q = pending.pop(0)
+            fl = pending.pop(0)
             with stage('fingerprint (contact top-k + RecCut + dctfp_quantize)'):
-                recs = fl.finish(objects=False) if fl is not None else None
-                if recs is None:
-                    recs = _records(_fingerprint_batch_generic(q, threads=cpu))
+                recs = fl.finish(objects=False)
             with stage('hand over to the writer'):
                 sink(recs)
 
@@ -526,9 +469,8 @@ def process_sequences(seqs, model, device, maxlen: int, cpu: int, flush: int, si
         finish_pending()
         with stage('fingerprint (contact top-k + RecCut + dctfp_quantize)'):
             fl = _Flush(q, threads=cpu)
-            if not fl.start():
-                fl = None
-        pending.append((fl, q))
+            fl.start()
+        pending.append(fl)
 
     for pid, seq in seqs:                          # same packing rule as Database.yield_seqs
         if batch and (cur + len(seq) > maxlen or len(batch) > cpu):

@@ -73,6 +73,51 @@ def _pinned_give(name: str, buf: torch.Tensor):
     _PINNED.__dict__.setdefault('free_' + name, []).append(buf)
 
 
+def contact_counts(n_res, t: float):
+    """(counts, offs) of ``dctfp_contact_count`` for all proteins at once: ``min(int(t * L), (L-5)(L-4)/2)`` contacts with
+    j >= i + 5 each; protein p's are ``[offs[p], offs[p+1])``."""
+    L64 = np.asarray(n_res, dtype=np.int64)
+    cand = np.where(L64 >= 6, (L64 - 5) * (L64 - 4) // 2, 0)
+    counts = np.minimum(np.maximum((float(t) * L64.astype(np.float64)).astype(np.int64), 0), cand)
+    offs = np.zeros(len(L64) + 1, dtype=np.int64)
+    np.cumsum(counts, out=offs[1:])
+    return counts, offs
+
+
+def map_geometry(maps: Sequence[torch.Tensor]):
+    """(ptrs, lds, n_res) of a list of contact maps, as ``dctfp_contact_topk`` takes them (C-level passes over the list:
+    three generator passes over 4 096 maps cost 3 ms)."""
+    n = len(maps)
+    n_res = np.fromiter(map(len, maps), dtype=np.int32, count=n)
+    ptrs = np.fromiter(map(torch.Tensor.data_ptr, maps), dtype=np.uint64, count=n)
+    lds = np.fromiter(map(torch.Tensor.stride, maps, repeat(0)), dtype=np.int64, count=n)
+    lds = np.where(n_res > 1, lds, np.maximum(n_res.astype(np.int64), 1))      # (a one-row map may carry any stride)
+    return ptrs, lds, n_res
+
+
+def enqueue_topk(ptrs, lds, n_res, t: float, device, stream):
+    """``dctfp_contact_topk`` on ``stream``, everything left on the device: (counts, offs [host], oi, oj, ov, on [device]);
+    ``on[p]`` is what the kernel wrote for protein p, to be held to ``counts``."""
+    n = len(n_res)
+    counts, offs = contact_counts(n_res, t)
+    total = max(int(offs[-1]), 1)
+    with torch.cuda.stream(stream):
+        oi = torch.empty(total, dtype=torch.int32, device=device)
+        oj = torch.empty(total, dtype=torch.int32, device=device)
+        ov = torch.empty(total, dtype=torch.float32, device=device)
+        on = torch.zeros(n, dtype=torch.int32, device=device)
+    lib = _lib.load()
+    _lib.check(lib.dctfp_contact_topk(_lib.get_context(device.index).handle, ptrs.ctypes.data, lds.ctypes.data, n_res.ctypes.data,
+                                      n, float(t), oi.data_ptr(), oj.data_ptr(), ov.data_ptr(), offs.ctypes.data, on.data_ptr(),
+                                      C.c_void_p(stream.cuda_stream)), lib)
+    return counts, offs, oi, oj, ov, on
+
+
+def _check_counts(written: np.ndarray, counts: np.ndarray):
+    if not (written == counts).all():
+        raise RuntimeError('dctfp_contact_topk wrote a different number of contacts than dctfp_contact_count says')
+
+
 def top_contacts_batch(maps: Sequence[torch.Tensor], t: float, sort: bool = True, own: bool = True):
     """Top ``int(t*L)`` contacts of each map.  Returns (offs, i, j, v) as numpy arrays: protein
     p's contacts are ``[offs[p], offs[p+1])``; with ``sort`` they are ordered by (-v, i, j) -- the
@@ -80,38 +125,21 @@ def top_contacts_batch(maps: Sequence[torch.Tensor], t: float, sort: bool = True
 
     Selection (``dctfp_contact_topk``) and order (``dctfp_contact_sort``) both happen on the GPU; what comes back is one
     copy of the selected entries through page-locked buffers.  ``own=False`` returns views of those buffers instead of
-    copies of them (64 MB for 4 096 proteins of 500 residues: 5 of the call's 12 ms): valid until this thread's next call,
-    which is all a database flush needs (it hands them to the domain cutter and waits for it)."""
+    copies of them (64 MB for 4 096 proteins of 500 residues: 5 of the call's 12 ms): valid until this thread's next call."""
     n = len(maps)
     if n == 0:
         return np.zeros(1, np.int64), np.zeros(0, np.int32), np.zeros(0, np.int32), np.zeros(0, np.float32)
     device = maps[0].device
-    lib = _lib.load()
-    n_res = np.fromiter(map(len, maps), dtype=np.int32, count=n)     # (C-level iteration: three generator passes over 4 096 maps cost 3 ms)
-    # dctfp_contact_count for all proteins at once: min(int(t * L), pairs with j >= i + 5)
-    L64 = n_res.astype(np.int64)
-    cand = np.where(L64 >= 6, (L64 - 5) * (L64 - 4) // 2, 0)
-    counts = np.minimum(np.maximum((float(t) * L64.astype(np.float64)).astype(np.int64), 0), cand)
-    offs = np.zeros(n + 1, dtype=np.int64)
-    np.cumsum(counts, out=offs[1:])
-    total = int(offs[-1])
-    oi = torch.empty(max(total, 1), dtype=torch.int32, device=device)
-    oj = torch.empty(max(total, 1), dtype=torch.int32, device=device)
-    ov = torch.empty(max(total, 1), dtype=torch.float32, device=device)
-    on = torch.zeros(n, dtype=torch.int32, device=device)
-    ptrs = np.fromiter(map(torch.Tensor.data_ptr, maps), dtype=np.uint64, count=n)
-    lds = np.fromiter(map(torch.Tensor.stride, maps, repeat(0)), dtype=np.int64, count=n)
-    lds = np.where(n_res > 1, lds, np.maximum(L64, 1))              # (a one-row map may carry any stride)
-    ctx = _lib.get_context(device.index)
     stream = torch.cuda.current_stream(device)
-    sp = C.c_void_p(stream.cuda_stream)
-    _lib.check(lib.dctfp_contact_topk(ctx.handle, ptrs.ctypes.data, lds.ctypes.data, n_res.ctypes.data, n, float(t),
-                                      oi.data_ptr(), oj.data_ptr(), ov.data_ptr(), offs.ctypes.data, on.data_ptr(), sp))
+    ptrs, lds, n_res = map_geometry(maps)
+    counts, offs, oi, oj, ov, on = enqueue_topk(ptrs, lds, n_res, t, device, stream)
+    total = int(offs[-1])
     on_device = np.ones(n, dtype=np.uint8)
     if sort:
-        _lib.check(lib.dctfp_contact_sort(ctx.handle, ptrs.ctypes.data, lds.ctypes.data, n_res.ctypes.data, n, float(t),
-                                          oi.data_ptr(), oj.data_ptr(), ov.data_ptr(), offs.ctypes.data,
-                                          on_device.ctypes.data, sp))
+        lib = _lib.load()
+        _lib.check(lib.dctfp_contact_sort(_lib.get_context(device.index).handle, ptrs.ctypes.data, lds.ctypes.data,
+                                          n_res.ctypes.data, n, float(t), oi.data_ptr(), oj.data_ptr(), ov.data_ptr(),
+                                          offs.ctypes.data, on_device.ctypes.data, C.c_void_p(stream.cuda_stream)))
     pi, pj, pv, pn = (_pinned('i', torch.int32, total), _pinned('j', torch.int32, total), _pinned('v', torch.float32, total),
                       _pinned('n', torch.int32, n))
     pi.copy_(oi[:total], non_blocking=True)
@@ -122,8 +150,7 @@ def top_contacts_batch(maps: Sequence[torch.Tensor], t: float, sort: bool = True
     hi, hj, hv = pi.numpy(), pj.numpy(), pv.numpy()
     if own:
         hi, hj, hv = hi.copy(), hj.copy(), hv.copy()
-    if not (pn.numpy() == counts).all():
-        raise RuntimeError('dctfp_contact_topk wrote a different number of contacts than dctfp_contact_count says')
+    _check_counts(pn.numpy(), counts)
     for p in (np.flatnonzero(on_device == 0) if sort else ()):       # longer than the device network holds (L > 6 301)
         a, b = offs[p], offs[p + 1]
         order = np.lexsort((hj[a:b], hi[a:b], -hv[a:b].astype(np.float64)))
@@ -131,86 +158,10 @@ def top_contacts_batch(maps: Sequence[torch.Tensor], t: float, sort: bool = True
     return offs, hi, hj, hv
 
 
-def _select_on_device(maps: Sequence[torch.Tensor], t: float):
-    """``dctfp_contact_topk`` for a batch, everything left on the device: (n_res, counts, offs [host], oi, oj, ov, on [device])."""
-    n = len(maps)
-    device = maps[0].device
-    lib = _lib.load()
-    n_res = np.fromiter(map(len, maps), dtype=np.int32, count=n)
-    L64 = n_res.astype(np.int64)
-    cand = np.where(L64 >= 6, (L64 - 5) * (L64 - 4) // 2, 0)
-    counts = np.minimum(np.maximum((float(t) * L64.astype(np.float64)).astype(np.int64), 0), cand)
-    offs = np.zeros(n + 1, dtype=np.int64)
-    np.cumsum(counts, out=offs[1:])
-    total = int(offs[-1])
-    oi = torch.empty(max(total, 1), dtype=torch.int32, device=device)
-    oj = torch.empty(max(total, 1), dtype=torch.int32, device=device)
-    ov = torch.empty(max(total, 1), dtype=torch.float32, device=device)
-    on = torch.zeros(n, dtype=torch.int32, device=device)
-    ptrs = np.fromiter(map(torch.Tensor.data_ptr, maps), dtype=np.uint64, count=n)
-    lds = np.fromiter(map(torch.Tensor.stride, maps, repeat(0)), dtype=np.int64, count=n)
-    lds = np.where(n_res > 1, lds, np.maximum(L64, 1))
-    ctx = _lib.get_context(device.index)
-    sp = C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
-    _lib.check(lib.dctfp_contact_topk(ctx.handle, ptrs.ctypes.data, lds.ctypes.data, n_res.ctypes.data, n, float(t),
-                                      oi.data_ptr(), oj.data_ptr(), ov.data_ptr(), offs.ctypes.data, on.data_ptr(), sp))
-    return n_res, counts, offs, oi, oj, ov, on
-
-
-#: proteins of the last ``domains_from_maps`` / ``domains_from_contacts_gpu`` call of this thread that the GPU cutter handed back
-#: to the host library (status -1) -- tests and profiles read it
+#: proteins of this thread's last ``CutInFlight.wait`` (``domains_from_maps``, ``domains_from_contacts_gpu``, a database flush)
+#: that went through the host library (``host_redo``), and the GPU's own times of the last timed one (``gpu_ms``: top-k, cutter,
+#: copies) -- tests and profiles read them
 LAST = threading.local()
-
-
-def _cut_on_device(n_res, counts, offs, oi, oj, ov, on, cut1, cut2, threads, before_wait):
-    """``dctfp_reccut`` on contacts that already sit on the device (+ the host library for what it hands back)."""
-    n = len(n_res)
-    device = oi.device
-    lib = _lib.load()
-    uniq = np.unique(n_res)
-    room = np.fromiter((lib.dctfp_reccut_room(int(v)) for v in uniq), dtype=np.int64, count=len(uniq))[np.searchsorted(uniq, n_res)]
-    enc_off = np.zeros(n + 1, dtype=np.int64)
-    np.cumsum(room, out=enc_off[1:])
-    enc = torch.empty(int(enc_off[-1]), dtype=torch.int32, device=device)
-    ctx = _lib.get_context(device.index)
-    stream = torch.cuda.current_stream(device)
-    _lib.check(lib.dctfp_reccut(ctx.handle, n_res.ctypes.data, n, oi.data_ptr(), oj.data_ptr(), ov.data_ptr(), offs.ctypes.data,
-                                float(cut1), float(cut2), enc.data_ptr(), enc_off.ctypes.data, C.c_void_p(stream.cuda_stream)), lib)
-    penc = _pinned('enc', torch.int32, int(enc_off[-1]))
-    penc.copy_(enc, non_blocking=True)
-    pn = None
-    if on is not None:
-        pn = _pinned('n', torch.int32, n)
-        pn.copy_(on, non_blocking=True)
-    if before_wait is not None:
-        before_wait()
-    stream.synchronize()
-    if pn is not None and not (pn.numpy() == counts).all():
-        raise RuntimeError('dctfp_contact_topk wrote a different number of contacts than dctfp_contact_count says')
-    rlib = _lib.load_reccut()
-    cap = 64 * n + 16 * int(n_res.astype(np.int64).sum())
-    buf = np.empty(cap, dtype=np.uint8)
-    out_off = np.zeros(n + 1, dtype=np.int64)
-    nd = np.zeros(n, dtype=np.int32)
-    needs = np.zeros(n, dtype=np.uint8)
-    ret = rlib.reccut_format_packed(n, penc.numpy().ctypes.data, enc_off.ctypes.data, buf.ctypes.data, cap, out_off.ctypes.data,
-                                    nd.ctypes.data, needs.ctypes.data)
-    if ret != 0:
-        raise RuntimeError(f'reccut_format_packed failed: {ret}')
-    text = buf[:int(out_off[-1])].tobytes().decode('ascii')
-    bounds = out_off.tolist()
-    doms = [text[a:b].split(';')[:-1] for a, b in zip(bounds[:-1], bounds[1:])]
-    redo = np.flatnonzero(needs)
-    LAST.host_redo = redo.tolist()
-    if len(redo):      # the host library on these proteins' own contacts (copied over now: they are few)
-        sel_off = np.zeros(len(redo) + 1, dtype=np.int64)
-        np.cumsum(counts[redo], out=sel_off[1:])
-        pick = np.concatenate([np.arange(offs[p], offs[p + 1]) for p in redo]) if sel_off[-1] else np.zeros(0, np.int64)
-        pick_t = torch.from_numpy(pick).to(device)
-        hi, hj, hv = (x[pick_t].cpu().numpy() for x in (oi, oj, ov))
-        for p, d in zip(redo.tolist(), domains_from_contacts(n_res[redo], sel_off, hi, hj, hv, cut1, cut2, threads=threads)):
-            doms[p] = d
-    return doms
 
 
 def reccut_room(n_res: np.ndarray) -> np.ndarray:
@@ -221,96 +172,133 @@ def reccut_room(n_res: np.ndarray) -> np.ndarray:
 
 
 class CutInFlight:
-    """Contact selection + domain cutter of a batch, enqueued on ``stream`` (``dctfp_contact_topk`` + ``dctfp_reccut``), the
-    encoded results on their way into a page-locked buffer: what a database flush starts early and picks up when it needs
-    the domains (``make_db._Flush``).  ``ptrs`` / ``lds`` / ``n_res``: the contact maps' geometry (``_geom.tensor_table``).
-    Its page-locked result buffers are its own, from this thread's free list, until ``release()``: any number of batches may be
-    in flight at once."""
+    """The domain cutter of a batch (``dctfp_reccut``), enqueued on ``stream``, the encoded results on their way into a
+    page-locked buffer; ``wait()`` picks them up.  The one GPU cut pipeline: a database flush starts it early and waits for it
+    when it needs the domains (``make_db.Flush``), ``domains_from_maps`` / ``domains_from_contacts_gpu`` wait at once.
+
+    ``CutInFlight(ptrs, lds, n_res, device, t, ...)`` selects the contacts first (``dctfp_contact_topk``) from the contact
+    maps' geometry (``map_geometry`` / ``_geom.tensor_table``); ``CutInFlight.from_contacts`` cuts contact lists already on the
+    device.  Its page-locked result buffers are its own, from this thread's free list, until ``release()``: any number of
+    batches may be in flight at once."""
 
     def __init__(self, ptrs, lds, n_res, device, t: float, cut1=CUT1_DEFAULT, cut2=CUT2_DEFAULT, stream=None,
                  timing: bool = False):
-        lib = _lib.load()
-        self.events = [torch.cuda.Event(enable_timing=True) for _ in range(4)] if timing else None    # (tools/flush_timeline.py)
-        n = len(n_res)
-        self.n = n
+        self._setup(n_res, device, cut1, cut2, stream, timing)
+        self._record(0)
+        self.counts, self.offs, self.oi, self.oj, self.ov, on = enqueue_topk(
+            np.ascontiguousarray(ptrs, dtype=np.uint64), np.ascontiguousarray(lds, dtype=np.int64), self.n_res, t, device,
+            self.stream)
+        self._record(1)
+        self._enqueue_cut(device, on)
+
+    @classmethod
+    def from_contacts(cls, n_res, offs, oi, oj, ov, device, cut1=CUT1_DEFAULT, cut2=CUT2_DEFAULT, stream=None):
+        """The cutter alone on contact lists on the device: protein p's are ``[offs[p], offs[p+1])`` of ``oi`` / ``oj`` / ``ov``."""
+        self = cls.__new__(cls)
+        self._setup(n_res, device, cut1, cut2, stream, False)
+        self.offs = np.ascontiguousarray(offs, dtype=np.int64)
+        self.counts = np.diff(self.offs)
+        self.oi, self.oj, self.ov = oi, oj, ov
+        self._enqueue_cut(device, None)
+        return self
+
+    def _setup(self, n_res, device, cut1, cut2, stream, timing):
         self.n_res = np.ascontiguousarray(n_res, dtype=np.int32)
-        L64 = self.n_res.astype(np.int64)
-        cand = np.where(L64 >= 6, (L64 - 5) * (L64 - 4) // 2, 0)
-        self.counts = np.minimum(np.maximum((float(t) * L64.astype(np.float64)).astype(np.int64), 0), cand)
-        self.offs = np.zeros(n + 1, dtype=np.int64)
-        np.cumsum(self.counts, out=self.offs[1:])
-        total = int(self.offs[-1])
+        self.n = len(self.n_res)
         self.cut1, self.cut2 = float(cut1), float(cut2)
         self.stream = stream if stream is not None else torch.cuda.current_stream(device)
-        ptrs = np.ascontiguousarray(ptrs, dtype=np.uint64)
-        lds = np.ascontiguousarray(lds, dtype=np.int64)
+        self.events = [torch.cuda.Event(enable_timing=True) for _ in range(4)] if timing else None    # (tools/flush_timeline.py)
+
+    def _record(self, i):
+        if self.events is not None:
+            self.events[i].record(self.stream)
+
+    def _enqueue_cut(self, device, on):
+        """``dctfp_reccut`` behind whatever is on the stream, then the copies of its results (and of ``on``, the contacts top-k
+        wrote) into page-locked buffers of this batch's own."""
+        lib = _lib.load()
+        n = self.n
+        self.enc_off = np.zeros(n + 1, dtype=np.int64)
+        np.cumsum(reccut_room(self.n_res), out=self.enc_off[1:])
+        n_enc = int(self.enc_off[-1])
         with torch.cuda.stream(self.stream):
-            self.oi = torch.empty(max(total, 1), dtype=torch.int32, device=device)
-            self.oj = torch.empty(max(total, 1), dtype=torch.int32, device=device)
-            self.ov = torch.empty(max(total, 1), dtype=torch.float32, device=device)
-            on = torch.zeros(n, dtype=torch.int32, device=device)
-            ctx = _lib.get_context(device.index)
-            sp = C.c_void_p(self.stream.cuda_stream)
-            if timing:
-                self.events[0].record(self.stream)
-            _lib.check(lib.dctfp_contact_topk(ctx.handle, ptrs.ctypes.data, lds.ctypes.data, self.n_res.ctypes.data, n, float(t),
-                                              self.oi.data_ptr(), self.oj.data_ptr(), self.ov.data_ptr(), self.offs.ctypes.data,
-                                              on.data_ptr(), sp), lib)
-            if timing:
-                self.events[1].record(self.stream)
-            room = reccut_room(self.n_res)
-            self.enc_off = np.zeros(n + 1, dtype=np.int64)
-            np.cumsum(room, out=self.enc_off[1:])
-            n_enc = int(self.enc_off[-1])
             enc = torch.empty(n_enc, dtype=torch.int32, device=device)
-            _lib.check(lib.dctfp_reccut(ctx.handle, self.n_res.ctypes.data, n, self.oi.data_ptr(), self.oj.data_ptr(), self.ov.data_ptr(),
-                                        self.offs.ctypes.data, self.cut1, self.cut2, enc.data_ptr(), self.enc_off.ctypes.data, sp), lib)
-            if timing:
-                self.events[2].record(self.stream)
-            self._pins = (_pinned_take('enc', torch.int32, n_enc), _pinned_take('n', torch.int32, n))
-            self.penc, self.pn = self._pins[0][:n_enc], self._pins[1][:n]
+            _lib.check(lib.dctfp_reccut(_lib.get_context(device.index).handle, self.n_res.ctypes.data, n, self.oi.data_ptr(),
+                                        self.oj.data_ptr(), self.ov.data_ptr(), self.offs.ctypes.data, self.cut1, self.cut2,
+                                        enc.data_ptr(), self.enc_off.ctypes.data, C.c_void_p(self.stream.cuda_stream)), lib)
+            self._record(2)
+            self._pins = (_pinned_take('enc', torch.int32, n_enc), _pinned_take('n', torch.int32, n) if on is not None else None)
+            self.penc = self._pins[0][:n_enc]
             self.penc.copy_(enc, non_blocking=True)
-            self.pn.copy_(on, non_blocking=True)
-            if timing:
-                self.events[3].record(self.stream)
+            self.pn = None
+            if on is not None:
+                self.pn = self._pins[1][:n]
+                self.pn.copy_(on, non_blocking=True)
+            self._record(3)
             self.done = torch.cuda.Event()
             self.done.record(self.stream)
         self._keep = (enc, on)
 
-    def wait(self) -> np.ndarray:
-        """The encoded results (host view, valid until ``release()``); proteins the GPU cutter handed back (status -1) are
-        redone by the host library here and written into the same encoding."""
+    def wait(self, threads: int = 1, strings: bool = False):
+        """Waits for the results and redoes in the host library (on ``threads`` threads, with each protein's own contacts) what
+        the GPU cutter handed back.  Without ``strings``: the encoded results (host view, valid until ``release()``), the
+        proteins with status < 1 redone and written into the same encoding (where a record does not fit, the status stays -1
+        and the caller sees it).  With ``strings``: per protein the binary's domain strings (``reccut_format_packed``), every
+        protein the format flags redone -- status < 1 or a record it cannot read."""
         self.done.synchronize()
         if self.events is not None:
             e = self.events
             LAST.gpu_ms = (e[0].elapsed_time(e[1]), e[1].elapsed_time(e[2]), e[2].elapsed_time(e[3]))   # top-k, cutter, copies
-        if not (self.pn.numpy() == self.counts).all():
-            raise RuntimeError('dctfp_contact_topk wrote a different number of contacts than dctfp_contact_count says')
+        if self.pn is not None:
+            _check_counts(self.pn.numpy(), self.counts)
         enc = self.penc.numpy()
-        redo = np.flatnonzero(enc[self.enc_off[:-1]] < 1)
+        if strings:
+            doms, redo = _format_packed(self.n, enc, self.enc_off, self.n_res)
+        else:
+            redo = np.flatnonzero(enc[self.enc_off[:-1]] < 1)
         LAST.host_redo = redo.tolist()
-        self.redo_strings = {}
-        if len(redo):
+        if len(redo):      # the host library on these proteins' own contacts (copied over now: they are few)
             sel_off = np.zeros(len(redo) + 1, dtype=np.int64)
             np.cumsum(self.counts[redo], out=sel_off[1:])
             pick = np.concatenate([np.arange(self.offs[p], self.offs[p + 1]) for p in redo]) if sel_off[-1] else np.zeros(0, np.int64)
             pick_t = torch.from_numpy(pick).to(self.oi.device)
             hi, hj, hv = (x[pick_t].cpu().numpy() for x in (self.oi, self.oj, self.ov))
-            for p, d in zip(redo.tolist(), domains_from_contacts(self.n_res[redo], sel_off, hi, hj, hv, self.cut1, self.cut2)):
-                self.redo_strings[p] = d
+            for p, d in zip(redo.tolist(), domains_from_contacts(self.n_res[redo], sel_off, hi, hj, hv, self.cut1, self.cut2,
+                                                                 threads=threads)):
+                if strings:
+                    doms[p] = d
+                    continue
                 rec = _encode_domains(d)
                 a, b = int(self.enc_off[p]), int(self.enc_off[p + 1])
                 if rec is not None and len(rec) <= b - a:
-                    enc[a:a + len(rec)] = rec           # (else: status stays -1 and the caller parses the strings itself)
-        return enc
+                    enc[a:a + len(rec)] = rec
+        return doms if strings else enc
 
     def release(self):
         """Waits for the copies into the page-locked result buffers and puts those back on this thread's free list."""
         if self._pins is not None:
             self.done.synchronize()
             _pinned_give('enc', self._pins[0])
-            _pinned_give('n', self._pins[1])
+            if self._pins[1] is not None:
+                _pinned_give('n', self._pins[1])
             self._pins = self.penc = self.pn = None
+
+
+def _format_packed(n: int, enc: np.ndarray, enc_off: np.ndarray, n_res: np.ndarray):
+    """``reccut_format_packed``: (per protein the domain strings, proteins it flags for the host library)."""
+    rlib = _lib.load_reccut()
+    cap = 64 * n + 16 * int(n_res.astype(np.int64).sum())
+    buf = np.empty(cap, dtype=np.uint8)
+    out_off = np.zeros(n + 1, dtype=np.int64)
+    nd = np.zeros(n, dtype=np.int32)
+    needs = np.zeros(n, dtype=np.uint8)
+    ret = rlib.reccut_format_packed(n, enc.ctypes.data, enc_off.ctypes.data, buf.ctypes.data, cap, out_off.ctypes.data,
+                                    nd.ctypes.data, needs.ctypes.data)
+    if ret != 0:
+        raise RuntimeError(f'reccut_format_packed failed: {ret}')
+    text = buf[:int(out_off[-1])].tobytes().decode('ascii')
+    bounds = out_off.tolist()
+    return [text[a:b].split(';')[:-1] for a, b in zip(bounds[:-1], bounds[1:])], np.flatnonzero(needs)
 
 
 def _encode_domains(doms: List[str]):
@@ -330,6 +318,15 @@ def _encode_domains(doms: List[str]):
     return np.asarray(rec, dtype=np.int32) if doms else None
 
 
+def _wait_strings(cut: CutInFlight, threads: int, before_wait=None) -> List[List[str]]:
+    try:
+        if before_wait is not None:
+            before_wait()
+        return cut.wait(threads, strings=True)
+    finally:
+        cut.release()
+
+
 def domains_from_maps(maps: Sequence[torch.Tensor], t: float, cut1=CUT1_DEFAULT, cut2=CUT2_DEFAULT, threads: int = 1,
                       before_wait=None) -> List[List[str]]:
     """``Fingerprint.reccut``'s domain lists for a batch of contact maps with NOTHING but the answer leaving the GPU: the contact
@@ -337,11 +334,11 @@ def domains_from_maps(maps: Sequence[torch.Tensor], t: float, cut1=CUT1_DEFAULT,
     workgroup per protein) run back to back on the device; what comes over is a few ints per domain, which libreccut formats
     into the binary's strings.  Proteins the GPU cutter hands back (status -1: longer than its tables, or a step the
     reference leaves undefined) go through the host library on their own contacts.  ``before_wait`` (a callable) runs after
-    the kernels are enqueued and before this thread waits for them -- a flush builds its embedding tables there."""
+    the kernels are enqueued and before this thread waits for them."""
     if len(maps) == 0:
         return []
-    n_res, counts, offs, oi, oj, ov, on = _select_on_device(maps, t)
-    return _cut_on_device(n_res, counts, offs, oi, oj, ov, on, cut1, cut2, threads, before_wait)
+    ptrs, lds, n_res = map_geometry(maps)
+    return _wait_strings(CutInFlight(ptrs, lds, n_res, maps[0].device, t, cut1, cut2), threads, before_wait)
 
 
 def domains_from_contacts_gpu(n_res: Sequence[int], offs, ci, cj, cv, cut1=CUT1_DEFAULT, cut2=CUT2_DEFAULT, threads: int = 1,
@@ -351,14 +348,13 @@ def domains_from_contacts_gpu(n_res: Sequence[int], offs, ci, cj, cv, cut1=CUT1_
     n_res = np.ascontiguousarray(n_res, dtype=np.int32)
     if len(n_res) == 0:
         return []
-    offs = np.ascontiguousarray(offs, dtype=np.int64)
     device = device if device is not None else torch.device('cuda', torch.cuda.current_device())
     oi = torch.from_numpy(np.ascontiguousarray(ci, dtype=np.int32)).to(device)
     oj = torch.from_numpy(np.ascontiguousarray(cj, dtype=np.int32)).to(device)
     ov = torch.from_numpy(np.ascontiguousarray(cv, dtype=np.float32)).to(device)
     if oi.numel() == 0:
         oi, oj, ov = (torch.zeros(1, dtype=d, device=device) for d in (torch.int32, torch.int32, torch.float32))
-    return _cut_on_device(n_res, np.diff(offs), offs, oi, oj, ov, None, cut1, cut2, threads, None)
+    return _wait_strings(CutInFlight.from_contacts(n_res, offs, oi, oj, ov, device, cut1, cut2), threads)
 
 
 def ce_text(pid: str, seq: str, ci, cj, cv) -> str:

@@ -242,47 +242,138 @@ def _embedded(lens, seed=5, dim=640):
     return fresh
 
 
-def test_two_phase_flush_equals_the_general_path_and_the_records():
+def _assert_same_as_queue_cpu(got, ref):
+    """Objects of a flush against ``queue_cpu`` run protein by protein: domains, key order, int64 quants."""
+    for fa, fb in zip(got, ref):
+        assert fa.domains == fb.domains and list(fa.quants) == list(fb.quants) == fa.domains, fa.pid
+        for k in fa.domains:
+            assert fa.quants[k].dtype == np.int64 == np.asarray(fb.quants[k]).dtype
+            np.testing.assert_array_equal(fa.quants[k], fb.quants[k], err_msg=f'{fa.pid} {k}')
+
+
+def test_two_phase_flush_equals_queue_cpu_and_the_records():
     """The flush as make_db runs it (geometry in one pass, strings + pieces from the cutter's integers, objects laid out while the
-    kernels run) against the general path it replaced, object for object; the writer's records against both; proteins the GPU
-    cutter hands back (L > 2 048), single-domain and 30-residue proteins inside."""
+    kernels run) against queue_cpu run protein by protein on fresh objects (the host RecCut library and the one-protein
+    quantize), object for object; the writer's records against both; proteins the GPU cutter hands back (L > 2 048),
+    single-domain and 30-residue proteins inside."""
     from dctdomain_amd import make_db, reccut
     rng = np.random.default_rng(3)
     lens = np.clip(rng.gamma(2.2, 150.0, size=160).astype(int), 30, 1500).tolist() + [30, 31, 45, 2100, 640, 2300, 97]
     fresh = _embedded(lens)
     a = make_db.fingerprint_batch(fresh(), threads=4)
     assert make_db.LAST_PATH[0] == 'flush' and sorted(reccut.LAST.host_redo) == [163, 165]
-    b = make_db._fingerprint_batch_generic(fresh(), threads=4)
+    b = [make_db.queue_cpu(fp) for fp in fresh()]
     recs = make_db.flush_records(fresh(), threads=4)
     assert make_db.LAST_PATH[0] == 'flush'
-    recs_b = make_db._records(b)
+    _assert_same_as_queue_cpu(a, b)
     n_multi = 0
-    for fa, fb, ra, rb in zip(a, b, recs, recs_b):
-        assert fa.domains == fb.domains and list(fa.quants) == list(fb.quants) == fa.domains
+    for fa, fb, ra in zip(a, b, recs):
         n_multi += len(fa.domains) > 1
-        for k in fa.domains:
-            assert fa.quants[k].dtype == np.int64 == fb.quants[k].dtype
-            np.testing.assert_array_equal(fa.quants[k], fb.quants[k])
-        assert ra[0] == rb[0] == fa.pid and ra[1] == rb[1] == fa.domains
+        assert ra[0] == fb.pid == fa.pid and ra[1] == fb.domains == fa.domains
         assert ra[2].dtype == np.int8 and ra[2].shape == (len(fa.domains), 480)
-        np.testing.assert_array_equal(ra[2], rb[2])
+        np.testing.assert_array_equal(ra[2].astype(np.int64), np.array([fb.quants[k] for k in fb.domains]))
         np.testing.assert_array_equal(ra[2].astype(np.int64), np.array([fa.quants[k] for k in fa.domains]))
     assert n_multi >= 100
     np.testing.assert_array_equal(make_db._records(a)[7][2], recs[7][2])
-    # what the plain flush does not take goes the general way, with the same results: numpy inputs, domains given by the caller
-    c = fresh()
-    for fp in c[:5]:
+
+
+def _every_other_row_strided(fps):
+    for fp in fps[::2]:
+        wide = {}
+        for k, v in fp.embed.items():
+            w = torch.zeros((v.shape[0], v.shape[1] + 64), dtype=v.dtype, device=v.device)
+            w[:, :v.shape[1]] = v
+            wide[k] = w[:, :v.shape[1]]
+        fp.embed = wide
+
+
+def _mixed(fps):
+    for fp in fps[len(fps) // 2:]:
+        fp.contacts = fp.contacts.cpu().numpy()
         fp.embed = {k: v.cpu().numpy() for k, v in fp.embed.items()}
-    c = make_db.fingerprint_batch(c, threads=4)
-    assert make_db.LAST_PATH[0] == 'generic'
-    d = fresh()
-    d[2].domains = ['1-20']
-    d = make_db.fingerprint_batch(d, threads=4)
-    assert make_db.LAST_PATH[0] == 'generic' and d[2].domains[0] == '1-20'
-    for fa, fc in zip(a, c):
-        assert fa.domains == fc.domains
-        for k in fa.domains:
-            np.testing.assert_array_equal(fa.quants[k], fc.quants[k])
+
+
+def _embed_as(f):
+    return lambda fps: [setattr(fp, 'embed', {k: f(v) for k, v in fp.embed.items()}) for fp in fps]
+
+
+def _maps_as(f):
+    return lambda fps: [setattr(fp, 'contacts', f(fp.contacts)) for fp in fps]
+
+
+#: every input kind the flush converts (or builds the piece table from strings for), and those it takes as they are
+_INPUT_KINDS = {
+    'numpy embeddings': (_embed_as(lambda v: v.cpu().numpy()), 'converted'),
+    'cpu embeddings': (_embed_as(lambda v: v.cpu()), 'converted'),
+    'numpy maps': (_maps_as(lambda c: c.cpu().numpy()), 'converted'),
+    'cpu maps': (_maps_as(lambda c: c.cpu()), 'converted'),
+    'flat maps': (_maps_as(lambda c: c.reshape(-1)), 'converted'),
+    'transposed embeddings': (_embed_as(lambda v: v.t().contiguous().t()), 'converted'),
+    'row-strided embeddings': (_every_other_row_strided, 'converted'),
+    'integer numpy embeddings': (_embed_as(lambda v: (v * 100).round().cpu().numpy().astype(np.int32)), 'converted'),
+    'embeddings one row short': (_embed_as(lambda v: v[:-1]), 'converted'),
+    'domains given': (lambda fps: [setattr(fp, 'domains', ['1-20', '5-9,30-40']) for fp in fps[::3]], 'converted'),
+    'mixed plain and converted': (_mixed, 'converted'),
+    'cuda float16 embeddings': (_embed_as(lambda v: v.half()), 'flush'),
+    'cuda bfloat16 embeddings': (_embed_as(lambda v: v.bfloat16()), 'flush'),
+}
+
+
+@pytest.mark.parametrize('kind', list(_INPUT_KINDS) + ['quants present'])
+def test_every_input_kind_through_the_one_flush_equals_queue_cpu(kind):
+    """What the flush does not take as it is -- numpy / CPU / flat maps, numpy / CPU / integer / transposed / row-strided
+    embeddings, embeddings of another length than the sequence, domains given by the caller, fingerprints already there (a
+    second flush on the same objects: the reference's second quantize) -- is converted and goes through the same flush, with
+    the results of queue_cpu run protein by protein (one protein handed back to the host library inside); the writer's records
+    are those of the objects.  Half-precision GPU embeddings are taken as they are."""
+    from dctdomain_amd import make_db
+    lens = [120, 31, 260, 45, 2100, 330, 700, 97, 22, 410, 150, 80]
+    fresh = _embedded(lens, seed=17)
+    if kind == 'quants present':
+        got = make_db.fingerprint_batch(make_db.fingerprint_batch(fresh(), threads=4), threads=4)
+        path = make_db.LAST_PATH[0]
+        ref = [make_db.queue_cpu(make_db.queue_cpu(fp)) for fp in fresh()]
+        recs = make_db.flush_records(make_db.fingerprint_batch(fresh(), threads=4), threads=4)
+        want = 'converted'
+    else:
+        change, want = _INPUT_KINDS[kind]
+        fps, ref, more = fresh(), fresh(), fresh()
+        for x in (fps, ref, more):
+            change(x)
+        got = make_db.fingerprint_batch(fps, threads=4)
+        path = make_db.LAST_PATH[0]
+        ref = [make_db.queue_cpu(fp) for fp in ref]
+        recs = make_db.flush_records(more, threads=4)
+    assert path == want and make_db.LAST_PATH[0] == want, (kind, path, make_db.LAST_PATH[0])
+    _assert_same_as_queue_cpu(got, ref)
+    assert sum(len(fp.domains) > 1 for fp in ref) >= 3
+    for r, e in zip(recs, make_db._records(ref)):
+        assert r[0] == e[0] and r[1] == e[1]
+        assert r[2].dtype == np.int8
+        np.testing.assert_array_equal(r[2], e[2])
+
+
+def test_inputs_the_flush_refuses_raise_what_they_raised():
+    """Embeddings far shorter than their sequences (a domain of 2 rows: the reference's reshape fails) and float32 and float64
+    proteins in one layer raise ValueError, as they did before the flush took every input; the next flush is whole."""
+    from dctdomain_amd import make_db
+    fresh = _embedded([120, 260, 45, 330], seed=19)
+    for fn in (make_db.fingerprint_batch, make_db.flush_records):
+        fps = fresh()
+        for fp in fps:
+            fp.embed = {k: v[:2] for k, v in fp.embed.items()}
+        with pytest.raises(ValueError):
+            fn(fps, threads=2)
+        fps = fresh()
+        for fp in fps[1::2]:
+            fp.embed = {k: v.double() if k == 15 else v for k, v in fp.embed.items()}
+        with pytest.raises(ValueError):
+            fn(fps, threads=2)
+    recs, ref = make_db.flush_records(fresh(), threads=2), [make_db.queue_cpu(fp) for fp in fresh()]
+    assert make_db.LAST_PATH[0] == 'flush'
+    for r, e in zip(recs, make_db._records(ref)):
+        assert r[1] == e[1]
+        np.testing.assert_array_equal(r[2], e[2])
 
 
 def test_process_sequences_with_deferred_second_halves_keeps_the_order():

@@ -60,7 +60,6 @@ def timed(label, fn, reps=5):
 
 timed(f'fingerprint_batch + _records of {n} (objects filled as queue_cpu does)', lambda q: make_db._records(make_db.fingerprint_batch(q, threads=16)))
 timed(f'flush_records of {n} (what make_db hands its writer)', lambda q: make_db.flush_records(q, threads=16))
-timed(f'general path of {n} (round 5, first half)', lambda q: make_db._records(make_db._fingerprint_batch_generic(q, threads=16)), reps=3)
 
 
 def two_halves(q):
@@ -72,7 +71,6 @@ def two_halves(q):
     t_mid = time.perf_counter()
     recs = fl.finish(objects=False)
     two_halves.second = time.perf_counter() - t_mid
-    make_db.LAST_PATH[0] = 'flush'
     return recs
 
 
@@ -81,10 +79,8 @@ timed(f'the two halves of a flush of {n} apart (as process_sequences runs them)'
 maps = [reccut._contact_tensor(f.contacts, len(f.seq)) for f in queue]
 for rep in range(2):
     torch.cuda.synchronize()
-    e = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
-    e[0].record()
-    sel = reccut._select_on_device(maps, make_db.THRESHOLD)
-    e[1].record()
-    doms = reccut._cut_on_device(*sel, reccut.CUT1_DEFAULT, reccut.CUT2_DEFAULT, 16, lambda: e[2].record())
-    torch.cuda.synchronize()
-print(f'GPU: contact top-k {e[0].elapsed_time(e[1]):.2f} ms (incl. its enqueue), cutter {e[1].elapsed_time(e[2]):.2f} ms')
+    cut = reccut.CutInFlight(*reccut.map_geometry(maps), dev, make_db.THRESHOLD, timing=True)
+    cut.wait(16)
+    cut.release()
+g = reccut.LAST.gpu_ms
+print(f'GPU: contact top-k {g[0]:.2f} ms, cutter {g[1]:.2f} ms, results to the host {g[2]:.2f} ms')

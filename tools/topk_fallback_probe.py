@@ -21,10 +21,10 @@ for a, b in zip(edges[:-1], edges[1:]):
     sel = [m for m, L in zip(maps, lens) if a <= L < b]
     if not sel:
         continue
-    reccut._select_on_device(sel, 2.6); torch.cuda.synchronize()
+    reccut.enqueue_topk(*reccut.map_geometry(sel), 2.6, dev, torch.cuda.current_stream(dev)); torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(3):
-        reccut._select_on_device(sel, 2.6)
+        reccut.enqueue_topk(*reccut.map_geometry(sel), 2.6, dev, torch.cuda.current_stream(dev))
     torch.cuda.synchronize()
     print(f'L in [{a}, {b}): {len(sel):4d} maps, {1e3 * (time.perf_counter() - t0) / 3:7.3f} ms per call', flush=True)
 m = maps[int(np.argmax((lens > 500) & (lens < 560)))] if ((lens > 500) & (lens < 560)).any() else None
