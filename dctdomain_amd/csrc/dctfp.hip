@@ -2711,6 +2711,57 @@ int dctfp_sim_lines(dctfp_ctx* ctx, const int32_t* mn, const int32_t* last, int6
     return DCTFP_OK;
 } DCTFP_GUARD("dctfp_sim_lines")
 
+int dctfp_tri_filter_count(dctfp_ctx* ctx, const int32_t* tile, int64_t n_rows, int64_t n_cols, int64_t ld, int64_t row0, int64_t col0,
+                           const uint8_t* row_empty, const uint8_t* col_empty, int32_t cap, int32_t bound, int32_t* out_count,
+                           void* stream_v) try {
+    if (!ctx || !tile || !out_count) return fail(DCTFP_ERR_INVALID, "dctfp_tri_filter_count: NULL argument");
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    if (n_rows < 0 || n_cols < 0 || ld < n_cols || row0 < 0 || col0 < 0 || cap < 0 || bound < -1 || bound > cap ||
+        (reinterpret_cast<uintptr_t>(tile) & 3u) != 0)
+        return fail(DCTFP_ERR_INVALID, "dctfp_tri_filter_count: bad shape, bound or alignment");
+    if (row0 + n_rows > 0x7fffffff || col0 + n_cols > 0x7fffffff)
+        return fail(DCTFP_ERR_LIMIT, "dctfp_tri_filter_count: protein indices above 2^31 - 1");
+    if (n_rows == 0) return DCTFP_OK;
+    HIP_TRY(hipSetDevice(ctx->device));
+    launch_tri_filter_count(tile, n_rows, n_cols, ld, row0, col0, row_empty, col_empty, cap, bound, out_count, (hipStream_t)stream_v);
+    HIP_TRY(hipGetLastError());
+    return DCTFP_OK;
+} DCTFP_GUARD("dctfp_tri_filter_count")
+
+int dctfp_tri_filter_fill(dctfp_ctx* ctx, const int32_t* tile, int64_t n_rows, int64_t n_cols, int64_t ld, int64_t row0, int64_t col0,
+                          const uint8_t* row_empty, const uint8_t* col_empty, int32_t cap, int32_t bound, const int64_t* offsets,
+                          int64_t out_len, int32_t* out_i, int32_t* out_j, void* stream_v) try {
+    if (!ctx || !tile || !offsets || !out_i || !out_j) return fail(DCTFP_ERR_INVALID, "dctfp_tri_filter_fill: NULL argument");
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    if (n_rows < 0 || n_cols < 0 || ld < n_cols || row0 < 0 || col0 < 0 || cap < 0 || bound < -1 || bound > cap || out_len < 0 ||
+        (reinterpret_cast<uintptr_t>(tile) & 3u) != 0)
+        return fail(DCTFP_ERR_INVALID, "dctfp_tri_filter_fill: bad shape, bound or alignment");
+    if (row0 + n_rows > 0x7fffffff || col0 + n_cols > 0x7fffffff)
+        return fail(DCTFP_ERR_LIMIT, "dctfp_tri_filter_fill: protein indices above 2^31 - 1");
+    if (n_rows == 0 || n_cols == 0 || out_len == 0) return DCTFP_OK;
+    HIP_TRY(hipSetDevice(ctx->device));
+    launch_tri_filter_fill(tile, n_rows, n_cols, ld, row0, col0, row_empty, col_empty, cap, bound, offsets, out_len, out_i, out_j,
+                           (hipStream_t)stream_v);
+    HIP_TRY(hipGetLastError());
+    return DCTFP_OK;
+} DCTFP_GUARD("dctfp_tri_filter_fill")
+
+int dctfp_pair_lines(dctfp_ctx* ctx, int64_t n_lines, const int32_t* pi, const int32_t* pj, const int32_t* mn, const int32_t* last,
+                     const uint8_t* ids, const int64_t* id_off, int64_t n_ids, const char* table, const int64_t* line_off, uint8_t* out,
+                     int64_t out_bytes, void* stream_v) try {
+    if (!ctx || !pi || !pj || !mn || !last || !ids || !id_off || !table || !line_off || !out)
+        return fail(DCTFP_ERR_INVALID, "dctfp_pair_lines: NULL argument");
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    if (n_lines < 0 || n_ids < 0 || out_bytes < 0) return fail(DCTFP_ERR_INVALID, "dctfp_pair_lines: bad shape");
+    // (sixteen lanes per line in 256-thread workgroups; the grid must stay below 2^32 workgroups)
+    if (n_lines > (int64_t)1 << 31) return fail(DCTFP_ERR_LIMIT, "dctfp_pair_lines: more than 2^31 lines per call");
+    if (n_lines == 0) return DCTFP_OK;
+    HIP_TRY(hipSetDevice(ctx->device));
+    launch_pair_lines(n_lines, pi, pj, mn, last, ids, id_off, n_ids, table, line_off, out, out_bytes, (hipStream_t)stream_v);
+    HIP_TRY(hipGetLastError());
+    return DCTFP_OK;
+} DCTFP_GUARD("dctfp_pair_lines")
+
 int dctfp_l1_knn(dctfp_ctx* ctx, const int8_t* q, int64_t nq, int64_t ldq, const int8_t* b, int64_t nb, int64_t ldb, int32_t d, int32_t k,
                  int64_t col0, int32_t* out_val, int32_t* out_idx, void* stream_v) try {
     if (!ctx || !q || !b || !out_val || !out_idx) return fail(DCTFP_ERR_INVALID, "dctfp_l1_knn: NULL argument");

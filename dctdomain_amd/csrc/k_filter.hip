@@ -1,0 +1,210 @@
+// dct-sim all-against-all with score cut-offs (--min-domain / --min-global): the pairs of the upper triangle that pass a
+// cut-off, selected on the device in output order, and the result lines of those pairs only:
+//   tri_filter_count_kernel -- per row of an int32 tile of L1 values: #(entries right of the diagonal with key <= bound);
+//   tri_filter_fill_kernel  -- those entries' (i, j), compacted in column order at the caller's prefix sum of the counts;
+//   pair_lines_kernel       -- "{id_i} {id_j} {a} {b}\n" for a list of pairs at caller-computed offsets (sim_lines_kernel's text,
+//                              without its closed form for the dense row).
+// No global atomic decides a position: a row's survivors go out in column order within one workgroup, rows at their offsets.
+#define DCTFP_TEMPLATES_ONLY
+#include "launch.h"
+
+namespace {
+
+constexpr int kFilterThreads = 256;            // one workgroup per row at a time
+constexpr int kFilterWaves = kFilterThreads / 64;
+constexpr int kFilterStep = kFilterThreads * 4;   // columns per step: one 16-byte load per thread
+constexpr int kLineLanes = 16;                 // lanes per result line
+constexpr int kLineThreads = 256;
+constexpr int kScoreRows = 17002;
+
+// The four entries a thread looks at in one step and which of them survive.  `v` counts columns from the 16-byte boundary at
+// or below the row's first entry (`shift` = entries between the two), so that v % 4 == 0 is a 16-byte aligned address: a quad
+// inside the row is one 16-byte load, the quads at the row's ends are read entry by entry.  Entry c survives when
+// c_min <= c < n_cols and min(L1, cap) <= bound, an empty protein on either side having key cap.
+struct Quad {
+    bool keep[4];
+};
+
+__device__ inline Quad filter_quad(const int32_t* __restrict__ row, int64_t v, int shift, int64_t c_min, int64_t n_cols, bool row_is_empty,
+                                   const uint8_t* __restrict__ col_empty, int32_t cap, int32_t bound) {
+    Quad q;
+    const int64_t c0 = v - shift;
+    uint32_t x[4] = {0u, 0u, 0u, 0u};
+    if (c0 >= 0 && c0 + 4 <= n_cols) {
+        const uint4 w = *reinterpret_cast<const uint4*>(row + c0);
+        x[0] = w.x;
+        x[1] = w.y;
+        x[2] = w.z;
+        x[3] = w.w;
+    } else {
+#pragma unroll
+        for (int e = 0; e < 4; ++e)
+            if (c0 + e >= 0 && c0 + e < n_cols) x[e] = (uint32_t)row[c0 + e];
+    }
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        const int64_t c = c0 + e;
+        const bool inside = c >= c_min && c < n_cols;
+        // (a negative value -- no L1 is -- counts as cap, as in select_count_kernel)
+        const bool full = row_is_empty || x[e] >= (uint32_t)cap || (inside && col_empty && col_empty[c]);
+        const int32_t key = full ? cap : (int32_t)x[e];
+        q.keep[e] = inside && key <= bound;
+    }
+    return q;
+}
+
+// Row r of the tile is protein i = row0 + r, column c protein j = col0 + c; only j > i counts: c >= c_min.
+__device__ inline int64_t first_column(int64_t row0, int64_t r, int64_t col0) { return max((int64_t)0, row0 + r + 1 - col0); }
+
+__device__ inline int row_shift(const int32_t* row) { return (int)((reinterpret_cast<uintptr_t>(row) >> 2) & 3u); }
+
+// out_count[r] = #survivors of row r.  One workgroup per row (rows loop over the grid), 1024 columns per step, a ballot and a
+// population count per entry of the quad, the waves' sums through LDS.
+__global__ __launch_bounds__(kFilterThreads) void tri_filter_count_kernel(const int32_t* __restrict__ tile, int64_t n_rows, int64_t n_cols,
+                                                                           int64_t ld, int64_t row0, int64_t col0,
+                                                                           const uint8_t* __restrict__ row_empty,
+                                                                           const uint8_t* __restrict__ col_empty, int32_t cap, int32_t bound,
+                                                                           int32_t* __restrict__ out_count) {
+    __shared__ int32_t wsum[kFilterWaves];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    for (int64_t r = blockIdx.x; r < n_rows; r += gridDim.x) {
+        const int32_t* row = tile + r * ld;
+        const int shift = row_shift(row);
+        const int64_t c_min = first_column(row0, r, col0);
+        const bool row_is_empty = row_empty && row_empty[r];
+        int32_t n = 0;   // (wave-uniform)
+        for (int64_t v0 = (c_min + shift) & ~(int64_t)3; v0 < n_cols + shift; v0 += kFilterStep) {
+            const Quad q = filter_quad(row, v0 + 4 * tid, shift, c_min, n_cols, row_is_empty, col_empty, cap, bound);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) n += __popcll(__ballot(q.keep[e]));
+        }
+        if (lane == 0) wsum[wave] = n;
+        __syncthreads();
+        if (tid == 0) {
+            int32_t s = 0;
+            for (int w = 0; w < kFilterWaves; ++w) s += wsum[w];
+            out_count[r] = s;
+        }
+        __syncthreads();   // (wsum is rewritten for the next row)
+    }
+}
+
+// The survivors of row r, in column order, to out_i / out_j [offsets[r], offsets[r + 1]) as global protein indices.  Same walk
+// as the count; a thread's place within a step = the survivors of the lanes below it (ballots) + of the waves below it (LDS,
+// double buffered: one barrier per step) + of its own earlier entries.  Nothing is written at or beyond out_len, nor beyond
+// the row's range.
+__global__ __launch_bounds__(kFilterThreads) void tri_filter_fill_kernel(const int32_t* __restrict__ tile, int64_t n_rows, int64_t n_cols,
+                                                                          int64_t ld, int64_t row0, int64_t col0,
+                                                                          const uint8_t* __restrict__ row_empty,
+                                                                          const uint8_t* __restrict__ col_empty, int32_t cap, int32_t bound,
+                                                                          const int64_t* __restrict__ offsets, int64_t out_len,
+                                                                          int32_t* __restrict__ out_i, int32_t* __restrict__ out_j) {
+    __shared__ int32_t wtot[2][kFilterWaves];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const unsigned long long below = (1ull << lane) - 1;
+    int64_t step = 0;   // (over all rows of this workgroup: the LDS buffers alternate)
+    for (int64_t r = blockIdx.x; r < n_rows; r += gridDim.x) {
+        const int32_t* row = tile + r * ld;
+        const int shift = row_shift(row);
+        const int64_t c_min = first_column(row0, r, col0);
+        const bool row_is_empty = row_empty && row_empty[r];
+        const int64_t base = offsets[r], len = min(offsets[r + 1], out_len) - base;
+        int64_t done = 0;
+        for (int64_t v0 = (c_min + shift) & ~(int64_t)3; v0 < n_cols + shift && done < len; v0 += kFilterStep, ++step) {
+            const int64_t v = v0 + 4 * tid;
+            const Quad q = filter_quad(row, v, shift, c_min, n_cols, row_is_empty, col_empty, cap, bound);
+            int32_t before = 0, mine = 0;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const unsigned long long b = __ballot(q.keep[e]);
+                before += __popcll(b & below);
+                mine += __popcll(b);
+            }
+            const int buf = (int)(step & 1);
+            if (lane == 0) wtot[buf][wave] = mine;
+            __syncthreads();
+            int32_t total = 0;
+            for (int w = 0; w < kFilterWaves; ++w) {
+                const int32_t t = wtot[buf][w];
+                if (w < wave) before += t;
+                total += t;
+            }
+            int64_t pos = done + before;
+#pragma unroll
+            for (int e = 0; e < 4; ++e)
+                if (q.keep[e]) {
+                    if (pos < len) {
+                        out_i[base + pos] = (int32_t)(row0 + r);
+                        out_j[base + pos] = (int32_t)(col0 + v - shift + e);
+                    }
+                    ++pos;
+                }
+            done += total;
+        }
+    }
+}
+
+// Line n = "{id_i} {id_j} {a} {b}\n" from byte line_off[n] of out: i = pi[n], j = pj[n], a / b = the five bytes of rows
+// min(mn[n], 17001) / min(last[n], 17001) of the two halves of the score table (sim_lines_kernel's).  Sixteen lanes per line,
+// lane l writing bytes l, l + 16, ...: byte stores, any id length, any alignment.  A line with an index outside [0, n_ids) or
+// an end beyond out_bytes is not written.
+__global__ __launch_bounds__(kLineThreads) void pair_lines_kernel(int64_t n_lines, const int32_t* __restrict__ pi, const int32_t* __restrict__ pj,
+                                                                  const int32_t* __restrict__ mn, const int32_t* __restrict__ last,
+                                                                  const uint8_t* __restrict__ ids, const int64_t* __restrict__ id_off,
+                                                                  int64_t n_ids, const char* __restrict__ table,
+                                                                  const int64_t* __restrict__ line_off, uint8_t* __restrict__ out,
+                                                                  int64_t out_bytes) {
+    const int64_t t = (int64_t)blockIdx.x * kLineThreads + threadIdx.x;
+    const int64_t n = t / kLineLanes;
+    const int sub = (int)(t % kLineLanes);
+    if (n >= n_lines) return;
+    const int64_t i = pi[n], j = pj[n];
+    if (i < 0 || i >= n_ids || j < 0 || j >= n_ids) return;
+    const int64_t off_i = id_off[i], len_i = id_off[i + 1] - off_i, off_j = id_off[j], len_j = id_off[j + 1] - off_j;
+    const int64_t at = line_off[n], total = len_i + len_j + 14;
+    if (at < 0 || at + total > out_bytes) return;
+    const char* __restrict__ ta = table + 5 * (int64_t)min((uint32_t)mn[n], (uint32_t)(kScoreRows - 1));
+    const char* __restrict__ tb = table + 5 * (int64_t)(kScoreRows + min((uint32_t)last[n], (uint32_t)(kScoreRows - 1)));
+    const int64_t tail0 = len_i + 1 + len_j;   // " a.aaa b.bbb\n"
+    for (int64_t o = sub; o < total; o += kLineLanes) {
+        uint8_t ch;
+        if (o < len_i) ch = ids[off_i + o];
+        else if (o == len_i) ch = ' ';
+        else if (o < tail0) ch = ids[off_j + (o - len_i - 1)];
+        else {
+            const int k = (int)(o - tail0);
+            ch = k == 0 || k == 6 ? (uint8_t)' ' : k == 12 ? (uint8_t)'\n' : k < 6 ? (uint8_t)ta[k - 1] : (uint8_t)tb[k - 7];
+        }
+        out[at + o] = ch;
+    }
+}
+
+unsigned filter_grid(int64_t n_rows) { return (unsigned)min(n_rows, (int64_t)1 << 20); }
+
+}  // namespace
+
+namespace dctfp_host {
+
+void launch_tri_filter_count(const int32_t* tile, int64_t n_rows, int64_t n_cols, int64_t ld, int64_t row0, int64_t col0,
+                             const uint8_t* row_empty, const uint8_t* col_empty, int32_t cap, int32_t bound, int32_t* out_count,
+                             hipStream_t stream) {
+    hipLaunchKernelGGL(tri_filter_count_kernel, dim3(filter_grid(n_rows)), dim3(kFilterThreads), 0, stream, tile, n_rows, n_cols, ld, row0, col0,
+                       row_empty, col_empty, cap, bound, out_count);
+}
+
+void launch_tri_filter_fill(const int32_t* tile, int64_t n_rows, int64_t n_cols, int64_t ld, int64_t row0, int64_t col0,
+                            const uint8_t* row_empty, const uint8_t* col_empty, int32_t cap, int32_t bound, const int64_t* offsets,
+                            int64_t out_len, int32_t* out_i, int32_t* out_j, hipStream_t stream) {
+    hipLaunchKernelGGL(tri_filter_fill_kernel, dim3(filter_grid(n_rows)), dim3(kFilterThreads), 0, stream, tile, n_rows, n_cols, ld, row0, col0,
+                       row_empty, col_empty, cap, bound, offsets, out_len, out_i, out_j);
+}
+
+void launch_pair_lines(int64_t n_lines, const int32_t* pi, const int32_t* pj, const int32_t* mn, const int32_t* last, const uint8_t* ids,
+                       const int64_t* id_off, int64_t n_ids, const char* table, const int64_t* line_off, uint8_t* out, int64_t out_bytes,
+                       hipStream_t stream) {
+    const int64_t threads = n_lines * kLineLanes;
+    hipLaunchKernelGGL(pair_lines_kernel, dim3((unsigned)((threads + kLineThreads - 1) / kLineThreads)), dim3(kLineThreads), 0, stream, n_lines,
+                       pi, pj, mn, last, ids, id_off, n_ids, table, line_off, out, out_bytes);
+}
+
+}  // namespace dctfp_host

@@ -153,6 +153,17 @@ void launch_select_fill(const int32_t* dist, int64_t n_rows, int64_t n_cols, int
 // all_sim's result lines (k_search.hip): text from a (min, last) tile at offsets computed from the id lengths
 void launch_sim_lines(const int32_t* mn, const int32_t* last, int64_t ld, int64_t n_rows, int64_t row0, int64_t col0, int64_t n_cols,
                       const uint8_t* ids, const int64_t* id_off, const char* table, const int64_t* row_base, uint8_t* out, hipStream_t stream);
+// all-against-all with score cut-offs (k_filter.hip): the surviving pairs of a tile of the triangle in output order, and result
+// lines for a list of pairs
+void launch_tri_filter_count(const int32_t* tile, int64_t n_rows, int64_t n_cols, int64_t ld, int64_t row0, int64_t col0,
+                             const uint8_t* row_empty, const uint8_t* col_empty, int32_t cap, int32_t bound, int32_t* out_count,
+                             hipStream_t stream);
+void launch_tri_filter_fill(const int32_t* tile, int64_t n_rows, int64_t n_cols, int64_t ld, int64_t row0, int64_t col0,
+                            const uint8_t* row_empty, const uint8_t* col_empty, int32_t cap, int32_t bound, const int64_t* offsets,
+                            int64_t out_len, int32_t* out_i, int32_t* out_j, hipStream_t stream);
+void launch_pair_lines(int64_t n_lines, const int32_t* pi, const int32_t* pj, const int32_t* mn, const int32_t* last, const uint8_t* ids,
+                       const int64_t* id_off, int64_t n_ids, const char* table, const int64_t* line_off, uint8_t* out, int64_t out_bytes,
+                       hipStream_t stream);
 
 // DCTdomain of every protein pair from the fingerprints (k_protein.hip): scratch bytes of one side's block plan, and the launches
 // (the two plans, then the protein-minimum kernel on a grid of n_workgroups that walks the block pairs)

@@ -2,10 +2,11 @@
 fingerprints (``-dct.npz``), with the L1 distances computed on the GPU.
 
     python -m dctdomain_amd.dct_sim --dct X-dct.npz [--pair P | --db Y-dct.npz [--rank {global,domain}]] [--output F]
-                                    [--pairfound F] [--top 5] [--threshold 0.25]
+                                    [--pairfound F] [--top 5] [--threshold 0.25] [--min-domain X] [--min-global Y]
 
 Same flags, same output text (src/dct-sim.py:179-211); ``--rank domain`` (not in the reference) orders database hits by
-DCTdomain instead of DCTglobal.  DCTdomain = max over all domain pairs of
+DCTdomain instead of DCTglobal, and ``--min-domain`` / ``--min-global`` (not in the reference either, which ignores
+``--threshold`` in that mode) keep only the all-against-all lines whose scores are not below the cut-offs.  DCTdomain = max over all domain pairs of
 ``1 - min(L1/17000, 1)``, DCTglobal = the same for the two last (whole-protein) fingerprints
 (:12-50).
 
@@ -14,6 +15,10 @@ Where the reference loops over protein pairs and, inside, over domain pairs in P
   against those of the later proteins (``dctfp_l1_matrix``), reduced per protein x protein block to (minimum, last-last)
   (``dctfp_block_min``) and turned into the result text on the device (``dctfp_sim_lines``), which streams out through two
   pinned buffers.  Host memory is the two buffers plus O(n), not the n x n block matrix (``Blocks``, kept for its callers);
+- with a cut-off, ``all_sim`` never forms the other lines (``FilteredPairs``): per stripe one tile of protein-pair L1 values
+  (``dctfp_protein_min``, or the last rows' ``dctfp_l1_matrix`` when DCTglobal is cut), the pairs of the triangle within the
+  bound selected on the device in output order (``dctfp_tri_filter_count`` / ``dctfp_tri_filter_fill``), both scores for those
+  (``dctfp_pair_min``) and their lines (``dctfp_pair_lines``);
 - ``db_search`` ranks on the whole-protein fingerprints only (one L1 per protein pair), selects the printed hits of
   every query on the GPU (``dctfp_select_count`` / ``dctfp_select_fill``) and computes DCTdomain for those pairs only
   (``dctfp_pair_min``): ``ProteinSearch``.  Host memory is what is printed plus one tile, not n_query x n_db.  With
@@ -31,8 +36,8 @@ import time
 
 import numpy as np
 
-from .similarity import (LineIds, block_min, block_min_device, l1_matrix, pair_min, protein_min, sim_lines, threshold_select,
-                         to_device_int8)
+from .similarity import (PROTEIN_MIN_MAX_D, LineIds, block_min, block_min_device, l1_matrix, pair_line_offsets, pair_lines, pair_min,
+                         pair_min_device, protein_min, sim_lines, threshold_select, to_device_int8, tri_filter_count, tri_filter_fill)
 
 L1_FULL_SCALE = 17000      # src/dct-sim.py:24
 HEADER = '#prot1 prot2 sim-domain sim-global'
@@ -321,6 +326,152 @@ def pair_scores(fps, idx, pairs, max_rows: int = None):
     return mn, last
 
 
+class FilteredPairs:
+    """all_sim's pairs whose scores are not below cut-offs -- DCTdomain >= ``min_domain`` and DCTglobal >= ``min_global``, either
+    may be None -- without forming the others: ``AllPairs``' output with lines removed.  A cut-off is the integer bound
+    ``sim_bound`` gives: a pair passes when min(L1, 17000) <= bound.  Per stripe of rows [i0, i1):
+
+    1. one int32 tile, stripe x every later protein (at most TILE_INTS entries): DCTglobal's L1 (``l1_matrix`` of the last rows)
+       when ``min_global`` excludes anything -- DCTglobal's fingerprint pair is one of DCTdomain's, so DCTdomain is never below
+       it and nothing that fails here could be printed -- else DCTdomain's (``protein_min``); the later proteins' fingerprints
+       go through the device in groups of at most COL_ROWS, each group filling its columns of the tile;
+    2. the entries right of the diagonal within the bound, counted per row and compacted in (i, j) order on the device
+       (``tri_filter_count`` / ``tri_filter_fill``).  Only the row counts come to the host; rows are then taken in ranges
+       whose text cannot exceed TEXT_BYTES (a row's count times its longest possible line; a single row may exceed it);
+    3. (min, last) of the survivors (``pair_min_device``; ``pair_scores``' chunks when the file does not stay on the device), and
+       the other cut-off, if any, on those;
+    4. the lines of what is left (``pair_lines``), out through two pinned buffers.
+
+    Nothing of size n x n exists anywhere; host memory beyond the data is O(n), one range's survivors and the two buffers."""
+
+    TEXT_BYTES = 1 << 28    # text of one range of rows
+    COL_ROWS = 1 << 22      # fingerprints on the device at a time (the whole file stays there if it fits)
+    TILE_INTS = 1 << 28     # int32 entries of one stripe's tile (1 GiB)
+
+    def __init__(self, sid, idx, fps, min_domain=None, min_global=None):
+        self.sid, self.idx, self.fps = sid, np.asarray(idx, dtype=np.int64), fps
+        self.bound_domain = L1_FULL_SCALE if min_domain is None else sim_bound(min_domain)
+        self.bound_global = L1_FULL_SCALE if min_global is None else sim_bound(min_global)
+        self.route = 'global' if self.bound_global < L1_FULL_SCALE else 'domain'
+
+    def stripes(self):
+        """[i0, i1) over rows 0 .. n - 2: as many rows as keep rows x later proteins within TILE_INTS and the rows' fingerprints
+        within COL_ROWS (within an ``AllPairs`` distance tile where ``protein_min`` falls back to one) -- at least one row."""
+        n = len(self.idx) - 1
+        total = int(self.idx[-1])
+        fp_rows = self.COL_ROWS
+        if self.route == 'domain' and self.fps.shape[1] > PROTEIN_MIN_MAX_D:
+            fp_rows = max(1, self.TILE_INTS // max(1, min(self.COL_ROWS, total)))
+        i0 = 0
+        while i0 < n - 1:
+            by_tile = i0 + max(1, self.TILE_INTS // (n - 1 - i0))
+            by_rows = int(np.searchsorted(self.idx, self.idx[i0] + fp_rows, 'right')) - 1
+            i1 = min(n - 1, max(i0 + 1, min(by_tile, by_rows)))
+            yield i0, i1
+            i0 = i1
+
+    def chunks(self):
+        """Yields device int32 tensors (i, j, min L1, last L1) of the surviving pairs, range of rows by range, in output order."""
+        import torch
+        n = len(self.idx) - 1
+        if n < 2 or min(self.bound_domain, self.bound_global) < 0:
+            return
+        dev = torch.device('cuda', torch.cuda.current_device())
+        total = int(self.idx[-1])
+        resident = to_device_int8(self.fps[:total]) if 0 < total <= self.COL_ROWS else None
+        idx_dev = torch.as_tensor(self.idx, device=dev) if resident is not None else None
+        id_lens = np.fromiter((len(f'{s}'.encode('utf8')) for s in self.sid), dtype=np.int64, count=n)
+        longest = int(id_lens.max())
+        if self.route == 'global':
+            last_rows, empty = _last_rows(self.fps[:total], self.idx)
+            last_dev = to_device_int8(last_rows) if n <= self.COL_ROWS else None
+            empty_dev = torch.as_tensor(empty, device=dev)
+            bound = self.bound_global
+        else:
+            bound = self.bound_domain
+
+        def rows(p0, p1):
+            if resident is not None:
+                return resident[self.idx[p0]:self.idx[p1]]
+            return to_device_int8(self.fps[self.idx[p0]:self.idx[p1]])
+
+        def lasts(p0, p1):
+            return last_dev[p0:p1] if last_dev is not None else to_device_int8(last_rows[p0:p1])
+
+        for i0, i1 in self.stripes():
+            col0 = i0 + 1
+            tile = torch.empty((i1 - i0, n - col0), dtype=torch.int32, device=dev)
+            if self.route == 'global':
+                a = lasts(i0, i1)
+                for q0 in range(col0, n, self.COL_ROWS):
+                    q1 = min(n, q0 + self.COL_ROWS)
+                    l1_matrix(a, lasts(q0, q1), out=tile[:, q0 - col0:q1 - col0])
+                flags = (empty_dev[i0:i1], empty_dev[col0:])
+            else:
+                a, ia = rows(i0, i1), self.idx[i0:i1 + 1] - self.idx[i0]
+                for q0, q1 in _protein_groups(self.idx[col0:] - self.idx[col0], self.COL_ROWS):
+                    q0, q1 = q0 + col0, q1 + col0
+                    protein_min(a, ia, rows(q0, q1), self.idx[q0:q1 + 1] - self.idx[q0], out=tile[:, q0 - col0:q1 - col0])
+                flags = (None, None)
+            count_dev = tri_filter_count(tile, i0, col0, bound, *flags)
+            count = count_dev.cpu().numpy().astype(np.int64)
+            # ranges of rows by the text they can make: count x (len_i + 14 + the longest id)
+            room = np.concatenate([[0], np.cumsum(count * (id_lens[i0:i1] + 14 + longest))])
+            r0 = 0
+            while r0 < i1 - i0:
+                r1 = min(i1 - i0, max(r0 + 1, int(np.searchsorted(room, room[r0] + self.TEXT_BYTES, 'right')) - 1))
+                m = int(count[r0:r1].sum())
+                if m:
+                    pi, pj = tri_filter_fill(tile[r0:r1], i0 + r0, col0, bound, count_dev[r0:r1], m,
+                                             flags[0][r0:r1] if flags[0] is not None else None, flags[1])
+                    if resident is not None:
+                        mn, last = pair_min_device(resident, idx_dev, resident, idx_dev, torch.stack([pi, pj], dim=1).contiguous())
+                    else:
+                        host = torch.stack([pi, pj], dim=1).cpu().numpy()
+                        mn, last = (torch.as_tensor(v.astype(np.int32), device=dev) for v in pair_scores(self.fps, self.idx, host, self.COL_ROWS))
+                    if self.route == 'global' and self.bound_domain < L1_FULL_SCALE:      # (the other cut-off; the order stays)
+                        keep = mn.clamp(max=L1_FULL_SCALE) <= self.bound_domain
+                        pi, pj, mn, last = (t[keep].contiguous() for t in (pi, pj, mn, last))
+                    if pi.numel():
+                        yield pi, pj, mn, last
+                r0 = r1
+            del tile
+
+    def pairs(self):
+        """(i, j, min L1, last L1): int64 numpy arrays of the surviving pairs in output order (i ascending, then j)."""
+        import torch
+        parts = [torch.stack(c, dim=0).cpu().numpy().astype(np.int64) for c in self.chunks()]
+        both = np.concatenate(parts, axis=1) if parts else np.zeros((4, 0), dtype=np.int64)
+        return both[0], both[1], both[2], both[3]
+
+    def write(self, sink):
+        """Calls ``sink(memoryview)`` with the text of each range of rows that has any, in order."""
+        import torch
+        ids = table = stream = None
+        pinned, pending, k = [None, None], None, 0
+        for pi, pj, mn, last in self.chunks():
+            if ids is None:
+                ids = LineIds([f'{s}' for s in self.sid])
+                table = torch.as_tensor(score_table(), device=pi.device)
+                stream = torch.cuda.current_stream(pi.device)
+            off = pair_line_offsets(pi, pj, ids)
+            nbytes = int(off[-1])
+            text = torch.empty(nbytes, dtype=torch.uint8, device=pi.device)
+            pair_lines(pi, pj, mn, last, ids, table, off, text)
+            pin = pinned[k % 2]                                 # (written out by the host two ranges ago)
+            if pin is None or pin.numel() < nbytes:
+                pin = pinned[k % 2] = torch.empty(max(nbytes, 1 << 16), dtype=torch.uint8, pin_memory=True)
+            pin[:nbytes].copy_(text, non_blocking=True)
+            done = torch.cuda.Event()
+            done.record(stream)
+            if pending is not None:                             # the previous range goes out while the device works on this one
+                AllPairs._flush(sink, *pending)
+            pending = (pin, nbytes, done)
+            k += 1
+        if pending is not None:
+            AllPairs._flush(sink, *pending)
+
+
 class ProteinSearch:
     """A fingerprint database (the ``dct`` / ``idx`` arrays of a ``-dct.npz``) searched protein by protein the way db_search
     does (src/dct-sim.py:126-156), without the n_query x n_db block matrix:
@@ -536,22 +687,30 @@ def db_search(npzfile: str, dbfile: str, top: int, threshold: float, report: Rep
 
 
 @_reporting
-def all_sim(npzfile: str, report: Report):
-    """All-against-all, upper triangle (src/dct-sim.py:158-176), streamed from the device (``AllPairs``)."""
+def all_sim(npzfile: str, report: Report, min_domain: float = None, min_global: float = None):
+    """All-against-all, upper triangle (src/dct-sim.py:158-176), streamed from the device (``AllPairs``).  With ``min_domain`` /
+    ``min_global``: only the pairs whose DCTdomain / DCTglobal is not below them (``FilteredPairs``)."""
     sid, idx, fps = _load_npz(npzfile)
-    AllPairs(sid, idx, fps).write(report.raw)
+    if min_domain is None and min_global is None:
+        AllPairs(sid, idx, fps).write(report.raw)
+    else:
+        FilteredPairs(sid, idx, fps, min_domain=min_domain, min_global=min_global).write(report.raw)
 
 
 RANKS = ('global', 'domain')
 
 
 class _Parser(argparse.ArgumentParser):
-    """``--rank`` orders database hits: it is an error without ``--db`` or beside ``--pair`` (which takes precedence)."""
+    """``--rank`` orders database hits: it is an error without ``--db`` or beside ``--pair`` (which takes precedence).
+    ``--min-domain`` / ``--min-global`` cut the all-against-all output: an error beside ``--pair`` or ``--db``."""
 
     def parse_known_args(self, args=None, namespace=None):
         ns, rest = super().parse_known_args(args, namespace)
         if getattr(ns, 'rank', None) is not None and (ns.pair or not ns.db):
             self.error('--rank applies to database search (--db) only, not to --pair or all-against-all')
+        for opt in ('min_domain', 'min_global'):
+            if getattr(ns, opt, None) is not None and (ns.pair or ns.db):
+                self.error(f'--{opt.replace("_", "-")} applies to all-against-all only, not to --pair or --db')
         return ns, rest
 
 
@@ -568,6 +727,10 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument('--rank', choices=RANKS, default=None,
                     help='database search: order hits by the whole-protein score (global, the default) or by the best '
                          'domain pair (domain)')
+    ap.add_argument('--min-domain', type=float, default=None, metavar='X',
+                    help='all-against-all: print a pair only if its DCTdomain is not below X')
+    ap.add_argument('--min-global', type=float, default=None, metavar='Y',
+                    help='all-against-all: print a pair only if its DCTglobal is not below Y (with --min-domain: both must hold)')
     return ap
 
 
@@ -581,7 +744,7 @@ def main(argv=None):
     elif args.db:
         db_search(args.dct, args.db, args.top, args.threshold, report, rank=args.rank or 'global')
     else:
-        all_sim(args.dct, report)
+        all_sim(args.dct, report, min_domain=args.min_domain, min_global=args.min_global)
     report.close()
     t_end = time.time()
     print(f'total time used {t_end - t_start:.1f}s')

@@ -27,12 +27,17 @@ def to_device_int8(fps) -> torch.Tensor:
     return t.contiguous()
 
 
-def l1_matrix(a, b) -> torch.Tensor:
-    """int32 (na, nb) matrix of L1 distances, on the GPU."""
+def l1_matrix(a, b, out: torch.Tensor = None) -> torch.Tensor:
+    """int32 (na, nb) matrix of L1 distances, on the GPU.  ``out``: an int32 (na, nb) device tensor with unit column stride to
+    write into (any row stride: a column range of a wider tile)."""
     ta, tb = to_device_int8(a), to_device_int8(b)
     if ta.dim() != 2 or tb.dim() != 2 or ta.shape[1] != tb.shape[1]:
         raise ValueError('fingerprint sets must be 2-D with equal width')
-    out = torch.empty((ta.shape[0], tb.shape[0]), dtype=torch.int32, device=ta.device)
+    if out is None:
+        out = torch.empty((ta.shape[0], tb.shape[0]), dtype=torch.int32, device=ta.device)
+    elif (out.dtype != torch.int32 or tuple(out.shape) != (ta.shape[0], tb.shape[0]) or out.device != ta.device
+          or (out.shape[1] > 1 and out.stride(1) != 1)):
+        raise ValueError('out must be an int32 (na, nb) tensor on the fingerprints\' device with unit column stride')
     if out.numel():
         ctx = _lib.get_context(ta.device.index)
         stream = torch.cuda.current_stream(ta.device)
@@ -163,6 +168,30 @@ def pair_min(a, idx_a, b, idx_b, pairs):
     return _pair_to_host(mn, last)
 
 
+def pair_min_device(a: torch.Tensor, idx_a: torch.Tensor, b: torch.Tensor, idx_b: torch.Tensor, pairs: torch.Tensor):
+    """``pair_min`` with everything on the device already: int8 fingerprint matrices, int64 prefix arrays (the caller's guarantee:
+    non-decreasing, within their matrices), ``pairs`` int32 (n, 2) contiguous.  Returns device int32 (min, last); a pair index out
+    of range gives -1 in both (the kernel's check)."""
+    if pairs.dtype != torch.int32 or pairs.dim() != 2 or pairs.shape[1] != 2 or not pairs.is_contiguous():
+        raise ValueError('pairs must be a contiguous int32 (n, 2) device tensor')
+    if a.dtype != torch.int8 or b.dtype != torch.int8 or a.dim() != 2 or b.dim() != 2 or a.shape[1] != b.shape[1]:
+        raise ValueError('fingerprint sets must be 2-D int8 with equal width')
+    if idx_a.dtype != torch.int64 or idx_b.dtype != torch.int64 or not (idx_a.is_contiguous() and idx_b.is_contiguous()):
+        raise ValueError('prefix arrays must be contiguous int64 device tensors')
+    n, dev = pairs.shape[0], pairs.device
+    mn = torch.full((n,), 0x7fffffff, dtype=torch.int32, device=dev)
+    last = torch.full((n,), 0x7fffffff, dtype=torch.int32, device=dev)
+    if n == 0 or a.shape[0] == 0 or b.shape[0] == 0:            # (no fingerprint on a side: every pair is empty)
+        return mn, last
+    ctx = _lib.get_context(dev.index)
+    stream = torch.cuda.current_stream(dev)
+    _lib.check(ctx._lib.dctfp_pair_min(ctx.handle, pairs.data_ptr(), n, a.data_ptr(), a.stride(0) if a.shape[0] > 1 else a.shape[1],
+                                       idx_a.data_ptr(), idx_a.numel() - 1, b.data_ptr(), b.stride(0) if b.shape[0] > 1 else b.shape[1],
+                                       idx_b.data_ptr(), idx_b.numel() - 1, a.shape[1], mn.data_ptr(), last.data_ptr(),
+                                       C.c_void_p(stream.cuda_stream)))
+    return mn, last
+
+
 def protein_min(a, idx_a, b, idx_b, out: torch.Tensor = None) -> torch.Tensor:
     """int32 (npa, npb) on the device: the smallest L1 over all fingerprint pairs of every (protein of ``a``, protein of ``b``)
     -- DCTdomain's distance, ``block_min(l1_matrix(a, b), idx_a, idx_b)[0]`` without the distance matrix
@@ -253,6 +282,71 @@ def threshold_select(dist: torch.Tensor, top: int, bound: int, row_empty=None, c
     return offsets, k, c
 
 
+def _empty_flags(flags, n: int, dev):
+    """A row / column flag array (or None) as a contiguous device uint8 tensor of ``n`` entries."""
+    if flags is None:
+        return None
+    f = torch.as_tensor(np.asarray(flags, dtype=np.uint8) if not isinstance(flags, torch.Tensor) else flags, device=dev).to(torch.uint8).contiguous()
+    if f.numel() != n:
+        raise ValueError('empty flags must have one entry per row / column')
+    return f
+
+
+def _tri_filter_args(tile: torch.Tensor, row0: int, col0: int, bound: int, row_empty, col_empty, cap: int):
+    if tile.dtype != torch.int32 or tile.dim() != 2 or tile.device.type != 'cuda' or (tile.shape[1] > 1 and tile.stride(1) != 1):
+        raise ValueError('tile must be a 2-D int32 device tensor with unit column stride')
+    if row0 < 0 or col0 < 0:
+        raise ValueError('row0 / col0 must not be negative')
+    n_rows, n_cols = tile.shape
+    ld = tile.stride(0) if n_rows > 1 else max(n_cols, 1)
+    re, ce = _empty_flags(row_empty, n_rows, tile.device), _empty_flags(col_empty, n_cols, tile.device)
+    return n_rows, n_cols, ld, re, ce, int(max(-1, min(int(bound), cap)))
+
+
+def tri_filter_count(tile: torch.Tensor, row0: int, col0: int, bound: int, row_empty=None, col_empty=None, cap: int = 17000) -> torch.Tensor:
+    """Device int32 (n_rows): per row of an L1 tile (entry (r, c) = proteins row0 + r, col0 + c) the entries with
+    col0 + c > row0 + r and min(L1, cap) <= bound -- ``cap`` for a row / column flagged empty (``dctfp_tri_filter_count``)."""
+    n_rows, n_cols, ld, re, ce, bound = _tri_filter_args(tile, row0, col0, bound, row_empty, col_empty, cap)
+    count = torch.zeros(n_rows, dtype=torch.int32, device=tile.device)
+    if n_rows and n_cols:
+        ctx = _lib.get_context(tile.device.index)
+        stream = C.c_void_p(torch.cuda.current_stream(tile.device).cuda_stream)
+        _lib.check(ctx._lib.dctfp_tri_filter_count(ctx.handle, tile.data_ptr(), n_rows, n_cols, ld, int(row0), int(col0),
+                                                   re.data_ptr() if re is not None else None, ce.data_ptr() if ce is not None else None,
+                                                   cap, bound, count.data_ptr(), stream))
+    return count
+
+
+def tri_filter_fill(tile: torch.Tensor, row0: int, col0: int, bound: int, count: torch.Tensor, total: int, row_empty=None, col_empty=None,
+                    cap: int = 17000):
+    """(i, j): device int32 (total) -- the entries ``tri_filter_count`` counted (``count`` = its result for this tile, ``total``
+    its sum) as global protein indices, i ascending, then j ascending (``dctfp_tri_filter_fill``; the prefix sum of the counts
+    is taken here, on the device)."""
+    n_rows, n_cols, ld, re, ce, bound = _tri_filter_args(tile, row0, col0, bound, row_empty, col_empty, cap)
+    if count.dtype != torch.int32 or count.numel() != n_rows or count.device != tile.device:
+        raise ValueError('count must be the int32 device result of tri_filter_count for this tile')
+    total = int(total)
+    out_i = torch.empty(total, dtype=torch.int32, device=tile.device)
+    out_j = torch.empty(total, dtype=torch.int32, device=tile.device)
+    if total and n_rows and n_cols:
+        offsets = torch.zeros(n_rows + 1, dtype=torch.int64, device=tile.device)
+        torch.cumsum(count, 0, out=offsets[1:])
+        ctx = _lib.get_context(tile.device.index)
+        stream = C.c_void_p(torch.cuda.current_stream(tile.device).cuda_stream)
+        _lib.check(ctx._lib.dctfp_tri_filter_fill(ctx.handle, tile.data_ptr(), n_rows, n_cols, ld, int(row0), int(col0),
+                                                  re.data_ptr() if re is not None else None, ce.data_ptr() if ce is not None else None,
+                                                  cap, bound, offsets.data_ptr(), total, out_i.data_ptr(), out_j.data_ptr(), stream))
+    return out_i, out_j
+
+
+def tri_filter(tile: torch.Tensor, row0: int, col0: int, bound: int, row_empty=None, col_empty=None, cap: int = 17000):
+    """(count, i, j) as int64 numpy arrays: ``tri_filter_count`` and ``tri_filter_fill`` on one tile."""
+    count = tri_filter_count(tile, row0, col0, bound, row_empty, col_empty, cap)
+    m = count.cpu().numpy().astype(np.int64)
+    i, j = tri_filter_fill(tile, row0, col0, bound, count, int(m.sum()), row_empty, col_empty, cap)
+    return m, i.cpu().numpy().astype(np.int64), j.cpu().numpy().astype(np.int64)
+
+
 class LineIds:
     """The protein ids of a file as ``dctfp_sim_lines`` reads them: ``off`` = int64 prefix offsets of their UTF-8 bytes (host),
     ``bytes_dev`` / ``off_dev`` = the concatenated bytes and the offsets on the device."""
@@ -266,6 +360,7 @@ class LineIds:
         raw = np.frombuffer(bytearray(b''.join(enc)), dtype=np.uint8)
         self.bytes_dev = torch.as_tensor(raw if len(raw) else np.zeros(1, dtype=np.uint8), device=device)
         self.off_dev = _device_int64(self.off, device)
+        self.lens_dev = _device_int64(self.lens, device)
 
 
 def sim_lines(mn: torch.Tensor, last: torch.Tensor, row0: int, col0: int, ids: LineIds, table: torch.Tensor, row_base, out: torch.Tensor):
@@ -298,6 +393,38 @@ def sim_lines(mn: torch.Tensor, last: torch.Tensor, row0: int, col0: int, ids: L
     _lib.check(ctx._lib.dctfp_sim_lines(ctx.handle, mn.data_ptr(), last.data_ptr(), n_cols, n_rows, int(row0), int(col0), n_cols,
                                         ids.bytes_dev.data_ptr(), ids.off_dev.data_ptr(), table.data_ptr(), base.data_ptr(), out.data_ptr(),
                                         stream))
+
+
+def pair_line_offsets(pi: torch.Tensor, pj: torch.Tensor, ids: LineIds) -> torch.Tensor:
+    """Device int64 (n + 1): where the lines of the pairs (pi[n], pj[n]) start -- the prefix sum of len_i + len_j + 14; the last
+    entry is the text's size."""
+    off = torch.zeros(pi.numel() + 1, dtype=torch.int64, device=pi.device)
+    if pi.numel():
+        torch.cumsum(ids.lens_dev[pi.long()] + ids.lens_dev[pj.long()] + 14, 0, out=off[1:])
+    return off
+
+
+def pair_lines(pi: torch.Tensor, pj: torch.Tensor, mn: torch.Tensor, last: torch.Tensor, ids: LineIds, table: torch.Tensor,
+               line_off: torch.Tensor, out: torch.Tensor):
+    """all_sim's text for a list of pairs: line n = ``"{id of pi[n]} {id of pj[n]} {a} {b}\\n"`` from byte ``line_off[n]`` of the
+    device uint8 buffer ``out`` (``dctfp_pair_lines``), a / b from ``table`` (``dct_sim.score_table`` on the device) by ``mn`` /
+    ``last``.  All device tensors: int32 pairs and values, int64 offsets (``pair_line_offsets``).  The kernel skips a line that
+    names a protein outside ``ids`` or that ends beyond ``out``."""
+    n = pi.numel()
+    for t in (pi, pj, mn, last):
+        if t.dtype != torch.int32 or t.numel() != n or not t.is_contiguous() or t.device != out.device:
+            raise ValueError('pi / pj / mn / last must be contiguous int32 device tensors of one length')
+    if line_off.dtype != torch.int64 or line_off.numel() < n or not line_off.is_contiguous() or line_off.device != out.device:
+        raise ValueError('line_off must be a contiguous int64 device tensor with an entry per line')
+    if table.dtype != torch.uint8 or table.numel() != 2 * 17002 * 5 or out.dtype != torch.uint8 or not out.is_contiguous():
+        raise ValueError('table must be uint8 (2, 17002, 5) and out a contiguous uint8 buffer')
+    if n == 0:
+        return
+    ctx = _lib.get_context(out.device.index)
+    stream = C.c_void_p(torch.cuda.current_stream(out.device).cuda_stream)
+    _lib.check(ctx._lib.dctfp_pair_lines(ctx.handle, n, pi.data_ptr(), pj.data_ptr(), mn.data_ptr(), last.data_ptr(), ids.bytes_dev.data_ptr(),
+                                         ids.off_dev.data_ptr(), len(ids.off) - 1, table.data_ptr(), line_off.data_ptr(), out.data_ptr(),
+                                         out.numel(), stream))
 
 
 KNN_MAX_K = 1024     # dctfp_l1_knn's limits: larger k or wider rows take l1_matrix + row_select

@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define DCTFP_VERSION 102 /* 0.1.2: dctfp_protein_min */
+#define DCTFP_VERSION 103 /* 0.1.3: dctfp_tri_filter_count / _fill, dctfp_pair_lines */
 
 #define DCTFP_OK 0
 #define DCTFP_ERR_INVALID (-1) /* bad argument (null pointer, piece outside its sequence, ...) */
@@ -354,6 +354,39 @@ int dctfp_select_fill(dctfp_ctx* ctx, const int32_t* dist, int64_t n_rows, int64
 int dctfp_sim_lines(dctfp_ctx* ctx, const int32_t* mn, const int32_t* last, int64_t ld, int64_t n_rows, int64_t row0, int64_t col0,
                     int64_t n_cols, const uint8_t* ids, const int64_t* id_off, const char* table, const int64_t* row_base, uint8_t* out,
                     void* stream);
+
+/* all_sim with score cut-offs (dct-sim --min-domain / --min-global; the reference parses --threshold but ignores it in this
+ * mode, src/dct-sim.py:158-176): the pairs of the upper triangle that pass a cut-off, selected on the device in output order.
+ * `tile` = device int32 (n_rows, n_cols), row stride ld, 4-byte aligned, any row alignment: entry (r, c) is an L1 of proteins
+ * i = row0 + r and j = col0 + c -- dctfp_protein_min's tile (DCTdomain) or the dctfp_l1_matrix of the proteins' last rows
+ * (DCTglobal).  An entry survives when j > i and key <= bound, key = min(L1, cap) as in dctfp_select_count (cap = 17000;
+ * row_empty[r] / col_empty[c], device uint8, either may be NULL, != 0: a protein without fingerprints, key cap against
+ * everything; a negative value counts as cap).  bound = -1: nothing survives; bound = cap: every j > i does.  Extends
+ * dctfp_select_count / dctfp_select_fill (a top-m per row by key order) to "all below a bound, in (i, j) order".
+ * dctfp_tri_filter_count: out_count[r] (device int32, n_rows) = the survivors of row r; n_cols may be 0.
+ * dctfp_tri_filter_fill: offsets (device int64, n_rows + 1) = the exclusive prefix sum of out_count, computed by the caller;
+ * row r's survivors go to out_i / out_j [offsets[r], offsets[r + 1]) (device int32) as the global indices i and j, j ascending.
+ * Positions come from that prefix sum and the column order alone, never from the order in which workgroups run.  out_len = the
+ * entries of out_i / out_j: nothing is written at or beyond it, nor outside a row's range.
+ * DCTFP_ERR_INVALID for a bound outside [-1, cap], ld < n_cols or a tile not on a 4-byte boundary; DCTFP_ERR_LIMIT when
+ * row0 + n_rows or col0 + n_cols exceeds 2^31 - 1. */
+int dctfp_tri_filter_count(dctfp_ctx* ctx, const int32_t* tile, int64_t n_rows, int64_t n_cols, int64_t ld, int64_t row0, int64_t col0,
+                           const uint8_t* row_empty, const uint8_t* col_empty, int32_t cap, int32_t bound, int32_t* out_count,
+                           void* stream);
+int dctfp_tri_filter_fill(dctfp_ctx* ctx, const int32_t* tile, int64_t n_rows, int64_t n_cols, int64_t ld, int64_t row0, int64_t col0,
+                          const uint8_t* row_empty, const uint8_t* col_empty, int32_t cap, int32_t bound, const int64_t* offsets,
+                          int64_t out_len, int32_t* out_i, int32_t* out_j, void* stream);
+
+/* all_sim's result lines for a LIST of pairs -- dctfp_sim_lines' text without its dense rows (there a line's place is a closed
+ * form of the row; here the caller gives it): line n = "{id_i} {id_j} {a} {b}\n" with i = pi[n], j = pj[n] (device int32),
+ * written from byte line_off[n] of out (device int64: the caller's prefix sum of len_i + len_j + 14, as dctfp_query_lines takes
+ * it).  ids / id_off (n_ids + 1 offsets) and the score table as in dctfp_sim_lines: a / b = the five bytes of rows
+ * min(mn[n], 17001) / min(last[n], 17001) (dctfp_pair_min's two outputs; 0x7fffffff -> row 17001).  Any id length, any
+ * alignment of out.  A line whose pair lies outside [0, n_ids) or whose end lies beyond out_bytes is skipped, nothing else is
+ * written.  DCTFP_ERR_LIMIT above 2^31 lines per call. */
+int dctfp_pair_lines(dctfp_ctx* ctx, int64_t n_lines, const int32_t* pi, const int32_t* pj, const int32_t* mn, const int32_t* last,
+                     const uint8_t* ids, const int64_t* id_off, int64_t n_ids, const char* table, const int64_t* line_off, uint8_t* out,
+                     int64_t out_bytes, void* stream);
 
 /* query_db's search (src/query_db.py:75-87: a flat FAISS index forced to METRIC_L1 at :76, index.search at :87) without a
  * distance matrix: for query rows q (nq x d, row stride ldq) and database rows b (nb x d, stride ldb), int8 on the device, each

@@ -2,7 +2,13 @@
 
     python tools/all_sim_bench.py --part compare [--n 2000]            # old (Blocks) and new path: sha256 of the text, times
     python tools/all_sim_bench.py --part scale --n 20000 [--dir D]     # new path to /dev/null and to a file under D
+    python tools/all_sim_bench.py --part scale --n 1000000 --min-global 0.5   # the same with cut-offs (dct_sim.FilteredPairs)
+    python tools/all_sim_bench.py --part filter --n 50000 [--min-domain 0.5]  # cut-offs beside the unfiltered run, one process
 
+`filter` loads one synthetic file and runs, after the load and a warm-up on a small file, the unfiltered path (AllPairs, to
+/dev/null as `scale` does) and the path with cut-offs; events around the device steps of the second (the tile: protein_min or
+l1_matrix; the filter; pair_min; the lines) say where its device time goes.  --planted fingerprints are overwritten with near
+copies of others first: random proteins alone leave nothing above a cut-off.
 `scale` writes a synthetic -dct.npz (about 4.5 fingerprints per protein, 17-character ids) and runs the new path in a child
 process per sink (and one that only initialises the GPU: the RSS floor), so that the child's peak RSS (ru_maxrss of RUSAGE_CHILDREN, as tools/run_with_rss.py) is that of the run
 alone.  The child also measures the pinned device-to-host copy rate of one TEXT_BYTES buffer.  The file run is skipped when
@@ -75,12 +81,15 @@ def part_run(args):
     from dctdomain_amd import dct_sim
     sid, idx, fps = dct_sim._load_npz(args.npz)
     n = len(sid)
-    ap = dct_sim.AllPairs(sid, idx, fps)
-    written = [0]
+    cut = args.min_domain is not None or args.min_global is not None
+    ap = dct_sim.FilteredPairs(sid, idx, fps, args.min_domain, args.min_global) if cut else dct_sim.AllPairs(sid, idx, fps)
+    written, kept = [0], [0]
     with open(args.sink, 'wb', buffering=0) as fh:
         def sink(mv):
             fh.write(mv)
             written[0] += len(mv)
+            if cut:
+                kept[0] += bytes(mv).count(b'\n')
         t0 = time.perf_counter()
         ap.write(sink)
         torch.cuda.synchronize()
@@ -101,9 +110,82 @@ def part_run(args):
     d2h = reps * size / (time.perf_counter() - t0)
     del src, pin
     lines = n * (n - 1) // 2
+    if cut:
+        return {'n': n, 'fingerprints': int(idx[-1]), 'pairs': lines, 'min_domain': args.min_domain, 'min_global': args.min_global,
+                'route': ap.route, 'lines': kept[0], 'text_bytes': written[0], 'seconds': round(dt, 3), 'pairs_per_s': round(lines / dt)}
     return {'n': n, 'fingerprints': int(idx[-1]), 'lines': lines, 'text_bytes': written[0], 'seconds': round(dt, 3),
             'lines_per_s': round(lines / dt), 'text_GBps': round(written[0] / dt / 1e9, 2), 'd2h_pinned_GBps': round(d2h / 1e9, 2),
             'text_over_d2h': round(written[0] / dt / d2h, 3)}
+
+
+def part_filter(args):
+    """One process: the unfiltered run (AllPairs, /dev/null) and the run with cut-offs on the same loaded file, after a warm-up
+    of both on a small one; device time of the second by step."""
+    import torch
+    from dctdomain_amd import dct_sim
+    min_domain = args.min_domain if args.min_domain is not None or args.min_global is not None else 0.5
+    with tempfile.TemporaryDirectory(dir=args.dir) as tmp:
+        small, path = os.path.join(tmp, 'w-dct.npz'), os.path.join(tmp, 'f-dct.npz')
+        synth(small, 2000, 5)
+        synth(path, args.n, 7)
+        warm = dct_sim._load_npz(small)
+        sid, idx, fps = dct_sim._load_npz(path)
+    # (random proteins lie far above any cut-off: some near copies of single fingerprints, so that pair_min and the lines run)
+    rng = np.random.default_rng(11)
+    for rows_of, k in ((warm[2], min(args.planted, 100)), (fps, args.planted)):     # (the warm-up takes every step too)
+        rows = rng.choice(len(rows_of), size=2 * k, replace=False)
+        rows_of[rows[:k]] = np.clip(rows_of[rows[k:]].astype(np.int64) + rng.integers(-2, 3, size=(k, rows_of.shape[1])), -127, 127)
+    spans = {}
+
+    def timed(name, label):
+        fn = getattr(dct_sim, name)
+
+        def run(*a, **k):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            out = fn(*a, **k)
+            e1.record()
+            spans.setdefault(label, []).append((e0, e1))
+            return out
+        setattr(dct_sim, name, run)
+        return fn
+    written, kept = [0], [0]
+    with open(os.devnull, 'wb', buffering=0) as fh:
+        def sink(mv):
+            fh.write(mv)
+            written[0] += len(mv)
+
+        def sink_counting(mv):
+            sink(mv)
+            kept[0] += bytes(mv).count(b'\n')
+        dct_sim.AllPairs(*warm).write(sink)
+        dct_sim.FilteredPairs(*warm, min_domain, args.min_global).write(sink)
+        torch.cuda.synchronize()
+        written[0] = 0
+        t0 = time.perf_counter()
+        dct_sim.AllPairs(sid, idx, fps).write(sink)
+        torch.cuda.synchronize()
+        t_all, text_all = time.perf_counter() - t0, written[0]
+        steps = (('protein_min', 'tile'), ('l1_matrix', 'tile'), ('tri_filter_count', 'filter'), ('tri_filter_fill', 'filter'),
+                 ('pair_min_device', 'pair_min'), ('pair_line_offsets', 'lines'), ('pair_lines', 'lines'))
+        real = [(name, timed(name, label)) for name, label in steps]
+        written[0] = 0
+        fp = dct_sim.FilteredPairs(sid, idx, fps, min_domain, args.min_global)
+        t0 = time.perf_counter()
+        fp.write(sink_counting)
+        torch.cuda.synchronize()
+        t_cut = time.perf_counter() - t0
+        for name, fn in real:
+            setattr(dct_sim, name, fn)
+    ms = {label: round(sum(a.elapsed_time(b) for a, b in ev), 3) for label, ev in spans.items()}
+    device = sum(ms.values())
+    n = len(sid)
+    return {'part': 'filter', 'n': n, 'fingerprints': int(idx[-1]), 'pairs': n * (n - 1) // 2, 'planted_rows': args.planted, 'min_domain': min_domain,
+            'min_global': args.min_global, 'route': fp.route, 'stripes': len(list(fp.stripes())),
+            'unfiltered_s': round(t_all, 3), 'unfiltered_text_bytes': text_all, 'filtered_s': round(t_cut, 3), 'filtered_lines': kept[0],
+            'filtered_text_bytes': written[0], 'speedup': round(t_all / t_cut, 2), 'filtered_faster': t_cut < t_all, 'device_ms': ms,
+            'share_outside_tile_of_run': round(1 - ms.get('tile', 0.0) / (1e3 * t_cut), 4),
+            'share_outside_tile_of_device_steps': round(1 - ms.get('tile', 0.0) / device, 4) if device else None}
 
 
 def part_base(args):
@@ -135,11 +217,15 @@ def part_scale(args):
         res['two_buffers_MB'] = round(2 * dct_sim.AllPairs.TEXT_BYTES / 2 ** 20)
         text = int(dct_sim.row_text_bytes(np.full(args.n, 17)).sum())
         p, res['base_rss_MB'] = _child_rss([sys.executable, os.path.abspath(__file__), '--part', 'base'], args.timeout)
+        cut = []
+        for opt, v in (('--min-domain', args.min_domain), ('--min-global', args.min_global)):
+            if v is not None:
+                cut += [opt, str(v)]
         for name, sink in (('devnull', os.devnull), ('file', os.path.join(tmp, 'all.txt'))):
-            if name == 'file' and shutil.disk_usage(tmp).free < text + (1 << 30):
+            if name == 'file' and not cut and shutil.disk_usage(tmp).free < text + (1 << 30):
                 res[name] = {'skipped': f'{shutil.disk_usage(tmp).free / 1e9:.0f} GB free, {text / 1e9:.0f} GB of text'}
                 continue
-            cmd = [sys.executable, os.path.abspath(__file__), '--part', 'run', '--npz', path, '--sink', sink]
+            cmd = [sys.executable, os.path.abspath(__file__), '--part', 'run', '--npz', path, '--sink', sink] + cut
             p, peak = _child_rss(cmd, args.timeout)
             if p.returncode != 0:
                 res[name] = {'rc': p.returncode, 'stderr': p.stderr[-2000:]}
@@ -154,15 +240,18 @@ def part_scale(args):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument('--part', required=True, choices=['compare', 'scale', 'run', 'base'])
+    ap.add_argument('--part', required=True, choices=['compare', 'scale', 'filter', 'run', 'base'])
     ap.add_argument('--n', type=int, default=2000)
     ap.add_argument('--dir', default=None, help='where the npz and the text file go (local disk)')
     ap.add_argument('--npz')
     ap.add_argument('--sink')
     ap.add_argument('--timeout', type=float, default=1200)
+    ap.add_argument('--planted', type=int, default=1000, help='filter: fingerprints overwritten with near copies of others')
+    ap.add_argument('--min-domain', type=float, default=None, help='scale / filter: print the pairs whose DCTdomain is not below this')
+    ap.add_argument('--min-global', type=float, default=None, help='scale / filter: print the pairs whose DCTglobal is not below this')
     ap.add_argument('--out')
     args = ap.parse_args()
-    res = {'compare': part_compare, 'scale': part_scale, 'run': part_run, 'base': part_base}[args.part](args)
+    res = {'compare': part_compare, 'scale': part_scale, 'filter': part_filter, 'run': part_run, 'base': part_base}[args.part](args)
     line = json.dumps(res)
     print(line)
     if args.out:
