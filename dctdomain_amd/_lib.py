@@ -59,7 +59,8 @@ EXPORTS = ('dctfp_version', 'dctfp_last_error', 'dctfp_create', 'dctfp_destroy',
            'dctfp_stitch_sequences', 'dctfp_quantize_windows', 'dctfp_reccut', 'dctfp_reccut_room', 'dctfp_quantize_one', 'dctfp_reccut_pieces',
            'dctfp_pair_min', 'dctfp_select_count', 'dctfp_select_fill', 'dctfp_sim_lines',
            'dctfp_l1_knn', 'dctfp_query_rank', 'dctfp_query_lines', 'dctfp_protein_min',
-           'dctfp_tri_filter_count', 'dctfp_tri_filter_fill', 'dctfp_pair_lines')
+           'dctfp_tri_filter_count', 'dctfp_tri_filter_fill', 'dctfp_pair_lines',
+           'dctfp_tri_link', 'dctfp_link_pairs', 'dctfp_cluster_labels')
 
 
 def load(path: str = None):
@@ -184,6 +185,10 @@ def _configure(lib):
                                               C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
         lib.dctfp_pair_lines.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                          C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
+        lib.dctfp_tri_link.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_void_p,
+                                       C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]
+        lib.dctfp_link_pairs.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]
+        lib.dctfp_cluster_labels.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
         lib.dctfp_l1_knn.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int32,
                                      C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
         lib.dctfp_query_rank.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,

@@ -2762,6 +2762,50 @@ int dctfp_pair_lines(dctfp_ctx* ctx, int64_t n_lines, const int32_t* pi, const i
     return DCTFP_OK;
 } DCTFP_GUARD("dctfp_pair_lines")
 
+int dctfp_tri_link(dctfp_ctx* ctx, const int32_t* tile, int64_t n_rows, int64_t n_cols, int64_t ld, int64_t row0, int64_t col0,
+                   const uint8_t* row_empty, const uint8_t* col_empty, int32_t cap, int32_t bound, int32_t* parent, int64_t n_nodes,
+                   void* stream_v) try {
+    if (!ctx || !tile || !parent) return fail(DCTFP_ERR_INVALID, "dctfp_tri_link: NULL argument");
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    if (n_rows < 0 || n_cols < 0 || ld < n_cols || row0 < 0 || col0 < 0 || cap < 0 || bound < -1 || bound > cap || n_nodes < 0 ||
+        (reinterpret_cast<uintptr_t>(tile) & 3u) != 0)
+        return fail(DCTFP_ERR_INVALID, "dctfp_tri_link: bad shape, bound or alignment");
+    if (n_nodes > 0x7fffffff) return fail(DCTFP_ERR_LIMIT, "dctfp_tri_link: more than 2^31 - 1 nodes");
+    // (every (i, j) the kernel can form lies inside the tile: bounded here, not on the device)
+    if (row0 + n_rows > n_nodes || col0 + n_cols > n_nodes) return fail(DCTFP_ERR_INVALID, "dctfp_tri_link: the tile names proteins outside parent");
+    if (n_rows == 0 || n_cols == 0 || n_nodes == 0) return DCTFP_OK;
+    HIP_TRY(hipSetDevice(ctx->device));
+    launch_tri_link(tile, n_rows, n_cols, ld, row0, col0, row_empty, col_empty, cap, bound, parent, (hipStream_t)stream_v);
+    HIP_TRY(hipGetLastError());
+    return DCTFP_OK;
+} DCTFP_GUARD("dctfp_tri_link")
+
+int dctfp_link_pairs(dctfp_ctx* ctx, const int32_t* pi, const int32_t* pj, int64_t n_pairs, int32_t* parent, int64_t n_nodes,
+                     void* stream_v) try {
+    if (!ctx || !parent || ((!pi || !pj) && n_pairs > 0)) return fail(DCTFP_ERR_INVALID, "dctfp_link_pairs: NULL argument");
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    if (n_pairs < 0 || n_nodes < 0) return fail(DCTFP_ERR_INVALID, "dctfp_link_pairs: bad shape");
+    // (one thread per pair in 256-thread workgroups: 2^23 workgroups at most, as dctfp_pair_lines' limit)
+    if (n_nodes > 0x7fffffff || n_pairs > (int64_t)1 << 31) return fail(DCTFP_ERR_LIMIT, "dctfp_link_pairs: more than 2^31 - 1 nodes or 2^31 pairs per call");
+    if (n_pairs == 0 || n_nodes == 0) return DCTFP_OK;
+    HIP_TRY(hipSetDevice(ctx->device));
+    launch_link_pairs(pi, pj, n_pairs, parent, n_nodes, (hipStream_t)stream_v);
+    HIP_TRY(hipGetLastError());
+    return DCTFP_OK;
+} DCTFP_GUARD("dctfp_link_pairs")
+
+int dctfp_cluster_labels(dctfp_ctx* ctx, int32_t* parent, int64_t n_nodes, int32_t* labels, void* stream_v) try {
+    if (!ctx || !parent || !labels) return fail(DCTFP_ERR_INVALID, "dctfp_cluster_labels: NULL argument");
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    if (n_nodes < 0) return fail(DCTFP_ERR_INVALID, "dctfp_cluster_labels: bad shape");
+    if (n_nodes > 0x7fffffff) return fail(DCTFP_ERR_LIMIT, "dctfp_cluster_labels: more than 2^31 - 1 nodes");
+    if (n_nodes == 0) return DCTFP_OK;
+    HIP_TRY(hipSetDevice(ctx->device));
+    launch_cluster_labels(parent, n_nodes, labels, (hipStream_t)stream_v);
+    HIP_TRY(hipGetLastError());
+    return DCTFP_OK;
+} DCTFP_GUARD("dctfp_cluster_labels")
+
 int dctfp_l1_knn(dctfp_ctx* ctx, const int8_t* q, int64_t nq, int64_t ldq, const int8_t* b, int64_t nb, int64_t ldb, int32_t d, int32_t k,
                  int64_t col0, int32_t* out_val, int32_t* out_idx, void* stream_v) try {
     if (!ctx || !q || !b || !out_val || !out_idx) return fail(DCTFP_ERR_INVALID, "dctfp_l1_knn: NULL argument");

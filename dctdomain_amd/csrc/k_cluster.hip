@@ -1,0 +1,148 @@
+// dct-sim --cluster: single-linkage clusters at a cut-off = the connected components of the pairs that pass it, joined on the
+// device in a lock-free union-find over parent[0 .. n_nodes):
+//   tri_link_kernel     -- tri_filter_count_kernel's walk over an int32 tile of L1 values; every surviving entry (i, j) is a union;
+//   link_pairs_kernel   -- the same union for a list of pairs;
+//   flatten_kernel / labels_kernel -- after all linking, in launches of their own: every node under its root, labels[x] = root.
+//
+// The forest.  parent[x] <= x at all times; x is a root when parent[x] == x.  A union finds both roots and, if they differ, hooks
+// the LARGER under the smaller with a compare-and-swap that expects the larger still to be a root; on failure it goes on from
+// the value the CAS returned.  A find replaces parent[x] by an ancestor with an atomic min (path halving), which keeps both the
+// invariant and the components.  Roots only ever get smaller parents, so the root of a finished component is its smallest
+// member whatever the order in which waves ran: the labels are a property of the graph.
+//
+// Visibility (eight XCDs with private L2s, a vector L1 per CU that no other CU's store refreshes).  Inside a launch that links,
+// EVERY access to parent is an agent-scope relaxed atomic -- load, CAS or min; no plain load or store, nothing through the
+// scalar path.  No ordering is needed beyond that: a stale or late view of parent can only show a node as a root that no longer
+// is one (parents change only from "self" to a smaller node, or from an ancestor to a further ancestor).  The CAS on such a
+// node then fails -- it is decided at the one copy the atomics of all XCDs reach -- and the find continues from what it returned.
+// So correctness never rests on when a write becomes visible, only on the atomicity of the hook.  No wave waits for another
+// workgroup's progress: a failed CAS means another wave succeeded, and there are no flags, tickets or spin loops.
+#define DCTFP_TEMPLATES_ONLY
+#include "launch.h"
+#include "tri_walk.hip.h"
+
+namespace {
+
+constexpr int kLinkThreads = 256;
+
+__device__ inline int32_t uf_load(int32_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+
+// parent[x] as the forest allows it: 0 <= parent[x] <= x.  Anything else (a caller's array that is no forest) reads as "root",
+// so that a walk only ever moves to smaller, non-negative indices: never an access outside parent[0 .. x].
+__device__ inline int32_t uf_parent(int32_t* parent, int32_t x) {
+    const int32_t p = uf_load(parent + x);
+    return (uint32_t)p <= (uint32_t)x ? p : x;
+}
+
+// The root above x (as this wave sees it), halving the path on the way: parent[x] = min(parent[x], grandparent).
+__device__ inline int32_t uf_find(int32_t* parent, int32_t x) {
+    int32_t p = uf_parent(parent, x);
+    while (p != x) {
+        const int32_t g = uf_parent(parent, p);
+        if (g != p) __hip_atomic_fetch_min(parent + x, g, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        x = p;
+        p = g;
+    }
+    return x;
+}
+
+// Joins the components of a and b.  Two endpoints already under one root cost reads only (and the halving of a long path).
+__device__ inline void uf_union(int32_t* parent, int32_t a, int32_t b) {
+    for (;;) {
+        a = uf_find(parent, a);
+        b = uf_find(parent, b);
+        if (a == b) return;
+        const int32_t hi = max(a, b), lo = min(a, b);
+        int32_t seen = hi;
+        if (__hip_atomic_compare_exchange_strong(parent + hi, &seen, lo, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) return;
+        if ((uint32_t)seen >= (uint32_t)hi) return;   // (no forest: see uf_parent)
+        a = seen;                                     // hi got a parent meanwhile: go on from there
+        b = lo;
+    }
+}
+
+// tri_filter_count_kernel's walk (one workgroup per row at a time, 16-byte loads, filter_quad).  Row r is protein i = row0 + r:
+// a step without survivors -- the common case -- costs what the count's step costs, the ballots show it and the wave moves on;
+// in a step with some, one lane finds i's root (once per step, carried to the next as the place to start from) and only the
+// lanes with a surviving entry find j and hook.  The host has checked row0 + n_rows <= n_nodes and col0 + n_cols <= n_nodes.
+__global__ __launch_bounds__(kFilterThreads) void tri_link_kernel(const int32_t* __restrict__ tile, int64_t n_rows, int64_t n_cols, int64_t ld,
+                                                                   int64_t row0, int64_t col0, const uint8_t* __restrict__ row_empty,
+                                                                   const uint8_t* __restrict__ col_empty, int32_t cap, int32_t bound,
+                                                                   int32_t* parent) {
+    const int tid = threadIdx.x, lane = tid & 63;
+    for (int64_t r = blockIdx.x; r < n_rows; r += gridDim.x) {
+        const int32_t* row = tile + r * ld;
+        const int shift = row_shift(row);
+        const int64_t c_min = first_column(row0, r, col0);
+        const bool row_is_empty = row_empty && row_empty[r];
+        int32_t above = (int32_t)(row0 + r);   // i, or an ancestor of i (wave-uniform)
+        for (int64_t v0 = (c_min + shift) & ~(int64_t)3; v0 < n_cols + shift; v0 += kFilterStep) {
+            const int64_t v = v0 + 4 * tid;
+            const Quad q = filter_quad(row, v, shift, c_min, n_cols, row_is_empty, col_empty, cap, bound);
+            if (__ballot(q.keep[0] || q.keep[1] || q.keep[2] || q.keep[3]) == 0) continue;
+            int32_t root = 0;
+            if (lane == 0) root = uf_find(parent, above);
+            above = __shfl(root, 0);
+#pragma unroll
+            for (int e = 0; e < 4; ++e)
+                if (q.keep[e]) uf_union(parent, above, (int32_t)(col0 + v - shift + e));
+        }
+    }
+}
+
+// The same union for pair n = (pi[n], pj[n]); a pair with an index outside [0, n_nodes) is skipped, as pair_lines_kernel skips it.
+__global__ __launch_bounds__(kLinkThreads) void link_pairs_kernel(const int32_t* __restrict__ pi, const int32_t* __restrict__ pj, int64_t n_pairs,
+                                                                  int32_t* parent, int64_t n_nodes) {
+    const int64_t n = (int64_t)blockIdx.x * kLinkThreads + threadIdx.x;
+    if (n >= n_pairs) return;
+    const int64_t i = pi[n], j = pj[n];
+    if (i < 0 || i >= n_nodes || j < 0 || j >= n_nodes || i == j) return;
+    uf_union(parent, (int32_t)i, (int32_t)j);
+}
+
+// After all linking, first launch: every node directly under its root.  Other threads shorten the same paths meanwhile, so
+// parent is read and written as in the links (agent-scope atomics); no root changes in this launch, so the root found is final.
+// Halving by every thread at once keeps the walk short whatever depth the forest came with.
+__global__ __launch_bounds__(kLinkThreads) void flatten_kernel(int32_t* parent, int64_t n_nodes) {
+    const int64_t x = (int64_t)blockIdx.x * kLinkThreads + threadIdx.x;
+    if (x >= n_nodes) return;
+    const int32_t root = uf_find(parent, (int32_t)x);
+    if (root != (int32_t)x) __hip_atomic_fetch_min(parent + x, root, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// Second launch: labels[x] = root of x.  This launch only reads parent (the kernel boundary separates it from every write), so
+// plain loads will do; after flatten_kernel the walk is one step.
+__global__ __launch_bounds__(kLinkThreads) void labels_kernel(const int32_t* __restrict__ parent, int64_t n_nodes, int32_t* __restrict__ labels) {
+    const int64_t x = (int64_t)blockIdx.x * kLinkThreads + threadIdx.x;
+    if (x >= n_nodes) return;
+    int32_t r = (int32_t)x;
+    for (;;) {
+        const int32_t p = parent[r];
+        if ((uint32_t)p >= (uint32_t)r) break;
+        r = p;
+    }
+    labels[x] = r;
+}
+
+unsigned link_grid(int64_t n) { return (unsigned)((n + kLinkThreads - 1) / kLinkThreads); }
+
+}  // namespace
+
+namespace dctfp_host {
+
+void launch_tri_link(const int32_t* tile, int64_t n_rows, int64_t n_cols, int64_t ld, int64_t row0, int64_t col0, const uint8_t* row_empty,
+                     const uint8_t* col_empty, int32_t cap, int32_t bound, int32_t* parent, hipStream_t stream) {
+    hipLaunchKernelGGL(tri_link_kernel, dim3(filter_grid(n_rows)), dim3(kFilterThreads), 0, stream, tile, n_rows, n_cols, ld, row0, col0,
+                       row_empty, col_empty, cap, bound, parent);
+}
+
+void launch_link_pairs(const int32_t* pi, const int32_t* pj, int64_t n_pairs, int32_t* parent, int64_t n_nodes, hipStream_t stream) {
+    hipLaunchKernelGGL(link_pairs_kernel, dim3(link_grid(n_pairs)), dim3(kLinkThreads), 0, stream, pi, pj, n_pairs, parent, n_nodes);
+}
+
+void launch_cluster_labels(int32_t* parent, int64_t n_nodes, int32_t* labels, hipStream_t stream) {
+    hipLaunchKernelGGL(flatten_kernel, dim3(link_grid(n_nodes)), dim3(kLinkThreads), 0, stream, parent, n_nodes);
+    hipLaunchKernelGGL(labels_kernel, dim3(link_grid(n_nodes)), dim3(kLinkThreads), 0, stream, parent, n_nodes, labels);
+}
+
+}  // namespace dctfp_host

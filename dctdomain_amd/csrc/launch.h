@@ -165,6 +165,13 @@ void launch_pair_lines(int64_t n_lines, const int32_t* pi, const int32_t* pj, co
                        const int64_t* id_off, int64_t n_ids, const char* table, const int64_t* line_off, uint8_t* out, int64_t out_bytes,
                        hipStream_t stream);
 
+// single-linkage clusters at a cut-off (k_cluster.hip): unions of a tile's surviving entries / of a list of pairs in a lock-free
+// union-find over parent[0 .. n_nodes), and the roots of all nodes afterwards (two launches: flatten, then read)
+void launch_tri_link(const int32_t* tile, int64_t n_rows, int64_t n_cols, int64_t ld, int64_t row0, int64_t col0, const uint8_t* row_empty,
+                     const uint8_t* col_empty, int32_t cap, int32_t bound, int32_t* parent, hipStream_t stream);
+void launch_link_pairs(const int32_t* pi, const int32_t* pj, int64_t n_pairs, int32_t* parent, int64_t n_nodes, hipStream_t stream);
+void launch_cluster_labels(int32_t* parent, int64_t n_nodes, int32_t* labels, hipStream_t stream);
+
 // DCTdomain of every protein pair from the fingerprints (k_protein.hip): scratch bytes of one side's block plan, and the launches
 // (the two plans, then the protein-minimum kernel on a grid of n_workgroups that walks the block pairs)
 size_t protein_plan_bytes(int64_t np);

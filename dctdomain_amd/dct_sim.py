@@ -2,7 +2,7 @@
 fingerprints (``-dct.npz``), with the L1 distances computed on the GPU.
 
     python -m dctdomain_amd.dct_sim --dct X-dct.npz [--pair P | --db Y-dct.npz [--rank {global,domain}]] [--output F]
-                                    [--pairfound F] [--top 5] [--threshold 0.25] [--min-domain X] [--min-global Y]
+                                    [--pairfound F] [--top 5] [--threshold 0.25] [--min-domain X] [--min-global Y] [--cluster]
 
 Same flags, same output text (src/dct-sim.py:179-211); ``--rank domain`` (not in the reference) orders database hits by
 DCTdomain instead of DCTglobal, and ``--min-domain`` / ``--min-global`` (not in the reference either, which ignores
@@ -19,6 +19,9 @@ Where the reference loops over protein pairs and, inside, over domain pairs in P
   (``dctfp_protein_min``, or the last rows' ``dctfp_l1_matrix`` when DCTglobal is cut), the pairs of the triangle within the
   bound selected on the device in output order (``dctfp_tri_filter_count`` / ``dctfp_tri_filter_fill``), both scores for those
   (``dctfp_pair_min``) and their lines (``dctfp_pair_lines``);
+- ``cluster_sim`` (``--cluster`` with a cut-off, not in the reference) joins those pairs into single-linkage clusters instead of
+  printing them (``Clusters``): the same tiles, a lock-free union-find on the device (``dctfp_tri_link`` / ``dctfp_link_pairs``
+  / ``dctfp_cluster_labels``), one ``representative member`` line per protein;
 - ``db_search`` ranks on the whole-protein fingerprints only (one L1 per protein pair), selects the printed hits of
   every query on the GPU (``dctfp_select_count`` / ``dctfp_select_fill``) and computes DCTdomain for those pairs only
   (``dctfp_pair_min``): ``ProteinSearch``.  Host memory is what is printed plus one tile, not n_query x n_db.  With
@@ -36,11 +39,13 @@ import time
 
 import numpy as np
 
-from .similarity import (PROTEIN_MIN_MAX_D, LineIds, block_min, block_min_device, l1_matrix, pair_line_offsets, pair_lines, pair_min,
-                         pair_min_device, protein_min, sim_lines, threshold_select, to_device_int8, tri_filter_count, tri_filter_fill)
+from .similarity import (PROTEIN_MIN_MAX_D, LineIds, block_min, block_min_device, cluster_labels, l1_matrix, link_pairs, pair_line_offsets,
+                         pair_lines, pair_min, pair_min_device, protein_min, sim_lines, threshold_select, to_device_int8, tri_filter_count,
+                         tri_filter_fill, tri_link)
 
 L1_FULL_SCALE = 17000      # src/dct-sim.py:24
 HEADER = '#prot1 prot2 sim-domain sim-global'
+CLUSTER_HEADER = '#representative member'
 
 
 def _sim(l1):
@@ -370,25 +375,31 @@ class FilteredPairs:
             yield i0, i1
             i0 = i1
 
-    def chunks(self):
-        """Yields device int32 tensors (i, j, min L1, last L1) of the surviving pairs, range of rows by range, in output order."""
+    @property
+    def bound(self) -> int:
+        """The bound of the route's tile: DCTglobal's when it excludes anything, else DCTdomain's."""
+        return self.bound_global if self.route == 'global' else self.bound_domain
+
+    def resident_rows(self):
+        """The file's fingerprints on the device when they fit there (at most COL_ROWS), else None."""
+        total = int(self.idx[-1])
+        return to_device_int8(self.fps[:total]) if 0 < total <= self.COL_ROWS else None
+
+    def tiles(self, resident=None):
+        """Yields, per stripe, (i0, i1, tile, (row flags, column flags)): step 1 of the class text.  The tile is device int32,
+        rows [i0, i1) x proteins i0 + 1 .. n - 1; the flags mark the proteins without fingerprints on the DCTglobal route (None on
+        the other: ``protein_min`` leaves 0x7fffffff there).  ``resident``: ``resident_rows()`` of a caller that needs the
+        fingerprints itself; taken here otherwise."""
         import torch
         n = len(self.idx) - 1
-        if n < 2 or min(self.bound_domain, self.bound_global) < 0:
-            return
         dev = torch.device('cuda', torch.cuda.current_device())
         total = int(self.idx[-1])
-        resident = to_device_int8(self.fps[:total]) if 0 < total <= self.COL_ROWS else None
-        idx_dev = torch.as_tensor(self.idx, device=dev) if resident is not None else None
-        id_lens = np.fromiter((len(f'{s}'.encode('utf8')) for s in self.sid), dtype=np.int64, count=n)
-        longest = int(id_lens.max())
+        if resident is None:
+            resident = self.resident_rows()
         if self.route == 'global':
             last_rows, empty = _last_rows(self.fps[:total], self.idx)
             last_dev = to_device_int8(last_rows) if n <= self.COL_ROWS else None
             empty_dev = torch.as_tensor(empty, device=dev)
-            bound = self.bound_global
-        else:
-            bound = self.bound_domain
 
         def rows(p0, p1):
             if resident is not None:
@@ -413,6 +424,23 @@ class FilteredPairs:
                     q0, q1 = q0 + col0, q1 + col0
                     protein_min(a, ia, rows(q0, q1), self.idx[q0:q1 + 1] - self.idx[q0], out=tile[:, q0 - col0:q1 - col0])
                 flags = (None, None)
+            yield i0, i1, tile, flags
+            del tile                                            # (before the next one is made; the caller drops its own too)
+
+    def chunks(self):
+        """Yields device int32 tensors (i, j, min L1, last L1) of the surviving pairs, range of rows by range, in output order."""
+        import torch
+        n = len(self.idx) - 1
+        if n < 2 or min(self.bound_domain, self.bound_global) < 0:
+            return
+        id_lens = np.fromiter((len(f'{s}'.encode('utf8')) for s in self.sid), dtype=np.int64, count=n)
+        longest = int(id_lens.max())
+        bound = self.bound
+        resident = self.resident_rows()
+        idx_dev = torch.as_tensor(self.idx, device=resident.device) if resident is not None else None
+        for i0, i1, tile, flags in self.tiles(resident):
+            col0 = i0 + 1
+            dev = tile.device
             count_dev = tri_filter_count(tile, i0, col0, bound, *flags)
             count = count_dev.cpu().numpy().astype(np.int64)
             # ranges of rows by the text they can make: count x (len_i + 14 + the longest id)
@@ -470,6 +498,112 @@ class FilteredPairs:
             k += 1
         if pending is not None:
             AllPairs._flush(sink, *pending)
+
+
+def _ragged_gather(raw: np.ndarray, starts: np.ndarray, lens: np.ndarray) -> np.ndarray:
+    """raw[starts[k]:starts[k] + lens[k]] for every k, concatenated (``_compact``'s index arithmetic, for bytes)."""
+    ends = np.cumsum(lens)
+    return raw[np.repeat(starts - (ends - lens), lens) + np.arange(int(ends[-1]) if len(ends) else 0, dtype=np.int64)]
+
+
+def _ascii_id_rows(sid):
+    """(uint8 (n, width) of the ids' bytes, their lengths) for a numpy unicode array whose ids are all ASCII -- what a
+    ``-dct.npz`` usually holds: a code point is a byte, every id padded to one width -- or None for anything else."""
+    if not (isinstance(sid, np.ndarray) and sid.dtype.kind == 'U' and sid.ndim == 1 and sid.dtype.itemsize and sid.dtype.isnative):
+        return None
+    points = np.ascontiguousarray(sid).view(np.uint32).reshape(len(sid), -1)
+    if points.max() >= 128:
+        return None
+    used = points != 0                                          # (numpy drops trailing NULs only: an id ends at its last other one)
+    lens = np.where(used.any(axis=1), points.shape[1] - np.argmax(used[:, ::-1], axis=1), 0)
+    return points.astype(np.uint8), lens
+
+
+def _ascii_lines(wide, lens, rep, member, chunk_bytes: int):
+    """``cluster_lines``' text from fixed-width id rows: a line is a row [representative, ' ', member, '\n'] with each id cut at
+    its length -- one masked copy per chunk of lines."""
+    width = wide.shape[1]
+    col = np.arange(width)[None, :]
+    per = max(1, chunk_bytes // (2 * width + 2))
+    for t0 in range(0, len(member), per):
+        r, m = rep[t0:t0 + per], member[t0:t0 + per]
+        sep = np.ones((len(r), 1), dtype=bool)
+        rows = np.concatenate([wide[r], np.full((len(r), 1), 32, np.uint8), wide[m], np.full((len(r), 1), 10, np.uint8)], axis=1)
+        yield rows[np.concatenate([col < lens[r, None], sep, col < lens[m, None], sep], axis=1)]
+
+
+def cluster_lines(sid, labels, chunk_bytes: int = 1 << 24):
+    """The text of ``--cluster`` for given labels (``labels[i]`` = index of the representative of protein i), as uint8 arrays of
+    whole lines of about ``chunk_bytes`` each: one line ``"{id of representative} {id of member}\n"`` per protein in the order of
+    a stable sort of the proteins by label -- clusters by representative index, members by index inside a cluster, so a
+    representative's own line comes first.  Composed from the ids' bytes by index arithmetic: no Python loop per line."""
+    labels = np.asarray(labels, dtype=np.int64)
+    n = len(labels)
+    if n != len(sid):
+        raise ValueError('one label per protein')
+    if n == 0:
+        return
+    if labels.min() < 0 or labels.max() >= n:
+        raise IndexError('a label outside the proteins of the file')
+    member = np.argsort(labels, kind='stable')
+    rep = labels[member]
+    wide = _ascii_id_rows(sid)
+    if wide is not None:
+        yield from _ascii_lines(*wide, rep, member, chunk_bytes)
+        return
+    enc = [f'{s}'.encode('utf8') for s in sid]
+    lens = np.fromiter((len(e) for e in enc), dtype=np.int64, count=n)
+    off = np.zeros(n + 1, dtype=np.int64)
+    np.cumsum(lens, out=off[1:])
+    raw = np.frombuffer(b''.join(enc) + b' \n', dtype=np.uint8)   # (the two separators sit behind the ids)
+    del enc
+    space, newline = int(off[-1]), int(off[-1]) + 1
+    ends = np.cumsum(lens[rep] + lens[member] + 2)
+    t0 = 0
+    while t0 < n:
+        t1 = min(n, max(t0 + 1, int(np.searchsorted(ends, (ends[t0 - 1] if t0 else 0) + chunk_bytes, 'right'))))
+        r, m = rep[t0:t1], member[t0:t1]
+        one = np.ones(t1 - t0, dtype=np.int64)
+        starts = np.stack([off[r], space * one, off[m], newline * one], axis=1).ravel()
+        yield _ragged_gather(raw, starts, np.stack([lens[r], one, lens[m], one], axis=1).ravel())
+        t0 = t1
+
+
+class Clusters(FilteredPairs):
+    """Single-linkage clusters of one file at cut-offs: the connected components of the graph whose nodes are all proteins and
+    whose edges are exactly ``FilteredPairs``' pairs, joined on the device in a union-find forest (``parent``, n int32) instead of
+    listed.  ``labels()[i]`` = the index of the representative of protein i = the smallest index in its cluster: a property of the
+    graph, whatever the stripes, the column groups or the order in which the device ran.
+
+    - One cut-off excludes anything: per stripe, ``FilteredPairs.tiles``' tile goes straight to ``tri_link``; nothing comes back
+      to the host before the end -- no count, no fill, no ``pair_min``, no lines.
+    - Both do: ``FilteredPairs.chunks`` -- which applies the second cut-off to the survivors of the first -- and ``link_pairs`` on
+      each chunk's pairs.
+    - Neither does (cut-offs <= 0, NaN): one cluster.  A bound below 0 (a cut-off above 1): every protein its own.  No tile.
+
+    Then ``cluster_labels`` on the device and one copy of n int32.  The text is composed on the host (``cluster_lines``), O(n)."""
+
+    def labels(self) -> np.ndarray:
+        n = len(self.idx) - 1
+        if n < 2 or min(self.bound_domain, self.bound_global) < 0:
+            return np.arange(max(n, 0), dtype=np.int32)
+        if min(self.bound_domain, self.bound_global) >= L1_FULL_SCALE:
+            return np.zeros(n, dtype=np.int32)
+        import torch
+        parent = torch.arange(n, dtype=torch.int32, device=torch.device('cuda', torch.cuda.current_device()))
+        if max(self.bound_domain, self.bound_global) < L1_FULL_SCALE:
+            for pi, pj, _, _ in self.chunks():
+                link_pairs(pi, pj, parent)
+        else:
+            for i0, _, tile, flags in self.tiles():
+                tri_link(tile, i0, i0 + 1, self.bound, parent, *flags)
+                del tile
+        return cluster_labels(parent).cpu().numpy()
+
+    def write(self, sink):
+        """Calls ``sink(memoryview)`` with the text, whole lines at a time, in order."""
+        for text in cluster_lines(self.sid, self.labels()):
+            sink(memoryview(text))
 
 
 class ProteinSearch:
@@ -600,10 +734,10 @@ class ProteinSearch:
 class Report:
     """Result lines to a file (header first) or to stdout."""
 
-    def __init__(self, path: str = None):
+    def __init__(self, path: str = None, header: str = HEADER):
         self.path = path
         self.out = open(path, 'w', encoding='utf8') if path else sys.stdout
-        self.line(HEADER)
+        self.line(header)
 
     def line(self, text: str):
         self.out.write(text + '\n')
@@ -626,14 +760,18 @@ class Report:
             self.out.flush()
 
 
-def _reporting(fn):
+def _reporting(fn=None, *, header: str = HEADER):
     """The mode functions keep the reference's signature -- the last argument may be an output path or
-    ``None`` (stdout) -- and also take an open ``Report``.  Keyword arguments (options beyond the reference's) pass through."""
+    ``None`` (stdout) -- and also take an open ``Report``.  Keyword arguments (options beyond the reference's) pass through.
+    ``@_reporting(header=...)``: the header of a report opened here."""
+    if fn is None:
+        return lambda f: _reporting(f, header=header)
+
     def run(*args, **kw):
         *head, output = args
         if isinstance(output, Report):
             return fn(*head, output, **kw)
-        report = Report(output)
+        report = Report(output, header)
         try:
             return fn(*head, report, **kw)
         finally:
@@ -697,17 +835,32 @@ def all_sim(npzfile: str, report: Report, min_domain: float = None, min_global: 
         FilteredPairs(sid, idx, fps, min_domain=min_domain, min_global=min_global).write(report.raw)
 
 
+@_reporting(header=CLUSTER_HEADER)
+def cluster_sim(npzfile: str, report: Report, min_domain: float = None, min_global: float = None):
+    """Single-linkage clusters at the cut-offs (``Clusters``): one line ``representative member`` per protein."""
+    if min_domain is None and min_global is None:
+        raise ValueError('clustering needs a cut-off: min_domain, min_global or both')
+    sid, idx, fps = _load_npz(npzfile)
+    Clusters(sid, idx, fps, min_domain=min_domain, min_global=min_global).write(report.raw)
+
+
 RANKS = ('global', 'domain')
 
 
 class _Parser(argparse.ArgumentParser):
     """``--rank`` orders database hits: it is an error without ``--db`` or beside ``--pair`` (which takes precedence).
-    ``--min-domain`` / ``--min-global`` cut the all-against-all output: an error beside ``--pair`` or ``--db``."""
+    ``--min-domain`` / ``--min-global`` cut the all-against-all output: an error beside ``--pair`` or ``--db``.
+    ``--cluster`` joins the pairs that pass into clusters: an error beside ``--pair`` or ``--db``, or without a cut-off."""
 
     def parse_known_args(self, args=None, namespace=None):
         ns, rest = super().parse_known_args(args, namespace)
         if getattr(ns, 'rank', None) is not None and (ns.pair or not ns.db):
             self.error('--rank applies to database search (--db) only, not to --pair or all-against-all')
+        if getattr(ns, 'cluster', False):
+            if ns.pair or ns.db:
+                self.error('--cluster applies to all-against-all only, not to --pair or --db')
+            if ns.min_domain is None and ns.min_global is None:
+                self.error('--cluster needs a cut-off: --min-domain, --min-global or both')
         for opt in ('min_domain', 'min_global'):
             if getattr(ns, opt, None) is not None and (ns.pair or ns.db):
                 self.error(f'--{opt.replace("_", "-")} applies to all-against-all only, not to --pair or --db')
@@ -731,18 +884,23 @@ def build_parser() -> argparse.ArgumentParser:
                     help='all-against-all: print a pair only if its DCTdomain is not below X')
     ap.add_argument('--min-global', type=float, default=None, metavar='Y',
                     help='all-against-all: print a pair only if its DCTglobal is not below Y (with --min-domain: both must hold)')
+    ap.add_argument('--cluster', action='store_true',
+                    help='all-against-all with a cut-off: print single-linkage clusters (one "representative member" line per '
+                         'protein) instead of the pairs')
     return ap
 
 
 def main(argv=None):
     t_start = time.time()
     args = build_parser().parse_args(argv)
-    report = Report(args.output)
+    report = Report(args.output, CLUSTER_HEADER if args.cluster else HEADER)
     t_work = time.time()
     if args.pair:
         pair_sim(args.dct, args.pair, args.pairfound, report)
     elif args.db:
         db_search(args.dct, args.db, args.top, args.threshold, report, rank=args.rank or 'global')
+    elif args.cluster:
+        cluster_sim(args.dct, report, min_domain=args.min_domain, min_global=args.min_global)
     else:
         all_sim(args.dct, report, min_domain=args.min_domain, min_global=args.min_global)
     report.close()

@@ -347,6 +347,55 @@ def tri_filter(tile: torch.Tensor, row0: int, col0: int, bound: int, row_empty=N
     return m, i.cpu().numpy().astype(np.int64), j.cpu().numpy().astype(np.int64)
 
 
+def _parent_arg(parent: torch.Tensor, device) -> int:
+    if parent.dtype != torch.int32 or parent.dim() != 1 or not parent.is_contiguous() or parent.device != device:
+        raise ValueError('parent must be a contiguous 1-D int32 tensor on the device of the other arguments')
+    return parent.numel()
+
+
+def tri_link(tile: torch.Tensor, row0: int, col0: int, bound: int, parent: torch.Tensor, row_empty=None, col_empty=None, cap: int = 17000):
+    """Joins, in the union-find forest ``parent`` (device int32, started as ``torch.arange(n)``), proteins row0 + r and col0 + c
+    for every entry of an L1 tile that ``tri_filter_count`` would count (``dctfp_tri_link``).  Nothing comes back: the forest is
+    read with ``cluster_labels`` once every tile has been linked."""
+    n_rows, n_cols, ld, re, ce, bound = _tri_filter_args(tile, row0, col0, bound, row_empty, col_empty, cap)
+    n_nodes = _parent_arg(parent, tile.device)
+    if row0 + n_rows > n_nodes or col0 + n_cols > n_nodes:
+        raise IndexError('tile outside the nodes of parent')
+    if n_rows and n_cols:
+        ctx = _lib.get_context(tile.device.index)
+        stream = C.c_void_p(torch.cuda.current_stream(tile.device).cuda_stream)
+        _lib.check(ctx._lib.dctfp_tri_link(ctx.handle, tile.data_ptr(), n_rows, n_cols, ld, int(row0), int(col0),
+                                           re.data_ptr() if re is not None else None, ce.data_ptr() if ce is not None else None,
+                                           cap, bound, parent.data_ptr(), n_nodes, stream))
+
+
+def link_pairs(pi: torch.Tensor, pj: torch.Tensor, parent: torch.Tensor):
+    """Joins proteins pi[n] and pj[n] (device int32, ``tri_filter_fill``'s output) in the forest ``parent`` (``dctfp_link_pairs``);
+    the kernel skips a pair that names a node outside it."""
+    n_nodes = _parent_arg(parent, pi.device)
+    for t in (pi, pj):
+        if t.dtype != torch.int32 or t.dim() != 1 or t.numel() != pi.numel() or not t.is_contiguous() or t.device != parent.device:
+            raise ValueError('pi / pj must be contiguous int32 device tensors of one length')
+    if pi.numel() and n_nodes:
+        ctx = _lib.get_context(parent.device.index)
+        stream = C.c_void_p(torch.cuda.current_stream(parent.device).cuda_stream)
+        _lib.check(ctx._lib.dctfp_link_pairs(ctx.handle, pi.data_ptr(), pj.data_ptr(), pi.numel(), parent.data_ptr(), n_nodes, stream))
+
+
+def cluster_labels(parent: torch.Tensor) -> torch.Tensor:
+    """A new device int32 tensor: labels[x] = the root of x in the forest ``parent`` = the smallest member of x's component
+    (``dctfp_cluster_labels``).  ``parent`` stays a forest of the same components (flattened): linking may go on."""
+    if parent.device.type != 'cuda':
+        raise ValueError('parent must be a device tensor')
+    n_nodes = _parent_arg(parent, parent.device)
+    labels = torch.empty(n_nodes, dtype=torch.int32, device=parent.device)
+    if n_nodes:
+        ctx = _lib.get_context(parent.device.index)
+        stream = C.c_void_p(torch.cuda.current_stream(parent.device).cuda_stream)
+        _lib.check(ctx._lib.dctfp_cluster_labels(ctx.handle, parent.data_ptr(), n_nodes, labels.data_ptr(), stream))
+    return labels
+
+
 class LineIds:
     """The protein ids of a file as ``dctfp_sim_lines`` reads them: ``off`` = int64 prefix offsets of their UTF-8 bytes (host),
     ``bytes_dev`` / ``off_dev`` = the concatenated bytes and the offsets on the device."""

@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define DCTFP_VERSION 103 /* 0.1.3: dctfp_tri_filter_count / _fill, dctfp_pair_lines */
+#define DCTFP_VERSION 104 /* 0.1.4: dctfp_tri_link, dctfp_link_pairs, dctfp_cluster_labels */
 
 #define DCTFP_OK 0
 #define DCTFP_ERR_INVALID (-1) /* bad argument (null pointer, piece outside its sequence, ...) */
@@ -387,6 +387,34 @@ int dctfp_tri_filter_fill(dctfp_ctx* ctx, const int32_t* tile, int64_t n_rows, i
 int dctfp_pair_lines(dctfp_ctx* ctx, int64_t n_lines, const int32_t* pi, const int32_t* pj, const int32_t* mn, const int32_t* last,
                      const uint8_t* ids, const int64_t* id_off, int64_t n_ids, const char* table, const int64_t* line_off, uint8_t* out,
                      int64_t out_bytes, void* stream);
+
+/* Single-linkage clusters at a cut-off (dct-sim --cluster; not in the reference): the connected components of the graph whose
+ * edges are the pairs dctfp_tri_filter_count / dctfp_tri_filter_fill select, joined on the device instead of listed.
+ * `parent` = device int32 (n_nodes), a union-find forest the caller starts as parent[x] = x and hands to any number of these
+ * calls on one stream: parent[x] <= x always, x is a root when parent[x] == x, a union hooks the larger of two roots under the
+ * smaller (compare-and-swap), finds shorten paths (atomic min).  The root of a finished component is therefore its smallest
+ * member, whatever the order in which the device ran the unions: the result is a property of the graph.
+ * dctfp_tri_link extends dctfp_tri_filter_count's survival rule -- the same tile arguments, j > i and min(L1, cap) <= bound, the
+ * same flags -- from counting the surviving entries (i, j) of a tile to joining i and j.  DCTFP_ERR_INVALID as there, and when
+ * row0 + n_rows or col0 + n_cols exceeds n_nodes (checked on the host: the device never forms an index outside parent);
+ * DCTFP_ERR_LIMIT for n_nodes >= 2^31.  n_rows, n_cols or n_nodes of 0: nothing to do. */
+int dctfp_tri_link(dctfp_ctx* ctx, const int32_t* tile, int64_t n_rows, int64_t n_cols, int64_t ld, int64_t row0, int64_t col0,
+                   const uint8_t* row_empty, const uint8_t* col_empty, int32_t cap, int32_t bound, int32_t* parent, int64_t n_nodes,
+                   void* stream);
+
+/* The union of dctfp_tri_link for a LIST of pairs (pi[n], pj[n]), device int32 -- dctfp_tri_filter_fill's output, or what is left
+ * of it after a second cut-off: extends dctfp_tri_filter_count's survival rule to pairs the caller has selected further.  A pair
+ * with an index outside [0, n_nodes) is skipped, as dctfp_pair_lines skips it; i == j does nothing.  DCTFP_ERR_LIMIT for
+ * n_nodes >= 2^31 or more than 2^31 pairs per call; n_pairs or n_nodes of 0: nothing to do. */
+int dctfp_link_pairs(dctfp_ctx* ctx, const int32_t* pi, const int32_t* pj, int64_t n_pairs, int32_t* parent, int64_t n_nodes,
+                     void* stream);
+
+/* After the links (dctfp_tri_link, dctfp_link_pairs -- the components of dctfp_tri_filter_count's survival rule): labels[x]
+ * (device int32, n_nodes) = the root of x = the smallest member of x's component.  Two launches of its own, ordered after the
+ * links by the stream: the first puts every node directly under its root (path halving by all threads at once: the depth of the
+ * forest handed in is not the run time), the second reads.  `parent` is left a valid forest of the same components, so linking
+ * may go on afterwards.  DCTFP_ERR_LIMIT for n_nodes >= 2^31; n_nodes of 0: nothing to do. */
+int dctfp_cluster_labels(dctfp_ctx* ctx, int32_t* parent, int64_t n_nodes, int32_t* labels, void* stream);
 
 /* query_db's search (src/query_db.py:75-87: a flat FAISS index forced to METRIC_L1 at :76, index.search at :87) without a
  * distance matrix: for query rows q (nq x d, row stride ldq) and database rows b (nb x d, stride ldb), int8 on the device, each

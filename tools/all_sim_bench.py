@@ -4,11 +4,16 @@
     python tools/all_sim_bench.py --part scale --n 20000 [--dir D]     # new path to /dev/null and to a file under D
     python tools/all_sim_bench.py --part scale --n 1000000 --min-global 0.5   # the same with cut-offs (dct_sim.FilteredPairs)
     python tools/all_sim_bench.py --part filter --n 50000 [--min-domain 0.5]  # cut-offs beside the unfiltered run, one process
+    python tools/all_sim_bench.py --part cluster --n 50000 --families 500 --family-size 100 --min-domain 0.5   # --cluster beside the cut-offs
 
 `filter` loads one synthetic file and runs, after the load and a warm-up on a small file, the unfiltered path (AllPairs, to
 /dev/null as `scale` does) and the path with cut-offs; events around the device steps of the second (the tile: protein_min or
 l1_matrix; the filter; pair_min; the lines) say where its device time goes.  --planted fingerprints are overwritten with near
 copies of others first: random proteins alone leave nothing above a cut-off.
+`cluster` loads one synthetic file (--families x --family-size proteins overwritten with near copies of a family's first member)
+and runs, after a warm-up of both on a small file, --repeat times each: the path with cut-offs (FilteredPairs, to /dev/null) and
+the clustering at the same cut-offs (Clusters); events around the device steps of the latter (tile / link / labels), the host
+text timed apart.
 `scale` writes a synthetic -dct.npz (about 4.5 fingerprints per protein, 17-character ids) and runs the new path in a child
 process per sink (and one that only initialises the GPU: the RSS floor), so that the child's peak RSS (ru_maxrss of RUSAGE_CHILDREN, as tools/run_with_rss.py) is that of the run
 alone.  The child also measures the pinned device-to-host copy rate of one TEXT_BYTES buffer.  The file run is skipped when
@@ -188,6 +193,110 @@ def part_filter(args):
             'share_outside_tile_of_device_steps': round(1 - ms.get('tile', 0.0) / device, 4) if device else None}
 
 
+def plant_families(idx, fps, families: int, size: int, seed: int = 13):
+    """Overwrites `families` x `size` proteins with near copies (+-2) of the first member of their family.  Returns (idx, fps)."""
+    n = len(idx) - 1
+    rng = np.random.default_rng(seed)
+    chosen = rng.choice(n, size=families * size, replace=False).reshape(families, size)
+    counts = np.diff(idx)
+    new_counts = counts.copy()
+    new_counts[chosen[:, 1:]] = counts[chosen[:, :1]]
+    new_idx = np.concatenate([[0], np.cumsum(new_counts)]).astype(np.int64)
+    out = np.empty((int(new_idx[-1]), fps.shape[1]), dtype=np.int8)
+    same = np.ones(n, dtype=bool)
+    same[chosen[:, 1:].ravel()] = False
+    out[np.repeat(same, new_counts)] = fps[np.repeat(same, counts)]
+    for fam in chosen:
+        src = fps[idx[fam[0]]:idx[fam[0] + 1]].astype(np.int64)
+        for p in fam[1:]:
+            out[new_idx[p]:new_idx[p + 1]] = np.clip(src + rng.integers(-2, 3, size=src.shape), -127, 127)
+    return new_idx, out
+
+
+def part_cluster(args):
+    """One process: FilteredPairs to /dev/null and Clusters at the same cut-offs on the same loaded file, --repeat times each
+    after a warm-up of both on a small one; device time of the clustering by step."""
+    import torch
+    from dctdomain_amd import dct_sim
+    min_domain = args.min_domain if args.min_domain is not None or args.min_global is not None else 0.5
+    with tempfile.TemporaryDirectory(dir=args.dir) as tmp:
+        small, path = os.path.join(tmp, 'w-dct.npz'), os.path.join(tmp, 'f-dct.npz')
+        synth(small, 2000, 5)
+        synth(path, args.n, 7)
+        wsid, widx, wfps = dct_sim._load_npz(small)
+        sid, idx, fps = dct_sim._load_npz(path)
+    widx, wfps = plant_families(widx, wfps, 10, 10)
+    if args.families:
+        idx, fps = plant_families(idx, fps, args.families, args.family_size)
+    spans = {}
+
+    def timed(name, label):
+        fn = getattr(dct_sim, name)
+
+        def run(*a, **k):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            out = fn(*a, **k)
+            e1.record()
+            spans.setdefault(label, []).append((e0, e1))
+            return out
+        setattr(dct_sim, name, run)
+        return fn
+    written, kept = [0], [0]
+    with open(os.devnull, 'wb', buffering=0) as fh:
+        def sink(mv):
+            fh.write(mv)
+            written[0] += len(mv)
+            kept[0] += bytes(mv).count(b'\n')
+        dct_sim.FilteredPairs(wsid, widx, wfps, min_domain, args.min_global).write(sink)
+        dct_sim.Clusters(wsid, widx, wfps, min_domain, args.min_global).write(sink)
+        torch.cuda.synchronize()
+        t_filter, t_cluster, t_text, device_ms = [], [], [], []
+        for _ in range(args.repeat):
+            written[0] = kept[0] = 0
+            fp = dct_sim.FilteredPairs(sid, idx, fps, min_domain, args.min_global)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            fp.write(sink)
+            torch.cuda.synchronize()
+            t_filter.append(time.perf_counter() - t0)
+            edges, edge_bytes = kept[0], written[0]
+        steps = (('protein_min', 'tile'), ('l1_matrix', 'tile'), ('tri_link', 'link'), ('link_pairs', 'link'), ('cluster_labels', 'labels'),
+                 ('tri_filter_count', 'filter'), ('tri_filter_fill', 'filter'), ('pair_min_device', 'pair_min'))
+        real = [(name, timed(name, label)) for name, label in steps]
+        for _ in range(args.repeat):
+            spans.clear()
+            written[0] = kept[0] = 0
+            cl = dct_sim.Clusters(sid, idx, fps, min_domain, args.min_global)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            labels = cl.labels()
+            torch.cuda.synchronize()
+            t1 = time.perf_counter()
+            for text in dct_sim.cluster_lines(sid, labels):
+                sink(memoryview(text))
+            t2 = time.perf_counter()
+            t_cluster.append(t2 - t0)
+            t_text.append(t2 - t1)
+            device_ms.append({label: round(sum(a.elapsed_time(b) for a, b in ev), 3) for label, ev in spans.items()})
+        for name, fn in real:
+            setattr(dct_sim, name, fn)
+    n = len(sid)
+    med = lambda v: sorted(v)[len(v) // 2]   # noqa: E731
+    ms = device_ms[t_cluster.index(med(t_cluster))]
+    return {'part': 'cluster', 'n': n, 'fingerprints': int(idx[-1]), 'pairs': n * (n - 1) // 2, 'families': args.families,
+            'family_size': args.family_size, 'min_domain': min_domain, 'min_global': args.min_global, 'route': cl.route,
+            'stripes': len(list(cl.stripes())), 'edges': edges, 'edge_text_bytes': edge_bytes, 'clusters': int(len(np.unique(labels))),
+            'largest': int(np.bincount(labels).max()), 'cluster_text_bytes': written[0], 'cluster_lines': kept[0],
+            'filtered_s': [round(t, 3) for t in t_filter], 'cluster_s': [round(t, 3) for t in t_cluster],
+            'cluster_host_text_s': [round(t, 3) for t in t_text], 'filtered_median_s': round(med(t_filter), 3),
+            'cluster_median_s': round(med(t_cluster), 3), 'filtered_spread_s': round(max(t_filter) - min(t_filter), 3),
+            'cluster_faster': med(t_cluster) < med(t_filter),
+            'cluster_within_filtered_spread': med(t_cluster) <= med(t_filter) + (max(t_filter) - min(t_filter)),
+            'device_ms_of_median_run': ms, 'device_ms_all': device_ms,
+            'link_over_tile': round(ms.get('link', 0.0) / ms['tile'], 4) if ms.get('tile') else None}
+
+
 def part_base(args):
     """(child) a process that has only initialised the GPU and run one small distance tile: the RSS floor of the run."""
     import torch
@@ -240,18 +349,21 @@ def part_scale(args):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument('--part', required=True, choices=['compare', 'scale', 'filter', 'run', 'base'])
+    ap.add_argument('--part', required=True, choices=['compare', 'scale', 'filter', 'cluster', 'run', 'base'])
     ap.add_argument('--n', type=int, default=2000)
     ap.add_argument('--dir', default=None, help='where the npz and the text file go (local disk)')
     ap.add_argument('--npz')
     ap.add_argument('--sink')
     ap.add_argument('--timeout', type=float, default=1200)
     ap.add_argument('--planted', type=int, default=1000, help='filter: fingerprints overwritten with near copies of others')
+    ap.add_argument('--families', type=int, default=0, help='cluster: families of near copies planted in the file')
+    ap.add_argument('--family-size', type=int, default=100, help='cluster: proteins per planted family')
+    ap.add_argument('--repeat', type=int, default=3, help='cluster: runs of each path')
     ap.add_argument('--min-domain', type=float, default=None, help='scale / filter: print the pairs whose DCTdomain is not below this')
     ap.add_argument('--min-global', type=float, default=None, help='scale / filter: print the pairs whose DCTglobal is not below this')
     ap.add_argument('--out')
     args = ap.parse_args()
-    res = {'compare': part_compare, 'scale': part_scale, 'filter': part_filter, 'run': part_run, 'base': part_base}[args.part](args)
+    res = {'compare': part_compare, 'scale': part_scale, 'filter': part_filter, 'cluster': part_cluster, 'run': part_run, 'base': part_base}[args.part](args)
     line = json.dumps(res)
     print(line)
     if args.out:
