@@ -60,7 +60,8 @@ EXPORTS = ('dctfp_version', 'dctfp_last_error', 'dctfp_create', 'dctfp_destroy',
            'dctfp_pair_min', 'dctfp_select_count', 'dctfp_select_fill', 'dctfp_sim_lines',
            'dctfp_l1_knn', 'dctfp_query_rank', 'dctfp_query_lines', 'dctfp_protein_min',
            'dctfp_tri_filter_count', 'dctfp_tri_filter_fill', 'dctfp_pair_lines',
-           'dctfp_tri_link', 'dctfp_link_pairs', 'dctfp_cluster_labels')
+           'dctfp_tri_link', 'dctfp_link_pairs', 'dctfp_cluster_labels',
+           'dctfp_pair_argmin', 'dctfp_pair_domain_lines')
 
 
 def load(path: str = None):
@@ -171,6 +172,7 @@ def _configure(lib):
         lib.dctfp_row_order.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p]
         lib.dctfp_pair_min.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p,
                                        C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.dctfp_pair_argmin.argtypes = lib.dctfp_pair_min.argtypes[:-1] + [C.c_void_p, C.c_void_p, C.c_void_p]
         lib.dctfp_protein_min.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p,
                                           C.c_int64, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]
         lib.dctfp_select_count.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32,
@@ -185,6 +187,8 @@ def _configure(lib):
                                               C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
         lib.dctfp_pair_lines.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                          C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
+        lib.dctfp_pair_domain_lines.argtypes = [C.c_void_p, C.c_int64] + [C.c_void_p] * 8 + [C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
+                                                C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
         lib.dctfp_tri_link.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_void_p,
                                        C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]
         lib.dctfp_link_pairs.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]

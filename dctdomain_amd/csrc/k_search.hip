@@ -1,5 +1,6 @@
 // Protein-level search (dct-sim --db / --pair, src/dct-sim.py:86-156) without the all-against-all block matrix:
-//   pair_min_kernel      -- DCTdomain / DCTglobal L1 of a list of protein pairs, read straight from the fingerprints;
+//   pair_min_kernel      -- DCTdomain / DCTglobal L1 of a list of protein pairs, read straight from the fingerprints, and
+//                           (ARG) the fingerprint pair DCTdomain came from;
 //   select_count_kernel  -- per row of a last-row distance tile: how many hits the reference prints, and where the cut is;
 //   select_fill_kernel   -- the hits themselves, compacted into a ragged array at host-computed offsets;
 //   select_order_kernel  -- each row's hits in the reference's order (key ascending, ties by column), rows of <= 1024 hits;
@@ -10,6 +11,7 @@
 namespace {
 
 constexpr int kPairWaves = 4;        // protein pairs per workgroup (one wave each)
+constexpr int32_t kFullScale = 17000;   // the L1 of similarity 0 (src/dct-sim.py:24)
 constexpr int kSelThreads = 1024;    // one workgroup per row in the selection
 constexpr int kSelWaves = kSelThreads / 64;
 constexpr int kBinsPerThread = 17;   // the key histogram: 17 bins per thread, keys 0 .. 17407
@@ -31,24 +33,34 @@ __device__ inline uint32_t wave_sum(uint32_t s) {
 // Rows of up to 512 bytes (every fingerprint file: 480) keep the pa row in two registers per lane and read four pb rows per
 // step, so that a wave has eight loads in flight instead of two.  An empty protein on either side leaves 0x7fffffff in both
 // outputs (block_min_kernel's fill); a pair index outside [0, npa) x [0, npb) writes -1 to both.
-template <bool ALIGNED>
+// ARG (dctfp_pair_argmin): also where the minimum was, as row indices within the two proteins -- the reference's loop
+// (src/dct-sim.py:42-50) replaces its maximum on `s > maxs` only, so among equal L1 values the first in (row of pa, row of pb)
+// order stands.  After wave_sum every lane holds the sum, so the comparison is wave-uniform; it is made once per fingerprint
+// pair in exactly that order (i, then j + u with u ascending), with `<`: the unroll cannot change which pair wins.  No pair
+// (-1, -1) when the minimum is 17000 or more -- similarity 0 never exceeds the loop's starting 0 -- which covers the empty sides.
+template <bool ALIGNED, bool ARG>
 __global__ __launch_bounds__(kPairWaves * 64) void pair_min_kernel(const int32_t* __restrict__ pairs, int64_t n_pairs,
                                                                    const int8_t* __restrict__ a, int64_t lda, const int64_t* __restrict__ idx_a,
                                                                    int64_t npa, const int8_t* __restrict__ b, int64_t ldb,
                                                                    const int64_t* __restrict__ idx_b, int64_t npb, int d,
-                                                                   int32_t* __restrict__ out_min, int32_t* __restrict__ out_last) {
+                                                                   int32_t* __restrict__ out_min, int32_t* __restrict__ out_last,
+                                                                   int32_t* __restrict__ out_arg_a, int32_t* __restrict__ out_arg_b) {
     const int lane = threadIdx.x & 63;
     const int64_t p = (int64_t)blockIdx.x * kPairWaves + (threadIdx.x >> 6);
     if (p >= n_pairs) return;
     const int32_t pa = pairs[2 * p], pb = pairs[2 * p + 1];
     if (pa < 0 || pa >= npa || pb < 0 || pb >= npb) {
-        if (lane == 0) out_min[p] = out_last[p] = -1;
+        if (lane == 0) {
+            out_min[p] = out_last[p] = -1;
+            if constexpr (ARG) out_arg_a[p] = out_arg_b[p] = -1;
+        }
         return;
     }
     const int64_t a0 = idx_a[pa], a1 = idx_a[pa + 1], b0 = idx_b[pb], b1 = idx_b[pb + 1];
     constexpr uint32_t kFlip = 0x80808080u;   // signed -> unsigned order, |x - y| unchanged
     const int nd = (d + 3) / 4;
     int32_t mn = 0x7fffffff, last = 0x7fffffff;
+    int32_t arg_a = -1, arg_b = -1;
     if (nd <= 128) {
         const bool has0 = lane < nd, has1 = lane + 64 < nd;
         for (int64_t i = a0; i < a1; ++i) {
@@ -72,6 +84,12 @@ __global__ __launch_bounds__(kPairWaves * 64) void pair_min_kernel(const int32_t
                 for (int u = 0; u < 4; ++u)
                     if (j + u < b1) {
                         last = (int32_t)s[u];
+                        if constexpr (ARG) {
+                            if (last < mn) {
+                                arg_a = (int32_t)(i - a0);
+                                arg_b = (int32_t)(j + u - b0);
+                            }
+                        }
                         mn = min(mn, last);
                     }
             }
@@ -84,6 +102,12 @@ __global__ __launch_bounds__(kPairWaves * 64) void pair_min_kernel(const int32_t
                 uint32_t s = 0;
                 for (int k = lane; k < nd; k += 64) s = __builtin_amdgcn_sad_u8(bytes4(ra, d, k, ALIGNED) ^ kFlip, bytes4(rb, d, k, ALIGNED) ^ kFlip, s);
                 last = (int32_t)wave_sum(s);
+                if constexpr (ARG) {
+                    if (last < mn) {
+                        arg_a = (int32_t)(i - a0);
+                        arg_b = (int32_t)(j - b0);
+                    }
+                }
                 mn = min(mn, last);
             }
         }
@@ -91,6 +115,11 @@ __global__ __launch_bounds__(kPairWaves * 64) void pair_min_kernel(const int32_t
     if (lane == 0) {
         out_min[p] = mn;
         out_last[p] = last;
+        if constexpr (ARG) {
+            const bool none = mn >= kFullScale;
+            out_arg_a[p] = none ? -1 : arg_a;
+            out_arg_b[p] = none ? -1 : arg_b;
+        }
     }
 }
 
@@ -362,16 +391,29 @@ __global__ __launch_bounds__(kLineThreads) void sim_lines_kernel(const int32_t* 
 
 namespace dctfp_host {
 
-void launch_pair_min(const int32_t* pairs, int64_t n_pairs, const int8_t* a, int64_t lda, const int64_t* idx_a, int64_t npa, const int8_t* b,
-                     int64_t ldb, const int64_t* idx_b, int64_t npb, int d, int32_t* out_min, int32_t* out_last, hipStream_t stream) {
+template <bool ARG>
+static void launch_pair_kernel(const int32_t* pairs, int64_t n_pairs, const int8_t* a, int64_t lda, const int64_t* idx_a, int64_t npa,
+                               const int8_t* b, int64_t ldb, const int64_t* idx_b, int64_t npb, int d, int32_t* out_min, int32_t* out_last,
+                               int32_t* out_arg_a, int32_t* out_arg_b, hipStream_t stream) {
     const bool aligned = ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b) | (uintptr_t)lda | (uintptr_t)ldb) & 3u) == 0;
     const dim3 grid((unsigned)((n_pairs + kPairWaves - 1) / kPairWaves));
     if (aligned)
-        hipLaunchKernelGGL((pair_min_kernel<true>), grid, dim3(kPairWaves * 64), 0, stream, pairs, n_pairs, a, lda, idx_a, npa, b, ldb, idx_b,
-                           npb, d, out_min, out_last);
+        hipLaunchKernelGGL((pair_min_kernel<true, ARG>), grid, dim3(kPairWaves * 64), 0, stream, pairs, n_pairs, a, lda, idx_a, npa, b, ldb,
+                           idx_b, npb, d, out_min, out_last, out_arg_a, out_arg_b);
     else
-        hipLaunchKernelGGL((pair_min_kernel<false>), grid, dim3(kPairWaves * 64), 0, stream, pairs, n_pairs, a, lda, idx_a, npa, b, ldb, idx_b,
-                           npb, d, out_min, out_last);
+        hipLaunchKernelGGL((pair_min_kernel<false, ARG>), grid, dim3(kPairWaves * 64), 0, stream, pairs, n_pairs, a, lda, idx_a, npa, b, ldb,
+                           idx_b, npb, d, out_min, out_last, out_arg_a, out_arg_b);
+}
+
+void launch_pair_min(const int32_t* pairs, int64_t n_pairs, const int8_t* a, int64_t lda, const int64_t* idx_a, int64_t npa, const int8_t* b,
+                     int64_t ldb, const int64_t* idx_b, int64_t npb, int d, int32_t* out_min, int32_t* out_last, hipStream_t stream) {
+    launch_pair_kernel<false>(pairs, n_pairs, a, lda, idx_a, npa, b, ldb, idx_b, npb, d, out_min, out_last, nullptr, nullptr, stream);
+}
+
+void launch_pair_argmin(const int32_t* pairs, int64_t n_pairs, const int8_t* a, int64_t lda, const int64_t* idx_a, int64_t npa,
+                        const int8_t* b, int64_t ldb, const int64_t* idx_b, int64_t npb, int d, int32_t* out_min, int32_t* out_last,
+                        int32_t* out_arg_a, int32_t* out_arg_b, hipStream_t stream) {
+    launch_pair_kernel<true>(pairs, n_pairs, a, lda, idx_a, npa, b, ldb, idx_b, npb, d, out_min, out_last, out_arg_a, out_arg_b, stream);
 }
 
 int select_max_cap() { return kSelThreads * kBinsPerThread - 1; }

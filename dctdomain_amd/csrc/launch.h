@@ -144,6 +144,10 @@ int launch_reccut(int cls, const dctfp::CutJob* jobs, unsigned n, double cut1, d
 // protein-level search (k_search.hip): pair minima from the fingerprints, threshold-aware selection on a last-row distance tile
 void launch_pair_min(const int32_t* pairs, int64_t n_pairs, const int8_t* a, int64_t lda, const int64_t* idx_a, int64_t npa, const int8_t* b,
                      int64_t ldb, const int64_t* idx_b, int64_t npb, int d, int32_t* out_min, int32_t* out_last, hipStream_t stream);
+// ... and the same with the fingerprint pair the minimum came from (dctfp_pair_argmin: row indices within the proteins, -1 = none)
+void launch_pair_argmin(const int32_t* pairs, int64_t n_pairs, const int8_t* a, int64_t lda, const int64_t* idx_a, int64_t npa,
+                        const int8_t* b, int64_t ldb, const int64_t* idx_b, int64_t npb, int d, int32_t* out_min, int32_t* out_last,
+                        int32_t* out_arg_a, int32_t* out_arg_b, hipStream_t stream);
 int select_max_cap();   // the largest key the selection's LDS histogram holds
 void launch_select_count(const int32_t* dist, int64_t n_rows, int64_t n_cols, int64_t ld, const uint8_t* row_empty, const uint8_t* col_empty,
                          int32_t cap, int32_t bound, int32_t top, int32_t* out_count, int32_t* out_cut, hipStream_t stream);
@@ -164,6 +168,11 @@ void launch_tri_filter_fill(const int32_t* tile, int64_t n_rows, int64_t n_cols,
 void launch_pair_lines(int64_t n_lines, const int32_t* pi, const int32_t* pj, const int32_t* mn, const int32_t* last, const uint8_t* ids,
                        const int64_t* id_off, int64_t n_ids, const char* table, const int64_t* line_off, uint8_t* out, int64_t out_bytes,
                        hipStream_t stream);
+// ... with the labels of DCTdomain's fingerprint pair behind the scores (dct-sim --domains)
+void launch_pair_domain_lines(int64_t n_lines, const int32_t* pi, const int32_t* pj, const int32_t* mn, const int32_t* last, const int32_t* la,
+                              const int32_t* lb, const uint8_t* ids, const int64_t* id_off, int64_t n_ids, const uint8_t* labels,
+                              const int64_t* label_off, int64_t n_labels, const char* table, const int64_t* line_off, uint8_t* out,
+                              int64_t out_bytes, hipStream_t stream);
 
 // single-linkage clusters at a cut-off (k_cluster.hip): unions of a tile's surviving entries / of a list of pairs in a lock-free
 // union-find over parent[0 .. n_nodes), and the roots of all nodes afterwards (two launches: flatten, then read)

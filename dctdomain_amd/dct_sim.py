@@ -3,6 +3,7 @@ fingerprints (``-dct.npz``), with the L1 distances computed on the GPU.
 
     python -m dctdomain_amd.dct_sim --dct X-dct.npz [--pair P | --db Y-dct.npz [--rank {global,domain}]] [--output F]
                                     [--pairfound F] [--top 5] [--threshold 0.25] [--min-domain X] [--min-global Y] [--cluster]
+                                    [--domains] [--dom X.dom] [--db-dom Y.dom]
 
 Same flags, same output text (src/dct-sim.py:179-211); ``--rank domain`` (not in the reference) orders database hits by
 DCTdomain instead of DCTglobal, and ``--min-domain`` / ``--min-global`` (not in the reference either, which ignores
@@ -28,6 +29,13 @@ Where the reference loops over protein pairs and, inside, over domain pairs in P
   ``--rank domain`` it ranks on DCTdomain instead: the tiles hold every protein pair's minimum over all fingerprint pairs
   (``dctfp_protein_min``), selected the same way;
 - ``pair_sim`` uploads the fingerprints of the proteins its pairs name and runs ``dctfp_pair_min`` on the pairs.
+``--domains`` (not in the reference) adds two fields to every result line: the fingerprint of each protein that DCTdomain came
+from -- the pair the reference's double loop (:42-50) ends on: the smallest L1, ties to the lowest row of the first protein, then
+of the second; ``-`` in both when no pair beats the loop's starting 0.  The scores then come from ``dctfp_pair_argmin`` instead
+of ``dctfp_pair_min`` (the same reads, the position of the minimum kept); the all-against-all goes through ``FilteredPairs``
+whatever the cut-offs and composes its lines with ``dctfp_pair_domain_lines``.  A fingerprint prints as its 1-based index within
+the protein, or, with the ``.dom`` file of the npz (``--dom`` / ``--db-dom``), as the residue ranges ``make_db`` wrote there
+(``whole`` for the unnamed whole-protein row).
 Scores are formed from the integer L1 values with the reference's arithmetic (int64 / 17000 in float64), so the printed
 floats are identical."""
 
@@ -39,13 +47,17 @@ import time
 
 import numpy as np
 
-from .similarity import (PROTEIN_MIN_MAX_D, LineIds, block_min, block_min_device, cluster_labels, l1_matrix, link_pairs, pair_line_offsets,
-                         pair_lines, pair_min, pair_min_device, protein_min, sim_lines, threshold_select, to_device_int8, tri_filter_count,
-                         tri_filter_fill, tri_link)
+from .similarity import (PROTEIN_MIN_MAX_D, LineIds, block_min, block_min_device, cluster_labels, l1_matrix, link_pairs, pair_argmin,
+                         pair_argmin_device, pair_domain_line_offsets, pair_domain_lines, pair_line_offsets, pair_lines, pair_min,
+                         pair_min_device, protein_min, sim_lines, threshold_select, to_device_int8, tri_filter_count, tri_filter_fill,
+                         tri_link)
 
 L1_FULL_SCALE = 17000      # src/dct-sim.py:24
 HEADER = '#prot1 prot2 sim-domain sim-global'
 CLUSTER_HEADER = '#representative member'
+DOMAIN_HEADER = HEADER + ' dom1 dom2'      # --domains
+NO_DOMAIN = '-'                            # no fingerprint pair scores above 0
+WHOLE = 'whole'                            # the whole-protein row a .dom file leaves unnamed
 
 
 def _sim(l1):
@@ -76,6 +88,65 @@ def domain_sim(dct_i: np.ndarray, dct_j: np.ndarray) -> tuple:
     """(DCTdomain, DCTglobal) of two proteins' fingerprint sets (src/dct-sim.py:28-50)."""
     mn, last = block_min(l1_matrix(dct_i, dct_j), [0, dct_i.shape[0]], [0, dct_j.shape[0]])
     return _scores(mn[0, 0], last[0, 0])
+
+
+def best_domain_pair(dct_i: np.ndarray, dct_j: np.ndarray) -> tuple:
+    """(DCTdomain, DCTglobal, pi, pj): ``domain_sim`` and the rows of ``dct_i`` / ``dct_j`` its loop ends on (src/dct-sim.py:42-50:
+    the first pair, in (pi, pj) order, of the largest similarity); ``pi = pj = None`` when no pair scores above 0."""
+    mn, last, arg_a, arg_b = pair_argmin(dct_i, [0, dct_i.shape[0]], dct_j, [0, dct_j.shape[0]], [(0, 0)])
+    none = arg_a[0] < 0
+    return _scores(mn[0], last[0]) + ((None, None) if none else (int(arg_a[0]), int(arg_b[0])))
+
+
+def read_dom_file(path: str) -> dict:
+    """{pid: [domain strings]} of a ``.dom`` file (``database.save_doms``: ``pid ndom d1;d2;...`` per line).  The last two
+    whitespace-separated fields are the count and the list, whatever stands before them is the pid; a repeated pid: the later
+    line.  ValueError for a line without those fields or whose count is not the length of its list."""
+    doms = {}
+    with open(path, encoding='utf8') as fh:
+        for number, text in enumerate(fh, 1):
+            if not text.strip():
+                continue
+            fields = text.rstrip('\r\n').rsplit(None, 2)
+            if len(fields) != 3 or not fields[1].isdigit():
+                raise ValueError(f'{path}:{number}: expected "pid ndom d1;d2;...", got {text.rstrip()!r}')
+            names = fields[2].split(';')
+            if len(names) != int(fields[1]):
+                raise ValueError(f'{path}:{number}: {fields[0]} declares {fields[1]} domains and lists {len(names)}')
+            doms[fields[0].lstrip()] = names
+    return doms
+
+
+def fingerprint_labels(sid, idx, doms: dict = None) -> list:
+    """What ``--domains`` prints for every fingerprint row of an npz, in row order.  ``doms`` None: the 1-based index of the row
+    within its protein.  Else (``read_dom_file`` of the npz's ``.dom``): the domain strings verbatim -- a protein of k > 0
+    fingerprints must have k names, or k - 1 with the last row, the whole protein, printing ``whole``; ValueError naming the protein
+    otherwise, also when it is absent from the file.  Proteins without fingerprints need no entry."""
+    counts = np.diff(np.asarray(idx, dtype=np.int64))
+    if doms is None:
+        return [str(r + 1) for k in counts.tolist() for r in range(k)]
+    labels = []
+    for name, k in zip(sid, counts.tolist()):
+        if k == 0:
+            continue
+        names = doms.get(f'{name}')
+        if names is None:
+            raise ValueError(f'protein {name} has {k} fingerprints and no line in the .dom file')
+        if len(names) == k:
+            labels += names
+        elif len(names) == k - 1:
+            labels += names + [WHOLE]
+        else:
+            raise ValueError(f'protein {name} has {k} fingerprints, the .dom file names {len(names)} domains (expected {k} or {k - 1})')
+    return labels
+
+
+def _labels_of(sid, idx, dom_path: str = None) -> list:
+    return fingerprint_labels(sid, idx, read_dom_file(dom_path) if dom_path else None)
+
+
+def _label(labels, first_row: int, arg: int) -> str:
+    return NO_DOMAIN if arg < 0 else labels[first_row + arg]
 
 
 def load_dct(filename: str, asmap=True) -> tuple:
@@ -316,19 +387,23 @@ def _compact(fps, idx, proteins):
     return fps[rows], sub_idx
 
 
-def pair_scores(fps, idx, pairs, max_rows: int = None):
+def pair_scores(fps, idx, pairs, max_rows: int = None, domains: bool = False):
     """(min, last) L1 of every (protein i, protein j) of ``pairs`` within one npz (``dctfp_pair_min``): only the fingerprints of
-    the proteins the pairs name go to the device, at most ``max_rows`` (``ProteinSearch.COL_ROWS``) of them at a time."""
+    the proteins the pairs name go to the device, at most ``max_rows`` (``ProteinSearch.COL_ROWS``) of them at a time.
+    ``domains``: (min, last, arg_i, arg_j) -- with the rows of the minimum within the two proteins, -1 = none
+    (``dctfp_pair_argmin``)."""
     pairs = np.asarray(pairs, dtype=np.int64).reshape(-1, 2)
-    mn = np.full(len(pairs), 0x7fffffff, dtype=np.int64)
-    last = mn.copy()
+    out = [np.full(len(pairs), 0x7fffffff, dtype=np.int64) for _ in range(2)]
+    if domains:
+        out += [np.full(len(pairs), -1, dtype=np.int64) for _ in range(2)]
     for k0, k1 in _pair_chunks(idx, pairs, max_rows or ProteinSearch.COL_ROWS):
         proteins, local = np.unique(pairs[k0:k1], return_inverse=True)
         rows, sub_idx = _compact(fps, idx, proteins)
         if len(rows):
             dev = to_device_int8(rows)
-            mn[k0:k1], last[k0:k1] = pair_min(dev, sub_idx, dev, sub_idx, local.reshape(-1, 2))
-    return mn, last
+            for o, v in zip(out, (pair_argmin if domains else pair_min)(dev, sub_idx, dev, sub_idx, local.reshape(-1, 2))):
+                o[k0:k1] = v
+    return tuple(out)
 
 
 class FilteredPairs:
@@ -347,14 +422,23 @@ class FilteredPairs:
        the other cut-off, if any, on those;
     4. the lines of what is left (``pair_lines``), out through two pinned buffers.
 
-    Nothing of size n x n exists anywhere; host memory beyond the data is O(n), one range's survivors and the two buffers."""
+    Nothing of size n x n exists anywhere; host memory beyond the data is O(n), one range's survivors and the two buffers.
+
+    ``labels`` (``--domains``: ``fingerprint_labels`` of the file) adds the domain pair to every line: step 3 takes
+    ``pair_argmin_device`` and keeps the two rows of the minimum, step 4 ``pair_domain_lines`` with the labels on the device (one
+    per fingerprint row and ``-``).  Without cut-offs both bounds keep every pair and the output is ``AllPairs``' with the two
+    fields added -- by the slower route: a protein-minimum tile, a filter that drops nothing and a second read of every pair's
+    fingerprints for the scores, where ``AllPairs`` reduces one distance matrix."""
 
     TEXT_BYTES = 1 << 28    # text of one range of rows
     COL_ROWS = 1 << 22      # fingerprints on the device at a time (the whole file stays there if it fits)
     TILE_INTS = 1 << 28     # int32 entries of one stripe's tile (1 GiB)
 
-    def __init__(self, sid, idx, fps, min_domain=None, min_global=None):
+    def __init__(self, sid, idx, fps, min_domain=None, min_global=None, labels=None):
         self.sid, self.idx, self.fps = sid, np.asarray(idx, dtype=np.int64), fps
+        self.row_labels = labels                                # (not `labels`: Clusters.labels() is a method)
+        if labels is not None and len(labels) != int(self.idx[-1]):
+            raise ValueError('labels must have one entry per fingerprint row')
         self.bound_domain = L1_FULL_SCALE if min_domain is None else sim_bound(min_domain)
         self.bound_global = L1_FULL_SCALE if min_global is None else sim_bound(min_global)
         self.route = 'global' if self.bound_global < L1_FULL_SCALE else 'domain'
@@ -428,7 +512,8 @@ class FilteredPairs:
             del tile                                            # (before the next one is made; the caller drops its own too)
 
     def chunks(self):
-        """Yields device int32 tensors (i, j, min L1, last L1) of the surviving pairs, range of rows by range, in output order."""
+        """Yields device int32 tensors (i, j, min L1, last L1) of the surviving pairs, range of rows by range, in output order; with
+        ``labels`` also (arg_i, arg_j), the rows of the minimum within the two proteins (-1: none)."""
         import torch
         n = len(self.idx) - 1
         if n < 2 or min(self.bound_domain, self.bound_global) < 0:
@@ -452,40 +537,57 @@ class FilteredPairs:
                 if m:
                     pi, pj = tri_filter_fill(tile[r0:r1], i0 + r0, col0, bound, count_dev[r0:r1], m,
                                              flags[0][r0:r1] if flags[0] is not None else None, flags[1])
+                    domains = self.row_labels is not None
                     if resident is not None:
-                        mn, last = pair_min_device(resident, idx_dev, resident, idx_dev, torch.stack([pi, pj], dim=1).contiguous())
+                        scores = (pair_argmin_device if domains else pair_min_device)(resident, idx_dev, resident, idx_dev,
+                                                                                      torch.stack([pi, pj], dim=1).contiguous())
                     else:
                         host = torch.stack([pi, pj], dim=1).cpu().numpy()
-                        mn, last = (torch.as_tensor(v.astype(np.int32), device=dev) for v in pair_scores(self.fps, self.idx, host, self.COL_ROWS))
+                        scores = tuple(torch.as_tensor(v.astype(np.int32), device=dev)
+                                       for v in pair_scores(self.fps, self.idx, host, self.COL_ROWS, domains=domains))
+                    chunk = (pi, pj) + tuple(scores)
                     if self.route == 'global' and self.bound_domain < L1_FULL_SCALE:      # (the other cut-off; the order stays)
-                        keep = mn.clamp(max=L1_FULL_SCALE) <= self.bound_domain
-                        pi, pj, mn, last = (t[keep].contiguous() for t in (pi, pj, mn, last))
-                    if pi.numel():
-                        yield pi, pj, mn, last
+                        keep = chunk[2].clamp(max=L1_FULL_SCALE) <= self.bound_domain
+                        chunk = tuple(t[keep].contiguous() for t in chunk)
+                    if chunk[0].numel():
+                        yield chunk
                 r0 = r1
             del tile
 
     def pairs(self):
-        """(i, j, min L1, last L1): int64 numpy arrays of the surviving pairs in output order (i ascending, then j)."""
+        """(i, j, min L1, last L1): int64 numpy arrays of the surviving pairs in output order (i ascending, then j); with ``labels``
+        also (arg_i, arg_j)."""
         import torch
         parts = [torch.stack(c, dim=0).cpu().numpy().astype(np.int64) for c in self.chunks()]
-        both = np.concatenate(parts, axis=1) if parts else np.zeros((4, 0), dtype=np.int64)
-        return both[0], both[1], both[2], both[3]
+        width = 4 if self.row_labels is None else 6
+        both = np.concatenate(parts, axis=1) if parts else np.zeros((width, 0), dtype=np.int64)
+        return tuple(both[k] for k in range(width))
 
     def write(self, sink):
         """Calls ``sink(memoryview)`` with the text of each range of rows that has any, in order."""
         import torch
-        ids = table = stream = None
+        ids = table = stream = labels = first_row = None
         pinned, pending, k = [None, None], None, 0
-        for pi, pj, mn, last in self.chunks():
+        for pi, pj, mn, last, *args in self.chunks():
             if ids is None:
                 ids = LineIds([f'{s}' for s in self.sid])
                 table = torch.as_tensor(score_table(), device=pi.device)
                 stream = torch.cuda.current_stream(pi.device)
-            off = pair_line_offsets(pi, pj, ids)
+                if self.row_labels is not None:                 # (one label per fingerprint row, then the "no pair" entry)
+                    labels = LineIds(list(self.row_labels) + [NO_DOMAIN], device=pi.device)
+                    first_row = torch.as_tensor(self.idx[:-1].astype(np.int32), device=pi.device)
+            if labels is not None:
+                la, lb = (torch.where(arg >= 0, first_row[p.long()] + arg, torch.full_like(arg, len(self.row_labels))).contiguous()
+                          for p, arg in zip((pi, pj), args))
+                off = pair_domain_line_offsets(pi, pj, la, lb, ids, labels)
+            else:
+                off = pair_line_offsets(pi, pj, ids)
             nbytes = int(off[-1])
             text = torch.empty(nbytes, dtype=torch.uint8, device=pi.device)
-            pair_lines(pi, pj, mn, last, ids, table, off, text)
+            if labels is not None:
+                pair_domain_lines(pi, pj, mn, last, la, lb, ids, labels, table, off, text)
+            else:
+                pair_lines(pi, pj, mn, last, ids, table, off, text)
             pin = pinned[k % 2]                                 # (written out by the host two ranges ago)
             if pin is None or pin.numel() < nbytes:
                 pin = pinned[k % 2] = torch.empty(max(nbytes, 1 << 16), dtype=torch.uint8, pin_memory=True)
@@ -583,6 +685,9 @@ class Clusters(FilteredPairs):
 
     Then ``cluster_labels`` on the device and one copy of n int32.  The text is composed on the host (``cluster_lines``), O(n)."""
 
+    def __init__(self, sid, idx, fps, min_domain=None, min_global=None):
+        super().__init__(sid, idx, fps, min_domain=min_domain, min_global=min_global)    # (no domain pairs: nothing is printed per pair)
+
     def labels(self) -> np.ndarray:
         n = len(self.idx) - 1
         if n < 2 or min(self.bound_domain, self.bound_global) < 0:
@@ -592,7 +697,7 @@ class Clusters(FilteredPairs):
         import torch
         parent = torch.arange(n, dtype=torch.int32, device=torch.device('cuda', torch.cuda.current_device()))
         if max(self.bound_domain, self.bound_global) < L1_FULL_SCALE:
-            for pi, pj, _, _ in self.chunks():
+            for pi, pj, *_ in self.chunks():
                 link_pairs(pi, pj, parent)
         else:
             for i0, _, tile, flags in self.tiles():
@@ -621,7 +726,9 @@ class ProteinSearch:
 
     The database goes to the device in protein groups of at most COL_ROWS fingerprints (a single group stays there between
     searches); the query side is tiled so that a distance tile holds at most TILE_INTS entries.  The groups' hit lists are
-    merged per query (``merge_candidates``).  ``search`` returns, per query, (database protein indices, min L1, last L1)."""
+    merged per query (``merge_candidates``).  ``search`` returns, per query, (database protein indices, min L1, last L1); with
+    ``domains=True`` also (row of the minimum within the query, within the database protein), -1 = none (step 3 through
+    ``pair_argmin``)."""
 
     COL_ROWS = 1 << 22      # fingerprints of the database on the device at a time (2 GB of int8 at 480 columns)
     TILE_INTS = 1 << 28     # int32 entries of one distance tile (1 GiB)
@@ -648,14 +755,14 @@ class ProteinSearch:
             self._resident[g] = entry
         return entry
 
-    def search(self, query_fps, query_idx, top: int, threshold: float, rank: str = 'global'):
+    def search(self, query_fps, query_idx, top: int, threshold: float, rank: str = 'global', domains: bool = False):
         if rank not in RANKS:
             raise ValueError(f'rank must be one of {RANKS}')
         top = int(top)
         qidx = np.asarray(query_idx, dtype=np.int64)
         nq, n_db = len(qidx) - 1, len(self.idx) - 1
         if nq == 0 or n_db == 0:
-            return [(np.zeros(0, dtype=np.int64),) * 3 for _ in range(nq)]
+            return [(np.zeros(0, dtype=np.int64),) * (5 if domains else 3) for _ in range(nq)]
         bound = sim_bound(threshold)
         top1 = max(top, 1)      # (top <= 0: the reference prints the threshold hits only -- trimmed after the merge)
         q_last, q_empty = _last_rows(query_fps, qidx)
@@ -678,9 +785,9 @@ class ProteinSearch:
         counts = np.array([len(h) for h in hits], dtype=np.int64)
         q_of = np.repeat(np.arange(nq, dtype=np.int64), counts)
         db_of = np.concatenate(hits).astype(np.int64) if nq else np.zeros(0, dtype=np.int64)
-        mn, last_l1 = self._pair_scores(query_fps, qidx, q_of, db_of)
+        scores = self._pair_scores(query_fps, qidx, q_of, db_of, domains)
         bounds = np.concatenate([[0], np.cumsum(counts)])
-        return [(db_of[a:b], mn[a:b], last_l1[a:b]) for a, b in zip(bounds[:-1], bounds[1:])]
+        return [(db_of[a:b],) + tuple(v[a:b] for v in scores) for a, b in zip(bounds[:-1], bounds[1:])]
 
     def _domain_parts(self, query_fps, qidx, q_empty, top1: int, bound: int, parts):
         """Step 1-2 of rank='domain': per database group (its fingerprints on the device) and query tile (at most TILE_INTS
@@ -710,10 +817,12 @@ class ProteinSearch:
                         parts[t0 + r].append((key[s], col[s] + p0))
                     del tile
 
-    def _pair_scores(self, query_fps, qidx, q_of, db_of):
-        """(min, last) L1 of the pairs (query q_of[k], database protein db_of[k]): per database group, per chunk of queries."""
-        mn = np.full(len(q_of), 0x7fffffff, dtype=np.int64)
-        last = mn.copy()
+    def _pair_scores(self, query_fps, qidx, q_of, db_of, domains: bool = False):
+        """(min, last) L1 of the pairs (query q_of[k], database protein db_of[k]): per database group, per chunk of queries.
+        ``domains``: (min, last, arg_q, arg_db) through ``pair_argmin``."""
+        out = [np.full(len(q_of), 0x7fffffff, dtype=np.int64) for _ in range(2)]
+        if domains:
+            out += [np.full(len(q_of), -1, dtype=np.int64) for _ in range(2)]
         for g, (p0, p1) in enumerate(self.groups):
             in_g = np.flatnonzero((db_of >= p0) & (db_of < p1))
             if len(in_g) == 0:
@@ -727,8 +836,9 @@ class ProteinSearch:
                     continue
                 qrows = to_device_int8(query_fps[qidx[c0]:qidx[c1]])
                 pairs = np.stack([q_of[sel] - c0, db_of[sel] - p0], axis=1)
-                mn[sel], last[sel] = pair_min(qrows, qidx[c0:c1 + 1] - qidx[c0], rows, sub_idx, pairs)
-        return mn, last
+                for o, v in zip(out, (pair_argmin if domains else pair_min)(qrows, qidx[c0:c1 + 1] - qidx[c0], rows, sub_idx, pairs)):
+                    o[sel] = v
+        return tuple(out)
 
 
 class Report:
@@ -771,7 +881,9 @@ def _reporting(fn=None, *, header: str = HEADER):
         *head, output = args
         if isinstance(output, Report):
             return fn(*head, output, **kw)
-        report = Report(output, header)
+        # (a report opened here for a call that asks for the domain pair carries the two extra column names)
+        wide = header == HEADER and any(kw.get(k) for k in ('domains', 'dom', 'db_dom'))
+        report = Report(output, DOMAIN_HEADER if wide else header)
         try:
             return fn(*head, report, **kw)
         finally:
@@ -781,10 +893,13 @@ def _reporting(fn=None, *, header: str = HEADER):
 
 
 @_reporting
-def pair_sim(npzfile: str, pairfile: str, pairfound: str, report: Report):
+def pair_sim(npzfile: str, pairfile: str, pairfound: str, report: Report, domains: bool = False, dom: str = None):
     """Similarity of every listed protein pair (src/dct-sim.py:86-124).  Lines starting with ``#``
-    are comments (copied to ``pairfound``); pairs with an unknown protein are counted, not printed."""
+    are comments (copied to ``pairfound``); pairs with an unknown protein are counted, not printed.  ``domains`` / ``dom`` (the
+    ``.dom`` of the npz): the best domain pair behind the scores."""
     sid, idx, fps = _load_npz(npzfile)
+    domains = domains or dom is not None
+    labels = _labels_of(sid, idx, dom) if domains else None
     where = {name: i for i, name in enumerate(sid)}           # a repeated id: the later one, like a dict of arrays
     listed = 0
     kept, found = [], []
@@ -799,10 +914,11 @@ def pair_sim(npzfile: str, pairfile: str, pairfound: str, report: Report):
                 continue
             found.append((first, second, where[first], where[second]))
             kept.append(text)
-    mn, last = pair_scores(fps, idx, [(i, j) for _, _, i, j in found])
-    for (first, second, _, _), m, l in zip(found, mn, last):
+    mn, last, *args = pair_scores(fps, idx, [(i, j) for _, _, i, j in found], domains=domains)
+    for k, ((first, second, i, j), m, l) in enumerate(zip(found, mn, last)):
         maxs, s = _scores(m, l)
-        report.line(f'{first} {second} {maxs} {s}')
+        tail = f' {_label(labels, idx[i], args[0][k])} {_label(labels, idx[j], args[1][k])}' if domains else ''
+        report.line(f'{first} {second} {maxs} {s}{tail}')
     print(f'total pair {pairfile} found {len(found)} (not found: {listed - len(found)})')
     if pairfound:
         with open(pairfound, 'w', encoding='utf8') as out:
@@ -811,28 +927,37 @@ def pair_sim(npzfile: str, pairfile: str, pairfound: str, report: Report):
 
 
 @_reporting
-def db_search(npzfile: str, dbfile: str, top: int, threshold: float, report: Report, rank: str = 'global'):
+def db_search(npzfile: str, dbfile: str, top: int, threshold: float, report: Report, rank: str = 'global', domains: bool = False,
+              dom: str = None, db_dom: str = None):
     """Hits of every query protein in a fingerprint database, best DCTglobal first (stable); the first
     ``top`` always, further ones while they reach ``threshold`` (src/dct-sim.py:126-156).  ``rank='domain'``: best
-    DCTdomain first, and the threshold applies to DCTdomain (the same loop with the domain score as the key)."""
+    DCTdomain first, and the threshold applies to DCTdomain (the same loop with the domain score as the key).  ``domains`` /
+    ``dom`` / ``db_dom`` (the ``.dom`` files of the two npz): the best domain pair behind the scores of every printed hit."""
     sid, idx, fps = _load_npz(npzfile)
     db_sid, db_idx, db_fps = _load_npz(dbfile)
-    hits = ProteinSearch(db_fps, db_idx).search(fps, idx, top, threshold, rank=rank)
-    for query, (cols, mn, last) in zip(sid, hits):
-        for q, m, l in zip(cols, mn, last):
+    domains = domains or dom is not None or db_dom is not None
+    if domains:
+        labels, db_labels = _labels_of(sid, idx, dom), _labels_of(db_sid, db_idx, db_dom)
+    hits = ProteinSearch(db_fps, db_idx).search(fps, idx, top, threshold, rank=rank, domains=domains)
+    for i, (query, (cols, mn, last, *args)) in enumerate(zip(sid, hits)):
+        for k, (q, m, l) in enumerate(zip(cols, mn, last)):
             maxs, s = _scores(m, l)
-            report.line(f'{query} {db_sid[q]} {maxs} {s}')
+            tail = f' {_label(labels, idx[i], args[0][k])} {_label(db_labels, db_idx[q], args[1][k])}' if domains else ''
+            report.line(f'{query} {db_sid[q]} {maxs} {s}{tail}')
 
 
 @_reporting
-def all_sim(npzfile: str, report: Report, min_domain: float = None, min_global: float = None):
+def all_sim(npzfile: str, report: Report, min_domain: float = None, min_global: float = None, domains: bool = False, dom: str = None):
     """All-against-all, upper triangle (src/dct-sim.py:158-176), streamed from the device (``AllPairs``).  With ``min_domain`` /
-    ``min_global``: only the pairs whose DCTdomain / DCTglobal is not below them (``FilteredPairs``)."""
+    ``min_global``: only the pairs whose DCTdomain / DCTglobal is not below them (``FilteredPairs``).  ``domains`` / ``dom`` (the
+    ``.dom`` of the npz): the best domain pair behind the scores -- ``FilteredPairs`` with or without cut-offs."""
     sid, idx, fps = _load_npz(npzfile)
-    if min_domain is None and min_global is None:
+    domains = domains or dom is not None
+    if min_domain is None and min_global is None and not domains:
         AllPairs(sid, idx, fps).write(report.raw)
     else:
-        FilteredPairs(sid, idx, fps, min_domain=min_domain, min_global=min_global).write(report.raw)
+        labels = _labels_of(sid, idx, dom) if domains else None
+        FilteredPairs(sid, idx, fps, min_domain=min_domain, min_global=min_global, labels=labels).write(report.raw)
 
 
 @_reporting(header=CLUSTER_HEADER)
@@ -850,13 +975,21 @@ RANKS = ('global', 'domain')
 class _Parser(argparse.ArgumentParser):
     """``--rank`` orders database hits: it is an error without ``--db`` or beside ``--pair`` (which takes precedence).
     ``--min-domain`` / ``--min-global`` cut the all-against-all output: an error beside ``--pair`` or ``--db``.
-    ``--cluster`` joins the pairs that pass into clusters: an error beside ``--pair`` or ``--db``, or without a cut-off."""
+    ``--cluster`` joins the pairs that pass into clusters: an error beside ``--pair`` or ``--db``, or without a cut-off.
+    ``--dom`` / ``--db-dom`` imply ``--domains``; ``--db-dom`` is an error without ``--db``, ``--domains`` beside ``--cluster``
+    (a cluster line has no scores to explain)."""
 
     def parse_known_args(self, args=None, namespace=None):
         ns, rest = super().parse_known_args(args, namespace)
         if getattr(ns, 'rank', None) is not None and (ns.pair or not ns.db):
             self.error('--rank applies to database search (--db) only, not to --pair or all-against-all')
+        if getattr(ns, 'db_dom', None) is not None and not ns.db:
+            self.error('--db-dom names the .dom file of --db: it needs --db')
+        if getattr(ns, 'dom', None) is not None or getattr(ns, 'db_dom', None) is not None:
+            ns.domains = True
         if getattr(ns, 'cluster', False):
+            if getattr(ns, 'domains', False):
+                self.error('--domains (--dom, --db-dom) explains the scores of result lines: not with --cluster')
             if ns.pair or ns.db:
                 self.error('--cluster applies to all-against-all only, not to --pair or --db')
             if ns.min_domain is None and ns.min_global is None:
@@ -887,22 +1020,29 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument('--cluster', action='store_true',
                     help='all-against-all with a cut-off: print single-linkage clusters (one "representative member" line per '
                          'protein) instead of the pairs')
+    # (absent from the namespace unless given: a command line without them parses to what it always did)
+    ap.add_argument('--domains', action='store_true', default=argparse.SUPPRESS,
+                    help='add two fields to every result line: the fingerprint of each protein that DCTdomain came from (its '
+                         '1-based index within the protein; "-" when no pair scores above 0)')
+    ap.add_argument('--dom', metavar='FILE', default=argparse.SUPPRESS, help='the .dom file of --dct: print residue ranges instead of indices (implies --domains)')
+    ap.add_argument('--db-dom', metavar='FILE', default=argparse.SUPPRESS, help='the .dom file of --db, likewise (implies --domains)')
     return ap
 
 
 def main(argv=None):
     t_start = time.time()
     args = build_parser().parse_args(argv)
-    report = Report(args.output, CLUSTER_HEADER if args.cluster else HEADER)
+    domains, dom, db_dom = (getattr(args, k, None) for k in ('domains', 'dom', 'db_dom'))
+    report = Report(args.output, CLUSTER_HEADER if args.cluster else DOMAIN_HEADER if domains else HEADER)
     t_work = time.time()
     if args.pair:
-        pair_sim(args.dct, args.pair, args.pairfound, report)
+        pair_sim(args.dct, args.pair, args.pairfound, report, domains=bool(domains), dom=dom)
     elif args.db:
-        db_search(args.dct, args.db, args.top, args.threshold, report, rank=args.rank or 'global')
+        db_search(args.dct, args.db, args.top, args.threshold, report, rank=args.rank or 'global', domains=bool(domains), dom=dom, db_dom=db_dom)
     elif args.cluster:
         cluster_sim(args.dct, report, min_domain=args.min_domain, min_global=args.min_global)
     else:
-        all_sim(args.dct, report, min_domain=args.min_domain, min_global=args.min_global)
+        all_sim(args.dct, report, min_domain=args.min_domain, min_global=args.min_global, domains=bool(domains), dom=dom)
     report.close()
     t_end = time.time()
     print(f'total time used {t_end - t_start:.1f}s')

@@ -192,6 +192,57 @@ def pair_min_device(a: torch.Tensor, idx_a: torch.Tensor, b: torch.Tensor, idx_b
     return mn, last
 
 
+def pair_argmin(a, idx_a, b, idx_b, pairs):
+    """``pair_min`` with the fingerprint pair the minimum came from (``dctfp_pair_argmin``): (min, last, arg_a, arg_b) int64 numpy
+    arrays, ``arg_a`` / ``arg_b`` = rows counted from 0 within the two proteins, ties to the lowest ``arg_a``, then the lowest
+    ``arg_b``; -1 in both when the minimum is 17000 or more or a protein has no fingerprints (the reference's loop keeps no pair
+    there, src/dct-sim.py:42-50)."""
+    pairs = np.ascontiguousarray(np.asarray(pairs, dtype=np.int64).reshape(-1, 2))
+    ia, ib = np.asarray(idx_a, dtype=np.int64), np.asarray(idx_b, dtype=np.int64)
+    npa, npb = len(ia) - 1, len(ib) - 1
+    ta, tb = to_device_int8(a), to_device_int8(b)
+    if ta.dim() != 2 or tb.dim() != 2 or ta.shape[1] != tb.shape[1]:
+        raise ValueError('fingerprint sets must be 2-D with equal width')
+    for idx, rows in ((ia, ta.shape[0]), (ib, tb.shape[0])):    # (the kernel trusts the prefix arrays: check them here)
+        if len(idx) < 1 or idx[0] < 0 or idx[-1] > rows or (np.diff(idx) < 0).any():
+            raise ValueError('idx must be a non-decreasing prefix array within its fingerprint matrix')
+    if len(pairs) and (pairs[:, 0].min() < 0 or pairs[:, 0].max() >= npa or pairs[:, 1].min() < 0 or pairs[:, 1].max() >= npb):
+        raise IndexError('protein index out of range')
+    n = len(pairs)
+    if n == 0 or ta.shape[0] == 0 or tb.shape[0] == 0:          # (no fingerprint on a side: every pair is empty)
+        full, none = np.full(n, 0x7fffffff, dtype=np.int64), np.full(n, -1, dtype=np.int64)
+        return full, full.copy(), none, none.copy()
+    dev = ta.device
+    tp = torch.as_tensor(pairs.astype(np.int32), device=dev)
+    mn, last, arg_a, arg_b = pair_argmin_device(ta, _device_int64(ia, dev), tb, _device_int64(ib, dev), tp)
+    return _pair_to_host(mn, last) + _pair_to_host(arg_a, arg_b)
+
+
+def pair_argmin_device(a: torch.Tensor, idx_a: torch.Tensor, b: torch.Tensor, idx_b: torch.Tensor, pairs: torch.Tensor):
+    """``pair_argmin`` with everything on the device already (``pair_min_device``'s arguments and guarantees).  Returns device int32
+    (min, last, arg_a, arg_b); a pair index out of range gives -1 in all four (the kernel's check)."""
+    if pairs.dtype != torch.int32 or pairs.dim() != 2 or pairs.shape[1] != 2 or not pairs.is_contiguous():
+        raise ValueError('pairs must be a contiguous int32 (n, 2) device tensor')
+    if a.dtype != torch.int8 or b.dtype != torch.int8 or a.dim() != 2 or b.dim() != 2 or a.shape[1] != b.shape[1]:
+        raise ValueError('fingerprint sets must be 2-D int8 with equal width')
+    if idx_a.dtype != torch.int64 or idx_b.dtype != torch.int64 or not (idx_a.is_contiguous() and idx_b.is_contiguous()):
+        raise ValueError('prefix arrays must be contiguous int64 device tensors')
+    n, dev = pairs.shape[0], pairs.device
+    mn = torch.full((n,), 0x7fffffff, dtype=torch.int32, device=dev)
+    last = torch.full((n,), 0x7fffffff, dtype=torch.int32, device=dev)
+    arg_a = torch.full((n,), -1, dtype=torch.int32, device=dev)
+    arg_b = torch.full((n,), -1, dtype=torch.int32, device=dev)
+    if n == 0 or a.shape[0] == 0 or b.shape[0] == 0:            # (no fingerprint on a side: every pair is empty)
+        return mn, last, arg_a, arg_b
+    ctx = _lib.get_context(dev.index)
+    stream = torch.cuda.current_stream(dev)
+    _lib.check(ctx._lib.dctfp_pair_argmin(ctx.handle, pairs.data_ptr(), n, a.data_ptr(), a.stride(0) if a.shape[0] > 1 else a.shape[1],
+                                          idx_a.data_ptr(), idx_a.numel() - 1, b.data_ptr(), b.stride(0) if b.shape[0] > 1 else b.shape[1],
+                                          idx_b.data_ptr(), idx_b.numel() - 1, a.shape[1], mn.data_ptr(), last.data_ptr(),
+                                          arg_a.data_ptr(), arg_b.data_ptr(), C.c_void_p(stream.cuda_stream)))
+    return mn, last, arg_a, arg_b
+
+
 def protein_min(a, idx_a, b, idx_b, out: torch.Tensor = None) -> torch.Tensor:
     """int32 (npa, npb) on the device: the smallest L1 over all fingerprint pairs of every (protein of ``a``, protein of ``b``)
     -- DCTdomain's distance, ``block_min(l1_matrix(a, b), idx_a, idx_b)[0]`` without the distance matrix
@@ -474,6 +525,42 @@ def pair_lines(pi: torch.Tensor, pj: torch.Tensor, mn: torch.Tensor, last: torch
     _lib.check(ctx._lib.dctfp_pair_lines(ctx.handle, n, pi.data_ptr(), pj.data_ptr(), mn.data_ptr(), last.data_ptr(), ids.bytes_dev.data_ptr(),
                                          ids.off_dev.data_ptr(), len(ids.off) - 1, table.data_ptr(), line_off.data_ptr(), out.data_ptr(),
                                          out.numel(), stream))
+
+
+def pair_domain_line_offsets(pi: torch.Tensor, pj: torch.Tensor, la: torch.Tensor, lb: torch.Tensor, ids: LineIds,
+                             labels: LineIds) -> torch.Tensor:
+    """Device int64 (n + 1): where the ``pair_domain_lines`` lines of the pairs (pi[n], pj[n]) with labels (la[n], lb[n]) start --
+    the prefix sum of len_i + len_j + 14 + len_label_a + len_label_b + 2; the last entry is the text's size."""
+    off = torch.zeros(pi.numel() + 1, dtype=torch.int64, device=pi.device)
+    if pi.numel():
+        torch.cumsum(ids.lens_dev[pi.long()] + ids.lens_dev[pj.long()] + labels.lens_dev[la.long()] + labels.lens_dev[lb.long()] + 16, 0,
+                     out=off[1:])
+    return off
+
+
+def pair_domain_lines(pi: torch.Tensor, pj: torch.Tensor, mn: torch.Tensor, last: torch.Tensor, la: torch.Tensor, lb: torch.Tensor,
+                      ids: LineIds, labels: LineIds, table: torch.Tensor, line_off: torch.Tensor, out: torch.Tensor):
+    """``pair_lines`` with the domain pair behind the scores: line n = ``"{id of pi[n]} {id of pj[n]} {a} {b} {label la[n]} {label
+    lb[n]}\\n"`` from byte ``line_off[n]`` of ``out`` (``dctfp_pair_domain_lines``).  ``labels``: the label table of the file as a
+    ``LineIds`` -- one entry per fingerprint row, then the "no pair" entry; ``la`` / ``lb``: device int32 indices into it;
+    ``line_off``: ``pair_domain_line_offsets``.  The kernel skips a line that names a protein outside ``ids``, a label outside
+    ``labels`` or that ends beyond ``out``."""
+    n = pi.numel()
+    for t in (pi, pj, mn, last, la, lb):
+        if t.dtype != torch.int32 or t.numel() != n or not t.is_contiguous() or t.device != out.device:
+            raise ValueError('pi / pj / mn / last / la / lb must be contiguous int32 device tensors of one length')
+    if line_off.dtype != torch.int64 or line_off.numel() < n or not line_off.is_contiguous() or line_off.device != out.device:
+        raise ValueError('line_off must be a contiguous int64 device tensor with an entry per line')
+    if table.dtype != torch.uint8 or table.numel() != 2 * 17002 * 5 or out.dtype != torch.uint8 or not out.is_contiguous():
+        raise ValueError('table must be uint8 (2, 17002, 5) and out a contiguous uint8 buffer')
+    if n == 0:
+        return
+    ctx = _lib.get_context(out.device.index)
+    stream = C.c_void_p(torch.cuda.current_stream(out.device).cuda_stream)
+    _lib.check(ctx._lib.dctfp_pair_domain_lines(ctx.handle, n, pi.data_ptr(), pj.data_ptr(), mn.data_ptr(), last.data_ptr(), la.data_ptr(),
+                                                lb.data_ptr(), ids.bytes_dev.data_ptr(), ids.off_dev.data_ptr(), len(ids.off) - 1,
+                                                labels.bytes_dev.data_ptr(), labels.off_dev.data_ptr(), len(labels.off) - 1,
+                                                table.data_ptr(), line_off.data_ptr(), out.data_ptr(), out.numel(), stream))
 
 
 KNN_MAX_K = 1024     # dctfp_l1_knn's limits: larger k or wider rows take l1_matrix + row_select

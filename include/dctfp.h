@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define DCTFP_VERSION 104 /* 0.1.4: dctfp_tri_link, dctfp_link_pairs, dctfp_cluster_labels */
+#define DCTFP_VERSION 105 /* 0.1.5: dctfp_pair_argmin, dctfp_pair_domain_lines */
 
 #define DCTFP_OK 0
 #define DCTFP_ERR_INVALID (-1) /* bad argument (null pointer, piece outside its sequence, ...) */
@@ -311,6 +311,18 @@ int dctfp_pair_min(dctfp_ctx* ctx, const int32_t* pairs, int64_t n_pairs, const 
                    const int8_t* b, int64_t ldb, const int64_t* idx_b, int64_t npb, int32_t d, int32_t* out_min, int32_t* out_last,
                    void* stream);
 
+/* dctfp_pair_min that also says WHICH fingerprint pair gave DCTdomain (dct-sim --domains): the same arguments, out_min and
+ * out_last exactly as there (0x7fffffff for a protein without fingerprints, -1 for a pair index out of range), and
+ * out_arg_a[p] / out_arg_b[p] (device int32) = the rows, counted from 0 within protein pairs[2p] of a and protein pairs[2p+1] of
+ * b, of the fingerprint pair with the smallest L1.  The reference's loop (src/dct-sim.py:42-50) runs over the rows of the first
+ * protein, then of the second, and replaces its maximum -- started at 0 -- only on `s > maxs`: equal L1 values go to the lowest
+ * row of a, then the lowest row of b, and there is NO best pair, -1 in both, when the smallest L1 is 17000 or more (similarity 0
+ * is never > 0), when either protein has no fingerprint, or when the pair index is out of range.  Reads the same bytes as
+ * dctfp_pair_min.  DCTFP_ERR_LIMIT above 2^31 - 1 proteins on a side; a protein must have fewer than 2^31 fingerprints. */
+int dctfp_pair_argmin(dctfp_ctx* ctx, const int32_t* pairs, int64_t n_pairs, const int8_t* a, int64_t lda, const int64_t* idx_a, int64_t npa,
+                      const int8_t* b, int64_t ldb, const int64_t* idx_b, int64_t npb, int32_t d, int32_t* out_min, int32_t* out_last,
+                      int32_t* out_arg_a, int32_t* out_arg_b, void* stream);
+
 /* DCTdomain's L1 for every protein pair of two fingerprint sets, straight from the fingerprints (dct-sim --db --rank domain):
  *     out[pa * ldo + pb] = min over rows r of protein pa (idx_a) and rows s of protein pb (idx_b) of
  *                          sum_k |a[r * lda + k] - b[s * ldb + k]|,  k < d
@@ -387,6 +399,19 @@ int dctfp_tri_filter_fill(dctfp_ctx* ctx, const int32_t* tile, int64_t n_rows, i
 int dctfp_pair_lines(dctfp_ctx* ctx, int64_t n_lines, const int32_t* pi, const int32_t* pj, const int32_t* mn, const int32_t* last,
                      const uint8_t* ids, const int64_t* id_off, int64_t n_ids, const char* table, const int64_t* line_off, uint8_t* out,
                      int64_t out_bytes, void* stream);
+
+/* dctfp_pair_lines with the domain pair behind the scores (dct-sim --domains): line n =
+ * "{id_i} {id_j} {a} {b} {label_a} {label_b}\n", everything up to b as in dctfp_pair_lines (and dctfp_sim_lines: ids, id_off,
+ * the score table).  labels / label_off (device bytes and n_labels + 1 int64 prefix offsets) = the label table of the file: one
+ * UTF-8 entry per fingerprint row and, last, one sentinel entry ("-") for "no domain pair"; la[n] / lb[n] (device int32) pick
+ * the two entries -- a global fingerprint row (the protein's first row + dctfp_pair_argmin's argument) or the sentinel.
+ * line_off[n] = the caller's prefix sum of len_i + len_j + 14 + len_label_a + len_label_b + 2.  Any id or label length, any
+ * alignment of out.  A line with a protein index outside [0, n_ids), a label index outside [0, n_labels) or an end beyond
+ * out_bytes is skipped, nothing else is written.  DCTFP_ERR_LIMIT above 2^31 lines per call. */
+int dctfp_pair_domain_lines(dctfp_ctx* ctx, int64_t n_lines, const int32_t* pi, const int32_t* pj, const int32_t* mn, const int32_t* last,
+                            const int32_t* la, const int32_t* lb, const uint8_t* ids, const int64_t* id_off, int64_t n_ids,
+                            const uint8_t* labels, const int64_t* label_off, int64_t n_labels, const char* table, const int64_t* line_off,
+                            uint8_t* out, int64_t out_bytes, void* stream);
 
 /* Single-linkage clusters at a cut-off (dct-sim --cluster; not in the reference): the connected components of the graph whose
  * edges are the pairs dctfp_tri_filter_count / dctfp_tri_filter_fill select, joined on the device instead of listed.

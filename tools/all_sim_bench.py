@@ -5,6 +5,7 @@
     python tools/all_sim_bench.py --part scale --n 1000000 --min-global 0.5   # the same with cut-offs (dct_sim.FilteredPairs)
     python tools/all_sim_bench.py --part filter --n 50000 [--min-domain 0.5]  # cut-offs beside the unfiltered run, one process
     python tools/all_sim_bench.py --part cluster --n 50000 --families 500 --family-size 100 --min-domain 0.5   # --cluster beside the cut-offs
+    python tools/all_sim_bench.py --part domains --n 50000 --families 500 --family-size 100 --min-domain 0.5   # --domains beside the same cut-offs
 
 `filter` loads one synthetic file and runs, after the load and a warm-up on a small file, the unfiltered path (AllPairs, to
 /dev/null as `scale` does) and the path with cut-offs; events around the device steps of the second (the tile: protein_min or
@@ -14,6 +15,8 @@ copies of others first: random proteins alone leave nothing above a cut-off.
 and runs, after a warm-up of both on a small file, --repeat times each: the path with cut-offs (FilteredPairs, to /dev/null) and
 the clustering at the same cut-offs (Clusters); events around the device steps of the latter (tile / link / labels), the host
 text timed apart.
+`domains` is `cluster`'s procedure for --domains: the path with cut-offs without the flag, then with it (labels = the 1-based index
+of a fingerprint within its protein), --repeat times each in that order, events around the device steps of the second.
 `scale` writes a synthetic -dct.npz (about 4.5 fingerprints per protein, 17-character ids) and runs the new path in a child
 process per sink (and one that only initialises the GPU: the RSS floor), so that the child's peak RSS (ru_maxrss of RUSAGE_CHILDREN, as tools/run_with_rss.py) is that of the run
 alone.  The child also measures the pinned device-to-host copy rate of one TEXT_BYTES buffer.  The file run is skipped when
@@ -297,6 +300,78 @@ def part_cluster(args):
             'link_over_tile': round(ms.get('link', 0.0) / ms['tile'], 4) if ms.get('tile') else None}
 
 
+def part_domains(args):
+    """One process: FilteredPairs to /dev/null without and with the domain pair on the same loaded file, --repeat times each after
+    a warm-up of both on a small one; device time of the second by step."""
+    import torch
+    from dctdomain_amd import dct_sim
+    min_domain = args.min_domain if args.min_domain is not None or args.min_global is not None else 0.5
+    with tempfile.TemporaryDirectory(dir=args.dir) as tmp:
+        small, path = os.path.join(tmp, 'w-dct.npz'), os.path.join(tmp, 'f-dct.npz')
+        synth(small, 2000, 5)
+        synth(path, args.n, 7)
+        wsid, widx, wfps = dct_sim._load_npz(small)
+        sid, idx, fps = dct_sim._load_npz(path)
+    widx, wfps = plant_families(widx, wfps, 10, 10)
+    if args.families:
+        idx, fps = plant_families(idx, fps, args.families, args.family_size)
+    t0 = time.perf_counter()
+    labels = dct_sim.fingerprint_labels(sid, idx)
+    t_labels = time.perf_counter() - t0
+    spans = {}
+
+    def timed(name, label):
+        fn = getattr(dct_sim, name)
+
+        def run(*a, **k):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            out = fn(*a, **k)
+            e1.record()
+            spans.setdefault(label, []).append((e0, e1))
+            return out
+        setattr(dct_sim, name, run)
+        return fn
+    written, kept = [0], [0]
+    with open(os.devnull, 'wb', buffering=0) as fh:
+        def sink(mv):
+            fh.write(mv)
+            written[0] += len(mv)
+            kept[0] += bytes(mv).count(b'\n')
+        dct_sim.FilteredPairs(wsid, widx, wfps, min_domain, args.min_global).write(sink)
+        dct_sim.FilteredPairs(wsid, widx, wfps, min_domain, args.min_global, labels=dct_sim.fingerprint_labels(wsid, widx)).write(sink)
+        torch.cuda.synchronize()
+        t_plain, t_dom, device_ms, sizes = [], [], [], {}
+        for flagged in (False, True):
+            if flagged:
+                steps = (('protein_min', 'tile'), ('l1_matrix', 'tile'), ('tri_filter_count', 'filter'), ('tri_filter_fill', 'filter'),
+                         ('pair_argmin_device', 'pair_argmin'), ('pair_domain_line_offsets', 'lines'), ('pair_domain_lines', 'lines'))
+                real = [(name, timed(name, label)) for name, label in steps]
+            for _ in range(args.repeat):
+                spans.clear()
+                written[0] = kept[0] = 0
+                fp = dct_sim.FilteredPairs(sid, idx, fps, min_domain, args.min_global, labels=labels if flagged else None)
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                fp.write(sink)
+                torch.cuda.synchronize()
+                (t_dom if flagged else t_plain).append(time.perf_counter() - t0)
+                sizes[flagged] = (kept[0], written[0])
+                if flagged:
+                    device_ms.append({label: round(sum(a.elapsed_time(b) for a, b in ev), 3) for label, ev in spans.items()})
+        for name, fn in real:
+            setattr(dct_sim, name, fn)
+    n = len(sid)
+    med = lambda v: sorted(v)[len(v) // 2]   # noqa: E731
+    return {'part': 'domains', 'n': n, 'fingerprints': int(idx[-1]), 'pairs': n * (n - 1) // 2, 'families': args.families,
+            'family_size': args.family_size, 'min_domain': min_domain, 'min_global': args.min_global, 'route': fp.route,
+            'lines': sizes[False][0], 'text_bytes': sizes[False][1], 'domain_lines': sizes[True][0], 'domain_text_bytes': sizes[True][1],
+            'labels_host_s': round(t_labels, 3), 'plain_s': [round(t, 3) for t in t_plain], 'domains_s': [round(t, 3) for t in t_dom],
+            'plain_median_s': round(med(t_plain), 3), 'domains_median_s': round(med(t_dom), 3),
+            'plain_spread_s': round(max(t_plain) - min(t_plain), 3), 'domains_over_plain': round(med(t_dom) / med(t_plain), 3),
+            'device_ms_of_median_run': device_ms[t_dom.index(med(t_dom))], 'device_ms_all': device_ms}
+
+
 def part_base(args):
     """(child) a process that has only initialised the GPU and run one small distance tile: the RSS floor of the run."""
     import torch
@@ -349,21 +424,21 @@ def part_scale(args):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument('--part', required=True, choices=['compare', 'scale', 'filter', 'cluster', 'run', 'base'])
+    ap.add_argument('--part', required=True, choices=['compare', 'scale', 'filter', 'cluster', 'domains', 'run', 'base'])
     ap.add_argument('--n', type=int, default=2000)
     ap.add_argument('--dir', default=None, help='where the npz and the text file go (local disk)')
     ap.add_argument('--npz')
     ap.add_argument('--sink')
     ap.add_argument('--timeout', type=float, default=1200)
     ap.add_argument('--planted', type=int, default=1000, help='filter: fingerprints overwritten with near copies of others')
-    ap.add_argument('--families', type=int, default=0, help='cluster: families of near copies planted in the file')
+    ap.add_argument('--families', type=int, default=0, help='cluster / domains: families of near copies planted in the file')
     ap.add_argument('--family-size', type=int, default=100, help='cluster: proteins per planted family')
-    ap.add_argument('--repeat', type=int, default=3, help='cluster: runs of each path')
+    ap.add_argument('--repeat', type=int, default=3, help='cluster / domains: runs of each path')
     ap.add_argument('--min-domain', type=float, default=None, help='scale / filter: print the pairs whose DCTdomain is not below this')
     ap.add_argument('--min-global', type=float, default=None, help='scale / filter: print the pairs whose DCTglobal is not below this')
     ap.add_argument('--out')
     args = ap.parse_args()
-    res = {'compare': part_compare, 'scale': part_scale, 'filter': part_filter, 'cluster': part_cluster, 'run': part_run, 'base': part_base}[args.part](args)
+    res = {'compare': part_compare, 'scale': part_scale, 'filter': part_filter, 'cluster': part_cluster, 'domains': part_domains, 'run': part_run, 'base': part_base}[args.part](args)
     line = json.dumps(res)
     print(line)
     if args.out:

@@ -3,6 +3,7 @@
     python tools/protein_search_bench.py --part search  [--db 1000000 --queries 10000]   # db_search, end to end after the load
     python tools/protein_search_bench.py --part kernels [--db 1000000]                    # selection kernels, dctfp_pair_min
     python tools/protein_search_bench.py --part blocks  [--old-db 100000 --old-queries 2000]  # the block-matrix path, and the new one
+    python tools/protein_search_bench.py --part argmin  [--db 1000000 --repeat 5]         # dctfp_pair_argmin beside dctfp_pair_min
 
 Each part is its own process (run each under its own time limit).  Data: random int8 fingerprints, 1-12 domains + the whole
 protein per protein, values in [-48, 48] (unrelated proteins at L1 ~ 15 000: similarity 0.1, below the 0.25 threshold) and
@@ -174,6 +175,54 @@ def part_kernels(a):
             'pair_min_sad_gb_s': sad_bytes / ms_pairs / 1e6}
 
 
+def part_argmin(a):
+    """dctfp_pair_argmin beside dctfp_pair_min on the 1 M random pairs of `kernels` (the same data, seeds and launch arguments), in
+    one process: --repeat rounds of (pair_min x 5, pair_argmin x 5), so that each list shows the run-to-run spread of its kernel
+    under the same conditions; every pair's outputs compared between the two, a sample against numpy."""
+    import ctypes as C
+    import torch
+    from dctdomain_amd import _lib
+    from dctdomain_amd.similarity import to_device_int8
+    idx, dct = synth(a.db, 1)
+    q_idx, q_dct = synth(a.queries, 2)
+    plant(q_idx, q_dct, idx, dct, a.planted, 3)
+    dev = torch.device('cuda')
+    ctx = _lib.get_context(0)
+    stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    rng = np.random.default_rng(7)
+    n_pairs = a.pairs
+    pairs = np.stack([rng.integers(0, len(q_idx) - 1, size=n_pairs), rng.integers(0, a.db, size=n_pairs)], axis=1)
+    da, db = to_device_int8(q_dct), to_device_int8(dct)
+    ia_d, ib_d = torch.as_tensor(q_idx, device=dev), torch.as_tensor(idx, device=dev)
+    pairs_d = torch.as_tensor(pairs.astype(np.int32), device=dev)
+    out = [torch.empty(n_pairs, dtype=torch.int32, device=dev) for _ in range(6)]
+    head = (ctx.handle, pairs_d.data_ptr(), n_pairs, da.data_ptr(), 480, ia_d.data_ptr(), len(q_idx) - 1, db.data_ptr(), 480, ib_d.data_ptr(),
+            a.db, 480)
+
+    def run_min():
+        _lib.check(ctx._lib.dctfp_pair_min(*head, out[0].data_ptr(), out[1].data_ptr(), stream))
+
+    def run_argmin():
+        _lib.check(ctx._lib.dctfp_pair_argmin(*head, out[2].data_ptr(), out[3].data_ptr(), out[4].data_ptr(), out[5].data_ptr(), stream))
+    ms_min, ms_arg = [], []
+    for _ in range(a.repeat):
+        ms_min.append(round(_events_ms(run_min, 5), 4))
+        ms_arg.append(round(_events_ms(run_argmin, 5), 4))
+    mn, last, mn2, last2, arg_a, arg_b = (t.cpu().numpy().astype(np.int64) for t in out)
+    assert np.array_equal(mn, mn2) and np.array_equal(last, last2)
+    assert np.array_equal(arg_a < 0, mn >= 17000) and np.array_equal(arg_b < 0, mn >= 17000)
+    for t in rng.integers(0, n_pairs, size=50).tolist() + np.flatnonzero(mn < 17000)[:50].tolist():
+        i, j = pairs[t]
+        blk = np.abs(q_dct[q_idx[i]:q_idx[i + 1]].astype(np.int16)[:, None] - dct[idx[j]:idx[j + 1]].astype(np.int16)[None]).sum(-1)
+        want = divmod(int(np.argmin(blk)), blk.shape[1]) if blk.min() < 17000 else (-1, -1)
+        assert mn[t] == blk.min() and (arg_a[t], arg_b[t]) == want
+    med = lambda v: sorted(v)[len(v) // 2]   # noqa: E731
+    return {'part': 'argmin', 'pairs': n_pairs, 'db': a.db, 'pairs_with_a_domain_pair': int((arg_a >= 0).sum()), 'pair_min_ms': ms_min,
+            'pair_argmin_ms': ms_arg, 'pair_min_median_ms': med(ms_min), 'pair_argmin_median_ms': med(ms_arg),
+            'pair_min_spread_ms': round(max(ms_min) - min(ms_min), 4), 'argmin_over_min': round(med(ms_arg) / med(ms_min), 4),
+            'argmin_within_pair_min_spread': med(ms_arg) <= med(ms_min) + (max(ms_min) - min(ms_min))}
+
+
 def part_blocks(a):
     import torch
     from dctdomain_amd import dct_sim
@@ -220,7 +269,8 @@ def part_blocks(a):
 
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument('--part', choices=('search', 'kernels', 'blocks'), required=True)
+    ap.add_argument('--part', choices=('search', 'kernels', 'blocks', 'argmin'), required=True)
+    ap.add_argument('--repeat', type=int, default=5, help='argmin: rounds of both kernels')
     ap.add_argument('--db', type=int, default=1_000_000)
     ap.add_argument('--queries', type=int, default=10_000)
     ap.add_argument('--old-db', type=int, default=100_000)
@@ -234,7 +284,7 @@ def main(argv=None):
     import torch
     if not torch.cuda.is_available():
         raise SystemExit('protein_search_bench needs the GPU')
-    res = {'search': part_search, 'kernels': part_kernels, 'blocks': part_blocks}[a.part](a)
+    res = {'search': part_search, 'kernels': part_kernels, 'blocks': part_blocks, 'argmin': part_argmin}[a.part](a)
     line = json.dumps(res)
     print(line, flush=True)
     if a.out:
