@@ -2628,36 +2628,35 @@ int dctfp_row_order(dctfp_ctx* ctx, int32_t* val, int32_t* idx, int64_t n_rows, 
     return DCTFP_OK;
 } DCTFP_GUARD("dctfp_row_order")
 
+// dctfp_pair_min (out_arg_a = out_arg_b = NULL) and dctfp_pair_argmin: `name` = the export, for its messages.
+static int pair_min_call(const char* name, dctfp_ctx* ctx, const int32_t* pairs, int64_t n_pairs, const int8_t* a, int64_t lda,
+                         const int64_t* idx_a, int64_t npa, const int8_t* b, int64_t ldb, const int64_t* idx_b, int64_t npb, int32_t d,
+                         int32_t* out_min, int32_t* out_last, int32_t* out_arg_a, int32_t* out_arg_b, void* stream_v) {
+    if (!ctx || !pairs || !a || !idx_a || !b || !idx_b || !out_min || !out_last) return fail(DCTFP_ERR_INVALID, "%s: NULL argument", name);
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    if (n_pairs < 0 || npa < 0 || npb < 0 || d < 1 || lda < d || ldb < d) return fail(DCTFP_ERR_INVALID, "%s: bad shape", name);
+    if (npa > 0x7fffffff || npb > 0x7fffffff) return fail(DCTFP_ERR_LIMIT, "%s: more than 2^31 - 1 proteins on a side", name);
+    if ((n_pairs + 3) / 4 > 0x7fffffff) return fail(DCTFP_ERR_LIMIT, "%s: too many pairs per call", name);
+    if (n_pairs == 0) return DCTFP_OK;
+    HIP_TRY(hipSetDevice(ctx->device));
+    launch_pair_argmin(pairs, n_pairs, a, lda, idx_a, npa, b, ldb, idx_b, npb, d, out_min, out_last, out_arg_a, out_arg_b, (hipStream_t)stream_v);
+    HIP_TRY(hipGetLastError());
+    return DCTFP_OK;
+}
+
 int dctfp_pair_min(dctfp_ctx* ctx, const int32_t* pairs, int64_t n_pairs, const int8_t* a, int64_t lda, const int64_t* idx_a, int64_t npa,
                    const int8_t* b, int64_t ldb, const int64_t* idx_b, int64_t npb, int32_t d, int32_t* out_min, int32_t* out_last,
                    void* stream_v) try {
-    if (!ctx || !pairs || !a || !idx_a || !b || !idx_b || !out_min || !out_last) return fail(DCTFP_ERR_INVALID, "dctfp_pair_min: NULL argument");
-    std::lock_guard<std::mutex> lock(ctx->mu);
-    if (n_pairs < 0 || npa < 0 || npb < 0 || d < 1 || lda < d || ldb < d) return fail(DCTFP_ERR_INVALID, "dctfp_pair_min: bad shape");
-    if (npa > 0x7fffffff || npb > 0x7fffffff) return fail(DCTFP_ERR_LIMIT, "dctfp_pair_min: more than 2^31 - 1 proteins on a side");
-    if ((n_pairs + 3) / 4 > 0x7fffffff) return fail(DCTFP_ERR_LIMIT, "dctfp_pair_min: too many pairs per call");
-    if (n_pairs == 0) return DCTFP_OK;
-    HIP_TRY(hipSetDevice(ctx->device));
-    launch_pair_min(pairs, n_pairs, a, lda, idx_a, npa, b, ldb, idx_b, npb, d, out_min, out_last, (hipStream_t)stream_v);
-    HIP_TRY(hipGetLastError());
-    return DCTFP_OK;
+    return pair_min_call("dctfp_pair_min", ctx, pairs, n_pairs, a, lda, idx_a, npa, b, ldb, idx_b, npb, d, out_min, out_last, nullptr, nullptr,
+                         stream_v);
 } DCTFP_GUARD("dctfp_pair_min")
 
 int dctfp_pair_argmin(dctfp_ctx* ctx, const int32_t* pairs, int64_t n_pairs, const int8_t* a, int64_t lda, const int64_t* idx_a, int64_t npa,
                       const int8_t* b, int64_t ldb, const int64_t* idx_b, int64_t npb, int32_t d, int32_t* out_min, int32_t* out_last,
                       int32_t* out_arg_a, int32_t* out_arg_b, void* stream_v) try {
-    if (!ctx || !pairs || !a || !idx_a || !b || !idx_b || !out_min || !out_last || !out_arg_a || !out_arg_b)
-        return fail(DCTFP_ERR_INVALID, "dctfp_pair_argmin: NULL argument");
-    std::lock_guard<std::mutex> lock(ctx->mu);
-    if (n_pairs < 0 || npa < 0 || npb < 0 || d < 1 || lda < d || ldb < d) return fail(DCTFP_ERR_INVALID, "dctfp_pair_argmin: bad shape");
-    if (npa > 0x7fffffff || npb > 0x7fffffff) return fail(DCTFP_ERR_LIMIT, "dctfp_pair_argmin: more than 2^31 - 1 proteins on a side");
-    if ((n_pairs + 3) / 4 > 0x7fffffff) return fail(DCTFP_ERR_LIMIT, "dctfp_pair_argmin: too many pairs per call");
-    if (n_pairs == 0) return DCTFP_OK;
-    HIP_TRY(hipSetDevice(ctx->device));
-    launch_pair_argmin(pairs, n_pairs, a, lda, idx_a, npa, b, ldb, idx_b, npb, d, out_min, out_last, out_arg_a, out_arg_b,
-                       (hipStream_t)stream_v);
-    HIP_TRY(hipGetLastError());
-    return DCTFP_OK;
+    if (!out_arg_a || !out_arg_b) return fail(DCTFP_ERR_INVALID, "dctfp_pair_argmin: NULL argument");
+    return pair_min_call("dctfp_pair_argmin", ctx, pairs, n_pairs, a, lda, idx_a, npa, b, ldb, idx_b, npb, d, out_min, out_last, out_arg_a,
+                         out_arg_b, stream_v);
 } DCTFP_GUARD("dctfp_pair_argmin")
 
 int dctfp_protein_min(dctfp_ctx* ctx, const int8_t* a, int64_t lda, const int64_t* idx_a, int64_t npa, const int8_t* b, int64_t ldb,
@@ -2763,38 +2762,39 @@ int dctfp_tri_filter_fill(dctfp_ctx* ctx, const int32_t* tile, int64_t n_rows, i
     return DCTFP_OK;
 } DCTFP_GUARD("dctfp_tri_filter_fill")
 
-int dctfp_pair_lines(dctfp_ctx* ctx, int64_t n_lines, const int32_t* pi, const int32_t* pj, const int32_t* mn, const int32_t* last,
-                     const uint8_t* ids, const int64_t* id_off, int64_t n_ids, const char* table, const int64_t* line_off, uint8_t* out,
-                     int64_t out_bytes, void* stream_v) try {
+// dctfp_pair_lines (labels = NULL: la, lb, label_off unused) and dctfp_pair_domain_lines: `name` = the export, for its messages.
+static int pair_lines_call(const char* name, dctfp_ctx* ctx, int64_t n_lines, const int32_t* pi, const int32_t* pj, const int32_t* mn,
+                           const int32_t* last, const int32_t* la, const int32_t* lb, const uint8_t* ids, const int64_t* id_off, int64_t n_ids,
+                           const uint8_t* labels, const int64_t* label_off, int64_t n_labels, const char* table, const int64_t* line_off,
+                           uint8_t* out, int64_t out_bytes, void* stream_v) {
     if (!ctx || !pi || !pj || !mn || !last || !ids || !id_off || !table || !line_off || !out)
-        return fail(DCTFP_ERR_INVALID, "dctfp_pair_lines: NULL argument");
+        return fail(DCTFP_ERR_INVALID, "%s: NULL argument", name);
     std::lock_guard<std::mutex> lock(ctx->mu);
-    if (n_lines < 0 || n_ids < 0 || out_bytes < 0) return fail(DCTFP_ERR_INVALID, "dctfp_pair_lines: bad shape");
+    if (n_lines < 0 || n_ids < 0 || n_labels < 0 || out_bytes < 0) return fail(DCTFP_ERR_INVALID, "%s: bad shape", name);
     // (sixteen lanes per line in 256-thread workgroups; the grid must stay below 2^32 workgroups)
-    if (n_lines > (int64_t)1 << 31) return fail(DCTFP_ERR_LIMIT, "dctfp_pair_lines: more than 2^31 lines per call");
-    if (n_lines == 0) return DCTFP_OK;
-    HIP_TRY(hipSetDevice(ctx->device));
-    launch_pair_lines(n_lines, pi, pj, mn, last, ids, id_off, n_ids, table, line_off, out, out_bytes, (hipStream_t)stream_v);
-    HIP_TRY(hipGetLastError());
-    return DCTFP_OK;
-} DCTFP_GUARD("dctfp_pair_lines")
-
-int dctfp_pair_domain_lines(dctfp_ctx* ctx, int64_t n_lines, const int32_t* pi, const int32_t* pj, const int32_t* mn, const int32_t* last,
-                            const int32_t* la, const int32_t* lb, const uint8_t* ids, const int64_t* id_off, int64_t n_ids,
-                            const uint8_t* labels, const int64_t* label_off, int64_t n_labels, const char* table, const int64_t* line_off,
-                            uint8_t* out, int64_t out_bytes, void* stream_v) try {
-    if (!ctx || !pi || !pj || !mn || !last || !la || !lb || !ids || !id_off || !labels || !label_off || !table || !line_off || !out)
-        return fail(DCTFP_ERR_INVALID, "dctfp_pair_domain_lines: NULL argument");
-    std::lock_guard<std::mutex> lock(ctx->mu);
-    if (n_lines < 0 || n_ids < 0 || n_labels < 0 || out_bytes < 0) return fail(DCTFP_ERR_INVALID, "dctfp_pair_domain_lines: bad shape");
-    // (dctfp_pair_lines' grid: sixteen lanes per line in 256-thread workgroups)
-    if (n_lines > (int64_t)1 << 31) return fail(DCTFP_ERR_LIMIT, "dctfp_pair_domain_lines: more than 2^31 lines per call");
+    if (n_lines > (int64_t)1 << 31) return fail(DCTFP_ERR_LIMIT, "%s: more than 2^31 lines per call", name);
     if (n_lines == 0) return DCTFP_OK;
     HIP_TRY(hipSetDevice(ctx->device));
     launch_pair_domain_lines(n_lines, pi, pj, mn, last, la, lb, ids, id_off, n_ids, labels, label_off, n_labels, table, line_off, out,
                              out_bytes, (hipStream_t)stream_v);
     HIP_TRY(hipGetLastError());
     return DCTFP_OK;
+}
+
+int dctfp_pair_lines(dctfp_ctx* ctx, int64_t n_lines, const int32_t* pi, const int32_t* pj, const int32_t* mn, const int32_t* last,
+                     const uint8_t* ids, const int64_t* id_off, int64_t n_ids, const char* table, const int64_t* line_off, uint8_t* out,
+                     int64_t out_bytes, void* stream_v) try {
+    return pair_lines_call("dctfp_pair_lines", ctx, n_lines, pi, pj, mn, last, nullptr, nullptr, ids, id_off, n_ids, nullptr, nullptr, 0, table,
+                           line_off, out, out_bytes, stream_v);
+} DCTFP_GUARD("dctfp_pair_lines")
+
+int dctfp_pair_domain_lines(dctfp_ctx* ctx, int64_t n_lines, const int32_t* pi, const int32_t* pj, const int32_t* mn, const int32_t* last,
+                            const int32_t* la, const int32_t* lb, const uint8_t* ids, const int64_t* id_off, int64_t n_ids,
+                            const uint8_t* labels, const int64_t* label_off, int64_t n_labels, const char* table, const int64_t* line_off,
+                            uint8_t* out, int64_t out_bytes, void* stream_v) try {
+    if (!la || !lb || !labels || !label_off) return fail(DCTFP_ERR_INVALID, "dctfp_pair_domain_lines: NULL argument");
+    return pair_lines_call("dctfp_pair_domain_lines", ctx, n_lines, pi, pj, mn, last, la, lb, ids, id_off, n_ids, labels, label_off, n_labels,
+                           table, line_off, out, out_bytes, stream_v);
 } DCTFP_GUARD("dctfp_pair_domain_lines")
 
 int dctfp_tri_link(dctfp_ctx* ctx, const int32_t* tile, int64_t n_rows, int64_t n_cols, int64_t ld, int64_t row0, int64_t col0,

@@ -405,15 +405,13 @@ static void launch_pair_kernel(const int32_t* pairs, int64_t n_pairs, const int8
                            idx_b, npb, d, out_min, out_last, out_arg_a, out_arg_b);
 }
 
-void launch_pair_min(const int32_t* pairs, int64_t n_pairs, const int8_t* a, int64_t lda, const int64_t* idx_a, int64_t npa, const int8_t* b,
-                     int64_t ldb, const int64_t* idx_b, int64_t npb, int d, int32_t* out_min, int32_t* out_last, hipStream_t stream) {
-    launch_pair_kernel<false>(pairs, n_pairs, a, lda, idx_a, npa, b, ldb, idx_b, npb, d, out_min, out_last, nullptr, nullptr, stream);
-}
-
 void launch_pair_argmin(const int32_t* pairs, int64_t n_pairs, const int8_t* a, int64_t lda, const int64_t* idx_a, int64_t npa,
                         const int8_t* b, int64_t ldb, const int64_t* idx_b, int64_t npb, int d, int32_t* out_min, int32_t* out_last,
                         int32_t* out_arg_a, int32_t* out_arg_b, hipStream_t stream) {
-    launch_pair_kernel<true>(pairs, n_pairs, a, lda, idx_a, npa, b, ldb, idx_b, npb, d, out_min, out_last, out_arg_a, out_arg_b, stream);
+    if (out_arg_a)
+        launch_pair_kernel<true>(pairs, n_pairs, a, lda, idx_a, npa, b, ldb, idx_b, npb, d, out_min, out_last, out_arg_a, out_arg_b, stream);
+    else
+        launch_pair_kernel<false>(pairs, n_pairs, a, lda, idx_a, npa, b, ldb, idx_b, npb, d, out_min, out_last, nullptr, nullptr, stream);
 }
 
 int select_max_cap() { return kSelThreads * kBinsPerThread - 1; }

@@ -142,9 +142,8 @@ constexpr int kCutClasses = 4;
 int reccut_class_of(int n_res, int64_t n_contacts);
 int launch_reccut(int cls, const dctfp::CutJob* jobs, unsigned n, double cut1, double cut2, hipStream_t stream, LaunchError* err);
 // protein-level search (k_search.hip): pair minima from the fingerprints, threshold-aware selection on a last-row distance tile
-void launch_pair_min(const int32_t* pairs, int64_t n_pairs, const int8_t* a, int64_t lda, const int64_t* idx_a, int64_t npa, const int8_t* b,
-                     int64_t ldb, const int64_t* idx_b, int64_t npb, int d, int32_t* out_min, int32_t* out_last, hipStream_t stream);
-// ... and the same with the fingerprint pair the minimum came from (dctfp_pair_argmin: row indices within the proteins, -1 = none)
+// (dctfp_pair_min and dctfp_pair_argmin: out_arg_a / out_arg_b = the fingerprint pair the minimum came from, row indices within
+// the proteins, -1 = none -- both NULL: dctfp_pair_min's kernel, which keeps no position)
 void launch_pair_argmin(const int32_t* pairs, int64_t n_pairs, const int8_t* a, int64_t lda, const int64_t* idx_a, int64_t npa,
                         const int8_t* b, int64_t ldb, const int64_t* idx_b, int64_t npb, int d, int32_t* out_min, int32_t* out_last,
                         int32_t* out_arg_a, int32_t* out_arg_b, hipStream_t stream);
@@ -165,10 +164,7 @@ void launch_tri_filter_count(const int32_t* tile, int64_t n_rows, int64_t n_cols
 void launch_tri_filter_fill(const int32_t* tile, int64_t n_rows, int64_t n_cols, int64_t ld, int64_t row0, int64_t col0,
                             const uint8_t* row_empty, const uint8_t* col_empty, int32_t cap, int32_t bound, const int64_t* offsets,
                             int64_t out_len, int32_t* out_i, int32_t* out_j, hipStream_t stream);
-void launch_pair_lines(int64_t n_lines, const int32_t* pi, const int32_t* pj, const int32_t* mn, const int32_t* last, const uint8_t* ids,
-                       const int64_t* id_off, int64_t n_ids, const char* table, const int64_t* line_off, uint8_t* out, int64_t out_bytes,
-                       hipStream_t stream);
-// ... with the labels of DCTdomain's fingerprint pair behind the scores (dct-sim --domains)
+// (dctfp_pair_lines and dctfp_pair_domain_lines: labels NULL = the line without the two label fields, la / lb / label_off not read)
 void launch_pair_domain_lines(int64_t n_lines, const int32_t* pi, const int32_t* pj, const int32_t* mn, const int32_t* last, const int32_t* la,
                               const int32_t* lb, const uint8_t* ids, const int64_t* id_off, int64_t n_ids, const uint8_t* labels,
                               const int64_t* label_off, int64_t n_labels, const char* table, const int64_t* line_off, uint8_t* out,

@@ -15,7 +15,8 @@ Where the reference loops over protein pairs and, inside, over domain pairs in P
 - ``all_sim`` walks the upper triangle in stripes of proteins (``AllPairs``): the int8 L1 matrix of a stripe's fingerprints
   against those of the later proteins (``dctfp_l1_matrix``), reduced per protein x protein block to (minimum, last-last)
   (``dctfp_block_min``) and turned into the result text on the device (``dctfp_sim_lines``), which streams out through two
-  pinned buffers.  Host memory is the two buffers plus O(n), not the n x n block matrix (``Blocks``, kept for its callers);
+  pinned buffers (``similarity.TextStream``, as every text composed on the device does).  Host memory is the two buffers plus
+  O(n), not the n x n block matrix (``Blocks``, kept for its callers);
 - with a cut-off, ``all_sim`` never forms the other lines (``FilteredPairs``): per stripe one tile of protein-pair L1 values
   (``dctfp_protein_min``, or the last rows' ``dctfp_l1_matrix`` when DCTglobal is cut), the pairs of the triangle within the
   bound selected on the device in output order (``dctfp_tri_filter_count`` / ``dctfp_tri_filter_fill``), both scores for those
@@ -47,10 +48,9 @@ import time
 
 import numpy as np
 
-from .similarity import (PROTEIN_MIN_MAX_D, LineIds, block_min, block_min_device, cluster_labels, l1_matrix, link_pairs, pair_argmin,
-                         pair_argmin_device, pair_domain_line_offsets, pair_domain_lines, pair_line_offsets, pair_lines, pair_min,
-                         pair_min_device, protein_min, sim_lines, threshold_select, to_device_int8, tri_filter_count, tri_filter_fill,
-                         tri_link)
+from .similarity import (PROTEIN_MIN_MAX_D, LineIds, TextStream, _utf8_binary, block_min, block_min_device, cluster_labels, l1_matrix,
+                         link_pairs, pair_argmin, pair_argmin_device, pair_line_offsets, pair_lines, pair_min, pair_min_device, protein_min,
+                         sim_lines, threshold_select, to_device_int8, tri_filter_count, tri_filter_fill, tri_link)
 
 L1_FULL_SCALE = 17000      # src/dct-sim.py:24
 HEADER = '#prot1 prot2 sim-domain sim-global'
@@ -151,11 +151,8 @@ def _label(labels, first_row: int, arg: int) -> str:
 
 def load_dct(filename: str, asmap=True) -> tuple:
     """npz -> ({sid: fingerprints} | [fingerprints], sid) (src/dct-sim.py:52-84)."""
-    t0 = time.time()
-    with np.load(filename) as data:
-        seqid, bounds, rows = data['sid'], data['idx'], data['dct']
+    seqid, bounds, rows = _load_npz(filename)
     per_protein = [rows[a:b, :] for a, b in zip(bounds[:-1], bounds[1:])]
-    print(f"dct loaded for {len(seqid)} sequences, time used: {time.time() - t0:.1f}s")
     return (dict(zip(seqid, per_protein)) if asmap else per_protein), seqid
 
 
@@ -174,18 +171,12 @@ class Blocks:
     """All protein-vs-protein (minimum, last-last) L1 blocks between two ``-dct.npz`` files."""
 
     def __init__(self, file_a: str, file_b: str = None):
-        load_dct(file_a, asmap=False)                       # the reference's progress line(s)
-        if file_b is not None:
-            load_dct(file_b, asmap=False)
-        a = np.load(file_a)
-        b = a if file_b is None else np.load(file_b)
-        self.rows, self.cols = a['sid'], b['sid']
+        self.rows, ia, da = _load_npz(file_a)               # (with the reference's progress line, one per file)
+        self.cols, ib, dbm = (self.rows, ia, da) if file_b is None else _load_npz(file_b)
         # protein stripes of `a`: the int32 distance matrix of a stripe stays within ~1 GiB (the protein x protein result
         # is what is kept; the reference loops pair by pair, src/dct-sim.py:126-176)
         # ... and protein groups of `b` of at most COL_ROWS fingerprints, so that neither the uploaded part of `b` nor
         # the distance matrix grows with the size of the files
-        da, ia = a['dct'], np.asarray(a['idx'], dtype=np.int64)
-        dbm, ib = b['dct'], np.asarray(b['idx'], dtype=np.int64)
         na, nb = len(ia) - 1, len(ib) - 1
         self.mn = np.full((na, nb), 0x7fffffff, dtype=np.int32)      # (an empty block keeps this: block_min_kernel's fill)
         self.last = np.full((na, nb), 0x7fffffff, dtype=np.int32)
@@ -248,6 +239,21 @@ def plan_stripes(id_lens, idx, text_bytes: int, fp_rows: int):
     return out
 
 
+class _DeviceRows:
+    """The fingerprints of proteins [p0, p1) of a file on the device: a slice of the whole file, which stays there (``resident``)
+    when it has at most ``col_rows`` fingerprints, else uploaded per request."""
+
+    def __init__(self, fps, idx, col_rows: int):
+        self.fps, self.idx = fps, idx
+        total = int(idx[-1]) if len(idx) else 0
+        self.resident = to_device_int8(fps[:total]) if 0 < total <= col_rows else None
+
+    def __call__(self, p0: int, p1: int):
+        if self.resident is not None:
+            return self.resident[self.idx[p0]:self.idx[p1]]
+        return to_device_int8(self.fps[self.idx[p0]:self.idx[p1]])
+
+
 class AllPairs:
     """all_sim's text (src/dct-sim.py:158-176) for one file, upper triangle only, streamed: rows in stripes (``plan_stripes``)
     whose text fits in TEXT_BYTES and whose fingerprints times a column group fit in TILE_INTS; per stripe and group of at most
@@ -275,18 +281,11 @@ class AllPairs:
             return
         ids = LineIds([f'{s}' for s in self.sid])
         dev = ids.bytes_dev.device
-        stream = torch.cuda.current_stream(dev)
         table = torch.as_tensor(score_table(), device=dev)
-        total = int(self.idx[-1])
-        resident = to_device_int8(self.fps[:total]) if 0 < total <= self.COL_ROWS else None
-
-        def rows(p0, p1):
-            if resident is not None:
-                return resident[self.idx[p0]:self.idx[p1]]
-            return to_device_int8(self.fps[self.idx[p0]:self.idx[p1]])
-
-        text, pinned, pending = None, [None, None], None
-        for k, (i0, i1, base, nbytes) in enumerate(self.stripes(ids.lens)):
+        rows = _DeviceRows(self.fps, self.idx, self.COL_ROWS)
+        out = TextStream(sink, room=lambda nbytes: max(nbytes, min(self.TEXT_BYTES, 2 * nbytes)))
+        text = None
+        for i0, i1, base, nbytes in self.stripes(ids.lens):
             if text is None or text.numel() < nbytes:
                 text = torch.empty(nbytes, dtype=torch.uint8, device=dev)
             a = rows(i0, i1) if self.idx[i1] > self.idx[i0] else None
@@ -299,21 +298,8 @@ class AllPairs:
                 mn, last = block_min_device(dist, ia, self.idx[q0:q1 + 1] - self.idx[q0])
                 sim_lines(mn, last, i0, q0, ids, table, base, text)
                 del dist, mn, last, b
-            pin = pinned[k % 2]                                 # (written out by the host two stripes ago)
-            if pin is None or pin.numel() < nbytes:
-                pin = pinned[k % 2] = torch.empty(max(nbytes, min(self.TEXT_BYTES, 2 * nbytes)), dtype=torch.uint8, pin_memory=True)
-            pin[:nbytes].copy_(text[:nbytes], non_blocking=True)
-            done = torch.cuda.Event()
-            done.record(stream)
-            if pending is not None:                             # the previous stripe goes out while the device fills this one
-                self._flush(sink, *pending)
-            pending = (pin, nbytes, done)
-        self._flush(sink, *pending)
-
-    @staticmethod
-    def _flush(sink, pin, nbytes, done):
-        done.synchronize()
-        sink(memoryview(pin.numpy())[:nbytes])
+            out.hand_over(text, nbytes)                         # (the previous stripe goes out while the device fills this one)
+        out.close()
 
 
 def _load_npz(filename: str) -> tuple:
@@ -387,21 +373,26 @@ def _compact(fps, idx, proteins):
     return fps[rows], sub_idx
 
 
+def _score_arrays(n: int, domains: bool):
+    """(the int64 arrays (min, last) -- ``domains``: (min, last, arg_a, arg_b) -- of ``n`` pairs, holding what a pair without
+    fingerprints scores; ``pair_min`` -- ``pair_argmin`` -- which fills them)."""
+    fills = (0x7fffffff, 0x7fffffff) + ((-1, -1) if domains else ())
+    return [np.full(n, f, dtype=np.int64) for f in fills], (pair_argmin if domains else pair_min)
+
+
 def pair_scores(fps, idx, pairs, max_rows: int = None, domains: bool = False):
     """(min, last) L1 of every (protein i, protein j) of ``pairs`` within one npz (``dctfp_pair_min``): only the fingerprints of
     the proteins the pairs name go to the device, at most ``max_rows`` (``ProteinSearch.COL_ROWS``) of them at a time.
     ``domains``: (min, last, arg_i, arg_j) -- with the rows of the minimum within the two proteins, -1 = none
     (``dctfp_pair_argmin``)."""
     pairs = np.asarray(pairs, dtype=np.int64).reshape(-1, 2)
-    out = [np.full(len(pairs), 0x7fffffff, dtype=np.int64) for _ in range(2)]
-    if domains:
-        out += [np.full(len(pairs), -1, dtype=np.int64) for _ in range(2)]
+    out, score = _score_arrays(len(pairs), domains)
     for k0, k1 in _pair_chunks(idx, pairs, max_rows or ProteinSearch.COL_ROWS):
         proteins, local = np.unique(pairs[k0:k1], return_inverse=True)
         rows, sub_idx = _compact(fps, idx, proteins)
         if len(rows):
             dev = to_device_int8(rows)
-            for o, v in zip(out, (pair_argmin if domains else pair_min)(dev, sub_idx, dev, sub_idx, local.reshape(-1, 2))):
+            for o, v in zip(out, score(dev, sub_idx, dev, sub_idx, local.reshape(-1, 2))):
                 o[k0:k1] = v
     return tuple(out)
 
@@ -425,7 +416,7 @@ class FilteredPairs:
     Nothing of size n x n exists anywhere; host memory beyond the data is O(n), one range's survivors and the two buffers.
 
     ``labels`` (``--domains``: ``fingerprint_labels`` of the file) adds the domain pair to every line: step 3 takes
-    ``pair_argmin_device`` and keeps the two rows of the minimum, step 4 ``pair_domain_lines`` with the labels on the device (one
+    ``pair_argmin_device`` and keeps the two rows of the minimum, step 4 gives ``pair_lines`` the labels on the device (one
     per fingerprint row and ``-``).  Without cut-offs both bounds keep every pair and the output is ``AllPairs``' with the two
     fields added -- by the slower route: a protein-minimum tile, a filter that drops nothing and a second read of every pair's
     fingerprints for the scores, where ``AllPairs`` reduces one distance matrix."""
@@ -464,31 +455,28 @@ class FilteredPairs:
         """The bound of the route's tile: DCTglobal's when it excludes anything, else DCTdomain's."""
         return self.bound_global if self.route == 'global' else self.bound_domain
 
+    def device_rows(self) -> _DeviceRows:
+        return _DeviceRows(self.fps, self.idx, self.COL_ROWS)
+
     def resident_rows(self):
         """The file's fingerprints on the device when they fit there (at most COL_ROWS), else None."""
-        total = int(self.idx[-1])
-        return to_device_int8(self.fps[:total]) if 0 < total <= self.COL_ROWS else None
+        return self.device_rows().resident
 
-    def tiles(self, resident=None):
+    def tiles(self, rows: _DeviceRows = None):
         """Yields, per stripe, (i0, i1, tile, (row flags, column flags)): step 1 of the class text.  The tile is device int32,
         rows [i0, i1) x proteins i0 + 1 .. n - 1; the flags mark the proteins without fingerprints on the DCTglobal route (None on
-        the other: ``protein_min`` leaves 0x7fffffff there).  ``resident``: ``resident_rows()`` of a caller that needs the
+        the other: ``protein_min`` leaves 0x7fffffff there).  ``rows``: ``device_rows()`` of a caller that needs the
         fingerprints itself; taken here otherwise."""
         import torch
         n = len(self.idx) - 1
         dev = torch.device('cuda', torch.cuda.current_device())
         total = int(self.idx[-1])
-        if resident is None:
-            resident = self.resident_rows()
+        if rows is None:
+            rows = self.device_rows()
         if self.route == 'global':
             last_rows, empty = _last_rows(self.fps[:total], self.idx)
             last_dev = to_device_int8(last_rows) if n <= self.COL_ROWS else None
             empty_dev = torch.as_tensor(empty, device=dev)
-
-        def rows(p0, p1):
-            if resident is not None:
-                return resident[self.idx[p0]:self.idx[p1]]
-            return to_device_int8(self.fps[self.idx[p0]:self.idx[p1]])
 
         def lasts(p0, p1):
             return last_dev[p0:p1] if last_dev is not None else to_device_int8(last_rows[p0:p1])
@@ -521,9 +509,10 @@ class FilteredPairs:
         id_lens = np.fromiter((len(f'{s}'.encode('utf8')) for s in self.sid), dtype=np.int64, count=n)
         longest = int(id_lens.max())
         bound = self.bound
-        resident = self.resident_rows()
+        rows = self.device_rows()
+        resident = rows.resident
         idx_dev = torch.as_tensor(self.idx, device=resident.device) if resident is not None else None
-        for i0, i1, tile, flags in self.tiles(resident):
+        for i0, i1, tile, flags in self.tiles(rows):
             col0 = i0 + 1
             dev = tile.device
             count_dev = tri_filter_count(tile, i0, col0, bound, *flags)
@@ -566,40 +555,25 @@ class FilteredPairs:
     def write(self, sink):
         """Calls ``sink(memoryview)`` with the text of each range of rows that has any, in order."""
         import torch
-        ids = table = stream = labels = first_row = None
-        pinned, pending, k = [None, None], None, 0
+        ids = table = labels = first_row = None
+        la = lb = None
+        out = TextStream(sink, room=lambda nbytes: max(nbytes, 1 << 16))
         for pi, pj, mn, last, *args in self.chunks():
             if ids is None:
                 ids = LineIds([f'{s}' for s in self.sid])
                 table = torch.as_tensor(score_table(), device=pi.device)
-                stream = torch.cuda.current_stream(pi.device)
                 if self.row_labels is not None:                 # (one label per fingerprint row, then the "no pair" entry)
                     labels = LineIds(list(self.row_labels) + [NO_DOMAIN], device=pi.device)
                     first_row = torch.as_tensor(self.idx[:-1].astype(np.int32), device=pi.device)
             if labels is not None:
                 la, lb = (torch.where(arg >= 0, first_row[p.long()] + arg, torch.full_like(arg, len(self.row_labels))).contiguous()
                           for p, arg in zip((pi, pj), args))
-                off = pair_domain_line_offsets(pi, pj, la, lb, ids, labels)
-            else:
-                off = pair_line_offsets(pi, pj, ids)
+            off = pair_line_offsets(pi, pj, ids, la, lb, labels)
             nbytes = int(off[-1])
             text = torch.empty(nbytes, dtype=torch.uint8, device=pi.device)
-            if labels is not None:
-                pair_domain_lines(pi, pj, mn, last, la, lb, ids, labels, table, off, text)
-            else:
-                pair_lines(pi, pj, mn, last, ids, table, off, text)
-            pin = pinned[k % 2]                                 # (written out by the host two ranges ago)
-            if pin is None or pin.numel() < nbytes:
-                pin = pinned[k % 2] = torch.empty(max(nbytes, 1 << 16), dtype=torch.uint8, pin_memory=True)
-            pin[:nbytes].copy_(text, non_blocking=True)
-            done = torch.cuda.Event()
-            done.record(stream)
-            if pending is not None:                             # the previous range goes out while the device works on this one
-                AllPairs._flush(sink, *pending)
-            pending = (pin, nbytes, done)
-            k += 1
-        if pending is not None:
-            AllPairs._flush(sink, *pending)
+            pair_lines(pi, pj, mn, last, ids, table, off, text, la, lb, labels)
+            out.hand_over(text, nbytes)                         # (the previous range goes out while the device works on this one)
+        out.close()
 
 
 def _ragged_gather(raw: np.ndarray, starts: np.ndarray, lens: np.ndarray) -> np.ndarray:
@@ -711,6 +685,14 @@ class Clusters(FilteredPairs):
             sink(memoryview(text))
 
 
+def _add_hits(parts, t0: int, p0: int, off, key, col):
+    """``threshold_select``'s hits of a tile -- query proteins from ``t0``, database proteins from ``p0`` -- each row's to the list
+    of its query in ``parts``, the columns as database protein indices."""
+    for r in range(len(off) - 1):
+        s = slice(off[r], off[r + 1])
+        parts[t0 + r].append((key[s], col[s] + p0))
+
+
 class ProteinSearch:
     """A fingerprint database (the ``dct`` / ``idx`` arrays of a ``-dct.npz``) searched protein by protein the way db_search
     does (src/dct-sim.py:126-156), without the n_query x n_db block matrix:
@@ -775,10 +757,7 @@ class ProteinSearch:
                 rows = int(min(self.MAX_TILE_ROWS, max(1, self.TILE_INTS // (p1 - p0))))
                 for t0 in range(0, nq, rows):
                     t1 = min(nq, t0 + rows)
-                    off, key, col = threshold_select(l1_matrix(q_last[t0:t1], last), top1, bound, q_empty[t0:t1], empty)
-                    for r in range(t1 - t0):
-                        s = slice(off[r], off[r + 1])
-                        parts[t0 + r].append((key[s], col[s] + p0))
+                    _add_hits(parts, t0, p0, *threshold_select(l1_matrix(q_last[t0:t1], last), top1, bound, q_empty[t0:t1], empty))
         merged = (merge_candidates(pq, top1, bound) for pq in parts)
         hits = [c if top >= 1 else c[k <= bound] for k, c in merged]
         del parts
@@ -811,18 +790,13 @@ class ProteinSearch:
                 for t0 in range(c0, c1, per):
                     t1 = min(c1, t0 + per)
                     tile = protein_min(q, qidx[t0:t1 + 1] - qidx[c0], rows, sub_idx)
-                    off, key, col = threshold_select(tile, top1, bound, q_empty[t0:t1], empty)
-                    for r in range(t1 - t0):
-                        s = slice(off[r], off[r + 1])
-                        parts[t0 + r].append((key[s], col[s] + p0))
+                    _add_hits(parts, t0, p0, *threshold_select(tile, top1, bound, q_empty[t0:t1], empty))
                     del tile
 
     def _pair_scores(self, query_fps, qidx, q_of, db_of, domains: bool = False):
         """(min, last) L1 of the pairs (query q_of[k], database protein db_of[k]): per database group, per chunk of queries.
         ``domains``: (min, last, arg_q, arg_db) through ``pair_argmin``."""
-        out = [np.full(len(q_of), 0x7fffffff, dtype=np.int64) for _ in range(2)]
-        if domains:
-            out += [np.full(len(q_of), -1, dtype=np.int64) for _ in range(2)]
+        out, score = _score_arrays(len(q_of), domains)
         for g, (p0, p1) in enumerate(self.groups):
             in_g = np.flatnonzero((db_of >= p0) & (db_of < p1))
             if len(in_g) == 0:
@@ -836,7 +810,7 @@ class ProteinSearch:
                     continue
                 qrows = to_device_int8(query_fps[qidx[c0]:qidx[c1]])
                 pairs = np.stack([q_of[sel] - c0, db_of[sel] - p0], axis=1)
-                for o, v in zip(out, (pair_argmin if domains else pair_min)(qrows, qidx[c0:c1 + 1] - qidx[c0], rows, sub_idx, pairs)):
+                for o, v in zip(out, score(qrows, qidx[c0:c1 + 1] - qidx[c0], rows, sub_idx, pairs)):
                     o[sel] = v
         return tuple(out)
 
@@ -855,8 +829,8 @@ class Report:
     def raw(self, data):
         """UTF-8 bytes straight to the binary layer under the text one (flushed first, so that the order of everything written
         stays as it is); text for a stream without one (a ``StringIO``) or with another encoding."""
-        buf = getattr(self.out, 'buffer', None)
-        if buf is None or (getattr(self.out, 'encoding', None) or '').lower().replace('-', '').replace('_', '') != 'utf8':
+        buf = _utf8_binary(self.out)
+        if buf is None:
             self.out.write(bytes(data).decode('utf8'))
             return
         self.out.flush()

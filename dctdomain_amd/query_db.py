@@ -20,7 +20,8 @@ import torch
 
 from . import _lib
 from .database import Database, _npy_vector
-from .similarity import _device_int64, _pair_to_host, l1_knn_device, l1_matrix, order_pairs, row_select, to_device_int8
+from .similarity import (TextStream, _device_int64, _pair_to_host, _utf8_binary, l1_knn_device, l1_matrix, order_pairs, row_select,
+                         to_device_int8)
 
 
 def _load_all(db: Database):
@@ -250,7 +251,7 @@ class QuerySearch:
     def search(self, q: Table, khits: int, sink, batch_rows: int = None, text_bytes: int = None, rank_cap: int = None):
         """Writes the lines of ``search()`` for the query table ``q`` to ``sink`` (a callable taking bytes), in batches of query
         proteins of at most ``batch_rows`` fingerprints (one protein with more is a batch of its own).  The text of a run of
-        lines is copied into one of two pinned buffers while the sink writes the other."""
+        lines is copied into one of two pinned buffers while the sink writes the other (``TextStream``)."""
         batch_rows = int(batch_rows or self.BATCH_ROWS)
         text_bytes = int(text_bytes or self.TEXT_BYTES)
         rank_cap = self.RANK_CAP if rank_cap is None else int(rank_cap)
@@ -268,23 +269,9 @@ class QuerySearch:
         q_pid_off = _device_int64(q.pid_off, dev)
         q_dom_off = _device_int64(q.dom_off + len(q.pid), dev)
         text = torch.empty(max(1, text_bytes), dtype=torch.uint8, device=dev)
-        pinned = [torch.empty(max(1, text_bytes), dtype=torch.uint8, pin_memory=True) for _ in range(2)]
+        out = TextStream(lambda view: sink(bytes(view)), room=lambda nbytes: max(1, text_bytes))      # (no run is longer than the text buffer)
         ctx = _lib.get_context(dev.index)
-        stream = torch.cuda.current_stream(dev)
-        sp = C.c_void_p(stream.cuda_stream)
-        held = None                                                         # (pinned buffer, bytes, event) not yet written out
-
-        def hand_over(buf, nbytes):
-            nonlocal held
-            pinned[buf][:nbytes].copy_(text[:nbytes], non_blocking=True)
-            ev = torch.cuda.Event()
-            ev.record(stream)
-            if held is not None:                                            # the previous run goes out while this one copies
-                held[2].synchronize()
-                sink(pinned[held[0]][:held[1]].numpy().tobytes())
-            held = (buf, nbytes, ev)
-
-        buf = 0
+        sp = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
         p0 = 0
         while p0 < n_prot:
             p1 = max(p0 + 1, int(np.searchsorted(qoff, qoff[p0] + batch_rows, side='right')) - 1)
@@ -337,20 +324,10 @@ class QuerySearch:
                                                       q_pid_off.data_ptr(), q_dom_off.data_ptr(), self.d_txt.data_ptr(),
                                                       self.d_pid_off.data_ptr(), self.d_dom_off.data_ptr(), self.score_txt_dev.data_ptr(),
                                                       self.score_off_dev.data_ptr(), rel.data_ptr(), text.data_ptr(), sp))
-                hand_over(buf, nbytes)
-                buf ^= 1
+                out.hand_over(text, nbytes)
                 a = b
             p0 = p1
-        if held is not None:
-            held[2].synchronize()
-            sink(pinned[held[0]][:held[1]].numpy().tobytes())
-
-
-def _utf8_binary(stream):
-    """The binary layer under a text stream whose encoding is UTF-8, else None."""
-    buf = getattr(stream, 'buffer', None)
-    enc = (getattr(stream, 'encoding', None) or '').lower().replace('-', '').replace('_', '')
-    return buf if buf is not None and enc == 'utf8' else None
+        out.close()
 
 
 def search_db(args: argparse.Namespace, query_db: str, fp_db: str):

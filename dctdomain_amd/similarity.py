@@ -27,26 +27,42 @@ def to_device_int8(fps) -> torch.Tensor:
     return t.contiguous()
 
 
+def _launch(device, name: str, *args):
+    """Calls the library's export ``name`` with the context of ``device``, ``args`` and the device's current stream (every
+    export's first and last argument); a failure raises what ``_lib.check`` maps its code to."""
+    ctx = _lib.get_context(device.index)
+    _lib.check(getattr(ctx._lib, name)(ctx.handle, *args, C.c_void_p(torch.cuda.current_stream(device).cuda_stream)))
+
+
+def _ld(t: torch.Tensor) -> int:
+    """The row stride of a 2-D tensor in elements; its width where there is at most one row (a size-1 axis may carry any stride)."""
+    return t.stride(0) if t.shape[0] > 1 else t.shape[1]
+
+
+def _check_pair(ta: torch.Tensor, tb: torch.Tensor):
+    if ta.dim() != 2 or tb.dim() != 2 or ta.shape[1] != tb.shape[1]:
+        raise ValueError('fingerprint sets must be 2-D with equal width')
+
+
+def _check_prefix(idx: np.ndarray, rows: int):
+    """The kernels trust the prefix arrays: checked here."""
+    if len(idx) < 1 or idx[0] < 0 or idx[-1] > rows or (np.diff(idx) < 0).any():
+        raise ValueError('idx must be a non-decreasing prefix array within its fingerprint matrix')
+
+
 def l1_matrix(a, b, out: torch.Tensor = None) -> torch.Tensor:
     """int32 (na, nb) matrix of L1 distances, on the GPU.  ``out``: an int32 (na, nb) device tensor with unit column stride to
     write into (any row stride: a column range of a wider tile)."""
     ta, tb = to_device_int8(a), to_device_int8(b)
-    if ta.dim() != 2 or tb.dim() != 2 or ta.shape[1] != tb.shape[1]:
-        raise ValueError('fingerprint sets must be 2-D with equal width')
+    _check_pair(ta, tb)
     if out is None:
         out = torch.empty((ta.shape[0], tb.shape[0]), dtype=torch.int32, device=ta.device)
     elif (out.dtype != torch.int32 or tuple(out.shape) != (ta.shape[0], tb.shape[0]) or out.device != ta.device
           or (out.shape[1] > 1 and out.stride(1) != 1)):
         raise ValueError('out must be an int32 (na, nb) tensor on the fingerprints\' device with unit column stride')
     if out.numel():
-        ctx = _lib.get_context(ta.device.index)
-        stream = torch.cuda.current_stream(ta.device)
-        lda = ta.stride(0) if ta.shape[0] > 1 else ta.shape[1]      # a size-1 axis may carry any stride
-        ldb = tb.stride(0) if tb.shape[0] > 1 else tb.shape[1]
-        ldo = out.stride(0) if out.shape[0] > 1 else out.shape[1]
-        _lib.check(ctx._lib.dctfp_l1_matrix(ctx.handle, ta.data_ptr(), ta.shape[0], lda, tb.data_ptr(),
-                                            tb.shape[0], ldb, ta.shape[1], out.data_ptr(), ldo,
-                                            C.c_void_p(stream.cuda_stream)))
+        _launch(ta.device, 'dctfp_l1_matrix', ta.data_ptr(), ta.shape[0], _ld(ta), tb.data_ptr(), tb.shape[0], _ld(tb), ta.shape[1],
+                out.data_ptr(), _ld(out))
     return out
 
 
@@ -66,12 +82,8 @@ def _block_min_launch(dist: torch.Tensor, ia: torch.Tensor, ib: torch.Tensor):
     mn = torch.empty((npa, npb), dtype=torch.int32, device=dist.device)
     last = torch.empty((npa, npb), dtype=torch.int32, device=dist.device)
     if mn.numel():
-        ctx = _lib.get_context(dist.device.index)
-        stream = torch.cuda.current_stream(dist.device)
-        _lib.check(ctx._lib.dctfp_block_min(ctx.handle, dist.data_ptr(),
-                                            dist.stride(0) if dist.shape[0] > 1 else dist.shape[1], ia.data_ptr(), npa,
-                                            ib.data_ptr(), npb, mn.data_ptr(), last.data_ptr(),
-                                            C.c_void_p(stream.cuda_stream)))
+        _launch(dist.device, 'dctfp_block_min', dist.data_ptr(), _ld(dist), ia.data_ptr(), npa, ib.data_ptr(), npb, mn.data_ptr(),
+                last.data_ptr())
     return mn, last
 
 
@@ -103,12 +115,9 @@ def row_select(dist: torch.Tensor, k: int):
     idx = torch.empty((n_rows, k), dtype=torch.int32, device=dist.device)
     on_device = k <= 1024
     if n_rows:
-        ctx = _lib.get_context(dist.device.index)
-        stream = C.c_void_p(torch.cuda.current_stream(dist.device).cuda_stream)
-        _lib.check(ctx._lib.dctfp_row_select(ctx.handle, dist.data_ptr(), n_rows, n_cols,
-                                             dist.stride(0) if n_rows > 1 else n_cols, k, val.data_ptr(), idx.data_ptr(), stream))
+        _launch(dist.device, 'dctfp_row_select', dist.data_ptr(), n_rows, n_cols, _ld(dist), k, val.data_ptr(), idx.data_ptr())
         if on_device:
-            _lib.check(ctx._lib.dctfp_row_order(ctx.handle, val.data_ptr(), idx.data_ptr(), n_rows, k, stream))
+            _launch(dist.device, 'dctfp_row_order', val.data_ptr(), idx.data_ptr(), n_rows, k)
     v, i = _pair_to_host(val, idx)
     return (v, i) if on_device else order_pairs(v, i)
 
@@ -131,8 +140,80 @@ def _pair_to_host(val: torch.Tensor, idx: torch.Tensor, dtype=np.int64):
     return host[:n].reshape(val.shape), host[n:].reshape(idx.shape)
 
 
+class TextStream:
+    """Device text out to a host ``sink`` through two pinned buffers: ``hand_over`` starts the copy of a chunk into buffer k % 2 and,
+    while it runs, gives ``sink`` the chunk before (a memoryview of the pinned bytes, good for the length of the call);
+    ``close`` gives it the last one.  ``room(nbytes)``: the size of a buffer made for a chunk of ``nbytes`` -- one is made when
+    the chunk does not fit in what is there."""
+
+    def __init__(self, sink, room=lambda nbytes: nbytes):
+        self.sink, self.room = sink, room
+        self.pinned, self.held, self.k = [None, None], None, 0
+
+    def hand_over(self, text: torch.Tensor, nbytes: int):
+        """The first ``nbytes`` of the device uint8 tensor ``text``, as the current stream leaves them."""
+        pin = self.pinned[self.k % 2]                           # (written out by the host two chunks ago)
+        if pin is None or pin.numel() < nbytes:
+            pin = self.pinned[self.k % 2] = torch.empty(self.room(nbytes), dtype=torch.uint8, pin_memory=True)
+        pin[:nbytes].copy_(text[:nbytes], non_blocking=True)
+        done = torch.cuda.Event()
+        done.record(torch.cuda.current_stream(text.device))
+        self.close()                                            # the previous chunk goes out while the device works on this one
+        self.held = (pin, nbytes, done)
+        self.k += 1
+
+    def close(self):
+        if self.held is not None:
+            (pin, nbytes, done), self.held = self.held, None
+            done.synchronize()
+            self.sink(memoryview(pin.numpy())[:nbytes])
+
+
+def _utf8_binary(stream):
+    """The binary layer under a text stream whose encoding is UTF-8, else None: where a ``TextStream`` sink may write its bytes."""
+    buf = getattr(stream, 'buffer', None)
+    enc = (getattr(stream, 'encoding', None) or '').lower().replace('-', '').replace('_', '')
+    return buf if buf is not None and enc == 'utf8' else None
+
+
 def _device_int64(a, device) -> torch.Tensor:
     return torch.as_tensor(np.ascontiguousarray(np.asarray(a, dtype=np.int64)), device=device)
+
+
+def _pair_scores_device(a: torch.Tensor, idx_a: torch.Tensor, b: torch.Tensor, idx_b: torch.Tensor, pairs: torch.Tensor, arg: bool):
+    """The device int32 tensors (min, last) -- with ``arg`` also (arg_a, arg_b) -- of ``pair_min_device`` / ``pair_argmin_device``:
+    ``dctfp_pair_min``, or ``dctfp_pair_argmin`` with its two more outputs."""
+    if pairs.dtype != torch.int32 or pairs.dim() != 2 or pairs.shape[1] != 2 or not pairs.is_contiguous():
+        raise ValueError('pairs must be a contiguous int32 (n, 2) device tensor')
+    if a.dtype != torch.int8 or b.dtype != torch.int8 or a.dim() != 2 or b.dim() != 2 or a.shape[1] != b.shape[1]:
+        raise ValueError('fingerprint sets must be 2-D int8 with equal width')
+    if idx_a.dtype != torch.int64 or idx_b.dtype != torch.int64 or not (idx_a.is_contiguous() and idx_b.is_contiguous()):
+        raise ValueError('prefix arrays must be contiguous int64 device tensors')
+    n, dev = pairs.shape[0], pairs.device
+    out = [torch.full((n,), fill, dtype=torch.int32, device=dev) for fill in (0x7fffffff, 0x7fffffff) + ((-1, -1) if arg else ())]
+    if n and a.shape[0] and b.shape[0]:                         # (no fingerprint on a side: every pair is empty)
+        _launch(dev, 'dctfp_pair_argmin' if arg else 'dctfp_pair_min', pairs.data_ptr(), n, a.data_ptr(), _ld(a), idx_a.data_ptr(),
+                idx_a.numel() - 1, b.data_ptr(), _ld(b), idx_b.data_ptr(), idx_b.numel() - 1, a.shape[1], *(t.data_ptr() for t in out))
+    return tuple(out)
+
+
+def _pair_scores_host(a, idx_a, b, idx_b, pairs, arg: bool):
+    """``_pair_scores_device`` for host arguments, which are checked here, as int64 numpy arrays."""
+    pairs = np.ascontiguousarray(np.asarray(pairs, dtype=np.int64).reshape(-1, 2))
+    ia, ib = np.asarray(idx_a, dtype=np.int64), np.asarray(idx_b, dtype=np.int64)
+    npa, npb = len(ia) - 1, len(ib) - 1
+    ta, tb = to_device_int8(a), to_device_int8(b)
+    _check_pair(ta, tb)
+    _check_prefix(ia, ta.shape[0])
+    _check_prefix(ib, tb.shape[0])
+    if len(pairs) and (pairs[:, 0].min() < 0 or pairs[:, 0].max() >= npa or pairs[:, 1].min() < 0 or pairs[:, 1].max() >= npb):
+        raise IndexError('protein index out of range')
+    n = len(pairs)
+    if n == 0 or ta.shape[0] == 0 or tb.shape[0] == 0:          # (no fingerprint on a side: every pair is empty)
+        return tuple(np.full(n, fill, dtype=np.int64) for fill in (0x7fffffff, 0x7fffffff) + ((-1, -1) if arg else ()))
+    dev = ta.device
+    out = _pair_scores_device(ta, _device_int64(ia, dev), tb, _device_int64(ib, dev), torch.as_tensor(pairs.astype(np.int32), device=dev), arg)
+    return _pair_to_host(*out[:2]) + (_pair_to_host(*out[2:]) if arg else ())
 
 
 def pair_min(a, idx_a, b, idx_b, pairs):
@@ -140,56 +221,14 @@ def pair_min(a, idx_a, b, idx_b, pairs):
     all fingerprint pairs of the two proteins and the L1 of their last rows (``dctfp_pair_min``; no distance matrix).
     ``idx_a`` / ``idx_b``: the npz prefix arrays of the two fingerprint matrices.  A protein without fingerprints gives
     0x7fffffff in both, as ``block_min``."""
-    pairs = np.ascontiguousarray(np.asarray(pairs, dtype=np.int64).reshape(-1, 2))
-    ia, ib = np.asarray(idx_a, dtype=np.int64), np.asarray(idx_b, dtype=np.int64)
-    npa, npb = len(ia) - 1, len(ib) - 1
-    ta, tb = to_device_int8(a), to_device_int8(b)
-    if ta.dim() != 2 or tb.dim() != 2 or ta.shape[1] != tb.shape[1]:
-        raise ValueError('fingerprint sets must be 2-D with equal width')
-    for idx, rows in ((ia, ta.shape[0]), (ib, tb.shape[0])):    # (the kernel trusts the prefix arrays: check them here)
-        if len(idx) < 1 or idx[0] < 0 or idx[-1] > rows or (np.diff(idx) < 0).any():
-            raise ValueError('idx must be a non-decreasing prefix array within its fingerprint matrix')
-    if len(pairs) and (pairs[:, 0].min() < 0 or pairs[:, 0].max() >= npa or pairs[:, 1].min() < 0 or pairs[:, 1].max() >= npb):
-        raise IndexError('protein index out of range')
-    n = len(pairs)
-    if n == 0 or ta.shape[0] == 0 or tb.shape[0] == 0:          # (no fingerprint on a side: every pair is empty)
-        full = np.full(n, 0x7fffffff, dtype=np.int64)
-        return full, full.copy()
-    dev = ta.device
-    mn = torch.empty(n, dtype=torch.int32, device=dev)
-    last = torch.empty(n, dtype=torch.int32, device=dev)
-    tp = torch.as_tensor(pairs.astype(np.int32), device=dev)
-    da, db = _device_int64(ia, dev), _device_int64(ib, dev)
-    ctx = _lib.get_context(dev.index)
-    stream = torch.cuda.current_stream(dev)
-    _lib.check(ctx._lib.dctfp_pair_min(ctx.handle, tp.data_ptr(), n, ta.data_ptr(), ta.stride(0) if ta.shape[0] > 1 else ta.shape[1],
-                                       da.data_ptr(), npa, tb.data_ptr(), tb.stride(0) if tb.shape[0] > 1 else tb.shape[1], db.data_ptr(),
-                                       npb, ta.shape[1], mn.data_ptr(), last.data_ptr(), C.c_void_p(stream.cuda_stream)))
-    return _pair_to_host(mn, last)
+    return _pair_scores_host(a, idx_a, b, idx_b, pairs, False)
 
 
 def pair_min_device(a: torch.Tensor, idx_a: torch.Tensor, b: torch.Tensor, idx_b: torch.Tensor, pairs: torch.Tensor):
     """``pair_min`` with everything on the device already: int8 fingerprint matrices, int64 prefix arrays (the caller's guarantee:
     non-decreasing, within their matrices), ``pairs`` int32 (n, 2) contiguous.  Returns device int32 (min, last); a pair index out
     of range gives -1 in both (the kernel's check)."""
-    if pairs.dtype != torch.int32 or pairs.dim() != 2 or pairs.shape[1] != 2 or not pairs.is_contiguous():
-        raise ValueError('pairs must be a contiguous int32 (n, 2) device tensor')
-    if a.dtype != torch.int8 or b.dtype != torch.int8 or a.dim() != 2 or b.dim() != 2 or a.shape[1] != b.shape[1]:
-        raise ValueError('fingerprint sets must be 2-D int8 with equal width')
-    if idx_a.dtype != torch.int64 or idx_b.dtype != torch.int64 or not (idx_a.is_contiguous() and idx_b.is_contiguous()):
-        raise ValueError('prefix arrays must be contiguous int64 device tensors')
-    n, dev = pairs.shape[0], pairs.device
-    mn = torch.full((n,), 0x7fffffff, dtype=torch.int32, device=dev)
-    last = torch.full((n,), 0x7fffffff, dtype=torch.int32, device=dev)
-    if n == 0 or a.shape[0] == 0 or b.shape[0] == 0:            # (no fingerprint on a side: every pair is empty)
-        return mn, last
-    ctx = _lib.get_context(dev.index)
-    stream = torch.cuda.current_stream(dev)
-    _lib.check(ctx._lib.dctfp_pair_min(ctx.handle, pairs.data_ptr(), n, a.data_ptr(), a.stride(0) if a.shape[0] > 1 else a.shape[1],
-                                       idx_a.data_ptr(), idx_a.numel() - 1, b.data_ptr(), b.stride(0) if b.shape[0] > 1 else b.shape[1],
-                                       idx_b.data_ptr(), idx_b.numel() - 1, a.shape[1], mn.data_ptr(), last.data_ptr(),
-                                       C.c_void_p(stream.cuda_stream)))
-    return mn, last
+    return _pair_scores_device(a, idx_a, b, idx_b, pairs, False)
 
 
 def pair_argmin(a, idx_a, b, idx_b, pairs):
@@ -197,50 +236,13 @@ def pair_argmin(a, idx_a, b, idx_b, pairs):
     arrays, ``arg_a`` / ``arg_b`` = rows counted from 0 within the two proteins, ties to the lowest ``arg_a``, then the lowest
     ``arg_b``; -1 in both when the minimum is 17000 or more or a protein has no fingerprints (the reference's loop keeps no pair
     there, src/dct-sim.py:42-50)."""
-    pairs = np.ascontiguousarray(np.asarray(pairs, dtype=np.int64).reshape(-1, 2))
-    ia, ib = np.asarray(idx_a, dtype=np.int64), np.asarray(idx_b, dtype=np.int64)
-    npa, npb = len(ia) - 1, len(ib) - 1
-    ta, tb = to_device_int8(a), to_device_int8(b)
-    if ta.dim() != 2 or tb.dim() != 2 or ta.shape[1] != tb.shape[1]:
-        raise ValueError('fingerprint sets must be 2-D with equal width')
-    for idx, rows in ((ia, ta.shape[0]), (ib, tb.shape[0])):    # (the kernel trusts the prefix arrays: check them here)
-        if len(idx) < 1 or idx[0] < 0 or idx[-1] > rows or (np.diff(idx) < 0).any():
-            raise ValueError('idx must be a non-decreasing prefix array within its fingerprint matrix')
-    if len(pairs) and (pairs[:, 0].min() < 0 or pairs[:, 0].max() >= npa or pairs[:, 1].min() < 0 or pairs[:, 1].max() >= npb):
-        raise IndexError('protein index out of range')
-    n = len(pairs)
-    if n == 0 or ta.shape[0] == 0 or tb.shape[0] == 0:          # (no fingerprint on a side: every pair is empty)
-        full, none = np.full(n, 0x7fffffff, dtype=np.int64), np.full(n, -1, dtype=np.int64)
-        return full, full.copy(), none, none.copy()
-    dev = ta.device
-    tp = torch.as_tensor(pairs.astype(np.int32), device=dev)
-    mn, last, arg_a, arg_b = pair_argmin_device(ta, _device_int64(ia, dev), tb, _device_int64(ib, dev), tp)
-    return _pair_to_host(mn, last) + _pair_to_host(arg_a, arg_b)
+    return _pair_scores_host(a, idx_a, b, idx_b, pairs, True)
 
 
 def pair_argmin_device(a: torch.Tensor, idx_a: torch.Tensor, b: torch.Tensor, idx_b: torch.Tensor, pairs: torch.Tensor):
     """``pair_argmin`` with everything on the device already (``pair_min_device``'s arguments and guarantees).  Returns device int32
     (min, last, arg_a, arg_b); a pair index out of range gives -1 in all four (the kernel's check)."""
-    if pairs.dtype != torch.int32 or pairs.dim() != 2 or pairs.shape[1] != 2 or not pairs.is_contiguous():
-        raise ValueError('pairs must be a contiguous int32 (n, 2) device tensor')
-    if a.dtype != torch.int8 or b.dtype != torch.int8 or a.dim() != 2 or b.dim() != 2 or a.shape[1] != b.shape[1]:
-        raise ValueError('fingerprint sets must be 2-D int8 with equal width')
-    if idx_a.dtype != torch.int64 or idx_b.dtype != torch.int64 or not (idx_a.is_contiguous() and idx_b.is_contiguous()):
-        raise ValueError('prefix arrays must be contiguous int64 device tensors')
-    n, dev = pairs.shape[0], pairs.device
-    mn = torch.full((n,), 0x7fffffff, dtype=torch.int32, device=dev)
-    last = torch.full((n,), 0x7fffffff, dtype=torch.int32, device=dev)
-    arg_a = torch.full((n,), -1, dtype=torch.int32, device=dev)
-    arg_b = torch.full((n,), -1, dtype=torch.int32, device=dev)
-    if n == 0 or a.shape[0] == 0 or b.shape[0] == 0:            # (no fingerprint on a side: every pair is empty)
-        return mn, last, arg_a, arg_b
-    ctx = _lib.get_context(dev.index)
-    stream = torch.cuda.current_stream(dev)
-    _lib.check(ctx._lib.dctfp_pair_argmin(ctx.handle, pairs.data_ptr(), n, a.data_ptr(), a.stride(0) if a.shape[0] > 1 else a.shape[1],
-                                          idx_a.data_ptr(), idx_a.numel() - 1, b.data_ptr(), b.stride(0) if b.shape[0] > 1 else b.shape[1],
-                                          idx_b.data_ptr(), idx_b.numel() - 1, a.shape[1], mn.data_ptr(), last.data_ptr(),
-                                          arg_a.data_ptr(), arg_b.data_ptr(), C.c_void_p(stream.cuda_stream)))
-    return mn, last, arg_a, arg_b
+    return _pair_scores_device(a, idx_a, b, idx_b, pairs, True)
 
 
 def protein_min(a, idx_a, b, idx_b, out: torch.Tensor = None) -> torch.Tensor:
@@ -252,11 +254,9 @@ def protein_min(a, idx_a, b, idx_b, out: torch.Tensor = None) -> torch.Tensor:
     ia, ib = np.asarray(idx_a, dtype=np.int64), np.asarray(idx_b, dtype=np.int64)
     npa, npb = len(ia) - 1, len(ib) - 1
     ta, tb = _row_major_int8(a), _row_major_int8(b)
-    if ta.dim() != 2 or tb.dim() != 2 or ta.shape[1] != tb.shape[1]:
-        raise ValueError('fingerprint sets must be 2-D with equal width')
-    for idx, rows in ((ia, ta.shape[0]), (ib, tb.shape[0])):    # (the kernel trusts the prefix arrays: check them here)
-        if len(idx) < 1 or idx[0] < 0 or idx[-1] > rows or (np.diff(idx) < 0).any():
-            raise ValueError('idx must be a non-decreasing prefix array within its fingerprint matrix')
+    _check_pair(ta, tb)
+    _check_prefix(ia, ta.shape[0])
+    _check_prefix(ib, tb.shape[0])
     dev = ta.device
     if out is None:
         out = torch.empty((npa, npb), dtype=torch.int32, device=dev)
@@ -271,13 +271,9 @@ def protein_min(a, idx_a, b, idx_b, out: torch.Tensor = None) -> torch.Tensor:
         w = (d + 15) // 16 * 16
         ta, tb = _rows16(ta, w), _rows16(tb, w)
     da, db = _device_int64(ia, dev), _device_int64(ib, dev)
-    ctx = _lib.get_context(dev.index)
-    stream = torch.cuda.current_stream(dev)
-    ldo = out.stride(0) if npa > 1 else npb
     try:
-        _lib.check(ctx._lib.dctfp_protein_min(ctx.handle, ta.data_ptr(), ta.stride(0) if ta.shape[0] > 1 else ta.shape[1], da.data_ptr(),
-                                              npa, tb.data_ptr(), tb.stride(0) if tb.shape[0] > 1 else tb.shape[1], db.data_ptr(), npb, d,
-                                              out.data_ptr(), ldo, C.c_void_p(stream.cuda_stream)))
+        _launch(dev, 'dctfp_protein_min', ta.data_ptr(), _ld(ta), da.data_ptr(), npa, tb.data_ptr(), _ld(tb), db.data_ptr(), npb, d,
+                out.data_ptr(), _ld(out))
     except _lib.DctfpError as e:
         if e.code != _lib.DCTFP_ERR_LIMIT:
             raise
@@ -303,28 +299,20 @@ def threshold_select(dist: torch.Tensor, top: int, bound: int, row_empty=None, c
         return np.zeros(1, dtype=np.int64), np.zeros(0, dtype=np.int64), np.zeros(0, dtype=np.int64)
     dev = dist.device
     ld = dist.stride(0) if n_rows > 1 else n_cols
-    flags = []
-    for f, n in ((row_empty, n_rows), (col_empty, n_cols)):
-        if f is not None:
-            f = torch.as_tensor(np.asarray(f, dtype=np.uint8) if not isinstance(f, torch.Tensor) else f, device=dev).to(torch.uint8).contiguous()
-            if f.numel() != n:
-                raise ValueError('empty flags must have one entry per row / column')
-        flags.append(f)
-    ptr = [f.data_ptr() if f is not None else None for f in flags]
+    flags = _empty_flags(row_empty, n_rows, dev), _empty_flags(col_empty, n_cols, dev)
+    ptr = [_ptr(f) for f in flags]
     bound = int(max(-1, min(int(bound), cap)))
-    ctx = _lib.get_context(dev.index)
-    stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
     count = torch.empty(n_rows, dtype=torch.int32, device=dev)
     cut = torch.empty((n_rows, 2), dtype=torch.int32, device=dev)
-    _lib.check(ctx._lib.dctfp_select_count(ctx.handle, dist.data_ptr(), n_rows, n_cols, ld, ptr[0], ptr[1], cap, bound, max(1, int(top)),
-                                           count.data_ptr(), cut.data_ptr(), stream))
+    _launch(dev, 'dctfp_select_count', dist.data_ptr(), n_rows, n_cols, ld, ptr[0], ptr[1], cap, bound, max(1, int(top)), count.data_ptr(),
+            cut.data_ptr())
     m = count.cpu().numpy().astype(np.int64)
     offsets = np.zeros(n_rows + 1, dtype=np.int64)
     np.cumsum(m, out=offsets[1:])
     key = torch.empty(int(offsets[-1]), dtype=torch.int32, device=dev)
     col = torch.empty(int(offsets[-1]), dtype=torch.int32, device=dev)
-    _lib.check(ctx._lib.dctfp_select_fill(ctx.handle, dist.data_ptr(), n_rows, n_cols, ld, ptr[0], ptr[1], cap, cut.data_ptr(),
-                                          _device_int64(offsets, dev).data_ptr(), int(m.max()), key.data_ptr(), col.data_ptr(), stream))
+    _launch(dev, 'dctfp_select_fill', dist.data_ptr(), n_rows, n_cols, ld, ptr[0], ptr[1], cap, cut.data_ptr(),
+            _device_int64(offsets, dev).data_ptr(), int(m.max()), key.data_ptr(), col.data_ptr())
     k, c = _pair_to_host(key, col)
     for r in np.flatnonzero(m > 1024):                             # (rows the device left in column order)
         s = slice(offsets[r], offsets[r + 1])
@@ -341,6 +329,11 @@ def _empty_flags(flags, n: int, dev):
     if f.numel() != n:
         raise ValueError('empty flags must have one entry per row / column')
     return f
+
+
+def _ptr(t):
+    """The address of an optional device tensor (None: the library's NULL)."""
+    return t.data_ptr() if t is not None else None
 
 
 def _tri_filter_args(tile: torch.Tensor, row0: int, col0: int, bound: int, row_empty, col_empty, cap: int):
@@ -360,11 +353,8 @@ def tri_filter_count(tile: torch.Tensor, row0: int, col0: int, bound: int, row_e
     n_rows, n_cols, ld, re, ce, bound = _tri_filter_args(tile, row0, col0, bound, row_empty, col_empty, cap)
     count = torch.zeros(n_rows, dtype=torch.int32, device=tile.device)
     if n_rows and n_cols:
-        ctx = _lib.get_context(tile.device.index)
-        stream = C.c_void_p(torch.cuda.current_stream(tile.device).cuda_stream)
-        _lib.check(ctx._lib.dctfp_tri_filter_count(ctx.handle, tile.data_ptr(), n_rows, n_cols, ld, int(row0), int(col0),
-                                                   re.data_ptr() if re is not None else None, ce.data_ptr() if ce is not None else None,
-                                                   cap, bound, count.data_ptr(), stream))
+        _launch(tile.device, 'dctfp_tri_filter_count', tile.data_ptr(), n_rows, n_cols, ld, int(row0), int(col0), _ptr(re), _ptr(ce), cap,
+                bound, count.data_ptr())
     return count
 
 
@@ -382,11 +372,8 @@ def tri_filter_fill(tile: torch.Tensor, row0: int, col0: int, bound: int, count:
     if total and n_rows and n_cols:
         offsets = torch.zeros(n_rows + 1, dtype=torch.int64, device=tile.device)
         torch.cumsum(count, 0, out=offsets[1:])
-        ctx = _lib.get_context(tile.device.index)
-        stream = C.c_void_p(torch.cuda.current_stream(tile.device).cuda_stream)
-        _lib.check(ctx._lib.dctfp_tri_filter_fill(ctx.handle, tile.data_ptr(), n_rows, n_cols, ld, int(row0), int(col0),
-                                                  re.data_ptr() if re is not None else None, ce.data_ptr() if ce is not None else None,
-                                                  cap, bound, offsets.data_ptr(), total, out_i.data_ptr(), out_j.data_ptr(), stream))
+        _launch(tile.device, 'dctfp_tri_filter_fill', tile.data_ptr(), n_rows, n_cols, ld, int(row0), int(col0), _ptr(re), _ptr(ce), cap,
+                bound, offsets.data_ptr(), total, out_i.data_ptr(), out_j.data_ptr())
     return out_i, out_j
 
 
@@ -413,11 +400,8 @@ def tri_link(tile: torch.Tensor, row0: int, col0: int, bound: int, parent: torch
     if row0 + n_rows > n_nodes or col0 + n_cols > n_nodes:
         raise IndexError('tile outside the nodes of parent')
     if n_rows and n_cols:
-        ctx = _lib.get_context(tile.device.index)
-        stream = C.c_void_p(torch.cuda.current_stream(tile.device).cuda_stream)
-        _lib.check(ctx._lib.dctfp_tri_link(ctx.handle, tile.data_ptr(), n_rows, n_cols, ld, int(row0), int(col0),
-                                           re.data_ptr() if re is not None else None, ce.data_ptr() if ce is not None else None,
-                                           cap, bound, parent.data_ptr(), n_nodes, stream))
+        _launch(tile.device, 'dctfp_tri_link', tile.data_ptr(), n_rows, n_cols, ld, int(row0), int(col0), _ptr(re), _ptr(ce), cap, bound,
+                parent.data_ptr(), n_nodes)
 
 
 def link_pairs(pi: torch.Tensor, pj: torch.Tensor, parent: torch.Tensor):
@@ -428,9 +412,7 @@ def link_pairs(pi: torch.Tensor, pj: torch.Tensor, parent: torch.Tensor):
         if t.dtype != torch.int32 or t.dim() != 1 or t.numel() != pi.numel() or not t.is_contiguous() or t.device != parent.device:
             raise ValueError('pi / pj must be contiguous int32 device tensors of one length')
     if pi.numel() and n_nodes:
-        ctx = _lib.get_context(parent.device.index)
-        stream = C.c_void_p(torch.cuda.current_stream(parent.device).cuda_stream)
-        _lib.check(ctx._lib.dctfp_link_pairs(ctx.handle, pi.data_ptr(), pj.data_ptr(), pi.numel(), parent.data_ptr(), n_nodes, stream))
+        _launch(parent.device, 'dctfp_link_pairs', pi.data_ptr(), pj.data_ptr(), pi.numel(), parent.data_ptr(), n_nodes)
 
 
 def cluster_labels(parent: torch.Tensor) -> torch.Tensor:
@@ -441,9 +423,7 @@ def cluster_labels(parent: torch.Tensor) -> torch.Tensor:
     n_nodes = _parent_arg(parent, parent.device)
     labels = torch.empty(n_nodes, dtype=torch.int32, device=parent.device)
     if n_nodes:
-        ctx = _lib.get_context(parent.device.index)
-        stream = C.c_void_p(torch.cuda.current_stream(parent.device).cuda_stream)
-        _lib.check(ctx._lib.dctfp_cluster_labels(ctx.handle, parent.data_ptr(), n_nodes, labels.data_ptr(), stream))
+        _launch(parent.device, 'dctfp_cluster_labels', parent.data_ptr(), n_nodes, labels.data_ptr())
     return labels
 
 
@@ -486,81 +466,65 @@ def sim_lines(mn: torch.Tensor, last: torch.Tensor, row0: int, col0: int, ids: L
     ends = row_base[live] + (j_hi - i[live] - 1) * (ids.lens[i[live]] + 14) + (ids.off[j_hi] - ids.off[i[live] + 1])
     if (row_base < 0).any() or (len(ends) and ends.max() > out.numel()):
         raise ValueError('the lines do not fit in the output buffer')
-    dev = mn.device
-    ctx = _lib.get_context(dev.index)
-    stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-    base = _device_int64(row_base, dev)
-    _lib.check(ctx._lib.dctfp_sim_lines(ctx.handle, mn.data_ptr(), last.data_ptr(), n_cols, n_rows, int(row0), int(col0), n_cols,
-                                        ids.bytes_dev.data_ptr(), ids.off_dev.data_ptr(), table.data_ptr(), base.data_ptr(), out.data_ptr(),
-                                        stream))
+    base = _device_int64(row_base, mn.device)
+    _launch(mn.device, 'dctfp_sim_lines', mn.data_ptr(), last.data_ptr(), n_cols, n_rows, int(row0), int(col0), n_cols,
+            ids.bytes_dev.data_ptr(), ids.off_dev.data_ptr(), table.data_ptr(), base.data_ptr(), out.data_ptr())
 
 
-def pair_line_offsets(pi: torch.Tensor, pj: torch.Tensor, ids: LineIds) -> torch.Tensor:
-    """Device int64 (n + 1): where the lines of the pairs (pi[n], pj[n]) start -- the prefix sum of len_i + len_j + 14; the last
-    entry is the text's size."""
+def pair_line_offsets(pi: torch.Tensor, pj: torch.Tensor, ids: LineIds, la: torch.Tensor = None, lb: torch.Tensor = None,
+                      labels: LineIds = None) -> torch.Tensor:
+    """Device int64 (n + 1): where the ``pair_lines`` lines of the pairs (pi[n], pj[n]) start -- the prefix sum of len_i + len_j + 14,
+    with ``labels`` (and the label indices la[n], lb[n]) + len_label_a + len_label_b + 2; the last entry is the text's size."""
     off = torch.zeros(pi.numel() + 1, dtype=torch.int64, device=pi.device)
     if pi.numel():
-        torch.cumsum(ids.lens_dev[pi.long()] + ids.lens_dev[pj.long()] + 14, 0, out=off[1:])
+        lens = ids.lens_dev[pi.long()] + ids.lens_dev[pj.long()] + 14
+        if labels is not None:
+            lens += labels.lens_dev[la.long()] + labels.lens_dev[lb.long()] + 2
+        torch.cumsum(lens, 0, out=off[1:])
     return off
 
 
 def pair_lines(pi: torch.Tensor, pj: torch.Tensor, mn: torch.Tensor, last: torch.Tensor, ids: LineIds, table: torch.Tensor,
-               line_off: torch.Tensor, out: torch.Tensor):
+               line_off: torch.Tensor, out: torch.Tensor, la: torch.Tensor = None, lb: torch.Tensor = None, labels: LineIds = None):
     """all_sim's text for a list of pairs: line n = ``"{id of pi[n]} {id of pj[n]} {a} {b}\\n"`` from byte ``line_off[n]`` of the
     device uint8 buffer ``out`` (``dctfp_pair_lines``), a / b from ``table`` (``dct_sim.score_table`` on the device) by ``mn`` /
     ``last``.  All device tensors: int32 pairs and values, int64 offsets (``pair_line_offsets``).  The kernel skips a line that
-    names a protein outside ``ids`` or that ends beyond ``out``."""
+    names a protein outside ``ids`` or that ends beyond ``out``.
+
+    ``labels`` adds the domain pair behind the scores: ``"... {a} {b} {label la[n]} {label lb[n]}\\n"``
+    (``dctfp_pair_domain_lines``).  ``labels``: the label table of the file as a ``LineIds`` -- one entry per fingerprint row, then
+    the "no pair" entry; ``la`` / ``lb``: device int32 indices into it, also given to ``pair_line_offsets``.  A line that names a
+    label outside ``labels`` is skipped too."""
     n = pi.numel()
-    for t in (pi, pj, mn, last):
+    cols = (pi, pj, mn, last) + ((la, lb) if labels is not None else ())
+    for t in cols:
         if t.dtype != torch.int32 or t.numel() != n or not t.is_contiguous() or t.device != out.device:
-            raise ValueError('pi / pj / mn / last must be contiguous int32 device tensors of one length')
+            raise ValueError(f'pi / pj / mn / last{" / la / lb" if labels is not None else ""} must be contiguous int32 device tensors of one length')
     if line_off.dtype != torch.int64 or line_off.numel() < n or not line_off.is_contiguous() or line_off.device != out.device:
         raise ValueError('line_off must be a contiguous int64 device tensor with an entry per line')
     if table.dtype != torch.uint8 or table.numel() != 2 * 17002 * 5 or out.dtype != torch.uint8 or not out.is_contiguous():
         raise ValueError('table must be uint8 (2, 17002, 5) and out a contiguous uint8 buffer')
     if n == 0:
         return
-    ctx = _lib.get_context(out.device.index)
-    stream = C.c_void_p(torch.cuda.current_stream(out.device).cuda_stream)
-    _lib.check(ctx._lib.dctfp_pair_lines(ctx.handle, n, pi.data_ptr(), pj.data_ptr(), mn.data_ptr(), last.data_ptr(), ids.bytes_dev.data_ptr(),
-                                         ids.off_dev.data_ptr(), len(ids.off) - 1, table.data_ptr(), line_off.data_ptr(), out.data_ptr(),
-                                         out.numel(), stream))
+    tail = (table.data_ptr(), line_off.data_ptr(), out.data_ptr(), out.numel())
+    if labels is None:
+        _launch(out.device, 'dctfp_pair_lines', n, *(t.data_ptr() for t in cols), ids.bytes_dev.data_ptr(), ids.off_dev.data_ptr(),
+                len(ids.off) - 1, *tail)
+    else:
+        _launch(out.device, 'dctfp_pair_domain_lines', n, *(t.data_ptr() for t in cols), ids.bytes_dev.data_ptr(), ids.off_dev.data_ptr(),
+                len(ids.off) - 1, labels.bytes_dev.data_ptr(), labels.off_dev.data_ptr(), len(labels.off) - 1, *tail)
 
 
 def pair_domain_line_offsets(pi: torch.Tensor, pj: torch.Tensor, la: torch.Tensor, lb: torch.Tensor, ids: LineIds,
                              labels: LineIds) -> torch.Tensor:
-    """Device int64 (n + 1): where the ``pair_domain_lines`` lines of the pairs (pi[n], pj[n]) with labels (la[n], lb[n]) start --
-    the prefix sum of len_i + len_j + 14 + len_label_a + len_label_b + 2; the last entry is the text's size."""
-    off = torch.zeros(pi.numel() + 1, dtype=torch.int64, device=pi.device)
-    if pi.numel():
-        torch.cumsum(ids.lens_dev[pi.long()] + ids.lens_dev[pj.long()] + labels.lens_dev[la.long()] + labels.lens_dev[lb.long()] + 16, 0,
-                     out=off[1:])
-    return off
+    """``pair_line_offsets`` with labels, in the argument order of ``pair_domain_lines``."""
+    return pair_line_offsets(pi, pj, ids, la, lb, labels)
 
 
 def pair_domain_lines(pi: torch.Tensor, pj: torch.Tensor, mn: torch.Tensor, last: torch.Tensor, la: torch.Tensor, lb: torch.Tensor,
                       ids: LineIds, labels: LineIds, table: torch.Tensor, line_off: torch.Tensor, out: torch.Tensor):
-    """``pair_lines`` with the domain pair behind the scores: line n = ``"{id of pi[n]} {id of pj[n]} {a} {b} {label la[n]} {label
-    lb[n]}\\n"`` from byte ``line_off[n]`` of ``out`` (``dctfp_pair_domain_lines``).  ``labels``: the label table of the file as a
-    ``LineIds`` -- one entry per fingerprint row, then the "no pair" entry; ``la`` / ``lb``: device int32 indices into it;
-    ``line_off``: ``pair_domain_line_offsets``.  The kernel skips a line that names a protein outside ``ids``, a label outside
-    ``labels`` or that ends beyond ``out``."""
-    n = pi.numel()
-    for t in (pi, pj, mn, last, la, lb):
-        if t.dtype != torch.int32 or t.numel() != n or not t.is_contiguous() or t.device != out.device:
-            raise ValueError('pi / pj / mn / last / la / lb must be contiguous int32 device tensors of one length')
-    if line_off.dtype != torch.int64 or line_off.numel() < n or not line_off.is_contiguous() or line_off.device != out.device:
-        raise ValueError('line_off must be a contiguous int64 device tensor with an entry per line')
-    if table.dtype != torch.uint8 or table.numel() != 2 * 17002 * 5 or out.dtype != torch.uint8 or not out.is_contiguous():
-        raise ValueError('table must be uint8 (2, 17002, 5) and out a contiguous uint8 buffer')
-    if n == 0:
-        return
-    ctx = _lib.get_context(out.device.index)
-    stream = C.c_void_p(torch.cuda.current_stream(out.device).cuda_stream)
-    _lib.check(ctx._lib.dctfp_pair_domain_lines(ctx.handle, n, pi.data_ptr(), pj.data_ptr(), mn.data_ptr(), last.data_ptr(), la.data_ptr(),
-                                                lb.data_ptr(), ids.bytes_dev.data_ptr(), ids.off_dev.data_ptr(), len(ids.off) - 1,
-                                                labels.bytes_dev.data_ptr(), labels.off_dev.data_ptr(), len(labels.off) - 1,
-                                                table.data_ptr(), line_off.data_ptr(), out.data_ptr(), out.numel(), stream))
+    """``pair_lines`` with labels (``line_off``: ``pair_domain_line_offsets``)."""
+    pair_lines(pi, pj, mn, last, ids, table, line_off, out, la, lb, labels)
 
 
 KNN_MAX_K = 1024     # dctfp_l1_knn's limits: larger k or wider rows take l1_matrix + row_select
@@ -570,8 +534,7 @@ PROTEIN_MIN_MAX_D = 512   # dctfp_protein_min's limit: wider rows take l1_matrix
 
 
 def _aligned16(t: torch.Tensor) -> bool:
-    ld = t.stride(0) if t.shape[0] > 1 else t.shape[1]
-    return (t.data_ptr() | ld) & 15 == 0 and t.stride(1) == 1
+    return (t.data_ptr() | _ld(t)) & 15 == 0 and t.stride(1) == 1
 
 
 def _rows16(t: torch.Tensor, w: int) -> torch.Tensor:
@@ -587,8 +550,7 @@ def l1_knn_device(q, db, k: int, col0: int = 0):
     lower row, ``col0`` added to the indices (``dctfp_l1_knn``: distances and selection in one kernel, no distance matrix).
     What ``row_select(l1_matrix(q, db), k)`` returns; k > 1024 or rows wider than 512 bytes go that way."""
     tq, tb = to_device_int8(q), to_device_int8(db)
-    if tq.dim() != 2 or tb.dim() != 2 or tq.shape[1] != tb.shape[1]:
-        raise ValueError('fingerprint sets must be 2-D with equal width')
+    _check_pair(tq, tb)
     nq, nb, d = tq.shape[0], tb.shape[0], tq.shape[1]
     k = min(int(k), nb)
     dev = tq.device
@@ -602,16 +564,13 @@ def l1_knn_device(q, db, k: int, col0: int = 0):
         tq, tb = _rows16(tq, w), _rows16(tb, w)
     val = torch.empty((nq, k), dtype=torch.int32, device=dev)
     idx = torch.empty((nq, k), dtype=torch.int32, device=dev)
-    ctx = _lib.get_context(dev.index)
-    stream = torch.cuda.current_stream(dev)
     # query rows per call sized by the scratch they take: 2 k-lists of k 8-byte keys per (row, database slice), and with several
     # slices (only when there are few row tiles) the slices' lists once more and a half -- about 2 GiB at most per call
     step = max(128, KNN_SCRATCH_BYTES // (32 * k) // 128 * 128)
     for q0 in range(0, nq, step):
         qs = tq[q0:q0 + step]
-        _lib.check(ctx._lib.dctfp_l1_knn(ctx.handle, qs.data_ptr(), qs.shape[0], qs.stride(0) if qs.shape[0] > 1 else tq.shape[1],
-                                         tb.data_ptr(), nb, tb.stride(0) if nb > 1 else tb.shape[1], tq.shape[1], k, int(col0),
-                                         val[q0:].data_ptr(), idx[q0:].data_ptr(), C.c_void_p(stream.cuda_stream)))
+        _launch(dev, 'dctfp_l1_knn', qs.data_ptr(), qs.shape[0], _ld(qs), tb.data_ptr(), nb, _ld(tb), tq.shape[1], k, int(col0),
+                val[q0:].data_ptr(), idx[q0:].data_ptr())
     return val, idx
 
 

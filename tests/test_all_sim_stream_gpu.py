@@ -1,6 +1,6 @@
 """All-against-all streamed from the device (dct_sim.AllPairs, dctfp_sim_lines): the reference's own output on a committed
 synthetic golden, the block-matrix path (dct_sim.Blocks) on random ragged files, a file whose block matrix is never built,
-and the text kernel against Python formatting."""
+the text kernel against Python formatting, and the two-buffer hand-over every device text goes out through."""
 
 import gzip
 import os
@@ -180,3 +180,36 @@ def test_kernel_refuses_a_buffer_too_small():
     out = torch.zeros(20, dtype=torch.uint8, device='cuda')          # the row needs 2 * 15 + 5 = 35 bytes
     with pytest.raises(ValueError):
         sim_lines(mn, mn.clone(), 0, 1, ids, torch.as_tensor(dct_sim.score_table(), device='cuda'), [0], out)
+
+
+# ---- similarity.TextStream
+
+_TEXT_BYTES = 1 << 28       # AllPairs.TEXT_BYTES
+_GROWTH = {
+    'all_pairs': lambda nbytes: max(nbytes, min(_TEXT_BYTES, 2 * nbytes)),
+    'filtered_pairs': lambda nbytes: max(nbytes, 1 << 16),
+    'query_db': lambda nbytes: max(1, 70000),                # (fixed at the text buffer's size, which no chunk exceeds)
+}
+
+
+@pytest.mark.parametrize('rule', sorted(_GROWTH))
+def test_text_stream_hands_every_chunk_over_once_and_one_behind(rule):
+    import torch
+    from dctdomain_amd.similarity import TextStream
+    rng = np.random.default_rng(8)
+    sizes = [1, 3, 70000, 5, 65536, 2]                          # (70 000: beyond a first buffer of 1 << 16 -- it has to grow)
+    chunks = [rng.integers(0, 256, size=n, dtype=np.uint8) for n in sizes]
+    got = []
+    out = TextStream(lambda view: got.append(bytes(view)), room=_GROWTH[rule])
+    for k, c in enumerate(chunks):
+        text = torch.full((len(c) + 7,), 0xEE, dtype=torch.uint8, device='cuda')     # (a text buffer longer than its text)
+        text[:len(c)] = torch.as_tensor(c, device='cuda')
+        out.hand_over(text, len(c))
+        assert len(got) == k                                    # chunk k + 1 handed over: the k before it have gone out
+        text.fill_(0)                                           # (what the sink gets is the chunk as it was handed over)
+    assert got == [c.tobytes() for c in chunks[:-1]]
+    out.close()
+    assert got == [c.tobytes() for c in chunks]
+    out.close()                                                 # (nothing is held: nothing goes out twice)
+    assert len(got) == len(chunks)
+    assert all(p.is_pinned() for p in out.pinned)

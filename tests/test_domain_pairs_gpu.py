@@ -71,7 +71,7 @@ def _ragged_sets(seed, d, n_a=40, n_b=33):
 @pytest.mark.parametrize('d', [1, 7, 480, 512, 516, 1000])
 def test_pair_argmin_ragged_against_the_rule(d):
     import torch
-    from dctdomain_amd.similarity import pair_argmin, pair_argmin_device, pair_min
+    from dctdomain_amd.similarity import pair_argmin, pair_argmin_device, pair_min, pair_min_device
     ia, a, ib, b = _ragged_sets(100 + d, d)
     npa, npb = len(ia) - 1, len(ib) - 1
     i, j = (x.ravel() for x in np.meshgrid(np.arange(npa), np.arange(npb), indexing='ij'))
@@ -83,6 +83,7 @@ def test_pair_argmin_ragged_against_the_rule(d):
     for g, w, name in zip(got, want, ('min', 'last', 'arg_a', 'arg_b')):
         assert np.array_equal(g, w), (d, name)
     ref = pair_min(a, ia, b, ib, pairs)
+    assert len(ref) == 2 and all(r.dtype == np.int64 for r in ref + got)
     assert np.array_equal(got[0], ref[0]) and np.array_equal(got[1], ref[1])
     # rows at any stride and base (the kernel's byte path), and pair indices out of range: -1 in all four outputs
     dev = torch.device('cuda')
@@ -102,6 +103,12 @@ def test_pair_argmin_ragged_against_the_rule(d):
     for g, w, name in zip(out, want, ('min', 'last', 'arg_a', 'arg_b')):
         assert np.array_equal(g[:len(i)], w), (d, 'strided', name)
         assert (g[len(i):] == -1).all(), (d, 'out of range', name)
+    # ... and the form without the position: the same two, by the other instantiation of the kernel
+    both = pair_min_device(views[0], torch.as_tensor(ia, device=dev), views[1], torch.as_tensor(ib, device=dev), tp)
+    assert len(both) == 2 and all(t.dtype == torch.int32 and t.is_cuda for t in both)
+    for g, w, name in zip((t.cpu().numpy().astype(np.int64) for t in both), ref, ('min', 'last')):
+        assert np.array_equal(g[:len(i)], w), (d, 'strided, no position', name)
+        assert (g[len(i):] == -1).all(), (d, 'out of range, no position', name)
 
 
 def test_pair_argmin_tie_order_does_not_depend_on_the_unroll():
@@ -218,6 +225,54 @@ def test_domain_line_kernel_against_python_formatting():
         pair_domain_lines(*tp[:5], tp[5].long(), ids, tab, table, off, buf)
     with pytest.raises(ValueError):
         pair_domain_lines(*tp, ids, tab, table, off[:10].contiguous(), buf)
+
+
+def test_line_kernel_with_and_without_labels_writes_the_same_first_four_fields():
+    """The two instantiations of the line kernel against each other and against Python, at the edges of the score table."""
+    import torch
+    from dctdomain_amd import dct_sim
+    from dctdomain_amd.similarity import LineIds, pair_domain_line_offsets, pair_domain_lines, pair_line_offsets, pair_lines
+    names = ['', 'a', 'B' * 17, 'pé-1']                         # (empty, one byte, more than the sixteen lanes, a two-byte character)
+    labels = ['1', '', '12-40;55-90', '-']
+    edge = [0, 1, 16999, 17000, 17001, 0x7fffffff]
+    pi, pj = [0, 1, 2, 3, 2, 0], [1, 2, 3, 0, 2, 0]
+    mn, last = edge, edge[::-1]
+    la, lb = [0, 1, 2, 3, 1, 2], [3, 2, 1, 0, 1, 2]
+    score = dct_sim.score_table()
+    plain = [f'{names[a]} {names[b]} '.encode('utf8') + bytes(score[0, min(m, 17001)]) + b' ' + bytes(score[1, min(l, 17001)])
+             for a, b, m, l in zip(pi, pj, mn, last)]
+    assert plain[0] == b' a 1.000 0.000' and plain[2].endswith(b' 0.000 0.000') and plain[4] == b'B' * 17 + b' ' + b'B' * 17 + b' 0.000 1.000'
+    named = [t + f' {labels[x]} {labels[y]}'.encode('utf8') for t, x, y in zip(plain, la, lb)]
+    want = {False: b''.join(t + b'\n' for t in plain), True: b''.join(t + b'\n' for t in named)}
+    ids, tab = LineIds(names), LineIds(labels)
+    tp = [torch.as_tensor(np.asarray(v, dtype=np.int32), device='cuda') for v in (pi, pj, mn, last, la, lb)]
+    table = torch.as_tensor(score, device='cuda')
+    got = {}
+    for named_lines in (False, True):
+        if named_lines:
+            off = pair_domain_line_offsets(tp[0], tp[1], tp[4], tp[5], ids, tab)
+        else:
+            off = pair_line_offsets(tp[0], tp[1], ids)
+        total = int(off[-1])
+        assert total == len(want[named_lines])
+        for short in (0, 1):                                    # (1: `out` ends one byte before the last line does)
+            buf = torch.full((5 + total + 3,), 0xAB, dtype=torch.uint8, device='cuda')
+            out = buf[5:5 + total - short]
+            assert out.data_ptr() & 1
+            if named_lines:
+                pair_domain_lines(*tp, ids, tab, table, off, out)
+            else:
+                pair_lines(*tp[:4], ids, table, off, out)
+            text = buf.cpu().numpy().tobytes()
+            assert text[:5] == b'\xab' * 5 and text[5 + total:] == b'\xab' * 3
+            if short:                                           # the last line is left out whole: its bytes keep their fill
+                start = int(off[-2])
+                assert text[5:5 + start] == want[named_lines][:start] and text[5 + start:] == b'\xab' * (total - start + 3)
+            else:
+                assert text[5:5 + total] == want[named_lines]
+                got[named_lines] = text[5:5 + total]
+    cut = [line.rsplit(b' ', 2)[0] for line in got[True].split(b'\n')[:-1]]
+    assert b''.join(c + b'\n' for c in cut) == got[False]
 
 
 # ---- end to end

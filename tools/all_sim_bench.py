@@ -345,7 +345,7 @@ def part_domains(args):
         for flagged in (False, True):
             if flagged:
                 steps = (('protein_min', 'tile'), ('l1_matrix', 'tile'), ('tri_filter_count', 'filter'), ('tri_filter_fill', 'filter'),
-                         ('pair_argmin_device', 'pair_argmin'), ('pair_domain_line_offsets', 'lines'), ('pair_domain_lines', 'lines'))
+                         ('pair_argmin_device', 'pair_argmin'), ('pair_line_offsets', 'lines'), ('pair_lines', 'lines'))
                 real = [(name, timed(name, label)) for name, label in steps]
             for _ in range(args.repeat):
                 spans.clear()
