@@ -53,6 +53,8 @@ int fail(int code, const char* fmt, ...) {
         hipError_t e_ = (expr);                                                                \
         if (e_ != hipSuccess) return fail(DCTFP_ERR_HIP, "%s: %s", #expr, hipGetErrorString(e_)); \
     } while (0)
+// ... and a step of the library's own that fails ends its caller with the same code
+#define RC_TRY(expr) do { const int rc_ = (expr); if (rc_) return rc_; } while (0)
 
 struct DevBuf {
     void* p = nullptr;
@@ -959,7 +961,7 @@ namespace {
 
 constexpr uint32_t kWalkMaxRows = 8192;  // longest domain a wave of the walk kernel streams on its own
 
-// Shapes the walk kernel takes (the rest of its conditions -- alignment, job count -- are judged per call in quantize_impl).
+// Shapes the walk kernel takes (the rest of its conditions -- alignment, job count -- are judged per call in choose_route).
 bool walk_shape(const dctfp_layer& ly) {
 #ifdef DCTFP_GEN_ALL
     return false;
@@ -1029,49 +1031,57 @@ struct PieceSrc {
     int64_t b, row_b;
 };
 
-// Set by dctfp_quantize_one around its dctfp_quantize: the caller waits for the stream before anything else can touch the context.
-thread_local bool tl_sync_call = false;
+// ---- the piece table, by domain --------------------------------------------------------------------------------------
+// Rows, first piece and piece count of every domain of a piece table, and the shortest and the longest domain.
+struct DomainTable {
+    std::vector<uint32_t> len, first, np;
+    uint32_t min_len = 0xffffffffu, max_len = 0;
+    bool sound = true;  // (lengths-only pass) every piece names a domain of the call, has rows, and no domain passes 2^31 rows
+};
 
-// dctfp_quantize proper.  `out_row` (optional): the output row of every domain of THIS piece table (a call that
-// dctfp_quantize has split in two); without it domain d writes row d.  `src` (optional, one per piece; n_data = windows):
-// see PieceSrc -- pieces, seq_rows and seq then speak of the STITCHED sequences.  The caller holds the context's mutex.
-int quantize_impl(dctfp_ctx* ctx, const dctfp_layer* layers, int32_t n_layers, int32_t n_seq, const int64_t* seq_rows,
-                  const dctfp_piece* pieces, int64_t n_pieces, int64_t n_domains, int8_t* out, int64_t out_stride,
-                  hipStream_t stream, const int64_t* out_row, const PieceSrc* src = nullptr, int64_t n_data = 0) {
-    if (!src) n_data = n_seq;
-    bool two_source = false;  // some piece is the mean of two windows' rows: only walk_ab_kernel reads those
-    if (src)
-        for (int64_t i = 0; i < n_pieces && !two_source; ++i) two_source = src[i].b >= 0;
-
-    // ---- validate the piece table, domain lengths --------------------------------
-    std::vector<uint32_t> dom_len((size_t)n_domains, 0), dom_first((size_t)n_domains, 0), dom_np((size_t)n_domains, 0);
-    {
-        int64_t prev = -1;
-        for (int64_t i = 0; i < n_pieces; ++i) {
-            const dctfp_piece& pc = pieces[i];
-            if (pc.domain < 0 || pc.domain >= n_domains || pc.domain < prev)
-                return fail(DCTFP_ERR_INVALID, "piece %lld: domain %d out of order or range", (long long)i, pc.domain);
-            if (pc.seq < 0 || pc.seq >= n_seq)
-                return fail(DCTFP_ERR_INVALID, "piece %lld: sequence %d out of range", (long long)i, pc.seq);
-            if (pc.n_rows <= 0 || pc.row_start < 0 || pc.row_start + pc.n_rows > seq_rows[pc.seq])
-                return fail(DCTFP_ERR_INVALID, "piece %lld: rows [%lld, +%d) outside sequence %d of %lld rows",
-                            (long long)i, (long long)pc.row_start, pc.n_rows, pc.seq, (long long)seq_rows[pc.seq]);
-            if (pc.domain != prev) dom_first[pc.domain] = (uint32_t)i;
-            if ((uint64_t)dom_len[pc.domain] + (uint64_t)pc.n_rows > 0x7fffffffu)
-                return fail(DCTFP_ERR_LIMIT, "domain %d longer than 2^31 rows", pc.domain);
-            dom_len[pc.domain] += (uint32_t)pc.n_rows;
-            dom_np[pc.domain] += 1;
-            prev = pc.domain;
+// The one pass over a piece table.  Strict (`seq_rows` given): the first broken piece is reported and `t` is not to be used.
+// Lengths only (`seq_rows` == nullptr): what dctfp_quantize's split at giant domains and dctfp_quantize_windows's early refusal
+// ask before the strict pass -- the rows per domain over the pieces that can be counted, and whether that was all of them
+// (a broken table goes on to the strict pass as it is: that one reports the error).  Reads nothing but the piece table.
+int build_domain_table(DomainTable& t, const dctfp_piece* pieces, int64_t n_pieces, int64_t n_domains, int32_t n_seq, const int64_t* seq_rows) {
+    const bool strict = seq_rows != nullptr;
+    t.len.assign((size_t)n_domains, 0);
+    if (strict) t.first.assign((size_t)n_domains, 0), t.np.assign((size_t)n_domains, 0);
+    int64_t prev = -1;
+    for (int64_t i = 0; i < n_pieces; ++i) {
+        const dctfp_piece& pc = pieces[i];
+        if (!strict) {
+            if (pc.domain >= 0 && pc.domain < n_domains && pc.n_rows > 0 && (uint64_t)t.len[pc.domain] + (uint64_t)pc.n_rows <= 0x7fffffffu)
+                t.len[pc.domain] += (uint32_t)pc.n_rows;
+            else t.sound = false;
+            continue;
         }
-        for (int64_t d = 0; d < n_domains; ++d)
-            if (dom_np[d] == 0) return fail(DCTFP_ERR_INVALID, "domain %lld has no piece", (long long)d);
+        if (pc.domain < 0 || pc.domain >= n_domains || pc.domain < prev)
+            return fail(DCTFP_ERR_INVALID, "piece %lld: domain %d out of order or range", (long long)i, pc.domain);
+        if (pc.seq < 0 || pc.seq >= n_seq) return fail(DCTFP_ERR_INVALID, "piece %lld: sequence %d out of range", (long long)i, pc.seq);
+        if (pc.n_rows <= 0 || pc.row_start < 0 || pc.row_start + pc.n_rows > seq_rows[pc.seq])
+            return fail(DCTFP_ERR_INVALID, "piece %lld: rows [%lld, +%d) outside sequence %d of %lld rows",
+                        (long long)i, (long long)pc.row_start, pc.n_rows, pc.seq, (long long)seq_rows[pc.seq]);
+        if (pc.domain != prev) t.first[pc.domain] = (uint32_t)i;
+        if ((uint64_t)t.len[pc.domain] + (uint64_t)pc.n_rows > 0x7fffffffu)
+            return fail(DCTFP_ERR_LIMIT, "domain %d longer than 2^31 rows", pc.domain);
+        t.len[pc.domain] += (uint32_t)pc.n_rows;
+        t.np[pc.domain] += 1;
+        prev = pc.domain;
     }
-    uint32_t min_len = 0xffffffffu, max_len_all = 0;
+    for (int64_t d = 0; d < n_domains && strict; ++d)
+        if (t.np[d] == 0) return fail(DCTFP_ERR_INVALID, "domain %lld has no piece", (long long)d);
     for (int64_t d = 0; d < n_domains; ++d) {
-        min_len = std::min(min_len, dom_len[d]);
-        max_len_all = std::max(max_len_all, dom_len[d]);
+        t.min_len = std::min(t.min_len, t.len[d]);
+        t.max_len = std::max(t.max_len, t.len[d]);
     }
+    return DCTFP_OK;
+}
 
+// The per-layer checks.  Reads the layers, the data pointers of the `n_data` sequences (windows) and the domain lengths.
+int validate_layers(const dctfp_layer* layers, int32_t n_layers, int64_t n_data, const int64_t* seq_rows, bool windows,
+                    const DomainTable& dt, int64_t out_stride) {
+    const int64_t n_domains = (int64_t)dt.len.size();
     for (int32_t l = 0; l < n_layers; ++l) {
         const dctfp_layer& ly = layers[l];
         if (!ly.seq_data) return fail(DCTFP_ERR_INVALID, "layer %d: seq_data is NULL", l);
@@ -1083,703 +1093,729 @@ int quantize_impl(dctfp_ctx* ctx, const dctfp_layer* layers, int32_t n_layers, i
         if (ly.out_offset < 0 || (int64_t)ly.out_offset + (int64_t)ly.n_keep * ly.m_keep > out_stride)
             return fail(DCTFP_ERR_INVALID, "layer %d: block [%d, +%d) outside out_stride %lld", l, ly.out_offset, ly.n_keep * ly.m_keep, (long long)out_stride);
         for (int64_t s = 0; s < n_data; ++s)
-            if (!ly.seq_data[s] && (src || seq_rows[s] > 0))
-                return fail(DCTFP_ERR_INVALID, src ? "layer %d: window %lld has no data" : "layer %d: sequence %lld has no data", l, (long long)s);
+            if (!ly.seq_data[s] && (windows || seq_rows[s] > 0))
+                return fail(DCTFP_ERR_INVALID, windows ? "layer %d: window %lld has no data" : "layer %d: sequence %lld has no data", l,
+                            (long long)s);
         // the reference's reshape failure (src/fingerprint.py:194): L_d < n or D < m
-        if ((int64_t)min_len < ly.n_keep) {
+        if ((int64_t)dt.min_len < ly.n_keep) {
             for (int64_t d = 0; d < n_domains; ++d)
-                if ((int64_t)dom_len[d] < ly.n_keep)
+                if ((int64_t)dt.len[d] < ly.n_keep)
                     return fail(DCTFP_ERR_SHAPE, "cannot reshape array of size %lld into shape (%d,) [domain %lld has %u rows < n = %d]",
-                                (long long)dom_len[d] * std::min(ly.m_keep, ly.n_cols), ly.n_keep * ly.m_keep, (long long)d, dom_len[d], ly.n_keep);
+                                (long long)dt.len[d] * std::min(ly.m_keep, ly.n_cols), ly.n_keep * ly.m_keep, (long long)d, dt.len[d], ly.n_keep);
         }
         if (ly.n_cols < ly.m_keep)
             return fail(DCTFP_ERR_SHAPE, "cannot reshape array of size %d into shape (%d,) [layer %d has %d channels < m = %d]",
                         ly.n_keep * ly.n_cols, ly.n_keep * ly.m_keep, l, ly.n_cols, ly.m_keep);
     }
+    return DCTFP_OK;
+}
 
-    // ---- fused groups: consecutive domains of one sequence whose last domain is the whole
-    // sequence and whose other domains tile it exactly (RecCut's output shape).  Their rows are
-    // streamed once: every part also accumulates the whole-protein coefficients.
-    std::vector<int32_t> grp_start((size_t)n_domains), grp_end((size_t)n_domains, -1);
-    std::vector<uint8_t> is_whole((size_t)n_domains, 0);
+// ---- fused groups: consecutive domains of one sequence whose last domain is the whole
+// sequence and whose other domains tile it exactly (RecCut's output shape).  Their rows are
+// streamed once: every part also accumulates the whole-protein coefficients.
+struct FusedGroups {
+    std::vector<int32_t> start, end;  // per domain: first and last domain of its group (end < 0: in no group)
+    std::vector<uint8_t> is_whole;    // per domain: it closes a group
     int64_t n_groups = 0;
-    for (int64_t d = 0; d < n_domains; ++d) grp_start[d] = (int32_t)d;
-    if (ctx->opt_fuse) {
-        std::vector<std::pair<int64_t, int64_t>> runs;  // scratch: (row_start, n_rows) of the parts
-        int64_t d = 0;
-        while (d < n_domains) {
-            const int32_t s0 = pieces[dom_first[d]].seq;
-            int64_t e = d;  // run [d, e] of domains of sequence s0
-            bool one_seq = true;
-            while (true) {
-                for (uint32_t k = 0; k < dom_np[e]; ++k)
-                    if (pieces[dom_first[e] + k].seq != s0) one_seq = false;
-                if (e + 1 < n_domains && pieces[dom_first[e + 1]].seq == s0) ++e;
-                else break;
-            }
-            bool ok = one_seq && e > d;
-            if (ok) {
-                const dctfp_piece& w = pieces[dom_first[e]];
-                ok = dom_np[e] == 1 && w.row_start == 0 && w.n_rows == seq_rows[s0];
-                if (src && !ok) {  // the whole protein of a windowed sequence: one piece per window region, back to back
-                    int64_t pos = 0;
-                    ok = true;
-                    for (uint32_t k = 0; k < dom_np[e] && ok; ++k) {
-                        ok = pieces[dom_first[e] + k].row_start == pos;
-                        pos += pieces[dom_first[e] + k].n_rows;
-                    }
-                    ok = ok && pos == seq_rows[s0];
-                }
-            }
-            if (ok) {
-                runs.clear();
-                for (int64_t q = d; q < e; ++q)
-                    for (uint32_t k = 0; k < dom_np[q]; ++k)
-                        runs.emplace_back(pieces[dom_first[q] + k].row_start, (int64_t)pieces[dom_first[q] + k].n_rows);
-                std::sort(runs.begin(), runs.end());
+};
+
+// Reads the piece table, its DomainTable and the rows per sequence; `windows`: the whole protein may come as one piece per
+// window region.  `enabled` == false (option "fuse" = 0): every domain on its own.
+void find_fused_groups(FusedGroups& fg, bool enabled, const dctfp_piece* pieces, const DomainTable& dt, const int64_t* seq_rows, bool windows) {
+    const int64_t n_domains = (int64_t)dt.len.size();
+    fg.start.resize((size_t)n_domains);
+    fg.end.assign((size_t)n_domains, -1);
+    fg.is_whole.assign((size_t)n_domains, 0);
+    for (int64_t d = 0; d < n_domains; ++d) fg.start[d] = (int32_t)d;
+    if (!enabled) return;
+    std::vector<std::pair<int64_t, int64_t>> runs;  // scratch: (row_start, n_rows) of the parts
+    int64_t d = 0;
+    while (d < n_domains) {
+        const int32_t s0 = pieces[dt.first[d]].seq;
+        int64_t e = d;  // run [d, e] of domains of sequence s0
+        bool one_seq = true;
+        while (true) {
+            for (uint32_t k = 0; k < dt.np[e]; ++k)
+                if (pieces[dt.first[e] + k].seq != s0) one_seq = false;
+            if (e + 1 < n_domains && pieces[dt.first[e + 1]].seq == s0) ++e;
+            else break;
+        }
+        bool ok = one_seq && e > d;
+        if (ok) {
+            const dctfp_piece& w = pieces[dt.first[e]];
+            ok = dt.np[e] == 1 && w.row_start == 0 && w.n_rows == seq_rows[s0];
+            if (windows && !ok) {  // the whole protein of a windowed sequence: one piece per window region, back to back
                 int64_t pos = 0;
-                for (auto& r : runs) {
-                    if (r.first != pos) { ok = false; break; }
-                    pos += r.second;
+                ok = true;
+                for (uint32_t k = 0; k < dt.np[e] && ok; ++k) {
+                    ok = pieces[dt.first[e] + k].row_start == pos;
+                    pos += pieces[dt.first[e] + k].n_rows;
                 }
                 ok = ok && pos == seq_rows[s0];
             }
-            if (ok) {
-                for (int64_t q = d; q <= e; ++q) {
-                    grp_start[q] = (int32_t)d;
-                    grp_end[q] = (int32_t)e;
-                }
-                is_whole[e] = 1;
-                ++n_groups;
+        }
+        if (ok) {
+            runs.clear();
+            for (int64_t q = d; q < e; ++q)
+                for (uint32_t k = 0; k < dt.np[q]; ++k) runs.emplace_back(pieces[dt.first[q] + k].row_start, (int64_t)pieces[dt.first[q] + k].n_rows);
+            std::sort(runs.begin(), runs.end());
+            int64_t pos = 0;
+            for (auto& r : runs) {
+                if (r.first != pos) { ok = false; break; }
+                pos += r.second;
             }
-            d = e + 1;
+            ok = ok && pos == seq_rows[s0];
+        }
+        if (ok) {
+            for (int64_t q = d; q <= e; ++q) {
+                fg.start[q] = (int32_t)d;
+                fg.end[q] = (int32_t)e;
+            }
+            fg.is_whole[e] = 1;
+            ++fg.n_groups;
+        }
+        d = e + 1;
+    }
+}
+
+// Consecutive layers of one geometry are planned and launched together: one past the last layer of the group that starts at l0.
+int32_t layer_group_end(const dctfp_layer* layers, int32_t l0, int32_t n_layers) {
+    const dctfp_layer& g = layers[l0];
+    int32_t l1 = l0 + 1;
+    while (l1 < n_layers && layers[l1].n_cols == g.n_cols && layers[l1].dtype == g.dtype && layers[l1].ld == g.ld &&
+           layers[l1].n_keep == g.n_keep && layers[l1].m_keep == g.m_keep) ++l1;
+    return l1;
+}
+
+constexpr char kNotWalkShape[] = "kept sizes / width outside the one-launch kernel's (n = 3, 64 < m <= 80, 512 <= D <= 2560, D % 4 == 0)";
+
+// Why the walk kernel would not take a layer group whatever the size of the call (nullptr: it would), in the words and the
+// order dctfp_quantize_windows reports.  `aligned()` (rows_aligned16 of the group) is asked only where the geometry passes, and
+// nothing is divided by anything: safe on layers that validate_layers has not seen yet.
+template <typename Aligned>
+const char* walk_refusal(const dctfp_layer& g, uint32_t max_len, Aligned aligned) {
+    if (!walk_shape(g)) return kNotWalkShape;
+    if (!aligned()) return "rows are not 16-byte aligned";
+    return walk_rows_ok(g, max_len) ? nullptr : "a domain above 8 192 rows";
+}
+// ... and why its two-source builds (rows that are the float32 mean of two windows' rows) would not take a call of `n_jobs` jobs
+template <typename Aligned>
+const char* two_source_refusal(const dctfp_ctx* ctx, const dctfp_layer& g, uint32_t max_len, int64_t n_jobs, Aligned aligned) {
+    if (!g.seq_data || g.dtype != DCTFP_F32) return "windows are averaged in float32 (as dctfp_stitch)";
+    if (g.m_keep > 80) return kNotWalkShape;
+    if (const char* why = walk_refusal(g, max_len, aligned)) return why;
+    return walk_by_path(ctx, n_jobs) ? nullptr : "fewer than 256 jobs (layers x domains) in the call";
+}
+
+// ---- which kernels run a layer group ---------------------------------------------------------------------------------
+struct Route {
+    enum Kind { kTrivial, kWalk, kGen, kTwoKernels } kind = kTwoKernels;
+    bool one_launch() const { return kind == kWalk || kind == kGen; }
+    bool fuse = false, gen_fuse = false;  // the parts of a fused group also accumulate their whole protein (... in the general kernel's fused builds)
+    int vec = 1;                          // channels per lane of the row loads (walk kernel, stage A)
+    int walk_s = 0;                       // waves per workgroup of the one-launch kernel
+    int gen_vec = 0, gen_waves = 0, gen_slots = 0;  // the general kernel's layout (gen_slots == 0: the shape does not fit it)
+    int64_t wg_per_cu = 1;                // workgroups of the one-launch kernel the chip holds at once, per CU
+};
+
+// Workgroups of the general walk kernel a CU holds at once with `slots` Y' slots per workgroup: by waves (the kernel's builds
+// hold 5 .. 7 waves per SIMD) and by LDS.
+int64_t gen_wg_per_cu(int n, int m, int waves, int vec, int slots) {
+    return std::min<int64_t>(std::max<int64_t>(1, 20 / waves), (int64_t)(kGenLdsBudget / ((size_t)slots * gen_slot_bytes(n, m, waves, vec) + 64)));
+}
+
+// The one decision.  Reads: the geometry of the group's first layer (all layers of a group share it), `vec_ok` (rows_aligned16
+// of the group), the longest domain of the call, the job count (layers x domains), whether the call has fused groups, and
+// the options "path", "fuse", "gen_fuse".
+//
+// The walk kernel (stage A + B in one launch, nothing but int8 written) takes the production
+// shapes: n = 3, 64 < m <= 80 (five 16-column groups), rows read 4 channels per lane, 512 <= D <= 2560, no giant domain
+// (a wave streams all rows of its channels).  Every other shape of float32 / float64 rows that fits the LDS goes to the
+// general walk kernel (round 4); the rest -- and calls too small to fill the chip -- run stage A -> Y' -> stage B.
+// (rows are addressed through a 32-bit buffer offset: a piece of at most kWalkMaxRows rows stays below 2^31 bytes)
+// Measured (profiles/r02): the walk kernel wins at every width it takes -- D = 2560 (10-wave workgroups, one per CU)
+// since its flush contracts the even and odd halves of the basis apart: 5.3 against 4.9-5.25 TB/s on config 4.
+// A small call (a protein at a time, the reference's calling pattern) is latency-bound: there the two-kernel path,
+// which spreads one job over slabs x 8 waves, finishes first.
+Route choose_route(const dctfp_ctx* ctx, const dctfp_layer& g, bool vec_ok, uint32_t max_len, int64_t n_jobs, bool has_groups) {
+    Route r;
+    const int n = g.n_keep, m = g.m_keep;
+    const bool trivial = (n == 1 || m == 1);  // single resampled value -> 0/0 -> 0
+    const int vec_want = (int)(16 / dtype_size(g.dtype));  // 16 bytes per lane
+    const bool rows_ok = walk_rows_ok(g, max_len);
+    const bool walk_ok = !trivial && !walk_refusal(g, max_len, [&] { return vec_ok; });
+    const bool use_walk = walk_ok && walk_by_path(ctx, n_jobs);
+    if (!trivial && !walk_ok && rows_ok && n >= 2 && m >= 2 && (g.dtype == DCTFP_F32 || g.dtype == DCTFP_F64)) {
+        r.gen_vec = vec_ok ? vec_want : 1;
+        r.gen_waves = (g.n_cols + 64 * r.gen_vec - 1) / (64 * r.gen_vec);
+        r.gen_slots = r.gen_waves <= 16 && gen_slot_bytes(n, m, r.gen_waves, r.gen_vec) + 64 <= kGenLdsBudget ? 1 : 0;
+        // A second slot (a wave writes the next job's Y' while the last arrival of this one still sums) only where it
+        // costs no workgroup per CU: resident workgroups hide the end of a job (epilogue, contraction, row sums), and a
+        // wave reaches its next write a whole job's stream after the last one anyway.
+        if (r.gen_slots == 1 && gen_wg_per_cu(n, m, r.gen_waves, r.gen_vec, 2) >= gen_wg_per_cu(n, m, r.gen_waves, r.gen_vec, 1)) r.gen_slots = 2;
+    }
+    // (a shape whose slot leaves fewer than eight waves resident per CU -- [8, 128] at D = 1280: one workgroup of five -- streams
+    //  at 3.8 TB/s there against 5.4 through the two kernels: only when asked for)
+    const int64_t gen_resident = r.gen_slots > 0 ? r.gen_waves * gen_wg_per_cu(n, m, r.gen_waves, r.gen_vec, r.gen_slots) : 0;
+    // (... and it streams every job on its own: where proteins come as parts + whole protein, the fused stage A of the two
+    //  kernels reads the rows once -- 3.6-4.7 against 2.1-2.3 TB/s on the c4 / c5 mixes at [5, 44] / [3, 85] / [4, 80],
+    //  tools/gen_probe.py; on whole-protein batches the general kernel is 2-6 % ahead)
+    // Round 5: the general kernel has FUSED builds for n <= 5 (its walks then read the rows of a protein once, as the tuned
+    // kernel's); with them and four k-steps of stage-B fragments in flight it streams the c4 / c5 mixes at [5, 44] / [3, 85] /
+    // [4, 80] at 2.6-3.3 TB/s (2.1-2.5 before) -- and the two kernels at 3.6-5.0 (tools/gen_probe.py,
+    // profiles/r05/gen_probe_fused.txt): a flush per ~ 100-row job, its Y' slot in LDS holding the workgroups per CU down, is
+    // not how short jobs want to be run.  So such batches still go to the two kernels by default; "path" = 2 gets the fused walks.
+    const bool would_fuse = ctx->opt_fuse && has_groups;
+    const bool use_gen = r.gen_slots > 0 && (ctx->opt_path == 2 || (ctx->opt_path == 0 && n_jobs >= 256 && gen_resident >= 8 && !would_fuse));
+    r.gen_fuse = use_gen && would_fuse && n <= kGenFusedMaxN && r.gen_waves <= kGenFusedMaxWaves && ctx->opt_gen_fuse && n_jobs >= 64;
+    // (a small call wants parallelism, not fewer bytes: every job on its own workgroups)
+    r.fuse = !trivial && has_groups && n_jobs >= 64 && (!use_gen || r.gen_fuse);
+    r.kind = trivial ? Route::kTrivial : (use_gen ? Route::kGen : (use_walk ? Route::kWalk : Route::kTwoKernels));
+    r.vec = vec_ok ? vec_want : 1;
+    // Fused walks of half-precision rows: 8 channels per lane mean two accumulator sets of 8 -- 27..37 registers per lane
+    // spilled, and scratch writes beside the row stream cost far more than their bytes (the c5 mix in float16 took 19 ms
+    // against 12.6 in float32).  4 channels per lane (8-byte loads) fit the registers.
+    if (r.fuse && n == 3 && r.vec == 8) r.vec = 4;
+    if (r.one_launch()) {
+        // workgroups of the kernel the chip holds at once, per CU (LDS: 5 / 3 / 1 at 3 / 5 / 10 waves of the walk kernel)
+        r.walk_s = use_gen ? r.gen_waves : (g.n_cols <= 768 ? 3 : (g.n_cols <= 1280 ? 5 : 10));
+        r.wg_per_cu = use_gen ? gen_wg_per_cu(n, m, r.gen_waves, r.gen_vec, r.gen_slots) : (r.walk_s == 3 ? 5 : (r.walk_s == 5 ? 3 : 1));
+    }
+    return r;
+}
+
+// Typed views of a staging layout, from either base pointer: the pinned host buffer or what the kernels read.
+struct TableView { JobB* jobb; JobA* joba; PieceA* pieces; Walk* walks; Run* runs; BasisJob* basis; };
+// The six tables of a layer group in one buffer (the run and cosine-table lists are bounded by the job count).
+struct TableLayout {
+    size_t jobb, joba, piece, walk, run, btab, bytes;
+    TableLayout(int64_t n_jobs, int ng, int64_t n_pieces, int64_t n_domains) {
+        jobb = 0;
+        joba = align_up(jobb + (size_t)n_jobs * sizeof(JobB), 16);
+        piece = align_up(joba + (size_t)n_jobs * sizeof(JobA), 16);
+        walk = align_up(piece + (size_t)ng * n_pieces * sizeof(PieceA), 16);
+        run = align_up(walk + (size_t)n_jobs * sizeof(Walk), 16);
+        btab = align_up(run + (size_t)n_jobs * sizeof(Run), 16);
+        bytes = align_up(btab + (size_t)n_domains * sizeof(BasisJob), 16);
+    }
+    TableView view(char* base) const {
+        return {(JobB*)(base + jobb), (JobA*)(base + joba), (PieceA*)(base + piece),
+                (Walk*)(base + walk), (Run*)(base + run), (BasisJob*)(base + btab)};
+    }
+};
+
+// One cosine table per distinct domain length, from the context's cache, in domain order; tables the context has not seen
+// yet are reserved in the arena and listed in `fresh`.
+int lookup_basis(dctfp_ctx* ctx, const DomainTable& dt, int nk, std::vector<double*>& dom_tab, std::vector<BasisJob>& fresh) {
+    const int64_t n_domains = (int64_t)dt.len.size();
+    LenTable seen(dt.max_len);  // length -> index of the first domain with it
+    for (int64_t d = 0; d < n_domains; ++d) {
+        if (seen.has(dt.len[d])) {
+            dom_tab[d] = dom_tab[seen[dt.len[d]]];
+        } else {
+            RC_TRY(basis_lookup(ctx, dt.len[d], nk, &dom_tab[d], fresh));
+            seen.set(dt.len[d], (uint32_t)d);
         }
     }
+    return DCTFP_OK;
+}
 
-    // ---- groups of consecutive layers with the same geometry ----------------------
-    if ((int64_t)ctx->basis_doubles > ctx->basis_cap_doubles) {  // the cosine-table arena starts over (nothing of this call uses it yet)
-        int rcp = basis_purge(ctx);
-        if (rcp) return rcp;
+// JobB / JobA of every (layer, domain) and PieceA of every (layer, piece) of the group.  Reads the layers' data pointers, the piece table (and
+// `src`, windows), the domain table, the fused groups (`fuse`: whether the route uses them), every domain's cosine table and the output rows.
+void fill_jobs(const TableView& h, const dctfp_layer* group, int ng, const dctfp_piece* pieces, int64_t n_pieces, const PieceSrc* src,
+               const DomainTable& dt, const FusedGroups& fg, bool fuse, double* const* dom_tab, const int64_t* out_row, int64_t out_stride) {
+    const int64_t n_domains = (int64_t)dt.len.size();
+    const size_t esz = dtype_size(group[0].dtype);
+    for (int li = 0; li < ng; ++li) {
+        const dctfp_layer& ly = group[li];
+        for (int64_t d = 0; d < n_domains; ++d) {
+            const int64_t job = (int64_t)li * n_domains + d;
+            h.jobb[job].out_off = (out_row ? out_row[d] : d) * out_stride + ly.out_offset;
+            h.joba[job] = JobA{(uint32_t)((int64_t)li * n_pieces + dt.first[d]), dt.np[d], dt.len[d], 0, dom_tab[d], nullptr, nullptr};
+            if (fuse && fg.end[d] >= 0 && !fg.is_whole[d]) {
+                const int64_t w = fg.end[d];  // the whole-protein domain closes the group
+                h.joba[job].w_basis = dom_tab[w];
+                // (windows: row 0 of a sequence is row 0 of its first window -- a window is longer than the overlap)
+                h.joba[job].w_ref = src ? ly.seq_data[src[dt.first[w]].a] : ly.seq_data[pieces[dt.first[w]].seq];
+            }
+        }
+        uint32_t t0 = 0;
+        int32_t prev_dom = -1;
+        for (int64_t i = 0; i < n_pieces; ++i) {
+            const dctfp_piece& pc = pieces[i];
+            if (pc.domain != prev_dom) t0 = 0;
+            prev_dom = pc.domain;
+            auto row = [&](int64_t seq, int64_t r) { return (const char*)ly.seq_data[seq] + (size_t)r * (size_t)ly.ld * esz; };
+            const char* ptr = src ? row(src[i].a, src[i].row_a) : row(pc.seq, pc.row_start);
+            const char* ptr2 = src && src[i].b >= 0 ? row(src[i].b, src[i].row_b) : nullptr;
+            h.pieces[(int64_t)li * n_pieces + i] = PieceA{ptr, (uint32_t)pc.n_rows, t0, (uint32_t)pc.row_start, 0, ptr2};
+            t0 += (uint32_t)pc.n_rows;
+        }
     }
-    int32_t l0 = 0;
-    while (l0 < n_layers) {
-        int32_t l1 = l0 + 1;
-        const dctfp_layer& g = layers[l0];
-        while (l1 < n_layers && layers[l1].n_cols == g.n_cols && layers[l1].dtype == g.dtype && layers[l1].ld == g.ld &&
-               layers[l1].n_keep == g.n_keep && layers[l1].m_keep == g.m_keep)
-            ++l1;
-        const int ng = l1 - l0;
-        const int n = g.n_keep, m = g.m_keep, nk = n - 1;
-        const int64_t n_jobs = (int64_t)ng * n_domains;
-        const size_t esz = dtype_size(g.dtype);
-        const bool trivial = (n == 1 || m == 1);  // single resampled value -> 0/0 -> 0
+}
 
-        // staging layout (the run and cosine-table lists are bounded by the job count)
-        const size_t off_jobb = 0;
-        const size_t off_joba = align_up(off_jobb + (size_t)n_jobs * sizeof(JobB), 16);
-        const size_t off_piece = align_up(off_joba + (size_t)n_jobs * sizeof(JobA), 16);
-        const size_t off_walk = align_up(off_piece + (size_t)ng * n_pieces * sizeof(PieceA), 16);
-        const size_t off_run = align_up(off_walk + (size_t)n_jobs * sizeof(Walk), 16);
-        const size_t off_btab = align_up(off_run + (size_t)n_jobs * sizeof(Run), 16);
-        const size_t max_bytes = align_up(off_btab + (size_t)n_domains * sizeof(BasisJob), 16);
+// The walks of jobs [j_begin, j_end), never begun inside a fused group: its parts and its whole protein in one walk, every other job on its
+// own.  Job ids are relative to `base` (0: the whole call, walk kernels; a chunk's first job: stage A).  Returns the number of walks written.
+int64_t build_walks(Walk* walks, int64_t j_begin, int64_t j_end, int64_t base, int64_t n_domains, bool fuse, const FusedGroups& fg) {
+    int64_t n_walks = 0;
+    for (int64_t j = j_begin; j < j_end;) {
+        const int64_t d = j % n_domains;
+        const int64_t parts = fuse && fg.end[d] >= 0 ? fg.end[d] - d : 0;  // > 0: d is the first part of a fused group
+        walks[n_walks++] = parts ? Walk{(uint32_t)(j - base), (uint32_t)parts, (int32_t)(j - base + parts), 0} : Walk{(uint32_t)(j - base), 1, -1, 0};
+        j += parts + 1;
+    }
+    return n_walks;
+}
+
+constexpr int walk_g = 4;  // jobs per flush: the rows of an MFMA tile (a flush costs the same MFMAs for 1..4 jobs)
+
+// Jobs per run (= per workgroup) of a one-launch kernel, and whether the runs go out longest first.  Reads the options
+// "ab_run_jobs" / "ab_longest_first", the route, the rows the jobs stream and the size of the chip.
+int64_t run_length(const dctfp_ctx* ctx, const Route& route, const DomainTable& dt, const FusedGroups& fg, int64_t n_jobs, size_t esz,
+                   bool* longest_first) {
+    const int64_t n_domains = (int64_t)dt.len.size();
+    int64_t want = ctx->opt_ab_run_jobs;
+    *longest_first = ctx->opt_ab_longest_first == 1;
+    if (want != 0) return want;
+    // Rows per job decide (profiles/r02/path_probe_run_jobs.log): long jobs (whole proteins) want ONE per
+    // workgroup -- a flush of one job costs the MFMAs of four, nothing beside 500 rows, and 4 x as many, smaller
+    // workgroups drain the chip more evenly at the end (C2 6.79 -> 6.97 TB/s, C3 6.70 -> 6.90); short jobs
+    // (domains) want many per workgroup, so that few flushes are partial (c4 5.80 -> 5.91 at 16).
+    int64_t rows = 0;
+    for (int64_t d = 0; d < n_domains; ++d)
+        if (!(route.fuse && fg.is_whole[d])) rows += dt.len[d];
+    // (rows of 4-byte elements: a half-precision job of 500 rows weighs like 250 -- 4.40 ms per C2 batch with four
+    //  jobs per workgroup, 4.85 with one)
+    const int64_t job_rows = rows * (int64_t)esz / 4 / std::max<int64_t>(1, n_domains);  // whole-protein jobs of fused walks stream nothing
+    const int64_t by_rows = job_rows >= 384 ? 1 : 4 * walk_g;
+    if (ctx->opt_ab_longest_first == 0) *longest_first = by_rows >= walk_g && route.walk_s == 10 && route.kind != Route::kGen;
+    const int64_t slots = (int64_t)ctx->n_cu * route.wg_per_cu;
+    if (n_jobs <= 6 * slots * by_rows) {
+        // fewer than a handful of rounds at that size: ONE round of equal workgroups instead (a second, partly
+        // filled round costs as much as a full one: 1 024 whole-protein jobs 509 us as 1 024 workgroups, 477 as 512)
+        want = std::max<int64_t>(1, (n_jobs + slots - 1) / slots);
+        if (by_rows >= walk_g && want > 1) want = (want + walk_g - 1) / walk_g * walk_g;  // short jobs: full flushes
+        want = std::min<int64_t>(want, 4 * walk_g);
+    } else {
+        want = by_rows;
+        while (want > walk_g && n_jobs / want < 8192) want -= walk_g;  // ... but ten rounds of workgroups at least
+    }
+    return want;
+}
+
+// Longest run first, for batches of domains at D > 1280 (one workgroup per CU: 256 slots, so the last round
+// weighs most): the workgroups that start last are the short ones and the chip drains together (c4 +2.8 %).
+// With 1 280 slots (D = 640) it gains nothing in the kernel and costs 70 us of host time per 340 000 jobs; on
+// whole-protein batches it would put every short protein -- the jobs whose flush weighs most -- at the end
+// together (C3 -1.5 %).  Counting sort on the rows a run streams, 16-row buckets, input order within a bucket.
+void sort_runs_longest_first(const TableView& h, int64_t n_runs, const DomainTable& dt) {
+    constexpr uint32_t kBuckets = 4096;
+    const int64_t n_domains = (int64_t)dt.len.size();
+    std::vector<uint32_t> key((size_t)n_runs), start(kBuckets + 1, 0);
+    for (int64_t r = 0; r < n_runs; ++r) {
+        uint64_t rows = 0;
+        for (uint32_t w = h.runs[r].walk_begin; w < h.runs[r].walk_begin + h.runs[r].n_walks; ++w)
+            for (uint32_t p = 0; p < h.walks[w].n_parts; ++p) rows += (uint64_t)dt.len[(h.walks[w].job_begin + p) % n_domains];
+        key[r] = kBuckets - 1 - (uint32_t)std::min<uint64_t>(rows >> 4, kBuckets - 1);  // descending
+        ++start[key[r] + 1];
+    }
+    for (uint32_t b = 0; b < kBuckets; ++b) start[b + 1] += start[b];
+    std::vector<Run> sorted((size_t)n_runs);
+    for (int64_t r = 0; r < n_runs; ++r) sorted[start[key[r]]++] = h.runs[r];
+    std::memcpy(h.runs, sorted.data(), (size_t)n_runs * sizeof(Run));
+}
+
+// The runs of a one-launch kernel (one workgroup each) over the `n_walks` walks of the whole call in h.walks: consecutive walks until a run
+// holds `want` jobs (a multiple of the flush group, so that most flushes are full); fewer jobs per run when the batch is small, to keep every
+// CU busy.  Reads the options "ab_taper" / "ab_align" and what run_length reads; returns the number of runs written to h.runs.
+int64_t plan_runs(const dctfp_ctx* ctx, const Route& route, const TableView& h, int64_t n_walks, const DomainTable& dt, const FusedGroups& fg,
+                  int64_t n_jobs, size_t esz) {
+    bool longest_first = false;
+    const int64_t want = run_length(ctx, route, dt, fg, n_jobs, esz, &longest_first);
+    // The end of the launch: its last workgroups run on a chip that is emptying (tools/walk_trace.py: the last 5 % of a
+    // c5 launch hold 15 % of the waves), for as long as ONE workgroup lives.  The jobs of the last round of workgroups
+    // therefore go out in runs of one flush group: four times as many workgroups, a quarter as long.
+    int64_t taper_from = n_jobs;  // runs that start at or after this job are short
+    if (want > walk_g && ctx->opt_ab_taper) {
+        const int64_t slots = (int64_t)ctx->n_cu * route.wg_per_cu;
+        taper_from = std::max<int64_t>(0, n_jobs - slots * want * ctx->opt_ab_taper / 4);
+    }
+    auto jobs_of = [&](int64_t w) { return h.walks[w].n_parts + (h.walks[w].whole_job >= 0 ? 1u : 0u); };
+    int64_t n_runs = 0, jobs_done = 0;
+    for (int64_t w = 0; w < n_walks;) {
+        Run& rn = h.runs[n_runs++];
+        rn.walk_begin = (uint32_t)w;
+        rn.job_begin = h.walks[w].job_begin;
+        uint32_t jobs_in = 0;
+        const int64_t want_here = jobs_done >= taper_from ? walk_g : want;
+        while (w < n_walks && (jobs_in == 0 || (int64_t)jobs_in < want_here)) {
+            jobs_in += jobs_of(w);
+            ++w;
+        }
+        // A run whose job count is no multiple of the flush group ends in a partial flush, which costs the MFMAs of a
+        // full one (walks of k parts + whole protein rarely add up).  Look one or two walks further for a count that is:
+        // c4 +1.9 %, c5 +0.2 %; looking further or longer runs gain nothing (profiles/r04/experiments/ab_run_alignment_and_length.txt).
+        if (ctx->opt_ab_align && want_here > walk_g && jobs_in % (uint32_t)walk_g != 0) {
+            uint32_t more = jobs_in;
+            for (int64_t x = w; x < n_walks && x < w + ctx->opt_ab_align && more < jobs_in + 2u * (uint32_t)walk_g; ++x) {
+                more += jobs_of(x);
+                if (more % (uint32_t)walk_g == 0) {
+                    jobs_in = more;
+                    w = x + 1;
+                    break;
+                }
+            }
+        }
+        rn.n_walks = (uint32_t)(w - rn.walk_begin);
+        rn.n_jobs = jobs_in;
+        jobs_done += jobs_in;
+    }
+    if (longest_first && n_runs > 1) sort_runs_longest_first(h, n_runs, dt);
+    return n_runs;
+}
+
+struct Chunk { int64_t j0, j1, w0, wn; };  // jobs [j0, j1), their walks [w0, w0 + wn)
+struct TwoKernelPlan {
+    std::vector<Chunk> chunks;
+    int slots = 1;         // regions of the scratch ring ...
+    int64_t sub = 1;       // ... of this many jobs each
+    int64_t avg_rows = 0;  // rows per streamed job (launch-shape heuristic)
+    bool small_b = false, packed = false;  // stage B over 64-channel slabs; Y' as one float64 t row + one state byte per channel
+    size_t job_bytes = 0;  // Y' of one job
+    int ldy = 0, n_slabs = 0;
+};
+
+// The chunk plan of the two-kernel path.  The float64 scratch is a ring of `slots` regions of `sub` jobs each; a chunk never splits a fused
+// group (its whole-protein job needs every part's slab).  The walks of every chunk go to `walks`, job ids relative to the chunk.  Reads the
+// group's geometry, the route (vec, fuse), the domain table, the fused groups and the options "small_b_jobs", "pack_y", "workspace_mb", "overlap".
+void plan_chunks(TwoKernelPlan& tk, const dctfp_ctx* ctx, const dctfp_layer& g, const Route& route, Walk* walks, const DomainTable& dt,
+                 const FusedGroups& fg, int64_t n_jobs) {
+    const int64_t n_domains = (int64_t)dt.len.size();
+    const int n = g.n_keep;
+    const bool fuse = route.fuse;
+    {
+        int64_t rows = 0, cnt = 0;
+        for (int64_t d = 0; d < n_domains; ++d)
+            if (!(fuse && fg.is_whole[d])) {
+                rows += dt.len[d];
+                ++cnt;
+            }
+        tk.avg_rows = cnt ? rows / cnt : 0;
+    }
+    // Y' per job: n float64 rows, or (n = 3 with the MFMA stage B) one float64 t row + one state byte per channel.
+    // Below 512 jobs the MFMA stage B (a few workgroups walking the D channels in 80 dependent steps: ~80 us of
+    // latency) loses to stage B over 64-channel slabs (stage_b_slab_kernel): 57 against 147 us at 8 jobs, 195 against
+    // 245 us at 256, even at 512 (profiles/r02/midsize_probe.txt); the walk kernel takes over from 256 jobs.
+    tk.ldy = (int)align_up((size_t)g.n_cols, 32);
+    tk.small_b = n_jobs < ctx->opt_small_b_jobs;
+    tk.packed = ctx->opt_pack_y && n == 3 && !tk.small_b;
+    tk.job_bytes = tk.packed ? (size_t)tk.ldy * 9 : (size_t)n * tk.ldy * sizeof(double);
+    tk.n_slabs = (tk.ldy + 64 * route.vec - 1) / (64 * route.vec);
+    const int64_t budget_jobs = std::max<int64_t>(1, (int64_t)(((size_t)ctx->opt_ws_mb << 20) / tk.job_bytes));
+    if (ctx->opt_overlap > 1 && n_jobs >= 2048 && budget_jobs >= 2048) tk.slots = (int)std::min<int64_t>(ctx->opt_overlap, kMaxSlots);
+    int64_t max_group = 1;
+    if (fuse)
+        for (int64_t d = 0; d < n_domains; ++d) max_group = std::max<int64_t>(max_group, d - fg.start[d] + 1);
+    // jobs one ring region may hold (a fused group always fits one region)
+    int64_t region = std::max<int64_t>(1, budget_jobs / tk.slots);
+    region = std::min<int64_t>(region, (int64_t)0x7fffffff / tk.n_slabs);
+    region = std::max<int64_t>(region, max_group);
+    // Chunk boundaries: equal shares (fixed-size cuts would leave a short extra chunk whose stage B runs on its
+    // own at the end); when the scratch budget is the limit, as many equal chunks as needed.
+    int64_t nck = tk.slots;
+    if (n_jobs / nck + max_group + 1 > region) nck = (n_jobs + region - 1) / region;
+    const double shares = (double)nck;
+    auto group_start = [&](int64_t j) {  // a chunk never splits a fused group
+        if (fuse && j < n_jobs) {
+            const int64_t d = j % n_domains;
+            if (d != 0 && fg.start[d] < d) j -= d - fg.start[d];
+        }
+        return j;
+    };
+    std::vector<int64_t> cuts;
+    for (int64_t k = 1; k < nck; ++k) {
+        const int64_t prev = cuts.empty() ? 0 : cuts.back();
+        int64_t j1 = std::min<int64_t>((int64_t)((double)n_jobs * (double)k / shares + 0.5), n_jobs);
+        j1 = group_start(std::min<int64_t>(j1, prev + region));
+        if (j1 > prev && j1 < n_jobs) cuts.push_back(j1);
+    }
+    cuts.push_back(n_jobs);
+    int64_t nw = 0;
+    size_t next_cut = 0;
+    for (int64_t j0 = 0; j0 < n_jobs;) {
+        while (cuts[next_cut] <= j0) ++next_cut;
+        const int64_t j1 = std::max<int64_t>(j0 + 1, group_start(std::min<int64_t>(cuts[next_cut], j0 + region)));
+        tk.sub = std::max<int64_t>(tk.sub, j1 - j0);
+        const int64_t wn = build_walks(walks + nw, j0, j1, j0, n_domains, fuse, fg);
+        tk.chunks.push_back(Chunk{j0, j1, nw, wn});
+        nw += wn;
+        j0 = j1;
+    }
+}
+
+// Waves per workgroup of stage A for a chunk of `n_workgroups` (walks x slabs).
+int stage_a_waves(const dctfp_ctx* ctx, int64_t avg_rows, int64_t n_workgroups, int vec) {
+    int waves = (int)ctx->opt_a_waves;  // (a forced count -- test hook -- goes through the same rules)
+    if (waves == 0) {  // auto: short walks want more, smaller workgroups per CU
+        waves = avg_rows >= 320 ? 8 : (avg_rows >= 160 ? 4 : 2);
+        // a call that cannot fill the chip (a protein at a time) is bound by the latency of one workgroup:
+        // as many waves and rows in flight as a workgroup can have (16 waves: k_stage_a.inc)
+        if (n_workgroups < 256 && avg_rows >= 128 && vec == 4) waves = 16;
+    }
+    if (waves == 16 && vec != 4) waves = 8;  // 16 waves at 4 channels per lane only
+    if (vec == 8 && waves > 4) waves = 4;    // 8 channels per lane: keep the LDS reduction buffer small
+    return waves;
+}
+
+// a call that cannot fill the chip: split the rows of every job over workgroups (stage_a_split_kernel)
+bool split_rows_over_workgroups(const dctfp_ctx* ctx, const dctfp_layer& g, const Route& route, int64_t n_workgroups, int64_t avg_rows,
+                                uint32_t max_len) {
+    return !route.fuse && g.n_keep == 3 && g.dtype == DCTFP_F32 && route.vec == 4 && ctx->opt_a_waves == 0 && n_workgroups < 128 &&
+           avg_rows >= 128 && max_len <= (1u << 24);
+}
+
+// The chunk loop.  Stage A of chunk c runs on the caller's stream, stage B of it on the context's side
+// stream, so the MFMA-bound stage B of one chunk overlaps the HBM-bound stage A of the next.  `d`: the tables as the kernels
+// read them.  `keep_buffers`: the caller waits for the stream before anything else can touch the context (see below).
+int run_two_kernels(dctfp_ctx* ctx, const dctfp_layer& g, const Route& route, const TwoKernelPlan& tk, const TableView& d, const StEntry* st,
+                    uint32_t max_len, int8_t* out, hipStream_t stream, TableLease& tables, Hold& ws, Fork& fork, bool keep_buffers) {
+    const int n = g.n_keep, m = g.m_keep, nk = n - 1, ldy = st->ldy, n_slabs = tk.n_slabs, slots = tk.slots;
+    const bool small_b = tk.small_b, packed = tk.packed;
+    const size_t job_bytes = tk.job_bytes;
+    static const InvTab<3> inv3 = make_inv<3>();
+    if (ldy != tk.ldy) return fail(DCTFP_ERR_INVALID, "internal: basis width mismatch");
+    RC_TRY(ws.take((size_t)tk.sub * slots * job_bytes, stream));  // (the scratch is the context's: behind whatever call used it last)
+    const bool side = slots > 1;
+    hipStream_t sb = stream;
+    if (side) {
+        RC_TRY(ctx->ensure_side());
+        RC_TRY(fork.branch(ctx->side, &sb));
+    }
+    int64_t c = 0;
+    for (const Chunk& ck : tk.chunks) {
+        const int64_t j0 = ck.j0, jn = ck.j1 - ck.j0;
+        const int slot = (int)(c % slots);
+        char* yprime = (char*)ws.p() + (size_t)slot * tk.sub * job_bytes;
+        if (side && c >= slots) HIP_TRY(hipStreamWaitEvent(stream, ctx->ev_b[slot], 0));  // slot free again?
+        EventPair* ep = nullptr;
+        RC_TRY(prof_begin(ctx, 0, stream, &ep));
+        // small call: stage B over 64-channel slabs (stage_b_slab_kernel), their partial blocks in the split scratch
+        const int n_kslabs = (g.n_cols + kSlabChannels - 1) / kSlabChannels;
+        auto zpart_bytes = [&](int64_t jobs_here) { return (size_t)jobs_here * n_kslabs * n * m * sizeof(double); };
+        double* zpart = nullptr;
+        if (split_rows_over_workgroups(ctx, g, route, jn * n_slabs, tk.avg_rows, max_len)) {
+            int64_t want_chunks = std::min<int64_t>(32, std::max<int64_t>(2, 384 / (jn * n_slabs)));
+            uint32_t chunk_rows = (uint32_t)((max_len + want_chunks - 1) / want_chunks);
+            chunk_rows = std::max<uint32_t>(32, (chunk_rows + 31) / 32 * 32);  // 8 waves x 4 rows in flight
+            const int n_chunks = (int)((max_len + chunk_rows - 1) / chunk_rows);
+            const size_t partial_bytes = (size_t)jn * n_chunks * nk * ldy * sizeof(double);
+            RC_TRY(ctx->split_ws.ensure(partial_bytes + (small_b ? zpart_bytes(jn) : 0)));
+            hipLaunchKernelGGL((stage_a_split_kernel<float, 3, 4, 8, 4>), dim3((unsigned)(jn * n_chunks * n_slabs)), dim3(512), 0, stream,
+                               d.joba + j0, d.pieces, (double*)ctx->split_ws.p, n_chunks, chunk_rows, g.n_cols, g.ld, ldy, n_slabs);
+            HIP_TRY(hipGetLastError());
+            if (small_b) {  // the slabs of stage B add the chunks and scale their channels themselves
+                zpart = (double*)((char*)ctx->split_ws.p + partial_bytes);
+                hipLaunchKernelGGL((stage_b_slab_kernel<true>), dim3((unsigned)n_kslabs, (unsigned)jn), dim3(256), 0, stream,
+                                   (const double*)nullptr, ldy, (const double*)ctx->split_ws.p, n_chunks, inv3, ctx->degenerate,
+                                   g.n_cols, (const double*)st->dev, st->cp, n, m, zpart);
+            } else {
+                hipLaunchKernelGGL((stage_a_combine_kernel<3>), dim3((unsigned)((ldy + 255) / 256), (unsigned)jn), dim3(256), 0, stream,
+                                   (const double*)ctx->split_ws.p, n_chunks, yprime, (int64_t)job_bytes, packed ? 1 : 0, g.n_cols, ldy,
+                                   inv3, ctx->degenerate);
+            }
+            HIP_TRY(hipGetLastError());
+        } else {
+            AParams ap{d.joba + j0, d.walks + ck.w0, route.fuse, d.pieces, ctx->degenerate, yprime, (int64_t)job_bytes, packed ? 1 : 0,
+                       g.n_cols, g.ld, ldy, n_slabs, (unsigned)(ck.wn * n_slabs), stream};
+            launch_a(ap, g.dtype, route.vec, n, stage_a_waves(ctx, tk.avg_rows, ck.wn * n_slabs, route.vec));
+        }
+        HIP_TRY(hipGetLastError());
+        RC_TRY(prof_end(ep, stream));
+        if (side) {
+            HIP_TRY(hipEventRecord(ctx->ev_a[slot], stream));
+            HIP_TRY(hipStreamWaitEvent(sb, ctx->ev_a[slot], 0));
+        }
+        RC_TRY(prof_begin(ctx, 1, sb, &ep));
+        if (!small_b) {
+            const int64_t rows = jn * n;
+            launch_b_mfma(st->cp / 16, packed, (unsigned)((rows + kBWaves * 16 - 1) / (kBWaves * 16)), sb, yprime, (int64_t)job_bytes, rows, ldy,
+                          st->dev, d.jobb + j0, n, m, out);
+        } else {
+            if (!zpart) {  // stage A wrote Y' (no row split): the slabs read it
+                RC_TRY(ctx->split_ws.ensure(zpart_bytes(jn)));
+                zpart = (double*)ctx->split_ws.p;
+                hipLaunchKernelGGL((stage_b_slab_kernel<false>), dim3((unsigned)n_kslabs, (unsigned)jn), dim3(256), 0, sb,
+                                   (const double*)yprime, ldy, (const double*)nullptr, 0, inv3, ctx->degenerate, g.n_cols,
+                                   (const double*)st->dev, st->cp, n, m, zpart);
+                HIP_TRY(hipGetLastError());
+            }
+            hipLaunchKernelGGL(stage_b_finish_kernel, dim3((unsigned)jn), dim3(256), 0, sb, (const double*)zpart, n_kslabs, d.jobb + j0, n, m, out);
+        }
+        HIP_TRY(hipGetLastError());
+        RC_TRY(prof_end(ep, sb));
+        if (side) HIP_TRY(hipEventRecord(ctx->ev_b[slot], sb));
+        ++c;
+    }
+    RC_TRY(fork.join());  // the caller's stream continues only after every stage B of this group
+    // (dctfp_quantize_one waits for the stream before it returns: scratch, tables and staging buffer ARE free for whoever
+    //  comes next, on whatever stream -- three event records, 4-5 us of a 56-us call, say nothing it does not already know)
+    // -- for the LAST layer group of the call only: an earlier group's buffers are taken again by a later group of the same call
+    // (five layers of five geometries: the staging buffer of group 1 is group 3's), long before the call's wait.
+    if (keep_buffers) {
+        ws.keep();
+        tables.keep();
+        return DCTFP_OK;
+    }
+    // ... and the scratch and this table buffer may be overwritten after this point
+    RC_TRY(ws.give_back());
+    return tables.release();
+}
+
+// The tables go up, the cosine tables this context has not seen yet are filled, and the caller's stream is behind both.  `d`: the tables as
+// the kernels will read them; `st`: the stage-B basis of the group (not for the zero fill, `with_basis` == false, which needs neither it nor
+// cosine tables).  The call's cosine-table reservations (`basis_guard`) stay armed on every error; past the fill they are published.
+int upload_tables_and_basis(dctfp_ctx* ctx, const dctfp_layer& g, bool with_basis, const TableLayout& lay, const std::vector<BasisJob>& fresh,
+                            int64_t n_jobs, hipStream_t stream, TableLease& tables, Fork& fork, BasisRollback& basis_guard, TableView* d,
+                            StEntry** st) {
+    const int nk = g.n_keep - 1;
+    const size_t tab_bytes = align_up(lay.btab + fresh.size() * sizeof(BasisJob), 16);  // what goes up
+    // The tables go up on the context's copy stream, so the upload of this call overlaps the kernels of
+    // the previous one; the copy waits until the last user of this table buffer (two calls ago) is done.
+    RC_TRY(ctx->ensure_copy());
+    // (a small call keeps everything on the caller's stream: the hop through the copy stream costs two event waits,
+    //  more than the upload itself)
+    const bool inline_tables = tab_bytes <= (64u << 10) && n_jobs < 512;
+    // ... and read the few hundred bytes of tables straight from the pinned staging buffer: an upload through the copy
+    // engine costs more latency than the kernels of such a call take
+    const bool zero_copy = inline_tables && tables.mapped();
+    hipStream_t ts = stream;
+    if (!inline_tables) RC_TRY(fork.branch(ctx->copy, &ts));
+    if (!zero_copy) RC_TRY(tables.upload(tab_bytes, ts));
+    *d = lay.view(zero_copy ? tables.zero_copy() : tables.dev());
+    if (!with_basis) return fork.join();
+
+    RC_TRY(get_st(ctx, g.n_cols, g.m_keep, st));
+#ifdef DCTFP_EXPERIMENTS
+    if (ctx->test_fail_once) {  // test hook: an allocation failure between the table lookup and the fill kernel
+        ctx->test_fail_once = 0;
+        return fail(DCTFP_ERR_NOMEM, "injected failure (option test_fail_once)");
+    }
+#endif
+    if (!fresh.empty()) {  // cosine tables this context has not seen yet (grid.y is limited to 65535)
+        // tables cached by earlier calls may have been filled on another stream: chain the events, so that whoever
+        // waits for the new ev_basis also has the older fills behind it
+        if (ctx->basis_valid && ctx->basis_stream != ts) HIP_TRY(hipStreamWaitEvent(ts, ctx->ev_basis, 0));
+        uint32_t max_len = 0;
+        for (const BasisJob& bj : fresh) max_len = std::max(max_len, bj.len);
+        const unsigned gx = (unsigned)std::min<uint64_t>(((2 * (uint64_t)max_len + 1) * nk + 255) / 256, 1024);
+        for (size_t b0 = 0; b0 < fresh.size(); b0 += 65535) {
+            const unsigned ny = (unsigned)std::min<size_t>(fresh.size() - b0, 65535);
+            hipLaunchKernelGGL(basis_kernel, dim3(gx, ny), dim3(256), 0, ts, (const BasisJob*)d->basis + b0, nk);
+            HIP_TRY(hipGetLastError());
+        }
+        HIP_TRY(hipEventRecord(ctx->ev_basis, ts));
+        ctx->basis_stream = ts;
+        ctx->basis_valid = true;
+        basis_publish(ctx, fresh, nk);
+    }
+    basis_guard.armed = false;
+    RC_TRY(fork.join());
+    // tables cached by an earlier call may have been filled on another stream
+    if (ctx->basis_valid && ctx->basis_stream != stream) HIP_TRY(hipStreamWaitEvent(stream, ctx->ev_basis, 0));
+    return DCTFP_OK;
+}
+
+// One launch of a one-launch kernel (stage A + stage B per workgroup, int8 out) through its launcher `launch(LaunchError*)`:
+// profile bracket, the launcher's error as this thread's, and the tables free again behind it.
+template <typename Launch> int launch_one(dctfp_ctx* ctx, hipStream_t stream, TableLease& tables, Launch launch) {
+    EventPair* ep = nullptr;
+    RC_TRY(prof_begin(ctx, 0, stream, &ep));
+    LaunchError le;
+    RC_TRY(launcher_rc(launch(&le), le));
+    HIP_TRY(hipGetLastError());
+    RC_TRY(prof_end(ep, stream));
+    return tables.release();
+}
+
+// Set by dctfp_quantize_one around its dctfp_quantize: the caller waits for the stream before anything else can touch the context.
+thread_local bool tl_sync_call = false;
+
+// dctfp_quantize proper.  `out_row` (optional): the output row of every domain of THIS piece table (a call that
+// dctfp_quantize has split in two); without it domain d writes row d.  `src` (optional, one per piece; n_data = windows):
+// see PieceSrc -- pieces, seq_rows and seq then speak of the STITCHED sequences.  The caller holds the context's mutex.
+// Validation, then per group of layers of one geometry: route -> tables -> upload -> launch.
+int quantize_impl(dctfp_ctx* ctx, const dctfp_layer* layers, int32_t n_layers, int32_t n_seq, const int64_t* seq_rows,
+                  const dctfp_piece* pieces, int64_t n_pieces, int64_t n_domains, int8_t* out, int64_t out_stride,
+                  hipStream_t stream, const int64_t* out_row, const PieceSrc* src = nullptr, int64_t n_data = 0) {
+    if (!src) n_data = n_seq;
+    bool two_source = false;  // some piece is the mean of two windows' rows: only walk_ab_kernel reads those
+    if (src)
+        for (int64_t i = 0; i < n_pieces && !two_source; ++i) two_source = src[i].b >= 0;
+
+    DomainTable dt;
+    RC_TRY(build_domain_table(dt, pieces, n_pieces, n_domains, n_seq, seq_rows));
+    RC_TRY(validate_layers(layers, n_layers, n_data, seq_rows, src != nullptr, dt, out_stride));
+    FusedGroups fg;
+    find_fused_groups(fg, ctx->opt_fuse != 0, pieces, dt, seq_rows, src != nullptr);
+    // the cosine-table arena starts over (nothing of this call uses it yet)
+    if ((int64_t)ctx->basis_doubles > ctx->basis_cap_doubles) RC_TRY(basis_purge(ctx));
+    for (int32_t l0 = 0, l1 = 0; l0 < n_layers; l0 = l1) {
+        l1 = layer_group_end(layers, l0, n_layers);
+        const dctfp_layer* group = layers + l0;
+        const dctfp_layer& g = group[0];
+        const int ng = l1 - l0, n = g.n_keep, m = g.m_keep;
+        const int64_t n_jobs = (int64_t)ng * n_domains;
+        // (16 bytes per lane where every row of every sequence allows it)
+        const Route route = choose_route(ctx, g, rows_aligned16(group, ng, n_data, src ? nullptr : seq_rows), dt.max_len, n_jobs, fg.n_groups > 0);
+
+        const TableLayout lay(n_jobs, ng, n_pieces, n_domains);
         TableLease tables(ctx->ring, stream);
         Hold ws{ctx->ws, stream};
         Fork fork(stream);
-        int rc = tables.stage(max_bytes);
-        if (rc) return rc;
-        char* h = tables.host();
-        JobB* hjb = (JobB*)(h + off_jobb);
-        JobA* hja = (JobA*)(h + off_joba);
-        PieceA* hpc = (PieceA*)(h + off_piece);
-        Walk* hwalk = (Walk*)(h + off_walk);
-        Run* hrun = (Run*)(h + off_run);
-        BasisJob* hbt = (BasisJob*)(h + off_btab);
-
-        // one cosine table per distinct domain length, from the context's cache
+        RC_TRY(tables.stage(lay.bytes));
+        const TableView h = lay.view(tables.host());
         BasisRollback basis_guard(ctx);  // until the fresh tables are filled and published
         std::vector<BasisJob> fresh;
         std::vector<double*> dom_tab((size_t)n_domains, nullptr);
-        if (!trivial) {
-            LenTable seen(max_len_all);  // length -> index of the first domain with it
-            for (int64_t d = 0; d < n_domains; ++d) {
-                if (seen.has(dom_len[d])) {
-                    dom_tab[d] = dom_tab[seen[dom_len[d]]];
-                } else {
-                    rc = basis_lookup(ctx, dom_len[d], nk, &dom_tab[d], fresh);
-                    if (rc) return rc;
-                    seen.set(dom_len[d], (uint32_t)d);
-                }
-            }
-        }
-        for (size_t i = 0; i < fresh.size(); ++i) hbt[i] = fresh[i];
-
-        const int ldy_pre = (int)align_up((size_t)g.n_cols, 32);
-        // 16 bytes per lane where every row of every sequence allows it
-        const bool vec_ok = rows_aligned16(layers + l0, ng, n_data, src ? nullptr : seq_rows);
-        const int vec_want = (int)(16 / esz);  // 16 bytes per lane
-        // ---- which kernels.  The walk kernel (stage A + B in one launch, nothing but int8 written) takes the production
-        // shapes: n = 3, 64 < m <= 80 (five 16-column groups), rows read 4 channels per lane, 512 <= D <= 2560, no giant domain
-        // (a wave streams all rows of its channels).  Every other shape of float32 / float64 rows that fits the LDS goes to the
-        // general walk kernel (round 4); the rest -- and calls too small to fill the chip -- run stage A -> Y' -> stage B.
-        // (rows are addressed through a 32-bit buffer offset: a piece of at most kWalkMaxRows rows stays below 2^31 bytes)
-        const bool rows_ok = walk_rows_ok(g, max_len_all);
-        const bool walk_ok = !trivial && walk_shape(g) && vec_ok && rows_ok;
-        const bool use_walk = walk_ok && walk_by_path(ctx, n_jobs);
-        if (two_source && !(use_walk && g.dtype == DCTFP_F32 && m <= 80))  // (dctfp_quantize_windows has asked takes_two_sources() before anything was launched)
+        if (route.kind != Route::kTrivial) RC_TRY(lookup_basis(ctx, dt, n - 1, dom_tab, fresh));
+        for (size_t i = 0; i < fresh.size(); ++i) h.basis[i] = fresh[i];
+        // (dctfp_quantize_windows has asked two_source_refusal(), the same conditions, before anything was launched)
+        if (two_source && !(route.kind == Route::kWalk && g.dtype == DCTFP_F32 && m <= 80))
             return fail(DCTFP_ERR_UNSUPPORTED, "internal: two-source pieces outside the walk kernel");
-        int gen_vec = 0, gen_waves = 0, gen_slots = 0;
-        if (!trivial && !walk_ok && rows_ok && n >= 2 && m >= 2 && (g.dtype == DCTFP_F32 || g.dtype == DCTFP_F64)) {
-            gen_vec = vec_ok ? vec_want : 1;
-            gen_waves = (g.n_cols + 64 * gen_vec - 1) / (64 * gen_vec);
-            const size_t slot = gen_slot_bytes(n, m, gen_waves, gen_vec);
-            gen_slots = gen_waves <= 16 && slot + 64 <= kGenLdsBudget ? 1 : 0;
-            // A second slot (a wave writes the next job's Y' while the last arrival of this one still sums) only where it
-            // costs no workgroup per CU: resident workgroups hide the end of a job (epilogue, contraction, row sums), and a
-            // wave reaches its next write a whole job's stream after the last one anyway.
-            if (gen_slots == 1) {
-                const size_t by_waves = std::max<size_t>(1, 20 / (size_t)gen_waves);   // (the kernel's builds hold 5 .. 7 waves per SIMD)
-                const size_t one = std::min(by_waves, kGenLdsBudget / (slot + 64)), two = std::min(by_waves, kGenLdsBudget / (2 * slot + 64));
-                if (two >= one) gen_slots = 2;
-            }
-        }
-        // (a shape whose slot leaves fewer than eight waves resident per CU -- [8, 128] at D = 1280: one workgroup of five -- streams
-        //  at 3.8 TB/s there against 5.4 through the two kernels: only when asked for)
-        const int64_t gen_resident = gen_slots > 0 ? gen_waves * std::min<int64_t>(std::max<int64_t>(1, 20 / gen_waves), (int64_t)(kGenLdsBudget / (gen_slots * gen_slot_bytes(n, m, gen_waves, gen_vec) + 64))) : 0;
-        // (... and it streams every job on its own: where proteins come as parts + whole protein, the fused stage A of the two
-        //  kernels reads the rows once -- 3.6-4.7 against 2.1-2.3 TB/s on the c4 / c5 mixes at [5, 44] / [3, 85] / [4, 80],
-        //  tools/gen_probe.py; on whole-protein batches the general kernel is 2-6 % ahead)
-        // Round 5: the general kernel has FUSED builds for n <= 5 (its walks then read the rows of a protein once, as the tuned
-        // kernel's); with them and four k-steps of stage-B fragments in flight it streams the c4 / c5 mixes at [5, 44] / [3, 85] /
-        // [4, 80] at 2.6-3.3 TB/s (2.1-2.5 before) -- and the two kernels at 3.6-5.0 (tools/gen_probe.py,
-        // profiles/r05/gen_probe_fused.txt): a flush per ~ 100-row job, its Y' slot in LDS holding the workgroups per CU down, is
-        // not how short jobs want to be run.  So such batches still go to the two kernels by default; "path" = 2 gets the fused walks.
-        const bool would_fuse = ctx->opt_fuse && n_groups > 0;
-        const bool use_gen = gen_slots > 0 && (ctx->opt_path == 2 || (ctx->opt_path == 0 && n_jobs >= 256 && gen_resident >= 8 && !would_fuse));
-        const bool gen_fuse = use_gen && would_fuse && n <= kGenFusedMaxN && gen_waves <= kGenFusedMaxWaves && ctx->opt_gen_fuse && n_jobs >= 64;
-        // (a small call wants parallelism, not fewer bytes: every job on its own workgroups)
-        const bool fuse = !trivial && n_groups > 0 && n_jobs >= 64 && (!use_gen || gen_fuse);
-        for (int li = 0; li < ng; ++li) {
-            const dctfp_layer& ly = layers[l0 + li];
-            for (int64_t d = 0; d < n_domains; ++d) {
-                const int64_t job = (int64_t)li * n_domains + d;
-                hjb[job].out_off = (out_row ? out_row[d] : d) * out_stride + ly.out_offset;
-                hja[job].piece_begin = (uint32_t)((int64_t)li * n_pieces + dom_first[d]);
-                hja[job].n_pieces = dom_np[d];
-                hja[job].n_rows = dom_len[d];
-                hja[job].reserved = 0;
-                hja[job].basis = dom_tab[d];
-                hja[job].w_basis = nullptr;
-                hja[job].w_ref = nullptr;
-                if (fuse && grp_end[d] >= 0 && !is_whole[d]) {
-                    const int64_t w = grp_end[d];  // the whole-protein domain closes the group
-                    hja[job].w_basis = dom_tab[w];
-                    // (windows: row 0 of a sequence is row 0 of its first window -- a window is longer than the overlap)
-                    hja[job].w_ref = src ? ly.seq_data[src[dom_first[w]].a] : ly.seq_data[pieces[dom_first[w]].seq];
-                }
-            }
-            uint32_t t0 = 0;
-            int32_t prev_dom = -1;
-            for (int64_t i = 0; i < n_pieces; ++i) {
-                const dctfp_piece& pc = pieces[i];
-                if (pc.domain != prev_dom) t0 = 0;
-                prev_dom = pc.domain;
-                PieceA& o = hpc[(int64_t)li * n_pieces + i];
-                if (src) {
-                    const PieceSrc& ps = src[i];
-                    o.ptr = (const char*)ly.seq_data[ps.a] + (size_t)ps.row_a * (size_t)ly.ld * esz;
-                    o.ptr2 = ps.b >= 0 ? (const char*)ly.seq_data[ps.b] + (size_t)ps.row_b * (size_t)ly.ld * esz : nullptr;
-                } else {
-                    o.ptr = (const char*)ly.seq_data[pc.seq] + (size_t)pc.row_start * (size_t)ly.ld * esz;
-                    o.ptr2 = nullptr;
-                }
-                o.n_rows = (uint32_t)pc.n_rows;
-                o.t0 = t0;
-                o.w0 = (uint32_t)pc.row_start;
-                o.reserved = 0;
-                t0 += (uint32_t)pc.n_rows;
-            }
-        }
-        int vec = vec_ok ? vec_want : 1;
-        // Fused walks of half-precision rows: 8 channels per lane mean two accumulator sets of 8 -- 27..37 registers per lane
-        // spilled, and scratch writes beside the row stream cost far more than their bytes (the c5 mix in float16 took 19 ms
-        // against 12.6 in float32).  4 channels per lane (8-byte loads) fit the registers.
-        if (fuse && n == 3 && vec == 8) vec = 4;
-
-        // Measured (profiles/r02): the walk kernel wins at every width it takes -- D = 2560 (10-wave workgroups, one per CU)
-        // since its flush contracts the even and odd halves of the basis apart: 5.3 against 4.9-5.25 TB/s on config 4.
-        // A small call (a protein at a time, the reference's calling pattern) is latency-bound: there the two-kernel path,
-        // which spreads one job over slabs x 8 waves, finishes first.
-        // walks of ALL jobs (walk kernel) -- the two-kernel path builds its walks per chunk below
-        int64_t n_walks = 0, n_runs = 0;
-        int walk_s = 0;
-        constexpr int walk_g = 4;  // jobs per flush: the rows of an MFMA tile (a flush costs the same MFMAs for 1..4 jobs)
-        // workgroups of the kernel the chip holds at once, per CU (LDS: 5 / 3 / 1 at 3 / 5 / 10 waves of the walk kernel)
-        int64_t wg_per_cu = 1;
-        if (use_walk || use_gen) {
-            walk_s = use_gen ? gen_waves : (g.n_cols <= 768 ? 3 : (g.n_cols <= 1280 ? 5 : 10));
-            wg_per_cu = use_gen ? std::max<int64_t>(1, std::min<int64_t>(20 / gen_waves, (int64_t)(kGenLdsBudget / (gen_slots * gen_slot_bytes(n, m, gen_waves, gen_vec) + 64))))
-                                : (walk_s == 3 ? 5 : (walk_s == 5 ? 3 : 1));
-            for (int64_t j = 0; j < n_jobs;) {
-                const int64_t d = j % n_domains;
-                Walk& wk = hwalk[n_walks++];
-                wk.job_begin = (uint32_t)j;
-                wk.reserved = 0;
-                if (fuse && grp_end[d] >= 0) {  // d is the first part of a fused group
-                    wk.n_parts = (uint32_t)(grp_end[d] - d);
-                    wk.whole_job = (int32_t)(j + (grp_end[d] - d));
-                    j += grp_end[d] - d + 1;
-                } else {
-                    wk.n_parts = 1;
-                    wk.whole_job = -1;
-                    j += 1;
-                }
-            }
-            // runs: consecutive walks until a run holds `want` jobs (a multiple of the flush group, so that most
-            // flushes are full); fewer jobs per run when the batch is small, to keep every CU busy
-            int64_t want = ctx->opt_ab_run_jobs;
-            bool longest_first = ctx->opt_ab_longest_first == 1;
-            if (want == 0) {
-                // Rows per job decide (profiles/r02/path_probe_run_jobs.log): long jobs (whole proteins) want ONE per
-                // workgroup -- a flush of one job costs the MFMAs of four, nothing beside 500 rows, and 4 x as many, smaller
-                // workgroups drain the chip more evenly at the end (C2 6.79 -> 6.97 TB/s, C3 6.70 -> 6.90); short jobs
-                // (domains) want many per workgroup, so that few flushes are partial (c4 5.80 -> 5.91 at 16).
-                int64_t rows = 0;
-                for (int64_t d = 0; d < n_domains; ++d)
-                    if (!(fuse && is_whole[d])) rows += dom_len[d];
-                // (rows of 4-byte elements: a half-precision job of 500 rows weighs like 250 -- 4.40 ms per C2 batch with four
-                //  jobs per workgroup, 4.85 with one)
-                const int64_t job_rows = rows * (int64_t)esz / 4 / std::max<int64_t>(1, n_domains);  // whole-protein jobs of fused walks stream nothing
-                const int64_t by_rows = job_rows >= 384 ? 1 : 4 * walk_g;
-                if (ctx->opt_ab_longest_first == 0) longest_first = by_rows >= walk_g && walk_s == 10 && !use_gen;
-                const int64_t slots = (int64_t)ctx->n_cu * wg_per_cu;
-                if (n_jobs <= 6 * slots * by_rows) {
-                    // fewer than a handful of rounds at that size: ONE round of equal workgroups instead (a second, partly
-                    // filled round costs as much as a full one: 1 024 whole-protein jobs 509 us as 1 024 workgroups, 477 as 512)
-                    want = std::max<int64_t>(1, (n_jobs + slots - 1) / slots);
-                    if (by_rows >= walk_g && want > 1) want = (want + walk_g - 1) / walk_g * walk_g;  // short jobs: full flushes
-                    want = std::min<int64_t>(want, 4 * walk_g);
-                } else {
-                    want = by_rows;
-                    while (want > walk_g && n_jobs / want < 8192) want -= walk_g;  // ... but ten rounds of workgroups at least
-                }
-            }
-            // The end of the launch: its last workgroups run on a chip that is emptying (tools/walk_trace.py: the last 5 % of a
-            // c5 launch hold 15 % of the waves), for as long as ONE workgroup lives.  The jobs of the last round of workgroups
-            // therefore go out in runs of one flush group: four times as many workgroups, a quarter as long.
-            int64_t taper_from = n_jobs;  // runs that start at or after this job are short
-            if (want > walk_g && ctx->opt_ab_taper) {
-                const int64_t slots = (int64_t)ctx->n_cu * wg_per_cu;
-                taper_from = std::max<int64_t>(0, n_jobs - slots * want * ctx->opt_ab_taper / 4);
-            }
-            int64_t jobs_done = 0;
-            for (int64_t w = 0; w < n_walks;) {
-                Run& rn = hrun[n_runs++];
-                rn.walk_begin = (uint32_t)w;
-                rn.job_begin = hwalk[w].job_begin;
-                uint32_t jobs_in = 0;
-                const int64_t want_here = jobs_done >= taper_from ? walk_g : want;
-                while (w < n_walks && (jobs_in == 0 || (int64_t)jobs_in < want_here)) {
-                    jobs_in += hwalk[w].n_parts + (hwalk[w].whole_job >= 0 ? 1u : 0u);
-                    ++w;
-                }
-                // A run whose job count is no multiple of the flush group ends in a partial flush, which costs the MFMAs of a
-                // full one (walks of k parts + whole protein rarely add up).  Look one or two walks further for a count that is:
-                // c4 +1.9 %, c5 +0.2 %; looking further or longer runs gain nothing (profiles/r04/experiments/ab_run_alignment_and_length.txt).
-                if (ctx->opt_ab_align && want_here > walk_g && jobs_in % (uint32_t)walk_g != 0) {
-                    uint32_t more = jobs_in;
-                    for (int64_t x = w; x < n_walks && x < w + ctx->opt_ab_align && more < jobs_in + 2u * (uint32_t)walk_g; ++x) {
-                        more += hwalk[x].n_parts + (hwalk[x].whole_job >= 0 ? 1u : 0u);
-                        if (more % (uint32_t)walk_g == 0) {
-                            jobs_in = more;
-                            w = x + 1;
-                            break;
-                        }
-                    }
-                }
-                rn.n_walks = (uint32_t)(w - rn.walk_begin);
-                rn.n_jobs = jobs_in;
-                jobs_done += jobs_in;
-            }
-            // Longest run first, for batches of domains at D > 1280 (one workgroup per CU: 256 slots, so the last round
-            // weighs most): the workgroups that start last are the short ones and the chip drains together (c4 +2.8 %).
-            // With 1 280 slots (D = 640) it gains nothing in the kernel and costs 70 us of host time per 340 000 jobs; on
-            // whole-protein batches it would put every short protein -- the jobs whose flush weighs most -- at the end
-            // together (C3 -1.5 %).  Counting sort on the rows a run streams, 16-row buckets, input order within a bucket.
-            if (longest_first && n_runs > 1) {
-                constexpr uint32_t kBuckets = 4096;
-                std::vector<uint32_t> key((size_t)n_runs), start(kBuckets + 1, 0);
-                for (int64_t r = 0; r < n_runs; ++r) {
-                    uint64_t rows = 0;
-                    for (uint32_t w = hrun[r].walk_begin; w < hrun[r].walk_begin + hrun[r].n_walks; ++w)
-                        for (uint32_t p = 0; p < hwalk[w].n_parts; ++p) rows += (uint64_t)dom_len[(hwalk[w].job_begin + p) % n_domains];
-                    key[r] = kBuckets - 1 - (uint32_t)std::min<uint64_t>(rows >> 4, kBuckets - 1);  // descending
-                    ++start[key[r] + 1];
-                }
-                for (uint32_t b = 0; b < kBuckets; ++b) start[b + 1] += start[b];
-                std::vector<Run> sorted((size_t)n_runs);
-                for (int64_t r = 0; r < n_runs; ++r) sorted[start[key[r]]++] = hrun[r];
-                std::memcpy(hrun, sorted.data(), (size_t)n_runs * sizeof(Run));
-            }
-        }
-
-        // ---- chunk plan of the two-kernel path.  The float64 scratch is a ring of `slots` regions of `sub` jobs
-        // each; a chunk never splits a fused group (its whole-protein job needs every part's slab).
-        struct Chunk { int64_t j0, j1, w0, wn; };
-        int64_t avg_rows = 0;  // rows per streamed job (launch-shape heuristic)
-        {
-            int64_t rows = 0, cnt = 0;
-            for (int64_t d = 0; d < n_domains; ++d)
-                if (!(fuse && is_whole[d])) {
-                    rows += dom_len[d];
-                    ++cnt;
-                }
-            avg_rows = cnt ? rows / cnt : 0;
-        }
-        std::vector<Chunk> plan;
-        // Y' per job: n float64 rows, or (n = 3 with the MFMA stage B) one float64 t row + one state byte per channel.
-        // Below 512 jobs the MFMA stage B (a few workgroups walking the D channels in 80 dependent steps: ~80 us of
-        // latency) loses to stage B over 64-channel slabs (stage_b_slab_kernel): 57 against 147 us at 8 jobs, 195 against
-        // 245 us at 256, even at 512 (profiles/r02/midsize_probe.txt); the walk kernel takes over from 256 jobs.
-        const bool small_b = n_jobs < ctx->opt_small_b_jobs;
-        const bool packed = ctx->opt_pack_y && n == 3 && !small_b;
-        const size_t job_bytes = packed ? (size_t)ldy_pre * 9 : (size_t)n * ldy_pre * sizeof(double);
-        const int n_slabs = (ldy_pre + 64 * vec - 1) / (64 * vec);
-        int slots = 1;
-        int64_t sub = 1;
-        if (!trivial && !use_walk && !use_gen) {
-            const int64_t budget_jobs = std::max<int64_t>(1, (int64_t)(((size_t)ctx->opt_ws_mb << 20) / job_bytes));
-            if (ctx->opt_overlap > 1 && n_jobs >= 2048 && budget_jobs >= 2048) slots = (int)std::min<int64_t>(ctx->opt_overlap, kMaxSlots);
-            int64_t max_group = 1;
-            if (fuse)
-                for (int64_t d = 0; d < n_domains; ++d) max_group = std::max<int64_t>(max_group, d - grp_start[d] + 1);
-            // jobs one ring region may hold (a fused group always fits one region)
-            int64_t region = std::max<int64_t>(1, budget_jobs / slots);
-            region = std::min<int64_t>(region, (int64_t)0x7fffffff / n_slabs);
-            region = std::max<int64_t>(region, max_group);
-            // Chunk boundaries: equal shares (fixed-size cuts would leave a short extra chunk whose stage B runs on its
-            // own at the end); when the scratch budget is the limit, as many equal chunks as needed.
-            int64_t nck = slots;
-            if (n_jobs / nck + max_group + 1 > region) nck = (n_jobs + region - 1) / region;
-            const double shares = (double)nck;
-            auto group_start = [&](int64_t j) {  // a chunk never splits a fused group
-                if (fuse && j < n_jobs) {
-                    const int64_t d = j % n_domains;
-                    if (d != 0 && grp_start[d] < d) j -= d - grp_start[d];
-                }
-                return j;
-            };
-            std::vector<int64_t> cuts;
-            for (int64_t k = 1; k < nck; ++k) {
-                const int64_t prev = cuts.empty() ? 0 : cuts.back();
-                int64_t j1 = std::min<int64_t>((int64_t)((double)n_jobs * (double)k / shares + 0.5), n_jobs);
-                j1 = group_start(std::min<int64_t>(j1, prev + region));
-                if (j1 > prev && j1 < n_jobs) cuts.push_back(j1);
-            }
-            cuts.push_back(n_jobs);
-            int64_t nw = 0;
-            size_t next_cut = 0;
-            for (int64_t j0 = 0; j0 < n_jobs;) {
-                while (cuts[next_cut] <= j0) ++next_cut;
-                const int64_t j1 = std::max<int64_t>(j0 + 1, group_start(std::min<int64_t>(cuts[next_cut], j0 + region)));
-                sub = std::max<int64_t>(sub, j1 - j0);
-                Chunk ck{j0, j1, nw, 0};
-                for (int64_t j = j0; j < j1;) {
-                    const int64_t d = j % n_domains;
-                    Walk& wk = hwalk[nw++];
-                    wk.job_begin = (uint32_t)(j - j0);
-                    wk.reserved = 0;
-                    if (fuse && grp_end[d] >= 0) {  // d is the first part of a fused group
-                        wk.n_parts = (uint32_t)(grp_end[d] - d);
-                        wk.whole_job = (int32_t)(j - j0 + (grp_end[d] - d));
-                        j += grp_end[d] - d + 1;
-                    } else {
-                        wk.n_parts = 1;
-                        wk.whole_job = -1;
-                        j += 1;
-                    }
-                    ++ck.wn;
-                }
-                plan.push_back(ck);
-                j0 = j1;
-            }
-        }
-
-        const size_t tab_bytes = align_up(off_btab + fresh.size() * sizeof(BasisJob), 16);
-        // The tables go up on the context's copy stream, so the upload of this call overlaps the kernels of
-        // the previous one; the copy waits until the last user of this table buffer (two calls ago) is done.
-        rc = ctx->ensure_copy();
-        if (rc) return rc;
-        // (a small call keeps everything on the caller's stream: the hop through the copy stream costs two event waits,
-        //  more than the upload itself)
-        const bool inline_tables = tab_bytes <= (64u << 10) && n_jobs < 512;
-        // ... and read the few hundred bytes of tables straight from the pinned staging buffer: an upload through the copy
-        // engine costs more latency than the kernels of such a call take
-        const bool zero_copy = inline_tables && tables.mapped();
-        hipStream_t ts = stream;
-        if (!inline_tables) rc = fork.branch(ctx->copy, &ts);
-        if (rc == DCTFP_OK && !zero_copy) rc = tables.upload(tab_bytes, ts);
-        if (rc) return rc;
-        char* dt = zero_copy ? tables.zero_copy() : tables.dev();
-        const JobB* djb = (const JobB*)(dt + off_jobb);
-        const JobA* dja = (const JobA*)(dt + off_joba);
-        const PieceA* dpc = (const PieceA*)(dt + off_piece);
-        const Walk* dwalk = (const Walk*)(dt + off_walk);
-        const Run* drun = (const Run*)(dt + off_run);
-        const BasisJob* dbt = (const BasisJob*)(dt + off_btab);
-
-        if (trivial) {
-            rc = fork.join();
-            if (rc) return rc;
+        fill_jobs(h, group, ng, pieces, n_pieces, src, dt, fg, route.fuse, dom_tab.data(), out_row, out_stride);
+        int64_t n_runs = 0;
+        TwoKernelPlan tk;
+        if (route.one_launch())  // walks of ALL jobs (walk kernel) -- the two-kernel path builds its walks per chunk
+            n_runs = plan_runs(ctx, route, h, build_walks(h.walks, 0, n_jobs, 0, n_domains, route.fuse, fg), dt, fg, n_jobs, dtype_size(g.dtype));
+        else if (route.kind == Route::kTwoKernels) plan_chunks(tk, ctx, g, route, h.walks, dt, fg, n_jobs);
+        TableView d;
+        StEntry* st = nullptr;
+        RC_TRY(upload_tables_and_basis(ctx, g, route.kind != Route::kTrivial, lay, fresh, n_jobs, stream, tables, fork, basis_guard, &d, &st));
+        if (route.kind == Route::kTrivial) {
             const int64_t total = n_jobs * n * m;
             const unsigned grid = (unsigned)std::min<int64_t>((total + 255) / 256, 4096);
-            hipLaunchKernelGGL(fill_zero_kernel, dim3(grid), dim3(256), 0, stream, djb, n_jobs, n * m, out);
+            hipLaunchKernelGGL(fill_zero_kernel, dim3(grid), dim3(256), 0, stream, (const JobB*)d.jobb, n_jobs, n * m, out);
             HIP_TRY(hipGetLastError());
-            rc = tables.release();
-            if (rc) return rc;
-            l0 = l1;
+            RC_TRY(tables.release());
             continue;
         }
-
-        StEntry* st = nullptr;
-        rc = get_st(ctx, g.n_cols, m, &st);
-        if (rc) return rc;
-        const int ldy = st->ldy;
-
-#ifdef DCTFP_EXPERIMENTS
-        if (ctx->test_fail_once) {  // test hook: an allocation failure between the table lookup and the fill kernel
-            ctx->test_fail_once = 0;
-            return fail(DCTFP_ERR_NOMEM, "injected failure (option test_fail_once)");
+        ctx->last_path = route.one_launch() ? 2 : 1;
+        ctx->last_gen_fused = route.gen_fuse ? 1 : 0;
+        ctx->last_walk_groups = route.kind == Route::kWalk ? (m > 80 ? 6 : 5) : 0;
+        ctx->walk_launches += route.one_launch() ? 1 : 0;
+        if (route.kind == Route::kGen) {
+            RC_TRY(get_st_plain(ctx, st, g.n_cols));
+            const size_t lds_bytes = (size_t)route.gen_slots * gen_slot_bytes(n, m, route.gen_waves, route.gen_vec) + 64;
+            GParams gp{d.joba, d.jobb, d.walks, route.gen_fuse, d.runs, d.pieces, st->fragp, out, g.n_cols, g.ld, m, route.gen_slots,
+                       ctx->degenerate, (unsigned)n_runs, (unsigned)route.gen_waves, lds_bytes, stream};
+            RC_TRY(launch_one(ctx, stream, tables, [&](LaunchError* le) { return launch_gen(gp, g.dtype, route.gen_vec, n, le); }));
+        } else if (route.kind == Route::kWalk) {
+            WParams wp{d.joba, d.jobb, d.walks, d.runs, d.pieces, st->frag, out, g.n_cols, g.ld, m, ctx->degenerate, (unsigned)n_runs, stream,
+                       two_source};
+            RC_TRY(launch_one(ctx, stream, tables, [&](LaunchError* le) { return launch_walk(wp, g.dtype, route.walk_s, route.fuse, le); }));
+        } else {
+            RC_TRY(run_two_kernels(ctx, g, route, tk, d, st, dt.max_len, out, stream, tables, ws, fork, tl_sync_call && l1 == n_layers));
         }
-#endif
-        if (!fresh.empty()) {  // cosine tables this context has not seen yet (grid.y is limited to 65535)
-            // tables cached by earlier calls may have been filled on another stream: chain the events, so that whoever
-            // waits for the new ev_basis also has the older fills behind it
-            if (ctx->basis_valid && ctx->basis_stream != ts) HIP_TRY(hipStreamWaitEvent(ts, ctx->ev_basis, 0));
-            uint32_t max_len = 0;
-            for (const BasisJob& bj : fresh) max_len = std::max(max_len, bj.len);
-            const unsigned gx = (unsigned)std::min<uint64_t>(((2 * (uint64_t)max_len + 1) * nk + 255) / 256, 1024);
-            for (size_t b0 = 0; b0 < fresh.size(); b0 += 65535) {
-                const unsigned ny = (unsigned)std::min<size_t>(fresh.size() - b0, 65535);
-                hipLaunchKernelGGL(basis_kernel, dim3(gx, ny), dim3(256), 0, ts, dbt + b0, nk);
-                HIP_TRY(hipGetLastError());
-            }
-        }
-        if (!fresh.empty()) {
-            HIP_TRY(hipEventRecord(ctx->ev_basis, ts));
-            ctx->basis_stream = ts;
-            ctx->basis_valid = true;
-            basis_publish(ctx, fresh, nk);
-        }
-        basis_guard.armed = false;
-        rc = fork.join();
-        if (rc) return rc;
-        // tables cached by an earlier call may have been filled on another stream
-        if (ctx->basis_valid && ctx->basis_stream != stream) HIP_TRY(hipStreamWaitEvent(stream, ctx->ev_basis, 0));
-
-        ctx->last_path = (use_walk || use_gen) ? 2 : 1;
-        ctx->last_gen_fused = gen_fuse ? 1 : 0;
-        ctx->last_walk_groups = use_walk ? (m > 80 ? 6 : 5) : 0;
-        ctx->walk_launches += (use_walk || use_gen) ? 1 : 0;
-        if (use_gen) {
-            // one launch of the general walk kernel: stage A + stage B per workgroup, int8 out
-            rc = get_st_plain(ctx, st, g.n_cols);
-            if (rc) return rc;
-            EventPair* ep = nullptr;
-            rc = prof_begin(ctx, 0, stream, &ep);
-            if (rc) return rc;
-            GParams gp;
-            gp.jobs = dja;
-            gp.jobb = djb;
-            gp.walks = dwalk;
-            gp.fused = gen_fuse;
-            gp.runs = drun;
-            gp.pieces = dpc;
-            gp.stp = st->fragp;
-            gp.out = out;
-            gp.n_cols = g.n_cols;
-            gp.ld = g.ld;
-            gp.m = m;
-            gp.n_slots = gen_slots;
-            gp.degenerate = ctx->degenerate;
-            gp.grid = (unsigned)n_runs;
-            gp.waves = (unsigned)gen_waves;
-            gp.lds_bytes = (size_t)gen_slots * gen_slot_bytes(n, m, gen_waves, gen_vec) + 64;
-            gp.stream = stream;
-            {
-                LaunchError le;
-                rc = launcher_rc(launch_gen(gp, g.dtype, gen_vec, n, &le), le);
-            }
-            if (rc) return rc;
-            HIP_TRY(hipGetLastError());
-            rc = prof_end(ep, stream);
-            if (rc) return rc;
-            rc = tables.release();
-            if (rc) return rc;
-            l0 = l1;
-            continue;
-        }
-        if (use_walk) {
-            // one launch: stage A + stage B per workgroup, int8 out
-            EventPair* ep = nullptr;
-            rc = prof_begin(ctx, 0, stream, &ep);
-            if (rc) return rc;
-            WParams wp;
-            wp.jobs = dja;
-            wp.jobb = djb;
-            wp.walks = dwalk;
-            wp.runs = drun;
-            wp.pieces = dpc;
-            wp.stf = st->frag;
-            wp.out = out;
-            wp.n_cols = g.n_cols;
-            wp.ld = g.ld;
-            wp.m = m;
-            wp.degenerate = ctx->degenerate;
-            wp.grid = (unsigned)n_runs;
-            wp.stream = stream;
-            wp.two_source = two_source;
-            {
-                LaunchError le;
-                rc = launcher_rc(launch_walk(wp, g.dtype, walk_s, fuse, &le), le);
-            }
-            if (rc) return rc;
-            HIP_TRY(hipGetLastError());
-            rc = prof_end(ep, stream);
-            if (rc) return rc;
-            rc = tables.release();
-            if (rc) return rc;
-            l0 = l1;
-            continue;
-        }
-
-        // Stage A of chunk c runs on the caller's stream, stage B of it on the context's side
-        // stream, so the MFMA-bound stage B of one chunk overlaps the HBM-bound stage A of the next.
-        if (ldy != ldy_pre) return fail(DCTFP_ERR_INVALID, "internal: basis width mismatch");
-        rc = ws.take((size_t)sub * slots * job_bytes, stream);  // (the scratch is the context's: behind whatever call used it last)
-        if (rc) return rc;
-        const bool side = slots > 1;
-        hipStream_t sb = stream;
-        if (side) {
-            rc = ctx->ensure_side();
-            if (rc == DCTFP_OK) rc = fork.branch(ctx->side, &sb);
-            if (rc) return rc;
-        }
-
-        int64_t c = 0;
-        for (const Chunk& ck : plan) {
-            const int64_t j0 = ck.j0, jn = ck.j1 - ck.j0;
-            const int slot = (int)(c % slots);
-            char* yprime = (char*)ws.p() + (size_t)slot * sub * job_bytes;
-            if (side && c >= slots) HIP_TRY(hipStreamWaitEvent(stream, ctx->ev_b[slot], 0));  // slot free again?
-            EventPair* ep = nullptr;
-            rc = prof_begin(ctx, 0, stream, &ep);
-            if (rc) return rc;
-            // small call: stage B over 64-channel slabs (stage_b_slab_kernel), their partial blocks in the split scratch
-            const int n_kslabs = (g.n_cols + kSlabChannels - 1) / kSlabChannels;
-            auto zpart_bytes = [&](int64_t jobs_here) { return (size_t)jobs_here * n_kslabs * n * m * sizeof(double); };
-            double* zpart = nullptr;
-            {
-                AParams ap;
-                ap.jobs = dja + j0;
-                ap.walks = dwalk + ck.w0;
-                ap.fused = fuse;
-                ap.pieces = dpc;
-                ap.degenerate = ctx->degenerate;
-                ap.yprime = yprime;
-                ap.job_bytes = (int64_t)job_bytes;
-                ap.packed = packed ? 1 : 0;
-                ap.n_cols = g.n_cols;
-                ap.ld = g.ld;
-                ap.ldy = ldy;
-                ap.n_slabs = n_slabs;
-                ap.grid = (unsigned)(ck.wn * n_slabs);
-                ap.stream = stream;
-                // a call that cannot fill the chip: split the rows of every job over workgroups (stage_a_split_kernel)
-                const bool split = !fuse && n == 3 && g.dtype == DCTFP_F32 && vec == 4 && ctx->opt_a_waves == 0 &&
-                                   jn * n_slabs < 128 && avg_rows >= 128 && max_len_all <= (1u << 24);
-                if (split) {
-                    int64_t want_chunks = std::min<int64_t>(32, std::max<int64_t>(2, 384 / (jn * n_slabs)));
-                    uint32_t chunk_rows = (uint32_t)((max_len_all + want_chunks - 1) / want_chunks);
-                    chunk_rows = std::max<uint32_t>(32, (chunk_rows + 31) / 32 * 32);  // 8 waves x 4 rows in flight
-                    const int n_chunks = (int)((max_len_all + chunk_rows - 1) / chunk_rows);
-                    const size_t partial_bytes = (size_t)jn * n_chunks * nk * ldy * sizeof(double);
-                    rc = ctx->split_ws.ensure(partial_bytes + (small_b ? zpart_bytes(jn) : 0));
-                    if (rc) return rc;
-                    static const InvTab<3> inv3 = make_inv<3>();
-                    hipLaunchKernelGGL((stage_a_split_kernel<float, 3, 4, 8, 4>), dim3((unsigned)(jn * n_chunks * n_slabs)), dim3(512), 0, stream,
-                                       dja + j0, dpc, (double*)ctx->split_ws.p, n_chunks, chunk_rows, g.n_cols, g.ld, ldy, n_slabs);
-                    HIP_TRY(hipGetLastError());
-                    if (small_b) {  // the slabs of stage B add the chunks and scale their channels themselves
-                        zpart = (double*)((char*)ctx->split_ws.p + partial_bytes);
-                        hipLaunchKernelGGL((stage_b_slab_kernel<true>), dim3((unsigned)n_kslabs, (unsigned)jn), dim3(256), 0, stream,
-                                           (const double*)nullptr, ldy, (const double*)ctx->split_ws.p, n_chunks, inv3, ctx->degenerate,
-                                           g.n_cols, (const double*)st->dev, st->cp, n, m, zpart);
-                    } else {
-                        hipLaunchKernelGGL((stage_a_combine_kernel<3>), dim3((unsigned)((ldy + 255) / 256), (unsigned)jn), dim3(256), 0, stream,
-                                           (const double*)ctx->split_ws.p, n_chunks, yprime, (int64_t)job_bytes, packed ? 1 : 0, g.n_cols, ldy,
-                                           inv3, ctx->degenerate);
-                    }
-                    HIP_TRY(hipGetLastError());
-                }
-                int waves = (int)ctx->opt_a_waves;  // (a forced count -- test hook -- goes through the same rules)
-                if (waves == 0) {  // auto: short walks want more, smaller workgroups per CU
-                    waves = avg_rows >= 320 ? 8 : (avg_rows >= 160 ? 4 : 2);
-                    // a call that cannot fill the chip (a protein at a time) is bound by the latency of one workgroup:
-                    // as many waves and rows in flight as a workgroup can have (16 waves: k_stage_a.inc)
-                    if (ck.wn * n_slabs < 256 && avg_rows >= 128 && vec == 4) waves = 16;
-                }
-                if (waves == 16 && vec != 4) waves = 8;  // 16 waves at 4 channels per lane only
-                if (vec == 8 && waves > 4) waves = 4;    // 8 channels per lane: keep the LDS reduction buffer small
-                if (!split) launch_a(ap, g.dtype, vec, n, waves);
-                HIP_TRY(hipGetLastError());
-            }
-            rc = prof_end(ep, stream);
-            if (rc) return rc;
-            if (side) {
-                HIP_TRY(hipEventRecord(ctx->ev_a[slot], stream));
-                HIP_TRY(hipStreamWaitEvent(sb, ctx->ev_a[slot], 0));
-            }
-
-            rc = prof_begin(ctx, 1, sb, &ep);
-            if (rc) return rc;
-            if (!small_b) {
-                const int64_t rows = jn * n;
-                launch_b_mfma(st->cp / 16, packed, (unsigned)((rows + kBWaves * 16 - 1) / (kBWaves * 16)), sb, yprime, (int64_t)job_bytes, rows, ldy,
-                              st->dev, djb + j0, n, m, out);
-            } else {
-                if (!zpart) {  // stage A wrote Y' (no row split): the slabs read it
-                    rc = ctx->split_ws.ensure(zpart_bytes(jn));
-                    if (rc) return rc;
-                    zpart = (double*)ctx->split_ws.p;
-                    static const InvTab<3> inv3 = make_inv<3>();
-                    hipLaunchKernelGGL((stage_b_slab_kernel<false>), dim3((unsigned)n_kslabs, (unsigned)jn), dim3(256), 0, sb,
-                                       (const double*)yprime, ldy, (const double*)nullptr, 0, inv3, ctx->degenerate, g.n_cols,
-                                       (const double*)st->dev, st->cp, n, m, zpart);
-                    HIP_TRY(hipGetLastError());
-                }
-                hipLaunchKernelGGL(stage_b_finish_kernel, dim3((unsigned)jn), dim3(256), 0, sb, (const double*)zpart, n_kslabs, djb + j0, n, m, out);
-            }
-            HIP_TRY(hipGetLastError());
-            rc = prof_end(ep, sb);
-            if (rc) return rc;
-            if (side) HIP_TRY(hipEventRecord(ctx->ev_b[slot], sb));
-            ++c;
-        }
-        rc = fork.join();  // the caller's stream continues only after every stage B of this group
-        if (rc) return rc;
-        // (dctfp_quantize_one waits for the stream before it returns: scratch, tables and staging buffer ARE free for whoever
-        //  comes next, on whatever stream -- three event records, 4-5 us of a 56-us call, say nothing it does not already know)
-        // -- for the LAST layer group of the call only: an earlier group's buffers are taken again by a later group of the same call
-        // (five layers of five geometries: the staging buffer of group 1 is group 3's), long before the call's wait.
-        if (tl_sync_call && l1 == n_layers) {
-            ws.keep();
-            tables.keep();
-        } else {  // ... and the scratch and this table buffer may be overwritten after this point
-            rc = ws.give_back();
-            if (rc == DCTFP_OK) rc = tables.release();
-            if (rc) return rc;
-        }
-        l0 = l1;
     }
     return DCTFP_OK;
 }
@@ -1808,33 +1844,26 @@ int dctfp_quantize(dctfp_ctx* ctx, const dctfp_layer* layers, int32_t n_layers, 
     bool all_walk = ctx->opt_path != 1;
     for (int32_t l = 0; l < n_layers && all_walk; ++l) all_walk = walk_shape(layers[l]) || gen_shape(layers[l]);
     if (all_walk && n_domains * n_layers >= 256) {
-        std::vector<uint32_t> len((size_t)n_domains, 0);
-        bool table_ok = true;
-        for (int64_t i = 0; i < n_pieces && table_ok; ++i) {
-            const dctfp_piece& pc = pieces[i];
-            table_ok = pc.domain >= 0 && pc.domain < n_domains && pc.n_rows > 0 && (uint64_t)len[pc.domain] + (uint64_t)pc.n_rows <= 0x7fffffffu;
-            if (table_ok) len[pc.domain] += (uint32_t)pc.n_rows;
-        }
-        int64_t n_giant = 0;
-        for (int64_t d = 0; d < n_domains && table_ok; ++d) n_giant += len[d] > kWalkMaxRows ? 1 : 0;
-        if (table_ok && n_giant > 0 && n_giant < n_domains) {  // (a broken table goes to quantize_impl as it is: it reports the error)
+        DomainTable lens;
+        (void)build_domain_table(lens, pieces, n_pieces, n_domains, n_seq, nullptr);
+        // some giants, not only giants  (a broken table goes to quantize_impl as it is: it reports the error)
+        if (lens.sound && lens.max_len > kWalkMaxRows && lens.min_len <= kWalkMaxRows) {
             std::vector<dctfp_piece> part[2];
             std::vector<int64_t> rows[2], new_id((size_t)n_domains);
             for (int64_t d = 0; d < n_domains; ++d) {
-                const int w = len[d] > kWalkMaxRows ? 1 : 0;
+                const int w = lens.len[d] > kWalkMaxRows ? 1 : 0;
                 new_id[d] = (int64_t)rows[w].size();
                 rows[w].push_back(d);
             }
             for (int64_t i = 0; i < n_pieces; ++i) {
                 dctfp_piece pc = pieces[i];
-                const int w = len[pc.domain] > kWalkMaxRows ? 1 : 0;
+                const int w = lens.len[pc.domain] > kWalkMaxRows ? 1 : 0;
                 pc.domain = (int32_t)new_id[pc.domain];
                 part[w].push_back(pc);
             }
             for (int w = 0; w < 2; ++w) {
-                const int rc = quantize_impl(ctx, layers, n_layers, n_seq, seq_rows, part[w].data(), (int64_t)part[w].size(),
-                                             (int64_t)rows[w].size(), out, out_stride, stream, rows[w].data());
-                if (rc) return rc;
+                RC_TRY(quantize_impl(ctx, layers, n_layers, n_seq, seq_rows, part[w].data(), (int64_t)part[w].size(), (int64_t)rows[w].size(), out,
+                                     out_stride, stream, rows[w].data()));
             }
             return DCTFP_OK;
         }
@@ -1925,25 +1954,22 @@ int dctfp_quantize_windows(dctfp_ctx* ctx, const dctfp_layer* layers, int32_t n_
 
     // ---- only walk_ab_kernel averages two windows in its row load: a call it would not get is refused before anything runs
     if (two_source) {
-        std::vector<uint32_t> len((size_t)n_domains, 0);
-        uint32_t max_len = 0;
-        for (const dctfp_piece& pc : sub)
-            if (pc.domain >= 0 && pc.domain < n_domains) max_len = std::max(max_len, len[(size_t)pc.domain] += (uint32_t)pc.n_rows);
-        for (int32_t l0 = 0; l0 < n_layers;) {
-            const dctfp_layer& g = layers[l0];
-            int32_t l1 = l0 + 1;
-            while (l1 < n_layers && layers[l1].n_cols == g.n_cols && layers[l1].dtype == g.dtype && layers[l1].ld == g.ld &&
-                   layers[l1].n_keep == g.n_keep && layers[l1].m_keep == g.m_keep)
-                ++l1;
-            const char* why = nullptr;
-            if (!g.seq_data || g.dtype != DCTFP_F32) why = "windows are averaged in float32 (as dctfp_stitch)";
-            else if (!walk_shape(g) || g.m_keep > 80) why = "kept sizes / width outside the one-launch kernel's (n = 3, 64 < m <= 80, 512 <= D <= 2560, D % 4 == 0)";
-            else if (!rows_aligned16(layers + l0, l1 - l0, n_win, nullptr)) why = "rows are not 16-byte aligned";
-            else if (!walk_rows_ok(g, max_len)) why = "a domain above 8 192 rows";
-            else if (!walk_by_path(ctx, (int64_t)(l1 - l0) * n_domains)) why = "fewer than 256 jobs (layers x domains) in the call";
+        // (lengths only, a broken table is the strict pass's to report.  `sub` has no empty piece; a piece that would take its domain past
+        //  2^31 rows is left out of the sum here, where this refusal used to see a wrapped sum: with such a table another error may win)
+        DomainTable lens;
+        (void)build_domain_table(lens, sub.data(), (int64_t)sub.size(), n_domains, n_seq, nullptr);
+        for (int32_t l0 = 0, l1 = 0; l0 < n_layers; l0 = l1) {
+            l1 = layer_group_end(layers, l0, n_layers);
+            int32_t no_data = -1;  // a later layer of the group without seq_data: not "unaligned" but invalid, as validate_layers says
+            auto aligned = [&] {
+                for (int32_t l = l0; l < l1 && no_data < 0; ++l)
+                    if (!layers[l].seq_data) no_data = l;
+                return no_data < 0 && rows_aligned16(layers + l0, l1 - l0, n_win, nullptr);
+            };
+            const char* why = two_source_refusal(ctx, layers[l0], lens.max_len, (int64_t)(l1 - l0) * n_domains, aligned);
+            if (no_data >= 0) return fail(DCTFP_ERR_INVALID, "layer %d: seq_data is NULL", no_data);
             if (why)
                 return fail(DCTFP_ERR_UNSUPPORTED, "dctfp_quantize_windows: layer %d: %s -- stitch with dctfp_stitch_sequences, then dctfp_quantize", l0, why);
-            l0 = l1;
         }
     }
     return quantize_impl(ctx, layers, n_layers, n_seq, seq_rows.data(), sub.data(), (int64_t)sub.size(), n_domains, out, out_stride, stream,

@@ -2,7 +2,10 @@
 // hip_stub.cpp (no GPU, no kernels: see there).  What it covers: every table dctfp_quantize builds (jobs, pieces, walks,
 // runs, cosine-table list), the staging / device copies it sizes, fused-group detection, the split at giant domains, the
 // chunk plan of the two-kernel path, the option surface, the cosine-table cache (failure injection, arena restart).
-// Usage: driver [rounds] [seed]
+// Usage: driver [rounds] [seed] [plain]
+// "plain": the same calls (every random number is still drawn), but no allocation failure, no launch failure and no
+// test_fail_once is injected -- every call runs to its end, which is what two builds' launch logs (hip_stub.cpp,
+// DCTFP_STUB_LAUNCH_LOG) are compared on.
 #include <algorithm>
 #include <cstdint>
 #include <cstdio>
@@ -26,8 +29,9 @@ extern "C" unsigned long stub_fail_launch(long n);
 #include <new>
 static long g_fail_after = -1;   // < 0: never
 static long g_failed = 0;
+static bool g_plain = false;     // mode "plain": nothing is injected
 static void* hooked_alloc(size_t n, size_t align) {
-    if (g_fail_after >= 0 && g_fail_after-- == 0) {
+    if (!g_plain && g_fail_after >= 0 && g_fail_after-- == 0) {
         ++g_failed;
         throw std::bad_alloc();
     }
@@ -80,7 +84,8 @@ static long g_launch_failures = 0;
 template <typename F>
 static int call(const char* name, F f, bool inject = false) {
     g_stream = g_streams[g_rotation++ % 3];
-    const unsigned long fired = stub_fail_launch(inject && g_aux() % 4 == 0 ? (long)(g_aux() % 8) : -1);
+    const long fail_at = inject && g_aux() % 4 == 0 ? (long)(g_aux() % 8) : -1;
+    const unsigned long fired = stub_fail_launch(g_plain ? -1 : fail_at);
     stub_call_begin();
     const int rc = f();
     const long unjoined = stub_call_end(g_stream);
@@ -426,6 +431,7 @@ static int other_entry_points(dctfp_ctx* ctx, std::mt19937_64& rng, int rounds, 
 
 int main(int argc, char** argv) {
     const int rounds = argc > 1 ? atoi(argv[1]) : 300;
+    g_plain = argc > 3 && !strcmp(argv[3], "plain");
     std::mt19937_64 rng(argc > 2 ? strtoull(argv[2], nullptr, 10) : 12345);
     auto uni = [&](int lo, int hi) { return (int)(lo + rng() % (uint64_t)(hi - lo + 1)); };
     g_aux.seed((argc > 2 ? strtoull(argv[2], nullptr, 10) : 12345) ^ 0x5eedu);
@@ -536,7 +542,7 @@ int main(int argc, char** argv) {
         }
         if (uni(0, 40) == 0) CHECK(dctfp_set_option(ctx, "basis_cap_kb", 64));
         const bool inject = uni(0, 25) == 0;
-        if (inject) CHECK(dctfp_set_option(ctx, "test_fail_once", 1));
+        if (inject && !g_plain) CHECK(dctfp_set_option(ctx, "test_fail_once", 1));
         // ---- the call (twice: the second is served from the caches); one call in six with a failing allocation inside
         const bool starve = uni(0, 5) == 0;
         for (int rep = 0; rep < 2; ++rep) {
@@ -600,6 +606,32 @@ int main(int argc, char** argv) {
             free(big[l]);
             for (int s = 0; s < n_seq; ++s) free(data[l][s]);
         }
+    }
+    // ---- a layer no kernel can run (n_cols <= 0) is an error code, whatever looks at the layers before they are validated: the split
+    // at giant domains (300 domains: large enough to be asked) and the early refusal of a two-source windows call.  (No random number
+    // is drawn and nothing is launched: the launch log of a seed stays what it was.)
+    for (const int bad_cols : {0, -3}) {
+        const int n_dom = 300;
+        const int64_t rows = 300;
+        std::vector<dctfp_piece> pcs;
+        for (int d = 0; d < n_dom; ++d) pcs.push_back({0, 300, d, 0, 0});
+        const void* data[2] = {&rows, &rows};   // never read: the call ends before anything looks at the rows
+        const dctfp_layer bad{data, 64, bad_cols, DCTFP_F32, 3, 4, 0, 0};
+        std::vector<int8_t> out((size_t)n_dom * 12);
+        int rc = dctfp_quantize(ctx, &bad, 1, 1, &rows, pcs.data(), n_dom, n_dom, out.data(), 12, nullptr);
+        if (rc != DCTFP_ERR_INVALID) {
+            fprintf(stderr, "dctfp_quantize with n_cols = %d -> %d: %s\n", bad_cols, rc, dctfp_last_error());
+            return 1;
+        }
+        const int64_t seq_win[2] = {0, 2};
+        const int32_t win_rows[2] = {250, 250};   // overlap 200: 300 stitched rows, 200 of them the mean of two windows' rows
+        rc = dctfp_quantize_windows(ctx, &bad, 1, 1, seq_win, win_rows, 200, pcs.data(), n_dom, n_dom, out.data(), 12, nullptr);
+        if (rc != DCTFP_ERR_UNSUPPORTED) {
+            fprintf(stderr, "dctfp_quantize_windows with n_cols = %d -> %d: %s\n", bad_cols, rc, dctfp_last_error());
+            return 1;
+        }
+        n_calls += 2;
+        n_errors_expected += 2;
     }
     int n_other_calls = 0, n_other_expected = 0;
     if (other_entry_points(ctx, rng, std::max(20, rounds / 3), &n_other_calls, &n_other_expected)) return 1;

@@ -4,6 +4,10 @@
 // instead `hipLaunchKernel` walks the job tables of the main kernels the way their waves do and touches every address they
 // would (first / last byte of every row range, cosine table, output block): an index that is wrong on the host side
 // shows up here as a heap-buffer-overflow instead of as a GPU fault on the box.
+// With DCTFP_STUB_LAUNCH_LOG=<file> in the environment every launch is also written down, one line each: kernel, grid, block,
+// dynamic LDS bytes, ordinal of the stream, the scalar arguments decoded below and -- for the kernels whose tables are walked --
+// a 64-bit hash over the JobA / PieceA / JobB / Walk / Run records the launch reaches (pointers as null / non-null only).  Two
+// builds of the host code that plan the same launches write the same file (driver.cpp, mode "plain").
 // Test infrastructure only: never linked into the product.
 #include <hip/hip_runtime_api.h>
 
@@ -80,6 +84,25 @@ int template_int(const std::string& n, const char* kernel, int index) {  // the 
 }
 unsigned long g_walk_launches = 0, g_stage_a_launches = 0, g_jobs_walked = 0;
 
+// ---- the launch log (off unless asked for).  Fixed buffers: nothing here may go through operator new (driver.cpp hooks it).
+FILE* g_log = nullptr;
+uint64_t g_hash = 0;
+bool g_hashed = false;
+char g_scalars[256];
+size_t g_scalars_len = 0;
+inline void mix(uint64_t v) {  // FNV-1a over the eight bytes of v
+    g_hashed = true;
+    for (int i = 0; i < 8; ++i) g_hash = (g_hash ^ ((v >> (8 * i)) & 0xff)) * 0x100000001b3ull;
+}
+inline void mix(const JobA& j) { mix(j.piece_begin); mix(j.n_pieces); mix(j.n_rows); mix(j.reserved); mix(j.basis != nullptr); mix(j.w_basis != nullptr); mix(j.w_ref != nullptr); }
+inline void mix(const PieceA& p) { mix(p.ptr != nullptr); mix(p.n_rows); mix(p.t0); mix(p.w0); mix(p.reserved); mix(p.ptr2 != nullptr); }
+inline void mix(const JobB& j) { mix((uint64_t)j.out_off); }
+inline void mix(const Walk& w) { mix(w.job_begin); mix(w.n_parts); mix((uint64_t)(int64_t)w.whole_job); mix(w.reserved); }
+inline void mix(const Run& r) { mix(r.walk_begin); mix(r.n_walks); mix(r.job_begin); mix(r.n_jobs); }
+void scalar(const char* name, long long v) {
+    if (g_log && g_scalars_len < sizeof g_scalars) g_scalars_len += (size_t)snprintf(g_scalars + g_scalars_len, sizeof g_scalars - g_scalars_len, " %s=%lld", name, v);
+}
+
 void emulate_walk(const std::string& name, dim3 grid, void** a) {
     const JobA* jobs = *(const JobA**)a[0];
     const JobB* jobb = *(const JobB**)a[1];
@@ -99,11 +122,14 @@ void emulate_walk(const std::string& name, dim3 grid, void** a) {
     if ((nt_w != 5 && nt_w != 6) || m > nt_w * 16 || (nt_w == 6 && m <= 80)) { fprintf(stderr, "stub: walk_ab_kernel build of %d column groups for m = %d\n", nt_w, m); abort(); }
     touch(stf, (size_t)(groups * 4 + 4) * nt_w * 64 * sizeof(double));  // fragments up to 4 k-steps past the last group
     ++g_walk_launches;
+    scalar("n_cols", n_cols), scalar("ld", ld), scalar("m", m);
     for (unsigned b = 0; b < grid.x; ++b) {
         const Run run = runs[b];
+        mix(run);
         uint32_t pending = 0, group_job = run.job_begin, jobs_seen = 0;
         for (uint32_t wi = 0; wi < run.n_walks; ++wi) {
             const Walk wk = walks[run.walk_begin + wi];
+            mix(wk);
             const bool has_w = wk.whole_job >= 0;
             const uint32_t w_rows = has_w ? jobs[wk.whole_job].n_rows : 0;
             const uint32_t n_walk_jobs = wk.n_parts + (has_w ? 1u : 0u);
@@ -115,9 +141,11 @@ void emulate_walk(const std::string& name, dim3 grid, void** a) {
                 }
                 if (part < wk.n_parts) {
                     const JobA job = jobs[job_id];
+                    mix(job);
                     uint32_t rows = 0;
                     for (uint32_t p = 0; p < job.n_pieces; ++p) {
                         const PieceA pc = pieces[job.piece_begin + p];
+                        mix(pc);
                         if (pc.n_rows == 0 || pc.t0 != rows) { fprintf(stderr, "stub: piece table of job %u broken\n", job_id); abort(); }
                         touch(pc.ptr, (size_t)n_cols * esz);
                         touch((const char*)pc.ptr + (size_t)(pc.n_rows - 1) * (size_t)ld * esz, (size_t)n_cols * esz);
@@ -144,7 +172,10 @@ void emulate_walk(const std::string& name, dim3 grid, void** a) {
                 ++g_jobs_walked;
                 const bool last = wi + 1 == run.n_walks && part + 1 == n_walk_jobs;
                 if (pending < (uint32_t)G && !last) continue;
-                for (uint32_t g = 0; g < pending; ++g) touch_w(out + jobb[group_job + g].out_off, (size_t)3 * m);
+                for (uint32_t g = 0; g < pending; ++g) {
+                    mix(jobb[group_job + g]);
+                    touch_w(out + jobb[group_job + g].out_off, (size_t)3 * m);
+                }
                 group_job += pending;
                 pending = 0;
             }
@@ -165,13 +196,17 @@ void emulate_stage_a(const std::string& name, dim3 grid, void** a) {
     const size_t esz = elem_size(name, "stage_a_kernel");
     const int nk = template_int(name, "stage_a_kernel", 0) - 1;
     ++g_stage_a_launches;
+    scalar("job_bytes", job_bytes), scalar("n_cols", n_cols), scalar("ld", ld), scalar("n_slabs", n_slabs);
     for (unsigned w = 0; w < grid.x / (unsigned)n_slabs; ++w) {
         const Walk wk = walks[w];
+        mix(wk);
         const bool has_w = wk.whole_job >= 0;
         for (uint32_t part = 0; part < wk.n_parts; ++part) {
             const JobA job = jobs[wk.job_begin + part];
+            mix(job);
             for (uint32_t p = 0; p < job.n_pieces; ++p) {
                 const PieceA pc = pieces[job.piece_begin + p];
+                mix(pc);
                 if (pc.ptr2) { fprintf(stderr, "stub: two-source piece sent to %s\n", name.c_str()); abort(); }
                 touch(pc.ptr, (size_t)n_cols * esz);
                 touch((const char*)pc.ptr + (size_t)(pc.n_rows - 1) * (size_t)ld * esz, (size_t)n_cols * esz);
@@ -215,14 +250,16 @@ void emulate_walk_gen(const std::string& name, dim3 grid, dim3 block, size_t shm
     }
     touch(stp, (size_t)((n_cols + 3) / 4) * nt * 64 * sizeof(double));
     ++g_walk_launches;
+    scalar("n_cols", n_cols), scalar("ld", ld), scalar("m", m), scalar("n_slots", n_slots);
     const int nk = n - 1;
     for (unsigned b = 0; b < grid.x; ++b) {
         const Run run = runs[b];
+        mix(run);
         uint32_t jn = 0;
         const uint32_t n_walks = fused ? run.n_walks : run.n_jobs;
         for (uint32_t wi = 0; wi < n_walks; ++wi) {
             Walk wk{run.job_begin + wi, 1, -1, 0};
-            if (fused) wk = walks[run.walk_begin + wi];
+            if (fused) mix(wk = walks[run.walk_begin + wi]);
             const bool has_w = fused && wk.whole_job >= 0;
             const uint32_t w_rows = has_w ? jobs[wk.whole_job].n_rows : 0;
             const uint32_t n_walk_jobs = wk.n_parts + (has_w ? 1u : 0u);
@@ -234,9 +271,11 @@ void emulate_walk_gen(const std::string& name, dim3 grid, dim3 block, size_t shm
                 }
                 if (part < wk.n_parts) {
                     const JobA job = jobs[job_id];
+                    mix(job);
                     uint32_t rows = 0;
                     for (uint32_t p = 0; p < job.n_pieces; ++p) {
                         const PieceA pc = pieces[job.piece_begin + p];
+                        mix(pc);
                         if (pc.n_rows == 0 || pc.t0 != rows) { fprintf(stderr, "stub: piece table of job %u broken\n", job_id); abort(); }
                         if (pc.ptr2) { fprintf(stderr, "stub: two-source piece sent to %s\n", name.c_str()); abort(); }
                         touch(pc.ptr, (size_t)n_cols * esz);
@@ -251,6 +290,7 @@ void emulate_walk_gen(const std::string& name, dim3 grid, dim3 block, size_t shm
                     if (rows != job.n_rows || (int)rows < n) { fprintf(stderr, "stub: job %u has %u rows, its pieces %u\n", job_id, job.n_rows, rows); abort(); }
                     if (has_w) touch(job.w_ref, (size_t)n_cols * esz);
                 }
+                mix(jobb[job_id]);
                 touch_w(out + jobb[job_id].out_off, (size_t)n * m);
                 ++g_jobs_walked;
             }
@@ -262,6 +302,8 @@ void emulate_walk_gen(const std::string& name, dim3 grid, dim3 block, size_t shm
 void emulate_basis(dim3 grid, void** a) {
     const BasisJob* tabs = *(const BasisJob**)a[0];
     const int nk = *(int*)a[1];
+    scalar("nk", nk);
+    for (unsigned y = 0; y < grid.y; ++y) mix(tabs[y].len);  // (the lengths of the fresh cosine tables, in the order of the list)
     for (unsigned y = 0; y < grid.y; ++y) touch_w(tabs[y].tab, ((size_t)tabs[y].len * nk + ((size_t)tabs[y].len + 1) * nk) * sizeof(double));
 }
 
@@ -315,7 +357,9 @@ void emulate_stage_b(void** a) {
     int8_t* out = *(int8_t**)a[8];
     const char* ypb = *(const char**)a[0];
     const int64_t job_bytes = *(int64_t*)a[1];
+    scalar("job_bytes", job_bytes), scalar("rows", rows), scalar("n", n), scalar("m", m);
     for (int64_t j = 0; j < rows / n; ++j) {
+        mix(jobs[j]);
         touch(ypb + (size_t)j * job_bytes, (size_t)job_bytes);
         touch_w(out + jobs[j].out_off, (size_t)n * m);
     }
@@ -425,11 +469,21 @@ hipError_t hipLaunchKernel(const void* fn, dim3 grid, dim3 block, void** args, s
     if (it == names().end()) { fprintf(stderr, "stub: launch of an unregistered kernel\n"); abort(); }
     const std::string& n = it->second;
     if (grid.x == 0 || grid.y == 0 || block.x == 0 || block.x > 1024) { fprintf(stderr, "stub: bad launch shape of %s\n", n.c_str()); abort(); }
+    static const char* log_path = getenv("DCTFP_STUB_LAUNCH_LOG");
+    if (log_path && !g_log && !(g_log = fopen(log_path, "w"))) { fprintf(stderr, "stub: cannot write %s\n", log_path); abort(); }
+    g_hash = 0xcbf29ce484222325ull, g_hashed = false, g_scalars_len = 0, g_scalars[0] = 0;
     if (n.find("walk_gen_kernel") != std::string::npos) emulate_walk_gen(n, grid, block, shmem, args);
     else if (n.find("walk_ab_kernel") != std::string::npos) emulate_walk(n, grid, args);
     else if (n.find("stage_a_kernel") != std::string::npos) emulate_stage_a(n, grid, args);
     else if (n.find("basis_kernel") != std::string::npos) emulate_basis(grid, args);
     else if (n.find("stage_b_mfma_kernel") != std::string::npos) emulate_stage_b(args);
+    if (g_log) {
+        fprintf(g_log, "%s grid=%u,%u,%u block=%u,%u,%u lds=%zu stream=%d%s", n.c_str(), grid.x, grid.y, grid.z, block.x, block.y, block.z, shmem,
+                of(stream)->id, g_scalars);
+        if (g_hashed) fprintf(g_log, " tables=%016llx", (unsigned long long)g_hash);
+        fputc('\n', g_log);
+        fflush(g_log);
+    }
     return hipSuccess;
 }
 }
