@@ -2867,6 +2867,56 @@ int dctfp_cluster_labels(dctfp_ctx* ctx, int32_t* parent, int64_t n_nodes, int32
     return DCTFP_OK;
 } DCTFP_GUARD("dctfp_cluster_labels")
 
+int dctfp_greedy_decide(dctfp_ctx* ctx, int32_t* assign, int32_t* state, const int32_t* blocked, int64_t n_nodes, int64_t i0, int64_t i1,
+                        int32_t round, int64_t* undecided, void* stream_v) try {
+    if (!ctx || !assign || !state || !blocked || !undecided) return fail(DCTFP_ERR_INVALID, "dctfp_greedy_decide: NULL argument");
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    if (n_nodes < 0 || i0 < 0 || i1 < i0 || round < 0) return fail(DCTFP_ERR_INVALID, "dctfp_greedy_decide: bad shape or round");
+    if (n_nodes > 0x7fffffff) return fail(DCTFP_ERR_LIMIT, "dctfp_greedy_decide: more than 2^31 - 1 nodes");
+    if (i1 > n_nodes) return fail(DCTFP_ERR_INVALID, "dctfp_greedy_decide: the range names proteins outside the nodes");
+    if (i1 == i0) return DCTFP_OK;
+    HIP_TRY(hipSetDevice(ctx->device));
+    launch_greedy_decide(assign, state, blocked, i0, i1, round, reinterpret_cast<unsigned long long*>(undecided), (hipStream_t)stream_v);
+    HIP_TRY(hipGetLastError());
+    return DCTFP_OK;
+} DCTFP_GUARD("dctfp_greedy_decide")
+
+int dctfp_greedy_tri_mark(dctfp_ctx* ctx, const int32_t* tile, int64_t n_rows, int64_t n_cols, int64_t ld, int64_t row0, int64_t col0,
+                          const uint8_t* row_empty, const uint8_t* col_empty, int32_t cap, int32_t bound, int32_t* assign, const int32_t* state,
+                          int32_t* blocked, int64_t n_nodes, int64_t range_end, int32_t next_round, void* stream_v) try {
+    if (!ctx || !tile || !assign || !state || !blocked) return fail(DCTFP_ERR_INVALID, "dctfp_greedy_tri_mark: NULL argument");
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    if (n_rows < 0 || n_cols < 0 || ld < n_cols || row0 < 0 || col0 < 0 || cap < 0 || bound < -1 || bound > cap || n_nodes < 0 ||
+        range_end < 0 || next_round < 1 || (reinterpret_cast<uintptr_t>(tile) & 3u) != 0)
+        return fail(DCTFP_ERR_INVALID, "dctfp_greedy_tri_mark: bad shape, bound, round or alignment");
+    if (n_nodes > 0x7fffffff) return fail(DCTFP_ERR_LIMIT, "dctfp_greedy_tri_mark: more than 2^31 - 1 nodes");
+    // (every (i, j) the kernel can form lies inside the tile, every stamp below range_end: bounded here, not on the device)
+    if (row0 + n_rows > n_nodes || col0 + n_cols > n_nodes || range_end > n_nodes)
+        return fail(DCTFP_ERR_INVALID, "dctfp_greedy_tri_mark: the tile or the range names proteins outside the nodes");
+    if (n_rows == 0 || n_cols == 0 || n_nodes == 0) return DCTFP_OK;
+    HIP_TRY(hipSetDevice(ctx->device));
+    launch_greedy_tri_mark(tile, n_rows, n_cols, ld, row0, col0, row_empty, col_empty, cap, bound, assign, state, blocked, range_end, next_round,
+                           (hipStream_t)stream_v);
+    HIP_TRY(hipGetLastError());
+    return DCTFP_OK;
+} DCTFP_GUARD("dctfp_greedy_tri_mark")
+
+int dctfp_greedy_pairs_mark(dctfp_ctx* ctx, const int32_t* pi, const int32_t* pj, int64_t n_pairs, int32_t* assign, const int32_t* state,
+                            int32_t* blocked, int64_t n_nodes, int64_t range_end, int32_t next_round, void* stream_v) try {
+    if (!ctx || !assign || !state || !blocked || ((!pi || !pj) && n_pairs > 0)) return fail(DCTFP_ERR_INVALID, "dctfp_greedy_pairs_mark: NULL argument");
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    if (n_pairs < 0 || n_nodes < 0 || range_end < 0 || next_round < 1) return fail(DCTFP_ERR_INVALID, "dctfp_greedy_pairs_mark: bad shape or round");
+    // (one thread per pair in 256-thread workgroups, as dctfp_link_pairs' limit)
+    if (n_nodes > 0x7fffffff || n_pairs > (int64_t)1 << 31)
+        return fail(DCTFP_ERR_LIMIT, "dctfp_greedy_pairs_mark: more than 2^31 - 1 nodes or 2^31 pairs per call");
+    if (range_end > n_nodes) return fail(DCTFP_ERR_INVALID, "dctfp_greedy_pairs_mark: the range names proteins outside the nodes");
+    if (n_pairs == 0 || n_nodes == 0) return DCTFP_OK;
+    HIP_TRY(hipSetDevice(ctx->device));
+    launch_greedy_pairs_mark(pi, pj, n_pairs, assign, state, blocked, n_nodes, range_end, next_round, (hipStream_t)stream_v);
+    HIP_TRY(hipGetLastError());
+    return DCTFP_OK;
+} DCTFP_GUARD("dctfp_greedy_pairs_mark")
+
 int dctfp_l1_knn(dctfp_ctx* ctx, const int8_t* q, int64_t nq, int64_t ldq, const int8_t* b, int64_t nb, int64_t ldb, int32_t d, int32_t k,
                  int64_t col0, int32_t* out_val, int32_t* out_idx, void* stream_v) try {
     if (!ctx || !q || !b || !out_val || !out_idx) return fail(DCTFP_ERR_INVALID, "dctfp_l1_knn: NULL argument");

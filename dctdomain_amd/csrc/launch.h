@@ -177,6 +177,17 @@ void launch_tri_link(const int32_t* tile, int64_t n_rows, int64_t n_cols, int64_
 void launch_link_pairs(const int32_t* pi, const int32_t* pj, int64_t n_pairs, int32_t* parent, int64_t n_nodes, hipStream_t stream);
 void launch_cluster_labels(int32_t* parent, int64_t n_nodes, int32_t* labels, hipStream_t stream);
 
+// greedy incremental clusters at a cut-off (k_greedy.hip): rounds over a range of nodes [i0, i1) -- decide (one thread per node;
+// *undecided grows by the nodes left undecided), then mark from a tile's rows / from a list of pairs (new representatives lower
+// assign at their surviving entries, undecided rows stamp blocked inside the range with the next round's number)
+void launch_greedy_decide(int32_t* assign, int32_t* state, const int32_t* blocked, int64_t i0, int64_t i1, int32_t round,
+                          unsigned long long* undecided, hipStream_t stream);
+void launch_greedy_tri_mark(const int32_t* tile, int64_t n_rows, int64_t n_cols, int64_t ld, int64_t row0, int64_t col0, const uint8_t* row_empty,
+                            const uint8_t* col_empty, int32_t cap, int32_t bound, int32_t* assign, const int32_t* state, int32_t* blocked,
+                            int64_t range_end, int32_t next_round, hipStream_t stream);
+void launch_greedy_pairs_mark(const int32_t* pi, const int32_t* pj, int64_t n_pairs, int32_t* assign, const int32_t* state, int32_t* blocked,
+                              int64_t n_nodes, int64_t range_end, int32_t next_round, hipStream_t stream);
+
 // DCTdomain of every protein pair from the fingerprints (k_protein.hip): scratch bytes of one side's block plan, and the launches
 // (the two plans, then the protein-minimum kernel on a grid of n_workgroups that walks the block pairs)
 size_t protein_plan_bytes(int64_t np);

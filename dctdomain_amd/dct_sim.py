@@ -2,8 +2,8 @@
 fingerprints (``-dct.npz``), with the L1 distances computed on the GPU.
 
     python -m dctdomain_amd.dct_sim --dct X-dct.npz [--pair P | --db Y-dct.npz [--rank {global,domain}]] [--output F]
-                                    [--pairfound F] [--top 5] [--threshold 0.25] [--min-domain X] [--min-global Y] [--cluster]
-                                    [--domains] [--dom X.dom] [--db-dom Y.dom]
+                                    [--pairfound F] [--top 5] [--threshold 0.25] [--min-domain X] [--min-global Y]
+                                    [--cluster [--linkage {single,greedy}]] [--domains] [--dom X.dom] [--db-dom Y.dom]
 
 Same flags, same output text (src/dct-sim.py:179-211); ``--rank domain`` (not in the reference) orders database hits by
 DCTdomain instead of DCTglobal, and ``--min-domain`` / ``--min-global`` (not in the reference either, which ignores
@@ -23,7 +23,11 @@ Where the reference loops over protein pairs and, inside, over domain pairs in P
   (``dctfp_pair_min``) and their lines (``dctfp_pair_lines``);
 - ``cluster_sim`` (``--cluster`` with a cut-off, not in the reference) joins those pairs into single-linkage clusters instead of
   printing them (``Clusters``): the same tiles, a lock-free union-find on the device (``dctfp_tri_link`` / ``dctfp_link_pairs``
-  / ``dctfp_cluster_labels``), one ``representative member`` line per protein;
+  / ``dctfp_cluster_labels``), one ``representative member`` line per protein.  ``--linkage greedy`` takes the proteins in file
+  order instead (``Representatives``; CD-HIT's rule): one that no earlier representative has an edge to becomes a representative,
+  every other one goes to the lowest representative it has an edge to -- so every member is within the cut-off of its
+  representative and no two representatives are within it of each other, decided on the device in rounds over the same tiles
+  (``dctfp_greedy_decide`` / ``dctfp_greedy_tri_mark`` / ``dctfp_greedy_pairs_mark``);
 - ``db_search`` ranks on the whole-protein fingerprints only (one L1 per protein pair), selects the printed hits of
   every query on the GPU (``dctfp_select_count`` / ``dctfp_select_fill``) and computes DCTdomain for those pairs only
   (``dctfp_pair_min``): ``ProteinSearch``.  Host memory is what is printed plus one tile, not n_query x n_db.  With
@@ -48,8 +52,8 @@ import time
 
 import numpy as np
 
-from .similarity import (PROTEIN_MIN_MAX_D, LineIds, TextStream, _utf8_binary, block_min, block_min_device, cluster_labels, l1_matrix,
-                         link_pairs, pair_argmin, pair_argmin_device, pair_line_offsets, pair_lines, pair_min, pair_min_device, protein_min,
+from .similarity import (PROTEIN_MIN_MAX_D, GreedyState, LineIds, TextStream, _utf8_binary, block_min, block_min_device, cluster_labels,
+                         greedy_decide, greedy_pairs_mark, greedy_tri_mark, l1_matrix, link_pairs, pair_argmin, pair_argmin_device, pair_line_offsets, pair_lines, pair_min, pair_min_device, protein_min,
                          sim_lines, threshold_select, to_device_int8, tri_filter_count, tri_filter_fill, tri_link)
 
 L1_FULL_SCALE = 17000      # src/dct-sim.py:24
@@ -685,6 +689,79 @@ class Clusters(FilteredPairs):
             sink(memoryview(text))
 
 
+class Representatives(FilteredPairs):
+    """Greedy incremental clusters of one file at cut-offs, in file order, over the graph ``Clusters`` takes the components of
+    (nodes: all proteins; edges: exactly ``FilteredPairs``' pairs):
+
+        for x in 0 .. n - 1:  if no earlier representative has an edge to x, x is a representative;
+                              else x belongs to the lowest representative it has an edge to.
+
+    So every member is within the cut-offs of its representative and no two representatives are within them of each other --
+    the representatives are the lexicographically first maximal independent set: a property of the graph, whatever the stripes,
+    the column groups, the row ranges or the order in which the device ran.  A user who wants CD-HIT's "longest first" sorts the
+    FASTA before ``make_db``.
+
+    The nodes are decided on the device, range by range in ascending order (``GreedyState``: assign, state, blocked).  When a
+    range [i0, i1) starts, every representative below i0 has marked all its columns; a cover pass makes members of the nodes
+    they marked, then rounds of ``greedy_decide`` (a node without a stamp from an earlier undecided node of the range becomes a
+    representative) and a mark launch (new representatives mark all their columns, undecided rows stamp their columns inside
+    the range) until the range has no undecided node.  Only the count of those comes back, once per round.  A full row is walked
+    once; the re-reads stay inside the range's diagonal block.  A path of k nodes inside one range takes about k rounds.
+
+    - One cut-off excludes anything: the ranges are the stripes of ``FilteredPairs.tiles``, marked by ``greedy_tri_mark``.
+    - Both do: the ranges are the rows of ``FilteredPairs.chunks``' pair lists, marked by ``greedy_pairs_mark``.
+    - Neither does: all labels 0.  A bound below 0: every protein its own.  No tile.
+
+    ``rounds`` = the rounds of the last ``labels()`` over all ranges.  The text is ``Clusters``': ``cluster_lines``."""
+
+    def __init__(self, sid, idx, fps, min_domain=None, min_global=None):
+        super().__init__(sid, idx, fps, min_domain=min_domain, min_global=min_global)
+        self.rounds = 0
+
+    def _decide_range(self, gs, i0: int, i1: int, mark):
+        """Rounds over the nodes [i0, i1); ``mark(next_round)`` = the mark launch of the range's rows."""
+        greedy_decide(gs, i0, i1, 0)
+        if gs.left() == 0:                                      # (every node of the range belongs to an earlier representative)
+            return
+        mark(self._round)                                       # (all rows undecided: the stamps of the first round)
+        while True:
+            greedy_decide(gs, i0, i1, self._round)
+            self._round += 1
+            self.rounds += 1
+            mark(self._round)                                   # (also after the last decide: its representatives mark)
+            if gs.left() == 0:
+                break
+        self._round += 1
+
+    def labels(self) -> np.ndarray:
+        n = len(self.idx) - 1
+        self.rounds = 0
+        if n < 2 or min(self.bound_domain, self.bound_global) < 0:
+            return np.arange(max(n, 0), dtype=np.int32)
+        if min(self.bound_domain, self.bound_global) >= L1_FULL_SCALE:
+            return np.zeros(n, dtype=np.int32)
+        gs = GreedyState(n)
+        self._round = 1                                         # the next unused round number (0 = the cover pass, blocked starts as 0)
+        done = 0                                                # every node below is decided and has marked
+        if max(self.bound_domain, self.bound_global) < L1_FULL_SCALE:
+            for pi, pj, *_ in self.chunks():
+                i1 = int(pi[-1]) + 1                            # (i ascending: the rows of this list end here, and none of them comes again)
+                self._decide_range(gs, done, i1, lambda nxt: greedy_pairs_mark(pi, pj, gs, i1, nxt))
+                done = i1
+        else:
+            for i0, i1, tile, flags in self.tiles():
+                self._decide_range(gs, i0, i1, lambda nxt: greedy_tri_mark(tile, i0, i0 + 1, self.bound, gs, i1, nxt, *flags))
+                done = i1
+                del tile
+        greedy_decide(gs, done, n, self._round)                 # no later neighbour, no stamp of this round: whoever is not marked represents itself
+        return gs.assign.cpu().numpy()
+
+    def write(self, sink):
+        """Calls ``sink(memoryview)`` with the text, whole lines at a time, in order."""
+        for text in cluster_lines(self.sid, self.labels()):
+            sink(memoryview(text))
+
+
 def _add_hits(parts, t0: int, p0: int, off, key, col):
     """``threshold_select``'s hits of a tile -- query proteins from ``t0``, database proteins from ``p0`` -- each row's to the list
     of its query in ``parts``, the columns as database protein indices."""
@@ -935,15 +1012,19 @@ def all_sim(npzfile: str, report: Report, min_domain: float = None, min_global: 
 
 
 @_reporting(header=CLUSTER_HEADER)
-def cluster_sim(npzfile: str, report: Report, min_domain: float = None, min_global: float = None):
-    """Single-linkage clusters at the cut-offs (``Clusters``): one line ``representative member`` per protein."""
+def cluster_sim(npzfile: str, report: Report, min_domain: float = None, min_global: float = None, linkage: str = 'single'):
+    """Clusters at the cut-offs, one line ``representative member`` per protein: single linkage (``Clusters``) or, with
+    ``linkage='greedy'``, greedy incremental clusters in file order (``Representatives``)."""
     if min_domain is None and min_global is None:
         raise ValueError('clustering needs a cut-off: min_domain, min_global or both')
+    if linkage not in LINKAGES:
+        raise ValueError(f'linkage must be one of {LINKAGES}')
     sid, idx, fps = _load_npz(npzfile)
-    Clusters(sid, idx, fps, min_domain=min_domain, min_global=min_global).write(report.raw)
+    (Representatives if linkage == 'greedy' else Clusters)(sid, idx, fps, min_domain=min_domain, min_global=min_global).write(report.raw)
 
 
 RANKS = ('global', 'domain')
+LINKAGES = ('single', 'greedy')
 
 
 class _Parser(argparse.ArgumentParser):
@@ -951,7 +1032,7 @@ class _Parser(argparse.ArgumentParser):
     ``--min-domain`` / ``--min-global`` cut the all-against-all output: an error beside ``--pair`` or ``--db``.
     ``--cluster`` joins the pairs that pass into clusters: an error beside ``--pair`` or ``--db``, or without a cut-off.
     ``--dom`` / ``--db-dom`` imply ``--domains``; ``--db-dom`` is an error without ``--db``, ``--domains`` beside ``--cluster``
-    (a cluster line has no scores to explain)."""
+    (a cluster line has no scores to explain).  ``--linkage`` says how ``--cluster`` forms its clusters: an error without it."""
 
     def parse_known_args(self, args=None, namespace=None):
         ns, rest = super().parse_known_args(args, namespace)
@@ -961,6 +1042,8 @@ class _Parser(argparse.ArgumentParser):
             self.error('--db-dom names the .dom file of --db: it needs --db')
         if getattr(ns, 'dom', None) is not None or getattr(ns, 'db_dom', None) is not None:
             ns.domains = True
+        if getattr(ns, 'linkage', None) is not None and not getattr(ns, 'cluster', False):
+            self.error('--linkage says how --cluster forms its clusters: it needs --cluster')
         if getattr(ns, 'cluster', False):
             if getattr(ns, 'domains', False):
                 self.error('--domains (--dom, --db-dom) explains the scores of result lines: not with --cluster')
@@ -1000,6 +1083,10 @@ def build_parser() -> argparse.ArgumentParser:
                          '1-based index within the protein; "-" when no pair scores above 0)')
     ap.add_argument('--dom', metavar='FILE', default=argparse.SUPPRESS, help='the .dom file of --dct: print residue ranges instead of indices (implies --domains)')
     ap.add_argument('--db-dom', metavar='FILE', default=argparse.SUPPRESS, help='the .dom file of --db, likewise (implies --domains)')
+    ap.add_argument('--linkage', choices=LINKAGES, default=argparse.SUPPRESS,
+                    help='--cluster: single linkage (the default: connected components, the representative is the first protein of '
+                         'the component) or greedy (in file order, a protein joins the first representative it is within the cut-off '
+                         'of, else it becomes one: every member is within the cut-off of its representative)')
     return ap
 
 
@@ -1014,7 +1101,7 @@ def main(argv=None):
     elif args.db:
         db_search(args.dct, args.db, args.top, args.threshold, report, rank=args.rank or 'global', domains=bool(domains), dom=dom, db_dom=db_dom)
     elif args.cluster:
-        cluster_sim(args.dct, report, min_domain=args.min_domain, min_global=args.min_global)
+        cluster_sim(args.dct, report, min_domain=args.min_domain, min_global=args.min_global, linkage=getattr(args, 'linkage', 'single'))
     else:
         all_sim(args.dct, report, min_domain=args.min_domain, min_global=args.min_global, domains=bool(domains), dom=dom)
     report.close()

@@ -427,6 +427,75 @@ def cluster_labels(parent: torch.Tensor) -> torch.Tensor:
     return labels
 
 
+GREEDY_NONE = 0x7fffffff                       # assign: no representative yet
+GREEDY_UNDECIDED, GREEDY_MEMBER, GREEDY_NEW, GREEDY_DONE = 0, 1, 2, 3
+
+
+class GreedyState:
+    """The device arrays of the greedy linkage over ``n`` nodes (``dctfp_greedy_decide``): ``assign`` (the lowest representative
+    seen so far, ``GREEDY_NONE`` at the start), ``state`` (``GREEDY_UNDECIDED`` at the start) and ``blocked`` (round stamps), int32
+    each, and ``undecided``, the int64 word the decide launches add the nodes they leave undecided to."""
+
+    def __init__(self, n: int, device=None):
+        device = device if device is not None else _dev()
+        self.assign = torch.full((n,), GREEDY_NONE, dtype=torch.int32, device=device)
+        self.state = torch.zeros(n, dtype=torch.int32, device=device)
+        self.blocked = torch.zeros(n, dtype=torch.int32, device=device)
+        self.undecided = torch.zeros(1, dtype=torch.int64, device=device)
+        self._read = 0
+
+    def left(self) -> int:
+        """The nodes the decide launches since the last call left undecided (one copy of 8 bytes: the host waits here)."""
+        total = int(self.undecided.item())
+        new, self._read = total - self._read, total
+        return new
+
+    def arrays(self, device) -> int:
+        for t in (self.assign, self.state, self.blocked):
+            if t.dtype != torch.int32 or t.dim() != 1 or not t.is_contiguous() or t.device != device or t.numel() != self.assign.numel():
+                raise ValueError('assign / state / blocked must be contiguous 1-D int32 tensors of one length on the device of the other arguments')
+        return self.assign.numel()
+
+
+def greedy_decide(gs: GreedyState, i0: int, i1: int, round: int):
+    """One decide launch over the nodes [i0, i1) (``dctfp_greedy_decide``): round 0 makes members only; ``gs.left()`` then says how
+    many nodes of the range are still undecided."""
+    n_nodes = gs.arrays(gs.assign.device)
+    if not 0 <= i0 <= i1 <= n_nodes:
+        raise IndexError('range outside the nodes')
+    if i1 > i0:
+        _launch(gs.assign.device, 'dctfp_greedy_decide', gs.assign.data_ptr(), gs.state.data_ptr(), gs.blocked.data_ptr(), n_nodes, int(i0), int(i1),
+                int(round), gs.undecided.data_ptr())
+
+
+def greedy_tri_mark(tile: torch.Tensor, row0: int, col0: int, bound: int, gs: GreedyState, range_end: int, next_round: int, row_empty=None,
+                    col_empty=None, cap: int = 17000):
+    """The mark launch of a round from an L1 tile (``dctfp_greedy_tri_mark``): over the entries ``tri_filter_count`` would count, a
+    row that is a new representative lowers ``assign`` of its columns, an undecided row stamps ``blocked`` of its columns below
+    ``range_end`` with ``next_round``."""
+    n_rows, n_cols, ld, re, ce, bound = _tri_filter_args(tile, row0, col0, bound, row_empty, col_empty, cap)
+    n_nodes = gs.arrays(tile.device)
+    if row0 + n_rows > n_nodes or col0 + n_cols > n_nodes or not 0 <= range_end <= n_nodes:
+        raise IndexError('tile or range outside the nodes')
+    if n_rows and n_cols:
+        _launch(tile.device, 'dctfp_greedy_tri_mark', tile.data_ptr(), n_rows, n_cols, ld, int(row0), int(col0), _ptr(re), _ptr(ce), cap, bound,
+                gs.assign.data_ptr(), gs.state.data_ptr(), gs.blocked.data_ptr(), n_nodes, int(range_end), int(next_round))
+
+
+def greedy_pairs_mark(pi: torch.Tensor, pj: torch.Tensor, gs: GreedyState, range_end: int, next_round: int):
+    """The mark launch of a round from pairs (pi[n], pj[n]) (device int32, ``tri_filter_fill``'s output; ``dctfp_greedy_pairs_mark``);
+    the kernel skips a pair that names a node outside the state."""
+    n_nodes = gs.arrays(pi.device)
+    for t in (pi, pj):
+        if t.dtype != torch.int32 or t.dim() != 1 or t.numel() != pi.numel() or not t.is_contiguous() or t.device != gs.assign.device:
+            raise ValueError('pi / pj must be contiguous int32 device tensors of one length')
+    if not 0 <= range_end <= n_nodes:
+        raise IndexError('range outside the nodes')
+    if pi.numel() and n_nodes:
+        _launch(pi.device, 'dctfp_greedy_pairs_mark', pi.data_ptr(), pj.data_ptr(), pi.numel(), gs.assign.data_ptr(), gs.state.data_ptr(),
+                gs.blocked.data_ptr(), n_nodes, int(range_end), int(next_round))
+
+
 class LineIds:
     """The protein ids of a file as ``dctfp_sim_lines`` reads them: ``off`` = int64 prefix offsets of their UTF-8 bytes (host),
     ``bytes_dev`` / ``off_dev`` = the concatenated bytes and the offsets on the device."""

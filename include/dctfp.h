@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define DCTFP_VERSION 105 /* 0.1.5: dctfp_pair_argmin, dctfp_pair_domain_lines */
+#define DCTFP_VERSION 106 /* 0.1.6: dctfp_greedy_decide, dctfp_greedy_tri_mark, dctfp_greedy_pairs_mark */
 
 #define DCTFP_OK 0
 #define DCTFP_ERR_INVALID (-1) /* bad argument (null pointer, piece outside its sequence, ...) */
@@ -440,6 +440,43 @@ int dctfp_link_pairs(dctfp_ctx* ctx, const int32_t* pi, const int32_t* pj, int64
  * forest handed in is not the run time), the second reads.  `parent` is left a valid forest of the same components, so linking
  * may go on afterwards.  DCTFP_ERR_LIMIT for n_nodes >= 2^31; n_nodes of 0: nothing to do. */
 int dctfp_cluster_labels(dctfp_ctx* ctx, int32_t* parent, int64_t n_nodes, int32_t* labels, void* stream);
+
+/* Greedy incremental clusters at a cut-off (dct-sim --cluster --linkage greedy; not in the reference): over the graph whose edges
+ * are the pairs dctfp_tri_filter_count / dctfp_tri_filter_fill select, the proteins taken in file order -- one that no earlier
+ * representative has an edge to becomes a representative, every other one belongs to the lowest representative it has an edge to.
+ * So every member is within the cut-off of its representative and no two representatives are within it of each other, which the
+ * components of dctfp_tri_link do not promise.  Device int32 (n_nodes) each, handed to any number of these calls on one stream:
+ * `assign` = the lowest representative seen so far (started as 0x7fffffff; a representative's own index), `state` = 0 undecided
+ * / 1 member / 2 representative decided by the latest dctfp_greedy_decide over its range / 3 representative done (started as 0),
+ * `blocked` = a round number (started as 0).  The caller takes the nodes in ranges [i0, i1) in ascending order -- when a range
+ * starts, every representative below i0 has marked all its columns -- and runs rounds over a range until none of it is undecided:
+ * a decide, then a mark of the range's rows (dctfp_greedy_tri_mark or dctfp_greedy_pairs_mark).  At the end assign holds the
+ * labels; they are a property of the graph, whatever the ranges or the order in which the device ran.
+ * dctfp_greedy_decide, one thread per node of [i0, i1): a representative of state 2 becomes 3; an undecided node becomes a member
+ * if assign is set, else a representative (assign = its index, state 2) unless blocked holds `round`, else it stays undecided.
+ * round 0 makes members only (the pass a range starts with, before its first mark).  *undecided (device int64, the caller's
+ * running total) grows by the nodes left undecided.  DCTFP_ERR_INVALID for i0 > i1, i1 > n_nodes or a negative round;
+ * DCTFP_ERR_LIMIT for n_nodes >= 2^31.  An empty range: nothing to do. */
+int dctfp_greedy_decide(dctfp_ctx* ctx, int32_t* assign, int32_t* state, const int32_t* blocked, int64_t n_nodes, int64_t i0, int64_t i1,
+                        int32_t round, int64_t* undecided, void* stream);
+
+/* The mark of a round of dctfp_greedy_decide from a tile: dctfp_tri_link's walk and arguments -- dctfp_tri_filter_count's survival
+ * rule, j > i and min(L1, cap) <= bound, the same flags -- over the rows of a range that ends at range_end.  A row of state 2 (a
+ * new representative) lowers assign[j] to its index at every surviving entry (atomic min); a row still undecided looks at the
+ * columns j < range_end only and stores next_round into blocked[j] there; any other row is skipped.  state is only read.
+ * DCTFP_ERR_INVALID as dctfp_tri_link, for range_end > n_nodes and for next_round < 1; DCTFP_ERR_LIMIT for n_nodes >= 2^31.
+ * n_rows, n_cols or n_nodes of 0: nothing to do. */
+int dctfp_greedy_tri_mark(dctfp_ctx* ctx, const int32_t* tile, int64_t n_rows, int64_t n_cols, int64_t ld, int64_t row0, int64_t col0,
+                          const uint8_t* row_empty, const uint8_t* col_empty, int32_t cap, int32_t bound, int32_t* assign, const int32_t* state,
+                          int32_t* blocked, int64_t n_nodes, int64_t range_end, int32_t next_round, void* stream);
+
+/* dctfp_greedy_tri_mark for a LIST of pairs (pi[n], pj[n]), device int32, as dctfp_link_pairs is to dctfp_tri_link -- what is left
+ * of dctfp_tri_filter_fill's output after a second cut-off: the pairs whose lower end lies in the range.  One thread per pair,
+ * the pair taken as (lo, hi) of its ends: lo of state 2 lowers assign[hi] to lo, lo undecided with hi < range_end stores
+ * next_round into blocked[hi].  A pair with an index outside [0, n_nodes) or with both ends equal is skipped.  DCTFP_ERR_LIMIT
+ * for n_nodes >= 2^31 or more than 2^31 pairs per call; n_pairs or n_nodes of 0: nothing to do. */
+int dctfp_greedy_pairs_mark(dctfp_ctx* ctx, const int32_t* pi, const int32_t* pj, int64_t n_pairs, int32_t* assign, const int32_t* state,
+                            int32_t* blocked, int64_t n_nodes, int64_t range_end, int32_t next_round, void* stream);
 
 /* query_db's search (src/query_db.py:75-87: a flat FAISS index forced to METRIC_L1 at :76, index.search at :87) without a
  * distance matrix: for query rows q (nq x d, row stride ldq) and database rows b (nb x d, stride ldb), int8 on the device, each

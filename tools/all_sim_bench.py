@@ -14,7 +14,8 @@ copies of others first: random proteins alone leave nothing above a cut-off.
 `cluster` loads one synthetic file (--families x --family-size proteins overwritten with near copies of a family's first member)
 and runs, after a warm-up of both on a small file, --repeat times each: the path with cut-offs (FilteredPairs, to /dev/null) and
 the clustering at the same cut-offs (Clusters); events around the device steps of the latter (tile / link / labels), the host
-text timed apart.
+text timed apart.  Then the greedy linkage (Representatives) on the same file in the same way: its device steps (tile / decide /
+mark), its rounds, and how many proteins its labels move away from single linkage's.
 `domains` is `cluster`'s procedure for --domains: the path with cut-offs without the flag, then with it (labels = the 1-based index
 of a fingerprint within its protein), --repeat times each in that order, events around the device steps of the second.
 `scale` writes a synthetic -dct.npz (about 4.5 fingerprints per protein, 17-character ids) and runs the new path in a child
@@ -217,8 +218,8 @@ def plant_families(idx, fps, families: int, size: int, seed: int = 13):
 
 
 def part_cluster(args):
-    """One process: FilteredPairs to /dev/null and Clusters at the same cut-offs on the same loaded file, --repeat times each
-    after a warm-up of both on a small one; device time of the clustering by step."""
+    """One process: FilteredPairs to /dev/null, Clusters and Representatives at the same cut-offs on the same loaded file, --repeat
+    times each after a warm-up of all three on a small one; device time of the two clusterings by step."""
     import torch
     from dctdomain_amd import dct_sim
     min_domain = args.min_domain if args.min_domain is not None or args.min_global is not None else 0.5
@@ -253,8 +254,10 @@ def part_cluster(args):
             kept[0] += bytes(mv).count(b'\n')
         dct_sim.FilteredPairs(wsid, widx, wfps, min_domain, args.min_global).write(sink)
         dct_sim.Clusters(wsid, widx, wfps, min_domain, args.min_global).write(sink)
+        dct_sim.Representatives(wsid, widx, wfps, min_domain, args.min_global).write(sink)
         torch.cuda.synchronize()
         t_filter, t_cluster, t_text, device_ms = [], [], [], []
+        t_greedy, greedy_ms, rounds = [], [], []
         for _ in range(args.repeat):
             written[0] = kept[0] = 0
             fp = dct_sim.FilteredPairs(sid, idx, fps, min_domain, args.min_global)
@@ -284,20 +287,46 @@ def part_cluster(args):
             device_ms.append({label: round(sum(a.elapsed_time(b) for a, b in ev), 3) for label, ev in spans.items()})
         for name, fn in real:
             setattr(dct_sim, name, fn)
+        cluster_bytes, cluster_lines = written[0], kept[0]
+        steps = (('protein_min', 'tile'), ('l1_matrix', 'tile'), ('greedy_decide', 'decide'), ('greedy_tri_mark', 'mark'),
+                 ('greedy_pairs_mark', 'mark'), ('tri_filter_count', 'filter'), ('tri_filter_fill', 'filter'), ('pair_min_device', 'pair_min'))
+        real = [(name, timed(name, label)) for name, label in steps]
+        for _ in range(args.repeat):
+            spans.clear()
+            rp = dct_sim.Representatives(sid, idx, fps, min_domain, args.min_global)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            greedy = rp.labels()
+            torch.cuda.synchronize()
+            t1 = time.perf_counter()
+            for text in dct_sim.cluster_lines(sid, greedy):
+                sink(memoryview(text))
+            t_greedy.append(time.perf_counter() - t0)
+            rounds.append(rp.rounds)
+            greedy_ms.append({label: round(sum(a.elapsed_time(b) for a, b in ev), 3) for label, ev in spans.items()})
+        for name, fn in real:
+            setattr(dct_sim, name, fn)
     n = len(sid)
     med = lambda v: sorted(v)[len(v) // 2]   # noqa: E731
     ms = device_ms[t_cluster.index(med(t_cluster))]
+    gms = greedy_ms[t_greedy.index(med(t_greedy))]
+    is_rep = greedy == np.arange(n)
+    res_greedy = {'greedy_s': [round(t, 3) for t in t_greedy], 'greedy_median_s': round(med(t_greedy), 3), 'greedy_rounds': rounds,
+                  'greedy_over_cluster': round(med(t_greedy) / med(t_cluster), 4), 'greedy_within_10_percent': med(t_greedy) <= 1.1 * med(t_cluster),
+                  'greedy_clusters': int(is_rep.sum()), 'greedy_largest': int(np.bincount(greedy).max()),
+                  'greedy_labels_other_than_single': int((greedy != labels).sum()),
+                  'greedy_device_ms_of_median_run': gms, 'greedy_device_ms_all': greedy_ms}
     return {'part': 'cluster', 'n': n, 'fingerprints': int(idx[-1]), 'pairs': n * (n - 1) // 2, 'families': args.families,
             'family_size': args.family_size, 'min_domain': min_domain, 'min_global': args.min_global, 'route': cl.route,
             'stripes': len(list(cl.stripes())), 'edges': edges, 'edge_text_bytes': edge_bytes, 'clusters': int(len(np.unique(labels))),
-            'largest': int(np.bincount(labels).max()), 'cluster_text_bytes': written[0], 'cluster_lines': kept[0],
+            'largest': int(np.bincount(labels).max()), 'cluster_text_bytes': cluster_bytes, 'cluster_lines': cluster_lines,
             'filtered_s': [round(t, 3) for t in t_filter], 'cluster_s': [round(t, 3) for t in t_cluster],
             'cluster_host_text_s': [round(t, 3) for t in t_text], 'filtered_median_s': round(med(t_filter), 3),
             'cluster_median_s': round(med(t_cluster), 3), 'filtered_spread_s': round(max(t_filter) - min(t_filter), 3),
             'cluster_faster': med(t_cluster) < med(t_filter),
             'cluster_within_filtered_spread': med(t_cluster) <= med(t_filter) + (max(t_filter) - min(t_filter)),
             'device_ms_of_median_run': ms, 'device_ms_all': device_ms,
-            'link_over_tile': round(ms.get('link', 0.0) / ms['tile'], 4) if ms.get('tile') else None}
+            'link_over_tile': round(ms.get('link', 0.0) / ms['tile'], 4) if ms.get('tile') else None, **res_greedy}
 
 
 def part_domains(args):
