@@ -62,7 +62,8 @@ EXPORTS = ('dctfp_version', 'dctfp_last_error', 'dctfp_create', 'dctfp_destroy',
            'dctfp_tri_filter_count', 'dctfp_tri_filter_fill', 'dctfp_pair_lines',
            'dctfp_tri_link', 'dctfp_link_pairs', 'dctfp_cluster_labels',
            'dctfp_pair_argmin', 'dctfp_pair_domain_lines',
-           'dctfp_greedy_decide', 'dctfp_greedy_tri_mark', 'dctfp_greedy_pairs_mark')
+           'dctfp_greedy_decide', 'dctfp_greedy_tri_mark', 'dctfp_greedy_pairs_mark',
+           'dctfp_rows_link')
 
 
 def load(path: str = None):
@@ -194,6 +195,8 @@ def _configure(lib):
                                        C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]
         lib.dctfp_link_pairs.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]
         lib.dctfp_cluster_labels.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
+        lib.dctfp_rows_link.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int32,
+                                        C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]
         lib.dctfp_greedy_decide.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.c_void_p,
                                             C.c_void_p]
         lib.dctfp_greedy_tri_mark.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_void_p,

@@ -2867,6 +2867,24 @@ int dctfp_cluster_labels(dctfp_ctx* ctx, int32_t* parent, int64_t n_nodes, int32
     return DCTFP_OK;
 } DCTFP_GUARD("dctfp_cluster_labels")
 
+int dctfp_rows_link(dctfp_ctx* ctx, const int8_t* a, int64_t na, int64_t lda, int64_t a0, const int8_t* b, int64_t nb, int64_t ldb, int64_t b0,
+                    int32_t d, const int32_t* owner, const uint8_t* skip, int32_t cap, int32_t bound, int32_t* parent, int64_t n_nodes,
+                    void* stream_v) try {
+    if (!ctx || !a || !b || !owner || !parent) return fail(DCTFP_ERR_INVALID, "dctfp_rows_link: NULL argument");
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    if (na < 0 || nb < 0 || d < 1 || lda < d || ldb < d || a0 < 0 || b0 < 0 || cap < 0 || bound < 0 || n_nodes < 0)
+        return fail(DCTFP_ERR_INVALID, "dctfp_rows_link: bad shape or bound");
+    if (n_nodes > 0x7fffffff) return fail(DCTFP_ERR_LIMIT, "dctfp_rows_link: more than 2^31 - 1 nodes");
+    // (every node the kernel can form is a row of a or b: bounded here, not on the device)
+    if (a0 + na > n_nodes || b0 + nb > n_nodes) return fail(DCTFP_ERR_INVALID, "dctfp_rows_link: the rows name nodes outside parent");
+    if (na == 0 || nb == 0) return DCTFP_OK;
+    if ((na + 127) / 128 > 65535) return fail(DCTFP_ERR_LIMIT, "dctfp_rows_link: more than 8M rows of a per call");
+    HIP_TRY(hipSetDevice(ctx->device));
+    launch_rows_link(a, na, lda, a0, b, nb, ldb, b0, d, owner, skip, cap, bound, parent, (hipStream_t)stream_v);
+    HIP_TRY(hipGetLastError());
+    return DCTFP_OK;
+} DCTFP_GUARD("dctfp_rows_link")
+
 int dctfp_greedy_decide(dctfp_ctx* ctx, int32_t* assign, int32_t* state, const int32_t* blocked, int64_t n_nodes, int64_t i0, int64_t i1,
                         int32_t round, int64_t* undecided, void* stream_v) try {
     if (!ctx || !assign || !state || !blocked || !undecided) return fail(DCTFP_ERR_INVALID, "dctfp_greedy_decide: NULL argument");

@@ -3,7 +3,8 @@ fingerprints (``-dct.npz``), with the L1 distances computed on the GPU.
 
     python -m dctdomain_amd.dct_sim --dct X-dct.npz [--pair P | --db Y-dct.npz [--rank {global,domain}]] [--output F]
                                     [--pairfound F] [--top 5] [--threshold 0.25] [--min-domain X] [--min-global Y]
-                                    [--cluster [--linkage {single,greedy}]] [--domains] [--dom X.dom] [--db-dom Y.dom]
+                                    [--cluster [--linkage {single,greedy}] [--level {protein,domain} [--no-whole]]] [--domains]
+                                    [--dom X.dom] [--db-dom Y.dom]
 
 Same flags, same output text (src/dct-sim.py:179-211); ``--rank domain`` (not in the reference) orders database hits by
 DCTdomain instead of DCTglobal, and ``--min-domain`` / ``--min-global`` (not in the reference either, which ignores
@@ -28,6 +29,13 @@ Where the reference loops over protein pairs and, inside, over domain pairs in P
   every other one goes to the lowest representative it has an edge to -- so every member is within the cut-off of its
   representative and no two representatives are within it of each other, decided on the device in rounds over the same tiles
   (``dctfp_greedy_decide`` / ``dctfp_greedy_tri_mark`` / ``dctfp_greedy_pairs_mark``);
+- ``--cluster --level domain`` (``DomainClusters``) clusters the fingerprint ROWS of the file instead of its proteins -- the
+  domain families: two rows of different proteins are joined when their own L1 passes ``--min-domain``, where the protein level
+  joins two proteins as soon as any one of their fingerprint pairs does.  One kernel (``dctfp_rows_link``) takes a stripe of
+  rows against the rows from the stripe's start onward: ``dctfp_l1_matrix``'s contraction, compared with the bound in registers
+  and joined in the same union-find -- no distance is stored; then ``dctfp_cluster_labels`` and one
+  ``representative member dom1 dom2`` line per row.  ``--no-whole`` leaves the whole-protein row of every multi-domain protein
+  out; ``--dom`` names the rows by their residue ranges;
 - ``db_search`` ranks on the whole-protein fingerprints only (one L1 per protein pair), selects the printed hits of
   every query on the GPU (``dctfp_select_count`` / ``dctfp_select_fill``) and computes DCTdomain for those pairs only
   (``dctfp_pair_min``): ``ProteinSearch``.  Host memory is what is printed plus one tile, not n_query x n_db.  With
@@ -54,12 +62,13 @@ import numpy as np
 
 from .similarity import (PROTEIN_MIN_MAX_D, GreedyState, LineIds, TextStream, _utf8_binary, block_min, block_min_device, cluster_labels,
                          greedy_decide, greedy_pairs_mark, greedy_tri_mark, l1_matrix, link_pairs, pair_argmin, pair_argmin_device, pair_line_offsets, pair_lines, pair_min, pair_min_device, protein_min,
-                         sim_lines, threshold_select, to_device_int8, tri_filter_count, tri_filter_fill, tri_link)
+                         rows_link, sim_lines, threshold_select, to_device_int8, tri_filter_count, tri_filter_fill, tri_link)
 
 L1_FULL_SCALE = 17000      # src/dct-sim.py:24
 HEADER = '#prot1 prot2 sim-domain sim-global'
 CLUSTER_HEADER = '#representative member'
 DOMAIN_HEADER = HEADER + ' dom1 dom2'      # --domains
+DOMAIN_CLUSTER_HEADER = CLUSTER_HEADER + ' dom1 dom2'      # --cluster --level domain
 NO_DOMAIN = '-'                            # no fingerprint pair scores above 0
 WHOLE = 'whole'                            # the whole-protein row a .dom file leaves unnamed
 
@@ -689,6 +698,119 @@ class Clusters(FilteredPairs):
             sink(memoryview(text))
 
 
+def domain_cluster_lines(sid, idx, labels, row_labels, chunk_bytes: int = 1 << 24):
+    """The text of ``--cluster --level domain`` for given labels (``labels[r]`` = the representative row of fingerprint row r, -1
+    for a row that is no node and prints nothing), as uint8 arrays of whole lines of about ``chunk_bytes`` each: one line
+    ``"{id of the representative's protein} {id of the member's protein} {label of the representative} {label of the member}\n"``
+    per node in the order of a stable sort of the nodes by label -- clusters by representative row, members by row, a
+    representative's own line first.  ``row_labels`` = one string per row (``fingerprint_labels``).  Composed from the bytes of
+    the ids and labels by index arithmetic, as ``cluster_lines``: no Python loop per line."""
+    idx = np.asarray(idx, dtype=np.int64)
+    labels = np.asarray(labels, dtype=np.int64)
+    total = int(idx[-1]) if len(idx) else 0
+    if len(labels) != total or len(row_labels) != total or len(sid) != len(idx) - 1:
+        raise ValueError('one label and one name per fingerprint row, one id per protein')
+    if total == 0:
+        return
+    if labels.min() < -1 or labels.max() >= total:
+        raise IndexError('a label outside the rows of the file')
+    nodes = np.flatnonzero(labels >= 0)
+    member = nodes[np.argsort(labels[nodes], kind='stable')]
+    rep = labels[member]
+    if len(member) == 0:
+        return
+    if (labels[rep] != rep).any():
+        raise IndexError('a representative that is no node of its own cluster')
+    owner = np.repeat(np.arange(len(idx) - 1, dtype=np.int64), np.diff(idx))
+    enc = [f'{s}'.encode('utf8') for s in sid] + [f'{s}'.encode('utf8') for s in row_labels]
+    lens = np.fromiter((len(e) for e in enc), dtype=np.int64, count=len(enc))
+    off = np.zeros(len(enc) + 1, dtype=np.int64)
+    np.cumsum(lens, out=off[1:])
+    raw = np.frombuffer(b''.join(enc) + b' \n', dtype=np.uint8)     # (the two separators sit behind the ids and the labels)
+    del enc
+    space, newline, n_ids = int(off[-1]), int(off[-1]) + 1, len(idx) - 1
+    ends = np.cumsum(lens[owner[rep]] + lens[owner[member]] + lens[n_ids + rep] + lens[n_ids + member] + 4)
+    t0, m = 0, len(member)
+    while t0 < m:
+        t1 = min(m, max(t0 + 1, int(np.searchsorted(ends, (ends[t0 - 1] if t0 else 0) + chunk_bytes, 'right'))))
+        one = np.ones(t1 - t0, dtype=np.int64)
+        fields = [owner[rep[t0:t1]], owner[member[t0:t1]], n_ids + rep[t0:t1], n_ids + member[t0:t1]]
+        starts = np.stack([v for f in fields for v in (off[f], space * one)], axis=1)
+        sizes = np.stack([v for f in fields for v in (lens[f], one)], axis=1)
+        starts[:, -1] = newline
+        yield _ragged_gather(raw, starts.ravel(), sizes.ravel())
+        t0 = t1
+
+
+class DomainClusters:
+    """Domain families of one file at a DCTdomain cut-off (``--cluster --level domain``): single-linkage clusters whose nodes
+    are the fingerprint ROWS.  Rows a < b are joined when they belong to different proteins, both are nodes and
+    min(L1(a, b), 17000) <= ``sim_bound(min_domain)`` -- ``FilteredPairs``' survival rule on row pairs instead of protein minima.
+    ``whole=False`` (``--no-whole``): the whole-protein row -- the last one -- of every protein of more than one fingerprint is no
+    node (``make_db`` appends it only when there are several domains: a single-domain protein's only row stays in).
+    ``labels()[r]`` = the smallest row of r's component, -1 for a row that is no node: a property of the graph, whatever the
+    stripes, the groups or the order in which the device ran.
+
+    The forest has one entry per row.  Stripes of at most STRIPE_ROWS rows run against the rows from the stripe's start onward,
+    those in groups of at most COL_ROWS (``rows_link``: the pairs on or left of the diagonal are left out inside the kernel); the
+    file stays on the device when it has at most COL_ROWS rows, else stripes and groups are uploaded as they come.  Nothing of
+    size rows x rows exists anywhere: the distances never leave the registers.  Then ``cluster_labels`` and one copy of one int32
+    per row.  A bound below 0 (a cut-off above 1): every node its own cluster, no launch.  There is no other shortcut: at a
+    bound of 17 000 the rows of a file's only non-empty protein still stay apart.  Joining all rows of each protein on top of
+    these components (with ``whole``) gives exactly ``Clusters(min_domain=...)``' proteins.
+
+    ``labels`` (``fingerprint_labels`` of the file; default: the 1-based indices) = what ``write`` prints for each row."""
+
+    COL_ROWS = 1 << 22      # fingerprints of a group on the device at a time (the whole file stays there if it fits)
+    STRIPE_ROWS = 1 << 20   # rows of a stripe (dctfp_rows_link takes at most 8M per call)
+
+    def __init__(self, sid, idx, fps, min_domain, whole: bool = True, labels=None):
+        self.sid, self.idx, self.fps = sid, np.asarray(idx, dtype=np.int64), fps
+        self.total = int(self.idx[-1]) if len(self.idx) else 0
+        self.row_labels = labels if labels is not None else fingerprint_labels(sid, self.idx)
+        if len(self.row_labels) != self.total:
+            raise ValueError('labels must have one entry per fingerprint row')
+        self.bound = sim_bound(min_domain)
+        self.whole = bool(whole)
+
+    def nodes(self) -> np.ndarray:
+        """bool per row: is it a node."""
+        keep = np.ones(self.total, dtype=bool)
+        if not self.whole:
+            counts = np.diff(self.idx)
+            keep[self.idx[1:][counts > 1] - 1] = False
+        return keep
+
+    def labels(self) -> np.ndarray:
+        total, keep = self.total, self.nodes()
+        if total == 0 or self.bound < 0:
+            return np.where(keep, np.arange(total), -1).astype(np.int32)
+        import torch
+        dev = torch.device('cuda', torch.cuda.current_device())
+        parent = torch.arange(total, dtype=torch.int32, device=dev)
+        owner = torch.as_tensor(np.repeat(np.arange(len(self.idx) - 1, dtype=np.int32), np.diff(self.idx)), device=dev)
+        skip = None if keep.all() else torch.as_tensor((~keep).astype(np.uint8), device=dev)
+        resident = to_device_int8(self.fps[:total]) if total <= self.COL_ROWS else None
+
+        def rows(r0, r1):
+            return resident[r0:r1] if resident is not None else to_device_int8(self.fps[r0:r1])
+
+        for s0 in range(0, total, self.STRIPE_ROWS):
+            s1 = min(total, s0 + self.STRIPE_ROWS)
+            a = rows(s0, s1)
+            for g0 in range(s0, total, self.COL_ROWS):
+                g1 = min(total, g0 + self.COL_ROWS)
+                rows_link(a, s0, a if (g0, g1) == (s0, s1) else rows(g0, g1), g0, owner, parent, self.bound, skip, cap=L1_FULL_SCALE)
+        out = cluster_labels(parent).cpu().numpy()
+        out[~keep] = -1
+        return out
+
+    def write(self, sink):
+        """Calls ``sink(memoryview)`` with the text, whole lines at a time, in order."""
+        for text in domain_cluster_lines(self.sid, self.idx, self.labels(), self.row_labels):
+            sink(memoryview(text))
+
+
 class Representatives(FilteredPairs):
     """Greedy incremental clusters of one file at cut-offs, in file order, over the graph ``Clusters`` takes the components of
     (nodes: all proteins; edges: exactly ``FilteredPairs``' pairs):
@@ -934,7 +1056,8 @@ def _reporting(fn=None, *, header: str = HEADER):
             return fn(*head, output, **kw)
         # (a report opened here for a call that asks for the domain pair carries the two extra column names)
         wide = header == HEADER and any(kw.get(k) for k in ('domains', 'dom', 'db_dom'))
-        report = Report(output, DOMAIN_HEADER if wide else header)
+        rows = header == CLUSTER_HEADER and kw.get('level') == 'domain'
+        report = Report(output, DOMAIN_HEADER if wide else DOMAIN_CLUSTER_HEADER if rows else header)
         try:
             return fn(*head, report, **kw)
         finally:
@@ -1012,19 +1135,34 @@ def all_sim(npzfile: str, report: Report, min_domain: float = None, min_global: 
 
 
 @_reporting(header=CLUSTER_HEADER)
-def cluster_sim(npzfile: str, report: Report, min_domain: float = None, min_global: float = None, linkage: str = 'single'):
+def cluster_sim(npzfile: str, report: Report, min_domain: float = None, min_global: float = None, linkage: str = 'single',
+                level: str = 'protein', whole: bool = True, dom: str = None):
     """Clusters at the cut-offs, one line ``representative member`` per protein: single linkage (``Clusters``) or, with
-    ``linkage='greedy'``, greedy incremental clusters in file order (``Representatives``)."""
+    ``linkage='greedy'``, greedy incremental clusters in file order (``Representatives``).  ``level='domain'``: the domain
+    families instead (``DomainClusters``: single linkage at ``min_domain`` alone), one line ``representative member dom1 dom2``
+    per fingerprint row -- ``whole=False`` without the whole-protein rows of multi-domain proteins, ``dom`` (the ``.dom`` of the
+    npz) names the rows by their residue ranges."""
     if min_domain is None and min_global is None:
         raise ValueError('clustering needs a cut-off: min_domain, min_global or both')
     if linkage not in LINKAGES:
         raise ValueError(f'linkage must be one of {LINKAGES}')
+    if level not in LEVELS:
+        raise ValueError(f'level must be one of {LEVELS}')
+    if level == 'domain':
+        if min_domain is None or min_global is not None or linkage != 'single':
+            raise ValueError('domain-level clusters are single-linkage clusters at min_domain alone')
+        sid, idx, fps = _load_npz(npzfile)
+        DomainClusters(sid, idx, fps, min_domain, whole=whole, labels=_labels_of(sid, idx, dom)).write(report.raw)
+        return
+    if not whole or dom is not None:
+        raise ValueError('whole and dom apply to level="domain" only')
     sid, idx, fps = _load_npz(npzfile)
     (Representatives if linkage == 'greedy' else Clusters)(sid, idx, fps, min_domain=min_domain, min_global=min_global).write(report.raw)
 
 
 RANKS = ('global', 'domain')
 LINKAGES = ('single', 'greedy')
+LEVELS = ('protein', 'domain')
 
 
 class _Parser(argparse.ArgumentParser):
@@ -1032,7 +1170,10 @@ class _Parser(argparse.ArgumentParser):
     ``--min-domain`` / ``--min-global`` cut the all-against-all output: an error beside ``--pair`` or ``--db``.
     ``--cluster`` joins the pairs that pass into clusters: an error beside ``--pair`` or ``--db``, or without a cut-off.
     ``--dom`` / ``--db-dom`` imply ``--domains``; ``--db-dom`` is an error without ``--db``, ``--domains`` beside ``--cluster``
-    (a cluster line has no scores to explain).  ``--linkage`` says how ``--cluster`` forms its clusters: an error without it."""
+    (a cluster line has no scores to explain).  ``--linkage`` says how ``--cluster`` forms its clusters: an error without it.
+    ``--level`` says what ``--cluster`` clusters: an error without it; ``--level domain`` takes ``--min-domain`` alone and single
+    linkage (an error without the one, beside ``--min-global`` or ``--linkage greedy``) and lets ``--dom`` name the rows;
+    ``--no-whole`` is an error without ``--level domain``."""
 
     def parse_known_args(self, args=None, namespace=None):
         ns, rest = super().parse_known_args(args, namespace)
@@ -1044,13 +1185,25 @@ class _Parser(argparse.ArgumentParser):
             ns.domains = True
         if getattr(ns, 'linkage', None) is not None and not getattr(ns, 'cluster', False):
             self.error('--linkage says how --cluster forms its clusters: it needs --cluster')
+        level = getattr(ns, 'level', None)
+        if level is not None and not getattr(ns, 'cluster', False):
+            self.error('--level says what --cluster clusters: it needs --cluster')
+        if getattr(ns, 'no_whole', False) and level != 'domain':
+            self.error('--no-whole leaves the whole-protein rows out of the domain families: it needs --level domain')
         if getattr(ns, 'cluster', False):
-            if getattr(ns, 'domains', False):
+            if getattr(ns, 'domains', False) and level != 'domain':
                 self.error('--domains (--dom, --db-dom) explains the scores of result lines: not with --cluster')
             if ns.pair or ns.db:
                 self.error('--cluster applies to all-against-all only, not to --pair or --db')
             if ns.min_domain is None and ns.min_global is None:
                 self.error('--cluster needs a cut-off: --min-domain, --min-global or both')
+            if level == 'domain':
+                if ns.min_domain is None:
+                    self.error('--level domain joins fingerprints by their own L1: it needs --min-domain')
+                if ns.min_global is not None:
+                    self.error('--level domain has no whole-protein score to cut: not with --min-global')
+                if getattr(ns, 'linkage', None) == 'greedy':
+                    self.error('--level domain forms single-linkage clusters: not with --linkage greedy')
         for opt in ('min_domain', 'min_global'):
             if getattr(ns, opt, None) is not None and (ns.pair or ns.db):
                 self.error(f'--{opt.replace("_", "-")} applies to all-against-all only, not to --pair or --db')
@@ -1087,6 +1240,12 @@ def build_parser() -> argparse.ArgumentParser:
                     help='--cluster: single linkage (the default: connected components, the representative is the first protein of '
                          'the component) or greedy (in file order, a protein joins the first representative it is within the cut-off '
                          'of, else it becomes one: every member is within the cut-off of its representative)')
+    ap.add_argument('--level', choices=LEVELS, default=argparse.SUPPRESS,
+                    help='--cluster: what is clustered -- the proteins (the default) or, with --min-domain, the fingerprints of '
+                         'the file (domain: the domain families; one "representative member dom1 dom2" line per fingerprint, --dom '
+                         'names them by residue ranges)')
+    ap.add_argument('--no-whole', action='store_true', default=argparse.SUPPRESS,
+                    help='--level domain: leave the whole-protein fingerprint of every multi-domain protein out')
     return ap
 
 
@@ -1094,14 +1253,17 @@ def main(argv=None):
     t_start = time.time()
     args = build_parser().parse_args(argv)
     domains, dom, db_dom = (getattr(args, k, None) for k in ('domains', 'dom', 'db_dom'))
-    report = Report(args.output, CLUSTER_HEADER if args.cluster else DOMAIN_HEADER if domains else HEADER)
+    level = getattr(args, 'level', 'protein')
+    report = Report(args.output, (DOMAIN_CLUSTER_HEADER if level == 'domain' else CLUSTER_HEADER) if args.cluster
+                    else DOMAIN_HEADER if domains else HEADER)
     t_work = time.time()
     if args.pair:
         pair_sim(args.dct, args.pair, args.pairfound, report, domains=bool(domains), dom=dom)
     elif args.db:
         db_search(args.dct, args.db, args.top, args.threshold, report, rank=args.rank or 'global', domains=bool(domains), dom=dom, db_dom=db_dom)
     elif args.cluster:
-        cluster_sim(args.dct, report, min_domain=args.min_domain, min_global=args.min_global, linkage=getattr(args, 'linkage', 'single'))
+        cluster_sim(args.dct, report, min_domain=args.min_domain, min_global=args.min_global, linkage=getattr(args, 'linkage', 'single'),
+                    level=level, whole=not getattr(args, 'no_whole', False), dom=dom if level == 'domain' else None)
     else:
         all_sim(args.dct, report, min_domain=args.min_domain, min_global=args.min_global, domains=bool(domains), dom=dom)
     report.close()

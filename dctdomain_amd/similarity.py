@@ -415,6 +415,23 @@ def link_pairs(pi: torch.Tensor, pj: torch.Tensor, parent: torch.Tensor):
         _launch(parent.device, 'dctfp_link_pairs', pi.data_ptr(), pj.data_ptr(), pi.numel(), parent.data_ptr(), n_nodes)
 
 
+def rows_link(a, a0: int, b, b0: int, owner: torch.Tensor, parent: torch.Tensor, bound: int, skip=None, cap: int = 17000):
+    """Joins, in the forest ``parent`` (one node per fingerprint row of a file), row r of ``a`` (node a0 + r) and row c of ``b``
+    (node b0 + c) wherever a0 + r < b0 + c, ``owner`` (device int32, one protein index per node) differs, neither node is flagged
+    in ``skip`` (uint8 per node, or None) and min(L1, cap) <= bound (``dctfp_rows_link``): ``l1_matrix``'s contraction with the
+    comparison in registers -- no distance is stored.  The library checks the shapes; its codes come back as ``DctfpError``."""
+    ta, tb = to_device_int8(a), to_device_int8(b)
+    _check_pair(ta, tb)
+    n_nodes = _parent_arg(parent, ta.device)
+    if owner.dtype != torch.int32 or owner.dim() != 1 or owner.numel() != n_nodes or not owner.is_contiguous() or owner.device != ta.device:
+        raise ValueError('owner must be a contiguous int32 device tensor with one entry per node of parent')
+    flags = _empty_flags(skip, n_nodes, ta.device)
+    if ta.shape[0] == 0 or tb.shape[0] == 0:
+        return
+    _launch(ta.device, 'dctfp_rows_link', ta.data_ptr(), ta.shape[0], _ld(ta), int(a0), tb.data_ptr(), tb.shape[0], _ld(tb), int(b0),
+            ta.shape[1], owner.data_ptr(), _ptr(flags), int(cap), int(bound), parent.data_ptr(), n_nodes)
+
+
 def cluster_labels(parent: torch.Tensor) -> torch.Tensor:
     """A new device int32 tensor: labels[x] = the root of x in the forest ``parent`` = the smallest member of x's component
     (``dctfp_cluster_labels``).  ``parent`` stays a forest of the same components (flattened): linking may go on."""

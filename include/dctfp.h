@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define DCTFP_VERSION 106 /* 0.1.6: dctfp_greedy_decide, dctfp_greedy_tri_mark, dctfp_greedy_pairs_mark */
+#define DCTFP_VERSION 107 /* 0.1.7: dctfp_rows_link */
 
 #define DCTFP_OK 0
 #define DCTFP_ERR_INVALID (-1) /* bad argument (null pointer, piece outside its sequence, ...) */
@@ -440,6 +440,22 @@ int dctfp_link_pairs(dctfp_ctx* ctx, const int32_t* pi, const int32_t* pj, int64
  * forest handed in is not the run time), the second reads.  `parent` is left a valid forest of the same components, so linking
  * may go on afterwards.  DCTFP_ERR_LIMIT for n_nodes >= 2^31; n_nodes of 0: nothing to do. */
 int dctfp_cluster_labels(dctfp_ctx* ctx, int32_t* parent, int64_t n_nodes, int32_t* labels, void* stream);
+
+/* Domain families (dct-sim --cluster --level domain; not in the reference): the nodes of the forest are fingerprint ROWS, and the
+ * distances are never stored.  dctfp_rows_link extends dctfp_tri_link from an int32 tile of protein-pair values to the rows
+ * themselves, with dctfp_tri_filter_count's survival rule applied to row pairs: a / b (device int8, na x d at row stride lda,
+ * nb x d at ldb; any alignment, dctfp_l1_matrix's three kernels by it) are two ranges of the file's rows, row r of a being node
+ * a0 + r and row c of b node b0 + c; owner (device int32, n_nodes) = the protein of every node, skip (device uint8, n_nodes, or
+ * NULL) = 1 for a row that is no node.  Every pair with a0 + r < b0 + c, owner[a0 + r] != owner[b0 + c], neither row skipped and
+ * min(L1(row r, row c), cap) <= bound is a union in `parent` (as in dctfp_tri_link: agent-scope atomics only, the root of a
+ * finished component is its smallest member).  Nothing else is written: the 128 x 128 sums of a workgroup are compared in
+ * registers, and a workgroup whose block lies wholly on or left of the diagonal ends before it loads anything.
+ * DCTFP_ERR_INVALID for a NULL argument (skip excepted), a negative count or offset, d < 1, lda or ldb < d, cap < 0, bound < 0,
+ * a0 + na > n_nodes or b0 + nb > n_nodes (checked on the host: the device never forms an index outside parent, owner or skip);
+ * DCTFP_ERR_LIMIT for n_nodes >= 2^31 or more than 8M rows of a per call.  na or nb of 0: nothing to do. */
+int dctfp_rows_link(dctfp_ctx* ctx, const int8_t* a, int64_t na, int64_t lda, int64_t a0, const int8_t* b, int64_t nb, int64_t ldb,
+                    int64_t b0, int32_t d, const int32_t* owner, const uint8_t* skip, int32_t cap, int32_t bound, int32_t* parent,
+                    int64_t n_nodes, void* stream);
 
 /* Greedy incremental clusters at a cut-off (dct-sim --cluster --linkage greedy; not in the reference): over the graph whose edges
  * are the pairs dctfp_tri_filter_count / dctfp_tri_filter_fill select, the proteins taken in file order -- one that no earlier

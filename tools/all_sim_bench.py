@@ -6,7 +6,13 @@
     python tools/all_sim_bench.py --part filter --n 50000 [--min-domain 0.5]  # cut-offs beside the unfiltered run, one process
     python tools/all_sim_bench.py --part cluster --n 50000 --families 500 --family-size 100 --min-domain 0.5   # --cluster beside the cut-offs
     python tools/all_sim_bench.py --part domains --n 50000 --families 500 --family-size 100 --min-domain 0.5   # --domains beside the same cut-offs
+    python tools/all_sim_bench.py --part rows_link --n 50000 --families 500 --family-size 100 --min-domain 0.5 # --cluster --level domain
 
+`rows_link` loads one synthetic file with planted families and runs, after a warm-up of both on a small file, --repeat times each:
+the domain families (DomainClusters.labels: dctfp_rows_link, no distance stored) and the materialising route over the same row
+pairs in the same process -- stripes of rows against the rows from the stripe's start onward, l1_matrix into int32 tiles of at
+most 1 GiB and tri_link over them (no owner exclusion there: the same contraction, other edges).  Events around rows_link and around
+l1_matrix give both kernels' rates in row pairs per second and the share of the one in the other.
 `filter` loads one synthetic file and runs, after the load and a warm-up on a small file, the unfiltered path (AllPairs, to
 /dev/null as `scale` does) and the path with cut-offs; events around the device steps of the second (the tile: protein_min or
 l1_matrix; the filter; pair_min; the lines) say where its device time goes.  --planted fingerprints are overwritten with near
@@ -329,6 +335,103 @@ def part_cluster(args):
             'link_over_tile': round(ms.get('link', 0.0) / ms['tile'], 4) if ms.get('tile') else None, **res_greedy}
 
 
+def _live_pairs(a0: int, na: int, b0: int, nb: int) -> int:
+    """Row pairs in the 128 x 128 blocks dctfp_rows_link contracts: those not wholly on or left of the diagonal."""
+    r_first = a0 + 128 * np.arange((na + 127) // 128, dtype=np.int64)
+    c_last = b0 + np.minimum(nb, 128 * (np.arange((nb + 127) // 128, dtype=np.int64) + 1)) - 1
+    return int((c_last[None, :] > r_first[:, None]).sum()) * 128 * 128
+
+
+def part_rows_link(args):
+    """One process: DomainClusters.labels and the materialising route (l1_matrix into 1 GiB tiles + tri_link) on the same loaded
+    file, --repeat times each after a warm-up of both on a small one; device time of rows_link and of l1_matrix by events."""
+    import torch
+    from dctdomain_amd import dct_sim, similarity
+    min_domain = args.min_domain if args.min_domain is not None else 0.5
+    with tempfile.TemporaryDirectory(dir=args.dir) as tmp:
+        small, path = os.path.join(tmp, 'w-dct.npz'), os.path.join(tmp, 'f-dct.npz')
+        synth(small, 2000, 5)
+        synth(path, args.n, 7)
+        wsid, widx, wfps = dct_sim._load_npz(small)
+        sid, idx, fps = dct_sim._load_npz(path)
+    widx, wfps = plant_families(widx, wfps, 10, 10)
+    if args.families:
+        idx, fps = plant_families(idx, fps, args.families, args.family_size)
+    bound = dct_sim.sim_bound(min_domain)
+    tile_ints = dct_sim.FilteredPairs.TILE_INTS
+    spans, pairs = {}, {}
+
+    def timed(module, name, count):
+        fn = getattr(module, name)
+
+        def run(*a, **k):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            out = fn(*a, **k)
+            e1.record()
+            spans.setdefault(name, []).append((e0, e1))
+            pairs[name] = pairs.get(name, 0) + count(*a)
+            return out
+        setattr(module, name, run)
+        return fn
+
+    def materialised(rows_dev):
+        """Stripes x the rows from the stripe's start onward: l1_matrix into a tile, tri_link over it."""
+        total = rows_dev.shape[0]
+        parent = torch.arange(total, dtype=torch.int32, device=rows_dev.device)
+        s0 = 0
+        while s0 < total:
+            s1 = min(total, s0 + max(1, tile_ints // (total - s0)))
+            tile = similarity.l1_matrix(rows_dev[s0:s1], rows_dev[s0:])
+            similarity.tri_link(tile, s0, s0, bound, parent)
+            del tile
+            s0 = s1
+        return similarity.cluster_labels(parent).cpu().numpy()
+
+    dct_sim.DomainClusters(wsid, widx, wfps, min_domain).labels()
+    materialised(similarity.to_device_int8(wfps))
+    torch.cuda.synchronize()
+    real = [(dct_sim, 'rows_link', timed(dct_sim, 'rows_link', lambda a, a0, b, b0, *_: _live_pairs(a0, a.shape[0], b0, b.shape[0]))),
+            (similarity, 'l1_matrix', timed(similarity, 'l1_matrix', lambda a, b, *_: a.shape[0] * b.shape[0]))]
+    t_fused, t_mat, ms_fused, ms_l1 = [], [], [], []
+    for _ in range(args.repeat):
+        spans.clear()
+        pairs.clear()
+        dc = dct_sim.DomainClusters(sid, idx, fps, min_domain)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        labels = dc.labels()
+        torch.cuda.synchronize()
+        t_fused.append(time.perf_counter() - t0)
+        ms_fused.append(sum(a.elapsed_time(b) for a, b in spans['rows_link']))
+        fused_pairs = pairs['rows_link']
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        rows_dev = similarity.to_device_int8(fps[:int(idx[-1])])          # (the upload is inside both times)
+        mat_labels = materialised(rows_dev)
+        torch.cuda.synchronize()
+        t_mat.append(time.perf_counter() - t0)
+        ms_l1.append(sum(a.elapsed_time(b) for a, b in spans['l1_matrix']))
+        l1_pairs = pairs['l1_matrix']
+        del rows_dev
+    for module, name, fn in real:
+        setattr(module, name, fn)
+    med = lambda v: sorted(v)[len(v) // 2]   # noqa: E731
+    rate_fused, rate_l1 = fused_pairs / (1e-3 * med(ms_fused)), l1_pairs / (1e-3 * med(ms_l1))
+    nodes = labels >= 0
+    return {'part': 'rows_link', 'n': len(sid), 'fingerprints': int(idx[-1]), 'families': args.families, 'family_size': args.family_size,
+            'min_domain': min_domain, 'bound': bound, 'clusters': int(len(np.unique(labels[nodes]))), 'largest': int(np.bincount(labels[nodes]).max()),
+            'clusters_without_owner_exclusion': int(len(np.unique(mat_labels))),
+            'fused_s': [round(t, 3) for t in t_fused], 'materialised_s': [round(t, 3) for t in t_mat],
+            'fused_median_s': round(med(t_fused), 3), 'materialised_median_s': round(med(t_mat), 3),
+            'fused_spread_s': round(max(t_fused) - min(t_fused), 3), 'materialised_spread_s': round(max(t_mat) - min(t_mat), 3),
+            'fused_not_slower_beyond_spread': med(t_fused) <= med(t_mat) + (max(t_fused) - min(t_fused)) + (max(t_mat) - min(t_mat)),
+            'rows_link_ms': [round(v, 3) for v in ms_fused], 'l1_matrix_ms': [round(v, 3) for v in ms_l1],
+            'rows_link_pairs': fused_pairs, 'l1_matrix_pairs': l1_pairs,
+            'rows_link_pairs_per_s': round(rate_fused, 1), 'l1_matrix_pairs_per_s': round(rate_l1, 1),
+            'rows_link_share_of_l1_matrix_rate': round(rate_fused / rate_l1, 4)}
+
+
 def part_domains(args):
     """One process: FilteredPairs to /dev/null without and with the domain pair on the same loaded file, --repeat times each after
     a warm-up of both on a small one; device time of the second by step."""
@@ -453,7 +556,7 @@ def part_scale(args):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument('--part', required=True, choices=['compare', 'scale', 'filter', 'cluster', 'domains', 'run', 'base'])
+    ap.add_argument('--part', required=True, choices=['compare', 'scale', 'filter', 'cluster', 'domains', 'rows_link', 'run', 'base'])
     ap.add_argument('--n', type=int, default=2000)
     ap.add_argument('--dir', default=None, help='where the npz and the text file go (local disk)')
     ap.add_argument('--npz')
@@ -467,7 +570,7 @@ def main():
     ap.add_argument('--min-global', type=float, default=None, help='scale / filter: print the pairs whose DCTglobal is not below this')
     ap.add_argument('--out')
     args = ap.parse_args()
-    res = {'compare': part_compare, 'scale': part_scale, 'filter': part_filter, 'cluster': part_cluster, 'domains': part_domains, 'run': part_run, 'base': part_base}[args.part](args)
+    res = {'compare': part_compare, 'scale': part_scale, 'filter': part_filter, 'cluster': part_cluster, 'domains': part_domains, 'rows_link': part_rows_link, 'run': part_run, 'base': part_base}[args.part](args)
     line = json.dumps(res)
     print(line)
     if args.out:
