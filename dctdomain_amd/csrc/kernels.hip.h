@@ -1751,6 +1751,28 @@ __global__ void fill_zero_kernel(const JobB* __restrict__ jobs, int64_t n_jobs, 
 //       coef[c][k] = s_k * (k ? fs[k][c] : fs[0][c])
 //   G2: y_j = sum_{k>=1} cos(pi k (2j+1)/(2 num)) fs[k][c], min-max scaled over j.
 // ---------------------------------------------------------------------------
+// One sum of the generic kernels: s + c carries twice the working precision (Ogita, Rump, Oishi: Dot2 -- the rounding of
+// every product, taken back with an fma, and of every addition go into c).  The first-row shift leaves -x[0][c] in every
+// term of G1: its cosine sum cancels in the end, but the partial sums pass |x0| N / (pi k), and a plain running sum of
+// 2 000 terms kept their rounding -- ten times the scipy reference's error in the low coefficients of a long matrix.
+struct Sum2 {
+    double s = 0.0, c = 0.0;
+    __device__ inline void add(double p) {
+#pragma clang fp contract(off)
+        const double t = s + p;
+        const double z = t - s;
+        c += (s - (t - z)) + (p - z);
+        s = t;
+    }
+    __device__ inline void add_product(double a, double b) {
+#pragma clang fp contract(off)
+        const double p = a * b;
+        c += fma(a, b, -p);
+        add(p);
+    }
+    __device__ inline double value() const { return s + c; }
+};
+
 template <typename T>
 __global__ void generic_forward_kernel(const T* __restrict__ x, int64_t n_rows, int64_t n_cols, int64_t ld, int num,
                                        double* __restrict__ fs, double* __restrict__ coef) {
@@ -1758,13 +1780,14 @@ __global__ void generic_forward_kernel(const T* __restrict__ x, int64_t n_rows, 
     const int k = blockIdx.y;
     if (c >= n_cols) return;
     const double x0 = (double)x[c];
-    double s = 0.0;
+    Sum2 acc;
     if (k == 0) {
-        for (int64_t t = 0; t < n_rows; ++t) s += (double)x[t * ld + c];
+        for (int64_t t = 0; t < n_rows; ++t) acc.add((double)x[t * ld + c]);
     } else {
         for (int64_t t = 0; t < n_rows; ++t)
-            s = fma(cospi_ratio((uint64_t)k * (2 * (uint64_t)t + 1), 2 * (uint64_t)n_rows), (double)x[t * ld + c] - x0, s);
+            acc.add_product(cospi_ratio((uint64_t)k * (2 * (uint64_t)t + 1), 2 * (uint64_t)n_rows), (double)x[t * ld + c] - x0);
     }
+    const double s = acc.value();
     fs[(size_t)k * n_cols + c] = s;
     if (coef) coef[(size_t)c * num + k] = s * (k == 0 ? sqrt(1.0 / (double)n_rows) : sqrt(2.0 / (double)n_rows));
 }
@@ -1777,9 +1800,10 @@ __global__ void generic_inverse_kernel(const double* __restrict__ fs, int64_t n_
     double mn = INFINITY, mx = -INFINITY;
     bool bad = false;
     for (int j = 0; j < num; ++j) {
-        double s = 0.0;
+        Sum2 acc;
         for (int k = 1; k < num; ++k)
-            s = fma(cospi_ratio((uint64_t)k * (2 * (uint64_t)j + 1), 2 * (uint64_t)num), fs[(size_t)k * n_cols + c], s);
+            acc.add_product(cospi_ratio((uint64_t)k * (2 * (uint64_t)j + 1), 2 * (uint64_t)num), fs[(size_t)k * n_cols + c]);
+        const double s = acc.value();
         scaled[(size_t)j * n_cols + c] = s;
         bad |= (s != s);
         mn = fmin(mn, s);
