@@ -63,7 +63,7 @@ EXPORTS = ('dctfp_version', 'dctfp_last_error', 'dctfp_create', 'dctfp_destroy',
            'dctfp_tri_link', 'dctfp_link_pairs', 'dctfp_cluster_labels',
            'dctfp_pair_argmin', 'dctfp_pair_domain_lines',
            'dctfp_greedy_decide', 'dctfp_greedy_tri_mark', 'dctfp_greedy_pairs_mark',
-           'dctfp_rows_link')
+           'dctfp_rows_link', 'dctfp_rows_assign')
 
 
 def load(path: str = None):
@@ -197,6 +197,8 @@ def _configure(lib):
         lib.dctfp_cluster_labels.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
         lib.dctfp_rows_link.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int32,
                                         C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]
+        lib.dctfp_rows_assign.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p,
+                                          C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]
         lib.dctfp_greedy_decide.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.c_void_p,
                                             C.c_void_p]
         lib.dctfp_greedy_tri_mark.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_void_p,

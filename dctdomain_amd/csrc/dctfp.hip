@@ -2885,6 +2885,23 @@ int dctfp_rows_link(dctfp_ctx* ctx, const int8_t* a, int64_t na, int64_t lda, in
     return DCTFP_OK;
 } DCTFP_GUARD("dctfp_rows_link")
 
+int dctfp_rows_assign(dctfp_ctx* ctx, const int8_t* a, int64_t na, int64_t lda, const int32_t* value_a, int64_t a0, const int8_t* b, int64_t nb,
+                      int64_t ldb, const int32_t* slot_b, int64_t b0, int32_t d, int32_t cap, int32_t bound, int32_t* assign, int64_t n_assign,
+                      void* stream_v) try {
+    if (!ctx || !a || !b || !assign) return fail(DCTFP_ERR_INVALID, "dctfp_rows_assign: NULL argument");
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    if (na < 0 || nb < 0 || d < 1 || lda < d || ldb < d || a0 < 0 || b0 < 0 || cap < 0 || bound < 0 || n_assign < 0)
+        return fail(DCTFP_ERR_INVALID, "dctfp_rows_assign: bad shape or bound");
+    if (n_assign > 0x7fffffff) return fail(DCTFP_ERR_LIMIT, "dctfp_rows_assign: more than 2^31 - 1 entries of assign");
+    if (na == 0 || nb == 0 || n_assign == 0) return DCTFP_OK;
+    if ((na + 127) / 128 > 65535) return fail(DCTFP_ERR_LIMIT, "dctfp_rows_assign: more than 8M rows of a per call");
+    HIP_TRY(hipSetDevice(ctx->device));
+    // (slots and values are bounded on the device: the host cannot see value_a and slot_b)
+    launch_rows_assign(a, na, lda, value_a, a0, b, nb, ldb, slot_b, b0, d, cap, bound, assign, n_assign, (hipStream_t)stream_v);
+    HIP_TRY(hipGetLastError());
+    return DCTFP_OK;
+} DCTFP_GUARD("dctfp_rows_assign")
+
 int dctfp_greedy_decide(dctfp_ctx* ctx, int32_t* assign, int32_t* state, const int32_t* blocked, int64_t n_nodes, int64_t i0, int64_t i1,
                         int32_t round, int64_t* undecided, void* stream_v) try {
     if (!ctx || !assign || !state || !blocked || !undecided) return fail(DCTFP_ERR_INVALID, "dctfp_greedy_decide: NULL argument");

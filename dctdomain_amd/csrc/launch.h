@@ -181,6 +181,12 @@ void launch_cluster_labels(int32_t* parent, int64_t n_nodes, int32_t* labels, hi
 void launch_rows_link(const int8_t* a, int64_t na, int64_t lda, int64_t a0, const int8_t* b, int64_t nb, int64_t ldb, int64_t b0, int d,
                       const int32_t* owner, const uint8_t* skip, int32_t cap, int32_t bound, int32_t* parent, hipStream_t stream);
 
+// (dctfp_rows_assign, k_assign.hip: the same contraction over a full rectangle -- every pair of rows within the bound lowers
+// assign[slot of the b row] to the value of the a row with an atomic minimum; value_a / slot_b NULL: a0 + r / b0 + c)
+void launch_rows_assign(const int8_t* a, int64_t na, int64_t lda, const int32_t* value_a, int64_t a0, const int8_t* b, int64_t nb, int64_t ldb,
+                        const int32_t* slot_b, int64_t b0, int d, int32_t cap, int32_t bound, int32_t* assign, int64_t n_assign,
+                        hipStream_t stream);
+
 // greedy incremental clusters at a cut-off (k_greedy.hip): rounds over a range of nodes [i0, i1) -- decide (one thread per node;
 // *undecided grows by the nodes left undecided), then mark from a tile's rows / from a list of pairs (new representatives lower
 // assign at their surviving entries, undecided rows stamp blocked inside the range with the next round's number)

@@ -5,6 +5,8 @@ fingerprints (``-dct.npz``), with the L1 distances computed on the GPU.
                                     [--pairfound F] [--top 5] [--threshold 0.25] [--min-domain X] [--min-global Y]
                                     [--cluster [--linkage {single,greedy}] [--level {protein,domain} [--no-whole]]] [--domains]
                                     [--dom X.dom] [--db-dom Y.dom]
+    python -m dctdomain_amd.dct_sim --dct NEW-dct.npz --assign REPS-dct.npz --min-domain X [--min-global Y] [--reps-out ALL-dct.npz]
+                                    [--output F]
 
 Same flags, same output text (src/dct-sim.py:179-211); ``--rank domain`` (not in the reference) orders database hits by
 DCTdomain instead of DCTglobal, and ``--min-domain`` / ``--min-global`` (not in the reference either, which ignores
@@ -29,6 +31,14 @@ Where the reference loops over protein pairs and, inside, over domain pairs in P
   every other one goes to the lowest representative it has an edge to -- so every member is within the cut-off of its
   representative and no two representatives are within it of each other, decided on the device in rounds over the same tiles
   (``dctfp_greedy_decide`` / ``dctfp_greedy_tri_mark`` / ``dctfp_greedy_pairs_mark``);
+- ``--assign REPS`` (``Assignment``, not in the reference) goes on from such a run when proteins are added: every protein of
+  ``REPS`` is a fixed representative, the proteins of ``--dct`` are taken in file order by the same rule.  The hot step compares
+  every fingerprint of the representatives with every fingerprint of the new proteins and keeps, per new protein, the lowest
+  representative within the cut-off (``dctfp_rows_assign``: ``dctfp_rows_link``'s contraction over the full rectangle, an atomic
+  minimum instead of a union -- no distance is stored); the proteins left uncovered are clustered among themselves by
+  ``Representatives``.  ``--reps-out`` writes the representatives as a ``-dct.npz`` (also with ``--cluster --linkage greedy``,
+  which starts the chain): greedy on the first k proteins, then ``--assign`` of the rest, ends on the representatives of one
+  greedy run over the whole file;
 - ``--cluster --level domain`` (``DomainClusters``) clusters the fingerprint ROWS of the file instead of its proteins -- the
   domain families: two rows of different proteins are joined when their own L1 passes ``--min-domain``, where the protein level
   joins two proteins as soon as any one of their fingerprint pairs does.  One kernel (``dctfp_rows_link``) takes a stripe of
@@ -60,9 +70,9 @@ import time
 
 import numpy as np
 
-from .similarity import (PROTEIN_MIN_MAX_D, GreedyState, LineIds, TextStream, _utf8_binary, block_min, block_min_device, cluster_labels,
+from .similarity import (GREEDY_NONE, PROTEIN_MIN_MAX_D, GreedyState, LineIds, TextStream, _utf8_binary, block_min, block_min_device, cluster_labels,
                          greedy_decide, greedy_pairs_mark, greedy_tri_mark, l1_matrix, link_pairs, pair_argmin, pair_argmin_device, pair_line_offsets, pair_lines, pair_min, pair_min_device, protein_min,
-                         rows_link, sim_lines, threshold_select, to_device_int8, tri_filter_count, tri_filter_fill, tri_link)
+                         rows_assign, rows_link, sim_lines, threshold_select, to_device_int8, tri_filter_count, tri_filter_fill, tri_link)
 
 L1_FULL_SCALE = 17000      # src/dct-sim.py:24
 HEADER = '#prot1 prot2 sim-domain sim-global'
@@ -635,14 +645,21 @@ def cluster_lines(sid, labels, chunk_bytes: int = 1 << 24):
     if labels.min() < 0 or labels.max() >= n:
         raise IndexError('a label outside the proteins of the file')
     member = np.argsort(labels, kind='stable')
-    rep = labels[member]
+    yield from _id_lines(sid, labels[member], member, chunk_bytes)
+
+
+def _id_lines(sid, rep, member, chunk_bytes: int):
+    """``cluster_lines``' text for given lines: line t is ``"{sid[rep[t]]} {sid[member[t]]}\n"``."""
+    n = len(member)
+    if n == 0:
+        return
     wide = _ascii_id_rows(sid)
     if wide is not None:
         yield from _ascii_lines(*wide, rep, member, chunk_bytes)
         return
     enc = [f'{s}'.encode('utf8') for s in sid]
-    lens = np.fromiter((len(e) for e in enc), dtype=np.int64, count=n)
-    off = np.zeros(n + 1, dtype=np.int64)
+    lens = np.fromiter((len(e) for e in enc), dtype=np.int64, count=len(enc))
+    off = np.zeros(len(enc) + 1, dtype=np.int64)
     np.cumsum(lens, out=off[1:])
     raw = np.frombuffer(b''.join(enc) + b' \n', dtype=np.uint8)   # (the two separators sit behind the ids)
     del enc
@@ -882,6 +899,215 @@ class Representatives(FilteredPairs):
         """Calls ``sink(memoryview)`` with the text, whole lines at a time, in order."""
         for text in cluster_lines(self.sid, self.labels()):
             sink(memoryview(text))
+
+
+def _all_ids(rep_sid, sid):
+    """The ids of the nodes of an assignment: the representatives' file, then the new one."""
+    if isinstance(rep_sid, np.ndarray) and isinstance(sid, np.ndarray) and rep_sid.dtype.kind == sid.dtype.kind == 'U':
+        return np.concatenate([rep_sid, sid])
+    return [f'{s}' for s in rep_sid] + [f'{s}' for s in sid]
+
+
+def assign_lines(rep_sid, sid, labels, chunk_bytes: int = 1 << 24):
+    """The text of ``--assign`` for given labels (``Assignment.labels()``: one per protein of ``sid``, in the numbering
+    0 .. m - 1 for ``rep_sid`` and m .. m + n - 1 for ``sid``): one line ``"{id of representative} {id of member}\n"`` per protein
+    of ``sid`` and none for those of ``rep_sid``, in the order of a stable sort by label -- the clusters of the old representatives
+    first, in their order, then the new representatives' clusters, each representative's own line first.  Composed as
+    ``cluster_lines`` composes its text: no Python loop per line."""
+    labels = np.asarray(labels, dtype=np.int64)
+    m, n = len(rep_sid), len(sid)
+    if len(labels) != n:
+        raise ValueError('one label per new protein')
+    if n == 0:
+        return
+    if labels.min() < 0 or labels.max() >= m + n:
+        raise IndexError('a label outside the proteins of the two files')
+    order = np.argsort(labels, kind='stable')
+    yield from _id_lines(_all_ids(rep_sid, sid), labels[order], m + order, chunk_bytes)
+
+
+class Assignment:
+    """New proteins placed on an existing set of representatives (``--assign``): greedy incremental clustering that starts from
+    a file ``R`` of m fixed representatives and goes through a file ``N`` of n new proteins.  Nodes are numbered 0 .. m - 1 for
+    ``R`` and m .. m + n - 1 for ``N``, each file in its own order.  An edge joins a node of R u N to a LATER node of N exactly
+    when ``FilteredPairs`` would keep that protein pair -- min(L1, 17000) <= ``sim_bound(cut-off)`` on the protein minimum for
+    DCTdomain, on the last-row pair for DCTglobal, on both when both cut-offs are given.  There are no edges inside R: every
+    protein of R is a representative, whatever its distance to the others.  Then ``Representatives``' rule over N in file order:
+
+        a protein of N with an edge from a representative (of R, or an earlier new one) belongs to the lowest such node;
+        otherwise it becomes a representative itself.
+
+    So for any file F and split point k, with R = the greedy representatives among the first k proteins and N = the rest, the
+    proteins of N get exactly the labels ``Representatives(F)`` gives them.  ``labels()`` = n int32 in the numbering above.
+
+    The cover pass fills ``assign`` (m + n int32 on the device, ``GREEDY_NONE`` at the start) with the lowest node of R within the
+    cut-offs of every new protein:
+    - one cut-off excludes anything: ``rows_assign`` per (group of at most COL_ROWS representative rows, stripe of at most
+      STRIPE_ROWS new rows) -- DCTdomain on all fingerprint rows with their proteins' nodes, DCTglobal on the last rows of the
+      proteins that have fingerprints.  No distance is stored;
+    - both do: per stripe of representatives the DCTglobal tile of the last rows (``l1_matrix``, at most TILE_INTS entries),
+      ``tri_filter_count`` / ``tri_filter_fill`` with col0 = m (the whole rectangle lies right of the diagonal), ``pair_min_device``
+      on the survivors, the DCTdomain bound, and an ``amin`` scatter of what is left.
+    Nothing of size m x n exists anywhere.  The proteins of N still uncovered are then clustered among themselves by
+    ``Representatives``, unchanged: covered proteins are members and influence nobody, so leaving them out is exact.
+
+    A protein without fingerprints has no L1 against anything: in N it becomes its own representative, in R it covers nobody.
+    A bound below 0 (a cut-off above 1): every new protein its own representative, no launch.  Bounds that exclude nothing (every
+    given cut-off <= 0 or NaN): ``FilteredPairs`` keeps every pair, so every new protein belongs to node 0, as in ``Clusters`` and
+    ``Representatives``."""
+
+    COL_ROWS = 1 << 22      # representative rows on the device at a time (they all stay there if they fit)
+    STRIPE_ROWS = 1 << 20   # new rows per call of rows_assign
+    TILE_INTS = 1 << 28     # int32 entries of one DCTglobal tile (both cut-offs)
+
+    def __init__(self, rep_sid, rep_idx, rep_fps, sid, idx, fps, min_domain=None, min_global=None):
+        self.rep_sid, self.rep_idx, self.rep_fps = rep_sid, np.asarray(rep_idx, dtype=np.int64), rep_fps
+        self.sid, self.idx, self.fps = sid, np.asarray(idx, dtype=np.int64), fps
+        if min_domain is None and min_global is None:
+            raise ValueError('an assignment needs a cut-off: min_domain, min_global or both')
+        self.min_domain, self.min_global = min_domain, min_global
+        self.bound_domain = L1_FULL_SCALE if min_domain is None else sim_bound(min_domain)
+        self.bound_global = L1_FULL_SCALE if min_global is None else sim_bound(min_global)
+        self.m, self.n = max(len(self.rep_idx) - 1, 0), max(len(self.idx) - 1, 0)
+        if self.m and self.n and int(self.rep_idx[-1]) and int(self.idx[-1]) and rep_fps.shape[1] != fps.shape[1]:
+            raise ValueError('the fingerprints of the two files differ in width')
+        self.calls = 0          # rows_assign calls / tiles of the last labels()
+
+    def _route_rows(self, fps, idx, node0: int):
+        """(rows, node of every row) one file hands to ``rows_assign``: all rows on the DCTdomain route, the last rows of the
+        proteins that have fingerprints on the DCTglobal route."""
+        counts = np.diff(idx)
+        if self.bound_global < L1_FULL_SCALE:
+            has = np.flatnonzero(counts > 0)
+            return fps[idx[1:][has] - 1], (node0 + has).astype(np.int32)
+        return fps[:int(idx[-1])], (node0 + np.repeat(np.arange(len(counts), dtype=np.int64), counts)).astype(np.int32)
+
+    def _cover_rows(self, assign):
+        """One cut-off excludes anything: ``rows_assign`` per (group, stripe)."""
+        import torch
+        a, va = self._route_rows(self.rep_fps, self.rep_idx, 0)
+        b, sb = self._route_rows(self.fps, self.idx, self.m)
+        if len(a) == 0 or len(b) == 0:
+            return
+        bound = min(self.bound_domain, self.bound_global)
+        dev = assign.device
+        resident = to_device_int8(a) if len(a) <= self.COL_ROWS else None
+        va_dev = torch.as_tensor(va, device=dev)
+        for s0 in range(0, len(b), self.STRIPE_ROWS):
+            s1 = min(len(b), s0 + self.STRIPE_ROWS)
+            stripe, slots = to_device_int8(b[s0:s1]), torch.as_tensor(sb[s0:s1], device=dev)
+            for g0 in range(0, len(a), self.COL_ROWS):
+                g1 = min(len(a), g0 + self.COL_ROWS)
+                group = resident[g0:g1] if resident is not None else to_device_int8(a[g0:g1])
+                rows_assign(group, stripe, assign, bound, va_dev[g0:g1], slots, cap=L1_FULL_SCALE)
+                self.calls += 1
+
+    def _cover_pairs(self, assign):
+        """Both cut-offs exclude something: DCTglobal tiles, the survivors' DCTdomain, an ``amin`` scatter."""
+        import torch
+        m, n, dev = self.m, self.n, assign.device
+        if int(self.rep_idx[-1]) == 0 or int(self.idx[-1]) == 0:
+            return
+        last_a, empty_a = _last_rows(self.rep_fps[:int(self.rep_idx[-1])], self.rep_idx)
+        last_b, empty_b = _last_rows(self.fps[:int(self.idx[-1])], self.idx)
+        rows_a = _DeviceRows(self.rep_fps, self.rep_idx, self.COL_ROWS)
+        rows_b = _DeviceRows(self.fps, self.idx, self.COL_ROWS)
+        for q0, q1 in _protein_groups(self.idx, self.COL_ROWS):            # new proteins: their fingerprints fit on the device
+            if self.idx[q1] == self.idx[q0]:
+                continue
+            b, idx_b = rows_b(q0, q1), torch.as_tensor(self.idx[q0:q1 + 1] - self.idx[q0], device=dev)
+            lb, eb = to_device_int8(last_b[q0:q1]), torch.as_tensor(empty_b[q0:q1], device=dev)
+            per = max(1, self.TILE_INTS // (q1 - q0))
+            p0 = 0
+            while p0 < m:                                                   # stripes of representatives: the tile and their rows fit
+                by_rows = int(np.searchsorted(self.rep_idx, self.rep_idx[p0] + self.COL_ROWS, 'right')) - 1
+                p1 = min(m, max(p0 + 1, min(p0 + per, by_rows)))
+                if self.rep_idx[p1] > self.rep_idx[p0]:
+                    tile = l1_matrix(to_device_int8(last_a[p0:p1]), lb)
+                    ea = torch.as_tensor(empty_a[p0:p1], device=dev)
+                    count = tri_filter_count(tile, p0, m + q0, self.bound_global, ea, eb)
+                    total = int(count.sum())
+                    self.calls += 1
+                    if total:
+                        pi, pj = tri_filter_fill(tile, p0, m + q0, self.bound_global, count, total, ea, eb)
+                        idx_a = torch.as_tensor(self.rep_idx[p0:p1 + 1] - self.rep_idx[p0], device=dev)
+                        pairs = torch.stack([pi - p0, pj - (m + q0)], dim=1).contiguous()
+                        mn, _ = pair_min_device(rows_a(p0, p1), idx_a, b, idx_b, pairs)
+                        keep = mn.clamp(max=L1_FULL_SCALE) <= self.bound_domain
+                        assign.scatter_reduce_(0, pj[keep].long(), pi[keep], 'amin')
+                    del tile
+                p0 = p1
+
+    def labels(self) -> np.ndarray:
+        m, n = self.m, self.n
+        self.calls = 0
+        lo, hi = min(self.bound_domain, self.bound_global), max(self.bound_domain, self.bound_global)
+        if n <= 0 or lo < 0:
+            return (m + np.arange(max(n, 0))).astype(np.int32)
+        if lo >= L1_FULL_SCALE:                                             # (every pair is kept: node 0 has an edge to every new protein)
+            return np.zeros(n, dtype=np.int32)
+        out = np.full(n, GREEDY_NONE, dtype=np.int32)
+        if m:
+            import torch
+            assign = torch.full((m + n,), GREEDY_NONE, dtype=torch.int32, device=torch.device('cuda', torch.cuda.current_device()))
+            if hi < L1_FULL_SCALE:
+                self._cover_pairs(assign)
+            else:
+                self._cover_rows(assign)
+            out = assign[m:].cpu().numpy()
+        rest = np.flatnonzero(out == GREEDY_NONE)                           # the uncovered: clustered among themselves, in file order
+        bare = np.diff(self.idx)[rest] == 0                                 # (no fingerprints, no edges: their own representatives)
+        out[rest[bare]] = m + rest[bare]
+        rest = rest[~bare]
+        if len(rest):
+            rows, sub_idx = _compact(self.fps, self.idx, rest)
+            sub_sid = np.asarray(self.sid)[rest] if isinstance(self.sid, np.ndarray) else [self.sid[k] for k in rest.tolist()]
+            sub = Representatives(sub_sid, sub_idx, rows, min_domain=self.min_domain, min_global=self.min_global).labels()
+            out[rest] = m + rest[sub]
+        return out.astype(np.int32)
+
+    def write(self, sink, labels=None):
+        """Calls ``sink(memoryview)`` with the text, whole lines at a time, in order."""
+        for text in assign_lines(self.rep_sid, self.sid, self.labels() if labels is None else labels):
+            sink(memoryview(text))
+
+
+def _npz_dom(filename: str, rows: int):
+    """The ``dom`` array of a ``-dct.npz`` (one name per fingerprint row), or None for a file that carries none."""
+    with np.load(filename) as data:
+        if 'dom' not in data.files:
+            return None
+        dom = np.asarray(data['dom'])
+    if dom.ndim != 1 or len(dom) != rows:
+        raise ValueError(f'{filename}: dom holds {dom.shape} names for {rows} fingerprint rows')
+    return dom
+
+
+def write_reps(path: str, parts):
+    """``--reps-out``: a ``-dct.npz`` (``sid``, ``idx``, ``dct``; ``dom`` too when every part has one) of the chosen proteins of
+    each part in turn, with their fingerprint rows.  ``parts`` = [(sid, idx, fps, dom or None, protein indices or None for all)].
+    ``_load_npz`` reads it back; written to ``path`` exactly (no suffix is added)."""
+    sids, counts, rows, doms = [], [], [], []
+    width = 0
+    for sid, idx, fps, dom, proteins in parts:
+        idx = np.asarray(idx, dtype=np.int64)
+        proteins = np.arange(len(idx) - 1) if proteins is None else np.asarray(proteins, dtype=np.int64)
+        lens = idx[proteins + 1] - idx[proteins]
+        take = np.repeat(idx[proteins] - (np.cumsum(lens) - lens), lens) + np.arange(int(lens.sum()), dtype=np.int64)
+        sids.append(np.asarray(sid, dtype=str)[proteins] if len(proteins) else np.zeros(0, dtype='<U1'))
+        counts.append(lens)
+        rows.append(np.asarray(fps)[take] if len(take) else None)
+        doms.append(None if dom is None else np.asarray(dom, dtype=str)[take])
+        width = max(width, np.asarray(fps).shape[1] if np.asarray(fps).ndim == 2 else 0)
+    rows = [r for r in rows if r is not None]
+    out = {'sid': np.concatenate(sids) if sids else np.zeros(0, dtype='<U1'),
+           'idx': np.concatenate([[0], np.cumsum(np.concatenate(counts))]).astype(np.int64) if counts else np.zeros(1, dtype=np.int64)}
+    if all(d is not None for d in doms) and doms:
+        out['dom'] = np.concatenate(doms) if sum(len(d) for d in doms) else np.zeros(0, dtype='<U1')
+    out['dct'] = np.concatenate(rows).astype(np.int8) if rows else np.zeros((0, width), dtype=np.int8)
+    with open(path, 'wb') as fh:
+        np.savez(fh, **out)
+    print(f'representatives saved to {path} ({len(out["sid"])} proteins)')
 
 
 def _add_hits(parts, t0: int, p0: int, off, key, col):
@@ -1136,14 +1362,17 @@ def all_sim(npzfile: str, report: Report, min_domain: float = None, min_global: 
 
 @_reporting(header=CLUSTER_HEADER)
 def cluster_sim(npzfile: str, report: Report, min_domain: float = None, min_global: float = None, linkage: str = 'single',
-                level: str = 'protein', whole: bool = True, dom: str = None):
+                level: str = 'protein', whole: bool = True, dom: str = None, reps_out: str = None):
     """Clusters at the cut-offs, one line ``representative member`` per protein: single linkage (``Clusters``) or, with
     ``linkage='greedy'``, greedy incremental clusters in file order (``Representatives``).  ``level='domain'``: the domain
     families instead (``DomainClusters``: single linkage at ``min_domain`` alone), one line ``representative member dom1 dom2``
     per fingerprint row -- ``whole=False`` without the whole-protein rows of multi-domain proteins, ``dom`` (the ``.dom`` of the
-    npz) names the rows by their residue ranges."""
+    npz) names the rows by their residue ranges.  ``reps_out`` (greedy linkage at protein level only): the representatives as a
+    ``-dct.npz`` of their own (``write_reps``), which ``assign_sim`` takes as its fixed set."""
     if min_domain is None and min_global is None:
         raise ValueError('clustering needs a cut-off: min_domain, min_global or both')
+    if reps_out is not None and (linkage != 'greedy' or level != 'protein'):
+        raise ValueError('reps_out writes the representatives of greedy clusters at protein level')
     if linkage not in LINKAGES:
         raise ValueError(f'linkage must be one of {LINKAGES}')
     if level not in LEVELS:
@@ -1157,7 +1386,31 @@ def cluster_sim(npzfile: str, report: Report, min_domain: float = None, min_glob
     if not whole or dom is not None:
         raise ValueError('whole and dom apply to level="domain" only')
     sid, idx, fps = _load_npz(npzfile)
-    (Representatives if linkage == 'greedy' else Clusters)(sid, idx, fps, min_domain=min_domain, min_global=min_global).write(report.raw)
+    if reps_out is None:
+        (Representatives if linkage == 'greedy' else Clusters)(sid, idx, fps, min_domain=min_domain, min_global=min_global).write(report.raw)
+        return
+    labels = Representatives(sid, idx, fps, min_domain=min_domain, min_global=min_global).labels()
+    for text in cluster_lines(sid, labels):
+        report.raw(memoryview(text))
+    write_reps(reps_out, [(sid, idx, fps, _npz_dom(npzfile, int(idx[-1])), np.flatnonzero(labels == np.arange(len(labels))))])
+
+
+@_reporting(header=CLUSTER_HEADER)
+def assign_sim(npzfile: str, repfile: str, report: Report, min_domain: float = None, min_global: float = None, reps_out: str = None):
+    """Places the proteins of ``npzfile`` on the representatives of ``repfile`` at the cut-offs (``Assignment``): one line
+    ``representative member`` per protein of ``npzfile``.  ``reps_out``: all proteins of ``repfile`` followed by the new
+    representatives, as a ``-dct.npz`` (``write_reps``) -- the fixed set of the next assignment."""
+    if min_domain is None and min_global is None:
+        raise ValueError('an assignment needs a cut-off: min_domain, min_global or both')
+    rep_sid, rep_idx, rep_fps = _load_npz(repfile)
+    sid, idx, fps = _load_npz(npzfile)
+    job = Assignment(rep_sid, rep_idx, rep_fps, sid, idx, fps, min_domain=min_domain, min_global=min_global)
+    labels = job.labels()
+    job.write(report.raw, labels)
+    if reps_out is not None:
+        m = len(rep_idx) - 1
+        write_reps(reps_out, [(rep_sid, rep_idx, rep_fps, _npz_dom(repfile, int(rep_idx[-1])), None),
+                              (sid, idx, fps, _npz_dom(npzfile, int(idx[-1])), np.flatnonzero(labels == m + np.arange(len(labels))))])
 
 
 RANKS = ('global', 'domain')
@@ -1173,10 +1426,26 @@ class _Parser(argparse.ArgumentParser):
     (a cluster line has no scores to explain).  ``--linkage`` says how ``--cluster`` forms its clusters: an error without it.
     ``--level`` says what ``--cluster`` clusters: an error without it; ``--level domain`` takes ``--min-domain`` alone and single
     linkage (an error without the one, beside ``--min-global`` or ``--linkage greedy``) and lets ``--dom`` name the rows;
-    ``--no-whole`` is an error without ``--level domain``."""
+    ``--no-whole`` is an error without ``--level domain``.  ``--assign`` places the proteins of ``--dct`` on the representatives of
+    another file: it needs a cut-off and is an error beside ``--pair``, ``--db``, ``--cluster``, ``--rank``, ``--domains`` /
+    ``--dom`` / ``--db-dom``, ``--linkage``, ``--level`` and ``--no-whole``.  ``--reps-out`` is an error unless ``--assign`` is
+    given, or ``--cluster --linkage greedy`` without ``--level domain``."""
 
     def parse_known_args(self, args=None, namespace=None):
         ns, rest = super().parse_known_args(args, namespace)
+        if getattr(ns, 'assign', None) is not None:
+            beside = [flag for flag, given in (('--pair', ns.pair), ('--db', ns.db), ('--cluster', getattr(ns, 'cluster', False)),
+                                               ('--rank', getattr(ns, 'rank', None) is not None), ('--domains', getattr(ns, 'domains', False)),
+                                               ('--dom', getattr(ns, 'dom', None) is not None), ('--db-dom', getattr(ns, 'db_dom', None) is not None),
+                                               ('--linkage', getattr(ns, 'linkage', None) is not None), ('--level', getattr(ns, 'level', None) is not None),
+                                               ('--no-whole', getattr(ns, 'no_whole', False))) if given]
+            if beside:
+                self.error(f'--assign places the proteins of --dct on a fixed set of representatives: not with {beside[0]}')
+            if ns.min_domain is None and ns.min_global is None:
+                self.error('--assign needs a cut-off: --min-domain, --min-global or both')
+        elif getattr(ns, 'reps_out', None) is not None and not (getattr(ns, 'cluster', False) and getattr(ns, 'linkage', None) == 'greedy'
+                                                                and getattr(ns, 'level', None) != 'domain'):
+            self.error('--reps-out writes representatives: it needs --assign, or --cluster --linkage greedy at protein level')
         if getattr(ns, 'rank', None) is not None and (ns.pair or not ns.db):
             self.error('--rank applies to database search (--db) only, not to --pair or all-against-all')
         if getattr(ns, 'db_dom', None) is not None and not ns.db:
@@ -1246,6 +1515,13 @@ def build_parser() -> argparse.ArgumentParser:
                          'names them by residue ranges)')
     ap.add_argument('--no-whole', action='store_true', default=argparse.SUPPRESS,
                     help='--level domain: leave the whole-protein fingerprint of every multi-domain protein out')
+    ap.add_argument('--assign', metavar='REPS', default=argparse.SUPPRESS,
+                    help='with a cut-off: place the proteins of --dct on the representatives in this -dct.npz (all of its proteins are '
+                         'representatives) -- one "representative member" line per protein of --dct; a protein within the cut-off of no '
+                         'representative becomes a new one, in file order')
+    ap.add_argument('--reps-out', metavar='FILE', default=argparse.SUPPRESS,
+                    help='--assign: write the proteins of REPS followed by the new representatives as a -dct.npz; --cluster --linkage '
+                         'greedy: write that run\'s representatives (the REPS of a later --assign)')
     return ap
 
 
@@ -1254,16 +1530,20 @@ def main(argv=None):
     args = build_parser().parse_args(argv)
     domains, dom, db_dom = (getattr(args, k, None) for k in ('domains', 'dom', 'db_dom'))
     level = getattr(args, 'level', 'protein')
-    report = Report(args.output, (DOMAIN_CLUSTER_HEADER if level == 'domain' else CLUSTER_HEADER) if args.cluster
+    assign, reps_out = getattr(args, 'assign', None), getattr(args, 'reps_out', None)
+    report = Report(args.output, (DOMAIN_CLUSTER_HEADER if level == 'domain' else CLUSTER_HEADER) if args.cluster or assign is not None
                     else DOMAIN_HEADER if domains else HEADER)
     t_work = time.time()
-    if args.pair:
+    if assign is not None:
+        assign_sim(args.dct, assign, report, min_domain=args.min_domain, min_global=args.min_global, reps_out=reps_out)
+    elif args.pair:
         pair_sim(args.dct, args.pair, args.pairfound, report, domains=bool(domains), dom=dom)
     elif args.db:
         db_search(args.dct, args.db, args.top, args.threshold, report, rank=args.rank or 'global', domains=bool(domains), dom=dom, db_dom=db_dom)
     elif args.cluster:
         cluster_sim(args.dct, report, min_domain=args.min_domain, min_global=args.min_global, linkage=getattr(args, 'linkage', 'single'),
-                    level=level, whole=not getattr(args, 'no_whole', False), dom=dom if level == 'domain' else None)
+                    level=level, whole=not getattr(args, 'no_whole', False), dom=dom if level == 'domain' else None,
+                    **({'reps_out': reps_out} if reps_out is not None else {}))
     else:
         all_sim(args.dct, report, min_domain=args.min_domain, min_global=args.min_global, domains=bool(domains), dom=dom)
     report.close()

@@ -432,6 +432,40 @@ def rows_link(a, a0: int, b, b0: int, owner: torch.Tensor, parent: torch.Tensor,
             ta.shape[1], owner.data_ptr(), _ptr(flags), int(cap), int(bound), parent.data_ptr(), n_nodes)
 
 
+def _rows_view(t) -> torch.Tensor:
+    """``to_device_int8`` that leaves a device int8 view with unit column stride as it is (any row stride, any alignment)."""
+    if isinstance(t, torch.Tensor) and t.dtype == torch.int8 and t.device.type == 'cuda' and t.dim() == 2 and (t.shape[1] <= 1 or t.stride(1) == 1) \
+            and (t.shape[0] <= 1 or t.stride(0) >= t.shape[1]):
+        return t
+    return to_device_int8(t)
+
+
+def _row_map(m, n: int, device, what: str):
+    if m is None:
+        return None
+    if not isinstance(m, torch.Tensor) or m.dtype != torch.int32 or m.dim() != 1 or m.numel() != n or not m.is_contiguous() or m.device != device:
+        raise ValueError(f'{what} must be a contiguous int32 device tensor with one entry per row')
+    return m
+
+
+def rows_assign(a, b, assign: torch.Tensor, bound: int, value_a=None, slot_b=None, a0: int = 0, b0: int = 0, cap: int = 17000):
+    """Lowers ``assign[slot]`` (device int32, started as ``GREEDY_NONE``) to ``value`` for every row r of ``a`` and row c of ``b``
+    with min(L1, cap) <= bound, where value = ``value_a[r]`` (device int32 per row; None: a0 + r) and slot = ``slot_b[c]`` (None:
+    b0 + c) (``dctfp_rows_assign``): ``l1_matrix``'s contraction over the full rectangle with the comparison in registers -- no
+    distance is stored.  ``a`` / ``b`` may be views with any row stride and alignment.  The kernel skips a slot outside ``assign``
+    and a negative value; the library checks the shapes, its codes come back as ``DctfpError``."""
+    ta, tb = _rows_view(a), _rows_view(b)
+    _check_pair(ta, tb)
+    if assign.dtype != torch.int32 or assign.dim() != 1 or not assign.is_contiguous() or assign.device != ta.device:
+        raise ValueError('assign must be a contiguous 1-D int32 tensor on the device of the rows')
+    va = _row_map(value_a, ta.shape[0], ta.device, 'value_a')
+    sb = _row_map(slot_b, tb.shape[0], ta.device, 'slot_b')
+    if ta.shape[0] == 0 or tb.shape[0] == 0 or assign.numel() == 0:
+        return
+    _launch(ta.device, 'dctfp_rows_assign', ta.data_ptr(), ta.shape[0], _ld(ta), _ptr(va), int(a0), tb.data_ptr(), tb.shape[0], _ld(tb), _ptr(sb),
+            int(b0), ta.shape[1], int(cap), int(bound), assign.data_ptr(), assign.numel())
+
+
 def cluster_labels(parent: torch.Tensor) -> torch.Tensor:
     """A new device int32 tensor: labels[x] = the root of x in the forest ``parent`` = the smallest member of x's component
     (``dctfp_cluster_labels``).  ``parent`` stays a forest of the same components (flattened): linking may go on."""

@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define DCTFP_VERSION 107 /* 0.1.7: dctfp_rows_link */
+#define DCTFP_VERSION 108 /* 0.1.8: dctfp_rows_assign */
 
 #define DCTFP_OK 0
 #define DCTFP_ERR_INVALID (-1) /* bad argument (null pointer, piece outside its sequence, ...) */
@@ -493,6 +493,24 @@ int dctfp_greedy_tri_mark(dctfp_ctx* ctx, const int32_t* tile, int64_t n_rows, i
  * for n_nodes >= 2^31 or more than 2^31 pairs per call; n_pairs or n_nodes of 0: nothing to do. */
 int dctfp_greedy_pairs_mark(dctfp_ctx* ctx, const int32_t* pi, const int32_t* pj, int64_t n_pairs, int32_t* assign, const int32_t* state,
                             int32_t* blocked, int64_t n_nodes, int64_t range_end, int32_t next_round, void* stream);
+
+/* Assignment to existing representatives (dct-sim --assign; not in the reference): the cover pass of greedy clustering between
+ * two files, with the distances never stored.  dctfp_rows_assign is to dctfp_greedy_tri_mark what dctfp_rows_link is to
+ * dctfp_tri_link: dctfp_tri_filter_count's survival rule applied to the row pairs of a FULL rectangle -- no diagonal, no owner.
+ * a / b (device int8, na x d at row stride lda, nb x d at ldb; any alignment, dctfp_l1_matrix's three kernels by it) are the
+ * representatives' rows and the new proteins' rows.  For every row r of a and row c of b with min(L1(row r, row c), cap) <= bound:
+ *     assign[slot] = min(assign[slot], value),  value = value_a ? value_a[r] : a0 + r,  slot = slot_b ? slot_b[c] : b0 + c
+ * value_a / slot_b (device int32, one entry per row of a / b, or NULL) map rows to the caller's nodes; assign (device int32,
+ * n_assign entries) starts as 0x7fffffff.  Inside the launch assign is touched by agent-scope relaxed atomics only (a load that
+ * skips a minimum which would change nothing, then the minimum); the 128 x 128 sums of a workgroup are compared in registers
+ * and nothing else is written.  The result is a minimum over a set the inputs alone fix: it does not depend on the order in
+ * which the device ran or on how the caller splits the rows into calls.  A slot outside [0, n_assign) or a negative value is
+ * skipped on the device (the host cannot see the two arrays).
+ * DCTFP_ERR_INVALID for a NULL ctx, a, b or assign, a negative count or offset, d < 1, lda or ldb < d, cap < 0 or bound < 0;
+ * DCTFP_ERR_LIMIT for n_assign >= 2^31 or more than 8M rows of a per call.  na, nb or n_assign of 0: nothing to do. */
+int dctfp_rows_assign(dctfp_ctx* ctx, const int8_t* a, int64_t na, int64_t lda, const int32_t* value_a, int64_t a0, const int8_t* b,
+                      int64_t nb, int64_t ldb, const int32_t* slot_b, int64_t b0, int32_t d, int32_t cap, int32_t bound, int32_t* assign,
+                      int64_t n_assign, void* stream);
 
 /* query_db's search (src/query_db.py:75-87: a flat FAISS index forced to METRIC_L1 at :76, index.search at :87) without a
  * distance matrix: for query rows q (nq x d, row stride ldq) and database rows b (nb x d, stride ldb), int8 on the device, each
