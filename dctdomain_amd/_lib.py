@@ -63,7 +63,7 @@ EXPORTS = ('dctfp_version', 'dctfp_last_error', 'dctfp_create', 'dctfp_destroy',
            'dctfp_tri_link', 'dctfp_link_pairs', 'dctfp_cluster_labels',
            'dctfp_pair_argmin', 'dctfp_pair_domain_lines',
            'dctfp_greedy_decide', 'dctfp_greedy_tri_mark', 'dctfp_greedy_pairs_mark',
-           'dctfp_rows_link', 'dctfp_rows_assign')
+           'dctfp_rows_link', 'dctfp_rows_assign', 'dctfp_tri_nearest', 'dctfp_tree_hook')
 
 
 def load(path: str = None):
@@ -199,6 +199,10 @@ def _configure(lib):
                                         C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]
         lib.dctfp_rows_assign.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p,
                                           C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]
+        lib.dctfp_tri_nearest.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_void_p,
+                                          C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
+        lib.dctfp_tree_hook.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                        C.c_void_p, C.c_int64, C.c_void_p]
         lib.dctfp_greedy_decide.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.c_void_p,
                                             C.c_void_p]
         lib.dctfp_greedy_tri_mark.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_void_p,

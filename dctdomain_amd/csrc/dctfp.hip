@@ -2902,6 +2902,39 @@ int dctfp_rows_assign(dctfp_ctx* ctx, const int8_t* a, int64_t na, int64_t lda, 
     return DCTFP_OK;
 } DCTFP_GUARD("dctfp_rows_assign")
 
+int dctfp_tri_nearest(dctfp_ctx* ctx, const int32_t* tile, int64_t n_rows, int64_t n_cols, int64_t ld, int64_t row0, int64_t col0,
+                      const uint8_t* row_empty, const uint8_t* col_empty, int32_t cap, int32_t bound, const int32_t* comp, uint64_t* best,
+                      int64_t n_nodes, void* stream_v) try {
+    // (the packed edge: 15 bits of key, 24 bits for each end -- said first: it holds whatever the other arguments are)
+    if (n_nodes > (int64_t)1 << 24 || cap > 0x7fff) return fail(DCTFP_ERR_LIMIT, "dctfp_tri_nearest: more than 2^24 nodes or a cap above 32767");
+    if (!ctx || !tile || !comp || !best) return fail(DCTFP_ERR_INVALID, "dctfp_tri_nearest: NULL argument");
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    if (n_rows < 0 || n_cols < 0 || ld < n_cols || row0 < 0 || col0 < 0 || cap < 0 || bound < -1 || bound > cap || n_nodes < 0 ||
+        (reinterpret_cast<uintptr_t>(tile) & 3u) != 0 || (reinterpret_cast<uintptr_t>(best) & 7u) != 0)
+        return fail(DCTFP_ERR_INVALID, "dctfp_tri_nearest: bad shape, bound or alignment");
+    // (every (i, j) the kernel can form lies inside the tile: bounded here, not on the device)
+    if (row0 + n_rows > n_nodes || col0 + n_cols > n_nodes) return fail(DCTFP_ERR_INVALID, "dctfp_tri_nearest: the tile names proteins outside the nodes");
+    if (n_rows == 0 || n_cols == 0 || n_nodes == 0) return DCTFP_OK;
+    HIP_TRY(hipSetDevice(ctx->device));
+    launch_tri_nearest(tile, n_rows, n_cols, ld, row0, col0, row_empty, col_empty, cap, bound, comp, best, n_nodes, (hipStream_t)stream_v);
+    HIP_TRY(hipGetLastError());
+    return DCTFP_OK;
+} DCTFP_GUARD("dctfp_tri_nearest")
+
+int dctfp_tree_hook(dctfp_ctx* ctx, const int32_t* comp, uint64_t* best, int32_t* parent, int64_t n_nodes, int32_t* edge_i, int32_t* edge_j,
+                    int32_t* edge_key, int32_t* counter, int64_t max_edges, void* stream_v) try {
+    if (n_nodes > (int64_t)1 << 24) return fail(DCTFP_ERR_LIMIT, "dctfp_tree_hook: more than 2^24 nodes");
+    if (!ctx || !comp || !best || !parent || !counter || ((!edge_i || !edge_j || !edge_key) && max_edges > 0))
+        return fail(DCTFP_ERR_INVALID, "dctfp_tree_hook: NULL argument");
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    if (n_nodes < 0 || max_edges < 0 || (reinterpret_cast<uintptr_t>(best) & 7u) != 0) return fail(DCTFP_ERR_INVALID, "dctfp_tree_hook: bad shape or alignment");
+    if (n_nodes == 0) return DCTFP_OK;
+    HIP_TRY(hipSetDevice(ctx->device));
+    HIP_TRY(launch_tree_hook(comp, best, parent, n_nodes, edge_i, edge_j, edge_key, counter, max_edges, (hipStream_t)stream_v));
+    HIP_TRY(hipGetLastError());
+    return DCTFP_OK;
+} DCTFP_GUARD("dctfp_tree_hook")
+
 int dctfp_greedy_decide(dctfp_ctx* ctx, int32_t* assign, int32_t* state, const int32_t* blocked, int64_t n_nodes, int64_t i0, int64_t i1,
                         int32_t round, int64_t* undecided, void* stream_v) try {
     if (!ctx || !assign || !state || !blocked || !undecided) return fail(DCTFP_ERR_INVALID, "dctfp_greedy_decide: NULL argument");

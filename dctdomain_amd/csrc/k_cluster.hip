@@ -67,6 +67,10 @@ __device__ inline void uf_union(int32_t* parent, int32_t a, int32_t b) {
     }
 }
 
+#ifdef DCTFP_UNION_FIND_ONLY   // k_tree.hip: the forest's routines above and none of the kernels below
+}  // namespace
+#else
+
 // tri_filter_count_kernel's walk (one workgroup per row at a time, 16-byte loads, filter_quad).  Row r is protein i = row0 + r:
 // a step without survivors -- the common case -- costs what the count's step costs, the ballots show it and the wave moves on;
 // in a step with some, one lane finds i's root (once per step, carried to the next as the place to start from) and only the
@@ -312,3 +316,5 @@ void launch_cluster_labels(int32_t* parent, int64_t n_nodes, int32_t* labels, hi
 }
 
 }  // namespace dctfp_host
+
+#endif  // DCTFP_UNION_FIND_ONLY

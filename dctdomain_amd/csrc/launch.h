@@ -181,6 +181,16 @@ void launch_cluster_labels(int32_t* parent, int64_t n_nodes, int32_t* labels, hi
 void launch_rows_link(const int8_t* a, int64_t na, int64_t lda, int64_t a0, const int8_t* b, int64_t nb, int64_t ldb, int64_t b0, int d,
                       const int32_t* owner, const uint8_t* skip, int32_t cap, int32_t bound, int32_t* parent, hipStream_t stream);
 
+// the single-linkage tree (k_tree.hip): a round of Boruvka's algorithm over the tiles -- tri_link's walk, every surviving entry whose
+// ends carry different labels in comp lowers best (packed key << 48 | i << 24 | j) of both labels -- then, once per round, the hook:
+// every label appends its best edge at *counter (nothing at or beyond max_edges), joins its ends in parent, and best is refilled
+// with "none" behind it on the stream
+void launch_tri_nearest(const int32_t* tile, int64_t n_rows, int64_t n_cols, int64_t ld, int64_t row0, int64_t col0, const uint8_t* row_empty,
+                        const uint8_t* col_empty, int32_t cap, int32_t bound, const int32_t* comp, uint64_t* best, int64_t n_nodes,
+                        hipStream_t stream);
+hipError_t launch_tree_hook(const int32_t* comp, uint64_t* best, int32_t* parent, int64_t n_nodes, int32_t* edge_i, int32_t* edge_j,
+                            int32_t* edge_key, int32_t* counter, int64_t max_edges, hipStream_t stream);
+
 // (dctfp_rows_assign, k_assign.hip: the same contraction over a full rectangle -- every pair of rows within the bound lowers
 // assign[slot of the b row] to the value of the a row with an atomic minimum; value_a / slot_b NULL: a0 + r / b0 + c)
 void launch_rows_assign(const int8_t* a, int64_t na, int64_t lda, const int32_t* value_a, int64_t a0, const int8_t* b, int64_t nb, int64_t ldb,

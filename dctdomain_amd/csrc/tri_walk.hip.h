@@ -1,5 +1,5 @@
 // The walk over a row of an int32 L1 tile that the kernels of the all-against-all cut-offs share (k_filter.hip: count and fill;
-// k_cluster.hip: link): one workgroup per row at a time, 1024 columns per step, one 16-byte load per thread, and the rule that
+// k_cluster.hip: link; k_greedy.hip: mark; k_tree.hip: nearest): one workgroup per row at a time, 1024 columns per step, one 16-byte load per thread, and the rule that
 // says which of a thread's four entries survive.
 #pragma once
 
@@ -16,9 +16,11 @@ constexpr int kFilterStep = kFilterThreads * 4;   // columns per step: one 16-by
 // The four entries a thread looks at in one step and which of them survive.  `v` counts columns from the 16-byte boundary at
 // or below the row's first entry (`shift` = entries between the two), so that v % 4 == 0 is a 16-byte aligned address: a quad
 // inside the row is one 16-byte load, the quads at the row's ends are read entry by entry.  Entry c survives when
-// c_min <= c < n_cols and min(L1, cap) <= bound, an empty protein on either side having key cap.
+// c_min <= c < n_cols and min(L1, cap) <= bound, an empty protein on either side having key cap.  `key` is that min(L1, cap), for
+// the kernels that rank the survivors (k_tree.hip); the others never read it and it costs them nothing.
 struct Quad {
     bool keep[4];
+    int32_t key[4];
 };
 
 __device__ inline Quad filter_quad(const int32_t* __restrict__ row, int64_t v, int shift, int64_t c_min, int64_t n_cols, bool row_is_empty,
@@ -45,6 +47,7 @@ __device__ inline Quad filter_quad(const int32_t* __restrict__ row, int64_t v, i
         const bool full = row_is_empty || x[e] >= (uint32_t)cap || (inside && col_empty && col_empty[c]);
         const int32_t key = full ? cap : (int32_t)x[e];
         q.keep[e] = inside && key <= bound;
+        q.key[e] = key;
     }
     return q;
 }

@@ -7,6 +7,7 @@ fingerprints (``-dct.npz``), with the L1 distances computed on the GPU.
                                     [--dom X.dom] [--db-dom Y.dom]
     python -m dctdomain_amd.dct_sim --dct NEW-dct.npz --assign REPS-dct.npz --min-domain X [--min-global Y] [--reps-out ALL-dct.npz]
                                     [--output F]
+    python -m dctdomain_amd.dct_sim --dct X-dct.npz --tree [domain|global] [--min-domain X | --min-global Y] [--output F]
 
 Same flags, same output text (src/dct-sim.py:179-211); ``--rank domain`` (not in the reference) orders database hits by
 DCTdomain instead of DCTglobal, and ``--min-domain`` / ``--min-global`` (not in the reference either, which ignores
@@ -39,6 +40,12 @@ Where the reference loops over protein pairs and, inside, over domain pairs in P
   ``Representatives``.  ``--reps-out`` writes the representatives as a ``-dct.npz`` (also with ``--cluster --linkage greedy``,
   which starts the chain): greedy on the first k proteins, then ``--assign`` of the rest, ends on the representatives of one
   greedy run over the whole file;
+- ``--tree`` (``Tree``, not in the reference) answers ``--cluster`` for every cut-off at once: the single-linkage tree of the file,
+  the minimum spanning forest of the pairs of similarity above 0 (or not below a cut-off) under the strict order (L1, i, j),
+  printed as the all-against-all's own lines for its n - 1 pairs, most similar first -- the merge order of single linkage.  Cut at
+  any score, its lines give the clusters ``--cluster`` finds there.  Boruvka's algorithm in at most ceil(log2 n) + 1 rounds over
+  the same tiles: per component the lightest edge that leaves it (``dctfp_tri_nearest``), then one hook per component in the same
+  union-find (``dctfp_tree_hook``) and the new labels (``dctfp_cluster_labels``);
 - ``--cluster --level domain`` (``DomainClusters``) clusters the fingerprint ROWS of the file instead of its proteins -- the
   domain families: two rows of different proteins are joined when their own L1 passes ``--min-domain``, where the protein level
   joins two proteins as soon as any one of their fingerprint pairs does.  One kernel (``dctfp_rows_link``) takes a stripe of
@@ -72,7 +79,8 @@ import numpy as np
 
 from .similarity import (GREEDY_NONE, PROTEIN_MIN_MAX_D, GreedyState, LineIds, TextStream, _utf8_binary, block_min, block_min_device, cluster_labels,
                          greedy_decide, greedy_pairs_mark, greedy_tri_mark, l1_matrix, link_pairs, pair_argmin, pair_argmin_device, pair_line_offsets, pair_lines, pair_min, pair_min_device, protein_min,
-                         rows_assign, rows_link, sim_lines, threshold_select, to_device_int8, tri_filter_count, tri_filter_fill, tri_link)
+                         rows_assign, rows_link, sim_lines, threshold_select, to_device_int8, tri_filter_count, tri_filter_fill, tri_link,
+                         TREE_MAX_NODES, TreeState, tree_hook, tri_nearest)
 
 L1_FULL_SCALE = 17000      # src/dct-sim.py:24
 HEADER = '#prot1 prot2 sim-domain sim-global'
@@ -713,6 +721,131 @@ class Clusters(FilteredPairs):
         """Calls ``sink(memoryview)`` with the text, whole lines at a time, in order."""
         for text in cluster_lines(self.sid, self.labels()):
             sink(memoryview(text))
+
+
+SCORES = ('domain', 'global')
+
+
+class Tree(FilteredPairs):
+    """The single-linkage tree of one file: the minimum spanning forest of the graph whose nodes are all proteins and whose edges
+    are the pairs i < j with key = min(L1, 17000) <= bound, under the strict order (key, i, j) -- unique, because no two edges
+    compare equal.  L1 is DCTdomain's (``score='domain'``: ``protein_min``) or DCTglobal's (``'global'``: ``l1_matrix`` of the last
+    rows, the proteins without fingerprints flagged as on ``FilteredPairs``' global route); bound = 16999, every pair of similarity
+    above 0, unless ``min_cut`` gives ``sim_bound(min_cut)``.  Cut at any bound b <= its own, the tree's edges with key <= b have
+    the components ``Clusters`` finds at b: one pass answers every cut-off (``labels``).
+
+    Boruvka's algorithm over ``FilteredPairs.tiles``, in rounds of
+
+    1. ``tri_nearest`` on every stripe's tile: per component the lightest edge that leaves it (both ends of every entry count);
+    2. ``tree_hook``: every component appends its edge and joins the two ends in the union-find forest;
+    3. ``cluster_labels``: the labels of the next round.
+
+    A round at least halves the components that can still grow, so there are at most ceil(log2 n) + 1 of them; the loop stops when
+    one appends nothing (one int32 comes back per round) or the tree is complete, and raises beyond that number rather than go
+    on.  When the triangle fits one stripe (TILE_INTS) its tile is computed once and kept; else the tiles are computed anew in
+    every round: the cost is rounds x one ``Clusters`` pass.  ``rounds`` = the rounds of the last build.
+
+    ``edges()`` = (i, j, key) in (key, i, j) order: the merge order of single linkage, most similar first.  ``write`` prints them
+    as the very lines the all-against-all prints for those pairs ((min, last) from ``pair_min_device``, text from ``pair_lines``):
+    n - c lines for a forest of c components."""
+
+    def __init__(self, sid, idx, fps, score: str = 'domain', min_cut=None):
+        if score not in SCORES:
+            raise ValueError(f'score must be one of {SCORES}')
+        super().__init__(sid, idx, fps)
+        bound = L1_FULL_SCALE - 1 if min_cut is None else sim_bound(min_cut)
+        self.score = self.route = score                         # (the tile of that score whatever the bound)
+        if score == 'domain':
+            self.bound_domain = bound
+        else:
+            self.bound_global = bound
+        self.rounds = 0
+        self._edges = None
+
+    def edges(self):
+        """(i, j, key): int64 numpy arrays of the tree's edges in (key, i, j) order (built once)."""
+        if self._edges is None:
+            i, j, key = self._build()
+            order = np.lexsort((j, i, key))
+            self._edges = i[order], j[order], key[order]
+        return self._edges
+
+    def _build(self):
+        n = len(self.idx) - 1
+        self.rounds = 0
+        if n < 2 or self.bound < 0:
+            return tuple(np.zeros(0, dtype=np.int64) for _ in range(3))
+        if n > TREE_MAX_NODES:
+            raise ValueError(f'the tree takes at most {TREE_MAX_NODES} proteins')
+        ts = TreeState(n)
+        rows = self.device_rows() if self.route == 'domain' else None
+        kept = None
+        if len(list(self.stripes())) == 1:                      # the whole triangle in one tile: computed once
+            kept = [(i0, tile, flags) for i0, _, tile, flags in self.tiles(rows)]
+        most = max(1, int(n - 1).bit_length()) + 1              # ceil(log2 n) + 1
+        done = 0
+        while done < n - 1:
+            if self.rounds >= most:
+                raise RuntimeError(f'the tree of {n} proteins is not finished after {most} rounds')
+            for i0, tile, flags in (kept if kept is not None else ((i0, tile, flags) for i0, _, tile, flags in self.tiles(rows))):
+                tri_nearest(tile, i0, i0 + 1, self.bound, ts, *flags)
+                del tile
+            tree_hook(ts)
+            self.rounds += 1
+            total = int(ts.counter.item())
+            if total == done:
+                break
+            done = total
+            ts.comp = cluster_labels(ts.parent)
+        return ts.edges()
+
+    def labels(self, cut: float) -> np.ndarray:
+        """The single-linkage clusters at the cut-off ``cut`` from the tree as it is built (no further pass over the pairs):
+        ``Clusters(min_domain=cut).labels()`` -- ``min_global`` for ``score='global'`` -- for every cut whose bound is not above the
+        tree's own.  ``link_pairs`` on the edges with key <= ``sim_bound(cut)``, then ``cluster_labels``."""
+        n = len(self.idx) - 1
+        bound = sim_bound(cut)
+        if bound > self.bound:
+            raise ValueError(f'the tree was built with bound {self.bound}: it does not hold the clusters at {cut} (bound {bound})')
+        i, j, key = self.edges()
+        keep = key <= bound
+        if n < 1 or not keep.any():
+            return np.arange(max(n, 0), dtype=np.int32)
+        import torch
+        dev = torch.device('cuda', torch.cuda.current_device())
+        parent = torch.arange(n, dtype=torch.int32, device=dev)
+        link_pairs(torch.as_tensor(i[keep].astype(np.int32), device=dev), torch.as_tensor(j[keep].astype(np.int32), device=dev), parent)
+        return cluster_labels(parent).cpu().numpy()
+
+    def write(self, sink):
+        """Calls ``sink(memoryview)`` with the text of the edges, ranges of at most TEXT_BYTES at a time, in order."""
+        i, j, _ = self.edges()
+        if not len(i):
+            return
+        import torch
+        dev = torch.device('cuda', torch.cuda.current_device())
+        ids = LineIds([f'{s}' for s in self.sid])
+        table = torch.as_tensor(score_table(), device=dev)
+        resident = self.resident_rows()
+        idx_dev = torch.as_tensor(self.idx, device=dev) if resident is not None else None
+        ends = np.cumsum(ids.lens[i] + ids.lens[j] + 14)
+        out = TextStream(sink, room=lambda nbytes: max(nbytes, 1 << 16))
+        k0 = 0
+        while k0 < len(i):
+            k1 = min(len(i), max(k0 + 1, int(np.searchsorted(ends, (ends[k0 - 1] if k0 else 0) + self.TEXT_BYTES, 'right'))))
+            pairs = np.stack([i[k0:k1], j[k0:k1]], axis=1)
+            pi, pj = (torch.as_tensor(np.ascontiguousarray(pairs[:, c]).astype(np.int32), device=dev) for c in (0, 1))
+            if resident is not None:
+                mn, last = pair_min_device(resident, idx_dev, resident, idx_dev, torch.stack([pi, pj], dim=1).contiguous())
+            else:
+                mn, last = (torch.as_tensor(v.astype(np.int32), device=dev) for v in pair_scores(self.fps, self.idx, pairs, self.COL_ROWS))
+            off = pair_line_offsets(pi, pj, ids)
+            nbytes = int(off[-1])
+            text = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+            pair_lines(pi, pj, mn, last, ids, table, off, text)
+            out.hand_over(text, nbytes)
+            k0 = k1
+        out.close()
 
 
 def domain_cluster_lines(sid, idx, labels, row_labels, chunk_bytes: int = 1 << 24):
@@ -1413,6 +1546,19 @@ def assign_sim(npzfile: str, repfile: str, report: Report, min_domain: float = N
                               (sid, idx, fps, _npz_dom(npzfile, int(idx[-1])), np.flatnonzero(labels == m + np.arange(len(labels))))])
 
 
+@_reporting
+def tree_sim(npzfile: str, report: Report, score: str = 'domain', min_domain: float = None, min_global: float = None):
+    """The single-linkage tree of the file (``Tree``) on DCTdomain (``score='domain'``) or DCTglobal (``'global'``): one all-against-all
+    line per edge, most similar first.  ``min_domain`` / ``min_global``: the cut-off of that score below which no edge is taken
+    (the forest then has a tree per cluster at that cut-off); the other score's cut-off is an error."""
+    if score not in SCORES:
+        raise ValueError(f'score must be one of {SCORES}')
+    if (min_global if score == 'domain' else min_domain) is not None:
+        raise ValueError('the tree orders the pairs by one score: only that score\'s cut-off applies')
+    sid, idx, fps = _load_npz(npzfile)
+    Tree(sid, idx, fps, score=score, min_cut=min_domain if score == 'domain' else min_global).write(report.raw)
+
+
 RANKS = ('global', 'domain')
 LINKAGES = ('single', 'greedy')
 LEVELS = ('protein', 'domain')
@@ -1429,10 +1575,27 @@ class _Parser(argparse.ArgumentParser):
     ``--no-whole`` is an error without ``--level domain``.  ``--assign`` places the proteins of ``--dct`` on the representatives of
     another file: it needs a cut-off and is an error beside ``--pair``, ``--db``, ``--cluster``, ``--rank``, ``--domains`` /
     ``--dom`` / ``--db-dom``, ``--linkage``, ``--level`` and ``--no-whole``.  ``--reps-out`` is an error unless ``--assign`` is
-    given, or ``--cluster --linkage greedy`` without ``--level domain``."""
+    given, or ``--cluster --linkage greedy`` without ``--level domain``.  ``--tree`` prints the single-linkage tree of the file by
+    one score: an error beside ``--pair``, ``--db``, ``--cluster``, ``--assign``, ``--rank``, ``--linkage``, ``--level``,
+    ``--no-whole``, ``--reps-out`` and ``--domains`` / ``--dom`` / ``--db-dom``, and beside the cut-off of the other score."""
 
     def parse_known_args(self, args=None, namespace=None):
         ns, rest = super().parse_known_args(args, namespace)
+        tree = getattr(ns, 'tree', None)
+        if tree is not None:
+            beside = [flag for flag, given in (('--pair', ns.pair), ('--db', ns.db), ('--cluster', getattr(ns, 'cluster', False)),
+                                               ('--assign', getattr(ns, 'assign', None) is not None),
+                                               ('--rank', getattr(ns, 'rank', None) is not None),
+                                               ('--linkage', getattr(ns, 'linkage', None) is not None), ('--level', getattr(ns, 'level', None) is not None),
+                                               ('--no-whole', getattr(ns, 'no_whole', False)), ('--reps-out', getattr(ns, 'reps_out', None) is not None),
+                                               ('--domains', getattr(ns, 'domains', False)), ('--dom', getattr(ns, 'dom', None) is not None),
+                                               ('--db-dom', getattr(ns, 'db_dom', None) is not None)) if given]
+            if beside:
+                self.error(f'--tree prints the single-linkage tree of --dct: not with {beside[0]}')
+            if tree == 'domain' and ns.min_global is not None:
+                self.error('--tree domain orders the pairs by DCTdomain: its cut-off is --min-domain, not --min-global')
+            if tree == 'global' and ns.min_domain is not None:
+                self.error('--tree global orders the pairs by DCTglobal: its cut-off is --min-global, not --min-domain')
         if getattr(ns, 'assign', None) is not None:
             beside = [flag for flag, given in (('--pair', ns.pair), ('--db', ns.db), ('--cluster', getattr(ns, 'cluster', False)),
                                                ('--rank', getattr(ns, 'rank', None) is not None), ('--domains', getattr(ns, 'domains', False)),
@@ -1522,6 +1685,10 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument('--reps-out', metavar='FILE', default=argparse.SUPPRESS,
                     help='--assign: write the proteins of REPS followed by the new representatives as a -dct.npz; --cluster --linkage '
                          'greedy: write that run\'s representatives (the REPS of a later --assign)')
+    ap.add_argument('--tree', nargs='?', choices=SCORES, const='domain', default=argparse.SUPPRESS,
+                    help='print the single-linkage tree of the file instead of all pairs: the n - 1 all-against-all lines that join the '
+                         'proteins most similar first, by DCTdomain (domain, the default) or DCTglobal (global) -- cut at any score they '
+                         'give the clusters --cluster finds there; --min-domain X (--min-global Y with global) takes no pair below it')
     return ap
 
 
@@ -1534,7 +1701,9 @@ def main(argv=None):
     report = Report(args.output, (DOMAIN_CLUSTER_HEADER if level == 'domain' else CLUSTER_HEADER) if args.cluster or assign is not None
                     else DOMAIN_HEADER if domains else HEADER)
     t_work = time.time()
-    if assign is not None:
+    if getattr(args, 'tree', None) is not None:
+        tree_sim(args.dct, report, score=args.tree, min_domain=args.min_domain, min_global=args.min_global)
+    elif assign is not None:
         assign_sim(args.dct, assign, report, min_domain=args.min_domain, min_global=args.min_global, reps_out=reps_out)
     elif args.pair:
         pair_sim(args.dct, args.pair, args.pairfound, report, domains=bool(domains), dom=dom)

@@ -478,6 +478,68 @@ def cluster_labels(parent: torch.Tensor) -> torch.Tensor:
     return labels
 
 
+TREE_NONE = -1                                 # best as torch shows it: int64 -1 = all 64 bits set = no edge
+TREE_MAX_NODES = 1 << 24                       # i and j take 24 bits each of a packed edge
+
+
+class TreeState:
+    """The device arrays of the single-linkage tree over ``n`` nodes (``dctfp_tri_nearest`` / ``dctfp_tree_hook``): ``comp`` (int32,
+    this round's labels: ``arange(n)`` at the start), ``best`` (int64 as torch has no uint64 arithmetic: the packed edge
+    ``key << 48 | i << 24 | j`` per label, ``TREE_NONE`` = none), ``parent`` (the union-find forest of ``tri_link``), the edge list
+    ``edge_i`` / ``edge_j`` / ``edge_key`` (int32, ``max_edges`` = n - 1 slots unless given) and ``counter`` (int32: the edges
+    appended so far)."""
+
+    def __init__(self, n: int, device=None, max_edges: int = None):
+        device = device if device is not None else _dev()
+        self.comp = torch.arange(n, dtype=torch.int32, device=device)
+        self.parent = torch.arange(n, dtype=torch.int32, device=device)
+        self.best = torch.full((n,), TREE_NONE, dtype=torch.int64, device=device)
+        m = max(n - 1, 0) if max_edges is None else int(max_edges)
+        self.edge_i, self.edge_j, self.edge_key = (torch.zeros(m, dtype=torch.int32, device=device) for _ in range(3))
+        self.counter = torch.zeros(1, dtype=torch.int32, device=device)
+
+    def arrays(self, device) -> int:
+        n = self.comp.numel()
+        for t, dtype in ((self.comp, torch.int32), (self.parent, torch.int32), (self.best, torch.int64)):
+            if t.dtype != dtype or t.dim() != 1 or not t.is_contiguous() or t.device != device or t.numel() != n:
+                raise ValueError('comp / parent (int32) and best (int64) must be contiguous 1-D tensors of one length on the device of the other arguments')
+        return n
+
+    def edges(self):
+        """(i, j, key): the edges appended so far as int64 numpy arrays, in the order of their slots (one copy; the host waits)."""
+        m = min(int(self.counter.item()), self.edge_i.numel())
+        return tuple(t[:m].cpu().numpy().astype(np.int64) for t in (self.edge_i, self.edge_j, self.edge_key))
+
+
+def tri_nearest(tile: torch.Tensor, row0: int, col0: int, bound: int, ts: TreeState, row_empty=None, col_empty=None, cap: int = 17000):
+    """Lowers ``ts.best`` of both labels to the packed edge of every entry of an L1 tile that ``tri_filter_count`` would count and
+    whose two proteins carry different labels in ``ts.comp`` (``dctfp_tri_nearest``): one round's candidates for the lightest
+    edge out of every component.  ``tree_hook`` ends the round once every tile has been through."""
+    n_rows, n_cols, ld, re, ce, bound = _tri_filter_args(tile, row0, col0, bound, row_empty, col_empty, cap)
+    n_nodes = ts.arrays(tile.device)
+    if row0 + n_rows > n_nodes or col0 + n_cols > n_nodes:
+        raise IndexError('tile outside the nodes')
+    if n_rows and n_cols:
+        _launch(tile.device, 'dctfp_tri_nearest', tile.data_ptr(), n_rows, n_cols, ld, int(row0), int(col0), _ptr(re), _ptr(ce), cap, bound,
+                ts.comp.data_ptr(), ts.best.data_ptr(), n_nodes)
+
+
+def tree_hook(ts: TreeState):
+    """Ends a round (``dctfp_tree_hook``): every label of ``ts.comp`` appends the edge ``ts.best`` holds for it to the edge list
+    (``ts.counter`` grows; an edge chosen from both sides once) and joins its ends in ``ts.parent``; ``ts.best`` is none again
+    afterwards.  ``ts.comp`` is the caller's to renew: ``ts.comp = cluster_labels(ts.parent)``."""
+    n_nodes = ts.arrays(ts.comp.device)
+    edges = (ts.edge_i, ts.edge_j, ts.edge_key)
+    for t in edges:
+        if t.dtype != torch.int32 or t.dim() != 1 or not t.is_contiguous() or t.device != ts.comp.device or t.numel() != ts.edge_i.numel():
+            raise ValueError('the edge arrays must be contiguous int32 device tensors of one length')
+    if ts.counter.dtype != torch.int32 or ts.counter.numel() != 1 or ts.counter.device != ts.comp.device:
+        raise ValueError('counter must be one int32 on the device')
+    if n_nodes:
+        _launch(ts.comp.device, 'dctfp_tree_hook', ts.comp.data_ptr(), ts.best.data_ptr(), ts.parent.data_ptr(), n_nodes,
+                *(t.data_ptr() if t.numel() else None for t in edges), ts.counter.data_ptr(), ts.edge_i.numel())
+
+
 GREEDY_NONE = 0x7fffffff                       # assign: no representative yet
 GREEDY_UNDECIDED, GREEDY_MEMBER, GREEDY_NEW, GREEDY_DONE = 0, 1, 2, 3
 

@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define DCTFP_VERSION 108 /* 0.1.8: dctfp_rows_assign */
+#define DCTFP_VERSION 109 /* 0.1.9: dctfp_tri_nearest, dctfp_tree_hook */
 
 #define DCTFP_OK 0
 #define DCTFP_ERR_INVALID (-1) /* bad argument (null pointer, piece outside its sequence, ...) */
@@ -511,6 +511,38 @@ int dctfp_greedy_pairs_mark(dctfp_ctx* ctx, const int32_t* pi, const int32_t* pj
 int dctfp_rows_assign(dctfp_ctx* ctx, const int8_t* a, int64_t na, int64_t lda, const int32_t* value_a, int64_t a0, const int8_t* b,
                       int64_t nb, int64_t ldb, const int32_t* slot_b, int64_t b0, int32_t d, int32_t cap, int32_t bound, int32_t* assign,
                       int64_t n_assign, void* stream);
+
+/* The single-linkage tree of a file (dct-sim --tree; not in the reference): the minimum spanning forest of the graph whose edges
+ * are the pairs dctfp_tri_filter_count selects, under the strict order (key, i, j) with key = min(L1, cap) -- cut at any bound b it
+ * gives the components dctfp_tri_link gives at b.  Boruvka's algorithm in rounds; per round the caller hands every tile of the
+ * triangle to dctfp_tri_nearest, then calls dctfp_tree_hook once, then takes the new labels with dctfp_cluster_labels.
+ * comp (device int32, n_nodes) = the labels of this round (the smallest member of every component; 0 .. n - 1 at the start);
+ * best (device uint64, n_nodes, 8-byte aligned, started as all ones = none) = per label the lightest edge that leaves its
+ * component, packed key << 48 | i << 24 | j with i < j: unsigned order is the edge order.
+ * dctfp_tri_nearest extends dctfp_tri_filter_count's survival rule -- the same tile arguments, j > i and min(L1, cap) <= bound, the
+ * same flags -- from counting the surviving entries (i, j) to ranking them: every survivor with comp[i] != comp[j] lowers
+ * best[comp[i]] and best[comp[j]] to its packed edge.  Inside the launch best is touched by agent-scope relaxed atomics only
+ * (a load that skips a minimum which would change nothing, then the minimum), after a reduction in the workgroup: at most one
+ * global atomic per (row, 1024 columns) and per (column, 64 rows).  The result is a minimum over a set the inputs fix: it does
+ * not depend on the order in which the device ran or on how the triangle is cut into tiles.  A label outside [0, n_nodes) is
+ * skipped.  DCTFP_ERR_INVALID as dctfp_tri_link (row0 + n_rows or col0 + n_cols above n_nodes: checked on the host) and for best
+ * off an 8-byte boundary; DCTFP_ERR_LIMIT for n_nodes > 2^24 or cap > 32767 (the packing).  n_rows, n_cols or n_nodes of 0:
+ * nothing to do. */
+int dctfp_tri_nearest(dctfp_ctx* ctx, const int32_t* tile, int64_t n_rows, int64_t n_cols, int64_t ld, int64_t row0, int64_t col0,
+                      const uint8_t* row_empty, const uint8_t* col_empty, int32_t cap, int32_t bound, const int32_t* comp, uint64_t* best,
+                      int64_t n_nodes, void* stream);
+
+/* The end of a round of dctfp_tri_nearest (which extends dctfp_tri_filter_count's survival rule to the lightest surviving edge
+ * per component), one thread per node, in launches of its own: every label c (comp[c] == c) whose best[c] names an edge (i, j)
+ * leaving its component appends it -- edge_i / edge_j / edge_key [slot] (device int32, max_edges entries each), slot = the old
+ * value of *counter (device int32, the caller's running total, started as 0), which grows by one -- and joins i and j in `parent`
+ * (dctfp_tri_link's forest).  An edge chosen by both of its components is appended once, by the lower label.  Nothing is written
+ * at or beyond max_edges (a forest of n_nodes has at most n_nodes - 1 edges; the counter still counts).  The hooks of a round
+ * close no cycle because the edge order is strict.  Afterwards every entry of best is set back to all ones.
+ * DCTFP_ERR_INVALID for a NULL argument (the edge arrays may be NULL when max_edges is 0), a negative count or best off an 8-byte
+ * boundary; DCTFP_ERR_LIMIT for n_nodes > 2^24.  n_nodes of 0: nothing to do. */
+int dctfp_tree_hook(dctfp_ctx* ctx, const int32_t* comp, uint64_t* best, int32_t* parent, int64_t n_nodes, int32_t* edge_i, int32_t* edge_j,
+                    int32_t* edge_key, int32_t* counter, int64_t max_edges, void* stream);
 
 /* query_db's search (src/query_db.py:75-87: a flat FAISS index forced to METRIC_L1 at :76, index.search at :87) without a
  * distance matrix: for query rows q (nq x d, row stride ldq) and database rows b (nb x d, stride ldb), int8 on the device, each
