@@ -2577,11 +2577,9 @@ int dctfp_l1_matrix(dctfp_ctx* ctx, const int8_t* a, int64_t na, int64_t lda, co
     HIP_TRY(hipSetDevice(ctx->device));
     hipStream_t stream = (hipStream_t)stream_v;
     dim3 grid((unsigned)((nb + 127) / 128), (unsigned)((na + 127) / 128));  // 128 x 128 distances per workgroup (l1_matrix_kernel)
-    const bool aligned = ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b) | (uintptr_t)lda | (uintptr_t)ldb) & 3u) == 0;
-    const bool aligned16 = ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b) | (uintptr_t)lda | (uintptr_t)ldb) & 15u) == 0 &&
-                           lda < (1 << 24) && ldb < (1 << 24);   // (the kernel addresses a tile's rows with 32-bit offsets)
-    if (aligned16 && ctx->opt_l1_kernel != 1) hipLaunchKernelGGL(l1_matrix16_kernel, grid, dim3(256), 0, stream, a, na, lda, b, nb, ldb, d, out, ldo);
-    else if (aligned) hipLaunchKernelGGL((l1_matrix_kernel<true>), grid, dim3(256), 0, stream, a, na, lda, b, nb, ldb, d, out, ldo);
+    const int align = sad_tile_align(a, lda, b, ldb);   // (sad_tile.hip.h: 16, 4 or 1)
+    if (align == 16 && ctx->opt_l1_kernel != 1) hipLaunchKernelGGL(l1_matrix16_kernel, grid, dim3(256), 0, stream, a, na, lda, b, nb, ldb, d, out, ldo);
+    else if (align >= 4) hipLaunchKernelGGL((l1_matrix_kernel<true>), grid, dim3(256), 0, stream, a, na, lda, b, nb, ldb, d, out, ldo);
     else hipLaunchKernelGGL((l1_matrix_kernel<false>), grid, dim3(256), 0, stream, a, na, lda, b, nb, ldb, d, out, ldo);
     HIP_TRY(hipGetLastError());
     return DCTFP_OK;
@@ -2692,8 +2690,7 @@ int dctfp_protein_min(dctfp_ctx* ctx, const int8_t* a, int64_t lda, const int64_
     if (npa < 0 || npb < 0 || d < 1 || lda < d || ldb < d || ldo < npb) return fail(DCTFP_ERR_INVALID, "dctfp_protein_min: bad shape");
     if (npa > 0x7fffffff || npb > 0x7fffffff) return fail(DCTFP_ERR_LIMIT, "dctfp_protein_min: more than 2^31 - 1 proteins on a side");
     if (d > 512) return fail(DCTFP_ERR_LIMIT, "dctfp_protein_min: rows above 512 bytes (use l1_matrix + block_min)");
-    if (((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b) | (uintptr_t)lda | (uintptr_t)ldb) & 15u) != 0 ||
-        lda >= (1 << 24) || ldb >= (1 << 24))
+    if (sad_tile_align(a, lda, b, ldb) != 16)
         return fail(DCTFP_ERR_LIMIT, "dctfp_protein_min: rows not on 16-byte boundaries or 2^24 bytes apart (use l1_matrix + block_min)");
     if (npa == 0 || npb == 0) return DCTFP_OK;
     HIP_TRY(hipSetDevice(ctx->device));

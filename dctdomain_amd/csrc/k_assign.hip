@@ -1,8 +1,8 @@
 // dct-sim --assign: place new proteins on an existing set of representatives.  The cover pass of an assignment compares every
 // fingerprint of the representatives (a) with every fingerprint of the new proteins (b) and keeps, per new protein, the lowest
 // representative within the cut-off:
-//   rows_assign_kernel  -- rows_link_kernel's 128 x 128 contraction (k_cluster.hip) of two sets of rows; every pair of rows
-//                          within the bound lowers assign[slot of the b row] to the value of the a row, straight from the
+//   rows_assign_kernel  -- the 128 x 128 contraction of two sets of rows (a copy of its own of sad_tile.hip.h's sad_tile, see
+//                          below: a fix to the tile is made in both places); every pair of rows within the bound lowers assign[slot of the b row] to the value of the a row, straight from the
 //                          accumulators: no distance is written anywhere.
 // The block is a full rectangle: there is no diagonal and no owner, a and b are different files.  The host maps rows to protein
 // nodes through value_a / slot_b (one int32 per row; NULL: a0 + r / b0 + c) -- the DCTdomain route hands in all rows with their
@@ -19,12 +19,18 @@
 
 namespace {
 
+using dctfp::kSadKC;
+using dctfp::kSadLD;
+using dctfp::kSadLds;
+using dctfp::kSadTile;
 using dctfp::load_bytes4;
+using dctfp::sad_b_slot;
 using dctfp::v4u32;
 
-constexpr int kRaTile = 128;          // rows of a / of b per workgroup
-constexpr int kRaKC = 32;             // dwords per chunk of the contraction
-constexpr int kRaLD = kRaKC + 4;      // LDS row stride (dwords): ds_read_b128 of 16 consecutive rows without a bank conflict
+// The kernel keeps a copy of its own of sad_tile<ALIGN> and sad_keep_mask (sad_tile.hip.h, which rows_link_kernel calls): through the
+// shared function its 16-byte arm compiled to 128 registers instead of 126 and the cover pass of tools/assign_bench.py measured
+// 285.8 ms against 285.0 ms (the third runs of five processes each, disjoint ranges; profiles/sad_tile/README.md).  A fix to
+// the tile is made there AND here.  The layout numbers (kSadTile, kSadKC, kSadLD, sad_b_slot) are the header's.
 
 // ALIGN = what the rows' addresses are multiples of, dctfp_l1_matrix's three arms: 16 fills the tiles with 16-byte loads (32-bit
 // lane offsets: lda, ldb < 2^24), 4 with dword loads, 1 with byte loads -- into the same LDS layout, for the same contraction
@@ -37,10 +43,10 @@ __global__ __launch_bounds__(256, 4) void rows_assign_kernel(const int8_t* __res
                                                              const int32_t* __restrict__ value_a, int64_t a0, const int8_t* __restrict__ b,
                                                              int64_t nb, int64_t ldb, const int32_t* __restrict__ slot_b, int64_t b0, int d,
                                                              uint32_t cap, uint32_t bound, int32_t* assign, int64_t n_assign) {
-    const int64_t r0 = (int64_t)blockIdx.y * kRaTile, c0 = (int64_t)blockIdx.x * kRaTile;
-    const int rows_a = (int)min((int64_t)kRaTile, na - r0), rows_b = (int)min((int64_t)kRaTile, nb - c0);
-    __shared__ uint32_t sa[kRaTile * kRaLD];
-    __shared__ uint32_t sb[kRaTile * kRaLD];
+    const int64_t r0 = (int64_t)blockIdx.y * kSadTile, c0 = (int64_t)blockIdx.x * kSadTile;
+    const int rows_a = (int)min((int64_t)kSadTile, na - r0), rows_b = (int)min((int64_t)kSadTile, nb - c0);
+    __shared__ uint32_t sa[kSadLds];
+    __shared__ uint32_t sb[kSadLds];
     const int ty = threadIdx.x >> 4, tx = threadIdx.x & 15;
     const v4u32 flip = {0x80808080u, 0x80808080u, 0x80808080u, 0x80808080u};   // signed -> unsigned order, |x - y| unchanged
     const int8_t* __restrict__ abase = a + r0 * lda;
@@ -50,12 +56,12 @@ __global__ __launch_bounds__(256, 4) void rows_assign_kernel(const int8_t* __res
         for (int k = 0; k < kn; k += 4) {
             v4u32 av[8];
 #pragma unroll
-            for (int i = 0; i < 8; ++i) av[i] = *reinterpret_cast<const v4u32*>(&sa[(ty * 8 + i) * kRaLD + k]);
+            for (int i = 0; i < 8; ++i) av[i] = *reinterpret_cast<const v4u32*>(&sa[(ty * 8 + i) * kSadLD + k]);
 #pragma unroll
             for (int h = 0; h < 4; ++h) {
                 v4u32 bv[2];
 #pragma unroll
-                for (int j = 0; j < 2; ++j) bv[j] = *reinterpret_cast<const v4u32*>(&sb[((2 * h + j) * 16 + tx) * kRaLD + k]);
+                for (int j = 0; j < 2; ++j) bv[j] = *reinterpret_cast<const v4u32*>(&sb[((2 * h + j) * 16 + tx) * kSadLD + k]);
 #pragma unroll
                 for (int q = 0; q < 4; ++q)
 #pragma unroll
@@ -65,20 +71,19 @@ __global__ __launch_bounds__(256, 4) void rows_assign_kernel(const int8_t* __res
             }
         }
     };
-    // the b rows sit in LDS in the order the lanes read them (column c at slot (c % 8) * 16 + c / 8)
-    auto b_slot = [](int r) { return (r & 7) * 16 + (r >> 3); };
+    // (the b rows sit in LDS in the order the lanes read them: sad_b_slot)
     if constexpr (ALIGN == 16) {
         const int seg = threadIdx.x & 7, frow = threadIdx.x >> 3;
         const uint32_t lda32 = (uint32_t)lda, ldb32 = (uint32_t)ldb;
         const int d16 = d & ~15;
-        for (int byte0 = 0; byte0 < d16; byte0 += kRaKC * 4) {
+        for (int byte0 = 0; byte0 < d16; byte0 += kSadKC * 4) {
             const int my0 = byte0 + seg * 16;
             const bool have = my0 < d16;
             __syncthreads();
             {
-                v4u32 va[kRaTile / 32], vb[kRaTile / 32];
+                v4u32 va[kSadTile / 32], vb[kSadTile / 32];
 #pragma unroll
-                for (int i = 0; i < kRaTile / 32; ++i) {
+                for (int i = 0; i < kSadTile / 32; ++i) {
                     const int r = frow + 32 * i;
                     va[i] = flip;
                     vb[i] = flip;
@@ -86,18 +91,18 @@ __global__ __launch_bounds__(256, 4) void rows_assign_kernel(const int8_t* __res
                     if (have && r < rows_b) vb[i] = *reinterpret_cast<const v4u32*>(bbase + ((uint32_t)r * ldb32 + (uint32_t)my0));
                 }
 #pragma unroll
-                for (int i = 0; i < kRaTile / 32; ++i) {
+                for (int i = 0; i < kSadTile / 32; ++i) {
                     const int r = frow + 32 * i;
-                    *reinterpret_cast<v4u32*>(&sa[r * kRaLD + seg * 4]) = va[i] ^ flip;
-                    *reinterpret_cast<v4u32*>(&sb[b_slot(r) * kRaLD + seg * 4]) = vb[i] ^ flip;
+                    *reinterpret_cast<v4u32*>(&sa[r * kSadLD + seg * 4]) = va[i] ^ flip;
+                    *reinterpret_cast<v4u32*>(&sb[sad_b_slot(r) * kSadLD + seg * 4]) = vb[i] ^ flip;
                 }
             }
             __syncthreads();
-            contract(min(kRaKC, (d16 - byte0) >> 2));
+            contract(min(kSadKC, (d16 - byte0) >> 2));
         }
         if (d16 < d) {   // the 1..15 bytes the fingerprints end with
             __syncthreads();
-            if (threadIdx.x < kRaTile) {
+            if (threadIdx.x < kSadTile) {
                 const int r = threadIdx.x;
                 v4u32 va = flip, vb = flip;
 #pragma unroll
@@ -106,8 +111,8 @@ __global__ __launch_bounds__(256, 4) void rows_assign_kernel(const int8_t* __res
                     if (n > 0 && r < rows_a) va[q] = load_bytes4(abase + ((uint32_t)r * lda32 + (uint32_t)(d16 + 4 * q)), n);
                     if (n > 0 && r < rows_b) vb[q] = load_bytes4(bbase + ((uint32_t)r * ldb32 + (uint32_t)(d16 + 4 * q)), n);
                 }
-                *reinterpret_cast<v4u32*>(&sa[r * kRaLD]) = va ^ flip;
-                *reinterpret_cast<v4u32*>(&sb[b_slot(r) * kRaLD]) = vb ^ flip;
+                *reinterpret_cast<v4u32*>(&sa[r * kSadLD]) = va ^ flip;
+                *reinterpret_cast<v4u32*>(&sb[sad_b_slot(r) * kSadLD]) = vb ^ flip;
             }
             __syncthreads();
             contract(4);
@@ -116,15 +121,15 @@ __global__ __launch_bounds__(256, 4) void rows_assign_kernel(const int8_t* __res
         // l1_matrix_kernel's fill: thread -> dword k = tid & 31 of the rows tid >> 5, + 8, + 16, ...; the dwords between the end of
         // the fingerprints and the next multiple of four hold no difference (the contraction takes four at a time)
         const int nd = (d + 3) / 4;
-        const int k = threadIdx.x & (kRaKC - 1);
-        for (int k0 = 0; k0 < nd; k0 += kRaKC) {
-            const int kn4 = (min(kRaKC, nd - k0) + 3) & ~3;
+        const int k = threadIdx.x & (kSadKC - 1);
+        for (int k0 = 0; k0 < nd; k0 += kSadKC) {
+            const int kn4 = (min(kSadKC, nd - k0) + 3) & ~3;
             const int byte0 = (k0 + k) * 4;
             const int valid = min(4, d - byte0);
             __syncthreads();
             if (k < kn4) {
 #pragma unroll 4
-                for (int r = threadIdx.x >> 5; r < kRaTile; r += 256 / kRaKC) {
+                for (int r = threadIdx.x >> 5; r < kSadTile; r += 256 / kSadKC) {
                     uint32_t va = 0x80808080u, vb = 0x80808080u;
                     if (valid > 0 && r < rows_a) {
                         const int8_t* p = abase + r * lda + byte0;
@@ -134,8 +139,8 @@ __global__ __launch_bounds__(256, 4) void rows_assign_kernel(const int8_t* __res
                         const int8_t* p = bbase + r * ldb + byte0;
                         vb = (ALIGN == 4 && valid == 4) ? *reinterpret_cast<const uint32_t*>(p) : load_bytes4(p, valid);
                     }
-                    sa[r * kRaLD + k] = va ^ 0x80808080u;
-                    sb[b_slot(r) * kRaLD + k] = vb ^ 0x80808080u;
+                    sa[r * kSadLD + k] = va ^ 0x80808080u;
+                    sb[sad_b_slot(r) * kSadLD + k] = vb ^ 0x80808080u;
                 }
             }
             __syncthreads();
@@ -176,12 +181,9 @@ namespace dctfp_host {
 void launch_rows_assign(const int8_t* a, int64_t na, int64_t lda, const int32_t* value_a, int64_t a0, const int8_t* b, int64_t nb, int64_t ldb,
                         const int32_t* slot_b, int64_t b0, int d, int32_t cap, int32_t bound, int32_t* assign, int64_t n_assign,
                         hipStream_t stream) {
-    const dim3 grid((unsigned)((nb + kRaTile - 1) / kRaTile), (unsigned)((na + kRaTile - 1) / kRaTile));
-    // dctfp_l1_matrix's three arms (the 16-byte one addresses a tile's rows with 32-bit offsets)
-    const uintptr_t bits = reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b) | (uintptr_t)lda | (uintptr_t)ldb;
-    auto* const kernel = (bits & 15u) == 0 && lda < (1 << 24) && ldb < (1 << 24) ? rows_assign_kernel<16>
-                         : (bits & 3u) == 0                                        ? rows_assign_kernel<4>
-                                                                                   : rows_assign_kernel<1>;
+    const dim3 grid((unsigned)((nb + kSadTile - 1) / kSadTile), (unsigned)((na + kSadTile - 1) / kSadTile));
+    const int align = sad_tile_align(a, lda, b, ldb);   // (sad_tile.hip.h)
+    auto* const kernel = align == 16 ? rows_assign_kernel<16> : align == 4 ? rows_assign_kernel<4> : rows_assign_kernel<1>;
     hipLaunchKernelGGL(kernel, grid, dim3(256), 0, stream, a, na, lda, value_a, a0, b, nb, ldb, slot_b, b0, d, (uint32_t)cap, (uint32_t)bound,
                        assign, n_assign);
 }

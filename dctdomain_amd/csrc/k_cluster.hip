@@ -2,8 +2,8 @@
 // device in a lock-free union-find over parent[0 .. n_nodes):
 //   tri_link_kernel     -- tri_filter_count_kernel's walk over an int32 tile of L1 values; every surviving entry (i, j) is a union;
 //   link_pairs_kernel   -- the same union for a list of pairs;
-//   rows_link_kernel    -- dct-sim --cluster --level domain: the nodes are fingerprint rows.  l1_matrix16_kernel's 128 x 128
-//                          contraction of two sets of rows; every pair of rows of different proteins within the bound is a union,
+//   rows_link_kernel    -- dct-sim --cluster --level domain: the nodes are fingerprint rows.  sad_tile's 128 x 128 contraction
+//                          (sad_tile.hip.h) of two sets of rows; every pair of rows of different proteins within the bound is a union,
 //                          straight from the accumulators: no distance is written anywhere;
 //   flatten_kernel / labels_kernel -- after all linking, in launches of their own: every node under its root, labels[x] = root.
 //
@@ -22,12 +22,13 @@
 // workgroup's progress: a failed CAS means another wave succeeded, and there are no flags, tickets or spin loops.
 #define DCTFP_TEMPLATES_ONLY
 #include "launch.h"
+#include "sad_tile.hip.h"
 #include "tri_walk.hip.h"
 
 namespace {
 
-using dctfp::load_bytes4;
-using dctfp::v4u32;
+using dctfp::kSadLds;
+using dctfp::kSadTile;
 
 constexpr int kLinkThreads = 256;
 
@@ -112,141 +113,25 @@ __global__ __launch_bounds__(kLinkThreads) void link_pairs_kernel(const int32_t*
 
 // dct-sim --cluster --level domain.  Row r of a is node a0 + r, row c of b node b0 + c; one workgroup per 128 x 128 block of the
 // pairs, left out before any load when it lies wholly on or left of the diagonal (its last column's node <= its first row's).
-// The contraction is l1_matrix16_kernel's (8 x 8 per thread, 16-byte segments of sign-flipped bytes through v_sad_u8,
-// ds_read_b128 from LDS at a row stride of 36 dwords; k_protein.hip and k_query.hip restate it the same way).  ALIGN = what the
-// rows' addresses are multiples of, dctfp_l1_matrix's three arms: 16 fills the tiles with 16-byte loads (32-bit lane offsets:
-// lda, ldb < 2^24), 4 with dword loads, 1 with byte loads -- into the same LDS layout, for the same contraction.
-// The epilogue: a thread's 64 sums against the bound as a 64-bit mask (bit 8 i + j), rows and columns beyond the sets masked out,
-// and a wave-wide ballot, which in the common case shows no survivor anywhere.  Else the lanes with a bit walk theirs: node a < node
-// b, owner[a] != owner[b] (rows of one protein never join), neither skipped, then uf_union.  The host has checked
+// The contraction is sad_tile's (sad_tile.hip.h); ALIGN = dctfp::sad_tile_align() of the rows, the fill it takes.
+// The epilogue: a thread's 64 sums against the bound as a 64-bit mask (sad_keep_mask: bit 8 i + j, rows and columns beyond the sets
+// masked out) and a wave-wide ballot, which in the common case shows no survivor anywhere.  Else the lanes with a bit walk theirs:
+// node a < node b, owner[a] != owner[b] (rows of one protein never join), neither skipped, then uf_union.  The host has checked
 // a0 + na <= n_nodes and b0 + nb <= n_nodes; owner and skip have n_nodes entries.
-constexpr int kRlTile = 128;          // rows of a / of b per workgroup
-constexpr int kRlKC = 32;             // dwords per chunk of the contraction
-constexpr int kRlLD = kRlKC + 4;      // LDS row stride (dwords)
-
 template <int ALIGN>
 __global__ __launch_bounds__(256, 4) void rows_link_kernel(const int8_t* __restrict__ a, int64_t na, int64_t lda, int64_t a0,
                                                            const int8_t* __restrict__ b, int64_t nb, int64_t ldb, int64_t b0, int d,
                                                            const int32_t* __restrict__ owner, const uint8_t* __restrict__ skip, uint32_t cap,
                                                            uint32_t bound, int32_t* parent) {
-    const int64_t r0 = (int64_t)blockIdx.y * kRlTile, c0 = (int64_t)blockIdx.x * kRlTile;
-    const int rows_a = (int)min((int64_t)kRlTile, na - r0), rows_b = (int)min((int64_t)kRlTile, nb - c0);
+    const int64_t r0 = (int64_t)blockIdx.y * kSadTile, c0 = (int64_t)blockIdx.x * kSadTile;
+    const int rows_a = (int)min((int64_t)kSadTile, na - r0), rows_b = (int)min((int64_t)kSadTile, nb - c0);
     if (b0 + c0 + rows_b - 1 <= a0 + r0) return;   // (the whole workgroup: no pair of the block has node a < node b)
-    __shared__ uint32_t sa[kRlTile * kRlLD];
-    __shared__ uint32_t sb[kRlTile * kRlLD];
+    __shared__ uint32_t sa[kSadLds];
+    __shared__ uint32_t sb[kSadLds];
     const int ty = threadIdx.x >> 4, tx = threadIdx.x & 15;
-    const v4u32 flip = {0x80808080u, 0x80808080u, 0x80808080u, 0x80808080u};   // signed -> unsigned order, |x - y| unchanged
-    const int8_t* __restrict__ abase = a + r0 * lda;
-    const int8_t* __restrict__ bbase = b + c0 * ldb;
     uint32_t acc[8][8] = {};
-    auto contract = [&](int kn) {
-        for (int k = 0; k < kn; k += 4) {
-            v4u32 av[8];
-#pragma unroll
-            for (int i = 0; i < 8; ++i) av[i] = *reinterpret_cast<const v4u32*>(&sa[(ty * 8 + i) * kRlLD + k]);
-#pragma unroll
-            for (int h = 0; h < 4; ++h) {
-                v4u32 bv[2];
-#pragma unroll
-                for (int j = 0; j < 2; ++j) bv[j] = *reinterpret_cast<const v4u32*>(&sb[((2 * h + j) * 16 + tx) * kRlLD + k]);
-#pragma unroll
-                for (int q = 0; q < 4; ++q)
-#pragma unroll
-                    for (int i = 0; i < 8; ++i)
-#pragma unroll
-                        for (int j = 0; j < 2; ++j) acc[i][2 * h + j] = __builtin_amdgcn_sad_u8(av[i][q], bv[j][q], acc[i][2 * h + j]);
-            }
-        }
-    };
-    // the b rows sit in LDS in the order the lanes read them (column c at slot (c % 8) * 16 + c / 8)
-    auto b_slot = [](int r) { return (r & 7) * 16 + (r >> 3); };
-    if constexpr (ALIGN == 16) {
-        const int seg = threadIdx.x & 7, frow = threadIdx.x >> 3;
-        const uint32_t lda32 = (uint32_t)lda, ldb32 = (uint32_t)ldb;
-        const int d16 = d & ~15;
-        for (int byte0 = 0; byte0 < d16; byte0 += kRlKC * 4) {
-            const int my0 = byte0 + seg * 16;
-            const bool have = my0 < d16;
-            __syncthreads();
-            {
-                v4u32 va[kRlTile / 32], vb[kRlTile / 32];
-#pragma unroll
-                for (int i = 0; i < kRlTile / 32; ++i) {
-                    const int r = frow + 32 * i;
-                    va[i] = flip;
-                    vb[i] = flip;
-                    if (have && r < rows_a) va[i] = *reinterpret_cast<const v4u32*>(abase + ((uint32_t)r * lda32 + (uint32_t)my0));
-                    if (have && r < rows_b) vb[i] = *reinterpret_cast<const v4u32*>(bbase + ((uint32_t)r * ldb32 + (uint32_t)my0));
-                }
-#pragma unroll
-                for (int i = 0; i < kRlTile / 32; ++i) {
-                    const int r = frow + 32 * i;
-                    *reinterpret_cast<v4u32*>(&sa[r * kRlLD + seg * 4]) = va[i] ^ flip;
-                    *reinterpret_cast<v4u32*>(&sb[b_slot(r) * kRlLD + seg * 4]) = vb[i] ^ flip;
-                }
-            }
-            __syncthreads();
-            contract(min(kRlKC, (d16 - byte0) >> 2));
-        }
-        if (d16 < d) {   // the 1..15 bytes the fingerprints end with
-            __syncthreads();
-            if (threadIdx.x < kRlTile) {
-                const int r = threadIdx.x;
-                v4u32 va = flip, vb = flip;
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    const int n = min(4, d - d16 - 4 * q);
-                    if (n > 0 && r < rows_a) va[q] = load_bytes4(abase + ((uint32_t)r * lda32 + (uint32_t)(d16 + 4 * q)), n);
-                    if (n > 0 && r < rows_b) vb[q] = load_bytes4(bbase + ((uint32_t)r * ldb32 + (uint32_t)(d16 + 4 * q)), n);
-                }
-                *reinterpret_cast<v4u32*>(&sa[r * kRlLD]) = va ^ flip;
-                *reinterpret_cast<v4u32*>(&sb[b_slot(r) * kRlLD]) = vb ^ flip;
-            }
-            __syncthreads();
-            contract(4);
-        }
-    } else {
-        // l1_matrix_kernel's fill: thread -> dword k = tid & 31 of the rows tid >> 5, + 8, + 16, ...; the dwords between the end of
-        // the fingerprints and the next multiple of four hold no difference (the contraction takes four at a time)
-        const int nd = (d + 3) / 4;
-        const int k = threadIdx.x & (kRlKC - 1);
-        for (int k0 = 0; k0 < nd; k0 += kRlKC) {
-            const int kn4 = (min(kRlKC, nd - k0) + 3) & ~3;
-            const int byte0 = (k0 + k) * 4;
-            const int valid = min(4, d - byte0);
-            __syncthreads();
-            if (k < kn4) {
-#pragma unroll 4
-                for (int r = threadIdx.x >> 5; r < kRlTile; r += 256 / kRlKC) {
-                    uint32_t va = 0x80808080u, vb = 0x80808080u;
-                    if (valid > 0 && r < rows_a) {
-                        const int8_t* p = abase + r * lda + byte0;
-                        va = (ALIGN == 4 && valid == 4) ? *reinterpret_cast<const uint32_t*>(p) : load_bytes4(p, valid);
-                    }
-                    if (valid > 0 && r < rows_b) {
-                        const int8_t* p = bbase + r * ldb + byte0;
-                        vb = (ALIGN == 4 && valid == 4) ? *reinterpret_cast<const uint32_t*>(p) : load_bytes4(p, valid);
-                    }
-                    sa[r * kRlLD + k] = va ^ 0x80808080u;
-                    sb[b_slot(r) * kRlLD + k] = vb ^ 0x80808080u;
-                }
-            }
-            __syncthreads();
-            contract(kn4);
-        }
-    }
-    // row ty * 8 + i, column tx * 8 + j: bit 8 i + j
-    uint32_t lo = 0, hi = 0;
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            lo |= (uint32_t)(min(acc[i][j], cap) <= bound) << (8 * i + j);
-            hi |= (uint32_t)(min(acc[i + 4][j], cap) <= bound) << (8 * i + j);
-        }
-    const int n_row = max(0, min(8, rows_a - ty * 8)), n_col = max(0, min(8, rows_b - tx * 8));
-    uint64_t keep = ((uint64_t)hi << 32 | lo) & (n_row == 8 ? ~(uint64_t)0 : ((uint64_t)1 << (8 * n_row)) - 1) &
-                    (0x0101010101010101ull * ((1u << n_col) - 1));
+    dctfp::sad_tile<ALIGN>(a + r0 * lda, rows_a, lda, b + c0 * ldb, rows_b, ldb, d, sa, sb, acc);
+    uint64_t keep = dctfp::sad_keep_mask(acc, cap, bound, rows_a, rows_b);
     if (__ballot(keep != 0) == 0) return;
     const int64_t node_a = a0 + r0 + ty * 8, node_b = b0 + c0 + tx * 8;
     while (keep) {
@@ -301,12 +186,9 @@ void launch_link_pairs(const int32_t* pi, const int32_t* pj, int64_t n_pairs, in
 
 void launch_rows_link(const int8_t* a, int64_t na, int64_t lda, int64_t a0, const int8_t* b, int64_t nb, int64_t ldb, int64_t b0, int d,
                       const int32_t* owner, const uint8_t* skip, int32_t cap, int32_t bound, int32_t* parent, hipStream_t stream) {
-    const dim3 grid((unsigned)((nb + kRlTile - 1) / kRlTile), (unsigned)((na + kRlTile - 1) / kRlTile));
-    // dctfp_l1_matrix's three arms (the 16-byte one addresses a tile's rows with 32-bit offsets)
-    const uintptr_t bits = reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b) | (uintptr_t)lda | (uintptr_t)ldb;
-    auto* const kernel = (bits & 15u) == 0 && lda < (1 << 24) && ldb < (1 << 24) ? rows_link_kernel<16>
-                         : (bits & 3u) == 0                                        ? rows_link_kernel<4>
-                                                                                   : rows_link_kernel<1>;
+    const dim3 grid((unsigned)((nb + kSadTile - 1) / kSadTile), (unsigned)((na + kSadTile - 1) / kSadTile));
+    const int align = sad_tile_align(a, lda, b, ldb);
+    auto* const kernel = align == 16 ? rows_link_kernel<16> : align == 4 ? rows_link_kernel<4> : rows_link_kernel<1>;
     hipLaunchKernelGGL(kernel, grid, dim3(256), 0, stream, a, na, lda, a0, b, nb, ldb, b0, d, owner, skip, (uint32_t)cap, (uint32_t)bound, parent);
 }
 

@@ -1,34 +1,32 @@
 // DCTdomain for every protein x protein pair of two fingerprint sets, straight from the fingerprints (dct-sim --db --rank domain):
 //   protein_plan_count_kernel / protein_plan_scan_kernel / protein_plan_write_kernel -- consecutive proteins packed into blocks
 //       of at most 128 fingerprint rows and 96 proteins (a protein of more rows: a block of its own), on the device;
-//   protein_min_kernel -- one (block of a, block of b) task at a time: l1_matrix16_kernel's 128 x 128 contraction, reduced to
+//   protein_min_kernel -- one (block of a, block of b) task at a time: sad_tile's 128 x 128 contraction (sad_tile.hip.h), reduced to
 //       protein minima in LDS, each task's output entries written once with plain stores (no atomics in global memory, no fill
 //       of the tile).
 #define DCTFP_TEMPLATES_ONLY
 #include "launch.h"
+#include "sad_tile.hip.h"
 
 namespace {
 
-using dctfp::load_bytes4;
-using dctfp::v4u32;
+using dctfp::kSadLds;
+using dctfp::kSadTile;                // fingerprint rows of a sub-tile
 
-constexpr int kPmTile = 128;          // fingerprint rows of a sub-tile (l1_matrix16_kernel's tile)
-constexpr int kPmKC = 32;             // dwords per chunk of the contraction
-constexpr int kPmLD = kPmKC + 4;      // LDS row stride (dwords)
 constexpr int kPmMaxProt = 96;        // proteins per block: 96 x 96 protein minima fill the two operand tiles' LDS exactly
 constexpr int kPlanSeg = 1024;        // proteins per packing segment (one thread each; a block never crosses a segment)
 constexpr int kPlanThreads = 256;
 
-static_assert(kPmMaxProt * kPmMaxProt <= 2 * kPmTile * kPmLD, "the protein tile must fit in the operand tiles' LDS");
+static_assert(kPmMaxProt * kPmMaxProt <= 2 * kSadLds, "the protein tile must fit in the operand tiles' LDS");
 
-// Greedy packing of the proteins [s0, s1) of one segment: a block takes proteins while its rows stay within kPmTile and its
-// proteins within kPmMaxProt (a protein of more rows than kPmTile alone).  With `starts` == nullptr only counts.
+// Greedy packing of the proteins [s0, s1) of one segment: a block takes proteins while its rows stay within kSadTile and its
+// proteins within kPmMaxProt (a protein of more rows than kSadTile alone).  With `starts` == nullptr only counts.
 __device__ inline int64_t plan_segment(const int64_t* __restrict__ idx, int64_t s0, int64_t s1, int32_t* __restrict__ starts) {
     int64_t n = 0;
     for (int64_t p = s0; p < s1;) {
         const int64_t r0 = idx[p];
         int64_t q = p + 1;
-        while (q < s1 && q - p < kPmMaxProt && idx[q + 1] - r0 <= kPmTile) ++q;
+        while (q < s1 && q - p < kPmMaxProt && idx[q + 1] - r0 <= kSadTile) ++q;
         if (starts) starts[n] = (int32_t)p;
         ++n;
         p = q;
@@ -84,8 +82,7 @@ __device__ inline void protein_map(const int64_t* __restrict__ idx, int64_t p0, 
 }
 
 // One task = (block ka of a, block kb of b); the grid walks the tasks.  Per pair of 128-row sub-tiles (one unless a block is a
-// single protein of more than 128 rows): the 128 x 128 L1 distances as l1_matrix16_kernel computes them (8 x 8 per thread,
-// 16-byte segments of sign-flipped bytes through v_sad_u8, ds_read_b128 from LDS), then each thread's 64 values folded along its
+// single protein of more than 128 rows): the 128 x 128 L1 distances from sad_tile<16>, then each thread's 64 values folded along its
 // runs of equal column protein and into the block's protein-minimum tile with LDS atomicMin.  That tile lives in the operand
 // tiles' LDS when there is one sub-tile (<= 96 x 96 proteins), in a small array of its own when there are several (one side
 // is then a single protein: <= 96 entries).  Every entry of the task's output is then stored once; a protein without rows keeps
@@ -95,106 +92,39 @@ __global__ __launch_bounds__(256, 2) void protein_min_kernel(const int8_t* __res
                                                              const int8_t* __restrict__ b, int64_t ldb, const int64_t* __restrict__ idx_b,
                                                              const int32_t* __restrict__ start_b, const int64_t* __restrict__ nblk_b, int d,
                                                              int32_t* __restrict__ out, int64_t ldo) {
-    __shared__ uint32_t lds[2 * kPmTile * kPmLD];
+    __shared__ uint32_t lds[2 * kSadLds];
     __shared__ int32_t small_tile[kPmMaxProt];
-    __shared__ uint8_t rmap[kPmTile], cmap[kPmTile];
+    __shared__ uint8_t rmap[kSadTile], cmap[kSadTile];
     uint32_t* const sa = lds;
-    uint32_t* const sb = lds + kPmTile * kPmLD;
+    uint32_t* const sb = lds + kSadLds;
     int32_t* const big_tile = reinterpret_cast<int32_t*>(lds);
     const int ty = threadIdx.x >> 4, tx = threadIdx.x & 15;
-    const int seg = threadIdx.x & 7, frow = threadIdx.x >> 3;
-    const v4u32 flip = {0x80808080u, 0x80808080u, 0x80808080u, 0x80808080u};   // signed -> unsigned order, |x - y| unchanged
     const int64_t n_blk_a = *nblk_a, n_blk_b = *nblk_b, n_tasks = n_blk_a * n_blk_b;
-    const int d16 = d & ~15;
-    auto b_slot = [](int r) { return (r & 7) * 16 + (r >> 3); };
     for (int64_t task = blockIdx.x; task < n_tasks; task += gridDim.x) {
         const int64_t ka = task / n_blk_b, kb = task - ka * n_blk_b;
         const int64_t pa0 = start_a[ka], pb0 = start_b[kb];
         const int na = (int)(start_a[ka + 1] - pa0), nb = (int)(start_b[kb + 1] - pb0);
         const int64_t ra0 = idx_a[pa0], ra1 = idx_a[pa0 + na], rb0 = idx_b[pb0], rb1 = idx_b[pb0 + nb];
-        const bool single = ra1 - ra0 <= kPmTile && rb1 - rb0 <= kPmTile;
+        const bool single = ra1 - ra0 <= kSadTile && rb1 - rb0 <= kSadTile;
         int32_t* const tile = single ? big_tile : small_tile;
         const int n_ent = na * nb;
         if (!single || ra1 == ra0 || rb1 == rb0) {
             for (int e = threadIdx.x; e < n_ent; e += 256) tile[e] = 0x7fffffff;
             __syncthreads();
         }
-        for (int64_t ta = ra0; ta < ra1; ta += kPmTile)
-            for (int64_t tb = rb0; tb < rb1; tb += kPmTile) {
-                const int rows_a = (int)min((int64_t)kPmTile, ra1 - ta), rows_b = (int)min((int64_t)kPmTile, rb1 - tb);
+        for (int64_t ta = ra0; ta < ra1; ta += kSadTile)
+            for (int64_t tb = rb0; tb < rb1; tb += kSadTile) {
+                const int rows_a = (int)min((int64_t)kSadTile, ra1 - ta), rows_b = (int)min((int64_t)kSadTile, rb1 - tb);
                 protein_map(idx_a, pa0, na, ta, rows_a, rmap);
                 protein_map(idx_b, pb0, nb, tb, rows_b, cmap);
                 uint32_t acc[8][8] = {};
-                const int8_t* __restrict__ abase = a + ta * lda;
-                const int8_t* __restrict__ bbase = b + tb * ldb;
-                const uint32_t lda32 = (uint32_t)lda, ldb32 = (uint32_t)ldb;
-                auto contract = [&](int kn) {
-                    for (int k = 0; k < kn; k += 4) {
-                        v4u32 av[8];
-#pragma unroll
-                        for (int i = 0; i < 8; ++i) av[i] = *reinterpret_cast<const v4u32*>(&sa[(ty * 8 + i) * kPmLD + k]);
-#pragma unroll
-                        for (int h = 0; h < 4; ++h) {
-                            v4u32 bv[2];
-#pragma unroll
-                            for (int j = 0; j < 2; ++j) bv[j] = *reinterpret_cast<const v4u32*>(&sb[((2 * h + j) * 16 + tx) * kPmLD + k]);
-#pragma unroll
-                            for (int q = 0; q < 4; ++q)
-#pragma unroll
-                                for (int i = 0; i < 8; ++i)
-#pragma unroll
-                                    for (int j = 0; j < 2; ++j)
-                                        acc[i][2 * h + j] = __builtin_amdgcn_sad_u8(av[i][q], bv[j][q], acc[i][2 * h + j]);
-                        }
-                    }
-                };
-                for (int byte0 = 0; byte0 < d16; byte0 += kPmKC * 4) {
-                    const int my0 = byte0 + seg * 16;
-                    const bool have = my0 < d16;
-                    __syncthreads();
-                    {
-                        v4u32 va[kPmTile / 32], vb[kPmTile / 32];
-#pragma unroll
-                        for (int i = 0; i < kPmTile / 32; ++i) {
-                            const int r = frow + 32 * i;
-                            va[i] = flip;
-                            vb[i] = flip;
-                            if (have && r < rows_a) va[i] = *reinterpret_cast<const v4u32*>(abase + ((uint32_t)r * lda32 + (uint32_t)my0));
-                            if (have && r < rows_b) vb[i] = *reinterpret_cast<const v4u32*>(bbase + ((uint32_t)r * ldb32 + (uint32_t)my0));
-                        }
-#pragma unroll
-                        for (int i = 0; i < kPmTile / 32; ++i) {
-                            const int r = frow + 32 * i;
-                            *reinterpret_cast<v4u32*>(&sa[r * kPmLD + seg * 4]) = va[i] ^ flip;
-                            *reinterpret_cast<v4u32*>(&sb[b_slot(r) * kPmLD + seg * 4]) = vb[i] ^ flip;
-                        }
-                    }
-                    __syncthreads();
-                    contract(min(kPmKC, (d16 - byte0) >> 2));
-                }
-                if (d16 < d) {   // the 1..15 bytes the fingerprints end with
-                    __syncthreads();
-                    if (threadIdx.x < kPmTile) {
-                        const int r = threadIdx.x;
-                        v4u32 va = flip, vb = flip;
-#pragma unroll
-                        for (int q = 0; q < 4; ++q) {
-                            const int n = min(4, d - d16 - 4 * q);
-                            if (n > 0 && r < rows_a) va[q] = load_bytes4(abase + ((uint32_t)r * lda32 + (uint32_t)(d16 + 4 * q)), n);
-                            if (n > 0 && r < rows_b) vb[q] = load_bytes4(bbase + ((uint32_t)r * ldb32 + (uint32_t)(d16 + 4 * q)), n);
-                        }
-                        *reinterpret_cast<v4u32*>(&sa[r * kPmLD]) = va ^ flip;
-                        *reinterpret_cast<v4u32*>(&sb[b_slot(r) * kPmLD]) = vb ^ flip;
-                    }
-                    __syncthreads();
-                    contract(4);
-                }
+                dctfp::sad_tile<16>(a + ta * lda, rows_a, lda, b + tb * ldb, rows_b, ldb, d, sa, sb, acc);
                 __syncthreads();                                   // (the operand tiles are read: the protein tile may take them)
                 if (single) {
                     for (int e = threadIdx.x; e < n_ent; e += 256) tile[e] = 0x7fffffff;
                     __syncthreads();
                 }
-                // row ty * 8 + i, column tx * 8 + j (the b rows' LDS slots: l1_matrix16_kernel)
+                // row ty * 8 + i, column tx * 8 + j (sad_tile)
                 const int c0 = tx * 8;
                 if (c0 < rows_b) {
                     int cp[8];

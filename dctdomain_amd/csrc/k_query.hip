@@ -1,6 +1,6 @@
 // query_db at database scale (src/query_db.py:17-91) without a distance matrix in HBM:
-//   l1_knn_kernel      -- the L1 distances of a 128-row query tile against a slice of the database (l1_matrix16_kernel's
-//                         contraction) and, fused behind them, each row's k nearest: keys below the row's threshold go to a
+//   l1_knn_kernel      -- the L1 distances of a 128-row query tile against a slice of the database (sad_tile's
+//                         contraction, in a copy of its own) and, fused behind them, each row's k nearest: keys below the row's threshold go to a
 //                         small LDS ring, a full ring is merged into the row's sorted k-list in global scratch;
 //   knn_merge2_kernel  -- two sorted k-lists of a row -> one (the slices of the database, pairwise);
 //   query_rank_kernel  -- the protein-level ranking of ranked_hits (src/query_db.py:33-40) from the sorted hit lists;
@@ -12,11 +12,18 @@
 
 namespace {
 
+using dctfp::kSadKC;
+using dctfp::kSadLD;
+using dctfp::kSadLds;
 using dctfp::load_bytes4;
+using dctfp::sad_b_slot;
 using dctfp::v4u32;
 
-constexpr int kTile = 128;            // query rows and database columns per block (l1_matrix16_kernel's tile)
-constexpr int kKC = 32, kLD = kKC + 4;  // dwords per chunk, LDS row stride in dwords
+// l1_knn_kernel keeps a copy of its own of sad_tile<16> (sad_tile.hip.h): it sits at the register ceiling, and through the shared
+// function (290 registers instead of 294) every k = 1024 configuration of tools/query_db_bench.py measured 0.7 - 1.4 % slower than
+// the parent's five runs, whose spread is 0.05 % (the k = 100 ones 1 - 2 % faster; profiles/sad_tile/README.md).  A fix to the
+// tile is made there AND here.  The layout numbers (kSadKC, kSadLD, sad_b_slot) are the header's.
+constexpr int kTile = dctfp::kSadTile;  // query rows and database columns per block: the tile's, and the size of the row state
 constexpr int kRing = 32;             // candidate slots per row in LDS
 constexpr unsigned long long kNone = ~0ull;
 
@@ -27,8 +34,8 @@ __global__ __launch_bounds__(256, 1) void l1_knn_kernel(const int8_t* __restrict
                                                         int64_t nb, int64_t ldb, int d, int k, int64_t slice_cols, int n_slices,
                                                         unsigned long long* __restrict__ work, unsigned long long* __restrict__ cand,
                                                         int32_t* __restrict__ out_val, int32_t* __restrict__ out_idx, int64_t col0, int k_eff) {
-    __shared__ uint32_t sa[kTile * kLD];
-    __shared__ uint32_t sb[kTile * kLD];
+    __shared__ uint32_t sa[kSadLds];
+    __shared__ uint32_t sb[kSadLds];
     __shared__ unsigned long long ring[kTile][kRing];
     __shared__ unsigned long long tau[kTile];   // the row's k-th key (kNone while its list holds fewer than k)
     __shared__ int cnt[kTile];                  // ring entries (attempts beyond kRing included)
@@ -133,7 +140,6 @@ __global__ __launch_bounds__(256, 1) void l1_knn_kernel(const int8_t* __restrict
     const v4u32 flip = {0x80808080u, 0x80808080u, 0x80808080u, 0x80808080u};  // signed -> unsigned order, |x - y| unchanged
     const int8_t* __restrict__ abase = a + r0 * lda;
     const uint32_t lda32 = (uint32_t)lda, ldb32 = (uint32_t)ldb;
-    auto b_slot = [](int r) { return (r & 7) * 16 + (r >> 3); };
     const int d16 = d & ~15;
     for (int64_t c0 = cs0; c0 < cs1; c0 += kTile) {
         const int8_t* __restrict__ bbase = b + c0 * ldb;
@@ -143,12 +149,12 @@ __global__ __launch_bounds__(256, 1) void l1_knn_kernel(const int8_t* __restrict
             for (int kk = 0; kk < kn; kk += 4) {
                 v4u32 av[8];
 #pragma unroll
-                for (int i = 0; i < 8; ++i) av[i] = *reinterpret_cast<const v4u32*>(&sa[(ty * 8 + i) * kLD + kk]);
+                for (int i = 0; i < 8; ++i) av[i] = *reinterpret_cast<const v4u32*>(&sa[(ty * 8 + i) * kSadLD + kk]);
 #pragma unroll
                 for (int h = 0; h < 4; ++h) {
                     v4u32 bv[2];
 #pragma unroll
-                    for (int j = 0; j < 2; ++j) bv[j] = *reinterpret_cast<const v4u32*>(&sb[((2 * h + j) * 16 + tx) * kLD + kk]);
+                    for (int j = 0; j < 2; ++j) bv[j] = *reinterpret_cast<const v4u32*>(&sb[((2 * h + j) * 16 + tx) * kSadLD + kk]);
 #pragma unroll
                     for (int q = 0; q < 4; ++q)
 #pragma unroll
@@ -158,7 +164,7 @@ __global__ __launch_bounds__(256, 1) void l1_knn_kernel(const int8_t* __restrict
                 }
             }
         };
-        for (int byte0 = 0; byte0 < d16; byte0 += kKC * 4) {
+        for (int byte0 = 0; byte0 < d16; byte0 += kSadKC * 4) {
             const int my0 = byte0 + seg * 16;
             const bool have = my0 < d16;
             __syncthreads();
@@ -175,12 +181,12 @@ __global__ __launch_bounds__(256, 1) void l1_knn_kernel(const int8_t* __restrict
 #pragma unroll
                 for (int i = 0; i < kTile / 32; ++i) {
                     const int r = frow + 32 * i;
-                    *reinterpret_cast<v4u32*>(&sa[r * kLD + seg * 4]) = va[i] ^ flip;
-                    *reinterpret_cast<v4u32*>(&sb[b_slot(r) * kLD + seg * 4]) = vb[i] ^ flip;
+                    *reinterpret_cast<v4u32*>(&sa[r * kSadLD + seg * 4]) = va[i] ^ flip;
+                    *reinterpret_cast<v4u32*>(&sb[sad_b_slot(r) * kSadLD + seg * 4]) = vb[i] ^ flip;
                 }
             }
             __syncthreads();
-            contract(min(kKC, (d16 - byte0) >> 2));
+            contract(min(kSadKC, (d16 - byte0) >> 2));
         }
         if (d16 < d) {   // the 1..15 bytes the fingerprints end with
             __syncthreads();
@@ -193,8 +199,8 @@ __global__ __launch_bounds__(256, 1) void l1_knn_kernel(const int8_t* __restrict
                     if (n > 0 && r < rows_a) va[q] = load_bytes4(abase + ((uint32_t)r * lda32 + (uint32_t)(d16 + 4 * q)), n);
                     if (n > 0 && r < rows_b) vb[q] = load_bytes4(bbase + ((uint32_t)r * ldb32 + (uint32_t)(d16 + 4 * q)), n);
                 }
-                *reinterpret_cast<v4u32*>(&sa[r * kLD]) = va ^ flip;
-                *reinterpret_cast<v4u32*>(&sb[b_slot(r) * kLD]) = vb ^ flip;
+                *reinterpret_cast<v4u32*>(&sa[r * kSadLD]) = va ^ flip;
+                *reinterpret_cast<v4u32*>(&sb[sad_b_slot(r) * kSadLD]) = vb ^ flip;
             }
             __syncthreads();
             contract(4);

@@ -176,8 +176,8 @@ void launch_tri_link(const int32_t* tile, int64_t n_rows, int64_t n_cols, int64_
                      const uint8_t* col_empty, int32_t cap, int32_t bound, int32_t* parent, hipStream_t stream);
 void launch_link_pairs(const int32_t* pi, const int32_t* pj, int64_t n_pairs, int32_t* parent, int64_t n_nodes, hipStream_t stream);
 void launch_cluster_labels(int32_t* parent, int64_t n_nodes, int32_t* labels, hipStream_t stream);
-// (dctfp_rows_link: the nodes are fingerprint rows -- l1_matrix16_kernel's contraction, every pair of rows of different owners
-// within the bound joined from the accumulators; the launcher picks dctfp_l1_matrix's arm by the rows' alignment)
+// (dctfp_rows_link: the nodes are fingerprint rows -- sad_tile's contraction (sad_tile.hip.h), every pair of rows of different owners
+// within the bound joined from the accumulators; the launcher picks the fill by the rows' alignment, sad_tile_align)
 void launch_rows_link(const int8_t* a, int64_t na, int64_t lda, int64_t a0, const int8_t* b, int64_t nb, int64_t ldb, int64_t b0, int d,
                       const int32_t* owner, const uint8_t* skip, int32_t cap, int32_t bound, int32_t* parent, hipStream_t stream);
 

@@ -313,6 +313,50 @@ def test_new_unit_and_shared_header_are_part_of_the_build():
         assert inc in text and 'filter_quad(' in text
 
 
+def test_the_sad_tile_is_defined_once_in_a_header_every_user_includes():
+    """The 128 x 128 v_sad_u8 contraction of l1_matrix16_kernel, protein_min_kernel and rows_link_kernel is one function template in
+    one shared header.  Exempt by name, each for a reason written at the place: l1_knn_kernel (k_query.hip) and rows_assign_kernel
+    (k_assign.hip) keep a copy of the tile because the shared one measured slower there (profiles/sad_tile/README.md);
+    k_search.hip's per-pair kernel (pair_min_kernel) and l1_matrix_kernel in kernels.hip.h are contractions of their own."""
+    import build_ext
+    csrc = os.path.join(ROOT, 'dctdomain_amd', 'csrc')
+    shared = [h for h in build_ext.HEADERS if os.path.dirname(h) == csrc]
+    code = {p: '\n'.join(line.split('//', 1)[0] for line in open(p).read().splitlines())
+            for p in shared + [os.path.join(csrc, u) for u in build_ext.UNITS]}
+    holders = [p for p, text in code.items() if re.search(r'\bvoid sad_tile\(', text)]
+    assert len(holders) == 1 and holders[0] in shared and holders[0] in build_ext.kernel_sources()
+    tile = holders[0]
+    exempt = {'k_search.hip': 'pair_min_kernel', 'kernels.hip.h': 'l1_matrix_kernel', 'k_query.hip': 'l1_knn_kernel',
+              'k_assign.hip': 'rows_assign_kernel'}
+    assert sorted(p for p, text in code.items() if '__builtin_amdgcn_sad_u8' in text) == sorted([tile] + [os.path.join(csrc, f) for f in exempt])
+    for name, kernel in exempt.items():
+        text = code[os.path.join(csrc, name)]
+        assert ' void %s(' % kernel in text
+        if name != 'kernels.hip.h':
+            assert 'sad_tile<' not in text
+            # the intrinsic lies inside the named kernel's body and nowhere else in the file
+            body = text[text.index(' void %s(' % kernel):]
+            assert body[:body.index('\n}\n')].count('__builtin_amdgcn_sad_u8') == text.count('__builtin_amdgcn_sad_u8')
+    for name in ('k_query.hip', 'k_assign.hip'):               # the copies say that they are copies, and of what
+        assert 'copy of its own of sad_tile<' in open(os.path.join(csrc, name)).read()
+        # ... with the header's layout numbers, not numbers of their own
+        assert 'using dctfp::kSadLD;' in code[os.path.join(csrc, name)] and 'sad_b_slot(r)' in code[os.path.join(csrc, name)]
+        assert not re.search(r'constexpr int k\w*(Tile|KC|LD) = \d', code[os.path.join(csrc, name)])
+    # l1_matrix_kernel's use lies inside its own body: the intrinsic is gone from kernels.hip.h behind the next kernel's head
+    text = code[os.path.join(csrc, 'kernels.hip.h')]
+    assert text.index(' void l1_matrix_kernel(') < text.index('__builtin_amdgcn_sad_u8') <= text.rindex('__builtin_amdgcn_sad_u8') \
+        < text.index(' void l1_matrix16_kernel(')
+    inc = '#include "%s"' % os.path.basename(tile)
+    for unit, call in (('kernels.hip.h', 'sad_tile<16>('), ('k_protein.hip', 'sad_tile<16>('), ('k_cluster.hip', 'sad_tile<ALIGN>(')):
+        assert inc in code[os.path.join(csrc, unit)] and code[os.path.join(csrc, unit)].count(call) == 1
+    # the constants and the choice of a fill are the header's too
+    for name in ('kSadTile = 128', 'kSadKC = 32', 'kSadLD = kSadKC + 4', 'int sad_tile_align(', 'uint64_t sad_keep_mask('):
+        assert sum(name in text for text in code.values()) == 1 and name in code[tile]
+    for unit in ('k_cluster.hip', 'k_assign.hip', 'dctfp.hip'):
+        text = code[os.path.join(csrc, unit)]
+        assert 'sad_tile_align(a, lda, b, ldb)' in text and '& 15u) == 0 &&' not in text
+
+
 def test_link_kernels_touch_the_forest_through_agent_scope_atomics_only():
     """The access rule of the kernels that link, read off the source: no plain load or store of `parent` in k_cluster.hip outside
     the launch that only reads it (labels_kernel)."""
