@@ -65,6 +65,10 @@ EXPORTS = ('dctfp_version', 'dctfp_last_error', 'dctfp_create', 'dctfp_destroy',
            'dctfp_greedy_decide', 'dctfp_greedy_tri_mark', 'dctfp_greedy_pairs_mark',
            'dctfp_rows_link', 'dctfp_rows_assign', 'dctfp_tri_nearest', 'dctfp_tree_hook')
 
+#: what the five exports that scan an L1 tile start with: the context, then the library's TriTile (tile, n_rows, n_cols, ld, row0, col0,
+#: row_empty, col_empty, cap, bound) -- ``similarity._tri_filter_args`` makes the values
+_TRI_TILE = [C.c_void_p, C.c_void_p] + [C.c_int64] * 5 + [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32]
+
 
 def load(path: str = None):
     """Loads libdctfp.so; raises ImportError when it has not been built.  ``path`` loads another
@@ -183,31 +187,25 @@ def _configure(lib):
                                           C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
         lib.dctfp_sim_lines.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_void_p,
                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-        lib.dctfp_tri_filter_count.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_void_p,
-                                               C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
-        lib.dctfp_tri_filter_fill.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_void_p,
-                                              C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.dctfp_tri_filter_count.argtypes = _TRI_TILE + [C.c_void_p, C.c_void_p]
+        lib.dctfp_tri_filter_fill.argtypes = _TRI_TILE + [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
         lib.dctfp_pair_lines.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                          C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
         lib.dctfp_pair_domain_lines.argtypes = [C.c_void_p, C.c_int64] + [C.c_void_p] * 8 + [C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
                                                 C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
-        lib.dctfp_tri_link.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_void_p,
-                                       C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]
+        lib.dctfp_tri_link.argtypes = _TRI_TILE + [C.c_void_p, C.c_int64, C.c_void_p]
         lib.dctfp_link_pairs.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]
         lib.dctfp_cluster_labels.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
         lib.dctfp_rows_link.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int32,
                                         C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]
         lib.dctfp_rows_assign.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p,
                                           C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]
-        lib.dctfp_tri_nearest.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_void_p,
-                                          C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
+        lib.dctfp_tri_nearest.argtypes = _TRI_TILE + [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
         lib.dctfp_tree_hook.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
                                         C.c_void_p, C.c_int64, C.c_void_p]
         lib.dctfp_greedy_decide.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.c_void_p,
                                             C.c_void_p]
-        lib.dctfp_greedy_tri_mark.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_void_p,
-                                              C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64,
-                                              C.c_int32, C.c_void_p]
+        lib.dctfp_greedy_tri_mark.argtypes = _TRI_TILE + [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_void_p]
         lib.dctfp_greedy_pairs_mark.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
                                                 C.c_int64, C.c_int32, C.c_void_p]
         lib.dctfp_l1_knn.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int32,

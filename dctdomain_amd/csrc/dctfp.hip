@@ -25,6 +25,7 @@
 
 #include "launch.h"   // (kernels.hip.h, the parameter blocks and the launchers of the kernel families built in their own units)
 #include "reccut_kernel.hip.h"   // (CutJob, table sizes; the kernel itself is instantiated in k_reccut.hip)
+#include "tri_walk.hip.h"        // (TriTile; the kernels that scan one are in k_filter / k_cluster / k_greedy / k_tree.hip)
 
 using namespace dctfp;
 using namespace dctfp_host;
@@ -2750,19 +2751,34 @@ int dctfp_sim_lines(dctfp_ctx* ctx, const int32_t* mn, const int32_t* last, int6
     return DCTFP_OK;
 } DCTFP_GUARD("dctfp_sim_lines")
 
+// What the five exports that scan a tile (count, fill, link, mark, nearest) ask of it; `name` = the export, for the message.
+static int check_tri_tile(const char* name, const TriTile& t) {
+    if (t.n_rows < 0 || t.n_cols < 0 || t.ld < t.n_cols || t.row0 < 0 || t.col0 < 0 || t.cap < 0 || t.bound < -1 || t.bound > t.cap ||
+        (reinterpret_cast<uintptr_t>(t.tile) & 3u) != 0)
+        return fail(DCTFP_ERR_INVALID, "%s: bad shape, bound or alignment", name);
+    return DCTFP_OK;
+}
+
+// ... and of the node arrays beside it: every (i, j) a kernel can form lies inside the tile, so the nodes are bounded here, on the
+// host, and not on the device.
+static int check_tri_nodes(const char* name, const TriTile& t, int64_t n_nodes) {
+    if (n_nodes < 0 || t.row0 + t.n_rows > n_nodes || t.col0 + t.n_cols > n_nodes)
+        return fail(DCTFP_ERR_INVALID, "%s: the tile names proteins outside the nodes", name);
+    return DCTFP_OK;
+}
+
 int dctfp_tri_filter_count(dctfp_ctx* ctx, const int32_t* tile, int64_t n_rows, int64_t n_cols, int64_t ld, int64_t row0, int64_t col0,
                            const uint8_t* row_empty, const uint8_t* col_empty, int32_t cap, int32_t bound, int32_t* out_count,
                            void* stream_v) try {
     if (!ctx || !tile || !out_count) return fail(DCTFP_ERR_INVALID, "dctfp_tri_filter_count: NULL argument");
     std::lock_guard<std::mutex> lock(ctx->mu);
-    if (n_rows < 0 || n_cols < 0 || ld < n_cols || row0 < 0 || col0 < 0 || cap < 0 || bound < -1 || bound > cap ||
-        (reinterpret_cast<uintptr_t>(tile) & 3u) != 0)
-        return fail(DCTFP_ERR_INVALID, "dctfp_tri_filter_count: bad shape, bound or alignment");
+    const TriTile t{tile, n_rows, n_cols, ld, row0, col0, row_empty, col_empty, cap, bound};
+    RC_TRY(check_tri_tile("dctfp_tri_filter_count", t));
     if (row0 + n_rows > 0x7fffffff || col0 + n_cols > 0x7fffffff)
         return fail(DCTFP_ERR_LIMIT, "dctfp_tri_filter_count: protein indices above 2^31 - 1");
-    if (n_rows == 0) return DCTFP_OK;
+    if (n_rows == 0) return DCTFP_OK;   // (n_cols == 0 still launches: the counts are zeros, written)
     HIP_TRY(hipSetDevice(ctx->device));
-    launch_tri_filter_count(tile, n_rows, n_cols, ld, row0, col0, row_empty, col_empty, cap, bound, out_count, (hipStream_t)stream_v);
+    launch_tri_filter_count(t, out_count, (hipStream_t)stream_v);
     HIP_TRY(hipGetLastError());
     return DCTFP_OK;
 } DCTFP_GUARD("dctfp_tri_filter_count")
@@ -2772,15 +2788,14 @@ int dctfp_tri_filter_fill(dctfp_ctx* ctx, const int32_t* tile, int64_t n_rows, i
                           int64_t out_len, int32_t* out_i, int32_t* out_j, void* stream_v) try {
     if (!ctx || !tile || !offsets || !out_i || !out_j) return fail(DCTFP_ERR_INVALID, "dctfp_tri_filter_fill: NULL argument");
     std::lock_guard<std::mutex> lock(ctx->mu);
-    if (n_rows < 0 || n_cols < 0 || ld < n_cols || row0 < 0 || col0 < 0 || cap < 0 || bound < -1 || bound > cap || out_len < 0 ||
-        (reinterpret_cast<uintptr_t>(tile) & 3u) != 0)
-        return fail(DCTFP_ERR_INVALID, "dctfp_tri_filter_fill: bad shape, bound or alignment");
+    const TriTile t{tile, n_rows, n_cols, ld, row0, col0, row_empty, col_empty, cap, bound};
+    RC_TRY(check_tri_tile("dctfp_tri_filter_fill", t));
+    if (out_len < 0) return fail(DCTFP_ERR_INVALID, "dctfp_tri_filter_fill: negative out_len");
     if (row0 + n_rows > 0x7fffffff || col0 + n_cols > 0x7fffffff)
         return fail(DCTFP_ERR_LIMIT, "dctfp_tri_filter_fill: protein indices above 2^31 - 1");
     if (n_rows == 0 || n_cols == 0 || out_len == 0) return DCTFP_OK;
     HIP_TRY(hipSetDevice(ctx->device));
-    launch_tri_filter_fill(tile, n_rows, n_cols, ld, row0, col0, row_empty, col_empty, cap, bound, offsets, out_len, out_i, out_j,
-                           (hipStream_t)stream_v);
+    launch_tri_filter_fill(t, offsets, out_len, out_i, out_j, (hipStream_t)stream_v);
     HIP_TRY(hipGetLastError());
     return DCTFP_OK;
 } DCTFP_GUARD("dctfp_tri_filter_fill")
@@ -2825,15 +2840,13 @@ int dctfp_tri_link(dctfp_ctx* ctx, const int32_t* tile, int64_t n_rows, int64_t 
                    void* stream_v) try {
     if (!ctx || !tile || !parent) return fail(DCTFP_ERR_INVALID, "dctfp_tri_link: NULL argument");
     std::lock_guard<std::mutex> lock(ctx->mu);
-    if (n_rows < 0 || n_cols < 0 || ld < n_cols || row0 < 0 || col0 < 0 || cap < 0 || bound < -1 || bound > cap || n_nodes < 0 ||
-        (reinterpret_cast<uintptr_t>(tile) & 3u) != 0)
-        return fail(DCTFP_ERR_INVALID, "dctfp_tri_link: bad shape, bound or alignment");
+    const TriTile t{tile, n_rows, n_cols, ld, row0, col0, row_empty, col_empty, cap, bound};
+    RC_TRY(check_tri_tile("dctfp_tri_link", t));
     if (n_nodes > 0x7fffffff) return fail(DCTFP_ERR_LIMIT, "dctfp_tri_link: more than 2^31 - 1 nodes");
-    // (every (i, j) the kernel can form lies inside the tile: bounded here, not on the device)
-    if (row0 + n_rows > n_nodes || col0 + n_cols > n_nodes) return fail(DCTFP_ERR_INVALID, "dctfp_tri_link: the tile names proteins outside parent");
+    RC_TRY(check_tri_nodes("dctfp_tri_link", t, n_nodes));
     if (n_rows == 0 || n_cols == 0 || n_nodes == 0) return DCTFP_OK;
     HIP_TRY(hipSetDevice(ctx->device));
-    launch_tri_link(tile, n_rows, n_cols, ld, row0, col0, row_empty, col_empty, cap, bound, parent, (hipStream_t)stream_v);
+    launch_tri_link(t, parent, (hipStream_t)stream_v);
     HIP_TRY(hipGetLastError());
     return DCTFP_OK;
 } DCTFP_GUARD("dctfp_tri_link")
@@ -2906,14 +2919,13 @@ int dctfp_tri_nearest(dctfp_ctx* ctx, const int32_t* tile, int64_t n_rows, int64
     if (n_nodes > (int64_t)1 << 24 || cap > 0x7fff) return fail(DCTFP_ERR_LIMIT, "dctfp_tri_nearest: more than 2^24 nodes or a cap above 32767");
     if (!ctx || !tile || !comp || !best) return fail(DCTFP_ERR_INVALID, "dctfp_tri_nearest: NULL argument");
     std::lock_guard<std::mutex> lock(ctx->mu);
-    if (n_rows < 0 || n_cols < 0 || ld < n_cols || row0 < 0 || col0 < 0 || cap < 0 || bound < -1 || bound > cap || n_nodes < 0 ||
-        (reinterpret_cast<uintptr_t>(tile) & 3u) != 0 || (reinterpret_cast<uintptr_t>(best) & 7u) != 0)
-        return fail(DCTFP_ERR_INVALID, "dctfp_tri_nearest: bad shape, bound or alignment");
-    // (every (i, j) the kernel can form lies inside the tile: bounded here, not on the device)
-    if (row0 + n_rows > n_nodes || col0 + n_cols > n_nodes) return fail(DCTFP_ERR_INVALID, "dctfp_tri_nearest: the tile names proteins outside the nodes");
+    const TriTile t{tile, n_rows, n_cols, ld, row0, col0, row_empty, col_empty, cap, bound};
+    RC_TRY(check_tri_tile("dctfp_tri_nearest", t));
+    if ((reinterpret_cast<uintptr_t>(best) & 7u) != 0) return fail(DCTFP_ERR_INVALID, "dctfp_tri_nearest: best is not 8-byte aligned");
+    RC_TRY(check_tri_nodes("dctfp_tri_nearest", t, n_nodes));
     if (n_rows == 0 || n_cols == 0 || n_nodes == 0) return DCTFP_OK;
     HIP_TRY(hipSetDevice(ctx->device));
-    launch_tri_nearest(tile, n_rows, n_cols, ld, row0, col0, row_empty, col_empty, cap, bound, comp, best, n_nodes, (hipStream_t)stream_v);
+    launch_tri_nearest(t, comp, best, n_nodes, (hipStream_t)stream_v);
     HIP_TRY(hipGetLastError());
     return DCTFP_OK;
 } DCTFP_GUARD("dctfp_tri_nearest")
@@ -2951,17 +2963,15 @@ int dctfp_greedy_tri_mark(dctfp_ctx* ctx, const int32_t* tile, int64_t n_rows, i
                           int32_t* blocked, int64_t n_nodes, int64_t range_end, int32_t next_round, void* stream_v) try {
     if (!ctx || !tile || !assign || !state || !blocked) return fail(DCTFP_ERR_INVALID, "dctfp_greedy_tri_mark: NULL argument");
     std::lock_guard<std::mutex> lock(ctx->mu);
-    if (n_rows < 0 || n_cols < 0 || ld < n_cols || row0 < 0 || col0 < 0 || cap < 0 || bound < -1 || bound > cap || n_nodes < 0 ||
-        range_end < 0 || next_round < 1 || (reinterpret_cast<uintptr_t>(tile) & 3u) != 0)
-        return fail(DCTFP_ERR_INVALID, "dctfp_greedy_tri_mark: bad shape, bound, round or alignment");
+    const TriTile t{tile, n_rows, n_cols, ld, row0, col0, row_empty, col_empty, cap, bound};
+    RC_TRY(check_tri_tile("dctfp_greedy_tri_mark", t));
+    if (range_end < 0 || next_round < 1) return fail(DCTFP_ERR_INVALID, "dctfp_greedy_tri_mark: bad range or round");
     if (n_nodes > 0x7fffffff) return fail(DCTFP_ERR_LIMIT, "dctfp_greedy_tri_mark: more than 2^31 - 1 nodes");
-    // (every (i, j) the kernel can form lies inside the tile, every stamp below range_end: bounded here, not on the device)
-    if (row0 + n_rows > n_nodes || col0 + n_cols > n_nodes || range_end > n_nodes)
-        return fail(DCTFP_ERR_INVALID, "dctfp_greedy_tri_mark: the tile or the range names proteins outside the nodes");
+    RC_TRY(check_tri_nodes("dctfp_greedy_tri_mark", t, n_nodes));
+    if (range_end > n_nodes) return fail(DCTFP_ERR_INVALID, "dctfp_greedy_tri_mark: the range (every stamp lies below it) ends outside the nodes");
     if (n_rows == 0 || n_cols == 0 || n_nodes == 0) return DCTFP_OK;
     HIP_TRY(hipSetDevice(ctx->device));
-    launch_greedy_tri_mark(tile, n_rows, n_cols, ld, row0, col0, row_empty, col_empty, cap, bound, assign, state, blocked, range_end, next_round,
-                           (hipStream_t)stream_v);
+    launch_greedy_tri_mark(t, assign, state, blocked, range_end, next_round, (hipStream_t)stream_v);
     HIP_TRY(hipGetLastError());
     return DCTFP_OK;
 } DCTFP_GUARD("dctfp_greedy_tri_mark")

@@ -24,79 +24,32 @@
 #include "launch.h"
 #include "sad_tile.hip.h"
 #include "tri_walk.hip.h"
+#include "union_find.hip.h"   // the forest: uf_find / uf_union, kLinkThreads
 
 namespace {
 
 using dctfp::kSadLds;
 using dctfp::kSadTile;
 
-constexpr int kLinkThreads = 256;
-
-__device__ inline int32_t uf_load(int32_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-
-// parent[x] as the forest allows it: 0 <= parent[x] <= x.  Anything else (a caller's array that is no forest) reads as "root",
-// so that a walk only ever moves to smaller, non-negative indices: never an access outside parent[0 .. x].
-__device__ inline int32_t uf_parent(int32_t* parent, int32_t x) {
-    const int32_t p = uf_load(parent + x);
-    return (uint32_t)p <= (uint32_t)x ? p : x;
-}
-
-// The root above x (as this wave sees it), halving the path on the way: parent[x] = min(parent[x], grandparent).
-__device__ inline int32_t uf_find(int32_t* parent, int32_t x) {
-    int32_t p = uf_parent(parent, x);
-    while (p != x) {
-        const int32_t g = uf_parent(parent, p);
-        if (g != p) __hip_atomic_fetch_min(parent + x, g, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        x = p;
-        p = g;
-    }
-    return x;
-}
-
-// Joins the components of a and b.  Two endpoints already under one root cost reads only (and the halving of a long path).
-__device__ inline void uf_union(int32_t* parent, int32_t a, int32_t b) {
-    for (;;) {
-        a = uf_find(parent, a);
-        b = uf_find(parent, b);
-        if (a == b) return;
-        const int32_t hi = max(a, b), lo = min(a, b);
-        int32_t seen = hi;
-        if (__hip_atomic_compare_exchange_strong(parent + hi, &seen, lo, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) return;
-        if ((uint32_t)seen >= (uint32_t)hi) return;   // (no forest: see uf_parent)
-        a = seen;                                     // hi got a parent meanwhile: go on from there
-        b = lo;
-    }
-}
-
-#ifdef DCTFP_UNION_FIND_ONLY   // k_tree.hip: the forest's routines above and none of the kernels below
-}  // namespace
-#else
-
 // tri_filter_count_kernel's walk (one workgroup per row at a time, 16-byte loads, filter_quad).  Row r is protein i = row0 + r:
 // a step without survivors -- the common case -- costs what the count's step costs, the ballots show it and the wave moves on;
 // in a step with some, one lane finds i's root (once per step, carried to the next as the place to start from) and only the
 // lanes with a surviving entry find j and hook.  The host has checked row0 + n_rows <= n_nodes and col0 + n_cols <= n_nodes.
-__global__ __launch_bounds__(kFilterThreads) void tri_link_kernel(const int32_t* __restrict__ tile, int64_t n_rows, int64_t n_cols, int64_t ld,
-                                                                   int64_t row0, int64_t col0, const uint8_t* __restrict__ row_empty,
-                                                                   const uint8_t* __restrict__ col_empty, int32_t cap, int32_t bound,
-                                                                   int32_t* parent) {
+__global__ __launch_bounds__(kFilterThreads) void tri_link_kernel(const TriTile t, int32_t* parent) {
     const int tid = threadIdx.x, lane = tid & 63;
-    for (int64_t r = blockIdx.x; r < n_rows; r += gridDim.x) {
-        const int32_t* row = tile + r * ld;
-        const int shift = row_shift(row);
-        const int64_t c_min = first_column(row0, r, col0);
-        const bool row_is_empty = row_empty && row_empty[r];
-        int32_t above = (int32_t)(row0 + r);   // i, or an ancestor of i (wave-uniform)
-        for (int64_t v0 = (c_min + shift) & ~(int64_t)3; v0 < n_cols + shift; v0 += kFilterStep) {
+    for (int64_t r = blockIdx.x; r < t.n_rows; r += gridDim.x) {
+        const TriRow w = tri_row(t, r);
+        int32_t above = (int32_t)(t.row0 + r);   // i, or an ancestor of i (wave-uniform)
+        for (int64_t v0 = tri_begin(w); v0 < t.n_cols + w.shift; v0 += kFilterStep) {
             const int64_t v = v0 + 4 * tid;
-            const Quad q = filter_quad(row, v, shift, c_min, n_cols, row_is_empty, col_empty, cap, bound);
+            const Quad q = filter_quad(t, w, v, t.n_cols);
             if (__ballot(q.keep[0] || q.keep[1] || q.keep[2] || q.keep[3]) == 0) continue;
             int32_t root = 0;
             if (lane == 0) root = uf_find(parent, above);
             above = __shfl(root, 0);
 #pragma unroll
             for (int e = 0; e < 4; ++e)
-                if (q.keep[e]) uf_union(parent, above, (int32_t)(col0 + v - shift + e));
+                if (q.keep[e]) uf_union(parent, above, (int32_t)(t.col0 + v - w.shift + e));
         }
     }
 }
@@ -174,10 +127,8 @@ unsigned link_grid(int64_t n) { return (unsigned)((n + kLinkThreads - 1) / kLink
 
 namespace dctfp_host {
 
-void launch_tri_link(const int32_t* tile, int64_t n_rows, int64_t n_cols, int64_t ld, int64_t row0, int64_t col0, const uint8_t* row_empty,
-                     const uint8_t* col_empty, int32_t cap, int32_t bound, int32_t* parent, hipStream_t stream) {
-    hipLaunchKernelGGL(tri_link_kernel, dim3(filter_grid(n_rows)), dim3(kFilterThreads), 0, stream, tile, n_rows, n_cols, ld, row0, col0,
-                       row_empty, col_empty, cap, bound, parent);
+void launch_tri_link(const TriTile& t, int32_t* parent, hipStream_t stream) {
+    hipLaunchKernelGGL(tri_link_kernel, dim3(filter_grid(t.n_rows)), dim3(kFilterThreads), 0, stream, t, parent);
 }
 
 void launch_link_pairs(const int32_t* pi, const int32_t* pj, int64_t n_pairs, int32_t* parent, int64_t n_nodes, hipStream_t stream) {
@@ -199,4 +150,3 @@ void launch_cluster_labels(int32_t* parent, int64_t n_nodes, int32_t* labels, hi
 
 }  // namespace dctfp_host
 
-#endif  // DCTFP_UNION_FIND_ONLY

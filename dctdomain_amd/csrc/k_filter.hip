@@ -8,7 +8,7 @@
 // No global atomic decides a position: a row's survivors go out in column order within one workgroup, rows at their offsets.
 #define DCTFP_TEMPLATES_ONLY
 #include "launch.h"
-#include "tri_walk.hip.h"   // the row walk and filter_quad, shared with k_cluster.hip
+#include "tri_walk.hip.h"   // TriTile, the row walk and filter_quad
 
 namespace {
 
@@ -18,21 +18,14 @@ constexpr int kScoreRows = 17002;
 
 // out_count[r] = #survivors of row r.  One workgroup per row (rows loop over the grid), 1024 columns per step, a ballot and a
 // population count per entry of the quad, the waves' sums through LDS.
-__global__ __launch_bounds__(kFilterThreads) void tri_filter_count_kernel(const int32_t* __restrict__ tile, int64_t n_rows, int64_t n_cols,
-                                                                           int64_t ld, int64_t row0, int64_t col0,
-                                                                           const uint8_t* __restrict__ row_empty,
-                                                                           const uint8_t* __restrict__ col_empty, int32_t cap, int32_t bound,
-                                                                           int32_t* __restrict__ out_count) {
+__global__ __launch_bounds__(kFilterThreads) void tri_filter_count_kernel(const TriTile t, int32_t* __restrict__ out_count) {
     __shared__ int32_t wsum[kFilterWaves];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    for (int64_t r = blockIdx.x; r < n_rows; r += gridDim.x) {
-        const int32_t* row = tile + r * ld;
-        const int shift = row_shift(row);
-        const int64_t c_min = first_column(row0, r, col0);
-        const bool row_is_empty = row_empty && row_empty[r];
+    for (int64_t r = blockIdx.x; r < t.n_rows; r += gridDim.x) {
+        const TriRow w = tri_row(t, r);
         int32_t n = 0;   // (wave-uniform)
-        for (int64_t v0 = (c_min + shift) & ~(int64_t)3; v0 < n_cols + shift; v0 += kFilterStep) {
-            const Quad q = filter_quad(row, v0 + 4 * tid, shift, c_min, n_cols, row_is_empty, col_empty, cap, bound);
+        for (int64_t v0 = tri_begin(w); v0 < t.n_cols + w.shift; v0 += kFilterStep) {
+            const Quad q = filter_quad(t, w, v0 + 4 * tid, t.n_cols);
 #pragma unroll
             for (int e = 0; e < 4; ++e) n += __popcll(__ballot(q.keep[e]));
         }
@@ -40,7 +33,7 @@ __global__ __launch_bounds__(kFilterThreads) void tri_filter_count_kernel(const 
         __syncthreads();
         if (tid == 0) {
             int32_t s = 0;
-            for (int w = 0; w < kFilterWaves; ++w) s += wsum[w];
+            for (int k = 0; k < kFilterWaves; ++k) s += wsum[k];
             out_count[r] = s;
         }
         __syncthreads();   // (wsum is rewritten for the next row)
@@ -51,26 +44,19 @@ __global__ __launch_bounds__(kFilterThreads) void tri_filter_count_kernel(const 
 // as the count; a thread's place within a step = the survivors of the lanes below it (ballots) + of the waves below it (LDS,
 // double buffered: one barrier per step) + of its own earlier entries.  Nothing is written at or beyond out_len, nor beyond
 // the row's range.
-__global__ __launch_bounds__(kFilterThreads) void tri_filter_fill_kernel(const int32_t* __restrict__ tile, int64_t n_rows, int64_t n_cols,
-                                                                          int64_t ld, int64_t row0, int64_t col0,
-                                                                          const uint8_t* __restrict__ row_empty,
-                                                                          const uint8_t* __restrict__ col_empty, int32_t cap, int32_t bound,
-                                                                          const int64_t* __restrict__ offsets, int64_t out_len,
+__global__ __launch_bounds__(kFilterThreads) void tri_filter_fill_kernel(const TriTile t, const int64_t* __restrict__ offsets, int64_t out_len,
                                                                           int32_t* __restrict__ out_i, int32_t* __restrict__ out_j) {
     __shared__ int32_t wtot[2][kFilterWaves];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const unsigned long long below = (1ull << lane) - 1;
     int64_t step = 0;   // (over all rows of this workgroup: the LDS buffers alternate)
-    for (int64_t r = blockIdx.x; r < n_rows; r += gridDim.x) {
-        const int32_t* row = tile + r * ld;
-        const int shift = row_shift(row);
-        const int64_t c_min = first_column(row0, r, col0);
-        const bool row_is_empty = row_empty && row_empty[r];
+    for (int64_t r = blockIdx.x; r < t.n_rows; r += gridDim.x) {
+        const TriRow w = tri_row(t, r);
         const int64_t base = offsets[r], len = min(offsets[r + 1], out_len) - base;
         int64_t done = 0;
-        for (int64_t v0 = (c_min + shift) & ~(int64_t)3; v0 < n_cols + shift && done < len; v0 += kFilterStep, ++step) {
+        for (int64_t v0 = tri_begin(w); v0 < t.n_cols + w.shift && done < len; v0 += kFilterStep, ++step) {
             const int64_t v = v0 + 4 * tid;
-            const Quad q = filter_quad(row, v, shift, c_min, n_cols, row_is_empty, col_empty, cap, bound);
+            const Quad q = filter_quad(t, w, v, t.n_cols);
             int32_t before = 0, mine = 0;
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
@@ -82,18 +68,18 @@ __global__ __launch_bounds__(kFilterThreads) void tri_filter_fill_kernel(const i
             if (lane == 0) wtot[buf][wave] = mine;
             __syncthreads();
             int32_t total = 0;
-            for (int w = 0; w < kFilterWaves; ++w) {
-                const int32_t t = wtot[buf][w];
-                if (w < wave) before += t;
-                total += t;
+            for (int k = 0; k < kFilterWaves; ++k) {
+                const int32_t n = wtot[buf][k];
+                if (k < wave) before += n;
+                total += n;
             }
             int64_t pos = done + before;
 #pragma unroll
             for (int e = 0; e < 4; ++e)
                 if (q.keep[e]) {
                     if (pos < len) {
-                        out_i[base + pos] = (int32_t)(row0 + r);
-                        out_j[base + pos] = (int32_t)(col0 + v - shift + e);
+                        out_i[base + pos] = (int32_t)(t.row0 + r);
+                        out_j[base + pos] = (int32_t)(t.col0 + v - w.shift + e);
                     }
                     ++pos;
                 }
@@ -159,18 +145,12 @@ __global__ __launch_bounds__(kLineThreads) void pair_lines_kernel(int64_t n_line
 
 namespace dctfp_host {
 
-void launch_tri_filter_count(const int32_t* tile, int64_t n_rows, int64_t n_cols, int64_t ld, int64_t row0, int64_t col0,
-                             const uint8_t* row_empty, const uint8_t* col_empty, int32_t cap, int32_t bound, int32_t* out_count,
-                             hipStream_t stream) {
-    hipLaunchKernelGGL(tri_filter_count_kernel, dim3(filter_grid(n_rows)), dim3(kFilterThreads), 0, stream, tile, n_rows, n_cols, ld, row0, col0,
-                       row_empty, col_empty, cap, bound, out_count);
+void launch_tri_filter_count(const TriTile& t, int32_t* out_count, hipStream_t stream) {
+    hipLaunchKernelGGL(tri_filter_count_kernel, dim3(filter_grid(t.n_rows)), dim3(kFilterThreads), 0, stream, t, out_count);
 }
 
-void launch_tri_filter_fill(const int32_t* tile, int64_t n_rows, int64_t n_cols, int64_t ld, int64_t row0, int64_t col0,
-                            const uint8_t* row_empty, const uint8_t* col_empty, int32_t cap, int32_t bound, const int64_t* offsets,
-                            int64_t out_len, int32_t* out_i, int32_t* out_j, hipStream_t stream) {
-    hipLaunchKernelGGL(tri_filter_fill_kernel, dim3(filter_grid(n_rows)), dim3(kFilterThreads), 0, stream, tile, n_rows, n_cols, ld, row0, col0,
-                       row_empty, col_empty, cap, bound, offsets, out_len, out_i, out_j);
+void launch_tri_filter_fill(const TriTile& t, const int64_t* offsets, int64_t out_len, int32_t* out_i, int32_t* out_j, hipStream_t stream) {
+    hipLaunchKernelGGL(tri_filter_fill_kernel, dim3(filter_grid(t.n_rows)), dim3(kFilterThreads), 0, stream, t, offsets, out_len, out_i, out_j);
 }
 
 void launch_pair_domain_lines(int64_t n_lines, const int32_t* pi, const int32_t* pj, const int32_t* mn, const int32_t* last, const int32_t* la,

@@ -62,29 +62,23 @@ __global__ __launch_bounds__(kGreedyThreads) void greedy_decide_kernel(int32_t* 
 // Row r is protein i = row0 + r.  `range_end` = i1 of the range the rows belong to: an undecided row looks at columns j < i1
 // only (a node beyond the range is decided in a later range, after every representative of this one has marked).  The host
 // has checked row0 + n_rows <= n_nodes and col0 + n_cols <= n_nodes.
-__global__ __launch_bounds__(kFilterThreads) void greedy_tri_mark_kernel(const int32_t* __restrict__ tile, int64_t n_rows, int64_t n_cols, int64_t ld,
-                                                                         int64_t row0, int64_t col0, const uint8_t* __restrict__ row_empty,
-                                                                         const uint8_t* __restrict__ col_empty, int32_t cap, int32_t bound,
-                                                                         int32_t* assign, const int32_t* __restrict__ state, int32_t* blocked,
-                                                                         int64_t range_end, int32_t next_round) {
+__global__ __launch_bounds__(kFilterThreads) void greedy_tri_mark_kernel(const TriTile t, int32_t* assign, const int32_t* __restrict__ state,
+                                                                         int32_t* blocked, int64_t range_end, int32_t next_round) {
     const int tid = threadIdx.x;
-    for (int64_t r = blockIdx.x; r < n_rows; r += gridDim.x) {
-        const int64_t i = row0 + r;
+    for (int64_t r = blockIdx.x; r < t.n_rows; r += gridDim.x) {
+        const int64_t i = t.row0 + r;
         const int32_t s = state[i];
         if (s != kNewRep && s != kUndecided) continue;
         const bool marks = s == kNewRep;
-        const int64_t cols = marks ? n_cols : min(n_cols, max((int64_t)0, range_end - col0));
-        const int32_t* row = tile + r * ld;
-        const int shift = row_shift(row);
-        const int64_t c_min = first_column(row0, r, col0);
-        const bool row_is_empty = row_empty && row_empty[r];
-        for (int64_t v0 = (c_min + shift) & ~(int64_t)3; v0 < cols + shift; v0 += kFilterStep) {
+        const int64_t cols = marks ? t.n_cols : min(t.n_cols, max((int64_t)0, range_end - t.col0));
+        const TriRow w = tri_row(t, r);
+        for (int64_t v0 = tri_begin(w); v0 < cols + w.shift; v0 += kFilterStep) {
             const int64_t v = v0 + 4 * tid;
-            const Quad q = filter_quad(row, v, shift, c_min, cols, row_is_empty, col_empty, cap, bound);
+            const Quad q = filter_quad(t, w, v, cols);
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
                 if (!q.keep[e]) continue;
-                const int64_t j = col0 + v - shift + e;
+                const int64_t j = t.col0 + v - w.shift + e;
                 if (marks) lower(assign, j, (int32_t)i);
                 else blocked[j] = next_round;
             }
@@ -119,11 +113,10 @@ void launch_greedy_decide(int32_t* assign, int32_t* state, const int32_t* blocke
                        undecided);
 }
 
-void launch_greedy_tri_mark(const int32_t* tile, int64_t n_rows, int64_t n_cols, int64_t ld, int64_t row0, int64_t col0, const uint8_t* row_empty,
-                            const uint8_t* col_empty, int32_t cap, int32_t bound, int32_t* assign, const int32_t* state, int32_t* blocked,
-                            int64_t range_end, int32_t next_round, hipStream_t stream) {
-    hipLaunchKernelGGL(greedy_tri_mark_kernel, dim3(filter_grid(n_rows)), dim3(kFilterThreads), 0, stream, tile, n_rows, n_cols, ld, row0, col0,
-                       row_empty, col_empty, cap, bound, assign, state, blocked, range_end, next_round);
+void launch_greedy_tri_mark(const TriTile& t, int32_t* assign, const int32_t* state, int32_t* blocked, int64_t range_end, int32_t next_round,
+                            hipStream_t stream) {
+    hipLaunchKernelGGL(greedy_tri_mark_kernel, dim3(filter_grid(t.n_rows)), dim3(kFilterThreads), 0, stream, t, assign, state, blocked, range_end,
+                       next_round);
 }
 
 void launch_greedy_pairs_mark(const int32_t* pi, const int32_t* pj, int64_t n_pairs, int32_t* assign, const int32_t* state, int32_t* blocked,

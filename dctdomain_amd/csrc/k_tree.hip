@@ -30,8 +30,10 @@
 // each have chosen the edge e_t that leads to the next.  e_t also leaves C_(t+1), whose choice e_(t+1) is its lightest: e_(t+1)
 // <= e_t.  Around the cycle all are equal, and equal keys are the same edge (i, j): k = 2 and both components chose one edge.
 // That edge is appended once: the component with the higher label skips it when best of the other holds the identical key.
-#define DCTFP_UNION_FIND_ONLY
-#include "k_cluster.hip"   // uf_find / uf_union (and launch.h, tri_walk.hip.h); none of its kernels
+#define DCTFP_TEMPLATES_ONLY
+#include "launch.h"
+#include "tri_walk.hip.h"
+#include "union_find.hip.h"   // the forest of k_cluster.hip: uf_union, kLinkThreads
 
 namespace {
 
@@ -56,10 +58,7 @@ __device__ inline void lower_best(unsigned long long* best, int32_t c, int64_t n
 // the row's own shift: LDS slot s stands for column v0 - 3 + s.  s_comp = comp of those columns, s_col = their minimum over the
 // band as key << 8 | row within the band, s_row = the rows' minimum over the step as key << 11 | slot -- both orders are the edge
 // order restricted to one column / one row.  The host has checked row0 + n_rows <= n_nodes and col0 + n_cols <= n_nodes.
-__global__ __launch_bounds__(kFilterThreads) void tri_nearest_kernel(const int32_t* __restrict__ tile, int64_t n_rows, int64_t n_cols, int64_t ld,
-                                                                      int64_t row0, int64_t col0, const uint8_t* __restrict__ row_empty,
-                                                                      const uint8_t* __restrict__ col_empty, int32_t cap, int32_t bound,
-                                                                      const int32_t* __restrict__ comp, unsigned long long* best,
+__global__ __launch_bounds__(kFilterThreads) void tri_nearest_kernel(const TriTile t, const int32_t* __restrict__ comp, unsigned long long* best,
                                                                       int64_t n_nodes, int64_t n_bands, int64_t n_steps) {
     __shared__ int32_t s_comp[kTreeCols];
     __shared__ uint32_t s_col[kTreeCols];
@@ -67,28 +66,24 @@ __global__ __launch_bounds__(kFilterThreads) void tri_nearest_kernel(const int32
     const int tid = threadIdx.x, lane = tid & 63;
     for (int64_t job = blockIdx.x; job < n_bands * n_steps; job += gridDim.x) {
         const int64_t r_lo = job / n_steps * kTreeBand, v0 = job % n_steps * kFilterStep;
-        const int rows = (int)min((int64_t)kTreeBand, n_rows - r_lo);
-        if (v0 + kFilterStep <= first_column(row0, r_lo, col0)) continue;   // (the whole step lies on or left of the diagonal)
+        const int rows = (int)min((int64_t)kTreeBand, t.n_rows - r_lo);
+        if (v0 + kFilterStep <= first_column(t, r_lo)) continue;   // (the whole step lies on or left of the diagonal)
         const int64_t c_lo = v0 - 3;                                        // column of slot 0
         __syncthreads();                                                    // (the previous job's flush has read the arrays)
         for (int s = tid; s < kTreeCols; s += kFilterThreads) {
             const int64_t c = c_lo + s;
-            s_comp[s] = c >= 0 && c < n_cols ? comp[col0 + c] : -1;
+            s_comp[s] = c >= 0 && c < t.n_cols ? comp[t.col0 + c] : -1;
             s_col[s] = kNone32;
         }
         if (tid < kTreeBand) s_row[tid] = kNone32;
         __syncthreads();
         for (int rl = 0; rl < rows; ++rl) {
             const int64_t r = r_lo + rl;
-            const int64_t c_min = first_column(row0, r, col0);
-            if (v0 + kFilterStep <= c_min) continue;
-            const int32_t* row = tile + r * ld;
-            const int shift = row_shift(row);
-            const bool row_is_empty = row_empty && row_empty[r];
-            const int32_t comp_i = comp[row0 + r];
-            const int64_t v = v0 + 4 * tid;
-            const Quad q = filter_quad(row, v, shift, c_min, n_cols, row_is_empty, col_empty, cap, bound);
-            const int slot0 = 4 * tid + 3 - shift;                          // slot of the quad's first column v - shift
+            if (v0 + kFilterStep <= first_column(t, r)) continue;
+            const TriRow w = tri_row(t, r);
+            const int32_t comp_i = comp[t.row0 + r];
+            const Quad q = filter_quad(t, w, v0 + 4 * tid, t.n_cols);
+            const int slot0 = 4 * tid + 3 - w.shift;                          // slot of the quad's first column v - shift
             uint32_t mine = kNone32;
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
@@ -103,12 +98,12 @@ __global__ __launch_bounds__(kFilterThreads) void tri_nearest_kernel(const int32
         }
         __syncthreads();
         if (tid < rows && s_row[tid] != kNone32) {
-            const int64_t i = row0 + r_lo + tid, j = col0 + c_lo + (s_row[tid] & 0x7ff);
+            const int64_t i = t.row0 + r_lo + tid, j = t.col0 + c_lo + (s_row[tid] & 0x7ff);
             lower_best(best, comp[i], n_nodes, pack_edge((int32_t)(s_row[tid] >> 11), i, j));
         }
         for (int s = tid; s < kTreeCols; s += kFilterThreads)
             if (s_col[s] != kNone32) {
-                const int64_t i = row0 + r_lo + (s_col[s] & 0xff), j = col0 + c_lo + s;
+                const int64_t i = t.row0 + r_lo + (s_col[s] & 0xff), j = t.col0 + c_lo + s;
                 lower_best(best, s_comp[s], n_nodes, pack_edge((int32_t)(s_col[s] >> 8), i, j));
             }
     }
@@ -145,12 +140,10 @@ __global__ __launch_bounds__(kLinkThreads) void tree_hook_kernel(const int32_t* 
 
 namespace dctfp_host {
 
-void launch_tri_nearest(const int32_t* tile, int64_t n_rows, int64_t n_cols, int64_t ld, int64_t row0, int64_t col0, const uint8_t* row_empty,
-                        const uint8_t* col_empty, int32_t cap, int32_t bound, const int32_t* comp, uint64_t* best, int64_t n_nodes,
-                        hipStream_t stream) {
-    const int64_t n_bands = (n_rows + kTreeBand - 1) / kTreeBand, n_steps = (n_cols + 3 + kFilterStep - 1) / kFilterStep;
-    hipLaunchKernelGGL(tri_nearest_kernel, dim3(filter_grid(n_bands * n_steps)), dim3(kFilterThreads), 0, stream, tile, n_rows, n_cols, ld, row0,
-                       col0, row_empty, col_empty, cap, bound, comp, reinterpret_cast<unsigned long long*>(best), n_nodes, n_bands, n_steps);
+void launch_tri_nearest(const TriTile& t, const int32_t* comp, uint64_t* best, int64_t n_nodes, hipStream_t stream) {
+    const int64_t n_bands = (t.n_rows + kTreeBand - 1) / kTreeBand, n_steps = (t.n_cols + 3 + kFilterStep - 1) / kFilterStep;
+    hipLaunchKernelGGL(tri_nearest_kernel, dim3(filter_grid(n_bands * n_steps)), dim3(kFilterThreads), 0, stream, t, comp,
+                       reinterpret_cast<unsigned long long*>(best), n_nodes, n_bands, n_steps);
 }
 
 hipError_t launch_tree_hook(const int32_t* comp, uint64_t* best, int32_t* parent, int64_t n_nodes, int32_t* edge_i, int32_t* edge_j,

@@ -19,6 +19,7 @@
 
 namespace dctfp {
 struct CutJob;   // reccut_kernel.hip.h
+struct TriTile;  // tri_walk.hip.h
 }
 
 namespace dctfp_host {
@@ -156,14 +157,10 @@ void launch_select_fill(const int32_t* dist, int64_t n_rows, int64_t n_cols, int
 // all_sim's result lines (k_search.hip): text from a (min, last) tile at offsets computed from the id lengths
 void launch_sim_lines(const int32_t* mn, const int32_t* last, int64_t ld, int64_t n_rows, int64_t row0, int64_t col0, int64_t n_cols,
                       const uint8_t* ids, const int64_t* id_off, const char* table, const int64_t* row_base, uint8_t* out, hipStream_t stream);
-// all-against-all with score cut-offs (k_filter.hip): the surviving pairs of a tile of the triangle in output order, and result
-// lines for a list of pairs
-void launch_tri_filter_count(const int32_t* tile, int64_t n_rows, int64_t n_cols, int64_t ld, int64_t row0, int64_t col0,
-                             const uint8_t* row_empty, const uint8_t* col_empty, int32_t cap, int32_t bound, int32_t* out_count,
-                             hipStream_t stream);
-void launch_tri_filter_fill(const int32_t* tile, int64_t n_rows, int64_t n_cols, int64_t ld, int64_t row0, int64_t col0,
-                            const uint8_t* row_empty, const uint8_t* col_empty, int32_t cap, int32_t bound, const int64_t* offsets,
-                            int64_t out_len, int32_t* out_i, int32_t* out_j, hipStream_t stream);
+// all-against-all with score cut-offs (k_filter.hip): the surviving pairs of a tile of the triangle (a TriTile, as for every
+// launcher below that takes one) in output order, and result lines for a list of pairs
+void launch_tri_filter_count(const TriTile& t, int32_t* out_count, hipStream_t stream);
+void launch_tri_filter_fill(const TriTile& t, const int64_t* offsets, int64_t out_len, int32_t* out_i, int32_t* out_j, hipStream_t stream);
 // (dctfp_pair_lines and dctfp_pair_domain_lines: labels NULL = the line without the two label fields, la / lb / label_off not read)
 void launch_pair_domain_lines(int64_t n_lines, const int32_t* pi, const int32_t* pj, const int32_t* mn, const int32_t* last, const int32_t* la,
                               const int32_t* lb, const uint8_t* ids, const int64_t* id_off, int64_t n_ids, const uint8_t* labels,
@@ -172,8 +169,7 @@ void launch_pair_domain_lines(int64_t n_lines, const int32_t* pi, const int32_t*
 
 // single-linkage clusters at a cut-off (k_cluster.hip): unions of a tile's surviving entries / of a list of pairs in a lock-free
 // union-find over parent[0 .. n_nodes), and the roots of all nodes afterwards (two launches: flatten, then read)
-void launch_tri_link(const int32_t* tile, int64_t n_rows, int64_t n_cols, int64_t ld, int64_t row0, int64_t col0, const uint8_t* row_empty,
-                     const uint8_t* col_empty, int32_t cap, int32_t bound, int32_t* parent, hipStream_t stream);
+void launch_tri_link(const TriTile& t, int32_t* parent, hipStream_t stream);
 void launch_link_pairs(const int32_t* pi, const int32_t* pj, int64_t n_pairs, int32_t* parent, int64_t n_nodes, hipStream_t stream);
 void launch_cluster_labels(int32_t* parent, int64_t n_nodes, int32_t* labels, hipStream_t stream);
 // (dctfp_rows_link: the nodes are fingerprint rows -- sad_tile's contraction (sad_tile.hip.h), every pair of rows of different owners
@@ -185,9 +181,7 @@ void launch_rows_link(const int8_t* a, int64_t na, int64_t lda, int64_t a0, cons
 // ends carry different labels in comp lowers best (packed key << 48 | i << 24 | j) of both labels -- then, once per round, the hook:
 // every label appends its best edge at *counter (nothing at or beyond max_edges), joins its ends in parent, and best is refilled
 // with "none" behind it on the stream
-void launch_tri_nearest(const int32_t* tile, int64_t n_rows, int64_t n_cols, int64_t ld, int64_t row0, int64_t col0, const uint8_t* row_empty,
-                        const uint8_t* col_empty, int32_t cap, int32_t bound, const int32_t* comp, uint64_t* best, int64_t n_nodes,
-                        hipStream_t stream);
+void launch_tri_nearest(const TriTile& t, const int32_t* comp, uint64_t* best, int64_t n_nodes, hipStream_t stream);
 hipError_t launch_tree_hook(const int32_t* comp, uint64_t* best, int32_t* parent, int64_t n_nodes, int32_t* edge_i, int32_t* edge_j,
                             int32_t* edge_key, int32_t* counter, int64_t max_edges, hipStream_t stream);
 
@@ -202,9 +196,8 @@ void launch_rows_assign(const int8_t* a, int64_t na, int64_t lda, const int32_t*
 // assign at their surviving entries, undecided rows stamp blocked inside the range with the next round's number)
 void launch_greedy_decide(int32_t* assign, int32_t* state, const int32_t* blocked, int64_t i0, int64_t i1, int32_t round,
                           unsigned long long* undecided, hipStream_t stream);
-void launch_greedy_tri_mark(const int32_t* tile, int64_t n_rows, int64_t n_cols, int64_t ld, int64_t row0, int64_t col0, const uint8_t* row_empty,
-                            const uint8_t* col_empty, int32_t cap, int32_t bound, int32_t* assign, const int32_t* state, int32_t* blocked,
-                            int64_t range_end, int32_t next_round, hipStream_t stream);
+void launch_greedy_tri_mark(const TriTile& t, int32_t* assign, const int32_t* state, int32_t* blocked, int64_t range_end, int32_t next_round,
+                            hipStream_t stream);
 void launch_greedy_pairs_mark(const int32_t* pi, const int32_t* pj, int64_t n_pairs, int32_t* assign, const int32_t* state, int32_t* blocked,
                               int64_t n_nodes, int64_t range_end, int32_t next_round, hipStream_t stream);
 

@@ -336,7 +336,11 @@ def _ptr(t):
     return t.data_ptr() if t is not None else None
 
 
-def _tri_filter_args(tile: torch.Tensor, row0: int, col0: int, bound: int, row_empty, col_empty, cap: int):
+def _tri_filter_args(tile: torch.Tensor, row0: int, col0: int, bound: int, row_empty, col_empty, cap: int, n_nodes: int = None,
+                     range_end: int = None):
+    """(n_rows, n_cols, lead, flags) of an L1 tile: ``lead`` = the ten arguments every export that scans a tile starts with (the
+    library's ``TriTile``), ``flags`` = the device copies of the flag arrays, which the caller holds until its launch is queued.
+    ``n_nodes``: the length of the node arrays beside the tile, which the tile (and ``range_end``, if given) must lie inside."""
     if tile.dtype != torch.int32 or tile.dim() != 2 or tile.device.type != 'cuda' or (tile.shape[1] > 1 and tile.stride(1) != 1):
         raise ValueError('tile must be a 2-D int32 device tensor with unit column stride')
     if row0 < 0 or col0 < 0:
@@ -344,17 +348,19 @@ def _tri_filter_args(tile: torch.Tensor, row0: int, col0: int, bound: int, row_e
     n_rows, n_cols = tile.shape
     ld = tile.stride(0) if n_rows > 1 else max(n_cols, 1)
     re, ce = _empty_flags(row_empty, n_rows, tile.device), _empty_flags(col_empty, n_cols, tile.device)
-    return n_rows, n_cols, ld, re, ce, int(max(-1, min(int(bound), cap)))
+    if n_nodes is not None and (row0 + n_rows > n_nodes or col0 + n_cols > n_nodes or (range_end is not None and not 0 <= range_end <= n_nodes)):
+        raise IndexError('tile or range outside the nodes')
+    lead = (tile.data_ptr(), n_rows, n_cols, ld, int(row0), int(col0), _ptr(re), _ptr(ce), cap, int(max(-1, min(int(bound), cap))))
+    return n_rows, n_cols, lead, (re, ce)
 
 
 def tri_filter_count(tile: torch.Tensor, row0: int, col0: int, bound: int, row_empty=None, col_empty=None, cap: int = 17000) -> torch.Tensor:
     """Device int32 (n_rows): per row of an L1 tile (entry (r, c) = proteins row0 + r, col0 + c) the entries with
     col0 + c > row0 + r and min(L1, cap) <= bound -- ``cap`` for a row / column flagged empty (``dctfp_tri_filter_count``)."""
-    n_rows, n_cols, ld, re, ce, bound = _tri_filter_args(tile, row0, col0, bound, row_empty, col_empty, cap)
+    n_rows, n_cols, lead, _flags = _tri_filter_args(tile, row0, col0, bound, row_empty, col_empty, cap)
     count = torch.zeros(n_rows, dtype=torch.int32, device=tile.device)
     if n_rows and n_cols:
-        _launch(tile.device, 'dctfp_tri_filter_count', tile.data_ptr(), n_rows, n_cols, ld, int(row0), int(col0), _ptr(re), _ptr(ce), cap,
-                bound, count.data_ptr())
+        _launch(tile.device, 'dctfp_tri_filter_count', *lead, count.data_ptr())
     return count
 
 
@@ -363,7 +369,7 @@ def tri_filter_fill(tile: torch.Tensor, row0: int, col0: int, bound: int, count:
     """(i, j): device int32 (total) -- the entries ``tri_filter_count`` counted (``count`` = its result for this tile, ``total``
     its sum) as global protein indices, i ascending, then j ascending (``dctfp_tri_filter_fill``; the prefix sum of the counts
     is taken here, on the device)."""
-    n_rows, n_cols, ld, re, ce, bound = _tri_filter_args(tile, row0, col0, bound, row_empty, col_empty, cap)
+    n_rows, n_cols, lead, _flags = _tri_filter_args(tile, row0, col0, bound, row_empty, col_empty, cap)
     if count.dtype != torch.int32 or count.numel() != n_rows or count.device != tile.device:
         raise ValueError('count must be the int32 device result of tri_filter_count for this tile')
     total = int(total)
@@ -372,8 +378,7 @@ def tri_filter_fill(tile: torch.Tensor, row0: int, col0: int, bound: int, count:
     if total and n_rows and n_cols:
         offsets = torch.zeros(n_rows + 1, dtype=torch.int64, device=tile.device)
         torch.cumsum(count, 0, out=offsets[1:])
-        _launch(tile.device, 'dctfp_tri_filter_fill', tile.data_ptr(), n_rows, n_cols, ld, int(row0), int(col0), _ptr(re), _ptr(ce), cap,
-                bound, offsets.data_ptr(), total, out_i.data_ptr(), out_j.data_ptr())
+        _launch(tile.device, 'dctfp_tri_filter_fill', *lead, offsets.data_ptr(), total, out_i.data_ptr(), out_j.data_ptr())
     return out_i, out_j
 
 
@@ -395,13 +400,10 @@ def tri_link(tile: torch.Tensor, row0: int, col0: int, bound: int, parent: torch
     """Joins, in the union-find forest ``parent`` (device int32, started as ``torch.arange(n)``), proteins row0 + r and col0 + c
     for every entry of an L1 tile that ``tri_filter_count`` would count (``dctfp_tri_link``).  Nothing comes back: the forest is
     read with ``cluster_labels`` once every tile has been linked."""
-    n_rows, n_cols, ld, re, ce, bound = _tri_filter_args(tile, row0, col0, bound, row_empty, col_empty, cap)
     n_nodes = _parent_arg(parent, tile.device)
-    if row0 + n_rows > n_nodes or col0 + n_cols > n_nodes:
-        raise IndexError('tile outside the nodes of parent')
+    n_rows, n_cols, lead, _flags = _tri_filter_args(tile, row0, col0, bound, row_empty, col_empty, cap, n_nodes)
     if n_rows and n_cols:
-        _launch(tile.device, 'dctfp_tri_link', tile.data_ptr(), n_rows, n_cols, ld, int(row0), int(col0), _ptr(re), _ptr(ce), cap, bound,
-                parent.data_ptr(), n_nodes)
+        _launch(tile.device, 'dctfp_tri_link', *lead, parent.data_ptr(), n_nodes)
 
 
 def link_pairs(pi: torch.Tensor, pj: torch.Tensor, parent: torch.Tensor):
@@ -515,13 +517,10 @@ def tri_nearest(tile: torch.Tensor, row0: int, col0: int, bound: int, ts: TreeSt
     """Lowers ``ts.best`` of both labels to the packed edge of every entry of an L1 tile that ``tri_filter_count`` would count and
     whose two proteins carry different labels in ``ts.comp`` (``dctfp_tri_nearest``): one round's candidates for the lightest
     edge out of every component.  ``tree_hook`` ends the round once every tile has been through."""
-    n_rows, n_cols, ld, re, ce, bound = _tri_filter_args(tile, row0, col0, bound, row_empty, col_empty, cap)
     n_nodes = ts.arrays(tile.device)
-    if row0 + n_rows > n_nodes or col0 + n_cols > n_nodes:
-        raise IndexError('tile outside the nodes')
+    n_rows, n_cols, lead, _flags = _tri_filter_args(tile, row0, col0, bound, row_empty, col_empty, cap, n_nodes)
     if n_rows and n_cols:
-        _launch(tile.device, 'dctfp_tri_nearest', tile.data_ptr(), n_rows, n_cols, ld, int(row0), int(col0), _ptr(re), _ptr(ce), cap, bound,
-                ts.comp.data_ptr(), ts.best.data_ptr(), n_nodes)
+        _launch(tile.device, 'dctfp_tri_nearest', *lead, ts.comp.data_ptr(), ts.best.data_ptr(), n_nodes)
 
 
 def tree_hook(ts: TreeState):
@@ -586,13 +585,11 @@ def greedy_tri_mark(tile: torch.Tensor, row0: int, col0: int, bound: int, gs: Gr
     """The mark launch of a round from an L1 tile (``dctfp_greedy_tri_mark``): over the entries ``tri_filter_count`` would count, a
     row that is a new representative lowers ``assign`` of its columns, an undecided row stamps ``blocked`` of its columns below
     ``range_end`` with ``next_round``."""
-    n_rows, n_cols, ld, re, ce, bound = _tri_filter_args(tile, row0, col0, bound, row_empty, col_empty, cap)
     n_nodes = gs.arrays(tile.device)
-    if row0 + n_rows > n_nodes or col0 + n_cols > n_nodes or not 0 <= range_end <= n_nodes:
-        raise IndexError('tile or range outside the nodes')
+    n_rows, n_cols, lead, _flags = _tri_filter_args(tile, row0, col0, bound, row_empty, col_empty, cap, n_nodes, range_end)
     if n_rows and n_cols:
-        _launch(tile.device, 'dctfp_greedy_tri_mark', tile.data_ptr(), n_rows, n_cols, ld, int(row0), int(col0), _ptr(re), _ptr(ce), cap, bound,
-                gs.assign.data_ptr(), gs.state.data_ptr(), gs.blocked.data_ptr(), n_nodes, int(range_end), int(next_round))
+        _launch(tile.device, 'dctfp_greedy_tri_mark', *lead, gs.assign.data_ptr(), gs.state.data_ptr(), gs.blocked.data_ptr(), n_nodes,
+                int(range_end), int(next_round))
 
 
 def greedy_pairs_mark(pi: torch.Tensor, pj: torch.Tensor, gs: GreedyState, range_end: int, next_round: int):

@@ -56,3 +56,37 @@ def filtered_text(lines, keep) -> bytes:
 def read_lines(path):
     with (gzip.open(path, 'rb') if path.endswith('.gz') else open(path, 'rb')) as fh:
         return fh.read().split(b'\n')[:-1]
+
+
+# ---- the rule on one int32 tile of L1 values, as the kernels that scan a tile apply it (test_all_sim_filter_gpu.py, test_tri_walk_gpu.py)
+
+def tile_keep(t, row0, col0, bound, row_empty=None, col_empty=None, cap=17000):
+    """(keep, key): entry (r, c) of the tile stands for proteins i = row0 + r and j = col0 + c; key = min(L1, cap), cap for a row or
+    column flagged empty; an entry is kept when j > i and key <= bound."""
+    key = np.minimum(t.astype(np.int64) & 0xffffffff, cap)    # (a negative value counts as cap)
+    if row_empty is not None:
+        key[np.asarray(row_empty, dtype=bool)] = cap
+    if col_empty is not None:
+        key[:, np.asarray(col_empty, dtype=bool)] = cap
+    i = row0 + np.arange(t.shape[0])[:, None]
+    j = col0 + np.arange(t.shape[1])[None, :]
+    return (j > i) & (key <= bound), key
+
+
+def tile_filter(t, row0, col0, bound, row_empty=None, col_empty=None, cap=17000):
+    """(count per row, i, j) of the kept entries."""
+    keep, _ = tile_keep(t, row0, col0, bound, row_empty, col_empty, cap)
+    r, c = np.nonzero(keep)                                   # (row-major: i ascending, then j)
+    return keep.sum(axis=1), row0 + r, col0 + c
+
+
+def random_tile(rng, n_rows, n_cols, bound):
+    """Values on both sides of the bound and of 17000, 0x7fffffff and negative ones."""
+    t = rng.integers(0, 17002, size=(n_rows, n_cols))
+    near = rng.random((n_rows, n_cols))
+    t[near < 0.2] = max(bound, 0)
+    t[(near >= 0.2) & (near < 0.3)] = bound + 1
+    t[(near >= 0.3) & (near < 0.4)] = 0x7fffffff
+    t[(near >= 0.4) & (near < 0.45)] = 17000
+    t[(near >= 0.45) & (near < 0.47)] = -5
+    return t.astype(np.int32)

@@ -254,28 +254,7 @@ def test_the_two_routes_agree(tmp_path, monkeypatch, cut):
 
 # ---- the kernels on their own
 
-def _np_filter(t, row0, col0, bound, row_empty=None, col_empty=None, cap=17000):
-    key = np.minimum(t.astype(np.int64) & 0xffffffff, cap)    # (a negative value counts as cap)
-    if row_empty is not None:
-        key[np.asarray(row_empty, dtype=bool)] = cap
-    if col_empty is not None:
-        key[:, np.asarray(col_empty, dtype=bool)] = cap
-    i = row0 + np.arange(t.shape[0])[:, None]
-    j = col0 + np.arange(t.shape[1])[None, :]
-    keep = (j > i) & (key <= bound)
-    r, c = np.nonzero(keep)                                   # (row-major: i ascending, then j)
-    return keep.sum(axis=1), row0 + r, col0 + c
-
-
-def _random_tile(rng, n_rows, n_cols, bound):
-    t = rng.integers(0, 17002, size=(n_rows, n_cols))
-    near = rng.random((n_rows, n_cols))
-    t[near < 0.2] = max(bound, 0)
-    t[(near >= 0.2) & (near < 0.3)] = bound + 1
-    t[(near >= 0.3) & (near < 0.4)] = 0x7fffffff
-    t[(near >= 0.4) & (near < 0.45)] = 17000
-    t[(near >= 0.45) & (near < 0.47)] = -5
-    return t.astype(np.int32)
+_np_filter, _random_tile = rule.tile_filter, rule.random_tile
 
 
 @pytest.mark.parametrize('n_rows,n_cols', [(7, 3000), (1, 5000), (40, 1), (3, 1023), (5, 1025), (9, 2048), (4, 0), (0, 10), (300, 37)])

@@ -313,6 +313,40 @@ def test_new_unit_and_shared_header_are_part_of_the_build():
         assert inc in text and 'filter_quad(' in text
 
 
+def test_the_tile_description_is_defined_once_and_checked_in_one_place():
+    """The ten values that describe an L1 tile are struct TriTile, in one header; the five kernels that scan a tile take the struct, not
+    the list; the five exports check it with one function.  The forest's routines live in a header of their own, part of the build."""
+    import build_ext
+    csrc = os.path.join(ROOT, 'dctdomain_amd', 'csrc')
+    code = {}
+    for name in sorted(os.listdir(csrc)):
+        with open(os.path.join(csrc, name)) as fh:
+            code[name] = '\n'.join(line.split('//', 1)[0] for line in fh.read().splitlines())
+    holders = [name for name, text in code.items() if re.search(r'\bstruct TriTile\s*\{', text)]
+    assert holders == ['tri_walk.hip.h'] and os.path.join(csrc, holders[0]) in build_ext.HEADERS
+    kernels = {'k_filter.hip': ('tri_filter_count_kernel', 'tri_filter_fill_kernel'), 'k_cluster.hip': ('tri_link_kernel',),
+               'k_greedy.hip': ('greedy_tri_mark_kernel',), 'k_tree.hip': ('tri_nearest_kernel',)}
+    # (every unit that includes the header: sim_lines_kernel of k_search.hip has a row0 / col0 of its own and scans no such tile)
+    assert sorted(kernels) == sorted(u for u in build_ext.UNITS if u.startswith('k_') and '#include "tri_walk.hip.h"' in code[u])
+    for unit, names in kernels.items():
+        heads = re.sub(r'\s+', ' ', ' '.join(re.findall(r'__global__[^{]*\{', code[unit])))
+        assert not re.search(r'int64_t row0, int64_t col0', heads), unit
+        for kernel in names:
+            assert ' %s(const TriTile t, ' % kernel in heads, kernel
+    host = code['dctfp.hip']
+    exports = ('dctfp_tri_filter_count', 'dctfp_tri_filter_fill', 'dctfp_tri_link', 'dctfp_greedy_tri_mark', 'dctfp_tri_nearest')
+    assert host.count('check_tri_tile(') == 1 + len(exports) and 'static int check_tri_tile(const char* name, const TriTile& t)' in host
+    for name in exports:
+        body = host[host.index('\nint %s(' % name):host.index('DCTFP_GUARD("%s")' % name)]
+        assert body.count('check_tri_tile("%s", t)' % name) == 1 and 'ld < n_cols' not in body, name
+    assert sum('check_tri_tile(' in text for text in code.values()) == 1
+    # the union-find is a header both users include, the last of build_ext.HEADERS (kernel_sources() covers it)
+    assert build_ext.HEADERS[-1] == os.path.join(csrc, 'union_find.hip.h') and build_ext.HEADERS[-1] in build_ext.kernel_sources()
+    assert sum(bool(re.search(r'\bint32_t uf_find\(', text)) for text in code.values()) == 1 and 'uf_find(' in code['union_find.hip.h']
+    for unit in ('k_cluster.hip', 'k_tree.hip'):
+        assert '#include "union_find.hip.h"' in code[unit] and 'DCTFP_UNION_FIND_ONLY' not in code[unit]
+
+
 def test_the_sad_tile_is_defined_once_in_a_header_every_user_includes():
     """The 128 x 128 v_sad_u8 contraction of l1_matrix16_kernel, protein_min_kernel and rows_link_kernel is one function template in
     one shared header.  Exempt by name, each for a reason written at the place: l1_knn_kernel (k_query.hip) and rows_assign_kernel
@@ -358,9 +392,10 @@ def test_the_sad_tile_is_defined_once_in_a_header_every_user_includes():
 
 
 def test_link_kernels_touch_the_forest_through_agent_scope_atomics_only():
-    """The access rule of the kernels that link, read off the source: no plain load or store of `parent` in k_cluster.hip outside
-    the launch that only reads it (labels_kernel)."""
-    text = open(os.path.join(ROOT, 'dctdomain_amd', 'csrc', 'k_cluster.hip')).read()
+    """The access rule of the kernels that link, read off the source: no plain load or store of `parent` in the forest's routines
+    (union_find.hip.h) and in k_cluster.hip outside the launch that only reads it (labels_kernel)."""
+    csrc = os.path.join(ROOT, 'dctdomain_amd', 'csrc')
+    text = open(os.path.join(csrc, 'union_find.hip.h')).read() + open(os.path.join(csrc, 'k_cluster.hip')).read()
     code = '\n'.join(line.split('//')[0] for line in text.splitlines())
     body = code[:code.index('void labels_kernel')] + code[code.index('unsigned link_grid'):]
     assert not re.search(r'parent\s*\[', body) and not re.search(r'(?<!_t)\*\(?\s*parent\b', body)    # (`int32_t* parent` declares)

@@ -183,7 +183,10 @@ def test_new_unit_is_part_of_the_build_and_touches_best_through_atomics_only_whi
     assert 'k_tree.hip' in build_ext.UNITS and 'k_cluster.hip' in build_ext.UNITS
     text = open(os.path.join(ROOT, 'dctdomain_amd', 'csrc', 'k_tree.hip')).read()
     code = '\n'.join(line.split('//', 1)[0] for line in text.splitlines())
-    assert '#include "k_cluster.hip"' in text and 'filter_quad(' in code and 'uf_union(parent' in code
+    assert '#include "union_find.hip.h"' in text and 'filter_quad(' in code and 'uf_union(parent' in code
+    csrc = os.path.join(ROOT, 'dctdomain_amd', 'csrc')
+    for unit in build_ext.UNITS:                              # (no translation unit is included into another)
+        assert not re.search(r'#include\s+"[^"]*\.hip"', open(os.path.join(csrc, unit)).read()), unit
     nearest = code[code.index('void tri_nearest_kernel'):code.index('void tree_hook_kernel')]
     lower = code[code.index('void lower_best'):code.index('void tri_nearest_kernel')]
     assert not re.search(r'\bbest\s*\[', nearest + lower) and 'lower_best(best' in nearest     # (no plain load or store of best)
