@@ -2944,6 +2944,28 @@ int dctfp_tree_hook(dctfp_ctx* ctx, const int32_t* comp, uint64_t* best, int32_t
     return DCTFP_OK;
 } DCTFP_GUARD("dctfp_tree_hook")
 
+int dctfp_rect_best(dctfp_ctx* ctx, const int32_t* tile, int64_t n_rows, int64_t n_cols, int64_t ld, int64_t row0, int64_t col0,
+                    const uint8_t* row_empty, const uint8_t* col_empty, int32_t cap, int32_t bound, uint64_t* best_row, int64_t n_a,
+                    uint64_t* best_col, int64_t n_b, void* stream_v) try {
+    if (!ctx || !tile || !best_row || !best_col) return fail(DCTFP_ERR_INVALID, "dctfp_rect_best: NULL argument");
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    // (a rectangle, not a tile of the triangle: its own few conditions)
+    if (n_rows < 0 || n_cols < 0 || ld < n_cols || row0 < 0 || col0 < 0 || cap < 0 || bound < -1 || bound > cap)
+        return fail(DCTFP_ERR_INVALID, "dctfp_rect_best: bad shape or bound");
+    if (((reinterpret_cast<uintptr_t>(tile) & 3u) | ((reinterpret_cast<uintptr_t>(best_row) | reinterpret_cast<uintptr_t>(best_col)) & 7u)) != 0)
+        return fail(DCTFP_ERR_INVALID, "dctfp_rect_best: the tile is not 4-byte aligned or best_row / best_col not 8-byte aligned");
+    if (cap > rect_best_max_cap())
+        return fail(DCTFP_ERR_INVALID, "dctfp_rect_best: a cap above %d does not fit the packed minima of a row", rect_best_max_cap());
+    if (n_a < 0 || n_b < 0 || n_a > 0x7fffffff || n_b > 0x7fffffff) return fail(DCTFP_ERR_INVALID, "dctfp_rect_best: n_a and n_b must lie in 0 .. 2^31 - 1");
+    // (every index the kernel can form lies inside the tile: bounded here, on the host, and not on the device)
+    if (row0 + n_rows > n_a || col0 + n_cols > n_b) return fail(DCTFP_ERR_INVALID, "dctfp_rect_best: the tile names proteins outside best_row / best_col");
+    if (n_rows == 0 || n_cols == 0) return DCTFP_OK;
+    HIP_TRY(hipSetDevice(ctx->device));
+    launch_rect_best(tile, n_rows, n_cols, ld, row0, col0, row_empty, col_empty, cap, bound, best_row, best_col, (hipStream_t)stream_v);
+    HIP_TRY(hipGetLastError());
+    return DCTFP_OK;
+} DCTFP_GUARD("dctfp_rect_best")
+
 int dctfp_greedy_decide(dctfp_ctx* ctx, int32_t* assign, int32_t* state, const int32_t* blocked, int64_t n_nodes, int64_t i0, int64_t i1,
                         int32_t round, int64_t* undecided, void* stream_v) try {
     if (!ctx || !assign || !state || !blocked || !undecided) return fail(DCTFP_ERR_INVALID, "dctfp_greedy_decide: NULL argument");

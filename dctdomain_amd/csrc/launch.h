@@ -185,6 +185,13 @@ void launch_tri_nearest(const TriTile& t, const int32_t* comp, uint64_t* best, i
 hipError_t launch_tree_hook(const int32_t* comp, uint64_t* best, int32_t* parent, int64_t n_nodes, int32_t* edge_i, int32_t* edge_j,
                             int32_t* edge_key, int32_t* counter, int64_t max_edges, hipStream_t stream);
 
+// reciprocal best hits of two files (k_best.hip): one pass over the full rectangle of an int32 L1 tile -- every entry with
+// min(L1, cap) <= bound (cap for a flagged protein) lowers best_row[row0 + r] to key << 32 | (col0 + c) and best_col[col0 + c] to
+// key << 32 | (row0 + r) with agent-scope atomic minima; rect_best_max_cap = the largest cap the kernel's packed LDS words hold
+int rect_best_max_cap();
+void launch_rect_best(const int32_t* tile, int64_t n_rows, int64_t n_cols, int64_t ld, int64_t row0, int64_t col0, const uint8_t* row_empty,
+                      const uint8_t* col_empty, int32_t cap, int32_t bound, uint64_t* best_row, uint64_t* best_col, hipStream_t stream);
+
 // (dctfp_rows_assign, k_assign.hip: the same contraction over a full rectangle -- every pair of rows within the bound lowers
 // assign[slot of the b row] to the value of the a row with an atomic minimum; value_a / slot_b NULL: a0 + r / b0 + c)
 void launch_rows_assign(const int8_t* a, int64_t na, int64_t lda, const int32_t* value_a, int64_t a0, const int8_t* b, int64_t nb, int64_t ldb,

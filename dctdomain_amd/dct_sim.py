@@ -8,6 +8,8 @@ fingerprints (``-dct.npz``), with the L1 distances computed on the GPU.
     python -m dctdomain_amd.dct_sim --dct NEW-dct.npz --assign REPS-dct.npz --min-domain X [--min-global Y] [--reps-out ALL-dct.npz]
                                     [--output F]
     python -m dctdomain_amd.dct_sim --dct X-dct.npz --tree [domain|global] [--min-domain X | --min-global Y] [--output F]
+    python -m dctdomain_amd.dct_sim --dct A-dct.npz --db B-dct.npz --rbh [domain|global] [--min-domain X | --min-global Y] [--domains]
+                                    [--dom A.dom] [--db-dom B.dom] [--output F]
 
 Same flags, same output text (src/dct-sim.py:179-211); ``--rank domain`` (not in the reference) orders database hits by
 DCTdomain instead of DCTglobal, and ``--min-domain`` / ``--min-global`` (not in the reference either, which ignores
@@ -58,6 +60,13 @@ Where the reference loops over protein pairs and, inside, over domain pairs in P
   (``dctfp_pair_min``): ``ProteinSearch``.  Host memory is what is printed plus one tile, not n_query x n_db.  With
   ``--rank domain`` it ranks on DCTdomain instead: the tiles hold every protein pair's minimum over all fingerprint pairs
   (``dctfp_protein_min``), selected the same way;
+- ``--db Y --rbh`` (``ReciprocalBest``, not in the reference) prints the reciprocal best hits of the two files, the usual first-pass
+  ortholog call: the pairs (a, b) where b is the best hit of a among the proteins of ``--db`` and a the best hit of b among those
+  of ``--dct``, by DCTdomain (``domain``) or DCTglobal (``global``), ties to the lower index in the file, hits being the pairs of
+  similarity above 0 (or not below that score's cut-off).  One search pass instead of two and a join by hand: ``ProteinSearch``'s
+  tiles (``dctfp_protein_min``, or ``dctfp_l1_matrix`` of the last rows) go to one kernel that keeps the best column of every row
+  and the best row of every column with atomic minima of ``key << 32 | index`` (``dctfp_rect_best``); 8 bytes per protein come
+  back at the end, and the lines are ``db_search``'s lines for those pairs;
 - ``pair_sim`` uploads the fingerprints of the proteins its pairs name and runs ``dctfp_pair_min`` on the pairs.
 ``--domains`` (not in the reference) adds two fields to every result line: the fingerprint of each protein that DCTdomain came
 from -- the pair the reference's double loop (:42-50) ends on: the smallest L1, ties to the lowest row of the first protein, then
@@ -80,7 +89,7 @@ import numpy as np
 from .similarity import (GREEDY_NONE, PROTEIN_MIN_MAX_D, GreedyState, LineIds, TextStream, _utf8_binary, block_min, block_min_device, cluster_labels,
                          greedy_decide, greedy_pairs_mark, greedy_tri_mark, l1_matrix, link_pairs, pair_argmin, pair_argmin_device, pair_line_offsets, pair_lines, pair_min, pair_min_device, protein_min,
                          rows_assign, rows_link, sim_lines, threshold_select, to_device_int8, tri_filter_count, tri_filter_fill, tri_link,
-                         TREE_MAX_NODES, TreeState, tree_hook, tri_nearest)
+                         TREE_MAX_NODES, TreeState, tree_hook, tri_nearest, BestState, rect_best)
 
 L1_FULL_SCALE = 17000      # src/dct-sim.py:24
 HEADER = '#prot1 prot2 sim-domain sim-global'
@@ -1373,6 +1382,118 @@ class ProteinSearch:
         return tuple(out)
 
 
+class ReciprocalBest(ProteinSearch):
+    """The reciprocal best hits of two files, A (``--dct``) and B (``--db``): the first-pass ortholog call.  key(a, b) =
+    min(L1, 17000), L1 = the smallest L1 over all fingerprint pairs of the two proteins (``score='domain'``: ``protein_min``) or
+    the L1 of their two last fingerprints (``'global'``: ``l1_matrix`` of the last rows, the proteins without fingerprints flagged:
+    key 17000 against everything).  A pair is a hit when key <= bound; bound = 16999, every pair of similarity above 0, unless
+    ``min_cut`` gives min(``sim_bound(min_cut)``, 16999) -- so a protein without fingerprints never has or is a hit.  best_b(a) = the
+    hit of a that is smallest under the strict order (key, b), best_a(b) the same under (key, a): ties go to the lower index in
+    the file, as ``db_search`` ranks.  (a, b) is a reciprocal best hit iff best_b(a) == b and best_a(b) == a: a property of the
+    two files, whatever the tiles, the groups or the order in which the device ran.
+
+    ``ProteinSearch``'s walk with B as the database: B in protein groups of at most COL_ROWS fingerprints, A in tiles of at most
+    TILE_INTS entries (for ``'domain'`` the fingerprints of A go up in chunks of at most COL_ROWS).  Every tile goes straight to
+    ``rect_best``, which keeps the best column of every row and the best row of every column in the same pass (``BestState``);
+    merging across tiles and groups is the atomic minimum itself.  Nothing returns to the host before the end except the two
+    arrays, 8 bytes per protein.  An empty side or a bound below 0 (a cut-off above 1): no hits, no device.
+
+    ``best()`` = ``BestState.hits()``; ``pairs()`` = (a, b, key) of the reciprocal best hits, a ascending; ``lines`` / ``write`` =
+    ``db_search``'s lines for them (both scores from ``_pair_scores``)."""
+
+    def __init__(self, sid_a, idx_a, fps_a, sid_b, idx_b, fps_b, score: str = 'domain', min_cut=None):
+        if score not in SCORES:
+            raise ValueError(f'score must be one of {SCORES}')
+        super().__init__(fps_b, idx_b)
+        self.sid_a, self.idx_a, self.fps_a, self.sid_b = sid_a, np.asarray(idx_a, dtype=np.int64), fps_a, sid_b
+        self.n_a, self.n_b = max(len(self.idx_a) - 1, 0), max(len(self.idx) - 1, 0)
+        if max(self.n_a, self.n_b) >= 1 << 31:
+            raise ValueError('reciprocal best hits take fewer than 2^31 proteins on a side')
+        self.score = score
+        self.bound = L1_FULL_SCALE - 1 if min_cut is None else min(sim_bound(min_cut), L1_FULL_SCALE - 1)
+        self._best = None
+
+    def best(self):
+        """((best_b, its key) per protein of A, (best_a, its key) per protein of B): int64 numpy arrays, -1 in both where a protein
+        has no hit (built once)."""
+        if self._best is None:
+            if self.n_a == 0 or self.n_b == 0 or self.bound < 0:
+                self._best = tuple((np.full(n, -1, dtype=np.int64), np.full(n, -1, dtype=np.int64)) for n in (self.n_a, self.n_b))
+            else:
+                state = BestState(self.n_a, self.n_b)
+                (self._domain_tiles if self.score == 'domain' else self._global_tiles)(state)
+                self._best = state.hits()
+        return self._best
+
+    def _domain_tiles(self, state):
+        """``ProteinSearch._domain_parts``' loops with ``rect_best`` in the place of the selection."""
+        qidx = self.idx_a
+        chunks = list(_protein_groups(qidx, self.COL_ROWS))
+        resident = None
+        for g, (p0, p1) in enumerate(self.groups):
+            rows, sub_idx, _, _ = self._group(g, need_rows=True)
+            if rows is None:                                    # (a group without fingerprints: no hits)
+                continue
+            per = int(max(1, self.TILE_INTS // (p1 - p0)))
+            for c0, c1 in chunks:
+                if qidx[c1] == qidx[c0]:
+                    continue
+                if resident is not None and resident[0] == c0:
+                    q = resident[1]
+                else:
+                    q = to_device_int8(self.fps_a[qidx[c0]:qidx[c1]])
+                    if len(chunks) == 1:
+                        resident = (c0, q)
+                for t0 in range(c0, c1, per):
+                    t1 = min(c1, t0 + per)
+                    # (a protein without fingerprints: 0x7fffffff from protein_min, key 17000 -- no flags needed)
+                    tile = protein_min(q, qidx[t0:t1 + 1] - qidx[c0], rows, sub_idx)
+                    rect_best(tile, t0, p0, self.bound, state, cap=L1_FULL_SCALE)
+                    del tile
+
+    def _global_tiles(self, state):
+        """``ProteinSearch.search``'s loops of rank='global' with ``rect_best`` in the place of the selection."""
+        a_last, a_empty = _last_rows(self.fps_a[:int(self.idx_a[-1])], self.idx_a)
+        a_dev = to_device_int8(a_last) if self.n_a <= self.COL_ROWS else None
+        for g, (p0, p1) in enumerate(self.groups):
+            _, _, last, empty = self._group(g, need_rows=False)
+            rows = int(min(self.MAX_TILE_ROWS, max(1, self.TILE_INTS // (p1 - p0))))
+            for t0 in range(0, self.n_a, rows):
+                t1 = min(self.n_a, t0 + rows)
+                tile = l1_matrix(a_dev[t0:t1] if a_dev is not None else a_last[t0:t1], last)
+                rect_best(tile, t0, p0, self.bound, state, a_empty[t0:t1], empty, cap=L1_FULL_SCALE)
+                del tile
+
+    def pairs(self):
+        """(a, b, key): int64 numpy arrays of the reciprocal best hits, a ascending."""
+        (best_b, key), (best_a, _) = self.best()
+        a = np.flatnonzero(best_b >= 0)
+        a = a[best_a[best_b[a]] == a]
+        return a, best_b[a], key[a]
+
+    def lines(self, domains: bool = False, labels=None, db_labels=None) -> list:
+        """``db_search``'s lines of the reciprocal best hits, in ascending order of a.  ``domains``: with the domain pair behind
+        DCTdomain, named by ``labels`` / ``db_labels`` (``fingerprint_labels`` of the two files; default: the 1-based indices)."""
+        a, b, _ = self.pairs()
+        if len(a) == 0:
+            return []
+        mn, last, *args = self._pair_scores(self.fps_a, self.idx_a, a, b, domains)
+        if domains:
+            labels = labels if labels is not None else fingerprint_labels(self.sid_a, self.idx_a)
+            db_labels = db_labels if db_labels is not None else fingerprint_labels(self.sid_b, self.idx)
+        out = []
+        for k, (i, j, m, l) in enumerate(zip(a.tolist(), b.tolist(), mn, last)):
+            maxs, s = _scores(m, l)
+            tail = f' {_label(labels, self.idx_a[i], args[0][k])} {_label(db_labels, self.idx[j], args[1][k])}' if domains else ''
+            out.append(f'{self.sid_a[i]} {self.sid_b[j]} {maxs} {s}{tail}')
+        return out
+
+    def write(self, report, domains: bool = False, labels=None, db_labels=None):
+        """One ``report.line`` per reciprocal best hit."""
+        for text in self.lines(domains, labels, db_labels):
+            report.line(text)
+
+
 class Report:
     """Result lines to a file (header first) or to stdout."""
 
@@ -1559,6 +1680,25 @@ def tree_sim(npzfile: str, report: Report, score: str = 'domain', min_domain: fl
     Tree(sid, idx, fps, score=score, min_cut=min_domain if score == 'domain' else min_global).write(report.raw)
 
 
+@_reporting
+def rbh_sim(npzfile: str, dbfile: str, report: Report, score: str = 'domain', min_domain: float = None, min_global: float = None,
+            domains: bool = False, dom: str = None, db_dom: str = None):
+    """The reciprocal best hits of the proteins of ``npzfile`` and ``dbfile`` (``ReciprocalBest``) on DCTdomain (``score='domain'``) or
+    DCTglobal (``'global'``): one ``db_search`` line per pair, in the order of ``npzfile``.  ``min_domain`` / ``min_global``: the cut-off
+    of that score below which a pair is no hit; the other score's cut-off is an error.  ``domains`` / ``dom`` / ``db_dom``: as in
+    ``db_search``."""
+    if score not in SCORES:
+        raise ValueError(f'score must be one of {SCORES}')
+    if (min_global if score == 'domain' else min_domain) is not None:
+        raise ValueError('reciprocal best hits are ranked by one score: only that score\'s cut-off applies')
+    sid, idx, fps = _load_npz(npzfile)
+    db_sid, db_idx, db_fps = _load_npz(dbfile)
+    domains = domains or dom is not None or db_dom is not None
+    labels, db_labels = (_labels_of(sid, idx, dom), _labels_of(db_sid, db_idx, db_dom)) if domains else (None, None)
+    job = ReciprocalBest(sid, idx, fps, db_sid, db_idx, db_fps, score=score, min_cut=min_domain if score == 'domain' else min_global)
+    job.write(report, domains=domains, labels=labels, db_labels=db_labels)
+
+
 RANKS = ('global', 'domain')
 LINKAGES = ('single', 'greedy')
 LEVELS = ('protein', 'domain')
@@ -1577,10 +1717,29 @@ class _Parser(argparse.ArgumentParser):
     ``--dom`` / ``--db-dom``, ``--linkage``, ``--level`` and ``--no-whole``.  ``--reps-out`` is an error unless ``--assign`` is
     given, or ``--cluster --linkage greedy`` without ``--level domain``.  ``--tree`` prints the single-linkage tree of the file by
     one score: an error beside ``--pair``, ``--db``, ``--cluster``, ``--assign``, ``--rank``, ``--linkage``, ``--level``,
-    ``--no-whole``, ``--reps-out`` and ``--domains`` / ``--dom`` / ``--db-dom``, and beside the cut-off of the other score."""
+    ``--no-whole``, ``--reps-out`` and ``--domains`` / ``--dom`` / ``--db-dom``, and beside the cut-off of the other score.
+    ``--rbh`` prints the reciprocal best hits of ``--dct`` and ``--db`` by one score: an error without ``--db``, beside ``--pair``,
+    ``--cluster``, ``--assign``, ``--tree``, ``--rank``, ``--linkage``, ``--level``, ``--no-whole`` and ``--reps-out``, and beside the
+    cut-off of the other score; its own score's cut-off is allowed with it (the one case in which a cut-off goes with ``--db``)."""
 
     def parse_known_args(self, args=None, namespace=None):
         ns, rest = super().parse_known_args(args, namespace)
+        rbh = getattr(ns, 'rbh', None)
+        if rbh is not None:
+            beside = [flag for flag, given in (('--pair', ns.pair), ('--cluster', getattr(ns, 'cluster', False)),
+                                               ('--assign', getattr(ns, 'assign', None) is not None), ('--tree', getattr(ns, 'tree', None) is not None),
+                                               ('--rank', getattr(ns, 'rank', None) is not None),
+                                               ('--linkage', getattr(ns, 'linkage', None) is not None), ('--level', getattr(ns, 'level', None) is not None),
+                                               ('--no-whole', getattr(ns, 'no_whole', False)), ('--reps-out', getattr(ns, 'reps_out', None) is not None))
+                      if given]
+            if beside:
+                self.error(f'--rbh prints the reciprocal best hits of --dct and --db: not with {beside[0]}')
+            if not ns.db:
+                self.error('--rbh compares the proteins of --dct with those of another file: it needs --db')
+            if rbh == 'domain' and ns.min_global is not None:
+                self.error('--rbh domain ranks the hits by DCTdomain: its cut-off is --min-domain, not --min-global')
+            if rbh == 'global' and ns.min_domain is not None:
+                self.error('--rbh global ranks the hits by DCTglobal: its cut-off is --min-global, not --min-domain')
         tree = getattr(ns, 'tree', None)
         if tree is not None:
             beside = [flag for flag, given in (('--pair', ns.pair), ('--db', ns.db), ('--cluster', getattr(ns, 'cluster', False)),
@@ -1637,7 +1796,7 @@ class _Parser(argparse.ArgumentParser):
                 if getattr(ns, 'linkage', None) == 'greedy':
                     self.error('--level domain forms single-linkage clusters: not with --linkage greedy')
         for opt in ('min_domain', 'min_global'):
-            if getattr(ns, opt, None) is not None and (ns.pair or ns.db):
+            if getattr(ns, opt, None) is not None and (ns.pair or ns.db) and rbh is None:     # (--rbh takes its own score's cut-off)
                 self.error(f'--{opt.replace("_", "-")} applies to all-against-all only, not to --pair or --db')
         return ns, rest
 
@@ -1689,6 +1848,13 @@ def build_parser() -> argparse.ArgumentParser:
                     help='print the single-linkage tree of the file instead of all pairs: the n - 1 all-against-all lines that join the '
                          'proteins most similar first, by DCTdomain (domain, the default) or DCTglobal (global) -- cut at any score they '
                          'give the clusters --cluster finds there; --min-domain X (--min-global Y with global) takes no pair below it')
+    ap.add_argument('--rbh', nargs='?', choices=SCORES, const='domain', default=argparse.SUPPRESS,
+                    help='with --db: print the reciprocal best hits of the two files instead of every query\'s hits -- the pairs in which '
+                         'each protein is the other\'s best hit among the proteins of the other file, by DCTdomain (domain, the default) or '
+                         'DCTglobal (global), ties to the lower index in the file; one database-search line per pair, in the order of '
+                         '--dct.  A hit is a pair of similarity above 0, or with --min-domain X (--min-global Y with global) one not '
+                         'below it; --top and --threshold do not apply.  If --db names the same file as --dct, every protein with a '
+                         'fingerprint is its own best hit')
     return ap
 
 
@@ -1703,6 +1869,9 @@ def main(argv=None):
     t_work = time.time()
     if getattr(args, 'tree', None) is not None:
         tree_sim(args.dct, report, score=args.tree, min_domain=args.min_domain, min_global=args.min_global)
+    elif getattr(args, 'rbh', None) is not None:
+        rbh_sim(args.dct, args.db, report, score=args.rbh, min_domain=args.min_domain, min_global=args.min_global, domains=bool(domains),
+                dom=dom, db_dom=db_dom)
     elif assign is not None:
         assign_sim(args.dct, assign, report, min_domain=args.min_domain, min_global=args.min_global, reps_out=reps_out)
     elif args.pair:

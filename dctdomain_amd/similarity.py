@@ -539,6 +539,50 @@ def tree_hook(ts: TreeState):
                 *(t.data_ptr() if t.numel() else None for t in edges), ts.counter.data_ptr(), ts.edge_i.numel())
 
 
+BEST_NONE = -1                                 # best_row / best_col as torch shows them: int64 -1 = all 64 bits set = no hit
+
+
+class BestState:
+    """The device arrays of the reciprocal best hits of ``n_a`` x ``n_b`` proteins (``dctfp_rect_best``): ``best_row`` (one entry per
+    protein of A) and ``best_col`` (per protein of B), int64 as torch has no uint64 arithmetic: the packed hit
+    ``key << 32 | index on the other side``, ``BEST_NONE`` = none."""
+
+    def __init__(self, n_a: int, n_b: int, device=None):
+        device = device if device is not None else _dev()
+        self.best_row = torch.full((n_a,), BEST_NONE, dtype=torch.int64, device=device)
+        self.best_col = torch.full((n_b,), BEST_NONE, dtype=torch.int64, device=device)
+
+    def arrays(self, device):
+        """(n_a, n_b), the arrays checked."""
+        for t in (self.best_row, self.best_col):
+            if t.dtype != torch.int64 or t.dim() != 1 or not t.is_contiguous() or t.device != device:
+                raise ValueError('best_row / best_col must be contiguous 1-D int64 tensors on the device of the other arguments')
+        return self.best_row.numel(), self.best_col.numel()
+
+    def hits(self):
+        """((index, key) per protein of A, (index, key) per protein of B) as int64 numpy arrays: the best hit on the other side and
+        its key, -1 in both where there is none (two copies of 8 bytes per protein; the host waits)."""
+        out = []
+        for t in (self.best_row, self.best_col):
+            v = t.cpu().numpy()
+            none = v == BEST_NONE
+            out.append((np.where(none, -1, v & 0xffffffff), np.where(none, -1, v >> 32)))
+        return tuple(out)
+
+
+def rect_best(tile: torch.Tensor, row0: int, col0: int, bound: int, state: BestState, row_empty=None, col_empty=None, cap: int = 17000):
+    """Lowers ``state.best_row[row0 + r]`` to ``key << 32 | (col0 + c)`` and ``state.best_col[col0 + c]`` to ``key << 32 | (row0 + r)``
+    for every entry (r, c) of an L1 tile -- the full rectangle, protein row0 + r of one file against protein col0 + c of another --
+    with key = min(L1, cap) <= bound, ``cap`` for a row / column flagged empty (``dctfp_rect_best``).  Packed that way, the
+    minimum is the best hit with ties to the lower index; it does not depend on how the rectangle is cut into tiles."""
+    n_a, n_b = state.arrays(tile.device)
+    n_rows, n_cols, lead, _flags = _tri_filter_args(tile, row0, col0, bound, row_empty, col_empty, cap)
+    if row0 + n_rows > n_a or col0 + n_cols > n_b:
+        raise IndexError('tile outside the proteins of the state')
+    if n_rows and n_cols:
+        _launch(tile.device, 'dctfp_rect_best', *lead, state.best_row.data_ptr(), n_a, state.best_col.data_ptr(), n_b)
+
+
 GREEDY_NONE = 0x7fffffff                       # assign: no representative yet
 GREEDY_UNDECIDED, GREEDY_MEMBER, GREEDY_NEW, GREEDY_DONE = 0, 1, 2, 3
 

@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define DCTFP_VERSION 109 /* 0.1.9: dctfp_tri_nearest, dctfp_tree_hook */
+#define DCTFP_VERSION 110 /* 0.1.10: dctfp_rect_best */
 
 #define DCTFP_OK 0
 #define DCTFP_ERR_INVALID (-1) /* bad argument (null pointer, piece outside its sequence, ...) */
@@ -543,6 +543,28 @@ int dctfp_tri_nearest(dctfp_ctx* ctx, const int32_t* tile, int64_t n_rows, int64
  * boundary; DCTFP_ERR_LIMIT for n_nodes > 2^24.  n_nodes of 0: nothing to do. */
 int dctfp_tree_hook(dctfp_ctx* ctx, const int32_t* comp, uint64_t* best, int32_t* parent, int64_t n_nodes, int32_t* edge_i, int32_t* edge_j,
                     int32_t* edge_key, int32_t* counter, int64_t max_edges, void* stream);
+
+/* Reciprocal best hits of two files (dct-sim --db --rbh; not in the reference): per protein of file A its best hit in file B and
+ * per protein of B its best hit in A, both kept in one pass over an int32 tile of L1 values (dctfp_protein_min's output, or
+ * dctfp_l1_matrix of the last rows).  Entry (r, c), at tile[r * ld + c], is the L1 of protein row0 + r of A and protein col0 + c of
+ * B -- a FULL rectangle: no diagonal, no components, no owner.  key = cap when the row is flagged in row_empty, the column in
+ * col_empty (device uint8, one per row / column of the tile, either may be NULL) or the value is negative or >= cap, else the
+ * value: dctfp_tri_filter_count's rule.  Every entry with key <= bound lowers
+ *     best_row[row0 + r] to key << 32 | (col0 + c)   and   best_col[col0 + c] to key << 32 | (row0 + r)
+ * (device uint64, n_a / n_b entries, 8-byte aligned).  Unsigned 64-bit order of these words is the order (key, index): ties go
+ * to the lower protein.  All ones = none; the caller fills both arrays before the first tile.  Inside the launch the two arrays
+ * are touched by agent-scope relaxed atomics only (a load that skips a minimum which would change nothing, then the minimum),
+ * after a reduction in the workgroup: at most one global atomic per (row, 1024 columns) and per (column, 64 rows).  The result
+ * is a minimum over a set the inputs fix: it does not depend on the order in which the device ran, on how the rectangle is cut
+ * into tiles or on the order of the calls.  The tile is read with plain 4-byte loads: any ld >= n_cols, a column view of a wider
+ * tensor included.
+ * DCTFP_ERR_INVALID, with a message, for: a NULL ctx, tile, best_row or best_col; a negative count or offset; ld < n_cols;
+ * cap < 0, bound outside -1 .. cap; a cap above 4194302 (a row's minimum is packed as key << 10 | column in 32 bits); n_a or n_b
+ * negative or >= 2^31; row0 + n_rows > n_a or col0 + n_cols > n_b (checked on the host: the kernel bounds no index); a tile off a
+ * 4-byte or an array off an 8-byte boundary.  n_rows or n_cols of 0: nothing to do. */
+int dctfp_rect_best(dctfp_ctx* ctx, const int32_t* tile, int64_t n_rows, int64_t n_cols, int64_t ld, int64_t row0, int64_t col0,
+                    const uint8_t* row_empty, const uint8_t* col_empty, int32_t cap, int32_t bound, uint64_t* best_row, int64_t n_a,
+                    uint64_t* best_col, int64_t n_b, void* stream);
 
 /* query_db's search (src/query_db.py:75-87: a flat FAISS index forced to METRIC_L1 at :76, index.search at :87) without a
  * distance matrix: for query rows q (nq x d, row stride ldq) and database rows b (nb x d, stride ldb), int8 on the device, each
