@@ -287,6 +287,15 @@ class _DeviceRows:
         self.fps, self.idx = fps, idx
         total = int(idx[-1]) if len(idx) else 0
         self.resident = to_device_int8(fps[:total]) if 0 < total <= col_rows else None
+        self._idx_dev = None
+
+    @property
+    def idx_dev(self):
+        """The prefix array beside ``resident`` (made when first asked for)."""
+        if self._idx_dev is None:
+            import torch
+            self._idx_dev = torch.as_tensor(self.idx, device=self.resident.device)
+        return self._idx_dev
 
     def __call__(self, p0: int, p1: int):
         if self.resident is not None:
@@ -539,10 +548,23 @@ class FilteredPairs:
             yield i0, i1, tile, flags
             del tile                                            # (before the next one is made; the caller drops its own too)
 
+    def _scores_of(self, pi, pj, domains: bool = False, rows: _DeviceRows = None):
+        """Step 3 of the class text: device int32 (min L1, last L1) of the pairs (pi[k], pj[k]) (device int32) -- ``domains``: also
+        (arg_i, arg_j).  ``pair_min_device`` / ``pair_argmin_device`` on the file where it stays on the device, else
+        ``pair_scores``' chunks of at most COL_ROWS fingerprints, copied back.  ``rows``: as in ``tiles``."""
+        import torch
+        if rows is None:
+            rows = self.device_rows()
+        pairs = torch.stack([pi, pj], dim=1)
+        if rows.resident is not None:
+            score = pair_argmin_device if domains else pair_min_device
+            return score(rows.resident, rows.idx_dev, rows.resident, rows.idx_dev, pairs.contiguous())
+        return tuple(torch.as_tensor(v.astype(np.int32), device=pi.device)
+                     for v in pair_scores(self.fps, self.idx, pairs.cpu().numpy(), self.COL_ROWS, domains=domains))
+
     def chunks(self):
         """Yields device int32 tensors (i, j, min L1, last L1) of the surviving pairs, range of rows by range, in output order; with
         ``labels`` also (arg_i, arg_j), the rows of the minimum within the two proteins (-1: none)."""
-        import torch
         n = len(self.idx) - 1
         if n < 2 or min(self.bound_domain, self.bound_global) < 0:
             return
@@ -550,11 +572,8 @@ class FilteredPairs:
         longest = int(id_lens.max())
         bound = self.bound
         rows = self.device_rows()
-        resident = rows.resident
-        idx_dev = torch.as_tensor(self.idx, device=resident.device) if resident is not None else None
         for i0, i1, tile, flags in self.tiles(rows):
             col0 = i0 + 1
-            dev = tile.device
             count_dev = tri_filter_count(tile, i0, col0, bound, *flags)
             count = count_dev.cpu().numpy().astype(np.int64)
             # ranges of rows by the text they can make: count x (len_i + 14 + the longest id)
@@ -566,15 +585,7 @@ class FilteredPairs:
                 if m:
                     pi, pj = tri_filter_fill(tile[r0:r1], i0 + r0, col0, bound, count_dev[r0:r1], m,
                                              flags[0][r0:r1] if flags[0] is not None else None, flags[1])
-                    domains = self.row_labels is not None
-                    if resident is not None:
-                        scores = (pair_argmin_device if domains else pair_min_device)(resident, idx_dev, resident, idx_dev,
-                                                                                      torch.stack([pi, pj], dim=1).contiguous())
-                    else:
-                        host = torch.stack([pi, pj], dim=1).cpu().numpy()
-                        scores = tuple(torch.as_tensor(v.astype(np.int32), device=dev)
-                                       for v in pair_scores(self.fps, self.idx, host, self.COL_ROWS, domains=domains))
-                    chunk = (pi, pj) + tuple(scores)
+                    chunk = (pi, pj) + tuple(self._scores_of(pi, pj, self.row_labels is not None, rows))
                     if self.route == 'global' and self.bound_domain < L1_FULL_SCALE:      # (the other cut-off; the order stays)
                         keep = chunk[2].clamp(max=L1_FULL_SCALE) <= self.bound_domain
                         chunk = tuple(t[keep].contiguous() for t in chunk)
@@ -594,26 +605,41 @@ class FilteredPairs:
 
     def write(self, sink):
         """Calls ``sink(memoryview)`` with the text of each range of rows that has any, in order."""
-        import torch
-        ids = table = labels = first_row = None
-        la = lb = None
         out = TextStream(sink, room=lambda nbytes: max(nbytes, 1 << 16))
-        for pi, pj, mn, last, *args in self.chunks():
-            if ids is None:
-                ids = LineIds([f'{s}' for s in self.sid])
-                table = torch.as_tensor(score_table(), device=pi.device)
-                if self.row_labels is not None:                 # (one label per fingerprint row, then the "no pair" entry)
-                    labels = LineIds(list(self.row_labels) + [NO_DOMAIN], device=pi.device)
-                    first_row = torch.as_tensor(self.idx[:-1].astype(np.int32), device=pi.device)
-            if labels is not None:
-                la, lb = (torch.where(arg >= 0, first_row[p.long()] + arg, torch.full_like(arg, len(self.row_labels))).contiguous()
-                          for p, arg in zip((pi, pj), args))
-            off = pair_line_offsets(pi, pj, ids, la, lb, labels)
-            nbytes = int(off[-1])
-            text = torch.empty(nbytes, dtype=torch.uint8, device=pi.device)
-            pair_lines(pi, pj, mn, last, ids, table, off, text, la, lb, labels)
-            out.hand_over(text, nbytes)                         # (the previous range goes out while the device works on this one)
+        lines = None
+        for chunk in self.chunks():
+            lines = lines or _PairText(self, out, chunk[0].device)
+            lines.write(*chunk)                                 # (the previous range goes out while the device works on this one)
         out.close()
+
+
+class _PairText:
+    """The pair lines of one ``write`` of a ``FilteredPairs``: the ids, the score table and, with ``row_labels``, the label ids and
+    every protein's first row go to the device once; ``write`` composes the lines of one list of pairs there (step 4 of the class
+    text) and hands them to the stream."""
+
+    def __init__(self, job, out: TextStream, dev):
+        import torch
+        self.out = out
+        self.ids = LineIds([f'{s}' for s in job.sid])
+        self.table = torch.as_tensor(score_table(), device=dev)
+        self.labels = self.first_row = None
+        if job.row_labels is not None:                          # (one label per fingerprint row, then the "no pair" entry)
+            self.labels = LineIds(list(job.row_labels) + [NO_DOMAIN], device=dev)
+            self.first_row = torch.as_tensor(job.idx[:-1].astype(np.int32), device=dev)
+            self.none = len(job.row_labels)
+
+    def write(self, pi, pj, mn, last, *args):
+        import torch
+        la = lb = None
+        if self.labels is not None:
+            la, lb = (torch.where(arg >= 0, self.first_row[p.long()] + arg, torch.full_like(arg, self.none)).contiguous()
+                      for p, arg in zip((pi, pj), args))
+        off = pair_line_offsets(pi, pj, self.ids, la, lb, self.labels)
+        nbytes = int(off[-1])
+        text = torch.empty(nbytes, dtype=torch.uint8, device=pi.device)
+        pair_lines(pi, pj, mn, last, self.ids, self.table, off, text, la, lb, self.labels)
+        self.out.hand_over(text, nbytes)
 
 
 def _ragged_gather(raw: np.ndarray, starts: np.ndarray, lens: np.ndarray) -> np.ndarray:
@@ -671,28 +697,57 @@ def _id_lines(sid, rep, member, chunk_bytes: int):
     if n == 0:
         return
     wide = _ascii_id_rows(sid)
-    if wide is not None:
-        yield from _ascii_lines(*wide, rep, member, chunk_bytes)
-        return
-    enc = [f'{s}'.encode('utf8') for s in sid]
+    yield from _ascii_lines(*wide, rep, member, chunk_bytes) if wide is not None else _field_lines(sid, [rep, member], chunk_bytes)
+
+
+def _field_lines(table, fields, chunk_bytes: int):
+    """Lines made of fields that all draw from one ``table`` of strings: line t is ``' '.join(table[f[t]] for f in fields) + '\n'``,
+    ``fields`` = k int64 index arrays of one length.  Yields uint8 arrays of whole lines of about ``chunk_bytes`` each (at least
+    one line), gathered from the table's bytes by index arithmetic: no Python loop per line."""
+    enc = [f'{s}'.encode('utf8') for s in table]
     lens = np.fromiter((len(e) for e in enc), dtype=np.int64, count=len(enc))
     off = np.zeros(len(enc) + 1, dtype=np.int64)
     np.cumsum(lens, out=off[1:])
-    raw = np.frombuffer(b''.join(enc) + b' \n', dtype=np.uint8)   # (the two separators sit behind the ids)
+    raw = np.frombuffer(b''.join(enc) + b' \n', dtype=np.uint8)   # (the two separators sit behind the table)
     del enc
     space, newline = int(off[-1]), int(off[-1]) + 1
-    ends = np.cumsum(lens[rep] + lens[member] + 2)
-    t0 = 0
+    ends = np.cumsum(sum(lens[f] for f in fields) + len(fields))
+    t0, n = 0, len(ends)
     while t0 < n:
         t1 = min(n, max(t0 + 1, int(np.searchsorted(ends, (ends[t0 - 1] if t0 else 0) + chunk_bytes, 'right'))))
-        r, m = rep[t0:t1], member[t0:t1]
         one = np.ones(t1 - t0, dtype=np.int64)
-        starts = np.stack([off[r], space * one, off[m], newline * one], axis=1).ravel()
-        yield _ragged_gather(raw, starts, np.stack([lens[r], one, lens[m], one], axis=1).ravel())
+        part = [np.asarray(f[t0:t1], dtype=np.int64) for f in fields]
+        starts = np.stack([v for f in part for v in (off[f], space * one)], axis=1)
+        sizes = np.stack([v for f in part for v in (lens[f], one)], axis=1)
+        starts[:, -1] = newline
+        yield _ragged_gather(raw, starts.ravel(), sizes.ravel())
         t0 = t1
 
 
-class Clusters(FilteredPairs):
+class _ProteinClusters(FilteredPairs):
+    """What ``Clusters`` and ``Representatives`` share: cut-offs without domain pairs (nothing is printed per pair), the answers
+    that need no tile, and the text."""
+
+    def __init__(self, sid, idx, fps, min_domain=None, min_global=None):
+        super().__init__(sid, idx, fps, min_domain=min_domain, min_global=min_global)
+
+    def _plain_labels(self):
+        """The labels where no pair has to be looked at -- every protein its own for fewer than two proteins or a bound below 0 (a
+        cut-off above 1), all 0 where no bound excludes anything -- else None."""
+        n = len(self.idx) - 1
+        if n < 2 or min(self.bound_domain, self.bound_global) < 0:
+            return np.arange(max(n, 0), dtype=np.int32)
+        if min(self.bound_domain, self.bound_global) >= L1_FULL_SCALE:
+            return np.zeros(n, dtype=np.int32)
+        return None
+
+    def write(self, sink, labels=None):
+        """Calls ``sink(memoryview)`` with the text (of ``labels()``, or of labels it gave before), whole lines at a time, in order."""
+        for text in cluster_lines(self.sid, self.labels() if labels is None else labels):
+            sink(memoryview(text))
+
+
+class Clusters(_ProteinClusters):
     """Single-linkage clusters of one file at cut-offs: the connected components of the graph whose nodes are all proteins and
     whose edges are exactly ``FilteredPairs``' pairs, joined on the device in a union-find forest (``parent``, n int32) instead of
     listed.  ``labels()[i]`` = the index of the representative of protein i = the smallest index in its cluster: a property of the
@@ -706,17 +761,12 @@ class Clusters(FilteredPairs):
 
     Then ``cluster_labels`` on the device and one copy of n int32.  The text is composed on the host (``cluster_lines``), O(n)."""
 
-    def __init__(self, sid, idx, fps, min_domain=None, min_global=None):
-        super().__init__(sid, idx, fps, min_domain=min_domain, min_global=min_global)    # (no domain pairs: nothing is printed per pair)
-
     def labels(self) -> np.ndarray:
-        n = len(self.idx) - 1
-        if n < 2 or min(self.bound_domain, self.bound_global) < 0:
-            return np.arange(max(n, 0), dtype=np.int32)
-        if min(self.bound_domain, self.bound_global) >= L1_FULL_SCALE:
-            return np.zeros(n, dtype=np.int32)
+        plain = self._plain_labels()
+        if plain is not None:
+            return plain
         import torch
-        parent = torch.arange(n, dtype=torch.int32, device=torch.device('cuda', torch.cuda.current_device()))
+        parent = torch.arange(len(self.idx) - 1, dtype=torch.int32, device=torch.device('cuda', torch.cuda.current_device()))
         if max(self.bound_domain, self.bound_global) < L1_FULL_SCALE:
             for pi, pj, *_ in self.chunks():
                 link_pairs(pi, pj, parent)
@@ -725,11 +775,6 @@ class Clusters(FilteredPairs):
                 tri_link(tile, i0, i0 + 1, self.bound, parent, *flags)
                 del tile
         return cluster_labels(parent).cpu().numpy()
-
-    def write(self, sink):
-        """Calls ``sink(memoryview)`` with the text, whole lines at a time, in order."""
-        for text in cluster_lines(self.sid, self.labels()):
-            sink(memoryview(text))
 
 
 SCORES = ('domain', 'global')
@@ -833,26 +878,15 @@ class Tree(FilteredPairs):
             return
         import torch
         dev = torch.device('cuda', torch.cuda.current_device())
-        ids = LineIds([f'{s}' for s in self.sid])
-        table = torch.as_tensor(score_table(), device=dev)
-        resident = self.resident_rows()
-        idx_dev = torch.as_tensor(self.idx, device=dev) if resident is not None else None
-        ends = np.cumsum(ids.lens[i] + ids.lens[j] + 14)
+        rows = self.device_rows()
         out = TextStream(sink, room=lambda nbytes: max(nbytes, 1 << 16))
+        lines = _PairText(self, out, dev)
+        ends = np.cumsum(lines.ids.lens[i] + lines.ids.lens[j] + 14)
         k0 = 0
         while k0 < len(i):
             k1 = min(len(i), max(k0 + 1, int(np.searchsorted(ends, (ends[k0 - 1] if k0 else 0) + self.TEXT_BYTES, 'right'))))
-            pairs = np.stack([i[k0:k1], j[k0:k1]], axis=1)
-            pi, pj = (torch.as_tensor(np.ascontiguousarray(pairs[:, c]).astype(np.int32), device=dev) for c in (0, 1))
-            if resident is not None:
-                mn, last = pair_min_device(resident, idx_dev, resident, idx_dev, torch.stack([pi, pj], dim=1).contiguous())
-            else:
-                mn, last = (torch.as_tensor(v.astype(np.int32), device=dev) for v in pair_scores(self.fps, self.idx, pairs, self.COL_ROWS))
-            off = pair_line_offsets(pi, pj, ids)
-            nbytes = int(off[-1])
-            text = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-            pair_lines(pi, pj, mn, last, ids, table, off, text)
-            out.hand_over(text, nbytes)
+            pi, pj = (torch.as_tensor(v[k0:k1].astype(np.int32), device=dev) for v in (i, j))
+            lines.write(pi, pj, *self._scores_of(pi, pj, rows=rows))
             k0 = k1
         out.close()
 
@@ -881,24 +915,8 @@ def domain_cluster_lines(sid, idx, labels, row_labels, chunk_bytes: int = 1 << 2
     if (labels[rep] != rep).any():
         raise IndexError('a representative that is no node of its own cluster')
     owner = np.repeat(np.arange(len(idx) - 1, dtype=np.int64), np.diff(idx))
-    enc = [f'{s}'.encode('utf8') for s in sid] + [f'{s}'.encode('utf8') for s in row_labels]
-    lens = np.fromiter((len(e) for e in enc), dtype=np.int64, count=len(enc))
-    off = np.zeros(len(enc) + 1, dtype=np.int64)
-    np.cumsum(lens, out=off[1:])
-    raw = np.frombuffer(b''.join(enc) + b' \n', dtype=np.uint8)     # (the two separators sit behind the ids and the labels)
-    del enc
-    space, newline, n_ids = int(off[-1]), int(off[-1]) + 1, len(idx) - 1
-    ends = np.cumsum(lens[owner[rep]] + lens[owner[member]] + lens[n_ids + rep] + lens[n_ids + member] + 4)
-    t0, m = 0, len(member)
-    while t0 < m:
-        t1 = min(m, max(t0 + 1, int(np.searchsorted(ends, (ends[t0 - 1] if t0 else 0) + chunk_bytes, 'right'))))
-        one = np.ones(t1 - t0, dtype=np.int64)
-        fields = [owner[rep[t0:t1]], owner[member[t0:t1]], n_ids + rep[t0:t1], n_ids + member[t0:t1]]
-        starts = np.stack([v for f in fields for v in (off[f], space * one)], axis=1)
-        sizes = np.stack([v for f in fields for v in (lens[f], one)], axis=1)
-        starts[:, -1] = newline
-        yield _ragged_gather(raw, starts.ravel(), sizes.ravel())
-        t0 = t1
+    n_ids = len(idx) - 1
+    yield from _field_lines(list(sid) + list(row_labels), [owner[rep], owner[member], n_ids + rep, n_ids + member], chunk_bytes)
 
 
 class DomainClusters:
@@ -970,7 +988,7 @@ class DomainClusters:
             sink(memoryview(text))
 
 
-class Representatives(FilteredPairs):
+class Representatives(_ProteinClusters):
     """Greedy incremental clusters of one file at cut-offs, in file order, over the graph ``Clusters`` takes the components of
     (nodes: all proteins; edges: exactly ``FilteredPairs``' pairs):
 
@@ -995,9 +1013,7 @@ class Representatives(FilteredPairs):
 
     ``rounds`` = the rounds of the last ``labels()`` over all ranges.  The text is ``Clusters``': ``cluster_lines``."""
 
-    def __init__(self, sid, idx, fps, min_domain=None, min_global=None):
-        super().__init__(sid, idx, fps, min_domain=min_domain, min_global=min_global)
-        self.rounds = 0
+    rounds = 0
 
     def _decide_range(self, gs, i0: int, i1: int, mark):
         """Rounds over the nodes [i0, i1); ``mark(next_round)`` = the mark launch of the range's rows."""
@@ -1017,10 +1033,9 @@ class Representatives(FilteredPairs):
     def labels(self) -> np.ndarray:
         n = len(self.idx) - 1
         self.rounds = 0
-        if n < 2 or min(self.bound_domain, self.bound_global) < 0:
-            return np.arange(max(n, 0), dtype=np.int32)
-        if min(self.bound_domain, self.bound_global) >= L1_FULL_SCALE:
-            return np.zeros(n, dtype=np.int32)
+        plain = self._plain_labels()
+        if plain is not None:
+            return plain
         gs = GreedyState(n)
         self._round = 1                                         # the next unused round number (0 = the cover pass, blocked starts as 0)
         done = 0                                                # every node below is decided and has marked
@@ -1036,11 +1051,6 @@ class Representatives(FilteredPairs):
                 del tile
         greedy_decide(gs, done, n, self._round)                 # no later neighbour, no stamp of this round: whoever is not marked represents itself
         return gs.assign.cpu().numpy()
-
-    def write(self, sink):
-        """Calls ``sink(memoryview)`` with the text, whole lines at a time, in order."""
-        for text in cluster_lines(self.sid, self.labels()):
-            sink(memoryview(text))
 
 
 def _all_ids(rep_sid, sid):
@@ -1304,6 +1314,55 @@ class ProteinSearch:
             self._resident[g] = entry
         return entry
 
+    def tiles(self, a_fps, a_idx, route: str, bare: bool = True):
+        """The walk over the rectangle A x database, A = the proteins of ``a_fps`` / ``a_idx``: yields, per database group and per
+        tile of A, (t0, p0, tile, (row flags, column flags)) -- ``tile`` = device int32, proteins [t0, t1) of A x [p0, p1) of the
+        database; the flags = ``_last_rows``' of the two sides (uint8, 1 = a protein without fingerprints).
+        - ``route='global'``: the L1 of the two last rows (``l1_matrix``; a zero row where a protein has none: the flags say so), A
+          in tiles of at most TILE_INTS entries and MAX_TILE_ROWS rows; A's last rows stay on the device when A has at most
+          COL_ROWS proteins.
+        - ``route='domain'``: the minimum over all fingerprint pairs (``protein_min``; 0x7fffffff where a protein has none), the
+          fingerprints of A going up in chunks of at most COL_ROWS (a single chunk once), each in tiles of at most TILE_INTS
+          entries.  ``bare=False`` leaves out the tiles whose database group or chunk of A has no fingerprint at all, which hold
+          nothing else; ``search`` takes them, because a query's first ``top`` hits are printed whatever they score."""
+        import torch
+        aidx = np.asarray(a_idx, dtype=np.int64)
+        na = len(aidx) - 1
+        if route == 'global':
+            a_last, a_empty = _last_rows(a_fps, aidx)
+            a_dev = to_device_int8(a_last) if na <= self.COL_ROWS else None
+            for g, (p0, p1) in enumerate(self.groups):
+                _, _, last, empty = self._group(g, need_rows=False)
+                per = int(min(self.MAX_TILE_ROWS, max(1, self.TILE_INTS // (p1 - p0))))
+                for t0 in range(0, na, per):
+                    t1 = min(na, t0 + per)
+                    yield t0, p0, l1_matrix(a_dev[t0:t1] if a_dev is not None else a_last[t0:t1], last), (a_empty[t0:t1], empty)
+            return
+        if route != 'domain':
+            raise ValueError(f'route must be one of {RANKS}')
+        a_empty = (aidx[1:] == aidx[:-1]).astype(np.uint8)
+        chunks = list(_protein_groups(aidx, self.COL_ROWS))
+        resident = None
+        for g, (p0, p1) in enumerate(self.groups):
+            rows, sub_idx, _, empty = self._group(g, need_rows=True)
+            if rows is None:                                    # (a group without fingerprints: every pair is empty)
+                if not bare:
+                    continue
+                rows = torch.empty((0, self.fps.shape[1]), dtype=torch.int8, device=torch.cuda.current_device())
+            per = int(max(1, self.TILE_INTS // (p1 - p0)))
+            for c0, c1 in chunks:
+                if not bare and aidx[c1] == aidx[c0]:
+                    continue
+                if resident is not None and resident[0] == c0:
+                    a = resident[1]
+                else:
+                    a = to_device_int8(a_fps[aidx[c0]:aidx[c1]])
+                    if len(chunks) == 1:
+                        resident = (c0, a)
+                for t0 in range(c0, c1, per):
+                    t1 = min(c1, t0 + per)
+                    yield t0, p0, protein_min(a, aidx[t0:t1 + 1] - aidx[c0], rows, sub_idx), (a_empty[t0:t1], empty)
+
     def search(self, query_fps, query_idx, top: int, threshold: float, rank: str = 'global', domains: bool = False):
         if rank not in RANKS:
             raise ValueError(f'rank must be one of {RANKS}')
@@ -1314,17 +1373,10 @@ class ProteinSearch:
             return [(np.zeros(0, dtype=np.int64),) * (5 if domains else 3) for _ in range(nq)]
         bound = sim_bound(threshold)
         top1 = max(top, 1)      # (top <= 0: the reference prints the threshold hits only -- trimmed after the merge)
-        q_last, q_empty = _last_rows(query_fps, qidx)
         parts = [[] for _ in range(nq)]
-        if rank == 'domain':
-            self._domain_parts(query_fps, qidx, q_empty, top1, bound, parts)
-        else:
-            for g, (p0, p1) in enumerate(self.groups):
-                _, _, last, empty = self._group(g, need_rows=False)
-                rows = int(min(self.MAX_TILE_ROWS, max(1, self.TILE_INTS // (p1 - p0))))
-                for t0 in range(0, nq, rows):
-                    t1 = min(nq, t0 + rows)
-                    _add_hits(parts, t0, p0, *threshold_select(l1_matrix(q_last[t0:t1], last), top1, bound, q_empty[t0:t1], empty))
+        for t0, p0, tile, flags in self.tiles(query_fps, qidx, rank):
+            _add_hits(parts, t0, p0, *threshold_select(tile, top1, bound, *flags))
+            del tile
         merged = (merge_candidates(pq, top1, bound) for pq in parts)
         hits = [c if top >= 1 else c[k <= bound] for k, c in merged]
         del parts
@@ -1334,31 +1386,6 @@ class ProteinSearch:
         scores = self._pair_scores(query_fps, qidx, q_of, db_of, domains)
         bounds = np.concatenate([[0], np.cumsum(counts)])
         return [(db_of[a:b],) + tuple(v[a:b] for v in scores) for a, b in zip(bounds[:-1], bounds[1:])]
-
-    def _domain_parts(self, query_fps, qidx, q_empty, top1: int, bound: int, parts):
-        """Step 1-2 of rank='domain': per database group (its fingerprints on the device) and query tile (at most TILE_INTS
-        protein pairs; the query fingerprints go up in chunks of at most COL_ROWS), the protein-minimum tile and its
-        selection, appended to ``parts``."""
-        import torch
-        chunks = list(_protein_groups(qidx, self.COL_ROWS))
-        resident = None
-        for g, (p0, p1) in enumerate(self.groups):
-            rows, sub_idx, _, empty = self._group(g, need_rows=True)
-            if rows is None:                                    # (a group without fingerprints: every pair is empty)
-                rows = torch.empty((0, self.fps.shape[1]), dtype=torch.int8, device=torch.cuda.current_device())
-            per = int(max(1, self.TILE_INTS // (p1 - p0)))
-            for c0, c1 in chunks:
-                if resident is not None and resident[0] == c0:
-                    q = resident[1]
-                else:
-                    q = to_device_int8(query_fps[qidx[c0]:qidx[c1]])
-                    if len(chunks) == 1:
-                        resident = (c0, q)
-                for t0 in range(c0, c1, per):
-                    t1 = min(c1, t0 + per)
-                    tile = protein_min(q, qidx[t0:t1 + 1] - qidx[c0], rows, sub_idx)
-                    _add_hits(parts, t0, p0, *threshold_select(tile, top1, bound, q_empty[t0:t1], empty))
-                    del tile
 
     def _pair_scores(self, query_fps, qidx, q_of, db_of, domains: bool = False):
         """(min, last) L1 of the pairs (query q_of[k], database protein db_of[k]): per database group, per chunk of queries.
@@ -1421,48 +1448,12 @@ class ReciprocalBest(ProteinSearch):
                 self._best = tuple((np.full(n, -1, dtype=np.int64), np.full(n, -1, dtype=np.int64)) for n in (self.n_a, self.n_b))
             else:
                 state = BestState(self.n_a, self.n_b)
-                (self._domain_tiles if self.score == 'domain' else self._global_tiles)(state)
+                for t0, p0, tile, flags in self.tiles(self.fps_a, self.idx_a, self.score, bare=False):
+                    # (the domain tile holds 0x7fffffff, key 17000, for a protein without fingerprints: no flags needed)
+                    rect_best(tile, t0, p0, self.bound, state, *(flags if self.score == 'global' else ()), cap=L1_FULL_SCALE)
+                    del tile
                 self._best = state.hits()
         return self._best
-
-    def _domain_tiles(self, state):
-        """``ProteinSearch._domain_parts``' loops with ``rect_best`` in the place of the selection."""
-        qidx = self.idx_a
-        chunks = list(_protein_groups(qidx, self.COL_ROWS))
-        resident = None
-        for g, (p0, p1) in enumerate(self.groups):
-            rows, sub_idx, _, _ = self._group(g, need_rows=True)
-            if rows is None:                                    # (a group without fingerprints: no hits)
-                continue
-            per = int(max(1, self.TILE_INTS // (p1 - p0)))
-            for c0, c1 in chunks:
-                if qidx[c1] == qidx[c0]:
-                    continue
-                if resident is not None and resident[0] == c0:
-                    q = resident[1]
-                else:
-                    q = to_device_int8(self.fps_a[qidx[c0]:qidx[c1]])
-                    if len(chunks) == 1:
-                        resident = (c0, q)
-                for t0 in range(c0, c1, per):
-                    t1 = min(c1, t0 + per)
-                    # (a protein without fingerprints: 0x7fffffff from protein_min, key 17000 -- no flags needed)
-                    tile = protein_min(q, qidx[t0:t1 + 1] - qidx[c0], rows, sub_idx)
-                    rect_best(tile, t0, p0, self.bound, state, cap=L1_FULL_SCALE)
-                    del tile
-
-    def _global_tiles(self, state):
-        """``ProteinSearch.search``'s loops of rank='global' with ``rect_best`` in the place of the selection."""
-        a_last, a_empty = _last_rows(self.fps_a[:int(self.idx_a[-1])], self.idx_a)
-        a_dev = to_device_int8(a_last) if self.n_a <= self.COL_ROWS else None
-        for g, (p0, p1) in enumerate(self.groups):
-            _, _, last, empty = self._group(g, need_rows=False)
-            rows = int(min(self.MAX_TILE_ROWS, max(1, self.TILE_INTS // (p1 - p0))))
-            for t0 in range(0, self.n_a, rows):
-                t1 = min(self.n_a, t0 + rows)
-                tile = l1_matrix(a_dev[t0:t1] if a_dev is not None else a_last[t0:t1], last)
-                rect_best(tile, t0, p0, self.bound, state, a_empty[t0:t1], empty, cap=L1_FULL_SCALE)
-                del tile
 
     def pairs(self):
         """(a, b, key): int64 numpy arrays of the reciprocal best hits, a ascending."""
@@ -1523,6 +1514,14 @@ class Report:
             self.out.flush()
 
 
+def _header(base: str, level: str = None, domains=False) -> str:
+    """The header of a report: ``base`` (HEADER, or CLUSTER_HEADER for the modes that print clusters) with the two columns of the
+    domain pair where the lines carry them."""
+    if base == CLUSTER_HEADER:
+        return DOMAIN_CLUSTER_HEADER if level == 'domain' else base
+    return DOMAIN_HEADER if base == HEADER and domains else base
+
+
 def _reporting(fn=None, *, header: str = HEADER):
     """The mode functions keep the reference's signature -- the last argument may be an output path or
     ``None`` (stdout) -- and also take an open ``Report``.  Keyword arguments (options beyond the reference's) pass through.
@@ -1535,9 +1534,7 @@ def _reporting(fn=None, *, header: str = HEADER):
         if isinstance(output, Report):
             return fn(*head, output, **kw)
         # (a report opened here for a call that asks for the domain pair carries the two extra column names)
-        wide = header == HEADER and any(kw.get(k) for k in ('domains', 'dom', 'db_dom'))
-        rows = header == CLUSTER_HEADER and kw.get('level') == 'domain'
-        report = Report(output, DOMAIN_HEADER if wide else DOMAIN_CLUSTER_HEADER if rows else header)
+        report = Report(output, _header(header, kw.get('level'), any(kw.get(k) for k in ('domains', 'dom', 'db_dom'))))
         try:
             return fn(*head, report, **kw)
         finally:
@@ -1640,13 +1637,11 @@ def cluster_sim(npzfile: str, report: Report, min_domain: float = None, min_glob
     if not whole or dom is not None:
         raise ValueError('whole and dom apply to level="domain" only')
     sid, idx, fps = _load_npz(npzfile)
-    if reps_out is None:
-        (Representatives if linkage == 'greedy' else Clusters)(sid, idx, fps, min_domain=min_domain, min_global=min_global).write(report.raw)
-        return
-    labels = Representatives(sid, idx, fps, min_domain=min_domain, min_global=min_global).labels()
-    for text in cluster_lines(sid, labels):
-        report.raw(memoryview(text))
-    write_reps(reps_out, [(sid, idx, fps, _npz_dom(npzfile, int(idx[-1])), np.flatnonzero(labels == np.arange(len(labels))))])
+    job = (Representatives if linkage == 'greedy' else Clusters)(sid, idx, fps, min_domain=min_domain, min_global=min_global)
+    labels = job.labels()
+    job.write(report.raw, labels)
+    if reps_out is not None:
+        write_reps(reps_out, [(sid, idx, fps, _npz_dom(npzfile, int(idx[-1])), np.flatnonzero(labels == np.arange(len(labels))))])
 
 
 @_reporting(header=CLUSTER_HEADER)
@@ -1667,17 +1662,23 @@ def assign_sim(npzfile: str, repfile: str, report: Report, min_domain: float = N
                               (sid, idx, fps, _npz_dom(npzfile, int(idx[-1])), np.flatnonzero(labels == m + np.arange(len(labels))))])
 
 
+def _cut_of(score: str, min_domain, min_global, what: str):
+    """The cut-off of ``score`` for a mode that goes by one score; ValueError for another score or the other score's cut-off."""
+    if score not in SCORES:
+        raise ValueError(f'score must be one of {SCORES}')
+    if (min_global if score == 'domain' else min_domain) is not None:
+        raise ValueError(f'{what} by one score: only that score\'s cut-off applies')
+    return min_domain if score == 'domain' else min_global
+
+
 @_reporting
 def tree_sim(npzfile: str, report: Report, score: str = 'domain', min_domain: float = None, min_global: float = None):
     """The single-linkage tree of the file (``Tree``) on DCTdomain (``score='domain'``) or DCTglobal (``'global'``): one all-against-all
     line per edge, most similar first.  ``min_domain`` / ``min_global``: the cut-off of that score below which no edge is taken
     (the forest then has a tree per cluster at that cut-off); the other score's cut-off is an error."""
-    if score not in SCORES:
-        raise ValueError(f'score must be one of {SCORES}')
-    if (min_global if score == 'domain' else min_domain) is not None:
-        raise ValueError('the tree orders the pairs by one score: only that score\'s cut-off applies')
+    min_cut = _cut_of(score, min_domain, min_global, 'the tree orders the pairs')
     sid, idx, fps = _load_npz(npzfile)
-    Tree(sid, idx, fps, score=score, min_cut=min_domain if score == 'domain' else min_global).write(report.raw)
+    Tree(sid, idx, fps, score=score, min_cut=min_cut).write(report.raw)
 
 
 @_reporting
@@ -1687,21 +1688,42 @@ def rbh_sim(npzfile: str, dbfile: str, report: Report, score: str = 'domain', mi
     DCTglobal (``'global'``): one ``db_search`` line per pair, in the order of ``npzfile``.  ``min_domain`` / ``min_global``: the cut-off
     of that score below which a pair is no hit; the other score's cut-off is an error.  ``domains`` / ``dom`` / ``db_dom``: as in
     ``db_search``."""
-    if score not in SCORES:
-        raise ValueError(f'score must be one of {SCORES}')
-    if (min_global if score == 'domain' else min_domain) is not None:
-        raise ValueError('reciprocal best hits are ranked by one score: only that score\'s cut-off applies')
+    min_cut = _cut_of(score, min_domain, min_global, 'reciprocal best hits are ranked')
     sid, idx, fps = _load_npz(npzfile)
     db_sid, db_idx, db_fps = _load_npz(dbfile)
     domains = domains or dom is not None or db_dom is not None
     labels, db_labels = (_labels_of(sid, idx, dom), _labels_of(db_sid, db_idx, db_dom)) if domains else (None, None)
-    job = ReciprocalBest(sid, idx, fps, db_sid, db_idx, db_fps, score=score, min_cut=min_domain if score == 'domain' else min_global)
+    job = ReciprocalBest(sid, idx, fps, db_sid, db_idx, db_fps, score=score, min_cut=min_cut)
     job.write(report, domains=domains, labels=labels, db_labels=db_labels)
 
 
 RANKS = ('global', 'domain')
 LINKAGES = ('single', 'greedy')
 LEVELS = ('protein', 'domain')
+
+
+def _dest(flag: str) -> str:
+    return flag[2:].replace('-', '_')
+
+
+def _is_set(value) -> bool:
+    return value is not None
+
+
+# flag -> is it on the command line, by its value in the namespace (None where the namespace has no such key: the options added
+# with ``argparse.SUPPRESS``)
+_GIVEN = {'--pair': bool, '--db': bool, '--cluster': bool, '--domains': bool, '--no-whole': bool,
+          '--assign': _is_set, '--tree': _is_set, '--rank': _is_set, '--linkage': _is_set, '--level': _is_set, '--reps-out': _is_set,
+          '--dom': _is_set, '--db-dom': _is_set}
+# mode -> (what it does; for a mode that takes a score, what that score does; the flags it refuses, in the order they are named).
+# The modes are checked in this order.
+_MODES = {'--rbh': ('prints the reciprocal best hits of --dct and --db', 'ranks the hits',
+                    ('--pair', '--cluster', '--assign', '--tree', '--rank', '--linkage', '--level', '--no-whole', '--reps-out')),
+          '--tree': ('prints the single-linkage tree of --dct', 'orders the pairs',
+                     ('--pair', '--db', '--cluster', '--assign', '--rank', '--linkage', '--level', '--no-whole', '--reps-out', '--domains',
+                      '--dom', '--db-dom')),
+          '--assign': ('places the proteins of --dct on a fixed set of representatives', None,
+                       ('--pair', '--db', '--cluster', '--rank', '--domains', '--dom', '--db-dom', '--linkage', '--level', '--no-whole'))}
 
 
 class _Parser(argparse.ArgumentParser):
@@ -1713,60 +1735,32 @@ class _Parser(argparse.ArgumentParser):
     ``--level`` says what ``--cluster`` clusters: an error without it; ``--level domain`` takes ``--min-domain`` alone and single
     linkage (an error without the one, beside ``--min-global`` or ``--linkage greedy``) and lets ``--dom`` name the rows;
     ``--no-whole`` is an error without ``--level domain``.  ``--assign`` places the proteins of ``--dct`` on the representatives of
-    another file: it needs a cut-off and is an error beside ``--pair``, ``--db``, ``--cluster``, ``--rank``, ``--domains`` /
-    ``--dom`` / ``--db-dom``, ``--linkage``, ``--level`` and ``--no-whole``.  ``--reps-out`` is an error unless ``--assign`` is
-    given, or ``--cluster --linkage greedy`` without ``--level domain``.  ``--tree`` prints the single-linkage tree of the file by
-    one score: an error beside ``--pair``, ``--db``, ``--cluster``, ``--assign``, ``--rank``, ``--linkage``, ``--level``,
-    ``--no-whole``, ``--reps-out`` and ``--domains`` / ``--dom`` / ``--db-dom``, and beside the cut-off of the other score.
-    ``--rbh`` prints the reciprocal best hits of ``--dct`` and ``--db`` by one score: an error without ``--db``, beside ``--pair``,
-    ``--cluster``, ``--assign``, ``--tree``, ``--rank``, ``--linkage``, ``--level``, ``--no-whole`` and ``--reps-out``, and beside the
-    cut-off of the other score; its own score's cut-off is allowed with it (the one case in which a cut-off goes with ``--db``)."""
+    another file and needs a cut-off; ``--tree`` prints the single-linkage tree of the file and ``--rbh`` the reciprocal best hits
+    of ``--dct`` and ``--db`` (an error without ``--db``), each by one score: an error beside the cut-off of the other score, while
+    its own score's cut-off is allowed (with ``--rbh`` the one case in which a cut-off goes with ``--db``).  What each of the three
+    refuses beside it is ``_MODES``.  ``--reps-out`` is an error unless ``--assign`` is given, or ``--cluster --linkage greedy``
+    without ``--level domain``."""
 
     def parse_known_args(self, args=None, namespace=None):
         ns, rest = super().parse_known_args(args, namespace)
-        rbh = getattr(ns, 'rbh', None)
-        if rbh is not None:
-            beside = [flag for flag, given in (('--pair', ns.pair), ('--cluster', getattr(ns, 'cluster', False)),
-                                               ('--assign', getattr(ns, 'assign', None) is not None), ('--tree', getattr(ns, 'tree', None) is not None),
-                                               ('--rank', getattr(ns, 'rank', None) is not None),
-                                               ('--linkage', getattr(ns, 'linkage', None) is not None), ('--level', getattr(ns, 'level', None) is not None),
-                                               ('--no-whole', getattr(ns, 'no_whole', False)), ('--reps-out', getattr(ns, 'reps_out', None) is not None))
-                      if given]
+        cut = ns.min_domain is not None or ns.min_global is not None
+        for mode, (does, orders, refused) in _MODES.items():
+            score = getattr(ns, _dest(mode), None)
+            if score is None:
+                continue
+            beside = [flag for flag in refused if _GIVEN[flag](getattr(ns, _dest(flag), None))]
             if beside:
-                self.error(f'--rbh prints the reciprocal best hits of --dct and --db: not with {beside[0]}')
-            if not ns.db:
+                self.error(f'{mode} {does}: not with {beside[0]}')
+            if mode == '--rbh' and not ns.db:
                 self.error('--rbh compares the proteins of --dct with those of another file: it needs --db')
-            if rbh == 'domain' and ns.min_global is not None:
-                self.error('--rbh domain ranks the hits by DCTdomain: its cut-off is --min-domain, not --min-global')
-            if rbh == 'global' and ns.min_domain is not None:
-                self.error('--rbh global ranks the hits by DCTglobal: its cut-off is --min-global, not --min-domain')
-        tree = getattr(ns, 'tree', None)
-        if tree is not None:
-            beside = [flag for flag, given in (('--pair', ns.pair), ('--db', ns.db), ('--cluster', getattr(ns, 'cluster', False)),
-                                               ('--assign', getattr(ns, 'assign', None) is not None),
-                                               ('--rank', getattr(ns, 'rank', None) is not None),
-                                               ('--linkage', getattr(ns, 'linkage', None) is not None), ('--level', getattr(ns, 'level', None) is not None),
-                                               ('--no-whole', getattr(ns, 'no_whole', False)), ('--reps-out', getattr(ns, 'reps_out', None) is not None),
-                                               ('--domains', getattr(ns, 'domains', False)), ('--dom', getattr(ns, 'dom', None) is not None),
-                                               ('--db-dom', getattr(ns, 'db_dom', None) is not None)) if given]
-            if beside:
-                self.error(f'--tree prints the single-linkage tree of --dct: not with {beside[0]}')
-            if tree == 'domain' and ns.min_global is not None:
-                self.error('--tree domain orders the pairs by DCTdomain: its cut-off is --min-domain, not --min-global')
-            if tree == 'global' and ns.min_domain is not None:
-                self.error('--tree global orders the pairs by DCTglobal: its cut-off is --min-global, not --min-domain')
-        if getattr(ns, 'assign', None) is not None:
-            beside = [flag for flag, given in (('--pair', ns.pair), ('--db', ns.db), ('--cluster', getattr(ns, 'cluster', False)),
-                                               ('--rank', getattr(ns, 'rank', None) is not None), ('--domains', getattr(ns, 'domains', False)),
-                                               ('--dom', getattr(ns, 'dom', None) is not None), ('--db-dom', getattr(ns, 'db_dom', None) is not None),
-                                               ('--linkage', getattr(ns, 'linkage', None) is not None), ('--level', getattr(ns, 'level', None) is not None),
-                                               ('--no-whole', getattr(ns, 'no_whole', False))) if given]
-            if beside:
-                self.error(f'--assign places the proteins of --dct on a fixed set of representatives: not with {beside[0]}')
-            if ns.min_domain is None and ns.min_global is None:
+            if mode == '--assign' and not cut:
                 self.error('--assign needs a cut-off: --min-domain, --min-global or both')
-        elif getattr(ns, 'reps_out', None) is not None and not (getattr(ns, 'cluster', False) and getattr(ns, 'linkage', None) == 'greedy'
-                                                                and getattr(ns, 'level', None) != 'domain'):
+            other = {'domain': 'global', 'global': 'domain'}.get(score)
+            if orders and getattr(ns, f'min_{other}') is not None:
+                self.error(f'{mode} {score} {orders} by DCT{score}: its cut-off is --min-{score}, not --min-{other}')
+        rbh = getattr(ns, 'rbh', None)
+        if getattr(ns, 'assign', None) is None and getattr(ns, 'reps_out', None) is not None and not (
+                getattr(ns, 'cluster', False) and getattr(ns, 'linkage', None) == 'greedy' and getattr(ns, 'level', None) != 'domain'):
             self.error('--reps-out writes representatives: it needs --assign, or --cluster --linkage greedy at protein level')
         if getattr(ns, 'rank', None) is not None and (ns.pair or not ns.db):
             self.error('--rank applies to database search (--db) only, not to --pair or all-against-all')
@@ -1864,8 +1858,7 @@ def main(argv=None):
     domains, dom, db_dom = (getattr(args, k, None) for k in ('domains', 'dom', 'db_dom'))
     level = getattr(args, 'level', 'protein')
     assign, reps_out = getattr(args, 'assign', None), getattr(args, 'reps_out', None)
-    report = Report(args.output, (DOMAIN_CLUSTER_HEADER if level == 'domain' else CLUSTER_HEADER) if args.cluster or assign is not None
-                    else DOMAIN_HEADER if domains else HEADER)
+    report = Report(args.output, _header(CLUSTER_HEADER if args.cluster or assign is not None else HEADER, level, domains))
     t_work = time.time()
     if getattr(args, 'tree', None) is not None:
         tree_sim(args.dct, report, score=args.tree, min_domain=args.min_domain, min_global=args.min_global)
