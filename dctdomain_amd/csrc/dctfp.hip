@@ -2705,6 +2705,29 @@ int dctfp_protein_min(dctfp_ctx* ctx, const int8_t* a, int64_t lda, const int64_
     return scratch.give_back();
 } DCTFP_GUARD("dctfp_protein_min")
 
+int dctfp_protein_cover(dctfp_ctx* ctx, const int8_t* a, int64_t lda, const int64_t* idx_a, int64_t npa, const int32_t* w_a, const int32_t* need_a,
+                        const int8_t* b, int64_t ldb, const int64_t* idx_b, int64_t npb, const int32_t* w_b, const int32_t* need_b, int32_t d,
+                        int32_t bound, int32_t* out, int64_t ldo, void* stream_v) try {
+    if (!ctx || !a || !idx_a || !w_a || !need_a || !b || !idx_b || !w_b || !need_b || !out)
+        return fail(DCTFP_ERR_INVALID, "dctfp_protein_cover: NULL argument");
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    if (npa < 0 || npb < 0 || d < 1 || lda < d || ldb < d || ldo < npb) return fail(DCTFP_ERR_INVALID, "dctfp_protein_cover: bad shape");
+    if (bound > 0x7ffffffe) return fail(DCTFP_ERR_INVALID, "dctfp_protein_cover: bound above 0x7ffffffe");
+    if (npa > 0x7fffffff || npb > 0x7fffffff) return fail(DCTFP_ERR_LIMIT, "dctfp_protein_cover: more than 2^31 - 1 proteins on a side");
+    if (d > 512) return fail(DCTFP_ERR_LIMIT, "dctfp_protein_cover: rows above 512 bytes");
+    if (sad_tile_align(a, lda, b, ldb) != 16)
+        return fail(DCTFP_ERR_LIMIT, "dctfp_protein_cover: rows not on 16-byte boundaries or 2^24 bytes apart");
+    if (npa == 0 || npb == 0) return DCTFP_OK;
+    HIP_TRY(hipSetDevice(ctx->device));
+    hipStream_t stream = (hipStream_t)stream_v;
+    Hold scratch{ctx->scratch, stream};   // the two block plans: given back after the kernel
+    int rc = scratch.take(protein_plan_bytes(npa) + protein_plan_bytes(npb), stream);
+    if (rc) return rc;
+    launch_protein_cover(a, lda, idx_a, npa, w_a, need_a, b, ldb, idx_b, npb, w_b, need_b, d, bound, out, ldo, scratch.p(), 2 * ctx->n_cu, stream);
+    HIP_TRY(hipGetLastError());
+    return scratch.give_back();
+} DCTFP_GUARD("dctfp_protein_cover")
+
 int dctfp_select_count(dctfp_ctx* ctx, const int32_t* dist, int64_t n_rows, int64_t n_cols, int64_t ld, const uint8_t* row_empty,
                        const uint8_t* col_empty, int32_t cap, int32_t bound, int32_t top, int32_t* out_count, int32_t* out_cut,
                        void* stream_v) try {

@@ -209,10 +209,14 @@ void launch_greedy_pairs_mark(const int32_t* pi, const int32_t* pj, int64_t n_pa
                               int64_t n_nodes, int64_t range_end, int32_t next_round, hipStream_t stream);
 
 // DCTdomain of every protein pair from the fingerprints (k_protein.hip): scratch bytes of one side's block plan, and the launches
-// (the two plans, then the protein-minimum kernel on a grid of n_workgroups that walks the block pairs)
+// (the two plans, then the protein-minimum kernel on a grid of n_workgroups that walks the block pairs); launch_protein_cover: the
+// same with the coverage requirement of dct-sim --min-coverage (row weights w_*, per-protein needs need_*, rows matched at L1 <= bound)
 size_t protein_plan_bytes(int64_t np);
 int launch_protein_min(const int8_t* a, int64_t lda, const int64_t* idx_a, int64_t npa, const int8_t* b, int64_t ldb, const int64_t* idx_b,
                        int64_t npb, int d, int32_t* out, int64_t ldo, void* scratch, int n_workgroups, hipStream_t stream);
+int launch_protein_cover(const int8_t* a, int64_t lda, const int64_t* idx_a, int64_t npa, const int32_t* w_a, const int32_t* need_a,
+                         const int8_t* b, int64_t ldb, const int64_t* idx_b, int64_t npb, const int32_t* w_b, const int32_t* need_b, int d,
+                         int32_t bound, int32_t* out, int64_t ldo, void* scratch, int n_workgroups, hipStream_t stream);
 
 // query_db at database scale (k_query.hip): fused L1 + k nearest, the protein-level ranking, the hit lines as text
 int knn_slices(int64_t na, int64_t nb, int k);

@@ -1,8 +1,8 @@
 // The 128 x 128 tile of L1 distances between int8 rows that every kernel of the similarity side is built on: rows_a rows of a
 // against rows_b rows of b, 256 threads, 8 x 8 sums per thread through v_sad_u8 (4 byte differences per instruction), both
 // operand tiles staged in LDS 32 dwords (128 bytes of the rows) at a time.  Device code only (and the host's choice of a fill),
-// defined once for its THREE callers: kernels.hip.h includes it for l1_matrix16_kernel, and k_protein.hip (protein_min_kernel) and
-// k_cluster.hip (rows_link_kernel) call the same function inside their own loops, each with its own launch bounds, LDS
+// defined once for its THREE callers: kernels.hip.h includes it for l1_matrix16_kernel, and k_protein.hip (protein_min_kernel and
+// protein_cover_kernel) and k_cluster.hip (rows_link_kernel) call the same function inside their own loops, each with its own launch bounds, LDS
 // declarations and epilogue.
 //
 // TWO COPIES remain, and a fix to the tile (tail round, lane offsets, bank layout, keep mask) goes there too: l1_knn_kernel

@@ -3,6 +3,7 @@ fingerprints (``-dct.npz``), with the L1 distances computed on the GPU.
 
     python -m dctdomain_amd.dct_sim --dct X-dct.npz [--pair P | --db Y-dct.npz [--rank {global,domain}]] [--output F]
                                     [--pairfound F] [--top 5] [--threshold 0.25] [--min-domain X] [--min-global Y]
+                                    [--min-coverage C [--cov-unit {residues,domains}]]
                                     [--cluster [--linkage {single,greedy}] [--level {protein,domain} [--no-whole]]] [--domains]
                                     [--dom X.dom] [--db-dom Y.dom]
     python -m dctdomain_amd.dct_sim --dct NEW-dct.npz --assign REPS-dct.npz --min-domain X [--min-global Y] [--reps-out ALL-dct.npz]
@@ -34,6 +35,14 @@ Where the reference loops over protein pairs and, inside, over domain pairs in P
   every other one goes to the lowest representative it has an edge to -- so every member is within the cut-off of its
   representative and no two representatives are within it of each other, decided on the device in rounds over the same tiles
   (``dctfp_greedy_decide`` / ``dctfp_greedy_tri_mark`` / ``dctfp_greedy_pairs_mark``);
+- ``--min-coverage C`` (with ``--min-domain``, in the all-against-all and in ``--cluster`` at protein level; MMseqs2's ``-c``, CD-HIT's
+  ``-aL`` / ``-aS``) keeps a pair only when it also covers the share C of BOTH proteins, so that one shared domain no longer links
+  a six-domain protein to everything that carries it.  A fingerprint of one protein is matched when some fingerprint of the other
+  is within the DCTdomain cut-off of it; the matched fingerprints' weights -- the residues ``make_db`` wrote for them
+  (``--cov-unit residues``: the ``dom`` array of the npz, or ``--dom``) or 1 per domain (``domains``), the whole-protein fingerprint
+  standing for all of them -- must reach ceil(C x the protein's weight).  The tiles then come from ``dctfp_protein_cover``:
+  ``dctfp_protein_min``'s values, and 0x7fffffff for the pairs that fail, so the filter, the union-find and the greedy rounds run
+  unchanged;
 - ``--assign REPS`` (``Assignment``, not in the reference) goes on from such a run when proteins are added: every protein of
   ``REPS`` is a fixed representative, the proteins of ``--dct`` are taken in file order by the same rule.  The hot step compares
   every fingerprint of the representatives with every fingerprint of the new proteins and keeps, per new protein, the lowest
@@ -87,7 +96,7 @@ import time
 import numpy as np
 
 from .similarity import (GREEDY_NONE, PROTEIN_MIN_MAX_D, GreedyState, LineIds, TextStream, _utf8_binary, block_min, block_min_device, cluster_labels,
-                         greedy_decide, greedy_pairs_mark, greedy_tri_mark, l1_matrix, link_pairs, pair_argmin, pair_argmin_device, pair_line_offsets, pair_lines, pair_min, pair_min_device, protein_min,
+                         greedy_decide, greedy_pairs_mark, greedy_tri_mark, l1_matrix, link_pairs, pair_argmin, pair_argmin_device, pair_line_offsets, pair_lines, pair_min, pair_min_device, protein_cover, protein_min,
                          rows_assign, rows_link, sim_lines, threshold_select, to_device_int8, tri_filter_count, tri_filter_fill, tri_link,
                          TREE_MAX_NODES, TreeState, tree_hook, tri_nearest, BestState, rect_best)
 
@@ -187,6 +196,66 @@ def _labels_of(sid, idx, dom_path: str = None) -> list:
 
 def _label(labels, first_row: int, arg: int) -> str:
     return NO_DOMAIN if arg < 0 else labels[first_row + arg]
+
+
+COV_UNITS = ('residues', 'domains')
+MAX_COVERAGE_WEIGHT = 1 << 30      # a protein's weight stays below it: twice that still fits the int32 the kernel reads
+
+
+def _residues(name: str) -> int:
+    """The residues a domain string names (``"1-30,61-100"`` -> 70); 0 for anything that is not a list of ranges a-b, 1 <= a <= b."""
+    total = 0
+    for part in f'{name}'.split(','):
+        ends = part.split('-')
+        if len(ends) != 2 or not (ends[0].isdigit() and ends[1].isdigit()) or not 1 <= int(ends[0]) <= int(ends[1]):
+            return 0
+        total += int(ends[1]) - int(ends[0]) + 1
+    return total
+
+
+def coverage_weights(sid, idx, dom_names, unit: str = 'residues') -> np.ndarray:
+    """What ``--min-coverage`` weighs: one int64 per fingerprint row of the file.  A protein of one row: that row carries the
+    protein's weight W.  A protein of k > 1 rows: its domain rows 0 .. k - 2 carry their own weights, W is their sum, and the last
+    row -- the whole-protein fingerprint -- carries W, so W is always the weight of a protein's last row.  ``unit='residues'``: a
+    row weighs the residues its name covers (``dom_names``: one string per row, the ``dom`` array of the npz or
+    ``fingerprint_labels`` of its ``.dom`` file; the name of a whole-protein row is not read); ValueError naming the protein
+    where there are no names or one does not parse.  ``unit='domains'``: every domain row weighs 1 (W = max(1, k - 1)); no names
+    needed.  ValueError for a W of 2^30 or more."""
+    if unit not in COV_UNITS:
+        raise ValueError(f'unit must be one of {COV_UNITS}')
+    idx = np.asarray(idx, dtype=np.int64)
+    counts = np.diff(idx)
+    total = int(idx[-1]) if len(idx) else 0
+    last = np.zeros(total, dtype=bool)
+    last[idx[1:][counts > 0] - 1] = True
+    whole = last & np.repeat(counts > 1, counts)                # the whole-protein rows: they get W
+    if unit == 'domains':
+        w = np.ones(total, dtype=np.int64)
+    else:
+        hint = 'use --cov-unit domains to count domains instead of residues'
+        if dom_names is None or len(dom_names) != total:
+            named = np.flatnonzero(counts > 0)
+            who = f'protein {sid[named[0]]}' if len(named) else 'the file'
+            raise ValueError(f'{who} has no domain names to count residues from (no dom array in the npz, no .dom file): {hint}')
+        w = np.fromiter((0 if skip else _residues(name) for name, skip in zip(dom_names, whole)), dtype=np.int64, count=total)
+        bad = np.flatnonzero((w <= 0) & ~whole)
+        if len(bad):
+            owner = int(np.searchsorted(idx, bad[0], 'right')) - 1
+            raise ValueError(f'protein {sid[owner]}: {dom_names[bad[0]]!r} names no residue ranges: {hint}')
+    w[whole] = 0
+    sums = np.concatenate([[0], np.cumsum(w)])
+    W = sums[idx[1:]] - sums[idx[:-1]]
+    w[whole] = W[counts > 1]
+    if len(W) and W.max() >= MAX_COVERAGE_WEIGHT:
+        raise ValueError(f'protein {sid[int(np.argmax(W))]} weighs {int(W.max())}: the coverage takes weights below 2^30')
+    return w
+
+
+def coverage_need(W, c: float):
+    """The weight of a protein of weight ``W`` that its matched rows must reach at coverage ``c``:
+    min(W, max(1, ceil(c W - 1e-9))) -- an integer, so that 0.7 of 10 is 7 and not 8; 0 for W = 0.  Arrays or single values."""
+    need = np.minimum(W, np.maximum(1, np.ceil(c * np.asarray(W, dtype=np.float64) - 1e-9))).astype(np.int64)
+    return need if need.ndim else int(need)
 
 
 def load_dct(filename: str, asmap=True) -> tuple:
@@ -468,13 +537,21 @@ class FilteredPairs:
     ``pair_argmin_device`` and keeps the two rows of the minimum, step 4 gives ``pair_lines`` the labels on the device (one
     per fingerprint row and ``-``).  Without cut-offs both bounds keep every pair and the output is ``AllPairs``' with the two
     fields added -- by the slower route: a protein-minimum tile, a filter that drops nothing and a second read of every pair's
-    fingerprints for the scores, where ``AllPairs`` reduces one distance matrix."""
+    fingerprints for the scores, where ``AllPairs`` reduces one distance matrix.
+
+    ``min_coverage`` (``--min-coverage``; needs ``min_domain`` and ``weights``, ``coverage_weights`` of the file) also asks that
+    the pair covers enough of BOTH proteins.  Row r of protein p is matched by protein q when min(L1(r, s), 17000) <= the DCTdomain
+    bound for some row s of q; cov(p by q) = the weights of the matched rows of p; the pair stays when cov(p by q) >=
+    ``coverage_need(W_p, min_coverage)`` and likewise for q.  The tile is then always DCTdomain's and comes from ``protein_cover``,
+    which writes 0x7fffffff for the pairs that fail: the filter, the union-find and the greedy rounds read it as they read
+    ``protein_min``'s, and ``min_global`` is applied to the survivors' last-row L1.  At a bound of 17000 every row is matched and
+    below 0 none is: the coverage then changes nothing and is not computed."""
 
     TEXT_BYTES = 1 << 28    # text of one range of rows
     COL_ROWS = 1 << 22      # fingerprints on the device at a time (the whole file stays there if it fits)
     TILE_INTS = 1 << 28     # int32 entries of one stripe's tile (1 GiB)
 
-    def __init__(self, sid, idx, fps, min_domain=None, min_global=None, labels=None):
+    def __init__(self, sid, idx, fps, min_domain=None, min_global=None, labels=None, min_coverage=None, weights=None):
         self.sid, self.idx, self.fps = sid, np.asarray(idx, dtype=np.int64), fps
         self.row_labels = labels                                # (not `labels`: Clusters.labels() is a method)
         if labels is not None and len(labels) != int(self.idx[-1]):
@@ -482,6 +559,27 @@ class FilteredPairs:
         self.bound_domain = L1_FULL_SCALE if min_domain is None else sim_bound(min_domain)
         self.bound_global = L1_FULL_SCALE if min_global is None else sim_bound(min_global)
         self.route = 'global' if self.bound_global < L1_FULL_SCALE else 'domain'
+        self.cover = None                                       # (row weights, protein needs) where a coverage can exclude a pair
+        if min_coverage is not None:
+            if min_domain is None:
+                raise ValueError('min_coverage needs min_domain: it counts the fingerprints within that cut-off')
+            self.with_coverage(min_coverage, weights)
+
+    def with_coverage(self, min_coverage: float, weights):
+        """Adds the coverage cut-off of the class text to a job that has a DCTdomain cut-off: ``weights`` = ``coverage_weights`` of
+        the file.  Returns the job (``Clusters(...).with_coverage(...)``: the cluster classes' constructors take the two cut-offs)."""
+        if weights is None or not 0 < min_coverage <= 1:
+            raise ValueError('a coverage is above 0 and at most 1 and needs the weights of the fingerprint rows')
+        w = np.asarray(weights, dtype=np.int64)
+        if len(w) != int(self.idx[-1]):
+            raise ValueError('weights must have one entry per fingerprint row')
+        if 0 <= self.bound_domain < L1_FULL_SCALE:              # (else every row is matched, or none: nothing to compute)
+            W = np.zeros(len(self.idx) - 1, dtype=np.int64)
+            has = np.diff(self.idx) > 0
+            W[has] = w[self.idx[1:][has] - 1]                   # (a protein's weight is its last row's)
+            self.cover = (w.astype(np.int32), coverage_need(W, min_coverage).astype(np.int32))
+            self.route = 'domain'
+        return self
 
     def stripes(self):
         """[i0, i1) over rows 0 .. n - 2: as many rows as keep rows x later proteins within TILE_INTS and the rows' fingerprints
@@ -514,7 +612,7 @@ class FilteredPairs:
     def tiles(self, rows: _DeviceRows = None):
         """Yields, per stripe, (i0, i1, tile, (row flags, column flags)): step 1 of the class text.  The tile is device int32,
         rows [i0, i1) x proteins i0 + 1 .. n - 1; the flags mark the proteins without fingerprints on the DCTglobal route (None on
-        the other: ``protein_min`` leaves 0x7fffffff there).  ``rows``: ``device_rows()`` of a caller that needs the
+        the other: ``protein_min`` leaves 0x7fffffff there, and so does ``protein_cover``, which takes its place under a coverage).  ``rows``: ``device_rows()`` of a caller that needs the
         fingerprints itself; taken here otherwise."""
         import torch
         n = len(self.idx) - 1
@@ -526,6 +624,8 @@ class FilteredPairs:
             last_rows, empty = _last_rows(self.fps[:total], self.idx)
             last_dev = to_device_int8(last_rows) if n <= self.COL_ROWS else None
             empty_dev = torch.as_tensor(empty, device=dev)
+        if self.cover is not None:
+            w_dev, need_dev = (torch.as_tensor(v, device=dev) for v in self.cover)
 
         def lasts(p0, p1):
             return last_dev[p0:p1] if last_dev is not None else to_device_int8(last_rows[p0:p1])
@@ -543,7 +643,12 @@ class FilteredPairs:
                 a, ia = rows(i0, i1), self.idx[i0:i1 + 1] - self.idx[i0]
                 for q0, q1 in _protein_groups(self.idx[col0:] - self.idx[col0], self.COL_ROWS):
                     q0, q1 = q0 + col0, q1 + col0
-                    protein_min(a, ia, rows(q0, q1), self.idx[q0:q1 + 1] - self.idx[q0], out=tile[:, q0 - col0:q1 - col0])
+                    b, ib, out = rows(q0, q1), self.idx[q0:q1 + 1] - self.idx[q0], tile[:, q0 - col0:q1 - col0]
+                    if self.cover is None:
+                        protein_min(a, ia, b, ib, out=out)
+                    else:
+                        protein_cover(a, ia, w_dev[self.idx[i0]:self.idx[i1]], need_dev[i0:i1], b, ib, w_dev[self.idx[q0]:self.idx[q1]],
+                                      need_dev[q0:q1], self.bound_domain, out=out, cap=L1_FULL_SCALE)
                 flags = (None, None)
             yield i0, i1, tile, flags
             del tile                                            # (before the next one is made; the caller drops its own too)
@@ -586,8 +691,10 @@ class FilteredPairs:
                     pi, pj = tri_filter_fill(tile[r0:r1], i0 + r0, col0, bound, count_dev[r0:r1], m,
                                              flags[0][r0:r1] if flags[0] is not None else None, flags[1])
                     chunk = (pi, pj) + tuple(self._scores_of(pi, pj, self.row_labels is not None, rows))
-                    if self.route == 'global' and self.bound_domain < L1_FULL_SCALE:      # (the other cut-off; the order stays)
-                        keep = chunk[2].clamp(max=L1_FULL_SCALE) <= self.bound_domain
+                    # the other cut-off (the order stays): DCTdomain's on the min L1, or under a coverage DCTglobal's on the last-row L1
+                    score, other = (2, self.bound_domain) if self.route == 'global' else (3, self.bound_global)
+                    if other < L1_FULL_SCALE:
+                        keep = chunk[score].clamp(max=L1_FULL_SCALE) <= other
                         chunk = tuple(t[keep].contiguous() for t in chunk)
                     if chunk[0].numel():
                         yield chunk
@@ -733,7 +840,8 @@ class _ProteinClusters(FilteredPairs):
 
     def _plain_labels(self):
         """The labels where no pair has to be looked at -- every protein its own for fewer than two proteins or a bound below 0 (a
-        cut-off above 1), all 0 where no bound excludes anything -- else None."""
+        cut-off above 1), all 0 where no bound excludes anything -- else None.  A coverage leaves both as they are: a DCTdomain
+        bound below 0 matches no row, one of 17000 matches every row of every pair."""
         n = len(self.idx) - 1
         if n < 2 or min(self.bound_domain, self.bound_global) < 0:
             return np.arange(max(n, 0), dtype=np.int32)
@@ -1597,29 +1705,45 @@ def db_search(npzfile: str, dbfile: str, top: int, threshold: float, report: Rep
             report.line(f'{query} {db_sid[q]} {maxs} {s}{tail}')
 
 
+def _file_weights(npzfile: str, sid, idx, unit: str, dom: str = None) -> np.ndarray:
+    """``coverage_weights`` of a file: residues from its ``.dom`` file (``dom``) if given, else from the ``dom`` array of the npz."""
+    names = None
+    if unit == 'residues':
+        names = fingerprint_labels(sid, idx, read_dom_file(dom)) if dom else _npz_dom(npzfile, int(idx[-1]))
+    return coverage_weights(sid, idx, names, unit)
+
+
 @_reporting
-def all_sim(npzfile: str, report: Report, min_domain: float = None, min_global: float = None, domains: bool = False, dom: str = None):
+def all_sim(npzfile: str, report: Report, min_domain: float = None, min_global: float = None, domains: bool = False, dom: str = None,
+            min_coverage: float = None, cov_unit: str = 'residues'):
     """All-against-all, upper triangle (src/dct-sim.py:158-176), streamed from the device (``AllPairs``).  With ``min_domain`` /
     ``min_global``: only the pairs whose DCTdomain / DCTglobal is not below them (``FilteredPairs``).  ``domains`` / ``dom`` (the
-    ``.dom`` of the npz): the best domain pair behind the scores -- ``FilteredPairs`` with or without cut-offs."""
+    ``.dom`` of the npz): the best domain pair behind the scores -- ``FilteredPairs`` with or without cut-offs.  ``min_coverage``
+    (with ``min_domain``): only the pairs that also cover that share of both proteins, in ``cov_unit`` -- residues (from ``dom``, else
+    from the npz) or domains (``FilteredPairs``)."""
     sid, idx, fps = _load_npz(npzfile)
     domains = domains or dom is not None
-    if min_domain is None and min_global is None and not domains:
+    if min_domain is None and min_global is None and not domains and min_coverage is None:
         AllPairs(sid, idx, fps).write(report.raw)
     else:
         labels = _labels_of(sid, idx, dom) if domains else None
-        FilteredPairs(sid, idx, fps, min_domain=min_domain, min_global=min_global, labels=labels).write(report.raw)
+        weights = _file_weights(npzfile, sid, idx, cov_unit, dom) if min_coverage is not None else None
+        FilteredPairs(sid, idx, fps, min_domain=min_domain, min_global=min_global, labels=labels, min_coverage=min_coverage,
+                      weights=weights).write(report.raw)
 
 
 @_reporting(header=CLUSTER_HEADER)
 def cluster_sim(npzfile: str, report: Report, min_domain: float = None, min_global: float = None, linkage: str = 'single',
-                level: str = 'protein', whole: bool = True, dom: str = None, reps_out: str = None):
+                level: str = 'protein', whole: bool = True, dom: str = None, reps_out: str = None, min_coverage: float = None,
+                cov_unit: str = 'residues'):
     """Clusters at the cut-offs, one line ``representative member`` per protein: single linkage (``Clusters``) or, with
     ``linkage='greedy'``, greedy incremental clusters in file order (``Representatives``).  ``level='domain'``: the domain
     families instead (``DomainClusters``: single linkage at ``min_domain`` alone), one line ``representative member dom1 dom2``
     per fingerprint row -- ``whole=False`` without the whole-protein rows of multi-domain proteins, ``dom`` (the ``.dom`` of the
     npz) names the rows by their residue ranges.  ``reps_out`` (greedy linkage at protein level only): the representatives as a
-    ``-dct.npz`` of their own (``write_reps``), which ``assign_sim`` takes as its fixed set."""
+    ``-dct.npz`` of their own (``write_reps``), which ``assign_sim`` takes as its fixed set.  ``min_coverage`` (protein level, with
+    ``min_domain``): two proteins are joined only if the pair also covers that share of both, in ``cov_unit`` (``all_sim``); ``dom``
+    then gives the residues."""
     if min_domain is None and min_global is None:
         raise ValueError('clustering needs a cut-off: min_domain, min_global or both')
     if reps_out is not None and (linkage != 'greedy' or level != 'protein'):
@@ -1629,15 +1753,19 @@ def cluster_sim(npzfile: str, report: Report, min_domain: float = None, min_glob
     if level not in LEVELS:
         raise ValueError(f'level must be one of {LEVELS}')
     if level == 'domain':
-        if min_domain is None or min_global is not None or linkage != 'single':
+        if min_domain is None or min_global is not None or linkage != 'single' or min_coverage is not None:
             raise ValueError('domain-level clusters are single-linkage clusters at min_domain alone')
         sid, idx, fps = _load_npz(npzfile)
         DomainClusters(sid, idx, fps, min_domain, whole=whole, labels=_labels_of(sid, idx, dom)).write(report.raw)
         return
-    if not whole or dom is not None:
-        raise ValueError('whole and dom apply to level="domain" only')
+    if not whole or (dom is not None and min_coverage is None):
+        raise ValueError('whole applies to level="domain" only, and so does dom without min_coverage')
     sid, idx, fps = _load_npz(npzfile)
     job = (Representatives if linkage == 'greedy' else Clusters)(sid, idx, fps, min_domain=min_domain, min_global=min_global)
+    if min_coverage is not None:
+        if min_domain is None:
+            raise ValueError('min_coverage needs min_domain: it counts the fingerprints within that cut-off')
+        job.with_coverage(min_coverage, _file_weights(npzfile, sid, idx, cov_unit, dom))
     labels = job.labels()
     job.write(report.raw, labels)
     if reps_out is not None:
@@ -1714,16 +1842,18 @@ def _is_set(value) -> bool:
 # with ``argparse.SUPPRESS``)
 _GIVEN = {'--pair': bool, '--db': bool, '--cluster': bool, '--domains': bool, '--no-whole': bool,
           '--assign': _is_set, '--tree': _is_set, '--rank': _is_set, '--linkage': _is_set, '--level': _is_set, '--reps-out': _is_set,
-          '--dom': _is_set, '--db-dom': _is_set}
+          '--dom': _is_set, '--db-dom': _is_set, '--min-coverage': _is_set, '--cov-unit': _is_set}
 # mode -> (what it does; for a mode that takes a score, what that score does; the flags it refuses, in the order they are named).
 # The modes are checked in this order.
 _MODES = {'--rbh': ('prints the reciprocal best hits of --dct and --db', 'ranks the hits',
-                    ('--pair', '--cluster', '--assign', '--tree', '--rank', '--linkage', '--level', '--no-whole', '--reps-out')),
+                    ('--pair', '--cluster', '--assign', '--tree', '--rank', '--linkage', '--level', '--no-whole', '--reps-out',
+                     '--min-coverage', '--cov-unit')),
           '--tree': ('prints the single-linkage tree of --dct', 'orders the pairs',
                      ('--pair', '--db', '--cluster', '--assign', '--rank', '--linkage', '--level', '--no-whole', '--reps-out', '--domains',
-                      '--dom', '--db-dom')),
+                      '--dom', '--db-dom', '--min-coverage', '--cov-unit')),
           '--assign': ('places the proteins of --dct on a fixed set of representatives', None,
-                       ('--pair', '--db', '--cluster', '--rank', '--domains', '--dom', '--db-dom', '--linkage', '--level', '--no-whole'))}
+                       ('--pair', '--db', '--cluster', '--rank', '--domains', '--dom', '--db-dom', '--linkage', '--level', '--no-whole',
+                        '--min-coverage', '--cov-unit'))}
 
 
 class _Parser(argparse.ArgumentParser):
@@ -1739,7 +1869,10 @@ class _Parser(argparse.ArgumentParser):
     of ``--dct`` and ``--db`` (an error without ``--db``), each by one score: an error beside the cut-off of the other score, while
     its own score's cut-off is allowed (with ``--rbh`` the one case in which a cut-off goes with ``--db``).  What each of the three
     refuses beside it is ``_MODES``.  ``--reps-out`` is an error unless ``--assign`` is given, or ``--cluster --linkage greedy``
-    without ``--level domain``."""
+    without ``--level domain``.  ``--min-coverage`` adds a coverage cut-off to ``--min-domain`` in the all-against-all and in
+    ``--cluster`` at protein level: an error without ``--min-domain``, outside (0, 1], beside ``--pair``, ``--db`` or ``--level
+    domain`` (and beside the three modes: ``_MODES``); ``--cov-unit`` says what it counts: an error without it.  Beside ``--cluster``
+    with ``--min-coverage``, ``--dom`` gives the residues and does not imply ``--domains``."""
 
     def parse_known_args(self, args=None, namespace=None):
         ns, rest = super().parse_known_args(args, namespace)
@@ -1766,11 +1899,24 @@ class _Parser(argparse.ArgumentParser):
             self.error('--rank applies to database search (--db) only, not to --pair or all-against-all')
         if getattr(ns, 'db_dom', None) is not None and not ns.db:
             self.error('--db-dom names the .dom file of --db: it needs --db')
-        if getattr(ns, 'dom', None) is not None or getattr(ns, 'db_dom', None) is not None:
+        level = getattr(ns, 'level', None)
+        coverage = getattr(ns, 'min_coverage', None)
+        if coverage is not None:
+            if ns.pair or ns.db:
+                self.error('--min-coverage applies to all-against-all only, not to --pair or --db')
+            if level == 'domain':
+                self.error('--min-coverage is a share of a protein: not with --level domain, which joins single fingerprints')
+            if ns.min_domain is None:
+                self.error('--min-coverage counts the fingerprints within the DCTdomain cut-off: it needs --min-domain')
+            if not 0 < coverage <= 1:
+                self.error('--min-coverage is a share of a protein: above 0 and at most 1')
+        elif getattr(ns, 'cov_unit', None) is not None:
+            self.error('--cov-unit says what --min-coverage counts: it needs --min-coverage')
+        weighs = coverage is not None and getattr(ns, 'cluster', False)     # (--dom gives --min-coverage its residues: no result lines to explain)
+        if (getattr(ns, 'dom', None) is not None and not weighs) or getattr(ns, 'db_dom', None) is not None:
             ns.domains = True
         if getattr(ns, 'linkage', None) is not None and not getattr(ns, 'cluster', False):
             self.error('--linkage says how --cluster forms its clusters: it needs --cluster')
-        level = getattr(ns, 'level', None)
         if level is not None and not getattr(ns, 'cluster', False):
             self.error('--level says what --cluster clusters: it needs --cluster')
         if getattr(ns, 'no_whole', False) and level != 'domain':
@@ -1812,6 +1958,13 @@ def build_parser() -> argparse.ArgumentParser:
                     help='all-against-all: print a pair only if its DCTdomain is not below X')
     ap.add_argument('--min-global', type=float, default=None, metavar='Y',
                     help='all-against-all: print a pair only if its DCTglobal is not below Y (with --min-domain: both must hold)')
+    ap.add_argument('--min-coverage', type=float, default=argparse.SUPPRESS, metavar='C',
+                    help='with --min-domain, all-against-all or --cluster: keep a pair only if the fingerprints of each protein that '
+                         'are within the cut-off of a fingerprint of the other cover at least the share C (above 0, at most 1) of '
+                         'that protein -- of both proteins')
+    ap.add_argument('--cov-unit', choices=COV_UNITS, default=argparse.SUPPRESS,
+                    help='--min-coverage: count a protein\'s covered residues (the default: from the dom array of the npz, or from '
+                         '--dom) or its covered domains')
     ap.add_argument('--cluster', action='store_true',
                     help='all-against-all with a cut-off: print single-linkage clusters (one "representative member" line per '
                          'protein) instead of the pairs')
@@ -1858,6 +2011,8 @@ def main(argv=None):
     domains, dom, db_dom = (getattr(args, k, None) for k in ('domains', 'dom', 'db_dom'))
     level = getattr(args, 'level', 'protein')
     assign, reps_out = getattr(args, 'assign', None), getattr(args, 'reps_out', None)
+    min_coverage = getattr(args, 'min_coverage', None)
+    cover = {'min_coverage': min_coverage, 'cov_unit': getattr(args, 'cov_unit', 'residues')} if min_coverage is not None else {}
     report = Report(args.output, _header(CLUSTER_HEADER if args.cluster or assign is not None else HEADER, level, domains))
     t_work = time.time()
     if getattr(args, 'tree', None) is not None:
@@ -1873,10 +2028,10 @@ def main(argv=None):
         db_search(args.dct, args.db, args.top, args.threshold, report, rank=args.rank or 'global', domains=bool(domains), dom=dom, db_dom=db_dom)
     elif args.cluster:
         cluster_sim(args.dct, report, min_domain=args.min_domain, min_global=args.min_global, linkage=getattr(args, 'linkage', 'single'),
-                    level=level, whole=not getattr(args, 'no_whole', False), dom=dom if level == 'domain' else None,
-                    **({'reps_out': reps_out} if reps_out is not None else {}))
+                    level=level, whole=not getattr(args, 'no_whole', False), dom=dom if level == 'domain' or cover else None,
+                    **({'reps_out': reps_out} if reps_out is not None else {}), **cover)
     else:
-        all_sim(args.dct, report, min_domain=args.min_domain, min_global=args.min_global, domains=bool(domains), dom=dom)
+        all_sim(args.dct, report, min_domain=args.min_domain, min_global=args.min_global, domains=bool(domains), dom=dom, **cover)
     report.close()
     t_end = time.time()
     print(f'total time used {t_end - t_start:.1f}s')

@@ -281,6 +281,57 @@ def protein_min(a, idx_a, b, idx_b, out: torch.Tensor = None) -> torch.Tensor:
     return out
 
 
+COVER_ALL = 0x7ffffffe     # dctfp_protein_cover's largest bound: every row of a pair with rows on both sides is matched
+
+
+def _device_int32(v, n: int, what: str, device) -> torch.Tensor:
+    """``v`` (host values, or a device int32 tensor as it is) as a contiguous device int32 vector of ``n`` entries."""
+    if isinstance(v, torch.Tensor) and v.device.type == 'cuda':
+        t = v
+    else:
+        t = torch.as_tensor(np.ascontiguousarray(np.asarray(v, dtype=np.int64).astype(np.int32)), device=device)
+    if t.dtype != torch.int32 or t.dim() != 1 or t.numel() != n or t.device != device:
+        raise ValueError(f'{what} must hold {n} int32 values on the fingerprints\' device')
+    return t.contiguous()
+
+
+def protein_cover(a, idx_a, w_a, need_a, b, idx_b, w_b, need_b, bound: int, out: torch.Tensor = None, cap: int = 17000) -> torch.Tensor:
+    """``protein_min`` with a coverage requirement (``dctfp_protein_cover``; dct-sim --min-coverage): int32 (npa, npb) on the
+    device, the smallest L1 over all fingerprint pairs where the rows of the protein of ``a`` that have a row of the other protein
+    within ``bound`` weigh at least ``need_a`` of it (``w_a``: one int32 weight per row of ``a``; ``need_a``: one int32 per
+    protein, 0 = no requirement) and likewise for the protein of ``b``; 0x7fffffff where they do not, and for a protein without
+    fingerprints.  A row is matched when min(L1, ``cap``) <= ``bound``: a bound of ``cap`` or more goes to the kernel as
+    ``COVER_ALL``, a negative one matches no row.  ``out`` and the 16-byte padding of rows as in ``protein_min``; rows wider than
+    512 bytes raise ValueError: there is no other route (fingerprints are 480 bytes)."""
+    ia, ib = np.asarray(idx_a, dtype=np.int64), np.asarray(idx_b, dtype=np.int64)
+    npa, npb = len(ia) - 1, len(ib) - 1
+    ta, tb = _row_major_int8(a), _row_major_int8(b)
+    _check_pair(ta, tb)
+    _check_prefix(ia, ta.shape[0])
+    _check_prefix(ib, tb.shape[0])
+    dev = ta.device
+    d = ta.shape[1]
+    if d > PROTEIN_MIN_MAX_D:
+        raise ValueError(f'protein_cover takes rows of at most {PROTEIN_MIN_MAX_D} bytes, not {d}')
+    wa, wb = _device_int32(w_a, ta.shape[0], 'w_a', dev), _device_int32(w_b, tb.shape[0], 'w_b', dev)
+    na, nb = _device_int32(need_a, npa, 'need_a', dev), _device_int32(need_b, npb, 'need_b', dev)
+    if out is None:
+        out = torch.empty((npa, npb), dtype=torch.int32, device=dev)
+    elif out.dtype != torch.int32 or tuple(out.shape) != (npa, npb) or out.device != dev or (npb > 1 and out.stride(1) != 1):
+        raise ValueError('out must be an int32 (npa, npb) tensor on the fingerprints\' device with unit column stride')
+    if out.numel() == 0:
+        return out
+    if ia[-1] == ia[0] or ib[-1] == ib[0]:                      # (no fingerprint on a side: every pair is empty)
+        return out.fill_(0x7fffffff)
+    if not (_aligned16(ta) and _aligned16(tb)):
+        w = (d + 15) // 16 * 16
+        ta, tb = _rows16(ta, w), _rows16(tb, w)
+    da, db = _device_int64(ia, dev), _device_int64(ib, dev)
+    _launch(dev, 'dctfp_protein_cover', ta.data_ptr(), _ld(ta), da.data_ptr(), npa, wa.data_ptr(), na.data_ptr(), tb.data_ptr(), _ld(tb),
+            db.data_ptr(), npb, wb.data_ptr(), nb.data_ptr(), d, COVER_ALL if bound >= cap else max(int(bound), -1), out.data_ptr(), _ld(out))
+    return out
+
+
 def _row_major_int8(x) -> torch.Tensor:
     """A device int8 matrix with unit column stride as it is (a row stride of its own is kept); anything else through
     ``to_device_int8``."""

@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define DCTFP_VERSION 110 /* 0.1.10: dctfp_rect_best */
+#define DCTFP_VERSION 111 /* 0.1.11: dctfp_protein_cover */
 
 #define DCTFP_OK 0
 #define DCTFP_ERR_INVALID (-1) /* bad argument (null pointer, piece outside its sequence, ...) */
@@ -335,6 +335,25 @@ int dctfp_pair_argmin(dctfp_ctx* ctx, const int32_t* pairs, int64_t n_pairs, con
  * side: dctfp_l1_matrix + dctfp_block_min give the same values there.  Uses the context's scratch. */
 int dctfp_protein_min(dctfp_ctx* ctx, const int8_t* a, int64_t lda, const int64_t* idx_a, int64_t npa, const int8_t* b, int64_t ldb,
                       const int64_t* idx_b, int64_t npb, int32_t d, int32_t* out, int64_t ldo, void* stream);
+
+/* dctfp_protein_min with a coverage requirement (dct-sim --min-coverage): a protein pair keeps its DCTdomain L1 only when enough
+ * of BOTH proteins is matched by the other one.  Row r of protein pa is matched by protein pb when
+ *     min over the rows s of pb of sum_k |a[r * lda + k] - b[s * ldb + k]| <= bound
+ * (signed: a negative bound matches nothing; bound <= 0x7ffffffe, which matches every row of a pair that has rows on both
+ * sides; DCTFP_ERR_INVALID above that), likewise a row of pb by pa.  cov(pa by pb) = the sum of w_a[r] over the matched rows r of
+ * pa, cov(pb by pa) = the sum of w_b[s] over the matched rows s of pb (w_a, w_b: device int32, one weight per row of a / of b;
+ * summed in 64 bits).  Then, with m = dctfp_protein_min's value of the pair,
+ *     out[pa * ldo + pb] = m           when cov(pa by pb) >= need_a[pa] and cov(pb by pa) >= need_b[pb],
+ *                          0x7fffffff  otherwise
+ * need_a (npa) / need_b (npb): device int32; a value <= 0 asks nothing of that side, so one-sided requirements are a need array of
+ * zeros -- and with both arrays all zero the output is dctfp_protein_min's, byte for byte.  A protein without fingerprints gives
+ * 0x7fffffff against everything, as there.  Everything else -- idx_a / idx_b, the packing into blocks, out and ldo, every entry
+ * written once, the scratch -- is dctfp_protein_min's, and so are the limits: DCTFP_ERR_LIMIT (nothing written) for rows above 512
+ * bytes, rows not on 16-byte boundaries (a, b, lda, ldb) or 2^24 bytes apart, or more than 2^31 - 1 proteins on a side.  A block
+ * that holds a protein of more than 128 rows costs two passes over its distances instead of one. */
+int dctfp_protein_cover(dctfp_ctx* ctx, const int8_t* a, int64_t lda, const int64_t* idx_a, int64_t npa, const int32_t* w_a, const int32_t* need_a,
+                        const int8_t* b, int64_t ldb, const int64_t* idx_b, int64_t npb, const int32_t* w_b, const int32_t* need_b, int32_t d,
+                        int32_t bound, int32_t* out, int64_t ldo, void* stream);
 
 /* The hits db_search prints (src/dct-sim.py:146-156), selected on the device from an int32 tile of L1 distances between the
  * queries' and the database proteins' last fingerprints (dctfp_l1_matrix).  Key of an entry: min(L1, cap) (cap = 17000: the
