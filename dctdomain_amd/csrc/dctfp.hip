@@ -2989,6 +2989,28 @@ int dctfp_rect_best(dctfp_ctx* ctx, const int32_t* tile, int64_t n_rows, int64_t
     return DCTFP_OK;
 } DCTFP_GUARD("dctfp_rect_best")
 
+int dctfp_label_sums(dctfp_ctx* ctx, const int32_t* tile, int64_t n_rows, int64_t n_cols, int64_t ld, int64_t row0, int64_t col0,
+                     const uint8_t* row_empty, const uint8_t* col_empty, int32_t cap, int32_t bound, const int32_t* labels, uint64_t* sums,
+                     int64_t n_nodes, void* stream_v) try {
+    (void)bound;   // (a sum has no cut-off: every pair of one label counts, with its key)
+    if (!ctx || !tile || !labels || !sums) return fail(DCTFP_ERR_INVALID, "dctfp_label_sums: NULL argument");
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    // (rect_best's walk, not a tile of the triangle's shifted one: its own few conditions)
+    if (n_rows < 0 || n_cols < 0 || ld < n_cols || row0 < 0 || col0 < 0 || cap < 0) return fail(DCTFP_ERR_INVALID, "dctfp_label_sums: bad shape or cap");
+    if (((reinterpret_cast<uintptr_t>(tile) | reinterpret_cast<uintptr_t>(labels)) & 3u) != 0 || (reinterpret_cast<uintptr_t>(sums) & 7u) != 0)
+        return fail(DCTFP_ERR_INVALID, "dctfp_label_sums: the tile or the labels are not 4-byte aligned or sums is not 8-byte aligned");
+    if (cap > label_sums_max_cap())
+        return fail(DCTFP_ERR_INVALID, "dctfp_label_sums: a cap above %d does not fit the 32-bit partial sums of a row", label_sums_max_cap());
+    if (n_nodes < 0 || n_nodes > 0x7fffffff) return fail(DCTFP_ERR_INVALID, "dctfp_label_sums: n_nodes must lie in 0 .. 2^31 - 1");
+    // (every index the kernel can form lies inside the tile, labels and sums: bounded here, on the host, and not on the device)
+    if (n_rows > n_nodes || row0 > n_nodes - n_rows || n_cols > n_nodes || col0 > n_nodes - n_cols) return fail(DCTFP_ERR_INVALID, "dctfp_label_sums: the tile names proteins outside labels / sums");
+    if (n_rows == 0 || n_cols == 0) return DCTFP_OK;
+    HIP_TRY(hipSetDevice(ctx->device));
+    launch_label_sums(tile, n_rows, n_cols, ld, row0, col0, row_empty, col_empty, cap, labels, sums, (hipStream_t)stream_v);
+    HIP_TRY(hipGetLastError());
+    return DCTFP_OK;
+} DCTFP_GUARD("dctfp_label_sums")
+
 int dctfp_greedy_decide(dctfp_ctx* ctx, int32_t* assign, int32_t* state, const int32_t* blocked, int64_t n_nodes, int64_t i0, int64_t i1,
                         int32_t round, int64_t* undecided, void* stream_v) try {
     if (!ctx || !assign || !state || !blocked || !undecided) return fail(DCTFP_ERR_INVALID, "dctfp_greedy_decide: NULL argument");

@@ -192,6 +192,13 @@ int rect_best_max_cap();
 void launch_rect_best(const int32_t* tile, int64_t n_rows, int64_t n_cols, int64_t ld, int64_t row0, int64_t col0, const uint8_t* row_empty,
                       const uint8_t* col_empty, int32_t cap, int32_t bound, uint64_t* best_row, uint64_t* best_col, hipStream_t stream);
 
+// the summed distances behind a cluster's medoid (k_medoid.hip): rect_best's walk over an int32 L1 tile of one file -- every entry
+// with col0 + c > row0 + r whose two proteins carry one label adds min(L1, cap) (cap for a flagged protein) to sums of both, with
+// agent-scope 64-bit atomic adds of partial sums kept in 32 bits; label_sums_max_cap = the largest cap for which those cannot overflow
+int label_sums_max_cap();
+void launch_label_sums(const int32_t* tile, int64_t n_rows, int64_t n_cols, int64_t ld, int64_t row0, int64_t col0, const uint8_t* row_empty,
+                       const uint8_t* col_empty, int32_t cap, const int32_t* labels, uint64_t* sums, hipStream_t stream);
+
 // (dctfp_rows_assign, k_assign.hip: the same contraction over a full rectangle -- every pair of rows within the bound lowers
 // assign[slot of the b row] to the value of the a row with an atomic minimum; value_a / slot_b NULL: a0 + r / b0 + c)
 void launch_rows_assign(const int8_t* a, int64_t na, int64_t lda, const int32_t* value_a, int64_t a0, const int8_t* b, int64_t nb, int64_t ldb,

@@ -4,7 +4,8 @@ fingerprints (``-dct.npz``), with the L1 distances computed on the GPU.
     python -m dctdomain_amd.dct_sim --dct X-dct.npz [--pair P | --db Y-dct.npz [--rank {global,domain}]] [--output F]
                                     [--pairfound F] [--top 5] [--threshold 0.25] [--min-domain X] [--min-global Y]
                                     [--min-coverage C [--cov-unit {residues,domains}]]
-                                    [--cluster [--linkage {single,greedy}] [--level {protein,domain} [--no-whole]]] [--domains]
+                                    [--cluster [--linkage {single,greedy}] [--level {protein,domain} [--no-whole]] [--rep {first,medoid}]]
+                                    [--domains]
                                     [--dom X.dom] [--db-dom Y.dom]
     python -m dctdomain_amd.dct_sim --dct NEW-dct.npz --assign REPS-dct.npz --min-domain X [--min-global Y] [--reps-out ALL-dct.npz]
                                     [--output F]
@@ -35,6 +36,13 @@ Where the reference loops over protein pairs and, inside, over domain pairs in P
   every other one goes to the lowest representative it has an edge to -- so every member is within the cut-off of its
   representative and no two representatives are within it of each other, decided on the device in rounds over the same tiles
   (``dctfp_greedy_decide`` / ``dctfp_greedy_tri_mark`` / ``dctfp_greedy_pairs_mark``);
+- ``--cluster --rep medoid`` (``Clusters.medoids``; CD-HIT names a cluster by its longest member, MMseqs2 has ``result2repseq``)
+  names every single-linkage cluster by its most central member instead of its first in the file: the member with the smallest
+  summed distance min(L1, 17000) to the others, ties to the lowest index.  A second pass over the same tiles with the final labels
+  on the device adds every pair of one cluster to the sums of both its proteins (``dctfp_label_sums``: exact 64-bit integer sums by
+  atomic adds of per-workgroup partial sums); the choice per cluster is n-element work in torch, n int32 come back.  Under
+  ``--min-coverage`` the coverage decides who is in a cluster and the plain distances decide its medoid.  The lines and their order
+  stay, only the first field changes; ``--reps-out`` writes the medoids for a later ``--assign``;
 - ``--min-coverage C`` (with ``--min-domain``, in the all-against-all and in ``--cluster`` at protein level; MMseqs2's ``-c``, CD-HIT's
   ``-aL`` / ``-aS``) keeps a pair only when it also covers the share C of BOTH proteins, so that one shared domain no longer links
   a six-domain protein to everything that carries it.  A fingerprint of one protein is matched when some fingerprint of the other
@@ -98,7 +106,7 @@ import numpy as np
 from .similarity import (GREEDY_NONE, PROTEIN_MIN_MAX_D, GreedyState, LineIds, TextStream, _utf8_binary, block_min, block_min_device, cluster_labels,
                          greedy_decide, greedy_pairs_mark, greedy_tri_mark, l1_matrix, link_pairs, pair_argmin, pair_argmin_device, pair_line_offsets, pair_lines, pair_min, pair_min_device, protein_cover, protein_min,
                          rows_assign, rows_link, sim_lines, threshold_select, to_device_int8, tri_filter_count, tri_filter_fill, tri_link,
-                         TREE_MAX_NODES, TreeState, tree_hook, tri_nearest, BestState, rect_best)
+                         TREE_MAX_NODES, TreeState, tree_hook, tri_nearest, BestState, rect_best, label_sums)
 
 L1_FULL_SCALE = 17000      # src/dct-sim.py:24
 HEADER = '#prot1 prot2 sim-domain sim-global'
@@ -609,12 +617,14 @@ class FilteredPairs:
         """The file's fingerprints on the device when they fit there (at most COL_ROWS), else None."""
         return self.device_rows().resident
 
-    def tiles(self, rows: _DeviceRows = None):
+    def tiles(self, rows: _DeviceRows = None, cover: bool = True):
         """Yields, per stripe, (i0, i1, tile, (row flags, column flags)): step 1 of the class text.  The tile is device int32,
         rows [i0, i1) x proteins i0 + 1 .. n - 1; the flags mark the proteins without fingerprints on the DCTglobal route (None on
         the other: ``protein_min`` leaves 0x7fffffff there, and so does ``protein_cover``, which takes its place under a coverage).  ``rows``: ``device_rows()`` of a caller that needs the
-        fingerprints itself; taken here otherwise."""
+        fingerprints itself; taken here otherwise.  ``cover=False``: ``protein_min``'s tile even under a coverage -- the plain distances, for a
+        caller that has the pairs' fate already (``Clusters.medoids``)."""
         import torch
+        covered = self.cover if cover else None
         n = len(self.idx) - 1
         dev = torch.device('cuda', torch.cuda.current_device())
         total = int(self.idx[-1])
@@ -624,8 +634,8 @@ class FilteredPairs:
             last_rows, empty = _last_rows(self.fps[:total], self.idx)
             last_dev = to_device_int8(last_rows) if n <= self.COL_ROWS else None
             empty_dev = torch.as_tensor(empty, device=dev)
-        if self.cover is not None:
-            w_dev, need_dev = (torch.as_tensor(v, device=dev) for v in self.cover)
+        if covered is not None:
+            w_dev, need_dev = (torch.as_tensor(v, device=dev) for v in covered)
 
         def lasts(p0, p1):
             return last_dev[p0:p1] if last_dev is not None else to_device_int8(last_rows[p0:p1])
@@ -644,7 +654,7 @@ class FilteredPairs:
                 for q0, q1 in _protein_groups(self.idx[col0:] - self.idx[col0], self.COL_ROWS):
                     q0, q1 = q0 + col0, q1 + col0
                     b, ib, out = rows(q0, q1), self.idx[q0:q1 + 1] - self.idx[q0], tile[:, q0 - col0:q1 - col0]
-                    if self.cover is None:
+                    if covered is None:
                         protein_min(a, ia, b, ib, out=out)
                     else:
                         protein_cover(a, ia, w_dev[self.idx[i0]:self.idx[i1]], need_dev[i0:i1], b, ib, w_dev[self.idx[q0]:self.idx[q1]],
@@ -781,11 +791,13 @@ def _ascii_lines(wide, lens, rep, member, chunk_bytes: int):
         yield rows[np.concatenate([col < lens[r, None], sep, col < lens[m, None], sep], axis=1)]
 
 
-def cluster_lines(sid, labels, chunk_bytes: int = 1 << 24):
+def cluster_lines(sid, labels, chunk_bytes: int = 1 << 24, rep=None):
     """The text of ``--cluster`` for given labels (``labels[i]`` = index of the representative of protein i), as uint8 arrays of
     whole lines of about ``chunk_bytes`` each: one line ``"{id of representative} {id of member}\n"`` per protein in the order of
     a stable sort of the proteins by label -- clusters by representative index, members by index inside a cluster, so a
-    representative's own line comes first.  Composed from the ids' bytes by index arithmetic: no Python loop per line."""
+    representative's own line comes first.  Composed from the ids' bytes by index arithmetic: no Python loop per line.
+    ``rep`` (``--rep medoid``: ``Clusters.medoids``): the protein that names the cluster of protein i in the first field instead of
+    ``labels[i]`` -- the lines and their order stay, so a medoid's own line need not come first."""
     labels = np.asarray(labels, dtype=np.int64)
     n = len(labels)
     if n != len(sid):
@@ -795,7 +807,20 @@ def cluster_lines(sid, labels, chunk_bytes: int = 1 << 24):
     if labels.min() < 0 or labels.max() >= n:
         raise IndexError('a label outside the proteins of the file')
     member = np.argsort(labels, kind='stable')
-    yield from _id_lines(sid, labels[member], member, chunk_bytes)
+    first = labels
+    if rep is not None:
+        first = np.asarray(rep, dtype=np.int64)
+        if len(first) != n:
+            raise ValueError('one representative per protein')
+        if first.min() < 0 or first.max() >= n:
+            raise IndexError('a representative outside the proteins of the file')
+    yield from _id_lines(sid, first[member], member, chunk_bytes)
+
+
+def medoid_cluster_lines(sid, labels, rep, chunk_bytes: int = 1 << 24):
+    """``cluster_lines`` in which ``rep[i]`` names the cluster of protein i: the same lines in the same order -- clusters by their
+    smallest member (``labels``), members by index -- with only the first field changed."""
+    return cluster_lines(sid, labels, chunk_bytes, rep=rep)
 
 
 def _id_lines(sid, rep, member, chunk_bytes: int):
@@ -849,9 +874,10 @@ class _ProteinClusters(FilteredPairs):
             return np.zeros(n, dtype=np.int32)
         return None
 
-    def write(self, sink, labels=None):
-        """Calls ``sink(memoryview)`` with the text (of ``labels()``, or of labels it gave before), whole lines at a time, in order."""
-        for text in cluster_lines(self.sid, self.labels() if labels is None else labels):
+    def write(self, sink, labels=None, rep=None):
+        """Calls ``sink(memoryview)`` with the text (of ``labels()``, or of labels it gave before), whole lines at a time, in order.
+        ``rep``: the first field of every line (``cluster_lines``)."""
+        for text in cluster_lines(self.sid, self.labels() if labels is None else labels, rep=rep):
             sink(memoryview(text))
 
 
@@ -867,22 +893,76 @@ class Clusters(_ProteinClusters):
       each chunk's pairs.
     - Neither does (cut-offs <= 0, NaN): one cluster.  A bound below 0 (a cut-off above 1): every protein its own.  No tile.
 
-    Then ``cluster_labels`` on the device and one copy of n int32.  The text is composed on the host (``cluster_lines``), O(n)."""
+    Then ``cluster_labels`` on the device and one copy of n int32.  The text is composed on the host (``cluster_lines``), O(n).
+
+    ``medoids()`` (``--rep medoid``) names every cluster by its most central member instead of its first: with key(x, y) =
+    min(L1(x, y), 17000) of the route's score -- DCTglobal's last-row L1 on the ``'global'`` route (a DCTglobal cut-off, alone or
+    beside the other), else DCTdomain's protein minimum; 17000 for a protein without fingerprints -- S(x) = the sum of key(x, y)
+    over the other members y of x's cluster, and the medoid of a cluster is its member with the smallest S, ties to the lowest
+    index.  A coverage decides membership only: the sums are taken on ``protein_min``'s tile, so a pair the coverage rejected
+    inside one cluster still counts with its distance.  A second pass over the triangle, ``label_sums`` on every stripe's tile
+    with the final labels on the device (n int64 sums, exact); when the triangle is one stripe that ``tri_link`` read as it is, the
+    tile of the first pass is kept and not filled again, else the tiles are computed anew (what ``Tree`` pays per round).  The
+    choice per cluster is n-element work on the device (two ``scatter_reduce_`` minima: of S per label, then of the indices that
+    attain it -- no (sum, index) word, so no limit on n beyond the class's own); n int32 come back."""
 
     def labels(self) -> np.ndarray:
         plain = self._plain_labels()
         if plain is not None:
             return plain
+        return self._link()[0].cpu().numpy()
+
+    def _link(self, keep: bool = False):
+        """(device int32 labels, kept): the linking of the class text.  ``keep``: kept = [(i0, tile, flags)] of the one stripe when
+        the triangle is one stripe, under no coverage, and ``tri_link`` read its tile -- else None."""
         import torch
         parent = torch.arange(len(self.idx) - 1, dtype=torch.int32, device=torch.device('cuda', torch.cuda.current_device()))
+        kept = None
         if max(self.bound_domain, self.bound_global) < L1_FULL_SCALE:
             for pi, pj, *_ in self.chunks():
                 link_pairs(pi, pj, parent)
         else:
+            keep = keep and self.cover is None and len(list(self.stripes())) == 1
             for i0, _, tile, flags in self.tiles():
                 tri_link(tile, i0, i0 + 1, self.bound, parent, *flags)
+                if keep:
+                    kept = [(i0, tile, flags)]
                 del tile
-        return cluster_labels(parent).cpu().numpy()
+        return cluster_labels(parent), kept
+
+    def medoids(self, labels=None) -> np.ndarray:
+        """``rep`` (int32, n): ``rep[x]`` = the medoid of the cluster of protein x (class text) -- of ``labels()``, or of ``labels``
+        given (one per protein, each the index of a protein, as ``labels()`` gives them).  ``last_labels`` = the labels it went by."""
+        import torch
+        n = len(self.idx) - 1
+        kept = None
+        if labels is None:
+            labels = self._plain_labels()
+            if labels is None:
+                lab_dev, kept = self._link(keep=True)
+                labels = lab_dev.cpu().numpy()
+        labels = np.ascontiguousarray(np.asarray(labels, dtype=np.int32))
+        if len(labels) != max(n, 0):
+            raise ValueError('one label per protein')
+        if n > 0 and (labels.min() < 0 or labels.max() >= n):
+            raise IndexError('a label outside the proteins of the file')
+        self.last_labels = labels
+        if n < 2 or np.array_equal(labels, np.arange(n, dtype=np.int32)):     # (every protein its own: no pair to sum)
+            return np.arange(max(n, 0), dtype=np.int32)
+        dev = torch.device('cuda', torch.cuda.current_device())
+        lab_dev = torch.as_tensor(labels, device=dev)
+        sums = torch.zeros(n, dtype=torch.int64, device=dev)
+        for i0, tile, flags in (kept if kept is not None else ((i0, tile, flags) for i0, _, tile, flags in self.tiles(cover=False))):
+            label_sums(tile, i0, i0 + 1, lab_dev, sums, *flags, cap=L1_FULL_SCALE)
+            del tile
+        del kept
+        lab = lab_dev.to(torch.int64)
+        # per label the smallest sum, then the lowest index that attains it
+        least = torch.full((n,), torch.iinfo(torch.int64).max, dtype=torch.int64, device=dev).scatter_reduce_(0, lab, sums, 'amin')
+        index = torch.arange(n, dtype=torch.int64, device=dev)
+        index = torch.where(sums == least[lab], index, torch.full_like(index, n))
+        medoid = torch.full((n,), n, dtype=torch.int64, device=dev).scatter_reduce_(0, lab, index, 'amin')
+        return medoid[lab].to(torch.int32).cpu().numpy()
 
 
 SCORES = ('domain', 'global')
@@ -1735,7 +1815,7 @@ def all_sim(npzfile: str, report: Report, min_domain: float = None, min_global: 
 @_reporting(header=CLUSTER_HEADER)
 def cluster_sim(npzfile: str, report: Report, min_domain: float = None, min_global: float = None, linkage: str = 'single',
                 level: str = 'protein', whole: bool = True, dom: str = None, reps_out: str = None, min_coverage: float = None,
-                cov_unit: str = 'residues'):
+                cov_unit: str = 'residues', rep: str = 'first'):
     """Clusters at the cut-offs, one line ``representative member`` per protein: single linkage (``Clusters``) or, with
     ``linkage='greedy'``, greedy incremental clusters in file order (``Representatives``).  ``level='domain'``: the domain
     families instead (``DomainClusters``: single linkage at ``min_domain`` alone), one line ``representative member dom1 dom2``
@@ -1743,10 +1823,17 @@ def cluster_sim(npzfile: str, report: Report, min_domain: float = None, min_glob
     npz) names the rows by their residue ranges.  ``reps_out`` (greedy linkage at protein level only): the representatives as a
     ``-dct.npz`` of their own (``write_reps``), which ``assign_sim`` takes as its fixed set.  ``min_coverage`` (protein level, with
     ``min_domain``): two proteins are joined only if the pair also covers that share of both, in ``cov_unit`` (``all_sim``); ``dom``
-    then gives the residues."""
+    then gives the residues.  ``rep='medoid'`` (single linkage at protein level): the first field of a line is the medoid of the
+    member's cluster -- the member with the smallest summed distance to the others (``Clusters.medoids``) -- instead of the cluster's
+    first member; the lines and their order stay.  ``reps_out`` then writes the medoids, in the order of the clusters' first members."""
     if min_domain is None and min_global is None:
         raise ValueError('clustering needs a cut-off: min_domain, min_global or both')
-    if reps_out is not None and (linkage != 'greedy' or level != 'protein'):
+    if rep not in REPS:
+        raise ValueError(f'rep must be one of {REPS}')
+    if rep == 'medoid' and (linkage != 'single' or level != 'protein'):
+        raise ValueError('medoids name single-linkage clusters at protein level: every member of a greedy cluster is within the '
+                         'cut-offs of its representative, which a medoid would not keep, and the domain level has no protein tile')
+    if reps_out is not None and (level != 'protein' or (linkage != 'greedy' and rep != 'medoid')):
         raise ValueError('reps_out writes the representatives of greedy clusters at protein level')
     if linkage not in LINKAGES:
         raise ValueError(f'linkage must be one of {LINKAGES}')
@@ -1766,10 +1853,15 @@ def cluster_sim(npzfile: str, report: Report, min_domain: float = None, min_glob
         if min_domain is None:
             raise ValueError('min_coverage needs min_domain: it counts the fingerprints within that cut-off')
         job.with_coverage(min_coverage, _file_weights(npzfile, sid, idx, cov_unit, dom))
-    labels = job.labels()
-    job.write(report.raw, labels)
+    if rep == 'medoid':
+        medoid = job.medoids()
+        labels = job.last_labels
+    else:
+        medoid, labels = None, job.labels()
+    job.write(report.raw, labels, rep=medoid)
     if reps_out is not None:
-        write_reps(reps_out, [(sid, idx, fps, _npz_dom(npzfile, int(idx[-1])), np.flatnonzero(labels == np.arange(len(labels))))])
+        first = np.flatnonzero(labels == np.arange(len(labels)))      # one per cluster, in the order of the clusters' first members
+        write_reps(reps_out, [(sid, idx, fps, _npz_dom(npzfile, int(idx[-1])), first if medoid is None else medoid[first])])
 
 
 @_reporting(header=CLUSTER_HEADER)
@@ -1828,6 +1920,7 @@ def rbh_sim(npzfile: str, dbfile: str, report: Report, score: str = 'domain', mi
 RANKS = ('global', 'domain')
 LINKAGES = ('single', 'greedy')
 LEVELS = ('protein', 'domain')
+REPS = ('first', 'medoid')
 
 
 def _dest(flag: str) -> str:
@@ -1842,18 +1935,18 @@ def _is_set(value) -> bool:
 # with ``argparse.SUPPRESS``)
 _GIVEN = {'--pair': bool, '--db': bool, '--cluster': bool, '--domains': bool, '--no-whole': bool,
           '--assign': _is_set, '--tree': _is_set, '--rank': _is_set, '--linkage': _is_set, '--level': _is_set, '--reps-out': _is_set,
-          '--dom': _is_set, '--db-dom': _is_set, '--min-coverage': _is_set, '--cov-unit': _is_set}
+          '--dom': _is_set, '--db-dom': _is_set, '--min-coverage': _is_set, '--cov-unit': _is_set, '--rep': _is_set}
 # mode -> (what it does; for a mode that takes a score, what that score does; the flags it refuses, in the order they are named).
 # The modes are checked in this order.
 _MODES = {'--rbh': ('prints the reciprocal best hits of --dct and --db', 'ranks the hits',
                     ('--pair', '--cluster', '--assign', '--tree', '--rank', '--linkage', '--level', '--no-whole', '--reps-out',
-                     '--min-coverage', '--cov-unit')),
+                     '--min-coverage', '--cov-unit', '--rep')),
           '--tree': ('prints the single-linkage tree of --dct', 'orders the pairs',
                      ('--pair', '--db', '--cluster', '--assign', '--rank', '--linkage', '--level', '--no-whole', '--reps-out', '--domains',
-                      '--dom', '--db-dom', '--min-coverage', '--cov-unit')),
+                      '--dom', '--db-dom', '--min-coverage', '--cov-unit', '--rep')),
           '--assign': ('places the proteins of --dct on a fixed set of representatives', None,
                        ('--pair', '--db', '--cluster', '--rank', '--domains', '--dom', '--db-dom', '--linkage', '--level', '--no-whole',
-                        '--min-coverage', '--cov-unit'))}
+                        '--min-coverage', '--cov-unit', '--rep'))}
 
 
 class _Parser(argparse.ArgumentParser):
@@ -1872,7 +1965,11 @@ class _Parser(argparse.ArgumentParser):
     without ``--level domain``.  ``--min-coverage`` adds a coverage cut-off to ``--min-domain`` in the all-against-all and in
     ``--cluster`` at protein level: an error without ``--min-domain``, outside (0, 1], beside ``--pair``, ``--db`` or ``--level
     domain`` (and beside the three modes: ``_MODES``); ``--cov-unit`` says what it counts: an error without it.  Beside ``--cluster``
-    with ``--min-coverage``, ``--dom`` gives the residues and does not imply ``--domains``."""
+    with ``--min-coverage``, ``--dom`` gives the residues and does not imply ``--domains``.  ``--rep`` says which member names a
+    cluster of ``--cluster``: an error without it, beside ``--level domain`` (its nodes are fingerprints: no protein tile to sum) and,
+    as ``--rep medoid``, beside ``--linkage greedy`` (whose representative every member is within the cut-offs of); ``--rep first`` is
+    the default and leaves the namespace of a command line without it.  ``--cluster --rep medoid`` at protein level is the third
+    case in which ``--reps-out`` is allowed: it writes the medoids."""
 
     def parse_known_args(self, args=None, namespace=None):
         ns, rest = super().parse_known_args(args, namespace)
@@ -1892,8 +1989,10 @@ class _Parser(argparse.ArgumentParser):
             if orders and getattr(ns, f'min_{other}') is not None:
                 self.error(f'{mode} {score} {orders} by DCT{score}: its cut-off is --min-{score}, not --min-{other}')
         rbh = getattr(ns, 'rbh', None)
+        names = getattr(ns, 'rep', None)
         if getattr(ns, 'assign', None) is None and getattr(ns, 'reps_out', None) is not None and not (
-                getattr(ns, 'cluster', False) and getattr(ns, 'linkage', None) == 'greedy' and getattr(ns, 'level', None) != 'domain'):
+                getattr(ns, 'cluster', False) and (getattr(ns, 'linkage', None) == 'greedy' or names == 'medoid')
+                and getattr(ns, 'level', None) != 'domain'):
             self.error('--reps-out writes representatives: it needs --assign, or --cluster --linkage greedy at protein level')
         if getattr(ns, 'rank', None) is not None and (ns.pair or not ns.db):
             self.error('--rank applies to database search (--db) only, not to --pair or all-against-all')
@@ -1921,6 +2020,16 @@ class _Parser(argparse.ArgumentParser):
             self.error('--level says what --cluster clusters: it needs --cluster')
         if getattr(ns, 'no_whole', False) and level != 'domain':
             self.error('--no-whole leaves the whole-protein rows out of the domain families: it needs --level domain')
+        if names is not None:
+            if not getattr(ns, 'cluster', False):
+                self.error('--rep says which member names a cluster: it needs --cluster')
+            if level == 'domain':
+                self.error('--rep names clusters of proteins: not with --level domain, whose nodes are fingerprints with no protein tile to sum')
+            if names == 'medoid' and getattr(ns, 'linkage', None) == 'greedy':
+                self.error('--rep medoid names single-linkage clusters: not with --linkage greedy, where every member is within the '
+                           'cut-offs of its representative -- a medoid would break that guarantee')
+            if names == 'first':
+                del ns.rep                                          # (the default: the namespace of a command line without it)
         if getattr(ns, 'cluster', False):
             if getattr(ns, 'domains', False) and level != 'domain':
                 self.error('--domains (--dom, --db-dom) explains the scores of result lines: not with --cluster')
@@ -1978,6 +2087,11 @@ def build_parser() -> argparse.ArgumentParser:
                     help='--cluster: single linkage (the default: connected components, the representative is the first protein of '
                          'the component) or greedy (in file order, a protein joins the first representative it is within the cut-off '
                          'of, else it becomes one: every member is within the cut-off of its representative)')
+    ap.add_argument('--rep', choices=REPS, default=argparse.SUPPRESS,
+                    help='--cluster (single linkage, protein level): what names a cluster in the first field -- its first protein in '
+                         'the file (first, the default) or its medoid, the member with the smallest summed distance to the others, '
+                         'ties to the first (medoid); the lines and their order stay.  With medoid, --reps-out FILE writes the '
+                         'medoids as a -dct.npz (the REPS of a later --assign)')
     ap.add_argument('--level', choices=LEVELS, default=argparse.SUPPRESS,
                     help='--cluster: what is clustered -- the proteins (the default) or, with --min-domain, the fingerprints of '
                          'the file (domain: the domain families; one "representative member dom1 dom2" line per fingerprint, --dom '
@@ -2029,7 +2143,8 @@ def main(argv=None):
     elif args.cluster:
         cluster_sim(args.dct, report, min_domain=args.min_domain, min_global=args.min_global, linkage=getattr(args, 'linkage', 'single'),
                     level=level, whole=not getattr(args, 'no_whole', False), dom=dom if level == 'domain' or cover else None,
-                    **({'reps_out': reps_out} if reps_out is not None else {}), **cover)
+                    **({'reps_out': reps_out} if reps_out is not None else {}), **cover,
+                    **({'rep': args.rep} if getattr(args, 'rep', None) is not None else {}))
     else:
         all_sim(args.dct, report, min_domain=args.min_domain, min_global=args.min_global, domains=bool(domains), dom=dom, **cover)
     report.close()

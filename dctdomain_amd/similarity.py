@@ -634,6 +634,23 @@ def rect_best(tile: torch.Tensor, row0: int, col0: int, bound: int, state: BestS
         _launch(tile.device, 'dctfp_rect_best', *lead, state.best_row.data_ptr(), n_a, state.best_col.data_ptr(), n_b)
 
 
+def label_sums(tile: torch.Tensor, row0: int, col0: int, labels: torch.Tensor, sums: torch.Tensor, row_empty=None, col_empty=None,
+               cap: int = 17000):
+    """Adds key = min(L1, cap) -- ``cap`` for a row / column flagged empty -- of every entry (r, c) of an L1 tile of ONE file with
+    col0 + c > row0 + r and ``labels[row0 + r] == labels[col0 + c]`` to ``sums[row0 + r]`` and to ``sums[col0 + c]``
+    (``dctfp_label_sums``).  ``labels``: device int32, one per protein (``cluster_labels``); ``sums``: device int64 of the same
+    length (torch has no uint64 arithmetic; the sums stay far below 2^63), zeroed by the caller before the first tile.  After every
+    tile of the triangle ``sums[x]`` is the summed distance of x to the other members of its cluster; integer addition commutes, so
+    it does not depend on how the triangle is cut into tiles or on the order of the calls."""
+    for t, dtype, what in ((labels, torch.int32, 'labels'), (sums, torch.int64, 'sums')):
+        if t.dtype != dtype or t.dim() != 1 or not t.is_contiguous() or t.device != tile.device or t.numel() != labels.numel():
+            raise ValueError(f'{what} must be a contiguous 1-D {dtype} tensor on the device of the tile, one entry per protein')
+    n_nodes = labels.numel()
+    n_rows, n_cols, lead, _flags = _tri_filter_args(tile, row0, col0, cap, row_empty, col_empty, cap, n_nodes)
+    if n_rows and n_cols:
+        _launch(tile.device, 'dctfp_label_sums', *lead, labels.data_ptr(), sums.data_ptr(), n_nodes)
+
+
 GREEDY_NONE = 0x7fffffff                       # assign: no representative yet
 GREEDY_UNDECIDED, GREEDY_MEMBER, GREEDY_NEW, GREEDY_DONE = 0, 1, 2, 3
 

@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define DCTFP_VERSION 111 /* 0.1.11: dctfp_protein_cover */
+#define DCTFP_VERSION 112 /* 0.1.12: dctfp_label_sums */
 
 #define DCTFP_OK 0
 #define DCTFP_ERR_INVALID (-1) /* bad argument (null pointer, piece outside its sequence, ...) */
@@ -584,6 +584,29 @@ int dctfp_tree_hook(dctfp_ctx* ctx, const int32_t* comp, uint64_t* best, int32_t
 int dctfp_rect_best(dctfp_ctx* ctx, const int32_t* tile, int64_t n_rows, int64_t n_cols, int64_t ld, int64_t row0, int64_t col0,
                     const uint8_t* row_empty, const uint8_t* col_empty, int32_t cap, int32_t bound, uint64_t* best_row, int64_t n_a,
                     uint64_t* best_col, int64_t n_b, void* stream);
+
+/* The summed distances behind a cluster's medoid (dct-sim --cluster --rep medoid; not in the reference): per protein of one file
+ * the sum of its distances to the other members of its own cluster, in one pass over an int32 tile of L1 values (dctfp_protein_min's
+ * output, or dctfp_l1_matrix of the last rows).  Entry (r, c), at tile[r * ld + c], is the L1 of proteins i = row0 + r and
+ * j = col0 + c of the file.  key = cap when the row is flagged in row_empty, the column in col_empty (device uint8, one per row /
+ * column of the tile, either may be NULL) or the value is negative or >= cap, else the value: dctfp_tri_filter_count's rule.  Every
+ * entry with j > i and labels[i] == labels[j] (device int32, n_nodes entries: dctfp_cluster_labels' output; the values are only
+ * compared) adds its key to
+ *     sums[i]   and   sums[j]
+ * (device uint64, n_nodes entries, 8-byte aligned; the caller zeroes it before the first tile).  The tile may hold entries on
+ * both sides of the diagonal: j > i takes every unordered pair once.  `bound` is accepted, so that the ten tile values are those
+ * of every export that scans a tile, and ignored: a sum has no cut-off.  Inside the launch sums is touched by agent-scope relaxed
+ * 64-bit atomic adds only, after a reduction in the workgroup to 32-bit partial sums: at most one global atomic per (row, 1024
+ * columns) and per (column, 64 rows), none for a partial sum of 0.  Integer addition commutes: the result is a sum over a set the
+ * inputs fix and does not depend on the order in which the device ran, on how the triangle is cut into tiles or on the order of
+ * the calls.  The tile is read with plain 4-byte loads: any ld >= n_cols, a column view of a wider tensor included.
+ * DCTFP_ERR_INVALID, with a message, for: a NULL ctx, tile, labels or sums; a negative count or offset; ld < n_cols; cap < 0; a
+ * cap above 4194303 (a row's partial sum of 1024 keys, and a column's of 64, stay in 32 bits); n_nodes negative or >= 2^31;
+ * row0 + n_rows > n_nodes or col0 + n_cols > n_nodes (checked on the host: the kernel bounds no index); a tile or labels off a
+ * 4-byte or sums off an 8-byte boundary.  n_rows or n_cols of 0: nothing to do. */
+int dctfp_label_sums(dctfp_ctx* ctx, const int32_t* tile, int64_t n_rows, int64_t n_cols, int64_t ld, int64_t row0, int64_t col0,
+                     const uint8_t* row_empty, const uint8_t* col_empty, int32_t cap, int32_t bound, const int32_t* labels, uint64_t* sums,
+                     int64_t n_nodes, void* stream);
 
 /* query_db's search (src/query_db.py:75-87: a flat FAISS index forced to METRIC_L1 at :76, index.search at :87) without a
  * distance matrix: for query rows q (nq x d, row stride ldq) and database rows b (nb x d, stride ldb), int8 on the device, each
