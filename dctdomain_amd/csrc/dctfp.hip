@@ -3011,6 +3011,49 @@ int dctfp_label_sums(dctfp_ctx* ctx, const int32_t* tile, int64_t n_rows, int64_
     return DCTFP_OK;
 } DCTFP_GUARD("dctfp_label_sums")
 
+// What dctfp_tri_degree and dctfp_tri_link_core ask of the tile and of n_nodes (label_sums' walk, so label_sums' conditions, and a
+// bound); `name` = the export, for the message.  The arrays beside the tile are checked by the export that knows them.
+static int density_tile_ok(const char* name, const int32_t* tile, int64_t n_rows, int64_t n_cols, int64_t ld, int64_t row0, int64_t col0,
+                           int32_t cap, int32_t bound, int64_t n_nodes) {
+    if (n_rows < 0 || n_cols < 0 || ld < n_cols || row0 < 0 || col0 < 0 || cap < 0 || bound < -1 || bound > cap)
+        return fail(DCTFP_ERR_INVALID, "%s: bad shape, cap or bound", name);
+    if ((reinterpret_cast<uintptr_t>(tile) & 3u) != 0) return fail(DCTFP_ERR_INVALID, "%s: the tile is not 4-byte aligned", name);
+    if (n_nodes < 0 || n_nodes > 0x7fffffff) return fail(DCTFP_ERR_INVALID, "%s: n_nodes must lie in 0 .. 2^31 - 1", name);
+    // (every index the kernel can form lies inside the tile and the arrays: bounded here, on the host, and not on the device)
+    if (n_rows > n_nodes || row0 > n_nodes - n_rows || n_cols > n_nodes || col0 > n_nodes - n_cols)
+        return fail(DCTFP_ERR_INVALID, "%s: the tile names proteins outside the arrays", name);
+    return DCTFP_OK;
+}
+
+int dctfp_tri_degree(dctfp_ctx* ctx, const int32_t* tile, int64_t n_rows, int64_t n_cols, int64_t ld, int64_t row0, int64_t col0,
+                     const uint8_t* row_empty, const uint8_t* col_empty, int32_t cap, int32_t bound, uint32_t* deg, int64_t n_nodes,
+                     void* stream_v) try {
+    if (!ctx || !tile || !deg) return fail(DCTFP_ERR_INVALID, "dctfp_tri_degree: NULL argument");
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    RC_TRY(density_tile_ok("dctfp_tri_degree", tile, n_rows, n_cols, ld, row0, col0, cap, bound, n_nodes));
+    if ((reinterpret_cast<uintptr_t>(deg) & 3u) != 0) return fail(DCTFP_ERR_INVALID, "dctfp_tri_degree: deg is not 4-byte aligned");
+    if (n_rows == 0 || n_cols == 0) return DCTFP_OK;
+    HIP_TRY(hipSetDevice(ctx->device));
+    launch_tri_degree(tile, n_rows, n_cols, ld, row0, col0, row_empty, col_empty, cap, bound, deg, (hipStream_t)stream_v);
+    HIP_TRY(hipGetLastError());
+    return DCTFP_OK;
+} DCTFP_GUARD("dctfp_tri_degree")
+
+int dctfp_tri_link_core(dctfp_ctx* ctx, const int32_t* tile, int64_t n_rows, int64_t n_cols, int64_t ld, int64_t row0, int64_t col0,
+                        const uint8_t* row_empty, const uint8_t* col_empty, int32_t cap, int32_t bound, const uint8_t* core, int32_t* parent,
+                        int32_t* nearest, int64_t n_nodes, void* stream_v) try {
+    if (!ctx || !tile || !core || !parent || !nearest) return fail(DCTFP_ERR_INVALID, "dctfp_tri_link_core: NULL argument");
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    RC_TRY(density_tile_ok("dctfp_tri_link_core", tile, n_rows, n_cols, ld, row0, col0, cap, bound, n_nodes));
+    if (((reinterpret_cast<uintptr_t>(parent) | reinterpret_cast<uintptr_t>(nearest)) & 3u) != 0)
+        return fail(DCTFP_ERR_INVALID, "dctfp_tri_link_core: parent or nearest is not 4-byte aligned");
+    if (n_rows == 0 || n_cols == 0) return DCTFP_OK;
+    HIP_TRY(hipSetDevice(ctx->device));
+    launch_tri_link_core(tile, n_rows, n_cols, ld, row0, col0, row_empty, col_empty, cap, bound, core, parent, nearest, (hipStream_t)stream_v);
+    HIP_TRY(hipGetLastError());
+    return DCTFP_OK;
+} DCTFP_GUARD("dctfp_tri_link_core")
+
 int dctfp_greedy_decide(dctfp_ctx* ctx, int32_t* assign, int32_t* state, const int32_t* blocked, int64_t n_nodes, int64_t i0, int64_t i1,
                         int32_t round, int64_t* undecided, void* stream_v) try {
     if (!ctx || !assign || !state || !blocked || !undecided) return fail(DCTFP_ERR_INVALID, "dctfp_greedy_decide: NULL argument");

@@ -199,6 +199,16 @@ int label_sums_max_cap();
 void launch_label_sums(const int32_t* tile, int64_t n_rows, int64_t n_cols, int64_t ld, int64_t row0, int64_t col0, const uint8_t* row_empty,
                        const uint8_t* col_empty, int32_t cap, const int32_t* labels, uint64_t* sums, hipStream_t stream);
 
+// density clusters (k_density.hip): label_sums' walk over an int32 L1 tile of one file, twice -- every entry tri_filter_count would
+// count (col0 + c > row0 + r, min(L1, cap) <= bound, cap for a flagged protein) adds 1 to deg of both ends; then, with core per
+// protein, a core-core entry is a union in parent and an entry with one core end lowers nearest of the other end to the core's index.
+// Agent-scope atomic adds / minima of parts reduced in the workgroup, and the forest's own atomics
+void launch_tri_degree(const int32_t* tile, int64_t n_rows, int64_t n_cols, int64_t ld, int64_t row0, int64_t col0, const uint8_t* row_empty,
+                       const uint8_t* col_empty, int32_t cap, int32_t bound, uint32_t* deg, hipStream_t stream);
+void launch_tri_link_core(const int32_t* tile, int64_t n_rows, int64_t n_cols, int64_t ld, int64_t row0, int64_t col0, const uint8_t* row_empty,
+                          const uint8_t* col_empty, int32_t cap, int32_t bound, const uint8_t* core, int32_t* parent, int32_t* nearest,
+                          hipStream_t stream);
+
 // (dctfp_rows_assign, k_assign.hip: the same contraction over a full rectangle -- every pair of rows within the bound lowers
 // assign[slot of the b row] to the value of the a row with an atomic minimum; value_a / slot_b NULL: a0 + r / b0 + c)
 void launch_rows_assign(const int8_t* a, int64_t na, int64_t lda, const int32_t* value_a, int64_t a0, const int8_t* b, int64_t nb, int64_t ldb,

@@ -4,7 +4,8 @@ fingerprints (``-dct.npz``), with the L1 distances computed on the GPU.
     python -m dctdomain_amd.dct_sim --dct X-dct.npz [--pair P | --db Y-dct.npz [--rank {global,domain}]] [--output F]
                                     [--pairfound F] [--top 5] [--threshold 0.25] [--min-domain X] [--min-global Y]
                                     [--min-coverage C [--cov-unit {residues,domains}]]
-                                    [--cluster [--linkage {single,greedy}] [--level {protein,domain} [--no-whole]] [--rep {first,medoid}]]
+                                    [--cluster [--linkage {single,greedy}] [--level {protein,domain} [--no-whole]] [--rep {first,medoid}]
+                                     [--min-neighbors M]]
                                     [--domains]
                                     [--dom X.dom] [--db-dom Y.dom]
     python -m dctdomain_amd.dct_sim --dct NEW-dct.npz --assign REPS-dct.npz --min-domain X [--min-global Y] [--reps-out ALL-dct.npz]
@@ -43,6 +44,12 @@ Where the reference loops over protein pairs and, inside, over domain pairs in P
   atomic adds of per-workgroup partial sums); the choice per cluster is n-element work in torch, n int32 come back.  Under
   ``--min-coverage`` the coverage decides who is in a cluster and the plain distances decide its medoid.  The lines and their order
   stay, only the first field changes; ``--reps-out`` writes the medoids for a later ``--assign``;
+- ``--cluster --min-neighbors M`` (``DensityClusters``; DBSCAN with the cut-off as its radius) keeps single linkage from chaining two
+  families through one pair: only a protein with at least M pairs within the cut-offs -- a core -- passes a link on.  Clusters are
+  the components of the core-core pairs; any other protein with a core neighbour joins the cluster of its lowest one, the rest are
+  clusters of their own.  Two passes over the same tiles: the degrees (``dctfp_tri_degree``), then the unions of the core-core pairs
+  and per non-core protein its lowest core neighbour (``dctfp_tri_link_core``); the rest is n-element work in torch.  M = 1 is
+  ``--cluster`` itself;
 - ``--min-coverage C`` (with ``--min-domain``, in the all-against-all and in ``--cluster`` at protein level; MMseqs2's ``-c``, CD-HIT's
   ``-aL`` / ``-aS``) keeps a pair only when it also covers the share C of BOTH proteins, so that one shared domain no longer links
   a six-domain protein to everything that carries it.  A fingerprint of one protein is matched when some fingerprint of the other
@@ -106,7 +113,8 @@ import numpy as np
 from .similarity import (GREEDY_NONE, PROTEIN_MIN_MAX_D, GreedyState, LineIds, TextStream, _utf8_binary, block_min, block_min_device, cluster_labels,
                          greedy_decide, greedy_pairs_mark, greedy_tri_mark, l1_matrix, link_pairs, pair_argmin, pair_argmin_device, pair_line_offsets, pair_lines, pair_min, pair_min_device, protein_cover, protein_min,
                          rows_assign, rows_link, sim_lines, threshold_select, to_device_int8, tri_filter_count, tri_filter_fill, tri_link,
-                         TREE_MAX_NODES, TreeState, tree_hook, tri_nearest, BestState, rect_best, label_sums)
+                         TREE_MAX_NODES, TreeState, tree_hook, tri_nearest, BestState, rect_best, label_sums, NEAREST_NONE, tri_degree,
+                         tri_link_core)
 
 L1_FULL_SCALE = 17000      # src/dct-sim.py:24
 HEADER = '#prot1 prot2 sim-domain sim-global'
@@ -965,6 +973,117 @@ class Clusters(_ProteinClusters):
         return medoid[lab].to(torch.int32).cpu().numpy()
 
 
+KIND_NOISE, KIND_BORDER, KIND_CORE = 0, 1, 2
+
+
+class DensityClusters(Clusters):
+    """Density clusters of one file at cut-offs (``--cluster --min-neighbors M``): DBSCAN whose radius is the cut-off.  G is
+    ``Clusters``' graph -- the proteins, and exactly ``FilteredPairs``' pairs as edges, coverage included -- and deg(x) the number of
+    edges at x (x itself is not counted).
+
+    - x is a **core** when deg(x) >= M.  A cluster's cores are a connected component of the edges whose two ends are both cores.
+    - A non-core with a core neighbour is a **border**: it joins the cluster of its LOWEST core neighbour, so the result does not
+      depend on the order in which anything ran (textbook DBSCAN gives a border to whichever cluster reaches it first).
+    - A non-core without a core neighbour is **noise**: a cluster of its own.  A protein without fingerprints is on no edge.
+
+    ``labels()[x]`` = the smallest index among ALL members of x's cluster, cores and borders alike -- every other mode's convention --
+    and the text is ``cluster_lines``' own.  M = 1 gives ``Clusters.labels()`` exactly: every protein on an edge is a core.
+
+    - One cut-off excludes anything: pass 1 over ``tiles()`` counts the degrees (``tri_degree``), ``core = deg >= M`` on the device,
+      pass 2 joins the core-core edges in the forest and keeps per non-core protein its lowest core neighbour (``tri_link_core``).
+      When the triangle is one stripe the tile of pass 1 is kept for pass 2; else the tiles are filled again -- twice the work of
+      ``Clusters``, the trade ``medoids`` makes.
+    - Both do: ``chunks()`` twice, as ``Clusters`` goes through it once -- the degrees by ``index_add_`` of the surviving pairs, then
+      the core-core pairs to ``link_pairs`` and the one-core pairs into a ``scatter_reduce_`` minimum: n- and m-element work.
+    - Neither does: the graph is complete -- one cluster if n - 1 >= M, else every protein its own.  A bound below 0, or fewer than
+      two proteins: every protein its own.  No tile.
+
+    Then n-element work on the device: ``cluster_labels``, the borders take the label of their nearest core, the labels become the
+    smallest member of each cluster (a ``scatter_reduce_`` minimum of the indices); n int32 come back.  ``kinds()`` (uint8: 0 noise,
+    1 border, 2 core) and ``degrees()`` (int32) are those of the last ``labels()`` / ``medoids()`` run, which they start when there was
+    none.  ``medoids()`` is ``Clusters``' on these labels."""
+
+    def __init__(self, sid, idx, fps, min_domain=None, min_global=None, min_neighbors: int = 1):
+        if int(min_neighbors) != min_neighbors or int(min_neighbors) < 1:
+            raise ValueError('min_neighbors is a number of neighbours: an integer, at least 1')
+        super().__init__(sid, idx, fps, min_domain=min_domain, min_global=min_global)
+        self.min_neighbors = int(min_neighbors)
+        self._found = None                                      # (degrees, kinds) of the last run: numpy arrays or device tensors
+
+    def _plain_labels(self):
+        plain = super()._plain_labels()
+        if plain is None:
+            return None
+        n = max(len(self.idx) - 1, 0)
+        if n < 2 or min(self.bound_domain, self.bound_global) < 0:     # (every protein its own: no edge at all)
+            self._found = (np.zeros(n, dtype=np.int32), np.full(n, KIND_NOISE, dtype=np.uint8))
+            return plain
+        dense = n - 1 >= self.min_neighbors                     # (the complete graph: every degree is n - 1)
+        self._found = (np.full(n, n - 1, dtype=np.int32), np.full(n, KIND_CORE if dense else KIND_NOISE, dtype=np.uint8))
+        return plain if dense else np.arange(n, dtype=np.int32)
+
+    def _found_array(self, k: int) -> np.ndarray:
+        if self._found is None:
+            self.labels()
+        v = self._found[k]
+        return v if isinstance(v, np.ndarray) else v.cpu().numpy()
+
+    def degrees(self) -> np.ndarray:
+        """int32 (n): the number of edges at every protein."""
+        return self._found_array(0)
+
+    def kinds(self) -> np.ndarray:
+        """uint8 (n): ``KIND_NOISE`` (0), ``KIND_BORDER`` (1) or ``KIND_CORE`` (2) per protein."""
+        return self._found_array(1)
+
+    def _link(self, keep: bool = False):
+        """(device int32 labels, kept) as ``Clusters._link`` gives them: the two passes and the n-element work of the class text."""
+        import torch
+        n = len(self.idx) - 1
+        dev = torch.device('cuda', torch.cuda.current_device())
+        deg = torch.zeros(n, dtype=torch.int32, device=dev)
+        parent = torch.arange(n, dtype=torch.int32, device=dev)
+        kept = None
+        if max(self.bound_domain, self.bound_global) < L1_FULL_SCALE:
+            for pi, pj, *_ in self.chunks():
+                one = torch.ones_like(pi)
+                deg.index_add_(0, pi.to(torch.int64), one).index_add_(0, pj.to(torch.int64), one)
+            core = deg >= self.min_neighbors
+            nearest = torch.full((n,), NEAREST_NONE, dtype=torch.int64, device=dev)
+            for pi, pj, *_ in self.chunks():
+                pi, pj = pi.to(torch.int64), pj.to(torch.int64)
+                ci, cj = core[pi], core[pj]
+                both = ci & cj
+                link_pairs(pi[both].to(torch.int32), pj[both].to(torch.int32), parent)
+                nearest.scatter_reduce_(0, pj[ci & ~cj], pi[ci & ~cj], 'amin')
+                nearest.scatter_reduce_(0, pi[cj & ~ci], pj[cj & ~ci], 'amin')
+        else:
+            held = [] if len(list(self.stripes())) == 1 else None
+            for i0, _, tile, flags in self.tiles():
+                tri_degree(tile, i0, i0 + 1, self.bound, deg, *flags)
+                if held is not None:
+                    held.append((i0, tile, flags))
+                del tile
+            core = deg >= self.min_neighbors
+            flag = core.to(torch.uint8)
+            nearest = torch.full((n,), NEAREST_NONE, dtype=torch.int32, device=dev)
+            for i0, tile, flags in (held if held is not None else ((i0, tile, flags) for i0, _, tile, flags in self.tiles())):
+                tri_link_core(tile, i0, i0 + 1, self.bound, flag, parent, nearest, *flags)
+                del tile
+            if keep and self.cover is None:
+                kept = held
+            del held
+            nearest = nearest.to(torch.int64)
+        lab = cluster_labels(parent).to(torch.int64)           # a core: the root of its component; a non-core: itself
+        border = ~core & (nearest != NEAREST_NONE)
+        lab = torch.where(border, lab[nearest.clamp(max=n - 1)], lab)
+        # per cluster its smallest member, borders included
+        index = torch.arange(n, dtype=torch.int64, device=dev)
+        first = torch.full((n,), n, dtype=torch.int64, device=dev).scatter_reduce_(0, lab, index, 'amin')
+        self._found = (deg, (core.to(torch.uint8) * KIND_CORE + border.to(torch.uint8) * KIND_BORDER))
+        return first[lab].to(torch.int32), kept
+
+
 SCORES = ('domain', 'global')
 
 
@@ -1815,7 +1934,7 @@ def all_sim(npzfile: str, report: Report, min_domain: float = None, min_global: 
 @_reporting(header=CLUSTER_HEADER)
 def cluster_sim(npzfile: str, report: Report, min_domain: float = None, min_global: float = None, linkage: str = 'single',
                 level: str = 'protein', whole: bool = True, dom: str = None, reps_out: str = None, min_coverage: float = None,
-                cov_unit: str = 'residues', rep: str = 'first'):
+                cov_unit: str = 'residues', rep: str = 'first', min_neighbors: int = None):
     """Clusters at the cut-offs, one line ``representative member`` per protein: single linkage (``Clusters``) or, with
     ``linkage='greedy'``, greedy incremental clusters in file order (``Representatives``).  ``level='domain'``: the domain
     families instead (``DomainClusters``: single linkage at ``min_domain`` alone), one line ``representative member dom1 dom2``
@@ -1825,9 +1944,14 @@ def cluster_sim(npzfile: str, report: Report, min_domain: float = None, min_glob
     ``min_domain``): two proteins are joined only if the pair also covers that share of both, in ``cov_unit`` (``all_sim``); ``dom``
     then gives the residues.  ``rep='medoid'`` (single linkage at protein level): the first field of a line is the medoid of the
     member's cluster -- the member with the smallest summed distance to the others (``Clusters.medoids``) -- instead of the cluster's
-    first member; the lines and their order stay.  ``reps_out`` then writes the medoids, in the order of the clusters' first members."""
+    first member; the lines and their order stay.  ``reps_out`` then writes the medoids, in the order of the clusters' first members.
+    ``min_neighbors`` (single linkage at protein level): density clusters instead (``DensityClusters``) -- only a protein with that
+    many pairs within the cut-offs passes a link on; 1 changes nothing."""
     if min_domain is None and min_global is None:
         raise ValueError('clustering needs a cut-off: min_domain, min_global or both')
+    if min_neighbors is not None and (linkage != 'single' or level != 'protein' or int(min_neighbors) != min_neighbors or min_neighbors < 1):
+        raise ValueError('min_neighbors is an integer of at least 1 and thins the graph of single linkage at protein level: the greedy '
+                         'rule names representatives another way, and the domain level has no protein tile')
     if rep not in REPS:
         raise ValueError(f'rep must be one of {REPS}')
     if rep == 'medoid' and (linkage != 'single' or level != 'protein'):
@@ -1848,7 +1972,10 @@ def cluster_sim(npzfile: str, report: Report, min_domain: float = None, min_glob
     if not whole or (dom is not None and min_coverage is None):
         raise ValueError('whole applies to level="domain" only, and so does dom without min_coverage')
     sid, idx, fps = _load_npz(npzfile)
-    job = (Representatives if linkage == 'greedy' else Clusters)(sid, idx, fps, min_domain=min_domain, min_global=min_global)
+    if min_neighbors is not None:
+        job = DensityClusters(sid, idx, fps, min_domain=min_domain, min_global=min_global, min_neighbors=min_neighbors)
+    else:
+        job = (Representatives if linkage == 'greedy' else Clusters)(sid, idx, fps, min_domain=min_domain, min_global=min_global)
     if min_coverage is not None:
         if min_domain is None:
             raise ValueError('min_coverage needs min_domain: it counts the fingerprints within that cut-off')
@@ -1935,18 +2062,19 @@ def _is_set(value) -> bool:
 # with ``argparse.SUPPRESS``)
 _GIVEN = {'--pair': bool, '--db': bool, '--cluster': bool, '--domains': bool, '--no-whole': bool,
           '--assign': _is_set, '--tree': _is_set, '--rank': _is_set, '--linkage': _is_set, '--level': _is_set, '--reps-out': _is_set,
-          '--dom': _is_set, '--db-dom': _is_set, '--min-coverage': _is_set, '--cov-unit': _is_set, '--rep': _is_set}
+          '--dom': _is_set, '--db-dom': _is_set, '--min-coverage': _is_set, '--cov-unit': _is_set, '--rep': _is_set,
+          '--min-neighbors': _is_set}
 # mode -> (what it does; for a mode that takes a score, what that score does; the flags it refuses, in the order they are named).
 # The modes are checked in this order.
 _MODES = {'--rbh': ('prints the reciprocal best hits of --dct and --db', 'ranks the hits',
                     ('--pair', '--cluster', '--assign', '--tree', '--rank', '--linkage', '--level', '--no-whole', '--reps-out',
-                     '--min-coverage', '--cov-unit', '--rep')),
+                     '--min-coverage', '--cov-unit', '--rep', '--min-neighbors')),
           '--tree': ('prints the single-linkage tree of --dct', 'orders the pairs',
                      ('--pair', '--db', '--cluster', '--assign', '--rank', '--linkage', '--level', '--no-whole', '--reps-out', '--domains',
-                      '--dom', '--db-dom', '--min-coverage', '--cov-unit', '--rep')),
+                      '--dom', '--db-dom', '--min-coverage', '--cov-unit', '--rep', '--min-neighbors')),
           '--assign': ('places the proteins of --dct on a fixed set of representatives', None,
                        ('--pair', '--db', '--cluster', '--rank', '--domains', '--dom', '--db-dom', '--linkage', '--level', '--no-whole',
-                        '--min-coverage', '--cov-unit', '--rep'))}
+                        '--min-coverage', '--cov-unit', '--rep', '--min-neighbors'))}
 
 
 class _Parser(argparse.ArgumentParser):
@@ -1969,7 +2097,9 @@ class _Parser(argparse.ArgumentParser):
     cluster of ``--cluster``: an error without it, beside ``--level domain`` (its nodes are fingerprints: no protein tile to sum) and,
     as ``--rep medoid``, beside ``--linkage greedy`` (whose representative every member is within the cut-offs of); ``--rep first`` is
     the default and leaves the namespace of a command line without it.  ``--cluster --rep medoid`` at protein level is the third
-    case in which ``--reps-out`` is allowed: it writes the medoids."""
+    case in which ``--reps-out`` is allowed: it writes the medoids.  ``--min-neighbors M`` makes ``--cluster`` form density clusters
+    from the single-linkage graph at protein level: an error without ``--cluster``, with M < 1, beside ``--linkage greedy`` or
+    ``--level domain`` (and beside the three modes: ``_MODES``); it leaves the conditions of ``--reps-out`` as they are."""
 
     def parse_known_args(self, args=None, namespace=None):
         ns, rest = super().parse_known_args(args, namespace)
@@ -2030,6 +2160,17 @@ class _Parser(argparse.ArgumentParser):
                            'cut-offs of its representative -- a medoid would break that guarantee')
             if names == 'first':
                 del ns.rep                                          # (the default: the namespace of a command line without it)
+        neighbors = getattr(ns, 'min_neighbors', None)
+        if neighbors is not None:
+            if not getattr(ns, 'cluster', False):
+                self.error('--min-neighbors says how many neighbours a protein needs to pass a link of --cluster on: it needs --cluster')
+            if neighbors < 1:
+                self.error('--min-neighbors is a number of neighbours: at least 1 (1 is plain single linkage)')
+            if getattr(ns, 'linkage', None) == 'greedy':
+                self.error('--min-neighbors thins the graph of single linkage: not with --linkage greedy, which names its '
+                           'representatives by a rule of its own')
+            if level == 'domain':
+                self.error('--min-neighbors counts the neighbours of a protein: not with --level domain, whose nodes are fingerprints')
         if getattr(ns, 'cluster', False):
             if getattr(ns, 'domains', False) and level != 'domain':
                 self.error('--domains (--dom, --db-dom) explains the scores of result lines: not with --cluster')
@@ -2092,6 +2233,11 @@ def build_parser() -> argparse.ArgumentParser:
                          'the file (first, the default) or its medoid, the member with the smallest summed distance to the others, '
                          'ties to the first (medoid); the lines and their order stay.  With medoid, --reps-out FILE writes the '
                          'medoids as a -dct.npz (the REPS of a later --assign)')
+    ap.add_argument('--min-neighbors', type=int, metavar='M', default=argparse.SUPPRESS,
+                    help='--cluster (single linkage, protein level): density clusters -- only a protein with at least M pairs within '
+                         'the cut-offs (a core) passes a link on, so a sparse bridge no longer chains two families; a protein with '
+                         'fewer joins the cluster of its first core neighbour in the file, or stays alone if it has none.  1 is '
+                         'plain single linkage')
     ap.add_argument('--level', choices=LEVELS, default=argparse.SUPPRESS,
                     help='--cluster: what is clustered -- the proteins (the default) or, with --min-domain, the fingerprints of '
                          'the file (domain: the domain families; one "representative member dom1 dom2" line per fingerprint, --dom '
@@ -2144,7 +2290,8 @@ def main(argv=None):
         cluster_sim(args.dct, report, min_domain=args.min_domain, min_global=args.min_global, linkage=getattr(args, 'linkage', 'single'),
                     level=level, whole=not getattr(args, 'no_whole', False), dom=dom if level == 'domain' or cover else None,
                     **({'reps_out': reps_out} if reps_out is not None else {}), **cover,
-                    **({'rep': args.rep} if getattr(args, 'rep', None) is not None else {}))
+                    **({'rep': args.rep} if getattr(args, 'rep', None) is not None else {}),
+                    **({'min_neighbors': args.min_neighbors} if getattr(args, 'min_neighbors', None) is not None else {}))
     else:
         all_sim(args.dct, report, min_domain=args.min_domain, min_global=args.min_global, domains=bool(domains), dom=dom, **cover)
     report.close()

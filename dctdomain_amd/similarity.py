@@ -651,6 +651,44 @@ def label_sums(tile: torch.Tensor, row0: int, col0: int, labels: torch.Tensor, s
         _launch(tile.device, 'dctfp_label_sums', *lead, labels.data_ptr(), sums.data_ptr(), n_nodes)
 
 
+NEAREST_NONE = 0x7fffffff                      # nearest: no core neighbour
+
+
+def _node_arrays(tile: torch.Tensor, arrays) -> int:
+    """n_nodes of the per-protein arrays beside a tile -- ``arrays`` = (tensor, dtype, name): contiguous 1-D device tensors of one
+    length on the tile's device."""
+    n_nodes = arrays[0][0].numel()
+    for t, dtype, what in arrays:
+        if t.dtype != dtype or t.dim() != 1 or not t.is_contiguous() or t.device != tile.device or t.numel() != n_nodes:
+            raise ValueError(f'{what} must be a contiguous 1-D {dtype} tensor on the device of the tile, one entry per protein')
+    return n_nodes
+
+
+def tri_degree(tile: torch.Tensor, row0: int, col0: int, bound: int, deg: torch.Tensor, row_empty=None, col_empty=None, cap: int = 17000):
+    """Adds 1 to ``deg[row0 + r]`` and to ``deg[col0 + c]`` for every entry (r, c) of an L1 tile of ONE file that ``tri_filter_count``
+    would count: col0 + c > row0 + r and min(L1, cap) <= bound, ``cap`` for a row / column flagged empty (``dctfp_tri_degree``).
+    ``deg``: device int32, one per protein (the library's uint32: a degree stays below 2^31), zeroed by the caller before the first
+    tile.  After every tile of the triangle ``deg[x]`` is the number of pairs within the bound that x is in; a count does not depend
+    on how the triangle is cut into tiles or on the order of the calls."""
+    n_nodes = _node_arrays(tile, ((deg, torch.int32, 'deg'),))
+    n_rows, n_cols, lead, _flags = _tri_filter_args(tile, row0, col0, bound, row_empty, col_empty, cap, n_nodes)
+    if n_rows and n_cols:
+        _launch(tile.device, 'dctfp_tri_degree', *lead, deg.data_ptr(), n_nodes)
+
+
+def tri_link_core(tile: torch.Tensor, row0: int, col0: int, bound: int, core: torch.Tensor, parent: torch.Tensor, nearest: torch.Tensor,
+                  row_empty=None, col_empty=None, cap: int = 17000):
+    """The second pass of the density clusters over an L1 tile (``dctfp_tri_link_core``): of the entries ``tri_degree`` counted, one
+    whose two proteins are both flagged in ``core`` (device uint8, one per protein) joins them in the forest ``parent`` (as
+    ``tri_link``; read with ``cluster_labels``), one with exactly one core end lowers ``nearest`` of the other end (device int32,
+    ``NEAREST_NONE`` at the start) to the core's index, one without a core end does nothing.  After every tile ``nearest[x]`` of a
+    non-core x is its lowest core neighbour; neither result depends on the tiling or on the order of the calls."""
+    n_nodes = _node_arrays(tile, ((core, torch.uint8, 'core'), (parent, torch.int32, 'parent'), (nearest, torch.int32, 'nearest')))
+    n_rows, n_cols, lead, _flags = _tri_filter_args(tile, row0, col0, bound, row_empty, col_empty, cap, n_nodes)
+    if n_rows and n_cols:
+        _launch(tile.device, 'dctfp_tri_link_core', *lead, core.data_ptr(), parent.data_ptr(), nearest.data_ptr(), n_nodes)
+
+
 GREEDY_NONE = 0x7fffffff                       # assign: no representative yet
 GREEDY_UNDECIDED, GREEDY_MEMBER, GREEDY_NEW, GREEDY_DONE = 0, 1, 2, 3
 

@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define DCTFP_VERSION 112 /* 0.1.12: dctfp_label_sums */
+#define DCTFP_VERSION 113 /* 0.1.13: dctfp_tri_degree, dctfp_tri_link_core */
 
 #define DCTFP_OK 0
 #define DCTFP_ERR_INVALID (-1) /* bad argument (null pointer, piece outside its sequence, ...) */
@@ -607,6 +607,37 @@ int dctfp_rect_best(dctfp_ctx* ctx, const int32_t* tile, int64_t n_rows, int64_t
 int dctfp_label_sums(dctfp_ctx* ctx, const int32_t* tile, int64_t n_rows, int64_t n_cols, int64_t ld, int64_t row0, int64_t col0,
                      const uint8_t* row_empty, const uint8_t* col_empty, int32_t cap, int32_t bound, const int32_t* labels, uint64_t* sums,
                      int64_t n_nodes, void* stream);
+
+/* Density clusters of one file (dct-sim --cluster --min-neighbors; not in the reference): DBSCAN whose radius is the cut-off.  The
+ * graph's edges are the pairs dctfp_tri_filter_count selects: entry (r, c) of an int32 tile of L1 values, at tile[r * ld + c], is
+ * the L1 of proteins i = row0 + r and j = col0 + c, and it COUNTS when j > i and key <= bound, key = cap when the row is flagged in
+ * row_empty, the column in col_empty (device uint8, one per row / column of the tile, either may be NULL) or the value is negative
+ * or >= cap, else the value.  The tile may hold entries on both sides of the diagonal: j > i takes every unordered pair once.  Two
+ * passes over the tiles of the triangle, in dctfp_label_sums' walk (plain 4-byte loads: any ld >= n_cols, a column view of a wider
+ * tensor included):
+ *   dctfp_tri_degree    -- every counted entry adds 1 to deg[i] and to deg[j] (device uint32, n_nodes entries; the caller zeroes
+ *                          it before the first tile).  Afterwards deg[x] = the number of edges at x.
+ *   dctfp_tri_link_core -- core (device uint8, n_nodes entries, nonzero = core: the caller's deg[x] >= M, written before the call)
+ *                          is only read.  A counted entry with both ends core is a union in `parent` (dctfp_tri_link's forest,
+ *                          read with dctfp_cluster_labels); one with exactly one core end lowers nearest[the other end] (device
+ *                          int32, n_nodes entries, 0x7fffffff = none: the caller fills it before the first tile) to the core's
+ *                          index; one without a core end does nothing.  Afterwards nearest[x] of a non-core x = its lowest core
+ *                          neighbour, the core whose cluster a border joins.
+ * Inside a launch deg, nearest and parent are touched by agent-scope relaxed atomics only (adds, minima, and the forest's loads
+ * and compare-and-swaps), after a reduction in the workgroup: at most one global atomic on deg / nearest per (row, 1024 columns)
+ * and per (column, 64 rows), none for a count of 0 or a minimum of none.  A count, a minimum and the components of a graph are
+ * fixed by the inputs: the results do not depend on the order in which the device ran, on how the triangle is cut into tiles or on
+ * the order of the calls.
+ * DCTFP_ERR_INVALID, with a message that starts with the export's name, for: a NULL ctx, tile or array; a negative count or
+ * offset; ld < n_cols; cap < 0, bound outside -1 .. cap; n_nodes negative or >= 2^31; row0 + n_rows > n_nodes or
+ * col0 + n_cols > n_nodes (checked on the host: the kernels bound no index); a tile, deg, parent or nearest off a 4-byte boundary.
+ * n_rows or n_cols of 0: nothing to do. */
+int dctfp_tri_degree(dctfp_ctx* ctx, const int32_t* tile, int64_t n_rows, int64_t n_cols, int64_t ld, int64_t row0, int64_t col0,
+                     const uint8_t* row_empty, const uint8_t* col_empty, int32_t cap, int32_t bound, uint32_t* deg, int64_t n_nodes,
+                     void* stream);
+int dctfp_tri_link_core(dctfp_ctx* ctx, const int32_t* tile, int64_t n_rows, int64_t n_cols, int64_t ld, int64_t row0, int64_t col0,
+                        const uint8_t* row_empty, const uint8_t* col_empty, int32_t cap, int32_t bound, const uint8_t* core, int32_t* parent,
+                        int32_t* nearest, int64_t n_nodes, void* stream);
 
 /* query_db's search (src/query_db.py:75-87: a flat FAISS index forced to METRIC_L1 at :76, index.search at :87) without a
  * distance matrix: for query rows q (nq x d, row stride ldq) and database rows b (nb x d, stride ldb), int8 on the device, each
