@@ -3054,6 +3054,40 @@ int dctfp_tri_link_core(dctfp_ctx* ctx, const int32_t* tile, int64_t n_rows, int
     return DCTFP_OK;
 } DCTFP_GUARD("dctfp_tri_link_core")
 
+// dct-sim --auc1 (k_auc.hip): tri_degree's walk, so density_tile_ok's conditions on the tile and on n_nodes; the arrays beside the
+// tile are checked here.
+int dctfp_tri_first_fp(dctfp_ctx* ctx, const int32_t* tile, int64_t n_rows, int64_t n_cols, int64_t ld, int64_t row0, int64_t col0,
+                       const uint8_t* row_empty, const uint8_t* col_empty, int32_t cap, int32_t bound, const int32_t* fam, uint64_t* first,
+                       int64_t n_nodes, void* stream_v) try {
+    if (!ctx || !tile || !fam || !first) return fail(DCTFP_ERR_INVALID, "dctfp_tri_first_fp: NULL argument");
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    RC_TRY(density_tile_ok("dctfp_tri_first_fp", tile, n_rows, n_cols, ld, row0, col0, cap, bound, n_nodes));
+    if ((reinterpret_cast<uintptr_t>(fam) & 3u) != 0 || (reinterpret_cast<uintptr_t>(first) & 7u) != 0)
+        return fail(DCTFP_ERR_INVALID, "dctfp_tri_first_fp: fam is not 4-byte aligned or first not 8-byte aligned");
+    if (cap > rect_best_max_cap())
+        return fail(DCTFP_ERR_INVALID, "dctfp_tri_first_fp: a cap above %d does not fit the packed minima of a row", rect_best_max_cap());
+    if (n_rows == 0 || n_cols == 0) return DCTFP_OK;
+    HIP_TRY(hipSetDevice(ctx->device));
+    launch_tri_first_fp(tile, n_rows, n_cols, ld, row0, col0, row_empty, col_empty, cap, bound, fam, first, (hipStream_t)stream_v);
+    HIP_TRY(hipGetLastError());
+    return DCTFP_OK;
+} DCTFP_GUARD("dctfp_tri_first_fp")
+
+int dctfp_tri_tp_before(dctfp_ctx* ctx, const int32_t* tile, int64_t n_rows, int64_t n_cols, int64_t ld, int64_t row0, int64_t col0,
+                        const uint8_t* row_empty, const uint8_t* col_empty, int32_t cap, int32_t bound, const int32_t* fam,
+                        const uint64_t* first, uint32_t* tp, int64_t n_nodes, void* stream_v) try {
+    if (!ctx || !tile || !fam || !first || !tp) return fail(DCTFP_ERR_INVALID, "dctfp_tri_tp_before: NULL argument");
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    RC_TRY(density_tile_ok("dctfp_tri_tp_before", tile, n_rows, n_cols, ld, row0, col0, cap, bound, n_nodes));
+    if (((reinterpret_cast<uintptr_t>(fam) | reinterpret_cast<uintptr_t>(tp)) & 3u) != 0 || (reinterpret_cast<uintptr_t>(first) & 7u) != 0)
+        return fail(DCTFP_ERR_INVALID, "dctfp_tri_tp_before: fam or tp is not 4-byte aligned or first not 8-byte aligned");
+    if (n_rows == 0 || n_cols == 0) return DCTFP_OK;
+    HIP_TRY(hipSetDevice(ctx->device));
+    launch_tri_tp_before(tile, n_rows, n_cols, ld, row0, col0, row_empty, col_empty, cap, bound, fam, first, tp, (hipStream_t)stream_v);
+    HIP_TRY(hipGetLastError());
+    return DCTFP_OK;
+} DCTFP_GUARD("dctfp_tri_tp_before")
+
 int dctfp_greedy_decide(dctfp_ctx* ctx, int32_t* assign, int32_t* state, const int32_t* blocked, int64_t n_nodes, int64_t i0, int64_t i1,
                         int32_t round, int64_t* undecided, void* stream_v) try {
     if (!ctx || !assign || !state || !blocked || !undecided) return fail(DCTFP_ERR_INVALID, "dctfp_greedy_decide: NULL argument");

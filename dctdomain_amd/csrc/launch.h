@@ -209,6 +209,17 @@ void launch_tri_link_core(const int32_t* tile, int64_t n_rows, int64_t n_cols, i
                           const uint8_t* col_empty, int32_t cap, int32_t bound, const uint8_t* core, int32_t* parent, int32_t* nearest,
                           hipStream_t stream);
 
+// AUC1 of a labelled file (k_auc.hip): tri_degree's walk over an int32 L1 tile of one file, twice, with fam (a family per protein)
+// beside it -- every entry tri_filter_count would count whose ends are of two families lowers first of both ends to
+// key << 32 | the other end (rect_best's packed minima: cap <= rect_best_max_cap()); then, with the finished first, every counted
+// entry of one family adds 1 to tp of each end whose own first its word is below.  Agent-scope atomic minima / adds of parts
+// reduced in the workgroup
+void launch_tri_first_fp(const int32_t* tile, int64_t n_rows, int64_t n_cols, int64_t ld, int64_t row0, int64_t col0, const uint8_t* row_empty,
+                         const uint8_t* col_empty, int32_t cap, int32_t bound, const int32_t* fam, uint64_t* first, hipStream_t stream);
+void launch_tri_tp_before(const int32_t* tile, int64_t n_rows, int64_t n_cols, int64_t ld, int64_t row0, int64_t col0, const uint8_t* row_empty,
+                          const uint8_t* col_empty, int32_t cap, int32_t bound, const int32_t* fam, const uint64_t* first, uint32_t* tp,
+                          hipStream_t stream);
+
 // (dctfp_rows_assign, k_assign.hip: the same contraction over a full rectangle -- every pair of rows within the bound lowers
 // assign[slot of the b row] to the value of the a row with an atomic minimum; value_a / slot_b NULL: a0 + r / b0 + c)
 void launch_rows_assign(const int8_t* a, int64_t na, int64_t lda, const int32_t* value_a, int64_t a0, const int8_t* b, int64_t nb, int64_t ldb,

@@ -13,6 +13,8 @@ fingerprints (``-dct.npz``), with the L1 distances computed on the GPU.
     python -m dctdomain_amd.dct_sim --dct X-dct.npz --tree [domain|global] [--min-domain X | --min-global Y] [--output F]
     python -m dctdomain_amd.dct_sim --dct A-dct.npz --db B-dct.npz --rbh [domain|global] [--min-domain X | --min-global Y] [--domains]
                                     [--dom A.dom] [--db-dom B.dom] [--output F]
+    python -m dctdomain_amd.dct_sim --dct X-dct.npz --auc1 [domain|global] (--families FILE | --family-sep C)
+                                    [--min-domain X | --min-global Y] [--output F]
 
 Same flags, same output text (src/dct-sim.py:179-211); ``--rank domain`` (not in the reference) orders database hits by
 DCTdomain instead of DCTglobal, and ``--min-domain`` / ``--min-global`` (not in the reference either, which ignores
@@ -72,6 +74,12 @@ Where the reference loops over protein pairs and, inside, over domain pairs in P
   any score, its lines give the clusters ``--cluster`` finds there.  Boruvka's algorithm in at most ceil(log2 n) + 1 rounds over
   the same tiles: per component the lightest edge that leaves it (``dctfp_tri_nearest``), then one hook per component in the same
   union-find (``dctfp_tree_hook``) and the new labels (``dctfp_cluster_labels``);
+- ``--auc1`` (``Auc1``) says how good the scores of a labelled file are, the number of the reference's own sensitivity benchmark
+  (bench/cathdb/plot_results.py): every protein is searched against the file, and its AUC1 is the share of its family's other
+  members ranked before the first hit of another family; the share of queries whose best hit is of their own family is the top-1
+  rate.  Two scans over the same tiles with a family per protein on the device -- the first false positive of every protein as
+  an atomic minimum of ``key << 32 | index`` (``dctfp_tri_first_fp``), then the true positives ranked before it
+  (``dctfp_tri_tp_before``) -- and 12 bytes per protein come back; no ranked list is ever printed or parsed;
 - ``--cluster --level domain`` (``DomainClusters``) clusters the fingerprint ROWS of the file instead of its proteins -- the
   domain families: two rows of different proteins are joined when their own L1 passes ``--min-domain``, where the protein level
   joins two proteins as soon as any one of their fingerprint pairs does.  One kernel (``dctfp_rows_link``) takes a stripe of
@@ -114,7 +122,7 @@ from .similarity import (GREEDY_NONE, PROTEIN_MIN_MAX_D, GreedyState, LineIds, T
                          greedy_decide, greedy_pairs_mark, greedy_tri_mark, l1_matrix, link_pairs, pair_argmin, pair_argmin_device, pair_line_offsets, pair_lines, pair_min, pair_min_device, protein_cover, protein_min,
                          rows_assign, rows_link, sim_lines, threshold_select, to_device_int8, tri_filter_count, tri_filter_fill, tri_link,
                          TREE_MAX_NODES, TreeState, tree_hook, tri_nearest, BestState, rect_best, label_sums, NEAREST_NONE, tri_degree,
-                         tri_link_core)
+                         tri_link_core, BEST_NONE, tri_first_fp, tri_tp_before)
 
 L1_FULL_SCALE = 17000      # src/dct-sim.py:24
 HEADER = '#prot1 prot2 sim-domain sim-global'
@@ -864,6 +872,26 @@ def _field_lines(table, fields, chunk_bytes: int):
         t0 = t1
 
 
+def _wide_field_lines(wide, lens, fields, chunk_bytes: int):
+    """``_field_lines`` for a table of ASCII strings held as fixed-width rows (``_ascii_id_rows`` of the table): a line is a row of
+    its fields' table rows -- each field as wide as its longest string in use -- every one followed by a separator slot, a space
+    or behind the last a newline, and cut at its length: one gather per field and one masked copy per chunk of lines."""
+    fields = [np.asarray(f, dtype=np.int64) for f in fields]
+    widths = [int(lens[f].max()) if len(f) else 0 for f in fields]
+    per = max(1, chunk_bytes // (sum(widths) + len(fields)))
+    for t0 in range(0, len(fields[0]), per):
+        blocks, masks = [], []
+        for k, (f, w) in enumerate(zip(fields, widths)):
+            f = f[t0:t0 + per]
+            end = lens[f][:, None]
+            block = np.empty((len(f), w + 1), dtype=np.uint8)
+            block[:, :w] = wide[:, :w][f]
+            np.put_along_axis(block, end, 32 if k + 1 < len(fields) else 10, axis=1)
+            blocks.append(block)
+            masks.append(np.arange(w + 1)[None, :] <= end)
+        yield np.concatenate(blocks, axis=1)[np.concatenate(masks, axis=1)]
+
+
 class _ProteinClusters(FilteredPairs):
     """What ``Clusters`` and ``Representatives`` share: cut-offs without domain pairs (nothing is printed per pair), the answers
     that need no tile, and the text."""
@@ -1196,6 +1224,158 @@ class Tree(FilteredPairs):
             lines.write(pi, pj, *self._scores_of(pi, pj, rows=rows))
             k0 = k1
         out.close()
+
+
+AUC1_HEADER = '#query family members tp auc1 first_fp fp_score'
+
+
+def dense_families(families):
+    """(int32 code per protein, the family behind every code) for one label per protein, of any hashable kind: codes in the order
+    in which the families first appear."""
+    codes = {}
+    fam = np.fromiter((codes.setdefault(f, len(codes)) for f in families), dtype=np.int32)
+    return fam, list(codes)
+
+
+def auc1_of_counts(tp, fam) -> np.ndarray:
+    """float64 (n): tp / (size of the protein's family - 1), 0 for a family of one (the reference's ``ZeroDivisionError`` branch,
+    bench/cathdb/plot_results.py)."""
+    fam = np.asarray(fam, dtype=np.int64)
+    others = (np.bincount(fam, minlength=1)[fam] - 1) if len(fam) else np.zeros(0, dtype=np.int64)
+    return np.where(others > 0, np.asarray(tp, dtype=np.float64) / np.maximum(others, 1), 0.0)
+
+
+def auc1_summary(tp, fam) -> dict:
+    """The summary over the queries -- the proteins whose family has at least two members: ``queries``, ``families`` (those with
+    queries), ``mean_auc1``, ``top1_raw`` (the share of queries whose best hit is of their own family: tp >= 1, see ``Auc1``) and
+    ``top1_norm`` (the mean over those families of each family's share).  Without a query the three rates are 0."""
+    fam, tp = np.asarray(fam, dtype=np.int64), np.asarray(tp, dtype=np.int64)
+    size = np.bincount(fam, minlength=1) if len(fam) else np.zeros(1, dtype=np.int64)
+    query = size[fam] > 1 if len(fam) else np.zeros(0, dtype=bool)
+    q = int(query.sum())
+    if q == 0:
+        return {'queries': 0, 'families': 0, 'mean_auc1': 0.0, 'top1_raw': 0.0, 'top1_norm': 0.0}
+    top = (tp >= 1) & query
+    share = np.bincount(fam[top], minlength=len(size))[size > 1] / size[size > 1]
+    return {'queries': q, 'families': int((size > 1).sum()), 'mean_auc1': float(auc1_of_counts(tp, fam)[query].mean()),
+            'top1_raw': float(top.sum() / q), 'top1_norm': float(share.mean())}
+
+
+def auc1_lines(sid, fam, names, tp, fp_index, fp_key, score: str = 'domain', chunk_bytes: int = 1 << 24):
+    """The text of ``--auc1`` as uint8 arrays of whole lines of about ``chunk_bytes`` each: per protein, in file order,
+    ``"{query} {family} {members} {tp} {auc1} {first_fp} {fp_score}\\n"`` -- ``members`` the family's size, ``auc1`` as ``%.4f``,
+    ``first_fp`` the id of the first false positive and ``fp_score`` that pair's similarity as the pair lines print the score
+    (``score_table``), both ``-`` where there is none -- then one line ``# queries=.. families=.. mean_auc1=.. top1_raw=..
+    top1_norm=..`` with the rates as ``%.4f``.  One table of strings -- the ids, the families, the integers, the distinct AUC1
+    values and score texts -- and index arithmetic over it: fixed-width rows cut at their lengths where every string is ASCII
+    (``_wide_field_lines``, ``cluster_lines``' way), else ``_field_lines``.  No Python loop per line."""
+    fam, tp = np.asarray(fam, dtype=np.int64), np.asarray(tp, dtype=np.int64)
+    fp_index, fp_key = np.asarray(fp_index, dtype=np.int64), np.asarray(fp_key, dtype=np.int64)
+    n = len(fam)
+    if n:
+        members = np.bincount(fam)[fam]
+        auc, auc_of = np.unique(auc1_of_counts(tp, fam), return_inverse=True)
+        none = fp_index < 0
+        keys, key_of = np.unique(np.where(none, 0, fp_key), return_inverse=True)
+        which = SCORES.index(score)                             # (score_table's entry, for the distinct keys alone)
+        parts = (np.asarray(sid, dtype=np.str_), [f'{f}' for f in names], [str(v) for v in range(int(max(members.max(), tp.max())) + 1)],
+                 ['%.4f' % v for v in auc], [f'{_scores(int(k), int(k))[which]:.3f}' for k in keys], [NO_DOMAIN])
+        at = np.concatenate([[0], np.cumsum([len(p) for p in parts])])
+        table = np.concatenate([np.asarray(p, dtype=np.str_) for p in parts])
+        me = np.arange(n, dtype=np.int64)
+        fields = [me, at[1] + fam, at[2] + members, at[2] + tp, at[3] + auc_of.reshape(-1), np.where(none, at[5], fp_index),
+                  np.where(none, at[5], at[4] + key_of.reshape(-1))]
+        wide = _ascii_id_rows(table)
+        yield from _wide_field_lines(*wide, fields, chunk_bytes) if wide is not None else _field_lines(table, fields, chunk_bytes)
+    s = auc1_summary(tp, fam)
+    last = '# queries=%d families=%d mean_auc1=%.4f top1_raw=%.4f top1_norm=%.4f\n' % (
+        s['queries'], s['families'], s['mean_auc1'], s['top1_raw'], s['top1_norm'])
+    yield np.frombuffer(last.encode('ascii'), dtype=np.uint8)
+
+
+class Auc1(FilteredPairs):
+    """How good the scores of one labelled file are (``--auc1``): the sensitivity benchmark of the reference's
+    bench/cathdb/plot_results.py without a line of ranked text.  Every protein x is searched against the whole file; y != x is a
+    **hit** of x when key(x, y) = min(L1, 17000) <= bound (17000 where either has no fingerprint), and the hits of x are ranked by
+    the word ``key << 32 | y``: by key, ties to the lower index in the file.  L1 is DCTdomain's (``score='domain'``:
+    ``protein_min``) or DCTglobal's (``'global'``: ``l1_matrix`` of the last rows, the proteins without fingerprints flagged as on
+    ``Tree``'s global route); bound = 16999, every pair of similarity above 0, unless ``min_cut`` gives ``sim_bound(min_cut)``.
+    ``families``: one label per protein, of any hashable kind.
+
+    - ``first_fp[x]`` = the smallest word over the hits of another family: the first false positive (all ones: none);
+    - ``tp[x]`` = the hits of x's own family whose word is below ``first_fp[x]``;
+    - ``auc1[x]`` = ``tp[x]`` / (size of x's family - 1), 0 for a family of one.
+
+    The best hit of x is of its own family exactly when ``tp[x] >= 1``: were the overall best hit of another family it would itself
+    be ``first_fp[x]`` and nothing could rank before it; else it is a true positive ranked before ``first_fp[x]``.  So the top-1
+    rates (Qraw, Qnorm) need no third pass.
+
+    Two passes over ``FilteredPairs.tiles`` with the dense families on the device: ``tri_first_fp`` on every tile, then
+    ``tri_tp_before`` with the finished words.  When the triangle is one stripe the tile of pass 1 is kept for pass 2, else the
+    tiles are filled again.  ``first`` and ``tp`` stay on the device between the passes and 12 bytes per protein come back, once.
+    Fewer than two proteins or a bound below 0: no hit at all, no tile.  Unlike the reference's script -- which ranks fingerprint
+    rows with faiss and keeps 300 hits per query -- this ranks proteins by ``dct-sim``'s own scores and has no hit limit."""
+
+    def __init__(self, sid, idx, fps, families, score: str = 'domain', min_cut=None):
+        if score not in SCORES:
+            raise ValueError(f'score must be one of {SCORES}')
+        super().__init__(sid, idx, fps)
+        bound = L1_FULL_SCALE - 1 if min_cut is None else sim_bound(min_cut)
+        self.score = self.route = score                         # (the tile of that score whatever the bound)
+        if score == 'domain':
+            self.bound_domain = bound
+        else:
+            self.bound_global = bound
+        self.fam, self.families = dense_families(families)
+        if len(self.fam) != len(self.idx) - 1:
+            raise ValueError('families must have one entry per protein')
+        self._counts = None
+
+    def counts(self):
+        """(tp int32, fp_index int32, fp_key int32) per protein: the true positives before the first false positive, that
+        protein's index (-1: none) and the pair's key (17000: none).  Computed once."""
+        if self._counts is None:
+            self._counts = self._scan()
+        return self._counts
+
+    def _scan(self):
+        n = len(self.idx) - 1
+        if n < 2 or self.bound < 0:
+            return np.zeros(max(n, 0), dtype=np.int32), np.full(max(n, 0), -1, dtype=np.int32), np.full(max(n, 0), L1_FULL_SCALE, dtype=np.int32)
+        import torch
+        dev = torch.device('cuda', torch.cuda.current_device())
+        fam = torch.as_tensor(self.fam, device=dev)
+        first = torch.full((n,), BEST_NONE, dtype=torch.int64, device=dev)
+        tp = torch.zeros(n, dtype=torch.int32, device=dev)
+        rows = self.device_rows() if self.route == 'domain' else None
+        held = [] if len(list(self.stripes())) == 1 else None
+        for i0, _, tile, flags in self.tiles(rows):
+            tri_first_fp(tile, i0, i0 + 1, self.bound, fam, first, *flags)
+            if held is not None:
+                held.append((i0, tile, flags))
+            del tile
+        for i0, tile, flags in (held if held is not None else ((i0, tile, flags) for i0, _, tile, flags in self.tiles(rows))):
+            tri_tp_before(tile, i0, i0 + 1, self.bound, fam, first, tp, *flags)
+            del tile
+        del held
+        back = torch.cat([first.view(torch.int32), tp]).cpu().numpy()       # one copy of 12 bytes per protein
+        word, count = back[:2 * n].view(np.int64), back[2 * n:]
+        none = word == BEST_NONE
+        return (count.copy(), np.where(none, -1, word & 0xffffffff).astype(np.int32),
+                np.where(none, L1_FULL_SCALE, word >> 32).astype(np.int32))
+
+    def auc1(self) -> np.ndarray:
+        """float64 (n): AUC1 per protein."""
+        return auc1_of_counts(self.counts()[0], self.fam)
+
+    def summary(self) -> dict:
+        """``auc1_summary`` of the file."""
+        return auc1_summary(self.counts()[0], self.fam)
+
+    def write(self, sink):
+        """Calls ``sink(memoryview)`` with the text (``auc1_lines``), whole lines at a time, in order."""
+        for text in auc1_lines(self.sid, self.fam, self.families, *self.counts(), score=self.score):
+            sink(memoryview(text))
 
 
 def domain_cluster_lines(sid, idx, labels, row_labels, chunk_bytes: int = 1 << 24):
@@ -2044,6 +2224,60 @@ def rbh_sim(npzfile: str, dbfile: str, report: Report, score: str = 'domain', mi
     job.write(report, domains=domains, labels=labels, db_labels=db_labels)
 
 
+def read_families(path: str, sid) -> list:
+    """The family of every protein of ``sid`` from a file of ``id family`` lines, separated by whitespace (``--families``).  Blank
+    lines and lines that start with ``#`` are skipped, ids that are not in ``sid`` ignored.  ValueError for a line that is not two
+    fields, an id given twice with different families and an id of ``sid`` the file does not have (the first such id is named)."""
+    wanted = {f'{s}' for s in sid}
+    family = {}
+    with open(path, encoding='utf8') as fh:
+        for number, line in enumerate(fh, 1):
+            fields = line.split()
+            if not fields or fields[0].startswith('#'):
+                continue
+            if len(fields) != 2:
+                raise ValueError(f'{path}, line {number}: a line is "id family", two fields separated by whitespace')
+            name, fam = fields
+            if name not in wanted:
+                continue
+            if family.setdefault(name, fam) != fam:
+                raise ValueError(f'{path}, line {number}: {name} is given two families, {family[name]} and {fam}')
+    for s in sid:
+        if f'{s}' not in family:
+            raise ValueError(f'{path} gives no family for {s}')
+    return [family[f'{s}'] for s in sid]
+
+
+def families_from_ids(sid, sep: str) -> list:
+    """The family of every protein from its own id: the text after the first ``sep`` (``--family-sep``; the reference's CATH20
+    ids, ``16vpA00|3.30.930.10`` with ``|``).  ValueError for an empty ``sep`` and for an id without it (the first is named)."""
+    if not sep:
+        raise ValueError('the separator between id and family is at least one character')
+    out = []
+    for s in sid:
+        head, found, fam = f'{s}'.partition(sep)
+        if not found:
+            raise ValueError(f'the id {s} has no {sep!r}: no family can be read from it')
+        out.append(fam)
+    return out
+
+
+@_reporting(header=AUC1_HEADER)
+def auc1_sim(npzfile: str, report: Report, score: str = 'domain', families: str = None, family_sep: str = None, min_domain: float = None,
+             min_global: float = None):
+    """AUC1 and the top-1 rates of a labelled file (``Auc1``) on DCTdomain (``score='domain'``) or DCTglobal (``'global'``): one line
+    ``query family members tp auc1 first_fp fp_score`` per protein and a last line with the summary.  The families come from
+    ``families`` (a file of ``id family`` lines: ``read_families``) or from the ids themselves (``family_sep``:
+    ``families_from_ids``) -- exactly one of the two.  ``min_domain`` / ``min_global``: the cut-off of that score below which a
+    pair is no hit; the other score's cut-off is an error."""
+    min_cut = _cut_of(score, min_domain, min_global, 'the hits of a query are ranked')
+    if (families is None) == (family_sep is None):
+        raise ValueError('the families come from one place: families (a file) or family_sep (the ids themselves)')
+    sid, idx, fps = _load_npz(npzfile)
+    labels = read_families(families, sid) if families is not None else families_from_ids(sid, family_sep)
+    Auc1(sid, idx, fps, labels, score=score, min_cut=min_cut).write(report.raw)
+
+
 RANKS = ('global', 'domain')
 LINKAGES = ('single', 'greedy')
 LEVELS = ('protein', 'domain')
@@ -2063,18 +2297,23 @@ def _is_set(value) -> bool:
 _GIVEN = {'--pair': bool, '--db': bool, '--cluster': bool, '--domains': bool, '--no-whole': bool,
           '--assign': _is_set, '--tree': _is_set, '--rank': _is_set, '--linkage': _is_set, '--level': _is_set, '--reps-out': _is_set,
           '--dom': _is_set, '--db-dom': _is_set, '--min-coverage': _is_set, '--cov-unit': _is_set, '--rep': _is_set,
-          '--min-neighbors': _is_set}
+          '--min-neighbors': _is_set, '--auc1': _is_set, '--families': _is_set, '--family-sep': _is_set}
 # mode -> (what it does; for a mode that takes a score, what that score does; the flags it refuses, in the order they are named).
 # The modes are checked in this order.
 _MODES = {'--rbh': ('prints the reciprocal best hits of --dct and --db', 'ranks the hits',
                     ('--pair', '--cluster', '--assign', '--tree', '--rank', '--linkage', '--level', '--no-whole', '--reps-out',
-                     '--min-coverage', '--cov-unit', '--rep', '--min-neighbors')),
+                     '--min-coverage', '--cov-unit', '--rep', '--min-neighbors', '--auc1')),
           '--tree': ('prints the single-linkage tree of --dct', 'orders the pairs',
                      ('--pair', '--db', '--cluster', '--assign', '--rank', '--linkage', '--level', '--no-whole', '--reps-out', '--domains',
-                      '--dom', '--db-dom', '--min-coverage', '--cov-unit', '--rep', '--min-neighbors')),
+                      '--dom', '--db-dom', '--min-coverage', '--cov-unit', '--rep', '--min-neighbors', '--auc1')),
           '--assign': ('places the proteins of --dct on a fixed set of representatives', None,
                        ('--pair', '--db', '--cluster', '--rank', '--domains', '--dom', '--db-dom', '--linkage', '--level', '--no-whole',
-                        '--min-coverage', '--cov-unit', '--rep', '--min-neighbors'))}
+                        '--min-coverage', '--cov-unit', '--rep', '--min-neighbors', '--auc1')),
+          '--auc1': ('measures the AUC1 and the top-1 rates of --dct', 'ranks the hits',
+                     ('--pair', '--db', '--cluster', '--assign', '--rank', '--linkage', '--level', '--no-whole', '--reps-out', '--domains',
+                      '--dom', '--db-dom', '--min-coverage', '--cov-unit', '--rep', '--min-neighbors'))}
+# the options that say where --auc1 finds the family of a protein: exactly one of them with it, none without
+_FAMILY_FLAGS = ('--families', '--family-sep')
 
 
 class _Parser(argparse.ArgumentParser):
@@ -2099,7 +2338,11 @@ class _Parser(argparse.ArgumentParser):
     the default and leaves the namespace of a command line without it.  ``--cluster --rep medoid`` at protein level is the third
     case in which ``--reps-out`` is allowed: it writes the medoids.  ``--min-neighbors M`` makes ``--cluster`` form density clusters
     from the single-linkage graph at protein level: an error without ``--cluster``, with M < 1, beside ``--linkage greedy`` or
-    ``--level domain`` (and beside the three modes: ``_MODES``); it leaves the conditions of ``--reps-out`` as they are."""
+    ``--level domain`` (and beside the three modes: ``_MODES``); it leaves the conditions of ``--reps-out`` as they are.
+    ``--auc1`` measures how well one score ranks the proteins of a labelled file, the fourth mode of ``_MODES``: it refuses what
+    ``--tree`` refuses and the other three refuse it; its own score's cut-off is allowed and the other score's an error, as for
+    ``--tree``.  It needs the family of every protein from exactly one of ``--families FILE`` and ``--family-sep C`` (``_FAMILY_FLAGS``):
+    an error with neither, with both or with an empty ``C``, and either of the two is an error without ``--auc1``."""
 
     def parse_known_args(self, args=None, namespace=None):
         ns, rest = super().parse_known_args(args, namespace)
@@ -2115,9 +2358,21 @@ class _Parser(argparse.ArgumentParser):
                 self.error('--rbh compares the proteins of --dct with those of another file: it needs --db')
             if mode == '--assign' and not cut:
                 self.error('--assign needs a cut-off: --min-domain, --min-global or both')
+            if mode == '--auc1':
+                named = [flag for flag in _FAMILY_FLAGS if _GIVEN[flag](getattr(ns, _dest(flag), None))]
+                if not named:
+                    self.error('--auc1 needs the family of every protein: --families FILE or --family-sep C')
+                if len(named) > 1:
+                    self.error('--auc1 takes the families from one place: --families or --family-sep, not both')
+                if getattr(ns, 'family_sep', None) == '':
+                    self.error('--family-sep is the text between id and family: at least one character')
             other = {'domain': 'global', 'global': 'domain'}.get(score)
             if orders and getattr(ns, f'min_{other}') is not None:
                 self.error(f'{mode} {score} {orders} by DCT{score}: its cut-off is --min-{score}, not --min-{other}')
+        if getattr(ns, 'auc1', None) is None:
+            for flag in _FAMILY_FLAGS:
+                if _GIVEN[flag](getattr(ns, _dest(flag), None)):
+                    self.error(f'{flag} says which family a protein belongs to, for --auc1 to judge the hits by: it needs --auc1')
         rbh = getattr(ns, 'rbh', None)
         names = getattr(ns, 'rep', None)
         if getattr(ns, 'assign', None) is None and getattr(ns, 'reps_out', None) is not None and not (
@@ -2262,6 +2517,19 @@ def build_parser() -> argparse.ArgumentParser:
                          '--dct.  A hit is a pair of similarity above 0, or with --min-domain X (--min-global Y with global) one not '
                          'below it; --top and --threshold do not apply.  If --db names the same file as --dct, every protein with a '
                          'fingerprint is its own best hit')
+    ap.add_argument('--auc1', nargs='?', choices=SCORES, const='domain', default=argparse.SUPPRESS,
+                    help='with --families or --family-sep: measure how well a score ranks the proteins of a labelled file instead of '
+                         'printing pairs -- every protein is searched against the file by DCTdomain (domain, the default) or DCTglobal '
+                         '(global), ties to the lower index in the file, and its AUC1 is the share of the other members of its family '
+                         'ranked before the first hit of another family; one "query family members tp auc1 first_fp fp_score" line per '
+                         'protein, then a line with the mean AUC1 and the top-1 rates.  A hit is a pair of similarity above 0, or with '
+                         '--min-domain X (--min-global Y with global) one not below it')
+    ap.add_argument('--families', metavar='FILE', default=argparse.SUPPRESS,
+                    help='--auc1: the family of every protein of --dct, one "id family" line each (blank lines and # lines are '
+                         'skipped, other ids ignored)')
+    ap.add_argument('--family-sep', metavar='C', default=argparse.SUPPRESS,
+                    help='--auc1: the family of a protein is the text after the first C in its own id (CATH20 ids: '
+                         '16vpA00|3.30.930.10 with C = "|")')
     return ap
 
 
@@ -2273,9 +2541,14 @@ def main(argv=None):
     assign, reps_out = getattr(args, 'assign', None), getattr(args, 'reps_out', None)
     min_coverage = getattr(args, 'min_coverage', None)
     cover = {'min_coverage': min_coverage, 'cov_unit': getattr(args, 'cov_unit', 'residues')} if min_coverage is not None else {}
-    report = Report(args.output, _header(CLUSTER_HEADER if args.cluster or assign is not None else HEADER, level, domains))
+    auc1 = getattr(args, 'auc1', None)
+    report = Report(args.output, _header(AUC1_HEADER if auc1 is not None else CLUSTER_HEADER if args.cluster or assign is not None else HEADER,
+                                         level, domains))
     t_work = time.time()
-    if getattr(args, 'tree', None) is not None:
+    if auc1 is not None:
+        auc1_sim(args.dct, report, score=auc1, families=getattr(args, 'families', None), family_sep=getattr(args, 'family_sep', None),
+                 min_domain=args.min_domain, min_global=args.min_global)
+    elif getattr(args, 'tree', None) is not None:
         tree_sim(args.dct, report, score=args.tree, min_domain=args.min_domain, min_global=args.min_global)
     elif getattr(args, 'rbh', None) is not None:
         rbh_sim(args.dct, args.db, report, score=args.rbh, min_domain=args.min_domain, min_global=args.min_global, domains=bool(domains),

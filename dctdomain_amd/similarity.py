@@ -689,6 +689,35 @@ def tri_link_core(tile: torch.Tensor, row0: int, col0: int, bound: int, core: to
         _launch(tile.device, 'dctfp_tri_link_core', *lead, core.data_ptr(), parent.data_ptr(), nearest.data_ptr(), n_nodes)
 
 
+def tri_first_fp(tile: torch.Tensor, row0: int, col0: int, bound: int, fam: torch.Tensor, first: torch.Tensor, row_empty=None,
+                 col_empty=None, cap: int = 17000):
+    """The first pass of ``dct-sim --auc1`` over an L1 tile of ONE file (``dctfp_tri_first_fp``): every entry (r, c) that
+    ``tri_degree`` would count -- col0 + c > row0 + r and key = min(L1, cap) <= bound, ``cap`` for a row / column flagged empty --
+    whose proteins i = row0 + r and j = col0 + c are of two families (``fam``: device int32, one per protein) lowers ``first[i]`` to
+    ``key << 32 | j`` and ``first[j]`` to ``key << 32 | i``.  ``first``: device int64, one per protein, held as ``BestState`` holds
+    its words (torch has no uint64 arithmetic) and filled with ``BEST_NONE`` by the caller before the first tile.  After every tile
+    of the triangle ``first[x]`` is the best-ranked hit of x from another family, ties to the lower index; a minimum does not
+    depend on how the triangle is cut into tiles or on the order of the calls."""
+    n_nodes = _node_arrays(tile, ((fam, torch.int32, 'fam'), (first, torch.int64, 'first')))
+    n_rows, n_cols, lead, _flags = _tri_filter_args(tile, row0, col0, bound, row_empty, col_empty, cap, n_nodes)
+    if n_rows and n_cols:
+        _launch(tile.device, 'dctfp_tri_first_fp', *lead, fam.data_ptr(), first.data_ptr(), n_nodes)
+
+
+def tri_tp_before(tile: torch.Tensor, row0: int, col0: int, bound: int, fam: torch.Tensor, first: torch.Tensor, tp: torch.Tensor,
+                  row_empty=None, col_empty=None, cap: int = 17000):
+    """The second pass of ``dct-sim --auc1`` (``dctfp_tri_tp_before``), with the ``first`` that ``tri_first_fp`` left after every
+    tile: an entry ``tri_degree`` would count whose two proteins are of one family adds 1 to ``tp[i]`` when ``key << 32 | j`` is
+    below ``first[i]`` (as unsigned words) and, decided on its own, 1 to ``tp[j]`` when ``key << 32 | i`` is below ``first[j]``.
+    ``tp``: device int32, one per protein (the library's uint32), zeroed by the caller before the first tile.  After every tile
+    ``tp[x]`` is the number of hits of x's own family ranked before its first false positive; a count does not depend on the tiling
+    or on the order of the calls."""
+    n_nodes = _node_arrays(tile, ((fam, torch.int32, 'fam'), (first, torch.int64, 'first'), (tp, torch.int32, 'tp')))
+    n_rows, n_cols, lead, _flags = _tri_filter_args(tile, row0, col0, bound, row_empty, col_empty, cap, n_nodes)
+    if n_rows and n_cols:
+        _launch(tile.device, 'dctfp_tri_tp_before', *lead, fam.data_ptr(), first.data_ptr(), tp.data_ptr(), n_nodes)
+
+
 GREEDY_NONE = 0x7fffffff                       # assign: no representative yet
 GREEDY_UNDECIDED, GREEDY_MEMBER, GREEDY_NEW, GREEDY_DONE = 0, 1, 2, 3
 

@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define DCTFP_VERSION 113 /* 0.1.13: dctfp_tri_degree, dctfp_tri_link_core */
+#define DCTFP_VERSION 114 /* 0.1.14: dctfp_tri_first_fp, dctfp_tri_tp_before */
 
 #define DCTFP_OK 0
 #define DCTFP_ERR_INVALID (-1) /* bad argument (null pointer, piece outside its sequence, ...) */
@@ -638,6 +638,38 @@ int dctfp_tri_degree(dctfp_ctx* ctx, const int32_t* tile, int64_t n_rows, int64_
 int dctfp_tri_link_core(dctfp_ctx* ctx, const int32_t* tile, int64_t n_rows, int64_t n_cols, int64_t ld, int64_t row0, int64_t col0,
                         const uint8_t* row_empty, const uint8_t* col_empty, int32_t cap, int32_t bound, const uint8_t* core, int32_t* parent,
                         int32_t* nearest, int64_t n_nodes, void* stream);
+
+/* AUC1 of a labelled file (dct-sim --auc1; the reference's bench/cathdb/plot_results.py reads the same number out of ranked text):
+ * per protein the hits of its own family ranked before its first hit of another family.  Entry (r, c) of an int32 tile of L1
+ * values, at tile[r * ld + c], is the L1 of proteins i = row0 + r and j = col0 + c of ONE file, and it COUNTS when
+ * dctfp_tri_degree would count it: j > i and key <= bound, key = cap when the row is flagged in row_empty, the column in col_empty
+ * (device uint8, one per row / column of the tile, either may be NULL) or the value is negative or >= cap, else the value.  A
+ * counted entry makes j a hit of i and i a hit of j.  fam (device int32, n_nodes entries, written before the call; the values are
+ * only compared) names every protein's family, and the hits of one protein are ranked by the word key << 32 | index of the hit:
+ * unsigned 64-bit order = (key, index), ties to the lower protein.  Two passes over the tiles of the triangle, in
+ * dctfp_tri_degree's walk (plain 4-byte loads: any ld >= n_cols, a column view of a wider tensor included):
+ *   dctfp_tri_first_fp  -- a counted entry with fam[i] != fam[j] lowers first[i] to key << 32 | j and first[j] to key << 32 | i
+ *                          (device uint64, n_nodes entries, 8-byte aligned, all ones = none: the caller fills it before the
+ *                          first tile).  Afterwards first[x] = the first false positive of x.
+ *   dctfp_tri_tp_before -- first is finished and only read.  A counted entry with fam[i] == fam[j] adds 1 to tp[i] when
+ *                          key << 32 | j < first[i] and, decided on its own, 1 to tp[j] when key << 32 | i < first[j] (device
+ *                          uint32, n_nodes entries; the caller zeroes it before the first tile).  Afterwards tp[x] = the true
+ *                          positives of x ranked before its first false positive.
+ * Inside a launch first (pass 1) and tp (pass 2) are touched by agent-scope relaxed atomics only -- dctfp_rect_best's load and
+ * minimum, dctfp_tri_degree's add -- after a reduction in the workgroup: at most one global atomic per (row, 1024 columns) and per
+ * (column, 64 rows), none for a minimum of none or a count of 0.  A minimum and a count are fixed by the inputs: the results do
+ * not depend on the order in which the device ran, on how the triangle is cut into tiles or on the order of the calls.
+ * DCTFP_ERR_INVALID, with a message that starts with the export's name, for: a NULL ctx, tile or array; a negative count or
+ * offset; ld < n_cols; cap < 0, bound outside -1 .. cap; n_nodes negative or >= 2^31; row0 + n_rows > n_nodes or
+ * col0 + n_cols > n_nodes (checked on the host: the kernels bound no index); a tile, fam or tp off a 4-byte or first off an 8-byte
+ * boundary; for dctfp_tri_first_fp a cap above 4194302 (a row's minimum is packed as key << 10 | column in 32 bits).  n_rows or
+ * n_cols of 0: nothing to do. */
+int dctfp_tri_first_fp(dctfp_ctx* ctx, const int32_t* tile, int64_t n_rows, int64_t n_cols, int64_t ld, int64_t row0, int64_t col0,
+                       const uint8_t* row_empty, const uint8_t* col_empty, int32_t cap, int32_t bound, const int32_t* fam, uint64_t* first,
+                       int64_t n_nodes, void* stream);
+int dctfp_tri_tp_before(dctfp_ctx* ctx, const int32_t* tile, int64_t n_rows, int64_t n_cols, int64_t ld, int64_t row0, int64_t col0,
+                        const uint8_t* row_empty, const uint8_t* col_empty, int32_t cap, int32_t bound, const int32_t* fam,
+                        const uint64_t* first, uint32_t* tp, int64_t n_nodes, void* stream);
 
 /* query_db's search (src/query_db.py:75-87: a flat FAISS index forced to METRIC_L1 at :76, index.search at :87) without a
  * distance matrix: for query rows q (nq x d, row stride ldq) and database rows b (nb x d, stride ldb), int8 on the device, each
