@@ -44,7 +44,7 @@ UNITS = ['dctfp.hip', 'k_walk.hip', 'k_gen.hip', 'k_reccut.hip', 'k_search.hip',
 TWIN_UNITS = ('dctfp.hip',)
 HEADERS = [os.path.join(CSRC, 'kernels.hip.h'), os.path.join(CSRC, 'launch.h'), os.path.join(ROOT, 'include', 'dctfp.h'),
            os.path.join(CSRC, 'reccut_kernel.hip.h'), os.path.join(CSRC, 'k_stage_a.inc'), os.path.join(CSRC, 'tri_walk.hip.h'), os.path.join(CSRC, 'sad_tile.hip.h'),
-           os.path.join(CSRC, 'union_find.hip.h')]
+           os.path.join(CSRC, 'tri_tile.hip.h'), os.path.join(CSRC, 'band_walk.hip.h'), os.path.join(CSRC, 'union_find.hip.h')]
 OBJ_DIR = os.path.join(ROOT, 'build', 'dctfp_objs')
 
 

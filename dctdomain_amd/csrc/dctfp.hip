@@ -25,7 +25,7 @@
 
 #include "launch.h"   // (kernels.hip.h, the parameter blocks and the launchers of the kernel families built in their own units)
 #include "reccut_kernel.hip.h"   // (CutJob, table sizes; the kernel itself is instantiated in k_reccut.hip)
-#include "tri_walk.hip.h"        // (TriTile; the kernels that scan one are in k_filter / k_cluster / k_greedy / k_tree.hip)
+#include "tri_tile.hip.h"        // (TriTile; the kernels that scan one include tri_walk.hip.h or band_walk.hip.h)
 
 using namespace dctfp;
 using namespace dctfp_host;
@@ -2967,6 +2967,19 @@ int dctfp_tree_hook(dctfp_ctx* ctx, const int32_t* comp, uint64_t* best, int32_t
     return DCTFP_OK;
 } DCTFP_GUARD("dctfp_tree_hook")
 
+// What the five exports of the band walk over a triangle (band_walk.hip.h) ask of the tile and of n_nodes; `name` = the export, for the
+// message.  The arrays beside the tile are checked by the export that knows them.
+static int check_band_tile(const char* name, const TriTile& t, int64_t n_nodes) {
+    if (t.n_rows < 0 || t.n_cols < 0 || t.ld < t.n_cols || t.row0 < 0 || t.col0 < 0 || t.cap < 0 || t.bound < -1 || t.bound > t.cap)
+        return fail(DCTFP_ERR_INVALID, "%s: bad shape, cap or bound", name);
+    if ((reinterpret_cast<uintptr_t>(t.tile) & 3u) != 0) return fail(DCTFP_ERR_INVALID, "%s: the tile is not 4-byte aligned", name);
+    if (n_nodes < 0 || n_nodes > 0x7fffffff) return fail(DCTFP_ERR_INVALID, "%s: n_nodes must lie in 0 .. 2^31 - 1", name);
+    // (every index the kernel can form lies inside the tile and the arrays: bounded here, on the host, and not on the device)
+    if (t.n_rows > n_nodes || t.row0 > n_nodes - t.n_rows || t.n_cols > n_nodes || t.col0 > n_nodes - t.n_cols)
+        return fail(DCTFP_ERR_INVALID, "%s: the tile names proteins outside the arrays", name);
+    return DCTFP_OK;
+}
+
 int dctfp_rect_best(dctfp_ctx* ctx, const int32_t* tile, int64_t n_rows, int64_t n_cols, int64_t ld, int64_t row0, int64_t col0,
                     const uint8_t* row_empty, const uint8_t* col_empty, int32_t cap, int32_t bound, uint64_t* best_row, int64_t n_a,
                     uint64_t* best_col, int64_t n_b, void* stream_v) try {
@@ -2984,7 +2997,7 @@ int dctfp_rect_best(dctfp_ctx* ctx, const int32_t* tile, int64_t n_rows, int64_t
     if (row0 + n_rows > n_a || col0 + n_cols > n_b) return fail(DCTFP_ERR_INVALID, "dctfp_rect_best: the tile names proteins outside best_row / best_col");
     if (n_rows == 0 || n_cols == 0) return DCTFP_OK;
     HIP_TRY(hipSetDevice(ctx->device));
-    launch_rect_best(tile, n_rows, n_cols, ld, row0, col0, row_empty, col_empty, cap, bound, best_row, best_col, (hipStream_t)stream_v);
+    launch_rect_best(TriTile{tile, n_rows, n_cols, ld, row0, col0, row_empty, col_empty, cap, bound}, best_row, best_col, (hipStream_t)stream_v);
     HIP_TRY(hipGetLastError());
     return DCTFP_OK;
 } DCTFP_GUARD("dctfp_rect_best")
@@ -2992,49 +3005,33 @@ int dctfp_rect_best(dctfp_ctx* ctx, const int32_t* tile, int64_t n_rows, int64_t
 int dctfp_label_sums(dctfp_ctx* ctx, const int32_t* tile, int64_t n_rows, int64_t n_cols, int64_t ld, int64_t row0, int64_t col0,
                      const uint8_t* row_empty, const uint8_t* col_empty, int32_t cap, int32_t bound, const int32_t* labels, uint64_t* sums,
                      int64_t n_nodes, void* stream_v) try {
-    (void)bound;   // (a sum has no cut-off: every pair of one label counts, with its key)
+    (void)bound;   // (a sum has no cut-off: every pair of one label counts, with its key -- the tile's bound is its cap)
     if (!ctx || !tile || !labels || !sums) return fail(DCTFP_ERR_INVALID, "dctfp_label_sums: NULL argument");
     std::lock_guard<std::mutex> lock(ctx->mu);
-    // (rect_best's walk, not a tile of the triangle's shifted one: its own few conditions)
-    if (n_rows < 0 || n_cols < 0 || ld < n_cols || row0 < 0 || col0 < 0 || cap < 0) return fail(DCTFP_ERR_INVALID, "dctfp_label_sums: bad shape or cap");
-    if (((reinterpret_cast<uintptr_t>(tile) | reinterpret_cast<uintptr_t>(labels)) & 3u) != 0 || (reinterpret_cast<uintptr_t>(sums) & 7u) != 0)
-        return fail(DCTFP_ERR_INVALID, "dctfp_label_sums: the tile or the labels are not 4-byte aligned or sums is not 8-byte aligned");
+    const TriTile t{tile, n_rows, n_cols, ld, row0, col0, row_empty, col_empty, cap, cap};
+    RC_TRY(check_band_tile("dctfp_label_sums", t, n_nodes));
+    if ((reinterpret_cast<uintptr_t>(labels) & 3u) != 0 || (reinterpret_cast<uintptr_t>(sums) & 7u) != 0)
+        return fail(DCTFP_ERR_INVALID, "dctfp_label_sums: the labels are not 4-byte aligned or sums is not 8-byte aligned");
     if (cap > label_sums_max_cap())
         return fail(DCTFP_ERR_INVALID, "dctfp_label_sums: a cap above %d does not fit the 32-bit partial sums of a row", label_sums_max_cap());
-    if (n_nodes < 0 || n_nodes > 0x7fffffff) return fail(DCTFP_ERR_INVALID, "dctfp_label_sums: n_nodes must lie in 0 .. 2^31 - 1");
-    // (every index the kernel can form lies inside the tile, labels and sums: bounded here, on the host, and not on the device)
-    if (n_rows > n_nodes || row0 > n_nodes - n_rows || n_cols > n_nodes || col0 > n_nodes - n_cols) return fail(DCTFP_ERR_INVALID, "dctfp_label_sums: the tile names proteins outside labels / sums");
     if (n_rows == 0 || n_cols == 0) return DCTFP_OK;
     HIP_TRY(hipSetDevice(ctx->device));
-    launch_label_sums(tile, n_rows, n_cols, ld, row0, col0, row_empty, col_empty, cap, labels, sums, (hipStream_t)stream_v);
+    launch_label_sums(t, labels, sums, (hipStream_t)stream_v);
     HIP_TRY(hipGetLastError());
     return DCTFP_OK;
 } DCTFP_GUARD("dctfp_label_sums")
-
-// What dctfp_tri_degree and dctfp_tri_link_core ask of the tile and of n_nodes (label_sums' walk, so label_sums' conditions, and a
-// bound); `name` = the export, for the message.  The arrays beside the tile are checked by the export that knows them.
-static int density_tile_ok(const char* name, const int32_t* tile, int64_t n_rows, int64_t n_cols, int64_t ld, int64_t row0, int64_t col0,
-                           int32_t cap, int32_t bound, int64_t n_nodes) {
-    if (n_rows < 0 || n_cols < 0 || ld < n_cols || row0 < 0 || col0 < 0 || cap < 0 || bound < -1 || bound > cap)
-        return fail(DCTFP_ERR_INVALID, "%s: bad shape, cap or bound", name);
-    if ((reinterpret_cast<uintptr_t>(tile) & 3u) != 0) return fail(DCTFP_ERR_INVALID, "%s: the tile is not 4-byte aligned", name);
-    if (n_nodes < 0 || n_nodes > 0x7fffffff) return fail(DCTFP_ERR_INVALID, "%s: n_nodes must lie in 0 .. 2^31 - 1", name);
-    // (every index the kernel can form lies inside the tile and the arrays: bounded here, on the host, and not on the device)
-    if (n_rows > n_nodes || row0 > n_nodes - n_rows || n_cols > n_nodes || col0 > n_nodes - n_cols)
-        return fail(DCTFP_ERR_INVALID, "%s: the tile names proteins outside the arrays", name);
-    return DCTFP_OK;
-}
 
 int dctfp_tri_degree(dctfp_ctx* ctx, const int32_t* tile, int64_t n_rows, int64_t n_cols, int64_t ld, int64_t row0, int64_t col0,
                      const uint8_t* row_empty, const uint8_t* col_empty, int32_t cap, int32_t bound, uint32_t* deg, int64_t n_nodes,
                      void* stream_v) try {
     if (!ctx || !tile || !deg) return fail(DCTFP_ERR_INVALID, "dctfp_tri_degree: NULL argument");
     std::lock_guard<std::mutex> lock(ctx->mu);
-    RC_TRY(density_tile_ok("dctfp_tri_degree", tile, n_rows, n_cols, ld, row0, col0, cap, bound, n_nodes));
+    const TriTile t{tile, n_rows, n_cols, ld, row0, col0, row_empty, col_empty, cap, bound};
+    RC_TRY(check_band_tile("dctfp_tri_degree", t, n_nodes));
     if ((reinterpret_cast<uintptr_t>(deg) & 3u) != 0) return fail(DCTFP_ERR_INVALID, "dctfp_tri_degree: deg is not 4-byte aligned");
     if (n_rows == 0 || n_cols == 0) return DCTFP_OK;
     HIP_TRY(hipSetDevice(ctx->device));
-    launch_tri_degree(tile, n_rows, n_cols, ld, row0, col0, row_empty, col_empty, cap, bound, deg, (hipStream_t)stream_v);
+    launch_tri_degree(t, deg, (hipStream_t)stream_v);
     HIP_TRY(hipGetLastError());
     return DCTFP_OK;
 } DCTFP_GUARD("dctfp_tri_degree")
@@ -3044,31 +3041,32 @@ int dctfp_tri_link_core(dctfp_ctx* ctx, const int32_t* tile, int64_t n_rows, int
                         int32_t* nearest, int64_t n_nodes, void* stream_v) try {
     if (!ctx || !tile || !core || !parent || !nearest) return fail(DCTFP_ERR_INVALID, "dctfp_tri_link_core: NULL argument");
     std::lock_guard<std::mutex> lock(ctx->mu);
-    RC_TRY(density_tile_ok("dctfp_tri_link_core", tile, n_rows, n_cols, ld, row0, col0, cap, bound, n_nodes));
+    const TriTile t{tile, n_rows, n_cols, ld, row0, col0, row_empty, col_empty, cap, bound};
+    RC_TRY(check_band_tile("dctfp_tri_link_core", t, n_nodes));
     if (((reinterpret_cast<uintptr_t>(parent) | reinterpret_cast<uintptr_t>(nearest)) & 3u) != 0)
         return fail(DCTFP_ERR_INVALID, "dctfp_tri_link_core: parent or nearest is not 4-byte aligned");
     if (n_rows == 0 || n_cols == 0) return DCTFP_OK;
     HIP_TRY(hipSetDevice(ctx->device));
-    launch_tri_link_core(tile, n_rows, n_cols, ld, row0, col0, row_empty, col_empty, cap, bound, core, parent, nearest, (hipStream_t)stream_v);
+    launch_tri_link_core(t, core, parent, nearest, (hipStream_t)stream_v);
     HIP_TRY(hipGetLastError());
     return DCTFP_OK;
 } DCTFP_GUARD("dctfp_tri_link_core")
 
-// dct-sim --auc1 (k_auc.hip): tri_degree's walk, so density_tile_ok's conditions on the tile and on n_nodes; the arrays beside the
-// tile are checked here.
+// dct-sim --auc1 (k_auc.hip)
 int dctfp_tri_first_fp(dctfp_ctx* ctx, const int32_t* tile, int64_t n_rows, int64_t n_cols, int64_t ld, int64_t row0, int64_t col0,
                        const uint8_t* row_empty, const uint8_t* col_empty, int32_t cap, int32_t bound, const int32_t* fam, uint64_t* first,
                        int64_t n_nodes, void* stream_v) try {
     if (!ctx || !tile || !fam || !first) return fail(DCTFP_ERR_INVALID, "dctfp_tri_first_fp: NULL argument");
     std::lock_guard<std::mutex> lock(ctx->mu);
-    RC_TRY(density_tile_ok("dctfp_tri_first_fp", tile, n_rows, n_cols, ld, row0, col0, cap, bound, n_nodes));
+    const TriTile t{tile, n_rows, n_cols, ld, row0, col0, row_empty, col_empty, cap, bound};
+    RC_TRY(check_band_tile("dctfp_tri_first_fp", t, n_nodes));
     if ((reinterpret_cast<uintptr_t>(fam) & 3u) != 0 || (reinterpret_cast<uintptr_t>(first) & 7u) != 0)
         return fail(DCTFP_ERR_INVALID, "dctfp_tri_first_fp: fam is not 4-byte aligned or first not 8-byte aligned");
     if (cap > rect_best_max_cap())
         return fail(DCTFP_ERR_INVALID, "dctfp_tri_first_fp: a cap above %d does not fit the packed minima of a row", rect_best_max_cap());
     if (n_rows == 0 || n_cols == 0) return DCTFP_OK;
     HIP_TRY(hipSetDevice(ctx->device));
-    launch_tri_first_fp(tile, n_rows, n_cols, ld, row0, col0, row_empty, col_empty, cap, bound, fam, first, (hipStream_t)stream_v);
+    launch_tri_first_fp(t, fam, first, (hipStream_t)stream_v);
     HIP_TRY(hipGetLastError());
     return DCTFP_OK;
 } DCTFP_GUARD("dctfp_tri_first_fp")
@@ -3078,12 +3076,13 @@ int dctfp_tri_tp_before(dctfp_ctx* ctx, const int32_t* tile, int64_t n_rows, int
                         const uint64_t* first, uint32_t* tp, int64_t n_nodes, void* stream_v) try {
     if (!ctx || !tile || !fam || !first || !tp) return fail(DCTFP_ERR_INVALID, "dctfp_tri_tp_before: NULL argument");
     std::lock_guard<std::mutex> lock(ctx->mu);
-    RC_TRY(density_tile_ok("dctfp_tri_tp_before", tile, n_rows, n_cols, ld, row0, col0, cap, bound, n_nodes));
+    const TriTile t{tile, n_rows, n_cols, ld, row0, col0, row_empty, col_empty, cap, bound};
+    RC_TRY(check_band_tile("dctfp_tri_tp_before", t, n_nodes));
     if (((reinterpret_cast<uintptr_t>(fam) | reinterpret_cast<uintptr_t>(tp)) & 3u) != 0 || (reinterpret_cast<uintptr_t>(first) & 7u) != 0)
         return fail(DCTFP_ERR_INVALID, "dctfp_tri_tp_before: fam or tp is not 4-byte aligned or first not 8-byte aligned");
     if (n_rows == 0 || n_cols == 0) return DCTFP_OK;
     HIP_TRY(hipSetDevice(ctx->device));
-    launch_tri_tp_before(tile, n_rows, n_cols, ld, row0, col0, row_empty, col_empty, cap, bound, fam, first, tp, (hipStream_t)stream_v);
+    launch_tri_tp_before(t, fam, first, tp, (hipStream_t)stream_v);
     HIP_TRY(hipGetLastError());
     return DCTFP_OK;
 } DCTFP_GUARD("dctfp_tri_tp_before")

@@ -19,7 +19,7 @@
 
 namespace dctfp {
 struct CutJob;   // reccut_kernel.hip.h
-struct TriTile;  // tri_walk.hip.h
+struct TriTile;  // tri_tile.hip.h
 }
 
 namespace dctfp_host {
@@ -189,36 +189,28 @@ hipError_t launch_tree_hook(const int32_t* comp, uint64_t* best, int32_t* parent
 // min(L1, cap) <= bound (cap for a flagged protein) lowers best_row[row0 + r] to key << 32 | (col0 + c) and best_col[col0 + c] to
 // key << 32 | (row0 + r) with agent-scope atomic minima; rect_best_max_cap = the largest cap the kernel's packed LDS words hold
 int rect_best_max_cap();
-void launch_rect_best(const int32_t* tile, int64_t n_rows, int64_t n_cols, int64_t ld, int64_t row0, int64_t col0, const uint8_t* row_empty,
-                      const uint8_t* col_empty, int32_t cap, int32_t bound, uint64_t* best_row, uint64_t* best_col, hipStream_t stream);
+void launch_rect_best(const TriTile& t, uint64_t* best_row, uint64_t* best_col, hipStream_t stream);
 
-// the summed distances behind a cluster's medoid (k_medoid.hip): rect_best's walk over an int32 L1 tile of one file -- every entry
+// the summed distances behind a cluster's medoid (k_medoid.hip): the band walk over an int32 L1 tile of one file -- every entry
 // with col0 + c > row0 + r whose two proteins carry one label adds min(L1, cap) (cap for a flagged protein) to sums of both, with
 // agent-scope 64-bit atomic adds of partial sums kept in 32 bits; label_sums_max_cap = the largest cap for which those cannot overflow
 int label_sums_max_cap();
-void launch_label_sums(const int32_t* tile, int64_t n_rows, int64_t n_cols, int64_t ld, int64_t row0, int64_t col0, const uint8_t* row_empty,
-                       const uint8_t* col_empty, int32_t cap, const int32_t* labels, uint64_t* sums, hipStream_t stream);
+void launch_label_sums(const TriTile& t, const int32_t* labels, uint64_t* sums, hipStream_t stream);
 
-// density clusters (k_density.hip): label_sums' walk over an int32 L1 tile of one file, twice -- every entry tri_filter_count would
+// density clusters (k_density.hip): the band walk over an int32 L1 tile of one file, twice -- every entry tri_filter_count would
 // count (col0 + c > row0 + r, min(L1, cap) <= bound, cap for a flagged protein) adds 1 to deg of both ends; then, with core per
 // protein, a core-core entry is a union in parent and an entry with one core end lowers nearest of the other end to the core's index.
 // Agent-scope atomic adds / minima of parts reduced in the workgroup, and the forest's own atomics
-void launch_tri_degree(const int32_t* tile, int64_t n_rows, int64_t n_cols, int64_t ld, int64_t row0, int64_t col0, const uint8_t* row_empty,
-                       const uint8_t* col_empty, int32_t cap, int32_t bound, uint32_t* deg, hipStream_t stream);
-void launch_tri_link_core(const int32_t* tile, int64_t n_rows, int64_t n_cols, int64_t ld, int64_t row0, int64_t col0, const uint8_t* row_empty,
-                          const uint8_t* col_empty, int32_t cap, int32_t bound, const uint8_t* core, int32_t* parent, int32_t* nearest,
-                          hipStream_t stream);
+void launch_tri_degree(const TriTile& t, uint32_t* deg, hipStream_t stream);
+void launch_tri_link_core(const TriTile& t, const uint8_t* core, int32_t* parent, int32_t* nearest, hipStream_t stream);
 
-// AUC1 of a labelled file (k_auc.hip): tri_degree's walk over an int32 L1 tile of one file, twice, with fam (a family per protein)
+// AUC1 of a labelled file (k_auc.hip): the band walk over an int32 L1 tile of one file, twice, with fam (a family per protein)
 // beside it -- every entry tri_filter_count would count whose ends are of two families lowers first of both ends to
 // key << 32 | the other end (rect_best's packed minima: cap <= rect_best_max_cap()); then, with the finished first, every counted
 // entry of one family adds 1 to tp of each end whose own first its word is below.  Agent-scope atomic minima / adds of parts
 // reduced in the workgroup
-void launch_tri_first_fp(const int32_t* tile, int64_t n_rows, int64_t n_cols, int64_t ld, int64_t row0, int64_t col0, const uint8_t* row_empty,
-                         const uint8_t* col_empty, int32_t cap, int32_t bound, const int32_t* fam, uint64_t* first, hipStream_t stream);
-void launch_tri_tp_before(const int32_t* tile, int64_t n_rows, int64_t n_cols, int64_t ld, int64_t row0, int64_t col0, const uint8_t* row_empty,
-                          const uint8_t* col_empty, int32_t cap, int32_t bound, const int32_t* fam, const uint64_t* first, uint32_t* tp,
-                          hipStream_t stream);
+void launch_tri_first_fp(const TriTile& t, const int32_t* fam, uint64_t* first, hipStream_t stream);
+void launch_tri_tp_before(const TriTile& t, const int32_t* fam, const uint64_t* first, uint32_t* tp, hipStream_t stream);
 
 // (dctfp_rows_assign, k_assign.hip: the same contraction over a full rectangle -- every pair of rows within the bound lowers
 // assign[slot of the b row] to the value of the a row with an atomic minimum; value_a / slot_b NULL: a0 + r / b0 + c)

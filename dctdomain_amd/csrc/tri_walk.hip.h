@@ -1,27 +1,13 @@
-// The int32 L1 tile that the kernels of the all-against-all cut-offs scan, and the walk over one of its rows.  Users: k_filter.hip
-// (count and fill), k_cluster.hip (link), k_greedy.hip (mark), k_tree.hip (nearest) and dctfp.hip, whose exports build and check
-// the TriTile.  One workgroup per row at a time, 1024 columns per step, one 16-byte load per thread, and the rule that says
-// which of a thread's four entries survive.
+// The walk over one row of a TriTile (tri_tile.hip.h).  Users: k_filter.hip (count and fill), k_cluster.hip (link), k_greedy.hip
+// (mark) and k_tree.hip (nearest).  One workgroup per row at a time, 1024 columns per step, one 16-byte load per thread, and the
+// rule that says which of a thread's four entries survive.
 #pragma once
 
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
 
-namespace dctfp {
-
-// The tile as every kernel, launcher and export of the family takes it.  Entry (r, c), at tile[r * ld + c], is the L1 of proteins
-// row0 + r and col0 + c; row_empty / col_empty (either may be NULL) flag the proteins without a fingerprint, whose key is cap;
-// an entry survives when its key = min(L1, cap) <= bound.  A kernel takes the struct by value as its first argument.
-struct TriTile {
-    const int32_t* tile;
-    int64_t n_rows, n_cols, ld, row0, col0;
-    const uint8_t* row_empty;
-    const uint8_t* col_empty;
-    int32_t cap, bound;
-};
-
-}  // namespace dctfp
+#include "tri_tile.hip.h"
 
 namespace {
 

@@ -679,6 +679,16 @@ class FilteredPairs:
             yield i0, i1, tile, flags
             del tile                                            # (before the next one is made; the caller drops its own too)
 
+    def tile_pass(self, rows: _DeviceRows = None, cover: bool = True, hold: list = None):
+        """Yields (i0, tile, flags) per stripe of ``tiles(rows, cover)``, each tile dropped before the next is made.  ``hold``: a list that
+        gets the one tile when the triangle is one stripe -- a later pass then iterates ``held or self.tile_pass(...)``."""
+        one = hold is not None and len(list(self.stripes())) == 1
+        for i0, _, tile, flags in self.tiles(rows, cover):
+            if one:
+                hold.append((i0, tile, flags))
+            yield i0, tile, flags
+            del tile
+
     def _scores_of(self, pi, pj, domains: bool = False, rows: _DeviceRows = None):
         """Step 3 of the class text: device int32 (min L1, last L1) of the pairs (pi[k], pj[k]) (device int32) -- ``domains``: also
         (arg_i, arg_j).  ``pair_min_device`` / ``pair_argmin_device`` on the file where it stays on the device, else
@@ -953,18 +963,15 @@ class Clusters(_ProteinClusters):
         the triangle is one stripe, under no coverage, and ``tri_link`` read its tile -- else None."""
         import torch
         parent = torch.arange(len(self.idx) - 1, dtype=torch.int32, device=torch.device('cuda', torch.cuda.current_device()))
-        kept = None
+        held = [] if keep and self.cover is None else None
         if max(self.bound_domain, self.bound_global) < L1_FULL_SCALE:
             for pi, pj, *_ in self.chunks():
                 link_pairs(pi, pj, parent)
         else:
-            keep = keep and self.cover is None and len(list(self.stripes())) == 1
-            for i0, _, tile, flags in self.tiles():
+            for i0, tile, flags in self.tile_pass(hold=held):
                 tri_link(tile, i0, i0 + 1, self.bound, parent, *flags)
-                if keep:
-                    kept = [(i0, tile, flags)]
                 del tile
-        return cluster_labels(parent), kept
+        return cluster_labels(parent), held or None
 
     def medoids(self, labels=None) -> np.ndarray:
         """``rep`` (int32, n): ``rep[x]`` = the medoid of the cluster of protein x (class text) -- of ``labels()``, or of ``labels``
@@ -988,7 +995,7 @@ class Clusters(_ProteinClusters):
         dev = torch.device('cuda', torch.cuda.current_device())
         lab_dev = torch.as_tensor(labels, device=dev)
         sums = torch.zeros(n, dtype=torch.int64, device=dev)
-        for i0, tile, flags in (kept if kept is not None else ((i0, tile, flags) for i0, _, tile, flags in self.tiles(cover=False))):
+        for i0, tile, flags in kept or self.tile_pass(cover=False):
             label_sums(tile, i0, i0 + 1, lab_dev, sums, *flags, cap=L1_FULL_SCALE)
             del tile
         del kept
@@ -1086,20 +1093,17 @@ class DensityClusters(Clusters):
                 nearest.scatter_reduce_(0, pj[ci & ~cj], pi[ci & ~cj], 'amin')
                 nearest.scatter_reduce_(0, pi[cj & ~ci], pj[cj & ~ci], 'amin')
         else:
-            held = [] if len(list(self.stripes())) == 1 else None
-            for i0, _, tile, flags in self.tiles():
+            held = []
+            for i0, tile, flags in self.tile_pass(hold=held):
                 tri_degree(tile, i0, i0 + 1, self.bound, deg, *flags)
-                if held is not None:
-                    held.append((i0, tile, flags))
                 del tile
             core = deg >= self.min_neighbors
             flag = core.to(torch.uint8)
             nearest = torch.full((n,), NEAREST_NONE, dtype=torch.int32, device=dev)
-            for i0, tile, flags in (held if held is not None else ((i0, tile, flags) for i0, _, tile, flags in self.tiles())):
+            for i0, tile, flags in held or self.tile_pass():
                 tri_link_core(tile, i0, i0 + 1, self.bound, flag, parent, nearest, *flags)
                 del tile
-            if keep and self.cover is None:
-                kept = held
+            kept = (held or None) if keep and self.cover is None else None
             del held
             nearest = nearest.to(torch.int64)
         lab = cluster_labels(parent).to(torch.int64)           # a core: the root of its component; a non-core: itself
@@ -1168,15 +1172,13 @@ class Tree(FilteredPairs):
             raise ValueError(f'the tree takes at most {TREE_MAX_NODES} proteins')
         ts = TreeState(n)
         rows = self.device_rows() if self.route == 'domain' else None
-        kept = None
-        if len(list(self.stripes())) == 1:                      # the whole triangle in one tile: computed once
-            kept = [(i0, tile, flags) for i0, _, tile, flags in self.tiles(rows)]
+        held = []                                               # (the whole triangle in one tile: computed once)
         most = max(1, int(n - 1).bit_length()) + 1              # ceil(log2 n) + 1
         done = 0
         while done < n - 1:
             if self.rounds >= most:
                 raise RuntimeError(f'the tree of {n} proteins is not finished after {most} rounds')
-            for i0, tile, flags in (kept if kept is not None else ((i0, tile, flags) for i0, _, tile, flags in self.tiles(rows))):
+            for i0, tile, flags in held or self.tile_pass(rows, hold=held):
                 tri_nearest(tile, i0, i0 + 1, self.bound, ts, *flags)
                 del tile
             tree_hook(ts)
@@ -1348,13 +1350,11 @@ class Auc1(FilteredPairs):
         first = torch.full((n,), BEST_NONE, dtype=torch.int64, device=dev)
         tp = torch.zeros(n, dtype=torch.int32, device=dev)
         rows = self.device_rows() if self.route == 'domain' else None
-        held = [] if len(list(self.stripes())) == 1 else None
-        for i0, _, tile, flags in self.tiles(rows):
+        held = []
+        for i0, tile, flags in self.tile_pass(rows, hold=held):
             tri_first_fp(tile, i0, i0 + 1, self.bound, fam, first, *flags)
-            if held is not None:
-                held.append((i0, tile, flags))
             del tile
-        for i0, tile, flags in (held if held is not None else ((i0, tile, flags) for i0, _, tile, flags in self.tiles(rows))):
+        for i0, tile, flags in held or self.tile_pass(rows):
             tri_tp_before(tile, i0, i0 + 1, self.bound, fam, first, tp, *flags)
             del tile
         del held

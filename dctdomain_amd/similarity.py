@@ -634,26 +634,6 @@ def rect_best(tile: torch.Tensor, row0: int, col0: int, bound: int, state: BestS
         _launch(tile.device, 'dctfp_rect_best', *lead, state.best_row.data_ptr(), n_a, state.best_col.data_ptr(), n_b)
 
 
-def label_sums(tile: torch.Tensor, row0: int, col0: int, labels: torch.Tensor, sums: torch.Tensor, row_empty=None, col_empty=None,
-               cap: int = 17000):
-    """Adds key = min(L1, cap) -- ``cap`` for a row / column flagged empty -- of every entry (r, c) of an L1 tile of ONE file with
-    col0 + c > row0 + r and ``labels[row0 + r] == labels[col0 + c]`` to ``sums[row0 + r]`` and to ``sums[col0 + c]``
-    (``dctfp_label_sums``).  ``labels``: device int32, one per protein (``cluster_labels``); ``sums``: device int64 of the same
-    length (torch has no uint64 arithmetic; the sums stay far below 2^63), zeroed by the caller before the first tile.  After every
-    tile of the triangle ``sums[x]`` is the summed distance of x to the other members of its cluster; integer addition commutes, so
-    it does not depend on how the triangle is cut into tiles or on the order of the calls."""
-    for t, dtype, what in ((labels, torch.int32, 'labels'), (sums, torch.int64, 'sums')):
-        if t.dtype != dtype or t.dim() != 1 or not t.is_contiguous() or t.device != tile.device or t.numel() != labels.numel():
-            raise ValueError(f'{what} must be a contiguous 1-D {dtype} tensor on the device of the tile, one entry per protein')
-    n_nodes = labels.numel()
-    n_rows, n_cols, lead, _flags = _tri_filter_args(tile, row0, col0, cap, row_empty, col_empty, cap, n_nodes)
-    if n_rows and n_cols:
-        _launch(tile.device, 'dctfp_label_sums', *lead, labels.data_ptr(), sums.data_ptr(), n_nodes)
-
-
-NEAREST_NONE = 0x7fffffff                      # nearest: no core neighbour
-
-
 def _node_arrays(tile: torch.Tensor, arrays) -> int:
     """n_nodes of the per-protein arrays beside a tile -- ``arrays`` = (tensor, dtype, name): contiguous 1-D device tensors of one
     length on the tile's device."""
@@ -664,16 +644,38 @@ def _node_arrays(tile: torch.Tensor, arrays) -> int:
     return n_nodes
 
 
+def _band_pass(export: str, tile: torch.Tensor, row0: int, col0: int, bound: int, row_empty, col_empty, cap: int, arrays):
+    """What the passes over a tile of ONE file share: the per-protein ``arrays`` checked (``_node_arrays``), the tile described with
+    them as its nodes (``_tri_filter_args``), and ``export`` launched -- the tile, the arrays in their order, n_nodes -- unless the
+    tile is empty."""
+    n_nodes = _node_arrays(tile, arrays)
+    n_rows, n_cols, lead, _flags = _tri_filter_args(tile, row0, col0, bound, row_empty, col_empty, cap, n_nodes)
+    if n_rows and n_cols:
+        _launch(tile.device, export, *lead, *(t.data_ptr() for t, _dtype, _what in arrays), n_nodes)
+
+
+def label_sums(tile: torch.Tensor, row0: int, col0: int, labels: torch.Tensor, sums: torch.Tensor, row_empty=None, col_empty=None,
+               cap: int = 17000):
+    """Adds key = min(L1, cap) -- ``cap`` for a row / column flagged empty -- of every entry (r, c) of an L1 tile of ONE file with
+    col0 + c > row0 + r and ``labels[row0 + r] == labels[col0 + c]`` to ``sums[row0 + r]`` and to ``sums[col0 + c]``
+    (``dctfp_label_sums``).  ``labels``: device int32, one per protein (``cluster_labels``); ``sums``: device int64 of the same
+    length (torch has no uint64 arithmetic; the sums stay far below 2^63), zeroed by the caller before the first tile.  After every
+    tile of the triangle ``sums[x]`` is the summed distance of x to the other members of its cluster; integer addition commutes, so
+    it does not depend on how the triangle is cut into tiles or on the order of the calls."""
+    _band_pass('dctfp_label_sums', tile, row0, col0, cap, row_empty, col_empty, cap,
+                ((labels, torch.int32, 'labels'), (sums, torch.int64, 'sums')))
+
+
+NEAREST_NONE = 0x7fffffff                      # nearest: no core neighbour
+
+
 def tri_degree(tile: torch.Tensor, row0: int, col0: int, bound: int, deg: torch.Tensor, row_empty=None, col_empty=None, cap: int = 17000):
     """Adds 1 to ``deg[row0 + r]`` and to ``deg[col0 + c]`` for every entry (r, c) of an L1 tile of ONE file that ``tri_filter_count``
     would count: col0 + c > row0 + r and min(L1, cap) <= bound, ``cap`` for a row / column flagged empty (``dctfp_tri_degree``).
     ``deg``: device int32, one per protein (the library's uint32: a degree stays below 2^31), zeroed by the caller before the first
     tile.  After every tile of the triangle ``deg[x]`` is the number of pairs within the bound that x is in; a count does not depend
     on how the triangle is cut into tiles or on the order of the calls."""
-    n_nodes = _node_arrays(tile, ((deg, torch.int32, 'deg'),))
-    n_rows, n_cols, lead, _flags = _tri_filter_args(tile, row0, col0, bound, row_empty, col_empty, cap, n_nodes)
-    if n_rows and n_cols:
-        _launch(tile.device, 'dctfp_tri_degree', *lead, deg.data_ptr(), n_nodes)
+    _band_pass('dctfp_tri_degree', tile, row0, col0, bound, row_empty, col_empty, cap, ((deg, torch.int32, 'deg'),))
 
 
 def tri_link_core(tile: torch.Tensor, row0: int, col0: int, bound: int, core: torch.Tensor, parent: torch.Tensor, nearest: torch.Tensor,
@@ -683,10 +685,8 @@ def tri_link_core(tile: torch.Tensor, row0: int, col0: int, bound: int, core: to
     ``tri_link``; read with ``cluster_labels``), one with exactly one core end lowers ``nearest`` of the other end (device int32,
     ``NEAREST_NONE`` at the start) to the core's index, one without a core end does nothing.  After every tile ``nearest[x]`` of a
     non-core x is its lowest core neighbour; neither result depends on the tiling or on the order of the calls."""
-    n_nodes = _node_arrays(tile, ((core, torch.uint8, 'core'), (parent, torch.int32, 'parent'), (nearest, torch.int32, 'nearest')))
-    n_rows, n_cols, lead, _flags = _tri_filter_args(tile, row0, col0, bound, row_empty, col_empty, cap, n_nodes)
-    if n_rows and n_cols:
-        _launch(tile.device, 'dctfp_tri_link_core', *lead, core.data_ptr(), parent.data_ptr(), nearest.data_ptr(), n_nodes)
+    _band_pass('dctfp_tri_link_core', tile, row0, col0, bound, row_empty, col_empty, cap,
+                ((core, torch.uint8, 'core'), (parent, torch.int32, 'parent'), (nearest, torch.int32, 'nearest')))
 
 
 def tri_first_fp(tile: torch.Tensor, row0: int, col0: int, bound: int, fam: torch.Tensor, first: torch.Tensor, row_empty=None,
@@ -698,10 +698,8 @@ def tri_first_fp(tile: torch.Tensor, row0: int, col0: int, bound: int, fam: torc
     its words (torch has no uint64 arithmetic) and filled with ``BEST_NONE`` by the caller before the first tile.  After every tile
     of the triangle ``first[x]`` is the best-ranked hit of x from another family, ties to the lower index; a minimum does not
     depend on how the triangle is cut into tiles or on the order of the calls."""
-    n_nodes = _node_arrays(tile, ((fam, torch.int32, 'fam'), (first, torch.int64, 'first')))
-    n_rows, n_cols, lead, _flags = _tri_filter_args(tile, row0, col0, bound, row_empty, col_empty, cap, n_nodes)
-    if n_rows and n_cols:
-        _launch(tile.device, 'dctfp_tri_first_fp', *lead, fam.data_ptr(), first.data_ptr(), n_nodes)
+    _band_pass('dctfp_tri_first_fp', tile, row0, col0, bound, row_empty, col_empty, cap,
+                ((fam, torch.int32, 'fam'), (first, torch.int64, 'first')))
 
 
 def tri_tp_before(tile: torch.Tensor, row0: int, col0: int, bound: int, fam: torch.Tensor, first: torch.Tensor, tp: torch.Tensor,
@@ -712,10 +710,8 @@ def tri_tp_before(tile: torch.Tensor, row0: int, col0: int, bound: int, fam: tor
     ``tp``: device int32, one per protein (the library's uint32), zeroed by the caller before the first tile.  After every tile
     ``tp[x]`` is the number of hits of x's own family ranked before its first false positive; a count does not depend on the tiling
     or on the order of the calls."""
-    n_nodes = _node_arrays(tile, ((fam, torch.int32, 'fam'), (first, torch.int64, 'first'), (tp, torch.int32, 'tp')))
-    n_rows, n_cols, lead, _flags = _tri_filter_args(tile, row0, col0, bound, row_empty, col_empty, cap, n_nodes)
-    if n_rows and n_cols:
-        _launch(tile.device, 'dctfp_tri_tp_before', *lead, fam.data_ptr(), first.data_ptr(), tp.data_ptr(), n_nodes)
+    _band_pass('dctfp_tri_tp_before', tile, row0, col0, bound, row_empty, col_empty, cap,
+                ((fam, torch.int32, 'fam'), (first, torch.int64, 'first'), (tp, torch.int32, 'tp')))
 
 
 GREEDY_NONE = 0x7fffffff                       # assign: no representative yet

@@ -381,21 +381,30 @@ def _code(path):
 
 
 def test_the_unit_touches_its_arrays_through_agent_scope_atomics_alone():
-    unit = _code(os.path.join(ROOT, 'dctdomain_amd', 'csrc', 'k_auc.hip'))
-    assert '__hip_atomic_fetch_add(' in unit and '__hip_atomic_fetch_min(' in unit and '__hip_atomic_load(' in unit and 'asm' not in unit
-    assert unit.count('__ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT') == 3          # lower_hit's load and minimum, add_count
-    one = unit[unit.index('void tri_first_fp_kernel('):unit.index('void tri_tp_before_kernel(')]
-    two = unit[unit.index('void tri_tp_before_kernel('):unit.index('static_assert')]
-    # pass 1 never reads or writes first, and pass 2 never tp, but through the helpers; pass 2 reads first through _first_of alone
-    assert not re.search(r'\b(first|tp|fam)\s*\[', one + two)
-    assert len(re.findall(r'lower_hit\(first \+ ', one)) == 2 and len(re.findall(r'add_count\(tp \+ ', two)) == 2
-    assert not re.search(r'\bwhile\b|for \(;;\)', one + two)
-    # a job on or left of the diagonal is left before anything is loaded
+    csrc = os.path.join(ROOT, 'dctdomain_amd', 'csrc')
+    unit, walk = _code(os.path.join(csrc, 'k_auc.hip')), _code(os.path.join(csrc, 'band_walk.hip.h'))
+    assert '#include "band_walk.hip.h"' in unit and 'asm' not in unit and 'asm' not in walk
+    assert '__hip_atomic_fetch_add(' in unit and '__hip_atomic_fetch_min(' in walk and '__hip_atomic_load(' in walk
+    # add_count here; lower_hit's load and minimum in the walk's header, where lower_hit and hit_word are defined once
+    assert unit.count('__ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT') == 1 and walk.count('__ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT') == 2
+    assert 'void lower_hit(' in walk and 'hit_word(' in walk and 'void lower_hit(' not in unit and 'long hit_word(' not in unit
+    one = unit[unit.index('struct FirstFpPass'):unit.index('struct TpBeforePass')]
+    two = unit[unit.index('struct TpBeforePass'):unit.index('__global__')]
+    kernels = unit[unit.index('__global__'):unit.index('namespace dctfp_host')]
+    assert 'void tri_first_fp_kernel(const TriTile t, ' in kernels and 'band_walk(t, n_bands, n_steps, FirstFpPass{fam, first});' in kernels
+    assert 'void tri_tp_before_kernel(const TriTile t, ' in kernels and 'band_walk(t, n_bands, n_steps, TpBeforePass{fam, first, tp});' in kernels
     for body in (one, two):
-        assert body.index('continue;') < body.index('col_empty[') < body.index('_family(')
-    # fam and first: one plain load per column and job, one per row and job -- none in the loop over a row's entries
-    for body, helper, calls in ((one, '_family(', 2), (two, '_family(', 2), (two, '_first_of(', 2)):
-        at = [m.start() for m in re.finditer(re.escape(helper), body)]
-        rows = body.index('for (int rl = 0;')
-        entries = body.index('for (int e = 0;', rows)
-        assert len(at) == calls and at[0] < rows < at[1] < entries
+        assert 'kBounded = true' in body
+    # pass 1 never reads or writes first, and pass 2 never tp, but through the helpers, in the two flushes; pass 2 reads first through
+    # _first_of alone and both read fam through _family alone -- in side(), which the walk calls once per column and job and once per
+    # row and band (test_cluster_host.py checks the walk); wants() sees the two families before the entry is loaded
+    assert not re.search(r'\b(first|tp|fam)\s*\[', one + two + kernels)
+    assert len(re.findall(r'\b(first|tp|fam)\s*\[', unit)) == 2                 # (_family's and _first_of's)
+    assert len(re.findall(r'lower_hit\(first \+ ', one)) == 2 and len(re.findall(r'add_count\(tp \+ ', two)) == 2
+    for body, helper in ((one, r'lower_hit\(first \+ '), (two, r'add_count\(tp \+ ')):
+        assert re.search(r'void row_out\([^)]*\) const \{ ' + helper, body) and re.search(r'void col_out\([^)]*\) const \{ ' + helper, body)
+    assert not re.search(r'\bwhile\b|\bfor\b', one + two + kernels)
+    assert 'Side side(int64_t x) const { return _family(fam, x); }' in one and 'Side side(int64_t x) const { return {_family(fam, x), _first_of(first, x)}; }' in two
+    assert len(re.findall(r'_family\(', one)) == 1 and len(re.findall(r'_family\(', two)) == 1 and len(re.findall(r'_first_of\(', two)) == 1
+    assert 'wants(Side row_fam, Side col_fam) { return row_fam != col_fam; }' in one
+    assert 'wants(const Side& row, const Side& col) { return row.fam == col.fam; }' in two

@@ -323,7 +323,13 @@ def test_the_tile_description_is_defined_once_and_checked_in_one_place():
         with open(os.path.join(csrc, name)) as fh:
             code[name] = '\n'.join(line.split('//', 1)[0] for line in fh.read().splitlines())
     holders = [name for name, text in code.items() if re.search(r'\bstruct TriTile\s*\{', text)]
-    assert holders == ['tri_walk.hip.h'] and os.path.join(csrc, holders[0]) in build_ext.HEADERS
+    assert holders == ['tri_tile.hip.h'] and os.path.join(csrc, holders[0]) in build_ext.HEADERS
+    # ... a header that holds nothing else, and no unit restates it under another name
+    assert not re.search(r'__device__|__global__|\binline\b', code['tri_tile.hip.h'])
+    assert set(re.findall(r'\bstruct (\w+Tile)\s*\{', '\n'.join(code.values()))) == {'TriTile'}
+    for header in ('tri_walk.hip.h', 'band_walk.hip.h'):
+        assert '#include "tri_tile.hip.h"' in code[header] and os.path.join(csrc, header) in build_ext.HEADERS
+    assert 'struct TriTile;' in code['launch.h']
     kernels = {'k_filter.hip': ('tri_filter_count_kernel', 'tri_filter_fill_kernel'), 'k_cluster.hip': ('tri_link_kernel',),
                'k_greedy.hip': ('greedy_tri_mark_kernel',), 'k_tree.hip': ('tri_nearest_kernel',)}
     # (every unit that includes the header: sim_lines_kernel of k_search.hip has a row0 / col0 of its own and scans no such tile)
@@ -345,6 +351,90 @@ def test_the_tile_description_is_defined_once_and_checked_in_one_place():
     assert sum(bool(re.search(r'\bint32_t uf_find\(', text)) for text in code.values()) == 1 and 'uf_find(' in code['union_find.hip.h']
     for unit in ('k_cluster.hip', 'k_tree.hip'):
         assert '#include "union_find.hip.h"' in code[unit] and 'DCTFP_UNION_FIND_ONLY' not in code[unit]
+
+
+def test_the_band_walk_is_defined_once_and_five_kernels_are_passes_of_it():
+    """The five kernels that reduce a band of rows of a tile of a triangle onto per-protein arrays (label_sums, tri_degree,
+    tri_link_core, tri_first_fp, tri_tp_before) are passes of ONE function template, band_walk, in a header of its own.  rect_best_kernel
+    is exempt by name -- it keeps a loop of its own over the same TriTile, constants and grid, because it measured slower as a pass
+    (the reason is written at the kernel and in profiles/band_walk/README.md).  What makes the walk right is asserted here, once; what a
+    pass does with its arrays is asserted beside its unit (test_rbh_host.py, test_medoid_host.py, test_density_host.py,
+    test_auc1_host.py).  The five exports over a triangle check the tile with one function."""
+    import build_ext
+    csrc = os.path.join(ROOT, 'dctdomain_amd', 'csrc')
+    code = {}
+    for name in sorted(os.listdir(csrc)):
+        with open(os.path.join(csrc, name)) as fh:
+            code[name] = '\n'.join(line.split('//', 1)[0] for line in fh.read().splitlines())
+    walk = code['band_walk.hip.h']
+    assert os.path.join(csrc, 'band_walk.hip.h') in build_ext.HEADERS and os.path.join(csrc, 'band_walk.hip.h') in build_ext.kernel_sources()
+    kernels = {'k_best.hip': ('rect_best_kernel',), 'k_medoid.hip': ('label_sums_kernel',), 'k_density.hip': ('tri_degree_kernel', 'tri_link_core_kernel'),
+               'k_auc.hip': ('tri_first_fp_kernel', 'tri_tp_before_kernel')}
+    exempt = {'k_best.hip': 'rect_best_kernel'}     # (keeps a loop of its own: the reason is at the kernel and in profiles/band_walk/README.md)
+    assert sorted(kernels) == sorted(u for u in build_ext.UNITS if '#include "band_walk.hip.h"' in code[u])
+    for unit, names in kernels.items():
+        heads = re.sub(r'\s+', ' ', ' '.join(re.findall(r'__global__[^{]*\{', code[unit])))
+        assert not re.search(r'int64_t row0, int64_t col0', code[unit]), unit
+        on_walk = [k for k in names if k != exempt.get(unit)]
+        assert len(re.findall(r'__global__', code[unit])) == len(names) and code[unit].count('band_walk(t, n_bands, n_steps, ') == len(on_walk)
+        for kernel in names:
+            assert ' %s(const TriTile t, ' % kernel in heads and '__launch_bounds__(kBandThreads)' in heads, kernel
+        # a unit has no loop, no LDS and no constants of the walk of its own
+        assert unit in exempt or not re.search(r'\bfor\b|\bwhile\b|__shared__|__syncthreads|__ballot|__shfl|= 256|= 64\b', code[unit]), unit
+        assert code[unit].count('band_grid(t)') == len(names) and 'n_cols +' not in code[unit], unit
+    # the skeleton -- rows of a band, a word of s_row per (row, wave) -- occurs in one file
+    assert [name for name, text in code.items() if 's_row[tid >> 2][tid & 3]' in text] == ['band_walk.hip.h']
+    assert [name for name, text in code.items() if 'rows = (int)min((int64_t)kBandRows, t.n_rows - r_lo)' in text] == ['band_walk.hip.h'] + sorted(exempt)
+    for unit, kernel in exempt.items():
+        assert 'EXEMPT from band_walk by name' in open(os.path.join(csrc, unit)).read() and kernel in open(os.path.join(ROOT, 'profiles', 'band_walk', 'README.md')).read()
+    assert len(re.findall(r'template <class Pass>', walk)) == 1 and 'void band_walk(const TriTile& t, int64_t n_bands, int64_t n_steps, const Pass& pass)' in walk
+    for constant in ('kBandThreads = 256;', 'kBandWaves = kBandThreads / 64;', 'kBandPer = 4;', 'kBandStep = kBandThreads * kBandPer;', 'kBandRows = 64;'):
+        assert walk.count('constexpr int ' + constant) == 1, constant
+    assert walk.count('static_assert(') == 2 and 'kBandRows * kBandWaves == kBandThreads' in walk and 'kBandStep == 1 << 10 && kBandRows == 1 << 6' in walk
+    assert '(int64_t)1 << 20' in walk and "flagged || x >= cap ? cap : x" in walk
+    for name in ('lower_hit', 'hit_word', 'key_of', 'band_grid'):
+        assert sum(bool(re.search(r'\b%s\([^)]*\)\s*\{' % name, text)) for text in code.values()) == 1 and re.search(r'\b%s\([^)]*\)\s*\{' % name, walk), name
+    body = walk[walk.index('void band_walk('):]
+    # the tile's pointers are __restrict__ locals of the walk, not struct members read per access
+    for pointer in ('const int32_t* __restrict__ tile = t.tile;', 'const uint8_t* __restrict__ row_empty = t.row_empty;', 'const uint8_t* __restrict__ col_empty = t.col_empty;'):
+        assert pointer in body
+    assert not re.search(r't\.(tile|row_empty|col_empty)\b', body.split('const int32_t bound = t.bound;', 1)[1])
+    # a job of a triangle on or left of the diagonal is left before anything is loaded
+    assert body.index('if (j_lo + min((int64_t)kBandStep, t.n_cols - v0) - 1 <= i_lo) continue;') < body.index('col_empty[') < body.index('pass.side(')
+    # one job loop, gridDim.x apart, and no loop that waits; s_row is cleared between two barriers, the flush behind a third
+    assert 'for (int64_t job = blockIdx.x; job < n_bands * n_steps; job += gridDim.x) {' in body and not re.search(r'\bwhile\b|for \(;;\)', walk)
+    clear = body.index('s_row[tid >> 2][tid & 3] = Pass::kIdle;')
+    sync = [m.start() for m in re.finditer(r'__syncthreads\(\);', body)]
+    rows = body.index('for (int rl = 0; rl < rows; ++rl) {')
+    entries = body.index('for (int e = 0; e < kBandPer; ++e) {', rows)
+    flush = body.index('if (tid < rows) {')
+    assert len(sync) == 3 and sync[0] < clear < sync[1] < rows < entries < sync[2] < flush
+    # the side value: fetched in exactly two places -- per column before the row loop, per row inside it and outside the entry loop
+    side = [m.start() for m in re.finditer(r'pass\.side\(', body)]
+    assert len(side) == 2 and side[0] < sync[0] and rows < side[1] < entries
+    # the entry is loaded only after inside, the diagonal and the pass's predicate; the bound follows the key
+    wants, load, bound, entry = (body.index(x, entries) for x in ('!Pass::wants(row_side, col_side[e])) continue;', '(uint32_t)row[kBandThreads * e]',
+                                                                   'if (Pass::kBounded && (int32_t)key > bound) continue;', 'pass.entry('))
+    assert body.index('if (!inside[e] || j <= i || ', entries) < wants < load < bound < entry and len(re.findall(r'\brow\[', body)) == 1
+    # the early-out, the reduction in the wave, one LDS slot per wave
+    ballot, shuffle, slot = body.index('if (__ballot(mine != Pass::kIdle) == 0) continue;'), body.index('__shfl_xor('), body.index('if (lane == 0) s_row[rl][wave] = mine;')
+    assert entry < ballot < shuffle < slot < sync[2] and 'atomic' not in body
+    # the flush: an idle part is not sent, and the output arrays are touched through row_out / col_out alone -- the walk knows no array
+    assert body.index('if (part != Pass::kIdle) pass.row_out(i_lo + tid, j_lo, part);') > flush
+    assert body.index('if (col[e] != Pass::kIdle) pass.col_out(j_lo + tid + kBandThreads * e, i_lo, col[e]);') > flush
+    assert re.findall(r'pass\.(\w+)\(', body) == ['side', 'side', 'entry', 'row_out', 'col_out'] and set(re.findall(r'Pass::(\w+)', body)) == {
+        'Word', 'Side', 'kBounded', 'kIdle', 'wants', 'join'}
+    # the exports: one check for the five over a triangle, the rectangle keeps its own conditions; check_tri_tile's users are as they were
+    host = code['dctfp.hip']
+    exports = ('dctfp_label_sums', 'dctfp_tri_degree', 'dctfp_tri_link_core', 'dctfp_tri_first_fp', 'dctfp_tri_tp_before')
+    assert host.count('check_band_tile(') == 1 + len(exports) and 'static int check_band_tile(const char* name, const TriTile& t, int64_t n_nodes)' in host
+    assert 'density_tile_ok' not in host and sum('check_band_tile(' in text for text in code.values()) == 1
+    for name in exports + ('dctfp_rect_best',):
+        body = host[host.index('\nint %s(' % name):host.index('DCTFP_GUARD("%s")' % name)]
+        assert body.count('check_band_tile("%s", t, n_nodes)' % name) == (name != 'dctfp_rect_best') and 'check_tri_tile(' not in body, name
+        assert ('ld < n_cols' in body) == (name == 'dctfp_rect_best') and 'TriTile' in body, name
+        launch = re.search(r'void launch_%s\(([^)]*)\);' % name[len('dctfp_'):], code['launch.h']).group(1)
+        assert launch.startswith('const TriTile& t, ') and 'n_rows' not in launch, name
 
 
 def test_the_sad_tile_is_defined_once_in_a_header_every_user_includes():

@@ -253,21 +253,25 @@ def test_the_exports_are_declared_bound_and_built():
 def test_the_unit_touches_its_arrays_through_agent_scope_atomics_alone():
     unit = _code(os.path.join(ROOT, 'dctdomain_amd', 'csrc', 'k_density.hip'))
     assert '__hip_atomic_fetch_add(' in unit and '__hip_atomic_fetch_min(' in unit and '__HIP_MEMORY_SCOPE_AGENT' in unit
-    assert '#include "union_find.hip.h"' in unit and 'uf_union(parent, ' in unit and 'asm' not in unit
+    assert '#include "union_find.hip.h"' in unit and '#include "band_walk.hip.h"' in unit and 'uf_union(parent, ' in unit and 'asm' not in unit
     assert unit.count('__ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT') == 2          # add_degree and lower_nearest; the forest has its own
-    degree = unit[unit.index('void tri_degree_kernel('):unit.index('void tri_link_core_kernel(')]
-    link = unit[unit.index('void tri_link_core_kernel('):unit.index('static_assert')]
-    # no plain load or store of deg, nearest or parent, and no loop that waits
-    assert not re.search(r'\b(deg|nearest|parent)\s*\[', degree + link)
-    assert len(re.findall(r'add_degree\(deg \+ ', degree)) == 2 and len(re.findall(r'lower_nearest\(nearest \+ ', link)) == 2
-    assert not re.search(r'\bwhile\b|for \(;;\)', degree + link)
-    # a job on or left of the diagonal is left before anything is loaded
+    degree = unit[unit.index('struct DegreePass'):unit.index('struct LinkCorePass')]
+    link = unit[unit.index('struct LinkCorePass'):unit.index('__global__')]
+    kernels = unit[unit.index('__global__'):unit.index('namespace dctfp_host')]
+    # two passes of the one band walk over a triangle with a bound
+    assert 'void tri_degree_kernel(const TriTile t, ' in kernels and 'band_walk(t, n_bands, n_steps, DegreePass{deg});' in kernels
+    assert 'void tri_link_core_kernel(const TriTile t, ' in kernels and 'band_walk(t, n_bands, n_steps, LinkCorePass{core, parent, nearest});' in kernels
     for body in (degree, link):
-        assert body.index('continue;') < body.index('col_empty[')
-    # core: one plain load per column and job, one per row and job -- none in the loop over a row's entries
+        assert 'kBounded = true' in body
+    # no plain load or store of deg, nearest or parent -- only ever offset and handed to the helpers, in the two flushes -- and no loop at all
+    assert not re.search(r'\b(deg|nearest|parent)\s*\[', unit)
+    assert len(re.findall(r'add_degree\(deg \+ ', degree)) == 2 and len(re.findall(r'lower_nearest\(nearest \+ ', link)) == 2
+    for body, helper in ((degree, r'add_degree\(deg \+ '), (link, r'lower_nearest\(nearest \+ ')):
+        assert re.search(r'void row_out\([^)]*\) const \{ ' + helper, body) and re.search(r'void col_out\([^)]*\) const \{ ' + helper, body)
+    assert not re.search(r'\bwhile\b|\bfor\b', degree + link + kernels)
+    # core: read in _is_core alone, which the pass's side() calls -- the walk takes a side value once per column and job and once per
+    # row and band (test_cluster_host.py checks the walk) -- and wants() sees the two flags before the entry is loaded
     assert '_is_core(const uint8_t* __restrict__ core, int64_t x)' in unit
-    calls = [m.start() for m in re.finditer(r'_is_core\(', link)]
-    rows = link.index('for (int rl = 0;')
-    entries = link.index('for (int e = 0;', rows)
-    assert len(calls) == 2 and calls[0] < rows < calls[1] < entries
-    assert not re.search(r'\bcore\s*\[', degree + link)
+    assert len(re.findall(r'_is_core\(', link)) == 1 and 'Side side(int64_t x) const { return _is_core(core, x); }' in link
+    assert 'bool wants(Side row_core, Side col_core) { return row_core || col_core; }' in link
+    assert len(re.findall(r'\bcore\s*\[', unit)) == 1 and not re.search(r'\bcore\s*\[', degree + link + kernels)

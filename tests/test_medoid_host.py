@@ -213,14 +213,25 @@ def test_the_export_is_declared_bound_and_built():
     csrc = os.path.join(ROOT, 'dctdomain_amd', 'csrc')
     with open(os.path.join(csrc, 'k_medoid.hip')) as fh:
         unit = fh.read()
-    assert 'label_sums_kernel(' in unit and '__hip_atomic_fetch_add(' in unit and '__HIP_MEMORY_SCOPE_AGENT' in unit
-    assert '#include "tri_walk.hip.h"' not in unit and 'asm' not in re.sub(r'//.*', '', unit)
+    assert 'label_sums_kernel(const TriTile t, ' in unit and '__hip_atomic_fetch_add(' in unit and '__HIP_MEMORY_SCOPE_AGENT' in unit
+    assert '#include "tri_walk.hip.h"' not in unit and '#include "band_walk.hip.h"' in unit
+    code = '\n'.join(line.split('//', 1)[0] for line in unit.splitlines())
+    assert 'asm' not in code and code.count('__ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT') == 1     # add_sum
+    # a pass of the one band walk, with no bound; sums is only ever offset and handed to add_sum, in the pass's two flushes, and
+    # labels is read in _label alone, which the pass's side() calls
+    assert 'band_walk(t, n_bands, n_steps, LabelSumsPass{labels, sums});' in code and 'kBounded = false' in code
+    assert not re.search(r'\bsums\s*\[', code) and len(re.findall(r'add_sum\(sums \+ ', code)) == 2
+    assert re.search(r'void row_out\([^)]*\) const \{ add_sum\(sums \+ ', code) and re.search(r'void col_out\([^)]*\) const \{ add_sum\(sums \+ ', code)
+    assert re.findall(r'[^\n]*\blabels\s*\[[^\n]*', code) == ['__device__ inline int32_t _label(const int32_t* __restrict__ labels, int64_t x) { return labels[x]; }']
+    assert len(re.findall(r'_label\(', code)) == 2 and 'Side side(int64_t x) const { return _label(labels, x); }' in code
+    assert not re.search(r'\bwhile\b|for \(;;\)', code)
     with open(os.path.join(csrc, 'launch.h')) as fh:
         assert 'void launch_label_sums(' in fh.read()
     with open(os.path.join(csrc, 'dctfp.hip')) as fh:
         host = fh.read()
     body = host[host.index('\nint dctfp_label_sums('):host.index('DCTFP_GUARD("dctfp_label_sums")')]
     assert 'check_tri_tile(' not in body and 'label_sums_max_cap()' in body
+    assert body.count('check_band_tile("dctfp_label_sums", t, n_nodes)') == 1 and 'cap, cap};' in body     # (no cut-off: the tile's bound is its cap)
     with open(os.path.join(ROOT, 'INTEGRATION.md')) as fh:
         assert 'dctfp_label_sums' in fh.read()
     import ctypes

@@ -177,20 +177,33 @@ def test_new_unit_is_part_of_the_build_and_touches_the_arrays_through_atomics_on
     csrc = os.path.join(ROOT, 'dctdomain_amd', 'csrc')
     text = open(os.path.join(csrc, 'k_best.hip')).read()
     code = '\n'.join(line.split('//', 1)[0] for line in text.splitlines())
-    assert '__HIP_MEMORY_SCOPE_AGENT' in text and 'asm' not in code and '__builtin_amdgcn_sad_u8' not in text
+    walk = '\n'.join(line.split('//', 1)[0] for line in open(os.path.join(csrc, 'band_walk.hip.h')).read().splitlines())
+    # the kernel is exempt from the one band walk by name (the reason is written at it and in profiles/band_walk/README.md): it keeps
+    # its loop, over the TriTile, with the walk's constants, grid and key rule; its atomics are lower_hit's, defined in the walk's
+    # header alone
+    assert '#include "band_walk.hip.h"' in text and 'void lower_hit(' in walk and 'void lower_hit(' not in code
+    assert 'EXEMPT from band_walk by name' in text and 'profiles/band_walk/README.md' in text and 'band_walk(' not in code
+    assert 'rect_best_kernel' in open(os.path.join(ROOT, 'profiles', 'band_walk', 'README.md')).read()
+    assert '__HIP_MEMORY_SCOPE_AGENT' in walk and 'asm' not in code and 'asm' not in walk and '__builtin_amdgcn_sad_u8' not in text + walk
+    assert code.count('__ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT') == 0        # (no atomic of its own on the arrays: lower_hit's two)
     assert not re.search(r'#include\s+"(tri_walk|union_find|sad_tile)\.hip\.h"', text) and not re.search(r'#include\s+"[^"]*\.hip"', text)
     kernel = code[code.index('void rect_best_kernel'):code.index('namespace dctfp_host')]
-    lower = code[code.index('void lower_hit'):code.index('void rect_best_kernel')]
+    assert 'void rect_best_kernel(const TriTile t, ' in kernel and not re.search(r'\b(256|1024|64)\b', kernel.replace('& 63', ''))
+    assert 'key_of(' in kernel and 'band_grid(t)' in code and 'n_cols +' not in code
+    lower = walk[walk.index('void lower_hit'):walk.index('template <class Pass>')]
     # no plain load or store of the two arrays: they are only ever offset and handed to lower_hit
     assert not re.search(r'\bbest_(row|col)\s*\[', code) and not re.search(r'\*\s*\(?\s*best_(row|col)\b', kernel.split(')', 1)[1])
     assert kernel.count('lower_hit(best_row + ') == 1 and kernel.count('lower_hit(best_col + ') == 1
     uses = re.findall(r'[^\n]*\bslot\b[^\n]*', lower.split('{', 1)[1])
     assert len(uses) == 2 and all('__hip_atomic_' in u and '__ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT' in u for u in uses)
     assert '__hip_atomic_fetch_min(slot' in lower
-    assert not re.search(r'\bwhile\b|\bfor \(;;\)', kernel)     # (no spin loop)
+    assert not re.search(r'\bwhile\b|\bfor \(;;\)', kernel + walk)     # (no spin loop)
+    # s_row is cleared between two barriers and the flush stands behind a third
+    sync = [m.start() for m in re.finditer(r'__syncthreads\(\);', kernel)]
+    assert len(sync) == 3 and sync[0] < kernel.index('s_row[tid] = kNone32;') < sync[1] < kernel.index('for (int rl = 0;') < sync[2] < kernel.index('lower_hit(best_row + ')
     host = open(os.path.join(csrc, 'dctfp.hip')).read()
     body = host[host.index('\nint dctfp_rect_best('):host.index('DCTFP_GUARD("dctfp_rect_best")')]
-    for check in ('ld < n_cols', 'row0 + n_rows > n_a', 'col0 + n_cols > n_b', '0x7fffffff', 'rect_best_max_cap()'):
+    for check in ('ld < n_cols', 'row0 + n_rows > n_a', 'col0 + n_cols > n_b', '0x7fffffff', 'rect_best_max_cap()', 'launch_rect_best(TriTile{'):
         assert check in body, check
 
 
