@@ -3087,6 +3087,32 @@ int dctfp_tri_tp_before(dctfp_ctx* ctx, const int32_t* tile, int64_t n_rows, int
     return DCTFP_OK;
 } DCTFP_GUARD("dctfp_tri_tp_before")
 
+// dct-sim --hist (k_hist.hip)
+int dctfp_tri_hist(dctfp_ctx* ctx, const int32_t* tile, int64_t n_rows, int64_t n_cols, int64_t ld, int64_t row0, int64_t col0,
+                   const uint8_t* row_empty, const uint8_t* col_empty, int32_t cap, int32_t bound, const int32_t* fam, int64_t n_nodes,
+                   uint64_t* hist, void* stream_v) try {
+    if (!ctx || !tile || !hist) return fail(DCTFP_ERR_INVALID, "dctfp_tri_hist: NULL argument");
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    // (one array for the whole grid, not an array per protein: its own few conditions)
+    if (n_rows < 0 || n_cols < 0 || ld < n_cols || row0 < 0 || col0 < 0 || cap < 0 || bound < -1 || bound > cap)
+        return fail(DCTFP_ERR_INVALID, "dctfp_tri_hist: bad shape, cap or bound");
+    if (((reinterpret_cast<uintptr_t>(tile) | reinterpret_cast<uintptr_t>(fam)) & 3u) != 0 || (reinterpret_cast<uintptr_t>(hist) & 7u) != 0)
+        return fail(DCTFP_ERR_INVALID, "dctfp_tri_hist: the tile or fam is not 4-byte aligned or hist not 8-byte aligned");
+    if (cap > tri_hist_max_cap())
+        return fail(DCTFP_ERR_INVALID, "dctfp_tri_hist: a cap above %d does not fit the counters of two classes in the LDS of a CU", tri_hist_max_cap());
+    if (n_nodes < 0 || n_nodes > 0x7fffffff) return fail(DCTFP_ERR_INVALID, "dctfp_tri_hist: n_nodes must lie in 0 .. 2^31 - 1");
+    // (every index the kernel can form lies inside the tile and fam: bounded here, on the host, and not on the device)
+    if (n_rows > n_nodes || row0 > n_nodes - n_rows || n_cols > n_nodes || col0 > n_nodes - n_cols)
+        return fail(DCTFP_ERR_INVALID, "dctfp_tri_hist: the tile names proteins outside fam");
+    if (n_rows == 0 || n_cols == 0) return DCTFP_OK;
+    HIP_TRY(hipSetDevice(ctx->device));
+    LaunchError le;
+    RC_TRY(launcher_rc(launch_tri_hist(TriTile{tile, n_rows, n_cols, ld, row0, col0, row_empty, col_empty, cap, bound}, fam, hist,
+                                       (hipStream_t)stream_v, &le), le));
+    HIP_TRY(hipGetLastError());
+    return DCTFP_OK;
+} DCTFP_GUARD("dctfp_tri_hist")
+
 int dctfp_greedy_decide(dctfp_ctx* ctx, int32_t* assign, int32_t* state, const int32_t* blocked, int64_t n_nodes, int64_t i0, int64_t i1,
                         int32_t round, int64_t* undecided, void* stream_v) try {
     if (!ctx || !assign || !state || !blocked || !undecided) return fail(DCTFP_ERR_INVALID, "dctfp_greedy_decide: NULL argument");

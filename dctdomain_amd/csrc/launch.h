@@ -212,6 +212,13 @@ void launch_tri_link_core(const TriTile& t, const uint8_t* core, int32_t* parent
 void launch_tri_first_fp(const TriTile& t, const int32_t* fam, uint64_t* first, hipStream_t stream);
 void launch_tri_tp_before(const TriTile& t, const int32_t* fam, const uint64_t* first, uint32_t* tp, hipStream_t stream);
 
+// the score distribution of a file (k_hist.hip): a loop of its own over an int32 L1 tile of one file -- every entry tri_degree would
+// count adds 1 to hist[cls * (cap + 1) + key], cls = 0 without fam, else fam[i] != fam[j].  32-bit counters private to the workgroup
+// in LDS over all its jobs, then one agent-scope 64-bit atomic add per non-zero bin; tri_hist_max_cap = the largest cap whose two
+// class rows fit the LDS of a CU.  A tile of more jobs than the counters of a launch can hold goes out as several launches
+int tri_hist_max_cap();
+int launch_tri_hist(const TriTile& t, const int32_t* fam, uint64_t* hist, hipStream_t stream, LaunchError* err);
+
 // (dctfp_rows_assign, k_assign.hip: the same contraction over a full rectangle -- every pair of rows within the bound lowers
 // assign[slot of the b row] to the value of the a row with an atomic minimum; value_a / slot_b NULL: a0 + r / b0 + c)
 void launch_rows_assign(const int8_t* a, int64_t na, int64_t lda, const int32_t* value_a, int64_t a0, const int8_t* b, int64_t nb, int64_t ldb,

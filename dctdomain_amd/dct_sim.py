@@ -15,6 +15,8 @@ fingerprints (``-dct.npz``), with the L1 distances computed on the GPU.
                                     [--dom A.dom] [--db-dom B.dom] [--output F]
     python -m dctdomain_amd.dct_sim --dct X-dct.npz --auc1 [domain|global] (--families FILE | --family-sep C)
                                     [--min-domain X | --min-global Y] [--output F]
+    python -m dctdomain_amd.dct_sim --dct X-dct.npz --hist [domain|global] [--bins B] [--families FILE | --family-sep C]
+                                    [--min-domain X | --min-global Y] [--output F]
 
 Same flags, same output text (src/dct-sim.py:179-211); ``--rank domain`` (not in the reference) orders database hits by
 DCTdomain instead of DCTglobal, and ``--min-domain`` / ``--min-global`` (not in the reference either, which ignores
@@ -80,6 +82,13 @@ Where the reference loops over protein pairs and, inside, over domain pairs in P
   rate.  Two scans over the same tiles with a family per protein on the device -- the first false positive of every protein as
   an atomic minimum of ``key << 32 | index`` (``dctfp_tri_first_fp``), then the true positives ranked before it
   (``dctfp_tri_tp_before``) -- and 12 bytes per protein come back; no ranked list is ever printed or parsed;
+- ``--hist`` (``Histogram``) helps to choose the cut-off that every mode above asks for: the distribution of one score over all
+  pairs of the file and, per cut-off of ``--bins``, how many pairs ``--min-domain`` / ``--min-global`` at that cut-off would keep;
+  with a family per protein (``--families`` / ``--family-sep``) the pairs of one family and of two apart, so recall, precision and
+  false-positive rate per cut-off, the ROC AUC and the cut-off of the best F1 -- what the reference's bench/G6PD/hist.py and
+  bench/homo/results/AUC.py compute from the printed all-against-all.  One scan over the same tiles bins every pair's key on the
+  device (``dctfp_tri_hist``: counters in LDS per workgroup, 64-bit atomic adds of the non-zero bins) and 8 bytes per bin and class
+  come back, whatever the size of the file; the similarity-0 bin follows from the totals on the host;
 - ``--cluster --level domain`` (``DomainClusters``) clusters the fingerprint ROWS of the file instead of its proteins -- the
   domain families: two rows of different proteins are joined when their own L1 passes ``--min-domain``, where the protein level
   joins two proteins as soon as any one of their fingerprint pairs does.  One kernel (``dctfp_rows_link``) takes a stripe of
@@ -122,7 +131,7 @@ from .similarity import (GREEDY_NONE, PROTEIN_MIN_MAX_D, GreedyState, LineIds, T
                          greedy_decide, greedy_pairs_mark, greedy_tri_mark, l1_matrix, link_pairs, pair_argmin, pair_argmin_device, pair_line_offsets, pair_lines, pair_min, pair_min_device, protein_cover, protein_min,
                          rows_assign, rows_link, sim_lines, threshold_select, to_device_int8, tri_filter_count, tri_filter_fill, tri_link,
                          TREE_MAX_NODES, TreeState, tree_hook, tri_nearest, BestState, rect_best, label_sums, NEAREST_NONE, tri_degree,
-                         tri_link_core, BEST_NONE, tri_first_fp, tri_tp_before)
+                         tri_link_core, BEST_NONE, tri_first_fp, tri_tp_before, tri_hist)
 
 L1_FULL_SCALE = 17000      # src/dct-sim.py:24
 HEADER = '#prot1 prot2 sim-domain sim-global'
@@ -1378,6 +1387,189 @@ class Auc1(FilteredPairs):
             sink(memoryview(text))
 
 
+HIST_BINS = 100            # --bins: the cut-offs of a --hist table
+HIST_MAX_BINS = 1000
+
+
+def hist_header(score: str, families: bool) -> str:
+    """The header of a ``--hist`` report."""
+    return f'#min-{score} same other kept-same kept-other recall precision fpr' if families else f'#min-{score} pairs kept'
+
+
+def hist_cuts(bins: int):
+    """(texts, bounds) of the ``bins`` cut-offs of a ``--hist`` table, highest first: cut-off b is the text
+    ``'%.4f' % ((bins - 1 - b) / bins)`` -- what a user types behind ``--min-domain`` -- and its bound is ``sim_bound`` of that text
+    read back as a float, not the arithmetic edge (b + 1) x 17000 / bins, which is off by one at a fifth of the edges of 100 bins.
+    The last text is ``0.0000``, whose bound is 17000: every pair."""
+    texts = ['%.4f' % ((bins - 1 - b) / bins) for b in range(bins)]
+    sims = _sim(np.arange(L1_FULL_SCALE + 1))                       # (sim_bound's expression, evaluated once for all texts)
+    return texts, [int(np.count_nonzero(~(sims < float(t)))) - 1 for t in texts]
+
+
+def hist_roc_auc(hist, rest):
+    """The ROC AUC of the key as a classifier of (same family, other family) from the two rows of counts: the Mann-Whitney statistic
+    with ties counted half, sum_k same[k] (2 (other pairs of a larger key) + other[k]) / (2 same other), the pairs of ``rest`` as one
+    more bin behind the last -- they tie at the bottom.  Python integers, divided once; None when either class is empty.  What
+    ``sklearn.metrics.roc_curve`` + ``auc`` give on the same scores."""
+    same = [int(v) for v in hist[0]] + [int(rest[0])]
+    other = [int(v) for v in hist[1]] + [int(rest[1])]
+    n_same, n_other = sum(same), sum(other)
+    if n_same == 0 or n_other == 0:
+        return None
+    above, total = n_other, 0
+    for s, o in zip(same, other):
+        above -= o
+        total += s * (2 * above + o)
+    return total / (2 * n_same * n_other)
+
+
+def hist_best_f1(hist, rest):
+    """(best F1, its bound) over the integer bounds 0 .. len - 1 of the two rows of counts: F1 of "keep the pairs of key <= b" as a
+    call of "same family" = 2 kept_same / (kept_same + kept_other + same).  Compared as fractions of Python integers; ties to the
+    lowest bound.  (None, None) without a pair of one family or without a bound."""
+    n_same = int(sum(int(v) for v in hist[0])) + int(rest[0])
+    if n_same == 0 or len(hist[0]) == 0:
+        return None, None
+    best_num, best_den, best_b, ks, ko = -1, 1, None, 0, 0
+    for b, (s, o) in enumerate(zip(hist[0], hist[1])):
+        ks, ko = ks + int(s), ko + int(o)
+        num, den = 2 * ks, ks + ko + n_same
+        if num * best_den > best_num * den:
+            best_num, best_den, best_b = num, den, b
+    return best_num / best_den, best_b
+
+
+def _rate(num: int, den: int) -> str:
+    return '%.4f' % (num / den) if den else '-'
+
+
+class Histogram(FilteredPairs):
+    """The distribution of one score over all pairs of a file (``--hist``), and with a family per protein what every cut-off would
+    keep of the pairs of one family and of the pairs of two: the number that chooses the cut-off of every clustering mode.  The
+    reference draws the one from the printed all-against-all (bench/G6PD/hist.py) and takes the ROC AUC of labelled pairs from it
+    (bench/homo/results/AUC.py); here no pair is printed.  L1 is DCTdomain's (``score='domain'``: ``protein_min``) or DCTglobal's
+    (``'global'``: ``l1_matrix`` of the last rows, the proteins without fingerprints flagged as on ``Tree``'s global route);
+    bound = 16999, every pair of similarity above 0, unless ``min_cut`` gives a lower ``sim_bound(min_cut)``.  ``families``: one
+    label per protein, of any hashable kind, or None.
+
+    One pass over ``FilteredPairs.tile_pass``: ``tri_hist`` adds every entry right of the diagonal with key = min(L1, 17000) <= bound
+    to ``hist[cls, key]`` on the device, cls = 0 without families, else (family of i != family of j).  No tile is held; ``hist``
+    stays on the device and its bins 0 .. bound come back once -- 8 bytes per bin and class, whatever the size of the file.  The
+    bin of similarity 0, where nearly all pairs of a large file land, is never counted on the device: the pairs above the bound
+    (``rest``) follow from the totals the host knows, n (n - 1) / 2 pairs and sum s (s - 1) / 2 of one family over the family sizes
+    s.  Fewer than two proteins or a bound below 0: no tile is filled and no kernel launched."""
+
+    def __init__(self, sid, idx, fps, families=None, score: str = 'domain', min_cut=None):
+        if score not in SCORES:
+            raise ValueError(f'score must be one of {SCORES}')
+        super().__init__(sid, idx, fps)
+        bound = L1_FULL_SCALE - 1 if min_cut is None else min(sim_bound(min_cut), L1_FULL_SCALE - 1)
+        self.score = self.route = score                         # (the tile of that score whatever the bound)
+        self.min_cut = min_cut
+        if score == 'domain':
+            self.bound_domain = bound
+        else:
+            self.bound_global = bound
+        self.fam = self.families = None
+        if families is not None:
+            self.fam, self.families = dense_families(families)
+            if len(self.fam) != len(self.idx) - 1:
+                raise ValueError('families must have one entry per protein')
+        self._counts = None
+
+    def totals(self):
+        """The pairs of every class as Python integers: (n (n - 1) / 2,) without families, else (same, other)."""
+        n = max(len(self.idx) - 1, 0)
+        pairs = n * (n - 1) // 2
+        if self.fam is None:
+            return (pairs,)
+        same = sum(int(s) * (int(s) - 1) // 2 for s in np.bincount(self.fam))
+        return same, pairs - same
+
+    def counts(self):
+        """(hist, rest): ``hist`` uint64 (classes, bound + 1), the pairs of every key 0 .. bound -- one row without families, else the
+        pairs of one family and the pairs of two --, and ``rest`` uint64 (classes), the pairs above the bound: similarity 0, no
+        fingerprint, or below the cut-off.  Computed once."""
+        if self._counts is None:
+            hist = self._scan()
+            rest = [t - int(hist[c].sum()) for c, t in enumerate(self.totals())]
+            self._counts = hist, np.asarray(rest, dtype=np.uint64)
+        return self._counts
+
+    def _scan(self):
+        n = len(self.idx) - 1
+        classes = 1 if self.fam is None else 2
+        if n < 2 or self.bound < 0:
+            return np.zeros((classes, max(self.bound + 1, 0)), dtype=np.uint64)
+        import torch
+        dev = torch.device('cuda', torch.cuda.current_device())
+        fam = torch.as_tensor(self.fam, device=dev) if self.fam is not None else None
+        hist = torch.zeros((classes, L1_FULL_SCALE + 1), dtype=torch.int64, device=dev)
+        rows = self.device_rows() if self.route == 'domain' else None
+        for i0, tile, flags in self.tile_pass(rows):
+            tri_hist(tile, i0, i0 + 1, self.bound, hist, fam, *flags)
+            del tile
+        return hist[:, :self.bound + 1].cpu().numpy().astype(np.uint64)     # one copy of 8 bytes per bin and class
+
+    def table(self, bins: int = HIST_BINS):
+        """(texts, kept): the cut-offs of ``hist_cuts(bins)`` that are not below ``min_cut`` -- the last, ``0.0000``, always -- and
+        ``kept`` int64 (lines, classes), the pairs whose score is not below each: exactly the lines ``dct-sim --min-<score> <text>``
+        prints.  A cut-off's bound is clipped to the instance's; the last keeps every pair."""
+        hist, _rest = self.counts()
+        below = np.concatenate([np.zeros((hist.shape[0], 1), dtype=np.int64), np.cumsum(hist.astype(np.int64), axis=1)], axis=1)
+        texts, kept = [], []
+        for b, (text, edge) in enumerate(zip(*hist_cuts(bins))):
+            if b == bins - 1:
+                kept.append(list(self.totals()))
+            elif self.min_cut is not None and float(text) < self.min_cut:
+                continue
+            else:
+                kept.append([int(v) for v in below[:, min(edge, self.bound) + 1]])
+            texts.append(text)
+        return texts, np.asarray(kept, dtype=np.int64).reshape(len(texts), hist.shape[0])
+
+    def summary(self) -> dict:
+        """From the counts at full resolution: ``pairs``; without families ``scored``, the pairs within the bound; with them
+        ``same``, ``other``, ``roc_auc`` (``hist_roc_auc``), ``best_f1`` and ``at`` (``hist_best_f1``): ``at`` is the text
+        ``'%.6f' % (1 - (b + 0.5) / 17000)``, halfway between two representable similarities, so ``sim_bound(float(at)) == b``
+        whatever the rounding and ``--min-<score> <at>`` reproduces the best-F1 set (None without a bound)."""
+        hist, rest = self.counts()
+        totals = self.totals()
+        if self.fam is None:
+            return {'pairs': totals[0], 'scored': int(hist[0].sum())}
+        f1, b = hist_best_f1(hist, rest)
+        return {'pairs': sum(totals), 'same': totals[0], 'other': totals[1], 'roc_auc': hist_roc_auc(hist, rest), 'best_f1': f1,
+                'at': None if b is None else '%.6f' % (1 - (b + 0.5) / L1_FULL_SCALE)}
+
+    def lines(self, bins: int = HIST_BINS) -> list:
+        """The text of ``--hist`` without its header: per cut-off of ``table(bins)`` one line -- ``cut-off pairs kept``, or with
+        families ``cut-off same other kept-same kept-other recall precision fpr``, ``pairs`` / ``same`` / ``other`` being the
+        pairs between this cut-off and the one before, the rates as ``%.4f`` and ``-`` where a denominator is 0 -- then the summary
+        line ``# pairs=.. scored=..`` or ``# pairs=.. same=.. other=.. roc_auc=.. best_f1=.. at=..``."""
+        texts, kept = self.table(bins)
+        totals = self.totals()
+        out, before = [], [0] * len(totals)
+        for text, row in zip(texts, kept.tolist()):
+            step = [k - p for k, p in zip(row, before)]
+            if self.fam is None:
+                out.append(f'{text} {step[0]} {row[0]}')
+            else:
+                out.append(f'{text} {step[0]} {step[1]} {row[0]} {row[1]} {_rate(row[0], totals[0])} {_rate(row[0], row[0] + row[1])} '
+                           f'{_rate(row[1], totals[1])}')
+            before = row
+        s = self.summary()
+        if self.fam is None:
+            out.append(f'# pairs={s["pairs"]} scored={s["scored"]}')
+        else:
+            auc, f1 = ('%.4f' % s[k] if s[k] is not None else '-' for k in ('roc_auc', 'best_f1'))
+            out.append(f'# pairs={s["pairs"]} same={s["same"]} other={s["other"]} roc_auc={auc} best_f1={f1} at={s["at"] or "-"}')
+        return out
+
+    def write(self, sink, bins: int = HIST_BINS):
+        """Calls ``sink(memoryview)`` with the text (``lines``), once."""
+        sink(memoryview(('\n'.join(self.lines(bins)) + '\n').encode('ascii')))
+
+
 def domain_cluster_lines(sid, idx, labels, row_labels, chunk_bytes: int = 1 << 24):
     """The text of ``--cluster --level domain`` for given labels (``labels[r]`` = the representative row of fingerprint row r, -1
     for a row that is no node and prints nothing), as uint8 arrays of whole lines of about ``chunk_bytes`` each: one line
@@ -2278,6 +2470,27 @@ def auc1_sim(npzfile: str, report: Report, score: str = 'domain', families: str 
     Auc1(sid, idx, fps, labels, score=score, min_cut=min_cut).write(report.raw)
 
 
+def hist_sim(npzfile: str, report: Report, score: str = 'domain', bins: int = HIST_BINS, families: str = None, family_sep: str = None,
+             min_domain: float = None, min_global: float = None):
+    """The distribution of DCTdomain (``score='domain'``) or DCTglobal (``'global'``) over all pairs of the file (``Histogram``): a
+    header, one line per cut-off of the ``bins`` (1 .. 1000) and a summary line (``Histogram.lines``).  The families, if any, come
+    from ``families`` (a file of ``id family`` lines: ``read_families``) or from the ids themselves (``family_sep``:
+    ``families_from_ids``) -- at most one of the two; with them the pairs of one family and of two are counted apart.
+    ``min_domain`` / ``min_global``: the cut-off of that score below which no pair is counted and no line printed but the last; the
+    other score's cut-off is an error.  ``report``: an open ``Report``, or a path / None as for the other modes."""
+    min_cut = _cut_of(score, min_domain, min_global, 'the histogram bins the pairs')
+    if families is not None and family_sep is not None:
+        raise ValueError('the families come from one place: families (a file) or family_sep (the ids themselves)')
+    if not isinstance(bins, (int, np.integer)) or not 1 <= bins <= HIST_MAX_BINS:
+        raise ValueError(f'bins is a number of cut-offs: 1 .. {HIST_MAX_BINS}')
+
+    def run(npzfile, report):
+        sid, idx, fps = _load_npz(npzfile)
+        labels = read_families(families, sid) if families is not None else families_from_ids(sid, family_sep) if family_sep is not None else None
+        Histogram(sid, idx, fps, labels, score=score, min_cut=min_cut).write(report.raw, bins)
+    return _reporting(run, header=hist_header(score, families is not None or family_sep is not None))(npzfile, report)
+
+
 RANKS = ('global', 'domain')
 LINKAGES = ('single', 'greedy')
 LEVELS = ('protein', 'domain')
@@ -2297,22 +2510,26 @@ def _is_set(value) -> bool:
 _GIVEN = {'--pair': bool, '--db': bool, '--cluster': bool, '--domains': bool, '--no-whole': bool,
           '--assign': _is_set, '--tree': _is_set, '--rank': _is_set, '--linkage': _is_set, '--level': _is_set, '--reps-out': _is_set,
           '--dom': _is_set, '--db-dom': _is_set, '--min-coverage': _is_set, '--cov-unit': _is_set, '--rep': _is_set,
-          '--min-neighbors': _is_set, '--auc1': _is_set, '--families': _is_set, '--family-sep': _is_set}
+          '--min-neighbors': _is_set, '--auc1': _is_set, '--families': _is_set, '--family-sep': _is_set, '--hist': _is_set, '--bins': _is_set}
 # mode -> (what it does; for a mode that takes a score, what that score does; the flags it refuses, in the order they are named).
 # The modes are checked in this order.
 _MODES = {'--rbh': ('prints the reciprocal best hits of --dct and --db', 'ranks the hits',
                     ('--pair', '--cluster', '--assign', '--tree', '--rank', '--linkage', '--level', '--no-whole', '--reps-out',
-                     '--min-coverage', '--cov-unit', '--rep', '--min-neighbors', '--auc1')),
+                     '--min-coverage', '--cov-unit', '--rep', '--min-neighbors', '--auc1', '--hist')),
           '--tree': ('prints the single-linkage tree of --dct', 'orders the pairs',
                      ('--pair', '--db', '--cluster', '--assign', '--rank', '--linkage', '--level', '--no-whole', '--reps-out', '--domains',
-                      '--dom', '--db-dom', '--min-coverage', '--cov-unit', '--rep', '--min-neighbors', '--auc1')),
+                      '--dom', '--db-dom', '--min-coverage', '--cov-unit', '--rep', '--min-neighbors', '--auc1', '--hist')),
           '--assign': ('places the proteins of --dct on a fixed set of representatives', None,
                        ('--pair', '--db', '--cluster', '--rank', '--domains', '--dom', '--db-dom', '--linkage', '--level', '--no-whole',
-                        '--min-coverage', '--cov-unit', '--rep', '--min-neighbors', '--auc1')),
+                        '--min-coverage', '--cov-unit', '--rep', '--min-neighbors', '--auc1', '--hist')),
           '--auc1': ('measures the AUC1 and the top-1 rates of --dct', 'ranks the hits',
                      ('--pair', '--db', '--cluster', '--assign', '--rank', '--linkage', '--level', '--no-whole', '--reps-out', '--domains',
-                      '--dom', '--db-dom', '--min-coverage', '--cov-unit', '--rep', '--min-neighbors'))}
-# the options that say where --auc1 finds the family of a protein: exactly one of them with it, none without
+                      '--dom', '--db-dom', '--min-coverage', '--cov-unit', '--rep', '--min-neighbors', '--hist')),
+          '--hist': ('bins the scores of all pairs of --dct', 'bins the pairs',
+                     ('--pair', '--db', '--cluster', '--assign', '--rank', '--linkage', '--level', '--no-whole', '--reps-out', '--domains',
+                      '--dom', '--db-dom', '--min-coverage', '--cov-unit', '--rep', '--min-neighbors', '--auc1'))}
+# the options that say where --auc1 and --hist find the family of a protein: exactly one of them with --auc1, at most one with --hist,
+# none without either
 _FAMILY_FLAGS = ('--families', '--family-sep')
 
 
@@ -2342,7 +2559,11 @@ class _Parser(argparse.ArgumentParser):
     ``--auc1`` measures how well one score ranks the proteins of a labelled file, the fourth mode of ``_MODES``: it refuses what
     ``--tree`` refuses and the other three refuse it; its own score's cut-off is allowed and the other score's an error, as for
     ``--tree``.  It needs the family of every protein from exactly one of ``--families FILE`` and ``--family-sep C`` (``_FAMILY_FLAGS``):
-    an error with neither, with both or with an empty ``C``, and either of the two is an error without ``--auc1``."""
+    an error with neither, with both or with an empty ``C``, and either of the two is an error without ``--auc1``.
+    ``--hist`` bins one score over all pairs of the file, the fifth mode of ``_MODES``: it refuses what ``--tree`` refuses and
+    ``--auc1``, and the other four refuse it; its own score's cut-off is allowed and the other score's an error.  The family flags
+    are optional with it -- at most one of the two, and ``C`` not empty -- and say which pairs are of one family.  ``--bins B`` is the
+    number of cut-offs of its table: 1 .. 1000, an error without ``--hist``."""
 
     def parse_known_args(self, args=None, namespace=None):
         ns, rest = super().parse_known_args(args, namespace)
@@ -2366,10 +2587,21 @@ class _Parser(argparse.ArgumentParser):
                     self.error('--auc1 takes the families from one place: --families or --family-sep, not both')
                 if getattr(ns, 'family_sep', None) == '':
                     self.error('--family-sep is the text between id and family: at least one character')
+            if mode == '--hist':
+                if all(_GIVEN[flag](getattr(ns, _dest(flag), None)) for flag in _FAMILY_FLAGS):
+                    self.error('--hist takes the families from one place: --families or --family-sep, not both')
+                if getattr(ns, 'family_sep', None) == '':
+                    self.error('--family-sep is the text between id and family: at least one character')
             other = {'domain': 'global', 'global': 'domain'}.get(score)
             if orders and getattr(ns, f'min_{other}') is not None:
                 self.error(f'{mode} {score} {orders} by DCT{score}: its cut-off is --min-{score}, not --min-{other}')
-        if getattr(ns, 'auc1', None) is None:
+        bins = getattr(ns, 'bins', None)
+        if bins is not None:
+            if getattr(ns, 'hist', None) is None:
+                self.error('--bins says how many cut-offs the table of --hist has: it needs --hist')
+            if not 1 <= bins <= HIST_MAX_BINS:
+                self.error(f'--bins is a number of cut-offs: 1 .. {HIST_MAX_BINS}')
+        if getattr(ns, 'auc1', None) is None and getattr(ns, 'hist', None) is None:
             for flag in _FAMILY_FLAGS:
                 if _GIVEN[flag](getattr(ns, _dest(flag), None)):
                     self.error(f'{flag} says which family a protein belongs to, for --auc1 to judge the hits by: it needs --auc1')
@@ -2530,6 +2762,14 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument('--family-sep', metavar='C', default=argparse.SUPPRESS,
                     help='--auc1: the family of a protein is the text after the first C in its own id (CATH20 ids: '
                          '16vpA00|3.30.930.10 with C = "|")')
+    ap.add_argument('--hist', nargs='?', choices=SCORES, const='domain', default=argparse.SUPPRESS,
+                    help='print the distribution of DCTdomain (domain, the default) or DCTglobal (global) over all pairs of the file '
+                         'instead of the pairs: per cut-off of --bins the pairs that --min-domain X (--min-global Y with global) would '
+                         'keep; with --families or --family-sep, the pairs of one family and of two apart, recall, precision and '
+                         'false-positive rate per cut-off, and a last line with the ROC AUC and the cut-off of the best F1.  '
+                         '--min-domain X (--min-global Y with global) leaves the cut-offs below it out')
+    ap.add_argument('--bins', type=int, metavar='B', default=argparse.SUPPRESS,
+                    help=f'--hist: the number of cut-offs of the table, (B - 1) / B down to 0 (default {HIST_BINS}, at most {HIST_MAX_BINS})')
     return ap
 
 
@@ -2541,13 +2781,17 @@ def main(argv=None):
     assign, reps_out = getattr(args, 'assign', None), getattr(args, 'reps_out', None)
     min_coverage = getattr(args, 'min_coverage', None)
     cover = {'min_coverage': min_coverage, 'cov_unit': getattr(args, 'cov_unit', 'residues')} if min_coverage is not None else {}
-    auc1 = getattr(args, 'auc1', None)
-    report = Report(args.output, _header(AUC1_HEADER if auc1 is not None else CLUSTER_HEADER if args.cluster or assign is not None else HEADER,
+    auc1, hist = getattr(args, 'auc1', None), getattr(args, 'hist', None)
+    family = {'families': getattr(args, 'families', None), 'family_sep': getattr(args, 'family_sep', None)}
+    report = Report(args.output, _header(hist_header(hist, any(v is not None for v in family.values())) if hist is not None else
+                                         AUC1_HEADER if auc1 is not None else CLUSTER_HEADER if args.cluster or assign is not None else HEADER,
                                          level, domains))
     t_work = time.time()
-    if auc1 is not None:
-        auc1_sim(args.dct, report, score=auc1, families=getattr(args, 'families', None), family_sep=getattr(args, 'family_sep', None),
-                 min_domain=args.min_domain, min_global=args.min_global)
+    if hist is not None:
+        hist_sim(args.dct, report, score=hist, bins=getattr(args, 'bins', HIST_BINS), min_domain=args.min_domain, min_global=args.min_global,
+                 **family)
+    elif auc1 is not None:
+        auc1_sim(args.dct, report, score=auc1, min_domain=args.min_domain, min_global=args.min_global, **family)
     elif getattr(args, 'tree', None) is not None:
         tree_sim(args.dct, report, score=args.tree, min_domain=args.min_domain, min_global=args.min_global)
     elif getattr(args, 'rbh', None) is not None:

@@ -714,6 +714,28 @@ def tri_tp_before(tile: torch.Tensor, row0: int, col0: int, bound: int, fam: tor
                 ((fam, torch.int32, 'fam'), (first, torch.int64, 'first'), (tp, torch.int32, 'tp')))
 
 
+def tri_hist(tile: torch.Tensor, row0: int, col0: int, bound: int, hist: torch.Tensor, fam: torch.Tensor = None, row_empty=None,
+             col_empty=None, cap: int = 17000):
+    """Adds 1 to ``hist[cls, key]`` for every entry (r, c) of an L1 tile of ONE file that ``tri_degree`` would count -- col0 + c >
+    row0 + r and key = min(L1, cap) <= bound, ``cap`` for a row / column flagged empty (``dctfp_tri_hist``).  ``hist``: a contiguous
+    device int64 tensor (the library's uint64; a count stays far below 2^63) of shape (1 or 2, cap + 1), zeroed by the caller before
+    the first tile.  Without ``fam`` there is one class, ``cls = 0``, and one row; with ``fam`` (device int32, one family per
+    protein) ``cls = (fam[row0 + r] != fam[col0 + c])`` and ``hist`` has two rows: the pairs of one family, then the pairs of two.
+    The counts add up over the tiles of the triangle and over calls; integer addition commutes, so they do not depend on how the
+    triangle is cut into tiles or on the order of the calls."""
+    if hist.dtype != torch.int64 or hist.dim() != 2 or not hist.is_contiguous() or hist.device != tile.device or hist.shape[1] != cap + 1:
+        raise ValueError('hist must be a contiguous int64 tensor of shape (classes, cap + 1) on the device of the tile')
+    if hist.shape[0] != (1 if fam is None else 2):
+        raise ValueError('hist has one row without fam and two rows with it')
+    if fam is not None:
+        n_nodes = _node_arrays(tile, ((fam, torch.int32, 'fam'),))
+    else:
+        n_nodes = max(int(row0) + tile.shape[0], int(col0) + tile.shape[1]) if tile.dim() == 2 else 0
+    n_rows, n_cols, lead, _flags = _tri_filter_args(tile, row0, col0, bound, row_empty, col_empty, cap, n_nodes)
+    if n_rows and n_cols:
+        _launch(tile.device, 'dctfp_tri_hist', *lead, _ptr(fam), n_nodes, hist.data_ptr())
+
+
 GREEDY_NONE = 0x7fffffff                       # assign: no representative yet
 GREEDY_UNDECIDED, GREEDY_MEMBER, GREEDY_NEW, GREEDY_DONE = 0, 1, 2, 3
 

@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define DCTFP_VERSION 114 /* 0.1.14: dctfp_tri_first_fp, dctfp_tri_tp_before */
+#define DCTFP_VERSION 115 /* 0.1.15: dctfp_tri_hist */
 
 #define DCTFP_OK 0
 #define DCTFP_ERR_INVALID (-1) /* bad argument (null pointer, piece outside its sequence, ...) */
@@ -670,6 +670,29 @@ int dctfp_tri_first_fp(dctfp_ctx* ctx, const int32_t* tile, int64_t n_rows, int6
 int dctfp_tri_tp_before(dctfp_ctx* ctx, const int32_t* tile, int64_t n_rows, int64_t n_cols, int64_t ld, int64_t row0, int64_t col0,
                         const uint8_t* row_empty, const uint8_t* col_empty, int32_t cap, int32_t bound, const int32_t* fam,
                         const uint64_t* first, uint32_t* tp, int64_t n_nodes, void* stream);
+
+/* The score distribution of one file (dct-sim --hist; the reference draws it from printed pairs, bench/G6PD/hist.py, and takes the
+ * ROC AUC of labelled pairs the same way, bench/homo/results/AUC.py): how many pairs have each key.  Entry (r, c) of an int32 tile
+ * of L1 values, at tile[r * ld + c], is the L1 of proteins i = row0 + r and j = col0 + c of ONE file, and it COUNTS when
+ * dctfp_tri_degree would count it: j > i and key <= bound, key = cap when the row is flagged in row_empty, the column in col_empty
+ * (device uint8, one per row / column of the tile, either may be NULL) or the value is negative or >= cap, else the value.  Every
+ * counted entry adds 1 to
+ *     hist[cls * (cap + 1) + key]
+ * (device uint64, 8-byte aligned, cap + 1 entries per class; the caller zeroes it before the first tile).  fam NULL: one class,
+ * cls = 0.  Else fam (device int32, n_nodes entries, written before the call; the values are only compared) names every protein's
+ * family and cls = (fam[i] != fam[j]): row 0 counts the pairs of one family, row 1 the pairs of two.  The tile may hold entries on
+ * both sides of the diagonal: j > i takes every unordered pair once.  A loop of its own over the tile (plain 4-byte loads: any
+ * ld >= n_cols, a column view of a wider tensor included); a workgroup counts in 32-bit counters of its own in LDS over all its jobs
+ * -- lanes of a wave that share a key add once -- and sends every non-zero bin out once.  Inside the launch hist is touched by
+ * agent-scope relaxed 64-bit atomic adds only.  Integer addition commutes: the counts add up over tiles and over calls and do not
+ * depend on the order in which the device ran, on how the triangle is cut into tiles or on the order of the calls.
+ * DCTFP_ERR_INVALID, with a message that starts with the export's name, for: a NULL ctx, tile or hist; a negative count or offset;
+ * ld < n_cols; cap < 0, bound outside -1 .. cap; a cap above 20479 (two classes of cap + 1 counters fill the 160 KiB of LDS of a
+ * CU); n_nodes negative or >= 2^31; row0 + n_rows > n_nodes or col0 + n_cols > n_nodes (checked on the host, with or without fam:
+ * the kernel bounds no index); a tile or fam off a 4-byte or hist off an 8-byte boundary.  n_rows or n_cols of 0: nothing to do. */
+int dctfp_tri_hist(dctfp_ctx* ctx, const int32_t* tile, int64_t n_rows, int64_t n_cols, int64_t ld, int64_t row0, int64_t col0,
+                   const uint8_t* row_empty, const uint8_t* col_empty, int32_t cap, int32_t bound, const int32_t* fam, int64_t n_nodes,
+                   uint64_t* hist, void* stream);
 
 /* query_db's search (src/query_db.py:75-87: a flat FAISS index forced to METRIC_L1 at :76, index.search at :87) without a
  * distance matrix: for query rows q (nq x d, row stride ldq) and database rows b (nb x d, stride ldb), int8 on the device, each
