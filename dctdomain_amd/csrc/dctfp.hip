@@ -3113,6 +3113,40 @@ int dctfp_tri_hist(dctfp_ctx* ctx, const int32_t* tile, int64_t n_rows, int64_t 
     return DCTFP_OK;
 } DCTFP_GUARD("dctfp_tri_hist")
 
+// dct-sim --db --zscore (k_moments.hip)
+int dctfp_rect_moments(dctfp_ctx* ctx, const int32_t* tile, int64_t n_rows, int64_t n_cols, int64_t ld, int64_t row0, int64_t col0,
+                       const uint8_t* row_empty, const uint8_t* col_empty, int32_t cap, int32_t bound, uint64_t* row_mom, int64_t n_a,
+                       uint64_t* col_mom, int64_t n_b, void* stream_v) try {
+    (void)bound;   // (a moment has no cut-off: cap is the exclusion limit and nothing else is compared)
+    if (!ctx || !tile) return fail(DCTFP_ERR_INVALID, "dctfp_rect_moments: NULL argument");
+    if (!row_mom && !col_mom) return fail(DCTFP_ERR_INVALID, "dctfp_rect_moments: row_mom and col_mom are both NULL");
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    // (a rectangle with three words per protein, either side optional: its own few conditions)
+    if (n_rows < 0 || n_cols < 0 || n_rows > 0x7fffffff || n_cols > 0x7fffffff || ld < n_cols || row0 < 0 || col0 < 0 || cap < 0)
+        return fail(DCTFP_ERR_INVALID, "dctfp_rect_moments: bad shape or cap");
+    if (((reinterpret_cast<uintptr_t>(tile) & 3u) | ((reinterpret_cast<uintptr_t>(row_mom) | reinterpret_cast<uintptr_t>(col_mom)) & 7u)) != 0)
+        return fail(DCTFP_ERR_INVALID, "dctfp_rect_moments: the tile is not 4-byte aligned or row_mom / col_mom not 8-byte aligned");
+    if (cap > rect_moments_max_cap())
+        return fail(DCTFP_ERR_INVALID, "dctfp_rect_moments: a cap above %d does not fit the 32-bit partial sums of a row", rect_moments_max_cap());
+    if (n_a < 0 || n_b < 0 || n_a > 0x7fffffff || n_b > 0x7fffffff) return fail(DCTFP_ERR_INVALID, "dctfp_rect_moments: n_a and n_b must lie in 0 .. 2^31 - 1");
+    // (every index the kernel can form lies inside the tile and the arrays it was given: bounded here, on the host, and not on the device)
+    if ((row_mom && row0 + n_rows > n_a) || (col_mom && col0 + n_cols > n_b))
+        return fail(DCTFP_ERR_INVALID, "dctfp_rect_moments: the tile names proteins outside row_mom / col_mom");
+    // a row's words add up over the columns it meets and a column's over its rows: n_b resp. n_a of them, at least this tile's
+    if (cap > 1) {
+        const unsigned __int128 sq = (unsigned __int128)(cap - 1) * (unsigned __int128)(cap - 1), most = ~(uint64_t)0;
+        const int64_t over_cols = std::max(n_b, col0 + n_cols), over_rows = std::max(n_a, row0 + n_rows);
+        if ((row_mom && sq * (unsigned __int128)over_cols > most) || (col_mom && sq * (unsigned __int128)over_rows > most))
+            return fail(DCTFP_ERR_INVALID, "dctfp_rect_moments: n x (cap - 1)^2 does not fit the 64 bits of a sum of squares");
+    }
+    if (n_rows == 0 || n_cols == 0) return DCTFP_OK;
+    HIP_TRY(hipSetDevice(ctx->device));
+    launch_rect_moments(TriTile{tile, n_rows, n_cols, ld, row0, col0, row_empty, col_empty, cap, cap}, row_mom, n_a, col_mom, n_b,
+                        (hipStream_t)stream_v);
+    HIP_TRY(hipGetLastError());
+    return DCTFP_OK;
+} DCTFP_GUARD("dctfp_rect_moments")
+
 int dctfp_greedy_decide(dctfp_ctx* ctx, int32_t* assign, int32_t* state, const int32_t* blocked, int64_t n_nodes, int64_t i0, int64_t i1,
                         int32_t round, int64_t* undecided, void* stream_v) try {
     if (!ctx || !assign || !state || !blocked || !undecided) return fail(DCTFP_ERR_INVALID, "dctfp_greedy_decide: NULL argument");

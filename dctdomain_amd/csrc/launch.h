@@ -219,6 +219,14 @@ void launch_tri_tp_before(const TriTile& t, const int32_t* fam, const uint64_t* 
 int tri_hist_max_cap();
 int launch_tri_hist(const TriTile& t, const int32_t* fam, uint64_t* hist, hipStream_t stream, LaunchError* err);
 
+// the moments of every protein's background (k_moments.hip): a loop of its own over the full rectangle of an int32 L1 tile -- every
+// entry whose row and column are not flagged and whose value x has (uint32_t)x < cap (an exclusion limit; bound is not read) adds
+// (1, x, x * x) to row_mom[k * n_a + row0 + r] and to col_mom[k * n_b + col0 + c], k = 0, 1, 2, with agent-scope 64-bit atomic adds
+// of parts reduced in the workgroup; either array may be NULL.  rect_moments_max_cap = the largest cap whose 32-bit partial sums
+// cannot overflow
+int rect_moments_max_cap();
+void launch_rect_moments(const TriTile& t, uint64_t* row_mom, int64_t n_a, uint64_t* col_mom, int64_t n_b, hipStream_t stream);
+
 // (dctfp_rows_assign, k_assign.hip: the same contraction over a full rectangle -- every pair of rows within the bound lowers
 // assign[slot of the b row] to the value of the a row with an atomic minimum; value_a / slot_b NULL: a0 + r / b0 + c)
 void launch_rows_assign(const int8_t* a, int64_t na, int64_t lda, const int32_t* value_a, int64_t a0, const int8_t* b, int64_t nb, int64_t ldb,

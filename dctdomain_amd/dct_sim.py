@@ -108,6 +108,11 @@ Where the reference loops over protein pairs and, inside, over domain pairs in P
   tiles (``dctfp_protein_min``, or ``dctfp_l1_matrix`` of the last rows) go to one kernel that keeps the best column of every row
   and the best row of every column with atomic minima of ``key << 32 | index`` (``dctfp_rect_best``); 8 bytes per protein come
   back at the end, and the lines are ``db_search``'s lines for those pairs;
+- ``--db Y --zscore`` (not in the reference) adds a z-score to every hit line, with or without ``--rbh``: the place of the hit's L1
+  in the query's background, the raw L1s of the query against every protein of the database under the score that ranks
+  (``zscore_of`` states the rule).  The tiles the search fills anyway are scanned once more before the hits are selected
+  (``dctfp_rect_moments``: count, sum and sum of squares per protein, exact 64-bit integers) and 24 bytes per protein come back;
+  z follows on the host from integers, the same on every machine.  ``--min-z Z`` drops the selected lines whose z is below Z;
 - ``pair_sim`` uploads the fingerprints of the proteins its pairs name and runs ``dctfp_pair_min`` on the pairs.
 ``--domains`` (not in the reference) adds two fields to every result line: the fingerprint of each protein that DCTdomain came
 from -- the pair the reference's double loop (:42-50) ends on: the smallest L1, ties to the lowest row of the first protein, then
@@ -122,6 +127,7 @@ floats are identical."""
 from __future__ import annotations
 
 import argparse
+import math
 import sys
 import time
 
@@ -131,7 +137,7 @@ from .similarity import (GREEDY_NONE, PROTEIN_MIN_MAX_D, GreedyState, LineIds, T
                          greedy_decide, greedy_pairs_mark, greedy_tri_mark, l1_matrix, link_pairs, pair_argmin, pair_argmin_device, pair_line_offsets, pair_lines, pair_min, pair_min_device, protein_cover, protein_min,
                          rows_assign, rows_link, sim_lines, threshold_select, to_device_int8, tri_filter_count, tri_filter_fill, tri_link,
                          TREE_MAX_NODES, TreeState, tree_hook, tri_nearest, BestState, rect_best, label_sums, NEAREST_NONE, tri_degree,
-                         tri_link_core, BEST_NONE, tri_first_fp, tri_tp_before, tri_hist)
+                         tri_link_core, BEST_NONE, tri_first_fp, tri_tp_before, tri_hist, MomentState, rect_moments)
 
 L1_FULL_SCALE = 17000      # src/dct-sim.py:24
 HEADER = '#prot1 prot2 sim-domain sim-global'
@@ -140,6 +146,60 @@ DOMAIN_HEADER = HEADER + ' dom1 dom2'      # --domains
 DOMAIN_CLUSTER_HEADER = CLUSTER_HEADER + ' dom1 dom2'      # --cluster --level domain
 NO_DOMAIN = '-'                            # no fingerprint pair scores above 0
 WHOLE = 'whole'                            # the whole-protein row a .dom file leaves unnamed
+
+
+def _z_spread(n: int, s1: int, s2: int):
+    """sqrt(n s2 - s1^2) = n sigma of a background (Python integers: the radicand is exact, then one ``math.sqrt``); None where no z is
+    defined against it: n < 2, or a radicand of 0."""
+    radicand = n * s2 - s1 * s1
+    return math.sqrt(radicand) if n >= 2 and radicand > 0 else None
+
+
+def zscore_of(n, s1, s2, d):
+    """The z-score of a hit with L1 ``d`` in a background of ``n`` L1s with sum ``s1`` and sum of squares ``s2`` (Python integers, or
+    what ``int`` takes): z = (s1 - n d) / sqrt(n s2 - s1^2) = (mean - d) / sigma with the population sigma -- numerator and radicand
+    exact integers, one ``math.sqrt``, one true division.  Positive = closer than the background.  The background of a query under a
+    score is every protein of the database with which it has an L1 (neither is without fingerprints), the query itself included
+    where the database holds it, each L1 raw (not capped at 17000).  None where z is undefined: ``d`` None (the pair has no L1),
+    n < 2, or a radicand of 0."""
+    if d is None:
+        return None
+    n, s1, s2, d = int(n), int(s1), int(s2), int(d)
+    spread = _z_spread(n, s1, s2)
+    return None if spread is None else (s1 - n * d) / spread
+
+
+def zscores_of(mom, owner, d, has_l1=None) -> np.ndarray:
+    """``zscore_of`` for many hits at once, to the same bits: float64, NaN where it has None.  ``mom`` = the (3, n) int64 array of
+    ``MomentState.moments`` (the library's uint64 words), hit k lies in the background of protein ``owner[k]`` with L1 ``d[k]``, and
+    ``has_l1[k]`` (default: all) says whether the pair has one.  The spread is taken per protein from Python integers
+    (``_z_spread``); the numerator s1 - n d is exact in int64 (n < 2^31, d < 2^31, s1 < 2^55), its conversion to float64 rounds as
+    Python's does, and the division is the same IEEE division."""
+    owner, d = np.asarray(owner, dtype=np.int64), np.asarray(d, dtype=np.int64)
+    used = np.unique(owner)
+    words = np.ascontiguousarray(mom[:, used]).view(np.uint64).tolist()
+    spread = np.full(mom.shape[1], np.nan)
+    spread[used] = [v if v is not None else np.nan for v in (_z_spread(*w) for w in zip(*words))]
+    with np.errstate(invalid='ignore'):
+        z = (mom[1][owner] - mom[0][owner] * d) / spread[owner]
+    if has_l1 is not None:
+        z[~np.asarray(has_l1, dtype=bool)] = np.nan
+    return z
+
+
+def zscore_text(z) -> str:
+    """The field of a z-score: two decimals, ``-`` where it is undefined (None or NaN)."""
+    return '-' if z is None or z != z else f'{z:.2f}'
+
+
+def _z_passes(min_z: float, *zs) -> bool:
+    """``--min-z``: every z is defined (neither None nor NaN) and not below ``min_z``."""
+    return all(z is not None and z >= min_z for z in zs)
+
+
+def _moment_ints(mom):
+    """[(n, s1, s2)] per protein as Python integers from a (3, n) int64 array of ``MomentState.moments`` (the library's uint64)."""
+    return list(zip(*np.ascontiguousarray(mom).view(np.uint64).tolist()))
 
 
 def _sim(l1):
@@ -2042,18 +2102,29 @@ class ProteinSearch:
                     t1 = min(c1, t0 + per)
                     yield t0, p0, protein_min(a, aidx[t0:t1 + 1] - aidx[c0], rows, sub_idx), (a_empty[t0:t1], empty)
 
-    def search(self, query_fps, query_idx, top: int, threshold: float, rank: str = 'global', domains: bool = False):
+    def moment_limit(self) -> int:
+        """``rect_moments``' limit for tiles of this database: one above the largest L1 of two int8 fingerprints of its width."""
+        return 255 * int(self.fps.shape[1]) + 1
+
+    def search(self, query_fps, query_idx, top: int, threshold: float, rank: str = 'global', domains: bool = False, zscore: bool = False):
+        """``zscore``: every tile also goes to ``rect_moments`` (the rows' side alone) before the selection, and each query's tuple
+        ends with one more array -- the z-score of every printed hit (``zscore_of``; float64, NaN where undefined) in the query's
+        background under the score of ``rank``."""
         if rank not in RANKS:
             raise ValueError(f'rank must be one of {RANKS}')
         top = int(top)
         qidx = np.asarray(query_idx, dtype=np.int64)
         nq, n_db = len(qidx) - 1, len(self.idx) - 1
         if nq == 0 or n_db == 0:
-            return [(np.zeros(0, dtype=np.int64),) * (5 if domains else 3) for _ in range(nq)]
+            return [(np.zeros(0, dtype=np.int64),) * (5 if domains else 3) + ((np.zeros(0, dtype=np.float64),) if zscore else ())
+                    for _ in range(nq)]
         bound = sim_bound(threshold)
         top1 = max(top, 1)      # (top <= 0: the reference prints the threshold hits only -- trimmed after the merge)
         parts = [[] for _ in range(nq)]
+        state = MomentState(nq, 0, cols=False) if zscore else None
         for t0, p0, tile, flags in self.tiles(query_fps, qidx, rank):
+            if state is not None:
+                rect_moments(tile, t0, p0, state, *flags, limit=self.moment_limit())
             _add_hits(parts, t0, p0, *threshold_select(tile, top1, bound, *flags))
             del tile
         merged = (merge_candidates(pq, top1, bound) for pq in parts)
@@ -2064,6 +2135,10 @@ class ProteinSearch:
         db_of = np.concatenate(hits).astype(np.int64) if nq else np.zeros(0, dtype=np.int64)
         scores = self._pair_scores(query_fps, qidx, q_of, db_of, domains)
         bounds = np.concatenate([[0], np.cumsum(counts)])
+        if state is not None:
+            # (a pair has an L1 when both proteins have a fingerprint; the hit's L1 under the ranking score is min / last)
+            has_l1 = (self.idx[db_of + 1] > self.idx[db_of]) & (qidx[q_of + 1] > qidx[q_of])
+            scores += (zscores_of(state.moments()[0], q_of, scores[0 if rank == 'domain' else 1], has_l1),)
         return [(db_of[a:b],) + tuple(v[a:b] for v in scores) for a, b in zip(bounds[:-1], bounds[1:])]
 
     def _pair_scores(self, query_fps, qidx, q_of, db_of, domains: bool = False):
@@ -2118,6 +2193,16 @@ class ReciprocalBest(ProteinSearch):
         self.score = score
         self.bound = L1_FULL_SCALE - 1 if min_cut is None else min(sim_bound(min_cut), L1_FULL_SCALE - 1)
         self._best = None
+        self.zscore, self._moments = False, None
+
+    def with_zscore(self):
+        """This job with z-scores: every tile of the pass also goes to ``rect_moments``, both sides -- the rows are the backgrounds of
+        the proteins of A over file B, the columns those of B over A -- and ``lines`` / ``write`` append `` z_a z_b``.  To be called
+        before the pass (``best``); returns the job."""
+        if self._best is not None:
+            raise ValueError('the pass has been made: ask for z-scores before best()')
+        self.zscore = True
+        return self
 
     def best(self):
         """((best_b, its key) per protein of A, (best_a, its key) per protein of B): int64 numpy arrays, -1 in both where a protein
@@ -2127,12 +2212,26 @@ class ReciprocalBest(ProteinSearch):
                 self._best = tuple((np.full(n, -1, dtype=np.int64), np.full(n, -1, dtype=np.int64)) for n in (self.n_a, self.n_b))
             else:
                 state = BestState(self.n_a, self.n_b)
+                background = MomentState(self.n_a, self.n_b) if self.zscore else None
                 for t0, p0, tile, flags in self.tiles(self.fps_a, self.idx_a, self.score, bare=False):
+                    if background is not None:                      # (both sides of the same tile: rows = A over B, columns = B over A)
+                        rect_moments(tile, t0, p0, background, *flags, limit=self.moment_limit())
                     # (the domain tile holds 0x7fffffff, key 17000, for a protein without fingerprints: no flags needed)
                     rect_best(tile, t0, p0, self.bound, state, *(flags if self.score == 'global' else ()), cap=L1_FULL_SCALE)
                     del tile
                 self._best = state.hits()
+                if background is not None:
+                    self._moments = background.moments()
         return self._best
+
+    def zscores(self, a, b, d):
+        """(z_a, z_b) of the pairs (a[k], b[k]) with L1 ``d[k]`` under the score: its place in a's background over file B (the rows'
+        side of the tiles) and in b's background over file A (the columns' side).  float64 arrays (``zscores_of``), NaN where undefined."""
+        self.best()
+        if self._moments is None:
+            raise ValueError('no z-scores were asked for: with_zscore()')
+        rows, cols = self._moments
+        return zscores_of(rows, a, d), zscores_of(cols, b, d)
 
     def pairs(self):
         """(a, b, key): int64 numpy arrays of the reciprocal best hits, a ascending."""
@@ -2141,9 +2240,11 @@ class ReciprocalBest(ProteinSearch):
         a = a[best_a[best_b[a]] == a]
         return a, best_b[a], key[a]
 
-    def lines(self, domains: bool = False, labels=None, db_labels=None) -> list:
+    def lines(self, domains: bool = False, labels=None, db_labels=None, min_z: float = None) -> list:
         """``db_search``'s lines of the reciprocal best hits, in ascending order of a.  ``domains``: with the domain pair behind
-        DCTdomain, named by ``labels`` / ``db_labels`` (``fingerprint_labels`` of the two files; default: the 1-based indices)."""
+        DCTdomain, named by ``labels`` / ``db_labels`` (``fingerprint_labels`` of the two files; default: the 1-based indices).  After
+        ``with_zscore``: every line ends with `` z_a z_b`` (``zscores``), and ``min_z`` keeps the lines whose two z are defined and
+        not below it."""
         a, b, _ = self.pairs()
         if len(a) == 0:
             return []
@@ -2152,15 +2253,20 @@ class ReciprocalBest(ProteinSearch):
             labels = labels if labels is not None else fingerprint_labels(self.sid_a, self.idx_a)
             db_labels = db_labels if db_labels is not None else fingerprint_labels(self.sid_b, self.idx)
         out = []
+        z_a, z_b = self.zscores(a, b, mn if self.score == 'domain' else last) if self.zscore else (None, None)
         for k, (i, j, m, l) in enumerate(zip(a.tolist(), b.tolist(), mn, last)):
             maxs, s = _scores(m, l)
             tail = f' {_label(labels, self.idx_a[i], args[0][k])} {_label(db_labels, self.idx[j], args[1][k])}' if domains else ''
+            if self.zscore:
+                if min_z is not None and not _z_passes(min_z, z_a[k], z_b[k]):
+                    continue
+                tail += f' {zscore_text(z_a[k])} {zscore_text(z_b[k])}'
             out.append(f'{self.sid_a[i]} {self.sid_b[j]} {maxs} {s}{tail}')
         return out
 
-    def write(self, report, domains: bool = False, labels=None, db_labels=None):
+    def write(self, report, domains: bool = False, labels=None, db_labels=None, min_z: float = None):
         """One ``report.line`` per reciprocal best hit."""
-        for text in self.lines(domains, labels, db_labels):
+        for text in self.lines(domains, labels, db_labels, min_z):
             report.line(text)
 
 
@@ -2201,19 +2307,25 @@ def _header(base: str, level: str = None, domains=False) -> str:
     return DOMAIN_HEADER if base == HEADER and domains else base
 
 
-def _reporting(fn=None, *, header: str = HEADER):
+def _z_header(zscore, rbh: bool = False, rank: str = None) -> str:
+    """What ``--zscore`` adds to the header, behind every other column: the z of the ranking score, or the two z of ``--rbh``."""
+    return '' if not zscore else ' z-query z-db' if rbh else f' z-{rank or "global"}'
+
+
+def _reporting(fn=None, *, header: str = HEADER, rbh: bool = False):
     """The mode functions keep the reference's signature -- the last argument may be an output path or
     ``None`` (stdout) -- and also take an open ``Report``.  Keyword arguments (options beyond the reference's) pass through.
-    ``@_reporting(header=...)``: the header of a report opened here."""
+    ``@_reporting(header=...)``: the header of a report opened here; ``rbh``: its z columns are ``--rbh``'s."""
     if fn is None:
-        return lambda f: _reporting(f, header=header)
+        return lambda f: _reporting(f, header=header, rbh=rbh)
 
     def run(*args, **kw):
         *head, output = args
         if isinstance(output, Report):
             return fn(*head, output, **kw)
-        # (a report opened here for a call that asks for the domain pair carries the two extra column names)
-        report = Report(output, _header(header, kw.get('level'), any(kw.get(k) for k in ('domains', 'dom', 'db_dom'))))
+        # (a report opened here for a call that asks for the domain pair carries the two extra column names, one that asks for z its)
+        report = Report(output, _header(header, kw.get('level'), any(kw.get(k) for k in ('domains', 'dom', 'db_dom')))
+                        + _z_header(kw.get('zscore') or kw.get('min_z') is not None, rbh, kw.get('rank')))
         try:
             return fn(*head, report, **kw)
         finally:
@@ -2258,21 +2370,28 @@ def pair_sim(npzfile: str, pairfile: str, pairfound: str, report: Report, domain
 
 @_reporting
 def db_search(npzfile: str, dbfile: str, top: int, threshold: float, report: Report, rank: str = 'global', domains: bool = False,
-              dom: str = None, db_dom: str = None):
+              dom: str = None, db_dom: str = None, zscore: bool = False, min_z: float = None):
     """Hits of every query protein in a fingerprint database, best DCTglobal first (stable); the first
     ``top`` always, further ones while they reach ``threshold`` (src/dct-sim.py:126-156).  ``rank='domain'``: best
     DCTdomain first, and the threshold applies to DCTdomain (the same loop with the domain score as the key).  ``domains`` /
-    ``dom`` / ``db_dom`` (the ``.dom`` files of the two npz): the best domain pair behind the scores of every printed hit."""
+    ``dom`` / ``db_dom`` (the ``.dom`` files of the two npz): the best domain pair behind the scores of every printed hit.
+    ``zscore``: one more field at the end of every line, the hit's z-score in the query's background over the database under the
+    ranking score (``zscore_of``); ``min_z`` (implies ``zscore``) prints a selected line only if its z is defined and not below it."""
     sid, idx, fps = _load_npz(npzfile)
     db_sid, db_idx, db_fps = _load_npz(dbfile)
     domains = domains or dom is not None or db_dom is not None
+    zscore = zscore or min_z is not None
     if domains:
         labels, db_labels = _labels_of(sid, idx, dom), _labels_of(db_sid, db_idx, db_dom)
-    hits = ProteinSearch(db_fps, db_idx).search(fps, idx, top, threshold, rank=rank, domains=domains)
+    hits = ProteinSearch(db_fps, db_idx).search(fps, idx, top, threshold, rank=rank, domains=domains, **({'zscore': True} if zscore else {}))
     for i, (query, (cols, mn, last, *args)) in enumerate(zip(sid, hits)):
         for k, (q, m, l) in enumerate(zip(cols, mn, last)):
             maxs, s = _scores(m, l)
             tail = f' {_label(labels, idx[i], args[0][k])} {_label(db_labels, db_idx[q], args[1][k])}' if domains else ''
+            if zscore:
+                if min_z is not None and not _z_passes(min_z, args[-1][k]):
+                    continue
+                tail += f' {zscore_text(args[-1][k])}'
             report.line(f'{query} {db_sid[q]} {maxs} {s}{tail}')
 
 
@@ -2400,20 +2519,25 @@ def tree_sim(npzfile: str, report: Report, score: str = 'domain', min_domain: fl
     Tree(sid, idx, fps, score=score, min_cut=min_cut).write(report.raw)
 
 
-@_reporting
+@_reporting(rbh=True)
 def rbh_sim(npzfile: str, dbfile: str, report: Report, score: str = 'domain', min_domain: float = None, min_global: float = None,
-            domains: bool = False, dom: str = None, db_dom: str = None):
+            domains: bool = False, dom: str = None, db_dom: str = None, zscore: bool = False, min_z: float = None):
     """The reciprocal best hits of the proteins of ``npzfile`` and ``dbfile`` (``ReciprocalBest``) on DCTdomain (``score='domain'``) or
     DCTglobal (``'global'``): one ``db_search`` line per pair, in the order of ``npzfile``.  ``min_domain`` / ``min_global``: the cut-off
     of that score below which a pair is no hit; the other score's cut-off is an error.  ``domains`` / ``dom`` / ``db_dom``: as in
-    ``db_search``."""
+    ``db_search``.  ``zscore``: two more fields at the end of every line, the pair's z-score in the background of the ``npzfile``
+    protein over ``dbfile`` and in that of the ``dbfile`` protein over ``npzfile``, both under ``score``; ``min_z`` (implies
+    ``zscore``) prints a pair only if both are defined and not below it."""
     min_cut = _cut_of(score, min_domain, min_global, 'reciprocal best hits are ranked')
     sid, idx, fps = _load_npz(npzfile)
     db_sid, db_idx, db_fps = _load_npz(dbfile)
     domains = domains or dom is not None or db_dom is not None
     labels, db_labels = (_labels_of(sid, idx, dom), _labels_of(db_sid, db_idx, db_dom)) if domains else (None, None)
+    zscore = zscore or min_z is not None
     job = ReciprocalBest(sid, idx, fps, db_sid, db_idx, db_fps, score=score, min_cut=min_cut)
-    job.write(report, domains=domains, labels=labels, db_labels=db_labels)
+    if zscore:
+        job.with_zscore()
+    job.write(report, domains=domains, labels=labels, db_labels=db_labels, **({'min_z': min_z} if min_z is not None else {}))
 
 
 def read_families(path: str, sid) -> list:
@@ -2510,7 +2634,8 @@ def _is_set(value) -> bool:
 _GIVEN = {'--pair': bool, '--db': bool, '--cluster': bool, '--domains': bool, '--no-whole': bool,
           '--assign': _is_set, '--tree': _is_set, '--rank': _is_set, '--linkage': _is_set, '--level': _is_set, '--reps-out': _is_set,
           '--dom': _is_set, '--db-dom': _is_set, '--min-coverage': _is_set, '--cov-unit': _is_set, '--rep': _is_set,
-          '--min-neighbors': _is_set, '--auc1': _is_set, '--families': _is_set, '--family-sep': _is_set, '--hist': _is_set, '--bins': _is_set}
+          '--min-neighbors': _is_set, '--auc1': _is_set, '--families': _is_set, '--family-sep': _is_set, '--hist': _is_set, '--bins': _is_set,
+          '--zscore': bool, '--min-z': _is_set}
 # mode -> (what it does; for a mode that takes a score, what that score does; the flags it refuses, in the order they are named).
 # The modes are checked in this order.
 _MODES = {'--rbh': ('prints the reciprocal best hits of --dct and --db', 'ranks the hits',
@@ -2518,16 +2643,16 @@ _MODES = {'--rbh': ('prints the reciprocal best hits of --dct and --db', 'ranks 
                      '--min-coverage', '--cov-unit', '--rep', '--min-neighbors', '--auc1', '--hist')),
           '--tree': ('prints the single-linkage tree of --dct', 'orders the pairs',
                      ('--pair', '--db', '--cluster', '--assign', '--rank', '--linkage', '--level', '--no-whole', '--reps-out', '--domains',
-                      '--dom', '--db-dom', '--min-coverage', '--cov-unit', '--rep', '--min-neighbors', '--auc1', '--hist')),
+                      '--dom', '--db-dom', '--min-coverage', '--cov-unit', '--rep', '--min-neighbors', '--zscore', '--min-z', '--auc1', '--hist')),
           '--assign': ('places the proteins of --dct on a fixed set of representatives', None,
                        ('--pair', '--db', '--cluster', '--rank', '--domains', '--dom', '--db-dom', '--linkage', '--level', '--no-whole',
-                        '--min-coverage', '--cov-unit', '--rep', '--min-neighbors', '--auc1', '--hist')),
+                        '--min-coverage', '--cov-unit', '--rep', '--min-neighbors', '--zscore', '--min-z', '--auc1', '--hist')),
           '--auc1': ('measures the AUC1 and the top-1 rates of --dct', 'ranks the hits',
                      ('--pair', '--db', '--cluster', '--assign', '--rank', '--linkage', '--level', '--no-whole', '--reps-out', '--domains',
-                      '--dom', '--db-dom', '--min-coverage', '--cov-unit', '--rep', '--min-neighbors', '--hist')),
+                      '--dom', '--db-dom', '--min-coverage', '--cov-unit', '--rep', '--min-neighbors', '--zscore', '--min-z', '--hist')),
           '--hist': ('bins the scores of all pairs of --dct', 'bins the pairs',
                      ('--pair', '--db', '--cluster', '--assign', '--rank', '--linkage', '--level', '--no-whole', '--reps-out', '--domains',
-                      '--dom', '--db-dom', '--min-coverage', '--cov-unit', '--rep', '--min-neighbors', '--auc1'))}
+                      '--dom', '--db-dom', '--min-coverage', '--cov-unit', '--rep', '--min-neighbors', '--zscore', '--min-z', '--auc1'))}
 # the options that say where --auc1 and --hist find the family of a protein: exactly one of them with --auc1, at most one with --hist,
 # none without either
 _FAMILY_FLAGS = ('--families', '--family-sep')
@@ -2563,7 +2688,11 @@ class _Parser(argparse.ArgumentParser):
     ``--hist`` bins one score over all pairs of the file, the fifth mode of ``_MODES``: it refuses what ``--tree`` refuses and
     ``--auc1``, and the other four refuse it; its own score's cut-off is allowed and the other score's an error.  The family flags
     are optional with it -- at most one of the two, and ``C`` not empty -- and say which pairs are of one family.  ``--bins B`` is the
-    number of cut-offs of its table: 1 .. 1000, an error without ``--hist``."""
+    number of cut-offs of its table: 1 .. 1000, an error without ``--hist``.
+    ``--zscore`` adds the z-score of every hit of ``--db``, with or without ``--rbh``, and ``--min-z Z`` (which implies it) keeps the
+    selected lines whose z is not below Z: either is an error without ``--db``, beside ``--pair`` or ``--cluster``, and beside
+    ``--tree``, ``--assign``, ``--auc1`` and ``--hist`` (``_MODES``); both are absent from the namespace of a command line without
+    them."""
 
     def parse_known_args(self, args=None, namespace=None):
         ns, rest = super().parse_known_args(args, namespace)
@@ -2605,6 +2734,15 @@ class _Parser(argparse.ArgumentParser):
             for flag in _FAMILY_FLAGS:
                 if _GIVEN[flag](getattr(ns, _dest(flag), None)):
                     self.error(f'{flag} says which family a protein belongs to, for --auc1 to judge the hits by: it needs --auc1')
+        for flag, does in (('--zscore', 'places every hit of a database search in the background of its query'),
+                           ('--min-z', 'cuts the hits of a database search by their z-score')):
+            if _GIVEN[flag](getattr(ns, _dest(flag), None)):
+                if ns.pair:
+                    self.error(f'{flag} {does}: not with --pair')
+                if getattr(ns, 'cluster', False):
+                    self.error(f'{flag} {does}: not with --cluster')
+                if not ns.db:
+                    self.error(f'{flag} {does}: it needs --db')
         rbh = getattr(ns, 'rbh', None)
         names = getattr(ns, 'rep', None)
         if getattr(ns, 'assign', None) is None and getattr(ns, 'reps_out', None) is not None and not (
@@ -2770,6 +2908,16 @@ def build_parser() -> argparse.ArgumentParser:
                          '--min-domain X (--min-global Y with global) leaves the cut-offs below it out')
     ap.add_argument('--bins', type=int, metavar='B', default=argparse.SUPPRESS,
                     help=f'--hist: the number of cut-offs of the table, (B - 1) / B down to 0 (default {HIST_BINS}, at most {HIST_MAX_BINS})')
+    ap.add_argument('--zscore', action='store_true', default=argparse.SUPPRESS,
+                    help='--db, with or without --rbh: add the z-score of every hit as the last field of its line -- (mean - L1) / sigma '
+                         'of the hit\'s L1 among the L1s of the query against EVERY protein of --db under the ranking score (--rank; with '
+                         '--rbh its score, and two fields: the pair among the hits of the --dct protein over --db, then among those of '
+                         'the --db protein over --dct); positive = closer than the background, "-" where undefined (fewer than two '
+                         'proteins to compare with, or all at one distance).  z is relative to the database searched; a query that is '
+                         'itself in --db counts in its own background like any other protein')
+    ap.add_argument('--min-z', type=float, metavar='Z', default=argparse.SUPPRESS,
+                    help='--db: of the lines --top / --threshold (or --rbh) selected, print only those whose z-score is defined and not '
+                         'below Z -- with --rbh both of them (implies --zscore)')
     return ap
 
 
@@ -2783,9 +2931,12 @@ def main(argv=None):
     cover = {'min_coverage': min_coverage, 'cov_unit': getattr(args, 'cov_unit', 'residues')} if min_coverage is not None else {}
     auc1, hist = getattr(args, 'auc1', None), getattr(args, 'hist', None)
     family = {'families': getattr(args, 'families', None), 'family_sep': getattr(args, 'family_sep', None)}
+    min_z = getattr(args, 'min_z', None)
+    zscore = getattr(args, 'zscore', False) or min_z is not None
+    z = {'zscore': True, **({'min_z': min_z} if min_z is not None else {})} if zscore else {}
     report = Report(args.output, _header(hist_header(hist, any(v is not None for v in family.values())) if hist is not None else
                                          AUC1_HEADER if auc1 is not None else CLUSTER_HEADER if args.cluster or assign is not None else HEADER,
-                                         level, domains))
+                                         level, domains) + _z_header(zscore, getattr(args, 'rbh', None) is not None, args.rank))
     t_work = time.time()
     if hist is not None:
         hist_sim(args.dct, report, score=hist, bins=getattr(args, 'bins', HIST_BINS), min_domain=args.min_domain, min_global=args.min_global,
@@ -2796,13 +2947,13 @@ def main(argv=None):
         tree_sim(args.dct, report, score=args.tree, min_domain=args.min_domain, min_global=args.min_global)
     elif getattr(args, 'rbh', None) is not None:
         rbh_sim(args.dct, args.db, report, score=args.rbh, min_domain=args.min_domain, min_global=args.min_global, domains=bool(domains),
-                dom=dom, db_dom=db_dom)
+                dom=dom, db_dom=db_dom, **z)
     elif assign is not None:
         assign_sim(args.dct, assign, report, min_domain=args.min_domain, min_global=args.min_global, reps_out=reps_out)
     elif args.pair:
         pair_sim(args.dct, args.pair, args.pairfound, report, domains=bool(domains), dom=dom)
     elif args.db:
-        db_search(args.dct, args.db, args.top, args.threshold, report, rank=args.rank or 'global', domains=bool(domains), dom=dom, db_dom=db_dom)
+        db_search(args.dct, args.db, args.top, args.threshold, report, rank=args.rank or 'global', domains=bool(domains), dom=dom, db_dom=db_dom, **z)
     elif args.cluster:
         cluster_sim(args.dct, report, min_domain=args.min_domain, min_global=args.min_global, linkage=getattr(args, 'linkage', 'single'),
                     level=level, whole=not getattr(args, 'no_whole', False), dom=dom if level == 'domain' or cover else None,

@@ -634,6 +634,49 @@ def rect_best(tile: torch.Tensor, row0: int, col0: int, bound: int, state: BestS
         _launch(tile.device, 'dctfp_rect_best', *lead, state.best_row.data_ptr(), n_a, state.best_col.data_ptr(), n_b)
 
 
+MOMENT_LIMIT = 255 * 480 + 1                   # above every L1 of two int8 fingerprints of the widest kind (480 columns)
+
+
+class MomentState:
+    """The device arrays of the background moments of ``n_a`` x ``n_b`` proteins (``dctfp_rect_moments``): ``row`` (3, n_a) for the
+    proteins of A and ``col`` (3, n_b) for those of B, zeroed -- the planes count, sum and sum of squares of the L1s that counted.
+    int64 as torch has no uint64 arithmetic: a sum of squares of 2^63 or more shows negative here and is the same 64 bits.
+    ``rows=False`` / ``cols=False``: that side is None and ``rect_moments`` does not compute it."""
+
+    def __init__(self, n_a: int, n_b: int, rows: bool = True, cols: bool = True, device=None):
+        device = device if device is not None else _dev()
+        self.n_a, self.n_b = int(n_a), int(n_b)
+        self.row = torch.zeros((3, self.n_a), dtype=torch.int64, device=device) if rows else None
+        self.col = torch.zeros((3, self.n_b), dtype=torch.int64, device=device) if cols else None
+
+    def arrays(self, device):
+        """(n_a, n_b), the arrays checked."""
+        if self.row is None and self.col is None:
+            raise ValueError('a MomentState without rows and without cols has nothing to add to')
+        for t, n in ((self.row, self.n_a), (self.col, self.n_b)):
+            if t is not None and (t.dtype != torch.int64 or t.shape != (3, n) or not t.is_contiguous() or t.device != device):
+                raise ValueError('row / col must be contiguous int64 tensors of shape (3, n) on the device of the other arguments')
+        return self.n_a, self.n_b
+
+    def moments(self):
+        """(row, col): the numpy int64 arrays (3, n), None for a side the state does not have (one copy per side; the host waits)."""
+        return tuple(t.cpu().numpy() if t is not None else None for t in (self.row, self.col))
+
+
+def rect_moments(tile: torch.Tensor, row0: int, col0: int, state: MomentState, row_empty=None, col_empty=None, limit: int = MOMENT_LIMIT):
+    """Adds (1, x, x^2) to ``state.row[:, row0 + r]`` and to ``state.col[:, col0 + c]`` for every entry (r, c) of an L1 tile -- the full
+    rectangle, protein row0 + r of one file against protein col0 + c of another -- whose row and column are not flagged empty and
+    whose value x lies in 0 .. limit - 1 (``dctfp_rect_moments``).  ``limit`` excludes, it does not cap: ``protein_min``'s 0x7fffffff
+    and a negative value are left out, every other value counts raw.  The words are exact integers and add up over tiles and
+    calls; they do not depend on how the rectangle is cut into tiles or on the order of the calls."""
+    n_a, n_b = state.arrays(tile.device)
+    n_rows, n_cols, lead, _flags = _tri_filter_args(tile, row0, col0, limit, row_empty, col_empty, int(limit))
+    if (state.row is not None and row0 + n_rows > n_a) or (state.col is not None and col0 + n_cols > n_b):
+        raise IndexError('tile outside the proteins of the state')
+    if n_rows and n_cols:
+        _launch(tile.device, 'dctfp_rect_moments', *lead, _ptr(state.row), n_a, _ptr(state.col), n_b)
+
+
 def _node_arrays(tile: torch.Tensor, arrays) -> int:
     """n_nodes of the per-protein arrays beside a tile -- ``arrays`` = (tensor, dtype, name): contiguous 1-D device tensors of one
     length on the tile's device."""

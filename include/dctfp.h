@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define DCTFP_VERSION 115 /* 0.1.15: dctfp_tri_hist */
+#define DCTFP_VERSION 116 /* 0.1.16: dctfp_rect_moments */
 
 #define DCTFP_OK 0
 #define DCTFP_ERR_INVALID (-1) /* bad argument (null pointer, piece outside its sequence, ...) */
@@ -693,6 +693,32 @@ int dctfp_tri_tp_before(dctfp_ctx* ctx, const int32_t* tile, int64_t n_rows, int
 int dctfp_tri_hist(dctfp_ctx* ctx, const int32_t* tile, int64_t n_rows, int64_t n_cols, int64_t ld, int64_t row0, int64_t col0,
                    const uint8_t* row_empty, const uint8_t* col_empty, int32_t cap, int32_t bound, const int32_t* fam, int64_t n_nodes,
                    uint64_t* hist, void* stream);
+
+/* The moments of every protein's background (dct-sim --db --zscore: a z-score beside every hit, the place of its L1 in the L1s of
+ * the query against the whole database -- what DALI's Z-score and the E-values of BLAST, MMseqs2 and Foldseek tell their users).
+ * Entry (r, c) of an int32 tile of L1 values, at tile[r * ld + c], is the L1 of protein row0 + r of one file and protein col0 + c
+ * of another: the full rectangle, no diagonal.  An entry COUNTS unless its row is flagged in row_empty, its column in col_empty
+ * (device uint8, one per row / column of the tile, either may be NULL) or its value x has (uint32_t)x >= cap: cap is the EXCLUSION
+ * LIMIT here, not a ceiling -- a negative value and dctfp_protein_min's 0x7fffffff are left out, a value below cap counts raw.
+ * bound is not read (pass cap).  A counting entry adds (1, x, x * x) to
+ *     row_mom[k * n_a + row0 + r]   and   col_mom[k * n_b + col0 + c],   k = 0, 1, 2
+ * (device uint64, 8-byte aligned, 3 n_a resp. 3 n_b entries: the planes count, sum and sum of squares; the caller zeroes them
+ * before the first tile).  Either array may be NULL: that side is not computed, its n is not compared with the tile, and the
+ * other side pays nothing for it.  A loop of its own over the tile (plain 4-byte loads: any ld >= n_cols, a column view of a wider
+ * tensor included), jobs of 64 rows x 1024 columns; partial sums are reduced in the workgroup -- 32-bit sums, 64-bit squares --
+ * and sent with agent-scope relaxed 64-bit atomic adds, the only way the arrays are touched inside the launch: at most 3 per
+ * (row, 1024 columns) and 3 per (column, 64 rows), none for a count of 0.  Integer addition commutes: the words are exact, add up
+ * over tiles and over calls and do not depend on the order in which the device ran, on how the rectangle is cut into tiles or on
+ * the order of the calls.
+ * DCTFP_ERR_INVALID, with a message that starts with the export's name, for: a NULL ctx or tile; row_mom and col_mom both NULL; a
+ * negative count or offset or one of 2^31 or more; ld < n_cols; cap < 0 or above 16777216 (a wave's 32-bit sum of one row, 256
+ * entries, and a column's over a band must hold); n_a or n_b negative or >= 2^31; row0 + n_rows > n_a with row_mom, col0 + n_cols >
+ * n_b with col_mom (checked on the host: the kernel bounds no index); n x (cap - 1)^2 of 2^64 or more, n = max(n_b, col0 + n_cols)
+ * for row_mom and max(n_a, row0 + n_rows) for col_mom (a sum of squares must fit its word); a tile off a 4-byte or an array off an
+ * 8-byte boundary.  n_rows or n_cols of 0: nothing to do. */
+int dctfp_rect_moments(dctfp_ctx* ctx, const int32_t* tile, int64_t n_rows, int64_t n_cols, int64_t ld, int64_t row0, int64_t col0,
+                       const uint8_t* row_empty, const uint8_t* col_empty, int32_t cap, int32_t bound, uint64_t* row_mom, int64_t n_a,
+                       uint64_t* col_mom, int64_t n_b, void* stream);
 
 /* query_db's search (src/query_db.py:75-87: a flat FAISS index forced to METRIC_L1 at :76, index.search at :87) without a
  * distance matrix: for query rows q (nq x d, row stride ldq) and database rows b (nb x d, stride ldb), int8 on the device, each
