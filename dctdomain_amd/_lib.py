@@ -65,7 +65,7 @@ EXPORTS = ('dctfp_version', 'dctfp_last_error', 'dctfp_create', 'dctfp_destroy',
            'dctfp_greedy_decide', 'dctfp_greedy_tri_mark', 'dctfp_greedy_pairs_mark',
            'dctfp_rows_link', 'dctfp_rows_assign', 'dctfp_tri_nearest', 'dctfp_tree_hook', 'dctfp_rect_best', 'dctfp_protein_cover',
            'dctfp_label_sums', 'dctfp_tri_degree', 'dctfp_tri_link_core', 'dctfp_tri_first_fp', 'dctfp_tri_tp_before',
-           'dctfp_tri_hist', 'dctfp_rect_moments')
+           'dctfp_tri_hist', 'dctfp_rect_moments', 'dctfp_pair_row_best', 'dctfp_pair_map_lines')
 
 #: what the five exports that scan an L1 tile of the triangle (and dctfp_rect_best and dctfp_label_sums, on a rectangle) start with: the context, then the library's TriTile (tile, n_rows, n_cols, ld, row0, col0,
 #: row_empty, col_empty, cap, bound) -- ``similarity._tri_filter_args`` makes the values
@@ -197,6 +197,9 @@ def _configure(lib):
                                          C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
         lib.dctfp_pair_domain_lines.argtypes = [C.c_void_p, C.c_int64] + [C.c_void_p] * 8 + [C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
                                                 C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
+        lib.dctfp_pair_row_best.argtypes = lib.dctfp_pair_min.argtypes[:12] + [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.dctfp_pair_map_lines.argtypes = lib.dctfp_pair_domain_lines.argtypes[:-1] + [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                                                        C.c_int32, C.c_void_p, C.c_void_p]
         lib.dctfp_tri_link.argtypes = _TRI_TILE + [C.c_void_p, C.c_int64, C.c_void_p]
         lib.dctfp_link_pairs.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]
         lib.dctfp_cluster_labels.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]

@@ -2684,6 +2684,22 @@ int dctfp_pair_argmin(dctfp_ctx* ctx, const int32_t* pairs, int64_t n_pairs, con
                          out_arg_b, stream_v);
 } DCTFP_GUARD("dctfp_pair_argmin")
 
+int dctfp_pair_row_best(dctfp_ctx* ctx, const int32_t* pairs, int64_t n_pairs, const int8_t* a, int64_t lda, const int64_t* idx_a, int64_t npa,
+                        const int8_t* b, int64_t ldb, const int64_t* idx_b, int64_t npb, int32_t d, const int64_t* row_off, int64_t out_len,
+                        int32_t* out_l1, int32_t* out_arg, void* stream_v) try {
+    if (!ctx || !pairs || !a || !idx_a || !b || !idx_b || !row_off || !out_l1 || !out_arg)
+        return fail(DCTFP_ERR_INVALID, "dctfp_pair_row_best: NULL argument");
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    if (n_pairs < 0 || npa < 0 || npb < 0 || d < 1 || lda < d || ldb < d || out_len < 0) return fail(DCTFP_ERR_INVALID, "dctfp_pair_row_best: bad shape");
+    if (npa > 0x7fffffff || npb > 0x7fffffff) return fail(DCTFP_ERR_LIMIT, "dctfp_pair_row_best: more than 2^31 - 1 proteins on a side");
+    if ((n_pairs + 3) / 4 > 0x7fffffff) return fail(DCTFP_ERR_LIMIT, "dctfp_pair_row_best: too many pairs per call");
+    if (n_pairs == 0) return DCTFP_OK;
+    HIP_TRY(hipSetDevice(ctx->device));
+    launch_pair_row_best(pairs, n_pairs, a, lda, idx_a, npa, b, ldb, idx_b, npb, d, row_off, out_len, out_l1, out_arg, (hipStream_t)stream_v);
+    HIP_TRY(hipGetLastError());
+    return DCTFP_OK;
+} DCTFP_GUARD("dctfp_pair_row_best")
+
 int dctfp_protein_min(dctfp_ctx* ctx, const int8_t* a, int64_t lda, const int64_t* idx_a, int64_t npa, const int8_t* b, int64_t ldb,
                       const int64_t* idx_b, int64_t npb, int32_t d, int32_t* out, int64_t ldo, void* stream_v) try {
     if (!ctx || !a || !idx_a || !b || !idx_b || !out) return fail(DCTFP_ERR_INVALID, "dctfp_protein_min: NULL argument");
@@ -2857,6 +2873,28 @@ int dctfp_pair_domain_lines(dctfp_ctx* ctx, int64_t n_lines, const int32_t* pi, 
     return pair_lines_call("dctfp_pair_domain_lines", ctx, n_lines, pi, pj, mn, last, la, lb, ids, id_off, n_ids, labels, label_off, n_labels,
                            table, line_off, out, out_bytes, stream_v);
 } DCTFP_GUARD("dctfp_pair_domain_lines")
+
+int dctfp_pair_map_lines(dctfp_ctx* ctx, int64_t n_lines, const int32_t* pi, const int32_t* pj, const int32_t* mn, const int32_t* last,
+                         const int32_t* la, const int32_t* lb, const uint8_t* ids, const int64_t* id_off, int64_t n_ids, const uint8_t* labels,
+                         const int64_t* label_off, int64_t n_labels, const char* table, const int64_t* line_off, uint8_t* out,
+                         int64_t out_bytes, const int64_t* row_off, int64_t n_rows, const int32_t* row_l1, const int32_t* row_arg,
+                         const int64_t* first_row, int32_t bound, int64_t* out_count, void* stream_v) try {
+    if (!ctx || !pi || !pj || !mn || !last || !la || !lb || !ids || !id_off || !labels || !label_off || !table || !row_off || !row_l1 ||
+        !row_arg || !first_row || (!out_count && (!line_off || !out)))
+        return fail(DCTFP_ERR_INVALID, "dctfp_pair_map_lines: NULL argument");
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    if (n_lines < 0 || n_ids < 0 || n_labels < 0 || out_bytes < 0 || n_rows < 0) return fail(DCTFP_ERR_INVALID, "dctfp_pair_map_lines: bad shape");
+    // (a matched row prints the score of its L1 from the table: no bound at or above similarity 0, dctfp_pair_argmin's "no pair")
+    if (bound >= 17000) return fail(DCTFP_ERR_INVALID, "dctfp_pair_map_lines: the bound must be below 17000");
+    // (dctfp_pair_lines' grid: sixteen lanes per line in 256-thread workgroups)
+    if (n_lines > (int64_t)1 << 31) return fail(DCTFP_ERR_LIMIT, "dctfp_pair_map_lines: more than 2^31 lines per call");
+    if (n_lines == 0) return DCTFP_OK;
+    HIP_TRY(hipSetDevice(ctx->device));
+    launch_pair_map_lines(n_lines, pi, pj, mn, last, la, lb, ids, id_off, n_ids, labels, label_off, n_labels, table, first_row, row_off, n_rows,
+                          row_l1, row_arg, bound, line_off, out, out_bytes, out_count, (hipStream_t)stream_v);
+    HIP_TRY(hipGetLastError());
+    return DCTFP_OK;
+} DCTFP_GUARD("dctfp_pair_map_lines")
 
 int dctfp_tri_link(dctfp_ctx* ctx, const int32_t* tile, int64_t n_rows, int64_t n_cols, int64_t ld, int64_t row0, int64_t col0,
                    const uint8_t* row_empty, const uint8_t* col_empty, int32_t cap, int32_t bound, int32_t* parent, int64_t n_nodes,

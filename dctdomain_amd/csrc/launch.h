@@ -167,6 +167,18 @@ void launch_pair_domain_lines(int64_t n_lines, const int32_t* pi, const int32_t*
                               const int64_t* label_off, int64_t n_labels, const char* table, const int64_t* line_off, uint8_t* out,
                               int64_t out_bytes, hipStream_t stream);
 
+// dct-sim --domain-map (k_map.hip): per pair, every fingerprint row's nearest row of the other protein (dctfp_pair_row_best), and
+// dctfp_pair_domain_lines' line with the map of the rows within `bound` behind it (dctfp_pair_map_lines; out_count non-NULL: the
+// count pass, every line's byte length and no text)
+void launch_pair_row_best(const int32_t* pairs, int64_t n_pairs, const int8_t* a, int64_t lda, const int64_t* idx_a, int64_t npa,
+                          const int8_t* b, int64_t ldb, const int64_t* idx_b, int64_t npb, int d, const int64_t* row_off, int64_t out_len,
+                          int32_t* out_l1, int32_t* out_arg, hipStream_t stream);
+void launch_pair_map_lines(int64_t n_lines, const int32_t* pi, const int32_t* pj, const int32_t* mn, const int32_t* last, const int32_t* la,
+                           const int32_t* lb, const uint8_t* ids, const int64_t* id_off, int64_t n_ids, const uint8_t* labels,
+                           const int64_t* label_off, int64_t n_labels, const char* table, const int64_t* first_row, const int64_t* row_off,
+                           int64_t n_rows, const int32_t* row_l1, const int32_t* row_arg, int32_t bound, const int64_t* line_off, uint8_t* out,
+                           int64_t out_bytes, int64_t* out_count, hipStream_t stream);
+
 // single-linkage clusters at a cut-off (k_cluster.hip): unions of a tile's surviving entries / of a list of pairs in a lock-free
 // union-find over parent[0 .. n_nodes), and the roots of all nodes afterwards (two launches: flatten, then read)
 void launch_tri_link(const TriTile& t, int32_t* parent, hipStream_t stream);

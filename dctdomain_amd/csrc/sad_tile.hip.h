@@ -47,6 +47,10 @@ __device__ inline uint32_t load_bytes4(const int8_t* p, int n_valid) {  // n_val
     return v;
 }
 
+// One step of the sum without the tile: s + the four byte differences of two sign-flipped dwords (v_sad_u8), for a kernel that
+// contracts one fingerprint pair per wave straight from global memory (k_map.hip's pair_row_best_kernel).
+__device__ inline uint32_t sad_dword(uint32_t x, uint32_t y, uint32_t s) { return __builtin_amdgcn_sad_u8(x, y, s); }
+
 // Which fill two sets of rows can take = what all their rows' addresses are multiples of: 16 (and rows less than 2^24 bytes
 // apart: that fill addresses a tile's rows with 32-bit lane offsets, 128 * ld < 2^31), 4 or 1.  dctfp_l1_matrix sends 4 and 1 to
 // l1_matrix_kernel<true / false>; dctfp_protein_min and dctfp_l1_knn refuse them.

@@ -6,7 +6,7 @@ fingerprints (``-dct.npz``), with the L1 distances computed on the GPU.
                                     [--min-coverage C [--cov-unit {residues,domains}]]
                                     [--cluster [--linkage {single,greedy}] [--level {protein,domain} [--no-whole]] [--rep {first,medoid}]
                                      [--min-neighbors M]]
-                                    [--domains]
+                                    [--domains] [--domain-map [X]]
                                     [--dom X.dom] [--db-dom Y.dom]
     python -m dctdomain_amd.dct_sim --dct NEW-dct.npz --assign REPS-dct.npz --min-domain X [--min-global Y] [--reps-out ALL-dct.npz]
                                     [--output F]
@@ -121,6 +121,15 @@ of ``dctfp_pair_min`` (the same reads, the position of the minimum kept); the al
 whatever the cut-offs and composes its lines with ``dctfp_pair_domain_lines``.  A fingerprint prints as its 1-based index within
 the protein, or, with the ``.dom`` file of the npz (``--dom`` / ``--db-dom``), as the residue ranges ``make_db`` wrote there
 (``whole`` for the unnamed whole-protein row).
+``--domain-map [X]`` (not in the reference; implies ``--domains``) adds one more field behind those two: every matched domain pair
+of the line, not only the best -- ``side/side``, the fingerprints of prot1 that have a counterpart in prot2, then those of prot2
+that have one in prot1, each as ``label=label of its nearest fingerprint of the other protein:similarity``, joined by ``;`` (``-``
+for none).  A fingerprint is matched when that L1 is at most ``map_bound``: ``sim_bound(X)`` -- X the option's value, else
+``--min-domain``, else 0.25 -- and never an L1 of similarity 0; with ``--min-domain`` alone these are the fingerprints
+``--min-coverage`` counts.  ``dctfp_pair_row_best`` keeps every row's nearest row of the other protein for the printed pairs
+(``dctfp_pair_argmin``'s contraction, both ways); ``--pair``, ``--db`` and ``--rbh`` compose the field on the host
+(``map_field``), the all-against-all on the device in two passes of one kernel (``dctfp_pair_map_lines``: the lines' lengths,
+then the text at their cumulative sum).
 Scores are formed from the integer L1 values with the reference's arithmetic (int64 / 17000 in float64), so the printed
 floats are identical."""
 
@@ -137,7 +146,8 @@ from .similarity import (GREEDY_NONE, PROTEIN_MIN_MAX_D, GreedyState, LineIds, T
                          greedy_decide, greedy_pairs_mark, greedy_tri_mark, l1_matrix, link_pairs, pair_argmin, pair_argmin_device, pair_line_offsets, pair_lines, pair_min, pair_min_device, protein_cover, protein_min,
                          rows_assign, rows_link, sim_lines, threshold_select, to_device_int8, tri_filter_count, tri_filter_fill, tri_link,
                          TREE_MAX_NODES, TreeState, tree_hook, tri_nearest, BestState, rect_best, label_sums, NEAREST_NONE, tri_degree,
-                         tri_link_core, BEST_NONE, tri_first_fp, tri_tp_before, tri_hist, MomentState, rect_moments)
+                         tri_link_core, BEST_NONE, tri_first_fp, tri_tp_before, tri_hist, MomentState, rect_moments, pair_row_best,
+                         pair_row_best_device, pair_row_offsets, pair_map_line_lengths, pair_map_lines)
 
 L1_FULL_SCALE = 17000      # src/dct-sim.py:24
 HEADER = '#prot1 prot2 sim-domain sim-global'
@@ -146,6 +156,8 @@ DOMAIN_HEADER = HEADER + ' dom1 dom2'      # --domains
 DOMAIN_CLUSTER_HEADER = CLUSTER_HEADER + ' dom1 dom2'      # --cluster --level domain
 NO_DOMAIN = '-'                            # no fingerprint pair scores above 0
 WHOLE = 'whole'                            # the whole-protein row a .dom file leaves unnamed
+MAP_COLUMN = ' domain-map'                 # --domain-map: what it adds to DOMAIN_HEADER
+MAP_SIMILARITY = 0.25                      # ... and the similarity from which a row is matched where neither it nor --min-domain says
 
 
 def _z_spread(n: int, s1: int, s2: int):
@@ -289,6 +301,56 @@ def _labels_of(sid, idx, dom_path: str = None) -> list:
 
 def _label(labels, first_row: int, arg: int) -> str:
     return NO_DOMAIN if arg < 0 else labels[first_row + arg]
+
+
+def map_bound(x=None, min_domain=None) -> int:
+    """B of ``--domain-map``: a fingerprint row is matched when its smallest L1 to the rows of the other protein is at most B =
+    min(``sim_bound(X)``, 16999) -- a similarity of 0 never matches, ``NO_DOMAIN``'s rule.  X = ``x`` where a value is given (not
+    None, not the bare flag's True), else ``min_domain`` where that is given, else MAP_SIMILARITY.  With X = ``--min-domain`` the
+    matched rows are the rows ``--min-coverage`` counts."""
+    given = x is not None and x is not True
+    return min(sim_bound(x if given else min_domain if min_domain is not None else MAP_SIMILARITY), L1_FULL_SCALE - 1)
+
+
+def map_entries(l1, arg, bound: int) -> list:
+    """One side of a domain map: [(row, counterpart, L1)] of the rows whose ``l1`` is at most ``bound``, in row order, from one
+    protein's slice of ``pair_row_best``'s (l1, arg)."""
+    return [(r, int(c), int(v)) for r, (v, c) in enumerate(zip(l1, arg)) if 0 <= v <= bound]
+
+
+def domain_map(dct_i: np.ndarray, dct_j: np.ndarray, x: float = MAP_SIMILARITY) -> tuple:
+    """(rows of ``dct_i`` matched by ``dct_j``, rows of ``dct_j`` matched by ``dct_i``), each a list of (row, counterpart, L1): every
+    row's nearest row of the other set (ties to the lowest) where that L1 is at most ``map_bound(x)``.  ``best_domain_pair``'s pair
+    is the first entry of the smallest L1 of the first list."""
+    k = dct_i.shape[0]
+    _, l1, arg = pair_row_best(dct_i, [0, k], dct_j, [0, dct_j.shape[0]], [(0, 0)])
+    bound = map_bound(x)
+    return map_entries(l1[:k], arg[:k], bound), map_entries(l1[k:], arg[k:], bound)
+
+
+def map_field(first, second, labels_i, labels_j, score=None) -> str:
+    """The field ``--domain-map`` adds to a result line: ``side/side``, the first side the entries of ``first`` (rows of prot1
+    against prot2), the second those of ``second`` (rows of prot2 against prot1); a side is ``-`` or its entries
+    ``label=label of the counterpart:score`` joined by ``;``.  ``labels_i`` / ``labels_j``: the labels of the rows of the two
+    proteins; ``score``: the text of an L1 -- by default the mode's own DCTdomain text outside the all-against-all,
+    ``str(_sim1(L1))``; the all-against-all prints ``score_table()``'s five characters."""
+    score = score or (lambda l1: str(_sim1(l1)))
+
+    def side(entries, own, other):
+        return ';'.join(f'{own[r]}={other[c]}:{score(v)}' for r, c, v in entries) or NO_DOMAIN
+    return f'{side(first, labels_i, labels_j)}/{side(second, labels_j, labels_i)}'
+
+
+def _map_fields(off, l1, arg, bound: int, pairs, labels, first_row, db_labels, db_first_row) -> list:
+    """``map_field`` of every pair (i, j) of ``pairs`` from ``pair_row_best``'s arrays: protein i's rows are ``labels`` from
+    ``first_row[i]``, protein j's ``db_labels`` from ``db_first_row[j]``."""
+    out = []
+    for p, (i, j) in enumerate(pairs):
+        a0, a1, b0, b1 = int(first_row[i]), int(first_row[i + 1]), int(db_first_row[j]), int(db_first_row[j + 1])
+        mid = int(off[p]) + a1 - a0
+        out.append(map_field(map_entries(l1[off[p]:mid], arg[off[p]:mid], bound), map_entries(l1[mid:off[p + 1]], arg[mid:off[p + 1]], bound),
+                             labels[a0:a1], db_labels[b0:b1]))
+    return out
 
 
 COV_UNITS = ('residues', 'domains')
@@ -608,6 +670,30 @@ def pair_scores(fps, idx, pairs, max_rows: int = None, domains: bool = False):
     return tuple(out)
 
 
+def _scatter_rows(out, off, sel, part_off, parts):
+    """The ragged results ``parts`` of the pairs ``sel`` (rows of pair sel[k] at [part_off[k], part_off[k + 1])) to their places in
+    the arrays ``out``, where pair p lies at [off[p], off[p + 1])."""
+    to = np.repeat(off[sel] - part_off[:-1], np.diff(part_off)) + np.arange(part_off[-1])
+    for o, v in zip(out, parts):
+        o[to] = v
+
+
+def pair_row_bests(fps, idx, pairs, max_rows: int = None):
+    """(row_off, l1, arg) of ``pair_row_best`` for the pairs (protein i, protein j) of one npz, in ``pair_scores``' chunks: only the
+    fingerprints of the proteins the pairs name go to the device, at most ``max_rows`` of them at a time."""
+    pairs = np.asarray(pairs, dtype=np.int64).reshape(-1, 2)
+    off = pair_row_offsets(idx, idx, pairs)
+    out = np.full(off[-1], 0x7fffffff, dtype=np.int64), np.full(off[-1], -1, dtype=np.int64)
+    for k0, k1 in _pair_chunks(idx, pairs, max_rows or ProteinSearch.COL_ROWS):
+        proteins, local = np.unique(pairs[k0:k1], return_inverse=True)
+        rows, sub_idx = _compact(fps, idx, proteins)
+        if len(rows):
+            dev = to_device_int8(rows)
+            part_off, *parts = pair_row_best(dev, sub_idx, dev, sub_idx, local.reshape(-1, 2))
+            _scatter_rows(out, off, np.arange(k0, k1), part_off, parts)
+    return (off,) + out
+
+
 class FilteredPairs:
     """all_sim's pairs whose scores are not below cut-offs -- DCTdomain >= ``min_domain`` and DCTglobal >= ``min_global``, either
     may be None -- without forming the others: ``AllPairs``' output with lines removed.  A cut-off is the integer bound
@@ -638,7 +724,13 @@ class FilteredPairs:
     ``coverage_need(W_p, min_coverage)`` and likewise for q.  The tile is then always DCTdomain's and comes from ``protein_cover``,
     which writes 0x7fffffff for the pairs that fail: the filter, the union-find and the greedy rounds read it as they read
     ``protein_min``'s, and ``min_global`` is applied to the survivors' last-row L1.  At a bound of 17000 every row is matched and
-    below 0 none is: the coverage then changes nothing and is not computed."""
+    below 0 none is: the coverage then changes nothing and is not computed.
+
+    ``with_map(bound)`` (``--domain-map``; needs ``labels``) adds the domain map to every line: after step 3, for the pairs that are
+    printed and no others, ``pair_row_best_device`` gives every row's nearest row of the other protein, and step 4 becomes two
+    passes of ``pair_map_lines`` -- the byte length of every line, a cumulative sum on the device, then the text.  The ranges of
+    rows are then sized by an upper bound of a line with its map: every row of both proteins matched, each entry with the longest
+    label of the file as its counterpart."""
 
     TEXT_BYTES = 1 << 28    # text of one range of rows
     COL_ROWS = 1 << 22      # fingerprints on the device at a time (the whole file stays there if it fits)
@@ -653,6 +745,7 @@ class FilteredPairs:
         self.bound_global = L1_FULL_SCALE if min_global is None else sim_bound(min_global)
         self.route = 'global' if self.bound_global < L1_FULL_SCALE else 'domain'
         self.cover = None                                       # (row weights, protein needs) where a coverage can exclude a pair
+        self.map_l1 = None                                      # the bound of the domain map where the lines carry one
         if min_coverage is not None:
             if min_domain is None:
                 raise ValueError('min_coverage needs min_domain: it counts the fingerprints within that cut-off')
@@ -673,6 +766,22 @@ class FilteredPairs:
             self.cover = (w.astype(np.int32), coverage_need(W, min_coverage).astype(np.int32))
             self.route = 'domain'
         return self
+
+    def with_map(self, bound: int):
+        """Adds the domain map of the class text to a job that has ``labels``: ``bound`` = ``map_bound`` of the run.  Returns the job."""
+        if self.row_labels is None:
+            raise ValueError('a domain map names fingerprint rows: it needs labels')
+        if not -1 <= int(bound) < L1_FULL_SCALE:
+            raise ValueError('the bound of a domain map is an L1 of similarity above 0: at most 16999')
+        self.map_l1 = int(bound)
+        return self
+
+    def _map_room(self) -> np.ndarray:
+        """Per protein, an upper bound of what its rows add to the map of a line: every row matched, each entry its own label, the
+        longest label of the file, ``=``, ``:``, five characters of score and a separator."""
+        lens = np.fromiter((len(f'{s}'.encode('utf8')) for s in self.row_labels), dtype=np.int64, count=len(self.row_labels))
+        own = np.concatenate([[0], np.cumsum(lens)])[self.idx]
+        return np.diff(own) + np.diff(self.idx) * (int(lens.max(initial=0)) + 8) + 1
 
     def stripes(self):
         """[i0, i1) over rows 0 .. n - 2: as many rows as keep rows x later proteins within TILE_INTS and the rows' fingerprints
@@ -772,22 +881,28 @@ class FilteredPairs:
         return tuple(torch.as_tensor(v.astype(np.int32), device=pi.device)
                      for v in pair_scores(self.fps, self.idx, pairs.cpu().numpy(), self.COL_ROWS, domains=domains))
 
-    def chunks(self):
+    def chunks(self, rows: _DeviceRows = None):
         """Yields device int32 tensors (i, j, min L1, last L1) of the surviving pairs, range of rows by range, in output order; with
-        ``labels`` also (arg_i, arg_j), the rows of the minimum within the two proteins (-1: none)."""
+        ``labels`` also (arg_i, arg_j), the rows of the minimum within the two proteins (-1: none).  ``rows``: as in ``tiles``."""
         n = len(self.idx) - 1
         if n < 2 or min(self.bound_domain, self.bound_global) < 0:
             return
         id_lens = np.fromiter((len(f'{s}'.encode('utf8')) for s in self.sid), dtype=np.int64, count=n)
         longest = int(id_lens.max())
+        line = id_lens + 14 + longest                           # (a line of row i is at most this long)
+        if self.map_l1 is not None:                             # (... and with its map: the two label fields, " ", "/", both sides)
+            side = self._map_room()
+            label = max((len(f'{s}'.encode('utf8')) for s in self.row_labels), default=0)
+            line = line + 2 * max(label, len(NO_DOMAIN)) + 4 + side + int(side.max())
         bound = self.bound
-        rows = self.device_rows()
+        if rows is None:
+            rows = self.device_rows()
         for i0, i1, tile, flags in self.tiles(rows):
             col0 = i0 + 1
             count_dev = tri_filter_count(tile, i0, col0, bound, *flags)
             count = count_dev.cpu().numpy().astype(np.int64)
-            # ranges of rows by the text they can make: count x (len_i + 14 + the longest id)
-            room = np.concatenate([[0], np.cumsum(count * (id_lens[i0:i1] + 14 + longest))])
+            # ranges of rows by the text they can make: count x the longest line of the row
+            room = np.concatenate([[0], np.cumsum(count * line[i0:i1])])
             r0 = 0
             while r0 < i1 - i0:
                 r1 = min(i1 - i0, max(r0 + 1, int(np.searchsorted(room, room[r0] + self.TEXT_BYTES, 'right')) - 1))
@@ -815,12 +930,23 @@ class FilteredPairs:
         both = np.concatenate(parts, axis=1) if parts else np.zeros((width, 0), dtype=np.int64)
         return tuple(both[k] for k in range(width))
 
+    def _row_best_of(self, pi, pj, rows: _DeviceRows):
+        """Device (row_off int64, l1 int32, arg int32) of ``pair_row_best_device`` for the pairs (pi[k], pj[k]) (device int32): on
+        the file where it stays on the device, else ``pair_row_bests``' chunks, copied back -- ``_scores_of``'s two routes."""
+        import torch
+        pairs = torch.stack([pi, pj], dim=1).contiguous()
+        if rows.resident is not None:
+            return pair_row_best_device(rows.resident, rows.idx_dev, rows.resident, rows.idx_dev, pairs)
+        off, l1, arg = pair_row_bests(self.fps, self.idx, pairs.cpu().numpy(), self.COL_ROWS)
+        return (torch.as_tensor(off, device=pi.device),) + tuple(torch.as_tensor(v.astype(np.int32), device=pi.device) for v in (l1, arg))
+
     def write(self, sink):
         """Calls ``sink(memoryview)`` with the text of each range of rows that has any, in order."""
         out = TextStream(sink, room=lambda nbytes: max(nbytes, 1 << 16))
         lines = None
-        for chunk in self.chunks():
-            lines = lines or _PairText(self, out, chunk[0].device)
+        rows = self.device_rows() if self.map_l1 is not None else None    # (the map reads the fingerprints of the printed pairs again)
+        for chunk in self.chunks(rows):
+            lines = lines or _PairText(self, out, chunk[0].device, rows)
             lines.write(*chunk)                                 # (the previous range goes out while the device works on this one)
         out.close()
 
@@ -828,11 +954,14 @@ class FilteredPairs:
 class _PairText:
     """The pair lines of one ``write`` of a ``FilteredPairs``: the ids, the score table and, with ``row_labels``, the label ids and
     every protein's first row go to the device once; ``write`` composes the lines of one list of pairs there (step 4 of the class
-    text) and hands them to the stream."""
+    text) and hands them to the stream.  With a domain map (``job.map_l1``; ``rows`` = the job's ``device_rows()``) the lines come
+    from ``pair_map_lines`` at the cumulative sum of ``pair_map_line_lengths``."""
 
-    def __init__(self, job, out: TextStream, dev):
+    def __init__(self, job, out: TextStream, dev, rows: _DeviceRows = None):
         import torch
         self.out = out
+        self.job, self.rows = job, rows
+        self.idx_dev = torch.as_tensor(job.idx, device=dev) if job.map_l1 is not None else None
         self.ids = LineIds([f'{s}' for s in job.sid])
         self.table = torch.as_tensor(score_table(), device=dev)
         self.labels = self.first_row = None
@@ -847,6 +976,16 @@ class _PairText:
         if self.labels is not None:
             la, lb = (torch.where(arg >= 0, self.first_row[p.long()] + arg, torch.full_like(arg, self.none)).contiguous()
                       for p, arg in zip((pi, pj), args))
+        if self.job.map_l1 is not None:
+            best = self.job._row_best_of(pi, pj, self.rows)
+            common = (pi, pj, mn, last, la, lb, self.ids, self.labels, self.table, self.idx_dev, *best, self.job.map_l1)
+            off = torch.zeros(pi.numel() + 1, dtype=torch.int64, device=pi.device)
+            torch.cumsum(pair_map_line_lengths(*common), 0, out=off[1:])
+            nbytes = int(off[-1])
+            text = torch.empty(nbytes, dtype=torch.uint8, device=pi.device)
+            pair_map_lines(*common, off, text)
+            self.out.hand_over(text, nbytes)
+            return
         off = pair_line_offsets(pi, pj, self.ids, la, lb, self.labels)
         nbytes = int(off[-1])
         text = torch.empty(nbytes, dtype=torch.uint8, device=pi.device)
@@ -2162,6 +2301,36 @@ class ProteinSearch:
                     o[sel] = v
         return tuple(out)
 
+    def _pair_row_best(self, query_fps, qidx, q_of, db_of):
+        """(row_off, l1, arg) of ``pair_row_best`` for the pairs (query q_of[k], database protein db_of[k]), in ``_pair_scores``'
+        chunks: per database group, per chunk of queries."""
+        q_of, db_of = np.asarray(q_of, dtype=np.int64), np.asarray(db_of, dtype=np.int64)
+        off = pair_row_offsets(qidx, self.idx, np.stack([q_of, db_of], axis=1))
+        out = np.full(off[-1], 0x7fffffff, dtype=np.int64), np.full(off[-1], -1, dtype=np.int64)
+        for g, (p0, p1) in enumerate(self.groups):
+            in_g = np.flatnonzero((db_of >= p0) & (db_of < p1))
+            if len(in_g) == 0:
+                continue
+            rows, sub_idx, _, _ = self._group(g, need_rows=True)
+            if rows is None:
+                continue
+            for c0, c1 in _protein_groups(qidx, self.COL_ROWS):
+                sel = in_g[(q_of[in_g] >= c0) & (q_of[in_g] < c1)]
+                if len(sel) == 0 or qidx[c1] == qidx[c0]:
+                    continue
+                qrows = to_device_int8(query_fps[qidx[c0]:qidx[c1]])
+                pairs = np.stack([q_of[sel] - c0, db_of[sel] - p0], axis=1)
+                part_off, *parts = pair_row_best(qrows, qidx[c0:c1 + 1] - qidx[c0], rows, sub_idx, pairs)
+                _scatter_rows(out, off, sel, part_off, parts)
+        return (off,) + out
+
+    def map_fields(self, query_fps, qidx, q_of, db_of, bound: int, labels, db_labels) -> list:
+        """``map_field`` of the pairs (query q_of[k], database protein db_of[k]): rows matched within ``bound``, named by the two
+        files' ``fingerprint_labels``."""
+        qidx = np.asarray(qidx, dtype=np.int64)
+        off, l1, arg = self._pair_row_best(query_fps, qidx, q_of, db_of)
+        return _map_fields(off, l1, arg, bound, list(zip(np.asarray(q_of).tolist(), np.asarray(db_of).tolist())), labels, qidx, db_labels, self.idx)
+
 
 class ReciprocalBest(ProteinSearch):
     """The reciprocal best hits of two files, A (``--dct``) and B (``--db``): the first-pass ortholog call.  key(a, b) =
@@ -2240,23 +2409,28 @@ class ReciprocalBest(ProteinSearch):
         a = a[best_a[best_b[a]] == a]
         return a, best_b[a], key[a]
 
-    def lines(self, domains: bool = False, labels=None, db_labels=None, min_z: float = None) -> list:
+    def lines(self, domains: bool = False, labels=None, db_labels=None, min_z: float = None, map_l1: int = None) -> list:
         """``db_search``'s lines of the reciprocal best hits, in ascending order of a.  ``domains``: with the domain pair behind
-        DCTdomain, named by ``labels`` / ``db_labels`` (``fingerprint_labels`` of the two files; default: the 1-based indices).  After
+        DCTdomain, named by ``labels`` / ``db_labels`` (``fingerprint_labels`` of the two files; default: the 1-based indices).
+        ``map_l1`` (``map_bound``; implies ``domains``): then the domain map of the pair (``map_field``).  After
         ``with_zscore``: every line ends with `` z_a z_b`` (``zscores``), and ``min_z`` keeps the lines whose two z are defined and
         not below it."""
         a, b, _ = self.pairs()
         if len(a) == 0:
             return []
+        domains = domains or map_l1 is not None
         mn, last, *args = self._pair_scores(self.fps_a, self.idx_a, a, b, domains)
         if domains:
             labels = labels if labels is not None else fingerprint_labels(self.sid_a, self.idx_a)
             db_labels = db_labels if db_labels is not None else fingerprint_labels(self.sid_b, self.idx)
+        maps = self.map_fields(self.fps_a, self.idx_a, a, b, map_l1, labels, db_labels) if map_l1 is not None else None
         out = []
         z_a, z_b = self.zscores(a, b, mn if self.score == 'domain' else last) if self.zscore else (None, None)
         for k, (i, j, m, l) in enumerate(zip(a.tolist(), b.tolist(), mn, last)):
             maxs, s = _scores(m, l)
             tail = f' {_label(labels, self.idx_a[i], args[0][k])} {_label(db_labels, self.idx[j], args[1][k])}' if domains else ''
+            if maps is not None:
+                tail += f' {maps[k]}'
             if self.zscore:
                 if min_z is not None and not _z_passes(min_z, z_a[k], z_b[k]):
                     continue
@@ -2264,9 +2438,9 @@ class ReciprocalBest(ProteinSearch):
             out.append(f'{self.sid_a[i]} {self.sid_b[j]} {maxs} {s}{tail}')
         return out
 
-    def write(self, report, domains: bool = False, labels=None, db_labels=None, min_z: float = None):
+    def write(self, report, domains: bool = False, labels=None, db_labels=None, min_z: float = None, map_l1: int = None):
         """One ``report.line`` per reciprocal best hit."""
-        for text in self.lines(domains, labels, db_labels, min_z):
+        for text in self.lines(domains, labels, db_labels, min_z, **({'map_l1': map_l1} if map_l1 is not None else {})):
             report.line(text)
 
 
@@ -2299,11 +2473,13 @@ class Report:
             self.out.flush()
 
 
-def _header(base: str, level: str = None, domains=False) -> str:
+def _header(base: str, level: str = None, domains=False, domain_map=None) -> str:
     """The header of a report: ``base`` (HEADER, or CLUSTER_HEADER for the modes that print clusters) with the two columns of the
-    domain pair where the lines carry them."""
+    domain pair where the lines carry them, and behind those the column of the domain map (``domain_map`` not None)."""
     if base == CLUSTER_HEADER:
         return DOMAIN_CLUSTER_HEADER if level == 'domain' else base
+    if base == HEADER and domain_map is not None:
+        return DOMAIN_HEADER + MAP_COLUMN
     return DOMAIN_HEADER if base == HEADER and domains else base
 
 
@@ -2324,7 +2500,7 @@ def _reporting(fn=None, *, header: str = HEADER, rbh: bool = False):
         if isinstance(output, Report):
             return fn(*head, output, **kw)
         # (a report opened here for a call that asks for the domain pair carries the two extra column names, one that asks for z its)
-        report = Report(output, _header(header, kw.get('level'), any(kw.get(k) for k in ('domains', 'dom', 'db_dom')))
+        report = Report(output, _header(header, kw.get('level'), any(kw.get(k) for k in ('domains', 'dom', 'db_dom')), kw.get('domain_map'))
                         + _z_header(kw.get('zscore') or kw.get('min_z') is not None, rbh, kw.get('rank')))
         try:
             return fn(*head, report, **kw)
@@ -2335,12 +2511,13 @@ def _reporting(fn=None, *, header: str = HEADER, rbh: bool = False):
 
 
 @_reporting
-def pair_sim(npzfile: str, pairfile: str, pairfound: str, report: Report, domains: bool = False, dom: str = None):
+def pair_sim(npzfile: str, pairfile: str, pairfound: str, report: Report, domains: bool = False, dom: str = None, domain_map=None):
     """Similarity of every listed protein pair (src/dct-sim.py:86-124).  Lines starting with ``#``
     are comments (copied to ``pairfound``); pairs with an unknown protein are counted, not printed.  ``domains`` / ``dom`` (the
-    ``.dom`` of the npz): the best domain pair behind the scores."""
+    ``.dom`` of the npz): the best domain pair behind the scores.  ``domain_map`` (True, or the similarity X from which a row is
+    matched: ``map_bound``; implies ``domains``): then the domain map of the pair (``map_field``)."""
     sid, idx, fps = _load_npz(npzfile)
-    domains = domains or dom is not None
+    domains = domains or dom is not None or domain_map is not None
     labels = _labels_of(sid, idx, dom) if domains else None
     where = {name: i for i, name in enumerate(sid)}           # a repeated id: the later one, like a dict of arrays
     listed = 0
@@ -2356,10 +2533,16 @@ def pair_sim(npzfile: str, pairfile: str, pairfound: str, report: Report, domain
                 continue
             found.append((first, second, where[first], where[second]))
             kept.append(text)
-    mn, last, *args = pair_scores(fps, idx, [(i, j) for _, _, i, j in found], domains=domains)
+    listed_pairs = [(i, j) for _, _, i, j in found]
+    mn, last, *args = pair_scores(fps, idx, listed_pairs, domains=domains)
+    maps = None
+    if domain_map is not None:
+        maps = _map_fields(*pair_row_bests(fps, idx, listed_pairs), map_bound(domain_map), listed_pairs, labels, idx, labels, idx)
     for k, ((first, second, i, j), m, l) in enumerate(zip(found, mn, last)):
         maxs, s = _scores(m, l)
         tail = f' {_label(labels, idx[i], args[0][k])} {_label(labels, idx[j], args[1][k])}' if domains else ''
+        if maps is not None:
+            tail += f' {maps[k]}'
         report.line(f'{first} {second} {maxs} {s}{tail}')
     print(f'total pair {pairfile} found {len(found)} (not found: {listed - len(found)})')
     if pairfound:
@@ -2370,24 +2553,33 @@ def pair_sim(npzfile: str, pairfile: str, pairfound: str, report: Report, domain
 
 @_reporting
 def db_search(npzfile: str, dbfile: str, top: int, threshold: float, report: Report, rank: str = 'global', domains: bool = False,
-              dom: str = None, db_dom: str = None, zscore: bool = False, min_z: float = None):
+              dom: str = None, db_dom: str = None, zscore: bool = False, min_z: float = None, domain_map=None):
     """Hits of every query protein in a fingerprint database, best DCTglobal first (stable); the first
     ``top`` always, further ones while they reach ``threshold`` (src/dct-sim.py:126-156).  ``rank='domain'``: best
     DCTdomain first, and the threshold applies to DCTdomain (the same loop with the domain score as the key).  ``domains`` /
     ``dom`` / ``db_dom`` (the ``.dom`` files of the two npz): the best domain pair behind the scores of every printed hit.
     ``zscore``: one more field at the end of every line, the hit's z-score in the query's background over the database under the
-    ranking score (``zscore_of``); ``min_z`` (implies ``zscore``) prints a selected line only if its z is defined and not below it."""
+    ranking score (``zscore_of``); ``min_z`` (implies ``zscore``) prints a selected line only if its z is defined and not below it.
+    ``domain_map`` (as in ``pair_sim``; implies ``domains``): the domain map of every selected hit, before the z."""
     sid, idx, fps = _load_npz(npzfile)
     db_sid, db_idx, db_fps = _load_npz(dbfile)
-    domains = domains or dom is not None or db_dom is not None
+    domains = domains or dom is not None or db_dom is not None or domain_map is not None
     zscore = zscore or min_z is not None
     if domains:
         labels, db_labels = _labels_of(sid, idx, dom), _labels_of(db_sid, db_idx, db_dom)
-    hits = ProteinSearch(db_fps, db_idx).search(fps, idx, top, threshold, rank=rank, domains=domains, **({'zscore': True} if zscore else {}))
+    search = ProteinSearch(db_fps, db_idx)
+    hits = search.search(fps, idx, top, threshold, rank=rank, domains=domains, **({'zscore': True} if zscore else {}))
+    maps = None
+    if domain_map is not None:                                  # (the selected hits only, in the order of the lines)
+        q_of = np.repeat(np.arange(len(hits), dtype=np.int64), [len(h[0]) for h in hits])
+        db_of = np.concatenate([h[0] for h in hits]).astype(np.int64) if hits else np.zeros(0, dtype=np.int64)
+        maps = iter(search.map_fields(fps, idx, q_of, db_of, map_bound(domain_map), labels, db_labels))
     for i, (query, (cols, mn, last, *args)) in enumerate(zip(sid, hits)):
         for k, (q, m, l) in enumerate(zip(cols, mn, last)):
             maxs, s = _scores(m, l)
             tail = f' {_label(labels, idx[i], args[0][k])} {_label(db_labels, db_idx[q], args[1][k])}' if domains else ''
+            if maps is not None:
+                tail += f' {next(maps)}'
             if zscore:
                 if min_z is not None and not _z_passes(min_z, args[-1][k]):
                     continue
@@ -2405,21 +2597,26 @@ def _file_weights(npzfile: str, sid, idx, unit: str, dom: str = None) -> np.ndar
 
 @_reporting
 def all_sim(npzfile: str, report: Report, min_domain: float = None, min_global: float = None, domains: bool = False, dom: str = None,
-            min_coverage: float = None, cov_unit: str = 'residues'):
+            min_coverage: float = None, cov_unit: str = 'residues', domain_map=None):
     """All-against-all, upper triangle (src/dct-sim.py:158-176), streamed from the device (``AllPairs``).  With ``min_domain`` /
     ``min_global``: only the pairs whose DCTdomain / DCTglobal is not below them (``FilteredPairs``).  ``domains`` / ``dom`` (the
     ``.dom`` of the npz): the best domain pair behind the scores -- ``FilteredPairs`` with or without cut-offs.  ``min_coverage``
     (with ``min_domain``): only the pairs that also cover that share of both proteins, in ``cov_unit`` -- residues (from ``dom``, else
-    from the npz) or domains (``FilteredPairs``)."""
+    from the npz) or domains (``FilteredPairs``).  ``domain_map`` (True, or the similarity X from which a row is matched; implies
+    ``domains``): then the domain map of every printed pair, composed on the device (``FilteredPairs.with_map``); without X the rows
+    within ``min_domain`` are matched, where that is given (``map_bound``)."""
     sid, idx, fps = _load_npz(npzfile)
-    domains = domains or dom is not None
+    domains = domains or dom is not None or domain_map is not None
     if min_domain is None and min_global is None and not domains and min_coverage is None:
         AllPairs(sid, idx, fps).write(report.raw)
     else:
         labels = _labels_of(sid, idx, dom) if domains else None
         weights = _file_weights(npzfile, sid, idx, cov_unit, dom) if min_coverage is not None else None
-        FilteredPairs(sid, idx, fps, min_domain=min_domain, min_global=min_global, labels=labels, min_coverage=min_coverage,
-                      weights=weights).write(report.raw)
+        job = FilteredPairs(sid, idx, fps, min_domain=min_domain, min_global=min_global, labels=labels, min_coverage=min_coverage,
+                            weights=weights)
+        if domain_map is not None:
+            job.with_map(map_bound(domain_map, min_domain))
+        job.write(report.raw)
 
 
 @_reporting(header=CLUSTER_HEADER)
@@ -2521,23 +2718,24 @@ def tree_sim(npzfile: str, report: Report, score: str = 'domain', min_domain: fl
 
 @_reporting(rbh=True)
 def rbh_sim(npzfile: str, dbfile: str, report: Report, score: str = 'domain', min_domain: float = None, min_global: float = None,
-            domains: bool = False, dom: str = None, db_dom: str = None, zscore: bool = False, min_z: float = None):
+            domains: bool = False, dom: str = None, db_dom: str = None, zscore: bool = False, min_z: float = None, domain_map=None):
     """The reciprocal best hits of the proteins of ``npzfile`` and ``dbfile`` (``ReciprocalBest``) on DCTdomain (``score='domain'``) or
     DCTglobal (``'global'``): one ``db_search`` line per pair, in the order of ``npzfile``.  ``min_domain`` / ``min_global``: the cut-off
     of that score below which a pair is no hit; the other score's cut-off is an error.  ``domains`` / ``dom`` / ``db_dom``: as in
     ``db_search``.  ``zscore``: two more fields at the end of every line, the pair's z-score in the background of the ``npzfile``
     protein over ``dbfile`` and in that of the ``dbfile`` protein over ``npzfile``, both under ``score``; ``min_z`` (implies
-    ``zscore``) prints a pair only if both are defined and not below it."""
+    ``zscore``) prints a pair only if both are defined and not below it.  ``domain_map``: as in ``all_sim``, before the two z."""
     min_cut = _cut_of(score, min_domain, min_global, 'reciprocal best hits are ranked')
     sid, idx, fps = _load_npz(npzfile)
     db_sid, db_idx, db_fps = _load_npz(dbfile)
-    domains = domains or dom is not None or db_dom is not None
+    domains = domains or dom is not None or db_dom is not None or domain_map is not None
     labels, db_labels = (_labels_of(sid, idx, dom), _labels_of(db_sid, db_idx, db_dom)) if domains else (None, None)
     zscore = zscore or min_z is not None
     job = ReciprocalBest(sid, idx, fps, db_sid, db_idx, db_fps, score=score, min_cut=min_cut)
     if zscore:
         job.with_zscore()
-    job.write(report, domains=domains, labels=labels, db_labels=db_labels, **({'min_z': min_z} if min_z is not None else {}))
+    job.write(report, domains=domains, labels=labels, db_labels=db_labels, **({'min_z': min_z} if min_z is not None else {}),
+              **({'map_l1': map_bound(domain_map, min_domain)} if domain_map is not None else {}))
 
 
 def read_families(path: str, sid) -> list:
@@ -2635,7 +2833,7 @@ _GIVEN = {'--pair': bool, '--db': bool, '--cluster': bool, '--domains': bool, '-
           '--assign': _is_set, '--tree': _is_set, '--rank': _is_set, '--linkage': _is_set, '--level': _is_set, '--reps-out': _is_set,
           '--dom': _is_set, '--db-dom': _is_set, '--min-coverage': _is_set, '--cov-unit': _is_set, '--rep': _is_set,
           '--min-neighbors': _is_set, '--auc1': _is_set, '--families': _is_set, '--family-sep': _is_set, '--hist': _is_set, '--bins': _is_set,
-          '--zscore': bool, '--min-z': _is_set}
+          '--zscore': bool, '--min-z': _is_set, '--domain-map': _is_set}
 # mode -> (what it does; for a mode that takes a score, what that score does; the flags it refuses, in the order they are named).
 # The modes are checked in this order.
 _MODES = {'--rbh': ('prints the reciprocal best hits of --dct and --db', 'ranks the hits',
@@ -2643,16 +2841,16 @@ _MODES = {'--rbh': ('prints the reciprocal best hits of --dct and --db', 'ranks 
                      '--min-coverage', '--cov-unit', '--rep', '--min-neighbors', '--auc1', '--hist')),
           '--tree': ('prints the single-linkage tree of --dct', 'orders the pairs',
                      ('--pair', '--db', '--cluster', '--assign', '--rank', '--linkage', '--level', '--no-whole', '--reps-out', '--domains',
-                      '--dom', '--db-dom', '--min-coverage', '--cov-unit', '--rep', '--min-neighbors', '--zscore', '--min-z', '--auc1', '--hist')),
+                      '--dom', '--db-dom', '--domain-map', '--min-coverage', '--cov-unit', '--rep', '--min-neighbors', '--zscore', '--min-z', '--auc1', '--hist')),
           '--assign': ('places the proteins of --dct on a fixed set of representatives', None,
-                       ('--pair', '--db', '--cluster', '--rank', '--domains', '--dom', '--db-dom', '--linkage', '--level', '--no-whole',
+                       ('--pair', '--db', '--cluster', '--rank', '--domains', '--dom', '--db-dom', '--domain-map', '--linkage', '--level', '--no-whole',
                         '--min-coverage', '--cov-unit', '--rep', '--min-neighbors', '--zscore', '--min-z', '--auc1', '--hist')),
           '--auc1': ('measures the AUC1 and the top-1 rates of --dct', 'ranks the hits',
                      ('--pair', '--db', '--cluster', '--assign', '--rank', '--linkage', '--level', '--no-whole', '--reps-out', '--domains',
-                      '--dom', '--db-dom', '--min-coverage', '--cov-unit', '--rep', '--min-neighbors', '--zscore', '--min-z', '--hist')),
+                      '--dom', '--db-dom', '--domain-map', '--min-coverage', '--cov-unit', '--rep', '--min-neighbors', '--zscore', '--min-z', '--hist')),
           '--hist': ('bins the scores of all pairs of --dct', 'bins the pairs',
                      ('--pair', '--db', '--cluster', '--assign', '--rank', '--linkage', '--level', '--no-whole', '--reps-out', '--domains',
-                      '--dom', '--db-dom', '--min-coverage', '--cov-unit', '--rep', '--min-neighbors', '--zscore', '--min-z', '--auc1'))}
+                      '--dom', '--db-dom', '--domain-map', '--min-coverage', '--cov-unit', '--rep', '--min-neighbors', '--zscore', '--min-z', '--auc1'))}
 # the options that say where --auc1 and --hist find the family of a protein: exactly one of them with --auc1, at most one with --hist,
 # none without either
 _FAMILY_FLAGS = ('--families', '--family-sep')
@@ -2692,7 +2890,11 @@ class _Parser(argparse.ArgumentParser):
     ``--zscore`` adds the z-score of every hit of ``--db``, with or without ``--rbh``, and ``--min-z Z`` (which implies it) keeps the
     selected lines whose z is not below Z: either is an error without ``--db``, beside ``--pair`` or ``--cluster``, and beside
     ``--tree``, ``--assign``, ``--auc1`` and ``--hist`` (``_MODES``); both are absent from the namespace of a command line without
-    them."""
+    them.
+    ``--domain-map [X]`` adds the map of all matched domain pairs to every result line and implies ``--domains``, in every mode that
+    prints pair lines (``--pair``, ``--db`` with or without ``--rbh``, the all-against-all): an error beside ``--cluster`` and beside
+    ``--tree``, ``--assign``, ``--auc1`` and ``--hist`` (``_MODES``), or with X outside (0, 1]; it is absent from the namespace of a
+    command line without it, True there for the bare flag."""
 
     def parse_known_args(self, args=None, namespace=None):
         ns, rest = super().parse_known_args(args, namespace)
@@ -2766,6 +2968,13 @@ class _Parser(argparse.ArgumentParser):
                 self.error('--min-coverage is a share of a protein: above 0 and at most 1')
         elif getattr(ns, 'cov_unit', None) is not None:
             self.error('--cov-unit says what --min-coverage counts: it needs --min-coverage')
+        mapped = getattr(ns, 'domain_map', None)                # (True for the bare flag, else its X)
+        if mapped is not None:
+            if getattr(ns, 'cluster', False):
+                self.error('--domain-map lists the matched domain pairs behind a result line: not with --cluster')
+            if mapped is not True and not 0 < mapped <= 1:
+                self.error('--domain-map X is the similarity from which a domain is matched: above 0 and at most 1')
+            ns.domains = True
         weighs = coverage is not None and getattr(ns, 'cluster', False)     # (--dom gives --min-coverage its residues: no result lines to explain)
         if (getattr(ns, 'dom', None) is not None and not weighs) or getattr(ns, 'db_dom', None) is not None:
             ns.domains = True
@@ -2849,6 +3058,12 @@ def build_parser() -> argparse.ArgumentParser:
                          '1-based index within the protein; "-" when no pair scores above 0)')
     ap.add_argument('--dom', metavar='FILE', default=argparse.SUPPRESS, help='the .dom file of --dct: print residue ranges instead of indices (implies --domains)')
     ap.add_argument('--db-dom', metavar='FILE', default=argparse.SUPPRESS, help='the .dom file of --db, likewise (implies --domains)')
+    ap.add_argument('--domain-map', nargs='?', type=float, const=True, metavar='X', default=argparse.SUPPRESS,
+                    help='add one more field behind dom1 dom2 (implies --domains): every fingerprint of prot1 that has a counterpart '
+                         'in prot2, then after "/" every fingerprint of prot2 that has one in prot1, each as '
+                         '"label=label of its nearest fingerprint in the other protein:similarity", joined by ";" ("-" when there is '
+                         'none).  A fingerprint has a counterpart when that similarity is at least X (above 0, at most 1; default: '
+                         f'--min-domain where given, else {MAP_SIMILARITY}) and above 0.  Not with --cluster')
     ap.add_argument('--linkage', choices=LINKAGES, default=argparse.SUPPRESS,
                     help='--cluster: single linkage (the default: connected components, the representative is the first protein of '
                          'the component) or greedy (in file order, a protein joins the first representative it is within the cut-off '
@@ -2934,9 +3149,11 @@ def main(argv=None):
     min_z = getattr(args, 'min_z', None)
     zscore = getattr(args, 'zscore', False) or min_z is not None
     z = {'zscore': True, **({'min_z': min_z} if min_z is not None else {})} if zscore else {}
+    mapped = getattr(args, 'domain_map', None)
+    maps = {'domain_map': mapped} if mapped is not None else {}  # (the functions take the option only where the command line has it)
     report = Report(args.output, _header(hist_header(hist, any(v is not None for v in family.values())) if hist is not None else
                                          AUC1_HEADER if auc1 is not None else CLUSTER_HEADER if args.cluster or assign is not None else HEADER,
-                                         level, domains) + _z_header(zscore, getattr(args, 'rbh', None) is not None, args.rank))
+                                         level, domains, mapped) + _z_header(zscore, getattr(args, 'rbh', None) is not None, args.rank))
     t_work = time.time()
     if hist is not None:
         hist_sim(args.dct, report, score=hist, bins=getattr(args, 'bins', HIST_BINS), min_domain=args.min_domain, min_global=args.min_global,
@@ -2947,13 +3164,13 @@ def main(argv=None):
         tree_sim(args.dct, report, score=args.tree, min_domain=args.min_domain, min_global=args.min_global)
     elif getattr(args, 'rbh', None) is not None:
         rbh_sim(args.dct, args.db, report, score=args.rbh, min_domain=args.min_domain, min_global=args.min_global, domains=bool(domains),
-                dom=dom, db_dom=db_dom, **z)
+                dom=dom, db_dom=db_dom, **z, **maps)
     elif assign is not None:
         assign_sim(args.dct, assign, report, min_domain=args.min_domain, min_global=args.min_global, reps_out=reps_out)
     elif args.pair:
-        pair_sim(args.dct, args.pair, args.pairfound, report, domains=bool(domains), dom=dom)
+        pair_sim(args.dct, args.pair, args.pairfound, report, domains=bool(domains), dom=dom, **maps)
     elif args.db:
-        db_search(args.dct, args.db, args.top, args.threshold, report, rank=args.rank or 'global', domains=bool(domains), dom=dom, db_dom=db_dom, **z)
+        db_search(args.dct, args.db, args.top, args.threshold, report, rank=args.rank or 'global', domains=bool(domains), dom=dom, db_dom=db_dom, **z, **maps)
     elif args.cluster:
         cluster_sim(args.dct, report, min_domain=args.min_domain, min_global=args.min_global, linkage=getattr(args, 'linkage', 'single'),
                     level=level, whole=not getattr(args, 'no_whole', False), dom=dom if level == 'domain' or cover else None,
@@ -2961,7 +3178,7 @@ def main(argv=None):
                     **({'rep': args.rep} if getattr(args, 'rep', None) is not None else {}),
                     **({'min_neighbors': args.min_neighbors} if getattr(args, 'min_neighbors', None) is not None else {}))
     else:
-        all_sim(args.dct, report, min_domain=args.min_domain, min_global=args.min_global, domains=bool(domains), dom=dom, **cover)
+        all_sim(args.dct, report, min_domain=args.min_domain, min_global=args.min_global, domains=bool(domains), dom=dom, **cover, **maps)
     report.close()
     t_end = time.time()
     print(f'total time used {t_end - t_start:.1f}s')

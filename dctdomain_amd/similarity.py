@@ -245,6 +245,69 @@ def pair_argmin_device(a: torch.Tensor, idx_a: torch.Tensor, b: torch.Tensor, id
     return _pair_scores_device(a, idx_a, b, idx_b, pairs, True)
 
 
+def pair_row_offsets(idx_a, idx_b, pairs) -> np.ndarray:
+    """int64 (n + 1): the prefix sum of k + m over the pairs -- where ``pair_row_best`` puts the rows of each pair."""
+    ia, ib = np.asarray(idx_a, dtype=np.int64), np.asarray(idx_b, dtype=np.int64)
+    pairs = np.asarray(pairs, dtype=np.int64).reshape(-1, 2)
+    off = np.zeros(len(pairs) + 1, dtype=np.int64)
+    np.cumsum((ia[pairs[:, 0] + 1] - ia[pairs[:, 0]]) + (ib[pairs[:, 1] + 1] - ib[pairs[:, 1]]), out=off[1:])
+    return off
+
+
+def pair_row_best(a, idx_a, b, idx_b, pairs):
+    """Every fingerprint row's counterpart, for the pairs (protein of ``a``, protein of ``b``) of ``pairs`` (``dctfp_pair_row_best``):
+    (row_off, l1, arg) numpy int64.  The rows of pair p lie at [row_off[p], row_off[p + 1]): first those of the protein of ``a``,
+    then those of the protein of ``b``; ``l1`` = the smallest L1 to any row of the other protein, raw, ``arg`` = that row within the
+    other protein, ties to the lowest; 0x7fffffff and -1 where the other protein has no rows.  ``pair_argmin``'s arguments and
+    checks."""
+    pairs = np.ascontiguousarray(np.asarray(pairs, dtype=np.int64).reshape(-1, 2))
+    ia, ib = np.asarray(idx_a, dtype=np.int64), np.asarray(idx_b, dtype=np.int64)
+    npa, npb = len(ia) - 1, len(ib) - 1
+    ta, tb = to_device_int8(a), to_device_int8(b)
+    _check_pair(ta, tb)
+    _check_prefix(ia, ta.shape[0])
+    _check_prefix(ib, tb.shape[0])
+    if len(pairs) and (pairs[:, 0].min() < 0 or pairs[:, 0].max() >= npa or pairs[:, 1].min() < 0 or pairs[:, 1].max() >= npb):
+        raise IndexError('protein index out of range')
+    off = pair_row_offsets(ia, ib, pairs)
+    total = int(off[-1])
+    if len(pairs) == 0 or ta.shape[0] == 0 or tb.shape[0] == 0:  # (no fingerprint on a side: no row has a counterpart)
+        return off, np.full(total, 0x7fffffff, dtype=np.int64), np.full(total, -1, dtype=np.int64)
+    dev = ta.device
+    _, l1, arg = pair_row_best_device(ta, _device_int64(ia, dev), tb, _device_int64(ib, dev), torch.as_tensor(pairs.astype(np.int32), device=dev),
+                                      _device_int64(off, dev))
+    return (off,) + _pair_to_host(l1, arg)
+
+
+def pair_row_best_device(a: torch.Tensor, idx_a: torch.Tensor, b: torch.Tensor, idx_b: torch.Tensor, pairs: torch.Tensor,
+                         row_off: torch.Tensor = None):
+    """``pair_row_best`` with everything on the device already (``pair_argmin_device``'s arguments and guarantees).  ``row_off``:
+    device int64 (n + 1), made here from the prefix arrays when None.  Returns device (row_off int64, l1 int32, arg int32); the
+    kernel leaves the fill, 0x7fffffff and -1, in the rows of a pair whose index is out of range or whose ``row_off`` range is not
+    its two proteins' rows."""
+    if pairs.dtype != torch.int32 or pairs.dim() != 2 or pairs.shape[1] != 2 or not pairs.is_contiguous():
+        raise ValueError('pairs must be a contiguous int32 (n, 2) device tensor')
+    if a.dtype != torch.int8 or b.dtype != torch.int8 or a.dim() != 2 or b.dim() != 2 or a.shape[1] != b.shape[1]:
+        raise ValueError('fingerprint sets must be 2-D int8 with equal width')
+    if idx_a.dtype != torch.int64 or idx_b.dtype != torch.int64 or not (idx_a.is_contiguous() and idx_b.is_contiguous()):
+        raise ValueError('prefix arrays must be contiguous int64 device tensors')
+    n, dev = pairs.shape[0], pairs.device
+    if row_off is None:
+        pa, pb = pairs[:, 0].long(), pairs[:, 1].long()
+        row_off = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+        if n:
+            torch.cumsum((idx_a[pa + 1] - idx_a[pa]) + (idx_b[pb + 1] - idx_b[pb]), 0, out=row_off[1:])
+    if row_off.dtype != torch.int64 or row_off.numel() != n + 1 or not row_off.is_contiguous() or row_off.device != dev:
+        raise ValueError('row_off must be a contiguous int64 device tensor with an entry per pair and one more')
+    total = int(row_off[-1]) if n else 0
+    l1 = torch.full((max(total, 0),), 0x7fffffff, dtype=torch.int32, device=dev)
+    arg = torch.full((max(total, 0),), -1, dtype=torch.int32, device=dev)
+    if n and total > 0 and a.shape[0] and b.shape[0]:           # (no fingerprint on a side: no row has a counterpart)
+        _launch(dev, 'dctfp_pair_row_best', pairs.data_ptr(), n, a.data_ptr(), _ld(a), idx_a.data_ptr(), idx_a.numel() - 1, b.data_ptr(),
+                _ld(b), idx_b.data_ptr(), idx_b.numel() - 1, a.shape[1], row_off.data_ptr(), total, l1.data_ptr(), arg.data_ptr())
+    return row_off, l1, arg
+
+
 def protein_min(a, idx_a, b, idx_b, out: torch.Tensor = None) -> torch.Tensor:
     """int32 (npa, npb) on the device: the smallest L1 over all fingerprint pairs of every (protein of ``a``, protein of ``b``)
     -- DCTdomain's distance, ``block_min(l1_matrix(a, b), idx_a, idx_b)[0]`` without the distance matrix
@@ -944,6 +1007,57 @@ def pair_domain_lines(pi: torch.Tensor, pj: torch.Tensor, mn: torch.Tensor, last
                       ids: LineIds, labels: LineIds, table: torch.Tensor, line_off: torch.Tensor, out: torch.Tensor):
     """``pair_lines`` with labels (``line_off``: ``pair_domain_line_offsets``)."""
     pair_lines(pi, pj, mn, last, ids, table, line_off, out, la, lb, labels)
+
+
+def _pair_map_args(pi, pj, mn, last, la, lb, ids: LineIds, labels: LineIds, table, first_row, row_off, row_l1, row_arg, bound: int):
+    """The checked arguments the two passes of ``dctfp_pair_map_lines`` share, as (head, tail): the line buffer goes between them."""
+    n, dev = pi.numel(), pi.device
+    for t in (pi, pj, mn, last, la, lb):
+        if t.dtype != torch.int32 or t.numel() != n or not t.is_contiguous() or t.device != dev:
+            raise ValueError('pi / pj / mn / last / la / lb must be contiguous int32 device tensors of one length')
+    if table.dtype != torch.uint8 or table.numel() != 2 * 17002 * 5 or not table.is_contiguous():
+        raise ValueError('table must be uint8 (2, 17002, 5)')
+    if row_off.dtype != torch.int64 or row_off.numel() != n + 1 or not row_off.is_contiguous() or row_off.device != dev:
+        raise ValueError('row_off must be a contiguous int64 device tensor with an entry per line and one more')
+    if first_row.dtype != torch.int64 or first_row.numel() != len(ids.off) or not first_row.is_contiguous() or first_row.device != dev:
+        raise ValueError('first_row must be a contiguous int64 device tensor with an entry per protein and one more')
+    for t in (row_l1, row_arg):
+        if t.dtype != torch.int32 or t.numel() != row_l1.numel() or not t.is_contiguous() or t.device != dev:
+            raise ValueError('row_l1 / row_arg must be contiguous int32 device tensors of one length')
+    if not -1 <= int(bound) < 17000:
+        raise ValueError('the bound of a map is an L1 of similarity above 0: -1 .. 16999')
+    head = (n, pi.data_ptr(), pj.data_ptr(), mn.data_ptr(), last.data_ptr(), la.data_ptr(), lb.data_ptr(), ids.bytes_dev.data_ptr(),
+            ids.off_dev.data_ptr(), len(ids.off) - 1, labels.bytes_dev.data_ptr(), labels.off_dev.data_ptr(), len(labels.off) - 1,
+            table.data_ptr())
+    tail = (row_off.data_ptr(), row_l1.numel(), _ptr(row_l1) or row_off.data_ptr(), _ptr(row_arg) or row_off.data_ptr(), first_row.data_ptr(),
+            int(bound))
+    return head, tail
+
+
+def pair_map_line_lengths(pi, pj, mn, last, la, lb, ids: LineIds, labels: LineIds, table, first_row, row_off, row_l1, row_arg,
+                          bound: int) -> torch.Tensor:
+    """Device int64 (n): the bytes of every ``pair_map_lines`` line -- the count pass of ``dctfp_pair_map_lines``, the same kernel
+    body as the text; 0 for a line the fill would skip."""
+    head, tail = _pair_map_args(pi, pj, mn, last, la, lb, ids, labels, table, first_row, row_off, row_l1, row_arg, bound)
+    count = torch.zeros(pi.numel(), dtype=torch.int64, device=pi.device)
+    if pi.numel():
+        _launch(pi.device, 'dctfp_pair_map_lines', *head, None, None, 0, *tail, count.data_ptr())
+    return count
+
+
+def pair_map_lines(pi, pj, mn, last, la, lb, ids: LineIds, labels: LineIds, table, first_row, row_off, row_l1, row_arg, bound: int,
+                   line_off: torch.Tensor, out: torch.Tensor):
+    """``pair_lines`` with labels and the domain map of every pair: line n = ``"... {label la[n]} {label lb[n]} {side}/{side}\\n"``
+    from byte ``line_off[n]`` of ``out`` (the fill pass of ``dctfp_pair_map_lines``).  ``row_off`` / ``row_l1`` / ``row_arg``:
+    ``pair_row_best_device`` of the pairs; ``first_row``: device int64, the prefix array of the file whose rows ``labels`` names;
+    ``bound``: a row is matched when its L1 is at most this.  ``line_off``: the prefix sum of ``pair_map_line_lengths``."""
+    head, tail = _pair_map_args(pi, pj, mn, last, la, lb, ids, labels, table, first_row, row_off, row_l1, row_arg, bound)
+    if line_off.dtype != torch.int64 or line_off.numel() < pi.numel() or not line_off.is_contiguous() or line_off.device != out.device:
+        raise ValueError('line_off must be a contiguous int64 device tensor with an entry per line')
+    if out.dtype != torch.uint8 or not out.is_contiguous() or out.device != pi.device:
+        raise ValueError('out must be a contiguous uint8 device buffer')
+    if pi.numel() and out.numel():
+        _launch(out.device, 'dctfp_pair_map_lines', *head, line_off.data_ptr(), out.data_ptr(), out.numel(), *tail, None)
 
 
 KNN_MAX_K = 1024     # dctfp_l1_knn's limits: larger k or wider rows take l1_matrix + row_select

@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define DCTFP_VERSION 116 /* 0.1.16: dctfp_rect_moments */
+#define DCTFP_VERSION 117 /* 0.1.17: dctfp_pair_row_best, dctfp_pair_map_lines */
 
 #define DCTFP_OK 0
 #define DCTFP_ERR_INVALID (-1) /* bad argument (null pointer, piece outside its sequence, ...) */
@@ -431,6 +431,40 @@ int dctfp_pair_domain_lines(dctfp_ctx* ctx, int64_t n_lines, const int32_t* pi, 
                             const int32_t* la, const int32_t* lb, const uint8_t* ids, const int64_t* id_off, int64_t n_ids,
                             const uint8_t* labels, const int64_t* label_off, int64_t n_labels, const char* table, const int64_t* line_off,
                             uint8_t* out, int64_t out_bytes, void* stream);
+
+/* Every fingerprint row's counterpart in the other protein, for a list of protein pairs (dct-sim --domain-map; not in the
+ * reference): where dctfp_pair_argmin keeps the one best fingerprint pair, this keeps the best partner of EVERY row, on both
+ * sides.  pairs, a, lda, idx_a, npa, b, ldb, idx_b, npb, d: as dctfp_pair_argmin, with its checks and error codes
+ * (DCTFP_ERR_LIMIT above 2^31 - 1 proteins on a side or too many pairs per call).  For pair p = (pa, pb) with k and m rows the
+ * results lie at [row_off[p], row_off[p + 1]) of out_l1 / out_arg (device int32, out_len entries; row_off = n_pairs + 1 device
+ * int64, the caller's prefix sum of k + m): first the k rows of pa, then the m rows of pb.  out_l1 = the smallest L1 between the
+ * row and any row of the other protein, raw (not capped at 17000); out_arg = the row of the other protein it was found at,
+ * counted from 0 within that protein, ties to the lowest.  Where the other protein has no rows: 0x7fffffff and -1.  A pair with
+ * an index outside [0, npa) x [0, npb), a range whose width is not k + m, that starts below 0 or ends beyond out_len writes
+ * nothing.  The smallest out_l1 of the first side, ties to the first row, is dctfp_pair_argmin's pair.  Any number of rows per
+ * protein; rows above 512 bytes take a slower loop. */
+int dctfp_pair_row_best(dctfp_ctx* ctx, const int32_t* pairs, int64_t n_pairs, const int8_t* a, int64_t lda, const int64_t* idx_a, int64_t npa,
+                        const int8_t* b, int64_t ldb, const int64_t* idx_b, int64_t npb, int32_t d, const int64_t* row_off, int64_t out_len,
+                        int32_t* out_l1, int32_t* out_arg, void* stream);
+
+/* dctfp_pair_domain_lines with one more field, the domain map of the pair (dct-sim --domain-map): line n =
+ * "{id_i} {id_j} {a} {b} {label_a} {label_b} {side}/{side}\n".  The first side lists the fingerprint rows of protein pi[n] that
+ * are matched by pj[n], the second those of pj[n] matched by pi[n], each in row order as
+ * "{label of the row}={label of its counterpart}:{score}" joined by ";", or "-" when no row is matched.  A row is matched when
+ * its row_l1 is in [0, bound]; score = the five bytes of the first half of the score table for that L1, so the entry of the best
+ * pair repeats the line's own a.  row_off (n_lines + 1), row_l1 and row_arg (n_rows entries): dctfp_pair_row_best's row_off,
+ * out_l1 and out_arg for these lines.  first_row (n_ids + 1 device int64): the rows of protein p are the labels
+ * first_row[p] .. first_row[p + 1] - 1 (the idx array of the file).  bound below 17000 (DCTFP_ERR_INVALID otherwise).
+ * Two passes of one kernel body: with out_count non-NULL (device int64, n_lines) every line's byte length is written there and no
+ * text (line_off and out may be NULL); with out_count NULL the text goes to out from line_off[n], the caller's prefix sum of those
+ * lengths.  A line with a protein or label index out of range, whose row_off range is not its two proteins' rows within
+ * [0, n_rows], whose row_arg names no row of the other protein, or (fill) that ends beyond out_bytes has length 0 and is not
+ * written.  Any id or label length, any alignment.  DCTFP_ERR_LIMIT above 2^31 lines per call. */
+int dctfp_pair_map_lines(dctfp_ctx* ctx, int64_t n_lines, const int32_t* pi, const int32_t* pj, const int32_t* mn, const int32_t* last,
+                         const int32_t* la, const int32_t* lb, const uint8_t* ids, const int64_t* id_off, int64_t n_ids, const uint8_t* labels,
+                         const int64_t* label_off, int64_t n_labels, const char* table, const int64_t* line_off, uint8_t* out,
+                         int64_t out_bytes, const int64_t* row_off, int64_t n_rows, const int32_t* row_l1, const int32_t* row_arg,
+                         const int64_t* first_row, int32_t bound, int64_t* out_count, void* stream);
 
 /* Single-linkage clusters at a cut-off (dct-sim --cluster; not in the reference): the connected components of the graph whose
  * edges are the pairs dctfp_tri_filter_count / dctfp_tri_filter_fill select, joined on the device instead of listed.

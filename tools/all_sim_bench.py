@@ -6,6 +6,7 @@
     python tools/all_sim_bench.py --part filter --n 50000 [--min-domain 0.5]  # cut-offs beside the unfiltered run, one process
     python tools/all_sim_bench.py --part cluster --n 50000 --families 500 --family-size 100 --min-domain 0.5   # --cluster beside the cut-offs
     python tools/all_sim_bench.py --part domains --n 50000 --families 500 --family-size 100 --min-domain 0.5   # --domains beside the same cut-offs
+    python tools/all_sim_bench.py --part map --n 50000 --families 500 --family-size 100 --min-domain 0.5       # --domain-map beside --domains
     python tools/all_sim_bench.py --part rows_link --n 50000 --families 500 --family-size 100 --min-domain 0.5 # --cluster --level domain
 
 `rows_link` loads one synthetic file with planted families and runs, after a warm-up of both on a small file, --repeat times each:
@@ -504,6 +505,85 @@ def part_domains(args):
             'device_ms_of_median_run': device_ms[t_dom.index(med(t_dom))], 'device_ms_all': device_ms}
 
 
+def part_map(args):
+    """One process: FilteredPairs to /dev/null with the domain pair (--domains) and with the domain map (--domain-map at the
+    cut-off of --min-domain) on the same loaded file, --repeat times each after a warm-up of both on a small one; the bytes of
+    text each wrote, and the device time of the map runs by step."""
+    import torch
+    from dctdomain_amd import dct_sim
+    min_domain = args.min_domain if args.min_domain is not None else 0.5
+    with tempfile.TemporaryDirectory(dir=args.dir) as tmp:
+        small, path = os.path.join(tmp, 'w-dct.npz'), os.path.join(tmp, 'f-dct.npz')
+        synth(small, 2000, 5)
+        synth(path, args.n, 7)
+        wsid, widx, wfps = dct_sim._load_npz(small)
+        sid, idx, fps = dct_sim._load_npz(path)
+    widx, wfps = plant_families(widx, wfps, 10, 10)
+    if args.families:
+        idx, fps = plant_families(idx, fps, args.families, args.family_size)
+    labels = dct_sim.fingerprint_labels(sid, idx)
+    bound = dct_sim.map_bound(None, min_domain)
+    spans = {}
+
+    def timed(name, label):
+        fn = getattr(dct_sim, name)
+
+        def run(*a, **k):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            out = fn(*a, **k)
+            e1.record()
+            spans.setdefault(label, []).append((e0, e1))
+            return out
+        setattr(dct_sim, name, run)
+        return fn
+
+    def job(s, i, f, names, mapped):
+        fp = dct_sim.FilteredPairs(s, i, f, min_domain, args.min_global, labels=names)
+        return fp.with_map(bound) if mapped else fp
+    written, kept = [0], [0]
+    with open(os.devnull, 'wb', buffering=0) as fh:
+        def sink(mv):
+            fh.write(mv)
+            written[0] += len(mv)
+            kept[0] += bytes(mv).count(b'\n')
+        for mapped in (False, True):
+            job(wsid, widx, wfps, dct_sim.fingerprint_labels(wsid, widx), mapped).write(sink)
+        torch.cuda.synchronize()
+        times, device_ms, sizes = {False: [], True: []}, [], {}
+        for mapped in (False, True):
+            if mapped:
+                steps = (('protein_min', 'tile'), ('l1_matrix', 'tile'), ('tri_filter_count', 'filter'), ('tri_filter_fill', 'filter'),
+                         ('pair_argmin_device', 'pair_argmin'), ('pair_row_best_device', 'pair_row_best'),
+                         ('pair_map_line_lengths', 'line lengths'), ('pair_map_lines', 'lines'))
+                real = [(name, timed(name, label)) for name, label in steps]
+            for _ in range(args.repeat):
+                spans.clear()
+                written[0] = kept[0] = 0
+                fp = job(sid, idx, fps, labels, mapped)
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                fp.write(sink)
+                torch.cuda.synchronize()
+                times[mapped].append(time.perf_counter() - t0)
+                sizes[mapped] = (kept[0], written[0])
+                if mapped:
+                    device_ms.append({label: round(sum(a.elapsed_time(b) for a, b in ev), 3) for label, ev in spans.items()})
+        for name, fn in real:
+            setattr(dct_sim, name, fn)
+    n = len(sid)
+    med = lambda v: sorted(v)[len(v) // 2]   # noqa: E731
+    t_dom, t_map = times[False], times[True]
+    return {'part': 'map', 'n': n, 'fingerprints': int(idx[-1]), 'families': args.families, 'family_size': args.family_size,
+            'min_domain': min_domain, 'min_global': args.min_global, 'map_bound': bound, 'route': fp.route,
+            'domain_lines': sizes[False][0], 'domain_text_bytes': sizes[False][1], 'map_lines': sizes[True][0], 'map_text_bytes': sizes[True][1],
+            'domains_s': [round(t, 3) for t in t_dom], 'map_s': [round(t, 3) for t in t_map],
+            'domains_median_s': round(med(t_dom), 3), 'map_median_s': round(med(t_map), 3),
+            'domains_spread_s': round(max(t_dom) - min(t_dom), 3), 'map_over_domains': round(med(t_map) / med(t_dom), 3),
+            'domains_ns_per_byte': round(1e9 * med(t_dom) / sizes[False][1], 3), 'map_ns_per_byte': round(1e9 * med(t_map) / sizes[True][1], 3),
+            'device_ms_of_median_run': device_ms[t_map.index(med(t_map))], 'device_ms_all': device_ms}
+
+
 def part_base(args):
     """(child) a process that has only initialised the GPU and run one small distance tile: the RSS floor of the run."""
     import torch
@@ -556,7 +636,7 @@ def part_scale(args):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument('--part', required=True, choices=['compare', 'scale', 'filter', 'cluster', 'domains', 'rows_link', 'run', 'base'])
+    ap.add_argument('--part', required=True, choices=['compare', 'scale', 'filter', 'cluster', 'domains', 'map', 'rows_link', 'run', 'base'])
     ap.add_argument('--n', type=int, default=2000)
     ap.add_argument('--dir', default=None, help='where the npz and the text file go (local disk)')
     ap.add_argument('--npz')
@@ -570,7 +650,7 @@ def main():
     ap.add_argument('--min-global', type=float, default=None, help='scale / filter: print the pairs whose DCTglobal is not below this')
     ap.add_argument('--out')
     args = ap.parse_args()
-    res = {'compare': part_compare, 'scale': part_scale, 'filter': part_filter, 'cluster': part_cluster, 'domains': part_domains, 'rows_link': part_rows_link, 'run': part_run, 'base': part_base}[args.part](args)
+    res = {'compare': part_compare, 'scale': part_scale, 'filter': part_filter, 'cluster': part_cluster, 'domains': part_domains, 'map': part_map, 'rows_link': part_rows_link, 'run': part_run, 'base': part_base}[args.part](args)
     line = json.dumps(res)
     print(line)
     if args.out:

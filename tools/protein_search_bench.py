@@ -4,6 +4,7 @@
     python tools/protein_search_bench.py --part kernels [--db 1000000]                    # selection kernels, dctfp_pair_min
     python tools/protein_search_bench.py --part blocks  [--old-db 100000 --old-queries 2000]  # the block-matrix path, and the new one
     python tools/protein_search_bench.py --part argmin  [--db 1000000 --repeat 5]         # dctfp_pair_argmin beside dctfp_pair_min
+    python tools/protein_search_bench.py --part rowbest [--db 1000000 --repeat 5]         # dctfp_pair_row_best beside dctfp_pair_argmin
 
 Each part is its own process (run each under its own time limit).  Data: random int8 fingerprints, 1-12 domains + the whole
 protein per protein, values in [-48, 48] (unrelated proteins at L1 ~ 15 000: similarity 0.1, below the 0.25 threshold) and
@@ -223,6 +224,64 @@ def part_argmin(a):
             'argmin_within_pair_min_spread': med(ms_arg) <= med(ms_min) + (max(ms_min) - min(ms_min))}
 
 
+def part_rowbest(a):
+    """dctfp_pair_row_best beside dctfp_pair_argmin on the 1 M random pairs of `argmin` (the same data, seeds and launch arguments),
+    in one process: --repeat rounds of (pair_argmin x 5, pair_row_best x 5) after a warm-up of both; the best first-side entry of
+    every pair compared with pair_argmin's, a sample against numpy.  Under `rocprofv3 --kernel-trace --stats` the kernel times are
+    the profiler's; the times printed here are hipEvents around five launches."""
+    import ctypes as C
+    import torch
+    from dctdomain_amd import _lib
+    from dctdomain_amd.similarity import pair_row_offsets, to_device_int8
+    idx, dct = synth(a.db, 1)
+    q_idx, q_dct = synth(a.queries, 2)
+    plant(q_idx, q_dct, idx, dct, a.planted, 3)
+    dev = torch.device('cuda')
+    ctx = _lib.get_context(0)
+    stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    rng = np.random.default_rng(7)
+    n_pairs = a.pairs
+    pairs = np.stack([rng.integers(0, len(q_idx) - 1, size=n_pairs), rng.integers(0, a.db, size=n_pairs)], axis=1)
+    off = pair_row_offsets(q_idx, idx, pairs)
+    rows = int(off[-1])
+    da, db = to_device_int8(q_dct), to_device_int8(dct)
+    ia_d, ib_d, off_d = (torch.as_tensor(v, device=dev) for v in (q_idx, idx, off))
+    pairs_d = torch.as_tensor(pairs.astype(np.int32), device=dev)
+    out = [torch.empty(n_pairs, dtype=torch.int32, device=dev) for _ in range(4)]
+    l1_d, arg_d = (torch.full((rows,), -7, dtype=torch.int32, device=dev) for _ in range(2))
+    head = (ctx.handle, pairs_d.data_ptr(), n_pairs, da.data_ptr(), 480, ia_d.data_ptr(), len(q_idx) - 1, db.data_ptr(), 480, ib_d.data_ptr(),
+            a.db, 480)
+
+    def run_argmin():
+        _lib.check(ctx._lib.dctfp_pair_argmin(*head, *(t.data_ptr() for t in out), stream))
+
+    def run_best():
+        _lib.check(ctx._lib.dctfp_pair_row_best(*head, off_d.data_ptr(), rows, l1_d.data_ptr(), arg_d.data_ptr(), stream))
+    run_argmin()
+    run_best()
+    sync()
+    ms_arg, ms_best = [], []
+    for _ in range(a.repeat):
+        ms_arg.append(round(_events_ms(run_argmin, 5), 4))
+        ms_best.append(round(_events_ms(run_best, 5), 4))
+    mn, _, arg_a, arg_b = (t.cpu().numpy().astype(np.int64) for t in out)
+    l1, arg = l1_d.cpu().numpy().astype(np.int64), arg_d.cpu().numpy().astype(np.int64)
+    assert (l1 >= 0).all() and (arg >= 0).all()                 # (every protein has rows: every entry was written)
+    k = q_idx[pairs[:, 0] + 1] - q_idx[pairs[:, 0]]
+    assert np.array_equal(np.minimum.reduceat(l1, off[:-1]), mn)      # (the smallest entry of a pair, on either side, is its minimum)
+    for t in rng.integers(0, n_pairs, size=200).tolist():
+        i, j = pairs[t]
+        blk = np.abs(q_dct[q_idx[i]:q_idx[i + 1]].astype(np.int16)[:, None] - dct[idx[j]:idx[j + 1]].astype(np.int16)[None]).sum(-1)
+        assert l1[off[t]:off[t] + k[t]].tolist() == blk.min(1).tolist() and arg[off[t]:off[t] + k[t]].tolist() == blk.argmin(1).tolist()
+        assert l1[off[t] + k[t]:off[t + 1]].tolist() == blk.min(0).tolist() and arg[off[t] + k[t]:off[t + 1]].tolist() == blk.argmin(0).tolist()
+        r = int(np.argmin(l1[off[t]:off[t] + k[t]]))
+        assert mn[t] == blk.min() and (mn[t] >= 17000 or (arg_a[t], arg_b[t]) == (r, arg[off[t] + r]))
+    med = lambda v: sorted(v)[len(v) // 2]   # noqa: E731
+    return {'part': 'rowbest', 'pairs': n_pairs, 'db': a.db, 'rows_written': rows, 'pair_argmin_ms': ms_arg, 'pair_row_best_ms': ms_best,
+            'pair_argmin_median_ms': med(ms_arg), 'pair_row_best_median_ms': med(ms_best),
+            'pair_argmin_spread_ms': round(max(ms_arg) - min(ms_arg), 4), 'row_best_over_argmin': round(med(ms_best) / med(ms_arg), 4)}
+
+
 def part_blocks(a):
     import torch
     from dctdomain_amd import dct_sim
@@ -269,8 +328,8 @@ def part_blocks(a):
 
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument('--part', choices=('search', 'kernels', 'blocks', 'argmin'), required=True)
-    ap.add_argument('--repeat', type=int, default=5, help='argmin: rounds of both kernels')
+    ap.add_argument('--part', choices=('search', 'kernels', 'blocks', 'argmin', 'rowbest'), required=True)
+    ap.add_argument('--repeat', type=int, default=5, help='argmin / rowbest: rounds of both kernels')
     ap.add_argument('--db', type=int, default=1_000_000)
     ap.add_argument('--queries', type=int, default=10_000)
     ap.add_argument('--old-db', type=int, default=100_000)
@@ -284,7 +343,7 @@ def main(argv=None):
     import torch
     if not torch.cuda.is_available():
         raise SystemExit('protein_search_bench needs the GPU')
-    res = {'search': part_search, 'kernels': part_kernels, 'blocks': part_blocks, 'argmin': part_argmin}[a.part](a)
+    res = {'search': part_search, 'kernels': part_kernels, 'blocks': part_blocks, 'argmin': part_argmin, 'rowbest': part_rowbest}[a.part](a)
     line = json.dumps(res)
     print(line, flush=True)
     if a.out:
