@@ -2568,13 +2568,24 @@ int dctfp_stitch_sequences(dctfp_ctx* ctx, const void* const* win, const int32_t
     return stitch_impl(ctx, jobs.data(), (int64_t)jobs.size(), n_cols, square, stream_v, simple ? once.data() : nullptr);
 } DCTFP_GUARD("dctfp_stitch_sequences")
 
+// Whether ONE launch takes n items at `per` items to a workgroup of `threads`: HIP launches nothing whose gridDim.x * blockDim.x
+// reaches 2^32 (hip_runtime_api.h, hipModuleLaunchKernel), so a grid has at most (2^32 - 1) / threads workgroups.  Written so
+// that no n overflows; launch_items(per, threads) is the number the messages and include/dctfp.h state.
+constexpr int64_t launch_items(int64_t per, int64_t threads) { return (int64_t)(0xffffffffu / threads) * per; }
+constexpr bool one_launch(int64_t n, int64_t per, int64_t threads) { return n <= launch_items(per, threads); }
+// Whether the `count` entries from `first` on lie within [0, n), for arguments that are not negative: first + count may not be formed,
+// an int64 near its end wraps and the check passes (the kernels bound no index: what passes here is what they touch).
+constexpr bool range_within(int64_t first, int64_t count, int64_t n) { return count <= n && first <= n - count; }
+
 int dctfp_l1_matrix(dctfp_ctx* ctx, const int8_t* a, int64_t na, int64_t lda, const int8_t* b, int64_t nb, int64_t ldb,
                     int32_t d, int32_t* out, int64_t ldo, void* stream_v) try {
     if (!ctx || !a || !b || !out) return fail(DCTFP_ERR_INVALID, "dctfp_l1_matrix: NULL argument");
     std::lock_guard<std::mutex> lock(ctx->mu);
     if (na < 0 || nb < 0 || d < 1 || lda < d || ldb < d || ldo < nb) return fail(DCTFP_ERR_INVALID, "dctfp_l1_matrix: bad shape");
     if (na == 0 || nb == 0) return DCTFP_OK;
-    if ((na + 127) / 128 > 65535) return fail(DCTFP_ERR_LIMIT, "dctfp_l1_matrix: more than 8M rows per call");
+    if (na > 65535 * 128) return fail(DCTFP_ERR_LIMIT, "dctfp_l1_matrix: more than 8M rows per call");
+    // (128 columns to a 256-thread workgroup along gridDim.x)
+    if (!one_launch(nb, 128, 256)) return fail(DCTFP_ERR_LIMIT, "dctfp_l1_matrix: more than %lld columns per call", (long long)launch_items(128, 256));
     HIP_TRY(hipSetDevice(ctx->device));
     hipStream_t stream = (hipStream_t)stream_v;
     dim3 grid((unsigned)((nb + 127) / 128), (unsigned)((na + 127) / 128));  // 128 x 128 distances per workgroup (l1_matrix_kernel)
@@ -2592,6 +2603,9 @@ int dctfp_block_min(dctfp_ctx* ctx, const int32_t* dist, int64_t ldo, const int6
     std::lock_guard<std::mutex> lock(ctx->mu);
     if (npa < 0 || npb < 0) return fail(DCTFP_ERR_INVALID, "dctfp_block_min: negative count");
     if (npa == 0 || npb == 0) return DCTFP_OK;
+    // (one thread per protein pair in 256-thread workgroups)
+    if (npa > launch_items(256, 256) / npb)
+        return fail(DCTFP_ERR_LIMIT, "dctfp_block_min: more than %lld protein pairs (npa x npb) per call", (long long)launch_items(256, 256));
     HIP_TRY(hipSetDevice(ctx->device));
     const int64_t total = npa * npb;
     hipLaunchKernelGGL(block_min_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream_v, dist, ldo,
@@ -2606,7 +2620,9 @@ int dctfp_row_select(dctfp_ctx* ctx, const int32_t* dist, int64_t n_rows, int64_
     std::lock_guard<std::mutex> lock(ctx->mu);
     if (n_rows < 0 || n_cols < 1 || ld < n_cols || k < 1 || k > n_cols) return fail(DCTFP_ERR_INVALID, "dctfp_row_select: bad shape");
     if (n_rows == 0) return DCTFP_OK;
-    if (n_rows > 0x7fffffff) return fail(DCTFP_ERR_LIMIT, "dctfp_row_select: too many rows");
+    // (one workgroup of up to 1024 threads to a row)
+    if (!one_launch(n_rows, 1, 1024)) return fail(DCTFP_ERR_LIMIT, "dctfp_row_select: more than %lld rows per call", (long long)launch_items(1, 1024));
+    if (n_cols > 0x7fffffff) return fail(DCTFP_ERR_LIMIT, "dctfp_row_select: more than 2^31 - 1 columns (out_idx is int32)");
     HIP_TRY(hipSetDevice(ctx->device));
     hipStream_t stream = (hipStream_t)stream_v;
     Hold scratch{ctx->scratch, stream};   // (given back when the candidates were used: the destructor)
@@ -2616,7 +2632,7 @@ int dctfp_row_select(dctfp_ctx* ctx, const int32_t* dist, int64_t n_rows, int64_
     constexpr int kPer = 40;
     constexpr int64_t kSeg = 1024 * kPer;
     const int64_t n_seg = (n_cols + kSeg - 1) / kSeg;
-    const bool reg_ok = ctx->opt_row_select != 1 && k <= 1024 && n_rows * n_seg <= 0x7fffffff && (n_seg == 1 || n_seg * k <= kSeg);
+    const bool reg_ok = ctx->opt_row_select != 1 && k <= 1024 && one_launch(n_rows * n_seg, 1, 512) && (n_seg == 1 || n_seg * k <= kSeg);
     if (reg_ok && n_seg == 1) {
         hipLaunchKernelGGL((row_select_reg_kernel<2 * kPer, false, 512>), dim3((unsigned)n_rows), dim3(512), 0, stream, dist, (const int32_t*)nullptr,
                            ld, n_cols, kSeg, (int64_t)1, (int)k, out_val, out_idx);
@@ -2642,7 +2658,8 @@ int dctfp_row_order(dctfp_ctx* ctx, int32_t* val, int32_t* idx, int64_t n_rows, 
     std::lock_guard<std::mutex> lock(ctx->mu);
     if (n_rows < 0 || k < 1) return fail(DCTFP_ERR_INVALID, "dctfp_row_order: bad shape");
     if (k > 1024) return fail(DCTFP_ERR_LIMIT, "dctfp_row_order: more than 1024 entries per row (order them on the host)");
-    if (n_rows > 0x7fffffff) return fail(DCTFP_ERR_LIMIT, "dctfp_row_order: too many rows");
+    // (one workgroup of up to 512 threads to a row)
+    if (!one_launch(n_rows, 1, 512)) return fail(DCTFP_ERR_LIMIT, "dctfp_row_order: more than %lld rows per call", (long long)launch_items(1, 512));
     if (n_rows == 0 || k == 1) return DCTFP_OK;
     HIP_TRY(hipSetDevice(ctx->device));
     hipStream_t stream = (hipStream_t)stream_v;
@@ -2661,7 +2678,8 @@ static int pair_min_call(const char* name, dctfp_ctx* ctx, const int32_t* pairs,
     std::lock_guard<std::mutex> lock(ctx->mu);
     if (n_pairs < 0 || npa < 0 || npb < 0 || d < 1 || lda < d || ldb < d) return fail(DCTFP_ERR_INVALID, "%s: bad shape", name);
     if (npa > 0x7fffffff || npb > 0x7fffffff) return fail(DCTFP_ERR_LIMIT, "%s: more than 2^31 - 1 proteins on a side", name);
-    if ((n_pairs + 3) / 4 > 0x7fffffff) return fail(DCTFP_ERR_LIMIT, "%s: too many pairs per call", name);
+    // (four pairs to a 256-thread workgroup)
+    if (!one_launch(n_pairs, 4, 256)) return fail(DCTFP_ERR_LIMIT, "%s: more than %lld pairs per call", name, (long long)launch_items(4, 256));
     if (n_pairs == 0) return DCTFP_OK;
     HIP_TRY(hipSetDevice(ctx->device));
     launch_pair_argmin(pairs, n_pairs, a, lda, idx_a, npa, b, ldb, idx_b, npb, d, out_min, out_last, out_arg_a, out_arg_b, (hipStream_t)stream_v);
@@ -2692,7 +2710,8 @@ int dctfp_pair_row_best(dctfp_ctx* ctx, const int32_t* pairs, int64_t n_pairs, c
     std::lock_guard<std::mutex> lock(ctx->mu);
     if (n_pairs < 0 || npa < 0 || npb < 0 || d < 1 || lda < d || ldb < d || out_len < 0) return fail(DCTFP_ERR_INVALID, "dctfp_pair_row_best: bad shape");
     if (npa > 0x7fffffff || npb > 0x7fffffff) return fail(DCTFP_ERR_LIMIT, "dctfp_pair_row_best: more than 2^31 - 1 proteins on a side");
-    if ((n_pairs + 3) / 4 > 0x7fffffff) return fail(DCTFP_ERR_LIMIT, "dctfp_pair_row_best: too many pairs per call");
+    if (!one_launch(n_pairs, 4, 256))
+        return fail(DCTFP_ERR_LIMIT, "dctfp_pair_row_best: more than %lld pairs per call", (long long)launch_items(4, 256));
     if (n_pairs == 0) return DCTFP_OK;
     HIP_TRY(hipSetDevice(ctx->device));
     launch_pair_row_best(pairs, n_pairs, a, lda, idx_a, npa, b, ldb, idx_b, npb, d, row_off, out_len, out_l1, out_arg, (hipStream_t)stream_v);
@@ -2752,7 +2771,9 @@ int dctfp_select_count(dctfp_ctx* ctx, const int32_t* dist, int64_t n_rows, int6
     if (n_rows < 0 || n_cols < 1 || ld < n_cols || top < 1 || cap < 0 || bound < -1 || bound > cap)
         return fail(DCTFP_ERR_INVALID, "dctfp_select_count: bad shape or bound");
     if (cap > select_max_cap()) return fail(DCTFP_ERR_LIMIT, "dctfp_select_count: cap above %d", select_max_cap());
-    if (n_rows > 0x7fffffff || n_cols > 0x7fffffff) return fail(DCTFP_ERR_LIMIT, "dctfp_select_count: more than 2^31 - 1 rows or columns");
+    // (one 1024-thread workgroup to a row)
+    if (!one_launch(n_rows, 1, 1024) || n_cols > 0x7fffffff)
+        return fail(DCTFP_ERR_LIMIT, "dctfp_select_count: more than %lld rows per call or 2^31 - 1 columns", (long long)launch_items(1, 1024));
     if (n_rows == 0) return DCTFP_OK;
     HIP_TRY(hipSetDevice(ctx->device));
     launch_select_count(dist, n_rows, n_cols, ld, row_empty, col_empty, cap, bound, top, out_count, out_cut, (hipStream_t)stream_v);
@@ -2767,7 +2788,8 @@ int dctfp_select_fill(dctfp_ctx* ctx, const int32_t* dist, int64_t n_rows, int64
     std::lock_guard<std::mutex> lock(ctx->mu);
     if (n_rows < 0 || n_cols < 1 || ld < n_cols || cap < 0 || max_count < 0) return fail(DCTFP_ERR_INVALID, "dctfp_select_fill: bad shape");
     if (cap > select_max_cap()) return fail(DCTFP_ERR_LIMIT, "dctfp_select_fill: cap above %d", select_max_cap());
-    if (n_rows > 0x7fffffff || n_cols > 0x7fffffff) return fail(DCTFP_ERR_LIMIT, "dctfp_select_fill: more than 2^31 - 1 rows or columns");
+    if (!one_launch(n_rows, 1, 1024) || n_cols > 0x7fffffff)
+        return fail(DCTFP_ERR_LIMIT, "dctfp_select_fill: more than %lld rows per call or 2^31 - 1 columns", (long long)launch_items(1, 1024));
     if (n_rows == 0) return DCTFP_OK;
     HIP_TRY(hipSetDevice(ctx->device));
     launch_select_fill(dist, n_rows, n_cols, ld, row_empty, col_empty, cap, cut, offsets, max_count, out_key, out_col, (hipStream_t)stream_v);
@@ -2781,8 +2803,8 @@ int dctfp_sim_lines(dctfp_ctx* ctx, const int32_t* mn, const int32_t* last, int6
     if (!ctx || !mn || !last || !ids || !id_off || !table || !row_base || !out) return fail(DCTFP_ERR_INVALID, "dctfp_sim_lines: NULL argument");
     std::lock_guard<std::mutex> lock(ctx->mu);
     if (n_rows < 0 || n_cols < 0 || ld < n_cols || row0 < 0 || col0 < 0) return fail(DCTFP_ERR_INVALID, "dctfp_sim_lines: bad shape");
-    // (one 256-thread workgroup per 256 columns; gridDim.x * blockDim.x must stay below 2^32)
-    if ((n_cols + 255) / 256 > (int64_t)(0xffffffffu / 256)) return fail(DCTFP_ERR_LIMIT, "dctfp_sim_lines: more than 2^32 - 256 columns per call");
+    // (one 256-thread workgroup per 256 columns)
+    if (!one_launch(n_cols, 256, 256)) return fail(DCTFP_ERR_LIMIT, "dctfp_sim_lines: more than 2^32 - 256 columns per call");
     if (n_rows == 0 || n_cols == 0) return DCTFP_OK;
     HIP_TRY(hipSetDevice(ctx->device));
     launch_sim_lines(mn, last, ld, n_rows, row0, col0, n_cols, ids, id_off, table, row_base, out, (hipStream_t)stream_v);
@@ -2801,7 +2823,7 @@ static int check_tri_tile(const char* name, const TriTile& t) {
 // ... and of the node arrays beside it: every (i, j) a kernel can form lies inside the tile, so the nodes are bounded here, on the
 // host, and not on the device.
 static int check_tri_nodes(const char* name, const TriTile& t, int64_t n_nodes) {
-    if (n_nodes < 0 || t.row0 + t.n_rows > n_nodes || t.col0 + t.n_cols > n_nodes)
+    if (n_nodes < 0 || !range_within(t.row0, t.n_rows, n_nodes) || !range_within(t.col0, t.n_cols, n_nodes))
         return fail(DCTFP_ERR_INVALID, "%s: the tile names proteins outside the nodes", name);
     return DCTFP_OK;
 }
@@ -2813,7 +2835,7 @@ int dctfp_tri_filter_count(dctfp_ctx* ctx, const int32_t* tile, int64_t n_rows, 
     std::lock_guard<std::mutex> lock(ctx->mu);
     const TriTile t{tile, n_rows, n_cols, ld, row0, col0, row_empty, col_empty, cap, bound};
     RC_TRY(check_tri_tile("dctfp_tri_filter_count", t));
-    if (row0 + n_rows > 0x7fffffff || col0 + n_cols > 0x7fffffff)
+    if (!range_within(row0, n_rows, 0x7fffffff) || !range_within(col0, n_cols, 0x7fffffff))
         return fail(DCTFP_ERR_LIMIT, "dctfp_tri_filter_count: protein indices above 2^31 - 1");
     if (n_rows == 0) return DCTFP_OK;   // (n_cols == 0 still launches: the counts are zeros, written)
     HIP_TRY(hipSetDevice(ctx->device));
@@ -2830,7 +2852,7 @@ int dctfp_tri_filter_fill(dctfp_ctx* ctx, const int32_t* tile, int64_t n_rows, i
     const TriTile t{tile, n_rows, n_cols, ld, row0, col0, row_empty, col_empty, cap, bound};
     RC_TRY(check_tri_tile("dctfp_tri_filter_fill", t));
     if (out_len < 0) return fail(DCTFP_ERR_INVALID, "dctfp_tri_filter_fill: negative out_len");
-    if (row0 + n_rows > 0x7fffffff || col0 + n_cols > 0x7fffffff)
+    if (!range_within(row0, n_rows, 0x7fffffff) || !range_within(col0, n_cols, 0x7fffffff))
         return fail(DCTFP_ERR_LIMIT, "dctfp_tri_filter_fill: protein indices above 2^31 - 1");
     if (n_rows == 0 || n_cols == 0 || out_len == 0) return DCTFP_OK;
     HIP_TRY(hipSetDevice(ctx->device));
@@ -2848,8 +2870,8 @@ static int pair_lines_call(const char* name, dctfp_ctx* ctx, int64_t n_lines, co
         return fail(DCTFP_ERR_INVALID, "%s: NULL argument", name);
     std::lock_guard<std::mutex> lock(ctx->mu);
     if (n_lines < 0 || n_ids < 0 || n_labels < 0 || out_bytes < 0) return fail(DCTFP_ERR_INVALID, "%s: bad shape", name);
-    // (sixteen lanes per line in 256-thread workgroups; the grid must stay below 2^32 workgroups)
-    if (n_lines > (int64_t)1 << 31) return fail(DCTFP_ERR_LIMIT, "%s: more than 2^31 lines per call", name);
+    // (sixteen lanes per line: sixteen lines to a 256-thread workgroup)
+    if (!one_launch(n_lines, 16, 256)) return fail(DCTFP_ERR_LIMIT, "%s: more than %lld lines per call", name, (long long)launch_items(16, 256));
     if (n_lines == 0) return DCTFP_OK;
     HIP_TRY(hipSetDevice(ctx->device));
     launch_pair_domain_lines(n_lines, pi, pj, mn, last, la, lb, ids, id_off, n_ids, labels, label_off, n_labels, table, line_off, out,
@@ -2887,7 +2909,8 @@ int dctfp_pair_map_lines(dctfp_ctx* ctx, int64_t n_lines, const int32_t* pi, con
     // (a matched row prints the score of its L1 from the table: no bound at or above similarity 0, dctfp_pair_argmin's "no pair")
     if (bound >= 17000) return fail(DCTFP_ERR_INVALID, "dctfp_pair_map_lines: the bound must be below 17000");
     // (dctfp_pair_lines' grid: sixteen lanes per line in 256-thread workgroups)
-    if (n_lines > (int64_t)1 << 31) return fail(DCTFP_ERR_LIMIT, "dctfp_pair_map_lines: more than 2^31 lines per call");
+    if (!one_launch(n_lines, 16, 256))
+        return fail(DCTFP_ERR_LIMIT, "dctfp_pair_map_lines: more than %lld lines per call", (long long)launch_items(16, 256));
     if (n_lines == 0) return DCTFP_OK;
     HIP_TRY(hipSetDevice(ctx->device));
     launch_pair_map_lines(n_lines, pi, pj, mn, last, la, lb, ids, id_off, n_ids, labels, label_off, n_labels, table, first_row, row_off, n_rows,
@@ -2917,7 +2940,7 @@ int dctfp_link_pairs(dctfp_ctx* ctx, const int32_t* pi, const int32_t* pj, int64
     if (!ctx || !parent || ((!pi || !pj) && n_pairs > 0)) return fail(DCTFP_ERR_INVALID, "dctfp_link_pairs: NULL argument");
     std::lock_guard<std::mutex> lock(ctx->mu);
     if (n_pairs < 0 || n_nodes < 0) return fail(DCTFP_ERR_INVALID, "dctfp_link_pairs: bad shape");
-    // (one thread per pair in 256-thread workgroups: 2^23 workgroups at most, as dctfp_pair_lines' limit)
+    // (one thread per pair in 256-thread workgroups: 2^31 pairs are 2^23 workgroups, 2^31 threads)
     if (n_nodes > 0x7fffffff || n_pairs > (int64_t)1 << 31) return fail(DCTFP_ERR_LIMIT, "dctfp_link_pairs: more than 2^31 - 1 nodes or 2^31 pairs per call");
     if (n_pairs == 0 || n_nodes == 0) return DCTFP_OK;
     HIP_TRY(hipSetDevice(ctx->device));
@@ -2947,9 +2970,11 @@ int dctfp_rows_link(dctfp_ctx* ctx, const int8_t* a, int64_t na, int64_t lda, in
         return fail(DCTFP_ERR_INVALID, "dctfp_rows_link: bad shape or bound");
     if (n_nodes > 0x7fffffff) return fail(DCTFP_ERR_LIMIT, "dctfp_rows_link: more than 2^31 - 1 nodes");
     // (every node the kernel can form is a row of a or b: bounded here, not on the device)
-    if (a0 + na > n_nodes || b0 + nb > n_nodes) return fail(DCTFP_ERR_INVALID, "dctfp_rows_link: the rows name nodes outside parent");
+    if (!range_within(a0, na, n_nodes) || !range_within(b0, nb, n_nodes)) return fail(DCTFP_ERR_INVALID, "dctfp_rows_link: the rows name nodes outside parent");
     if (na == 0 || nb == 0) return DCTFP_OK;
-    if ((na + 127) / 128 > 65535) return fail(DCTFP_ERR_LIMIT, "dctfp_rows_link: more than 8M rows of a per call");
+    if (na > 65535 * 128) return fail(DCTFP_ERR_LIMIT, "dctfp_rows_link: more than 8M rows of a per call");
+    // (128 rows of b to a 256-thread workgroup along gridDim.x)
+    if (!one_launch(nb, 128, 256)) return fail(DCTFP_ERR_LIMIT, "dctfp_rows_link: more than %lld rows of b per call", (long long)launch_items(128, 256));
     HIP_TRY(hipSetDevice(ctx->device));
     launch_rows_link(a, na, lda, a0, b, nb, ldb, b0, d, owner, skip, cap, bound, parent, (hipStream_t)stream_v);
     HIP_TRY(hipGetLastError());
@@ -2965,7 +2990,9 @@ int dctfp_rows_assign(dctfp_ctx* ctx, const int8_t* a, int64_t na, int64_t lda, 
         return fail(DCTFP_ERR_INVALID, "dctfp_rows_assign: bad shape or bound");
     if (n_assign > 0x7fffffff) return fail(DCTFP_ERR_LIMIT, "dctfp_rows_assign: more than 2^31 - 1 entries of assign");
     if (na == 0 || nb == 0 || n_assign == 0) return DCTFP_OK;
-    if ((na + 127) / 128 > 65535) return fail(DCTFP_ERR_LIMIT, "dctfp_rows_assign: more than 8M rows of a per call");
+    if (na > 65535 * 128) return fail(DCTFP_ERR_LIMIT, "dctfp_rows_assign: more than 8M rows of a per call");
+    // (128 rows of b to a 256-thread workgroup along gridDim.x)
+    if (!one_launch(nb, 128, 256)) return fail(DCTFP_ERR_LIMIT, "dctfp_rows_assign: more than %lld rows of b per call", (long long)launch_items(128, 256));
     HIP_TRY(hipSetDevice(ctx->device));
     // (slots and values are bounded on the device: the host cannot see value_a and slot_b)
     launch_rows_assign(a, na, lda, value_a, a0, b, nb, ldb, slot_b, b0, d, cap, bound, assign, n_assign, (hipStream_t)stream_v);
@@ -3032,7 +3059,8 @@ int dctfp_rect_best(dctfp_ctx* ctx, const int32_t* tile, int64_t n_rows, int64_t
         return fail(DCTFP_ERR_INVALID, "dctfp_rect_best: a cap above %d does not fit the packed minima of a row", rect_best_max_cap());
     if (n_a < 0 || n_b < 0 || n_a > 0x7fffffff || n_b > 0x7fffffff) return fail(DCTFP_ERR_INVALID, "dctfp_rect_best: n_a and n_b must lie in 0 .. 2^31 - 1");
     // (every index the kernel can form lies inside the tile: bounded here, on the host, and not on the device)
-    if (row0 + n_rows > n_a || col0 + n_cols > n_b) return fail(DCTFP_ERR_INVALID, "dctfp_rect_best: the tile names proteins outside best_row / best_col");
+    if (!range_within(row0, n_rows, n_a) || !range_within(col0, n_cols, n_b))
+        return fail(DCTFP_ERR_INVALID, "dctfp_rect_best: the tile names proteins outside best_row / best_col");
     if (n_rows == 0 || n_cols == 0) return DCTFP_OK;
     HIP_TRY(hipSetDevice(ctx->device));
     launch_rect_best(TriTile{tile, n_rows, n_cols, ld, row0, col0, row_empty, col_empty, cap, bound}, best_row, best_col, (hipStream_t)stream_v);
@@ -3160,7 +3188,8 @@ int dctfp_rect_moments(dctfp_ctx* ctx, const int32_t* tile, int64_t n_rows, int6
     if (!row_mom && !col_mom) return fail(DCTFP_ERR_INVALID, "dctfp_rect_moments: row_mom and col_mom are both NULL");
     std::lock_guard<std::mutex> lock(ctx->mu);
     // (a rectangle with three words per protein, either side optional: its own few conditions)
-    if (n_rows < 0 || n_cols < 0 || n_rows > 0x7fffffff || n_cols > 0x7fffffff || ld < n_cols || row0 < 0 || col0 < 0 || cap < 0)
+    if (n_rows < 0 || n_cols < 0 || n_rows > 0x7fffffff || n_cols > 0x7fffffff || ld < n_cols || row0 < 0 || col0 < 0 || row0 > 0x7fffffff ||
+        col0 > 0x7fffffff || cap < 0)
         return fail(DCTFP_ERR_INVALID, "dctfp_rect_moments: bad shape or cap");
     if (((reinterpret_cast<uintptr_t>(tile) & 3u) | ((reinterpret_cast<uintptr_t>(row_mom) | reinterpret_cast<uintptr_t>(col_mom)) & 7u)) != 0)
         return fail(DCTFP_ERR_INVALID, "dctfp_rect_moments: the tile is not 4-byte aligned or row_mom / col_mom not 8-byte aligned");
@@ -3168,7 +3197,7 @@ int dctfp_rect_moments(dctfp_ctx* ctx, const int32_t* tile, int64_t n_rows, int6
         return fail(DCTFP_ERR_INVALID, "dctfp_rect_moments: a cap above %d does not fit the 32-bit partial sums of a row", rect_moments_max_cap());
     if (n_a < 0 || n_b < 0 || n_a > 0x7fffffff || n_b > 0x7fffffff) return fail(DCTFP_ERR_INVALID, "dctfp_rect_moments: n_a and n_b must lie in 0 .. 2^31 - 1");
     // (every index the kernel can form lies inside the tile and the arrays it was given: bounded here, on the host, and not on the device)
-    if ((row_mom && row0 + n_rows > n_a) || (col_mom && col0 + n_cols > n_b))
+    if ((row_mom && !range_within(row0, n_rows, n_a)) || (col_mom && !range_within(col0, n_cols, n_b)))
         return fail(DCTFP_ERR_INVALID, "dctfp_rect_moments: the tile names proteins outside row_mom / col_mom");
     // a row's words add up over the columns it meets and a column's over its rows: n_b resp. n_a of them, at least this tile's
     if (cap > 1) {
@@ -3242,7 +3271,7 @@ int dctfp_l1_knn(dctfp_ctx* ctx, const int8_t* q, int64_t nq, int64_t ldq, const
         return fail(DCTFP_ERR_INVALID, "dctfp_l1_knn: fingerprint rows must start on 16-byte boundaries");
     if (nq == 0 || nb == 0) return DCTFP_OK;
     if (k > 1024 || d > 512) return fail(DCTFP_ERR_LIMIT, "dctfp_l1_knn: k above 1024 or rows above 512 bytes (use l1_matrix + row_select)");
-    if ((nq + 127) / 128 > 65535 || nb + col0 > 0x7fffffff || ldq >= (1 << 24) || ldb >= (1 << 24))
+    if (nq > 65535 * 128 || !range_within(col0, nb, 0x7fffffff) || ldq >= (1 << 24) || ldb >= (1 << 24))
         return fail(DCTFP_ERR_LIMIT, "dctfp_l1_knn: more than 8M query rows, 2^31 - 1 columns or 2^24-byte rows per call");
     HIP_TRY(hipSetDevice(ctx->device));
     hipStream_t stream = (hipStream_t)stream_v;
@@ -3263,7 +3292,9 @@ int dctfp_query_rank(dctfp_ctx* ctx, const int32_t* val, const int32_t* idx, int
         return fail(DCTFP_ERR_INVALID, "dctfp_query_rank: NULL argument");
     std::lock_guard<std::mutex> lock(ctx->mu);
     if (n_rows < 0 || k < 1 || khits < 1) return fail(DCTFP_ERR_INVALID, "dctfp_query_rank: bad shape");
-    if (n_rows * (int64_t)k > (int64_t)0xffffffffu * 256 / 2) return fail(DCTFP_ERR_LIMIT, "dctfp_query_rank: too many hits per call");
+    // (one thread per hit in 256-thread workgroups)
+    if (n_rows > launch_items(256, 256) / k)
+        return fail(DCTFP_ERR_LIMIT, "dctfp_query_rank: more than %lld hits (n_rows x k) per call", (long long)launch_items(256, 256));
     if (n_rows == 0) return DCTFP_OK;
     HIP_TRY(hipSetDevice(ctx->device));
     launch_query_rank(val, idx, n_rows, k, qoff, prot_of_row, line_base, khits, out_qrow, out_drow, out_dist, (hipStream_t)stream_v);
@@ -3280,7 +3311,8 @@ int dctfp_query_lines(dctfp_ctx* ctx, int64_t n_lines, const int32_t* qrow, cons
         return fail(DCTFP_ERR_INVALID, "dctfp_query_lines: NULL argument");
     std::lock_guard<std::mutex> lock(ctx->mu);
     if (n_lines < 0) return fail(DCTFP_ERR_INVALID, "dctfp_query_lines: bad shape");
-    if ((n_lines + 255) / 256 > (int64_t)0xffffffffu / 256) return fail(DCTFP_ERR_LIMIT, "dctfp_query_lines: too many lines per call");
+    if (!one_launch(n_lines, 256, 256))
+        return fail(DCTFP_ERR_LIMIT, "dctfp_query_lines: more than %lld lines per call", (long long)launch_items(256, 256));
     if (n_lines == 0) return DCTFP_OK;
     HIP_TRY(hipSetDevice(ctx->device));
     launch_query_lines(n_lines, qrow, drow, dist, rank, q_txt, q_pid_off, q_dom_off, d_txt, d_pid_off, d_dom_off, score_txt, score_off, line_off,

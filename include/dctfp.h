@@ -277,26 +277,32 @@ int dctfp_stitch_sequences(dctfp_ctx* ctx, const void* const* win, const int32_t
 /* L1 distance matrix between two sets of int8 fingerprints, the quantity under the
  * reference's similarity scores 1 - min(L1 / 17000, 1) (src/dct-sim.py:12-26) and
  * round(1 - L1 / 17000, 4) (src/query_db.py:57; FAISS METRIC_L1, :76):
- *     out[i * ldo + j] = sum_k |a[i * lda + k] - b[j * ldb + k]|,  k < d.   All device pointers. */
+ *     out[i * ldo + j] = sum_k |a[i * lda + k] - b[j * ldb + k]|,  k < d.   All device pointers.  DCTFP_ERR_LIMIT above 8M
+ * (8388480) rows of a or 2147483520 rows of b per call (128 x 128 distances to a 256-thread workgroup, and one launch holds
+ * fewer than 2^32 threads along the columns, 65535 workgroups along the rows). */
 int dctfp_l1_matrix(dctfp_ctx* ctx, const int8_t* a, int64_t na, int64_t lda, const int8_t* b, int64_t nb, int64_t ldb,
                     int32_t d, int32_t* out, int64_t ldo, void* stream);
 
 /* domain_sim (src/dct-sim.py:28-50) on a distance matrix: protein pa owns rows
  * [idx_a[pa], idx_a[pa+1]), protein pb columns [idx_b[pb], idx_b[pb+1]) (device int64 prefix
  * arrays, the npz "idx"); out_min[pa*npb+pb] = smallest distance of the block (-> DCTdomain),
- * out_last = its last row / last column entry (-> DCTglobal). */
+ * out_last = its last row / last column entry (-> DCTglobal).  DCTFP_ERR_LIMIT above 4294967040 protein pairs (npa x npb) per
+ * call: one thread per pair, and one launch holds fewer than 2^32 threads. */
 int dctfp_block_min(dctfp_ctx* ctx, const int32_t* dist, int64_t ldo, const int64_t* idx_a, int64_t npa,
                     const int64_t* idx_b, int64_t npb, int32_t* out_min, int32_t* out_last, void* stream);
 
 /* The k nearest database fingerprints of every query fingerprint: the k smallest entries of each row of an
  * int32 distance matrix (dctfp_l1_matrix), ties to the lower column as a flat index scan returns them
- * (index.search at src/query_db.py:87).  out_val / out_idx: device int32 (n_rows, k), unordered within a row. */
+ * (index.search at src/query_db.py:87).  out_val / out_idx: device int32 (n_rows, k), unordered within a row.  DCTFP_ERR_LIMIT
+ * above 4194303 rows per call (a workgroup of up to 1024 threads per row, and one launch holds fewer than 2^32 threads) or
+ * 2^31 - 1 columns (out_idx is int32). */
 int dctfp_row_select(dctfp_ctx* ctx, const int32_t* dist, int64_t n_rows, int64_t n_cols, int64_t ld, int32_t k,
                      int32_t* out_val, int32_t* out_idx, void* stream);
 
 /* Orders what dctfp_row_select left, in place and on the device: each row's k (value, column) pairs ascending by value, ties by
  * column -- the order in which a flat L1 index reports its hits (src/query_db.py:87).  k <= 1024 (DCTFP_ERR_LIMIT beyond:
- * order those on the host). */
+ * order those on the host) and at most 8388607 rows per call (DCTFP_ERR_LIMIT: a workgroup of up to 512 threads per row, and one
+ * launch holds fewer than 2^32 threads). */
 int dctfp_row_order(dctfp_ctx* ctx, int32_t* val, int32_t* idx, int64_t n_rows, int32_t k, void* stream);
 
 /* domain_sim (src/dct-sim.py:28-50) for a list of protein pairs, straight from the fingerprints -- no distance matrix: pair p
@@ -306,7 +312,8 @@ int dctfp_row_order(dctfp_ctx* ctx, int32_t* val, int32_t* idx, int64_t n_rows, 
  * of pair_sim (:104-111) and the per-hit domain_sim of db_search (:143-145).  All device pointers; the prefix arrays must be
  * non-decreasing and within their matrices (the caller's guarantee, as for dctfp_block_min).  A protein without fingerprints
  * gives 0x7fffffff in both outputs (dctfp_block_min's fill); a pair index outside [0, npa) x [0, npb) gives -1 in both.
- * DCTFP_ERR_LIMIT above 2^31 - 1 proteins on a side. */
+ * DCTFP_ERR_LIMIT above 2^31 - 1 proteins on a side or 67108860 pairs per call (four pairs to a 256-thread workgroup, and one
+ * launch holds fewer than 2^32 threads). */
 int dctfp_pair_min(dctfp_ctx* ctx, const int32_t* pairs, int64_t n_pairs, const int8_t* a, int64_t lda, const int64_t* idx_a, int64_t npa,
                    const int8_t* b, int64_t ldb, const int64_t* idx_b, int64_t npb, int32_t d, int32_t* out_min, int32_t* out_last,
                    void* stream);
@@ -318,7 +325,8 @@ int dctfp_pair_min(dctfp_ctx* ctx, const int32_t* pairs, int64_t n_pairs, const 
  * protein, then of the second, and replaces its maximum -- started at 0 -- only on `s > maxs`: equal L1 values go to the lowest
  * row of a, then the lowest row of b, and there is NO best pair, -1 in both, when the smallest L1 is 17000 or more (similarity 0
  * is never > 0), when either protein has no fingerprint, or when the pair index is out of range.  Reads the same bytes as
- * dctfp_pair_min.  DCTFP_ERR_LIMIT above 2^31 - 1 proteins on a side; a protein must have fewer than 2^31 fingerprints. */
+ * dctfp_pair_min.  DCTFP_ERR_LIMIT above 2^31 - 1 proteins on a side or 67108860 pairs per call; a protein must have fewer than
+ * 2^31 fingerprints. */
 int dctfp_pair_argmin(dctfp_ctx* ctx, const int32_t* pairs, int64_t n_pairs, const int8_t* a, int64_t lda, const int64_t* idx_a, int64_t npa,
                       const int8_t* b, int64_t ldb, const int64_t* idx_b, int64_t npb, int32_t d, int32_t* out_min, int32_t* out_last,
                       int32_t* out_arg_a, int32_t* out_arg_b, void* stream);
@@ -365,7 +373,8 @@ int dctfp_protein_cover(dctfp_ctx* ctx, const int8_t* a, int64_t lda, const int6
  * dctfp_select_fill: offsets (device int64, n_rows + 1) = the exclusive prefix sum of out_count, computed by the caller; the
  * hits of row r go to out_key / out_col [offsets[r], offsets[r+1]) (device int32), ordered by (key, column) when
  * m <= min(max_count, 1024) -- max_count = the largest m of the call -- and in column order when m > 1024 (the caller orders
- * those).  cap <= 17407 (the LDS histogram of the count; DCTFP_ERR_LIMIT beyond), top >= 1, n_rows and n_cols < 2^31. */
+ * those).  cap <= 17407 (the LDS histogram of the count; DCTFP_ERR_LIMIT beyond), top >= 1, n_cols < 2^31, at most 4194303 rows per
+ * call (DCTFP_ERR_LIMIT: one 1024-thread workgroup per row, and one launch holds fewer than 2^32 threads). */
 int dctfp_select_count(dctfp_ctx* ctx, const int32_t* dist, int64_t n_rows, int64_t n_cols, int64_t ld, const uint8_t* row_empty,
                        const uint8_t* col_empty, int32_t cap, int32_t bound, int32_t top, int32_t* out_count, int32_t* out_cut,
                        void* stream);
@@ -414,7 +423,7 @@ int dctfp_tri_filter_fill(dctfp_ctx* ctx, const int32_t* tile, int64_t n_rows, i
  * it).  ids / id_off (n_ids + 1 offsets) and the score table as in dctfp_sim_lines: a / b = the five bytes of rows
  * min(mn[n], 17001) / min(last[n], 17001) (dctfp_pair_min's two outputs; 0x7fffffff -> row 17001).  Any id length, any
  * alignment of out.  A line whose pair lies outside [0, n_ids) or whose end lies beyond out_bytes is skipped, nothing else is
- * written.  DCTFP_ERR_LIMIT above 2^31 lines per call. */
+ * written.  DCTFP_ERR_LIMIT above 268435440 lines per call (sixteen lanes to a line, and one launch holds fewer than 2^32 threads). */
 int dctfp_pair_lines(dctfp_ctx* ctx, int64_t n_lines, const int32_t* pi, const int32_t* pj, const int32_t* mn, const int32_t* last,
                      const uint8_t* ids, const int64_t* id_off, int64_t n_ids, const char* table, const int64_t* line_off, uint8_t* out,
                      int64_t out_bytes, void* stream);
@@ -426,7 +435,7 @@ int dctfp_pair_lines(dctfp_ctx* ctx, int64_t n_lines, const int32_t* pi, const i
  * the two entries -- a global fingerprint row (the protein's first row + dctfp_pair_argmin's argument) or the sentinel.
  * line_off[n] = the caller's prefix sum of len_i + len_j + 14 + len_label_a + len_label_b + 2.  Any id or label length, any
  * alignment of out.  A line with a protein index outside [0, n_ids), a label index outside [0, n_labels) or an end beyond
- * out_bytes is skipped, nothing else is written.  DCTFP_ERR_LIMIT above 2^31 lines per call. */
+ * out_bytes is skipped, nothing else is written.  DCTFP_ERR_LIMIT above 268435440 lines per call. */
 int dctfp_pair_domain_lines(dctfp_ctx* ctx, int64_t n_lines, const int32_t* pi, const int32_t* pj, const int32_t* mn, const int32_t* last,
                             const int32_t* la, const int32_t* lb, const uint8_t* ids, const int64_t* id_off, int64_t n_ids,
                             const uint8_t* labels, const int64_t* label_off, int64_t n_labels, const char* table, const int64_t* line_off,
@@ -435,7 +444,7 @@ int dctfp_pair_domain_lines(dctfp_ctx* ctx, int64_t n_lines, const int32_t* pi, 
 /* Every fingerprint row's counterpart in the other protein, for a list of protein pairs (dct-sim --domain-map; not in the
  * reference): where dctfp_pair_argmin keeps the one best fingerprint pair, this keeps the best partner of EVERY row, on both
  * sides.  pairs, a, lda, idx_a, npa, b, ldb, idx_b, npb, d: as dctfp_pair_argmin, with its checks and error codes
- * (DCTFP_ERR_LIMIT above 2^31 - 1 proteins on a side or too many pairs per call).  For pair p = (pa, pb) with k and m rows the
+ * (DCTFP_ERR_LIMIT above 2^31 - 1 proteins on a side or 67108860 pairs per call).  For pair p = (pa, pb) with k and m rows the
  * results lie at [row_off[p], row_off[p + 1]) of out_l1 / out_arg (device int32, out_len entries; row_off = n_pairs + 1 device
  * int64, the caller's prefix sum of k + m): first the k rows of pa, then the m rows of pb.  out_l1 = the smallest L1 between the
  * row and any row of the other protein, raw (not capped at 17000); out_arg = the row of the other protein it was found at,
@@ -459,7 +468,7 @@ int dctfp_pair_row_best(dctfp_ctx* ctx, const int32_t* pairs, int64_t n_pairs, c
  * text (line_off and out may be NULL); with out_count NULL the text goes to out from line_off[n], the caller's prefix sum of those
  * lengths.  A line with a protein or label index out of range, whose row_off range is not its two proteins' rows within
  * [0, n_rows], whose row_arg names no row of the other protein, or (fill) that ends beyond out_bytes has length 0 and is not
- * written.  Any id or label length, any alignment.  DCTFP_ERR_LIMIT above 2^31 lines per call. */
+ * written.  Any id or label length, any alignment.  DCTFP_ERR_LIMIT above 268435440 lines per call. */
 int dctfp_pair_map_lines(dctfp_ctx* ctx, int64_t n_lines, const int32_t* pi, const int32_t* pj, const int32_t* mn, const int32_t* last,
                          const int32_t* la, const int32_t* lb, const uint8_t* ids, const int64_t* id_off, int64_t n_ids, const uint8_t* labels,
                          const int64_t* label_off, int64_t n_labels, const char* table, const int64_t* line_off, uint8_t* out,
@@ -505,7 +514,8 @@ int dctfp_cluster_labels(dctfp_ctx* ctx, int32_t* parent, int64_t n_nodes, int32
  * registers, and a workgroup whose block lies wholly on or left of the diagonal ends before it loads anything.
  * DCTFP_ERR_INVALID for a NULL argument (skip excepted), a negative count or offset, d < 1, lda or ldb < d, cap < 0, bound < 0,
  * a0 + na > n_nodes or b0 + nb > n_nodes (checked on the host: the device never forms an index outside parent, owner or skip);
- * DCTFP_ERR_LIMIT for n_nodes >= 2^31 or more than 8M rows of a per call.  na or nb of 0: nothing to do. */
+ * DCTFP_ERR_LIMIT for n_nodes >= 2^31, more than 8M (8388480) rows of a or more than 2147483520 rows of b per call.  na or nb of 0:
+ * nothing to do. */
 int dctfp_rows_link(dctfp_ctx* ctx, const int8_t* a, int64_t na, int64_t lda, int64_t a0, const int8_t* b, int64_t nb, int64_t ldb,
                     int64_t b0, int32_t d, const int32_t* owner, const uint8_t* skip, int32_t cap, int32_t bound, int32_t* parent,
                     int64_t n_nodes, void* stream);
@@ -560,7 +570,8 @@ int dctfp_greedy_pairs_mark(dctfp_ctx* ctx, const int32_t* pi, const int32_t* pj
  * which the device ran or on how the caller splits the rows into calls.  A slot outside [0, n_assign) or a negative value is
  * skipped on the device (the host cannot see the two arrays).
  * DCTFP_ERR_INVALID for a NULL ctx, a, b or assign, a negative count or offset, d < 1, lda or ldb < d, cap < 0 or bound < 0;
- * DCTFP_ERR_LIMIT for n_assign >= 2^31 or more than 8M rows of a per call.  na, nb or n_assign of 0: nothing to do. */
+ * DCTFP_ERR_LIMIT for n_assign >= 2^31, more than 8M (8388480) rows of a or more than 2147483520 rows of b per call.  na, nb or
+ * n_assign of 0: nothing to do. */
 int dctfp_rows_assign(dctfp_ctx* ctx, const int8_t* a, int64_t na, int64_t lda, const int32_t* value_a, int64_t a0, const int8_t* b,
                       int64_t nb, int64_t ldb, const int32_t* slot_b, int64_t b0, int32_t d, int32_t cap, int32_t bound, int32_t* assign,
                       int64_t n_assign, void* stream);
@@ -770,7 +781,8 @@ int dctfp_l1_knn(dctfp_ctx* ctx, const int8_t* q, int64_t nq, int64_t ldq, const
  * its protein; < 0: a protein the caller ranks itself, skipped).  The protein's hits ordered by (distance, fingerprint within
  * the protein, hit rank); the first min(khits, f k) of them are written from line line_base[p] on: out_qrow = the fingerprint
  * row, out_drow = the database row (idx), out_dist.  All device pointers.  Work per hit grows with the protein's f (one binary
- * search per other fingerprint): callers send proteins of many fingerprints to the host. */
+ * search per other fingerprint): callers send proteins of many fingerprints to the host.  DCTFP_ERR_LIMIT above 4294967040 hits
+ * (n_rows x k) per call: one thread per hit, and one launch holds fewer than 2^32 threads. */
 int dctfp_query_rank(dctfp_ctx* ctx, const int32_t* val, const int32_t* idx, int64_t n_rows, int32_t k, const int64_t* qoff,
                      const int32_t* prot_of_row, const int64_t* line_base, int32_t khits, int32_t* out_qrow, int32_t* out_drow,
                      int32_t* out_dist, void* stream);
@@ -780,7 +792,7 @@ int dctfp_query_rank(dctfp_ctx* ctx, const int32_t* val, const int32_t* idx, int
  * [q_pid_off[r], q_pid_off[r + 1]) of q_txt, its domain [q_dom_off[r], q_dom_off[r + 1]) (likewise d_*); rank = the printed
  * number; the score of distance x is bytes [score_off[x], score_off[x + 1]) of score_txt (a host-built table of the strings the
  * reference prints).  line_off = the prefix sum of the line lengths (the caller's: every line must fit in out).  All device
- * pointers. */
+ * pointers.  DCTFP_ERR_LIMIT above 4294967040 lines per call. */
 int dctfp_query_lines(dctfp_ctx* ctx, int64_t n_lines, const int32_t* qrow, const int32_t* drow, const int32_t* dist, const int32_t* rank,
                       const uint8_t* q_txt, const int64_t* q_pid_off, const int64_t* q_dom_off, const uint8_t* d_txt, const int64_t* d_pid_off,
                       const int64_t* d_dom_off, const uint8_t* score_txt, const int64_t* score_off, const int64_t* line_off, uint8_t* out,

@@ -2,6 +2,8 @@
 // hip_stub.cpp (no GPU, no kernels: see there).  What it covers: every table dctfp_quantize builds (jobs, pieces, walks,
 // runs, cosine-table list), the staging / device copies it sizes, fused-group detection, the split at giant domains, the
 // chunk plan of the two-kernel path, the option surface, the cosine-table cache (failure injection, arena restart).
+// The exports of dct-sim and query_db run behind these sections, from driver_sim.cpp (sim_entry_points), and the run ends with one
+// line per export: calls, calls that ended DCTFP_OK with a launch, refusals by code, limit rows passed.
 // Usage: driver [rounds] [seed] [plain]
 // "plain": the same calls (every random number is still drawn), but no allocation failure, no launch failure and no
 // test_fail_once is injected -- every call runs to its end, which is what two builds' launch logs (hip_stub.cpp,
@@ -16,20 +18,15 @@
 #include <vector>
 
 #include "dctfp.h"
-
-extern "C" unsigned long dctfp_stub_counter(int which);
-extern "C" void* stub_new_stream();
-extern "C" void stub_call_begin();
-extern "C" long stub_call_end(void* stream);
-extern "C" unsigned long stub_fail_launch(long n);
+#include "driver.h"
 
 // ---- allocation-failure hook: the N-th operator new from now on throws std::bad_alloc (once).  Nothing may throw across
 // the C ABI -- an exception that left dctfp_quantize would end this process in std::terminate (SIGABRT on the calling
 // thread) -- so the call has to come back with DCTFP_ERR_NOMEM (or have succeeded, if it needed fewer allocations).
 #include <new>
-static long g_fail_after = -1;   // < 0: never
+long drv::g_fail_after = -1;   // < 0: never
 static long g_failed = 0;
-static bool g_plain = false;     // mode "plain": nothing is injected
+bool drv::g_plain = false;     // mode "plain": nothing is injected
 static void* hooked_alloc(size_t n, size_t align) {
     if (!g_plain && g_fail_after >= 0 && g_fail_after-- == 0) {
         ++g_failed;
@@ -69,37 +66,30 @@ void operator delete[](void* p, std::align_val_t, const std::nothrow_t&) noexcep
         }                                                                                   \
     } while (0)
 
-// ---- stream order and launch failures (hip_stub.cpp).  Every call runs on the caller's stream of the moment -- the null stream
-// or one of two others, in turn -- and must leave nothing running on another stream that this one is not ordered after: the
-// context's own streams are joined back before a call returns, on its error paths too.  Where `inject` is set, one kernel launch
-// of the call fails now and then, and the call must come back as DCTFP_ERR_HIP.  (Decisions from a generator of their own: the
-// seeded shapes of the batches stay what they were.)
-static void* g_streams[3];
-static void* g_stream = nullptr;
-static unsigned long g_rotation = 0;
-static std::mt19937_64 g_aux;
-static bool g_launch_failed = false;   // the last call's injected launch failure fired
-static int g_stream_errors = 0;
-static long g_launch_failures = 0;
-template <typename F>
-static int call(const char* name, F f, bool inject = false) {
-    g_stream = g_streams[g_rotation++ % 3];
-    const long fail_at = inject && g_aux() % 4 == 0 ? (long)(g_aux() % 8) : -1;
-    const unsigned long fired = stub_fail_launch(g_plain ? -1 : fail_at);
-    stub_call_begin();
-    const int rc = f();
-    const long unjoined = stub_call_end(g_stream);
-    g_launch_failed = stub_fail_launch(-1) != fired;
-    g_launch_failures += g_launch_failed ? 1 : 0;
-    if (unjoined) {
-        fprintf(stderr, "%s (rc %d): %ld operations left on other streams the caller's stream is not ordered after\n", name, rc, unjoined);
-        ++g_stream_errors;
+// ---- what driver.h declares: the caller's streams and the checks of `call`, and the tallies of the report
+void* drv::g_streams[3];
+void* drv::g_stream = nullptr;
+unsigned long drv::g_rotation = 0;
+std::mt19937_64 drv::g_aux;
+bool drv::g_launch_failed = false;
+int drv::g_stream_errors = 0;
+long drv::g_launch_failures = 0;
+static Tally g_tallies[128];
+static int g_n_tallies = 0;
+Tally& tally_of(const char* name) {
+    for (int i = 0; i < g_n_tallies; ++i)
+        if (!strcmp(g_tallies[i].name, name)) return g_tallies[i];
+    if (g_n_tallies == 128) { fprintf(stderr, "more than 128 exports tallied\n"); abort(); }
+    g_tallies[g_n_tallies] = Tally{name, 0, 0, 0, {0, 0, 0, 0, 0, 0, 0}, 0, 0};
+    return g_tallies[g_n_tallies++];
+}
+void print_tallies() {
+    for (int i = 0; i < g_n_tallies; ++i) {
+        const Tally& t = g_tallies[i];
+        printf("export %s: %ld calls, %ld ok, %ld ok with a launch, refused invalid %ld shape %ld limit %ld unsupported %ld, nomem %ld hip %ld, "
+               "limit rows %ld of %ld\n", t.name, t.calls, t.ok, t.ok_launching, t.code[1], t.code[2], t.code[5], t.code[6], t.code[4], t.code[3],
+               t.limit_rows_passed, t.limit_rows);
     }
-    if (g_launch_failed && rc != DCTFP_ERR_HIP) {
-        fprintf(stderr, "%s: an injected launch failure came back as %d\n", name, rc);
-        ++g_stream_errors;
-    }
-    return rc;
 }
 
 // ---- the entry points either side of dctfp_quantize: argument checks, table builds (top-k jobs and stripes, sorting-network
@@ -109,6 +99,8 @@ static int other_entry_points(dctfp_ctx* ctx, std::mt19937_64& rng, int rounds, 
     auto uni = [&](int lo, int hi) { return (int)(lo + rng() % (uint64_t)(hi - lo + 1)); };
     auto ok_or_expected = [&](int rc, const char* what) {
         ++*n_calls;
+        for (const char* host_only : {"dctfp_build_pieces", "dctfp_reccut_pieces", "dctfp_stitch_sizes"})   // (the others are tallied by `call`)
+            if (!strncmp(what, host_only, strlen(host_only))) tally(host_only, rc, 0);
         if (rc == DCTFP_OK) return true;
         if (rc == DCTFP_ERR_NOMEM || rc == DCTFP_ERR_SHAPE || rc == DCTFP_ERR_INVALID || rc == DCTFP_ERR_LIMIT || rc == DCTFP_ERR_UNSUPPORTED ||
             (rc == DCTFP_ERR_HIP && g_launch_failed)) { ++*n_expected; return true; }
@@ -637,6 +629,9 @@ int main(int argc, char** argv) {
     if (other_entry_points(ctx, rng, std::max(20, rounds / 3), &n_other_calls, &n_other_expected)) return 1;
     printf("the other entry points: %d calls (%d ended in an expected error)\n", n_other_calls, n_other_expected);
     CHECK(dctfp_destroy(ctx));
+    // ---- the exports of dct-sim and query_db (driver_sim.cpp), from a generator and on contexts of their own: what came before is
+    // what it was, draw for draw and launch for launch
+    if (sim_entry_points(std::max(8, rounds / 10), (argc > 2 ? strtoull(argv[2], nullptr, 10) : 12345) ^ 0x51a1u)) return 1;
     printf("kernel launch failures injected and reported as DCTFP_ERR_HIP: %ld\n", g_launch_failures);
     if (g_stream_errors) {
         printf("stream order: %d calls left work running that the caller's stream is not ordered after\n", g_stream_errors);
@@ -646,5 +641,7 @@ int main(int argc, char** argv) {
     printf("asan driver: %d calls over %d rounds (%d ended in an expected error), %lu walk-kernel launches, %lu stage-A launches, "
            "%lu jobs walked by the table emulation: no memory error\n", n_calls, rounds, n_errors_expected, dctfp_stub_counter(0),
            dctfp_stub_counter(1), dctfp_stub_counter(2));
-    return 0;
+    print_tallies();
+    printf("launches the stub refused for their shape: %lu\n", dctfp_stub_counter(4));
+    return dctfp_stub_counter(4) ? 1 : 0;
 }

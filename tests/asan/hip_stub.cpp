@@ -83,6 +83,7 @@ int template_int(const std::string& n, const char* kernel, int index) {  // the 
     return atoi(n.c_str() + at + 2);
 }
 unsigned long g_walk_launches = 0, g_stage_a_launches = 0, g_jobs_walked = 0;
+unsigned long g_launches_taken = 0, g_launch_refusals = 0, g_scratch_regions = 0;   // launches that passed the checks of hipLaunchKernel / that it refused; regions the scratch emulators touched
 
 // ---- the launch log (off unless asked for).  Fixed buffers: nothing here may go through operator new (driver.cpp hooks it).
 FILE* g_log = nullptr;
@@ -364,10 +365,89 @@ void emulate_stage_b(void** a) {
         touch_w(out + jobs[j].out_off, (size_t)n * m);
     }
 }
+
+// ---- the five users of the context's generic scratch: what the kernel would read or write INSIDE that scratch, from the kernel's
+// own arguments, first and last byte of every region.  The scratch is one hipMalloc block (= one malloc block here), so a size
+// function that promises less than its launcher carves up is a heap-buffer-overflow.  Caller-owned arrays are not touched: the
+// limit probes of driver_sim.cpp pass pointers that point nowhere.
+void region(void* p, size_t bytes) { touch_w(p, bytes); ++g_scratch_regions; }
+void emulate_plan_count(void** a) {   // protein_plan_count_kernel(idx, np, n_seg, seg_count): one count per segment
+    region(*(void**)a[3], (size_t)*(int64_t*)a[2] * sizeof(int64_t));
+}
+void emulate_plan_scan(void** a) {    // protein_plan_scan_kernel(seg_count, n_seg): the offsets in place + the total behind them
+    region(*(void**)a[0], ((size_t)*(int64_t*)a[1] + 1) * sizeof(int64_t));
+}
+void emulate_plan_write(void** a) {   // protein_plan_write_kernel(idx, np, n_seg, seg_off, starts): at most np blocks + the closing entry
+    region(*(void**)a[3], ((size_t)*(int64_t*)a[2] + 1) * sizeof(int64_t));
+    region(*(void**)a[4], ((size_t)*(int64_t*)a[1] + 1) * sizeof(int32_t));
+}
+void emulate_protein_pairs(void** a, bool cover) {   // protein_min_kernel / protein_cover_kernel: the totals and the first block of both plans
+    const int sb = cover ? 10 : 8;   // (start_a, nblk_a at 3, 4; start_b, nblk_b behind b, ldb, idx_b)
+    region(*(void**)a[4], sizeof(int64_t)), region(*(void**)a[3], 2 * sizeof(int32_t));
+    region(*(void**)a[sb + 1], sizeof(int64_t)), region(*(void**)a[sb], 2 * sizeof(int32_t));
+}
+void emulate_l1_knn(dim3 grid, void** a) {   // l1_knn_kernel(a, na, lda, b, nb, ldb, d, k, slice_cols, n_slices, work, cand, ...)
+    const size_t na = (size_t)*(int64_t*)a[1], k = (size_t)*(int*)a[7], S = (size_t)*(int*)a[9];
+    if (S != grid.x) { fprintf(stderr, "stub: l1_knn_kernel on %u slices, told %zu\n", grid.x, S); abort(); }
+    region(*(void**)a[10], na * S * 2 * k * sizeof(unsigned long long));          // the rows' work lists
+    if (S > 1) region(*(void**)a[11], na * S * k * sizeof(unsigned long long));   // the slices' candidates
+}
+void emulate_knn_merge(dim3 grid, void** a) {   // knn_merge2_kernel(in, n_in, k, out, ...): grid = (rows, lists out)
+    const size_t n_in = (size_t)*(int*)a[1], k = (size_t)*(int*)a[2];
+    region(*(void**)a[0], (size_t)grid.x * n_in * k * sizeof(unsigned long long));
+    if (grid.y > 1) region(*(void**)a[3], (size_t)grid.x * grid.y * k * sizeof(unsigned long long));   // (the last level writes out_val / out_idx)
+}
+void emulate_row_select_reg(const std::string& name, dim3 grid, void** a) {
+    // row_select_reg_kernel<PER, SRC, TH>(src_val, src_col, ld, n_cols, seg_cols, n_seg, k, out_val, out_idx): the first pass over
+    // segments writes k candidates per (row, segment), the second (SRC) reads n_cols = ld of them per row
+    const size_t n_seg = (size_t)*(int64_t*)a[5], k = (size_t)*(int*)a[6];
+    if (name.find("Lb1E") != std::string::npos) {
+        const size_t bytes = (size_t)grid.x * (size_t)*(int64_t*)a[2] * sizeof(int32_t);
+        region(*(void**)a[0], bytes), region(*(void**)a[1], bytes);
+    } else if (n_seg > 1) {
+        region(*(void**)a[7], (size_t)grid.x * k * sizeof(int32_t)), region(*(void**)a[8], (size_t)grid.x * k * sizeof(int32_t));
+    }
+}
+void emulate_generic_forward(void** a) {   // generic_forward_kernel(x, n_rows, n_cols, ld, num, fs, coef): num coefficients per column
+    region(*(void**)a[5], (size_t)*(int64_t*)a[2] * (size_t)*(int*)a[4] * sizeof(double));
+}
+void emulate_generic_inverse(void** a) {   // generic_inverse_kernel(fs, n_cols, num, scaled)
+    region(*(void**)a[0], (size_t)*(int64_t*)a[1] * (size_t)*(int*)a[2] * sizeof(double));
+}
+
+// ---- what the runtime enforces at a launch.  The largest dynamic LDS a kernel was granted (hipFuncSetAttribute), in a fixed table:
+// nothing here may go through operator new.
+struct FuncLds { const void* fn; int bytes; } g_func_lds[64];
+int g_n_func_lds = 0;
+constexpr size_t kLdsDefault = 64 * 1024;    // dynamic LDS of a launch that asked for no more through hipFuncSetAttribute
+constexpr size_t kLdsPerCu = 160 * 1024;     // the LDS of a gfx950 CU: no attribute raises a workgroup's share above it
+constexpr size_t kMallocBudget = (size_t)1 << 30;   // one "device" allocation: a limit probe that plans more gets hipErrorOutOfMemory
+long g_malloc_fail_after = -1;
+bool launch_shape_ok(const void* fn, dim3 g, dim3 b, size_t shmem) {
+    if (!g.x || !g.y || !g.z || !b.x || !b.y || !b.z) return false;
+    // hipDeviceProp_t::maxThreadsPerBlock (hip_runtime_api.h) is 1024 on gfx950
+    if ((uint64_t)b.x * b.y * b.z > 1024) return false;
+    // the second and third grid dimension: 65535, the bound the library's own two-dimensional launches (rows_link, l1_knn) keep to
+    if (g.y > 65535 || g.z > 65535) return false;
+    // hip_runtime_api.h, hipModuleLaunchKernel: "HIP does not support kernel launch with total work items defined in dimension with
+    // size gridDim x blockDim >= 2^32. So gridDim.x * blockDim.x, gridDim.y * blockDim.y and gridDim.z * blockDim.z are always less
+    // than 2^32."
+    if ((uint64_t)g.x * b.x >= (1ull << 32) || (uint64_t)g.y * b.y >= (1ull << 32) || (uint64_t)g.z * b.z >= (1ull << 32)) return false;
+    size_t allowed = kLdsDefault;
+    for (int i = 0; i < g_n_func_lds; ++i)
+        if (g_func_lds[i].fn == fn) allowed = (size_t)g_func_lds[i].bytes;
+    return shmem <= (allowed < kLdsPerCu ? allowed : kLdsPerCu);
+}
 }  // namespace
 
 extern "C" {
-unsigned long dctfp_stub_counter(int which) { return which == 0 ? g_walk_launches : (which == 1 ? g_stage_a_launches : g_jobs_walked); }
+unsigned long dctfp_stub_counter(int which) {
+    // 0 .. 2: walk-kernel launches, stage-A launches, jobs walked; 3: launches taken, 4: launches refused for their shape, 5: scratch regions touched
+    const unsigned long v[] = {g_walk_launches, g_stage_a_launches, g_jobs_walked, g_launches_taken, g_launch_refusals, g_scratch_regions};
+    return which >= 0 && which < 6 ? v[which] : 0;
+}
+// the n-th hipMalloc from now on fails (n < 0: none)
+void stub_fail_malloc(long n) { g_malloc_fail_after = n; }
 void* stub_new_stream() { return new_stream(); }
 void stub_call_begin() {
     for (int i = 0; i < g_n_streams; ++i)
@@ -399,7 +479,12 @@ hipError_t hipGetDevicePropertiesR0600(hipDeviceProp_t* p, int) {
     p->multiProcessorCount = 256;
     return hipSuccess;
 }
-hipError_t hipMalloc(void** p, size_t n) { *p = malloc(n ? n : 1); return *p ? hipSuccess : hipErrorOutOfMemory; }
+hipError_t hipMalloc(void** p, size_t n) {
+    *p = nullptr;
+    if (n > kMallocBudget || (g_malloc_fail_after >= 0 && g_malloc_fail_after-- == 0)) return hipErrorOutOfMemory;
+    *p = malloc(n ? n : 1);
+    return *p ? hipSuccess : hipErrorOutOfMemory;
+}
 hipError_t hipFree(void* p) { free(p); return hipSuccess; }
 hipError_t hipHostMalloc(void** p, size_t n, unsigned) { *p = malloc(n ? n : 1); return *p ? hipSuccess : hipErrorOutOfMemory; }
 hipError_t hipHostFree(void* p) { free(p); return hipSuccess; }
@@ -458,7 +543,15 @@ hipError_t __hipPopCallConfiguration(dim3* grid, dim3* block, size_t* shmem, hip
     *grid = g_grid; *block = g_block; *shmem = g_shmem; *stream = g_stream;
     return hipSuccess;
 }
-hipError_t hipFuncSetAttribute(const void*, hipFuncAttribute, int) { return hipSuccess; }
+hipError_t hipFuncSetAttribute(const void* fn, hipFuncAttribute attr, int value) {
+    if (attr != hipFuncAttributeMaxDynamicSharedMemorySize) return hipSuccess;
+    if (value < 0 || (size_t)value > kLdsPerCu) return hipErrorInvalidValue;
+    for (int i = 0; i < g_n_func_lds; ++i)
+        if (g_func_lds[i].fn == fn) { g_func_lds[i].bytes = value; return hipSuccess; }
+    if (g_n_func_lds == 64) { fprintf(stderr, "stub: more than 64 kernels with an LDS attribute\n"); abort(); }
+    g_func_lds[g_n_func_lds++] = {fn, value};
+    return hipSuccess;
+}
 hipError_t hipLaunchKernel(const void* fn, dim3 grid, dim3 block, void** args, size_t shmem, hipStream_t stream) {
     enqueue(stream);   // (a failed launch too: what the caller cannot know is whether its stream still runs something)
     if (g_launch_fail_after >= 0 && g_launch_fail_after-- == 0) {
@@ -468,7 +561,14 @@ hipError_t hipLaunchKernel(const void* fn, dim3 grid, dim3 block, void** args, s
     const auto it = names().find(fn);
     if (it == names().end()) { fprintf(stderr, "stub: launch of an unregistered kernel\n"); abort(); }
     const std::string& n = it->second;
-    if (grid.x == 0 || grid.y == 0 || block.x == 0 || block.x > 1024) { fprintf(stderr, "stub: bad launch shape of %s\n", n.c_str()); abort(); }
+    // a shape the runtime refuses comes back as the runtime's error, so that the library's own error path is what runs
+    if (!launch_shape_ok(fn, grid, block, shmem)) {
+        ++g_launch_refusals;
+        if (getenv("DCTFP_STUB_VERBOSE"))
+            fprintf(stderr, "stub: refused %s grid=%u,%u,%u block=%u,%u,%u lds=%zu\n", n.c_str(), grid.x, grid.y, grid.z, block.x, block.y, block.z, shmem);
+        return g_last_error = hipErrorInvalidConfiguration;
+    }
+    ++g_launches_taken;
     static const char* log_path = getenv("DCTFP_STUB_LAUNCH_LOG");
     if (log_path && !g_log && !(g_log = fopen(log_path, "w"))) { fprintf(stderr, "stub: cannot write %s\n", log_path); abort(); }
     g_hash = 0xcbf29ce484222325ull, g_hashed = false, g_scalars_len = 0, g_scalars[0] = 0;
@@ -477,6 +577,16 @@ hipError_t hipLaunchKernel(const void* fn, dim3 grid, dim3 block, void** args, s
     else if (n.find("stage_a_kernel") != std::string::npos) emulate_stage_a(n, grid, args);
     else if (n.find("basis_kernel") != std::string::npos) emulate_basis(grid, args);
     else if (n.find("stage_b_mfma_kernel") != std::string::npos) emulate_stage_b(args);
+    else if (n.find("protein_plan_count_kernel") != std::string::npos) emulate_plan_count(args);
+    else if (n.find("protein_plan_scan_kernel") != std::string::npos) emulate_plan_scan(args);
+    else if (n.find("protein_plan_write_kernel") != std::string::npos) emulate_plan_write(args);
+    else if (n.find("protein_min_kernel") != std::string::npos) emulate_protein_pairs(args, false);
+    else if (n.find("protein_cover_kernel") != std::string::npos) emulate_protein_pairs(args, true);
+    else if (n.find("l1_knn_kernel") != std::string::npos) emulate_l1_knn(grid, args);
+    else if (n.find("knn_merge2_kernel") != std::string::npos) emulate_knn_merge(grid, args);
+    else if (n.find("row_select_reg_kernel") != std::string::npos) emulate_row_select_reg(n, grid, args);
+    else if (n.find("generic_forward_kernel") != std::string::npos) emulate_generic_forward(args);
+    else if (n.find("generic_inverse_kernel") != std::string::npos) emulate_generic_inverse(args);
     if (g_log) {
         fprintf(g_log, "%s grid=%u,%u,%u block=%u,%u,%u lds=%zu stream=%d%s", n.c_str(), grid.x, grid.y, grid.z, block.x, block.y, block.z, shmem,
                 of(stream)->id, g_scalars);

@@ -12,7 +12,11 @@ groups, the window jobs of the stitcher in both forms, the L1 matrix / block min
 -- over random and malformed arguments, again with allocation failures injected.  Every call runs on one of three caller's
 streams in turn, the stub keeps the stream order (a vector clock per stream and event), and no call may return with work on
 another stream that its caller's stream is not ordered after -- on its error paths either, where kernel launches are made to
-fail now and then."""
+fail now and then.  A second section (tests/asan/driver_sim.cpp) does the same for every export of dct-sim and query_db, and holds
+each of them to the limits include/dctfp.h states: the stub refuses what the HIP runtime refuses (a grid of 2^32 threads or more
+in a dimension, more than 1024 threads in a workgroup, ...), so the largest accepted value of every limit must launch and the
+smallest refused one must come back as the library's own error code.  UndefinedBehaviorSanitizer runs beside AddressSanitizer: an
+argument check that overflows is a report, not a wrapped comparison that passes."""
 
 import os
 import re
@@ -52,9 +56,39 @@ def test_stub_records_match_the_kernel_header():
     assert a == b
 
 
+# Exports the driver does not have to call, each with its reason.  Every other `int dctfp_*(` of include/dctfp.h must be in the
+# driver's report: an export added without a driver section fails the test.  (dctfp_last_error, dctfp_contact_count and
+# dctfp_reccut_room do not return int and are not parsed; the driver calls all three.)
+NOT_DRIVEN = {
+    'dctfp_version': 'a constant',
+    'dctfp_runtime_info': 'reads the process map for the HIP runtime: there is none under the stub',
+    'dctfp_crash_handler': 'installs signal handlers: the sanitizer has its own',
+    'dctfp_host_device_pointer': 'one runtime call, no argument to check beyond NULL',
+    'dctfp_stream_synchronize': 'one runtime call',
+    'dctfp_profile': 'hipEvent timing: the stub has no clock',
+}
+# Exports with nothing to refuse: a successful call is all that is asked of them.
+NO_REFUSAL = {
+    'dctfp_destroy': 'dctfp_destroy(NULL) is a no-op, like free(NULL)',
+}
+
+
+def _exports():
+    with open(os.path.join(ROOT, 'include', 'dctfp.h')) as fh:
+        return sorted(set(re.findall(r'^int (dctfp_\w+)\(', fh.read(), re.M)))
+
+
+def test_the_header_parse_finds_the_exports():
+    names = _exports()
+    assert len(names) >= 60 and 'dctfp_quantize' in names and 'dctfp_query_lines' in names and set(NOT_DRIVEN) <= set(names)
+
+
 @pytest.mark.skipif(not (os.path.exists(HIPCC) and os.path.exists(CLANG)), reason='needs the ROCm compilers')
 def test_host_calls_under_address_sanitizer(tmp_path):
-    flags = ['-O1', '-g', '-std=c++17', '-fsanitize=address', '-fno-omit-frame-pointer']
+    sanitize = ['-fsanitize=address', '-fsanitize=undefined', '-fno-sanitize-recover=undefined']
+    flags = ['-O1', '-g', '-std=c++17', '-fno-omit-frame-pointer', *sanitize]
+    # (the host side only: -Xarch_host keeps the flags the device target does not take away from it)
+    hip_flags = ['-O1', '-g', '-std=c++17', '-fno-omit-frame-pointer', *(x for f in sanitize for x in ('-Xarch_host', f))]
     inc = ['-I', os.path.join(ROOT, 'include'), '-I', os.path.join(ROOT, 'dctdomain_amd', 'csrc')]
     import build_ext
     stub_o, syms, exe = (str(tmp_path / n) for n in ('hip_stub.o', 'fatbin_syms.cpp', 'driver'))
@@ -63,7 +97,7 @@ def test_host_calls_under_address_sanitizer(tmp_path):
     for unit in build_ext.UNITS:          # every unit of the library, host side only (the launchers live in their own units)
         obj = str(tmp_path / (unit[:-4] + '.host.o'))
         host_objs.append(obj)
-        procs.append(subprocess.Popen([HIPCC, '--offload-arch=gfx950', '--cuda-host-only', '-fPIC', '-DDCTFP_EXPERIMENTS', *flags, *inc, '-c',
+        procs.append(subprocess.Popen([HIPCC, '--offload-arch=gfx950', '--cuda-host-only', '-fPIC', '-DDCTFP_EXPERIMENTS', *hip_flags, *inc, '-c',
                                        os.path.join(ROOT, 'dctdomain_amd', 'csrc', unit), '-o', obj]))
     assert all(p.wait() == 0 for p in procs)
     subprocess.run([CLANG, '-D__HIP_PLATFORM_AMD__', '-fPIC', *flags, '-I', '/opt/rocm/include', '-c',
@@ -73,9 +107,10 @@ def test_host_calls_under_address_sanitizer(tmp_path):
     with open(syms, 'w') as fh:
         for sym in sorted(set(re.findall(r'__hip_fatbin_[0-9a-f]+', undefined))):
             fh.write(f'extern "C" {{ extern const unsigned long long {sym}[4]; const unsigned long long {sym}[4] = {{0, 0, 0, 0}}; }}\n')
-    subprocess.run([CLANG, *flags, '-I', os.path.join(ROOT, 'include'), os.path.join(ROOT, 'tests', 'asan', 'driver.cpp'), syms,
+    subprocess.run([CLANG, *flags, '-I', os.path.join(ROOT, 'include'), os.path.join(ROOT, 'tests', 'asan', 'driver.cpp'),
+                    os.path.join(ROOT, 'tests', 'asan', 'driver_sim.cpp'), syms,
                     *host_objs, stub_o, '-o', exe, '-lpthread'], check=True)
-    env = dict(os.environ, ASAN_OPTIONS='detect_leaks=1:abort_on_error=0')
+    env = dict(os.environ, ASAN_OPTIONS='detect_leaks=1:abort_on_error=0', UBSAN_OPTIONS='print_stacktrace=1')
     for seed in (1, 2, 3):
         r = subprocess.run([exe, '250', str(seed)], env=env, capture_output=True, text=True, timeout=900)
         assert r.returncode == 0, (r.stdout + r.stderr)[-4000:]
@@ -90,4 +125,29 @@ def test_host_calls_under_address_sanitizer(tmp_path):
         # the entry points either side of dctfp_quantize (round 4): domain-string parser, top-k tables, stitch jobs, row select
         other = re.search(r'the other entry points: (\d+) calls \((\d+) ended in an expected error\)', r.stdout)
         assert int(other.group(1)) >= 500 and int(other.group(2)) < int(other.group(1)) // 3, r.stdout
+        # ---- the exports of dct-sim and query_db (driver_sim.cpp), reported apart: the thresholds above count the old section only
+        rows = re.search(r'limit table: (\d+) of (\d+) rows passed', r.stdout)
+        assert int(rows.group(1)) == int(rows.group(2)) >= 70, r.stdout
+        probes = re.search(r'overflow probes: (\d+) of (\d+) refused', r.stdout)
+        assert int(probes.group(1)) == int(probes.group(2)) >= 20, r.stdout
+        # no launch anywhere in the run had a shape the runtime refuses
+        assert int(re.search(r'launches the stub refused for their shape: (\d+)', r.stdout).group(1)) == 0, r.stdout
+        # the scratch users ran on a scratch of exactly the bytes they asked for, with the emulators touching every region's ends
+        tight = re.search(r'(\d+) calls on a scratch of exactly the bytes asked for, (\d+) scratch regions touched', r.stdout)
+        assert int(tight.group(1)) >= 20 and int(tight.group(2)) >= 200, r.stdout
+        # completeness: every export of the header, but for the two literal lists above
+        report = {}
+        for m in re.finditer(r'^export (dctfp_\w+): (\d+) calls, (\d+) ok, (\d+) ok with a launch, refused invalid (\d+) shape (\d+) limit (\d+) '
+                             r'unsupported (\d+), nomem \d+ hip \d+, limit rows (\d+) of (\d+)$', r.stdout, re.M):
+            report[m.group(1)] = [int(x) for x in m.groups()[1:]]
+        host_only = {'dctfp_build_pieces', 'dctfp_reccut_pieces', 'dctfp_stitch_sizes', 'dctfp_create', 'dctfp_destroy', 'dctfp_set_option',
+                     'dctfp_get_option'}       # (no kernel of their own: a successful call, not a launching one)
+        for name in _exports():
+            if name in NOT_DRIVEN:
+                continue
+            assert name in report, f'{name} is exported by include/dctfp.h and never called by tests/asan/driver*.cpp'
+            calls, ok, launching, invalid, shape, limit, unsupported, rows_ok, rows_all = report[name]
+            assert (ok if name in host_only else launching) >= 1, (name, report[name])
+            assert name in NO_REFUSAL or invalid + shape + limit + unsupported >= 1, (name, report[name])
+            assert rows_ok == rows_all, (name, report[name])
         print(r.stdout.strip().splitlines()[-3:])

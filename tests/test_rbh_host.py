@@ -203,8 +203,12 @@ def test_new_unit_is_part_of_the_build_and_touches_the_arrays_through_atomics_on
     assert len(sync) == 3 and sync[0] < kernel.index('s_row[tid] = kNone32;') < sync[1] < kernel.index('for (int rl = 0;') < sync[2] < kernel.index('lower_hit(best_row + ')
     host = open(os.path.join(csrc, 'dctfp.hip')).read()
     body = host[host.index('\nint dctfp_rect_best('):host.index('DCTFP_GUARD("dctfp_rect_best")')]
-    for check in ('ld < n_cols', 'row0 + n_rows > n_a', 'col0 + n_cols > n_b', '0x7fffffff', 'rect_best_max_cap()', 'launch_rect_best(TriTile{'):
+    # (the two range checks in the form that cannot overflow: range_within(first, count, n) is count <= n && first <= n - count)
+    for check in ('ld < n_cols', '!range_within(row0, n_rows, n_a)', '!range_within(col0, n_cols, n_b)', '0x7fffffff', 'rect_best_max_cap()',
+                  'launch_rect_best(TriTile{'):
         assert check in body, check
+    assert 'row0 + n_rows' not in body and 'col0 + n_cols' not in body
+    assert 'constexpr bool range_within(int64_t first, int64_t count, int64_t n) { return count <= n && first <= n - count; }' in host
 
 
 def test_the_wrappers_are_public_and_carry_the_stated_signatures():
