@@ -52,6 +52,11 @@ class DctfpError(RuntimeError):
 _lib = None
 _lib_lock = threading.Lock()
 
+#: the exports of include/dctfp_linkage.h (dct-sim --hac), which counts its own version
+LINKAGE_EXPORTS = ('dctfp_linkage_version', 'dctfp_linkage_nearest', 'dctfp_linkage_merge')
+DCTFP_LINKAGE_VERSION = 1
+LINKAGE_MAX_N = 46340
+
 EXPORTS = ('dctfp_version', 'dctfp_last_error', 'dctfp_create', 'dctfp_destroy', 'dctfp_quantize',
            'dctfp_idct_quant', 'dctfp_scale', 'dctfp_gather_rows', 'dctfp_contact_topk',
            'dctfp_contact_count', 'dctfp_stitch', 'dctfp_l1_matrix', 'dctfp_block_min', 'dctfp_row_select', 'dctfp_row_order', 'dctfp_set_option', 'dctfp_get_option', 'dctfp_profile', 'dctfp_host_device_pointer',
@@ -143,7 +148,11 @@ def runtime_report(lib=None) -> str:
 
 
 def _configure(lib):
-    """Declares the argument / result types of every export of include/dctfp.h."""
+    """Declares the argument / result types of every export of include/dctfp.h and include/dctfp_linkage.h."""
+    missing = [fn for fn in LINKAGE_EXPORTS if not hasattr(lib, fn)]
+    if missing:
+        raise ImportError(f'{getattr(lib, "_name", "libdctfp.so")} lacks {", ".join(missing)} (include/dctfp_linkage.h): it was built from '
+                          f'an older tree -- rebuild it (python build_ext.py)')
     if True:
         lib.dctfp_version.restype = C.c_int
         lib.dctfp_last_error.restype = C.c_char_p
@@ -210,6 +219,11 @@ def _configure(lib):
         lib.dctfp_tri_nearest.argtypes = _TRI_TILE + [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
         lib.dctfp_tree_hook.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
                                         C.c_void_p, C.c_int64, C.c_void_p]
+        lib.dctfp_linkage_version.argtypes = []
+        lib.dctfp_linkage_nearest.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32,
+                                              C.c_void_p, C.c_void_p]
+        lib.dctfp_linkage_merge.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
+                                            C.c_void_p]
         lib.dctfp_rect_best.argtypes = _TRI_TILE + [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]
         lib.dctfp_label_sums.argtypes = _TRI_TILE + [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
         lib.dctfp_tri_degree.argtypes = _TRI_TILE + [C.c_void_p, C.c_int64, C.c_void_p]
@@ -245,6 +259,8 @@ def _configure(lib):
         for fn in EXPORTS:
             if fn not in ('dctfp_last_error', 'dctfp_contact_count', 'dctfp_reccut_room'):
                 getattr(lib, fn).restype = C.c_int
+        for fn in LINKAGE_EXPORTS:
+            getattr(lib, fn).restype = C.c_int
         lib.dctfp_contact_count.restype = C.c_int64
         lib.dctfp_reccut_room.restype = C.c_int64
         return lib

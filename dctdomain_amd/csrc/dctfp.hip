@@ -3,6 +3,7 @@
 // scratch, and launches the gfx950 kernels of kernels.hip.h.  No CPU compute path:
 // every entry point needs the GPU.
 #include "dctfp.h"
+#include "dctfp_linkage.h"
 
 #include <hip/hip_runtime.h>
 
@@ -3031,6 +3032,54 @@ int dctfp_tree_hook(dctfp_ctx* ctx, const int32_t* comp, uint64_t* best, int32_t
     HIP_TRY(hipGetLastError());
     return DCTFP_OK;
 } DCTFP_GUARD("dctfp_tree_hook")
+
+// ---- include/dctfp_linkage.h: the two kernels of complete- and average-linkage clustering (k_linkage.hip)
+int dctfp_linkage_version(void) { return DCTFP_LINKAGE_VERSION; }
+
+// What both exports ask of the matrix; `name` = the export, for the message.  The limit first: it holds whatever else is passed.
+static int check_linkage_matrix(const char* name, const void* mat, int32_t wide, int64_t n, int64_t ld) {
+    if (n > DCTFP_LINKAGE_MAX_N) return fail(DCTFP_ERR_LIMIT, "%s: more than %d nodes", name, DCTFP_LINKAGE_MAX_N);
+    if (!mat) return fail(DCTFP_ERR_INVALID, "%s: NULL argument", name);
+    if (wide < 0 || wide > 1) return fail(DCTFP_ERR_INVALID, "%s: wide is 0 (int32 entries) or 1 (int64)", name);
+    if (n < 0 || ld < n) return fail(DCTFP_ERR_INVALID, "%s: bad shape (n < 0 or ld < n)", name);
+    if ((reinterpret_cast<uintptr_t>(mat) & (wide ? 7u : 3u)) != 0) return fail(DCTFP_ERR_INVALID, "%s: the matrix is not aligned to its entries", name);
+    return DCTFP_OK;
+}
+
+int dctfp_linkage_nearest(dctfp_ctx* ctx, const void* mat, int32_t wide, int64_t n, int64_t ld, const int32_t* size, const int32_t* live,
+                          int64_t n_live, int32_t bound, int32_t* nn, void* stream_v) try {
+    if (n > DCTFP_LINKAGE_MAX_N || bound > DCTFP_LINKAGE_MAX_BOUND)
+        return fail(DCTFP_ERR_LIMIT, "dctfp_linkage_nearest: more than %d nodes or a bound above %d", DCTFP_LINKAGE_MAX_N, DCTFP_LINKAGE_MAX_BOUND);
+    if (!ctx || !size || !live || !nn) return fail(DCTFP_ERR_INVALID, "dctfp_linkage_nearest: NULL argument");
+    RC_TRY(check_linkage_matrix("dctfp_linkage_nearest", mat, wide, n, ld));
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    if (n_live < 0 || n_live > n || bound < -1) return fail(DCTFP_ERR_INVALID, "dctfp_linkage_nearest: a live list of %lld ids for %lld nodes, or a bound below -1", (long long)n_live, (long long)n);
+    if (((reinterpret_cast<uintptr_t>(size) | reinterpret_cast<uintptr_t>(live) | reinterpret_cast<uintptr_t>(nn)) & 3u) != 0)
+        return fail(DCTFP_ERR_INVALID, "dctfp_linkage_nearest: size, live or nn is not 4-byte aligned");
+    if (n == 0 || n_live == 0) return DCTFP_OK;
+    HIP_TRY(hipSetDevice(ctx->device));
+    // (one workgroup per live row: at most 46340 of them)
+    launch_linkage_nearest(mat, wide, n, ld, size, live, n_live, bound, nn, (hipStream_t)stream_v);
+    HIP_TRY(hipGetLastError());
+    return DCTFP_OK;
+} DCTFP_GUARD("dctfp_linkage_nearest")
+
+int dctfp_linkage_merge(dctfp_ctx* ctx, void* mat, int32_t wide, int64_t n, int64_t ld, const int32_t* size, const int32_t* partner,
+                        const int32_t* keep, int64_t n_keep, void* stream_v) try {
+    if (n > DCTFP_LINKAGE_MAX_N) return fail(DCTFP_ERR_LIMIT, "dctfp_linkage_merge: more than %d nodes", DCTFP_LINKAGE_MAX_N);
+    if (!ctx || !size || !partner || !keep) return fail(DCTFP_ERR_INVALID, "dctfp_linkage_merge: NULL argument");
+    RC_TRY(check_linkage_matrix("dctfp_linkage_merge", mat, wide, n, ld));
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    if (n_keep < 0 || n_keep > n / 2) return fail(DCTFP_ERR_INVALID, "dctfp_linkage_merge: %lld pairs of %lld nodes", (long long)n_keep, (long long)n);
+    if (((reinterpret_cast<uintptr_t>(size) | reinterpret_cast<uintptr_t>(partner) | reinterpret_cast<uintptr_t>(keep)) & 3u) != 0)
+        return fail(DCTFP_ERR_INVALID, "dctfp_linkage_merge: size, partner or keep is not 4-byte aligned");
+    if (n == 0 || n_keep == 0) return DCTFP_OK;
+    HIP_TRY(hipSetDevice(ctx->device));
+    // (the grid: ceil(n / 256) x n_keep workgroups, n_keep <= 23170 < 65536)
+    launch_linkage_merge(mat, wide, n, ld, size, partner, keep, n_keep, (hipStream_t)stream_v);
+    HIP_TRY(hipGetLastError());
+    return DCTFP_OK;
+} DCTFP_GUARD("dctfp_linkage_merge")
 
 // What the five exports of the band walk over a triangle (band_walk.hip.h) ask of the tile and of n_nodes; `name` = the export, for the
 // message.  The arrays beside the tile are checked by the export that knows them.

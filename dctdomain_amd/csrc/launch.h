@@ -197,6 +197,14 @@ void launch_tri_nearest(const TriTile& t, const int32_t* comp, uint64_t* best, i
 hipError_t launch_tree_hook(const int32_t* comp, uint64_t* best, int32_t* parent, int64_t n_nodes, int32_t* edge_i, int32_t* edge_j,
                             int32_t* edge_key, int32_t* counter, int64_t max_edges, hipStream_t stream);
 
+// complete- and average-linkage clustering (k_linkage.hip; include/dctfp_linkage.h has the state): on a dense n x n matrix of int32
+// (wide = 0) or int64 (wide = 1) entries, per live row the nearest live column within the bound (a workgroup per entry of the live
+// list, no atomics), and the in-place merge of the pairs of a round (a thread per entry of the rows of keep)
+void launch_linkage_nearest(const void* mat, int wide, int64_t n, int64_t ld, const int32_t* size, const int32_t* live, int64_t n_live,
+                            int32_t bound, int32_t* nn, hipStream_t stream);
+void launch_linkage_merge(void* mat, int wide, int64_t n, int64_t ld, const int32_t* size, const int32_t* partner, const int32_t* keep,
+                          int64_t n_keep, hipStream_t stream);
+
 // reciprocal best hits of two files (k_best.hip): one pass over the full rectangle of an int32 L1 tile -- every entry with
 // min(L1, cap) <= bound (cap for a flagged protein) lowers best_row[row0 + r] to key << 32 | (col0 + c) and best_col[col0 + c] to
 // key << 32 | (row0 + r) with agent-scope atomic minima; rect_best_max_cap = the largest cap the kernel's packed LDS words hold

@@ -11,6 +11,8 @@ fingerprints (``-dct.npz``), with the L1 distances computed on the GPU.
     python -m dctdomain_amd.dct_sim --dct NEW-dct.npz --assign REPS-dct.npz --min-domain X [--min-global Y] [--reps-out ALL-dct.npz]
                                     [--output F]
     python -m dctdomain_amd.dct_sim --dct X-dct.npz --tree [domain|global] [--min-domain X | --min-global Y] [--output F]
+    python -m dctdomain_amd.dct_sim --dct X-dct.npz --hac [domain|global] [--method {average,complete}] [--min-domain X | --min-global Y]
+                                    [--flat] [--newick FILE] [--output F]
     python -m dctdomain_amd.dct_sim --dct A-dct.npz --db B-dct.npz --rbh [domain|global] [--min-domain X | --min-global Y] [--domains]
                                     [--dom A.dom] [--db-dom B.dom] [--output F]
     python -m dctdomain_amd.dct_sim --dct X-dct.npz --auc1 [domain|global] (--families FILE | --family-sep C)
@@ -76,6 +78,13 @@ Where the reference loops over protein pairs and, inside, over domain pairs in P
   any score, its lines give the clusters ``--cluster`` finds there.  Boruvka's algorithm in at most ceil(log2 n) + 1 rounds over
   the same tiles: per component the lightest edge that leaves it (``dctfp_tri_nearest``), then one hook per component in the same
   union-find (``dctfp_tree_hook``) and the new labels (``dctfp_cluster_labels``);
+- ``--hac`` (``Dendrogram``, not in the reference) gives the two hierarchical clusterings the modes above lack: complete linkage, whose
+  clusters have a diameter -- every pair inside one is within the cut-off, where single linkage chains and the greedy rule only bounds
+  the distance to the representative -- and average linkage, UPGMA.  The dense n x n matrix of the file stays on the device (n <= 46 340),
+  filled by ``dctfp_protein_min`` / ``dctfp_l1_matrix``; in rounds, every live cluster takes its nearest live cluster within the bound
+  (``dctfp_linkage_nearest``), the mutual pairs merge all at once, and the matrix is updated in place (``dctfp_linkage_merge``).
+  Distances are exact integers -- maxima in int32, sums in int64 compared as fractions -- so the lines ``rep1 rep2 similarity size``,
+  the ``--flat`` clusters and the ``--newick`` trees are the same on every machine;
 - ``--auc1`` (``Auc1``) says how good the scores of a labelled file are, the number of the reference's own sensitivity benchmark
   (bench/cathdb/plot_results.py): every protein is searched against the file, and its AUC1 is the share of its family's other
   members ranked before the first hit of another family; the share of queries whose best hit is of their own family is the top-1
@@ -1434,6 +1443,228 @@ class Tree(FilteredPairs):
             lines.write(pi, pj, *self._scores_of(pi, pj, rows=rows))
             k0 = k1
         out.close()
+
+
+HAC_HEADER = '#rep1 rep2 similarity size'
+HAC_METHODS = ('average', 'complete')
+HAC_MAX_PROTEINS = 46340                   # similarity.LINKAGE_MAX_N: the dense matrix of --hac
+_NEWICK_QUOTED = frozenset("(),:;'[]")
+
+
+def newick_name(name) -> str:
+    """An id as a Newick label: single-quoted, with ``'`` doubled, when it holds any of ``(),:;'[]`` or whitespace."""
+    name = f'{name}'
+    if any(ch in _NEWICK_QUOTED or ch.isspace() for ch in name):
+        return "'" + name.replace("'", "''") + "'"
+    return name
+
+
+class Dendrogram:
+    """The complete- (``method='complete'``) or average-linkage (``'average'``: UPGMA) tree of one file, built on the GPU.
+
+    Nodes are the n proteins; key(i, j) = min(L1, 17000) with ``Tree``'s L1 -- DCTdomain's (``score='domain'``: ``protein_min``) or
+    DCTglobal's (``'global'``: ``l1_matrix`` of the last rows) -- and 17000 against a protein without fingerprints; bound = 16999
+    unless ``min_cut`` gives ``sim_bound(min_cut)``.  A cluster is named by its lowest member.  complete: D(A, B) = the largest key
+    over the member pairs, int32; average: S(A, B) = their sum, int64, height = S / (cA cB) compared as an exact fraction -- "D <=
+    bound" is S <= bound cA cB.  The state is the dense n x n matrix of D or S on the device (n <= ``LINKAGE_MAX_N`` = 46 340; n * n
+    * 4 or 8 bytes, which must fit the free device memory), ``size`` and the live ids.  A round:
+
+    1. ``linkage_nearest``: per live cluster a, nn(a) = the live b != a with D(a, b) <= bound that minimises (D(a, b), id b);
+    2. every pair with nn(a) = b and nn(b) = a merges, all at once, under the lower id (n-element work in torch; one int32, the
+       number of pairs, comes back per round), recorded as (a, b, height, new size, round);
+    3. ``linkage_merge``: every distance to a merged cluster becomes the max / the sum over the pre-round clusters.
+
+    The smallest pair under (D, lo, hi) is always mutual, so a round with a pair within the bound merges at least one: the loop
+    ends with the round that merges nothing and raises beyond n - 1 merging rounds rather than go on.  ``rounds`` = the merging
+    rounds of the last build.  Merge order: (height exact, round, a); both linkages are reducible, so the heights
+    of a parent is never below its children's.
+
+    ``merges()`` = (a, b, num, den, size, round) as int64 numpy arrays in merge order, height = num / den (den = 1 for complete).
+    ``labels(cut)`` replays them: the clusters at any cut whose bound is not above the object's own -- for complete linkage every
+    pair inside a cluster is then within the cut-off."""
+
+    COL_ROWS = FilteredPairs.COL_ROWS
+    TILE_INTS = 1 << 26          # int32 entries of one stripe of the matrix while it is built
+
+    def __init__(self, sid, idx, fps, method: str = 'average', score: str = 'domain', min_cut=None):
+        if method not in HAC_METHODS:
+            raise ValueError(f'method must be one of {HAC_METHODS}')
+        if score not in SCORES:
+            raise ValueError(f'score must be one of {SCORES}')
+        self.sid, self.idx, self.fps = sid, np.asarray(idx, dtype=np.int64), fps
+        self.method, self.score = method, score
+        self.bound = L1_FULL_SCALE - 1 if min_cut is None else min(sim_bound(min_cut), L1_FULL_SCALE)
+        self.rounds = 0
+        self.seconds = {}            # matrix / scan / merge of the last build, filled when ``timed`` is set (tools/linkage_bench.py)
+        self.timed = False
+        self._merges = None
+
+    @property
+    def n(self) -> int:
+        return len(self.idx) - 1
+
+    def matrix_bytes(self) -> int:
+        return self.n * self.n * (4 if self.method == 'complete' else 8)
+
+    def _matrix(self, dev):
+        """The dense key matrix on the device, int32 (complete) or int64 (average), the diagonal at the sentinel; rows padded to
+        16 bytes, so that every row is read with 16-byte loads alone.  Built in stripes of rows x all n columns."""
+        import torch
+        from .similarity import LINKAGE_NONE
+        n, idx = self.n, self.idx
+        dtype = torch.int32 if self.method == 'complete' else torch.int64
+        ld = (n + 3) // 4 * 4
+        store = torch.empty((n, ld), dtype=dtype, device=dev)
+        mat = store[:, :n]
+        total = int(idx[-1])
+        empty = torch.as_tensor(idx[1:] == idx[:-1], device=dev)
+        if self.score == 'global':
+            last_rows, _ = _last_rows(self.fps[:total], idx)
+            last = to_device_int8(last_rows)
+            groups = [(i0, min(n, i0 + max(1, self.TILE_INTS // n))) for i0 in range(0, n, max(1, self.TILE_INTS // n))]
+        else:
+            rows = _DeviceRows(self.fps, idx, self.COL_ROWS)
+            groups = list(_protein_groups(idx, self.COL_ROWS))
+            step = max(1, self.TILE_INTS // n)
+            groups = [(j0, min(i1, j0 + step)) for i0, i1 in groups for j0 in range(i0, i1, step)]
+        for i0, i1 in groups:
+            tile = mat[i0:i1] if dtype == torch.int32 else torch.empty((i1 - i0, n), dtype=torch.int32, device=dev)
+            if self.score == 'global':
+                l1_matrix(last[i0:i1], last, out=tile)
+            else:
+                a, ia = rows(i0, i1), idx[i0:i1 + 1] - idx[i0]
+                for q0, q1 in _protein_groups(idx, self.COL_ROWS):
+                    protein_min(a, ia, rows(q0, q1), idx[q0:q1 + 1] - idx[q0], out=tile[:, q0:q1])
+            tile.clamp_(max=L1_FULL_SCALE)
+            tile[empty[i0:i1]] = L1_FULL_SCALE                 # (the last rows of a protein without fingerprints are zeros: no L1)
+            tile[:, empty] = L1_FULL_SCALE
+            if dtype != torch.int32:
+                mat[i0:i1] = tile
+            del tile
+        mat.diagonal().fill_(LINKAGE_NONE[dtype])
+        return mat
+
+    def _build(self):
+        n = self.n
+        self.rounds = 0
+        self.seconds = {}
+        none = tuple(np.zeros(0, dtype=np.int64) for _ in range(6))
+        if n < 2 or self.bound < 0:
+            return none
+        from .similarity import LINKAGE_MAX_N, linkage_merge, linkage_nearest
+        if n > LINKAGE_MAX_N:
+            raise ValueError(f'--hac keeps the dense matrix of the file on the device: at most {LINKAGE_MAX_N} proteins, not {n}')
+        import torch
+        dev = torch.device('cuda', torch.cuda.current_device())
+        free = torch.cuda.mem_get_info(dev)[0]
+        if self.matrix_bytes() > free:
+            raise ValueError(f'the {self.method}-linkage matrix of {n} proteins needs {self.matrix_bytes()} bytes on the device: {free} are free')
+
+        def clock(name, t0=None):
+            if not self.timed:
+                return None
+            torch.cuda.synchronize(dev)
+            now = time.perf_counter()
+            if t0 is not None:
+                self.seconds[name] = self.seconds.get(name, 0.0) + now - t0
+            return now
+
+        t0 = clock(None)
+        mat = self._matrix(dev)
+        clock('matrix', t0)
+        wide = mat.dtype == torch.int64
+        size = torch.ones(n, dtype=torch.int32, device=dev)
+        live = torch.arange(n, dtype=torch.int32, device=dev)
+        made = []
+        while True:
+            if live.numel() < 2:                                # (one cluster left: nothing to scan for)
+                break
+            if self.rounds >= n - 1:
+                raise RuntimeError(f'the {self.method}-linkage tree of {n} proteins is not finished after {n - 1} merging rounds')
+            t0 = clock(None)
+            nn = linkage_nearest(mat, size, live, self.bound)
+            clock('scan', t0)
+            a = live.long()
+            b = nn[a].long()
+            mutual = (b > a) & (nn[b.clamp(min=0)].long() == a)
+            lo, hi = a[mutual], b[mutual]
+            if lo.numel() == 0:                                 # (the one number a round sends to the host)
+                break
+            self.rounds += 1
+            num = mat[lo, hi].long()
+            den = size[lo].long() * size[hi].long() if wide else torch.ones_like(num)
+            partner = torch.full((n,), -1, dtype=torch.int32, device=dev)
+            partner[lo] = hi.int()
+            partner[hi] = lo.int()
+            t0 = clock(None)
+            linkage_merge(mat, size, partner, lo.int().contiguous())
+            clock('merge', t0)
+            size[lo] += size[hi]
+            size[hi] = 0
+            made.append(torch.stack([lo, hi, num, den, size[lo].long(), torch.full_like(lo, self.rounds)]))
+            live = live[size[live.long()] > 0].contiguous()
+        del mat
+        if not made:
+            return none
+        out = torch.cat(made, dim=1).cpu().numpy()
+        a, b, num, den, sz, rnd = out
+        # merge order (height exact, round, a): heights as Python fractions -- S * den' against S' * den in integers, never floats
+        from fractions import Fraction
+        order = sorted(range(len(a)), key=lambda k: (Fraction(int(num[k]), int(den[k])), rnd[k], a[k]))
+        return tuple(v[order] for v in (a, b, num, den, sz, rnd))
+
+    def merges(self):
+        """(a, b, num, den, size, round): int64 numpy arrays of the merges in merge order (built once); height = num / den."""
+        if self._merges is None:
+            self._merges = self._build()
+        return self._merges
+
+    def heights(self) -> list:
+        """The heights as exact integer pairs (numerator, denominator), in merge order."""
+        _, _, num, den, _, _ = self.merges()
+        return [(int(p), int(q)) for p, q in zip(num, den)]
+
+    def labels(self, cut: float = None) -> np.ndarray:
+        """labels[i] = the lowest member of protein i's cluster at the object's own bound, or at the cut-off ``cut``: the merges of
+        height <= ``sim_bound(cut)`` replayed in merge order.  ValueError for a cut whose bound is above the object's own."""
+        bound = self.bound if cut is None else sim_bound(cut)
+        if bound > self.bound:
+            raise ValueError(f'the tree was built with bound {self.bound}: it does not hold the clusters at {cut} (bound {bound})')
+        lab = np.arange(max(self.n, 0), dtype=np.int32)
+        a, b, num, den, _, _ = self.merges()
+        members = {}
+        for k in np.flatnonzero(num <= bound * den):           # (int64: at most 17000 * 46340^2 / 4)
+            x, y = int(lab[a[k]]), int(lab[b[k]])
+            x, y = min(x, y), max(x, y)
+            mx, my = members.pop(x, [x]), members.pop(y, [y])
+            lab[my] = x
+            members[x] = mx + my
+        return lab
+
+    def lines(self) -> list:
+        """The merge lines ``{id a} {id b} {similarity:.4f} {size}`` in merge order; similarity = 1 - height / 17000 in one correctly
+        rounded division of Python ints."""
+        a, b, num, den, size, _ = self.merges()
+        return [f'{self.sid[a[k]]} {self.sid[b[k]]} {1 - int(num[k]) / (L1_FULL_SCALE * int(den[k])):.4f} {size[k]}' for k in range(len(a))]
+
+    def write(self, sink):
+        """Calls ``sink(bytes)`` with the text of the merges (no header)."""
+        text = ''.join(line + '\n' for line in self.lines())
+        if text:
+            sink(text.encode('utf8'))
+
+    def newick(self) -> str:
+        """One tree per line in id order, each ending in ``;``: a merge is ``(A:la,B:lb)`` with the lower id first, a branch
+        (height - the child's height, 0 for a leaf) / 17000 as ``.6f``, an unmerged protein ``id;``."""
+        from fractions import Fraction
+        a, b, num, den, _, _ = self.merges()
+        node = {i: (newick_name(self.sid[i]), Fraction(0)) for i in range(self.n)}
+        for k in range(len(a)):
+            h = Fraction(int(num[k]), int(den[k]))
+            (ta, ha), (tb, hb) = node[int(a[k])], node.pop(int(b[k]))
+            la, lb = (h - ha) / L1_FULL_SCALE, (h - hb) / L1_FULL_SCALE
+            node[int(a[k])] = (f'({ta}:{la.numerator / la.denominator:.6f},{tb}:{lb.numerator / lb.denominator:.6f})', h)
+        return ''.join(node[i][0] + ';\n' for i in sorted(node))
 
 
 AUC1_HEADER = '#query family members tp auc1 first_fp fp_score'
@@ -2813,6 +3044,34 @@ def hist_sim(npzfile: str, report: Report, score: str = 'domain', bins: int = HI
     return _reporting(run, header=hist_header(score, families is not None or family_sep is not None))(npzfile, report)
 
 
+def hac_sim(npzfile: str, report: Report, score: str = 'domain', method: str = 'average', min_domain: float = None, min_global: float = None,
+            flat: bool = False, newick: str = None):
+    """The average- (``method='average'``: UPGMA) or complete-linkage (``'complete'``) tree of the file (``Dendrogram``) on DCTdomain
+    (``score='domain'``) or DCTglobal (``'global'``): a header and one line ``rep1 rep2 similarity size`` per merge, most similar
+    first.  ``min_domain`` / ``min_global``: the cut-off of that score above which nothing merges; the other score's cut-off is an
+    error.  ``flat`` (needs the cut-off): the clusters at the cut-off instead, as ``cluster_sim``'s ``representative member`` lines
+    -- with complete linkage every pair inside a cluster is within the cut-off.  ``newick``: a file that gets the trees beside
+    either output (``Dendrogram.newick``).  ``report``: an open ``Report``, or a path / None as for the other modes."""
+    min_cut = _cut_of(score, min_domain, min_global, 'the linkage tree orders the pairs')
+    if method not in HAC_METHODS:
+        raise ValueError(f'method must be one of {HAC_METHODS}')
+    if flat and min_cut is None:
+        raise ValueError('flat clusters are the clusters at a cut-off: min_domain, or min_global with score="global"')
+
+    def run(npzfile, report):
+        sid, idx, fps = _load_npz(npzfile)
+        tree = Dendrogram(sid, idx, fps, method=method, score=score, min_cut=min_cut)
+        if flat:
+            for part in cluster_lines(sid, tree.labels()):
+                report.raw(memoryview(part))
+        else:
+            tree.write(report.raw)
+        if newick is not None:
+            with open(newick, 'w', encoding='utf8') as fh:
+                fh.write(tree.newick())
+    return _reporting(run, header=CLUSTER_HEADER if flat else HAC_HEADER)(npzfile, report)
+
+
 RANKS = ('global', 'domain')
 LINKAGES = ('single', 'greedy')
 LEVELS = ('protein', 'domain')
@@ -2833,7 +3092,8 @@ _GIVEN = {'--pair': bool, '--db': bool, '--cluster': bool, '--domains': bool, '-
           '--assign': _is_set, '--tree': _is_set, '--rank': _is_set, '--linkage': _is_set, '--level': _is_set, '--reps-out': _is_set,
           '--dom': _is_set, '--db-dom': _is_set, '--min-coverage': _is_set, '--cov-unit': _is_set, '--rep': _is_set,
           '--min-neighbors': _is_set, '--auc1': _is_set, '--families': _is_set, '--family-sep': _is_set, '--hist': _is_set, '--bins': _is_set,
-          '--zscore': bool, '--min-z': _is_set, '--domain-map': _is_set}
+          '--zscore': bool, '--min-z': _is_set, '--domain-map': _is_set,
+          '--hac': _is_set, '--method': _is_set, '--flat': bool, '--newick': _is_set}
 # mode -> (what it does; for a mode that takes a score, what that score does; the flags it refuses, in the order they are named).
 # The modes are checked in this order.
 _MODES = {'--rbh': ('prints the reciprocal best hits of --dct and --db', 'ranks the hits',
@@ -2851,6 +3111,13 @@ _MODES = {'--rbh': ('prints the reciprocal best hits of --dct and --db', 'ranks 
           '--hist': ('bins the scores of all pairs of --dct', 'bins the pairs',
                      ('--pair', '--db', '--cluster', '--assign', '--rank', '--linkage', '--level', '--no-whole', '--reps-out', '--domains',
                       '--dom', '--db-dom', '--domain-map', '--min-coverage', '--cov-unit', '--rep', '--min-neighbors', '--zscore', '--min-z', '--auc1'))}
+# --hac, a mode like --tree, in a table of its own beside the five above: it refuses what --tree refuses and --tree itself, and each of the
+# five refuses it and the options that go with it (_HAC_FLAGS), named after the flags of its own list
+_HAC_MODE = {'--hac': ('prints the average- or complete-linkage tree of --dct', 'orders the pairs',
+                    ('--pair', '--db', '--cluster', '--assign', '--tree', '--rank', '--linkage', '--level', '--no-whole', '--reps-out', '--domains',
+                     '--dom', '--db-dom', '--domain-map', '--min-coverage', '--cov-unit', '--rep', '--min-neighbors', '--zscore', '--min-z', '--auc1',
+                     '--hist'))}
+_HAC_FLAGS = ('--hac', '--method', '--flat', '--newick')
 # the options that say where --auc1 and --hist find the family of a protein: exactly one of them with --auc1, at most one with --hist,
 # none without either
 _FAMILY_FLAGS = ('--families', '--family-sep')
@@ -2894,15 +3161,22 @@ class _Parser(argparse.ArgumentParser):
     ``--domain-map [X]`` adds the map of all matched domain pairs to every result line and implies ``--domains``, in every mode that
     prints pair lines (``--pair``, ``--db`` with or without ``--rbh``, the all-against-all): an error beside ``--cluster`` and beside
     ``--tree``, ``--assign``, ``--auc1`` and ``--hist`` (``_MODES``), or with X outside (0, 1]; it is absent from the namespace of a
-    command line without it, True there for the bare flag."""
+    command line without it, True there for the bare flag.
+    ``--hac`` prints the average- or complete-linkage tree of the file, a sixth mode (``_HAC_MODE``, checked after the five): it refuses what ``--tree`` refuses
+    and ``--tree`` itself, and the other five refuse it and the three options that go with it; its own score's cut-off is allowed and
+    the other score's an error.  ``--method`` (average, the default, or complete), ``--flat`` (the clusters at the cut-off: an error
+    without that cut-off) and ``--newick FILE`` are errors without ``--hac``; all four are absent from the namespace of a command line
+    without them.  ``--linkage`` is not extended: it names the rules of ``--cluster``."""
 
     def parse_known_args(self, args=None, namespace=None):
         ns, rest = super().parse_known_args(args, namespace)
         cut = ns.min_domain is not None or ns.min_global is not None
-        for mode, (does, orders, refused) in _MODES.items():
+        for mode, (does, orders, refused) in {**_MODES, **_HAC_MODE}.items():
             score = getattr(ns, _dest(mode), None)
             if score is None:
                 continue
+            if mode in _MODES:
+                refused = refused + _HAC_FLAGS
             beside = [flag for flag in refused if _GIVEN[flag](getattr(ns, _dest(flag), None))]
             if beside:
                 self.error(f'{mode} {does}: not with {beside[0]}')
@@ -2926,6 +3200,13 @@ class _Parser(argparse.ArgumentParser):
             other = {'domain': 'global', 'global': 'domain'}.get(score)
             if orders and getattr(ns, f'min_{other}') is not None:
                 self.error(f'{mode} {score} {orders} by DCT{score}: its cut-off is --min-{score}, not --min-{other}')
+        hac = getattr(ns, 'hac', None)
+        for flag, does in (('--method', 'says which linkage the tree of --hac is built by'), ('--flat', 'prints the clusters of --hac at its cut-off'),
+                           ('--newick', 'writes the tree of --hac in Newick format')):
+            if hac is None and _GIVEN[flag](getattr(ns, _dest(flag), None)):
+                self.error(f'{flag} {does}: it needs --hac')
+        if hac is not None and getattr(ns, 'flat', False) and getattr(ns, f'min_{hac}') is None:
+            self.error(f'--flat prints the clusters at a cut-off: with --hac {hac} it needs --min-{hac}')
         bins = getattr(ns, 'bins', None)
         if bins is not None:
             if getattr(ns, 'hist', None) is None:
@@ -3095,6 +3376,20 @@ def build_parser() -> argparse.ArgumentParser:
                     help='print the single-linkage tree of the file instead of all pairs: the n - 1 all-against-all lines that join the '
                          'proteins most similar first, by DCTdomain (domain, the default) or DCTglobal (global) -- cut at any score they '
                          'give the clusters --cluster finds there; --min-domain X (--min-global Y with global) takes no pair below it')
+    ap.add_argument('--hac', nargs='?', choices=SCORES, const='domain', default=argparse.SUPPRESS,
+                    help='print the average- or complete-linkage tree of the file (--method) instead of all pairs: one "rep1 rep2 similarity '
+                         'size" line per merge, most similar first, by DCTdomain (domain, the default) or DCTglobal (global); a cluster is '
+                         'named by its first protein in the file.  --min-domain X (--min-global Y with global) merges nothing below it.  At '
+                         f'most {HAC_MAX_PROTEINS} proteins: the dense matrix of the file stays on the GPU')
+    ap.add_argument('--method', choices=HAC_METHODS, default=argparse.SUPPRESS,
+                    help='--hac: average linkage (the default: UPGMA, the mean distance of the member pairs) or complete linkage (the '
+                         'largest: every pair inside a cluster is then within the height at which it formed)')
+    ap.add_argument('--flat', action='store_true', default=argparse.SUPPRESS,
+                    help='--hac with a cut-off: print the clusters at the cut-off, one "representative member" line per protein as --cluster '
+                         'does, instead of the merges')
+    ap.add_argument('--newick', metavar='FILE', default=argparse.SUPPRESS,
+                    help='--hac: also write the tree to FILE in Newick format, one tree per line for a forest, branch lengths in units of '
+                         'distance (1 - similarity)')
     ap.add_argument('--rbh', nargs='?', choices=SCORES, const='domain', default=argparse.SUPPRESS,
                     help='with --db: print the reciprocal best hits of the two files instead of every query\'s hits -- the pairs in which '
                          'each protein is the other\'s best hit among the proteins of the other file, by DCTdomain (domain, the default) or '
@@ -3145,6 +3440,7 @@ def main(argv=None):
     min_coverage = getattr(args, 'min_coverage', None)
     cover = {'min_coverage': min_coverage, 'cov_unit': getattr(args, 'cov_unit', 'residues')} if min_coverage is not None else {}
     auc1, hist = getattr(args, 'auc1', None), getattr(args, 'hist', None)
+    hac, flat = getattr(args, 'hac', None), getattr(args, 'flat', False)
     family = {'families': getattr(args, 'families', None), 'family_sep': getattr(args, 'family_sep', None)}
     min_z = getattr(args, 'min_z', None)
     zscore = getattr(args, 'zscore', False) or min_z is not None
@@ -3152,7 +3448,8 @@ def main(argv=None):
     mapped = getattr(args, 'domain_map', None)
     maps = {'domain_map': mapped} if mapped is not None else {}  # (the functions take the option only where the command line has it)
     report = Report(args.output, _header(hist_header(hist, any(v is not None for v in family.values())) if hist is not None else
-                                         AUC1_HEADER if auc1 is not None else CLUSTER_HEADER if args.cluster or assign is not None else HEADER,
+                                         AUC1_HEADER if auc1 is not None else HAC_HEADER if hac is not None and not flat else
+                                         CLUSTER_HEADER if args.cluster or assign is not None or hac is not None else HEADER,
                                          level, domains, mapped) + _z_header(zscore, getattr(args, 'rbh', None) is not None, args.rank))
     t_work = time.time()
     if hist is not None:
@@ -3160,6 +3457,9 @@ def main(argv=None):
                  **family)
     elif auc1 is not None:
         auc1_sim(args.dct, report, score=auc1, min_domain=args.min_domain, min_global=args.min_global, **family)
+    elif hac is not None:
+        hac_sim(args.dct, report, score=hac, method=getattr(args, 'method', 'average'), min_domain=args.min_domain, min_global=args.min_global,
+                flat=flat, newick=getattr(args, 'newick', None))
     elif getattr(args, 'tree', None) is not None:
         tree_sim(args.dct, report, score=args.tree, min_domain=args.min_domain, min_global=args.min_global)
     elif getattr(args, 'rbh', None) is not None:

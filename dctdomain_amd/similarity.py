@@ -653,6 +653,56 @@ def tree_hook(ts: TreeState):
                 *(t.data_ptr() if t.numel() else None for t in edges), ts.counter.data_ptr(), ts.edge_i.numel())
 
 
+LINKAGE_MAX_N = _lib.LINKAGE_MAX_N             # dctfp_linkage_*'s limit: n * n fits 31 bits and S * c fits 63
+LINKAGE_NONE = {torch.int32: 0x7fffffff, torch.int64: 0x7fffffffffffffff}     # the diagonal: passes no bound test
+
+
+def _linkage_args(mat: torch.Tensor, size: torch.Tensor, arrays):
+    """(n, lead) of a linkage matrix: ``lead`` = (address, wide, n, ld), the arguments both exports of include/dctfp_linkage.h take
+    first.  ``mat``: 2-D device int32 (complete linkage) or int64 (average), unit column stride, n = ``len(size)`` columns and
+    at most n rows; ``arrays``: the int32 node arrays beside it."""
+    if mat.dtype not in LINKAGE_NONE or mat.dim() != 2 or mat.device.type != 'cuda' or (mat.shape[1] > 1 and mat.stride(1) != 1):
+        raise ValueError('the matrix must be a 2-D int32 or int64 device tensor with unit column stride')
+    n = size.numel()
+    if mat.shape[1] != n or mat.shape[0] > n:
+        raise ValueError('the matrix has one column per entry of size and no more rows than columns')
+    if n > LINKAGE_MAX_N:
+        raise ValueError(f'at most {LINKAGE_MAX_N} nodes')
+    for t in (size, *arrays):
+        if t.dtype != torch.int32 or t.dim() != 1 or not t.is_contiguous() or t.device != mat.device:
+            raise ValueError('size and the arrays beside it must be contiguous 1-D int32 tensors on the device of the matrix')
+    return n, (mat.data_ptr(), int(mat.dtype == torch.int64), n, mat.stride(0) if mat.shape[0] > 1 else max(n, 1))
+
+
+def linkage_nearest(mat: torch.Tensor, size: torch.Tensor, live: torch.Tensor, bound: int, nn: torch.Tensor = None) -> torch.Tensor:
+    """Step 1 of a round of complete (int32 ``mat``) or average (int64) linkage (``dctfp_linkage_nearest``): device int32 ``nn``, for
+    every a of ``live`` the x != a with ``size[x] > 0`` and D(a, x) <= ``bound`` that minimises (D(a, x), x), -1 = none; D is the
+    entry, or for int64 the entry over ``size[a] * size[x]`` as an exact fraction.  The entries of ``nn`` (made here, all -1, unless
+    given) for ids outside ``live`` are left alone.  ``mat`` may hold the first rows of the matrix only when ``live`` names no other."""
+    n, lead = _linkage_args(mat, size, (live,) if nn is None else (live, nn))
+    if nn is None:
+        nn = torch.full((n,), -1, dtype=torch.int32, device=mat.device)
+    if nn.numel() != n or live.numel() > n:
+        raise ValueError('nn has one entry per node and live at most as many')
+    if live.numel() and mat.shape[0] < n and not 0 <= int(live.min()) <= int(live.max()) < mat.shape[0]:
+        raise IndexError('a live id outside the rows of the matrix')
+    if n and live.numel():
+        _launch(mat.device, 'dctfp_linkage_nearest', *lead, size.data_ptr(), live.data_ptr(), live.numel(), int(max(-1, bound)), nn.data_ptr())
+    return nn
+
+
+def linkage_merge(mat: torch.Tensor, size: torch.Tensor, partner: torch.Tensor, keep: torch.Tensor):
+    """Step 2 of a round, in place (``dctfp_linkage_merge``): ``partner[x]`` = the other cluster of x's pair, -1 = none; ``keep`` = the
+    lower id of every pair.  Every entry between a cluster of ``keep`` and a cluster that lives on becomes the maximum (int32) or
+    the sum (int64) of the up to four entries of the clusters they consist of, on both sides of the diagonal.  Rows and columns of
+    the absorbed clusters keep their values: the caller sets their ``size`` to 0, which masks them in ``linkage_nearest``."""
+    n, lead = _linkage_args(mat, size, (partner, keep))
+    if mat.shape[0] != n or partner.numel() != n or 2 * keep.numel() > n:
+        raise ValueError('a square matrix, one partner per node and at most n / 2 pairs')
+    if n and keep.numel():
+        _launch(mat.device, 'dctfp_linkage_merge', *lead, size.data_ptr(), partner.data_ptr(), keep.data_ptr(), keep.numel())
+
+
 BEST_NONE = -1                                 # best_row / best_col as torch shows them: int64 -1 = all 64 bits set = no hit
 
 
