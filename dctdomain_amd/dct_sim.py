@@ -145,9 +145,11 @@ floats are identical."""
 from __future__ import annotations
 
 import argparse
+import contextlib
 import math
 import sys
 import time
+import typing
 
 import numpy as np
 
@@ -2719,24 +2721,41 @@ def _z_header(zscore, rbh: bool = False, rank: str = None) -> str:
     return '' if not zscore else ' z-query z-db' if rbh else f' z-{rank or "global"}'
 
 
-def _reporting(fn=None, *, header: str = HEADER, rbh: bool = False):
-    """The mode functions keep the reference's signature -- the last argument may be an output path or
-    ``None`` (stdout) -- and also take an open ``Report``.  Keyword arguments (options beyond the reference's) pass through.
-    ``@_reporting(header=...)``: the header of a report opened here; ``rbh``: its z columns are ``--rbh``'s."""
-    if fn is None:
-        return lambda f: _reporting(f, header=header, rbh=rbh)
+def _lines_header(kw: dict, rbh: bool = False) -> str:
+    """The header of the modes that print pair lines, from the keyword arguments of the mode function: a call that asks for the domain
+    pair carries the two extra column names, one that asks for the map its column, one that asks for z its (``rbh``: the two of ``--rbh``)."""
+    return (_header(HEADER, None, any(kw.get(k) for k in ('domains', 'dom', 'db_dom')), kw.get('domain_map'))
+            + _z_header(kw.get('zscore') or kw.get('min_z') is not None, rbh, kw.get('rank')))
 
+
+def mode_header(name: str, kw: dict) -> str:
+    """The header under which the mode function ``name`` prints when it is called with the keyword arguments ``kw``: the one place that
+    knows it (the entry of ``_MODES``), for ``main`` and for a mode function that opens its own report."""
+    return next(mode for mode in _MODES if mode.fn == name).header(kw)
+
+
+@contextlib.contextmanager
+def _opened(report, header: str):
+    """The report argument of a mode function as an open ``Report``: itself if it is one (the caller closes it), else one opened here on
+    that path (``None``: stdout) under ``header`` and closed on the way out."""
+    if isinstance(report, Report):
+        yield report
+        return
+    report = Report(report, header)
+    try:
+        yield report
+    finally:
+        report.close()
+
+
+def _reporting(fn):
+    """The mode functions keep the reference's signature -- the last positional argument may be an output path or ``None`` (stdout) --
+    and also take an open ``Report``.  Keyword arguments (options beyond the reference's) pass through, and say under which header a
+    report opened here prints (``mode_header`` of the function's name)."""
     def run(*args, **kw):
         *head, output = args
-        if isinstance(output, Report):
-            return fn(*head, output, **kw)
-        # (a report opened here for a call that asks for the domain pair carries the two extra column names, one that asks for z its)
-        report = Report(output, _header(header, kw.get('level'), any(kw.get(k) for k in ('domains', 'dom', 'db_dom')), kw.get('domain_map'))
-                        + _z_header(kw.get('zscore') or kw.get('min_z') is not None, rbh, kw.get('rank')))
-        try:
+        with _opened(output, mode_header(fn.__name__, kw)) as report:
             return fn(*head, report, **kw)
-        finally:
-            report.close()
     run.__doc__, run.__name__ = fn.__doc__, fn.__name__
     return run
 
@@ -2850,7 +2869,7 @@ def all_sim(npzfile: str, report: Report, min_domain: float = None, min_global: 
         job.write(report.raw)
 
 
-@_reporting(header=CLUSTER_HEADER)
+@_reporting
 def cluster_sim(npzfile: str, report: Report, min_domain: float = None, min_global: float = None, linkage: str = 'single',
                 level: str = 'protein', whole: bool = True, dom: str = None, reps_out: str = None, min_coverage: float = None,
                 cov_unit: str = 'residues', rep: str = 'first', min_neighbors: int = None):
@@ -2910,7 +2929,7 @@ def cluster_sim(npzfile: str, report: Report, min_domain: float = None, min_glob
         write_reps(reps_out, [(sid, idx, fps, _npz_dom(npzfile, int(idx[-1])), first if medoid is None else medoid[first])])
 
 
-@_reporting(header=CLUSTER_HEADER)
+@_reporting
 def assign_sim(npzfile: str, repfile: str, report: Report, min_domain: float = None, min_global: float = None, reps_out: str = None):
     """Places the proteins of ``npzfile`` on the representatives of ``repfile`` at the cut-offs (``Assignment``): one line
     ``representative member`` per protein of ``npzfile``.  ``reps_out``: all proteins of ``repfile`` followed by the new
@@ -2947,7 +2966,7 @@ def tree_sim(npzfile: str, report: Report, score: str = 'domain', min_domain: fl
     Tree(sid, idx, fps, score=score, min_cut=min_cut).write(report.raw)
 
 
-@_reporting(rbh=True)
+@_reporting
 def rbh_sim(npzfile: str, dbfile: str, report: Report, score: str = 'domain', min_domain: float = None, min_global: float = None,
             domains: bool = False, dom: str = None, db_dom: str = None, zscore: bool = False, min_z: float = None, domain_map=None):
     """The reciprocal best hits of the proteins of ``npzfile`` and ``dbfile`` (``ReciprocalBest``) on DCTdomain (``score='domain'``) or
@@ -3007,7 +3026,7 @@ def families_from_ids(sid, sep: str) -> list:
     return out
 
 
-@_reporting(header=AUC1_HEADER)
+@_reporting
 def auc1_sim(npzfile: str, report: Report, score: str = 'domain', families: str = None, family_sep: str = None, min_domain: float = None,
              min_global: float = None):
     """AUC1 and the top-1 rates of a labelled file (``Auc1``) on DCTdomain (``score='domain'``) or DCTglobal (``'global'``): one line
@@ -3036,12 +3055,10 @@ def hist_sim(npzfile: str, report: Report, score: str = 'domain', bins: int = HI
         raise ValueError('the families come from one place: families (a file) or family_sep (the ids themselves)')
     if not isinstance(bins, (int, np.integer)) or not 1 <= bins <= HIST_MAX_BINS:
         raise ValueError(f'bins is a number of cut-offs: 1 .. {HIST_MAX_BINS}')
-
-    def run(npzfile, report):
+    with _opened(report, mode_header('hist_sim', {'score': score, 'families': families, 'family_sep': family_sep})) as report:
         sid, idx, fps = _load_npz(npzfile)
         labels = read_families(families, sid) if families is not None else families_from_ids(sid, family_sep) if family_sep is not None else None
         Histogram(sid, idx, fps, labels, score=score, min_cut=min_cut).write(report.raw, bins)
-    return _reporting(run, header=hist_header(score, families is not None or family_sep is not None))(npzfile, report)
 
 
 def hac_sim(npzfile: str, report: Report, score: str = 'domain', method: str = 'average', min_domain: float = None, min_global: float = None,
@@ -3057,8 +3074,7 @@ def hac_sim(npzfile: str, report: Report, score: str = 'domain', method: str = '
         raise ValueError(f'method must be one of {HAC_METHODS}')
     if flat and min_cut is None:
         raise ValueError('flat clusters are the clusters at a cut-off: min_domain, or min_global with score="global"')
-
-    def run(npzfile, report):
+    with _opened(report, mode_header('hac_sim', {'flat': flat})) as report:
         sid, idx, fps = _load_npz(npzfile)
         tree = Dendrogram(sid, idx, fps, method=method, score=score, min_cut=min_cut)
         if flat:
@@ -3069,7 +3085,6 @@ def hac_sim(npzfile: str, report: Report, score: str = 'domain', method: str = '
         if newick is not None:
             with open(newick, 'w', encoding='utf8') as fh:
                 fh.write(tree.newick())
-    return _reporting(run, header=CLUSTER_HEADER if flat else HAC_HEADER)(npzfile, report)
 
 
 RANKS = ('global', 'domain')
@@ -3078,231 +3093,261 @@ LEVELS = ('protein', 'domain')
 REPS = ('first', 'medoid')
 
 
-def _dest(flag: str) -> str:
-    return flag[2:].replace('-', '_')
+def _value(ns, flag: str):
+    """The value of ``flag`` in the namespace; None where the namespace has no such key (the options added with ``argparse.SUPPRESS``)."""
+    return getattr(ns, flag[2:].replace('-', '_'), None)
 
 
-def _is_set(value) -> bool:
-    return value is not None
+# the flags that are given when their value is true; every other one when it is not None
+_SWITCHES = frozenset(('--pair', '--db', '--cluster', '--domains', '--no-whole', '--zscore', '--flat'))
 
 
-# flag -> is it on the command line, by its value in the namespace (None where the namespace has no such key: the options added
-# with ``argparse.SUPPRESS``)
-_GIVEN = {'--pair': bool, '--db': bool, '--cluster': bool, '--domains': bool, '--no-whole': bool,
-          '--assign': _is_set, '--tree': _is_set, '--rank': _is_set, '--linkage': _is_set, '--level': _is_set, '--reps-out': _is_set,
-          '--dom': _is_set, '--db-dom': _is_set, '--min-coverage': _is_set, '--cov-unit': _is_set, '--rep': _is_set,
-          '--min-neighbors': _is_set, '--auc1': _is_set, '--families': _is_set, '--family-sep': _is_set, '--hist': _is_set, '--bins': _is_set,
-          '--zscore': bool, '--min-z': _is_set, '--domain-map': _is_set,
-          '--hac': _is_set, '--method': _is_set, '--flat': bool, '--newick': _is_set}
-# mode -> (what it does; for a mode that takes a score, what that score does; the flags it refuses, in the order they are named).
-# The modes are checked in this order.
-_MODES = {'--rbh': ('prints the reciprocal best hits of --dct and --db', 'ranks the hits',
-                    ('--pair', '--cluster', '--assign', '--tree', '--rank', '--linkage', '--level', '--no-whole', '--reps-out',
-                     '--min-coverage', '--cov-unit', '--rep', '--min-neighbors', '--auc1', '--hist')),
-          '--tree': ('prints the single-linkage tree of --dct', 'orders the pairs',
-                     ('--pair', '--db', '--cluster', '--assign', '--rank', '--linkage', '--level', '--no-whole', '--reps-out', '--domains',
-                      '--dom', '--db-dom', '--domain-map', '--min-coverage', '--cov-unit', '--rep', '--min-neighbors', '--zscore', '--min-z', '--auc1', '--hist')),
-          '--assign': ('places the proteins of --dct on a fixed set of representatives', None,
-                       ('--pair', '--db', '--cluster', '--rank', '--domains', '--dom', '--db-dom', '--domain-map', '--linkage', '--level', '--no-whole',
-                        '--min-coverage', '--cov-unit', '--rep', '--min-neighbors', '--zscore', '--min-z', '--auc1', '--hist')),
-          '--auc1': ('measures the AUC1 and the top-1 rates of --dct', 'ranks the hits',
-                     ('--pair', '--db', '--cluster', '--assign', '--rank', '--linkage', '--level', '--no-whole', '--reps-out', '--domains',
-                      '--dom', '--db-dom', '--domain-map', '--min-coverage', '--cov-unit', '--rep', '--min-neighbors', '--zscore', '--min-z', '--hist')),
-          '--hist': ('bins the scores of all pairs of --dct', 'bins the pairs',
-                     ('--pair', '--db', '--cluster', '--assign', '--rank', '--linkage', '--level', '--no-whole', '--reps-out', '--domains',
-                      '--dom', '--db-dom', '--domain-map', '--min-coverage', '--cov-unit', '--rep', '--min-neighbors', '--zscore', '--min-z', '--auc1'))}
-# --hac, a mode like --tree, in a table of its own beside the five above: it refuses what --tree refuses and --tree itself, and each of the
-# five refuses it and the options that go with it (_HAC_FLAGS), named after the flags of its own list
-_HAC_MODE = {'--hac': ('prints the average- or complete-linkage tree of --dct', 'orders the pairs',
-                    ('--pair', '--db', '--cluster', '--assign', '--tree', '--rank', '--linkage', '--level', '--no-whole', '--reps-out', '--domains',
-                     '--dom', '--db-dom', '--domain-map', '--min-coverage', '--cov-unit', '--rep', '--min-neighbors', '--zscore', '--min-z', '--auc1',
-                     '--hist'))}
-_HAC_FLAGS = ('--hac', '--method', '--flat', '--newick')
-# the options that say where --auc1 and --hist find the family of a protein: exactly one of them with --auc1, at most one with --hist,
-# none without either
-_FAMILY_FLAGS = ('--families', '--family-sep')
+def _given(ns, flag: str) -> bool:
+    """Is ``flag`` on the command line, by its value in the namespace."""
+    return bool(_value(ns, flag)) if flag in _SWITCHES else _value(ns, flag) is not None
+
+
+# The conditions of a rule, each a function of the namespace: one of the flags is given, none of them is, the value of a flag is
+# ``test`` or passes it, all of several conditions hold.
+def _with(*flags):
+    return lambda ns: any(_given(ns, flag) for flag in flags)
+
+
+def _without(*flags):
+    return lambda ns: not any(_given(ns, flag) for flag in flags)
+
+
+def _when(flag: str, test):
+    return lambda ns: test(_value(ns, flag)) if callable(test) else _value(ns, flag) == test
+
+
+def _and(*conditions):
+    return lambda ns: all(holds(ns) for holds in conditions)
+
+
+_DOMAIN_LEVEL = _when('--level', 'domain')
+
+
+def _needs_hac(does: str) -> tuple:
+    return ((_without('--hac'), f'{{0}} {does}: it needs --hac'),)
+
+
+def _of_db_hits(does: str) -> tuple:
+    return ((_with('--pair'), f'{{0}} {does}: not with --pair'), (_with('--cluster'), f'{{0}} {does}: not with --cluster'),
+            (_without('--db'), f'{{0}} {does}: it needs --db'))
+
+
+def _reps_out_has_no_set(ns) -> bool:
+    """--reps-out has three contexts: --assign, and --cluster at protein level with --linkage greedy or with --rep medoid."""
+    clusters = _given(ns, '--cluster') and (_value(ns, '--linkage') == 'greedy' or _value(ns, '--rep') == 'medoid')
+    return not _given(ns, '--assign') and not (clusters and not _DOMAIN_LEVEL(ns))
+
+
+def _explains(ns) -> bool:
+    """Do the result lines carry the domain pair: --domains, or what implies it -- --domain-map, --db-dom and --dom, except that beside
+    --cluster with --min-coverage --dom gives the coverage its residues (no result lines to explain)."""
+    weighs = _given(ns, '--min-coverage') and _given(ns, '--cluster')
+    return _with('--domains', '--domain-map', '--db-dom')(ns) or (_given(ns, '--dom') and not weighs)
+
+
+# The family options of --auc1 and --hist: none without either, and each the same text for both.
+_FAMILY = ((_without('--auc1', '--hist'), '{0} says which family a protein belongs to, for --auc1 to judge the hits by: it needs --auc1'),)
+_FAMILIES = ((_and(_with('--families'), _with('--family-sep')), '{0} takes the families from one place: --families or --family-sep, not both'),
+             (_when('--family-sep', ''), '--family-sep is the text between id and family: at least one character'))
+# (--rbh takes its own score's cut-off)
+_ALL_ONLY = ((_and(_with('--pair', '--db'), _without('--rbh')), '{0} applies to all-against-all only, not to --pair or --db'),)
+
+# flag -> its rules as rows (condition on the namespace, message), checked in this order when the flag is given; the message is formatted
+# with the flag ({0}) and the namespace.  The options are checked in the order of the table, after the modes.
+_OPTIONS = {
+    '--method': _needs_hac('says which linkage the tree of --hac is built by'),
+    '--flat': _needs_hac('prints the clusters of --hac at its cut-off') + (
+        (lambda ns: getattr(ns, f'min_{ns.hac}') is None, '--flat prints the clusters at a cut-off: with --hac {hac} it needs --min-{hac}'),),
+    '--newick': _needs_hac('writes the tree of --hac in Newick format'),
+    '--bins': ((_without('--hist'), '--bins says how many cut-offs the table of --hist has: it needs --hist'),
+               (_when('--bins', lambda bins: not 1 <= bins <= HIST_MAX_BINS), f'--bins is a number of cut-offs: 1 .. {HIST_MAX_BINS}')),
+    '--families': _FAMILY,
+    '--family-sep': _FAMILY,
+    '--zscore': _of_db_hits('places every hit of a database search in the background of its query'),
+    '--min-z': _of_db_hits('cuts the hits of a database search by their z-score'),
+    '--reps-out': ((_reps_out_has_no_set, '--reps-out writes representatives: it needs --assign, or --cluster --linkage greedy at protein level'),),
+    '--rank': ((lambda ns: _given(ns, '--pair') or not _given(ns, '--db'),
+                '--rank applies to database search (--db) only, not to --pair or all-against-all'),),
+    '--db-dom': ((_without('--db'), '--db-dom names the .dom file of --db: it needs --db'),),
+    '--min-coverage': (
+        (_with('--pair', '--db'), '--min-coverage applies to all-against-all only, not to --pair or --db'),
+        (_DOMAIN_LEVEL, '--min-coverage is a share of a protein: not with --level domain, which joins single fingerprints'),
+        (_without('--min-domain'), '--min-coverage counts the fingerprints within the DCTdomain cut-off: it needs --min-domain'),
+        (_when('--min-coverage', lambda c: not 0 < c <= 1), '--min-coverage is a share of a protein: above 0 and at most 1')),
+    '--cov-unit': ((_without('--min-coverage'), '--cov-unit says what --min-coverage counts: it needs --min-coverage'),),
+    '--domain-map': (      # (True for the bare flag, else its X)
+        (_with('--cluster'), '--domain-map lists the matched domain pairs behind a result line: not with --cluster'),
+        (_when('--domain-map', lambda x: x is not True and not 0 < x <= 1),
+         '--domain-map X is the similarity from which a domain is matched: above 0 and at most 1')),
+    '--linkage': ((_without('--cluster'), '--linkage says how --cluster forms its clusters: it needs --cluster'),),
+    '--level': ((_without('--cluster'), '--level says what --cluster clusters: it needs --cluster'),),
+    '--no-whole': ((lambda ns: not _DOMAIN_LEVEL(ns),
+                    '--no-whole leaves the whole-protein rows out of the domain families: it needs --level domain'),),
+    '--rep': (
+        (_without('--cluster'), '--rep says which member names a cluster: it needs --cluster'),
+        (_DOMAIN_LEVEL, '--rep names clusters of proteins: not with --level domain, whose nodes are fingerprints with no protein tile to sum'),
+        (_and(_when('--rep', 'medoid'), _when('--linkage', 'greedy')),
+         '--rep medoid names single-linkage clusters: not with --linkage greedy, where every member is within the '
+         'cut-offs of its representative -- a medoid would break that guarantee')),
+    '--min-neighbors': (
+        (_without('--cluster'), '--min-neighbors says how many neighbours a protein needs to pass a link of --cluster on: it needs --cluster'),
+        (_when('--min-neighbors', lambda m: m < 1), '--min-neighbors is a number of neighbours: at least 1 (1 is plain single linkage)'),
+        (_when('--linkage', 'greedy'), '--min-neighbors thins the graph of single linkage: not with --linkage greedy, which names its '
+                                       'representatives by a rule of its own'),
+        (_DOMAIN_LEVEL, '--min-neighbors counts the neighbours of a protein: not with --level domain, whose nodes are fingerprints')),
+    '--cluster': (
+        (lambda ns: _explains(ns) and not _DOMAIN_LEVEL(ns), '--domains (--dom, --db-dom) explains the scores of result lines: not with --cluster'),
+        (_with('--pair', '--db'), '--cluster applies to all-against-all only, not to --pair or --db'),
+        (_without('--min-domain', '--min-global'), '--cluster needs a cut-off: --min-domain, --min-global or both'),
+        (_and(_DOMAIN_LEVEL, _without('--min-domain')), '--level domain joins fingerprints by their own L1: it needs --min-domain'),
+        (_and(_DOMAIN_LEVEL, _with('--min-global')), '--level domain has no whole-protein score to cut: not with --min-global'),
+        (_and(_DOMAIN_LEVEL, _when('--linkage', 'greedy')), '--level domain forms single-linkage clusters: not with --linkage greedy')),
+    '--min-domain': _ALL_ONLY,
+    '--min-global': _ALL_ONLY}
+
+
+class _Mode(typing.NamedTuple):
+    """A mode of dct-sim.  ``fn``: the name of its function, a module attribute looked up when it is called.  ``args``: the options
+    that are its positional arguments before the report.  ``kw``: its keyword arguments -- name -> the default where the command line
+    has no such option, or ``_IF_GIVEN`` for an argument that is passed only where it has; a mode that goes by a score gets ``score``.
+    ``header``: the keyword arguments of a call -> the first line of its report.  ``flag``: what selects the mode (None: what is
+    left, the all-against-all).  A mode with ``does`` (what it does, for the message) refuses every flag of ``names`` beside it but
+    its own, those it ``takes`` and the flags of the modes before it in ``_MODES``, which have refused it by then; ``orders``: what
+    its score does -- the other score's cut-off is then an error; ``needs``: rules as those of ``_OPTIONS``, checked between the two.
+    ``adjust``: what the keyword arguments need beyond the table, done to them in place."""
+    fn: str
+    args: tuple
+    kw: dict
+    header: typing.Callable
+    flag: str = None
+    does: str = None
+    orders: str = None
+    takes: tuple = ()
+    needs: tuple = ()
+    names: tuple = None
+    adjust: typing.Callable = None
+
+
+# The order in which a mode names the flags it refuses: the first of them that is given is the one in the message.  --families,
+# --family-sep and --bins are in no mode's "not with": their own "it needs" rule catches them later.
+_NAMES = ('--pair', '--db', '--cluster', '--assign', '--tree', '--rank', '--linkage', '--level', '--no-whole', '--reps-out', '--domains', '--dom',
+          '--db-dom', '--domain-map', '--min-coverage', '--cov-unit', '--rep', '--min-neighbors', '--zscore', '--min-z', '--auc1', '--hist',
+          '--hac', '--method', '--flat', '--newick')
+# --assign alone names the four flags of the domain pair before --linkage, --level and --no-whole (its messages are older than the order)
+_PAIR_FLAGS = ('--domains', '--dom', '--db-dom', '--domain-map')
+_ASSIGN_NAMES = tuple(flag for name in _NAMES if name not in _PAIR_FLAGS for flag in (_PAIR_FLAGS + (name,) if name == '--linkage' else (name,)))
+
+
+def _cluster_kw(kw: dict):
+    """``cluster_sim`` takes ``whole``, the opposite of --no-whole, and ``dom`` only where it names the rows of the domain level or gives
+    --min-coverage its residues."""
+    kw['whole'] = not kw.pop('no_whole')
+    if kw['level'] != 'domain' and 'min_coverage' not in kw:
+        kw['dom'] = None
+
+
+_IF_GIVEN = object()
+_CUTS = {'min_domain': None, 'min_global': None}
+_PAIR_KW = {'domains': False, 'dom': None, 'domain_map': _IF_GIVEN}
+_DB_KW = {**_PAIR_KW, 'db_dom': None, 'zscore': _IF_GIVEN, 'min_z': _IF_GIVEN}
+_FAMILY_KW = {'families': None, 'family_sep': None}
+_COVER_KW = {'min_coverage': _IF_GIVEN, 'cov_unit': _IF_GIVEN}
+# an option that brings another argument with it: --min-z implies --zscore, --min-coverage counts residues unless --cov-unit says otherwise
+_BRINGS = {'min_z': ('zscore', True), 'min_coverage': ('cov_unit', 'residues')}
+
+# The modes, in the order in which the parser checks them and main looks for the one to run: the first that is given.
+_MODES = (
+    _Mode('rbh_sim', ('dct', 'db'), {**_CUTS, **_DB_KW}, lambda kw: _lines_header(kw, rbh=True),
+          '--rbh', 'prints the reciprocal best hits of --dct and --db', 'ranks the hits', takes=('--db',) + _PAIR_FLAGS + ('--zscore', '--min-z'),
+          needs=((_without('--db'), '--rbh compares the proteins of --dct with those of another file: it needs --db'),)),
+    _Mode('tree_sim', ('dct',), _CUTS, lambda kw: HEADER, '--tree', 'prints the single-linkage tree of --dct', 'orders the pairs'),
+    _Mode('assign_sim', ('dct', 'assign'), {**_CUTS, 'reps_out': None}, lambda kw: CLUSTER_HEADER,
+          '--assign', 'places the proteins of --dct on a fixed set of representatives', takes=('--reps-out',), names=_ASSIGN_NAMES,
+          needs=((_without('--min-domain', '--min-global'), '--assign needs a cut-off: --min-domain, --min-global or both'),)),
+    _Mode('auc1_sim', ('dct',), {**_CUTS, **_FAMILY_KW}, lambda kw: AUC1_HEADER,
+          '--auc1', 'measures the AUC1 and the top-1 rates of --dct', 'ranks the hits',
+          needs=((_without('--families', '--family-sep'), '--auc1 needs the family of every protein: --families FILE or --family-sep C'),)
+          + _FAMILIES),
+    _Mode('hist_sim', ('dct',), {**_CUTS, **_FAMILY_KW, 'bins': HIST_BINS},
+          lambda kw: hist_header(kw.get('score', 'domain'), kw.get('families') is not None or kw.get('family_sep') is not None),
+          '--hist', 'bins the scores of all pairs of --dct', 'bins the pairs', needs=_FAMILIES),
+    _Mode('hac_sim', ('dct',), {**_CUTS, 'method': 'average', 'flat': False, 'newick': None},
+          lambda kw: CLUSTER_HEADER if kw.get('flat') else HAC_HEADER,
+          '--hac', 'prints the average- or complete-linkage tree of --dct', 'orders the pairs', takes=('--method', '--flat', '--newick')),
+    # (no "not with" of their own: the rules of the options refuse what does not go with them)
+    _Mode('pair_sim', ('dct', 'pair', 'pairfound'), _PAIR_KW, _lines_header, '--pair'),
+    _Mode('db_search', ('dct', 'db', 'top', 'threshold'), {'rank': 'global', **_DB_KW}, _lines_header, '--db'),
+    _Mode('cluster_sim', ('dct',), {**_CUTS, 'linkage': 'single', 'level': 'protein', 'no_whole': False, 'dom': None, 'reps_out': _IF_GIVEN,
+                                    **_COVER_KW, 'rep': _IF_GIVEN, 'min_neighbors': _IF_GIVEN},
+          lambda kw: _header(CLUSTER_HEADER, kw.get('level')), '--cluster', adjust=_cluster_kw),
+    _Mode('all_sim', ('dct',), {**_CUTS, **_PAIR_KW, **_COVER_KW}, _lines_header))
+# mode flag -> the flags it refuses, in the order they are named
+_REFUSED = {mode.flag: tuple(flag for flag in mode.names or _NAMES if flag != mode.flag and flag not in mode.takes
+                             and flag not in [earlier.flag for earlier in _MODES[:at]])
+            for at, mode in enumerate(_MODES) if mode.does}
+
+
+def _call_of(mode: _Mode, ns) -> tuple:
+    """(the positional arguments before the report, the keyword arguments) with which ``main`` calls the function of ``mode``."""
+    kw = {}
+    for name, default in mode.kw.items():
+        value = getattr(ns, name, None)
+        if value is not None or default is not _IF_GIVEN:
+            kw[name] = default if value is None else value
+    for name, (brought, default) in _BRINGS.items():
+        if name in kw:
+            kw.setdefault(brought, default)
+    if mode.orders:
+        kw['score'] = _value(ns, mode.flag)
+    if mode.adjust:
+        mode.adjust(kw)
+    return tuple(getattr(ns, name) for name in mode.args), kw
 
 
 class _Parser(argparse.ArgumentParser):
-    """``--rank`` orders database hits: it is an error without ``--db`` or beside ``--pair`` (which takes precedence).
-    ``--min-domain`` / ``--min-global`` cut the all-against-all output: an error beside ``--pair`` or ``--db``.
-    ``--cluster`` joins the pairs that pass into clusters: an error beside ``--pair`` or ``--db``, or without a cut-off.
-    ``--dom`` / ``--db-dom`` imply ``--domains``; ``--db-dom`` is an error without ``--db``, ``--domains`` beside ``--cluster``
-    (a cluster line has no scores to explain).  ``--linkage`` says how ``--cluster`` forms its clusters: an error without it.
-    ``--level`` says what ``--cluster`` clusters: an error without it; ``--level domain`` takes ``--min-domain`` alone and single
-    linkage (an error without the one, beside ``--min-global`` or ``--linkage greedy``) and lets ``--dom`` name the rows;
-    ``--no-whole`` is an error without ``--level domain``.  ``--assign`` places the proteins of ``--dct`` on the representatives of
-    another file and needs a cut-off; ``--tree`` prints the single-linkage tree of the file and ``--rbh`` the reciprocal best hits
-    of ``--dct`` and ``--db`` (an error without ``--db``), each by one score: an error beside the cut-off of the other score, while
-    its own score's cut-off is allowed (with ``--rbh`` the one case in which a cut-off goes with ``--db``).  What each of the three
-    refuses beside it is ``_MODES``.  ``--reps-out`` is an error unless ``--assign`` is given, or ``--cluster --linkage greedy``
-    without ``--level domain``.  ``--min-coverage`` adds a coverage cut-off to ``--min-domain`` in the all-against-all and in
-    ``--cluster`` at protein level: an error without ``--min-domain``, outside (0, 1], beside ``--pair``, ``--db`` or ``--level
-    domain`` (and beside the three modes: ``_MODES``); ``--cov-unit`` says what it counts: an error without it.  Beside ``--cluster``
-    with ``--min-coverage``, ``--dom`` gives the residues and does not imply ``--domains``.  ``--rep`` says which member names a
-    cluster of ``--cluster``: an error without it, beside ``--level domain`` (its nodes are fingerprints: no protein tile to sum) and,
-    as ``--rep medoid``, beside ``--linkage greedy`` (whose representative every member is within the cut-offs of); ``--rep first`` is
-    the default and leaves the namespace of a command line without it.  ``--cluster --rep medoid`` at protein level is the third
-    case in which ``--reps-out`` is allowed: it writes the medoids.  ``--min-neighbors M`` makes ``--cluster`` form density clusters
-    from the single-linkage graph at protein level: an error without ``--cluster``, with M < 1, beside ``--linkage greedy`` or
-    ``--level domain`` (and beside the three modes: ``_MODES``); it leaves the conditions of ``--reps-out`` as they are.
-    ``--auc1`` measures how well one score ranks the proteins of a labelled file, the fourth mode of ``_MODES``: it refuses what
-    ``--tree`` refuses and the other three refuse it; its own score's cut-off is allowed and the other score's an error, as for
-    ``--tree``.  It needs the family of every protein from exactly one of ``--families FILE`` and ``--family-sep C`` (``_FAMILY_FLAGS``):
-    an error with neither, with both or with an empty ``C``, and either of the two is an error without ``--auc1``.
-    ``--hist`` bins one score over all pairs of the file, the fifth mode of ``_MODES``: it refuses what ``--tree`` refuses and
-    ``--auc1``, and the other four refuse it; its own score's cut-off is allowed and the other score's an error.  The family flags
-    are optional with it -- at most one of the two, and ``C`` not empty -- and say which pairs are of one family.  ``--bins B`` is the
-    number of cut-offs of its table: 1 .. 1000, an error without ``--hist``.
-    ``--zscore`` adds the z-score of every hit of ``--db``, with or without ``--rbh``, and ``--min-z Z`` (which implies it) keeps the
-    selected lines whose z is not below Z: either is an error without ``--db``, beside ``--pair`` or ``--cluster``, and beside
-    ``--tree``, ``--assign``, ``--auc1`` and ``--hist`` (``_MODES``); both are absent from the namespace of a command line without
-    them.
-    ``--domain-map [X]`` adds the map of all matched domain pairs to every result line and implies ``--domains``, in every mode that
-    prints pair lines (``--pair``, ``--db`` with or without ``--rbh``, the all-against-all): an error beside ``--cluster`` and beside
-    ``--tree``, ``--assign``, ``--auc1`` and ``--hist`` (``_MODES``), or with X outside (0, 1]; it is absent from the namespace of a
-    command line without it, True there for the bare flag.
-    ``--hac`` prints the average- or complete-linkage tree of the file, a sixth mode (``_HAC_MODE``, checked after the five): it refuses what ``--tree`` refuses
-    and ``--tree`` itself, and the other five refuse it and the three options that go with it; its own score's cut-off is allowed and
-    the other score's an error.  ``--method`` (average, the default, or complete), ``--flat`` (the clusters at the cut-off: an error
-    without that cut-off) and ``--newick FILE`` are errors without ``--hac``; all four are absent from the namespace of a command line
-    without them.  ``--linkage`` is not extended: it names the rules of ``--cluster``."""
+    """argparse's parser with the rules of dct-sim's command line, which are data: ``_MODES`` and ``_OPTIONS``.  After argparse's own
+    checks, in this order:
+
+    1. every mode of ``_MODES`` that is given and has a refusal list (``_REFUSED``, derived from what it takes), in the order of
+       the table: the first refused flag that is given, in the mode's naming order; then the mode's own requirements; then, for a
+       mode that goes by one score, the cut-off of the other score;
+    2. every option of ``_OPTIONS`` that is given, in the order of the table: its rules, in their order;
+    3. what the namespace of an accepted command line says beyond its own words: ``domains`` is True where the lines carry the
+       domain pair (``_explains``), and ``--rep first``, the default, leaves the namespace of a command line without it.
+
+    The first rule that fails ends the parse with its message.  What an option is for is in its help text (``build_parser``), why a
+    rule holds in its message."""
+
+    def _check(self, ns, flag, rules):
+        for fails, message in rules:
+            if fails(ns):
+                self.error(message.format(flag, **vars(ns)))
 
     def parse_known_args(self, args=None, namespace=None):
         ns, rest = super().parse_known_args(args, namespace)
-        cut = ns.min_domain is not None or ns.min_global is not None
-        for mode, (does, orders, refused) in {**_MODES, **_HAC_MODE}.items():
-            score = getattr(ns, _dest(mode), None)
-            if score is None:
+        for mode in _MODES:
+            if not mode.does or not _given(ns, mode.flag):
                 continue
-            if mode in _MODES:
-                refused = refused + _HAC_FLAGS
-            beside = [flag for flag in refused if _GIVEN[flag](getattr(ns, _dest(flag), None))]
+            beside = [flag for flag in _REFUSED[mode.flag] if _given(ns, flag)]
             if beside:
-                self.error(f'{mode} {does}: not with {beside[0]}')
-            if mode == '--rbh' and not ns.db:
-                self.error('--rbh compares the proteins of --dct with those of another file: it needs --db')
-            if mode == '--assign' and not cut:
-                self.error('--assign needs a cut-off: --min-domain, --min-global or both')
-            if mode == '--auc1':
-                named = [flag for flag in _FAMILY_FLAGS if _GIVEN[flag](getattr(ns, _dest(flag), None))]
-                if not named:
-                    self.error('--auc1 needs the family of every protein: --families FILE or --family-sep C')
-                if len(named) > 1:
-                    self.error('--auc1 takes the families from one place: --families or --family-sep, not both')
-                if getattr(ns, 'family_sep', None) == '':
-                    self.error('--family-sep is the text between id and family: at least one character')
-            if mode == '--hist':
-                if all(_GIVEN[flag](getattr(ns, _dest(flag), None)) for flag in _FAMILY_FLAGS):
-                    self.error('--hist takes the families from one place: --families or --family-sep, not both')
-                if getattr(ns, 'family_sep', None) == '':
-                    self.error('--family-sep is the text between id and family: at least one character')
+                self.error(f'{mode.flag} {mode.does}: not with {beside[0]}')
+            self._check(ns, mode.flag, mode.needs)
+            score = _value(ns, mode.flag)
             other = {'domain': 'global', 'global': 'domain'}.get(score)
-            if orders and getattr(ns, f'min_{other}') is not None:
-                self.error(f'{mode} {score} {orders} by DCT{score}: its cut-off is --min-{score}, not --min-{other}')
-        hac = getattr(ns, 'hac', None)
-        for flag, does in (('--method', 'says which linkage the tree of --hac is built by'), ('--flat', 'prints the clusters of --hac at its cut-off'),
-                           ('--newick', 'writes the tree of --hac in Newick format')):
-            if hac is None and _GIVEN[flag](getattr(ns, _dest(flag), None)):
-                self.error(f'{flag} {does}: it needs --hac')
-        if hac is not None and getattr(ns, 'flat', False) and getattr(ns, f'min_{hac}') is None:
-            self.error(f'--flat prints the clusters at a cut-off: with --hac {hac} it needs --min-{hac}')
-        bins = getattr(ns, 'bins', None)
-        if bins is not None:
-            if getattr(ns, 'hist', None) is None:
-                self.error('--bins says how many cut-offs the table of --hist has: it needs --hist')
-            if not 1 <= bins <= HIST_MAX_BINS:
-                self.error(f'--bins is a number of cut-offs: 1 .. {HIST_MAX_BINS}')
-        if getattr(ns, 'auc1', None) is None and getattr(ns, 'hist', None) is None:
-            for flag in _FAMILY_FLAGS:
-                if _GIVEN[flag](getattr(ns, _dest(flag), None)):
-                    self.error(f'{flag} says which family a protein belongs to, for --auc1 to judge the hits by: it needs --auc1')
-        for flag, does in (('--zscore', 'places every hit of a database search in the background of its query'),
-                           ('--min-z', 'cuts the hits of a database search by their z-score')):
-            if _GIVEN[flag](getattr(ns, _dest(flag), None)):
-                if ns.pair:
-                    self.error(f'{flag} {does}: not with --pair')
-                if getattr(ns, 'cluster', False):
-                    self.error(f'{flag} {does}: not with --cluster')
-                if not ns.db:
-                    self.error(f'{flag} {does}: it needs --db')
-        rbh = getattr(ns, 'rbh', None)
-        names = getattr(ns, 'rep', None)
-        if getattr(ns, 'assign', None) is None and getattr(ns, 'reps_out', None) is not None and not (
-                getattr(ns, 'cluster', False) and (getattr(ns, 'linkage', None) == 'greedy' or names == 'medoid')
-                and getattr(ns, 'level', None) != 'domain'):
-            self.error('--reps-out writes representatives: it needs --assign, or --cluster --linkage greedy at protein level')
-        if getattr(ns, 'rank', None) is not None and (ns.pair or not ns.db):
-            self.error('--rank applies to database search (--db) only, not to --pair or all-against-all')
-        if getattr(ns, 'db_dom', None) is not None and not ns.db:
-            self.error('--db-dom names the .dom file of --db: it needs --db')
-        level = getattr(ns, 'level', None)
-        coverage = getattr(ns, 'min_coverage', None)
-        if coverage is not None:
-            if ns.pair or ns.db:
-                self.error('--min-coverage applies to all-against-all only, not to --pair or --db')
-            if level == 'domain':
-                self.error('--min-coverage is a share of a protein: not with --level domain, which joins single fingerprints')
-            if ns.min_domain is None:
-                self.error('--min-coverage counts the fingerprints within the DCTdomain cut-off: it needs --min-domain')
-            if not 0 < coverage <= 1:
-                self.error('--min-coverage is a share of a protein: above 0 and at most 1')
-        elif getattr(ns, 'cov_unit', None) is not None:
-            self.error('--cov-unit says what --min-coverage counts: it needs --min-coverage')
-        mapped = getattr(ns, 'domain_map', None)                # (True for the bare flag, else its X)
-        if mapped is not None:
-            if getattr(ns, 'cluster', False):
-                self.error('--domain-map lists the matched domain pairs behind a result line: not with --cluster')
-            if mapped is not True and not 0 < mapped <= 1:
-                self.error('--domain-map X is the similarity from which a domain is matched: above 0 and at most 1')
+            if mode.orders and _given(ns, f'--min-{other}'):
+                self.error(f'{mode.flag} {score} {mode.orders} by DCT{score}: its cut-off is --min-{score}, not --min-{other}')
+        for flag, rules in _OPTIONS.items():
+            if _given(ns, flag):
+                self._check(ns, flag, rules)
+        if _explains(ns):
             ns.domains = True
-        weighs = coverage is not None and getattr(ns, 'cluster', False)     # (--dom gives --min-coverage its residues: no result lines to explain)
-        if (getattr(ns, 'dom', None) is not None and not weighs) or getattr(ns, 'db_dom', None) is not None:
-            ns.domains = True
-        if getattr(ns, 'linkage', None) is not None and not getattr(ns, 'cluster', False):
-            self.error('--linkage says how --cluster forms its clusters: it needs --cluster')
-        if level is not None and not getattr(ns, 'cluster', False):
-            self.error('--level says what --cluster clusters: it needs --cluster')
-        if getattr(ns, 'no_whole', False) and level != 'domain':
-            self.error('--no-whole leaves the whole-protein rows out of the domain families: it needs --level domain')
-        if names is not None:
-            if not getattr(ns, 'cluster', False):
-                self.error('--rep says which member names a cluster: it needs --cluster')
-            if level == 'domain':
-                self.error('--rep names clusters of proteins: not with --level domain, whose nodes are fingerprints with no protein tile to sum')
-            if names == 'medoid' and getattr(ns, 'linkage', None) == 'greedy':
-                self.error('--rep medoid names single-linkage clusters: not with --linkage greedy, where every member is within the '
-                           'cut-offs of its representative -- a medoid would break that guarantee')
-            if names == 'first':
-                del ns.rep                                          # (the default: the namespace of a command line without it)
-        neighbors = getattr(ns, 'min_neighbors', None)
-        if neighbors is not None:
-            if not getattr(ns, 'cluster', False):
-                self.error('--min-neighbors says how many neighbours a protein needs to pass a link of --cluster on: it needs --cluster')
-            if neighbors < 1:
-                self.error('--min-neighbors is a number of neighbours: at least 1 (1 is plain single linkage)')
-            if getattr(ns, 'linkage', None) == 'greedy':
-                self.error('--min-neighbors thins the graph of single linkage: not with --linkage greedy, which names its '
-                           'representatives by a rule of its own')
-            if level == 'domain':
-                self.error('--min-neighbors counts the neighbours of a protein: not with --level domain, whose nodes are fingerprints')
-        if getattr(ns, 'cluster', False):
-            if getattr(ns, 'domains', False) and level != 'domain':
-                self.error('--domains (--dom, --db-dom) explains the scores of result lines: not with --cluster')
-            if ns.pair or ns.db:
-                self.error('--cluster applies to all-against-all only, not to --pair or --db')
-            if ns.min_domain is None and ns.min_global is None:
-                self.error('--cluster needs a cut-off: --min-domain, --min-global or both')
-            if level == 'domain':
-                if ns.min_domain is None:
-                    self.error('--level domain joins fingerprints by their own L1: it needs --min-domain')
-                if ns.min_global is not None:
-                    self.error('--level domain has no whole-protein score to cut: not with --min-global')
-                if getattr(ns, 'linkage', None) == 'greedy':
-                    self.error('--level domain forms single-linkage clusters: not with --linkage greedy')
-        for opt in ('min_domain', 'min_global'):
-            if getattr(ns, opt, None) is not None and (ns.pair or ns.db) and rbh is None:     # (--rbh takes its own score's cut-off)
-                self.error(f'--{opt.replace("_", "-")} applies to all-against-all only, not to --pair or --db')
+        if _value(ns, '--rep') == 'first':
+            del ns.rep
         return ns, rest
 
 
@@ -3434,51 +3479,11 @@ def build_parser() -> argparse.ArgumentParser:
 def main(argv=None):
     t_start = time.time()
     args = build_parser().parse_args(argv)
-    domains, dom, db_dom = (getattr(args, k, None) for k in ('domains', 'dom', 'db_dom'))
-    level = getattr(args, 'level', 'protein')
-    assign, reps_out = getattr(args, 'assign', None), getattr(args, 'reps_out', None)
-    min_coverage = getattr(args, 'min_coverage', None)
-    cover = {'min_coverage': min_coverage, 'cov_unit': getattr(args, 'cov_unit', 'residues')} if min_coverage is not None else {}
-    auc1, hist = getattr(args, 'auc1', None), getattr(args, 'hist', None)
-    hac, flat = getattr(args, 'hac', None), getattr(args, 'flat', False)
-    family = {'families': getattr(args, 'families', None), 'family_sep': getattr(args, 'family_sep', None)}
-    min_z = getattr(args, 'min_z', None)
-    zscore = getattr(args, 'zscore', False) or min_z is not None
-    z = {'zscore': True, **({'min_z': min_z} if min_z is not None else {})} if zscore else {}
-    mapped = getattr(args, 'domain_map', None)
-    maps = {'domain_map': mapped} if mapped is not None else {}  # (the functions take the option only where the command line has it)
-    report = Report(args.output, _header(hist_header(hist, any(v is not None for v in family.values())) if hist is not None else
-                                         AUC1_HEADER if auc1 is not None else HAC_HEADER if hac is not None and not flat else
-                                         CLUSTER_HEADER if args.cluster or assign is not None or hac is not None else HEADER,
-                                         level, domains, mapped) + _z_header(zscore, getattr(args, 'rbh', None) is not None, args.rank))
+    mode = next(mode for mode in _MODES if mode.flag is None or _given(args, mode.flag))
+    head, kw = _call_of(mode, args)
+    report = Report(args.output, mode.header(kw))
     t_work = time.time()
-    if hist is not None:
-        hist_sim(args.dct, report, score=hist, bins=getattr(args, 'bins', HIST_BINS), min_domain=args.min_domain, min_global=args.min_global,
-                 **family)
-    elif auc1 is not None:
-        auc1_sim(args.dct, report, score=auc1, min_domain=args.min_domain, min_global=args.min_global, **family)
-    elif hac is not None:
-        hac_sim(args.dct, report, score=hac, method=getattr(args, 'method', 'average'), min_domain=args.min_domain, min_global=args.min_global,
-                flat=flat, newick=getattr(args, 'newick', None))
-    elif getattr(args, 'tree', None) is not None:
-        tree_sim(args.dct, report, score=args.tree, min_domain=args.min_domain, min_global=args.min_global)
-    elif getattr(args, 'rbh', None) is not None:
-        rbh_sim(args.dct, args.db, report, score=args.rbh, min_domain=args.min_domain, min_global=args.min_global, domains=bool(domains),
-                dom=dom, db_dom=db_dom, **z, **maps)
-    elif assign is not None:
-        assign_sim(args.dct, assign, report, min_domain=args.min_domain, min_global=args.min_global, reps_out=reps_out)
-    elif args.pair:
-        pair_sim(args.dct, args.pair, args.pairfound, report, domains=bool(domains), dom=dom, **maps)
-    elif args.db:
-        db_search(args.dct, args.db, args.top, args.threshold, report, rank=args.rank or 'global', domains=bool(domains), dom=dom, db_dom=db_dom, **z, **maps)
-    elif args.cluster:
-        cluster_sim(args.dct, report, min_domain=args.min_domain, min_global=args.min_global, linkage=getattr(args, 'linkage', 'single'),
-                    level=level, whole=not getattr(args, 'no_whole', False), dom=dom if level == 'domain' or cover else None,
-                    **({'reps_out': reps_out} if reps_out is not None else {}), **cover,
-                    **({'rep': args.rep} if getattr(args, 'rep', None) is not None else {}),
-                    **({'min_neighbors': args.min_neighbors} if getattr(args, 'min_neighbors', None) is not None else {}))
-    else:
-        all_sim(args.dct, report, min_domain=args.min_domain, min_global=args.min_global, domains=bool(domains), dom=dom, **cover, **maps)
+    globals()[mode.fn](*head, report, **kw)
     report.close()
     t_end = time.time()
     print(f'total time used {t_end - t_start:.1f}s')

@@ -2,7 +2,9 @@
 hand-made cases, the host composer ``dct_sim.map_field`` against literal strings, the command line, and the two entry points in the
 header and the libraries."""
 
+import contextlib
 import ctypes
+import io
 import os
 import re
 
@@ -208,20 +210,63 @@ def test_parser_rejects(argv, message, capsys):
     assert message in capsys.readouterr().err
 
 
+DOES = {'--rbh': '--rbh prints the reciprocal best hits of --dct and --db', '--tree': '--tree prints the single-linkage tree of --dct',
+        '--assign': '--assign places the proteins of --dct on a fixed set of representatives',
+        '--auc1': '--auc1 measures the AUC1 and the top-1 rates of --dct', '--hist': '--hist bins the scores of all pairs of --dct'}
+MODE_ARGV = {'--rbh': ['--db', 'y.npz', '--rbh'], '--tree': ['--tree'], '--assign': ['--assign', 'r.npz', '--min-domain', '0.5'],
+             '--auc1': ['--auc1', '--family-sep', '|'], '--hist': ['--hist']}
+FLAG_ARGV = {'--pair': ['--pair', 'p'], '--db': ['--db', 'y'], '--cluster': ['--cluster'], '--assign': ['--assign', 'r'], '--tree': ['--tree'],
+             '--rank': ['--rank', 'domain'], '--linkage': ['--linkage', 'single'], '--level': ['--level', 'protein'], '--no-whole': ['--no-whole'],
+             '--reps-out': ['--reps-out', 'o'], '--domains': ['--domains'], '--dom': ['--dom', 'f'], '--db-dom': ['--db-dom', 'f'],
+             '--domain-map': ['--domain-map'], '--min-coverage': ['--min-coverage', '0.5'], '--cov-unit': ['--cov-unit', 'domains'],
+             '--rep': ['--rep', 'first'], '--min-neighbors': ['--min-neighbors', '3'], '--zscore': ['--zscore'], '--min-z': ['--min-z', '2'],
+             '--auc1': ['--auc1'], '--hist': ['--hist']}
+TREE_REFUSES = ('--pair', '--db', '--cluster', '--assign', '--rank', '--linkage', '--level', '--no-whole', '--reps-out', '--domains', '--dom',
+                '--db-dom', '--domain-map', '--min-coverage', '--cov-unit', '--rep', '--min-neighbors', '--zscore', '--min-z', '--auc1', '--hist')
+# what each of the four modes checked before --hist refuses beside --hist (a mode checked earlier names the pair itself: --tree beside
+# --assign, --assign beside --auc1)
+REFUSES_BESIDE_HIST = {
+    '--rbh': ('--pair', '--cluster', '--assign', '--tree', '--rank', '--linkage', '--level', '--no-whole', '--reps-out', '--min-coverage',
+              '--cov-unit', '--rep', '--min-neighbors', '--auc1'),
+    '--tree': TREE_REFUSES[:-1],
+    '--assign': tuple(f for f in TREE_REFUSES[:-1] if f not in ('--assign', '--reps-out')),
+    '--auc1': tuple(f for f in TREE_REFUSES[:-1] if f not in ('--assign', '--auc1'))}
+
+
+def _refusal(argv):
+    from dctdomain_amd import dct_sim
+    err = io.StringIO()
+    with pytest.raises(SystemExit) as e, contextlib.redirect_stderr(err):
+        dct_sim.build_parser().parse_args(['--dct', 'x.npz'] + argv)
+    assert e.value.code == 2
+    return err.getvalue().rstrip('\n').rsplit(': error: ', 1)[1]
+
+
 def test_the_option_is_no_mode_and_stands_behind_db_dom():
     from dctdomain_amd import dct_sim
-    assert len(dct_sim._MODES) == 5 and '--domain-map' not in dct_sim._MODES and list(dct_sim._MODES)[-1] == '--hist'
-    assert dct_sim._GIVEN['--domain-map'](True) and dct_sim._GIVEN['--domain-map'](0.5) and not dct_sim._GIVEN['--domain-map'](None)
-    for mode in ('--tree', '--assign', '--auc1', '--hist'):
-        refused = dct_sim._MODES[mode][2]
-        assert refused[refused.index('--db-dom') + 1] == '--domain-map' and refused.count('--domain-map') == 1
-        at = refused.index('--min-neighbors')
-        assert refused[at:at + 3] == ('--min-neighbors', '--zscore', '--min-z')
-    assert '--domain-map' not in dct_sim._MODES['--rbh'][2]     # (--rbh prints pair lines: it takes the option)
+    parse = dct_sim.build_parser().parse_args
+    # no mode: alone it is the all-against-all with one more column; and the five modes are checked with --hist last
+    assert vars(parse(['--dct', 'x.npz', '--domain-map'])) == dict(vars(parse(['--dct', 'x.npz'])), domain_map=True, domains=True)
     for mode in ('--rbh', '--tree', '--assign', '--auc1'):
-        assert dct_sim._MODES[mode][2][-1] == '--hist'
-    assert set(dct_sim._MODES['--hist'][2]) == set(dct_sim._MODES['--tree'][2]) - {'--hist'}
-    assert '--domain-map [X]' in dct_sim._Parser.__doc__
+        assert _refusal(MODE_ARGV[mode] + ['--hist']) == f'{DOES[mode]}: not with --hist'
+    for mode in ('--tree', '--assign', '--auc1', '--hist'):
+        # given as the bare flag and with X, not without it
+        assert _refusal(MODE_ARGV[mode] + ['--domain-map']) == _refusal(MODE_ARGV[mode] + ['--domain-map', '0.5']) == f'{DOES[mode]}: not with --domain-map'
+        assert 'domain_map' not in vars(parse(['--dct', 'x.npz'] + MODE_ARGV[mode]))
+        # named behind --db-dom; --min-neighbors, --zscore and --min-z in that order
+        for first, second in (('--db-dom', '--domain-map'), ('--min-neighbors', '--zscore'), ('--zscore', '--min-z')):
+            assert _refusal(MODE_ARGV[mode] + FLAG_ARGV[second] + FLAG_ARGV[first]) == f'{DOES[mode]}: not with {first}'
+    assert parse(['--dct', 'x.npz'] + MODE_ARGV['--rbh'] + ['--domain-map']).domain_map is True     # (--rbh prints pair lines: it takes the option)
+    # --hist is the last flag the four name: beside any other flag they refuse, that one is named
+    for mode, others in REFUSES_BESIDE_HIST.items():
+        for flag in others:
+            assert _refusal(MODE_ARGV[mode] + ['--hist'] + FLAG_ARGV[flag]) == f'{DOES[mode]}: not with {flag}'
+    # --hist refuses what --tree refuses, minus itself (beside --assign and --auc1 those two, checked before it, say so)
+    for flag in TREE_REFUSES[:-1]:
+        assert _refusal(['--tree'] + FLAG_ARGV[flag]) == f'{DOES["--tree"]}: not with {flag}'
+        got = _refusal(['--hist'] + FLAG_ARGV[flag] + (['--family-sep', '|'] if flag == '--auc1' else []))
+        assert got == (f'{DOES[flag]}: not with --hist' if flag in ('--assign', '--auc1') else f'{DOES["--hist"]}: not with {flag}')
+    assert '--domain-map [X]' in dct_sim.build_parser().format_help()
 
 
 def test_header_text(tmp_path):
@@ -230,24 +275,26 @@ def test_header_text(tmp_path):
     assert dct_sim._header(dct_sim.HEADER, None, True, 0.5) == dct_sim.DOMAIN_HEADER + ' domain-map'
     assert dct_sim._header(dct_sim.HEADER, None, True) == dct_sim.DOMAIN_HEADER and dct_sim._header(dct_sim.HEADER) == dct_sim.HEADER
     assert dct_sim._header(dct_sim.CLUSTER_HEADER, None, False, None) == dct_sim.CLUSTER_HEADER
-    # a report a mode function opens itself: the z columns stay last
+    # a report a mode function opens itself (the header is that of the mode of its name): the z columns stay last
     seen = []
 
-    @dct_sim._reporting
-    def mode(report, **kw):
+    def all_sim(report, **kw):
         seen.append(kw)
 
-    @dct_sim._reporting(rbh=True)
-    def rbh(report, **kw):
+    def db_search(report, **kw):
         seen.append(kw)
 
-    for run, kw, want in ((mode, {'domain_map': True}, ' dom1 dom2 domain-map'), (mode, {'domain_map': 0.5, 'zscore': True, 'rank': 'domain'},
-                                                                                   ' dom1 dom2 domain-map z-domain'),
-                          (rbh, {'domain_map': True, 'min_z': 1.0}, ' dom1 dom2 domain-map z-query z-db'), (mode, {'domains': True}, ' dom1 dom2'),
-                          (mode, {}, '')):
+    def rbh_sim(report, **kw):
+        seen.append(kw)
+
+    for fn, kw, want in ((all_sim, {'domain_map': True}, ' dom1 dom2 domain-map'), (db_search, {'domain_map': 0.5, 'zscore': True, 'rank': 'domain'},
+                                                                                     ' dom1 dom2 domain-map z-domain'),
+                         (rbh_sim, {'domain_map': True, 'min_z': 1.0}, ' dom1 dom2 domain-map z-query z-db'), (all_sim, {'domains': True}, ' dom1 dom2'),
+                         (all_sim, {}, '')):
         path = tmp_path / 'out.txt'
-        run(str(path), **kw)
+        dct_sim._reporting(fn)(str(path), **kw)
         assert path.read_text() == dct_sim.HEADER + want + '\n' and seen[-1] == kw
+        assert dct_sim.mode_header(fn.__name__, kw) == dct_sim.HEADER + want
 
 
 # ---- the entry points

@@ -243,17 +243,24 @@ def test_the_parser_refuses(argv, message):
     ('--domains', ['--domains']), ('--dom', ['--dom', 'f']), ('--db-dom', ['--db-dom', 'f']), ('--min-coverage', ['--min-coverage', '0.5']),
     ('--cov-unit', ['--cov-unit', 'domains']), ('--rep', ['--rep', 'first']), ('--min-neighbors', ['--min-neighbors', '3'])])
 def test_it_refuses_what_the_tree_refuses(flag, argv):
-    from dctdomain_amd import dct_sim
-    assert set(dct_sim._MODES['--hist'][2]) == set(dct_sim._MODES['--tree'][2]) - {'--hist'} and '--auc1' in dct_sim._MODES['--hist'][2]
-    assert list(dct_sim._MODES)[-1] == '--hist' and len(dct_sim._MODES) == 5
+    assert _parse(['--tree'] + argv) == '--tree prints the single-linkage tree of --dct: not with ' + flag
+    assert _parse(['--hist', '--auc1'] + SEP) == '--auc1 measures the AUC1 and the top-1 rates of --dct: not with --hist'
+    # (a mode, checked after the other four; --bins and the family flags are its options, no modes of their own)
+    for mode, line in (('--tree', ['--tree']), ('--rbh', ['--db', 'y', '--rbh']), ('--assign', ['--assign', 'r', '--min-domain', '0.5']),
+                       ('--auc1', ['--auc1'] + SEP)):
+        assert _parse(line + ['--hist']).startswith(mode + ' ')
+    assert _parse(['--hist', '--bins', '10'] + SEP)['hist'] == 'domain'
     assert _parse(['--hist'] + argv) == DOES + flag
 
 
 @pytest.mark.parametrize('argv, mode', [(['--tree'], '--tree'), (['--db', 'y', '--rbh'], '--rbh'), (['--assign', 'r', '--min-domain', '0.5'], '--assign'),
                                         (['--auc1'] + SEP, '--auc1')])
 def test_the_four_modes_refuse_it(argv, mode):
-    from dctdomain_amd import dct_sim
-    assert dct_sim._MODES[mode][2][-1] == '--hist'
+    # --hist is the last flag they name: beside any other flag the mode refuses, that one is named
+    for flag, more in (('--pair', ['--pair', 'p']), ('--cluster', ['--cluster']), ('--rank', ['--rank', 'domain']), ('--linkage', ['--linkage', 'single']),
+                       ('--level', ['--level', 'protein']), ('--no-whole', ['--no-whole']), ('--min-coverage', ['--min-coverage', '0.5']),
+                       ('--cov-unit', ['--cov-unit', 'domains']), ('--rep', ['--rep', 'first']), ('--min-neighbors', ['--min-neighbors', '3'])):
+        assert _parse(argv + ['--hist'] + more) == _parse(argv + more) and _parse(argv + more).endswith(': not with ' + flag)
     got = _parse(argv + ['--hist'])
     assert isinstance(got, str) and got.startswith(mode + ' ') and got.endswith(': not with --hist'), got
 

@@ -173,12 +173,15 @@ def test_the_help_says_what_z_is_relative_to():
     from dctdomain_amd import dct_sim
     text = re.sub(r'\s+', ' ', dct_sim.build_parser().format_help())
     assert 'z is relative to the database searched' in text and 'counts in its own background like any other protein' in text
-    assert 'zscore' in dct_sim._Parser.__doc__ and '--min-z' in dct_sim._Parser.__doc__
-    assert dct_sim._GIVEN['--zscore'] is bool and dct_sim._GIVEN['--min-z'](0.0)
-    for mode in ('--tree', '--assign', '--auc1', '--hist'):
-        refused = dct_sim._MODES[mode][2]
-        assert refused.index('--min-neighbors') + 2 == refused.index('--zscore') + 1 == refused.index('--min-z')
-    assert '--zscore' not in dct_sim._MODES['--rbh'][2]
+    assert '--zscore' in text and '--min-z Z' in text
+    # --zscore is given when it is there, --min-z whatever its Z (0 too)
+    assert _parse(['--tree', '--zscore']).endswith(': not with --zscore') and _parse(['--tree', '--min-z', '0']).endswith(': not with --min-z')
+    # the four modes name --min-neighbors, --zscore and --min-z in that order
+    for mode in (['--tree'], ['--assign', 'r', '--min-domain', '0.5'], ['--auc1', '--family-sep', '|'], ['--hist']):
+        assert _parse(mode + ['--min-z', '2', '--zscore', '--min-neighbors', '3']).endswith(': not with --min-neighbors')
+        assert _parse(mode + ['--min-z', '2', '--zscore']).endswith(': not with --zscore')
+        assert _parse(mode + ['--min-z', '2']).endswith(': not with --min-z')
+    assert _parse(['--db', 'y', '--rbh', '--zscore'])['zscore'] is True
     assert dct_sim._z_header(False) == '' and dct_sim._z_header(True) == ' z-global' and dct_sim._z_header(True, rank='domain') == ' z-domain'
     assert dct_sim._z_header(True, True, 'domain') == ' z-query z-db'
 
