@@ -1,10 +1,11 @@
-"""ctypes binding of libdctfp.so (include/dctfp.h).  No fallback: if the HIP library is
-missing or no MI355X is visible, everything here raises."""
+"""ctypes binding of libdctfp.so; its signatures and constants are read from include/dctfp.h and include/dctfp_linkage.h.
+No fallback: if the HIP library is missing or no MI355X is visible, everything here raises."""
 
 from __future__ import annotations
 
 import ctypes as C
 import os
+import re
 import threading
 
 import numpy as np
@@ -14,20 +15,6 @@ RECCUT_LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'libr
 #: the same library with the engineering knobs and test hooks of dctfp_set_option compiled in (-DDCTFP_EXPERIMENTS): what
 #: tools/ and the kernel-variant / cache tests load; the product (`LIB_PATH`) knows only the options of include/dctfp.h
 EXPERIMENTS_LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'libdctfp_experiments.so')
-
-DCTFP_OK = 0
-DCTFP_ERR_INVALID = -1
-DCTFP_ERR_SHAPE = -2
-DCTFP_ERR_HIP = -3
-DCTFP_ERR_NOMEM = -4
-DCTFP_ERR_LIMIT = -5
-DCTFP_ERR_UNSUPPORTED = -6
-DCTFP_MAX_N = 8
-DCTFP_MAX_M = 128
-DCTFP_F32 = 0
-DCTFP_F64 = 1
-DCTFP_F16 = 2
-DCTFP_BF16 = 3
 
 #: numpy image of ``dctfp_piece`` (include/dctfp.h)
 PIECE_DTYPE = np.dtype([('row_start', '<i8'), ('n_rows', '<i4'), ('domain', '<i4'),
@@ -52,25 +39,51 @@ class DctfpError(RuntimeError):
 _lib = None
 _lib_lock = threading.Lock()
 
-#: the exports of include/dctfp_linkage.h (dct-sim --hac), which counts its own version
-LINKAGE_EXPORTS = ('dctfp_linkage_version', 'dctfp_linkage_nearest', 'dctfp_linkage_merge')
-DCTFP_LINKAGE_VERSION = 1
-LINKAGE_MAX_N = 46340
+INCLUDE_DIR = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'include')
+_ARGUMENT = {'int32_t': C.c_int32, 'int': C.c_int, 'int64_t': C.c_int64, 'double': C.c_double, 'float': C.c_float}
+_RESULT = {'int': C.c_int, 'int64_t': C.c_int64, 'const char*': C.c_char_p}
+_DECLARATION = re.compile(r'^(\w[\w\s]*?[\s*]+)(dctfp_\w+)\s*\(([^()]*)\)\s*;', re.M)
+_DEFINE = re.compile(r'^#define\s+(DCTFP_\w+)\s+\(?(-?\d+)\)?\s*$', re.M)
 
-EXPORTS = ('dctfp_version', 'dctfp_last_error', 'dctfp_create', 'dctfp_destroy', 'dctfp_quantize',
-           'dctfp_idct_quant', 'dctfp_scale', 'dctfp_gather_rows', 'dctfp_contact_topk',
-           'dctfp_contact_count', 'dctfp_stitch', 'dctfp_l1_matrix', 'dctfp_block_min', 'dctfp_row_select', 'dctfp_row_order', 'dctfp_set_option', 'dctfp_get_option', 'dctfp_profile', 'dctfp_host_device_pointer',
-           'dctfp_stream_synchronize', 'dctfp_runtime_info', 'dctfp_crash_handler', 'dctfp_build_pieces', 'dctfp_contact_sort', 'dctfp_stitch_sizes',
-           'dctfp_stitch_sequences', 'dctfp_quantize_windows', 'dctfp_reccut', 'dctfp_reccut_room', 'dctfp_quantize_one', 'dctfp_reccut_pieces',
-           'dctfp_pair_min', 'dctfp_select_count', 'dctfp_select_fill', 'dctfp_sim_lines',
-           'dctfp_l1_knn', 'dctfp_query_rank', 'dctfp_query_lines', 'dctfp_protein_min',
-           'dctfp_tri_filter_count', 'dctfp_tri_filter_fill', 'dctfp_pair_lines',
-           'dctfp_tri_link', 'dctfp_link_pairs', 'dctfp_cluster_labels',
-           'dctfp_pair_argmin', 'dctfp_pair_domain_lines',
-           'dctfp_greedy_decide', 'dctfp_greedy_tri_mark', 'dctfp_greedy_pairs_mark',
-           'dctfp_rows_link', 'dctfp_rows_assign', 'dctfp_tri_nearest', 'dctfp_tree_hook', 'dctfp_rect_best', 'dctfp_protein_cover',
-           'dctfp_label_sums', 'dctfp_tri_degree', 'dctfp_tri_link_core', 'dctfp_tri_first_fp', 'dctfp_tri_tp_before',
-           'dctfp_tri_hist', 'dctfp_rect_moments', 'dctfp_pair_row_best', 'dctfp_pair_map_lines')
+
+def parse_header(path):
+    """({export: (restype, [argtypes])} in the order declared, {name: value} of the integer ``#define``s) of one public header:
+    plain C in one declaration style, ``<ret> dctfp_name(<params>);``.  Every pointer or array parameter is a ``c_void_p``,
+    ``const char*`` included -- the ``table`` parameters take ``tensor.data_ptr()`` integers, which ``c_char_p`` refuses, and
+    ``c_void_p`` takes all the callers pass: bytes, ``byref(...)``, ctypes arrays, None, integers.  A type that is in neither
+    table above is an error that shows the declaration, never a guess."""
+    try:
+        with open(path, encoding='utf8') as fh:
+            text = re.sub(r'/\*.*?\*/', '', fh.read(), flags=re.S)
+    except OSError as err:
+        raise ImportError(f'{path} is missing ({err.strerror}): the binding of libdctfp.so reads its signatures from the public headers') from None
+    exports = {}
+    for found in _DECLARATION.finditer(text):
+        declaration = ' '.join(found.group(0).split())
+        ret, name, params = re.sub(r'\s*\*', '*', ' '.join(found.group(1).split())), found.group(2), found.group(3).strip()
+        if ret not in _RESULT:
+            raise ImportError(f'{path}: no ctypes type for the result "{ret}" of: {declaration}')
+        argtypes = []
+        for param in ([] if params in ('', 'void') else params.split(',')):
+            words = [w for w in param.split() if w != 'const']          # "<type> <name>", or the type alone
+            ctype = C.c_void_p if '*' in param or '[' in param else _ARGUMENT.get(' '.join(words[:-1] or words))
+            if ctype is None:
+                raise ImportError(f'{path}: no ctypes type for the parameter "{param.strip()}" of: {declaration}')
+            argtypes.append(ctype)
+        exports[name] = (_RESULT[ret], argtypes)
+    return exports, {name: int(value) for name, value in _DEFINE.findall(text)}
+
+
+_SIGNATURES, _defines = parse_header(os.path.join(INCLUDE_DIR, 'dctfp.h'))
+_LINKAGE_SIGNATURES, _linkage_defines = parse_header(os.path.join(INCLUDE_DIR, 'dctfp_linkage.h'))
+#: the names include/dctfp.h declares, in its order
+EXPORTS = tuple(_SIGNATURES)
+#: the exports of include/dctfp_linkage.h (dct-sim --hac), which counts its own version
+LINKAGE_EXPORTS = tuple(_LINKAGE_SIGNATURES)
+#: DCTFP_OK, DCTFP_ERR_INVALID .. DCTFP_ERR_UNSUPPORTED, DCTFP_MAX_N, DCTFP_MAX_M, DCTFP_F32 .. DCTFP_BF16, DCTFP_VERSION and
+#: DCTFP_LINKAGE_VERSION: every integer ``#define`` of the two headers, under its own name
+globals().update(_defines, **_linkage_defines)
+LINKAGE_MAX_N = 46340                          # dctfp_linkage_*'s limit on n (floor(sqrt(2^31)))
 
 #: what the five exports that scan an L1 tile of the triangle (and dctfp_rect_best and dctfp_label_sums, on a rectangle) start with: the context, then the library's TriTile (tile, n_rows, n_cols, ld, row0, col0,
 #: row_empty, col_empty, cap, bound) -- ``similarity._tri_filter_args`` makes the values
@@ -153,117 +166,10 @@ def _configure(lib):
     if missing:
         raise ImportError(f'{getattr(lib, "_name", "libdctfp.so")} lacks {", ".join(missing)} (include/dctfp_linkage.h): it was built from '
                           f'an older tree -- rebuild it (python build_ext.py)')
-    if True:
-        lib.dctfp_version.restype = C.c_int
-        lib.dctfp_last_error.restype = C.c_char_p
-        lib.dctfp_create.argtypes = [C.c_int, C.POINTER(C.c_void_p)]
-        lib.dctfp_destroy.argtypes = [C.c_void_p]
-        lib.dctfp_quantize.argtypes = [C.c_void_p, C.POINTER(Layer), C.c_int32, C.c_int32, C.c_void_p,
-                                       C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]
-        lib.dctfp_quantize_windows.argtypes = [C.c_void_p, C.POINTER(Layer), C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32,
-                                               C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]
-        lib.dctfp_quantize_one.argtypes = [C.c_void_p, C.POINTER(Layer), C.c_int32, C.c_int64, C.c_char_p, C.c_int64, C.c_int32, C.c_void_p,
-                                           C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
-                                           C.c_void_p, C.c_void_p, C.c_void_p]
-        lib.dctfp_reccut.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_double,
-                                     C.c_void_p, C.c_void_p, C.c_void_p]
-        lib.dctfp_reccut_room.argtypes = [C.c_int32]
-        lib.dctfp_reccut_pieces.argtypes = [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int64), C.c_void_p,
-                                            C.c_void_p, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
-        lib.dctfp_idct_quant.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_int64,
-                                         C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
-        lib.dctfp_scale.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
-        lib.dctfp_gather_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_int64,
-                                          C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
-        lib.dctfp_contact_topk.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_double,
-                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-        lib.dctfp_contact_count.argtypes = [C.c_int32, C.c_double]
-        lib.dctfp_contact_sort.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_double,
-                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-        lib.dctfp_l1_matrix.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_int64,
-                                        C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]
-        lib.dctfp_block_min.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
-                                        C.c_void_p, C.c_void_p, C.c_void_p]
-        lib.dctfp_row_select.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.c_void_p,
-                                         C.c_void_p, C.c_void_p]
-        lib.dctfp_row_order.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p]
-        lib.dctfp_pair_min.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p,
-                                       C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
-        lib.dctfp_pair_argmin.argtypes = lib.dctfp_pair_min.argtypes[:-1] + [C.c_void_p, C.c_void_p, C.c_void_p]
-        lib.dctfp_protein_min.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p,
-                                          C.c_int64, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]
-        lib.dctfp_protein_cover.argtypes = ([C.c_void_p] + [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p] * 2 +
-                                            [C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p])
-        lib.dctfp_select_count.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32,
-                                           C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
-        lib.dctfp_select_fill.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32,
-                                          C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
-        lib.dctfp_sim_lines.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_void_p,
-                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-        lib.dctfp_tri_filter_count.argtypes = _TRI_TILE + [C.c_void_p, C.c_void_p]
-        lib.dctfp_tri_filter_fill.argtypes = _TRI_TILE + [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
-        lib.dctfp_pair_lines.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                         C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
-        lib.dctfp_pair_domain_lines.argtypes = [C.c_void_p, C.c_int64] + [C.c_void_p] * 8 + [C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
-                                                C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
-        lib.dctfp_pair_row_best.argtypes = lib.dctfp_pair_min.argtypes[:12] + [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
-        lib.dctfp_pair_map_lines.argtypes = lib.dctfp_pair_domain_lines.argtypes[:-1] + [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
-                                                                                        C.c_int32, C.c_void_p, C.c_void_p]
-        lib.dctfp_tri_link.argtypes = _TRI_TILE + [C.c_void_p, C.c_int64, C.c_void_p]
-        lib.dctfp_link_pairs.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]
-        lib.dctfp_cluster_labels.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
-        lib.dctfp_rows_link.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int32,
-                                        C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]
-        lib.dctfp_rows_assign.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p,
-                                          C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]
-        lib.dctfp_tri_nearest.argtypes = _TRI_TILE + [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
-        lib.dctfp_tree_hook.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
-                                        C.c_void_p, C.c_int64, C.c_void_p]
-        lib.dctfp_linkage_version.argtypes = []
-        lib.dctfp_linkage_nearest.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32,
-                                              C.c_void_p, C.c_void_p]
-        lib.dctfp_linkage_merge.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
-                                            C.c_void_p]
-        lib.dctfp_rect_best.argtypes = _TRI_TILE + [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]
-        lib.dctfp_label_sums.argtypes = _TRI_TILE + [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
-        lib.dctfp_tri_degree.argtypes = _TRI_TILE + [C.c_void_p, C.c_int64, C.c_void_p]
-        lib.dctfp_tri_link_core.argtypes = _TRI_TILE + [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
-        lib.dctfp_tri_first_fp.argtypes = _TRI_TILE + [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
-        lib.dctfp_tri_tp_before.argtypes = _TRI_TILE + [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
-        lib.dctfp_tri_hist.argtypes = _TRI_TILE + [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
-        lib.dctfp_rect_moments.argtypes = _TRI_TILE + [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]
-        lib.dctfp_greedy_decide.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.c_void_p,
-                                            C.c_void_p]
-        lib.dctfp_greedy_tri_mark.argtypes = _TRI_TILE + [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_void_p]
-        lib.dctfp_greedy_pairs_mark.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
-                                                C.c_int64, C.c_int32, C.c_void_p]
-        lib.dctfp_l1_knn.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int32,
-                                     C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
-        lib.dctfp_query_rank.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
-                                         C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-        lib.dctfp_query_lines.argtypes = [C.c_void_p, C.c_int64] + [C.c_void_p] * 15
-        lib.dctfp_stitch.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p]
-        lib.dctfp_stitch_sizes.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p]
-        lib.dctfp_stitch_sequences.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
-                                               C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]
-        lib.dctfp_set_option.argtypes = [C.c_void_p, C.c_char_p, C.c_int64]
-        lib.dctfp_get_option.argtypes = [C.c_void_p, C.c_char_p, C.POINTER(C.c_int64)]
-        lib.dctfp_profile.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int64)]
-        lib.dctfp_host_device_pointer.argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
-        lib.dctfp_stream_synchronize.argtypes = [C.c_void_p]
-        lib.dctfp_runtime_info.argtypes = [C.c_char_p, C.c_int64]
-        lib.dctfp_crash_handler.argtypes = [C.c_int]
-        lib.dctfp_build_pieces.argtypes = [C.c_char_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int64,
-                                           C.POINTER(C.c_int64), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
-                                           C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
-        for fn in EXPORTS:
-            if fn not in ('dctfp_last_error', 'dctfp_contact_count', 'dctfp_reccut_room'):
-                getattr(lib, fn).restype = C.c_int
-        for fn in LINKAGE_EXPORTS:
-            getattr(lib, fn).restype = C.c_int
-        lib.dctfp_contact_count.restype = C.c_int64
-        lib.dctfp_reccut_room.restype = C.c_int64
-        return lib
+    for name, (restype, argtypes) in {**_SIGNATURES, **_LINKAGE_SIGNATURES}.items():
+        fn = getattr(lib, name)
+        fn.restype, fn.argtypes = restype, list(argtypes)
+    return lib
 
 
 def check(rc: int, lib=None):
@@ -306,6 +212,19 @@ class Context:
         if not self._h:
             raise RuntimeError('context is closed')
         return self._h
+
+    def call(self, name: str, *args, stream=None):
+        """Calls the export ``name`` with this context first and the stream last; a failure raises what ``check`` maps its code
+        to, with this library's message.  ``stream``: a torch stream; None = the current stream of the context's device.
+        Every call of an export of that shape goes through here, but for two kinds that stay inline on purpose: the quantize
+        entry points (dctfp_quantize, dctfp_quantize_windows, dctfp_quantize_one in batch.py and fingerprint.py), which are what
+        bench.py times and which cache their stream pointer; and the exports that take no context or no stream
+        (dctfp_build_pieces, dctfp_reccut_pieces, dctfp_stitch_sizes, dctfp_host_device_pointer, dctfp_stream_synchronize,
+        dctfp_runtime_info, dctfp_contact_count)."""
+        if stream is None:
+            import torch
+            stream = torch.cuda.current_stream(self.device)
+        check(getattr(self._lib, name)(self.handle, *args, C.c_void_p(stream.cuda_stream)), self._lib)
 
     def set_option(self, name: str, value: int):
         check(self._lib.dctfp_set_option(self.handle, name.encode(), int(value)), self._lib)

@@ -106,10 +106,7 @@ class SyntheticModel:
 
 def _stitch(jobs: List[StitchJob], n_cols: int, square: bool, device):
     arr = (StitchJob * len(jobs))(*jobs)
-    ctx = _lib.get_context(device.index)
-    stream = torch.cuda.current_stream(device)
-    _lib.check(ctx._lib.dctfp_stitch(ctx.handle, arr, len(jobs), int(n_cols), 1 if square else 0,
-                                     C.c_void_p(stream.cuda_stream)))
+    _lib.get_context(device.index).call('dctfp_stitch', arr, len(jobs), int(n_cols), 1 if square else 0)
 
 
 def stitch_embeddings(windows: List[torch.Tensor], overlap: int = OVERLAP) -> torch.Tensor:
@@ -196,11 +193,9 @@ def _stitch_sequences(flat, counts, step: int, square: bool, n_cols: int):
         first = np.zeros(n_seq, dtype=np.int64)
         np.cumsum(sizes[:-1], out=first[1:])
         dst = np.uint64(big.data_ptr()) + first.astype(np.uint64) * np.uint64(4 * n_cols)
-    ctx = _lib.get_context(device.index)
-    stream = torch.cuda.current_stream(device)
-    _lib.check(lib.dctfp_stitch_sequences(ctx.handle, ptrs.ctypes.data, rows.ctypes.data, lds.ctypes.data, seq_win.ctypes.data,
-                                          n_seq, dst.ctypes.data, np.ascontiguousarray(dst_ld, dtype=np.int64).ctypes.data,
-                                          int(n_cols), int(step), 1 if square else 0, C.c_void_p(stream.cuda_stream)), lib)
+    _lib.get_context(device.index).call('dctfp_stitch_sequences', ptrs.ctypes.data, rows.ctypes.data, lds.ctypes.data, seq_win.ctypes.data,
+                                        n_seq, dst.ctypes.data, np.ascontiguousarray(dst_ld, dtype=np.int64).ctypes.data, int(n_cols),
+                                        int(step), 1 if square else 0)
     return _Views(big, first, sizes, square)
 
 
@@ -217,13 +212,10 @@ def stitch_windows_flat(layer, win_rows, seq_win, sizes, overlap: int = OVERLAP)
     dst = np.uint64(big.data_ptr()) + first.astype(np.uint64) * np.uint64(4 * layer.n_cols)
     lds = np.full(n_win, layer.ld, dtype=np.int64)
     dst_ld = np.full(n_seq, layer.n_cols, dtype=np.int64)
-    lib = _lib.load()
-    ctx = _lib.get_context(layer.device.index)
-    stream = torch.cuda.current_stream(layer.device)
-    _lib.check(lib.dctfp_stitch_sequences(ctx.handle, layer.ptrs.ctypes.data, np.ascontiguousarray(win_rows, dtype=np.int32).ctypes.data,
-                                          lds.ctypes.data, np.ascontiguousarray(seq_win, dtype=np.int64).ctypes.data, n_seq,
-                                          dst.ctypes.data, dst_ld.ctypes.data, int(layer.n_cols), int(overlap), 0,
-                                          C.c_void_p(stream.cuda_stream)), lib)
+    win_rows, seq_win = np.ascontiguousarray(win_rows, dtype=np.int32), np.ascontiguousarray(seq_win, dtype=np.int64)
+    _lib.get_context(layer.device.index).call('dctfp_stitch_sequences', layer.ptrs.ctypes.data, win_rows.ctypes.data, lds.ctypes.data,
+                                              seq_win.ctypes.data, n_seq, dst.ctypes.data, dst_ld.ctypes.data, int(layer.n_cols),
+                                              int(overlap), 0)
     return big, first
 
 

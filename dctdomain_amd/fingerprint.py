@@ -124,10 +124,7 @@ class Fingerprint:
         t = t.contiguous()
         flat = t.reshape(-1)
         out = torch.empty_like(flat)
-        ctx = _lib.get_context(t.device.index)
-        stream = torch.cuda.current_stream(t.device)
-        _lib.check(ctx._lib.dctfp_scale(ctx.handle, flat.data_ptr(), flat.numel(), out.data_ptr(),
-                                        C.c_void_p(stream.cuda_stream)))
+        _lib.get_context(t.device.index).call('dctfp_scale', flat.data_ptr(), flat.numel(), out.data_ptr())
         return _like_input(out.reshape(t.shape), vec)
 
     def idct_quant(self, vec, num: int):
@@ -137,11 +134,8 @@ class Fingerprint:
         n_rows, n_cols = t.shape
         k = min(int(num), n_rows)      # f[:, :num] cannot be wider than the transform
         out = torch.empty((k, n_cols), dtype=torch.float64, device=t.device)
-        ctx = _lib.get_context(t.device.index)
-        stream = torch.cuda.current_stream(t.device)
-        _lib.check(ctx._lib.dctfp_idct_quant(ctx.handle, t.data_ptr(), _dtype_code(t), n_rows, n_cols,
-                                             t.stride(0) if n_rows > 1 else n_cols, k, out.data_ptr(), None,
-                                             C.c_void_p(stream.cuda_stream)))
+        _lib.get_context(t.device.index).call('dctfp_idct_quant', t.data_ptr(), _dtype_code(t), n_rows, n_cols,
+                                              t.stride(0) if n_rows > 1 else n_cols, k, out.data_ptr(), None)
         return _like_input(out, vec)
 
     def dct_coefficients(self, vec, num: int):
@@ -151,11 +145,8 @@ class Fingerprint:
         n_rows, n_cols = t.shape
         k = min(int(num), n_rows)
         coef = torch.empty((n_cols, k), dtype=torch.float64, device=t.device)
-        ctx = _lib.get_context(t.device.index)
-        stream = torch.cuda.current_stream(t.device)
-        _lib.check(ctx._lib.dctfp_idct_quant(ctx.handle, t.data_ptr(), _dtype_code(t), n_rows, n_cols,
-                                             t.stride(0) if n_rows > 1 else n_cols, k, None, coef.data_ptr(),
-                                             C.c_void_p(stream.cuda_stream)))
+        _lib.get_context(t.device.index).call('dctfp_idct_quant', t.data_ptr(), _dtype_code(t), n_rows, n_cols,
+                                              t.stride(0) if n_rows > 1 else n_cols, k, None, coef.data_ptr())
         return _like_input(coef, vec)
 
     def get_doms(self, embed, dom: str) -> tuple:
@@ -170,11 +161,8 @@ class Fingerprint:
             rec = np.zeros(len(pieces), dtype=_lib.PIECE_DTYPE)
             rec['row_start'] = [p[0] for p in pieces]
             rec['n_rows'] = [p[1] for p in pieces]
-            ctx = _lib.get_context(t.device.index)
-            stream = torch.cuda.current_stream(t.device)
-            _lib.check(ctx._lib.dctfp_gather_rows(ctx.handle, t.data_ptr(), _dtype_code(t), n_rows, n_cols,
-                                                  t.stride(0) if n_rows > 1 else n_cols, rec.ctypes.data, len(rec),
-                                                  out.data_ptr(), C.c_void_p(stream.cuda_stream)))
+            _lib.get_context(t.device.index).call('dctfp_gather_rows', t.data_ptr(), _dtype_code(t), n_rows, n_cols,
+                                                  t.stride(0) if n_rows > 1 else n_cols, rec.ctypes.data, len(rec), out.data_ptr())
         return _like_input(out, embed), key
 
     # -- the hot path ----------------------------------------------------------------------

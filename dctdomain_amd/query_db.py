@@ -10,7 +10,6 @@ here the exact L1 matrix comes from the GPU kernel and needs no index file.
 from __future__ import annotations
 
 import argparse
-import ctypes as C
 import logging
 import os
 from io import BytesIO
@@ -271,7 +270,7 @@ class QuerySearch:
         text = torch.empty(max(1, text_bytes), dtype=torch.uint8, device=dev)
         out = TextStream(lambda view: sink(bytes(view)), room=lambda nbytes: max(1, text_bytes))      # (no run is longer than the text buffer)
         ctx = _lib.get_context(dev.index)
-        sp = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        stream = torch.cuda.current_stream(dev)
         p0 = 0
         while p0 < n_prot:
             p1 = max(p0 + 1, int(np.searchsorted(qoff, qoff[p0] + batch_rows, side='right')) - 1)
@@ -292,9 +291,8 @@ class QuerySearch:
             lx = torch.empty_like(lq)
             # (named: a temporary's memory would go back to the allocator, and to the next argument, before the kernel ran)
             qoff_dev, prot_dev, base_dev = _device_int64(qoff[p0:p1 + 1] - r0, dev), torch.as_tensor(prot_of_row, device=dev), _device_int64(base, dev)
-            _lib.check(ctx._lib.dctfp_query_rank(ctx.handle, val.data_ptr(), idx.data_ptr(), len(rows), kk, qoff_dev.data_ptr(),
-                                                 prot_dev.data_ptr(), base_dev.data_ptr(), int(khits), lq.data_ptr(), ld.data_ptr(),
-                                                 lx.data_ptr(), sp))
+            ctx.call('dctfp_query_rank', val.data_ptr(), idx.data_ptr(), len(rows), kk, qoff_dev.data_ptr(), prot_dev.data_ptr(),
+                     base_dev.data_ptr(), int(khits), lq.data_ptr(), ld.data_ptr(), lx.data_ptr(), stream=stream)
             qr, dr, dx = (t.cpu().numpy().astype(np.int64)[:total] for t in (lq, ld, lx))
             if host.any():                                                  # proteins of many hits: ranked_hits on the host
                 vh, ih = _pair_to_host(val, idx)
@@ -320,10 +318,9 @@ class QuerySearch:
                 b = max(b, a + 1)
                 nbytes = int(off[b] - off[a])
                 rel = off_dev[a:b + 1] - int(off[a])
-                _lib.check(ctx._lib.dctfp_query_lines(ctx.handle, b - a, *(t[a:].data_ptr() for t in dev_cols), q_txt.data_ptr(),
-                                                      q_pid_off.data_ptr(), q_dom_off.data_ptr(), self.d_txt.data_ptr(),
-                                                      self.d_pid_off.data_ptr(), self.d_dom_off.data_ptr(), self.score_txt_dev.data_ptr(),
-                                                      self.score_off_dev.data_ptr(), rel.data_ptr(), text.data_ptr(), sp))
+                ctx.call('dctfp_query_lines', b - a, *(t[a:].data_ptr() for t in dev_cols), q_txt.data_ptr(), q_pid_off.data_ptr(),
+                         q_dom_off.data_ptr(), self.d_txt.data_ptr(), self.d_pid_off.data_ptr(), self.d_dom_off.data_ptr(),
+                         self.score_txt_dev.data_ptr(), self.score_off_dev.data_ptr(), rel.data_ptr(), text.data_ptr(), stream=stream)
                 out.hand_over(text, nbytes)
                 a = b
             p0 = p1

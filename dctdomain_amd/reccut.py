@@ -11,7 +11,6 @@ subprocess:
 
 from __future__ import annotations
 
-import ctypes as C
 import threading
 from typing import List, Sequence
 
@@ -106,10 +105,8 @@ def enqueue_topk(ptrs, lds, n_res, t: float, device, stream):
         oj = torch.empty(total, dtype=torch.int32, device=device)
         ov = torch.empty(total, dtype=torch.float32, device=device)
         on = torch.zeros(n, dtype=torch.int32, device=device)
-    lib = _lib.load()
-    _lib.check(lib.dctfp_contact_topk(_lib.get_context(device.index).handle, ptrs.ctypes.data, lds.ctypes.data, n_res.ctypes.data,
-                                      n, float(t), oi.data_ptr(), oj.data_ptr(), ov.data_ptr(), offs.ctypes.data, on.data_ptr(),
-                                      C.c_void_p(stream.cuda_stream)), lib)
+    _lib.get_context(device.index).call('dctfp_contact_topk', ptrs.ctypes.data, lds.ctypes.data, n_res.ctypes.data, n, float(t),
+                                        oi.data_ptr(), oj.data_ptr(), ov.data_ptr(), offs.ctypes.data, on.data_ptr(), stream=stream)
     return counts, offs, oi, oj, ov, on
 
 
@@ -136,10 +133,9 @@ def top_contacts_batch(maps: Sequence[torch.Tensor], t: float, sort: bool = True
     total = int(offs[-1])
     on_device = np.ones(n, dtype=np.uint8)
     if sort:
-        lib = _lib.load()
-        _lib.check(lib.dctfp_contact_sort(_lib.get_context(device.index).handle, ptrs.ctypes.data, lds.ctypes.data,
-                                          n_res.ctypes.data, n, float(t), oi.data_ptr(), oj.data_ptr(), ov.data_ptr(),
-                                          offs.ctypes.data, on_device.ctypes.data, C.c_void_p(stream.cuda_stream)))
+        _lib.get_context(device.index).call('dctfp_contact_sort', ptrs.ctypes.data, lds.ctypes.data, n_res.ctypes.data, n, float(t),
+                                            oi.data_ptr(), oj.data_ptr(), ov.data_ptr(), offs.ctypes.data, on_device.ctypes.data,
+                                            stream=stream)
     pi, pj, pv, pn = (_pinned('i', torch.int32, total), _pinned('j', torch.int32, total), _pinned('v', torch.float32, total),
                       _pinned('n', torch.int32, n))
     pi.copy_(oi[:total], non_blocking=True)
@@ -216,16 +212,15 @@ class CutInFlight:
     def _enqueue_cut(self, device, on):
         """``dctfp_reccut`` behind whatever is on the stream, then the copies of its results (and of ``on``, the contacts top-k
         wrote) into page-locked buffers of this batch's own."""
-        lib = _lib.load()
         n = self.n
         self.enc_off = np.zeros(n + 1, dtype=np.int64)
         np.cumsum(reccut_room(self.n_res), out=self.enc_off[1:])
         n_enc = int(self.enc_off[-1])
         with torch.cuda.stream(self.stream):
             enc = torch.empty(n_enc, dtype=torch.int32, device=device)
-            _lib.check(lib.dctfp_reccut(_lib.get_context(device.index).handle, self.n_res.ctypes.data, n, self.oi.data_ptr(),
-                                        self.oj.data_ptr(), self.ov.data_ptr(), self.offs.ctypes.data, self.cut1, self.cut2,
-                                        enc.data_ptr(), self.enc_off.ctypes.data, C.c_void_p(self.stream.cuda_stream)), lib)
+            _lib.get_context(device.index).call('dctfp_reccut', self.n_res.ctypes.data, n, self.oi.data_ptr(), self.oj.data_ptr(),
+                                                self.ov.data_ptr(), self.offs.ctypes.data, self.cut1, self.cut2, enc.data_ptr(),
+                                                self.enc_off.ctypes.data, stream=self.stream)
             self._record(2)
             self._pins = (_pinned_take('enc', torch.int32, n_enc), _pinned_take('n', torch.int32, n) if on is not None else None)
             self.penc = self._pins[0][:n_enc]

@@ -3,7 +3,6 @@ arithmetic under the reference's two consumers, ``src/dct-sim.py`` and ``src/que
 
 from __future__ import annotations
 
-import ctypes as C
 import threading
 
 import numpy as np
@@ -29,14 +28,24 @@ def to_device_int8(fps) -> torch.Tensor:
 
 def _launch(device, name: str, *args):
     """Calls the library's export ``name`` with the context of ``device``, ``args`` and the device's current stream (every
-    export's first and last argument); a failure raises what ``_lib.check`` maps its code to."""
-    ctx = _lib.get_context(device.index)
-    _lib.check(getattr(ctx._lib, name)(ctx.handle, *args, C.c_void_p(torch.cuda.current_stream(device).cuda_stream)))
+    export's first and last argument: ``_lib.Context.call``); a failure raises what ``_lib.check`` maps its code to."""
+    _lib.get_context(device.index).call(name, *args)
 
 
 def _ld(t: torch.Tensor) -> int:
     """The row stride of a 2-D tensor in elements; its width where there is at most one row (a size-1 axis may carry any stride)."""
     return t.stride(0) if t.shape[0] > 1 else t.shape[1]
+
+
+# ---- the argument checks, each written once: the library bounds no index on the device, its kernels trust what these let through
+
+def _vector(t: torch.Tensor, dtype, device, what: str, n: int = None, flat: bool = True) -> int:
+    """The length of ``t``, which must be a contiguous 1-D tensor of ``dtype`` on ``device`` -- of ``n`` entries, if given.
+    ``flat=False``: any shape of that many entries (the columns of the line writers, which never asked for one dimension)."""
+    if t.dtype != dtype or (flat and t.dim() != 1) or not t.is_contiguous() or t.device != device or (n is not None and t.numel() != n):
+        raise ValueError(f'{what} must be a contiguous {"1-D " if flat else ""}{dtype} tensor'
+                         f'{"" if n is None else f" of {n} entries"} on the device of the other arguments')
+    return t.numel()
 
 
 def _check_pair(ta: torch.Tensor, tb: torch.Tensor):
@@ -50,16 +59,50 @@ def _check_prefix(idx: np.ndarray, rows: int):
         raise ValueError('idx must be a non-decreasing prefix array within its fingerprint matrix')
 
 
+def _prefix_sides(ta: torch.Tensor, idx_a, tb: torch.Tensor, idx_b):
+    """(ia, ib): the prefix arrays of two device fingerprint matrices as int64 numpy arrays, matrices and arrays checked."""
+    ia, ib = np.asarray(idx_a, dtype=np.int64), np.asarray(idx_b, dtype=np.int64)
+    _check_pair(ta, tb)
+    _check_prefix(ia, ta.shape[0])
+    _check_prefix(ib, tb.shape[0])
+    return ia, ib
+
+
+def _out_tile(out, n_rows: int, n_cols: int, device) -> torch.Tensor:
+    """``out``, or a fresh tile where it is None: int32 (n_rows, n_cols) on ``device`` with unit column stride (any row stride: a
+    column range of a wider tile)."""
+    if out is None:
+        return torch.empty((n_rows, n_cols), dtype=torch.int32, device=device)
+    if out.dtype != torch.int32 or tuple(out.shape) != (n_rows, n_cols) or out.device != device or (n_cols > 1 and out.stride(1) != 1):
+        raise ValueError(f'out must be an int32 ({n_rows}, {n_cols}) tensor on the fingerprints\' device with unit column stride')
+    return out
+
+
+def _text_buffer(out: torch.Tensor, device):
+    """The buffer the line writers fill: contiguous uint8 on ``device``."""
+    if out.dtype != torch.uint8 or not out.is_contiguous() or out.device != device:
+        raise ValueError('out must be a contiguous uint8 buffer on the device of the other arguments')
+
+
+def _line_offsets(line_off: torch.Tensor, n: int, device):
+    """Where the lines start: contiguous int64 on ``device``, an entry per line at least (a prefix sum has one more)."""
+    _vector(line_off, torch.int64, device, 'line_off', flat=False)
+    if line_off.numel() < n:
+        raise ValueError('line_off must have an entry per line')
+
+
+def _score_table(table: torch.Tensor):
+    """``dct_sim.score_table`` on the device, as the line writers read it: 2 x 17002 rows of 5 bytes, one after the other."""
+    if table.dtype != torch.uint8 or table.numel() != 2 * 17002 * 5 or not table.is_contiguous():
+        raise ValueError('table must be a contiguous uint8 (2, 17002, 5) tensor')
+
+
 def l1_matrix(a, b, out: torch.Tensor = None) -> torch.Tensor:
     """int32 (na, nb) matrix of L1 distances, on the GPU.  ``out``: an int32 (na, nb) device tensor with unit column stride to
     write into (any row stride: a column range of a wider tile)."""
     ta, tb = to_device_int8(a), to_device_int8(b)
     _check_pair(ta, tb)
-    if out is None:
-        out = torch.empty((ta.shape[0], tb.shape[0]), dtype=torch.int32, device=ta.device)
-    elif (out.dtype != torch.int32 or tuple(out.shape) != (ta.shape[0], tb.shape[0]) or out.device != ta.device
-          or (out.shape[1] > 1 and out.stride(1) != 1)):
-        raise ValueError('out must be an int32 (na, nb) tensor on the fingerprints\' device with unit column stride')
+    out = _out_tile(out, ta.shape[0], tb.shape[0], ta.device)
     if out.numel():
         _launch(ta.device, 'dctfp_l1_matrix', ta.data_ptr(), ta.shape[0], _ld(ta), tb.data_ptr(), tb.shape[0], _ld(tb), ta.shape[1],
                 out.data_ptr(), _ld(out))
@@ -180,16 +223,32 @@ def _device_int64(a, device) -> torch.Tensor:
     return torch.as_tensor(np.ascontiguousarray(np.asarray(a, dtype=np.int64)), device=device)
 
 
-def _pair_scores_device(a: torch.Tensor, idx_a: torch.Tensor, b: torch.Tensor, idx_b: torch.Tensor, pairs: torch.Tensor, arg: bool):
-    """The device int32 tensors (min, last) -- with ``arg`` also (arg_a, arg_b) -- of ``pair_min_device`` / ``pair_argmin_device``:
-    ``dctfp_pair_min``, or ``dctfp_pair_argmin`` with its two more outputs."""
+def _pair_device_args(a: torch.Tensor, idx_a: torch.Tensor, b: torch.Tensor, idx_b: torch.Tensor, pairs: torch.Tensor):
+    """(n, device) of ``pairs``: what the ``*_device`` pair functions ask of arguments that are on the device already."""
     if pairs.dtype != torch.int32 or pairs.dim() != 2 or pairs.shape[1] != 2 or not pairs.is_contiguous():
         raise ValueError('pairs must be a contiguous int32 (n, 2) device tensor')
     if a.dtype != torch.int8 or b.dtype != torch.int8 or a.dim() != 2 or b.dim() != 2 or a.shape[1] != b.shape[1]:
-        raise ValueError('fingerprint sets must be 2-D int8 with equal width')
+        raise ValueError('fingerprint sets a / b must be 2-D int8 with equal width')
     if idx_a.dtype != torch.int64 or idx_b.dtype != torch.int64 or not (idx_a.is_contiguous() and idx_b.is_contiguous()):
-        raise ValueError('prefix arrays must be contiguous int64 device tensors')
-    n, dev = pairs.shape[0], pairs.device
+        raise ValueError('prefix arrays idx_a / idx_b must be contiguous int64 device tensors')
+    return pairs.shape[0], pairs.device
+
+
+def _pair_host_args(a, idx_a, b, idx_b, pairs):
+    """(ta, ia, tb, ib, pairs) of the host pair functions: the fingerprints as device int8, the prefix arrays and the (n, 2) pairs
+    as int64 numpy arrays -- prefix arrays within their matrices, pair indices within the proteins."""
+    pairs = np.ascontiguousarray(np.asarray(pairs, dtype=np.int64).reshape(-1, 2))
+    ta, tb = to_device_int8(a), to_device_int8(b)
+    ia, ib = _prefix_sides(ta, idx_a, tb, idx_b)
+    if len(pairs) and (pairs[:, 0].min() < 0 or pairs[:, 0].max() >= len(ia) - 1 or pairs[:, 1].min() < 0 or pairs[:, 1].max() >= len(ib) - 1):
+        raise IndexError('protein index of pairs out of range')
+    return ta, ia, tb, ib, pairs
+
+
+def _pair_scores_device(a: torch.Tensor, idx_a: torch.Tensor, b: torch.Tensor, idx_b: torch.Tensor, pairs: torch.Tensor, arg: bool):
+    """The device int32 tensors (min, last) -- with ``arg`` also (arg_a, arg_b) -- of ``pair_min_device`` / ``pair_argmin_device``:
+    ``dctfp_pair_min``, or ``dctfp_pair_argmin`` with its two more outputs."""
+    n, dev = _pair_device_args(a, idx_a, b, idx_b, pairs)
     out = [torch.full((n,), fill, dtype=torch.int32, device=dev) for fill in (0x7fffffff, 0x7fffffff) + ((-1, -1) if arg else ())]
     if n and a.shape[0] and b.shape[0]:                         # (no fingerprint on a side: every pair is empty)
         _launch(dev, 'dctfp_pair_argmin' if arg else 'dctfp_pair_min', pairs.data_ptr(), n, a.data_ptr(), _ld(a), idx_a.data_ptr(),
@@ -199,15 +258,7 @@ def _pair_scores_device(a: torch.Tensor, idx_a: torch.Tensor, b: torch.Tensor, i
 
 def _pair_scores_host(a, idx_a, b, idx_b, pairs, arg: bool):
     """``_pair_scores_device`` for host arguments, which are checked here, as int64 numpy arrays."""
-    pairs = np.ascontiguousarray(np.asarray(pairs, dtype=np.int64).reshape(-1, 2))
-    ia, ib = np.asarray(idx_a, dtype=np.int64), np.asarray(idx_b, dtype=np.int64)
-    npa, npb = len(ia) - 1, len(ib) - 1
-    ta, tb = to_device_int8(a), to_device_int8(b)
-    _check_pair(ta, tb)
-    _check_prefix(ia, ta.shape[0])
-    _check_prefix(ib, tb.shape[0])
-    if len(pairs) and (pairs[:, 0].min() < 0 or pairs[:, 0].max() >= npa or pairs[:, 1].min() < 0 or pairs[:, 1].max() >= npb):
-        raise IndexError('protein index out of range')
+    ta, ia, tb, ib, pairs = _pair_host_args(a, idx_a, b, idx_b, pairs)
     n = len(pairs)
     if n == 0 or ta.shape[0] == 0 or tb.shape[0] == 0:          # (no fingerprint on a side: every pair is empty)
         return tuple(np.full(n, fill, dtype=np.int64) for fill in (0x7fffffff, 0x7fffffff) + ((-1, -1) if arg else ()))
@@ -260,15 +311,7 @@ def pair_row_best(a, idx_a, b, idx_b, pairs):
     then those of the protein of ``b``; ``l1`` = the smallest L1 to any row of the other protein, raw, ``arg`` = that row within the
     other protein, ties to the lowest; 0x7fffffff and -1 where the other protein has no rows.  ``pair_argmin``'s arguments and
     checks."""
-    pairs = np.ascontiguousarray(np.asarray(pairs, dtype=np.int64).reshape(-1, 2))
-    ia, ib = np.asarray(idx_a, dtype=np.int64), np.asarray(idx_b, dtype=np.int64)
-    npa, npb = len(ia) - 1, len(ib) - 1
-    ta, tb = to_device_int8(a), to_device_int8(b)
-    _check_pair(ta, tb)
-    _check_prefix(ia, ta.shape[0])
-    _check_prefix(ib, tb.shape[0])
-    if len(pairs) and (pairs[:, 0].min() < 0 or pairs[:, 0].max() >= npa or pairs[:, 1].min() < 0 or pairs[:, 1].max() >= npb):
-        raise IndexError('protein index out of range')
+    ta, ia, tb, ib, pairs = _pair_host_args(a, idx_a, b, idx_b, pairs)
     off = pair_row_offsets(ia, ib, pairs)
     total = int(off[-1])
     if len(pairs) == 0 or ta.shape[0] == 0 or tb.shape[0] == 0:  # (no fingerprint on a side: no row has a counterpart)
@@ -285,20 +328,13 @@ def pair_row_best_device(a: torch.Tensor, idx_a: torch.Tensor, b: torch.Tensor, 
     device int64 (n + 1), made here from the prefix arrays when None.  Returns device (row_off int64, l1 int32, arg int32); the
     kernel leaves the fill, 0x7fffffff and -1, in the rows of a pair whose index is out of range or whose ``row_off`` range is not
     its two proteins' rows."""
-    if pairs.dtype != torch.int32 or pairs.dim() != 2 or pairs.shape[1] != 2 or not pairs.is_contiguous():
-        raise ValueError('pairs must be a contiguous int32 (n, 2) device tensor')
-    if a.dtype != torch.int8 or b.dtype != torch.int8 or a.dim() != 2 or b.dim() != 2 or a.shape[1] != b.shape[1]:
-        raise ValueError('fingerprint sets must be 2-D int8 with equal width')
-    if idx_a.dtype != torch.int64 or idx_b.dtype != torch.int64 or not (idx_a.is_contiguous() and idx_b.is_contiguous()):
-        raise ValueError('prefix arrays must be contiguous int64 device tensors')
-    n, dev = pairs.shape[0], pairs.device
+    n, dev = _pair_device_args(a, idx_a, b, idx_b, pairs)
     if row_off is None:
         pa, pb = pairs[:, 0].long(), pairs[:, 1].long()
         row_off = torch.zeros(n + 1, dtype=torch.int64, device=dev)
         if n:
             torch.cumsum((idx_a[pa + 1] - idx_a[pa]) + (idx_b[pb + 1] - idx_b[pb]), 0, out=row_off[1:])
-    if row_off.dtype != torch.int64 or row_off.numel() != n + 1 or not row_off.is_contiguous() or row_off.device != dev:
-        raise ValueError('row_off must be a contiguous int64 device tensor with an entry per pair and one more')
+    _vector(row_off, torch.int64, dev, 'row_off (an entry per pair and one more)', n + 1, flat=False)
     total = int(row_off[-1]) if n else 0
     l1 = torch.full((max(total, 0),), 0x7fffffff, dtype=torch.int32, device=dev)
     arg = torch.full((max(total, 0),), -1, dtype=torch.int32, device=dev)
@@ -308,31 +344,40 @@ def pair_row_best_device(a: torch.Tensor, idx_a: torch.Tensor, b: torch.Tensor, 
     return row_off, l1, arg
 
 
+def _rows_view(t) -> torch.Tensor:
+    """``to_device_int8`` that leaves a device int8 view with unit column stride and rows that do not overlap as it is (any row
+    stride from the width up, any alignment); anything else becomes a contiguous copy."""
+    if isinstance(t, torch.Tensor) and t.dtype == torch.int8 and t.device.type == 'cuda' and t.dim() == 2 and (t.shape[1] <= 1 or t.stride(1) == 1) \
+            and (t.shape[0] <= 1 or t.stride(0) >= t.shape[1]):
+        return t
+    return to_device_int8(t)
+
+
+def _protein_out(out, ia: np.ndarray, ib: np.ndarray, device):
+    """(out, done) for the proteins of ``ia`` x ``ib``: ``out`` checked, or made (``_out_tile``); ``done`` = there is nothing to
+    launch -- no protein pair, or no fingerprint on a side: every pair is empty and has its 0x7fffffff from here."""
+    out = _out_tile(out, len(ia) - 1, len(ib) - 1, device)
+    if out.numel() == 0:
+        return out, True
+    if ia[-1] == ia[0] or ib[-1] == ib[0]:
+        return out.fill_(0x7fffffff), True
+    return out, False
+
+
 def protein_min(a, idx_a, b, idx_b, out: torch.Tensor = None) -> torch.Tensor:
     """int32 (npa, npb) on the device: the smallest L1 over all fingerprint pairs of every (protein of ``a``, protein of ``b``)
     -- DCTdomain's distance, ``block_min(l1_matrix(a, b), idx_a, idx_b)[0]`` without the distance matrix
     (``dctfp_protein_min``).  ``idx_a`` / ``idx_b``: the npz prefix arrays; a protein without fingerprints gives 0x7fffffff.
     ``out``: an int32 (npa, npb) device tensor with unit column stride to write into (any row stride).  Rows not on 16-byte
     boundaries are copied into padded ones; rows wider than 512 bytes (the kernel's limit) take l1_matrix + block_min."""
-    ia, ib = np.asarray(idx_a, dtype=np.int64), np.asarray(idx_b, dtype=np.int64)
-    npa, npb = len(ia) - 1, len(ib) - 1
-    ta, tb = _row_major_int8(a), _row_major_int8(b)
-    _check_pair(ta, tb)
-    _check_prefix(ia, ta.shape[0])
-    _check_prefix(ib, tb.shape[0])
-    dev = ta.device
-    if out is None:
-        out = torch.empty((npa, npb), dtype=torch.int32, device=dev)
-    elif out.dtype != torch.int32 or tuple(out.shape) != (npa, npb) or out.device != dev or (npb > 1 and out.stride(1) != 1):
-        raise ValueError('out must be an int32 (npa, npb) tensor on the fingerprints\' device with unit column stride')
-    if out.numel() == 0:
+    ta, tb = _rows_view(a), _rows_view(b)
+    ia, ib = _prefix_sides(ta, idx_a, tb, idx_b)
+    npa, npb, dev, d = len(ia) - 1, len(ib) - 1, ta.device, ta.shape[1]
+    out, done = _protein_out(out, ia, ib, dev)
+    if done:
         return out
-    if ia[-1] == ia[0] or ib[-1] == ib[0]:                      # (no fingerprint on a side: every pair is empty)
-        return out.fill_(0x7fffffff)
-    d = ta.shape[1]
-    if d <= PROTEIN_MIN_MAX_D and not (_aligned16(ta) and _aligned16(tb)):
-        w = (d + 15) // 16 * 16
-        ta, tb = _rows16(ta, w), _rows16(tb, w)
+    if d <= PROTEIN_MIN_MAX_D:
+        ta, tb = _rows_on_16(ta, tb)
     da, db = _device_int64(ia, dev), _device_int64(ib, dev)
     try:
         _launch(dev, 'dctfp_protein_min', ta.data_ptr(), _ld(ta), da.data_ptr(), npa, tb.data_ptr(), _ld(tb), db.data_ptr(), npb, d,
@@ -348,14 +393,14 @@ COVER_ALL = 0x7ffffffe     # dctfp_protein_cover's largest bound: every row of a
 
 
 def _device_int32(v, n: int, what: str, device) -> torch.Tensor:
-    """``v`` (host values, or a device int32 tensor as it is) as a contiguous device int32 vector of ``n`` entries."""
+    """``v`` (host values, or a device int32 tensor, copied only where it is not contiguous) as a contiguous device int32 vector of
+    ``n`` entries."""
     if isinstance(v, torch.Tensor) and v.device.type == 'cuda':
-        t = v
+        t = v.contiguous()
     else:
         t = torch.as_tensor(np.ascontiguousarray(np.asarray(v, dtype=np.int64).astype(np.int32)), device=device)
-    if t.dtype != torch.int32 or t.dim() != 1 or t.numel() != n or t.device != device:
-        raise ValueError(f'{what} must hold {n} int32 values on the fingerprints\' device')
-    return t.contiguous()
+    _vector(t, torch.int32, device, what, n)
+    return t
 
 
 def protein_cover(a, idx_a, w_a, need_a, b, idx_b, w_b, need_b, bound: int, out: torch.Tensor = None, cap: int = 17000) -> torch.Tensor:
@@ -366,41 +411,21 @@ def protein_cover(a, idx_a, w_a, need_a, b, idx_b, w_b, need_b, bound: int, out:
     fingerprints.  A row is matched when min(L1, ``cap``) <= ``bound``: a bound of ``cap`` or more goes to the kernel as
     ``COVER_ALL``, a negative one matches no row.  ``out`` and the 16-byte padding of rows as in ``protein_min``; rows wider than
     512 bytes raise ValueError: there is no other route (fingerprints are 480 bytes)."""
-    ia, ib = np.asarray(idx_a, dtype=np.int64), np.asarray(idx_b, dtype=np.int64)
-    npa, npb = len(ia) - 1, len(ib) - 1
-    ta, tb = _row_major_int8(a), _row_major_int8(b)
-    _check_pair(ta, tb)
-    _check_prefix(ia, ta.shape[0])
-    _check_prefix(ib, tb.shape[0])
-    dev = ta.device
-    d = ta.shape[1]
+    ta, tb = _rows_view(a), _rows_view(b)
+    ia, ib = _prefix_sides(ta, idx_a, tb, idx_b)
+    npa, npb, dev, d = len(ia) - 1, len(ib) - 1, ta.device, ta.shape[1]
     if d > PROTEIN_MIN_MAX_D:
         raise ValueError(f'protein_cover takes rows of at most {PROTEIN_MIN_MAX_D} bytes, not {d}')
     wa, wb = _device_int32(w_a, ta.shape[0], 'w_a', dev), _device_int32(w_b, tb.shape[0], 'w_b', dev)
     na, nb = _device_int32(need_a, npa, 'need_a', dev), _device_int32(need_b, npb, 'need_b', dev)
-    if out is None:
-        out = torch.empty((npa, npb), dtype=torch.int32, device=dev)
-    elif out.dtype != torch.int32 or tuple(out.shape) != (npa, npb) or out.device != dev or (npb > 1 and out.stride(1) != 1):
-        raise ValueError('out must be an int32 (npa, npb) tensor on the fingerprints\' device with unit column stride')
-    if out.numel() == 0:
+    out, done = _protein_out(out, ia, ib, dev)
+    if done:
         return out
-    if ia[-1] == ia[0] or ib[-1] == ib[0]:                      # (no fingerprint on a side: every pair is empty)
-        return out.fill_(0x7fffffff)
-    if not (_aligned16(ta) and _aligned16(tb)):
-        w = (d + 15) // 16 * 16
-        ta, tb = _rows16(ta, w), _rows16(tb, w)
+    ta, tb = _rows_on_16(ta, tb)
     da, db = _device_int64(ia, dev), _device_int64(ib, dev)
     _launch(dev, 'dctfp_protein_cover', ta.data_ptr(), _ld(ta), da.data_ptr(), npa, wa.data_ptr(), na.data_ptr(), tb.data_ptr(), _ld(tb),
             db.data_ptr(), npb, wb.data_ptr(), nb.data_ptr(), d, COVER_ALL if bound >= cap else max(int(bound), -1), out.data_ptr(), _ld(out))
     return out
-
-
-def _row_major_int8(x) -> torch.Tensor:
-    """A device int8 matrix with unit column stride as it is (a row stride of its own is kept); anything else through
-    ``to_device_int8``."""
-    if isinstance(x, torch.Tensor) and x.dtype == torch.int8 and x.device.type == 'cuda' and x.dim() == 2 and (x.shape[1] <= 1 or x.stride(1) == 1):
-        return x
-    return to_device_int8(x)
 
 
 def threshold_select(dist: torch.Tensor, top: int, bound: int, row_empty=None, col_empty=None, cap: int = 17000):
@@ -504,17 +529,11 @@ def tri_filter(tile: torch.Tensor, row0: int, col0: int, bound: int, row_empty=N
     return m, i.cpu().numpy().astype(np.int64), j.cpu().numpy().astype(np.int64)
 
 
-def _parent_arg(parent: torch.Tensor, device) -> int:
-    if parent.dtype != torch.int32 or parent.dim() != 1 or not parent.is_contiguous() or parent.device != device:
-        raise ValueError('parent must be a contiguous 1-D int32 tensor on the device of the other arguments')
-    return parent.numel()
-
-
 def tri_link(tile: torch.Tensor, row0: int, col0: int, bound: int, parent: torch.Tensor, row_empty=None, col_empty=None, cap: int = 17000):
     """Joins, in the union-find forest ``parent`` (device int32, started as ``torch.arange(n)``), proteins row0 + r and col0 + c
     for every entry of an L1 tile that ``tri_filter_count`` would count (``dctfp_tri_link``).  Nothing comes back: the forest is
     read with ``cluster_labels`` once every tile has been linked."""
-    n_nodes = _parent_arg(parent, tile.device)
+    n_nodes = _vector(parent, torch.int32, tile.device, 'parent')
     n_rows, n_cols, lead, _flags = _tri_filter_args(tile, row0, col0, bound, row_empty, col_empty, cap, n_nodes)
     if n_rows and n_cols:
         _launch(tile.device, 'dctfp_tri_link', *lead, parent.data_ptr(), n_nodes)
@@ -523,10 +542,9 @@ def tri_link(tile: torch.Tensor, row0: int, col0: int, bound: int, parent: torch
 def link_pairs(pi: torch.Tensor, pj: torch.Tensor, parent: torch.Tensor):
     """Joins proteins pi[n] and pj[n] (device int32, ``tri_filter_fill``'s output) in the forest ``parent`` (``dctfp_link_pairs``);
     the kernel skips a pair that names a node outside it."""
-    n_nodes = _parent_arg(parent, pi.device)
-    for t in (pi, pj):
-        if t.dtype != torch.int32 or t.dim() != 1 or t.numel() != pi.numel() or not t.is_contiguous() or t.device != parent.device:
-            raise ValueError('pi / pj must be contiguous int32 device tensors of one length')
+    n_nodes = _vector(parent, torch.int32, pi.device, 'parent')
+    for t, what in ((pi, 'pi'), (pj, 'pj')):
+        _vector(t, torch.int32, parent.device, what, pi.numel())
     if pi.numel() and n_nodes:
         _launch(parent.device, 'dctfp_link_pairs', pi.data_ptr(), pj.data_ptr(), pi.numel(), parent.data_ptr(), n_nodes)
 
@@ -538,9 +556,8 @@ def rows_link(a, a0: int, b, b0: int, owner: torch.Tensor, parent: torch.Tensor,
     comparison in registers -- no distance is stored.  The library checks the shapes; its codes come back as ``DctfpError``."""
     ta, tb = to_device_int8(a), to_device_int8(b)
     _check_pair(ta, tb)
-    n_nodes = _parent_arg(parent, ta.device)
-    if owner.dtype != torch.int32 or owner.dim() != 1 or owner.numel() != n_nodes or not owner.is_contiguous() or owner.device != ta.device:
-        raise ValueError('owner must be a contiguous int32 device tensor with one entry per node of parent')
+    n_nodes = _vector(parent, torch.int32, ta.device, 'parent')
+    _vector(owner, torch.int32, ta.device, 'owner (one entry per node of parent)', n_nodes)
     flags = _empty_flags(skip, n_nodes, ta.device)
     if ta.shape[0] == 0 or tb.shape[0] == 0:
         return
@@ -548,19 +565,12 @@ def rows_link(a, a0: int, b, b0: int, owner: torch.Tensor, parent: torch.Tensor,
             ta.shape[1], owner.data_ptr(), _ptr(flags), int(cap), int(bound), parent.data_ptr(), n_nodes)
 
 
-def _rows_view(t) -> torch.Tensor:
-    """``to_device_int8`` that leaves a device int8 view with unit column stride as it is (any row stride, any alignment)."""
-    if isinstance(t, torch.Tensor) and t.dtype == torch.int8 and t.device.type == 'cuda' and t.dim() == 2 and (t.shape[1] <= 1 or t.stride(1) == 1) \
-            and (t.shape[0] <= 1 or t.stride(0) >= t.shape[1]):
-        return t
-    return to_device_int8(t)
-
-
 def _row_map(m, n: int, device, what: str):
     if m is None:
         return None
-    if not isinstance(m, torch.Tensor) or m.dtype != torch.int32 or m.dim() != 1 or m.numel() != n or not m.is_contiguous() or m.device != device:
-        raise ValueError(f'{what} must be a contiguous int32 device tensor with one entry per row')
+    if not isinstance(m, torch.Tensor):                         # (the one argument that is refused by name where it is a host array)
+        raise ValueError(f'{what} must be a device tensor')
+    _vector(m, torch.int32, device, f'{what} (one entry per row)', n)
     return m
 
 
@@ -572,8 +582,7 @@ def rows_assign(a, b, assign: torch.Tensor, bound: int, value_a=None, slot_b=Non
     and a negative value; the library checks the shapes, its codes come back as ``DctfpError``."""
     ta, tb = _rows_view(a), _rows_view(b)
     _check_pair(ta, tb)
-    if assign.dtype != torch.int32 or assign.dim() != 1 or not assign.is_contiguous() or assign.device != ta.device:
-        raise ValueError('assign must be a contiguous 1-D int32 tensor on the device of the rows')
+    _vector(assign, torch.int32, ta.device, 'assign')
     va = _row_map(value_a, ta.shape[0], ta.device, 'value_a')
     sb = _row_map(slot_b, tb.shape[0], ta.device, 'slot_b')
     if ta.shape[0] == 0 or tb.shape[0] == 0 or assign.numel() == 0:
@@ -587,7 +596,7 @@ def cluster_labels(parent: torch.Tensor) -> torch.Tensor:
     (``dctfp_cluster_labels``).  ``parent`` stays a forest of the same components (flattened): linking may go on."""
     if parent.device.type != 'cuda':
         raise ValueError('parent must be a device tensor')
-    n_nodes = _parent_arg(parent, parent.device)
+    n_nodes = _vector(parent, torch.int32, parent.device, 'parent')
     labels = torch.empty(n_nodes, dtype=torch.int32, device=parent.device)
     if n_nodes:
         _launch(parent.device, 'dctfp_cluster_labels', parent.data_ptr(), n_nodes, labels.data_ptr())
@@ -616,9 +625,8 @@ class TreeState:
 
     def arrays(self, device) -> int:
         n = self.comp.numel()
-        for t, dtype in ((self.comp, torch.int32), (self.parent, torch.int32), (self.best, torch.int64)):
-            if t.dtype != dtype or t.dim() != 1 or not t.is_contiguous() or t.device != device or t.numel() != n:
-                raise ValueError('comp / parent (int32) and best (int64) must be contiguous 1-D tensors of one length on the device of the other arguments')
+        for t, dtype, what in ((self.comp, torch.int32, 'comp'), (self.parent, torch.int32, 'parent'), (self.best, torch.int64, 'best')):
+            _vector(t, dtype, device, what, n)
         return n
 
     def edges(self):
@@ -643,9 +651,8 @@ def tree_hook(ts: TreeState):
     afterwards.  ``ts.comp`` is the caller's to renew: ``ts.comp = cluster_labels(ts.parent)``."""
     n_nodes = ts.arrays(ts.comp.device)
     edges = (ts.edge_i, ts.edge_j, ts.edge_key)
-    for t in edges:
-        if t.dtype != torch.int32 or t.dim() != 1 or not t.is_contiguous() or t.device != ts.comp.device or t.numel() != ts.edge_i.numel():
-            raise ValueError('the edge arrays must be contiguous int32 device tensors of one length')
+    for t, what in zip(edges, ('edge_i', 'edge_j', 'edge_key')):
+        _vector(t, torch.int32, ts.comp.device, what, ts.edge_i.numel())
     if ts.counter.dtype != torch.int32 or ts.counter.numel() != 1 or ts.counter.device != ts.comp.device:
         raise ValueError('counter must be one int32 on the device')
     if n_nodes:
@@ -669,8 +676,7 @@ def _linkage_args(mat: torch.Tensor, size: torch.Tensor, arrays):
     if n > LINKAGE_MAX_N:
         raise ValueError(f'at most {LINKAGE_MAX_N} nodes')
     for t in (size, *arrays):
-        if t.dtype != torch.int32 or t.dim() != 1 or not t.is_contiguous() or t.device != mat.device:
-            raise ValueError('size and the arrays beside it must be contiguous 1-D int32 tensors on the device of the matrix')
+        _vector(t, torch.int32, mat.device, 'size and each array beside it')
     return n, (mat.data_ptr(), int(mat.dtype == torch.int64), n, mat.stride(0) if mat.shape[0] > 1 else max(n, 1))
 
 
@@ -718,10 +724,7 @@ class BestState:
 
     def arrays(self, device):
         """(n_a, n_b), the arrays checked."""
-        for t in (self.best_row, self.best_col):
-            if t.dtype != torch.int64 or t.dim() != 1 or not t.is_contiguous() or t.device != device:
-                raise ValueError('best_row / best_col must be contiguous 1-D int64 tensors on the device of the other arguments')
-        return self.best_row.numel(), self.best_col.numel()
+        return _vector(self.best_row, torch.int64, device, 'best_row'), _vector(self.best_col, torch.int64, device, 'best_col')
 
     def hits(self):
         """((index, key) per protein of A, (index, key) per protein of B) as int64 numpy arrays: the best hit on the other side and
@@ -795,8 +798,7 @@ def _node_arrays(tile: torch.Tensor, arrays) -> int:
     length on the tile's device."""
     n_nodes = arrays[0][0].numel()
     for t, dtype, what in arrays:
-        if t.dtype != dtype or t.dim() != 1 or not t.is_contiguous() or t.device != tile.device or t.numel() != n_nodes:
-            raise ValueError(f'{what} must be a contiguous 1-D {dtype} tensor on the device of the tile, one entry per protein')
+        _vector(t, dtype, tile.device, f'{what} (one entry per protein)', n_nodes)
     return n_nodes
 
 
@@ -916,9 +918,8 @@ class GreedyState:
         return new
 
     def arrays(self, device) -> int:
-        for t in (self.assign, self.state, self.blocked):
-            if t.dtype != torch.int32 or t.dim() != 1 or not t.is_contiguous() or t.device != device or t.numel() != self.assign.numel():
-                raise ValueError('assign / state / blocked must be contiguous 1-D int32 tensors of one length on the device of the other arguments')
+        for t, what in ((self.assign, 'assign'), (self.state, 'state'), (self.blocked, 'blocked')):
+            _vector(t, torch.int32, device, what, self.assign.numel())
         return self.assign.numel()
 
 
@@ -949,9 +950,8 @@ def greedy_pairs_mark(pi: torch.Tensor, pj: torch.Tensor, gs: GreedyState, range
     """The mark launch of a round from pairs (pi[n], pj[n]) (device int32, ``tri_filter_fill``'s output; ``dctfp_greedy_pairs_mark``);
     the kernel skips a pair that names a node outside the state."""
     n_nodes = gs.arrays(pi.device)
-    for t in (pi, pj):
-        if t.dtype != torch.int32 or t.dim() != 1 or t.numel() != pi.numel() or not t.is_contiguous() or t.device != gs.assign.device:
-            raise ValueError('pi / pj must be contiguous int32 device tensors of one length')
+    for t, what in ((pi, 'pi'), (pj, 'pj')):
+        _vector(t, torch.int32, gs.assign.device, what, pi.numel())
     if not 0 <= range_end <= n_nodes:
         raise IndexError('range outside the nodes')
     if pi.numel() and n_nodes:
@@ -986,8 +986,8 @@ def sim_lines(mn: torch.Tensor, last: torch.Tensor, row0: int, col0: int, ids: L
         raise ValueError('mn / last must be int32 tiles of one shape, one row base per row')
     if not (mn.is_contiguous() and last.is_contiguous()):
         raise ValueError('mn / last must be contiguous')
-    if table.dtype != torch.uint8 or table.numel() != 2 * 17002 * 5 or out.dtype != torch.uint8 or not out.is_contiguous():
-        raise ValueError('table must be uint8 (2, 17002, 5) and out a contiguous uint8 buffer')
+    _score_table(table)
+    _text_buffer(out, out.device)
     if n_rows == 0 or n_cols == 0:
         return
     if row0 < 0 or col0 < 0 or row0 + n_rows > n or col0 + n_cols > n:
@@ -1029,13 +1029,11 @@ def pair_lines(pi: torch.Tensor, pj: torch.Tensor, mn: torch.Tensor, last: torch
     label outside ``labels`` is skipped too."""
     n = pi.numel()
     cols = (pi, pj, mn, last) + ((la, lb) if labels is not None else ())
-    for t in cols:
-        if t.dtype != torch.int32 or t.numel() != n or not t.is_contiguous() or t.device != out.device:
-            raise ValueError(f'pi / pj / mn / last{" / la / lb" if labels is not None else ""} must be contiguous int32 device tensors of one length')
-    if line_off.dtype != torch.int64 or line_off.numel() < n or not line_off.is_contiguous() or line_off.device != out.device:
-        raise ValueError('line_off must be a contiguous int64 device tensor with an entry per line')
-    if table.dtype != torch.uint8 or table.numel() != 2 * 17002 * 5 or out.dtype != torch.uint8 or not out.is_contiguous():
-        raise ValueError('table must be uint8 (2, 17002, 5) and out a contiguous uint8 buffer')
+    for t, what in zip(cols, ('pi', 'pj', 'mn', 'last', 'la', 'lb')):
+        _vector(t, torch.int32, out.device, what, n, flat=False)
+    _line_offsets(line_off, n, out.device)
+    _score_table(table)
+    _text_buffer(out, out.device)
     if n == 0:
         return
     tail = (table.data_ptr(), line_off.data_ptr(), out.data_ptr(), out.numel())
@@ -1062,18 +1060,13 @@ def pair_domain_lines(pi: torch.Tensor, pj: torch.Tensor, mn: torch.Tensor, last
 def _pair_map_args(pi, pj, mn, last, la, lb, ids: LineIds, labels: LineIds, table, first_row, row_off, row_l1, row_arg, bound: int):
     """The checked arguments the two passes of ``dctfp_pair_map_lines`` share, as (head, tail): the line buffer goes between them."""
     n, dev = pi.numel(), pi.device
-    for t in (pi, pj, mn, last, la, lb):
-        if t.dtype != torch.int32 or t.numel() != n or not t.is_contiguous() or t.device != dev:
-            raise ValueError('pi / pj / mn / last / la / lb must be contiguous int32 device tensors of one length')
-    if table.dtype != torch.uint8 or table.numel() != 2 * 17002 * 5 or not table.is_contiguous():
-        raise ValueError('table must be uint8 (2, 17002, 5)')
-    if row_off.dtype != torch.int64 or row_off.numel() != n + 1 or not row_off.is_contiguous() or row_off.device != dev:
-        raise ValueError('row_off must be a contiguous int64 device tensor with an entry per line and one more')
-    if first_row.dtype != torch.int64 or first_row.numel() != len(ids.off) or not first_row.is_contiguous() or first_row.device != dev:
-        raise ValueError('first_row must be a contiguous int64 device tensor with an entry per protein and one more')
-    for t in (row_l1, row_arg):
-        if t.dtype != torch.int32 or t.numel() != row_l1.numel() or not t.is_contiguous() or t.device != dev:
-            raise ValueError('row_l1 / row_arg must be contiguous int32 device tensors of one length')
+    for t, what in zip((pi, pj, mn, last, la, lb), ('pi', 'pj', 'mn', 'last', 'la', 'lb')):
+        _vector(t, torch.int32, dev, what, n, flat=False)
+    _score_table(table)
+    _vector(row_off, torch.int64, dev, 'row_off (an entry per line and one more)', n + 1, flat=False)
+    _vector(first_row, torch.int64, dev, 'first_row (an entry per protein and one more)', len(ids.off), flat=False)
+    for t, what in ((row_l1, 'row_l1'), (row_arg, 'row_arg')):
+        _vector(t, torch.int32, dev, what, row_l1.numel(), flat=False)
     if not -1 <= int(bound) < 17000:
         raise ValueError('the bound of a map is an L1 of similarity above 0: -1 .. 16999')
     head = (n, pi.data_ptr(), pj.data_ptr(), mn.data_ptr(), last.data_ptr(), la.data_ptr(), lb.data_ptr(), ids.bytes_dev.data_ptr(),
@@ -1102,10 +1095,8 @@ def pair_map_lines(pi, pj, mn, last, la, lb, ids: LineIds, labels: LineIds, tabl
     ``pair_row_best_device`` of the pairs; ``first_row``: device int64, the prefix array of the file whose rows ``labels`` names;
     ``bound``: a row is matched when its L1 is at most this.  ``line_off``: the prefix sum of ``pair_map_line_lengths``."""
     head, tail = _pair_map_args(pi, pj, mn, last, la, lb, ids, labels, table, first_row, row_off, row_l1, row_arg, bound)
-    if line_off.dtype != torch.int64 or line_off.numel() < pi.numel() or not line_off.is_contiguous() or line_off.device != out.device:
-        raise ValueError('line_off must be a contiguous int64 device tensor with an entry per line')
-    if out.dtype != torch.uint8 or not out.is_contiguous() or out.device != pi.device:
-        raise ValueError('out must be a contiguous uint8 device buffer')
+    _line_offsets(line_off, pi.numel(), out.device)
+    _text_buffer(out, pi.device)
     if pi.numel() and out.numel():
         _launch(out.device, 'dctfp_pair_map_lines', *head, line_off.data_ptr(), out.data_ptr(), out.numel(), *tail, None)
 
@@ -1128,6 +1119,14 @@ def _rows16(t: torch.Tensor, w: int) -> torch.Tensor:
     return out
 
 
+def _rows_on_16(ta: torch.Tensor, tb: torch.Tensor):
+    """Both matrices with their rows on 16-byte boundaries: as they are, or both as padded copies of one width."""
+    if _aligned16(ta) and _aligned16(tb):
+        return ta, tb
+    w = (ta.shape[1] + 15) // 16 * 16
+    return _rows16(ta, w), _rows16(tb, w)
+
+
 def l1_knn_device(q, db, k: int, col0: int = 0):
     """(values, indices): device int32 (nq, min(k, nb)) -- each query row's k nearest database rows by L1, ascending, ties to the
     lower row, ``col0`` added to the indices (``dctfp_l1_knn``: distances and selection in one kernel, no distance matrix).
@@ -1142,9 +1141,7 @@ def l1_knn_device(q, db, k: int, col0: int = 0):
     if k > KNN_MAX_K or d > KNN_MAX_D:
         v, i = row_select(l1_matrix(tq, tb), k)
         return (torch.as_tensor(v.astype(np.int32), device=dev), torch.as_tensor((i + col0).astype(np.int32), device=dev))
-    if not (_aligned16(tq) and _aligned16(tb)):
-        w = (d + 15) // 16 * 16
-        tq, tb = _rows16(tq, w), _rows16(tb, w)
+    tq, tb = _rows_on_16(tq, tb)
     val = torch.empty((nq, k), dtype=torch.int32, device=dev)
     idx = torch.empty((nq, k), dtype=torch.int32, device=dev)
     # query rows per call sized by the scratch they take: 2 k-lists of k 8-byte keys per (row, database slice), and with several
