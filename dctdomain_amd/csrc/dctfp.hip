@@ -380,6 +380,9 @@ struct dctfp_ctx {
     int64_t last_path = 0;  // which kernels the last dctfp_quantize launched: 1 = stage A + stage B, 2 = walk kernel
     int64_t last_gen_fused = 0;  // ... and whether that was the general walk kernel streaming fused walks (parts + whole protein)
     int64_t last_walk_groups = 0;  // ... or walk_ab_kernel: its build's 16-column groups (5: m <= 80, 6: 80 < m <= 96), 0 = another kernel
+    // ... or the two kernels: the builds of the last chunk's stage A and stage B as their launchers named them (launch.h:
+    // stage_a_word and the stage-B words), 0 = another route
+    int64_t last_stage_a = 0, last_stage_b = 0;
     int64_t opt_gen_fuse = 1;    // "gen_fuse": fused walks through the general walk kernel (n <= 5); 0 = the two kernels, as through round 4
     int64_t walk_launches = 0;  // walk-kernel launches so far (a call split at a giant domain ends on the two-kernel path)
     int64_t last_knn_slices = 0;  // database slices that owned a column in the last dctfp_l1_knn launch
@@ -877,6 +880,8 @@ int dctfp_get_option(dctfp_ctx* ctx, const char* name, int64_t* value) try {
     else if (n == "last_path") *value = ctx->last_path;
     else if (n == "last_gen_fused") *value = ctx->last_gen_fused;
     else if (n == "last_walk_groups") *value = ctx->last_walk_groups;
+    else if (n == "last_stage_a") *value = ctx->last_stage_a;
+    else if (n == "last_stage_b") *value = ctx->last_stage_b;
     else if (n == "gen_fuse") *value = ctx->opt_gen_fuse;
     else if (n == "walk_launches") *value = ctx->walk_launches;
     else if (n == "last_knn_slices") *value = ctx->last_knn_slices;
@@ -1576,6 +1581,19 @@ bool split_rows_over_workgroups(const dctfp_ctx* ctx, const dctfp_layer& g, cons
            avg_rows >= 128 && max_len <= (1u << 24);
 }
 
+// The row-split stage A and the slab stage B: launched and named (launch.h: "last_stage_a" / "last_stage_b") from one set of
+// template arguments.
+template <typename T, int N, int VEC, int WAVES, int UNROLL, typename... Args>
+void launch_a_split(int64_t* built, unsigned grid, hipStream_t stream, Args... args) {
+    hipLaunchKernelGGL((stage_a_split_kernel<T, N, VEC, WAVES, UNROLL>), dim3(grid), dim3(WAVES * 64), 0, stream, args...);
+    *built = stage_a_word<T, N, VEC, WAVES, UNROLL, false>(false, true);
+}
+template <bool FROM_SPLIT, typename... Args>
+void launch_b_slab(int64_t* built, dim3 grid, hipStream_t stream, Args... args) {
+    hipLaunchKernelGGL((stage_b_slab_kernel<FROM_SPLIT>), grid, dim3(256), 0, stream, args...);
+    *built = FROM_SPLIT ? kStageBSlabFromSplit : kStageBSlab;
+}
+
 // The chunk loop.  Stage A of chunk c runs on the caller's stream, stage B of it on the context's side
 // stream, so the MFMA-bound stage B of one chunk overlaps the HBM-bound stage A of the next.  `d`: the tables as the kernels
 // read them.  `keep_buffers`: the caller waits for the stream before anything else can touch the context (see below).
@@ -1605,6 +1623,7 @@ int run_two_kernels(dctfp_ctx* ctx, const dctfp_layer& g, const Route& route, co
         const int n_kslabs = (g.n_cols + kSlabChannels - 1) / kSlabChannels;
         auto zpart_bytes = [&](int64_t jobs_here) { return (size_t)jobs_here * n_kslabs * n * m * sizeof(double); };
         double* zpart = nullptr;
+        int64_t a_built = 0, b_built = 0, combined = 0;  // what the launchers say they launched
         if (split_rows_over_workgroups(ctx, g, route, jn * n_slabs, tk.avg_rows, max_len)) {
             int64_t want_chunks = std::min<int64_t>(32, std::max<int64_t>(2, 384 / (jn * n_slabs)));
             uint32_t chunk_rows = (uint32_t)((max_len + want_chunks - 1) / want_chunks);
@@ -1612,23 +1631,24 @@ int run_two_kernels(dctfp_ctx* ctx, const dctfp_layer& g, const Route& route, co
             const int n_chunks = (int)((max_len + chunk_rows - 1) / chunk_rows);
             const size_t partial_bytes = (size_t)jn * n_chunks * nk * ldy * sizeof(double);
             RC_TRY(ctx->split_ws.ensure(partial_bytes + (small_b ? zpart_bytes(jn) : 0)));
-            hipLaunchKernelGGL((stage_a_split_kernel<float, 3, 4, 8, 4>), dim3((unsigned)(jn * n_chunks * n_slabs)), dim3(512), 0, stream,
-                               d.joba + j0, d.pieces, (double*)ctx->split_ws.p, n_chunks, chunk_rows, g.n_cols, g.ld, ldy, n_slabs);
+            launch_a_split<float, 3, 4, 8, 4>(&a_built, (unsigned)(jn * n_chunks * n_slabs), stream, d.joba + j0, d.pieces,
+                                              (double*)ctx->split_ws.p, n_chunks, chunk_rows, g.n_cols, g.ld, ldy, n_slabs);
             HIP_TRY(hipGetLastError());
             if (small_b) {  // the slabs of stage B add the chunks and scale their channels themselves
                 zpart = (double*)((char*)ctx->split_ws.p + partial_bytes);
-                hipLaunchKernelGGL((stage_b_slab_kernel<true>), dim3((unsigned)n_kslabs, (unsigned)jn), dim3(256), 0, stream,
-                                   (const double*)nullptr, ldy, (const double*)ctx->split_ws.p, n_chunks, inv3, ctx->degenerate,
-                                   g.n_cols, (const double*)st->dev, st->cp, n, m, zpart);
+                launch_b_slab<true>(&b_built, dim3((unsigned)n_kslabs, (unsigned)jn), stream, (const double*)nullptr, ldy,
+                                    (const double*)ctx->split_ws.p, n_chunks, inv3, ctx->degenerate, g.n_cols, (const double*)st->dev,
+                                    st->cp, n, m, zpart);
             } else {
                 hipLaunchKernelGGL((stage_a_combine_kernel<3>), dim3((unsigned)((ldy + 255) / 256), (unsigned)jn), dim3(256), 0, stream,
                                    (const double*)ctx->split_ws.p, n_chunks, yprime, (int64_t)job_bytes, packed ? 1 : 0, g.n_cols, ldy,
                                    inv3, ctx->degenerate);
+                combined = kStageBCombine | (packed ? kStageBCombinePacked : 0);
             }
             HIP_TRY(hipGetLastError());
         } else {
             AParams ap{d.joba + j0, d.walks + ck.w0, route.fuse, d.pieces, ctx->degenerate, yprime, (int64_t)job_bytes, packed ? 1 : 0,
-                       g.n_cols, g.ld, ldy, n_slabs, (unsigned)(ck.wn * n_slabs), stream};
+                       g.n_cols, g.ld, ldy, n_slabs, (unsigned)(ck.wn * n_slabs), stream, &a_built};
             launch_a(ap, g.dtype, route.vec, n, stage_a_waves(ctx, tk.avg_rows, ck.wn * n_slabs, route.vec));
         }
         HIP_TRY(hipGetLastError());
@@ -1641,14 +1661,14 @@ int run_two_kernels(dctfp_ctx* ctx, const dctfp_layer& g, const Route& route, co
         if (!small_b) {
             const int64_t rows = jn * n;
             launch_b_mfma(st->cp / 16, packed, (unsigned)((rows + kBWaves * 16 - 1) / (kBWaves * 16)), sb, yprime, (int64_t)job_bytes, rows, ldy,
-                          st->dev, d.jobb + j0, n, m, out);
+                          st->dev, d.jobb + j0, n, m, out, &b_built);
         } else {
             if (!zpart) {  // stage A wrote Y' (no row split): the slabs read it
                 RC_TRY(ctx->split_ws.ensure(zpart_bytes(jn)));
                 zpart = (double*)ctx->split_ws.p;
-                hipLaunchKernelGGL((stage_b_slab_kernel<false>), dim3((unsigned)n_kslabs, (unsigned)jn), dim3(256), 0, sb,
-                                   (const double*)yprime, ldy, (const double*)nullptr, 0, inv3, ctx->degenerate, g.n_cols,
-                                   (const double*)st->dev, st->cp, n, m, zpart);
+                launch_b_slab<false>(&b_built, dim3((unsigned)n_kslabs, (unsigned)jn), sb, (const double*)yprime, ldy,
+                                     (const double*)nullptr, 0, inv3, ctx->degenerate, g.n_cols, (const double*)st->dev, st->cp, n, m,
+                                     zpart);
                 HIP_TRY(hipGetLastError());
             }
             hipLaunchKernelGGL(stage_b_finish_kernel, dim3((unsigned)jn), dim3(256), 0, sb, (const double*)zpart, n_kslabs, d.jobb + j0, n, m, out);
@@ -1656,6 +1676,8 @@ int run_two_kernels(dctfp_ctx* ctx, const dctfp_layer& g, const Route& route, co
         HIP_TRY(hipGetLastError());
         RC_TRY(prof_end(ep, sb));
         if (side) HIP_TRY(hipEventRecord(ctx->ev_b[slot], sb));
+        ctx->last_stage_a = a_built;
+        ctx->last_stage_b = b_built | combined;
         ++c;
     }
     RC_TRY(fork.join());  // the caller's stream continues only after every stage B of this group
@@ -1769,6 +1791,7 @@ int quantize_impl(dctfp_ctx* ctx, const dctfp_layer* layers, int32_t n_layers, i
         const int64_t n_jobs = (int64_t)ng * n_domains;
         // (16 bytes per lane where every row of every sequence allows it)
         const Route route = choose_route(ctx, g, rows_aligned16(group, ng, n_data, src ? nullptr : seq_rows), dt.max_len, n_jobs, fg.n_groups > 0);
+        ctx->last_stage_a = ctx->last_stage_b = 0;  // (run_two_kernels writes them)
 
         const TableLayout lay(n_jobs, ng, n_pieces, n_domains);
         TableLease tables(ctx->ring, stream);

@@ -7,6 +7,7 @@ void launch_a_build(const AParams& p) {
     hipLaunchKernelGGL((stage_a_kernel<T, N, VEC, WAVES, UNROLL, FUSED>), dim3(p.grid), dim3(WAVES * 64), 0, p.stream,
                        p.jobs, p.walks, p.pieces, p.yprime, p.job_bytes, p.packed, p.n_cols, p.ld, p.ldy, p.n_slabs,
                        inv, p.degenerate);
+    *p.built = stage_a_word<T, N, VEC, WAVES, UNROLL, FUSED>(p.packed != 0, false);
 }
 
 // 4 rows in flight, plain and fused

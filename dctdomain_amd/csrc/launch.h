@@ -61,6 +61,23 @@ inline InvTab<N> make_inv() {
     return t;
 }
 
+// What the options "last_stage_a" / "last_stage_b" read (include/dctfp.h has the layout): one byte per field, filled in by
+// whoever launches from the template arguments of the instantiation it names -- never from what the dispatcher asked for.
+template <typename T> constexpr int64_t storage_code();
+template <> constexpr int64_t storage_code<float>() { return DCTFP_F32 + 1; }
+template <> constexpr int64_t storage_code<double>() { return DCTFP_F64 + 1; }
+template <> constexpr int64_t storage_code<_Float16>() { return DCTFP_F16 + 1; }
+template <> constexpr int64_t storage_code<bf16_t>() { return DCTFP_BF16 + 1; }
+template <typename T, int N, int VEC, int WAVES, int UNROLL, bool FUSED>
+constexpr int64_t stage_a_word(bool packed, bool split) {
+    return storage_code<T>() | (int64_t)N << 8 | (int64_t)VEC << 16 | (int64_t)WAVES << 24 | (int64_t)UNROLL << 32 |
+           (int64_t)((FUSED ? 1 : 0) | (packed ? 2 : 0) | (split ? 4 : 0)) << 40;
+}
+constexpr int64_t kStageBMfma = 1, kStageBSlab = 2, kStageBSlabFromSplit = 3;  // "last_stage_b": form ...
+constexpr int64_t kStageBPacked = 1 << 16, kStageBCombine = 1 << 17, kStageBCombinePacked = 1 << 18;  // ... and flags
+template <int NT, bool PACKED>
+constexpr int64_t stage_b_mfma_word() { return kStageBMfma | (int64_t)NT << 8 | (PACKED ? kStageBPacked : 0); }
+
 struct AParams {
     const JobA* jobs;
     const Walk* walks;
@@ -76,6 +93,7 @@ struct AParams {
     int n_slabs;
     unsigned grid;
     hipStream_t stream;
+    int64_t* built;  // the launcher's stage_a_word
 };
 
 struct WParams {
@@ -133,8 +151,9 @@ void launch_a_f64(const AParams& p, int vec, int n, int waves);
 void launch_a_f16(const AParams& p, int vec, int n, int waves);
 void launch_a_bf16(const AParams& p, int vec, int n, int waves);
 // stage B on the matrix pipe (k_stage_b.hip)
+// (*built: the stage_b_mfma_word of the instantiation that was launched)
 void launch_b_mfma(int nt, bool packed, unsigned grid, hipStream_t s, const char* yp, int64_t job_bytes, int64_t rows,
-                   int ldy, const double* st, const JobB* jobs, int n, int m, int8_t* out);
+                   int ldy, const double* st, const JobB* jobs, int n, int m, int8_t* out, int64_t* built);
 // the walk kernels (k_walk.hip, k_gen.hip)
 int launch_walk(const WParams& p, int dtype, int s, bool fused, LaunchError* err);
 int launch_gen(const GParams& p, int dtype, int vec, int n, LaunchError* err);

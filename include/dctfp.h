@@ -829,6 +829,16 @@ int dctfp_crash_handler(int enable);
  *                  stage A -> scratch -> stage B otherwise.
  *                  1 = always the two-kernel path; 2 = the walk kernel wherever its shapes allow (any number of jobs)
  *   "last_path"    read only: which kernels the last dctfp_quantize launched last (1 = two kernels, 2 = walk kernel)
+ *   "last_stage_a" read only: the stage-A build the two-kernel path launched last (the last chunk of the last layer group
+ *                  of the last dctfp_quantize), written by its launcher from the template arguments of the instantiation;
+ *                  0 = that group took another route (walk kernel, general walk kernel, zero fill).  One byte per field:
+ *                  byte 0 storage type (DCTFP_F32 .. DCTFP_BF16, plus 1), byte 1 N (kept rows), byte 2 VEC (channels per
+ *                  lane), byte 3 WAVES, byte 4 UNROLL (rows in flight), byte 5 flags: 1 = FUSED build, 2 = Y' packed,
+ *                  4 = split (stage_a_split_kernel ran instead: float32, N 3, VEC 4, WAVES 8, UNROLL 4, not fused)
+ *   "last_stage_b" read only: ... and its stage B.  Byte 0 form: 1 = MFMA kernel, 2 = slab kernel reading Y', 3 = slab
+ *                  kernel reading the row-split partial sums; byte 1 NT (16-column tiles of the MFMA build, 1 .. 8; 0 for
+ *                  the slab forms); byte 2 flags: 1 = PACKED MFMA build, 2 = stage_a_combine_kernel ran before it,
+ *                  4 = ... writing packed Y'.  0 as for "last_stage_a"
  *   "walk_launches" read only: walk-kernel launches of this context so far
  *   "last_knn_slices" read only: database slices that owned a column in the last dctfp_l1_knn launch (1: no merge kernels)
  *   "knn_calls"    read only: dctfp_l1_knn launches of this context so far

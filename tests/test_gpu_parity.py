@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 
 import golden_util as gu
+import stage_ladder as sl
 from oracle import dct_oracle as orc
 from recipes import make_input
 
@@ -821,6 +822,10 @@ def test_one_protein_per_call_bit_exact(dd):
         for embed in ({i: torch.from_numpy(x).cuda() for i, x in enumerate(layers)}, {i: x for i, x in enumerate(layers)}):
             fp = dd.Fingerprint(pid=f'small{rep}', seq='A' * L, embed=embed, domains=list(doms))
             fp.quantize(list(qdim))
+            if (L, D) == (500, 1280) and torch.is_tensor(embed[0]):
+                # 8 jobs x 5 slabs: what split_rows_over_workgroups and "small_b_jobs" promise for such a call
+                assert sl.decode_stage_a(ctx.get_option('last_stage_a')) == sl.StageA('f32', 3, 4, 8, 4, False, False, True)
+                assert sl.decode_stage_b(ctx.get_option('last_stage_b')) == sl.StageB(sl.SLAB_FROM_SPLIT, 0, False, False, False)
             assert list(fp.quants) == list(want)
             for key in want:
                 np.testing.assert_array_equal(fp.quants[key], want[key], err_msg=f'L={L} D={D} {qdim} {key}')
