@@ -36,14 +36,15 @@ def _stale(target: str, sources) -> bool:
 EXPERIMENTS_LIB_PATH = os.path.join(PKG_DIR, 'libdctfp_experiments.so')
 
 
-#: translation units of libdctfp.so: the host side of the C ABI, and one unit per kernel family so that the device code
-#: compiles side by side (the stage-A instantiations alone are a third of it).  `twin` = units that differ in
-#: libdctfp_experiments.so (-DDCTFP_EXPERIMENTS: option names); the others are compiled once and linked into both libraries.
-UNITS = ['dctfp.hip', 'k_walk.hip', 'k_gen.hip', 'k_reccut.hip', 'k_search.hip', 'k_protein.hip', 'k_query.hip', 'k_filter.hip', 'k_cluster.hip', 'k_greedy.hip', 'k_assign.hip', 'k_tree.hip', 'k_linkage.hip', 'k_best.hip', 'k_medoid.hip', 'k_density.hip', 'k_auc.hip', 'k_hist.hip', 'k_moments.hip', 'k_map.hip', 'k_stage_b.hip',
+#: translation units of libdctfp.so: the two host units of the C ABI (dctfp.hip: the context and the fingerprint path;
+#: dctfp_sim.hip: the stateless dct-sim / query_db exports), and one unit per kernel family so that the device code compiles
+#: side by side (the stage-A instantiations alone are a third of it).  `twin` = units that differ in libdctfp_experiments.so
+#: (-DDCTFP_EXPERIMENTS: option names); the others are compiled once and linked into both libraries.
+UNITS = ['dctfp.hip', 'dctfp_sim.hip', 'k_walk.hip', 'k_gen.hip', 'k_reccut.hip', 'k_search.hip', 'k_protein.hip', 'k_query.hip', 'k_filter.hip', 'k_cluster.hip', 'k_greedy.hip', 'k_assign.hip', 'k_tree.hip', 'k_linkage.hip', 'k_best.hip', 'k_medoid.hip', 'k_density.hip', 'k_auc.hip', 'k_hist.hip', 'k_moments.hip', 'k_map.hip', 'k_stage_b.hip',
          'k_stage_a_f32.hip', 'k_stage_a_f64.hip', 'k_stage_a_f16.hip', 'k_stage_a_bf16.hip']
 TWIN_UNITS = ('dctfp.hip',)
 HEADERS = [os.path.join(CSRC, 'kernels.hip.h'), os.path.join(CSRC, 'launch.h'), os.path.join(ROOT, 'include', 'dctfp.h'),
-           os.path.join(ROOT, 'include', 'dctfp_linkage.h'),
+           os.path.join(ROOT, 'include', 'dctfp_linkage.h'), os.path.join(CSRC, 'dctfp_host.h'),
            os.path.join(CSRC, 'reccut_kernel.hip.h'), os.path.join(CSRC, 'k_stage_a.inc'), os.path.join(CSRC, 'tri_walk.hip.h'), os.path.join(CSRC, 'sad_tile.hip.h'),
            os.path.join(CSRC, 'tri_tile.hip.h'), os.path.join(CSRC, 'band_walk.hip.h'), os.path.join(CSRC, 'union_find.hip.h')]
 OBJ_DIR = os.path.join(ROOT, 'build', 'dctfp_objs')

@@ -570,7 +570,7 @@ const Export* find_export(const char* name) {
     abort();
 }
 
-// ---- (b) the limit table: include/dctfp.h's comment of the export and the message in dctfp.hip say the same number
+// ---- (b) the limit table: include/dctfp.h's comment of the export and the message in dctfp_sim.hip say the same number
 constexpr int64_t kPairsMax = (int64_t)(0xffffffffu / 256) * 4;      // four pairs to a 256-thread workgroup, gridDim.x * blockDim.x < 2^32
 constexpr int64_t kLinesMax = (int64_t)(0xffffffffu / 256) * 16;     // sixteen lanes to a line: sixteen lines to a 256-thread workgroup
 constexpr int64_t kThreadsMax = (int64_t)(0xffffffffu / 256) * 256;  // one thread to an item, 256-thread workgroups

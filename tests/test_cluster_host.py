@@ -339,7 +339,7 @@ def test_the_tile_description_is_defined_once_and_checked_in_one_place():
         assert not re.search(r'int64_t row0, int64_t col0', heads), unit
         for kernel in names:
             assert ' %s(const TriTile t, ' % kernel in heads, kernel
-    host = code['dctfp.hip']
+    host = code['dctfp_sim.hip']
     exports = ('dctfp_tri_filter_count', 'dctfp_tri_filter_fill', 'dctfp_tri_link', 'dctfp_greedy_tri_mark', 'dctfp_tri_nearest')
     assert host.count('check_tri_tile(') == 1 + len(exports) and 'static int check_tri_tile(const char* name, const TriTile& t)' in host
     for name in exports:
@@ -425,7 +425,7 @@ def test_the_band_walk_is_defined_once_and_five_kernels_are_passes_of_it():
     assert re.findall(r'pass\.(\w+)\(', body) == ['side', 'side', 'entry', 'row_out', 'col_out'] and set(re.findall(r'Pass::(\w+)', body)) == {
         'Word', 'Side', 'kBounded', 'kIdle', 'wants', 'join'}
     # the exports: one check for the five over a triangle, the rectangle keeps its own conditions; check_tri_tile's users are as they were
-    host = code['dctfp.hip']
+    host = code['dctfp_sim.hip']
     exports = ('dctfp_label_sums', 'dctfp_tri_degree', 'dctfp_tri_link_core', 'dctfp_tri_first_fp', 'dctfp_tri_tp_before')
     assert host.count('check_band_tile(') == 1 + len(exports) and 'static int check_band_tile(const char* name, const TriTile& t, int64_t n_nodes)' in host
     assert 'density_tile_ok' not in host and sum('check_band_tile(' in text for text in code.values()) == 1
@@ -476,7 +476,7 @@ def test_the_sad_tile_is_defined_once_in_a_header_every_user_includes():
     # the constants and the choice of a fill are the header's too
     for name in ('kSadTile = 128', 'kSadKC = 32', 'kSadLD = kSadKC + 4', 'int sad_tile_align(', 'uint64_t sad_keep_mask('):
         assert sum(name in text for text in code.values()) == 1 and name in code[tile]
-    for unit in ('k_cluster.hip', 'k_assign.hip', 'dctfp.hip'):
+    for unit in ('k_cluster.hip', 'k_assign.hip', 'dctfp_sim.hip'):
         text = code[os.path.join(csrc, unit)]
         assert 'sad_tile_align(a, lda, b, ldb)' in text and '& 15u) == 0 &&' not in text
 

@@ -363,7 +363,7 @@ def test_the_unit_touches_hist_through_agent_scope_atomics_alone():
     assert 'static_assert(kHistJobsPerBlock * kHistRows * kHistCols < ((int64_t)1 << 32)' in unit
     host = unit[unit.index('namespace dctfp_host'):]
     assert 'most * kHistJobsPerBlock / n_steps' in host and 'min(bands * n_steps, most)' in host
-    with open(os.path.join(csrc, 'dctfp.hip')) as fh:
+    with open(os.path.join(csrc, 'dctfp_sim.hip')) as fh:
         text = fh.read()
     body = text[text.index('\nint dctfp_tri_hist('):text.index('DCTFP_GUARD("dctfp_tri_hist")')]
     assert 'check_band_tile(' not in body and 'check_tri_tile(' not in body and 'ld < n_cols' in body and 'tri_hist_max_cap()' in body

@@ -1,7 +1,7 @@
 """AddressSanitizer over the HOST side of libdctfp.so, on this machine, without a GPU.
 
 GPU AddressSanitizer is not available on the pool, and a wrong index in a job table shows up on the GPU box as a fault
-(or as an abort without a message).  So the host code of dctdomain_amd/csrc/dctfp.hip is compiled on its own
+(or as an abort without a message).  So the host code of dctdomain_amd/csrc (dctfp.hip, dctfp_sim.hip and the launchers' units) is compiled on its own
 (`hipcc --cuda-host-only -fsanitize=address`), linked against a stand-in for the HIP runtime (tests/asan/hip_stub.cpp:
 device memory = host memory; a kernel launch walks the job tables the way the kernel's waves do and touches every address
 they would) and driven over a few hundred seeded random batches (tests/asan/driver.cpp): every shape class, option,

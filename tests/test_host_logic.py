@@ -29,6 +29,23 @@ def test_library_exports_every_declared_symbol():
     assert sorted(_lib.EXPORTS) == declared
 
 
+def test_the_two_host_units_share_one_context_and_define_every_export_once():
+    """dctfp_sim.hip is compiled once and linked into both libraries: neither it nor the header it shares with dctfp.hip may know the
+    switch that tells the two builds of dctfp.hip apart.  It carries device code, so the traffic stamp covers it."""
+    import build_ext
+    csrc = os.path.join(ROOT, 'dctdomain_amd', 'csrc')
+    text = {name: open(os.path.join(csrc, name)).read() for name in ('dctfp.hip', 'dctfp_sim.hip', 'dctfp_host.h')}
+    assert 'DCTFP_EXPERIMENTS' not in text['dctfp_host.h'] and 'DCTFP_EXPERIMENTS' not in text['dctfp_sim.hip']
+    assert 'dctfp_sim.hip' in build_ext.UNITS and 'dctfp_sim.hip' not in build_ext.TWIN_UNITS
+    assert os.path.join(csrc, 'dctfp_sim.hip') in build_ext.kernel_sources() and os.path.join(csrc, 'dctfp_host.h') in build_ext.HEADERS
+    public = [os.path.join(ROOT, 'include', name) for name in ('dctfp.h', 'dctfp_linkage.h')]
+    assert all(p in build_ext.HEADERS and p not in build_ext.kernel_sources() for p in public)
+    exports = sorted(set(name for p in public for name in re.findall(r'^int (dctfp_\w+)\(', open(p).read(), re.M)))
+    assert len(exports) >= 60
+    for name in exports:
+        assert text['dctfp.hip'].count('\nint %s(' % name) + text['dctfp_sim.hip'].count('\nint %s(' % name) == 1, name
+
+
 def test_struct_layouts_match_header():
     from dctdomain_amd import _lib
     assert ctypes.sizeof(_lib.Layer) == 40

@@ -227,7 +227,7 @@ def test_the_export_is_declared_bound_and_built():
     assert not re.search(r'\bwhile\b|for \(;;\)', code)
     with open(os.path.join(csrc, 'launch.h')) as fh:
         assert 'void launch_label_sums(' in fh.read()
-    with open(os.path.join(csrc, 'dctfp.hip')) as fh:
+    with open(os.path.join(csrc, 'dctfp_sim.hip')) as fh:
         host = fh.read()
     body = host[host.index('\nint dctfp_label_sums('):host.index('DCTFP_GUARD("dctfp_label_sums")')]
     assert 'check_tri_tile(' not in body and 'label_sums_max_cap()' in body

@@ -201,7 +201,7 @@ def test_new_unit_is_part_of_the_build_and_touches_the_arrays_through_atomics_on
     # s_row is cleared between two barriers and the flush stands behind a third
     sync = [m.start() for m in re.finditer(r'__syncthreads\(\);', kernel)]
     assert len(sync) == 3 and sync[0] < kernel.index('s_row[tid] = kNone32;') < sync[1] < kernel.index('for (int rl = 0;') < sync[2] < kernel.index('lower_hit(best_row + ')
-    host = open(os.path.join(csrc, 'dctfp.hip')).read()
+    host = open(os.path.join(csrc, 'dctfp_sim.hip')).read()
     body = host[host.index('\nint dctfp_rect_best('):host.index('DCTFP_GUARD("dctfp_rect_best")')]
     # (the two range checks in the form that cannot overflow: range_within(first, count, n) is count <= n && first <= n - count)
     for check in ('ld < n_cols', '!range_within(row0, n_rows, n_a)', '!range_within(col0, n_cols, n_b)', '0x7fffffff', 'rect_best_max_cap()',

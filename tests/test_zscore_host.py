@@ -256,7 +256,7 @@ def test_the_unit_touches_the_arrays_through_agent_scope_atomics_alone():
     # why the 32-bit sums cannot overflow is asserted where it is written, and the export holds the caller to it
     assert 'static_assert((int64_t)64 * kMomPer * (kMomMaxCap - 1) < ((int64_t)1 << 32)' in unit
     assert 'static_assert((int64_t)kMomRows * (kMomMaxCap - 1) < ((int64_t)1 << 32)' in unit
-    with open(os.path.join(csrc, 'dctfp.hip')) as fh:
+    with open(os.path.join(csrc, 'dctfp_sim.hip')) as fh:
         text = fh.read()
     body = text[text.index('\nint dctfp_rect_moments('):text.index('DCTFP_GUARD("dctfp_rect_moments")')]
     assert 'check_band_tile(' not in body and 'check_tri_tile(' not in body and 'ld < n_cols' in body and 'rect_moments_max_cap()' in body
