@@ -530,6 +530,8 @@ int dctfp_get_option(dctfp_ctx* ctx, const char* name, int64_t* value) try {
     else if (n == "last_walk_groups") *value = ctx->last_walk_groups;
     else if (n == "last_stage_a") *value = ctx->last_stage_a;
     else if (n == "last_stage_b") *value = ctx->last_stage_b;
+    else if (n == "last_walk") *value = ctx->last_walk;
+    else if (n == "last_gen") *value = ctx->last_gen;
     else if (n == "gen_fuse") *value = ctx->opt_gen_fuse;
     else if (n == "walk_launches") *value = ctx->walk_launches;
     else if (n == "last_knn_slices") *value = ctx->last_knn_slices;
@@ -1440,6 +1442,7 @@ int quantize_impl(dctfp_ctx* ctx, const dctfp_layer* layers, int32_t n_layers, i
         // (16 bytes per lane where every row of every sequence allows it)
         const Route route = choose_route(ctx, g, rows_aligned16(group, ng, n_data, src ? nullptr : seq_rows), dt.max_len, n_jobs, fg.n_groups > 0);
         ctx->last_stage_a = ctx->last_stage_b = 0;  // (run_two_kernels writes them)
+        ctx->last_walk = ctx->last_gen = 0;         // (... and launch_walk / launch_gen these)
 
         const TableLayout lay(n_jobs, ng, n_pieces, n_domains);
         TableLease tables(ctx->ring, stream);
@@ -1480,11 +1483,11 @@ int quantize_impl(dctfp_ctx* ctx, const dctfp_layer* layers, int32_t n_layers, i
             RC_TRY(get_st_plain(ctx, st, g.n_cols));
             const size_t lds_bytes = (size_t)route.gen_slots * gen_slot_bytes(n, m, route.gen_waves, route.gen_vec) + 64;
             GParams gp{d.joba, d.jobb, d.walks, route.gen_fuse, d.runs, d.pieces, st->fragp, out, g.n_cols, g.ld, m, route.gen_slots,
-                       ctx->degenerate, (unsigned)n_runs, (unsigned)route.gen_waves, lds_bytes, stream};
+                       ctx->degenerate, (unsigned)n_runs, (unsigned)route.gen_waves, lds_bytes, stream, &ctx->last_gen};
             RC_TRY(launch_one(ctx, stream, tables, [&](LaunchError* le) { return launch_gen(gp, g.dtype, route.gen_vec, n, le); }));
         } else if (route.kind == Route::kWalk) {
             WParams wp{d.joba, d.jobb, d.walks, d.runs, d.pieces, st->frag, out, g.n_cols, g.ld, m, ctx->degenerate, (unsigned)n_runs, stream,
-                       two_source};
+                       two_source, &ctx->last_walk};
             RC_TRY(launch_one(ctx, stream, tables, [&](LaunchError* le) { return launch_walk(wp, g.dtype, route.walk_s, route.fuse, le); }));
         } else {
             RC_TRY(run_two_kernels(ctx, g, route, tk, d, st, dt.max_len, out, stream, tables, ws, fork, tl_sync_call && l1 == n_layers));

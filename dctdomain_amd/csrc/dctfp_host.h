@@ -351,6 +351,8 @@ struct Context {   // (what a dctfp_ctx is: below)
     // ... or the two kernels: the builds of the last chunk's stage A and stage B as their launchers named them (launch.h:
     // stage_a_word and the stage-B words), 0 = another route
     int64_t last_stage_a = 0, last_stage_b = 0;
+    // ... and the one-launch kernels by name: the build their launcher instantiated (launch.h: walk_word / gen_word), 0 = another route
+    int64_t last_walk = 0, last_gen = 0;
     int64_t opt_gen_fuse = 1;    // "gen_fuse": fused walks through the general walk kernel (n <= 5); 0 = the two kernels, as through round 4
     int64_t walk_launches = 0;  // walk-kernel launches so far (a call split at a giant domain ends on the two-kernel path)
     int64_t last_knn_slices = 0;  // database slices that owned a column in the last dctfp_l1_knn launch

@@ -16,6 +16,7 @@ int launch_gen_ntc(const GParams& p, LaunchError* err) {
     }
     hipLaunchKernelGGL((walk_gen_kernel<T, N, VEC, FUSED, NTC>), dim3(p.grid), dim3(p.waves * 64), p.lds_bytes, p.stream, p.jobs, p.jobb, p.walks, p.runs,
                        p.pieces, p.stp, p.out, p.n_cols, p.ld, p.m, p.n_slots, inv, p.degenerate);
+    if (p.built) *p.built = gen_word<T, N, VEC, FUSED, NTC>(p.waves, p.n_slots);
     return DCTFP_OK;
 }
 

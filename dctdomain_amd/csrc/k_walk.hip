@@ -9,21 +9,27 @@ void launch_walk_impl(const WParams& p, bool fused) {
     static const InvTab<3> inv = make_inv<3>();
     if constexpr (sizeof(T) == 4 && NT == 5) {
         if (p.two_source) {  // pieces that are the mean of two windows' rows (dctfp_quantize_windows): builds of their own
-            if (fused)
+            if (fused) {
                 hipLaunchKernelGGL((walk_ab_kernel<T, S, 4, NT, 8, true, true>), dim3(p.grid), dim3(S * 64), 0, p.stream, p.jobs, p.jobb,
                                    p.walks, p.runs, p.pieces, p.stf, p.out, p.n_cols, p.ld, p.m, inv, p.degenerate);
-            else
+                if (p.built) *p.built = walk_word<T, S, NT, true, true>();
+            } else {
                 hipLaunchKernelGGL((walk_ab_kernel<T, S, 4, NT, 8, false, true>), dim3(p.grid), dim3(S * 64), 0, p.stream, p.jobs, p.jobb,
                                    p.walks, p.runs, p.pieces, p.stf, p.out, p.n_cols, p.ld, p.m, inv, p.degenerate);
+                if (p.built) *p.built = walk_word<T, S, NT, false, true>();
+            }
             return;
         }
     }
-    if (fused)
+    if (fused) {
         hipLaunchKernelGGL((walk_ab_kernel<T, S, 4, NT, 8, true>), dim3(p.grid), dim3(S * 64), 0, p.stream, p.jobs, p.jobb, p.walks,
                            p.runs, p.pieces, p.stf, p.out, p.n_cols, p.ld, p.m, inv, p.degenerate);
-    else
+        if (p.built) *p.built = walk_word<T, S, NT, true, false>();
+    } else {
         hipLaunchKernelGGL((walk_ab_kernel<T, S, 4, NT, 8, false>), dim3(p.grid), dim3(S * 64), 0, p.stream, p.jobs, p.jobb, p.walks,
                            p.runs, p.pieces, p.stf, p.out, p.n_cols, p.ld, p.m, inv, p.degenerate);
+        if (p.built) *p.built = walk_word<T, S, NT, false, false>();
+    }
 }
 
 // Instantiated shapes: S waves cover up to 256 S channels; G = 4 jobs per flush, the rows of an MFMA tile (a flush costs the

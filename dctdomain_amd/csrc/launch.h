@@ -77,6 +77,16 @@ constexpr int64_t kStageBMfma = 1, kStageBSlab = 2, kStageBSlabFromSplit = 3;  /
 constexpr int64_t kStageBPacked = 1 << 16, kStageBCombine = 1 << 17, kStageBCombinePacked = 1 << 18;  // ... and flags
 template <int NT, bool PACKED>
 constexpr int64_t stage_b_mfma_word() { return kStageBMfma | (int64_t)NT << 8 | (PACKED ? kStageBPacked : 0); }
+// ... and "last_walk" / "last_gen", the same for the two one-launch kernels (waves and slots: what the launch was given)
+template <typename T, int S, int NT, bool FUSED, bool WIN>
+constexpr int64_t walk_word() {
+    return storage_code<T>() | (int64_t)S << 8 | (int64_t)NT << 16 | (int64_t)((FUSED ? 1 : 0) | (WIN ? 2 : 0)) << 24;
+}
+template <typename T, int N, int VEC, bool FUSED, int NTC>
+constexpr int64_t gen_word(unsigned waves, int slots) {
+    return storage_code<T>() | (int64_t)N << 8 | (int64_t)VEC << 16 | (int64_t)NTC << 24 | (int64_t)(FUSED ? 1 : 0) << 32 |
+           (int64_t)(waves & 0xff) << 40 | (int64_t)(slots & 0xff) << 48;
+}
 
 struct AParams {
     const JobA* jobs;
@@ -111,6 +121,7 @@ struct WParams {
     unsigned grid;
     hipStream_t stream;
     bool two_source = false;  // some piece has PieceA::ptr2 (float32 rows, m <= 80 only)
+    int64_t* built = nullptr;  // the launcher's walk_word
 };
 
 // walk_gen_kernel: the shapes walk_ab_kernel does not take.
@@ -132,6 +143,7 @@ struct GParams {
     unsigned waves;
     size_t lds_bytes;
     hipStream_t stream;
+    int64_t* built = nullptr;  // the launcher's gen_word
 };
 
 constexpr size_t kGenLdsBudget = 150 * 1024;  // of the 160 KB of a CU

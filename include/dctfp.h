@@ -839,6 +839,15 @@ int dctfp_crash_handler(int enable);
  *                  kernel reading the row-split partial sums; byte 1 NT (16-column tiles of the MFMA build, 1 .. 8; 0 for
  *                  the slab forms); byte 2 flags: 1 = PACKED MFMA build, 2 = stage_a_combine_kernel ran before it,
  *                  4 = ... writing packed Y'.  0 as for "last_stage_a"
+ *   "last_walk"    read only: the walk-kernel build launched last (the last layer group of the last dctfp_quantize /
+ *                  dctfp_quantize_windows), written by its launcher from the template arguments of the instantiation; 0 = that
+ *                  group took another route.  Byte 0 storage type (as "last_stage_a"), byte 1 S (waves per workgroup: 3, 5,
+ *                  10), byte 2 NT (16-column groups: 5 or 6, what "last_walk_groups" reads), byte 3 flags: 1 = FUSED build,
+ *                  2 = WIN (a two-source build: rows that are the mean of two windows' rows)
+ *   "last_gen"     read only: ... and the general walk kernel's.  Byte 0 storage type, byte 1 N (kept rows), byte 2 VEC (channels
+ *                  per lane), byte 3 NTC (column groups of fragments per step: 4 for m <= 64, else 8), byte 4 flags: 1 = FUSED
+ *                  build (what "last_gen_fused" reads), byte 5 the waves per workgroup it was launched with, byte 6 its Y' slots
+ *                  in LDS (1 or 2).  0 as for "last_walk"
  *   "walk_launches" read only: walk-kernel launches of this context so far
  *   "last_knn_slices" read only: database slices that owned a column in the last dctfp_l1_knn launch (1: no merge kernels)
  *   "knn_calls"    read only: dctfp_l1_knn launches of this context so far

@@ -6,6 +6,7 @@ import pytest
 
 import golden_util as gu
 import stage_ladder as sl
+import walk_ladder as wl
 from oracle import dct_oracle as orc
 from recipes import make_input
 
@@ -605,7 +606,9 @@ def test_walk_kernel_widths_and_kept_columns_against_oracle(dd):
     """The walk kernel contracts stage B in even/odd halves over channel pairs (d, D-1-d) and column pairs (c, m-1-c):
     widths where D/2 is not a multiple of 4 (D % 8 == 4: two lanes hold the same four channels) or of 16 (zero-padded
     pair groups), odd m (the middle column is its own mirror) and every wave count (3, 5, 10), forced through the walk
-    kernel (path=2) with RecCut-shaped (fused) and plain domain lists, a NaN channel and a constant channel among them."""
+    kernel (path=2) with RecCut-shaped and plain domain lists, a NaN channel and a constant channel among them.  Eight jobs a
+    call: choose_route fuses walks from 64 jobs, so these are the PLAIN builds, asserted by name ("last_walk"); the FUSED builds
+    see these widths in tests/test_walk_ladder_gpu.py."""
     import torch
     rng = np.random.default_rng(20261004)
     ctx = dd.get_context(torch.cuda.current_device())
@@ -635,6 +638,7 @@ def test_walk_kernel_widths_and_kept_columns_against_oracle(dd):
             ctx.set_option('degenerate_channels', 0)
             out = dd.quantize_batch([dd.LayerBatch(ts, 3, m)], dd.PieceTable(lens, doms)).cpu().numpy()
             assert ctx.get_option('last_path') == 2
+            assert wl.decode_walk(ctx.get_option('last_walk')) == wl.expected_walk('f32', D, m, False), (D, m)
             row = 0
             for s in range(3):
                 for dom in doms[s]:
@@ -730,9 +734,12 @@ def test_midsize_calls_fused_walks_with_both_stage_b_forms(dd):
 def test_half_precision_fused_walks(dd, tdtype):
     """Multi-domain proteins in half precision in one call large enough to be fused (>= 64 jobs: the parts and the whole
     protein fed from the same rows; 4 channels per lane for half-precision rows): against the oracle on the same values
-    promoted to float32, and byte for byte against the unfused form."""
+    promoted to float32, and byte for byte against the unfused form.  About 100 jobs, fewer than the 256 the default "path"
+    wants for the walk kernel: this is the TWO-KERNEL path -- its fused stage-A build at 4 channels per lane and its plain one at
+    8, asserted by name ("last_stage_a"); the walk kernel's FUSED half-precision builds run in tests/test_walk_ladder_gpu.py."""
     import torch
     dt = getattr(torch, tdtype)
+    storage = {'float16': 'f16', 'bfloat16': 'bf16'}[tdtype]
     rng = np.random.default_rng(77)
     ctx = dd.get_context(torch.cuda.current_device())
     for D in (640, 1000):
@@ -748,9 +755,14 @@ def test_half_precision_fused_walks(dd, tdtype):
         assert 2 * table.n_domains >= 64
         lbs = [dd.LayerBatch([x[li] for x in xs], 3, 80) for li in range(2)]
         out = dd.quantize_batch(lbs, table).cpu().numpy()
+        a = sl.decode_stage_a(ctx.get_option('last_stage_a'))
+        assert ctx.get_option('last_path') == 1 and ctx.get_option('last_walk') == 0
+        assert (a.storage, a.n, a.vec, a.fused) == (storage, 3, 4, True), (D, a)
         ctx.set_option('fuse', 0)
         try:
             assert (dd.quantize_batch(lbs, table).cpu().numpy() == out).all()
+            a = sl.decode_stage_a(ctx.get_option('last_stage_a'))
+            assert ctx.get_option('last_path') == 1 and (a.storage, a.n, a.vec, a.fused) == (storage, 3, 8, False), (D, a)
         finally:
             ctx.set_option('fuse', 1)
         row = 0
@@ -766,10 +778,12 @@ def test_half_precision_fused_walks(dd, tdtype):
 @pytest.mark.parametrize('tdtype', ['float16', 'bfloat16'])
 def test_walk_kernel_on_half_precision_rows(dd, tdtype):
     """The walk kernel reads float16 / bfloat16 rows as 8 bytes per lane (4 channels, like float32): forced (path=2) on
-    small batches of whole proteins and of fused multi-domain proteins at the three wave counts, against the oracle on the
-    same values promoted to float32."""
+    small batches of whole proteins and of multi-domain proteins at the three wave counts, against the oracle on the same
+    values promoted to float32.  Nine jobs a call, fewer than the 64 choose_route fuses walks from: the PLAIN builds, asserted by
+    name ("last_walk"); the FUSED ones run in tests/test_walk_ladder_gpu.py."""
     import torch
     dt = getattr(torch, tdtype)
+    storage = {'float16': 'f16', 'bfloat16': 'bf16'}[tdtype]
     rng = np.random.default_rng(515)
     ctx = dd.get_context(torch.cuda.current_device())
     try:
@@ -787,6 +801,7 @@ def test_walk_kernel_on_half_precision_rows(dd, tdtype):
                 xs.append(torch.from_numpy(make_input('esm', L, D, 61_000 + 10 * s + D)).to(dt).cuda())
             out = dd.quantize_batch([dd.LayerBatch(xs, 3, m)], dd.PieceTable(lens, doms)).cpu().numpy()
             assert ctx.get_option('last_path') == 2, (D, m)
+            assert wl.decode_walk(ctx.get_option('last_walk')) == wl.expected_walk(storage, D, m, False), (D, m)
             row = 0
             for s in range(5):
                 x = xs[s].float().cpu().numpy()

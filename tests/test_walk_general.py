@@ -5,14 +5,16 @@ sizes other than 3 x 65..80 (PROST's [5, 44] / [3, 85], anything n = 2..8, m <= 
 * the reference's golden cases `qdim_*` and `contact_layer_*` (and every other golden the kernel is eligible for) with the
   walk path forced on a one-protein call, `last_path == 2` asserted;
 * batches large enough for the default dispatch (>= 256 jobs), `last_path == 2` asserted, bit-exact against the oracle:
-  PROST's shapes, n = 2 .. 8, unaligned widths (one channel per lane), float64 rows (through `walk_ab_kernel<double>` at the
-  reference's [3, 80], through the general kernel otherwise), multi-domain lists (parts + whole protein, discontinuous).
+  PROST's shapes, n = 2 .. 8, unaligned widths (one channel per lane), float64 rows (the general kernel at every kept size, the
+  reference's [3, 80] included: `walk_shape` refuses float64 -- the build is asserted by name, "last_gen"), multi-domain lists
+  (parts + whole protein, discontinuous).
 """
 
 import numpy as np
 import pytest
 
 import golden_util as gu
+import walk_ladder as wl
 from oracle import dct_oracle as orc
 from recipes import make_input
 
@@ -125,7 +127,7 @@ SHAPES = [  # (id, qdim of the two layers, D, storage, min rows)
     ('prost_5x44_D2560', [5, 44, 5, 44], 2560, np.float32, 12),            # ten waves, one slot
     ('contact_like_5x44_D257', [5, 44, 5, 44], 257, np.float32, 12),       # odd width: one channel per lane
     ('3x80_D200', [3, 80, 3, 80], 200, np.float32, 12),                    # the reference's qdim below the tuned kernel's widths
-    ('f64_rows_3x80_D1280', [3, 80, 3, 80], 1280, np.float64, 12),         # walk_ab_kernel<double>
+    ('f64_rows_3x80_D1280', [3, 80, 3, 80], 1280, np.float64, 12),         # walk_gen_kernel<double, 3, 2>: ten waves, two slots
     ('f64_rows_5x44_D640', [5, 44, 5, 44], 640, np.float64, 12),
     ('mixed_5x44_then_3x80_D640', [5, 44, 3, 80], 640, np.float32, 12),    # two layer groups: general, then tuned
     # round 5: 80 < m <= 96 through walk_ab_kernel's builds with six column groups ([E | O] halves of 48 slots)
@@ -153,6 +155,10 @@ def test_general_shapes_in_batches_default_dispatch(dd, name, qdim, D, dtype, lo
     launches = ctx.get_option('walk_launches')
     out_whole = dd.quantize_batch(lbs, whole, ctx=ctx).cpu().numpy()
     assert ctx.get_option('last_path') == 2, name
+    f64_rows = dtype == np.float64             # float64 rows: the general kernel, whatever the kept sizes -- by name
+    if f64_rows:
+        assert ctx.get_option('last_walk') == 0, name
+        assert wl.decode_gen(ctx.get_option('last_gen')) == wl.expected_gen('f64', True, qdim[2], qdim[3], D, False), name
     assert ctx.get_option('walk_launches') - launches == (1 if one_group else 2), name
     # (b) parts + whole protein, discontinuous parts: the general kernel when asked for (by default the two kernels take such a
     # batch: their stage A reads the rows of a protein once for all of its domains)
@@ -166,11 +172,15 @@ def test_general_shapes_in_batches_default_dispatch(dd, name, qdim, D, dtype, lo
         assert ctx.get_option('last_path') == 2, name
         assert ctx.get_option('last_gen_fused') == expect_fused, name
         assert ctx.get_option('last_walk_groups') == ((6 if m_last > 80 else 5) if tuned_last else 0), name
+        if f64_rows:
+            assert wl.decode_gen(ctx.get_option('last_gen')) == wl.expected_gen('f64', True, n_last, m_last, D, True), name
         if expect_fused:                      # ... and every job on its own when asked to: the same bytes
             ctx.set_option('gen_fuse', 0)
             try:
                 unfused = dd.quantize_batch(lbs, table, ctx=ctx).cpu().numpy()
                 assert ctx.get_option('last_path') == 2 and ctx.get_option('last_gen_fused') == 0
+                if f64_rows:
+                    assert wl.decode_gen(ctx.get_option('last_gen')) == wl.expected_gen('f64', True, n_last, m_last, D, False), name
             finally:
                 ctx.set_option('gen_fuse', 1)
             np.testing.assert_array_equal(out, unfused, err_msg=f'{name}: fused vs unfused general kernel')

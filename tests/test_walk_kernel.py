@@ -5,14 +5,15 @@ dispatch a user gets: calls of >= 256 jobs.  Three things the one-protein golden
   first-row load, the tail groups and a partially filled flush, plain and fused (parts of 3 .. 7 rows + whole protein);
 * the BASELINE config 2 shape (L = 500, D = 1280, 2 layers) and the config 3 shape (ragged L in [50, 2000]) as batches
   large enough for the default dispatch, with the reference's golden cases placed inside the batch;
-* that the kernel that ran IS the walk kernel (`last_path == 2`), so a dispatch regression cannot silently move these
-  tests to the two-kernel path.
+* that the kernel that ran IS the walk kernel (`last_path == 2`) and which of its builds ("last_walk", decoded by
+  tests/walk_ladder.py), so a dispatch regression cannot silently move these tests to the two-kernel path or to another build.
 """
 
 import numpy as np
 import pytest
 
 import golden_util as gu
+import walk_ladder as wl
 from oracle import dct_oracle as orc
 from recipes import make_input
 
@@ -115,11 +116,14 @@ def test_short_jobs_through_the_walk_kernel(dd, D, storage):
     lbs = [dd.LayerBatch(dev[k], 3, 80) for k in range(2)]
     ctx = dd.get_context(torch.cuda.current_device())
     outs = {}
+    short = {'float32': 'f32', 'float16': 'f16'}[storage]
     for name, opts in (('default', {}), ('forced', dict(path=2)), ('forced_unfused', dict(path=2, fuse=0)),
                        ('two_kernels', dict(path=1))):
         with _Options(ctx, **opts):
             outs[name] = dd.quantize_batch(lbs, table).cpu().numpy()
             assert ctx.get_option('last_path') == (1 if name == 'two_kernels' else 2), name
+            build = None if name == 'two_kernels' else wl.expected_walk(short, D, 80, name != 'forced_unfused')
+            assert wl.decode_walk(ctx.get_option('last_walk')) == build, name
     row = 0
     for s, L in enumerate(lens):
         q = orc.quantize([seen[0][s], seen[1][s]], doms[s], [3, 80, 3, 80])
@@ -195,6 +199,7 @@ def test_config2_shape_batch_default_dispatch_with_goldens_inside(dd):
     table = dd.PieceTable.whole_sequences(lens)
     out = dd.quantize_batch(lbs, table).cpu().numpy()
     assert ctx.get_option('last_path') == 2
+    assert wl.decode_walk(ctx.get_option('last_walk')) == wl.WalkBuild('f32', 5, 5, False, False)      # whole proteins: plain
     _check_goldens(out, table, placed)
     _check_oracle(out, table, layers, offs, lens, doms, (2, 100, 286, 288, 574))
     with _Options(ctx, path=1):
@@ -210,6 +215,7 @@ def test_config2_shape_batch_default_dispatch_with_goldens_inside(dd):
     table2 = dd.PieceTable(lens, doms)
     out2 = dd.quantize_batch(lbs, table2).cpu().numpy()
     assert ctx.get_option('last_path') == 2
+    assert wl.decode_walk(ctx.get_option('last_walk')) == wl.WalkBuild('f32', 5, 5, True, False)       # three proteins in parts: fused
     _check_goldens(out2, table2, {**placed, **multi})
     _check_oracle(out2, table2, layers, offs, lens, doms, (4, 6, 299, 301))
 
@@ -231,6 +237,7 @@ def test_config3_shape_ragged_batch_default_dispatch_with_goldens_inside(dd):
     table = dd.PieceTable.whole_sequences(lens)
     out = dd.quantize_batch([dd.LayerBatch(x, 3, 80, row_offsets=offs) for x in layers], table).cpu().numpy()
     assert ctx.get_option('last_path') == 2
+    assert wl.decode_walk(ctx.get_option('last_walk')) == wl.WalkBuild('f32', 5, 5, False, False)
     _check_goldens(out, table, placed)
     doms = [[f'1-{L}'] for L in lens]
     shortest, longest = int(np.argmin(lens)), int(np.argmax(lens))
@@ -258,6 +265,7 @@ def test_one_giant_domain_does_not_take_the_call_off_the_walk_kernel(dd):
     out = dd.quantize_batch(lbs, table).cpu().numpy()
     assert ctx.get_option('walk_launches') == before + 1      # the 300-odd ordinary domains: one walk-kernel launch
     assert ctx.get_option('last_path') == 1                   # ... the two giants after them: two-kernel path
+    assert ctx.get_option('last_walk') == 0 and ctx.get_option('last_stage_a') != 0
     with _Options(ctx, path=1):
         ref = dd.quantize_batch(lbs, table).cpu().numpy()
     np.testing.assert_array_equal(out, ref)
@@ -314,6 +322,7 @@ def test_first_row_shift_walk_matches_two_kernels(dd, D):
             xctx.set_option('degenerate_channels', 0)
             out = dd.quantize_batch(lbs, table, ctx=xctx).cpu().numpy()
             assert xctx.get_option('last_path') == path
+            assert wl.decode_walk(xctx.get_option('last_walk')) == (wl.expected_walk('f32', D, 80, True) if path == 2 else None)
             got[path] = (out, xctx.get_option('degenerate_channels'))
     assert got[2][1] > 0 and got[1][1] == got[2][1], (got[2][1], got[1][1])      # the same channels were found constant
     np.testing.assert_array_equal(got[1][0], got[2][0])
