@@ -40,11 +40,11 @@ EXPERIMENTS_LIB_PATH = os.path.join(PKG_DIR, 'libdctfp_experiments.so')
 #: dctfp_sim.hip: the stateless dct-sim / query_db exports), and one unit per kernel family so that the device code compiles
 #: side by side (the stage-A instantiations alone are a third of it).  `twin` = units that differ in libdctfp_experiments.so
 #: (-DDCTFP_EXPERIMENTS: option names); the others are compiled once and linked into both libraries.
-UNITS = ['dctfp.hip', 'dctfp_sim.hip', 'k_walk.hip', 'k_gen.hip', 'k_reccut.hip', 'k_search.hip', 'k_protein.hip', 'k_query.hip', 'k_filter.hip', 'k_cluster.hip', 'k_greedy.hip', 'k_assign.hip', 'k_tree.hip', 'k_linkage.hip', 'k_best.hip', 'k_medoid.hip', 'k_density.hip', 'k_auc.hip', 'k_hist.hip', 'k_moments.hip', 'k_map.hip', 'k_stage_b.hip',
+UNITS = ['dctfp.hip', 'dctfp_sim.hip', 'k_walk.hip', 'k_gen.hip', 'k_reccut.hip', 'k_search.hip', 'k_protein.hip', 'k_query.hip', 'k_filter.hip', 'k_cluster.hip', 'k_greedy.hip', 'k_assign.hip', 'k_tree.hip', 'k_linkage.hip', 'k_best.hip', 'k_medoid.hip', 'k_density.hip', 'k_auc.hip', 'k_hist.hip', 'k_moments.hip', 'k_silhouette.hip', 'k_map.hip', 'k_stage_b.hip',
          'k_stage_a_f32.hip', 'k_stage_a_f64.hip', 'k_stage_a_f16.hip', 'k_stage_a_bf16.hip']
 TWIN_UNITS = ('dctfp.hip',)
 HEADERS = [os.path.join(CSRC, 'kernels.hip.h'), os.path.join(CSRC, 'launch.h'), os.path.join(ROOT, 'include', 'dctfp.h'),
-           os.path.join(ROOT, 'include', 'dctfp_linkage.h'), os.path.join(CSRC, 'dctfp_host.h'),
+           os.path.join(ROOT, 'include', 'dctfp_linkage.h'), os.path.join(ROOT, 'include', 'dctfp_silhouette.h'), os.path.join(CSRC, 'dctfp_host.h'),
            os.path.join(CSRC, 'reccut_kernel.hip.h'), os.path.join(CSRC, 'k_stage_a.inc'), os.path.join(CSRC, 'tri_walk.hip.h'), os.path.join(CSRC, 'sad_tile.hip.h'),
            os.path.join(CSRC, 'tri_tile.hip.h'), os.path.join(CSRC, 'band_walk.hip.h'), os.path.join(CSRC, 'union_find.hip.h')]
 OBJ_DIR = os.path.join(ROOT, 'build', 'dctfp_objs')
@@ -52,7 +52,7 @@ OBJ_DIR = os.path.join(ROOT, 'build', 'dctfp_objs')
 
 def kernel_sources():
     """Every file the device code and its dispatch come from (what a PMC traffic measurement is stamped with)."""
-    return [os.path.join(CSRC, u) for u in UNITS] + HEADERS[:2] + HEADERS[4:]   # (not the two public headers of include/)
+    return [os.path.join(CSRC, u) for u in UNITS] + HEADERS[:2] + HEADERS[5:]   # (not the three public headers of include/)
 
 
 def sha256_of(path: str) -> str:

@@ -1,4 +1,5 @@
-"""ctypes binding of libdctfp.so; its signatures and constants are read from include/dctfp.h and include/dctfp_linkage.h.
+"""ctypes binding of libdctfp.so; its signatures and constants are read from include/dctfp.h, include/dctfp_linkage.h and
+include/dctfp_silhouette.h.
 No fallback: if the HIP library is missing or no MI355X is visible, everything here raises."""
 
 from __future__ import annotations
@@ -76,13 +77,16 @@ def parse_header(path):
 
 _SIGNATURES, _defines = parse_header(os.path.join(INCLUDE_DIR, 'dctfp.h'))
 _LINKAGE_SIGNATURES, _linkage_defines = parse_header(os.path.join(INCLUDE_DIR, 'dctfp_linkage.h'))
+_SILHOUETTE_SIGNATURES, _silhouette_defines = parse_header(os.path.join(INCLUDE_DIR, 'dctfp_silhouette.h'))
 #: the names include/dctfp.h declares, in its order
 EXPORTS = tuple(_SIGNATURES)
 #: the exports of include/dctfp_linkage.h (dct-sim --hac), which counts its own version
 LINKAGE_EXPORTS = tuple(_LINKAGE_SIGNATURES)
-#: DCTFP_OK, DCTFP_ERR_INVALID .. DCTFP_ERR_UNSUPPORTED, DCTFP_MAX_N, DCTFP_MAX_M, DCTFP_F32 .. DCTFP_BF16, DCTFP_VERSION and
-#: DCTFP_LINKAGE_VERSION: every integer ``#define`` of the two headers, under its own name
-globals().update(_defines, **_linkage_defines)
+#: the exports of include/dctfp_silhouette.h (python -m dctdomain_amd.cluster_quality), which counts its own version too
+SILHOUETTE_EXPORTS = tuple(_SILHOUETTE_SIGNATURES)
+#: DCTFP_OK, DCTFP_ERR_INVALID .. DCTFP_ERR_UNSUPPORTED, DCTFP_MAX_N, DCTFP_MAX_M, DCTFP_F32 .. DCTFP_BF16, DCTFP_VERSION,
+#: DCTFP_LINKAGE_VERSION and DCTFP_SILHOUETTE_VERSION: every integer ``#define`` of the three headers, under its own name
+globals().update(_defines, **_linkage_defines, **_silhouette_defines)
 LINKAGE_MAX_N = 46340                          # dctfp_linkage_*'s limit on n (floor(sqrt(2^31)))
 
 #: what the five exports that scan an L1 tile of the triangle (and dctfp_rect_best and dctfp_label_sums, on a rectangle) start with: the context, then the library's TriTile (tile, n_rows, n_cols, ld, row0, col0,
@@ -161,12 +165,14 @@ def runtime_report(lib=None) -> str:
 
 
 def _configure(lib):
-    """Declares the argument / result types of every export of include/dctfp.h and include/dctfp_linkage.h."""
-    missing = [fn for fn in LINKAGE_EXPORTS if not hasattr(lib, fn)]
-    if missing:
-        raise ImportError(f'{getattr(lib, "_name", "libdctfp.so")} lacks {", ".join(missing)} (include/dctfp_linkage.h): it was built from '
-                          f'an older tree -- rebuild it (python build_ext.py)')
-    for name, (restype, argtypes) in {**_SIGNATURES, **_LINKAGE_SIGNATURES}.items():
+    """Declares the argument / result types of every export of include/dctfp.h, include/dctfp_linkage.h and
+    include/dctfp_silhouette.h."""
+    for header, names in (('dctfp_linkage.h', LINKAGE_EXPORTS), ('dctfp_silhouette.h', SILHOUETTE_EXPORTS)):
+        missing = [fn for fn in names if not hasattr(lib, fn)]
+        if missing:
+            raise ImportError(f'{getattr(lib, "_name", "libdctfp.so")} lacks {", ".join(missing)} (include/{header}): it was built from '
+                              f'an older tree -- rebuild it (python build_ext.py)')
+    for name, (restype, argtypes) in {**_SIGNATURES, **_LINKAGE_SIGNATURES, **_SILHOUETTE_SIGNATURES}.items():
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = restype, list(argtypes)
     return lib

@@ -1,10 +1,12 @@
-// libdctfp.so -- the stateless exports of include/dctfp.h behind dct-sim and query_db, and include/dctfp_linkage.h.
+// libdctfp.so -- the stateless exports of include/dctfp.h behind dct-sim and query_db, include/dctfp_linkage.h and
+// include/dctfp_silhouette.h.
 // Each checks its arguments, takes the context's mutex and makes the launches of one kernel family.  Of the context they read
 // mu, device, n_cu, scratch and the options l1_kernel / row_select, and dctfp_l1_knn writes last_knn_slices / knn_calls.
 // Built once and linked into both libraries (not in build_ext.TWIN_UNITS): see dctfp_host.h.
 #define DCTFP_TEMPLATES_ONLY   // (the plain kernels of kernels.hip.h are defined in dctfp.hip; the three launched here: below)
 #include "dctfp.h"
 #include "dctfp_linkage.h"
+#include "dctfp_silhouette.h"
 
 #include "dctfp_host.h"
 #include "tri_tile.hip.h"   // (TriTile; the kernels that scan one include tri_walk.hip.h or band_walk.hip.h)
@@ -666,6 +668,45 @@ int dctfp_rect_moments(dctfp_ctx* ctx, const int32_t* tile, int64_t n_rows, int6
                             (hipStream_t)stream_v);
     });
 } DCTFP_GUARD("dctfp_rect_moments")
+
+// python -m dctdomain_amd.cluster_quality (k_silhouette.hip; include/dctfp_silhouette.h)
+int dctfp_silhouette_version(void) { return DCTFP_SILHOUETTE_VERSION; }
+
+int dctfp_silhouette_rows(dctfp_ctx* ctx, const int32_t* tile, int64_t n_rows, int64_t n_cols, int64_t ld, int64_t row0, int64_t col0,
+                          const uint8_t* row_empty, const uint8_t* col_empty, int32_t cap, const int32_t* cid, const int32_t* size,
+                          const int32_t* first, int64_t n_clusters, int32_t pass_clusters, uint64_t* own_sum, uint64_t* near_sum,
+                          int32_t* near_size, int32_t* near_first, int64_t n_nodes, void* stream_v) try {
+    static_assert(DCTFP_SILHOUETTE_MAX_CAP == 1 << 22 && DCTFP_SILHOUETTE_MAX_PASS_CLUSTERS == 4096, "the header states the kernel's limits");
+    // the limits first: they hold whatever else is passed
+    if (cap > silhouette_max_cap())
+        return fail(DCTFP_ERR_LIMIT, "dctfp_silhouette_rows: a cap above %d does not keep a sum below 2^53", silhouette_max_cap());
+    if (pass_clusters > silhouette_max_pass())
+        return fail(DCTFP_ERR_LIMIT, "dctfp_silhouette_rows: more than %d clusters to a pass do not fit the LDS of a workgroup", silhouette_max_pass());
+    if (n_nodes > 0x7fffffff) return fail(DCTFP_ERR_LIMIT, "dctfp_silhouette_rows: n_nodes must lie in 0 .. 2^31 - 1");
+    if (!ctx || !tile || !cid || !own_sum || !near_sum || !near_size || !near_first)
+        return fail(DCTFP_ERR_INVALID, "dctfp_silhouette_rows: NULL argument");
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    // (a full row per workgroup and four words per protein: its own few conditions)
+    if (n_rows < 0 || n_cols < 0 || ld < n_cols || row0 < 0 || col0 < 0 || cap < 0 || n_nodes < 0)
+        return fail(DCTFP_ERR_INVALID, "dctfp_silhouette_rows: bad shape or cap");
+    if (pass_clusters < 1) return fail(DCTFP_ERR_INVALID, "dctfp_silhouette_rows: pass_clusters must lie in 1 .. %d", silhouette_max_pass());
+    if (n_clusters < 0 || n_clusters > n_nodes / 2)
+        return fail(DCTFP_ERR_INVALID, "dctfp_silhouette_rows: %lld clusters of two or more members among %lld proteins", (long long)n_clusters, (long long)n_nodes);
+    if (n_clusters > 0 && (!size || !first)) return fail(DCTFP_ERR_INVALID, "dctfp_silhouette_rows: NULL size or first with clusters to read");
+    if (((reinterpret_cast<uintptr_t>(tile) | reinterpret_cast<uintptr_t>(cid) | reinterpret_cast<uintptr_t>(size) | reinterpret_cast<uintptr_t>(first) |
+          reinterpret_cast<uintptr_t>(near_size) | reinterpret_cast<uintptr_t>(near_first)) & 3u) != 0 ||
+        ((reinterpret_cast<uintptr_t>(own_sum) | reinterpret_cast<uintptr_t>(near_sum)) & 7u) != 0)
+        return fail(DCTFP_ERR_INVALID, "dctfp_silhouette_rows: the tile or an int32 array is not 4-byte aligned or own_sum / near_sum not 8-byte aligned");
+    // (every index the kernel can form lies inside the tile and the arrays of n_nodes entries: bounded here, on the host, and not on
+    // the device -- but for cid's values, which the caller vouches for: include/dctfp_silhouette.h)
+    if (!range_within(row0, n_rows, n_nodes) || !range_within(col0, n_cols, n_nodes))
+        return fail(DCTFP_ERR_INVALID, "dctfp_silhouette_rows: the tile names proteins outside the arrays of n_nodes entries");
+    if (n_rows == 0 || n_cols == 0) return DCTFP_OK;
+    return on_device(ctx, [&] {
+        launch_silhouette_rows(TriTile{tile, n_rows, n_cols, ld, row0, col0, row_empty, col_empty, cap, cap}, cid, size, first,
+                               (int32_t)n_clusters, pass_clusters, own_sum, near_sum, near_size, near_first, (hipStream_t)stream_v);
+    });
+} DCTFP_GUARD("dctfp_silhouette_rows")
 
 int dctfp_greedy_decide(dctfp_ctx* ctx, int32_t* assign, int32_t* state, const int32_t* blocked, int64_t n_nodes, int64_t i0, int64_t i1,
                         int32_t round, int64_t* undecided, void* stream_v) try {

@@ -278,6 +278,17 @@ int launch_tri_hist(const TriTile& t, const int32_t* fam, uint64_t* hist, hipStr
 int rect_moments_max_cap();
 void launch_rect_moments(const TriTile& t, uint64_t* row_mom, int64_t n_a, uint64_t* col_mom, int64_t n_b, hipStream_t stream);
 
+// the sums behind the silhouette of a clustering (k_silhouette.hip; include/dctfp_silhouette.h has the rule): one workgroup per row of
+// the full square of an int32 L1 tile of one file -- the key of every column j != i (the tile scans' rule, without a bound) goes to
+// the 64-bit LDS sum of j's cluster, pass_clusters cluster ids at a time, a singleton column into a running minimum; per row the sum
+// over its own cluster and the other cluster of the smallest mean (sum, size, first member), compared as exact fractions.  No global
+// atomics.  silhouette_max_cap = the largest cap whose sums stay below 2^53, silhouette_max_pass = the most sums the LDS of a pass holds
+int silhouette_max_cap();
+int silhouette_max_pass();
+void launch_silhouette_rows(const TriTile& t, const int32_t* cid, const int32_t* size, const int32_t* first, int32_t n_clusters,
+                            int32_t pass_clusters, uint64_t* own_sum, uint64_t* near_sum, int32_t* near_size, int32_t* near_first,
+                            hipStream_t stream);
+
 // (dctfp_rows_assign, k_assign.hip: the same contraction over a full rectangle -- every pair of rows within the bound lowers
 // assign[slot of the b row] to the value of the a row with an atomic minimum; value_a / slot_b NULL: a0 + r / b0 + c)
 void launch_rows_assign(const int8_t* a, int64_t na, int64_t lda, const int32_t* value_a, int64_t a0, const int8_t* b, int64_t nb, int64_t ldb,

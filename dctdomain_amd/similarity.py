@@ -793,6 +793,39 @@ def rect_moments(tile: torch.Tensor, row0: int, col0: int, state: MomentState, r
         _launch(tile.device, 'dctfp_rect_moments', *lead, _ptr(state.row), n_a, _ptr(state.col), n_b)
 
 
+SILHOUETTE_PASS_CLUSTERS = _lib.DCTFP_SILHOUETTE_MAX_PASS_CLUSTERS     # cluster sums in the LDS of a workgroup at a time: the default
+
+
+def silhouette_rows(tile: torch.Tensor, row0: int, col0: int, cid: torch.Tensor, size: torch.Tensor, first: torch.Tensor,
+                    own_sum: torch.Tensor, near_sum: torch.Tensor, near_size: torch.Tensor, near_first: torch.Tensor, row_empty=None,
+                    col_empty=None, cap: int = 17000, pass_clusters: int = SILHOUETTE_PASS_CLUSTERS):
+    """The sums behind the silhouette of the rows of an L1 tile of ONE file (``dctfp_silhouette_rows``; include/dctfp_silhouette.h
+    has the rule): entry (r, c) = proteins row0 + r and col0 + c, the columns being the whole file.  ``cid`` (device int32, one per
+    protein): the dense id of the protein's cluster if that has two or more members, -1 for a singleton; ``size`` / ``first``
+    (device int32, one per id): the members of every such cluster and the first of them.  For every row i = row0 + r, with key =
+    min(L1, cap) -- ``cap`` for a row / column flagged empty -- over the columns j != i: ``own_sum[i]`` = the summed key over i's own
+    cluster, and (``near_sum[i]``, ``near_size[i]``, ``near_first[i]``) = (sum, members, first member) of the other cluster with the
+    smallest mean key, an exact comparison with ties to the lower first member; (0, 0, -1) where there is no other cluster.  The
+    sums are device int64 (the library's uint64; they stay below 2^53), one entry per protein like the two int32 arrays; only the
+    entries of the tile's rows are written.  ``pass_clusters``: the cluster sums a workgroup keeps at a time (the row is read once
+    per that many clusters; the results do not depend on it).  The library cannot check ``cid`` against the arrays it indexes:
+    that is done here, on the host, at one small device reduction per call."""
+    dev = tile.device
+    n_nodes = _vector(cid, torch.int32, dev, 'cid (one entry per protein)')
+    n_clusters = _vector(size, torch.int32, dev, 'size (one entry per cluster)')
+    _vector(first, torch.int32, dev, 'first (one entry per cluster)', n_clusters)
+    for t, dtype, what in ((own_sum, torch.int64, 'own_sum'), (near_sum, torch.int64, 'near_sum'), (near_size, torch.int32, 'near_size'),
+                           (near_first, torch.int32, 'near_first')):
+        _vector(t, dtype, dev, f'{what} (one entry per protein)', n_nodes)
+    n_rows, n_cols, lead, _flags = _tri_filter_args(tile, row0, col0, cap, row_empty, col_empty, cap, n_nodes)
+    if n_nodes and not -1 <= int(cid.min()) <= int(cid.max()) < n_clusters:
+        raise IndexError('a cluster id outside -1 .. the number of clusters - 1')
+    if n_rows and n_cols:
+        _launch(dev, 'dctfp_silhouette_rows', *lead[:-1], cid.data_ptr(), _ptr(size if n_clusters else None),
+                _ptr(first if n_clusters else None), n_clusters, int(pass_clusters), own_sum.data_ptr(), near_sum.data_ptr(),
+                near_size.data_ptr(), near_first.data_ptr(), n_nodes)
+
+
 def _node_arrays(tile: torch.Tensor, arrays) -> int:
     """n_nodes of the per-protein arrays beside a tile -- ``arrays`` = (tensor, dtype, name): contiguous 1-D device tensors of one
     length on the tile's device."""
